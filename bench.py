@@ -12,15 +12,17 @@ One "step" = one pass of the hot path over one synthetic registration problem, a
 `value` = surface points x model points (all ranks) x steps / wall time: end-to-end Gpairs/s including the filters
 and RANSAC; 1000 / ms_per_step is registrations/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model-points M_TOTAL] [--surface-points Q]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model-points M_TOTAL] [--surface-points Q] [--dump-outputs DIR] [--full]
 
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR also writes what the
+last timed step returned (matched pairs, their coordinates, the RANSAC transform, inliers and counts) as DIR/<name>.npy.
 N > 1 (launched by torch.distributed.run, one rank per GPU) is STRONG scaling: the model has --model-points rows in
-TOTAL (default 1M, the metric's) and is sharded by rows, M_TOTAL / N per GPU.  The same line then also carries, as
+TOTAL (default 1M, the metric's) and is sharded by rows, M_TOTAL / N per GPU.  With --full the same line also carries, as
 extra objects, cfg 3's fixed 2M-point model sharded N ways (`cfg3_model_2M`) and the weak-scaling run with 1M rows
-per GPU (`weak_1M_per_gpu`), and cfg 5's crop batch dealt over the ranks (`cfg5_batch`).  At N = 1 the line also
-carries the other BASELINE configs at their real sizes, each with its own ms / roofline / cpu_baseline
-(`extras`: getMatches D = 981 at cfg 2, descriptors at cfg 4, AlignPoints_KNN batched, RANSAC alone at cfg 1).
-Nothing here imports oracle/ on the GPU path: the oracle is only the `cpu_baseline` leg.
+per GPU (`weak_1M_per_gpu`), and cfg 5's crop batch dealt over the ranks (`cfg5_batch`).  At N = 1, --full also adds
+the CPU baseline, the two-in-flight comparison and the other BASELINE configs at their real sizes, each with its own
+ms / roofline / cpu_baseline (`extras`: getMatches D = 981 at cfg 2, descriptors at cfg 4, AlignPoints_KNN batched,
+RANSAC alone at cfg 1).  Nothing here imports oracle/ on the GPU path: the oracle is only the `cpu_baseline` leg.
 """
 from __future__ import annotations
 
@@ -171,10 +173,11 @@ class Ctx:
 
 
 def run_registration(ctx: Ctx, M_total: int, Q: int, steps: int, warmup: int, time_kernel: bool, in_flight: int = 1,
-                     coef: dict | None = None) -> dict:
+                     coef: dict | None = None, keep_outputs: bool = False) -> dict:
     """The step described in the module docstring on a model of M_total rows sharded over ctx.world ranks.  in_flight > 1: that many
     registrations in flight per rank (pcreg_amd/pipelined.py: one lane = one HIP stream + its own buffers, surfaces dealt round-robin;
-    every lane issues its collectives in host program order, the same on every rank)."""
+    every lane issues its collectives in host program order, the same on every rank).  keep_outputs: the result also carries
+    `_outputs`, what the LAST timed step handed its caller (step_outputs)."""
     import torch
     import torch.distributed as dist
     from pcreg_amd.device import PreparedModel, RegistrationPipeline, soa
@@ -203,9 +206,10 @@ def run_registration(ctx: Ctx, M_total: int, Q: int, steps: int, warmup: int, ti
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
 
     def step(k):
+        """One registration; returns the RegistrationPipeline (lane) whose buffers hold its results."""
         if piped:
-            pr.submit(q_soa, model_soa, MATCH_THR_ABS, MATCH_RATIO, coef, unique=True, seed=7, inputs_ready=True)   # resident before the loop
-            return
+            lane = pr.submit(q_soa, model_soa, MATCH_THR_ABS, MATCH_RATIO, coef, unique=True, seed=7, inputs_ready=True)   # resident before the loop
+            return pr.lanes[lane]
         if k is not None:
             ev[k][0].record()
         pipe.search_local(q_soa, model_soa)
@@ -213,6 +217,7 @@ def run_registration(ctx: Ctx, M_total: int, Q: int, steps: int, warmup: int, ti
             ev[k][1].record()
         pipe.match_after_search(q_soa, model_soa, MATCH_THR_ABS, MATCH_RATIO, unique=True)
         pipe.ransac_sharded(coef, seed=7)               # one rank: plain ransac(); N ranks: hypotheses split N ways
+        return pipe
 
     for _ in range(max(warmup, in_flight if piped else 0)):
         step(None)
@@ -223,7 +228,7 @@ def run_registration(ctx: Ctx, M_total: int, Q: int, steps: int, warmup: int, ti
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(steps):
-        step(k)
+        last = step(k)
     torch.cuda.synchronize()
     if ctx.collective:
         dist.barrier()
@@ -253,11 +258,39 @@ def run_registration(ctx: Ctx, M_total: int, Q: int, steps: int, warmup: int, ti
            "model_prepare_ms": prepare_ms, "in_flight": in_flight,
            "ransac": {"n_pairs": n_pairs, "max_inliers": res["maxInliers"], "num_success": res["numSuccess"],
                       "failed": res["failed"]}, "_model": model, "_surf": surf}
+    if keep_outputs:
+        out["_outputs"] = step_outputs(last, res, n_pairs)
     if piped:
         del pr
     del pipe, model_soa, model_t, q_soa
     torch.cuda.empty_cache()
     return out
+
+
+def step_outputs(pipe, res: dict, n_pairs: int) -> dict:
+    """What one step hands its caller, as float64 host arrays: the matched pairs (1-based surface row, model row), their
+    coordinates (pts1 = surface, pts2 = model) -- match_after_search's returns -- and the RANSAC result of fetch_result."""
+    n = int(n_pairs)
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    return {"pairs": f64(pipe.pairs[:n].cpu().numpy()),
+            "pts1": f64(pipe.pts1[:, :n].cpu().numpy().T), "pts2": f64(pipe.pts2[:, :n].cpu().numpy().T),
+            "T": f64(res["T"]), "inlier_idx": f64(res["inlierIdx"]),
+            "counts": f64([n, res["n_inliers"], res["numSuccess"], res["maxInliers"], int(res["failed"])])}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outputs: dict, out_dir: str, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """out_dir/<name>.npy for every output.  Over `budget` bytes in all, every array of more than 4096 rows keeps the same
+    fraction of its rows, picked by a fixed seed (arrays of equal length keep the same rows, so pairs and pts stay aligned)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in outputs.items():
+        if total > budget and a.shape[0] > 4096:
+            keep = max(4096, int(a.shape[0] * (budget / total) * 0.9))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def extra_two_in_flight(ctx: Ctx, Q: int, steps: int) -> dict:
@@ -862,12 +895,21 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--model-points", type=int, default=1_000_000, help="model points in TOTAL (sharded over the GPUs)")
     ap.add_argument("--surface-points", type=int, default=50_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only")
-    ap.add_argument("--crops", type=int, default=64, help="crops of the cfg 5 batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other configs and sizes (extras), the two-in-flight "
+                         "comparison and the CPU baseline; without it a run is set-up, warm-up, the timed steps and the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extras (headline + CPU baseline)")
+    ap.add_argument("--crops", type=int, default=64, help="crops of the cfg 5 batch (--full)")
     ap.add_argument("--in-flight", type=int, default=2, help="registrations in flight per rank (one HIP stream + buffer set each); 1 = the serial step of rounds 1-3")
-    ap.add_argument("--skip", default="", help="comma-separated extras to leave out (e.g. host_tier,desc_chain)")
+    ap.add_argument("--skip", default="", help="comma-separated extras to leave out (e.g. host_tier,desc_chain; --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (pairs, pts1, pts2, T, inlier_idx, counts) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
+    with_cpu = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as dist
@@ -898,11 +940,14 @@ def main() -> None:
     ctx = Ctx(rank, world, dev, collective)
 
     Q, M_total = args.surface_points, args.model_points
-    head = run_registration(ctx, M_total, Q, args.steps, args.warmup, time_kernel=True, in_flight=args.in_flight)
+    head = run_registration(ctx, M_total, Q, args.steps, args.warmup, time_kernel=True, in_flight=args.in_flight,
+                            keep_outputs=args.dump_outputs is not None and rank == 0)
     model, surf = head.pop("_model"), head.pop("_surf")
+    if "_outputs" in head:
+        dump_outputs(head.pop("_outputs"), args.dump_outputs)
     extra_steps, extra_warm = max(3, min(args.steps, 10)), min(args.warmup, 2)
     more = {}
-    if not args.no_extras:
+    if extras:
         if world > 1:
             for key, mt in (("cfg3_model_2M", 2_000_000), ("weak_1M_per_gpu", 1_000_000 * world)):
                 r = run_registration(ctx, mt, Q, extra_steps, extra_warm, time_kernel=False, in_flight=args.in_flight)
@@ -982,13 +1027,12 @@ def main() -> None:
             if k1 and M_total == 1_000_000 and Q == 50_000:
                 t1 = FLOP_PER_PAIR * float(Q) * rows / (k1 * 1e-3) / 1e12
                 out["roofline"]["alone"] = {"ms": k1, "achieved": round(t1, 2), "frac": round(t1 / PEAK_F16_MFMA_TFLOPS, 4)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and with_cpu:
             out["cpu_baseline"] = cpu_baseline(model, surf)
     del model, surf
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         ex = {}
         skip = set(x for x in args.skip.split(",") if x)
-        with_cpu = not args.no_cpu_baseline
         for name, fn in (("getMatches_cfg2", extra_get_matches), ("descriptors_cfg4", extra_descriptors),
                          ("align_points_knn_batched", extra_align), ("ransac_cfg1", extra_ransac_cfg1),
                          ("ransac_cfg1_batched", extra_ransac_cfg1_batched), ("sweep", extra_sweep),

@@ -24,5 +24,5 @@ bash scripts/pmc_traffic.sh r03_desc gpurun_out/r03_pmc_desc_traffic.json "" -- 
 echo "== sweep bench"
 python scripts/sweep_bench.py > gpurun_out/r03_sweep_bench.json 2> gpurun_out/r03_sweep_bench.err || exit 1
 echo "== full bench line"
-python bench.py > gpurun_out/r03_bench_line.json 2> gpurun_out/r03_bench_line.err || exit 1
+python bench.py --full > profiles/r03_bench_line.json || exit 1
 echo done

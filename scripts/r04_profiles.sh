@@ -19,5 +19,5 @@ bash scripts/pmc_traffic.sh r04_step gpurun_out/r04_pmc_step_traffic.json "knn_c
 echo "== descriptors at cfg 4: kernel stats"
 bash scripts/prof_stats.sh r04_desc_1m 1 -m desc_kernel -- scripts/desc_dev_bench.py 1000000 1000000 > gpurun_out/r04_desc_1m_stats.txt 2>&1 || exit 1
 echo "== full bench line"
-python bench.py > gpurun_out/r04_bench_line.json 2> gpurun_out/r04_bench_line.err || exit 1
+python bench.py --full > profiles/r04_bench_line.json || exit 1
 echo done
