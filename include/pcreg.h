@@ -77,7 +77,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
 /* Test hook, not part of the reference's interface: selects the OTHER side of a certified fast path (process-wide), so that
  * the parity tests can run both sides inside one process.  Every setting returns the same indices and counts.  Keys:
  * "knn_exact", "match_exact", "match_force_fallback" (1, 2), "ransac_fused", "ransac_nolane", "ransac_f64score",
- * "ransac_resident_f64", "align_times", "align_shape", "seg_debug", "seg_batched", "seg_wave_finalize", "match_stats"; value 0 restores the default.  The library reads NO
+ * "ransac_resident_f64", "align_times", "align_shape", "seg_debug", "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb" (the
+ * descriptor memory bound of pcreg_final_stage in MB instead of 4 GB, to exercise its batches); value 0 restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
 /* With pcreg_debug_set("match_stats", 1): the counters of the certified SAD matcher summed over the calls since the last
@@ -288,6 +289,43 @@ int pcreg_spatial_histogram_descriptors_f32(const float* pts, int P, int ld, con
 int pcreg_spatial_histogram_descriptors_mixed(const void* pts, int pts_is_single, int P, int ld, const void* sample_pts,
                                               int sample_is_single, int S, int lds, const pcreg_desc_opts* options,
                                               double* feat, double* desc, int* V);
+
+/* The final stage of completeExperimentFast.m:280-394 at the host tier, in two calls (the first fixes the keypoint draw of the
+ * second, as pcreg_sphere_counts does for pcreg_sphere_sweep).  K clusters: locs K x 3 column-major (locCur of :283-288), T [K][16]:
+ * the transforms that MOVE the surface, T_k = invertTF(transCur_k) (:291) computed by the caller in its own arithmetic, K
+ * column-major 4 x 4 matrices back to back (MATLAB's 4 x 4 x K).
+ *
+ * pcreg_final_stage_limits: limits [K][6] = (xmin xmax ymin ymax zmin zmax) of pts_tform_k = quickTF(pts, T_k) as the library moves
+ * the surface -- bit for bit the copies pcreg_final_stage describes.  pcRandomUniformSamples (:418-432) draws from MATLAB's rand
+ * stream, so the keypoints stay the caller's; their count and box come from these limits.
+ *
+ * pcreg_final_stage: per cluster k (:291-353)
+ *     pts_tform = quickTF(pts, T_k);  [feat, desc] = getSpacialHistogramDescriptors(pts_tform, keypoints_k, desc_opts with ALIGN_POINTS = 0)
+ *     mask = getDescriptorMask(featModel_noLRF, locs(k,:), R_desc);  matches = getMatches(desc, descModel_noLRF(mask, :), par)
+ * then (:357-394) the matches closer than maxDist, precision(k) = numel(close) / size(matches, 1) * 100 (NaN for 0 / 0), the best
+ * cluster by MATLAB's max (first maximum, NaN skipped, the first cluster when all are NaN), T_refine = estimateTransform over its
+ * close matches, pts_final = quickTF(pts_tform_best, invertTF(T_refine)) (pts_tform_best itself when T_refine is []).
+ * model: the no-LRF model descriptors (pcreg_desc_set, D = 980); featModel VM x 3 column-major; pts N x 3 (ld >= N); keypoints
+ * kp_off[K] x 3 column-major (ld = kp_off[K]), cluster k's rows [kp_off[k], kp_off[k+1]).
+ * Outputs: num_keypoints (V_k, the surviving keypoints), num_desc (model keypoints in the sphere), num_matches, num_close,
+ * precision: K each; *best 0-based; T_refine column-major 4 x 4 (zeros with *refine_empty = 1 for MATLAB's []); pts_final N x 3
+ * (ld N); pairs (or NULL): capacity kp_off[K] rows of [surface, model] 1-based uint32 pairs, cluster k's num_matches[k] pairs at
+ * row kp_off[k] (the model index counting inside the sphere, like matches of :344).  Metric SAD.
+ * Enqueue order: upload, every moved copy in one launch, per cluster the descriptor chain, the spheres' counts, ONE read of the
+ * sizes, the spheres' row lists, per cluster the row gather and getMatches, the close-match / refine kernel (one wave per cluster),
+ * the pick / final-surface kernel, ONE read of the results.  (getMatches with Unique on more than ~4500 keypoints synchronises once
+ * per cluster to size its back-search, as pcreg_dev_get_matches documents.)
+ * Memory: a cluster's fp64 descriptors take 7.84 KB per keypoint drawn.  Up to 4 GB of them the clusters run as one batch; above,
+ * they run in batches of consecutive clusters whose descriptors fit 4 GB together (a larger single cluster runs alone), reusing
+ * the buffers: one more synchronisation (the batch's sizes) per batch, identical results.
+ * Every size is checked before anything is enqueued: K >= 1, kp_off[0] = 0 and non-decreasing, N >= 1, ld >= N, the set's D = 980;
+ * a support above the LDS capacity is refused with PCREG_E_ARG. */
+int pcreg_final_stage_limits(const double* pts, int N, int ld, const double* T, int K, double* limits);
+int pcreg_final_stage(const pcreg_desc_set* model_noLRF, const double* featModel_noLRF, int ldM, const double* pts, int N, int ld,
+                      const double* locs, const double* T, int K, const double* keypoints, const int32_t* kp_off,
+                      const pcreg_desc_opts* desc_opts, const pcreg_match_opts* par, double R_desc, double maxDist,
+                      int32_t* num_keypoints, int32_t* num_desc, int32_t* num_matches, int32_t* num_close, double* precision,
+                      int32_t* best, double T_refine[16], int32_t* refine_empty, double* pts_final, uint32_t* pairs);
 
 /* ---- device tier ------------------------------------------------------------------
  * All pointers are device memory on the current device; `stream` is a hipStream_t.
@@ -535,6 +573,25 @@ int pcreg_dev_quick_tf(const double* pts, int n, int ld, const double T[16], dou
  * empty), info[0] = number of inliers, info[1] = 1 if the transform is empty. */
 int pcreg_dev_refine_by_distance(const double* pts1, const double* pts2, const int32_t* n_dev, int cap, int ld,
                                  double maxDist, double* T16, int32_t* info, void* stream);
+
+/* The final stage's device pieces, batched over its K clusters (pcreg_final_stage runs on them).
+ * pcreg_dev_quick_tf_batched: out copy k (n x 3 column-major, leading dimension ldo, starting at out + 3 k ldo) = [pts, 1] * T_k,
+ *   T_dev [K][16] column-major 4 x 4 on the DEVICE; bit for bit K calls of pcreg_dev_quick_tf.  limits (or NULL) [K][6]: every
+ *   copy's (xmin xmax ymin ymax zmin zmax) (+inf / -inf for n = 0).  One launch for the copies.
+ * pcreg_dev_final_close_refine_batched: completeExperimentFast.m:357-391 for K clusters, one wave each.  Cluster k's pairs (1-based
+ *   [.][2], as pcreg_dev_get_matches writes them) and its surviving keypoints (feat, row-major [.][3]) start at row kp_off[k] (capacity
+ *   kp_off[k+1] - kp_off[k]); its model keypoints at row seg_off[k] of featCur_all ([.][3]); n_pairs[k] pairs.  Out: n_close[k],
+ *   precision[k] = n_close / n * 100 (fp64, NaN for n = 0), T16 [K][16] and empty[k] -- bit for bit pcreg_dev_gather_matched_rows +
+ *   pcreg_dev_refine_by_distance on the cluster (one device function serves both kernels).  kp_off / seg_off on the device.
+ * pcreg_dev_final_pick_apply: best = MATLAB's max over precision (first maximum, NaN skipped, 0 if all are NaN) into *best (device
+ *   int32), out (n x 3, ldo) = quickTF(copy best of pts_tform_all, invertTF(T16[best])) with invertTF.m's arithmetic, or copy best
+ *   itself when empty[best]; pts_tform_all holds K copies of n x 3 (leading dimension ld) at 3 k ld.  Nothing is read on the host. */
+int pcreg_dev_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, void* stream);
+int pcreg_dev_final_close_refine_batched(const uint32_t* pairs, const int32_t* n_pairs, const double* feat, const int32_t* kp_off,
+                                         const double* featCur_all, const int32_t* seg_off, int K, double maxDist, int32_t* n_close,
+                                         double* precision, double* T16, int32_t* empty, void* stream);
+int pcreg_dev_final_pick_apply(const double* precision, const double* T16, const int32_t* empty, int K, const double* pts_tform_all, int n,
+                               int ld, double* out, int ldo, int32_t* best, void* stream);
 
 /* ---- multi-GPU behind the C ABI (RCCL over xGMI inside the library; comm.hip) -----------------------------
  * One process per GPU -- a MATLAB parfor / spmd worker each, the reference's own unit of parallelism

@@ -18,6 +18,9 @@
 //       R_desc, par, putativeThresh, coef, seed -> modelRows, pairs, nPairs, trial, T, numSuccess, maxInliers, failed   (completeExperimentFast.m:52-224)
 //   'sphereModelCreate', hModel, featModel, centres, int32 numDesc, R_desc -> handle, modelRows | 'sphereSweepOnModel', hSphereModel, hSurface,
 //       featSurface, S, par, putativeThresh, coef, seed -> pairs, nPairs, trial, T, numSuccess, maxInliers, failed | 'sphereModelDestroy', handle
+//   'finalStageLimits', pts, T (4x4xK, invertTF of each transCur) -> limits (K x 6) | 'finalStage', hModelNoLRF, featModel_noLRF, pts,
+//       locs, T, keypoints, int32 kpOff, descOpt, par, R_desc, maxDist -> numKeypoints, numDesc, numMatches, numClose, precisions,
+//       best (1-based), T_refine ([] if empty), ptsFinal, pairs         (completeExperimentFast.m:280-394 after clusterPoints)
 //   'getLocalPoints', pts, R, c, min_points, max_points   -> pts_sphere, dists
 //   'setDevice', ordinal | 'commId' -> id | 'commInit', rank, world, id | 'commDestroy'     (one worker per GPU)
 //   'matchPointsSharded', surface, modelRows, m_lo, M_total, thrAbs, maxRatio, unique     -> pairs (P x 2 uint32, global model rows)
@@ -259,6 +262,96 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 if (nlhs > 1) for (int v = 0; v < V; ++v) for (int c = 0; c < PCREG_DESC_LEN; ++c) mxGetPr(plhs[1])[v + (size_t)c * V] = mxGetPr(d)[c + PCREG_DESC_LEN * (size_t)v];
             }
             mxDestroyArray(f); mxDestroyArray(d);
+        }
+    } else if (!strcmp(cmd, "finalStageLimits")) {            // limits = pcreg_mex('finalStageLimits', pts, T)
+        // limits(k, :) = [xmin xmax ymin ymax zmin zmax] of quickTF(pts, T(:, :, k)) as the library moves the surface (the box of
+        // pcRandomUniformSamples, :418-432); T(:, :, k) = invertTF(transCur_k).  matlab/finalStage.m
+        if (nrhs != 3 || !mxIsDouble(prhs[1]) || !mxIsDouble(prhs[2]) || mxGetN(prhs[1]) != 3 || mxGetM(prhs[1]) == 0 || mxGetM(prhs[2]) != 4 ||
+            mxGetN(prhs[2]) == 0 || mxGetN(prhs[2]) % 4 != 0)
+            usage = "finalStageLimits: pts (N x 3 double, N >= 1), T (4 x 4 x K double)";
+        else {
+            const int N = (int)mxGetM(prhs[1]), K = (int)(mxGetN(prhs[2]) / 4);
+            mxArray* lim = mxCreateDoubleMatrix(6, K, mxREAL);                      // [K][6] == 6 x K column-major
+            rc = pcreg_final_stage_limits(mxGetPr(prhs[1]), N, N, mxGetPr(prhs[2]), K, mxGetPr(lim));
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateDoubleMatrix(K, 6, mxREAL);
+                for (int k = 0; k < K; ++k) for (int c = 0; c < 6; ++c) mxGetPr(plhs[0])[k + (size_t)c * K] = mxGetPr(lim)[c + 6 * (size_t)k];
+            }
+            mxDestroyArray(lim);
+        }
+    } else if (!strcmp(cmd, "finalStage")) {
+        // [numKeypoints, numDesc, numMatches, numClose, precisions, best, T_refine, ptsFinal, pairs] = pcreg_mex('finalStage', hModelNoLRF,
+        //     featModel_noLRF, pts, locs, T, keypoints, int32(kpOff), descOpt, par, R_desc, maxDist)
+        // completeExperimentFast.m:291-394 for K clusters in one call: locs K x 3 (locCur), T 4 x 4 x K (invertTF(transCur)), keypoints: every
+        // cluster's draw back to back, kpOff: the K + 1 running row offsets (0-based).  best is 1-based; T_refine is [] when empty; pairs:
+        // sum(numMatches) x 2 uint32, cluster after cluster (model index inside the cluster's sphere).  matlab/finalStage.m
+        if (nrhs != 12 || !mxIsUint64(prhs[1]) || !mxIsDouble(prhs[2]) || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4]) || !mxIsDouble(prhs[5]) ||
+            !mxIsDouble(prhs[6]) || !mxIsInt32(prhs[7]))
+            usage = "finalStage: hModelNoLRF (uint64), featModel_noLRF, pts, locs (double n x 3), T (4 x 4 x K double), keypoints (double S x 3), "
+                    "int32 kpOff, descOpt, par, R_desc, maxDist";
+        else {
+            const mxArray* q = prhs[8];
+            pcreg_desc_opts d;
+            const double mx = field(q, "max_pts", 6000);
+            d.min_pts = (int)field(q, "min_pts", 500); d.max_pts = mx > 2147483647.0 ? 2147483647 : (int)mx;
+            d.R = field(q, "R", 3.5); d.ALIGN_POINTS = 0;                            // :300
+            const mxArray* tv = mxIsStruct(q) ? mxGetField(q, 0, "thVar") : nullptr;
+            d.thVar[0] = (tv && mxGetM(tv) * mxGetN(tv) >= 2) ? mxGetPr(tv)[0] : 3.0; d.thVar[1] = (tv && mxGetM(tv) * mxGetN(tv) >= 2) ? mxGetPr(tv)[1] : 1.5;
+            const mxArray* kk = mxIsStruct(q) ? mxGetField(q, 0, "k") : nullptr;
+            d.k = (!kk || mxIsChar(kk)) ? 1.0 : mxGetScalar(kk);
+            const mxArray* p = prhs[9];
+            pcreg_match_opts o;
+            o.metric = field_is(p, "Metric", "SAD") ? PCREG_METRIC_SAD : PCREG_METRIC_SSD;
+            o.matchThreshold = field(p, "MatchThreshold", 1.0); o.maxRatio = field(p, "MaxRatio", 0.6);
+            o.unique = (int)field(p, "Unique", 0); o.prenormalized = 0;
+            o.unnormalize = (int)field(p, "UNNORMALIZE", 0); o.norm_factor = field(p, "norm_factor", 0.0);
+            o.change_metric = (int)field(p, "CHANGE_METRIC", 0); o.metric_factor = field(p, "metric_factor", 1.0);
+            pcreg_desc_set* hM = (pcreg_desc_set*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            int VM = 0, D = 0;
+            rc = pcreg_desc_set_size(hM, &VM, &D);
+            // every size below is the gateway's own: rows of the arrays it was handed, checked against each other
+            const int N = (int)mxGetM(prhs[3]), K = (int)mxGetM(prhs[4]), S = (int)mxGetM(prhs[6]);
+            const int32_t* off = (const int32_t*)mxGetData(prhs[7]);
+            const int n_off = (int)(mxGetM(prhs[7]) * mxGetN(prhs[7]));
+            if (rc == PCREG_OK && ((int)mxGetM(prhs[2]) != VM || (VM > 0 && mxGetN(prhs[2]) != 3) || N == 0 || mxGetN(prhs[3]) != 3 || K == 0 ||
+                                   mxGetN(prhs[4]) != 3 || mxGetM(prhs[5]) != 4 || mxGetN(prhs[5]) != 4 * (size_t)K || (S > 0 && mxGetN(prhs[6]) != 3) ||
+                                   n_off != K + 1 || off[0] != 0 || off[K] != S))
+                usage = "finalStage: featModel_noLRF must have the rows of the model set, pts N x 3 (N >= 1), locs K x 3 (K >= 1), T 4 x 4 x K, "
+                        "keypoints S x 3, kpOff K + 1 offsets from 0 to S";
+            else if (rc == PCREG_OK) {
+                const size_t k1 = (size_t)K, s1 = (size_t)(S > 0 ? S : 1);
+                mxArray* nk = mxCreateNumericMatrix(k1, 1, mxINT32_CLASS, mxREAL); mxArray* nd = mxCreateNumericMatrix(k1, 1, mxINT32_CLASS, mxREAL);
+                mxArray* nm = mxCreateNumericMatrix(k1, 1, mxINT32_CLASS, mxREAL); mxArray* nc = mxCreateNumericMatrix(k1, 1, mxINT32_CLASS, mxREAL);
+                mxArray* pr = mxCreateDoubleMatrix(k1, 1, mxREAL);
+                mxArray* pf = mxCreateDoubleMatrix((size_t)N, 3, mxREAL);
+                mxArray* buf = mxCreateNumericMatrix(2, s1, mxUINT32_CLASS, mxREAL);     // [S][2]: cluster k's pairs from row kpOff(k)
+                double Tr[16]; int32_t best = 0, empty = 1;
+                rc = pcreg_final_stage(hM, mxGetPr(prhs[2]), VM > 0 ? VM : 1, mxGetPr(prhs[3]), N, N, mxGetPr(prhs[4]), mxGetPr(prhs[5]), K, mxGetPr(prhs[6]), off,
+                                       &d, &o, mxGetScalar(prhs[10]), mxGetScalar(prhs[11]), (int32_t*)mxGetData(nk), (int32_t*)mxGetData(nd),
+                                       (int32_t*)mxGetData(nm), (int32_t*)mxGetData(nc), mxGetPr(pr), &best, Tr, &empty, mxGetPr(pf),
+                                       (uint32_t*)mxGetData(buf));
+                if (rc == PCREG_OK) {
+                    auto out = [&](int k, mxArray* a) { if (nlhs > k) plhs[k] = a; else mxDestroyArray(a); };
+                    auto col = [&](const mxArray* v) { mxArray* a = mxCreateDoubleMatrix(k1, 1, mxREAL); for (int i = 0; i < K; ++i) mxGetPr(a)[i] = (double)((const int32_t*)mxGetData(v))[i]; return a; };
+                    plhs[0] = col(nk);
+                    out(1, col(nd)); out(2, col(nm)); out(3, col(nc));
+                    out(4, mxDuplicateArray(pr));
+                    out(5, mxCreateDoubleScalar((double)best + 1.0));
+                    { mxArray* Ta = empty ? mxCreateDoubleMatrix(0, 0, mxREAL) : mxCreateDoubleMatrix(4, 4, mxREAL); if (!empty) memcpy(mxGetPr(Ta), Tr, sizeof Tr); out(6, Ta); }
+                    out(7, mxDuplicateArray(pf));
+                    {
+                        const int32_t* n = (const int32_t*)mxGetData(nm);
+                        size_t P = 0; for (int k = 0; k < K; ++k) P += (size_t)n[k];
+                        mxArray* pa = mxCreateNumericMatrix(P, 2, mxUINT32_CLASS, mxREAL);
+                        const uint32_t* src = (const uint32_t*)mxGetData(buf); uint32_t* dst = (uint32_t*)mxGetData(pa);
+                        size_t j = 0;
+                        for (int k = 0; k < K; ++k)
+                            for (int e = 0; e < n[k]; ++e, ++j) { dst[j] = src[((size_t)off[k] + e) * 2]; dst[j + P] = src[((size_t)off[k] + e) * 2 + 1]; }
+                        out(8, pa);
+                    }
+                }
+                mxDestroyArray(nk); mxDestroyArray(nd); mxDestroyArray(nm); mxDestroyArray(nc); mxDestroyArray(pr); mxDestroyArray(pf); mxDestroyArray(buf);
+            }
         }
     } else if (!strcmp(cmd, "getLocalPoints")) {              // [pts_sphere, dists] = pcreg_mex('getLocalPoints', pts, R, c, min_points, max_points)
         if (nrhs != 6 || mxGetN(prhs[1]) != 3) usage = "getLocalPoints: pts (N x 3), R, c (1 x 3), min_points, max_points";

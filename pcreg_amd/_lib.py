@@ -52,7 +52,7 @@ class DevRansacResult(C.Structure):
 SYMBOLS = [
     "pcreg_last_error", "pcreg_version", "pcreg_device_count", "pcreg_set_device", "pcreg_device_name", "pcreg_debug_set", "pcreg_debug_match_stats",
     "pcreg_estimate_transform", "pcreg_calc_dists", "pcreg_ransac", "pcreg_ransac_batched",
-    "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_get_matches_segmented", "pcreg_get_local_points",
+    "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
     "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_match_points_f32",
     "pcreg_dev_model_create", "pcreg_dev_model_destroy", "pcreg_dev_model_search_workspace", "pcreg_dev_model_search_f32",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
@@ -69,6 +69,7 @@ SYMBOLS = [
     "pcreg_dev_get_matches_segmented_workspace", "pcreg_dev_get_matches_segmented", "pcreg_dev_segmented_model_bytes", "pcreg_dev_segmented_model_prepare", "pcreg_dev_get_matches_segmented_prepared",
     "pcreg_dev_gather_rows_f64", "pcreg_dev_sweep_plan", "pcreg_dev_sweep_gather", "pcreg_dev_ransac_batched_workspace",
     "pcreg_dev_ransac_batched", "pcreg_dev_align_points_knn_batched", "pcreg_dev_quick_tf", "pcreg_dev_refine_by_distance",
+    "pcreg_dev_quick_tf_batched", "pcreg_dev_final_close_refine_batched", "pcreg_dev_final_pick_apply",
     "pcreg_comm_get_unique_id", "pcreg_comm_init", "pcreg_comm_init_host_staged", "pcreg_comm_rank", "pcreg_comm_destroy",
     "pcreg_match_points_sharded_f32", "pcreg_ransac_sharded",
     "pcreg_pcd_info", "pcreg_pcd_read", "pcreg_pcd_write", "pcreg_mat_read_double",

@@ -478,6 +478,60 @@ def sphereSweepOnModel(sm: SphereModel, hSurface: DescSet, featSurface, par: dic
                 transforms=[None if fl[t] else T[t].reshape(4, 4, order="F").copy() for t in range(n)])
 
 
+def _moving_transforms(transforms) -> np.ndarray:
+    """[K, 16]: invertTF(transCur_k) (:291) column-major, cluster after cluster -- the host arithmetic of FinalStage.run."""
+    return np.ascontiguousarray([invertTF(np.asarray(T, dtype=np.float64)).ravel(order="F") for T in transforms], dtype=np.float64).reshape(-1, 16)
+
+
+def finalStageLimits(pts, transforms) -> np.ndarray:
+    """[K, 6] (xmin xmax ymin ymax zmin zmax) of quickTF(pts, invertTF(transCur_k)) for every transCur_k of `transforms`, as the
+    library moves the surface (pcreg_final_stage_limits): the box and count of pcRandomUniformSamples (:418-432) for cluster k."""
+    P = _pts3(pts, "pts")
+    Tm = _moving_transforms(transforms)
+    K = Tm.shape[0]
+    lim = np.zeros((max(K, 1), 6))
+    check(lib().pcreg_final_stage_limits(_ptr(P, C.c_double), P.shape[0], max(P.shape[0], 1), _ptr(Tm, C.c_double), K, _ptr(lim, C.c_double)))
+    return lim[:K].copy()
+
+
+def finalStage(hModel: DescSet, featModel, pts, clusters, sample_pts, descOpt: dict, par: dict, R_desc: float, maxDist: float = 1.5,
+               return_matches: bool = True) -> dict:
+    """completeExperimentFast.m:280-394 after clusterPoints in ONE library call (pcreg_final_stage) -- pcreg_amd.sweep.FinalStage.run
+    at the host tier.  hModel: the no-LRF model descriptors (DescSet); featModel: their keypoints; pts: the surface N x 3;
+    clusters = [(locCur, transCur)]; sample_pts[i]: the keypoints drawn for cluster i (S_i x 3, see finalStageLimits).
+    Keys as FinalStage.run's, without pts_tform (the moved copies stay in the library) and model_rows; pts_final is N x 3 here."""
+    K = len(clusters)
+    fM, P = _pts3(featModel, "featModel"), _pts3(pts, "pts")
+    locs = _fcol(np.asarray([np.asarray(c[0], dtype=np.float64).ravel()[:3] for c in clusters], dtype=np.float64).reshape(-1, 3))
+    Tm = _moving_transforms([c[1] for c in clusters])
+    kps = [np.asarray(k, dtype=np.float64).reshape(-1, 3) for k in sample_pts]
+    if len(kps) != K:
+        raise ValueError(f"{len(kps)} keypoint sets for {K} clusters")
+    kp_off = np.zeros(K + 1, dtype=np.int32); kp_off[1:] = np.cumsum([k.shape[0] for k in kps])
+    kp = _fcol(np.vstack(kps) if K and kp_off[-1] else np.zeros((0, 3)))
+    tot, N = int(kp_off[-1]), P.shape[0]
+    i32 = lambda: np.zeros(max(K, 1), dtype=np.int32)
+    nk, nd, nm, nc = i32(), i32(), i32(), i32()
+    prec = np.zeros(max(K, 1))
+    best, empty = C.c_int32(0), C.c_int32(1)
+    T = np.zeros(16)
+    out = np.zeros((max(N, 1), 3), order="F")
+    pairs = np.zeros((max(tot, 1), 2), dtype=np.uint32)
+    do, mo = _desc_opts(dict(descOpt, ALIGN_POINTS=False)), _match_opts(par)
+    check(lib().pcreg_final_stage(hModel._h, _ptr(fM, C.c_double), max(fM.shape[0], 1), _ptr(P, C.c_double), N, max(N, 1), _ptr(locs, C.c_double),
+                                  _ptr(Tm, C.c_double), K, _ptr(kp, C.c_double), _ptr(kp_off, C.c_int32), C.byref(do), C.byref(mo), C.c_double(R_desc),
+                                  C.c_double(maxDist), _ptr(nk, C.c_int32), _ptr(nd, C.c_int32), _ptr(nm, C.c_int32), _ptr(nc, C.c_int32),
+                                  _ptr(prec, C.c_double), C.byref(best), _ptr(T, C.c_double), C.byref(empty), _ptr(out, C.c_double),
+                                  _ptr(pairs, C.c_uint32) if return_matches else None))
+    npr = nm[:K].astype(np.int64)
+    res = dict(num_keypoints=nk[:K].astype(np.int64), num_desc=nd[:K].astype(np.int64), num_matches=npr, num_close=nc[:K].astype(np.int64),
+               precisions=prec[:K].copy(), best=int(best.value), T_refine=None if empty.value else T.reshape(4, 4, order="F").copy(),
+               pts_final=np.ascontiguousarray(out[:N]))
+    if return_matches:
+        res["matches"] = [pairs[kp_off[i]:kp_off[i] + npr[i]].copy() for i in range(K)]
+    return res
+
+
 def getMatches(descSurface, descModel, par: dict) -> np.ndarray:
     """matches = getMatches(descSurface, descModel, par)  (getMatches.m:1-59):
     P x 2 uint32, 1-based [surfaceIdx, modelIdx], ascending in the first column."""

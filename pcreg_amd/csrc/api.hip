@@ -107,7 +107,7 @@ extern "C" {
 int pcreg_debug_set(const char* key, int value) {
     static const char* const names[pcreg::kDbgCount] = {"knn_exact", "match_exact", "match_force_fallback", "ransac_fused", "ransac_nolane",
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
-                                                        "seg_batched", "seg_wave_finalize", "match_stats"};
+                                                        "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -1438,6 +1438,206 @@ int pcreg_dev_refine_by_distance(const double* pts1, const double* pts2, const i
     PCREG_ARG(pts1 && pts2 && n_dev && T16 && info && cap >= 0 && ld >= cap);
     GUARD();
     return launch_refine_by_distance(pts1, pts2, n_dev, cap, ld, maxDist, T16, info, (hipStream_t)stream);
+}
+int pcreg_dev_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, void* stream) {
+    PCREG_ARG(T_dev && K >= 0 && n >= 0 && ld >= n && ldo >= n && (n == 0 || (pts && out)));
+    GUARD();
+    return launch_quick_tf_batched(pts, n, ld, T_dev, K, out, ldo, limits, (hipStream_t)stream);
+}
+int pcreg_dev_final_close_refine_batched(const uint32_t* pairs, const int32_t* n_pairs, const double* feat, const int32_t* kp_off,
+                                         const double* featCur_all, const int32_t* seg_off, int K, double maxDist, int32_t* n_close,
+                                         double* precision, double* T16, int32_t* empty, void* stream) {
+    PCREG_ARG(pairs && n_pairs && feat && kp_off && featCur_all && seg_off && n_close && precision && T16 && empty && K >= 0);
+    GUARD();
+    return launch_final_close_refine_batched(pairs, n_pairs, feat, kp_off, featCur_all, seg_off, K, maxDist, n_close, precision, T16, empty,
+                                             (hipStream_t)stream);
+}
+int pcreg_dev_final_pick_apply(const double* precision, const double* T16, const int32_t* empty, int K, const double* pts_tform_all, int n, int ld,
+                               double* out, int ldo, int32_t* best, void* stream) {
+    PCREG_ARG(precision && T16 && empty && best && K >= 1 && n >= 0 && ld >= n && ldo >= n && (n == 0 || (pts_tform_all && out)));
+    GUARD();
+    return launch_final_pick_apply(precision, T16, empty, K, pts_tform_all, n, ld, out, ldo, best, (hipStream_t)stream);
+}
+
+// ---- the final stage of completeExperimentFast.m:280-394 at the host tier ------------------------------------------------------
+int pcreg_final_stage_limits(const double* pts, int N, int ld, const double* T, int K, double* limits) {
+    PCREG_ARG(pts && T && limits && N >= 1 && ld >= N);
+    if (K < 1) { set_error("pcreg_final_stage_limits: K = %d clusters (at least one)", K); return PCREG_E_ARG; }
+    GUARD();
+    const size_t n = (size_t)N, k = (size_t)K;
+    void *dp, *dT, *tf, *lim;
+    TRY(scratch().get(0, sizeof(double) * 3 * n, &dp));
+    TRY(scratch().get(1, sizeof(double) * 16 * k, &dT));
+    TRY(scratch().get(2, sizeof(double) * 3 * n * k, &tf));
+    TRY(scratch().get(3, sizeof(double) * 6 * k, &lim));
+    TRY(upload_cols(pts, N, ld, 3, (double*)dp, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * k, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_quick_tf_batched((const double*)dp, N, N, (const double*)dT, K, (double*)tf, N, (double*)lim, g_stream));
+    PCREG_HIP(hipMemcpyAsync(limits, lim, sizeof(double) * 6 * k, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+
+// the bound on the clusters' fp64 descriptors held at once (debug key "final_batch_mb" lowers it for the tests)
+static size_t final_stage_bound() {
+    const int mb = debug_flag(kDbgFinalBatchMB);
+    return mb > 0 ? (size_t)mb << 20 : (size_t)4 << 30;
+}
+
+int pcreg_final_stage(const pcreg_desc_set* model, const double* featModel, int ldM, const double* pts, int N, int ld, const double* locs,
+                      const double* T, int K, const double* keypoints, const int32_t* kp_off, const pcreg_desc_opts* desc_opts,
+                      const pcreg_match_opts* par, double R_desc, double maxDist, int32_t* num_keypoints, int32_t* num_desc,
+                      int32_t* num_matches, int32_t* num_close, double* precision, int32_t* best, double T_refine[16], int32_t* refine_empty,
+                      double* pts_final, uint32_t* pairs) {
+    // every caller-supplied size is checked before anything is enqueued
+    PCREG_ARG(model && pts && locs && T && kp_off && desc_opts && par && num_keypoints && num_desc && num_matches && num_close && precision);
+    PCREG_ARG(best && T_refine && refine_empty && pts_final && N >= 1 && ld >= N && ldM >= model->n && (model->n == 0 || featModel));
+    if (K < 1) { set_error("pcreg_final_stage: K = %d clusters (at least one)", K); return PCREG_E_ARG; }
+    if (kp_off[0] != 0) { set_error("pcreg_final_stage: kp_off[0] = %d (must be 0)", kp_off[0]); return PCREG_E_ARG; }
+    for (int k = 0; k < K; ++k)
+        if (kp_off[k + 1] < kp_off[k]) { set_error("pcreg_final_stage: kp_off decreases at %d (%d -> %d)", k, kp_off[k], kp_off[k + 1]); return PCREG_E_ARG; }
+    const int total = kp_off[K];
+    PCREG_ARG(total == 0 || keypoints);
+    if (model->D != PCREG_DESC_LEN) {
+        set_error("pcreg_final_stage: the model set has D = %d columns, the descriptors have %d", model->D, PCREG_DESC_LEN);
+        return PCREG_E_ARG;
+    }
+    if (par->metric != PCREG_METRIC_SAD) { set_error("pcreg_final_stage: Metric must be SAD (as in pcreg_sphere_sweep)"); return PCREG_E_ARG; }
+    PCREG_ARG(desc_opts->R > 0 && desc_opts->k > 0 && desc_opts->min_pts >= 0);
+    GUARD();
+    const int VM = model->n, D = model->D;
+    const size_t n = (size_t)N, k1 = (size_t)K, tot = (size_t)(total > 0 ? total : 1);
+    pcreg_desc_opts o = *desc_opts;
+    o.ALIGN_POINTS = 0;                                                       // :300 "this false is the key"
+
+    // consecutive batches of clusters whose fp64 descriptors (7.84 KB per keypoint drawn) fit the bound together; a cluster
+    // larger than the bound runs alone
+    const size_t bound = final_stage_bound(), row_bytes = sizeof(double) * (size_t)D;
+    std::vector<int> cut{0};
+    size_t acc = 0, batch_rows = 1;
+    int S_max = 1;
+    for (int k = 0; k < K; ++k) {
+        const size_t b = row_bytes * (size_t)(kp_off[k + 1] - kp_off[k]);
+        if (k > cut.back() && acc + b > bound) { cut.push_back(k); acc = 0; }
+        acc += b;
+        S_max = std::max(S_max, kp_off[k + 1] - kp_off[k]);
+    }
+    cut.push_back(K);
+    const int nbatch = (int)cut.size() - 1;
+    for (int b = 0; b < nbatch; ++b) batch_rows = std::max(batch_rows, (size_t)(kp_off[cut[b + 1]] - kp_off[cut[b]]));
+
+    void *tmp, *dp, *dT, *dkp, *fm, *cen, *tf, *feat, *desc, *ws, *ints, *dbl, *dpairs;
+    const size_t wsb = descriptors_workspace_bytes(N, S_max);
+    // int32 block: counters [2K] | n_in [K] | nsel [K] | n_pairs [K] | n_close [K] | empty [K] | best | kp_off [K + 1] | seg_off [K + nbatch]
+    const size_t ni = 7 * k1 + 1 + (k1 + 1) + (k1 + (size_t)nbatch);
+    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)std::max({N, VM, K}), &tmp));
+    TRY(scratch().get(1, sizeof(double) * 3 * n, &dp));
+    TRY(scratch().get(2, sizeof(double) * 16 * k1, &dT));
+    TRY(scratch().get(3, sizeof(double) * 3 * tot, &dkp));
+    TRY(scratch().get(4, sizeof(double) * 3 * (size_t)std::max(VM, 1), &fm));
+    TRY(scratch().get(5, sizeof(double) * 3 * k1, &cen));
+    TRY(scratch().get(6, sizeof(double) * 3 * n * k1, &tf));
+    TRY(scratch().get(7, sizeof(double) * 3 * tot, &feat));
+    TRY(scratch().get(8, row_bytes * batch_rows, &desc));
+    TRY(scratch().get(9, wsb, &ws));
+    TRY(scratch().get(10, sizeof(int32_t) * ni, &ints));
+    TRY(scratch().get(11, sizeof(double) * 17 * k1, &dbl));
+    TRY(scratch().get(16, sizeof(uint32_t) * 2 * tot, &dpairs));
+    int32_t* counters = (int32_t*)ints;
+    int32_t *n_in = counters + 2 * k1, *nsel = n_in + k1, *n_pairs = nsel + k1, *n_close = n_pairs + k1, *empty = n_close + k1, *dbest = empty + k1;
+    int32_t *dkpoff = dbest + 1, *dseg = dkpoff + (k1 + 1);
+    double *dprec = (double*)dbl, *dT16 = dprec + k1;
+    const double* rM = nullptr;
+    if (VM > 0) TRY(desc_set_rows(model, &rM));
+    std::vector<int32_t> seg_h(k1 + (size_t)nbatch, 0);       // per batch its running sums
+    std::vector<int32_t> h_cnt(2 * k1), h_in(k1), h_res(3 * k1 + 1);
+    std::vector<double> h_T16(16 * k1);
+    struct DrainAtExit { ~DrainAtExit() { (void)hipStreamSynchronize(g_stream); } } drain;   // no host array is freed under a pending copy
+
+    // upload; :291 pts_tform = quickTF(ptsSurface, invertTF(transCur)) for every cluster in one launch
+    TRY(upload_cols(pts, N, ld, 3, (double*)dp, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * k1, hipMemcpyHostToDevice, g_stream));
+    TRY(upload_cols(keypoints, total, total, 3, (double*)dkp, g_stream));
+    TRY(upload_points_aos(featModel, VM, ldM, (double*)tmp, (double*)fm, g_stream));
+    TRY(upload_points_aos(locs, K, K, (double*)tmp, (double*)cen, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dkpoff, kp_off, sizeof(int32_t) * (k1 + 1), hipMemcpyHostToDevice, g_stream));
+    PCREG_HIP(hipMemsetAsync(ints, 0, sizeof(int32_t) * 7 * k1, g_stream));
+    PCREG_HIP(hipMemsetAsync(dpairs, 0, sizeof(uint32_t) * 2 * tot, g_stream));
+    TRY(launch_quick_tf_batched((const double*)dp, N, N, (const double*)dT, K, (double*)tf, N, nullptr, g_stream));
+
+    size_t seg_pos = 0;
+    for (int b = 0; b < nbatch; ++b) {
+        const int k0 = cut[b], kb = cut[b + 1], nb = kb - k0, r0 = kp_off[k0];
+        // :309-310 descriptors of every moved surface WITHOUT local alignment (keypoints: the caller's draw, :297)
+        for (int k = k0; k < kb; ++k) {
+            const int S = kp_off[k + 1] - kp_off[k];
+            if (S == 0) continue;
+            TRY(launch_descriptors((const double*)tf + (size_t)k * 3 * n, N, N, (const double*)dkp + kp_off[k], S, total, o, 0,
+                                   (double*)feat + (size_t)kp_off[k] * 3, (double*)desc + (size_t)(kp_off[k] - r0) * D, nullptr, nullptr,
+                                   counters + 2 * k, counters + 2 * k + 1, ws, wsb, g_stream));
+        }
+        // :319 the model keypoints inside every cluster's sphere, counted
+        if (VM > 0) TRY(launch_sphere_counts((const double*)fm, VM, (const double*)cen + (size_t)k0 * 3, nb, R_desc, n_in + k0, g_stream));
+        // ---- the sizes: V_k, the over-capacity flags, the sphere counts (one synchronisation per batch)
+        PCREG_HIP(hipMemcpyAsync(h_cnt.data() + 2 * (size_t)k0, counters + 2 * (size_t)k0, sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipMemcpyAsync(h_in.data() + k0, n_in + k0, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipStreamSynchronize(g_stream));
+        int n_max = 0, v_max = 0;
+        int32_t* sh = seg_h.data() + seg_pos;
+        sh[0] = 0;
+        for (int k = k0; k < kb; ++k) {
+            if (h_cnt[2 * k + 1]) {
+                set_error("a support holds %d points: more than an LDS-resident support may have (lower max_pts)", h_cnt[2 * k + 1]);
+                return PCREG_E_ARG;
+            }
+            sh[k - k0 + 1] = sh[k - k0] + h_in[k];
+            n_max = std::max(n_max, (int)h_in[k]); v_max = std::max(v_max, (int)h_cnt[2 * k]);
+        }
+        const int tot_b = sh[nb];
+        int32_t* dsb = dseg + seg_pos;
+        seg_pos += (size_t)nb + 1;
+        void *rows, *featCur, *descCur, *mws;
+        size_t off6[6];
+        const size_t mwsb = dev_get_matches_layout(std::max(v_max, 1), std::max(n_max, 1), D, D + 1, off6);
+        TRY(scratch().get(12, sizeof(int32_t) * (size_t)std::max(tot_b, 1), &rows));
+        TRY(scratch().get(13, sizeof(double) * 3 * (size_t)std::max(tot_b, 1), &featCur));
+        TRY(scratch().get(14, row_bytes * (size_t)std::max(n_max, 1), &descCur));
+        TRY(scratch().get(15, mwsb, &mws));
+        PCREG_HIP(hipMemcpyAsync(dsb, sh, sizeof(int32_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, g_stream));
+        if (VM > 0) TRY(launch_sphere_select_batched((const double*)fm, VM, (const double*)cen + (size_t)k0 * 3, nb, R_desc, dsb, (int32_t*)rows,
+                                                     (double*)featCur, nsel + k0, g_stream));
+        // :321-344 descCur = descModel_noLRF(mask, :), matches = getMatches(desc, descCur, par)
+        for (int k = k0; k < kb; ++k) {
+            const int v = h_cnt[2 * k], m = h_in[k];
+            if (v == 0 || m == 0) continue;
+            TRY(launch_gather_rows_f64(rM, D, (const int32_t*)rows + sh[k - k0], nsel + k, m, (double*)descCur, g_stream));
+            TRY(dev_get_matches_impl((const double*)desc + (size_t)(kp_off[k] - r0) * D, v, D, descCur, m, D, D, PCREG_LAYOUT_ROW_MAJOR, par,
+                                     (uint32_t*)dpairs + (size_t)kp_off[k] * 2, nullptr, n_pairs + k, mws, mwsb, g_stream));
+        }
+        // :357-391 the close matches, the precision and the refined transform of every cluster of the batch
+        TRY(launch_final_close_refine_batched((const uint32_t*)dpairs, n_pairs + k0, (const double*)feat, dkpoff + k0, (const double*)featCur, dsb, nb,
+                                              maxDist, n_close + k0, dprec + k0, dT16 + (size_t)k0 * 16, empty + k0, g_stream));
+    }
+    // :381-394 the best cluster, invertTF(T_refine), the final surface -- on the device
+    double* dpf;
+    { void* q; TRY(scratch().get(17, sizeof(double) * 3 * n, &q)); dpf = (double*)q; }
+    TRY(launch_final_pick_apply(dprec, dT16, empty, K, (const double*)tf, N, N, dpf, N, dbest, g_stream));
+    // ---- the results (one synchronisation)
+    PCREG_HIP(hipMemcpyAsync(h_res.data(), n_pairs, sizeof(int32_t) * (3 * k1 + 1), hipMemcpyDeviceToHost, g_stream));   // n_pairs | n_close | empty | best
+    PCREG_HIP(hipMemcpyAsync(precision, dprec, sizeof(double) * k1, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(h_T16.data(), dT16, sizeof(double) * 16 * k1, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(pts_final, dpf, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, g_stream));
+    if (pairs && total > 0) PCREG_HIP(hipMemcpyAsync(pairs, dpairs, sizeof(uint32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    for (int k = 0; k < K; ++k) {
+        num_keypoints[k] = h_cnt[2 * k]; num_desc[k] = h_in[k];
+        num_matches[k] = h_res[k]; num_close[k] = h_res[k1 + k];
+    }
+    const int bsel = h_res[3 * k1];
+    *best = bsel;
+    *refine_empty = h_res[2 * k1 + bsel];
+    memcpy(T_refine, h_T16.data() + (size_t)bsel * 16, sizeof(double) * 16);
+    return PCREG_OK;
 }
 
 }  // extern "C"

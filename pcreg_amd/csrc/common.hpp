@@ -70,6 +70,7 @@ enum DebugKey {
     kDbgSegBatched,            // "seg_batched": the segmented matcher runs its bounded-workspace (batched) form whatever the size
     kDbgSegWaveFinalize,       // "seg_wave_finalize": the segmented matcher's forward re-rank as one wave per query (rounds 2-3) instead of pick / pairs / decide
     kDbgMatchStats,            // "match_stats": the certified matcher counts what it proves / re-scores / hands on (pcreg_debug_match_stats)
+    kDbgFinalBatchMB,          // "final_batch_mb": pcreg_final_stage's descriptor memory bound in MB instead of 4 GB (0 = the default)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -166,6 +167,13 @@ int launch_gather_rows_f64(const double* src, int D, const int32_t* idx, const i
 int launch_quick_tf(const double* pts, int n, int ld, const double T[16], double* out, int ldo, hipStream_t st);
 int launch_refine_by_distance(const double* p1, const double* p2, const int32_t* n_dev, int cap, int ld, double maxDist,
                               double* T16_dev, int32_t* info_dev, hipStream_t st);
+// the final stage batched over its K clusters (sweep.hip, ransac.hip)
+int launch_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, hipStream_t st);
+int launch_final_close_refine_batched(const uint32_t* pairs, const int32_t* n_pairs, const double* feat, const int32_t* kp_off,
+                                      const double* featCur_all, const int32_t* seg_off, int K, double maxDist, int32_t* n_close,
+                                      double* precision, double* T16, int32_t* empty, hipStream_t st);
+int launch_final_pick_apply(const double* precision, const double* T16, const int32_t* empty, int K, const double* pts_all, int n, int ld,
+                            double* out, int ldo, int32_t* best, hipStream_t st);
 
 void knn_f16_timing_enable(bool on);
 int knn_f16_timing_read(float* mean_ms, int* launches);

@@ -2723,13 +2723,13 @@ __global__ __launch_bounds__(64) void estimate_transform_kernel(const double* p1
 }
 
 // completeExperimentFast.m:368-391: inliers = find(vecnorm(pts1 - pts2, 2, 2) < maxDist), then
-// T_refine = estimateTransform(pts1(inliers,:), pts2(inliers,:)).  One wave; n read from the device.
-__global__ __launch_bounds__(64) void refine_by_distance_kernel(const double* p1, const double* p2, const int32_t* n_dev, int cap,
-                                                                int ld, double maxDist, double* T16, int32_t* info /*[2]: inliers, empty*/) {
-    __shared__ double s3[18];
+// T_refine = estimateTransform(pts1(inliers,:), pts2(inliers,:)) on ONE wave: 64-point chunks in order, the inlier moments
+// summed per lane then across the wave (wave_sum27), the first three inliers kept for the N == 3 branch.  T16 (lanes < 16) is
+// written here; the number of inliers and whether T is empty are returned to every lane.  PTS: anything with
+// load(i, double[6]) -> (pts1(i,:), pts2(i,:)); both kernels below call this body, so they agree bit for bit.
+template <class PTS>
+__device__ __forceinline__ void refine_by_distance_wave(const PTS& P, int n, double maxDist, double* s3, double* T16, int& cnt_out, bool& ok_out) {
     const int lane = threadIdx.x;
-    const int n = min(*n_dev, cap);
-    Pts<false> P{p1, p2, ld, nullptr, n};
     double T[12]; bool ok = false;
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = 0.0;
@@ -2783,7 +2783,50 @@ __global__ __launch_bounds__(64) void refine_by_distance_kernel(const double* p1
         }
         T16[k + 4 * j] = v;
     }
-    if (lane == 0) { info[0] = cnt; info[1] = ok ? 0 : 1; }
+    cnt_out = cnt; ok_out = ok;
+}
+
+// One wave; n read from the device.
+__global__ __launch_bounds__(64) void refine_by_distance_kernel(const double* p1, const double* p2, const int32_t* n_dev, int cap,
+                                                                int ld, double maxDist, double* T16, int32_t* info /*[2]: inliers, empty*/) {
+    __shared__ double s3[18];
+    const int n = min(*n_dev, cap);
+    Pts<false> P{p1, p2, ld, nullptr, n};
+    int cnt; bool ok;
+    refine_by_distance_wave(P, n, maxDist, s3, T16, cnt, ok);
+    if (threadIdx.x == 0) { info[0] = cnt; info[1] = ok ? 0 : 1; }
+}
+
+// pts1 = feat(pairs(:,1),:), pts2 = featCur(pairs(:,2),:) read straight from the 1-based pairs (what gather_matched_rows would
+// have copied out: the same doubles, so the refine sees the same operands)
+struct PairPts {
+    const uint32_t* pairs; const double* fS; const double* fM;
+    __device__ __forceinline__ void load(int i, double (&p)[6]) const {
+        const size_t a = (size_t)(pairs[(size_t)i * 2] - 1u), b = (size_t)(pairs[(size_t)i * 2 + 1] - 1u);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { p[c] = fS[a * 3 + c]; p[3 + c] = fM[b * 3 + c]; }
+    }
+};
+
+// completeExperimentFast.m:357-391 for K clusters, one wave each: cluster k's pairs and surviving keypoints start at row kp_off[k]
+// of pairs / feat (capacity kp_off[k+1] - kp_off[k]), its model keypoints at row seg_off[k] of featCur_all.
+__global__ __launch_bounds__(64) void final_close_refine_batched_kernel(const uint32_t* __restrict__ pairs, const int32_t* __restrict__ n_pairs,
+                                                                        const double* __restrict__ feat, const int32_t* __restrict__ kp_off,
+                                                                        const double* __restrict__ featCur_all, const int32_t* __restrict__ seg_off,
+                                                                        double maxDist, int32_t* __restrict__ n_close, double* __restrict__ precision,
+                                                                        double* __restrict__ T16, int32_t* __restrict__ empty) {
+    __shared__ double s3[18];
+    const int k = blockIdx.x;
+    const int lo = kp_off[k], cap = kp_off[k + 1] - lo;
+    const int n = max(0, min(n_pairs[k], cap));
+    PairPts P{pairs + (size_t)lo * 2, feat + (size_t)lo * 3, featCur_all + (size_t)seg_off[k] * 3};
+    int cnt; bool ok;
+    refine_by_distance_wave(P, n, maxDist, s3, T16 + (size_t)k * 16, cnt, ok);
+    if (threadIdx.x == 0) {
+        n_close[k] = cnt;
+        precision[k] = n > 0 ? (double)cnt / (double)n * 100.0 : __builtin_nan("");     // :373, 0 / 0 = NaN
+        empty[k] = ok ? 0 : 1;
+    }
 }
 
 __global__ void calc_dists_kernel(const double* T16, const double* p1, const double* p2, int n, int ld, double* d) {
@@ -3047,6 +3090,16 @@ int launch_estimate_transform(const double* p1, const double* p2, int n, int ld,
 int launch_refine_by_distance(const double* p1, const double* p2, const int32_t* n_dev, int cap, int ld, double maxDist,
                               double* T16_dev, int32_t* info_dev, hipStream_t st) {
     hipLaunchKernelGGL(refine_by_distance_kernel, dim3(1), dim3(64), 0, st, p1, p2, n_dev, cap, ld, maxDist, T16_dev, info_dev);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+int launch_final_close_refine_batched(const uint32_t* pairs, const int32_t* n_pairs, const double* feat, const int32_t* kp_off,
+                                      const double* featCur_all, const int32_t* seg_off, int K, double maxDist, int32_t* n_close,
+                                      double* precision, double* T16, int32_t* empty, hipStream_t st) {
+    if (K <= 0) return PCREG_OK;
+    hipLaunchKernelGGL(final_close_refine_batched_kernel, dim3(K), dim3(64), 0, st, pairs, n_pairs, feat, kp_off, featCur_all, seg_off, maxDist,
+                       n_close, precision, T16, empty);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -3,7 +3,8 @@
 //   sphere_counts   #{ ||feat - c|| < R } for many centres        getLocalPoints.m:23-34 as used at :57-64
 //   sphere_select   getDescriptorMask (:435-439) as an ordered index list
 //   gather_rows     featCur / descCur = X(mask, :)                 :122-125
-//   quick_tf        quickTF.m:5-7
+//   quick_tf        quickTF.m:5-7 (also K transforms of one cloud in one launch, with each copy's limits)
+//   final_pick      :381-394: MATLAB's max over the clusters' precisions, invertTF(T_refine), the final surface
 // All of it is streaming fp64 work of a few MB: HBM/latency-bound, no tuning beyond coalescing.
 #include "common.hpp"
 #include "select.hpp"
@@ -252,6 +253,101 @@ __global__ void quick_tf_kernel(const double* __restrict__ pts, int n, int ld, T
     }
 }
 
+// the same for K transforms in one launch: blockIdx.y = k, copy k at out + k * 3 * ldo, exactly quick_tf_kernel's arithmetic per
+// point.  lim (or NULL): [K][6] order-preserving keys of (xmin xmax ymin ymax zmin zmax) -- pcIn.XLimits etc. of
+// pcRandomUniformSamples (:418-432) -- reduced with integer atomics (min / max are exact in any order; NaN never wins)
+__device__ __forceinline__ unsigned long long order_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double order_key_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+__global__ __launch_bounds__(256) void quick_tf_batched_kernel(const double* __restrict__ pts, int n, int ld, const double* __restrict__ T_all,
+                                                               double* __restrict__ out, int ldo, unsigned long long* __restrict__ lim) {
+    const int k = blockIdx.y;
+    double t[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) t[e] = T_all[(size_t)k * 16 + e];
+    double* o = out + (size_t)k * 3 * ldo;
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double x = pts[i], y = pts[i + (size_t)ld], z = pts[i + 2 * (size_t)ld];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double v = ((x * t[4 * j] + y * t[4 * j + 1]) + z * t[4 * j + 2]) + t[4 * j + 3];
+            o[i + (size_t)j * ldo] = v;
+            mn[j] = v < mn[j] ? v : mn[j];
+            mx[j] = v > mx[j] ? v : mx[j];
+        }
+    }
+    if (!lim) return;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        for (int s = 32; s > 0; s >>= 1) {
+            const double a = __shfl_xor(mn[j], s), b = __shfl_xor(mx[j], s);
+            mn[j] = a < mn[j] ? a : mn[j];
+            mx[j] = b > mx[j] ? b : mx[j];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (mn[j] < INFINITY) atomicMin(&lim[(size_t)k * 6 + 2 * j], order_key(mn[j]));
+            if (mx[j] > -INFINITY) atomicMax(&lim[(size_t)k * 6 + 2 * j + 1], order_key(mx[j]));
+        }
+    }
+}
+__global__ void limits_init_kernel(unsigned long long* __restrict__ lim, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 6 * K) lim[i] = (i & 1) ? order_key(-INFINITY) : order_key(INFINITY);
+}
+__global__ void limits_decode_kernel(unsigned long long* __restrict__ lim, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 6 * K) { double* d = (double*)lim; d[i] = order_key_value(lim[i]); }
+}
+
+// :381 [~, best] = max(precisions) (first maximum, NaN skipped, the first index when all are NaN); :383-394 T_refine of the best
+// cluster, pts_Surface_final = quickTF(pts_tform{best}, invertTF(T_refine)), or pts_tform{best} itself when T_refine is empty.
+// Every thread picks (K is a handful); block 0 reports the pick.
+__device__ __forceinline__ int matlab_max_index(const double* __restrict__ p, int K) {
+    int best = -1;
+    for (int k = 0; k < K; ++k) {
+        const double v = p[k];
+        if (v == v && (best < 0 || v > p[best])) best = k;
+    }
+    return best < 0 ? 0 : best;
+}
+__global__ __launch_bounds__(256) void final_pick_apply_kernel(const double* __restrict__ precision, const double* __restrict__ T16,
+                                                               const int32_t* __restrict__ empty, int K, const double* __restrict__ pts_all,
+                                                               int n, int ld, double* __restrict__ out, int ldo, int32_t* __restrict__ best_out) {
+    const int best = matlab_max_index(precision, K);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *best_out = best;
+    const double* src = pts_all + (size_t)best * 3 * ld;
+    if (empty[best]) {
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) out[i + (size_t)j * ldo] = src[i + (size_t)j * ld];
+        }
+        return;
+    }
+    // invertTF.m: TFinv(1:3,1:3) = TF(1:3,1:3)';  TFinv(4,1:3) = -TF(4,1:3) * TF(1:3,1:3)'  (dot products left to right)
+    const double* T = T16 + (size_t)best * 16;                 // column-major: T(r, c) = T[r + 4 c]
+    double u[16];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) u[r + 4 * c] = (r < 3 && c < 3) ? T[c + 4 * r] : (r == c ? 1.0 : 0.0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) u[3 + 4 * j] = ((-T[3] * T[j]) + (-T[7] * T[j + 4])) + (-T[11] * T[j + 8]);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double x = src[i], y = src[i + (size_t)ld], z = src[i + 2 * (size_t)ld];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            out[i + (size_t)j * ldo] = ((x * u[4 * j] + y * u[4 * j + 1]) + z * u[4 * j + 2]) + u[4 * j + 3];
+    }
+}
+
 }  // namespace
 
 int launch_sphere_counts(const double* feat, int V, const double* centres, int S, double R, int32_t* counts, hipStream_t st) {
@@ -327,6 +423,29 @@ int launch_quick_tf(const double* pts, int n, int ld, const double T[16], double
     if (n <= 0) return PCREG_OK;
     TF16 t; for (int k = 0; k < 16; ++k) t.t[k] = T[k];
     hipLaunchKernelGGL(quick_tf_kernel, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, st, pts, n, ld, t, out, ldo);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+int launch_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, hipStream_t st) {
+    if (K <= 0) return PCREG_OK;
+    unsigned long long* lim = (unsigned long long*)limits;
+    const int kb = (6 * K + 255) / 256;
+    if (lim) hipLaunchKernelGGL(limits_init_kernel, dim3(kb), dim3(256), 0, st, lim, K);
+    if (n > 0) {
+        const int gx = std::max(1, std::min((n + 255) / 256, std::max(1, 2048 / K)));
+        hipLaunchKernelGGL(quick_tf_batched_kernel, dim3(gx, K), dim3(256), 0, st, pts, n, ld, T_dev, out, ldo, lim);
+    }
+    if (lim) hipLaunchKernelGGL(limits_decode_kernel, dim3(kb), dim3(256), 0, st, lim, K);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+int launch_final_pick_apply(const double* precision, const double* T16, const int32_t* empty, int K, const double* pts_all, int n, int ld,
+                            double* out, int ldo, int32_t* best, hipStream_t st) {
+    if (K <= 0) return PCREG_OK;
+    hipLaunchKernelGGL(final_pick_apply_kernel, dim3(std::max(1, std::min((n + 255) / 256, 2048))), dim3(256), 0, st, precision, T16, empty, K,
+                       pts_all, n, ld, out, ldo, best);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
