@@ -115,6 +115,9 @@ int launch_calc_dists(const double* T16_dev, const double* p1, const double* p2,
 struct ModelView {
     const float* m; int M, ldm;
     void* prep; unsigned* rm2; float* box_part; void* tiles; int32_t* seed_cnt; void* seed_slots; int seeded;
+    // the rows in spatial order: perm[sorted row] = row of m, an fp32 SoA copy (ld = M), one box per f16 tile; the
+    // ordering grid's counters
+    int32_t* perm; float* ms; float* tbox; int32_t* sort_cnt;
 };
 size_t model_prep_bytes(int M);
 ModelView model_view(const float* m, int M, int ldm, void* block);
@@ -124,6 +127,7 @@ struct SearchWs {
     void* ctr; unsigned* gthr; int32_t* flag_list; int32_t* cand_cnt; void* cand_ent; int cap;
     int32_t* tail_idx; float* tail_dist;
     void* ug_prep; float* ug_part; int32_t* ug_cnt; void* ug_slots; int ug_cells, ug_nparts;
+    int32_t* qcnt; int32_t* qperm; float* dk;          // the call's query order (counters, slot -> query) and seed distances
 };
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes);
 size_t search_ws_bytes(int Q, int M);

@@ -5,16 +5,23 @@
 //
 // The reference matches MANY surfaces against ONE model (completeExperimentFast.m:131-149,201-216), so everything that
 // depends on the model alone is done once (model_prepare):
-//   P1  model_bbox_partial/final_kernel   box of the model -> centre c, power-of-two scale sigma, seeding-grid geometry
-//   P2  prep_model_f16_kernel             model -> tiles of f16 matrix-core operands, R_m^2, and the seeding grid's cells
-// and a search is FOUR launches (round 2: eleven):
-//   S1  seed_query_kernel    a first threshold per query from the model-wide seeding grid; clears the call's counters
-//                            and the candidate lists; per-workgroup boxes of the queries (query grid, below)
-//   S2  knn_candidates_f16_pipe_kernel (knn_mfma16.hip)   all Q x M scores on the matrix cores + selection
-//   S3  knn_finalize_kernel  one 8-lane group per query: exact fmaf-chain distances of the listed candidates,
-//                            (distance, index) top-2, and the CERTIFICATE: every point outside the lists has
+//   P1  model_bbox_partial/final_kernel   box of the model -> centre c, power-of-two scale sigma, seeding- and ordering-grid geometry
+//   P2  model_order_*                     counting sort of the rows by the Morton code of their ordering-grid cell: perm, the
+//                                         sorted fp32 copy the rest is built from
+//   P3  prep_model_f16_kernel             sorted rows -> tiles of f16 matrix-core operands, R_m^2, and the seeding grid's cells
+//   P4  tile_box_kernel                   the exact fp32 box of every tile of kT16 sorted rows
+// and a search is SEVEN launches:
+//   S1  seed_query_kernel    a first threshold per query from the model-wide seeding grid and its seed distance dk; clears
+//                            the call's counters and the candidate lists; per-workgroup boxes of the queries (query grid,
+//                            below); counts the queries per parent cell of the ordering grid (after a memset)
+//   S1b exclusive_scan_1wg_kernel, query_order_kernel   the query SLOTS in spatial order (qperm)
+//   S2  knn_candidates_f16_pipe_kernel (knn_mfma16.hip)   per block of 512 query slots, the scores against every model
+//                            tile the block's box and largest dk cannot rule out, on the matrix cores + selection
+//   S3  knn_finalize_kernel  one 8-lane group per query: exact fmaf-chain distances of the listed candidates over the sorted
+//                            copy, (distance, original index) top-2, and the CERTIFICATE: every point outside the lists has
 //                            s >= G (the final threshold word), hence exact d >= G + |q~|^2 - E; proven answers are
-//                            written, the others are listed; fills the query grid
+//                            written, the others are listed; fills the query grid (a point of a skipped tile is farther
+//                            than two real model points: DESIGN 4.1, culling)
 //   S4  knn_tail_kernel      the listed queries again, exactly: slices of the model per query when few, the tiled
 //                            all-pairs form when many; per-query / per-tile arrival counters let the last workgroup
 //                            merge, so there is no second launch.  Idle (one read) when the list is empty.
@@ -34,12 +41,13 @@
 namespace pcreg {
 
 size_t knn_f16_prep_bytes(int M);
-void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* S, int* tiles_per_chunk);
+void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* W);
 int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsigned* rm2, void* mtiles, int32_t* seed_cnt,
                           void* seed_slots, hipStream_t st);
-int launch_knn_candidates_f16(const float* q, int Q, int ldq, int M, const void* prep, const void* mtiles, unsigned* gthr,
-                              void* cand_ent, int32_t* cand_cnt, int target_blocks, bool dry, bool timed, const float* ug_part,
-                              int ug_nparts, int ug_cells, void* ug_prep, int* S_out, hipStream_t st);
+int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
+                              const void* mtiles, const float* tbox, int cull, unsigned* gthr, void* cand_ent, int32_t* cand_cnt,
+                              void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part, int ug_nparts, int ug_cells,
+                              void* ug_prep, int* W_out, hipStream_t st);
 
 namespace {
 
@@ -115,8 +123,86 @@ __global__ void model_bbox_final_kernel(const float* __restrict__ part, int npar
         }
         prep->gx0 = g0[0]; prep->gy0 = g0[1]; prep->gz0 = g0[2]; prep->inv_h = 1.0f / h;
         prep->nx = n[0]; prep->ny = n[1]; prep->nz = n[2]; prep->ncell = n[0] * n[1] * n[2];
+        // ordering grid: cubic cells, 2^kSortBits along the longest side (a flat axis gets fewer)
+        prep->sx0 = lo[0]; prep->sy0 = lo[1]; prep->sz0 = lo[2];
+        prep->inv_s = (emax > 0.0f && emax < INFINITY) ? (float)(1 << kSortBits) / emax : 0.0f;
         *rm2_bits = 0u;
     }
+}
+
+// ---- P2 / S1b. counting sort by ordering-grid cell (as descriptors.hip builds its grid: count, scan, scatter) -------
+// The scatter takes places inside a cell by atomics, so the order inside a cell varies from run to run; nothing but the
+// set of tiles a query block visits depends on it (ties are ordered by ORIGINAL row: knn_finalize_kernel).
+__global__ __launch_bounds__(kBlock) void model_order_count_kernel(const float* __restrict__ m, int M, int ldm, const Prep* __restrict__ prep,
+                                                                   int32_t* __restrict__ cnt) {
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < M; i += gridDim.x * kBlock)
+        atomicAdd(&cnt[sort_key(m[i], m[i + (size_t)ldm], m[i + 2 * (size_t)ldm], prep)], 1);
+}
+// in place, ONE workgroup of 1024: thread t owns n / 1024 consecutive counters (n a multiple of 4096)
+__global__ __launch_bounds__(1024) void exclusive_scan_1wg_kernel(int32_t* __restrict__ a, int n) {
+    __shared__ int s_w[16];
+    const int per4 = n / 4096, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int4* p = (int4*)a + (size_t)threadIdx.x * per4;
+    int sum = 0;
+#pragma unroll 8
+    for (int k = 0; k < per4; ++k) { const int4 v = p[k]; sum += v.x + v.y + v.z + v.w; }      // eight loads in flight
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o); if (lane >= o) inc += y; }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int k = 0; k < wave; ++k) run += s_w[k];
+#pragma unroll 8
+    for (int k = 0; k < per4; ++k) {
+        const int4 v = p[k];
+        int4 o;
+        o.x = run; run += v.x; o.y = run; run += v.y; o.z = run; run += v.z; o.w = run; run += v.w;
+        p[k] = o;
+    }
+}
+__global__ __launch_bounds__(kBlock) void model_order_scatter_kernel(const float* __restrict__ m, int M, int ldm, const Prep* __restrict__ prep,
+                                                                     int32_t* __restrict__ off, int32_t* __restrict__ perm, float* __restrict__ ms) {
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < M; i += gridDim.x * kBlock) {
+        const float x = m[i], y = m[i + (size_t)ldm], z = m[i + 2 * (size_t)ldm];
+        const int d = atomicAdd(&off[sort_key(x, y, z, prep)], 1);
+        perm[d] = i; ms[d] = x; ms[d + (size_t)M] = y; ms[d + 2 * (size_t)M] = z;
+    }
+}
+// P4: the exact box of each tile of kT16 sorted rows (padding rows excluded); one workgroup per tile
+__global__ __launch_bounds__(kBlock) void tile_box_kernel(const float* __restrict__ ms, int M, float* __restrict__ tbox) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int r = threadIdx.x; r < kT16; r += kBlock) {
+        const int i = blockIdx.x * kT16 + r;
+        if (i < M) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { const float v = ms[i + (size_t)c * M]; lo[c] = fminf(lo[c], v); hi[c] = fmaxf(hi[c], v); }
+        }
+    }
+    __shared__ float s[kBlock / 64][6];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], o)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], o)); }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s[threadIdx.x >> 6][c] = lo[c]; s[threadIdx.x >> 6][3 + c] = hi[c]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float v = s[0][threadIdx.x];
+        for (int w = 1; w < kBlock / 64; ++w) v = threadIdx.x < 3 ? fminf(v, s[w][threadIdx.x]) : fmaxf(v, s[w][threadIdx.x]);
+        tbox[(size_t)blockIdx.x * 6 + threadIdx.x] = v;
+    }
+}
+// S1b: query slot of every query (the counts come from seed_query_kernel, scanned in place)
+__global__ __launch_bounds__(kBlock) void query_order_kernel(const float* __restrict__ q, int Q, int ldq, const Prep* __restrict__ prep,
+                                                             int32_t* __restrict__ off, int32_t* __restrict__ qperm) {
+    const int qi = blockIdx.x * kBlock + threadIdx.x;
+    if (qi >= Q) return;
+    const int key = sort_key(q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq], prep) >> 3;
+    qperm[atomicAdd(&off[key], 1)] = qi;
 }
 
 // ---- S1. seeding: a first threshold per query from the model-wide grid ------------------------------------------
@@ -143,7 +229,8 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
                                                             const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
                                                             const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
                                                             int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
-                                                            float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells) {
+                                                            float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells,
+                                                            float* __restrict__ dk_out, int32_t* __restrict__ qcnt) {
     // housekeeping for the launches that follow
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < (int)(sizeof(SearchCounters) / 4); i += gridDim.x * kBlock) ((int32_t*)ctr)[i] = 0;
     if (ug_cnt) for (int i = blockIdx.x * kBlock + threadIdx.x; i < ug_cells; i += gridDim.x * kBlock) ug_cnt[i] = 0;
@@ -170,8 +257,11 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
             ug_part[(size_t)blockIdx.x * 6 + threadIdx.x] = r;
         }
     }
-    if (live && sub == 0) cand_cnt[qi] = 0;                   // the query's candidate list starts empty
-    if (!seeded) { if (live && sub == 0) gthr[qi] = 0xFFFFFFFFu; return; }       // +inf: no hint
+    if (live && sub == 0) {
+        cand_cnt[qi] = 0;                                     // the query's candidate list starts empty
+        if (qcnt) atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);     // the query order's counts
+    }
+    if (!seeded) { if (live && sub == 0) { gthr[qi] = 0xFFFFFFFFu; dk_out[qi] = INFINITY; } return; }       // +inf: no hint
     const int nx = prep->nx, ny = prep->ny, nz = prep->nz;
     const int cx = seed_cell(qx, prep->gx0, prep->inv_h, nx), cy = seed_cell(qy, prep->gy0, prep->inv_h, ny), cz = seed_cell(qz, prep->gz0, prep->inv_h, nz);
     float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -221,18 +311,21 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
         word = f2ord(nextafterf((float)t, INFINITY));
     }
     gthr[qi] = word;
+    dk_out[qi] = dk;                   // the distance itself: two real model points lie within dk of the query (culling)
 }
 
 // ---- S3. exact re-rank + certificate: one 8-lane group per query --------------------------------------------------
 __device__ __forceinline__ bool lex_lt_f(float da, int ia, float db, int ib) {
     return da < db || (da == db && (unsigned)ia < (unsigned)ib);
 }
-// A list entry is (first row jb, minimum score) of the 16 model points jb + 8 (r / 4) + r % 4, r = 0..15, that one lane
-// of knn_candidates_f16_pipe_kernel scored together; pass 2 expands every entry that can still matter.  Points past M
-// (tile padding) are skipped.  A query's list: cand_cnt[qi] entries at ent[(size_t)qi * cap + e].
+// A list entry is (first sorted row jb, minimum score) of the 16 model points jb + 8 (r / 4) + r % 4, r = 0..15, that one
+// lane of knn_candidates_f16_pipe_kernel scored together; pass 2 expands every entry that can still matter over the
+// sorted copy ms (ld = M) and ranks by (distance, ORIGINAL row perm[jj]), so the lowest-row tie rule holds whatever tile
+// a point was sorted into.  Points past M (tile padding) are skipped.  A query's list: cand_cnt[qi] entries at
+// ent[(size_t)qi * cap + e].
 constexpr int LPQ = 8;
 __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
-    const float* __restrict__ q, int Q, int ldq, const float* __restrict__ m, int M, int ldm,
+    const float* __restrict__ q, int Q, int ldq, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm,
     const Prep* __restrict__ prep, const unsigned* __restrict__ rm2_bits, const unsigned* __restrict__ gthr,
     const uint2* __restrict__ ent_all, const int32_t* __restrict__ cand_cnt, int cap, int idx_base,
     int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ flag_list, int32_t* __restrict__ n_flag,
@@ -286,10 +379,11 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
             for (int rr = 0; rr < 16; ++rr) {
                 const int jj = j + 8 * (rr >> 2) + (rr & 3);
                 if (jj >= M) continue;
-                float dx = qx - m[jj], dy = qy - m[jj + (size_t)ldm], dz = qz - m[jj + 2 * (size_t)ldm];
+                float dx = qx - ms[jj], dy = qy - ms[jj + (size_t)M], dz = qz - ms[jj + 2 * (size_t)M];
                 float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                if (lex_lt_f(d, jj, d2, i2)) {
-                    if (lex_lt_f(d, jj, d1, i1)) { d2 = d1; i2 = i1; d1 = d; i1 = jj; } else { d2 = d; i2 = jj; }
+                const int oj = perm[jj];
+                if (lex_lt_f(d, oj, d2, i2)) {
+                    if (lex_lt_f(d, oj, d1, i1)) { d2 = d1; i2 = i1; d1 = d; i1 = oj; } else { d2 = d; i2 = oj; }
                 }
             }
         }
@@ -517,10 +611,14 @@ size_t seed_cell_cap(int M) { return std::min<size_t>((size_t)kSeedMaxCells, std
 }  // namespace
 
 // ---- a prepared model in device memory ---------------------------------------------------------------------------
-// layout of the prepared block: Prep | R_m^2 bits | box partials | f16 tiles | seeding-grid counters | seeding-grid slots
+// layout of the prepared block: Prep | R_m^2 bits | box partials | f16 tiles | ordering-grid counters | seeding-grid
+// counters | seeding-grid slots | perm | sorted fp32 copy | tile boxes  (the two counter arrays adjoin: one clear)
+static size_t n_f16_tiles(int M) { return (size_t)((M > 0 ? M : 0) + kT16 - 1) / kT16; }
 size_t model_prep_bytes(int M) {
-    size_t b = 256 + 256 + align_up(512 * 6 * sizeof(float), 256) + align_up(knn_f16_prep_bytes(M), 256);
+    const size_t mm = (size_t)(M > 0 ? M : 1);
+    size_t b = 256 + 256 + align_up(512 * 6 * sizeof(float), 256) + align_up(knn_f16_prep_bytes(M), 256) + (size_t)kSortKeys * 4;
     if (M >= kSeedMinM) b += align_up(seed_cell_cap(M) * 4, 256) + align_up(seed_cell_cap(M) * kSeedSlots * 16, 256);
+    b += align_up(mm * 4, 256) + align_up(mm * 12, 256) + align_up(std::max<size_t>(n_f16_tiles(M), 1) * 24, 256);
     return b;
 }
 ModelView model_view(const float* m, int M, int ldm, void* block) {
@@ -531,11 +629,16 @@ ModelView model_view(const float* m, int M, int ldm, void* block) {
     v.rm2 = (unsigned*)w; w += 256;
     v.box_part = (float*)w; w += align_up(512 * 6 * sizeof(float), 256);
     v.tiles = w; w += align_up(knn_f16_prep_bytes(M), 256);
+    v.sort_cnt = (int32_t*)w; w += (size_t)kSortKeys * 4;
     v.seeded = M >= kSeedMinM && PCREG_EXP_ENV("PCREG_KNN_NOSEED", 0) == 0;
     if (M >= kSeedMinM) {
         v.seed_cnt = (int32_t*)w; w += align_up(seed_cell_cap(M) * 4, 256);
-        v.seed_slots = w;
+        v.seed_slots = w; w += align_up(seed_cell_cap(M) * kSeedSlots * 16, 256);
     }
+    const size_t mm = (size_t)(M > 0 ? M : 1);
+    v.perm = (int32_t*)w; w += align_up(mm * 4, 256);
+    v.ms = (float*)w; w += align_up(mm * 12, 256);
+    v.tbox = (float*)w;
     return v;
 }
 // enqueue the two preparation passes (P1, P2) on `st`
@@ -543,11 +646,20 @@ int launch_model_prepare(const ModelView& v, hipStream_t st) {
     PCREG_ARG(v.M >= 0 && v.ldm >= v.M);
     if (v.M == 0) return PCREG_OK;
     int nb = (v.M + kBlock * 16 - 1) / (kBlock * 16); if (nb > 512) nb = 512; if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(model_bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, v.m, v.M, v.ldm, v.box_part, v.seed_cnt,
-                       v.seeded ? (int)seed_cell_cap(v.M) : 0);
+    hipLaunchKernelGGL(model_bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, v.m, v.M, v.ldm, v.box_part, v.sort_cnt,
+                       kSortKeys + (v.seeded ? (int)seed_cell_cap(v.M) : 0));
     hipLaunchKernelGGL(model_bbox_final_kernel, dim3(1), dim3(64), 0, st, v.box_part, nb, v.M, (int)seed_cell_cap(v.M), (Prep*)v.prep, v.rm2);
+    // the rows in Morton order of their ordering-grid cells; everything below is built from the sorted copy
+    int ob = (v.M + kBlock * 4 - 1) / (kBlock * 4); if (ob > 2048) ob = 2048;
+    hipLaunchKernelGGL(model_order_count_kernel, dim3(ob), dim3(kBlock), 0, st, v.m, v.M, v.ldm, (const Prep*)v.prep, v.sort_cnt);
+    hipLaunchKernelGGL(exclusive_scan_1wg_kernel, dim3(1), dim3(1024), 0, st, v.sort_cnt, kSortKeys);
+    hipLaunchKernelGGL(model_order_scatter_kernel, dim3(ob), dim3(kBlock), 0, st, v.m, v.M, v.ldm, (const Prep*)v.prep, v.sort_cnt, v.perm, v.ms);
     PCREG_HIP(hipGetLastError());
-    return launch_prep_model_f16(v.m, v.M, v.ldm, v.prep, v.rm2, v.tiles, v.seeded ? v.seed_cnt : nullptr, v.seed_slots, st);
+    int rc = launch_prep_model_f16(v.ms, v.M, v.M, v.prep, v.rm2, v.tiles, v.seeded ? v.seed_cnt : nullptr, v.seed_slots, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)n_f16_tiles(v.M)), dim3(kBlock), 0, st, (const float*)v.ms, v.M, v.tbox);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
 }
 
 // ---- the per-call workspace of a search (and of the match stage that follows it) ----------------------------------
@@ -555,9 +667,9 @@ static constexpr int kTargetBlocks = 4096;
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     SearchWs s{};
     const size_t qq = (size_t)(Q > 0 ? Q : 1);
-    int q_blocks, S, tpc;
-    knn_f16_shape(Q > 0 ? Q : 1, M > 0 ? M : 1, kTargetBlocks, &q_blocks, &S, &tpc);
-    s.cap = S * KC;
+    int q_blocks, W;
+    knn_f16_shape(Q > 0 ? Q : 1, M > 0 ? M : 1, kTargetBlocks, &q_blocks, &W);
+    s.cap = W * KC;
     char* w = (char*)base;
     s.ctr = w; w += align_up(sizeof(SearchCounters), 256);
     s.gthr = (unsigned*)w; w += align_up(qq * 4, 256);
@@ -573,6 +685,9 @@ SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     s.ug_part = (float*)w; w += align_up((size_t)s.ug_nparts * 6 * 4, 256);
     s.ug_cnt = (int32_t*)w; w += align_up((size_t)s.ug_cells * 4, 256);
     s.ug_slots = w; w += align_up((size_t)s.ug_cells * kUgSlots * 16, 256);
+    s.qcnt = (int32_t*)w; w += (size_t)kQueryKeys * 4;
+    s.qperm = (int32_t*)w; w += align_up(qq * 4, 256);
+    s.dk = (float*)w; w += align_up(qq * 4, 256);
     *bytes = (size_t)(w - (char*)base);
     return s;
 }
@@ -588,23 +703,36 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     if (ws_bytes < need) { set_error("search workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
     SearchCounters* ctr = (SearchCounters*)s.ctr;
     const bool grid = with_grid && v.M > 0;          // (an empty model matches nothing: the match stage never looks at the grid)
+    const bool order = v.M > 0;                      // (an empty model: no prepared block, no candidate launch)
+    if (order) PCREG_HIP(hipMemsetAsync(s.qcnt, 0, (size_t)kQueryKeys * 4, st));
     hipLaunchKernelGGL(seed_query_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, (const int32_t*)v.seed_cnt,
                        (const float4*)v.seed_slots, (v.seeded && v.M > 0) ? 1 : 0, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr,
-                       grid ? s.ug_cnt : nullptr, s.ug_cells);
-    int S = 1;
+                       grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr);
+    if (order) {
+        hipLaunchKernelGGL(exclusive_scan_1wg_kernel, dim3(1), dim3(1024), 0, st, s.qcnt, kQueryKeys);
+        hipLaunchKernelGGL(query_order_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, s.qcnt, s.qperm);
+    }
+    int W = 1;
     const int variant = PCREG_EXP_ENV("PCREG_KNN_VARIANT", 40);      // 41: timing-only form of the candidate kernel (EXPERIMENTS builds)
-    const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS chunks)
-    int rc = launch_knn_candidates_f16(q, Q, ldq, v.M, v.prep, v.tiles, s.gthr, s.cand_ent, s.cand_cnt, target_env > 0 ? target_env : kTargetBlocks,
-                                       variant == 41, timed, grid ? s.ug_part : nullptr, s.ug_nparts, s.ug_cells, grid ? s.ug_prep : nullptr, &S, st);
+    const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS workgroups)
+    const int cull = PCREG_EXP_ENV("PCREG_KNN_NOCULL", 0) ? 0 : 1;    // EXPERIMENTS builds: visit every tile (A/B of the culling)
+    int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, cull, s.gthr, s.cand_ent, s.cand_cnt, ctr,
+                                       target_env > 0 ? target_env : kTargetBlocks, variant == 41, timed, grid ? s.ug_part : nullptr,
+                                       s.ug_nparts, s.ug_cells, grid ? s.ug_prep : nullptr, &W, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((Q + kBlock / LPQ - 1) / (kBlock / LPQ)), dim3(kBlock), 0, st, q, Q, ldq, v.m, v.M, v.ldm,
-                       (const Prep*)v.prep, (const unsigned*)v.rm2, (const unsigned*)s.gthr, (const uint2*)s.cand_ent, (const int32_t*)s.cand_cnt,
-                       S * KC, (int)idx_base, idx, dist, s.flag_list, &ctr->n_flag, grid ? (const UgPrep*)s.ug_prep : nullptr,
-                       s.ug_cnt, (float4*)s.ug_slots);
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((Q + kBlock / LPQ - 1) / (kBlock / LPQ)), dim3(kBlock), 0, st, q, Q, ldq, (const float*)v.ms, v.M,
+                       (const int32_t*)v.perm, (const Prep*)v.prep, (const unsigned*)v.rm2, (const unsigned*)s.gthr, (const uint2*)s.cand_ent,
+                       (const int32_t*)s.cand_cnt, W * KC, (int)idx_base, idx, dist, s.flag_list, &ctr->n_flag,
+                       grid ? (const UgPrep*)s.ug_prep : nullptr, s.ug_cnt, (float4*)s.ug_slots);
     if (PCREG_EXP_ENV("PCREG_KNN_DEBUG", 0)) {
-        int32_t nf = 0;
-        PCREG_HIP(hipMemcpyAsync(&nf, &ctr->n_flag, 4, hipMemcpyDeviceToHost, st)); PCREG_HIP(hipStreamSynchronize(st));
-        fprintf(stderr, "[pcreg] knn fast: Q=%d M=%d S=%d unproven=%d\n", Q, v.M, S, nf);
+        int32_t nf = 0, vis[kVisitSlots];
+        PCREG_HIP(hipMemcpyAsync(&nf, &ctr->n_flag, 4, hipMemcpyDeviceToHost, st));
+        PCREG_HIP(hipMemcpyAsync(vis, ctr->visited, sizeof(vis), hipMemcpyDeviceToHost, st)); PCREG_HIP(hipStreamSynchronize(st));
+        long long nv = 0;
+        for (int k = 0; k < kVisitSlots; ++k) nv += vis[k];
+        const long long qb = (Q + 511) / 512, nt = (long long)n_f16_tiles(v.M);
+        fprintf(stderr, "[pcreg] knn fast: Q=%d M=%d W=%d unproven=%d visited tile pairs=%lld of %lld (%.4f)%s\n", Q, v.M, W, nf, nv, qb * nt,
+                qb * nt > 0 ? (double)nv / (double)(qb * nt) : 0.0, cull ? "" : " (culling off)");
     }
     hipLaunchKernelGGL(knn_tail_kernel, dim3(kTailGrid), dim3(kBlock), 0, st, q, ldq, v.m, v.M, v.ldm, (int)idx_base, (const int32_t*)s.flag_list, ctr,
                        s.tail_idx, s.tail_dist, idx, dist);

@@ -10,13 +10,17 @@ constexpr int kBlock = 256;
 #ifndef PCREG_KC
 #define PCREG_KC 4
 #endif
-constexpr int KC = PCREG_KC;                 // group entries kept per lane, query and chunk (>= 2: the two nearest points sit in the two best groups)
+constexpr int KC = PCREG_KC;                 // group entries kept per lane, query and workgroup (>= 2: the two nearest points sit in the two best groups)
 #ifndef PCREG_SEED_RANK
 #define PCREG_SEED_RANK 2
 #endif
 constexpr int kSeedRank = PCREG_SEED_RANK;   // the first threshold: the kSeedRank-th smallest exact distance among the seeding grid's points (>= 2;
                                              // 2 is the tightest valid hint: -1.3 % on the candidates kernel against 4, interleaved A/B in round 3)
 constexpr int kMTile = 1024;                 // model points per LDS tile (16 KiB)
+#ifndef PCREG_KT16
+#define PCREG_KT16 512
+#endif
+constexpr int kT16 = PCREG_KT16;              // model points per f16 tile: [2 k-halves][512 points][8 f16] = 16 KiB (768 / 1024 measured in round 3: docs/NOTES_r01_r03.md 4.1)
 
 // What a PREPARED MODEL carries besides its f16 tiles (model-only quantities: one model, many query sets --
 // completeExperimentFast.m:131-149): the centre of the model's bounding box, the power-of-two scale that brings its
@@ -25,11 +29,32 @@ struct Prep {
     float cx, cy, cz, rm2, sigma, inv_sigma2, pad0, pad1;
     float gx0, gy0, gz0, inv_h;                  // seeding grid over the model's bounding box plus one cell of margin
     int nx, ny, nz, ncell;
+    float sx0, sy0, sz0, inv_s;                  // ordering grid: 2^kSortBits cubic cells along the box's longest side
 };
+// The prepared model's rows are stored in Morton order of the ordering grid's cells, so that each f16 tile of kT16 rows is
+// compact in space; the queries of a search call are ordered by the parent cells (kSortBits - 1 bits per axis).  The order
+// only decides which (query block, tile) pairs the candidate kernel can prove useless; no result depends on it.
+constexpr int kSortBits = 6;
+constexpr int kSortKeys = 1 << (3 * kSortBits);
+constexpr int kQueryKeys = kSortKeys >> 3;
+__device__ __forceinline__ unsigned morton_spread(unsigned v) {           // bits 0..9 -> bits 0, 3, 6, ..
+    v &= 0x3FFu;
+    v = (v | (v << 16)) & 0x030000FFu; v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u; v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+__device__ __forceinline__ int sort_key(float x, float y, float z, const Prep* __restrict__ p) {
+    const float top = (float)((1 << kSortBits) - 1);
+    // clamped into the grid before the conversion (NaN -> 0: fmaxf returns the number)
+    const unsigned ix = (unsigned)fminf(fmaxf(floorf((x - p->sx0) * p->inv_s), 0.0f), top);
+    const unsigned iy = (unsigned)fminf(fmaxf(floorf((y - p->sy0) * p->inv_s), 0.0f), top);
+    const unsigned iz = (unsigned)fminf(fmaxf(floorf((z - p->sz0) * p->inv_s), 0.0f), top);
+    return (int)(morton_spread(ix) | (morton_spread(iy) << 1) | (morton_spread(iz) << 2));
+}
 // A query whose scaled coordinate leaves this range is not scored on the matrix cores (its f16 operands would
 // overflow or lose the error bound's assumptions): it goes to the exact fallback.
 constexpr float kQueryScaledMax = 16384.0f;
-constexpr int kF16MaxS = 80;                      // most model chunks the f16 candidate kernel is split in
+constexpr int kF16MaxS = 80;                      // most workgroups per query block of the f16 candidate kernel (a multiple of 8)
 constexpr int kSeedSlots = 4;                    // model points remembered per grid cell
 constexpr int kSeedMaxCells = 1 << 21;
 
@@ -85,11 +110,13 @@ __device__ __forceinline__ void ug_make_prep(const float lo[3], const float hi[3
 // the small counters of one search call (+ the match stage that follows it), cleared by seed_query_kernel
 constexpr int kMaxQTiles = 4096;                 // tiles of 1024 queries: Q <= 4 Mi per call
 constexpr int kMatchMaxBlocks = 2048;
+constexpr int kVisitSlots = 32;
 struct SearchCounters {
     int32_t n_flag;                  // unproven queries (knn_finalize_kernel -> knn_tail_kernel)
     int32_t ticket;                  // match_finish_kernel's workgroup tickets
     int32_t finished;                // ... and how many of its workgroups are through (the last one clears ticket / status again)
-    int32_t pad[61];
+    int32_t pad[29];
+    int32_t visited[kVisitSlots];    // (query block, model tile) pairs the candidate kernel scored, spread over words by workgroup
     int32_t done[kMaxQTiles];        // tail: arrivals per listed query (few) or per tile of listed queries (many)
     int32_t status[kMatchMaxBlocks]; // match_finish_kernel: per-workgroup kept counts (ready bit 31)
 };

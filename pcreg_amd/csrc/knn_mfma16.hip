@@ -35,10 +35,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef PCREG_KT16
-#define PCREG_KT16 512
-#endif
-constexpr int kT16 = PCREG_KT16;              // model points per tile: [2 k-halves][512 points][8 f16] = 16 KiB (768 / 1024 measured in round 3: see DESIGN 4.1)
 #ifndef PCREG_KREFRESH
 #define PCREG_KREFRESH 16
 #endif
@@ -159,21 +155,24 @@ __device__ void ug_reduce_boxes(const float* __restrict__ part /*[n][6]*/, int n
 // cross the back edge (tests/test_isa_lint.py checks the emitted ISA for a VGPR read between load and wait).
 template <int QG, bool DRY>   // DRY: timing only (no compare, no lists; PCREG_KNN_VARIANT=41)
 __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2 ? 5 : (QG <= 4 ? 4 : 2)))) void knn_candidates_f16_pipe_kernel(
-    const float* __restrict__ q, int Q, int ldq, const uint4* __restrict__ mt, int n_tiles, int tiles_per_chunk,
+    const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm, const float* __restrict__ dk,
+    const uint4* __restrict__ mt, const float* __restrict__ tbox, int n_tiles, int W, int cull,
     const Prep* __restrict__ prep, unsigned* __restrict__ gthr, uint2* __restrict__ cand_ent, int32_t* __restrict__ cand_cnt,
-    int cap, int q_blocks, int xcd_map, int n_chunks, const float* __restrict__ ug_part, int ug_nparts, int ug_cells, UgPrep* __restrict__ ug_prep) {
+    int cap, SearchCounters* __restrict__ ctr, const float* __restrict__ ug_part, int ug_nparts, int ug_cells, UgPrep* __restrict__ ug_prep) {
     static_assert(QG % 2 == 0, "two accumulator tiles alternate: an even number of steps per sub-tile");
     if (blockIdx.x == gridDim.x - 1 && ug_prep != nullptr) {     // the surplus workgroup (the launcher adds it): query-grid geometry
         ug_reduce_boxes(ug_part, ug_nparts, Q, ug_cells, ug_prep);
         return;
     }
     __shared__ __attribute__((aligned(16))) uint4 tile[2][2 * kT16];
+    __shared__ float s_red[kBlock / 64][8], s_box[8];
+    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, half = lane >> 5;
-    int qb, chunk;
-    if (xcd_map) { const int j = (int)blockIdx.x >> 3; chunk = (j / q_blocks) * 8 + ((int)blockIdx.x & 7); qb = j % q_blocks; }
-    else { qb = (int)blockIdx.x % q_blocks; chunk = (int)blockIdx.x / q_blocks; }
-    if (chunk >= n_chunks) return;            // the grid rounds the chunk count up to a multiple of 8 for the XCD map
+    // workgroup w of query block qb walks the block's visited tiles among w, w + W, w + 2W, ..  (W is a multiple of 8 from
+    // 8 on: workgroup b runs on XCD b % 8, so with nothing culled an XCD reads one eighth of the model, as the chunks did)
+    const int qb = (int)blockIdx.x / W, w = (int)blockIdx.x % W;
+    // query SLOTS: the call's queries in spatial order (qperm), so that the 512 slots of a block are compact in space
     const int q_base = (qb * (kBlock / 64) + wave) * (QG * 32);
     const float sg = prep->sigma, inv2 = prep->inv_sigma2, sg2 = sg * sg;
 
@@ -181,16 +180,23 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
     float thr[QG];
     unsigned gseen[QG];
     Cand cand[QG];
+    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY}, bdk = 0.0f;
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        const int qi = q_base + g * 32 + col;
+        const int slot = q_base + g * 32 + col;
         float X = 0.0f, Y = 0.0f, Z = 0.0f, one = 0.0f;
-        if (qi < Q) {
-            const float sx = sg * (q[qi] - prep->cx), sy = sg * (q[qi + (size_t)ldq] - prep->cy), sz = sg * (q[qi + 2 * (size_t)ldq] - prep->cz);
+        if (slot < Q) {
+            const int qi = qperm[slot];
+            const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
+            const float sx = sg * (px - prep->cx), sy = sg * (py - prep->cy), sz = sg * (pz - prep->cz);
             // a query far outside the prepared model's box (or not finite) is not scored here: all-zero operands, no list
             // entries; knn_finalize_kernel applies the same test and sends it to the exact fallback
             if (fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
                 X = -2.0f * sx; Y = -2.0f * sy; Z = -2.0f * sz; one = 1.0f;
+                blo[0] = fminf(blo[0], px); blo[1] = fminf(blo[1], py); blo[2] = fminf(blo[2], pz);
+                bhi[0] = fmaxf(bhi[0], px); bhi[1] = fmaxf(bhi[1], py); bhi[2] = fmaxf(bhi[2], pz);
+                const float e = dk[qi];
+                bdk = e < INFINITY ? fmaxf(bdk, e) : INFINITY;         // an unseeded query turns culling off for the block
             }
         }
         _Float16 Xh, Xl, Yh, Yl, Zh, Zl;
@@ -201,27 +207,80 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         for (int k = 0; k < KC; ++k) { cand[g].s[k] = INFINITY; cand[g].i[k] = -1; }
         thr[g] = INFINITY; gseen[g] = 0xFFFFFFFFu;
     }
+    // the block's box and largest seed distance over its SCORED queries (culling); every workgroup of the
+    // block reduces the same 512 queries to the same values
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { blo[c] = fminf(blo[c], __shfl_xor(blo[c], o)); bhi[c] = fmaxf(bhi[c], __shfl_xor(bhi[c], o)); }
+        bdk = fmaxf(bdk, __shfl_xor(bdk, o));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s_red[wave][c] = blo[c]; s_red[wave][3 + c] = bhi[c]; }
+        s_red[wave][6] = bdk;
+    }
+    __syncthreads();
+    if (tid < 7) {                                // the block's values stay in LDS: registers are full in the hot loop
+        float v = s_red[0][tid];
+#pragma unroll
+        for (int k = 1; k < kBlock / 64; ++k) v = tid < 3 ? fminf(v, s_red[k][tid]) : fmaxf(v, s_red[k][tid]);
+        s_box[tid] = v;
+    }
+    __syncthreads();
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)&tile[0][0];
-    const int t_begin = chunk * tiles_per_chunk, t_end = min(n_tiles, t_begin + tiles_per_chunk);
-    const int ntile = t_end - t_begin;
+    int walked = 0;                               // tiles walked so far (the threshold refresh's cadence)
+    const f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    constexpr int kSubs = kT16 / 32;
 #define PCREG_TILE_DMA(T, BUF)                                                                                     \
     _Pragma("unroll") for (int k = 0; k < kT16 / 128; ++k) {                                                        \
         const int seg = k * 4 + wave;                                                                              \
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mt + (size_t)(T) * (2 * kT16) + seg * 64 + lane), \
                                          (__attribute__((address_space(3))) void*)(&tile[BUF][seg * 64]), 16, 0, 0);   \
     }
-    if (ntile > 0) { PCREG_TILE_DMA(t_begin, 0) }
+    // rounds of kBlock candidate tiles: each thread tests one, the visited ones are listed in LDS in ascending order
+    for (int c0 = w; c0 < n_tiles; c0 += W * kBlock) {
+    {
+        const int ct = c0 + W * tid;
+        bool visit = ct < n_tiles;
+        const float bdk_b = s_box[6];
+        if (visit && cull != 0 && bdk_b < INFINITY) {
+            // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to
+            // any point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of
+            // 32u, and no bound at all below 1e-30 (subnormal squares)
+            const float* bx = tbox + (size_t)ct * 6;
+            double g2 = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
+                g2 += gap * gap;
+            }
+            const double u = 5.9604644775390625e-08;
+            if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b) visit = false;
+        }
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
+        if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
+        __syncthreads();
+        int base = 0;
+#pragma unroll
+        for (int k = 0; k < kBlock / 64; ++k) base += k < wave ? s_wcnt[k] : 0;
+        if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
+    }
+    __syncthreads();
+    const int ntile = __builtin_amdgcn_readfirstlane(s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3]);
+    if (tid == 0 && ntile > 0) atomicAdd(&ctr->visited[blockIdx.x % kVisitSlots], ntile);
+    if (ntile > 0) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[0]), 0) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    const f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    constexpr int kSubs = kT16 / 32;
-    for (int t = 0; t < ntile; ++t) {
-        if (t + 1 < ntile) { PCREG_TILE_DMA(t_begin + t + 1, (t + 1) & 1) }
-        if ((t & (kRefresh - 1)) == 0) {          // chunks share one monotone threshold word per query (unscaled units)
+    for (int t = 0; t < ntile; ++t, ++walked) {
+        const int tcur = __builtin_amdgcn_readfirstlane(s_list[t]);
+        if (t + 1 < ntile) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[t + 1]), (t + 1) & 1) }
+        if ((walked & (kRefresh - 1)) == 0) {     // the block's workgroups share one monotone threshold word per query (unscaled units)
 #pragma unroll
             for (int g = 0; g < QG; ++g) {
-                const int qi = q_base + g * 32 + col;
-                if (qi < Q) {
+                const int slot = q_base + g * 32 + col;
+                if (slot < Q) {
+                    const int qi = qperm[slot];
                     if (cand[g].s[KC - 1] < INFINITY) { unsigned k = f2ord(cand[g].s[KC - 1] * inv2); if (k < gseen[g]) atomicMin(&gthr[qi], k); }
                     unsigned gv = __hip_atomic_load(&gthr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     gseen[g] = gv;
@@ -230,7 +289,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
             }
         }
         const unsigned cur = lds_base + (unsigned)((t & 1) * (2 * kT16) + half * kT16 + col) * 16u;
-        const int jt = (t_begin + t) * kT16 + 4 * half;
+        const int jt = tcur * kT16 + 4 * half;
         f16x8 av;
         {
             u32x4 a0;
@@ -314,13 +373,14 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
+    }
 #undef PCREG_TILE_DMA
     // The two half-waves of a query (lanes l and l ^ 32) merge their sorted fours in registers and lane l < 32
-    // writes ONE list of at most four GROUP entries per (chunk, query); the merged 4th-best is published too, so
+    // writes ONE list of at most four GROUP entries per (workgroup, query); the merged 4th-best is published too, so
     // every group dropped here still has a minimum >= the final threshold word G.
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        const int qi = q_base + g * 32 + col;
+        const int slot = q_base + g * 32 + col;
         Cand mine = cand[g];
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
@@ -336,7 +396,8 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
                 for (int t = 0; t < KC; ++t) if (t == pos) { mine.s[t] = os; mine.i[t] = oi; }
             }
         }
-        if (qi < Q && half == 0) {
+        if (slot < Q && half == 0 && mine.i[0] >= 0) {
+            const int qi = qperm[slot];
             if (mine.s[KC - 1] < INFINITY) { unsigned k = f2ord(mine.s[KC - 1] * inv2); if (k < gseen[g]) atomicMin(&gthr[qi], k); }
             int nv = 0;
 #pragma unroll
@@ -375,18 +436,19 @@ int knn_f16_timing_read(float* mean_ms, int* launches) {
 
 size_t knn_f16_prep_bytes(int M) { return (size_t)((M > 0 ? M : 1) + kT16 - 1) / kT16 * (2 * kT16) * sizeof(uint4); }
 
-// the launch shape of the candidate kernel for Q queries against M model rows: q_blocks x S workgroups (+ surplus);
-// a (chunk, query) pair lists at most KC group entries, so a query's list holds at most S * KC
-void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* S, int* tiles_per_chunk) {
+// the launch shape of the candidate kernel for Q queries against M model rows: q_blocks query blocks of 512 x W workgroups
+// each (+ surplus).  W is what the chunk count of the exhaustive form was (target_blocks / q_blocks, at most kF16MaxS and
+// the tile count), rounded up to a multiple of 8 from 8 on; a (workgroup, query) pair lists at most KC group entries,
+// so a query's list holds at most W * KC <= kF16MaxS * KC.
+void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* W) {
     constexpr int QG = 4;
     const int n_tiles = (M + kT16 - 1) / kT16;
     const int qb = (Q + (kBlock / 64) * QG * 32 - 1) / ((kBlock / 64) * QG * 32);
     int s = target_blocks / (qb > 0 ? qb : 1); if (s < 1) s = 1;
     if (s > kF16MaxS) s = kF16MaxS;
     if (s > n_tiles) s = n_tiles > 0 ? n_tiles : 1;
-    const int tpc = n_tiles > 0 ? (n_tiles + s - 1) / s : 1;
-    s = n_tiles > 0 ? (n_tiles + tpc - 1) / tpc : 1;
-    *q_blocks = qb; *S = s; *tiles_per_chunk = tpc;
+    if (s >= 8) s = (s + 7) / 8 * 8;                  // kF16MaxS is a multiple of 8
+    *q_blocks = qb; *W = s;
 }
 
 // model -> f16 tiles (+ the seeding grid when seed_cnt != nullptr); once per prepared model
@@ -401,20 +463,18 @@ int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsi
     return PCREG_OK;
 }
 
-// The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it).
-// ug_*: the query-grid by-product (null: none).  Returns S (chunks) through S_out; list capacity per query = S * KC.
-int launch_knn_candidates_f16(const float* q, int Q, int ldq, int M, const void* prep, const void* mtiles, unsigned* gthr,
-                              void* cand_ent, int32_t* cand_cnt, int target_blocks, bool dry, bool timed, const float* ug_part,
-                              int ug_nparts, int ug_cells, void* ug_prep, int* S_out, hipStream_t st) {
-    int q_blocks, S, tiles_per_chunk;
-    knn_f16_shape(Q, M, target_blocks, &q_blocks, &S, &tiles_per_chunk);
-    *S_out = S;
+// The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it).  qperm: query
+// slot -> query row (spatial order); dk: each query's seed distance; tbox: the model tiles' boxes; cull = 0 visits every
+// tile.  ug_*: the query-grid by-product (null: none).  Returns W through W_out; list capacity per query = W * KC.
+int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
+                              const void* mtiles, const float* tbox, int cull, unsigned* gthr, void* cand_ent, int32_t* cand_cnt,
+                              void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part, int ug_nparts, int ug_cells,
+                              void* ug_prep, int* W_out, hipStream_t st) {
+    int q_blocks, W;
+    knn_f16_shape(Q, M, target_blocks, &q_blocks, &W);
+    *W_out = W;
     if (M <= 0 || Q <= 0) return PCREG_OK;
     const int n_tiles = (M + kT16 - 1) / kT16;
-    // XCD-aware placement deals chunk c to the XCD that runs workgroups b = c (mod 8): the grid rounds the chunk count
-    // up to a multiple of 8 and the surplus workgroups leave at once
-    const int xcd_map = S >= 8 ? 1 : 0;
-    const int grid_chunks = xcd_map ? (S + 7) / 8 * 8 : S;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_time_on && timed) {
         if (g_time_used == g_time_ev.size()) { hipEvent_t a, b; PCREG_HIP(hipEventCreate(&a)); PCREG_HIP(hipEventCreate(&b)); g_time_ev.emplace_back(a, b); }
@@ -422,9 +482,9 @@ int launch_knn_candidates_f16(const float* q, int Q, int ldq, int M, const void*
         PCREG_HIP(hipEventRecord(ev0, st));
     }
     const int aux = ug_prep != nullptr ? 1 : 0;
-#define PCREG_F16_LAUNCH(QGV, DRYV) hipLaunchKernelGGL((knn_candidates_f16_pipe_kernel<QGV, DRYV>), dim3(q_blocks * grid_chunks + aux), dim3(kBlock), 0, st, q, Q, ldq, \
-                           (const uint4*)mtiles, n_tiles, tiles_per_chunk, (const Prep*)prep, gthr, (uint2*)cand_ent, cand_cnt, S * KC, q_blocks, xcd_map, S, \
-                           ug_part, ug_nparts, ug_cells, (UgPrep*)ug_prep)
+#define PCREG_F16_LAUNCH(QGV, DRYV) hipLaunchKernelGGL((knn_candidates_f16_pipe_kernel<QGV, DRYV>), dim3(q_blocks * W + aux), dim3(kBlock), 0, st, q, Q, ldq, \
+                           qperm, dk, (const uint4*)mtiles, tbox, n_tiles, W, cull, (const Prep*)prep, gthr, (uint2*)cand_ent, cand_cnt, W * KC, \
+                           (SearchCounters*)ctr, ug_part, ug_nparts, ug_cells, (UgPrep*)ug_prep)
 #ifdef PCREG_EXPERIMENTS
     if (dry) PCREG_F16_LAUNCH(4, true); else
 #endif
