@@ -78,7 +78,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * the parity tests can run both sides inside one process.  Every setting returns the same indices and counts.  Keys:
  * "knn_exact", "match_exact", "match_force_fallback" (1, 2), "ransac_fused", "ransac_nolane", "ransac_f64score",
  * "ransac_resident_f64", "align_times", "align_shape", "seg_debug", "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb" (the
- * descriptor memory bound of pcreg_final_stage in MB instead of 4 GB, to exercise its batches); value 0 restores the default.  The library reads NO
+ * descriptor memory bound of pcreg_final_stage in MB instead of 4 GB, to exercise its batches), "knn_nocull" (the point search
+ * visits every model tile), "knn_stats" (counters for pcreg_debug_knn_stats); value 0 restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
 /* With pcreg_debug_set("match_stats", 1): the counters of the certified SAD matcher summed over the calls since the last
@@ -87,6 +88,11 @@ int  pcreg_debug_set(const char* key, int value);
  * handed to the exhaustive kernel, [6] matcher calls, [7] segments.  Synchronises the device.  bench.py reports them so that
  * a throughput figure says how much of it the certificates carried. */
 int  pcreg_debug_match_stats(long long out[8], int reset);
+/* With pcreg_debug_set("knn_stats", 1): the counters of the point search against a prepared model summed over the searches
+ * since the last reset -- out[0] searches, [1] (query block, model tile) pairs the candidate kernel visited, [2] nominal
+ * pairs (query blocks of 512 x tiles of 512 rows), [3] queries the certificate sent to the exhaustive tail.  Off: no extra
+ * work; on: one small launch per search, no host sync.  The read synchronises the device. */
+int  pcreg_debug_knn_stats(long long out[4], int reset);
 
 /* ---- host tier ------------------------------------------------------------------ */
 
@@ -352,6 +358,14 @@ int pcreg_dev_model_destroy(pcreg_dev_model* model);
 /* Top-2 of every query over the prepared model (pcreg_dev_knn2_points_f32's contract and bits).  The workspace also
  * receives a uniform grid over the queries, which pcreg_dev_model_match_f32 / _match_table_f32 need for Unique: pass
  * the SAME workspace to them, with no other search on it in between. */
+/* Test hooks: copy what a prepared model holds into device buffers of the caller, enqueued on `stream` (any pointer may be
+ * NULL): perm [M] (perm[sorted row] = original row), the fp32 sorted copy [3][M] (ld = M), the tile boxes [n_tiles][6]
+ * (lo x, y, z, hi x, y, z of every tile of 512 sorted rows) -- and the raw 24-word preparation record to the HOST (waits for
+ * the stream; 20 words used, ints as their bit patterns; zeros for M = 0).  pcreg_debug_search_export copies the query order qperm [Q]
+ * (slot -> query) and the seed distances dk [Q] of the last search on `workspace` (sized for Q, M). */
+int pcreg_debug_dev_model_export(const pcreg_dev_model* model, int32_t* perm, float* sorted_soa, float* tile_box, float prep[24],
+                                 void* stream);
+int pcreg_debug_search_export(const void* workspace, size_t workspace_bytes, int Q, int M, int32_t* qperm, float* dk, void* stream);
 size_t pcreg_dev_model_search_workspace(int Q, int M);
 int pcreg_dev_model_search_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int32_t idx_base,
                                int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);

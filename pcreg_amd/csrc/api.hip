@@ -100,6 +100,15 @@ unsigned long long* match_stats_dev() {
     }
     return g_match_stats;
 }
+static unsigned long long* g_knn_stats = nullptr;
+unsigned long long* knn_stats_dev() {
+    if (!debug_flag(kDbgKnnStats)) return nullptr;
+    if (!g_knn_stats) {
+        if (hipMalloc((void**)&g_knn_stats, 4 * sizeof(unsigned long long)) != hipSuccess) { g_knn_stats = nullptr; return nullptr; }
+        (void)hipMemset(g_knn_stats, 0, 4 * sizeof(unsigned long long));
+    }
+    return g_knn_stats;
+}
 }
 
 extern "C" {
@@ -107,7 +116,8 @@ extern "C" {
 int pcreg_debug_set(const char* key, int value) {
     static const char* const names[pcreg::kDbgCount] = {"knn_exact", "match_exact", "match_force_fallback", "ransac_fused", "ransac_nolane",
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
-                                                        "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb"};
+                                                        "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
+                                                        "knn_stats"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -124,6 +134,18 @@ int pcreg_debug_match_stats(long long out[8], int reset) {
     PCREG_HIP(hipMemcpy(h, pcreg::g_match_stats, sizeof h, hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) out[k] = (long long)h[k];
     if (reset) PCREG_HIP(hipMemset(pcreg::g_match_stats, 0, sizeof h));
+    return PCREG_OK;
+}
+
+int pcreg_debug_knn_stats(long long out[4], int reset) {
+    PCREG_ARG(out != nullptr);
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    if (!pcreg::g_knn_stats) return PCREG_OK;                 // "knn_stats" was never on
+    PCREG_HIP(hipDeviceSynchronize());
+    unsigned long long h[4];
+    PCREG_HIP(hipMemcpy(h, pcreg::g_knn_stats, sizeof h, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) out[k] = (long long)h[k];
+    if (reset) PCREG_HIP(hipMemset(pcreg::g_knn_stats, 0, sizeof h));
     return PCREG_OK;
 }
 
@@ -324,6 +346,16 @@ int pcreg_dev_model_destroy(pcreg_dev_model* model) {
     (void)hipFree(model->block);
     delete model;
     return PCREG_OK;
+}
+int pcreg_debug_dev_model_export(const pcreg_dev_model* model, int32_t* perm, float* sorted_soa, float* tile_box, float prep[24],
+                                 void* stream) {
+    PCREG_ARG(model != nullptr);
+    GUARD();
+    return model_export(model->v, perm, sorted_soa, tile_box, prep, (hipStream_t)stream);
+}
+int pcreg_debug_search_export(const void* ws, size_t ws_bytes, int Q, int M, int32_t* qperm, float* dk, void* stream) {
+    GUARD();
+    return search_export(ws, ws_bytes, Q, M, qperm, dk, (hipStream_t)stream);
 }
 size_t pcreg_dev_model_search_workspace(int Q, int M) { return search_ws_bytes(Q, M); }
 int pcreg_dev_model_search_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int32_t idx_base, int32_t* idx,

@@ -71,6 +71,8 @@ enum DebugKey {
     kDbgSegWaveFinalize,       // "seg_wave_finalize": the segmented matcher's forward re-rank as one wave per query (rounds 2-3) instead of pick / pairs / decide
     kDbgMatchStats,            // "match_stats": the certified matcher counts what it proves / re-scores / hands on (pcreg_debug_match_stats)
     kDbgFinalBatchMB,          // "final_batch_mb": pcreg_final_stage's descriptor memory bound in MB instead of 4 GB (0 = the default)
+    kDbgKnnNoCull,             // "knn_nocull": the point search's candidate kernel visits every model tile (no culling)
+    kDbgKnnStats,              // "knn_stats": the point search counts what it visits (pcreg_debug_knn_stats)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -79,6 +81,9 @@ int debug_flag(DebugKey k);
 //   [3] queries handed to the exhaustive exact-rows kernel   [4] Unique back-check items (segmented form)
 //   [5] back-check items handed to the exhaustive kernel   [6] matcher calls   [7] segments
 unsigned long long* match_stats_dev();
+// Device counters of the point search (knn_fast.hip), or null while "knn_stats" is off:
+//   [0] searches   [1] visited (query block, model tile) pairs   [2] nominal pairs (q_blocks x n_tiles)   [3] queries sent to the tail
+unsigned long long* knn_stats_dev();
 #ifdef PCREG_EXPERIMENTS
 static inline int pcreg_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline const char* pcreg_env_str(const char* name) { return getenv(name); }
@@ -131,6 +136,9 @@ struct SearchWs {
 };
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes);
 size_t search_ws_bytes(int Q, int M);
+// test hooks (pcreg_debug_dev_model_export, pcreg_debug_search_export): copies out of a prepared model / a search workspace
+int model_export(const ModelView& v, int32_t* perm, float* sorted_soa, float* tile_box, float prep[24], hipStream_t st);
+int search_export(const void* ws, size_t ws_bytes, int Q, int M, int32_t* qperm, float* dk, hipStream_t st);
 int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int32_t idx_base, int32_t* idx, float* dist,
                         void* ws, size_t ws_bytes, bool with_grid, bool timed, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)

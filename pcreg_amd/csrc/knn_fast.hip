@@ -360,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const double u = 5.9604644775390625e-08;                     // 2^-24
     const float cxf = prep->cx, cyf = prep->cy, czf = prep->cz, sg = prep->sigma;
     const float tx = qx - cxf, ty = qy - cyf, tz = qz - czf;       // the same q~ the candidate kernel formed
-    const bool scored = fabsf(sg * tx) <= kQueryScaledMax && fabsf(sg * ty) <= kQueryScaledMax && fabsf(sg * tz) <= kQueryScaledMax;
+    const bool scored = scale_usable(prep) && fabsf(sg * tx) <= kQueryScaledMax && fabsf(sg * ty) <= kQueryScaledMax && fabsf(sg * tz) <= kQueryScaledMax;
     const double r2 = (double)tx * tx + (double)ty * ty + (double)tz * tz;
     const double r = sqrt(r2);
     const double Rm2 = (double)__uint_as_float(*rm2_bits);
@@ -604,6 +604,16 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
     }
 }
 
+// pcreg_debug_set("knn_stats", 1): one thread adds this search's counters to the process-wide sums (after S3, which
+// leaves n_flag; nothing waits for the host)
+__global__ void knn_stats_kernel(const SearchCounters* __restrict__ ctr, long long nominal, unsigned long long* __restrict__ stats) {
+    if (threadIdx.x != 0) return;
+    long long nv = 0;
+    for (int k = 0; k < kVisitSlots; ++k) nv += ctr->visited[k];
+    atomicAdd(&stats[0], 1ull); atomicAdd(&stats[1], (unsigned long long)nv);         // (searches on other streams add too)
+    atomicAdd(&stats[2], (unsigned long long)nominal); atomicAdd(&stats[3], (unsigned long long)ctr->n_flag);
+}
+
 constexpr int kSeedMinM = 16 * 1024;             // below this the lists settle within the first tiles anyway
 // the grid is sized on the device (about M/2 cells plus the margin layer); this is the capacity it may use
 size_t seed_cell_cap(int M) { return std::min<size_t>((size_t)kSeedMaxCells, std::max<size_t>(4096, (size_t)M)); }
@@ -715,7 +725,7 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     int W = 1;
     const int variant = PCREG_EXP_ENV("PCREG_KNN_VARIANT", 40);      // 41: timing-only form of the candidate kernel (EXPERIMENTS builds)
     const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS workgroups)
-    const int cull = PCREG_EXP_ENV("PCREG_KNN_NOCULL", 0) ? 0 : 1;    // EXPERIMENTS builds: visit every tile (A/B of the culling)
+    const int cull = (debug_flag(kDbgKnnNoCull) || PCREG_EXP_ENV("PCREG_KNN_NOCULL", 0)) ? 0 : 1;    // "knn_nocull": visit every tile
     int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, cull, s.gthr, s.cand_ent, s.cand_cnt, ctr,
                                        target_env > 0 ? target_env : kTargetBlocks, variant == 41, timed, grid ? s.ug_part : nullptr,
                                        s.ug_nparts, s.ug_cells, grid ? s.ug_prep : nullptr, &W, st);
@@ -724,6 +734,10 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
                        (const int32_t*)v.perm, (const Prep*)v.prep, (const unsigned*)v.rm2, (const unsigned*)s.gthr, (const uint2*)s.cand_ent,
                        (const int32_t*)s.cand_cnt, W * KC, (int)idx_base, idx, dist, s.flag_list, &ctr->n_flag,
                        grid ? (const UgPrep*)s.ug_prep : nullptr, s.ug_cnt, (float4*)s.ug_slots);
+    if (unsigned long long* stats = knn_stats_dev()) {
+        const long long nominal = (long long)((Q + 511) / 512) * (long long)n_f16_tiles(v.M);
+        hipLaunchKernelGGL(knn_stats_kernel, dim3(1), dim3(64), 0, st, (const SearchCounters*)ctr, nominal, stats);
+    }
     if (PCREG_EXP_ENV("PCREG_KNN_DEBUG", 0)) {
         int32_t nf = 0, vis[kVisitSlots];
         PCREG_HIP(hipMemcpyAsync(&nf, &ctr->n_flag, 4, hipMemcpyDeviceToHost, st));
@@ -737,6 +751,31 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     hipLaunchKernelGGL(knn_tail_kernel, dim3(kTailGrid), dim3(kBlock), 0, st, q, ldq, v.m, v.M, v.ldm, (int)idx_base, (const int32_t*)s.flag_list, ctr,
                        s.tail_idx, s.tail_dist, idx, dist);
     PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+// ---- test hooks: what a prepared model and the last search on a workspace hold (device-to-device copies) ------------
+int model_export(const ModelView& v, int32_t* perm, float* sorted_soa, float* tile_box, float prep[24], hipStream_t st) {
+    static_assert(sizeof(Prep) <= 24 * sizeof(float), "pcreg_debug_dev_model_export copies Prep into 24 words");
+    if (prep) std::fill(prep, prep + 24, 0.0f);
+    if (v.M == 0) return PCREG_OK;                   // nothing was prepared
+    if (perm) PCREG_HIP(hipMemcpyAsync(perm, v.perm, (size_t)v.M * 4, hipMemcpyDeviceToDevice, st));
+    if (sorted_soa) PCREG_HIP(hipMemcpyAsync(sorted_soa, v.ms, (size_t)v.M * 12, hipMemcpyDeviceToDevice, st));
+    if (tile_box) PCREG_HIP(hipMemcpyAsync(tile_box, v.tbox, n_f16_tiles(v.M) * 24, hipMemcpyDeviceToDevice, st));
+    if (prep) {
+        PCREG_HIP(hipMemcpyAsync(prep, v.prep, sizeof(Prep), hipMemcpyDeviceToHost, st));
+        PCREG_HIP(hipStreamSynchronize(st));
+    }
+    return PCREG_OK;
+}
+int search_export(const void* ws, size_t ws_bytes, int Q, int M, int32_t* qperm, float* dk, hipStream_t st) {
+    PCREG_ARG(ws != nullptr && Q >= 0 && M >= 0);
+    if (Q == 0) return PCREG_OK;
+    size_t need;
+    const SearchWs s = search_ws_layout(Q, M, const_cast<void*>(ws), &need);
+    if (ws_bytes < need) { set_error("search workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
+    if (qperm) PCREG_HIP(hipMemcpyAsync(qperm, s.qperm, (size_t)Q * 4, hipMemcpyDeviceToDevice, st));
+    if (dk) PCREG_HIP(hipMemcpyAsync(dk, s.dk, (size_t)Q * 4, hipMemcpyDeviceToDevice, st));
     return PCREG_OK;
 }
 

@@ -54,6 +54,12 @@ __device__ __forceinline__ int sort_key(float x, float y, float z, const Prep* _
 // A query whose scaled coordinate leaves this range is not scored on the matrix cores (its f16 operands would
 // overflow or lose the error bound's assumptions): it goes to the exact fallback.
 constexpr float kQueryScaledMax = 16384.0f;
+// The scores, thresholds and list entries move between unscaled and scaled units through sigma^2 and 1/sigma^2; both are
+// normal fp32 numbers only for half extents H in [2^-58, 2^69).  Outside, no query is scored: all go to the exact tail.
+__device__ __forceinline__ bool scale_usable(const Prep* __restrict__ p) {
+    const float sg2 = p->sigma * p->sigma;
+    return sg2 >= 1.17549435e-38f && sg2 < INFINITY && p->inv_sigma2 >= 1.17549435e-38f && p->inv_sigma2 < INFINITY;
+}
 constexpr int kF16MaxS = 80;                      // most workgroups per query block of the f16 candidate kernel (a multiple of 8)
 constexpr int kSeedSlots = 4;                    // model points remembered per grid cell
 constexpr int kSeedMaxCells = 1 << 21;

@@ -175,6 +175,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
     // query SLOTS: the call's queries in spatial order (qperm), so that the 512 slots of a block are compact in space
     const int q_base = (qb * (kBlock / 64) + wave) * (QG * 32);
     const float sg = prep->sigma, inv2 = prep->inv_sigma2, sg2 = sg * sg;
+    const bool scale_ok = scale_usable(prep);
 
     f16x8 bq[QG];
     float thr[QG];
@@ -189,9 +190,10 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
             const int qi = qperm[slot];
             const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
             const float sx = sg * (px - prep->cx), sy = sg * (py - prep->cy), sz = sg * (pz - prep->cz);
-            // a query far outside the prepared model's box (or not finite) is not scored here: all-zero operands, no list
-            // entries; knn_finalize_kernel applies the same test and sends it to the exact fallback
-            if (fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
+            // a query far outside the prepared model's box (or not finite), or any query of a model whose scale leaves fp32
+            // (scale_usable), is not scored here: all-zero operands, no list entries; knn_finalize_kernel applies the same
+            // test and sends it to the exact fallback
+            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
                 X = -2.0f * sx; Y = -2.0f * sy; Z = -2.0f * sz; one = 1.0f;
                 blo[0] = fminf(blo[0], px); blo[1] = fminf(blo[1], py); blo[2] = fminf(blo[2], pz);
                 bhi[0] = fmaxf(bhi[0], px); bhi[1] = fmaxf(bhi[1], py); bhi[2] = fmaxf(bhi[2], pz);
