@@ -41,6 +41,9 @@ extern "C" {
 #define PCREG_E_NODEVICE    3   /* no usable gfx950 device                                */
 #define PCREG_E_WORKSPACE   4   /* caller's workspace too small (device tier)             */
 
+/* largest k of the k-nearest point searches (pcreg_knn_points_f32, pcreg_model_knn_f32, pcreg_dev_model_knn_f32) */
+#define PCREG_KNN_MAX_K 32
+
 #define PCREG_METRIC_SAD 0
 #define PCREG_METRIC_SSD 1
 
@@ -150,6 +153,13 @@ int pcreg_model_create(const float* m, int M, int ldm, pcreg_model** model);
 int pcreg_model_destroy(pcreg_model* model);
 int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int ldq, float thr_abs, float max_ratio,
                                  int unique, uint32_t* pairs, int* P);
+/* MATLAB's [Idx, D] = knnsearch(model, q, 'K', k) / findNearestNeighbors(ptCloud, p, K) against the handle: for each query the
+ * k (1 <= k <= PCREG_KNN_MAX_K) model rows with the smallest fp32 squared distance fmaf(dz,dz,fmaf(dy,dy,dx*dx)), ordered by
+ * (distance, row), ties to the lowest row.  idx [Q][k] 0-based (-1 past M), dist [Q][k] squared (+inf past M), both
+ * row-major.  Exact: the same bits as a brute force; for k = 1, 2 the columns of the top-2 search. */
+int pcreg_model_knn_f32(pcreg_model* model, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist);
+/* The same without a handle (knnsearch(m, q, 'K', k)): uploads and prepares the model for this call only. */
+int pcreg_knn_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int k, int32_t* idx, float* dist);
 
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
@@ -369,6 +379,13 @@ int pcreg_debug_search_export(const void* workspace, size_t workspace_bytes, int
 size_t pcreg_dev_model_search_workspace(int Q, int M);
 int pcreg_dev_model_search_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int32_t idx_base,
                                int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
+/* knnsearch(model, q, 'K', k) on the device: pcreg_model_knn_f32's contract, reported rows idx_base + local row (-1 past
+ * M).  Q <= 4 Mi per call; the workspace (O(Q) bytes, any k) is sized by pcreg_dev_model_knn_workspace.  Nothing is
+ * certified and there is no fallback: every distance is the fp32 chain itself, tiles are skipped by DESIGN 4.1's rule
+ * with the k-th-neighbour bound.  A handle may serve several streams at once, each call with its own workspace. */
+size_t pcreg_dev_model_knn_workspace(int Q, int M, int k);
+int pcreg_dev_model_knn_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int k, int32_t idx_base, int32_t* idx,
+                            float* dist, void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */
@@ -399,6 +416,11 @@ int pcreg_dev_merge_top2_f32(const int32_t* idx_in, const float* dist_in, int R,
  * carry a rank's indices and distances in a single buffer. */
 int pcreg_dev_merge_top2_strided_f32(const int32_t* idx_in, const float* dist_in, int R, int Q, size_t rank_stride,
                                      int32_t* idx, float* dist, void* stream);
+/* The k analogue (knnsearch over a model split into shards): R lists of [Q][k] with list r starting r * rank_stride
+ * ELEMENTS in (0: densely packed, Q * k; else >= Q * k) -> one [Q][k] per query by (dist, idx); -1 entries are empty and
+ * an index repeated across lists is kept once. */
+int pcreg_dev_merge_topk_f32(const int32_t* idx_in, const float* dist_in, int R, int Q, int k, size_t rank_stride,
+                             int32_t* idx, float* dist, void* stream);
 
 /* Device-resident ransac: n is read from device memory (*n_dev <= n_cap), so the
  * match stage can feed it without a host round trip.  Results land in `out`

@@ -9,6 +9,8 @@
 //   'getSpacialHistogramDescriptors', pts, sample_pts, options -> feat (V x 3), desc (V x 980)
 //   'modelCreate', model (single M x 3) -> handle (uint64) | 'modelMatchPoints', handle, surface (single Q x 3), thrAbs, maxRatio, unique
 //                                          -> pairs (P x 2 uint32) | 'modelDestroy', handle      (one model, many surfaces)
+//   'modelKnn', handle, queries (single Q x 3), k        -> idx (Q x k int32, 1-based, 0 past M), D2 (Q x k single, squared)
+//                                          (knnsearch(model, Y, 'K', k) against the handle; matlab/knnsearchModel.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -407,6 +409,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 for (int k = 0; k < P; ++k) { dst[k] = src[2 * k]; dst[k + P] = src[2 * k + 1]; }
             }
             mxDestroyArray(buf);
+        }
+    } else if (!strcmp(cmd, "modelKnn")) {                    // [idx, D2] = pcreg_mex('modelKnn', h, single(Y), k): knnsearch(model, Y, 'K', k)
+        if (nrhs != 4 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || mxGetM(prhs[3]) * mxGetN(prhs[3]) != 1 ||
+            !(mxGetScalar(prhs[3]) >= 1.0 && mxGetScalar(prhs[3]) <= (double)PCREG_KNN_MAX_K) || mxGetScalar(prhs[3]) != (double)(int)mxGetScalar(prhs[3]))
+            usage = "modelKnn: handle (uint64), queries (single Q x 3), k (an integer in 1..32)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), k = (int)mxGetScalar(prhs[3]);
+            mxArray* bi = mxCreateNumericMatrix((size_t)k, Q > 0 ? Q : 1, mxINT32_CLASS, mxREAL);      // [Q][k] row-major
+            mxArray* bd = mxCreateNumericMatrix((size_t)k, Q > 0 ? Q : 1, mxSINGLE_CLASS, mxREAL);
+            if (Q > 0) rc = pcreg_model_knn_f32(h, (const float*)mxGetData(prhs[2]), Q, Q, k, (int32_t*)mxGetData(bi), (float*)mxGetData(bd));
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateNumericMatrix((size_t)Q, (size_t)k, mxINT32_CLASS, mxREAL);
+                plhs[1] = mxCreateNumericMatrix((size_t)Q, (size_t)k, mxSINGLE_CLASS, mxREAL);
+                const int32_t* si = (const int32_t*)mxGetData(bi); const float* sd = (const float*)mxGetData(bd);
+                int32_t* di = (int32_t*)mxGetData(plhs[0]); float* dd = (float*)mxGetData(plhs[1]);
+                for (int i = 0; i < Q; ++i)
+                    for (int j = 0; j < k; ++j) { di[i + (size_t)j * Q] = si[(size_t)i * k + j] + 1; dd[i + (size_t)j * Q] = sd[(size_t)i * k + j]; }
+            }
+            mxDestroyArray(bi); mxDestroyArray(bd);
         }
     } else if (!strcmp(cmd, "descCreate")) {                  // h = pcreg_mex('descCreate', desc): an n x D double descriptor set, uploaded ONCE
         if (nrhs != 2 || !mxIsDouble(prhs[1])) usage = "descCreate: desc (double n x D)";

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PCREG_LIB") or os.path.join(_HERE, "libpcreg_hip.so")     # PCREG_LIB: another build of the same library (A/B runs)
 
 PCREG_OK, PCREG_E_ARG, PCREG_E_HIP, PCREG_E_NODEVICE, PCREG_E_WORKSPACE = 0, 1, 2, 3, 4
+KNN_MAX_K = 32                   # PCREG_KNN_MAX_K
 METRIC_SAD, METRIC_SSD = 0, 1
 LAYOUT_FEATURE_MAJOR, LAYOUT_ROW_MAJOR = 0, 1
 
@@ -54,8 +55,9 @@ SYMBOLS = [
     "pcreg_debug_knn_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
     "pcreg_estimate_transform", "pcreg_calc_dists", "pcreg_ransac", "pcreg_ransac_batched",
     "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
-    "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_match_points_f32",
+    "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
     "pcreg_dev_model_create", "pcreg_dev_model_destroy", "pcreg_dev_model_search_workspace", "pcreg_dev_model_search_f32",
+    "pcreg_dev_model_knn_workspace", "pcreg_dev_model_knn_f32", "pcreg_dev_merge_topk_f32",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
     "pcreg_align_points_knn", "pcreg_align_points_knn_f32", "pcreg_align_points_knn_batched", "pcreg_spatial_histogram_descriptors",
     "pcreg_spatial_histogram_descriptors_f32", "pcreg_spatial_histogram_descriptors_mixed",
@@ -102,6 +104,8 @@ def lib() -> C.CDLL:
                      "pcreg_dev_get_matches_workspace", "pcreg_dev_sphere_select_workspace", "pcreg_dev_ransac_batched_workspace",
                      "pcreg_dev_get_matches_segmented_workspace", "pcreg_dev_segmented_model_bytes"):
             getattr(L, name).restype = C.c_size_t
+        if hasattr(L, "pcreg_dev_model_knn_workspace"):     # (an older build given through PCREG_LIB lacks the k-nearest search)
+            L.pcreg_dev_model_knn_workspace.restype = C.c_size_t
         for name, args in (("pcreg_debug_knn_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_dev_model_export", [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),
                            ("pcreg_debug_search_export", [C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3)):

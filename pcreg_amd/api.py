@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import DescOpts, MatchOpts, RansacOpts, check, lib
+from ._lib import KNN_MAX_K, DescOpts, MatchOpts, RansacOpts, check, lib
 
 EMPTY = np.zeros((0, 0))
 """MATLAB's ``[]`` (what estimateTransform / ransac return on failure)."""
@@ -586,6 +586,26 @@ def knn2_points(query, model):
     return idx[:Q], dist[:Q]
 
 
+def _knn_k(k) -> int:
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must lie in [1, {KNN_MAX_K}], got {k}")
+    return k
+
+
+def knn_points(query, model, k: int):
+    """knnsearch(model, query, 'K', k) in fp32: (idx [Q,k] 0-based int32, -1 past M; dist [Q,k] squared float32, +inf past M),
+    ordered by (distance, row).  The model is prepared for this call only: keep a Model for repeated searches."""
+    k = _knn_k(k)
+    q, m = _fcol(query, np.float32), _fcol(model, np.float32)
+    Q, M = q.shape[0], m.shape[0]
+    idx = np.zeros((max(Q, 1), k), dtype=np.int32)
+    dist = np.zeros((max(Q, 1), k), dtype=np.float32)
+    check(lib().pcreg_knn_points_f32(_ptr(q, C.c_float), C.c_int(Q), C.c_int(max(Q, 1)), _ptr(m, C.c_float), C.c_int(M),
+                                     C.c_int(max(M, 1)), C.c_int(k), _ptr(idx, C.c_int32), _ptr(dist, C.c_float)))
+    return idx[:Q], dist[:Q]
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or
@@ -607,6 +627,20 @@ class Model:
         check(lib().pcreg_model_match_points_f32(self._h, _ptr(q, C.c_float), C.c_int(Q), C.c_int(max(Q, 1)), C.c_float(thr_abs),
                                                  C.c_float(max_ratio), C.c_int(int(unique)), _ptr(pairs, C.c_uint32), C.byref(P)))
         return pairs[:P.value].copy()
+
+    def knn(self, query, k: int):
+        """knnsearch(model, query, 'K', k) against the prepared model: (idx [Q,k] 0-based int32, -1 past M; dist [Q,k]
+        squared float32, +inf past M), ordered by (distance, row) -- the bits of a brute-force fp32 search."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        k = _knn_k(k)
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        idx = np.zeros((max(Q, 1), k), dtype=np.int32)
+        dist = np.zeros((max(Q, 1), k), dtype=np.float32)
+        check(lib().pcreg_model_knn_f32(self._h, _ptr(q, C.c_float), C.c_int(Q), C.c_int(max(Q, 1)), C.c_int(k), _ptr(idx, C.c_int32),
+                                        _ptr(dist, C.c_float)))
+        return idx[:Q], dist[:Q]
 
     def close(self):
         if self._h.value:

@@ -23,6 +23,8 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+constexpr int kKnnMaxK = PCREG_KNN_MAX_K;        // (named here so that no argument message spells the macro)
+constexpr int kKnnMaxQ = 4 << 20;                  // queries per k-nearest call: the top-2 search's limit
 static std::mutex g_mu;
 static int g_device_ok = -1;          // -1 unknown, 0 ok, else error code
 static hipStream_t g_stream = nullptr;
@@ -364,6 +366,13 @@ int pcreg_dev_model_search_f32(const pcreg_dev_model* model, const float* q, int
     GUARD();
     return launch_model_search(model->v, q, Q, ldq, idx_base, idx, dist, workspace, workspace_bytes, true, true, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_knn_workspace(int Q, int M, int k) { return knn_k_ws_bytes(Q, M, k); }
+int pcreg_dev_model_knn_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int k, int32_t idx_base, int32_t* idx,
+                            float* dist, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && q && idx && dist && workspace && k >= 1 && k <= kKnnMaxK && Q >= 0 && ldq >= Q && Q <= kKnnMaxQ);
+    GUARD();
+    return launch_model_knn(model->v, q, Q, ldq, k, idx_base, idx, dist, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -443,6 +452,41 @@ int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int 
     PCREG_ARG(model && model->dm && q && pairs && P && Q >= 0 && ldq >= Q);
     GUARD();
     return match_points_on_view(model->dm->v, q, Q, ldq, thr_abs, max_ratio, unique, pairs, P);
+}
+
+// the k nearest rows on a prepared model: upload the queries, search, copy [Q][k] back
+static int knn_on_view(const ModelView& v, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist) {
+    if (Q == 0) return PCREG_OK;
+    void *dq, *di, *dd, *ws;
+    const size_t wsb = knn_k_ws_bytes(Q, v.M, k), nk = (size_t)Q * k;
+    TRY(scratch().get(0, sizeof(float) * 3 * (size_t)Q, &dq));
+    TRY(scratch().get(2, sizeof(int32_t) * nk, &di));
+    TRY(scratch().get(3, sizeof(float) * nk, &dd));
+    TRY(scratch().get(4, wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, (float*)dq, g_stream));
+    TRY(launch_model_knn(v, (float*)dq, Q, Q, k, 0, (int32_t*)di, (float*)dd, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * nk, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_knn_f32(pcreg_model* model, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist) {
+    PCREG_ARG(model && q && idx && dist && k >= 1 && k <= kKnnMaxK && Q >= 0 && ldq >= Q && Q <= kKnnMaxQ);
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    return knn_on_view(model->dm->v, q, Q, ldq, k, idx, dist);
+}
+int pcreg_knn_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int k, int32_t* idx, float* dist) {
+    PCREG_ARG(q && m && idx && dist && k >= 1 && k <= kKnnMaxK && Q >= 0 && M >= 0 && ldq >= Q && ldm >= M && Q <= kKnnMaxQ);
+    GUARD();
+    if (Q == 0) return PCREG_OK;
+    void *dm, *block;
+    TRY(scratch().get(1, sizeof(float) * 3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(scratch().get(10, model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, (float*)dm, g_stream));
+    const ModelView v = model_view((float*)dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return knn_on_view(v, q, Q, ldq, k, idx, dist);
 }
 
 int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float thr_abs,
@@ -1233,6 +1277,14 @@ int pcreg_dev_merge_top2_strided_f32(const int32_t* idx_in, const float* dist_in
     PCREG_ARG(idx_in && dist_in && idx && dist);
     GUARD();
     return launch_merge_top2_f32(idx_in, dist_in, R, Q, idx, dist, (hipStream_t)stream, rank_stride);
+}
+
+int pcreg_dev_merge_topk_f32(const int32_t* idx_in, const float* dist_in, int R, int Q, int k, size_t rank_stride, int32_t* idx,
+                             float* dist, void* stream) {
+    PCREG_ARG(idx_in && dist_in && idx && dist && k >= 1 && k <= kKnnMaxK && R >= 1 && Q >= 0 &&
+              (rank_stride == 0 || rank_stride >= (size_t)Q * k));
+    GUARD();
+    return launch_merge_topk_f32(idx_in, dist_in, R, Q, k, rank_stride, idx, dist, (hipStream_t)stream);
 }
 
 size_t pcreg_dev_ransac_workspace(int n_cap, int iterNum) { return ransac_workspace_bytes(iterNum, 1, n_cap); }

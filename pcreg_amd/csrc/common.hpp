@@ -141,6 +141,14 @@ int model_export(const ModelView& v, int32_t* perm, float* sorted_soa, float* ti
 int search_export(const void* ws, size_t ws_bytes, int Q, int M, int32_t* qperm, float* dk, hipStream_t st);
 int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int32_t idx_base, int32_t* idx, float* dist,
                         void* ws, size_t ws_bytes, bool with_grid, bool timed, hipStream_t st);
+// S1b alone (scan of the per-parent-cell counts qcnt [kQueryKeys], then the slots qperm [Q]) for a search of its own
+int launch_query_order(const ModelView& v, const float* q, int Q, int ldq, int32_t* qcnt, int32_t* qperm, hipStream_t st);
+// the k nearest model rows per query (knn_k.hip): idx / dist [Q][k], (distance, original row) order, exact fp32
+size_t knn_k_ws_bytes(int Q, int M, int k);
+int launch_model_knn(const ModelView& v, const float* q, int Q, int ldq, int k, int32_t idx_base, int32_t* idx, float* dist,
+                     void* ws, size_t ws_bytes, hipStream_t st);
+int launch_merge_topk_f32(const int32_t* idx_in, const float* dist_in, int R, int Q, int k, size_t rank_stride, int32_t* idx, float* dist,
+                          hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,

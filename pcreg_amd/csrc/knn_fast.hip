@@ -754,6 +754,14 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     return PCREG_OK;
 }
 
+// S1b for another search (the k-nearest search, knn_k.hip): qcnt holds the per-parent-cell counts of the call's queries
+int launch_query_order(const ModelView& v, const float* q, int Q, int ldq, int32_t* qcnt, int32_t* qperm, hipStream_t st) {
+    hipLaunchKernelGGL(exclusive_scan_1wg_kernel, dim3(1), dim3(1024), 0, st, qcnt, kQueryKeys);
+    hipLaunchKernelGGL(query_order_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, qcnt, qperm);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
 // ---- test hooks: what a prepared model and the last search on a workspace hold (device-to-device copies) ------------
 int model_export(const ModelView& v, int32_t* perm, float* sorted_soa, float* tile_box, float prep[24], hipStream_t st) {
     static_assert(sizeof(Prep) <= 24 * sizeof(float), "pcreg_debug_dev_model_export copies Prep into 24 words");

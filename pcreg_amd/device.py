@@ -44,6 +44,33 @@ class PreparedModel:
         with torch.cuda.device(model_soa.device):
             check(lib().pcreg_dev_model_create(_p(model_soa), self.M, max(self.ld, 1), _stream(), C.byref(self.handle)))
 
+    def knn(self, q_soa: torch.Tensor, k: int, idx_base: int = 0, out=None):
+        """knnsearch(model, q, 'K', k) on torch's current stream (pcreg_dev_model_knn_f32): q_soa a [3, Q] float32 tensor with
+        contiguous rows -> (idx [Q, k] int32, idx_base + 0-based row, -1 past M; dist [Q, k] float32 squared, +inf past M),
+        ordered by (distance, row).  The workspace is cached on the model and grown on demand; calls that may overlap on two
+        streams pass buffers of their own, out=(idx, dist, ws) with ws of pcreg_dev_model_knn_workspace(Q, M, k) bytes."""
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if not 1 <= int(k) <= _l.KNN_MAX_K:
+            raise ValueError(f"k must lie in [1, {_l.KNN_MAX_K}], got {k}")
+        k, Q = int(k), int(q_soa.shape[1])
+        L = lib()
+        if Q == 0:
+            return (torch.empty((0, k), dtype=torch.int32, device=q_soa.device), torch.empty((0, k), dtype=torch.float32, device=q_soa.device))
+        need = max(int(L.pcreg_dev_model_knn_workspace(Q, self.M, k)), 256)
+        if out is not None:
+            idx, dist, ws = out
+        else:
+            idx = torch.empty((Q, k), dtype=torch.int32, device=q_soa.device)
+            dist = torch.empty((Q, k), dtype=torch.float32, device=q_soa.device)
+            ws = getattr(self, "_knn_ws", None)
+            if ws is None or ws.numel() < need or ws.device != q_soa.device:
+                ws = self._knn_ws = torch.empty(need, dtype=torch.uint8, device=q_soa.device)
+        with torch.cuda.device(q_soa.device):
+            check(L.pcreg_dev_model_knn_f32(self.handle, _p(q_soa), Q, int(q_soa.stride(0)), k, C.c_int32(idx_base), _p(idx), _p(dist), _p(ws),
+                                            C.c_size_t(ws.numel()), _stream()))
+        return idx, dist
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             lib().pcreg_dev_model_destroy(self.handle)
