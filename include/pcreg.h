@@ -82,7 +82,9 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * "knn_exact", "match_exact", "match_force_fallback" (1, 2), "ransac_fused", "ransac_nolane", "ransac_f64score",
  * "ransac_resident_f64", "align_times", "align_shape", "seg_debug", "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb" (the
  * descriptor memory bound of pcreg_final_stage in MB instead of 4 GB, to exercise its batches), "knn_nocull" (the point search
- * visits every model tile), "knn_stats" (counters for pcreg_debug_knn_stats); value 0 restores the default.  The library reads NO
+ * visits every model tile), "knn_stats" (counters for pcreg_debug_knn_stats), "ransac_pass2" (the staged RANSAC
+ * chain's second scoring pass: 1 always the full pass, 2 always the bounded pass where allowed; 0 chooses by shape),
+ * "ransac_stats" (counters for pcreg_debug_ransac_stats); value 0 restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
 /* With pcreg_debug_set("match_stats", 1): the counters of the certified SAD matcher summed over the calls since the last
@@ -96,6 +98,10 @@ int  pcreg_debug_match_stats(long long out[8], int reset);
  * pairs (query blocks of 512 x tiles of 512 rows), [3] queries the certificate sent to the exhaustive tail.  Off: no extra
  * work; on: one small launch per search, no host sync.  The read synchronises the device. */
 int  pcreg_debug_knn_stats(long long out[4], int reset);
+/* With pcreg_debug_set("ransac_stats", 1): the counters of the staged RANSAC chain's bounded second pass summed over the calls
+ * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
+ * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */
+int  pcreg_debug_ransac_stats(long long out[3], int reset);
 
 /* ---- host tier ------------------------------------------------------------------ */
 

@@ -111,6 +111,15 @@ unsigned long long* knn_stats_dev() {
     }
     return g_knn_stats;
 }
+static unsigned long long* g_ransac_stats = nullptr;
+unsigned long long* ransac_stats_dev() {
+    if (!debug_flag(kDbgRansacStats)) return nullptr;
+    if (!g_ransac_stats) {
+        if (hipMalloc((void**)&g_ransac_stats, 3 * sizeof(unsigned long long)) != hipSuccess) { g_ransac_stats = nullptr; return nullptr; }
+        (void)hipMemset(g_ransac_stats, 0, 3 * sizeof(unsigned long long));
+    }
+    return g_ransac_stats;
+}
 }
 
 extern "C" {
@@ -119,7 +128,7 @@ int pcreg_debug_set(const char* key, int value) {
     static const char* const names[pcreg::kDbgCount] = {"knn_exact", "match_exact", "match_force_fallback", "ransac_fused", "ransac_nolane",
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
-                                                        "knn_stats"};
+                                                        "knn_stats", "ransac_pass2", "ransac_stats"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -148,6 +157,18 @@ int pcreg_debug_knn_stats(long long out[4], int reset) {
     PCREG_HIP(hipMemcpy(h, pcreg::g_knn_stats, sizeof h, hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; ++k) out[k] = (long long)h[k];
     if (reset) PCREG_HIP(hipMemset(pcreg::g_knn_stats, 0, sizeof h));
+    return PCREG_OK;
+}
+
+int pcreg_debug_ransac_stats(long long out[3], int reset) {
+    PCREG_ARG(out != nullptr);
+    for (int k = 0; k < 3; ++k) out[k] = 0;
+    if (!pcreg::g_ransac_stats) return PCREG_OK;              // "ransac_stats" was never on
+    PCREG_HIP(hipDeviceSynchronize());
+    unsigned long long h[3];
+    PCREG_HIP(hipMemcpy(h, pcreg::g_ransac_stats, sizeof h, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) out[k] = (long long)h[k];
+    if (reset) PCREG_HIP(hipMemset(pcreg::g_ransac_stats, 0, sizeof h));
     return PCREG_OK;
 }
 

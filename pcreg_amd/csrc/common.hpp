@@ -73,6 +73,9 @@ enum DebugKey {
     kDbgFinalBatchMB,          // "final_batch_mb": pcreg_final_stage's descriptor memory bound in MB instead of 4 GB (0 = the default)
     kDbgKnnNoCull,             // "knn_nocull": the point search's candidate kernel visits every model tile (no culling)
     kDbgKnnStats,              // "knn_stats": the point search counts what it visits (pcreg_debug_knn_stats)
+    kDbgRansacPass2,           // "ransac_pass2": the staged chain's second scoring pass -- 0 by shape (bounded_pays), 1 always the full pass,
+                               // 2 always the bounded pass where it is allowed
+    kDbgRansacStats,           // "ransac_stats": the bounded pass counts what it scans (pcreg_debug_ransac_stats)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -84,6 +87,9 @@ unsigned long long* match_stats_dev();
 // Device counters of the point search (knn_fast.hip), or null while "knn_stats" is off:
 //   [0] searches   [1] visited (query block, model tile) pairs   [2] nominal pairs (q_blocks x n_tiles)   [3] queries sent to the tail
 unsigned long long* knn_stats_dev();
+// Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
+//   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
+unsigned long long* ransac_stats_dev();
 #ifdef PCREG_EXPERIMENTS
 static inline int pcreg_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline const char* pcreg_env_str(const char* name) { return getenv(name); }

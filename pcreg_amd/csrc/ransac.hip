@@ -20,6 +20,8 @@
 // No data leaves the chip between the sample fit and the final inlier list.
 #include "common.hpp"
 #include <cfloat>
+#include <cstddef>
+#include <cstdio>
 #include <cstdlib>
 
 namespace pcreg {
@@ -1036,6 +1038,18 @@ constexpr int kRec = 16;                        // doubles per correspondence re
 #define PCREG_SCHUNK 32
 #endif
 constexpr int kSChunk = PCREG_SCHUNK;                     // hypotheses per workgroup
+// bounded second pass (rs_bounded_kernel): decision blocks of kSS * 64 correspondences, up to kBSeeds refits scored
+// in full first, kBBuckets residual buckets for the pass's order
+constexpr int kBBlk = kSS * 64, kBSeeds = 64, kBBuckets = 16, kBChunk = 4;
+struct BCtr {
+    int32_t lb;                  // largest exact refit count known so far (atomic max; only grows)
+    int32_t hstar;               // the refit whose residuals order the pass (first maximum of cnt1 among the refits)
+    int32_t hist[kBBuckets], cursor[kBBuckets];
+    int32_t seed_cnt[kBSeeds];   // exact counts of the seed refits (summed over the point blocks)
+    unsigned long long stats[3]; // this call's counters in ransac_stats_dev()'s layout (EXPERIMENTS print)
+    int32_t seed_h[kBSeeds];     // the seed refits (-1: none); written every call
+};
+constexpr int kBCtrClearWords = (int)(offsetof(BCtr, seed_h) / 4);
 
 struct StagedArgs {
     RansacArgs a;
@@ -1066,6 +1080,12 @@ struct StagedArgs {
     int n32;                     // row length of c32
     float* T32a; float* T32b;    // [iters][16]: R (9, rows), t' (3), thlo, thhi, 2 pad -- sample fits / refits
     int use_f32;
+    // bounded second pass (rs_bounded_kernel): c32 permuted into "likely outliers first" order, the original index of
+    // every position, each correspondence's order bucket, and the pass's counters (cleared by rs_stage1_kernel)
+    float* p32;                  // [6][n32]
+    int32_t* perm;               // [n32]
+    unsigned char* bkt;          // [n32]
+    void* bctr;                  // BCtr
 };
 
 __device__ __forceinline__ int staged_n(const RansacArgs& a) { return min(a.n_dev ? *a.n_dev : a.n_cap, a.n_cap); }
@@ -1202,6 +1222,7 @@ __global__ __launch_bounds__(256) void rs_stage1_kernel(StagedArgs sa, int n_fit
         if (blockIdx.x == 0) {
             if (threadIdx.x == 0) *sa.n_pass = 0;
             if (threadIdx.x < 64 + 2) ((int32_t*)sa.sel_ctr)[threadIdx.x] = 0;
+            if (sa.bctr && threadIdx.x < kBCtrClearWords) ((int32_t*)sa.bctr)[threadIdx.x] = 0;
         }
         rs_fit1_body(sa, blockIdx.x);
     } else {
@@ -1524,6 +1545,281 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
 #pragma unroll
         for (int w = 0; w < kSW; ++w) c += s_cnt[w][hl];
         if (acc) { if (c) atomicAdd(&acc[h0 + hl], c); } else sa.part[(size_t)blockIdx.x * a.iters + h0 + hl] = c;
+    }
+}
+
+// ---- bounded second pass --------------------------------------------------------------------------------------
+// The selection needs three things from the refit counts (ransac.m:53-98): numSuccess = #(cnt2 >= thInlr), max(cnt2) and the
+// first index that reaches it; the inlier list is recomputed from that refit's transform.  A refit whose scan has met `in`
+// inliers and `out` outliers so far has in <= cnt2 <= n - out.  With LB the exact count of SOME refit (so LB <= max):
+//   out > n - LB                     ->  cnt2 < LB <= max: it is neither the maximum nor tied with it;
+//   in >= thInlr  /  out > n - thInlr  ->  it succeeds / fails.
+// Once "cannot win" and one of the other two hold, the rest of its scan decides nothing: it stores thInlr (success) or 0
+// (failure), which the selection counts right and, both being below the maximum, never picks.  A refit with cnt2 >= LB -- the
+// maximum and every tie of it -- never meets out > n - LB, scans to the end and stores its exact count.  LB only grows and every
+// value it takes is an exact count, so a stale read only stops refits later.
+// Three launches: rs_bprep (seed refits scored in full + order buckets), rs_bscatter (the permuted copy), rs_bounded.
+
+// inliers of refit h among the kBBlk correspondences at positions [base, base + kBBlk) of an order (x32: the fp32 centred copy
+// in that order; perm: the original index of each position, null = identity): rs_score32_kernel's screen and its fp64
+// re-score on the raw coordinates per slot, so every decision is the fp64 one.  q: the block's rows (NaN in lanes past n).
+__device__ __forceinline__ void rs_load_block(const StagedArgs& sa, const float* __restrict__ x32, int base, int n, float (&q)[kSS][6]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int s = 0; s < kSS; ++s) {
+        const int i = base + s * 64 + lane;
+        const bool act = i < n;
+        const int ii = act ? i : 0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) q[s][c] = x32[(size_t)c * sa.n32 + ii];
+        if (!act) q[s][0] = __builtin_nanf("");
+    }
+}
+__device__ __forceinline__ int rs_block_count(const StagedArgs& sa, const float* __restrict__ x32, const int32_t* __restrict__ perm,
+                                              int base, int n, const float (&q)[kSS][6], const float (&T)[12], float thlo, float thhi,
+                                              int h) {
+    const RansacArgs& a = sa.a;
+    const int lane = threadIdx.x & 63;
+    unsigned long long b[kSS], band = 0ull;
+#pragma unroll
+    for (int s = 0; s < kSS; ++s) {
+        const float d = sqdist32(q[s], T);
+        b[s] = __ballot(d < thlo);
+        band |= __ballot(d <= thhi) ^ b[s];
+    }
+    if (band != 0ull) {                                  // wave-uniform; the rolled loop as in rs_score32_kernel
+        double T64[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T64[k] = a.TF[(size_t)h * 12 + k];
+#pragma unroll 1
+        for (int s = 0; s < kSS; ++s) {
+            const int i = base + s * 64 + lane;
+            const bool act = i < n;
+            const int ii = act ? i : 0;
+            float qq[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) qq[c] = x32[(size_t)c * sa.n32 + ii];
+            if (!act) qq[0] = __builtin_nanf("");
+            const float d = sqdist32(qq, T);
+            if ((__ballot(d <= thhi) ^ __ballot(d < thlo)) != 0ull) {
+                const int oi = perm ? perm[ii] : ii;
+                double p[6];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { p[c] = a.p1[oi + (size_t)c * a.ld]; p[3 + c] = a.p2[oi + (size_t)c * a.ld]; }
+                const unsigned long long bb = __ballot((sqdist(p, T64) < a.thDist) & act);
+#pragma unroll
+                for (int s2 = 0; s2 < kSS; ++s2) if (s2 == s) b[s2] = bb;
+            }
+        }
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < kSS; ++s) cnt += __popcll(b[s]);
+    return cnt;
+}
+
+// (cnt1 << 32 | ~index) maximised over the refits in [lo, hi) that exist (v2): the first maximum of cnt1; 0 = none.  One wave.
+__device__ __forceinline__ unsigned long long rs_cnt1_key(const StagedArgs& sa, int lo, int hi) {
+    unsigned long long key = 0ull;
+#pragma unroll 4
+    for (int p = lo + (int)(threadIdx.x & 63); p < hi; p += 64) {      // branch-free: the loads of all trips issue together
+        const unsigned char v = sa.v2[p];
+        const unsigned long long k = ((unsigned long long)(unsigned)sa.a.cnt1[p] << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)p);
+        key = v && k > key ? k : key;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long ot = __shfl_xor(key, o); key = ot > key ? ot : key; }
+    return key;
+}
+__device__ __forceinline__ int rs_key_index(unsigned long long key) { return key ? (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : -1; }
+
+// order bucket of a correspondence from its fp32 residual d under refit hstar: 0 for d >= thDist, then 1 .. kBBuckets - 1 by
+// DEScending d (speed only: the counts do not depend on the order)
+__device__ __forceinline__ int rs_order_bucket(float d, float th) {
+    if (!(d < th) || !(th < 3.0e38f)) return 0;
+    const int k = (int)((th - d) * ((float)(kBBuckets - 1) / th));
+    return 1 + min(kBBuckets - 2, max(k, 0));
+}
+
+// workgroups [0, n_seed_wg): one wave per (seed, block of kBBlk correspondences) -- seed s is the first maximum of cnt1 in the
+// s-th of S slices of the refits, scored in stored order, its count ADDED to seed_cnt[s]; the rest: 256 correspondences each,
+// their order bucket under hstar (the first maximum of cnt1 over all refits) and the buckets' sizes
+__global__ __launch_bounds__(256) void rs_bprep_kernel(StagedArgs sa, int n_seed_wg, int S, int nbc) {
+    const RansacArgs& a = sa.a;
+    BCtr* bc = (BCtr*)sa.bctr;
+    const int n = staged_n(a);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((int)blockIdx.x < n_seed_wg) {
+        const int u = blockIdx.x * 4 + wave;
+        const int s = u / nbc, blk = u - s * nbc;
+        if (s >= S || (blk > 0 && blk * kBBlk >= n)) return;
+        const int lo = (int)((long long)s * a.iters / S), hi = (int)((long long)(s + 1) * a.iters / S);
+        const int h = rs_key_index(rs_cnt1_key(sa, lo, hi));
+        if (blk == 0 && lane == 0) bc->seed_h[s] = h;
+        if (h < 0 || blk * kBBlk >= n) return;
+        float q[kSS][6];
+        rs_load_block(sa, sa.c32, blk * kBBlk, n, q);
+        const float* row = sa.T32b + (size_t)h * 16;
+        float T[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = row[k];
+        const int c = rs_block_count(sa, sa.c32, nullptr, blk * kBBlk, n, q, T, row[12], row[13], h);
+        if (lane == 0 && c) atomicAdd(&bc->seed_cnt[s], c);
+        return;
+    }
+    const int ob = blockIdx.x - n_seed_wg;
+    __shared__ unsigned long long s_key[4];
+    __shared__ int s_hist[kBBuckets];
+    if (threadIdx.x < kBBuckets) s_hist[threadIdx.x] = 0;
+    {   // every workgroup reads all of cnt1 / v2 (10^4 refits: 50 KB from L2), four refits per load, branch-free
+        unsigned long long k = 0ull;
+        const int n4 = a.iters >> 2;
+        const int4* c4 = (const int4*)a.cnt1;                   // both 256-byte aligned (workspace layout)
+        const unsigned* v4 = (const unsigned*)sa.v2;
+#pragma unroll 4
+        for (int p4 = threadIdx.x; p4 < n4; p4 += 256) {
+            const int4 c = c4[p4];
+            const unsigned v = v4[p4];
+            const int cc[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned p = (unsigned)(4 * p4 + e);
+                const unsigned long long ke = ((v >> (8 * e)) & 0xFFu) ? ((unsigned long long)(unsigned)cc[e] << 32) | (0xFFFFFFFFu - p) : 0ull;
+                k = ke > k ? ke : k;
+            }
+        }
+        for (int p = 4 * n4 + (int)threadIdx.x; p < a.iters; p += 256)
+            if (sa.v2[p]) { const unsigned long long ke = ((unsigned long long)(unsigned)a.cnt1[p] << 32) | (0xFFFFFFFFu - (unsigned)p); k = ke > k ? ke : k; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long ot = __shfl_xor(k, o); k = ot > k ? ot : k; }
+        if (lane == 0) s_key[wave] = k;
+    }
+    __syncthreads();
+    unsigned long long key = s_key[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) key = s_key[w] > key ? s_key[w] : key;
+    const int hs = rs_key_index(key);
+    if (ob == 0) {
+        if (threadIdx.x == 0) bc->hstar = hs;
+        if ((int)threadIdx.x >= S && threadIdx.x < kBSeeds) bc->seed_h[threadIdx.x] = -1;
+    }
+    const int i = ob * 256 + threadIdx.x;
+    if (i < n) {
+        int bk = 0;
+        if (hs >= 0) {
+            float q[6], T[12];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) q[c] = sa.c32[(size_t)c * sa.n32 + i];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = sa.T32b[(size_t)hs * 16 + k];
+            bk = rs_order_bucket(sqdist32(q, T), (float)a.thDist);
+        }
+        sa.bkt[i] = (unsigned char)bk;
+        atomicAdd(&s_hist[bk], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < kBBuckets && s_hist[threadIdx.x]) atomicAdd(&bc->hist[threadIdx.x], s_hist[threadIdx.x]);
+}
+
+// the permuted copy: bucket by bucket, any order inside a bucket (arrival order: speed only)
+__global__ __launch_bounds__(256) void rs_bscatter_kernel(StagedArgs sa) {
+    BCtr* bc = (BCtr*)sa.bctr;
+    const int n = staged_n(sa.a);
+    __shared__ int s_cnt[kBBuckets], s_off[kBBuckets];
+    if (threadIdx.x < kBBuckets) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int bk = 0, r = 0;
+    if (i < n) { bk = sa.bkt[i]; r = atomicAdd(&s_cnt[bk], 1); }
+    __syncthreads();
+    if (threadIdx.x < kBBuckets) {
+        int off = 0;
+        for (int k = 0; k < (int)threadIdx.x; ++k) off += bc->hist[k];
+        s_off[threadIdx.x] = off + (s_cnt[threadIdx.x] ? atomicAdd(&bc->cursor[threadIdx.x], s_cnt[threadIdx.x]) : 0);
+    }
+    __syncthreads();
+    if (i < n) {                     // pos < hist[0] + ... + hist[bk] <= n
+        const int pos = s_off[bk] + r;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) sa.p32[(size_t)c * sa.n32 + pos] = sa.c32[(size_t)c * sa.n32 + i];
+        sa.perm[pos] = i;
+    }
+}
+
+// One wave per chunk of C refits (lane j: refit h0 + j's fp32 row and inlier count), walking the blocks of the permuted order;
+// the block's rows are loaded once for all the chunk's live refits, the next block's while this one is scored.  Between blocks
+// the decision rule above, lane-parallel.  Seed refits store their exact counts from rs_bprep.  stats (null: off): passes, units
+// scanned (seed refits included), units of a full pass, added up (ransac_stats_dev()).
+template <int C>
+__global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned long long* __restrict__ stats) {
+    static_assert(C >= 1 && C <= 64, "one lane per refit");
+    const RansacArgs& a = sa.a;
+    BCtr* bc = (BCtr*)sa.bctr;
+    const int n = staged_n(a);
+    const int lane = threadIdx.x;
+    const int thInlr = matlab_round_i(a.ratio * (double)n);
+    const int h0 = blockIdx.x * C, hl = h0 + lane;
+    const bool mine = lane < C && hl < a.iters;
+    const int nb = (n + kBBlk - 1) / kBBlk;
+    const int sh = bc->seed_h[lane], sc = bc->seed_cnt[lane];
+    int lb = sh >= 0 ? sc : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lb = max(lb, __shfl_xor(lb, o));
+    bool live = mine && sa.v2[hl] != 0;
+    const unsigned long long exist = __ballot(live);
+    int seedc = -1;
+    for (int s = 0; s < kBSeeds; ++s) {
+        const int hs = __builtin_amdgcn_readlane(sh, s), cs = __builtin_amdgcn_readlane(sc, s);
+        if (hs == hl) seedc = cs;
+    }
+    if (live && seedc >= 0) { a.cnt2[hl] = seedc; live = false; }
+    unsigned long long active = __ballot(live);
+    const unsigned long long seeded = exist & ~active;
+    float comp[14];
+#pragma unroll
+    for (int k = 0; k < 14; ++k) comp[k] = live ? sa.T32b[(size_t)hl * 16 + k] : 0.0f;
+    int in_v = 0;
+    unsigned long long units = 0ull;
+    float qa[kSS][6], qb[kSS][6];
+    if (active != 0ull && nb > 0) rs_load_block(sa, sa.p32, 0, n, qa);
+    // LB is re-read between blocks, but an agent-scope load travels past the XCD's L2: each read is consumed two blocks after
+    // it was issued (lbr[0] / lbr[1] alternate with the blocks), so its latency hides behind the scoring
+    int lbr0 = lb, lbr1 = lb;
+    auto step = [&](int blk, const float (&cur)[kSS][6], float (&nxt)[kSS][6], int& lbr) {
+        if (blk + 1 < nb) rs_load_block(sa, sa.p32, (blk + 1) * kBBlk, n, nxt);
+        const int base = blk * kBBlk;
+        for (unsigned long long m = active; m != 0ull; m &= m - 1ull) {
+            const int j = __builtin_ctzll(m);
+            float T[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(comp[k]), j));
+            const float thlo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(comp[12]), j));
+            const float thhi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(comp[13]), j));
+            const int c = rs_block_count(sa, sa.p32, sa.perm, base, n, cur, T, thlo, thhi, h0 + j);
+            in_v += lane == j ? c : 0;
+        }
+        units += (unsigned long long)__popcll(active);
+        lb = max(lb, lbr);
+        lbr = __hip_atomic_load(&bc->lb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int out_v = min(n, base + kBBlk) - in_v;
+        const bool stop = ((active >> lane) & 1ull) && out_v > n - lb && (in_v >= thInlr || out_v > n - thInlr);
+        if (stop) a.cnt2[hl] = in_v >= thInlr ? thInlr : 0;
+        active &= ~__ballot(stop);
+    };
+    for (int blk = 0; blk < nb && active != 0ull; blk += 2) {
+        step(blk, qa, qb, lbr0);
+        if (blk + 1 < nb && active != 0ull) step(blk + 1, qb, qa, lbr1);
+    }
+    const bool full = (active >> lane) & 1ull;           // scanned to the end: the exact count
+    if (full) a.cnt2[hl] = in_v;
+    int mx = full ? in_v : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+    if (lane == 0 && active != 0ull && mx > lb) __hip_atomic_fetch_max(&bc->lb, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (stats && lane == 0) {
+        if (blockIdx.x == 0) atomicAdd(&stats[0], 1ull);
+        atomicAdd(&stats[1], units + (unsigned long long)__popcll(seeded) * (unsigned long long)nb);
+        atomicAdd(&stats[2], (unsigned long long)__popcll(exist) * (unsigned long long)nb);
     }
 }
 
@@ -2849,6 +3145,14 @@ __global__ void calc_dists_kernel(const double* T16, const double* p1, const dou
 // Measured (round 4, same box, REFINE): n = 2100 / 3000 / 4000 with 10^4 hypotheses 0.206 / 0.244 / 0.267 ms tiled against
 // 0.149 / 0.158 / 0.169 staged; (4000, 10^3) 0.099 against 0.119, (2500, 2 x 10^3) 0.079 against 0.114.
 static bool staged_pays(int n_cap, int iters) { return n_cap >= 4096 || (n_cap >= kStagedMinN && (long long)n_cap * iters >= 20000000LL); }
+// The bounded second pass pays where the full pass's work (n x iterNum pair scores, ~2.4 per ps on one idle MI355X) exceeds
+// the bounded pass's floor: a refit near the maximum walks all n / 512 blocks one after another in one wave (~1.4 us each), plus
+// ~30 us of seeding, ordering and launches.  Both measured at the bench's shape (n 32558, iterNum 10^4: 135 against 120 us) and
+// at the shapes of DESIGN 4.9's table; 10 % margin.
+static bool bounded_pays(int n_cap, int iters) {
+    const double full_us = (double)n_cap * (double)iters / 2.4e6, bounded_us = 1.4 * (double)((n_cap + kBBlk - 1) / kBBlk) + 30.0;
+    return full_us > 1.1 * bounded_us;
+}
 static size_t staged_slots_cap(int n_cap) { return (size_t)((n_cap + kSPts - 1) / kSPts) * (kSPts / 64); }
 static size_t staged_chunks_cap(int n_cap) { return (staged_slots_cap(n_cap) + kMomSlots - 1) / kMomSlots; }
 static size_t staged_extra_bytes(size_t h, int n_cap) {    // T1 | mom | part | v1 | pass1 | v2 | cert | dense | lane-path buffers
@@ -2859,7 +3163,9 @@ static size_t staged_extra_bytes(size_t h, int n_cap) {    // T1 | mom | part | 
         b += align_up(staged_slots_cap(n_cap) * 64 * 6 * sizeof(float), 256) + 2 * align_up(h * 16 * sizeof(float), 256) +
              align_up(h * staged_slots_cap(n_cap) * 8, 256) + align_up(staged_slots_cap(n_cap) * 64 * kRec * sizeof(double) + 256, 256) +
              align_up(staged_chunks_cap(n_cap) * h * 15 * sizeof(double), 256) + align_up(h * sizeof(int32_t), 256) + 256 +
-             align_up(staged_slots_cap(n_cap) * 2 * 256 * sizeof(uint4), 256);
+             align_up(staged_slots_cap(n_cap) * 2 * 256 * sizeof(uint4), 256) +
+             /* bounded second pass: p32, perm, bkt, BCtr */
+             align_up(staged_slots_cap(n_cap) * 64 * (6 * sizeof(float) + sizeof(int32_t) + 1) + 3 * 256, 256) + align_up(sizeof(BCtr), 256);
     return b;
 }
 size_t ransac_workspace_bytes(int iters, int B, int n_cap) {
@@ -2973,6 +3279,10 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         sa.c32 = (float*)w; w += align_up((size_t)sa.n32 * 6 * sizeof(float), 256);
         sa.T32a = (float*)w; w += align_up(h * 16 * sizeof(float), 256);
         sa.T32b = (float*)w; w += align_up(h * 16 * sizeof(float), 256);
+        sa.p32 = (float*)w; w += align_up((size_t)sa.n32 * 6 * sizeof(float), 256);
+        sa.perm = (int32_t*)w; w += align_up((size_t)sa.n32 * sizeof(int32_t), 256);
+        sa.bkt = (unsigned char*)w; w += align_up((size_t)sa.n32, 256);
+        sa.bctr = w; w += align_up(sizeof(BCtr), 256);
         sa.use_lane = a.refine && !debug_flag(kDbgRansacNoLane);
         sa.use_f32 = !debug_flag(kDbgRansacF64Score);
         int pb = (n_cap + kSPts - 1) / kSPts; if (pb > kSMaxPB) pb = kSMaxPB; if (pb < 1) pb = 1;
@@ -3011,7 +3321,35 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
             fold_finish = !part && n_cap <= kSelBlocks * kSelPerThread * kSelThreads;        // ransac_select_multi_kernel does rs_finish's job
             // with the finish folded into the selection the second pass ADDS its point blocks' counts into cnt2 (zeroed by rs_pass1;
             // integer sums are order-free) instead of leaving pb partial rows that every selecting workgroup would have to sum
-            if (sa.use_f32)
+            // the bounded pass where only what the selection needs is asked for and the shape pays; per-iteration refined
+            // counts, the sharded split and the fp64-only scoring take the full pass; "ransac_pass2" 1 / 2 forces either side
+            const int p2mode = debug_flag(kDbgRansacPass2);
+            const bool bounded = fold_finish && sa.use_f32 && !iter_inl_ref && p2mode != 1 && (p2mode == 2 || bounded_pays(n_cap, it));
+            if (bounded) {
+                const int S = std::min(kBSeeds, it), nbc = (n_cap + kBBlk - 1) / kBBlk;
+                const int n_seed_wg = (S * nbc + 3) / 4, n_ord_wg = (n_cap + 255) / 256;
+                unsigned long long* stats = ransac_stats_dev();          // "ransac_stats": process-wide counters
+                hipLaunchKernelGGL(rs_bprep_kernel, dim3((unsigned)(n_seed_wg + n_ord_wg)), dim3(256), 0, st, sa, n_seed_wg, S, nbc);
+                hipLaunchKernelGGL(rs_bscatter_kernel, dim3((unsigned)n_ord_wg), dim3(256), 0, st, sa);
+#ifdef PCREG_EXPERIMENTS
+                // PCREG_RANSAC_DEBUG=1: print this call's scanned fraction.  It synchronises the stream here, so it must not be set
+                // while a graph is being captured.  PCREG_RANSAC_BCHUNK: refits per wave (2 / 4 / 8).
+                const int dbg = PCREG_EXP_ENV("PCREG_RANSAC_DEBUG", 0), chunk = PCREG_EXP_ENV("PCREG_RANSAC_BCHUNK", kBChunk);
+                unsigned long long* kst = dbg ? ((BCtr*)sa.bctr)->stats : stats;
+                if (chunk == 8) hipLaunchKernelGGL(rs_bounded_kernel<8>, dim3((unsigned)((it + 7) / 8)), dim3(64), 0, st, sa, kst);
+                else if (chunk == 2) hipLaunchKernelGGL(rs_bounded_kernel<2>, dim3((unsigned)((it + 1) / 2)), dim3(64), 0, st, sa, kst);
+                else hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, kst);
+                if (dbg) {
+                    unsigned long long u[3] = {0, 0, 0};
+                    PCREG_HIP(hipMemcpyAsync(u, kst, sizeof u, hipMemcpyDeviceToHost, st));
+                    PCREG_HIP(hipStreamSynchronize(st));
+                    fprintf(stderr, "[pcreg] ransac bounded pass 2: iters=%d n_cap=%d chunk=%d (refit, block) units scanned %llu of %llu (%.4f)\n", it, n_cap,
+                            chunk == 8 || chunk == 2 ? chunk : kBChunk, u[1], u[2], u[2] ? (double)u[1] / (double)u[2] : 0.0);
+                }
+#else
+                hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, stats);
+#endif
+            } else if (sa.use_f32)
                 hipLaunchKernelGGL(rs_score32_kernel<false>, sgrid, dim3(kSW * 64), 0, st, sa, (const double*)a.TF, (const float*)sa.T32b, (const unsigned char*)sa.v2,
                                    fold_finish ? a.cnt2 : (int32_t*)nullptr);
             else
