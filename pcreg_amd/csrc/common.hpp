@@ -102,6 +102,16 @@ static inline const char* pcreg_env_str(const char* name) { return getenv(name);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// One walk over a caller-allocated workspace: a layout function takes its buffers in order; the size
+// function runs it with base == nullptr (measure only: every pointer null), the launcher with the caller's block.
+struct WsWalk {
+    char* base; size_t off = 0;
+    explicit WsWalk(void* b) : base((char*)b) {}
+    void* take_bytes(size_t bytes) { void* p = base ? base + off : nullptr; off += bytes; return p; }   // the fixed 256 / 512 / 1024 slots
+    template <class T> T* take(size_t count, size_t align = 256) { return (T*)take_bytes(align_up(count * sizeof(T), align)); }
+    size_t bytes() const { return off; }
+};
+
 // ---- kernel launchers implemented in the .hip files (device pointers, async) --------
 struct RansacDims { int n_cap; int iters; int B; };
 

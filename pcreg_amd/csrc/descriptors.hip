@@ -1014,17 +1014,37 @@ __global__ void desc_index_kernel(const int32_t* __restrict__ slot, const double
 
 }  // namespace
 
-// workspace: Grid | Edges | bbox partials | cell_total | cell_start | cell_id [P] | counts [tiles][kMaxCells]
-//            | sorted_idx [P] | sx sy sz [P] (f64) | f4 [P] (float4) | staging rows u16 [S][980] | valid [S] | slot [S]
-//            | block counters | keypoint cell counts / starts / fill | keypoint cell [S] | perm [S]
-size_t descriptors_workspace_bytes(int P, int S) {
-    size_t p = (size_t)(P > 0 ? P : 1), s = (size_t)(S > 0 ? S : 1);
-    size_t tiles = (p + kSortTile - 1) / kSortTile;
-    return 256 + 1024 + align_up(512 * 6 * 8, 256) + 2 * align_up(((size_t)kMaxCells + 1) * 4, 256) + align_up(p * 4, 256) +
-           align_up(tiles * kMaxCells * 4, 256) + align_up(p * 4, 256) + 3 * align_up(p * 8, 256) + align_up(p * 16, 256) +
-           align_up(s * ND * 2, 256) + 2 * align_up(s * 4, 256) + align_up((s / 256 + 2) * 4, 256) +
-           3 * align_up(((size_t)kMaxCells + 1) * 4, 256) + 2 * align_up(s * 4, 256);
+// the workspace of launch_descriptors, walked once
+struct DescWs {
+    Grid* grid; Edges* edges_dev; double* bpart;                       // the cell grid, the bin edges, bounding-box partials
+    int32_t* cell_total; int32_t* cell_start; int32_t* cell_id;         // points per cell and their starts; the cell of every point [P]
+    int32_t* counts; int tiles;                                         // [tiles][kMaxCells]
+    int32_t* sorted_idx; double* sx; double* sy; double* sz; float4* f4;        // the cloud in cell order [P]: index, f64 and float4 copies
+    uint16_t* stage; int32_t* valid; int32_t* slot; int32_t* bcnt;      // staging rows [S][ND], survivors, their slots, block counters
+    int32_t* kc_total; int32_t* kc_start; int32_t* kc_fill;             // keypoint cell counts / starts / fill
+    int32_t* kcell; int32_t* perm;                                      // the cell of every keypoint, keypoints in cell order [S]
+};
+static DescWs desc_ws_layout(int P, int S, void* base, size_t* bytes) {
+    const size_t p = (size_t)std::max(P, 1), s = (size_t)std::max(S, 1), cells = (size_t)kMaxCells + 1;
+    WsWalk w(base);
+    DescWs d{};
+    d.tiles = (int)((p + kSortTile - 1) / kSortTile);
+    static_assert(sizeof(Edges) <= 1024, "Edges fits its slot");
+    d.grid = (Grid*)w.take_bytes(256); d.edges_dev = (Edges*)w.take_bytes(1024); d.bpart = w.take<double>(512 * 6);
+    d.cell_total = w.take<int32_t>(cells); d.cell_start = w.take<int32_t>(cells);
+    d.cell_id = w.take<int32_t>(p);
+    d.counts = w.take<int32_t>((size_t)d.tiles * kMaxCells);
+    d.sorted_idx = w.take<int32_t>(p);
+    d.sx = w.take<double>(p); d.sy = w.take<double>(p); d.sz = w.take<double>(p);
+    d.f4 = w.take<float4>(p);
+    d.stage = w.take<uint16_t>(s * ND);
+    d.valid = w.take<int32_t>(s); d.slot = w.take<int32_t>(s); d.bcnt = w.take<int32_t>(s / 256 + 2);
+    // kc_total | kc_start | kc_fill stay adjacent and directly in front of kcell: launch_descriptors clears the three with one memset
+    d.kc_total = w.take<int32_t>(cells); d.kc_start = w.take<int32_t>(cells); d.kc_fill = w.take<int32_t>(cells);
+    d.kcell = w.take<int32_t>(s); d.perm = w.take<int32_t>(s);
+    *bytes = w.bytes(); return d;
 }
+size_t descriptors_workspace_bytes(int P, int S) { size_t b; (void)desc_ws_layout(P, S, nullptr, &b); return b; }
 
 // single_mode: 0 = double data; 1 = single data, keypoints single; 2 = single cloud, double keypoints (MATLAB: "single wins",
 // but getLocalPoints.m:8-10's xLim = c + [-R, R] is then formed in double).  The inputs are double arrays either way
@@ -1040,48 +1060,23 @@ int launch_descriptors(const double* pts, int P, int ld, const double* kp, int S
     if (S == 0 || P == 0) return PCREG_OK;
     // desc_kernel addresses the sorted cloud as scalar base + 32-bit byte offset (16 P bytes of float4 copies)
     if (P >= (1 << 28)) { set_error("descriptors: clouds of 2^28 points or more are not supported (got %d)", P); return PCREG_E_ARG; }
-    size_t need = descriptors_workspace_bytes(P, S);
+    size_t need; const DescWs L = desc_ws_layout(P, S, ws, &need);
     if (ws_bytes < need) { set_error("descriptor workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
-    size_t p = (size_t)P, s = (size_t)S;
-    const int tiles = (P + kSortTile - 1) / kSortTile;
-    char* w = (char*)ws;
-    Grid* grid = (Grid*)w;                  w += 256;
-    Edges* edges_dev = (Edges*)w;           w += 1024;
-    static_assert(sizeof(Edges) <= 1024, "Edges fits its slot");
-    double* bpart = (double*)w;             w += align_up(512 * 6 * 8, 256);
-    int32_t* cell_total = (int32_t*)w;      w += align_up(((size_t)kMaxCells + 1) * 4, 256);
-    int32_t* cell_start = (int32_t*)w;      w += align_up(((size_t)kMaxCells + 1) * 4, 256);
-    int32_t* cell_id = (int32_t*)w;         w += align_up(p * 4, 256);
-    int32_t* counts = (int32_t*)w;          w += align_up((size_t)tiles * kMaxCells * 4, 256);
-    int32_t* sorted_idx = (int32_t*)w;      w += align_up(p * 4, 256);
-    double* sx = (double*)w;                w += align_up(p * 8, 256);
-    double* sy = (double*)w;                w += align_up(p * 8, 256);
-    double* sz = (double*)w;                w += align_up(p * 8, 256);
-    float4* f4 = (float4*)w;                w += align_up(p * 16, 256);
-    uint16_t* stage = (uint16_t*)w;         w += align_up(s * ND * 2, 256);
-    int32_t* valid = (int32_t*)w;           w += align_up(s * 4, 256);
-    int32_t* slot = (int32_t*)w;            w += align_up(s * 4, 256);
-    int32_t* bcnt = (int32_t*)w;            w += align_up((s / 256 + 2) * 4, 256);
-    int32_t* kc_total = (int32_t*)w;        w += align_up(((size_t)kMaxCells + 1) * 4, 256);
-    int32_t* kc_start = (int32_t*)w;        w += align_up(((size_t)kMaxCells + 1) * 4, 256);
-    int32_t* kc_fill = (int32_t*)w;         w += align_up(((size_t)kMaxCells + 1) * 4, 256);
-    int32_t* kcell = (int32_t*)w;           w += align_up(s * 4, 256);
-    int32_t* perm = (int32_t*)w;
-
+    const int tiles = L.tiles;
     int nb = (P + kBlock * 16 - 1) / (kBlock * 16); if (nb > 512) nb = 512; if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(bbox_partial_d_kernel, dim3(nb), dim3(kBlock), 0, st, pts, P, ld, bpart);
-    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, bpart, nb, o.R, grid, PCREG_EXP_ENV("PCREG_DESC_SUBDIV", -1));
-    PCREG_HIP(hipMemsetAsync(counts, 0, (size_t)tiles * kMaxCells * 4, st));
-    hipLaunchKernelGGL(grid_count_kernel, dim3(tiles), dim3(kBlock), 0, st, pts, P, ld, grid, cell_id, counts);
-    hipLaunchKernelGGL(grid_cell_prefix_kernel, dim3((kMaxCells + 1 + 255) / 256), dim3(256), 0, st, counts, tiles, grid, cell_total);
-    hipLaunchKernelGGL(grid_cell_scan_kernel, dim3(1), dim3(256), 0, st, cell_total, cell_start);
-    hipLaunchKernelGGL(grid_scatter_kernel, dim3(tiles), dim3(kBlock), 0, st, pts, P, ld, cell_id, counts, cell_start,
-                       sorted_idx, sx, sy, sz, (const Grid*)grid, single_mode != 0 ? 1 : 0, f4);
-    // keypoints in cell order (kc_total | kc_start | kc_fill are contiguous: one memset)
-    PCREG_HIP(hipMemsetAsync(kc_total, 0, 3 * align_up(((size_t)kMaxCells + 1) * 4, 256), st));
-    hipLaunchKernelGGL(kp_count_kernel, dim3((S + 255) / 256), dim3(256), 0, st, kp, S, ldk, grid, kcell, kc_total);
-    hipLaunchKernelGGL(grid_cell_scan_kernel, dim3(1), dim3(256), 0, st, kc_total, kc_start);
-    hipLaunchKernelGGL(kp_scatter_kernel, dim3((S + 255) / 256), dim3(256), 0, st, kcell, S, kc_start, kc_fill, perm);
+    hipLaunchKernelGGL(bbox_partial_d_kernel, dim3(nb), dim3(kBlock), 0, st, pts, P, ld, L.bpart);
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, L.bpart, nb, o.R, L.grid, PCREG_EXP_ENV("PCREG_DESC_SUBDIV", -1));
+    PCREG_HIP(hipMemsetAsync(L.counts, 0, (size_t)tiles * kMaxCells * 4, st));
+    hipLaunchKernelGGL(grid_count_kernel, dim3(tiles), dim3(kBlock), 0, st, pts, P, ld, L.grid, L.cell_id, L.counts);
+    hipLaunchKernelGGL(grid_cell_prefix_kernel, dim3((kMaxCells + 1 + 255) / 256), dim3(256), 0, st, L.counts, tiles, L.grid, L.cell_total);
+    hipLaunchKernelGGL(grid_cell_scan_kernel, dim3(1), dim3(256), 0, st, L.cell_total, L.cell_start);
+    hipLaunchKernelGGL(grid_scatter_kernel, dim3(tiles), dim3(kBlock), 0, st, pts, P, ld, L.cell_id, L.counts, L.cell_start,
+                       L.sorted_idx, L.sx, L.sy, L.sz, (const Grid*)L.grid, single_mode != 0 ? 1 : 0, L.f4);
+    // keypoints in cell order (kc_total | kc_start | kc_fill are contiguous, kcell follows them: one memset)
+    PCREG_HIP(hipMemsetAsync(L.kc_total, 0, (size_t)((char*)L.kcell - (char*)L.kc_total), st));
+    hipLaunchKernelGGL(kp_count_kernel, dim3((S + 255) / 256), dim3(256), 0, st, kp, S, ldk, L.grid, L.kcell, L.kc_total);
+    hipLaunchKernelGGL(grid_cell_scan_kernel, dim3(1), dim3(256), 0, st, L.kc_total, L.kc_start);
+    hipLaunchKernelGGL(kp_scatter_kernel, dim3((S + 255) / 256), dim3(256), 0, st, L.kcell, S, L.kc_start, L.kc_fill, L.perm);
     PCREG_HIP(hipGetLastError());
 
     Edges ed; Edges32 e32;
@@ -1099,25 +1094,25 @@ int launch_descriptors(const double* pts, int P, int ld, const double* kp, int S
     size_t lds = (size_t)cap * sizeof(int);
     const int xcd_chunk = PCREG_EXP_ENV("PCREG_DESC_XCD", 1) ? (S + 7) / 8 : 0;
     const double R2T = sqrt_threshold(o.R);
-    hipLaunchKernelGGL(edges_store_kernel, dim3(1), dim3(1), 0, st, ed, edges_dev);
-    void* rows_out = rows_u16 ? (void*)rows_u16 : (void*)stage;
+    hipLaunchKernelGGL(edges_store_kernel, dim3(1), dim3(1), 0, st, ed, L.edges_dev);
+    void* rows_out = rows_u16 ? (void*)rows_u16 : (void*)L.stage;
     const int dbg = PCREG_EXP_ENV("PCREG_DESC_STOP", 0);
     if (single_mode) {
         PCREG_HIP(hipFuncSetAttribute((const void*)desc_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(desc_kernel<1>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, sx, sy, sz, (const float4*)f4, sorted_idx, cell_start, grid, kp, perm,
-                           S, ldk, o, (const Edges*)edges_dev, e32, R2T, single_mode == 1 ? 1 : 0, cap, dbg, xcd_chunk, rows_out, 1, valid, err_dev);
+        hipLaunchKernelGGL(desc_kernel<1>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, L.sx, L.sy, L.sz, (const float4*)L.f4, L.sorted_idx, L.cell_start, L.grid, kp, L.perm,
+                           S, ldk, o, (const Edges*)L.edges_dev, e32, R2T, single_mode == 1 ? 1 : 0, cap, dbg, xcd_chunk, rows_out, 1, L.valid, err_dev);
     } else {
         PCREG_HIP(hipFuncSetAttribute((const void*)desc_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(desc_kernel<0>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, sx, sy, sz, (const float4*)f4, sorted_idx, cell_start, grid, kp, perm,
-                           S, ldk, o, (const Edges*)edges_dev, e32, R2T, 0, cap, dbg, xcd_chunk, rows_out, 1, valid, err_dev);
+        hipLaunchKernelGGL(desc_kernel<0>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, L.sx, L.sy, L.sz, (const float4*)L.f4, L.sorted_idx, L.cell_start, L.grid, kp, L.perm,
+                           S, ldk, o, (const Edges*)L.edges_dev, e32, R2T, 0, cap, dbg, xcd_chunk, rows_out, 1, L.valid, err_dev);
     }
     PCREG_HIP(hipGetLastError());
     const int nbs = (S + 255) / 256;
-    hipLaunchKernelGGL(desc_count_kernel, dim3(nbs), dim3(256), 0, st, valid, S, bcnt);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, bcnt, nbs, V_dev);
-    hipLaunchKernelGGL(desc_slot_kernel, dim3(nbs), dim3(256), 0, st, valid, S, bcnt, slot);
-    if (desc_f64) hipLaunchKernelGGL(desc_emit_kernel, dim3(S), dim3(kBlock), 0, st, (const uint16_t*)stage, slot, kp, S, ldk, feat, desc_f64, row_index);
-    else hipLaunchKernelGGL(desc_index_kernel, dim3(nbs), dim3(256), 0, st, slot, kp, S, ldk, feat, row_index);
+    hipLaunchKernelGGL(desc_count_kernel, dim3(nbs), dim3(256), 0, st, L.valid, S, L.bcnt);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, L.bcnt, nbs, V_dev);
+    hipLaunchKernelGGL(desc_slot_kernel, dim3(nbs), dim3(256), 0, st, L.valid, S, L.bcnt, L.slot);
+    if (desc_f64) hipLaunchKernelGGL(desc_emit_kernel, dim3(S), dim3(kBlock), 0, st, (const uint16_t*)L.stage, L.slot, kp, S, ldk, feat, desc_f64, row_index);
+    else hipLaunchKernelGGL(desc_index_kernel, dim3(nbs), dim3(256), 0, st, L.slot, kp, S, ldk, feat, row_index);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -621,36 +621,31 @@ size_t seed_cell_cap(int M) { return std::min<size_t>((size_t)kSeedMaxCells, std
 }  // namespace
 
 // ---- a prepared model in device memory ---------------------------------------------------------------------------
-// layout of the prepared block: Prep | R_m^2 bits | box partials | f16 tiles | ordering-grid counters | seeding-grid
-// counters | seeding-grid slots | perm | sorted fp32 copy | tile boxes  (the two counter arrays adjoin: one clear)
+// The prepared block, walked once.  sort_cnt and seed_cnt adjoin (model_bbox_partial_kernel clears both in one go), so the
+// ordering grid's counters take exactly their bytes.
 static size_t n_f16_tiles(int M) { return (size_t)((M > 0 ? M : 0) + kT16 - 1) / kT16; }
-size_t model_prep_bytes(int M) {
+static ModelView model_layout(const float* m, int M, int ldm, void* block, size_t* bytes) {
     const size_t mm = (size_t)(M > 0 ? M : 1);
-    size_t b = 256 + 256 + align_up(512 * 6 * sizeof(float), 256) + align_up(knn_f16_prep_bytes(M), 256) + (size_t)kSortKeys * 4;
-    if (M >= kSeedMinM) b += align_up(seed_cell_cap(M) * 4, 256) + align_up(seed_cell_cap(M) * kSeedSlots * 16, 256);
-    b += align_up(mm * 4, 256) + align_up(mm * 12, 256) + align_up(std::max<size_t>(n_f16_tiles(M), 1) * 24, 256);
-    return b;
-}
-ModelView model_view(const float* m, int M, int ldm, void* block) {
+    WsWalk w(block);
     ModelView v{};
-    char* w = (char*)block;
     v.m = m; v.M = M; v.ldm = ldm;
-    v.prep = w; w += 256;
-    v.rm2 = (unsigned*)w; w += 256;
-    v.box_part = (float*)w; w += align_up(512 * 6 * sizeof(float), 256);
-    v.tiles = w; w += align_up(knn_f16_prep_bytes(M), 256);
-    v.sort_cnt = (int32_t*)w; w += (size_t)kSortKeys * 4;
+    v.prep = w.take_bytes(256);                                    // Prep
+    v.rm2 = (unsigned*)w.take_bytes(256);                          // R_m^2 bits
+    v.box_part = w.take<float>(512 * 6);                           // box partials
+    v.tiles = w.take_bytes(align_up(knn_f16_prep_bytes(M), 256));  // f16 tiles
+    v.sort_cnt = (int32_t*)w.take_bytes((size_t)kSortKeys * 4);    // ordering-grid counters
     v.seeded = M >= kSeedMinM && PCREG_EXP_ENV("PCREG_KNN_NOSEED", 0) == 0;
-    if (M >= kSeedMinM) {
-        v.seed_cnt = (int32_t*)w; w += align_up(seed_cell_cap(M) * 4, 256);
-        v.seed_slots = w; w += align_up(seed_cell_cap(M) * kSeedSlots * 16, 256);
+    if (M >= kSeedMinM) {                                          // seeding-grid counters and slots
+        v.seed_cnt = w.take<int32_t>(seed_cell_cap(M));
+        v.seed_slots = w.take_bytes(align_up(seed_cell_cap(M) * kSeedSlots * 16, 256));
     }
-    const size_t mm = (size_t)(M > 0 ? M : 1);
-    v.perm = (int32_t*)w; w += align_up(mm * 4, 256);
-    v.ms = (float*)w; w += align_up(mm * 12, 256);
-    v.tbox = (float*)w;
-    return v;
+    v.perm = w.take<int32_t>(mm);
+    v.ms = w.take<float>(mm * 3);                                  // sorted fp32 SoA copy
+    v.tbox = w.take<float>(std::max<size_t>(n_f16_tiles(M), 1) * 6);       // one box per f16 tile
+    *bytes = w.bytes(); return v;
 }
+size_t model_prep_bytes(int M) { size_t b; (void)model_layout(nullptr, M, 0, nullptr, &b); return b; }
+ModelView model_view(const float* m, int M, int ldm, void* block) { size_t b; return model_layout(m, M, ldm, block, &b); }
 // enqueue the two preparation passes (P1, P2) on `st`
 int launch_model_prepare(const ModelView& v, hipStream_t st) {
     PCREG_ARG(v.M >= 0 && v.ldm >= v.M);
@@ -680,26 +675,21 @@ SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     int q_blocks, W;
     knn_f16_shape(Q > 0 ? Q : 1, M > 0 ? M : 1, kTargetBlocks, &q_blocks, &W);
     s.cap = W * KC;
-    char* w = (char*)base;
-    s.ctr = w; w += align_up(sizeof(SearchCounters), 256);
-    s.gthr = (unsigned*)w; w += align_up(qq * 4, 256);
-    s.flag_list = (int32_t*)w; w += align_up(qq * 4, 256);
-    s.cand_cnt = (int32_t*)w; w += align_up(qq * 4, 256);
-    s.cand_ent = w; w += align_up(qq * (size_t)(kF16MaxS * KC) * 8, 256);      // the call may see a smaller M than the sizing did
+    WsWalk w(base);
+    s.ctr = w.take_bytes(align_up(sizeof(SearchCounters), 256));
+    s.gthr = w.take<unsigned>(qq); s.flag_list = w.take<int32_t>(qq); s.cand_cnt = w.take<int32_t>(qq);
+    s.cand_ent = w.take_bytes(align_up(qq * (size_t)(kF16MaxS * KC) * 8, 256));      // the call may see a smaller M than the sizing did
     const size_t few = (size_t)kFew * kFbSlices * 2, many = (size_t)(kTailGrid + (qq + kTailQ - 1) / kTailQ) * kTailQ * 2;
-    s.tail_idx = (int32_t*)w; w += align_up(std::max(few, many) * 4, 256);
-    s.tail_dist = (float*)w; w += align_up(std::max(few, many) * 4, 256);
+    s.tail_idx = w.take<int32_t>(std::max(few, many)); s.tail_dist = w.take<float>(std::max(few, many));
     s.ug_cells = (int)ug_cells_cap(Q);
     s.ug_nparts = (int)((qq * 8 + kBlock - 1) / kBlock);
-    s.ug_prep = w; w += 256;
-    s.ug_part = (float*)w; w += align_up((size_t)s.ug_nparts * 6 * 4, 256);
-    s.ug_cnt = (int32_t*)w; w += align_up((size_t)s.ug_cells * 4, 256);
-    s.ug_slots = w; w += align_up((size_t)s.ug_cells * kUgSlots * 16, 256);
-    s.qcnt = (int32_t*)w; w += (size_t)kQueryKeys * 4;
-    s.qperm = (int32_t*)w; w += align_up(qq * 4, 256);
-    s.dk = (float*)w; w += align_up(qq * 4, 256);
-    *bytes = (size_t)(w - (char*)base);
-    return s;
+    s.ug_prep = w.take_bytes(256);
+    s.ug_part = w.take<float>((size_t)s.ug_nparts * 6);
+    s.ug_cnt = w.take<int32_t>((size_t)s.ug_cells);
+    s.ug_slots = w.take_bytes(align_up((size_t)s.ug_cells * kUgSlots * 16, 256));
+    s.qcnt = (int32_t*)w.take_bytes((size_t)kQueryKeys * 4);
+    s.qperm = w.take<int32_t>(qq); s.dk = w.take<float>(qq);
+    *bytes = w.bytes(); return s;
 }
 size_t search_ws_bytes(int Q, int M) { size_t b; (void)search_ws_layout(Q, M, nullptr, &b); return b; }
 

@@ -303,11 +303,11 @@ struct KnnKWs { int32_t* qcnt; int32_t* qperm; float* dk; };
 KnnKWs knn_k_ws_layout(int Q, void* base, size_t* bytes) {
     KnnKWs s{};
     const size_t qq = (size_t)(Q > 0 ? Q : 1);
-    char* w = (char*)base;
-    s.qcnt = (int32_t*)w; w += (size_t)kQueryKeys * 4;
-    s.qperm = (int32_t*)w; w += align_up(qq * 4, 256);
-    s.dk = (float*)w; w += align_up(qq * 4, 256);
-    *bytes = (size_t)(w - (char*)base);
+    WsWalk w(base);
+    s.qcnt = (int32_t*)w.take_bytes((size_t)kQueryKeys * 4);
+    s.qperm = w.take<int32_t>(qq);
+    s.dk = w.take<float>(qq);
+    *bytes = w.bytes();
     return s;
 }
 

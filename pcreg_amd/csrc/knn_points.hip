@@ -350,11 +350,17 @@ int chunk_of(int M, int S) {
 
 }  // namespace
 
+// the [S][Q][2] partials of knn2_exact_impl, walked once
+struct Knn2ExactWs { int32_t* part_idx; float* part_dist; };
+static Knn2ExactWs knn2_exact_ws_layout(int Q, int S, void* base, size_t* bytes) {
+    WsWalk w(base);
+    const Knn2ExactWs p{w.take<int32_t>((size_t)S * Q * 2), w.take<float>((size_t)S * Q * 2)};      // (a braced list is evaluated left to right)
+    *bytes = w.bytes(); return p;
+}
 size_t knn2_points_exact_workspace_bytes(int Q, int M) {
     // sized for the most-split configuration any tuning variant can pick
     int n_tiles = (Q + kBlock * 8 - 1) / (kBlock * 8); if (n_tiles < 1) n_tiles = 1;
-    int S = pick_splits(n_tiles, M > 0 ? M : 1, 8192);
-    return 2 * align_up((size_t)S * (size_t)(Q > 0 ? Q : 1) * 2 * sizeof(float), 256);
+    size_t b; (void)knn2_exact_ws_layout(Q > 0 ? Q : 1, pick_splits(n_tiles, M > 0 ? M : 1, 8192), nullptr, &b); return b;
 }
 
 size_t knn2_points_exact_workspace_bytes(int Q, int M);
@@ -376,10 +382,10 @@ static int knn2_exact_impl(const float* q, int Q, int ldq, const float* m, int M
     int S = pick_splits(n_tiles, M > 0 ? M : 1, target);
     int chunk = chunk_of(M > 0 ? M : 1, S);
     S = M > 0 ? (M + chunk - 1) / chunk : 1;
-    int32_t* part_idx = (int32_t*)ws;
-    float* part_dist = (float*)((char*)ws + align_up((size_t)S * Q * 2 * sizeof(float), 256));
+    const Knn2ExactWs p = knn2_exact_ws_layout(Q, S, ws, &need);           // S is final: the sizing's bound must hold for it
+    if (ws_bytes < need) { set_error("knn workspace too small for %d splits: %zu < %zu", S, ws_bytes, need); return PCREG_E_WORKSPACE; }
     dim3 grid(n_tiles, S);
-#define PCREG_KNN_LAUNCH(QP, UBV) hipLaunchKernelGGL((knn2_points_kernel<QP, UBV>), grid, dim3(kBlock), 0, st, q, Q, ldq, m, M, ldm, chunk, (int)idx_base, part_idx, part_dist, qlist, n_list, min_active)
+#define PCREG_KNN_LAUNCH(QP, UBV) hipLaunchKernelGGL((knn2_points_kernel<QP, UBV>), grid, dim3(kBlock), 0, st, q, Q, ldq, m, M, ldm, chunk, (int)idx_base, p.part_idx, p.part_dist, qlist, n_list, min_active)
     switch (variant) {
         case 1: PCREG_KNN_LAUNCH(4, 8); break;
         case 2: PCREG_KNN_LAUNCH(8, 4); break;
@@ -389,9 +395,9 @@ static int knn2_exact_impl(const float* q, int Q, int ldq, const float* m, int M
 #undef PCREG_KNN_LAUNCH
     PCREG_HIP(hipGetLastError());
     if (qlist)
-        hipLaunchKernelGGL(merge_top2_list_kernel, dim3(64), dim3(256), 0, st, part_idx, part_dist, S, Q, qlist, n_list, min_active, idx, dist);
+        hipLaunchKernelGGL(merge_top2_list_kernel, dim3(64), dim3(256), 0, st, p.part_idx, p.part_dist, S, Q, qlist, n_list, min_active, idx, dist);
     else
-        hipLaunchKernelGGL(merge_top2_kernel_t<float>, dim3((Q + 255) / 256), dim3(256), 0, st, part_idx, part_dist, S, Q, idx, dist, (size_t)0);
+        hipLaunchKernelGGL(merge_top2_kernel_t<float>, dim3((Q + 255) / 256), dim3(256), 0, st, p.part_idx, p.part_dist, S, Q, idx, dist, (size_t)0);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

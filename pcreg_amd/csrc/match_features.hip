@@ -283,29 +283,34 @@ int pick_splits_desc(int n_tiles, int nB) {
     return S < 1 ? 1 : S;
 }
 
-// top-2 of every row of A against all rows of B; tmp holds the [S][nA][2] partials
+// the [S][nA][2] partials of run_score_top2, walked once; the sizing passes the most splits a call can pick
+struct ScoreTmp { int32_t* part_idx; double* part_dist; };
+ScoreTmp score_tmp_layout(int nA, int S, void* base, size_t* bytes) {
+    WsWalk w(base);
+    const ScoreTmp t{w.take<int32_t>((size_t)S * nA * 2), w.take<double>((size_t)S * nA * 2)};      // (a braced list is evaluated left to right)
+    *bytes = w.bytes(); return t;
+}
+// top-2 of every row of A against all rows of B
 int run_score_top2(const double* A, int nA, int lda, const double* B, int nB, int ldb, int D, int metric,
-                   int32_t* idx, double* dist, void* tmp, hipStream_t st) {
+                   int32_t* idx, double* dist, void* tmp, size_t tmp_bytes, hipStream_t st) {
     int n_tiles = (nA + BQ - 1) / BQ;
     int S = pick_splits_desc(n_tiles, nB);
     int chunk = ((nB + S - 1) / S + BM - 1) / BM * BM;
     S = (nB + chunk - 1) / chunk;
-    int32_t* part_idx = (int32_t*)tmp;
-    double* part_dist = (double*)((char*)tmp + align_up((size_t)S * nA * 2 * sizeof(int32_t), 256));
+    size_t need; const ScoreTmp t = score_tmp_layout(nA, S, tmp, &need);
+    if (tmp_bytes < need) { set_error("score workspace too small: %zu < %zu", tmp_bytes, need); return PCREG_E_WORKSPACE; }
     if (metric == PCREG_METRIC_SAD)
-        hipLaunchKernelGGL(score_top2_kernel<PCREG_METRIC_SAD>, dim3(n_tiles, S), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, chunk, part_idx, part_dist);
+        hipLaunchKernelGGL(score_top2_kernel<PCREG_METRIC_SAD>, dim3(n_tiles, S), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, chunk, t.part_idx, t.part_dist);
     else
-        hipLaunchKernelGGL(score_top2_kernel<PCREG_METRIC_SSD>, dim3(n_tiles, S), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, chunk, part_idx, part_dist);
+        hipLaunchKernelGGL(score_top2_kernel<PCREG_METRIC_SSD>, dim3(n_tiles, S), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, chunk, t.part_idx, t.part_dist);
     PCREG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(merge_top2_kernel_t<double>, dim3((nA + 255) / 256), dim3(256), 0, st, part_idx, part_dist, S, nA, idx, dist, (size_t)0);
+    hipLaunchKernelGGL(merge_top2_kernel_t<double>, dim3((nA + 255) / 256), dim3(256), 0, st, t.part_idx, t.part_dist, S, nA, idx, dist, (size_t)0);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
 size_t score_tmp_bytes(int nA, int nB) {
-    int n_tiles = (nA + BQ - 1) / BQ; if (n_tiles < 1) n_tiles = 1;
-    int S = pick_splits_desc(n_tiles, nB > 0 ? nB : 1);
-    size_t n = (size_t)(nA > 0 ? nA : 1);
-    return align_up((size_t)S * n * 2 * sizeof(int32_t), 256) + align_up((size_t)S * n * 2 * sizeof(double), 256);
+    const int S = pick_splits_desc(std::max((nA + BQ - 1) / BQ, 1), std::max(nB, 1));
+    size_t b; (void)score_tmp_layout(std::max(nA, 1), S, nullptr, &b); return b;
 }
 
 }  // namespace
@@ -320,23 +325,29 @@ static bool use_sad16(int metric) {
     return metric == PCREG_METRIC_SAD && debug_flag(kDbgMatchExact) == 0;
 }
 
-// workspace layout of launch_match_features (all sizes for capacity Q):
-//   idx [Q][2] i32 | dist [Q][2] f64 | cand_q [Q] | cand_m [Q] | keep [Q] | n_cand | filter tmp
-//   | back_idx [Q][2] | back_dist [Q][2] | gathered rows [Q x D] | score partials
-size_t match_features_workspace_bytes(int Q, int M, int D) {
-    size_t q = (size_t)(Q > 0 ? Q : 1);
-    size_t b = 0;
-    b += align_up(q * 2 * sizeof(int32_t), 256) + align_up(q * 2 * sizeof(double), 256);
-    b += 3 * align_up(q * sizeof(int32_t), 256) + 256;
-    b += align_up((q + q / 256 + 2) * sizeof(int32_t), 256);
-    b += align_up(q * 2 * sizeof(int32_t), 256) + align_up(q * 2 * sizeof(double), 256);
-    b += align_up(q * (size_t)(D > 0 ? D : 1) * sizeof(double), 256);
-    size_t t1 = score_tmp_bytes(Q, M), t2 = score_tmp_bytes(Q, Q);
-    size_t t3 = sad16_workspace_bytes(Q, M > Q ? M : Q, D);
-    t1 = t1 > t2 ? t1 : t2;
-    b += t1 > t3 ? t1 : t3;
-    return b;
+// the workspace of launch_match_features, walked once (all sizes for capacity Q)
+struct MatchWs {
+    int32_t* idx; double* dist;                     // [Q][2] top-2 of the forward search
+    int32_t* cand_q; int32_t* cand_m; int32_t* keep; int32_t* n_cand; int32_t* ftmp;      // the filters' lists, count and scan space
+    int32_t* back_idx; double* back_dist;           // [Q][2] top-2 of the Unique back-search
+    double* rows;                                   // [Q x D] gathered model rows
+    void* stmp; size_t stmp_bytes;                  // whichever search runs: score partials (Q x M, Q x Q) or the sad16 workspace
+};
+static MatchWs match_ws_layout(int Q, int M, int D, void* base, size_t* bytes) {
+    const size_t q = (size_t)std::max(Q, 1);
+    WsWalk w(base);
+    MatchWs s{};
+    s.idx = w.take<int32_t>(q * 2); s.dist = w.take<double>(q * 2);
+    s.cand_q = w.take<int32_t>(q); s.cand_m = w.take<int32_t>(q); s.keep = w.take<int32_t>(q);
+    s.n_cand = (int32_t*)w.take_bytes(256);
+    s.ftmp = w.take<int32_t>(q + q / 256 + 2);
+    s.back_idx = w.take<int32_t>(q * 2); s.back_dist = w.take<double>(q * 2);
+    s.rows = w.take<double>(q * (size_t)std::max(D, 1));
+    s.stmp_bytes = std::max({score_tmp_bytes(Q, M), score_tmp_bytes(Q, Q), sad16_workspace_bytes(Q, std::max(M, Q), D)});
+    s.stmp = w.take_bytes(s.stmp_bytes);
+    *bytes = w.bytes(); return s;
 }
+size_t match_features_workspace_bytes(int Q, int M, int D) { size_t b; (void)match_ws_layout(Q, M, D, nullptr, &b); return b; }
 
 int launch_preprocess(const double* dS, int Q, int ldS, const double* dM, int M, int ldM, int D,
                       const pcreg_match_opts& o, double* outS, double* outM, void* ws, size_t ws_bytes,
@@ -377,30 +388,16 @@ int launch_match_features(const double* fS, int Q, int ldS, const double* fM, in
                           void* ws, size_t ws_bytes, hipStream_t st) {
     PCREG_ARG(Q >= 0 && M >= 0 && D >= 1);
     if (Q == 0 || M == 0) { PCREG_HIP(hipMemsetAsync(P_dev, 0, sizeof(int32_t), st)); return PCREG_OK; }
-    size_t need = match_features_workspace_bytes(Q, M, D);
+    size_t need; const MatchWs L = match_ws_layout(Q, M, D, ws, &need);
     if (ws_bytes < need) { set_error("match workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
-    char* w = (char*)ws;
-    size_t q = (size_t)Q;
-    int32_t* idx = (int32_t*)w;        w += align_up(q * 2 * sizeof(int32_t), 256);
-    double* dist = (double*)w;         w += align_up(q * 2 * sizeof(double), 256);
-    int32_t* cand_q = (int32_t*)w;     w += align_up(q * sizeof(int32_t), 256);
-    int32_t* cand_m = (int32_t*)w;     w += align_up(q * sizeof(int32_t), 256);
-    int32_t* keep = (int32_t*)w;       w += align_up(q * sizeof(int32_t), 256);
-    int32_t* n_cand = (int32_t*)w;     w += 256;
-    int32_t* ftmp = (int32_t*)w;       w += align_up((q + q / 256 + 2) * sizeof(int32_t), 256);
-    int32_t* back_idx = (int32_t*)w;   w += align_up(q * 2 * sizeof(int32_t), 256);
-    double* back_dist = (double*)w;    w += align_up(q * 2 * sizeof(double), 256);
-    double* rows = (double*)w;         w += align_up(q * (size_t)D * sizeof(double), 256);
-    void* stmp = w;
-    const size_t stmp_bytes = ws_bytes - (size_t)(w - (char*)ws);
     const bool fast = use_sad16(o.metric);
 
-    int rc = fast ? run_sad16_top2(fS, Q, ldS, fM, M, ldM, D, idx, dist, stmp, stmp_bytes, st)
-                  : run_score_top2(fS, Q, ldS, fM, M, ldM, D, o.metric, idx, dist, stmp, st);
+    int rc = fast ? run_sad16_top2(fS, Q, ldS, fM, M, ldM, D, L.idx, L.dist, L.stmp, L.stmp_bytes, st)
+                  : run_score_top2(fS, Q, ldS, fM, M, ldM, D, o.metric, L.idx, L.dist, L.stmp, L.stmp_bytes, st);
     if (rc) return rc;
     double maxval = o.metric == PCREG_METRIC_SSD ? 4.0 : 2.0 * sqrt((double)D);   // percentToLevel
     double thr = (o.matchThreshold * 0.01) * maxval;
-    rc = run_filter_top2<double>(idx, dist, Q, M, thr, o.maxRatio, cand_q, cand_m, n_cand, ftmp, st);
+    rc = run_filter_top2<double>(L.idx, L.dist, Q, M, thr, o.maxRatio, L.cand_q, L.cand_m, L.n_cand, L.ftmp, st);
     if (rc) return rc;
     const int32_t* keep_ptr = nullptr;
     if (o.unique) {
@@ -409,28 +406,28 @@ int launch_match_features(const double* fS, int Q, int ldS, const double* fM, in
         // ones keep the read-back: there 50 us of latency are nothing, and sizing the grid by the real count balances
         // the candidates kernel better (measured +3 % at 50 k x 50 k on the capacity).
         if (fast && (double)Q * (double)Q * (double)D <= 2.0e10) {
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(1024), dim3(256), 0, st, fM, ldM, D, cand_m, n_cand, Q, rows);
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(1024), dim3(256), 0, st, fM, ldM, D, L.cand_m, L.n_cand, Q, L.rows);
             PCREG_HIP(hipGetLastError());
-            rc = run_sad16_top2(rows, Q, Q, fS, Q, ldS, D, back_idx, back_dist, stmp, stmp_bytes, st, n_cand);
+            rc = run_sad16_top2(L.rows, Q, Q, fS, Q, ldS, D, L.back_idx, L.back_dist, L.stmp, L.stmp_bytes, st, L.n_cand);
             if (rc) return rc;
-            hipLaunchKernelGGL(unique_flag_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, back_idx, cand_q, n_cand, keep);
+            hipLaunchKernelGGL(unique_flag_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, L.back_idx, L.cand_q, L.n_cand, L.keep);
         } else {
             // sized by the real candidate count (one small D2H read); also the exhaustive fp64 form (SSD, PCREG_MATCH_EXACT)
             int32_t P_host = 0;
-            PCREG_HIP(hipMemcpyAsync(&P_host, n_cand, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            PCREG_HIP(hipMemcpyAsync(&P_host, L.n_cand, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             PCREG_HIP(hipStreamSynchronize(st));
             if (P_host > 0) {
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(1024), dim3(256), 0, st, fM, ldM, D, cand_m, n_cand, Q, rows);
+                hipLaunchKernelGGL(gather_rows_kernel, dim3(1024), dim3(256), 0, st, fM, ldM, D, L.cand_m, L.n_cand, Q, L.rows);
                 PCREG_HIP(hipGetLastError());
-                rc = fast ? run_sad16_top2(rows, P_host, Q, fS, Q, ldS, D, back_idx, back_dist, stmp, stmp_bytes, st)
-                          : run_score_top2(rows, P_host, Q, fS, Q, ldS, D, o.metric, back_idx, back_dist, stmp, st);
+                rc = fast ? run_sad16_top2(L.rows, P_host, Q, fS, Q, ldS, D, L.back_idx, L.back_dist, L.stmp, L.stmp_bytes, st)
+                          : run_score_top2(L.rows, P_host, Q, fS, Q, ldS, D, o.metric, L.back_idx, L.back_dist, L.stmp, L.stmp_bytes, st);
                 if (rc) return rc;
-                hipLaunchKernelGGL(unique_flag_kernel, dim3((P_host + 255) / 256), dim3(256), 0, st, back_idx, cand_q, n_cand, keep);
+                hipLaunchKernelGGL(unique_flag_kernel, dim3((P_host + 255) / 256), dim3(256), 0, st, L.back_idx, L.cand_q, L.n_cand, L.keep);
             }
         }
-        keep_ptr = keep;
+        keep_ptr = L.keep;
     }
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(1), dim3(256), 0, st, cand_q, cand_m, keep_ptr, n_cand, dist, pairs, metric, P_dev);
+    hipLaunchKernelGGL(emit_pairs_kernel, dim3(1), dim3(256), 0, st, L.cand_q, L.cand_m, keep_ptr, L.n_cand, L.dist, pairs, metric, P_dev);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -1960,17 +1960,29 @@ int launch_widen_rows_u16(const uint16_t* rows, const int32_t* index, int n, int
     return PCREG_OK;
 }
 
-// workspace: Range | n_flag | minmax partials | Aq | Bq | At | Bt | part_idx | part_s | flag_list
-//            | fallback: fi | fd | slice partials [kFbSlices][nA][2] (i32, f64)
-size_t sad16_workspace_bytes(int nA, int nB, int D) {
-    size_t a = (size_t)(nA > 0 ? nA : 1), b = (size_t)(nB > 0 ? nB : 1);
-    size_t D2p = align_up((size_t)(D + 1) / 2, DK2);
-    return 256 + 256 + align_up(1024 * 2 * 8, 256) + D2p * align_up(a, BQ) * 4 + D2p * align_up(b, BQ) * 4 +
-           align_up(a * (size_t)D * 8, 256) + align_up(b * (size_t)D * 8, 256) +
-           2 * align_up((size_t)kMaxSplit * a * KC * 4, 256) + align_up(a * 4, 256) +
-           align_up(a * 2 * 4, 256) + align_up(a * 2 * 8, 256) +
-           align_up((size_t)kFbSlices * a * 2 * 4, 256) + align_up((size_t)kFbSlices * a * 2 * 8, 256);
+// the workspace of run_sad16_top2, walked once (sizes by max(n, 1): the size function is asked about empty sets too)
+namespace {
+struct Sad16Ws {
+    Range* range; int32_t* n_flag; double* mpart;                             // value range, count of unproven rows, minmax partials
+    uint32_t* Aq; uint32_t* Bq; int D2p, ldqa, ldqb; double* At; double* Bt;  // the quantised, packed operands; feature-major fp64 copies
+    int32_t* part_idx; uint32_t* part_s; int32_t* flag_list;                  // candidate lists [kMaxSplit][nA][KC]; the unproven rows
+    int32_t* fpi; double* fpd;                                                // fallback slice partials [kFbSlices][nA][2]
+};
+Sad16Ws sad16_ws_layout(int nA, int nB, int D, void* base, size_t* bytes) {
+    const size_t a = (size_t)std::max(nA, 1), b = (size_t)std::max(nB, 1);
+    WsWalk w(base);
+    Sad16Ws s{};
+    s.D2p = (int)align_up((size_t)(D + 1) / 2, DK2); s.ldqa = (int)align_up(a, BQ); s.ldqb = (int)align_up(b, BQ);
+    s.range = (Range*)w.take_bytes(256); s.n_flag = (int32_t*)w.take_bytes(256); s.mpart = w.take<double>(1024 * 2);
+    s.Aq = (uint32_t*)w.take_bytes((size_t)s.D2p * s.ldqa * 4); s.Bq = (uint32_t*)w.take_bytes((size_t)s.D2p * s.ldqb * 4);
+    s.At = w.take<double>(a * (size_t)D); s.Bt = w.take<double>(b * (size_t)D);
+    s.part_idx = w.take<int32_t>((size_t)kMaxSplit * a * KC); s.part_s = w.take<uint32_t>((size_t)kMaxSplit * a * KC);
+    s.flag_list = w.take<int32_t>(a);
+    s.fpi = w.take<int32_t>((size_t)kFbSlices * a * 2); s.fpd = w.take<double>((size_t)kFbSlices * a * 2);
+    *bytes = w.bytes(); return s;
 }
+}  // namespace
+size_t sad16_workspace_bytes(int nA, int nB, int D) { size_t b; (void)sad16_ws_layout(nA, nB, D, nullptr, &b); return b; }
 
 // Top-2 of every row of A against all rows of B under SAD: indices and fp64 distances identical to
 // the exhaustive fp64 search (launch_score_top2_exact).  No host round trip.
@@ -1979,33 +1991,17 @@ size_t sad16_workspace_bytes(int nA, int nB, int D) {
 int run_sad16_top2(const double* A, int nA, int lda, const double* B, int nB, int ldb, int D,
                    int32_t* idx, double* dist, void* ws, size_t ws_bytes, hipStream_t st, const int32_t* nA_live) {
     PCREG_ARG(nA >= 1 && nB >= 1 && D >= 1);
-    size_t need = sad16_workspace_bytes(nA, nB, D);
+    size_t need; const Sad16Ws L = sad16_ws_layout(nA, nB, D, ws, &need);
     if (ws_bytes < need) { set_error("sad16 workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
-    const int D2p = (int)align_up((size_t)(D + 1) / 2, DK2);
-    const int ldqa = (int)align_up((size_t)nA, BQ), ldqb = (int)align_up((size_t)nB, BQ);
-    size_t a = (size_t)nA, b = (size_t)nB;
-    char* w = (char*)ws;
-    Range* range = (Range*)w;               w += 256;
-    int32_t* n_flag = (int32_t*)w;          w += 256;
-    double* mpart = (double*)w;             w += align_up(1024 * 2 * 8, 256);
-    uint32_t* Aq = (uint32_t*)w;            w += (size_t)D2p * ldqa * 4;
-    uint32_t* Bq = (uint32_t*)w;            w += (size_t)D2p * ldqb * 4;
-    double* At = (double*)w;                w += align_up(a * (size_t)D * 8, 256);
-    double* Bt = (double*)w;                w += align_up(b * (size_t)D * 8, 256);
-    int32_t* part_idx = (int32_t*)w;        w += align_up((size_t)kMaxSplit * a * KC * 4, 256);
-    uint32_t* part_s = (uint32_t*)w;        w += align_up((size_t)kMaxSplit * a * KC * 4, 256);
-    int32_t* flag_list = (int32_t*)w;       w += align_up(a * 4, 256);
-    w += align_up(a * 2 * 4, 256) + align_up(a * 2 * 8, 256);      // (formerly the merged fallback rows)
-    int32_t* fpi = (int32_t*)w;             w += align_up((size_t)kFbSlices * a * 2 * 4, 256);
-    double* fpd = (double*)w;
-
+    const int D2p = L.D2p, ldqa = L.ldqa, ldqb = L.ldqb;
+    const size_t a = (size_t)nA, b = (size_t)nB;
     PCREG_ARG(lda >= nA && ldb >= nB);
     int nb = (int)std::min<size_t>(1024, ((a + b) * D + kBlock * 8 - 1) / (kBlock * 8)); if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(minmax_partial_kernel, dim3(nb), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, mpart, nA_live);
-    hipLaunchKernelGGL(range_final_kernel, dim3(1), dim3(64), 0, st, mpart, nb, range);
-    hipLaunchKernelGGL(quantize_pack_kernel, dim3(2048), dim3(kBlock), 0, st, A, nA, lda, D, D2p, ldqa, range, Aq, nA_live);
-    hipLaunchKernelGGL(quantize_pack_kernel, dim3(2048), dim3(kBlock), 0, st, B, nB, ldb, D, D2p, ldqb, range, Bq, (const int32_t*)nullptr);
-    PCREG_HIP(hipMemsetAsync(n_flag, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(minmax_partial_kernel, dim3(nb), dim3(kBlock), 0, st, A, nA, lda, B, nB, ldb, D, L.mpart, nA_live);
+    hipLaunchKernelGGL(range_final_kernel, dim3(1), dim3(64), 0, st, L.mpart, nb, L.range);
+    hipLaunchKernelGGL(quantize_pack_kernel, dim3(2048), dim3(kBlock), 0, st, A, nA, lda, D, D2p, ldqa, L.range, L.Aq, nA_live);
+    hipLaunchKernelGGL(quantize_pack_kernel, dim3(2048), dim3(kBlock), 0, st, B, nB, ldb, D, D2p, ldqb, L.range, L.Bq, (const int32_t*)nullptr);
+    PCREG_HIP(hipMemsetAsync(L.n_flag, 0, sizeof(int32_t), st));
     // Split B into S chunks so that the grid loads every CU equally: a CU holds 3 workgroups, all
     // resident at once, so the kernel lasts (workgroups on the fullest CU) x (row tiles per chunk).
     const int n_tiles = (nA + BQ - 1) / BQ, row_tiles = (nB + BM - 1) / BM;
@@ -2028,10 +2024,10 @@ int run_sad16_top2(const double* A, int nA, int lda, const double* B, int nB, in
     if (tl) PCREG_HIP(hipMalloc(&dbg, (size_t)n_tiles * S * 4 * sizeof(unsigned long long)));
 #ifdef PCREG_EXPERIMENTS
     if (PCREG_EXP_ENV("PCREG_SAD_DRY", 0))      // timing experiment only: list maintenance compiled out, results invalid
-        hipLaunchKernelGGL(sad16_candidates_kernel<kSadDry>, dim3(n_tiles, S), dim3(kBlock), 0, st, Aq, nA, ldqa, Bq, nB, ldqb, D2p, chunk, part_idx, part_s, dbg, nA_live, SegZ{0, 0, 0, 0, nullptr, nullptr, 0});
+        hipLaunchKernelGGL(sad16_candidates_kernel<kSadDry>, dim3(n_tiles, S), dim3(kBlock), 0, st, L.Aq, nA, ldqa, L.Bq, nB, ldqb, D2p, chunk, L.part_idx, L.part_s, dbg, nA_live, SegZ{0, 0, 0, 0, nullptr, nullptr, 0});
     else
 #endif
-        hipLaunchKernelGGL(sad16_candidates_kernel<kSadLists>, dim3(n_tiles, S), dim3(kBlock), 0, st, Aq, nA, ldqa, Bq, nB, ldqb, D2p, chunk, part_idx, part_s, dbg, nA_live, SegZ{0, 0, 0, 0, nullptr, nullptr, 0});
+        hipLaunchKernelGGL(sad16_candidates_kernel<kSadLists>, dim3(n_tiles, S), dim3(kBlock), 0, st, L.Aq, nA, ldqa, L.Bq, nB, ldqb, D2p, chunk, L.part_idx, L.part_s, dbg, nA_live, SegZ{0, 0, 0, 0, nullptr, nullptr, 0});
     const int force = debug_flag(kDbgMatchForceFallback) != 0;
     unsigned long long* stats = match_stats_dev();
     if (stats) hipLaunchKernelGGL(stats_bump_kernel, dim3(1), dim3(1), 0, st, stats, 6, 1ull);
@@ -2047,14 +2043,14 @@ int run_sad16_top2(const double* A, int nA, int lda, const double* B, int nB, in
             fclose(f);
         }
     }
-    hipLaunchKernelGGL(transpose_rows_kernel, dim3((nA + 63) / 64, (D + 63) / 64), dim3(kBlock), 0, st, A, nA, lda, D, At, nA_live);
-    hipLaunchKernelGGL(transpose_rows_kernel, dim3((nB + 63) / 64, (D + 63) / 64), dim3(kBlock), 0, st, B, nB, ldb, D, Bt, (const int32_t*)nullptr);
-    hipLaunchKernelGGL(sad16_finalize_kernel, dim3((nA + 3) / 4), dim3(kBlock), 0, st, At, nA, Bt, nB, D, range,
-                       part_idx, part_s, S, idx, dist, flag_list, n_flag, force, nA_live, stats);
+    hipLaunchKernelGGL(transpose_rows_kernel, dim3((nA + 63) / 64, (D + 63) / 64), dim3(kBlock), 0, st, A, nA, lda, D, L.At, nA_live);
+    hipLaunchKernelGGL(transpose_rows_kernel, dim3((nB + 63) / 64, (D + 63) / 64), dim3(kBlock), 0, st, B, nB, ldb, D, L.Bt, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(sad16_finalize_kernel, dim3((nA + 3) / 4), dim3(kBlock), 0, st, L.At, nA, L.Bt, nB, D, L.range,
+                       L.part_idx, L.part_s, S, idx, dist, L.flag_list, L.n_flag, force, nA_live, stats);
     PCREG_HIP(hipGetLastError());
     if (PCREG_EXP_ENV("PCREG_MATCH_DEBUG", 0)) {                       // the only host round trip of the call, debugging only
         int32_t nf = 0;
-        PCREG_HIP(hipMemcpyAsync(&nf, n_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        PCREG_HIP(hipMemcpyAsync(&nf, L.n_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         PCREG_HIP(hipStreamSynchronize(st));
         int occ = -1; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, sad16_candidates_kernel<kSadLists>, kBlock, 0);
         fprintf(stderr, "[pcreg] sad16: nA=%d nB=%d D=%d S=%d unproven=%d (candidates kernel: %d blocks/CU)\n", nA, nB, D, S, nf, occ);
@@ -2064,9 +2060,9 @@ int run_sad16_top2(const double* A, int nA, int lda, const double* B, int nB, in
         int slice = (nB + slices - 1) / slices;
         slices = (nB + slice - 1) / slice;
         hipLaunchKernelGGL(sad_exact_rows_kernel, dim3(std::min(nA, 64), slices), dim3(kBlock), (size_t)D * sizeof(double), st,
-                           A, lda, B, nB, ldb, D, flag_list, n_flag, nA, slice, fpi, fpd);
-        hipLaunchKernelGGL(sad_fallback_finish_kernel, dim3(std::min((nA + 255) / 256, 64)), dim3(256), 0, st, flag_list, n_flag, nA, slices,
-                           fpi, fpd, idx, dist);
+                           A, lda, B, nB, ldb, D, L.flag_list, L.n_flag, nA, slice, L.fpi, L.fpd);
+        hipLaunchKernelGGL(sad_fallback_finish_kernel, dim3(std::min((nA + 255) / 256, 64)), dim3(256), 0, st, L.flag_list, L.n_flag, nA, slices,
+                           L.fpi, L.fpd, idx, dist);
         PCREG_HIP(hipGetLastError());
     }
     return PCREG_OK;
@@ -2125,11 +2121,20 @@ SegLayout seg_layout(int Q, int VM, int D, int Dp, int S, int tot, int n_max) {
 // segment offsets) and one or two per batch (the size of its union); a model row is scored once per batch that names it.
 constexpr size_t kSegBudget = (size_t)3 << 30;          // the one-chain workspace of a batch
 constexpr size_t kSegGatherBytes = (size_t)1 << 30;     // the gathered sub-model of a batch
-static size_t seg_batched_fixed_bytes(int VM, int tot, int S) {
+// the fixed head of the batched form's workspace; the gathered sub-model and the one-chain workspace of a batch follow it
+struct SegBatchWs { int32_t* flag; int32_t* newidx; int32_t* urows; int32_t* rows_b; int32_t* off_b; int32_t* bcnt; int32_t* n_union; };
+static SegBatchWs seg_batch_ws_layout(int VM, int tot, int S, void* base, size_t* bytes) {
     const size_t vm = (size_t)std::max(VM, 1);
-    return 3 * align_up(vm * 4, 256) + align_up((size_t)std::max(tot, 1) * 4, 256) + align_up(((size_t)std::max(S, 1) + 1) * 4, 256) +
-           align_up((vm + 1023) / 1024 * 4, 256) + 256;
+    WsWalk w(base);
+    SegBatchWs s{};
+    s.flag = w.take<int32_t>(vm); s.newidx = w.take<int32_t>(vm); s.urows = w.take<int32_t>(vm);      // marks, numbers, the union's rows
+    s.rows_b = w.take<int32_t>((size_t)std::max(tot, 1));                                              // the batch's lists, renumbered
+    s.off_b = w.take<int32_t>((size_t)std::max(S, 1) + 1);
+    s.bcnt = w.take<int32_t>((vm + 1023) / 1024);
+    s.n_union = (int32_t*)w.take_bytes(256);
+    *bytes = w.bytes(); return s;
 }
+static size_t seg_batched_fixed_bytes(int VM, int tot, int S) { size_t b; (void)seg_batch_ws_layout(VM, tot, S, nullptr, &b); return b; }
 size_t get_matches_segmented_workspace_bytes(int Q, int VM, int D, int S, int tot, int n_max) {
     const size_t one = seg_layout(Q, VM, D, D + 1, S, tot, n_max).total;
     if (one <= kSegBudget + kSegGatherBytes) return one;
@@ -2384,23 +2389,15 @@ int launch_get_matches_segmented(const double* descS, int Q, const double* descM
     if (one <= kSegBudget + kSegGatherBytes && !debug_flag(kDbgSegBatched))
         return launch_get_matches_segmented_one(descS, Q, descM, VM, D, seg_rows, seg_off, S, tot, n_max, o, pairs_all, metric_all, n_pairs, ws, ws_bytes, st, prepared);
     // ---- batches of consecutive segments on gathered sub-models (they gather the RAW rows: a prepared model is not used)
-    const size_t fixed = seg_batched_fixed_bytes(VM, tot, S);
+    size_t fixed; const SegBatchWs H = seg_batch_ws_layout(VM, tot, S, ws, &fixed);
     if (ws_bytes < fixed + 4096) { set_error("segmented get_matches workspace too small: %zu bytes", ws_bytes); return PCREG_E_WORKSPACE; }
     // whatever the caller's workspace holds beyond the fixed part is split 1 : 3 between the gathered rows and the one-chain form
     // (the workspace query returns the fixed part + kSegGatherBytes + kSegBudget for a problem that needs batches)
     const size_t room = ws_bytes - fixed;
     const size_t gather_bytes = std::min(kSegGatherBytes, room / 4) / 256 * 256, one_bytes = std::min(budget, room - gather_bytes);
     const size_t vm = (size_t)VM;
-    char* w = (char*)ws;
-    int32_t* flag = (int32_t*)w; w += align_up(vm * 4, 256);
-    int32_t* newidx = (int32_t*)w; w += align_up(vm * 4, 256);
-    int32_t* urows = (int32_t*)w; w += align_up(vm * 4, 256);
-    int32_t* rows_b = (int32_t*)w; w += align_up((size_t)std::max(tot, 1) * 4, 256);
-    int32_t* off_b = (int32_t*)w; w += align_up(((size_t)S + 1) * 4, 256);
-    int32_t* bcnt = (int32_t*)w; w += align_up((vm + 1023) / 1024 * 4, 256);
-    int32_t* n_union = (int32_t*)w; w += 256;
-    double* descMb = (double*)w; w += gather_bytes;
-    void* ws_one = w;
+    double* descMb = (double*)((char*)ws + fixed);
+    void* ws_one = (char*)descMb + gather_bytes;
     const int nb = (VM + 1023) / 1024;
     const size_t cap_rows = gather_bytes / ((size_t)D * 8);
     std::vector<int32_t> off((size_t)S + 1);
@@ -2418,11 +2415,11 @@ int launch_get_matches_segmented(const double* descS, int Q, const double* descM
             // first the terms that do not depend on the union (the per-segment lists), on the host alone
             if (Sb > 1 && seg_layout(Q, 1, D, D + 1, Sb, tot_b, nmax_b).total > one_bytes / 2) { Sb = (Sb + 1) / 2; continue; }
             int VMb = 0;
-            PCREG_HIP(hipMemsetAsync(flag, 0, vm * 4, st));
-            hipLaunchKernelGGL(segb_mark_kernel, dim3((tot_b + 255) / 256), dim3(256), 0, st, seg_rows, off[z0], off[z0 + Sb], flag);
-            hipLaunchKernelGGL(segb_count_kernel, dim3(nb), dim3(256), 0, st, flag, VM, bcnt);
-            hipLaunchKernelGGL(segb_scan_kernel, dim3(1), dim3(1024), 0, st, bcnt, nb, n_union);
-            PCREG_HIP(hipMemcpyAsync(&VMb, n_union, 4, hipMemcpyDeviceToHost, st));
+            PCREG_HIP(hipMemsetAsync(H.flag, 0, vm * 4, st));
+            hipLaunchKernelGGL(segb_mark_kernel, dim3((tot_b + 255) / 256), dim3(256), 0, st, seg_rows, off[z0], off[z0 + Sb], H.flag);
+            hipLaunchKernelGGL(segb_count_kernel, dim3(nb), dim3(256), 0, st, H.flag, VM, H.bcnt);
+            hipLaunchKernelGGL(segb_scan_kernel, dim3(1), dim3(1024), 0, st, H.bcnt, nb, H.n_union);
+            PCREG_HIP(hipMemcpyAsync(&VMb, H.n_union, 4, hipMemcpyDeviceToHost, st));
             PCREG_HIP(hipStreamSynchronize(st));
             const size_t lay = seg_layout(Q, VMb, D, D + 1, Sb, tot_b, nmax_b).total;
             if (lay > one_bytes || (size_t)VMb > cap_rows) {
@@ -2433,12 +2430,12 @@ int launch_get_matches_segmented(const double* descS, int Q, const double* descM
                 Sb = (Sb + 1) / 2;
                 continue;
             }
-            hipLaunchKernelGGL(segb_number_kernel, dim3(nb), dim3(256), 0, st, flag, VM, bcnt, newidx, urows);
-            hipLaunchKernelGGL(segb_renumber_kernel, dim3((tot_b + 255) / 256), dim3(256), 0, st, seg_rows, off[z0], off[z0 + Sb], newidx, rows_b);
-            hipLaunchKernelGGL(segb_offsets_kernel, dim3((Sb + 256) / 256), dim3(256), 0, st, seg_off, z0, Sb, off_b);
-            hipLaunchKernelGGL(segb_gather_kernel, dim3((VMb + 3) / 4), dim3(256), 0, st, descM, D, urows, VMb, descMb);
+            hipLaunchKernelGGL(segb_number_kernel, dim3(nb), dim3(256), 0, st, H.flag, VM, H.bcnt, H.newidx, H.urows);
+            hipLaunchKernelGGL(segb_renumber_kernel, dim3((tot_b + 255) / 256), dim3(256), 0, st, seg_rows, off[z0], off[z0 + Sb], H.newidx, H.rows_b);
+            hipLaunchKernelGGL(segb_offsets_kernel, dim3((Sb + 256) / 256), dim3(256), 0, st, seg_off, z0, Sb, H.off_b);
+            hipLaunchKernelGGL(segb_gather_kernel, dim3((VMb + 3) / 4), dim3(256), 0, st, descM, D, H.urows, VMb, descMb);
             PCREG_HIP(hipGetLastError());
-            const int rc = launch_get_matches_segmented_one(descS, Q, descMb, VMb, D, rows_b, off_b, Sb, tot_b, nmax_b, o, pairs_all + (size_t)z0 * Q * 2,
+            const int rc = launch_get_matches_segmented_one(descS, Q, descMb, VMb, D, H.rows_b, H.off_b, Sb, tot_b, nmax_b, o, pairs_all + (size_t)z0 * Q * 2,
                                                             metric_all ? metric_all + (size_t)z0 * Q : nullptr, n_pairs + z0, ws_one, one_bytes, st);
             if (rc) return rc;
             break;

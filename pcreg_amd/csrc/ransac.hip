@@ -3155,24 +3155,47 @@ static bool bounded_pays(int n_cap, int iters) {
 }
 static size_t staged_slots_cap(int n_cap) { return (size_t)((n_cap + kSPts - 1) / kSPts) * (kSPts / 64); }
 static size_t staged_chunks_cap(int n_cap) { return (staged_slots_cap(n_cap) + kMomSlots - 1) / kMomSlots; }
-static size_t staged_extra_bytes(size_t h, int n_cap) {    // T1 | mom | part | v1 | pass1 | v2 | cert | dense | lane-path buffers
-    size_t b = align_up(h * 12 * sizeof(double), 256) + align_up(h * 27 * sizeof(double), 256) +
-               align_up(h * kSMaxPB * sizeof(int32_t), 256) + 5 * align_up(h, 256) + 256 + align_up(h * 2 * sizeof(double), 256) +
-               align_up((staged_slots_cap(n_cap) * 64 + 255) / 256 * 4 * sizeof(double), 256) + 512;
-    if (n_cap >= kStagedMinN)
-        b += align_up(staged_slots_cap(n_cap) * 64 * 6 * sizeof(float), 256) + 2 * align_up(h * 16 * sizeof(float), 256) +
-             align_up(h * staged_slots_cap(n_cap) * 8, 256) + align_up(staged_slots_cap(n_cap) * 64 * kRec * sizeof(double) + 256, 256) +
-             align_up(staged_chunks_cap(n_cap) * h * 15 * sizeof(double), 256) + align_up(h * sizeof(int32_t), 256) + 256 +
-             align_up(staged_slots_cap(n_cap) * 2 * 256 * sizeof(uint4), 256) +
-             /* bounded second pass: p32, perm, bkt, BCtr */
-             align_up(staged_slots_cap(n_cap) * 64 * (6 * sizeof(float) + sizeof(int32_t) + 1) + 3 * 256, 256) + align_up(sizeof(BCtr), 256);
-    return b;
+// The workspace of launch_ransac_impl, walked once: the per-hypothesis results every path writes, then the staged chain's buffers
+// (StagedArgs with its pointer and capacity fields set).  That chain runs for one registration only: a batch reserves its small block for n_cap 0.
+struct RansacWs { double* TF; int32_t* cnt1; int32_t* cnt2; unsigned char* has; double* msc; StagedArgs sa; };
+static RansacWs ransac_ws_layout(int iters, int B, int n_cap, void* base, size_t* bytes) {
+    const size_t h = (size_t)iters * (size_t)B;
+    const int nc = B == 1 ? n_cap : 0;
+    const size_t slots = staged_slots_cap(nc);
+    WsWalk w(base);
+    RansacWs s{};
+    StagedArgs& sa = s.sa;
+    s.TF = w.take<double>(h * 12);
+    s.cnt1 = w.take<int32_t>(h); s.cnt2 = w.take<int32_t>(h);
+    s.has = w.take<unsigned char>(h); s.msc = w.take<double>(h * 16);     // (msc: ransac_hyp32_kernel's refit sums)
+    sa.T1 = w.take<double>(h * 12); sa.mom = w.take<double>(h * 27);
+    sa.part = w.take<int32_t>(h * kSMaxPB);
+    sa.v1 = w.take<unsigned char>(h); sa.pass1 = w.take<unsigned char>(h); sa.v2 = w.take<unsigned char>(h);
+    sa.cert = w.take<unsigned char>(h); sa.dense = w.take<unsigned char>(h);
+    sa.bounds = (double*)w.take_bytes(256);
+    sa.n_rec_blocks = (int)((slots * 64 + 255) / 256);
+    sa.bpart = w.take<double>((size_t)sa.n_rec_blocks * 4);
+    sa.sel_ctr = w.take_bytes(512);
+    sa.certq = w.take<double>(h * 2);
+    if (nc >= kStagedMinN) {      // one registration that may run staged: the large block
+        sa.nslots_cap = (int)slots;
+        sa.masks = w.take<unsigned long long>(h * slots);
+        sa.rec = w.take<double>(slots * 64 * kRec + 32);      // 256 bytes past the last record
+        sa.mpart = w.take<double>(staged_chunks_cap(nc) * h * 15);
+        sa.pass_list = w.take<int32_t>(h);
+        sa.dig = w.take<uint4>(slots * 2 * 256);
+        sa.n_pass = (int32_t*)w.take_bytes(256);
+        sa.n32 = (int)slots * 64;
+        sa.c32 = w.take<float>((size_t)sa.n32 * 6);
+        sa.T32a = w.take<float>(h * 16); sa.T32b = w.take<float>(h * 16);
+        sa.p32 = w.take<float>((size_t)sa.n32 * 6);           // bounded second pass: p32, perm, bkt, BCtr
+        sa.perm = w.take<int32_t>((size_t)sa.n32);
+        sa.bkt = w.take<unsigned char>((size_t)sa.n32);
+        sa.bctr = w.take_bytes(align_up(sizeof(BCtr), 256));
+    }
+    *bytes = w.bytes(); return s;
 }
-size_t ransac_workspace_bytes(int iters, int B, int n_cap) {
-    size_t h = (size_t)iters * (size_t)B;
-    return align_up(h * 12 * sizeof(double), 256) + 2 * align_up(h * sizeof(int32_t), 256) + align_up(h, 256) +
-           align_up(h * 16 * sizeof(double), 256) /* ransac_hyp32_kernel's refit sums */ + staged_extra_bytes(h, B == 1 ? n_cap : 0);
-}
+size_t ransac_workspace_bytes(int iters, int B, int n_cap) { size_t b; (void)ransac_ws_layout(iters, B, n_cap, nullptr, &b); return b; }
 
 // ransac_hyp32_kernel: launch classes by correspondences per registration (LDS = 72 B per correspondence, rounded up to 128 of
 // them).  The kernel holds 126 VGPRs, four waves per SIMD, so a CU takes sixteen waves: two 8-wave workgroups of up to 1024
@@ -3200,19 +3223,15 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
                   void* ws, size_t ws_bytes, hipStream_t st, int hyp_begin, pcreg_dev_ransac_part* part) {
     PCREG_ARG(o.iterNum >= 1 && o.minPtNum >= 3 && B >= 1 && n_cap >= 0);
     PCREG_ARG(o.minPtNum == 3 || sample_idx_dev != nullptr);   // built-in sampler draws triples
-    size_t need = ransac_workspace_bytes(o.iterNum, B, n_cap);
+    size_t need; const RansacWs lay = ransac_ws_layout(o.iterNum, B, n_cap, ws, &need);
     if (ws_bytes < need) { set_error("ransac workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
     size_t h = (size_t)o.iterNum * (size_t)B;
-    char* w = (char*)ws;
     RansacArgs a{};
     a.p1 = p1; a.p2 = p2; a.ld = ld; a.offsets = offsets; a.n_dev = n_dev; a.n_cap = n_cap;
     a.iters = o.iterNum; a.m = o.minPtNum; a.thDist = o.thDist; a.ratio = o.thInlrRatio;
     a.refine = o.REFINE != 0; a.seed = o.seed; a.sample_idx = sample_idx_dev; a.hyp0g = hyp_begin;
     a.n_hi = 0x7FFFFFFF; a.n_lo = -1;
-    a.TF = (double*)w; w += align_up(h * 12 * sizeof(double), 256);
-    a.cnt1 = (int32_t*)w; w += align_up(h * sizeof(int32_t), 256);
-    a.cnt2 = (int32_t*)w; w += align_up(h * sizeof(int32_t), 256);
-    a.has = (unsigned char*)w; w += align_up(h, 256);
+    a.TF = lay.TF; a.cnt1 = lay.cnt1; a.cnt2 = lay.cnt2; a.has = lay.has;
     long long total = (long long)o.iterNum * B;
     void* sel_ctr = nullptr;              // set by the staged chain: its selection runs on several workgroups
     SelFinish sel_fin{nullptr, nullptr, 0};
@@ -3236,7 +3255,7 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         int hpw = 64;
         while (hpw > 8 && total / hpw < 256LL * 4 * 2) hpw >>= 1;
         a.hpw = hpw;
-        a.msc = (double*)w; w += align_up(h * 16 * sizeof(double), 256);
+        a.msc = lay.msc;
         // one launch: capacities up to 1024 as 8-wave workgroups with the LDS of the capacity (two to a CU), larger ones as 16-wave
         // workgroups with the LDS of min(capacity, 2048) correspondences (one to a CU: the same sixteen waves)
         const int c = n_cap <= kHyp32Classes[0] ? 0 : 1;
@@ -3253,36 +3272,8 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         }
     } else if (B == 1 && !offsets && staged_pays(n_cap, o.iterNum) && !debug_flag(kDbgRansacFused)) {
         // one large registration: the staged chain of lean kernels (see rs_* above)
-        StagedArgs sa{};
-        sa.T1 = (double*)w; w += align_up(h * 12 * sizeof(double), 256);
-        sa.mom = (double*)w; w += align_up(h * 27 * sizeof(double), 256);
-        sa.part = (int32_t*)w; w += align_up(h * kSMaxPB * sizeof(int32_t), 256);
-        sa.v1 = (unsigned char*)w; w += align_up(h, 256);
-        sa.pass1 = (unsigned char*)w; w += align_up(h, 256);
-        sa.v2 = (unsigned char*)w; w += align_up(h, 256);
-        sa.cert = (unsigned char*)w; w += align_up(h, 256);
-        sa.dense = (unsigned char*)w; w += align_up(h, 256);
-        sa.bounds = (double*)w; w += 256;
-        sa.n_rec_blocks = (int)((staged_slots_cap(n_cap) * 64 + 255) / 256);
-        sa.bpart = (double*)w; w += align_up((size_t)sa.n_rec_blocks * 4 * sizeof(double), 256);
-        sa.sel_ctr = w; w += 512;
+        StagedArgs sa = lay.sa;
         sel_ctr = sa.sel_ctr;
-        sa.certq = (double*)w; w += align_up(h * 2 * sizeof(double), 256);
-        sa.nslots_cap = (int)staged_slots_cap(n_cap);
-        sa.masks = (unsigned long long*)w; w += align_up(h * staged_slots_cap(n_cap) * 8, 256);
-        sa.rec = (double*)w; w += align_up(staged_slots_cap(n_cap) * 64 * kRec * sizeof(double) + 256, 256);
-        sa.mpart = (double*)w; w += align_up(staged_chunks_cap(n_cap) * h * 15 * sizeof(double), 256);
-        sa.pass_list = (int32_t*)w; w += align_up(h * sizeof(int32_t), 256);
-        sa.dig = (uint4*)w; w += align_up(staged_slots_cap(n_cap) * 2 * 256 * sizeof(uint4), 256);
-        sa.n_pass = (int32_t*)w; w += 256;
-        sa.n32 = (int)staged_slots_cap(n_cap) * 64;
-        sa.c32 = (float*)w; w += align_up((size_t)sa.n32 * 6 * sizeof(float), 256);
-        sa.T32a = (float*)w; w += align_up(h * 16 * sizeof(float), 256);
-        sa.T32b = (float*)w; w += align_up(h * 16 * sizeof(float), 256);
-        sa.p32 = (float*)w; w += align_up((size_t)sa.n32 * 6 * sizeof(float), 256);
-        sa.perm = (int32_t*)w; w += align_up((size_t)sa.n32 * sizeof(int32_t), 256);
-        sa.bkt = (unsigned char*)w; w += align_up((size_t)sa.n32, 256);
-        sa.bctr = w; w += align_up(sizeof(BCtr), 256);
         sa.use_lane = a.refine && !debug_flag(kDbgRansacNoLane);
         sa.use_f32 = !debug_flag(kDbgRansacF64Score);
         int pb = (n_cap + kSPts - 1) / kSPts; if (pb > kSMaxPB) pb = kSMaxPB; if (pb < 1) pb = 1;

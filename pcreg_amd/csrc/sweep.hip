@@ -357,20 +357,24 @@ int launch_sphere_counts(const double* feat, int V, const double* centres, int S
     return PCREG_OK;
 }
 
-size_t sphere_select_workspace_bytes(int V) {
-    size_t v = (size_t)(V > 0 ? V : 1);
-    return align_up(v * 4, 256) + align_up((v / 256 + 2) * 4, 256);
+// the workspace of launch_sphere_select, walked once: the in-sphere flag of every row, then the 256-row blocks' counts
+struct SphereWs { int32_t* flag; int32_t* bc; };
+static SphereWs sphere_ws_layout(int V, void* base, size_t* bytes) {
+    const size_t v = (size_t)std::max(V, 1);
+    WsWalk w(base);
+    const SphereWs s{w.take<int32_t>(v), w.take<int32_t>(v / 256 + 2)};          // (a braced list is evaluated left to right)
+    *bytes = w.bytes(); return s;
 }
+size_t sphere_select_workspace_bytes(int V) { size_t b; (void)sphere_ws_layout(V, nullptr, &b); return b; }
 int launch_sphere_select(const double* feat, int V, const double c[3], double R, int32_t* idx, int32_t* n_out, void* ws, size_t ws_bytes,
                          hipStream_t st) {
     if (V <= 0) { PCREG_HIP(hipMemsetAsync(n_out, 0, sizeof(int32_t), st)); return PCREG_OK; }
-    if (ws_bytes < sphere_select_workspace_bytes(V)) { set_error("sphere_select workspace too small"); return PCREG_E_WORKSPACE; }
-    int32_t* flag = (int32_t*)ws;
-    int32_t* bc = (int32_t*)((char*)ws + align_up((size_t)V * 4, 256));
+    size_t need; const SphereWs L = sphere_ws_layout(V, ws, &need);
+    if (ws_bytes < need) { set_error("sphere_select workspace too small"); return PCREG_E_WORKSPACE; }
     const int nb = (V + 255) / 256;
-    hipLaunchKernelGGL(sphere_flag_kernel, dim3(nb), dim3(256), 0, st, feat, V, c[0], c[1], c[2], sphere_sqrt_threshold(R), flag, bc);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, bc, nb, n_out);
-    hipLaunchKernelGGL(sphere_scatter_kernel, dim3(nb), dim3(256), 0, st, flag, V, bc, idx);
+    hipLaunchKernelGGL(sphere_flag_kernel, dim3(nb), dim3(256), 0, st, feat, V, c[0], c[1], c[2], sphere_sqrt_threshold(R), L.flag, L.bc);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, L.bc, nb, n_out);
+    hipLaunchKernelGGL(sphere_scatter_kernel, dim3(nb), dim3(256), 0, st, L.flag, V, L.bc, idx);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
@@ -382,14 +386,21 @@ int launch_sphere_select_batched(const double* feat, int V, const double* centre
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
-size_t local_points_workspace_bytes(int N) { return align_up(((size_t)(N + 255) / 256 + 1) * 2 * sizeof(int32_t), 256) + 256; }
+// the workspace of launch_local_points, walked once: (box, sphere) counts per 256-point block, and a spare slot nothing writes
+static int32_t* local_points_ws_layout(int N, void* base, size_t* bytes) {
+    WsWalk w(base);
+    int32_t* cnt = w.take<int32_t>(((size_t)(N + 255) / 256 + 1) * 2);
+    (void)w.take_bytes(256);                 // (kept: the size callers are given does not change)
+    *bytes = w.bytes(); return cnt;
+}
+size_t local_points_workspace_bytes(int N) { size_t b; (void)local_points_ws_layout(N, nullptr, &b); return b; }
 // counts -> totals[0] = points in the box, totals[1] = points in the sphere; pts_sphere / dists hold totals[1] rows
 int launch_local_points(const double* pts, int N, int ld, double R, const double c[3], int mode, double* out, int ldo, double* dists,
                         int32_t* totals, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (ws_bytes < local_points_workspace_bytes(N)) { set_error("getLocalPoints workspace too small"); return PCREG_E_WORKSPACE; }
+    size_t need; int32_t* const cnt = local_points_ws_layout(N, ws, &need);
+    if (ws_bytes < need) { set_error("getLocalPoints workspace too small"); return PCREG_E_WORKSPACE; }
     if (N <= 0) { PCREG_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int32_t), st)); return PCREG_OK; }
     const int nb = (N + 255) / 256;
-    int32_t* cnt = (int32_t*)ws;
     const LocalArgs a{c[0], c[1], c[2], R, mode};
     hipLaunchKernelGGL(local_count_kernel, dim3(nb), dim3(256), 0, st, pts, N, ld, a, cnt);
     hipLaunchKernelGGL(local_scan_kernel, dim3(1), dim3(256), 0, st, cnt, nb, totals);

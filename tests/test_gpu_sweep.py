@@ -262,8 +262,9 @@ def test_batched_sweep_counts_its_host_syncs(monkeypatch):
         np.testing.assert_array_equal(a, b)
 
 
-def _segments_direct(descS, descM, rows_list, par, metric=False):
-    """pcreg_dev_get_matches_segmented on explicit row lists -> per-segment (pairs, metric)."""
+def _segments_direct(descS, descM, rows_list, par, metric=False, ws=None):
+    """pcreg_dev_get_matches_segmented on explicit row lists -> per-segment (pairs, metric).  ws: the caller's (workspace tensor,
+    the workspace_bytes to pass) in place of one of the reported size."""
     import ctypes as C
     import torch
     from pcreg_amd._lib import check, lib
@@ -287,9 +288,9 @@ def _segments_direct(descS, descM, rows_list, par, metric=False):
     n_pairs = torch.full((S,), -1, dtype=torch.int32, device=dev)
     o = _match_opts(par)
     wsb = L.pcreg_dev_get_matches_segmented_workspace(Q, VM, D, S, tot, n_max)
-    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = ws if ws is not None else (torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev), None)
     check(L.pcreg_dev_get_matches_segmented(p(dS), Q, p(dM), VM, D, p(rows), p(seg_off), S, tot, n_max, C.byref(o), p(pairs),
-                                            p(met) if metric else None, p(n_pairs), p(ws), C.c_size_t(ws.numel()),
+                                            p(met) if metric else None, p(n_pairs), p(ws), C.c_size_t(ws.numel() if ws_bytes is None else ws_bytes),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     n = n_pairs.cpu().numpy()
     ph, mh = pairs.cpu().numpy().astype(np.uint32), met.cpu().numpy()
