@@ -9,7 +9,6 @@
 #include <atomic>
 #include <cstdarg>
 #include <cmath>
-#include <map>
 #include <mutex>
 #include <algorithm>
 #include <vector>
@@ -68,18 +67,6 @@ void Scratch::release_all() {
     for (int i = 0; i < kSlots; ++i) if (ptr[i]) { (void)hipFree(ptr[i]); ptr[i] = nullptr; size[i] = 0; }
 }
 Scratch& scratch() { static Scratch s; return s; }
-static std::map<hipStream_t, Scratch>& stream_scratches() { static std::map<hipStream_t, Scratch> m; return m; }
-Scratch& stream_scratch(hipStream_t st) { return stream_scratches()[st]; }
-
-// copy an n x cols column-major host matrix (leading dimension ld) to a compact device
-// matrix (leading dimension n)
-template <typename T>
-static int upload_cols(const T* host, int n, int ld, int cols, T* dev, hipStream_t st) {
-    if (n <= 0 || cols <= 0) return PCREG_OK;
-    if (ld == n) { PCREG_HIP(hipMemcpyAsync(dev, host, sizeof(T) * (size_t)n * cols, hipMemcpyHostToDevice, st)); }
-    else PCREG_HIP(hipMemcpy2DAsync(dev, sizeof(T) * (size_t)n, host, sizeof(T) * (size_t)ld, sizeof(T) * (size_t)n, cols, hipMemcpyHostToDevice, st));
-    return PCREG_OK;
-}
 
 }  // namespace pcreg
 
@@ -93,33 +80,31 @@ using namespace pcreg;
 namespace pcreg {
 static std::atomic<int> g_debug[kDbgCount];
 int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); }
-static unsigned long long* g_match_stats = nullptr;
-unsigned long long* match_stats_dev() {
-    if (!debug_flag(kDbgMatchStats)) return nullptr;
-    if (!g_match_stats) {
-        if (hipMalloc((void**)&g_match_stats, 8 * sizeof(unsigned long long)) != hipSuccess) { g_match_stats = nullptr; return nullptr; }
-        (void)hipMemset(g_match_stats, 0, 8 * sizeof(unsigned long long));
+// one block of device counters behind a debug key: allocated (zeroed) at the first use while the key is on
+struct Counters { DebugKey key; int n; unsigned long long* dev; };
+static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 4, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr};
+static unsigned long long* counters_dev(Counters& c) {
+    if (!debug_flag(c.key)) return nullptr;
+    if (!c.dev) {
+        if (hipMalloc((void**)&c.dev, c.n * sizeof(unsigned long long)) != hipSuccess) { c.dev = nullptr; return nullptr; }
+        (void)hipMemset(c.dev, 0, c.n * sizeof(unsigned long long));
     }
-    return g_match_stats;
+    return c.dev;
 }
-static unsigned long long* g_knn_stats = nullptr;
-unsigned long long* knn_stats_dev() {
-    if (!debug_flag(kDbgKnnStats)) return nullptr;
-    if (!g_knn_stats) {
-        if (hipMalloc((void**)&g_knn_stats, 4 * sizeof(unsigned long long)) != hipSuccess) { g_knn_stats = nullptr; return nullptr; }
-        (void)hipMemset(g_knn_stats, 0, 4 * sizeof(unsigned long long));
-    }
-    return g_knn_stats;
+static int counters_read(const Counters& c, long long* out, int reset) {
+    PCREG_ARG(out != nullptr);
+    for (int k = 0; k < c.n; ++k) out[k] = 0;
+    if (!c.dev) return PCREG_OK;                               // the key was never on
+    PCREG_HIP(hipDeviceSynchronize());
+    unsigned long long h[8];
+    PCREG_HIP(hipMemcpy(h, c.dev, c.n * sizeof h[0], hipMemcpyDeviceToHost));
+    for (int k = 0; k < c.n; ++k) out[k] = (long long)h[k];
+    if (reset) PCREG_HIP(hipMemset(c.dev, 0, c.n * sizeof h[0]));
+    return PCREG_OK;
 }
-static unsigned long long* g_ransac_stats = nullptr;
-unsigned long long* ransac_stats_dev() {
-    if (!debug_flag(kDbgRansacStats)) return nullptr;
-    if (!g_ransac_stats) {
-        if (hipMalloc((void**)&g_ransac_stats, 3 * sizeof(unsigned long long)) != hipSuccess) { g_ransac_stats = nullptr; return nullptr; }
-        (void)hipMemset(g_ransac_stats, 0, 3 * sizeof(unsigned long long));
-    }
-    return g_ransac_stats;
-}
+unsigned long long* match_stats_dev() { return counters_dev(g_match_stats); }
+unsigned long long* knn_stats_dev() { return counters_dev(g_knn_stats); }
+unsigned long long* ransac_stats_dev() { return counters_dev(g_ransac_stats); }
 }
 
 extern "C" {
@@ -136,41 +121,9 @@ int pcreg_debug_set(const char* key, int value) {
     return PCREG_E_ARG;
 }
 
-int pcreg_debug_match_stats(long long out[8], int reset) {
-    PCREG_ARG(out != nullptr);
-    for (int k = 0; k < 8; ++k) out[k] = 0;
-    if (!pcreg::g_match_stats) return PCREG_OK;               // "match_stats" was never on
-    PCREG_HIP(hipDeviceSynchronize());
-    unsigned long long h[8];
-    PCREG_HIP(hipMemcpy(h, pcreg::g_match_stats, sizeof h, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 8; ++k) out[k] = (long long)h[k];
-    if (reset) PCREG_HIP(hipMemset(pcreg::g_match_stats, 0, sizeof h));
-    return PCREG_OK;
-}
-
-int pcreg_debug_knn_stats(long long out[4], int reset) {
-    PCREG_ARG(out != nullptr);
-    for (int k = 0; k < 4; ++k) out[k] = 0;
-    if (!pcreg::g_knn_stats) return PCREG_OK;                 // "knn_stats" was never on
-    PCREG_HIP(hipDeviceSynchronize());
-    unsigned long long h[4];
-    PCREG_HIP(hipMemcpy(h, pcreg::g_knn_stats, sizeof h, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 4; ++k) out[k] = (long long)h[k];
-    if (reset) PCREG_HIP(hipMemset(pcreg::g_knn_stats, 0, sizeof h));
-    return PCREG_OK;
-}
-
-int pcreg_debug_ransac_stats(long long out[3], int reset) {
-    PCREG_ARG(out != nullptr);
-    for (int k = 0; k < 3; ++k) out[k] = 0;
-    if (!pcreg::g_ransac_stats) return PCREG_OK;              // "ransac_stats" was never on
-    PCREG_HIP(hipDeviceSynchronize());
-    unsigned long long h[3];
-    PCREG_HIP(hipMemcpy(h, pcreg::g_ransac_stats, sizeof h, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) out[k] = (long long)h[k];
-    if (reset) PCREG_HIP(hipMemset(pcreg::g_ransac_stats, 0, sizeof h));
-    return PCREG_OK;
-}
+int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counters_read(pcreg::g_match_stats, out, reset); }
+int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset); }
+int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset); }
 
 const char* pcreg_last_error(void) { return g_err; }
 const char* pcreg_version(void) { return "pcreg-hip 0.1 (gfx950)"; }
@@ -193,8 +146,6 @@ int pcreg_set_device(int ordinal) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { set_error("no HIP device available"); (void)hipGetLastError(); return PCREG_E_NODEVICE; }
     PCREG_ARG(ordinal >= 0 && ordinal < count);
     scratch().release_all();
-    for (auto& kv : stream_scratches()) kv.second.release_all();
-    stream_scratches().clear();
     if (g_stream) { (void)hipStreamDestroy(g_stream); g_stream = nullptr; }
     if (g_pairs_ev) { (void)hipEventDestroy(g_pairs_ev); g_pairs_ev = nullptr; }
     for (int k = 0; k < 2; ++k) if (g_pin[k]) { (void)hipHostFree(g_pin[k]); g_pin[k] = nullptr; g_pin_bytes[k] = 0; }
@@ -219,14 +170,15 @@ int pcreg_estimate_transform(const double* pts1, const double* pts2, int n, int 
     for (int k = 0; k < 16; ++k) T[k] = 0.0;
     *empty = 1;
     if (n < 3) return PCREG_OK;          // rank(pts1) < 3 -> [] (estimateTransform.m:11-14)
-    void *d1, *d2, *dT;
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)n, &d1));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)n, &d2));
-    TRY(scratch().get(2, 256, &dT));
-    TRY(upload_cols(pts1, n, ld, 3, (double*)d1, g_stream));
-    TRY(upload_cols(pts2, n, ld, 3, (double*)d2, g_stream));
-    int32_t* dE = (int32_t*)((char*)dT + 128);
-    TRY(launch_estimate_transform((double*)d1, (double*)d2, n, n, (double*)dT, dE, g_stream));
+    Stage st{scratch()};
+    double *d1, *d2, *dT;
+    TRY(st.take(3 * (size_t)n, &d1));
+    TRY(st.take(3 * (size_t)n, &d2));
+    TRY(st.take(32, &dT));                                  // T [16] | empty, 128 bytes in
+    TRY(upload_cols(pts1, n, ld, 3, d1, g_stream));
+    TRY(upload_cols(pts2, n, ld, 3, d2, g_stream));
+    int32_t* dE = (int32_t*)(dT + 16);
+    TRY(launch_estimate_transform(d1, d2, n, n, dT, dE, g_stream));
     int32_t e = 1;
     PCREG_HIP(hipMemcpyAsync(T, dT, sizeof(double) * 16, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(&e, dE, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
@@ -239,15 +191,16 @@ int pcreg_calc_dists(const double T[16], const double* pts1, const double* pts2,
     PCREG_ARG(T && pts1 && pts2 && d && n >= 0 && ld >= n);
     GUARD();
     if (n == 0) return PCREG_OK;
-    void *d1, *d2, *dT, *dd;
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)n, &d1));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)n, &d2));
-    TRY(scratch().get(2, 256, &dT));
-    TRY(scratch().get(3, sizeof(double) * (size_t)n, &dd));
-    TRY(upload_cols(pts1, n, ld, 3, (double*)d1, g_stream));
-    TRY(upload_cols(pts2, n, ld, 3, (double*)d2, g_stream));
+    Stage st{scratch()};
+    double *d1, *d2, *dT, *dd;
+    TRY(st.take(3 * (size_t)n, &d1));
+    TRY(st.take(3 * (size_t)n, &d2));
+    TRY(st.take(16, &dT));
+    TRY(st.take((size_t)n, &dd));
+    TRY(upload_cols(pts1, n, ld, 3, d1, g_stream));
+    TRY(upload_cols(pts2, n, ld, 3, d2, g_stream));
     PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16, hipMemcpyHostToDevice, g_stream));
-    TRY(launch_calc_dists((double*)dT, (double*)d1, (double*)d2, n, n, (double*)dd, g_stream));
+    TRY(launch_calc_dists(dT, d1, d2, n, n, dd, g_stream));
     PCREG_HIP(hipMemcpyAsync(d, dd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     return PCREG_OK;
@@ -264,25 +217,27 @@ static int ransac_host(const double* pts1, const double* pts2, int total, int ld
     PCREG_ARG(offsets[0] == 0 && offsets[B] == total);
     size_t hyps = (size_t)o->iterNum * B;
     size_t wsb = ransac_workspace_bytes(o->iterNum, B, max_n);
-    void *d1, *d2, *dOff, *dS = nullptr, *dOut, *dInl, *ws, *dI1 = nullptr, *dI2 = nullptr;
+    Stage st{scratch()};
+    double *d1, *d2; int32_t *dOff, *dInl, *dS, *dI1, *dI2; pcreg_dev_ransac_result* dOut; char* ws;
     size_t tot = (size_t)(total > 0 ? total : 1);
-    TRY(scratch().get(0, sizeof(double) * 3 * tot, &d1));
-    TRY(scratch().get(1, sizeof(double) * 3 * tot, &d2));
-    TRY(scratch().get(2, sizeof(int32_t) * ((size_t)B + 1), &dOff));
-    TRY(scratch().get(3, sizeof(pcreg_dev_ransac_result) * (size_t)B, &dOut));
-    TRY(scratch().get(4, sizeof(int32_t) * tot, &dInl));
-    TRY(scratch().get(5, wsb, &ws));
-    if (sample_idx) {
-        TRY(scratch().get(6, sizeof(int32_t) * hyps * o->minPtNum, &dS));
-        PCREG_HIP(hipMemcpyAsync(dS, sample_idx, sizeof(int32_t) * hyps * o->minPtNum, hipMemcpyHostToDevice, g_stream));
-    }
-    if (iter_inl) TRY(scratch().get(7, sizeof(int32_t) * hyps, &dI1));
-    if (iter_inl_ref) TRY(scratch().get(8, sizeof(int32_t) * hyps, &dI2));
-    TRY(upload_cols(pts1, total, ld, 3, (double*)d1, g_stream));
-    TRY(upload_cols(pts2, total, ld, 3, (double*)d2, g_stream));
+    TRY(st.take(3 * tot, &d1));
+    TRY(st.take(3 * tot, &d2));
+    TRY(st.take((size_t)B + 1, &dOff));
+    TRY(st.take((size_t)B, &dOut));
+    TRY(st.take(tot, &dInl));
+    TRY(st.take(wsb, &ws));
+    // the optional tables behind everything else, taken (empty) on every path: each keeps its slot
+    TRY(st.take(sample_idx ? hyps * o->minPtNum : 0, &dS));
+    TRY(st.take(iter_inl ? hyps : 0, &dI1));
+    TRY(st.take(iter_inl_ref ? hyps : 0, &dI2));
+    if (!sample_idx) dS = nullptr;
+    if (!iter_inl) dI1 = nullptr;
+    if (!iter_inl_ref) dI2 = nullptr;
+    if (sample_idx) PCREG_HIP(hipMemcpyAsync(dS, sample_idx, sizeof(int32_t) * hyps * o->minPtNum, hipMemcpyHostToDevice, g_stream));
+    TRY(upload_cols(pts1, total, ld, 3, d1, g_stream));
+    TRY(upload_cols(pts2, total, ld, 3, d2, g_stream));
     PCREG_HIP(hipMemcpyAsync(dOff, offsets, sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, g_stream));
-    TRY(launch_ransac((double*)d1, (double*)d2, total, (int32_t*)dOff, nullptr, max_n, B, *o, (int32_t*)dS,
-                      (pcreg_dev_ransac_result*)dOut, (int32_t*)dInl, (int32_t*)dI1, (int32_t*)dI2, ws, wsb, g_stream));
+    TRY(launch_ransac(d1, d2, total, dOff, nullptr, max_n, B, *o, dS, dOut, dInl, dI1, dI2, ws, wsb, g_stream));
     std::vector<pcreg_dev_ransac_result> res((size_t)B);
     PCREG_HIP(hipMemcpyAsync(res.data(), dOut, sizeof(pcreg_dev_ransac_result) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
     if (total > 0) PCREG_HIP(hipMemcpyAsync(inlier_idx, dInl, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, g_stream));
@@ -324,16 +279,17 @@ int pcreg_knn2_points_f32(const float* q, int Q, int ldq, const float* m, int M,
     PCREG_ARG(q && m && idx && dist && Q >= 0 && M >= 0 && ldq >= Q && ldm >= M);
     GUARD();
     if (Q == 0) return PCREG_OK;
-    void *dq, *dm, *di, *dd, *ws;
+    Stage st{scratch()};
+    float *dq, *dm, *dd; int32_t* di; char* ws;
     size_t wsb = knn2_points_workspace_bytes(Q, M);
-    TRY(scratch().get(0, sizeof(float) * 3 * (size_t)Q, &dq));
-    TRY(scratch().get(1, sizeof(float) * 3 * (size_t)(M > 0 ? M : 1), &dm));
-    TRY(scratch().get(2, sizeof(int32_t) * 2 * (size_t)Q, &di));
-    TRY(scratch().get(3, sizeof(float) * 2 * (size_t)Q, &dd));
-    TRY(scratch().get(4, wsb, &ws));
-    TRY(upload_cols(q, Q, ldq, 3, (float*)dq, g_stream));
-    TRY(upload_cols(m, M, ldm, 3, (float*)dm, g_stream));
-    TRY(launch_knn2_points_f32((float*)dq, Q, Q, (float*)dm, M, M, 0, (int32_t*)di, (float*)dd, ws, wsb, g_stream));
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(2 * (size_t)Q, &di));
+    TRY(st.take(2 * (size_t)Q, &dd));
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    TRY(launch_knn2_points_f32(dq, Q, Q, dm, M, M, 0, di, dd, ws, wsb, g_stream));
     PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * 2 * (size_t)Q, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
@@ -420,23 +376,21 @@ int pcreg_dev_match_from_table_f32(const float* q, int Q, int ldq, int M_total, 
 }
 
 // matchFeatures' chain on raw points against a prepared model: upload the surface, search (4 launches), match (1)
-static int match_points_on_view(const ModelView& v, const float* q, int Q, int ldq, float thr_abs, float max_ratio, int unique,
+static int match_points_on_view(Stage& st, const ModelView& v, const float* q, int Q, int ldq, float thr_abs, float max_ratio, int unique,
                                 uint32_t* pairs, int* P) {
     *P = 0;
     if (Q == 0 || v.M == 0) return PCREG_OK;
-    void *dq, *di, *dd, *ws, *dcnt, *dpairs;
+    float *dq, *dd; int32_t *di, *n_pairs; char* ws; uint32_t* dpairs;
     const size_t wsb = search_ws_bytes(Q, v.M);
-    TRY(scratch().get(0, sizeof(float) * 3 * (size_t)Q, &dq));
-    TRY(scratch().get(2, sizeof(int32_t) * 2 * (size_t)Q, &di));
-    TRY(scratch().get(3, sizeof(float) * 2 * (size_t)Q, &dd));
-    TRY(scratch().get(4, wsb, &ws));
-    TRY(scratch().get(8, 256, &dcnt));
-    TRY(scratch().get(9, sizeof(uint32_t) * 2 * (size_t)Q, &dpairs));
-    int32_t* n_pairs = (int32_t*)dcnt;
-    TRY(upload_cols(q, Q, ldq, 3, (float*)dq, g_stream));
-    TRY(launch_model_search(v, (float*)dq, Q, Q, 0, (int32_t*)di, (float*)dd, ws, wsb, true, true, g_stream));
-    TRY(launch_match_finish(v, (float*)dq, Q, Q, (int32_t*)di, (float*)dd, thr_abs, max_ratio, unique, ws, wsb, (uint32_t*)dpairs, nullptr,
-                            nullptr, n_pairs, g_stream));
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(2 * (size_t)Q, &di));
+    TRY(st.take(2 * (size_t)Q, &dd));
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(1, &n_pairs));
+    TRY(st.take(2 * (size_t)Q, &dpairs));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    TRY(launch_model_search(v, dq, Q, Q, 0, di, dd, ws, wsb, true, true, g_stream));
+    TRY(launch_match_finish(v, dq, Q, Q, di, dd, thr_abs, max_ratio, unique, ws, wsb, dpairs, nullptr, nullptr, n_pairs, g_stream));
     int32_t np = 0;
     PCREG_HIP(hipMemcpyAsync(&np, n_pairs, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
@@ -472,20 +426,21 @@ int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int 
                                  uint32_t* pairs, int* P) {
     PCREG_ARG(model && model->dm && q && pairs && P && Q >= 0 && ldq >= Q);
     GUARD();
-    return match_points_on_view(model->dm->v, q, Q, ldq, thr_abs, max_ratio, unique, pairs, P);
+    Stage st{scratch()};
+    return match_points_on_view(st, model->dm->v, q, Q, ldq, thr_abs, max_ratio, unique, pairs, P);
 }
 
 // the k nearest rows on a prepared model: upload the queries, search, copy [Q][k] back
-static int knn_on_view(const ModelView& v, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist) {
+static int knn_on_view(Stage& st, const ModelView& v, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist) {
     if (Q == 0) return PCREG_OK;
-    void *dq, *di, *dd, *ws;
+    float *dq, *dd; int32_t* di; char* ws;
     const size_t wsb = knn_k_ws_bytes(Q, v.M, k), nk = (size_t)Q * k;
-    TRY(scratch().get(0, sizeof(float) * 3 * (size_t)Q, &dq));
-    TRY(scratch().get(2, sizeof(int32_t) * nk, &di));
-    TRY(scratch().get(3, sizeof(float) * nk, &dd));
-    TRY(scratch().get(4, wsb, &ws));
-    TRY(upload_cols(q, Q, ldq, 3, (float*)dq, g_stream));
-    TRY(launch_model_knn(v, (float*)dq, Q, Q, k, 0, (int32_t*)di, (float*)dd, ws, wsb, g_stream));
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(nk, &di));
+    TRY(st.take(nk, &dd));
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    TRY(launch_model_knn(v, dq, Q, Q, k, 0, di, dd, ws, wsb, g_stream));
     PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * nk, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
@@ -495,19 +450,21 @@ int pcreg_model_knn_f32(pcreg_model* model, const float* q, int Q, int ldq, int 
     PCREG_ARG(model && q && idx && dist && k >= 1 && k <= kKnnMaxK && Q >= 0 && ldq >= Q && Q <= kKnnMaxQ);
     PCREG_ARG(model->dm != nullptr);
     GUARD();
-    return knn_on_view(model->dm->v, q, Q, ldq, k, idx, dist);
+    Stage st{scratch()};
+    return knn_on_view(st, model->dm->v, q, Q, ldq, k, idx, dist);
 }
 int pcreg_knn_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int k, int32_t* idx, float* dist) {
     PCREG_ARG(q && m && idx && dist && k >= 1 && k <= kKnnMaxK && Q >= 0 && M >= 0 && ldq >= Q && ldm >= M && Q <= kKnnMaxQ);
     GUARD();
     if (Q == 0) return PCREG_OK;
-    void *dm, *block;
-    TRY(scratch().get(1, sizeof(float) * 3 * (size_t)(M > 0 ? M : 1), &dm));
-    TRY(scratch().get(10, model_prep_bytes(M), &block));
-    TRY(upload_cols(m, M, ldm, 3, (float*)dm, g_stream));
-    const ModelView v = model_view((float*)dm, M, M > 0 ? M : 1, block);
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
-    return knn_on_view(v, q, Q, ldq, k, idx, dist);
+    return knn_on_view(st, v, q, Q, ldq, k, idx, dist);
 }
 
 int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float thr_abs,
@@ -516,94 +473,86 @@ int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M
     GUARD();
     *P = 0;
     if (Q == 0 || M == 0) return PCREG_OK;
-    void *dm, *block;
-    TRY(scratch().get(1, sizeof(float) * 3 * (size_t)M, &dm));
-    TRY(scratch().get(10, model_prep_bytes(M), &block));
-    TRY(upload_cols(m, M, ldm, 3, (float*)dm, g_stream));
-    const ModelView v = model_view((float*)dm, M, M, block);
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)M, &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M, block);
     TRY(launch_model_prepare(v, g_stream));
-    return match_points_on_view(v, q, Q, ldq, thr_abs, max_ratio, unique, pairs, P);
+    return match_points_on_view(st, v, q, Q, ldq, thr_abs, max_ratio, unique, pairs, P);
 }
 
-// raw descriptor matrices on the device (column-major, ld = rows) -> getMatches.m:22-56 -> pairs on the host.  rawS / rawM are not
-// modified: the preprocessing writes its own copies (scratch slots 0, 1).
-static int match_dev_raw(const double* rawS, int Q, const double* rawM, int M, int D, const pcreg_match_opts* o, uint32_t* pairs, double* metric, int* P) {
-    *P = 0;
-    if (Q == 0 || M == 0) return PCREG_OK;
-    const int Dp = D + (o->unnormalize ? 1 : 0);
-    void *dS, *dM, *ws, *dpairs, *dmet, *dcnt, *pws = nullptr;
-    size_t wsb = match_features_workspace_bytes(Q, M, Dp);
-    TRY(scratch().get(0, sizeof(double) * (size_t)Q * Dp, &dS));
-    TRY(scratch().get(1, sizeof(double) * (size_t)M * Dp, &dM));
-    TRY(scratch().get(2, wsb, &ws));
-    TRY(scratch().get(3, sizeof(uint32_t) * 2 * (size_t)Q, &dpairs));
-    TRY(scratch().get(4, sizeof(double) * (size_t)Q, &dmet));
-    TRY(scratch().get(5, 256, &dcnt));
-    size_t pwb = sizeof(double) * ((size_t)Q + M + 1);
-    TRY(scratch().get(8, pwb, &pws));
-    TRY(launch_preprocess(rawS, Q, Q, rawM, M, M, D, *o, (double*)dS, (double*)dM, pws, pwb, g_stream));
+// the matcher's own buffers, staged in front of the rows it will read: its workspace meets the same slot whether the rows are
+// uploaded as they are (matchFeatures) or made by the preprocessing (getMatches)
+struct MatchStage { char* ws; size_t wsb; uint32_t* dpairs; double* dmet; int32_t* dcnt; };
+static int match_stage(Stage& st, int Q, int M, int Dp, MatchStage* m) {
+    m->wsb = match_features_workspace_bytes(Q, M, Dp);
+    TRY(st.take(m->wsb, &m->ws));
+    TRY(st.take(2 * (size_t)Q, &m->dpairs));
+    TRY(st.take((size_t)Q, &m->dmet));
+    return st.take(1, &m->dcnt);
+}
+// the matcher on prepared rows dS [Q][Dp], dM [M][Dp] (column-major, ld = rows; normalized in place unless prenormalized) -> pairs on the host
+static int match_rows(const MatchStage& m, double* dS, int Q, double* dM, int M, int Dp, const pcreg_match_opts* o, uint32_t* pairs, double* metric, int* P) {
     if (!o->prenormalized) {
-        TRY(launch_normalize_rows2((double*)dS, Q, Q, (double*)dM, M, M, Dp, g_stream));
+        TRY(launch_normalize_rows2(dS, Q, Q, dM, M, M, Dp, g_stream));
     }
-    TRY(launch_match_features((double*)dS, Q, Q, (double*)dM, M, M, Dp, *o, (uint32_t*)dpairs,
-                              metric ? (double*)dmet : nullptr, (int32_t*)dcnt, ws, wsb, g_stream));
+    TRY(launch_match_features(dS, Q, Q, dM, M, M, Dp, *o, m.dpairs, metric ? m.dmet : nullptr, m.dcnt, m.ws, m.wsb, g_stream));
     int32_t np = 0;
-    PCREG_HIP(hipMemcpyAsync(&np, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(&np, m.dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     if (np > 0) {
-        PCREG_HIP(hipMemcpy(pairs, dpairs, sizeof(uint32_t) * 2 * (size_t)np, hipMemcpyDeviceToHost));
-        if (metric) PCREG_HIP(hipMemcpy(metric, dmet, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost));
+        PCREG_HIP(hipMemcpy(pairs, m.dpairs, sizeof(uint32_t) * 2 * (size_t)np, hipMemcpyDeviceToHost));
+        if (metric) PCREG_HIP(hipMemcpy(metric, m.dmet, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost));
     }
     *P = np;
     return PCREG_OK;
+}
+
+// raw descriptor matrices on the device (column-major, ld = rows) -> getMatches.m:22-56 -> pairs on the host.  rawS / rawM are not
+// modified: the preprocessing writes its own copies.
+static int match_dev_raw(Stage& st, const double* rawS, int Q, const double* rawM, int M, int D, const pcreg_match_opts* o, uint32_t* pairs, double* metric, int* P) {
+    *P = 0;
+    if (Q == 0 || M == 0) return PCREG_OK;
+    const int Dp = D + (o->unnormalize ? 1 : 0);
+    MatchStage m;
+    double *dS, *dM, *pws;
+    const size_t pwn = (size_t)Q + M + 1;
+    TRY(match_stage(st, Q, M, Dp, &m));
+    TRY(st.take((size_t)Q * Dp, &dS));
+    TRY(st.take((size_t)M * Dp, &dM));
+    TRY(st.take(pwn, &pws));
+    TRY(launch_preprocess(rawS, Q, Q, rawM, M, M, D, *o, dS, dM, pws, sizeof(double) * pwn, g_stream));
+    return match_rows(m, dS, Q, dM, M, Dp, o, pairs, metric, P);
 }
 
 static int match_host(const double* f1, int Q, int ld1, const double* f2, int M, int ld2, int D,
                       const pcreg_match_opts* o, bool preprocess, uint32_t* pairs, double* metric, int* P) {
     *P = 0;
     if (Q == 0 || M == 0) return PCREG_OK;
-    if (preprocess) {
-        void *rawS = nullptr, *rawM = nullptr;
-        TRY(scratch().get(6, sizeof(double) * (size_t)Q * D, &rawS));
-        TRY(scratch().get(7, sizeof(double) * (size_t)M * D, &rawM));
-        TRY(upload_cols(f1, Q, ld1, D, (double*)rawS, g_stream));
-        TRY(upload_cols(f2, M, ld2, D, (double*)rawM, g_stream));
-        return match_dev_raw((const double*)rawS, Q, (const double*)rawM, M, D, o, pairs, metric, P);
-    }
-    const int Dp = D;
-    void *dS, *dM, *ws, *dpairs, *dmet, *dcnt;
-    size_t wsb = match_features_workspace_bytes(Q, M, Dp);
-    TRY(scratch().get(0, sizeof(double) * (size_t)Q * Dp, &dS));
-    TRY(scratch().get(1, sizeof(double) * (size_t)M * Dp, &dM));
-    TRY(scratch().get(2, wsb, &ws));
-    TRY(scratch().get(3, sizeof(uint32_t) * 2 * (size_t)Q, &dpairs));
-    TRY(scratch().get(4, sizeof(double) * (size_t)Q, &dmet));
-    TRY(scratch().get(5, 256, &dcnt));
-    TRY(upload_cols(f1, Q, ld1, D, (double*)dS, g_stream));
-    TRY(upload_cols(f2, M, ld2, D, (double*)dM, g_stream));
-    if (!o->prenormalized) {
-        TRY(launch_normalize_rows2((double*)dS, Q, Q, (double*)dM, M, M, Dp, g_stream));
-    }
-    TRY(launch_match_features((double*)dS, Q, Q, (double*)dM, M, M, Dp, *o, (uint32_t*)dpairs,
-                              metric ? (double*)dmet : nullptr, (int32_t*)dcnt, ws, wsb, g_stream));
-    int32_t np = 0;
-    PCREG_HIP(hipMemcpyAsync(&np, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    if (np > 0) {
-        PCREG_HIP(hipMemcpy(pairs, dpairs, sizeof(uint32_t) * 2 * (size_t)np, hipMemcpyDeviceToHost));
-        if (metric) PCREG_HIP(hipMemcpy(metric, dmet, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost));
-    }
-    *P = np;
-    return PCREG_OK;
+    Stage st{scratch()};
+    double *dS, *dM;                                  // the raw matrices (getMatches) or the rows themselves (matchFeatures)
+    TRY(st.take((size_t)Q * D, &dS));
+    TRY(st.take((size_t)M * D, &dM));
+    TRY(upload_cols(f1, Q, ld1, D, dS, g_stream));
+    TRY(upload_cols(f2, M, ld2, D, dM, g_stream));
+    if (preprocess) return match_dev_raw(st, dS, Q, dM, M, D, o, pairs, metric, P);
+    MatchStage m;
+    TRY(match_stage(st, Q, M, D, &m));
+    return match_rows(m, dS, Q, dM, M, D, o, pairs, metric, P);
 }
 
 // ---- resident descriptor sets (host tier): one surface set against hundreds of row subsets of one model set
 // (completeExperimentFast.m:101-150) without re-uploading ~28 MB of doubles per sphere
+// The powered rows + row scalars of a MODEL of the segmented matcher (SegPreparedModel), valid for the getMatches options they
+// were made with: made at the first use, remade when the options change (caller holds the library lock).
+struct PreparedRows { double* P = nullptr; int cm = -1; double factor = 0.0; };
+static int prepared_rows(PreparedRows& c, const double* rows, int n, int D, const pcreg_match_opts& o, SegPreparedModel* out);
 struct pcreg_desc_set {
     double* d; int n, D;            // n x D column-major on the device (ld = n), as uploaded
     double* rows;                   // the dense row-major copy the segmented matcher reads, made at its first use
-    double* prep;                   // as a MODEL of the segmented matcher: powered rows + row scalars (SegPreparedModel), for ...
-    int prep_cm; double prep_factor;   // ... these getMatches options (made at the first use, remade when they change)
+    PreparedRows prep;              // the set as a model of the segmented matcher
 };
 
 __global__ void gather_cols_kernel(const double* __restrict__ src, int n_src, int D, const int32_t* __restrict__ rows, int n, double* __restrict__ dst) {
@@ -620,7 +569,7 @@ int pcreg_desc_set_create(const double* desc, int n, int ld, int D, pcreg_desc_s
     int rc = upload_cols(desc, n, ld, D, d, g_stream);
     if (!rc && hipStreamSynchronize(g_stream) != hipSuccess) { set_error("descriptor upload failed"); rc = PCREG_E_HIP; }
     if (rc) { (void)hipFree(d); return rc; }
-    *set = new pcreg_desc_set{d, n, D, nullptr, nullptr, 0, 0.0};
+    *set = new pcreg_desc_set{d, n, D, nullptr, {}};
     return PCREG_OK;
 }
 int pcreg_desc_set_destroy(pcreg_desc_set* set) {
@@ -629,7 +578,7 @@ int pcreg_desc_set_destroy(pcreg_desc_set* set) {
     (void)hipDeviceSynchronize();
     (void)hipFree(set->d);
     if (set->rows) (void)hipFree(set->rows);
-    if (set->prep) (void)hipFree(set->prep);
+    if (set->prep.P) (void)hipFree(set->prep.P);
     delete set;
     return PCREG_OK;
 }
@@ -645,16 +594,17 @@ int pcreg_get_matches_on_sets(const pcreg_desc_set* surface, const pcreg_desc_se
     GUARD();
     *P = 0;
     const int Q = surface->n, D = surface->D;
-    if (!model_rows) return match_dev_raw(surface->d, Q, model->d, model->n, D, par, pairs, metric, P);      // descModel(:, :)
-    for (int k = 0; k < n_rows; ++k) PCREG_ARG(model_rows[k] >= 0 && model_rows[k] < model->n);
+    if (model_rows) for (int k = 0; k < n_rows; ++k) PCREG_ARG(model_rows[k] >= 0 && model_rows[k] < model->n);
+    Stage st{scratch()};
+    double* rawM; int32_t* drows;                     // taken (empty) without a row list too: the matcher's buffers keep their slots
+    TRY(st.take(model_rows ? (size_t)n_rows * D : 0, &rawM));
+    TRY(st.take(model_rows ? (size_t)n_rows : 0, &drows));
+    if (!model_rows) return match_dev_raw(st, surface->d, Q, model->d, model->n, D, par, pairs, metric, P);      // descModel(:, :)
     if (Q == 0 || n_rows == 0) return PCREG_OK;
-    void *rawM, *drows;
-    TRY(scratch().get(7, sizeof(double) * (size_t)n_rows * D, &rawM));
-    TRY(scratch().get(9, sizeof(int32_t) * (size_t)n_rows, &drows));
     PCREG_HIP(hipMemcpyAsync(drows, model_rows, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, g_stream));
-    hipLaunchKernelGGL(gather_cols_kernel, dim3((n_rows + 255) / 256, D), dim3(256), 0, g_stream, model->d, model->n, D, (const int32_t*)drows, n_rows, (double*)rawM);   // descModel(rows, :)
+    hipLaunchKernelGGL(gather_cols_kernel, dim3((n_rows + 255) / 256, D), dim3(256), 0, g_stream, model->d, model->n, D, (const int32_t*)drows, n_rows, rawM);   // descModel(rows, :)
     PCREG_HIP(hipGetLastError());
-    return match_dev_raw(surface->d, Q, (const double*)rawM, n_rows, D, par, pairs, metric, P);
+    return match_dev_raw(st, surface->d, Q, rawM, n_rows, D, par, pairs, metric, P);
 }
 
 int pcreg_match_features(const double* f1, int Q, int ld1, const double* f2, int M, int ld2, int D,
@@ -680,14 +630,15 @@ int pcreg_get_local_points(const double* pts, int N, int ld, double R, const dou
     GUARD();
     *n_out = 0;
     if (N == 0) return PCREG_OK;
-    void *dp, *dout, *dd, *dt, *ws;
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)N, &dp));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)N, &dout));
-    TRY(scratch().get(2, sizeof(double) * (size_t)N, &dd));
-    TRY(scratch().get(3, 256, &dt));
-    TRY(scratch().get(4, local_points_workspace_bytes(N), &ws));
-    TRY(upload_cols(pts, N, ld, 3, (double*)dp, g_stream));
-    TRY(launch_local_points((const double*)dp, N, N, R, c, single_mode, (double*)dout, N, (double*)dd, (int32_t*)dt, ws, local_points_workspace_bytes(N), g_stream));
+    Stage st{scratch()};
+    double *dp, *dout, *dd; int32_t* dt; char* ws;
+    TRY(st.take(3 * (size_t)N, &dp));
+    TRY(st.take(3 * (size_t)N, &dout));
+    TRY(st.take((size_t)N, &dd));
+    TRY(st.take(2, &dt));
+    TRY(st.take(local_points_workspace_bytes(N), &ws));
+    TRY(upload_cols(pts, N, ld, 3, dp, g_stream));
+    TRY(launch_local_points(dp, N, N, R, c, single_mode, dout, N, dd, dt, ws, local_points_workspace_bytes(N), g_stream));
     int32_t tot[2] = {0, 0};
     PCREG_HIP(hipMemcpyAsync(tot, dt, sizeof(tot), hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
@@ -695,7 +646,7 @@ int pcreg_get_local_points(const double* pts, int N, int ld, double R, const dou
     if ((double)tot[0] < min_points || (double)tot[1] < min_points || (double)tot[1] > max_points || tot[1] == 0) return PCREG_OK;
     const size_t n = (size_t)tot[1];
     for (int k = 0; k < 3; ++k)
-        PCREG_HIP(hipMemcpyAsync(pts_sphere + (size_t)k * n, (const double*)dout + (size_t)k * N, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipMemcpyAsync(pts_sphere + (size_t)k * n, dout + (size_t)k * N, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     if (dists) PCREG_HIP(hipMemcpyAsync(dists, dd, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     *n_out = tot[1];
@@ -728,7 +679,7 @@ static int pairs_fetch_begin(const int32_t* dn, int S, PairFetch& f) {
     PCREG_HIP(hipEventRecord(g_pairs_ev, g_stream));
     return PCREG_OK;
 }
-static int pairs_fetch_enqueue(PairFetch& f, const uint32_t* dp, size_t vs, int S, int pack_slot, uint32_t* pairs_all) {
+static int pairs_fetch_enqueue(Stage& st, PairFetch& f, const uint32_t* dp, size_t vs, int S, uint32_t* pairs_all) {
     PCREG_HIP(hipEventSynchronize(g_pairs_ev));
     int m = 0;
     for (int z = 0; z < S; ++z) m = std::max(m, (int)f.h_np[z]);
@@ -739,9 +690,9 @@ static int pairs_fetch_enqueue(PairFetch& f, const uint32_t* dp, size_t vs, int 
         PCREG_HIP(hipMemcpyAsync(pairs_all, dp, sizeof(uint32_t) * (size_t)S * vs * 2, hipMemcpyDeviceToHost, g_stream));
         return PCREG_OK;
     }
-    void* packed;
+    char* packed;
     const size_t row = sizeof(uint32_t) * 2 * (size_t)m;
-    TRY(scratch().get(pack_slot, row * (size_t)S, &packed));
+    TRY(st.take(row * (size_t)S, &packed));
     TRY(pinned_get(1, row * (size_t)S, &f.h_packed));
     PCREG_HIP(hipMemcpy2DAsync(packed, row, dp, sizeof(uint32_t) * 2 * vs, row, (size_t)S, hipMemcpyDeviceToDevice, g_stream));
     PCREG_HIP(hipMemcpyAsync(f.h_packed, packed, row * (size_t)S, hipMemcpyDeviceToHost, g_stream));
@@ -754,50 +705,6 @@ static void pairs_fetch_finish(const PairFetch& f, size_t vs, int S, uint32_t* p
         if (!f.whole && f.m > 0 && f.h_np[z] > 0)
             memcpy(pairs_all + (size_t)z * vs * 2, (const char*)f.h_packed + sizeof(uint32_t) * 2 * (size_t)f.m * z, sizeof(uint32_t) * 2 * (size_t)f.h_np[z]);
     }
-}
-
-// getMatches for S row subsets of one model set, host tier (the parfor of completeExperimentFast.m:131-149 as ONE call)
-int pcreg_get_matches_segmented(const double* descSurface, int Q, int ldS, const double* descModel, int VM, int ldM, int D,
-                                const int32_t* seg_rows, const int32_t* seg_off, int S, const pcreg_match_opts* par,
-                                uint32_t* pairs_all, int32_t* n_pairs) {
-    PCREG_ARG(descSurface && descModel && seg_off && par && pairs_all && n_pairs && Q >= 0 && VM >= 0 && D >= 1 && S >= 0 && ldS >= Q && ldM >= VM);
-    PCREG_ARG(S <= 65535);
-    if (par->metric != PCREG_METRIC_SAD) { set_error("pcreg_get_matches_segmented: Metric must be SAD (call pcreg_get_matches per segment for SSD)"); return PCREG_E_ARG; }
-    GUARD();
-    if (S == 0) return PCREG_OK;
-    PCREG_ARG(seg_off[0] == 0);
-    int n_max = 0;
-    for (int z = 0; z < S; ++z) { const int n = seg_off[z + 1] - seg_off[z]; PCREG_ARG(n >= 0); if (n > n_max) n_max = n; }
-    const int tot = seg_off[S];
-    PCREG_ARG(tot == 0 || seg_rows);
-    for (int k = 0; k < tot; ++k) PCREG_ARG(seg_rows[k] >= 0 && seg_rows[k] < VM);
-    if (Q == 0 || VM == 0 || tot == 0) { for (int z = 0; z < S; ++z) n_pairs[z] = 0; return PCREG_OK; }
-    const size_t q = (size_t)Q, vm = (size_t)VM;
-    void *fS, *fM, *rS, *rM, *dr, *doff, *dp, *dn, *ws;
-    TRY(scratch().get(0, sizeof(double) * q * D, &fS));
-    TRY(scratch().get(1, sizeof(double) * vm * D, &fM));
-    TRY(scratch().get(2, sizeof(double) * q * D, &rS));
-    TRY(scratch().get(3, sizeof(double) * vm * D, &rM));
-    TRY(scratch().get(4, sizeof(int32_t) * (size_t)tot, &dr));
-    TRY(scratch().get(5, sizeof(int32_t) * ((size_t)S + 1), &doff));
-    TRY(scratch().get(6, sizeof(uint32_t) * (size_t)S * q * 2, &dp));
-    TRY(scratch().get(7, sizeof(int32_t) * (size_t)S, &dn));
-    const size_t wsb = get_matches_segmented_workspace_bytes(Q, VM, D, S, tot, n_max);
-    TRY(scratch().get(8, wsb, &ws));
-    TRY(upload_cols(descSurface, Q, ldS, D, (double*)fS, g_stream));
-    TRY(upload_cols(descModel, VM, ldM, D, (double*)fM, g_stream));
-    TRY(launch_transpose_rows((const double*)fS, Q, Q, D, (double*)rS, g_stream));          // MATLAB's n x D -> dense rows
-    TRY(launch_transpose_rows((const double*)fM, VM, VM, D, (double*)rM, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dr, seg_rows, sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g_stream));
-    PCREG_HIP(hipMemcpyAsync(doff, seg_off, sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream));
-    TRY(launch_get_matches_segmented((const double*)rS, Q, (const double*)rM, VM, D, (const int32_t*)dr, (const int32_t*)doff, S, tot, n_max, *par,
-                                     (uint32_t*)dp, nullptr, (int32_t*)dn, ws, wsb, g_stream));
-    PairFetch pf;
-    TRY(pairs_fetch_begin((const int32_t*)dn, S, pf));
-    TRY(pairs_fetch_enqueue(pf, (const uint32_t*)dp, q, S, 20, pairs_all));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    pairs_fetch_finish(pf, q, S, pairs_all, n_pairs);
-    return PCREG_OK;
 }
 
 // the set's rows as the segmented matcher wants them (dense row-major), transposed once per set (caller holds the library lock)
@@ -813,21 +720,89 @@ static int desc_set_rows(const pcreg_desc_set* cs, const double** out) {
     *out = s->rows;
     return PCREG_OK;
 }
-// the set as the segmented matcher's prepared model for these options (caller holds the library lock)
-static int desc_set_prepared(const pcreg_desc_set* cs, const pcreg_match_opts& o, SegPreparedModel* out) {
-    pcreg_desc_set* s = const_cast<pcreg_desc_set*>(cs);
-    const double* rows;
-    TRY(desc_set_rows(cs, &rows));
-    const bool have = s->prep && s->prep_cm == o.change_metric && (!o.change_metric || s->prep_factor == o.metric_factor);
+static int prepared_rows(PreparedRows& c, const double* rows, int n, int D, const pcreg_match_opts& o, SegPreparedModel* out) {
+    const size_t r_off = (size_t)(n > 0 ? n : 1) * D;
+    const bool have = c.P && c.cm == o.change_metric && (!o.change_metric || c.factor == o.metric_factor);
     if (!have) {
-        if (!s->prep) PCREG_HIP(hipMalloc((void**)&s->prep, segmented_prepared_model_bytes(s->n, s->D)));
-        s->prep_cm = -1;                                         // not valid until the launch below has been enqueued
-        TRY(launch_segmented_prepare_model(rows, s->n, s->D, o, s->prep, s->prep + (size_t)(s->n > 0 ? s->n : 1) * s->D, g_stream));
-        s->prep_cm = o.change_metric; s->prep_factor = o.metric_factor;
+        if (!c.P) PCREG_HIP(hipMalloc((void**)&c.P, segmented_prepared_model_bytes(n, D)));
+        c.cm = -1;                                               // not valid until the launch below has been enqueued
+        TRY(launch_segmented_prepare_model(rows, n, D, o, c.P, c.P + r_off, g_stream));
+        c.cm = o.change_metric; c.factor = o.metric_factor;
     }
-    *out = SegPreparedModel{s->prep, s->prep + (size_t)(s->n > 0 ? s->n : 1) * s->D, s->n, s->D, s->prep_cm, s->prep_factor};
+    *out = SegPreparedModel{c.P, c.P + r_off, n, D, c.cm, c.factor};
     return PCREG_OK;
 }
+// the set as the segmented matcher's prepared model for these options
+static int desc_set_prepared(const pcreg_desc_set* cs, const pcreg_match_opts& o, SegPreparedModel* out) {
+    const double* rows;
+    TRY(desc_set_rows(cs, &rows));
+    return prepared_rows(const_cast<pcreg_desc_set*>(cs)->prep, rows, cs->n, cs->D, o, out);
+}
+
+// The segment list of a segmented call: offsets from 0, no negative length, every row inside the model.  *tot = 0 on return:
+// nothing to match, n_pairs is all zero already.
+static int check_segments(const int32_t* seg_rows, const int32_t* seg_off, int S, int Q, int VM, int32_t* n_pairs, int* n_max, int* tot) {
+    PCREG_ARG(seg_off[0] == 0);
+    *n_max = 0;
+    for (int z = 0; z < S; ++z) { const int n = seg_off[z + 1] - seg_off[z]; PCREG_ARG(n >= 0); if (n > *n_max) *n_max = n; }
+    *tot = seg_off[S];
+    PCREG_ARG(*tot == 0 || seg_rows);
+    for (int k = 0; k < *tot; ++k) PCREG_ARG(seg_rows[k] >= 0 && seg_rows[k] < VM);
+    if (Q == 0 || VM == 0 || *tot == 0) { for (int z = 0; z < S; ++z) n_pairs[z] = 0; *tot = 0; }
+    return PCREG_OK;
+}
+// the segmented matcher on dense rows rS [Q][D], rM [VM][D] (on the model's prepared rows where the set keeps them) and its
+// pair lists back on the host
+static int segmented_run(Stage& st, const double* rS, int Q, const double* rM, int VM, int D, const int32_t* seg_rows, const int32_t* seg_off,
+                         int S, int tot, int n_max, const pcreg_match_opts* par, const pcreg_desc_set* model_set, uint32_t* pairs_all,
+                         int32_t* n_pairs) {
+    const size_t q = (size_t)Q;
+    int32_t *dr, *doff, *dn; uint32_t* dp; char* ws;
+    TRY(st.take((size_t)tot, &dr));
+    TRY(st.take((size_t)S + 1, &doff));
+    TRY(st.take((size_t)S * q * 2, &dp));
+    TRY(st.take((size_t)S, &dn));
+    const size_t wsb = get_matches_segmented_workspace_bytes(Q, VM, D, S, tot, n_max);
+    TRY(st.take(wsb, &ws));
+    PCREG_HIP(hipMemcpyAsync(dr, seg_rows, sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g_stream));
+    PCREG_HIP(hipMemcpyAsync(doff, seg_off, sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream));
+    SegPreparedModel prep;
+    if (model_set) TRY(desc_set_prepared(model_set, *par, &prep));
+    TRY(launch_get_matches_segmented(rS, Q, rM, VM, D, dr, doff, S, tot, n_max, *par, dp, nullptr, dn, ws, wsb, g_stream, model_set ? &prep : nullptr));
+    PairFetch pf;
+    TRY(pairs_fetch_begin(dn, S, pf));
+    TRY(pairs_fetch_enqueue(st, pf, dp, q, S, pairs_all));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    pairs_fetch_finish(pf, q, S, pairs_all, n_pairs);
+    return PCREG_OK;
+}
+
+// getMatches for S row subsets of one model set, host tier (the parfor of completeExperimentFast.m:131-149 as ONE call)
+int pcreg_get_matches_segmented(const double* descSurface, int Q, int ldS, const double* descModel, int VM, int ldM, int D,
+                                const int32_t* seg_rows, const int32_t* seg_off, int S, const pcreg_match_opts* par,
+                                uint32_t* pairs_all, int32_t* n_pairs) {
+    PCREG_ARG(descSurface && descModel && seg_off && par && pairs_all && n_pairs && Q >= 0 && VM >= 0 && D >= 1 && S >= 0 && ldS >= Q && ldM >= VM);
+    PCREG_ARG(S <= 65535);
+    if (par->metric != PCREG_METRIC_SAD) { set_error("pcreg_get_matches_segmented: Metric must be SAD (call pcreg_get_matches per segment for SSD)"); return PCREG_E_ARG; }
+    GUARD();
+    if (S == 0) return PCREG_OK;
+    int n_max, tot;
+    TRY(check_segments(seg_rows, seg_off, S, Q, VM, n_pairs, &n_max, &tot));
+    if (tot == 0) return PCREG_OK;
+    const size_t q = (size_t)Q, vm = (size_t)VM;
+    Stage st{scratch()};
+    double *fS, *fM, *rS, *rM;
+    TRY(st.take(q * D, &fS));
+    TRY(st.take(vm * D, &fM));
+    TRY(st.take(q * D, &rS));
+    TRY(st.take(vm * D, &rM));
+    TRY(upload_cols(descSurface, Q, ldS, D, fS, g_stream));
+    TRY(upload_cols(descModel, VM, ldM, D, fM, g_stream));
+    TRY(launch_transpose_rows(fS, Q, Q, D, rS, g_stream));          // MATLAB's n x D -> dense rows
+    TRY(launch_transpose_rows(fM, VM, VM, D, rM, g_stream));
+    return segmented_run(st, rS, Q, rM, VM, D, seg_rows, seg_off, S, tot, n_max, par, nullptr, pairs_all, n_pairs);
+}
+
 int pcreg_get_matches_segmented_on_sets(const pcreg_desc_set* surface, const pcreg_desc_set* model, const int32_t* seg_rows,
                                         const int32_t* seg_off, int S, const pcreg_match_opts* par, uint32_t* pairs_all, int32_t* n_pairs) {
     PCREG_ARG(surface && model && seg_off && par && pairs_all && n_pairs && S >= 0 && surface->D == model->D);
@@ -836,36 +811,16 @@ int pcreg_get_matches_segmented_on_sets(const pcreg_desc_set* surface, const pcr
     GUARD();
     if (S == 0) return PCREG_OK;
     const int Q = surface->n, VM = model->n, D = surface->D;
-    PCREG_ARG(seg_off[0] == 0);
-    int n_max = 0;
-    for (int z = 0; z < S; ++z) { const int n = seg_off[z + 1] - seg_off[z]; PCREG_ARG(n >= 0); if (n > n_max) n_max = n; }
-    const int tot = seg_off[S];
-    PCREG_ARG(tot == 0 || seg_rows);
-    for (int k = 0; k < tot; ++k) PCREG_ARG(seg_rows[k] >= 0 && seg_rows[k] < VM);
-    if (Q == 0 || VM == 0 || tot == 0) { for (int z = 0; z < S; ++z) n_pairs[z] = 0; return PCREG_OK; }
+    int n_max, tot;
+    TRY(check_segments(seg_rows, seg_off, S, Q, VM, n_pairs, &n_max, &tot));
+    if (tot == 0) return PCREG_OK;
     const double *rS, *rM;
     TRY(desc_set_rows(surface, &rS));
     TRY(desc_set_rows(model, &rM));
-    const size_t q = (size_t)Q;
-    void *dr, *doff, *dp, *dn, *ws;
-    TRY(scratch().get(4, sizeof(int32_t) * (size_t)tot, &dr));
-    TRY(scratch().get(5, sizeof(int32_t) * ((size_t)S + 1), &doff));
-    TRY(scratch().get(6, sizeof(uint32_t) * (size_t)S * q * 2, &dp));
-    TRY(scratch().get(7, sizeof(int32_t) * (size_t)S, &dn));
-    const size_t wsb = get_matches_segmented_workspace_bytes(Q, VM, D, S, tot, n_max);
-    TRY(scratch().get(8, wsb, &ws));
-    PCREG_HIP(hipMemcpyAsync(dr, seg_rows, sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g_stream));
-    PCREG_HIP(hipMemcpyAsync(doff, seg_off, sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream));
-    SegPreparedModel prep;
-    TRY(desc_set_prepared(model, *par, &prep));
-    TRY(launch_get_matches_segmented(rS, Q, rM, VM, D, (const int32_t*)dr, (const int32_t*)doff, S, tot, n_max, *par,
-                                     (uint32_t*)dp, nullptr, (int32_t*)dn, ws, wsb, g_stream, &prep));
-    PairFetch pf;
-    TRY(pairs_fetch_begin((const int32_t*)dn, S, pf));
-    TRY(pairs_fetch_enqueue(pf, (const uint32_t*)dp, q, S, 20, pairs_all));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    pairs_fetch_finish(pf, q, S, pairs_all, n_pairs);
-    return PCREG_OK;
+    Stage st{scratch()};
+    double* none;                                     // the four matrices pcreg_get_matches_segmented stages live in the sets: their slots
+    for (int k = 0; k < 4; ++k) TRY(st.take(0, &none));      // are taken empty, so that the run's pairs and workspace meet the same slots
+    return segmented_run(st, rS, Q, rM, VM, D, seg_rows, seg_off, S, tot, n_max, par, model, pairs_all, n_pairs);
 }
 
 // n x 3 column-major host doubles -> [n][3] on the device (what the sphere kernels and the gather read)
@@ -879,19 +834,122 @@ int pcreg_sphere_counts(const double* featModel, int VM, int ldM, const double* 
     GUARD();
     if (S == 0) return PCREG_OK;
     if (VM == 0) { for (int i = 0; i < S; ++i) counts[i] = 0; return PCREG_OK; }
-    void *tmp, *fm, *tc, *cen, *cnt;
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)VM, &tmp));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)VM, &fm));
-    TRY(scratch().get(2, sizeof(double) * 3 * (size_t)S, &tc));
-    TRY(scratch().get(3, sizeof(double) * 3 * (size_t)S, &cen));
-    TRY(scratch().get(4, sizeof(int32_t) * (size_t)S, &cnt));
-    TRY(upload_points_aos(featModel, VM, ldM, (double*)tmp, (double*)fm, g_stream));
-    TRY(upload_points_aos(centres, S, ldC, (double*)tc, (double*)cen, g_stream));
-    TRY(launch_sphere_counts((const double*)fm, VM, (const double*)cen, S, R, (int32_t*)cnt, g_stream));
+    Stage st{scratch()};
+    double *tmp, *fm, *tc, *cen; int32_t* cnt;
+    TRY(st.take(3 * (size_t)VM, &tmp));
+    TRY(st.take(3 * (size_t)VM, &fm));
+    TRY(st.take(3 * (size_t)S, &tc));
+    TRY(st.take(3 * (size_t)S, &cen));
+    TRY(st.take((size_t)S, &cnt));
+    TRY(upload_points_aos(featModel, VM, ldM, tmp, fm, g_stream));
+    TRY(upload_points_aos(centres, S, ldC, tc, cen, g_stream));
+    TRY(launch_sphere_counts(fm, VM, cen, S, R, cnt, g_stream));
     PCREG_HIP(hipMemcpyAsync(counts, cnt, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     return PCREG_OK;
 }
+
+// ---- the sphere sweep (completeExperimentFast.m:46-225) at the host tier ------------------------------------------------------
+// no host array is freed under a pending copy: whatever way a call leaves, the stream is drained first (unless it just was)
+struct DrainAtExit { bool armed = true; ~DrainAtExit() { if (armed) (void)hipStreamSynchronize(g_stream); } };
+
+// a sweep's spheres: the caller's per-sphere counts and the segment tables made of them, off [S + 1] (rows in front of sphere i), roff
+// the same as int64
+struct SphereSegs { const int32_t* num_desc; int S; std::vector<int32_t> off; std::vector<int64_t> roff; int n_max, tot; };
+static int sphere_segs(const int32_t* num_desc, int S, int VM, SphereSegs* g) {
+    g->num_desc = num_desc; g->S = S; g->n_max = 0;
+    g->off.assign((size_t)S + 1, 0); g->roff.assign((size_t)S, 0);
+    for (int i = 0; i < S; ++i) {
+        PCREG_ARG(num_desc[i] >= 0 && num_desc[i] <= VM && (long long)g->off[i] + num_desc[i] < 2147483647LL);
+        g->off[i + 1] = g->off[i] + num_desc[i]; g->roff[i] = g->off[i]; g->n_max = std::max(g->n_max, num_desc[i]);
+    }
+    g->tot = g->off[S];
+    return PCREG_OK;
+}
+// where a sphere head leaves the model side: the caller's segment tables and gathered keypoints, and the row lists the head stages
+struct SphereDst { int32_t* off; int64_t* roff; double* feat_all; int32_t* rows; };
+// The model side of a sweep (:52-125) behind the upload of the model keypoints fm [VM][3]: the centres go up, the segment tables to
+// d->off / d->roff, every sphere's row list to d->rows and its keypoints to d->feat_all.  The counts and the lists come back and the
+// counts are held against num_desc BEFORE anything reads the lists: the select clips at a segment's capacity, so behind a count that
+// is too large the tail of the segment is unwritten.  The stream is synchronised on return (g's tables may go).  `who`: the public entry.
+static int sphere_head(Stage& st, const char* who, const SphereSegs& g, const double* fm, int VM, const double* centres, int ldC, double R_desc,
+                       SphereDst* d, int32_t* model_rows) {
+    const int S = g.S;
+    double *tc, *cen; int32_t* nsel;
+    TRY(st.take(3 * (size_t)S, &tc));
+    TRY(st.take(3 * (size_t)S, &cen));
+    TRY(st.take((size_t)S, &nsel));
+    TRY(st.take((size_t)g.tot, &d->rows));
+    std::vector<int32_t> h_nsel((size_t)S);
+    DrainAtExit drain;
+    TRY(upload_points_aos(centres, S, ldC, tc, cen, g_stream));
+    PCREG_HIP(hipMemcpyAsync(d->off, g.off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream));
+    PCREG_HIP(hipMemcpyAsync(d->roff, g.roff.data(), sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_sphere_select_batched(fm, VM, cen, S, R_desc, d->off, d->rows, d->feat_all, nsel, g_stream));
+    PCREG_HIP(hipMemcpyAsync(h_nsel.data(), nsel, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(model_rows, d->rows, sizeof(int32_t) * (size_t)g.tot, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    drain.armed = false;
+    for (int i = 0; i < S; ++i)
+        if (h_nsel[i] != g.num_desc[i]) { set_error("%s: num_desc[%d] = %d, but the sphere holds %d keypoints (pass pcreg_sphere_counts' values)", who, i, g.num_desc[i], h_nsel[i]); return PCREG_E_ARG; }
+    return PCREG_OK;
+}
+
+// The surface side of a sweep.  Its buffers are staged first by both entries, so that each meets the same slot with and without
+// a sphere model; the pairs, the counts and the matcher's workspace come behind six others, in the slots segmented_run gives
+// them in pcreg_get_matches_segmented{,_on_sets}.  tmp: column-major temporary of tmp_rows keypoints.
+struct SweepStage {
+    double *tmp, *fs; uint32_t* dp; int32_t* dn; char* ws; size_t wsb;
+    int32_t* tidx; double* p12; pcreg_dev_ransac_result* res; int32_t* inl; char* rws; size_t rwsb;      // tidx: trial_idx [S] | offsets [S + 1] | n_trials
+};
+static int sweep_stage(Stage& st, int S, int VS, int tmp_rows, size_t wsb, const pcreg_ransac_opts* coef, SweepStage* b) {
+    const size_t vs = (size_t)VS, ld = (size_t)S * vs;
+    b->wsb = wsb; b->rwsb = ransac_workspace_bytes(coef->iterNum, S, VS);
+    TRY(st.take(3 * (size_t)tmp_rows, &b->tmp));
+    TRY(st.take(3 * vs, &b->fs));
+    TRY(st.take(3 * (size_t)S + 2, &b->tidx));
+    TRY(st.take((size_t)S, &b->res));
+    TRY(st.take(ld, &b->inl));
+    TRY(st.take(b->rwsb, &b->rws));
+    TRY(st.take((size_t)S * vs * 2, &b->dp));
+    TRY(st.take((size_t)S, &b->dn));
+    TRY(st.take(b->wsb, &b->ws));
+    return st.take(6 * ld, &b->p12);
+}
+// :166-216 behind the matcher (pairs in b.dp, counts in b.dn): the putative threshold, the trial spheres' correspondences, one
+// batched ransac (registration t: seed + t), the pair lists and the trials' results back on the host
+static int sweep_tail(Stage& st, const SweepStage& b, int S, int VS, const double* feat_all, const int64_t* roff, int putative_thresh,
+                      const pcreg_ransac_opts* coef, uint32_t* pairs_all, int32_t* n_pairs, int32_t* trial, int* n_trials, double* T,
+                      int32_t* num_success, int32_t* max_inliers, int32_t* failed) {
+    const size_t vs = (size_t)VS, ld = (size_t)S * vs;
+    int32_t *toff = b.tidx + S, *nt = b.tidx + 2 * (size_t)S + 1;
+    TRY(launch_sweep_plan(b.dn, S, putative_thresh, b.tidx, toff, nt, g_stream));
+    double *p1 = b.p12, *p2 = b.p12 + 3 * ld;
+    PCREG_HIP(hipMemsetAsync(b.p12, 0, sizeof(double) * 6 * ld, g_stream));
+    TRY(launch_sweep_gather(b.dp, VS, b.dn, b.tidx, toff, nt, S, b.fs, feat_all, roff, p1, p2, (int)ld, g_stream));
+    PairFetch pf;
+    TRY(pairs_fetch_begin(b.dn, S, pf));          // the counts leave in front of the RANSAC launch; the lists are packed while it runs
+    PCREG_HIP(hipMemsetAsync(b.res, 0, sizeof(pcreg_dev_ransac_result) * (size_t)S, g_stream));
+    TRY(launch_ransac(p1, p2, (int)ld, toff, nullptr, VS, S, *coef, nullptr, b.res, b.inl, nullptr, nullptr, b.rws, b.rwsb, g_stream));
+    std::vector<int32_t> h_tr((size_t)S);
+    std::vector<pcreg_dev_ransac_result> h_res((size_t)S);
+    int32_t h_nt = 0;
+    TRY(pairs_fetch_enqueue(st, pf, b.dp, vs, S, pairs_all));
+    PCREG_HIP(hipMemcpyAsync(h_tr.data(), b.tidx, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(&h_nt, nt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(h_res.data(), b.res, sizeof(pcreg_dev_ransac_result) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    pairs_fetch_finish(pf, vs, S, pairs_all, n_pairs);
+    *n_trials = h_nt;
+    for (int t = 0; t < h_nt; ++t) {
+        trial[t] = h_tr[t];
+        const pcreg_dev_ransac_result& r = h_res[t];
+        for (int k = 0; k < 16; ++k) T[(size_t)t * 16 + k] = r.failed ? 0.0 : r.T[k];
+        num_success[t] = r.num_success; max_inliers[t] = r.max_inliers; failed[t] = r.failed;
+    }
+    return PCREG_OK;
+}
+
 int pcreg_sphere_sweep(const pcreg_desc_set* surface, const pcreg_desc_set* model, const double* featSurface, int ldS, const double* featModel, int ldM,
                        const double* centres, int S, int ldC, const int32_t* num_desc, double R_desc, const pcreg_match_opts* par, int putative_thresh,
                        const pcreg_ransac_opts* coef, int32_t* model_rows, uint32_t* pairs_all, int32_t* n_pairs, int32_t* trial, int* n_trials,
@@ -904,86 +962,32 @@ int pcreg_sphere_sweep(const pcreg_desc_set* surface, const pcreg_desc_set* mode
     *n_trials = 0;
     if (S == 0) return PCREG_OK;
     const int VS = surface->n, VM = model->n, D = surface->D;
-    std::vector<int32_t> off((size_t)S + 1, 0); std::vector<int64_t> roff((size_t)S, 0);
-    int n_max = 0;
-    for (int i = 0; i < S; ++i) {
-        PCREG_ARG(num_desc[i] >= 0 && num_desc[i] <= VM && (long long)off[i] + num_desc[i] < 2147483647LL);
-        off[i + 1] = off[i] + num_desc[i]; roff[i] = off[i]; n_max = std::max(n_max, num_desc[i]);
-    }
-    const int tot = off[S];
+    SphereSegs g;
+    TRY(sphere_segs(num_desc, S, VM, &g));
+    const int tot = g.tot;
     if (VS == 0 || VM == 0 || tot == 0) { for (int i = 0; i < S; ++i) n_pairs[i] = 0; return PCREG_OK; }
-    const size_t vs = (size_t)VS, ld = (size_t)S * vs;
+    const size_t ld = (size_t)S * (size_t)VS;
     PCREG_ARG(ld <= 0x7FFFFFFFull);                              // the packed correspondences are indexed with int
-    void *tmp, *fm, *fs, *tc, *cen, *doff, *droff, *rows, *fall, *nsel, *dp, *dn, *ws, *tidx, *toff, *nt, *p12, *res, *inl, *rws;
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)std::max(VM, VS), &tmp));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)VM, &fm));
-    TRY(scratch().get(2, sizeof(double) * 3 * vs, &fs));
-    TRY(scratch().get(3, sizeof(double) * 3 * (size_t)S, &tc));
-    TRY(scratch().get(9, sizeof(double) * 3 * (size_t)S, &cen));
-    TRY(scratch().get(4, sizeof(int32_t) * (size_t)tot, &rows));
-    TRY(scratch().get(5, sizeof(int32_t) * ((size_t)S + 1), &doff));
-    TRY(scratch().get(6, sizeof(uint32_t) * (size_t)S * vs * 2, &dp));
-    TRY(scratch().get(7, sizeof(int32_t) * (size_t)S, &dn));
-    const size_t wsb = get_matches_segmented_workspace_bytes(VS, VM, D, S, tot, n_max);
-    TRY(scratch().get(8, wsb, &ws));
-    TRY(scratch().get(10, sizeof(int64_t) * (size_t)S, &droff));
-    TRY(scratch().get(11, sizeof(double) * 3 * (size_t)tot, &fall));
-    TRY(scratch().get(12, sizeof(int32_t) * (size_t)S, &nsel));
-    TRY(scratch().get(13, sizeof(int32_t) * (3 * (size_t)S + 2), &tidx));          // trial_idx [S] | offsets [S + 1] | n_trials
-    toff = (int32_t*)tidx + S; nt = (int32_t*)tidx + 2 * (size_t)S + 1;
-    TRY(scratch().get(14, sizeof(double) * 6 * ld, &p12));
-    TRY(scratch().get(15, sizeof(pcreg_dev_ransac_result) * (size_t)S, &res));
-    TRY(scratch().get(16, sizeof(int32_t) * ld, &inl));
-    const size_t rwsb = ransac_workspace_bytes(coef->iterNum, S, VS);
-    TRY(scratch().get(17, rwsb, &rws));
+    Stage st{scratch()};
+    SweepStage b;
+    TRY(sweep_stage(st, S, VS, std::max(VM, VS), get_matches_segmented_workspace_bytes(VS, VM, D, S, tot, g.n_max), coef, &b));
+    double* fm; SphereDst d;
+    TRY(st.take(3 * (size_t)VM, &fm));
+    TRY(st.take((size_t)S + 1, &d.off));
+    TRY(st.take((size_t)S, &d.roff));
+    TRY(st.take(3 * (size_t)tot, &d.feat_all));
     const double *rS, *rM;
     TRY(desc_set_rows(surface, &rS));
     TRY(desc_set_rows(model, &rM));
     // :52-125: the keypoints, the spheres' row lists and their keypoints back to back
-    TRY(upload_points_aos(featModel, VM, ldM, (double*)tmp, (double*)fm, g_stream));
-    TRY(upload_points_aos(featSurface, VS, ldS, (double*)tmp, (double*)fs, g_stream));
-    TRY(upload_points_aos(centres, S, ldC, (double*)tc, (double*)cen, g_stream));
-    PCREG_HIP(hipMemcpyAsync(doff, off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream));
-    PCREG_HIP(hipMemcpyAsync(droff, roff.data(), sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));                   // off / roff are locals: the copies must have read them before anything can fail and return
-    TRY(launch_sphere_select_batched((const double*)fm, VM, (const double*)cen, S, R_desc, (const int32_t*)doff, (int32_t*)rows, (double*)fall, (int32_t*)nsel, g_stream));
+    TRY(upload_points_aos(featModel, VM, ldM, b.tmp, fm, g_stream));
+    TRY(upload_points_aos(featSurface, VS, ldS, b.tmp, b.fs, g_stream));
+    TRY(sphere_head(st, "pcreg_sphere_sweep", g, fm, VM, centres, ldC, R_desc, &d, model_rows));
     // :131-149: getMatches of the surface against every sphere's rows
     SegPreparedModel prep;
     TRY(desc_set_prepared(model, *par, &prep));
-    TRY(launch_get_matches_segmented(rS, VS, rM, VM, D, (const int32_t*)rows, (const int32_t*)doff, S, tot, n_max, *par, (uint32_t*)dp, nullptr, (int32_t*)dn,
-                                     ws, wsb, g_stream, &prep));
-    // :166-216: the putative threshold, the trial spheres' correspondences, one batched ransac (registration t: seed + t)
-    TRY(launch_sweep_plan((const int32_t*)dn, S, putative_thresh, (int32_t*)tidx, (int32_t*)toff, (int32_t*)nt, g_stream));
-    double *p1 = (double*)p12, *p2 = (double*)p12 + 3 * ld;
-    PCREG_HIP(hipMemsetAsync(p12, 0, sizeof(double) * 6 * ld, g_stream));
-    TRY(launch_sweep_gather((const uint32_t*)dp, VS, (const int32_t*)dn, (const int32_t*)tidx, (const int32_t*)toff, (const int32_t*)nt, S, (const double*)fs,
-                            (const double*)fall, (const int64_t*)droff, p1, p2, (int)ld, g_stream));
-    PairFetch pf;
-    TRY(pairs_fetch_begin((const int32_t*)dn, S, pf));          // the counts leave in front of the RANSAC launch; the lists are packed while it runs
-    PCREG_HIP(hipMemsetAsync(res, 0, sizeof(pcreg_dev_ransac_result) * (size_t)S, g_stream));
-    TRY(launch_ransac(p1, p2, (int)ld, (const int32_t*)toff, nullptr, VS, S, *coef, nullptr, (pcreg_dev_ransac_result*)res, (int32_t*)inl, nullptr, nullptr,
-                      rws, rwsb, g_stream));
-    std::vector<int32_t> h_nsel((size_t)S), h_tr((size_t)S);
-    std::vector<pcreg_dev_ransac_result> h_res((size_t)S);
-    int32_t h_nt = 0;
-    TRY(pairs_fetch_enqueue(pf, (const uint32_t*)dp, vs, S, 20, pairs_all));
-    PCREG_HIP(hipMemcpyAsync(h_nsel.data(), nsel, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(model_rows, rows, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(h_tr.data(), tidx, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(&h_nt, nt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(h_res.data(), res, sizeof(pcreg_dev_ransac_result) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    pairs_fetch_finish(pf, vs, S, pairs_all, n_pairs);
-    for (int i = 0; i < S; ++i)
-        if (h_nsel[i] != num_desc[i]) { set_error("pcreg_sphere_sweep: num_desc[%d] = %d, but the sphere holds %d keypoints (pass pcreg_sphere_counts' values)", i, num_desc[i], h_nsel[i]); return PCREG_E_ARG; }
-    *n_trials = h_nt;
-    for (int t = 0; t < h_nt; ++t) {
-        trial[t] = h_tr[t];
-        const pcreg_dev_ransac_result& r = h_res[t];
-        for (int k = 0; k < 16; ++k) T[(size_t)t * 16 + k] = r.failed ? 0.0 : r.T[k];
-        num_success[t] = r.num_success; max_inliers[t] = r.max_inliers; failed[t] = r.failed;
-    }
-    return PCREG_OK;
+    TRY(launch_get_matches_segmented(rS, VS, rM, VM, D, d.rows, d.off, S, tot, g.n_max, *par, b.dp, nullptr, b.dn, b.ws, b.wsb, g_stream, &prep));
+    return sweep_tail(st, b, S, VS, d.feat_all, d.roff, putative_thresh, coef, pairs_all, n_pairs, trial, n_trials, T, num_success, max_inliers, failed);
 }
 
 // ---- the sphere sweep's model side as a handle: one model, many surfaces ----------------------------------------------------
@@ -991,12 +995,12 @@ int pcreg_sphere_sweep(const pcreg_desc_set* surface, const pcreg_desc_set* mode
 // set restricted to the union of those rows (the lists renumbered into it) and, per set of getMatches options, its powered rows.
 struct pcreg_sphere_model {
     int S, VMu, D, tot, n_max;
-    int32_t *seg_off, *rows_u; int64_t* roff; double *feat_all, *desc_u, *prep;
-    int prep_cm; double prep_factor;
+    int32_t *seg_off, *rows_u; int64_t* roff; double *feat_all, *desc_u;
+    PreparedRows prep;
 };
 static void sphere_model_free(pcreg_sphere_model* m) {
     if (!m) return;
-    void* p[] = {m->seg_off, m->rows_u, m->roff, m->feat_all, m->desc_u, m->prep};
+    void* p[] = {m->seg_off, m->rows_u, m->roff, m->feat_all, m->desc_u, m->prep.P};
     for (void* q : p) if (q) (void)hipFree(q);
     delete m;
 }
@@ -1006,39 +1010,23 @@ int pcreg_sphere_model_create(const pcreg_desc_set* model, const double* featMod
     GUARD();
     *out = nullptr;
     const int VM = model->n, D = model->D;
-    std::vector<int32_t> off((size_t)S + 1, 0); std::vector<int64_t> roff((size_t)S, 0);
-    int n_max = 0;
-    for (int i = 0; i < S; ++i) {
-        PCREG_ARG(num_desc[i] >= 0 && num_desc[i] <= VM && (long long)off[i] + num_desc[i] < 2147483647LL);
-        off[i + 1] = off[i] + num_desc[i]; roff[i] = off[i]; n_max = std::max(n_max, num_desc[i]);
-    }
-    const int tot = off[S];
-    pcreg_sphere_model* m = new pcreg_sphere_model{S, 0, D, tot, n_max, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1, 0.0};
+    SphereSegs g;
+    TRY(sphere_segs(num_desc, S, VM, &g));
+    const int tot = g.tot;
+    pcreg_sphere_model* m = new pcreg_sphere_model{S, 0, D, tot, g.n_max, nullptr, nullptr, nullptr, nullptr, nullptr, {}};
     auto fail = [&](int rc) { sphere_model_free(m); return rc; };
     if (S == 0 || tot == 0 || VM == 0) { *out = m; return PCREG_OK; }
-    void *tmp, *fm, *tc, *cen, *nsel, *rows, *nd;
     int rc = PCREG_OK;
-    if ((rc = scratch().get(0, sizeof(double) * 3 * (size_t)VM, &tmp)) || (rc = scratch().get(1, sizeof(double) * 3 * (size_t)VM, &fm)) ||
-        (rc = scratch().get(3, sizeof(double) * 3 * (size_t)S, &tc)) || (rc = scratch().get(9, sizeof(double) * 3 * (size_t)S, &cen)) ||
-        (rc = scratch().get(12, sizeof(int32_t) * (size_t)S, &nsel)) || (rc = scratch().get(4, sizeof(int32_t) * (size_t)tot, &rows)) ||
-        (rc = scratch().get(5, 256, &nd)))
-        return fail(rc);
     if (hipMalloc((void**)&m->seg_off, sizeof(int32_t) * ((size_t)S + 1)) != hipSuccess || hipMalloc((void**)&m->roff, sizeof(int64_t) * (size_t)S) != hipSuccess ||
         hipMalloc((void**)&m->rows_u, sizeof(int32_t) * (size_t)tot) != hipSuccess || hipMalloc((void**)&m->feat_all, sizeof(double) * 3 * (size_t)tot) != hipSuccess) {
         set_error("pcreg_sphere_model_create: out of device memory"); return fail(PCREG_E_HIP);
     }
-    if ((rc = upload_points_aos(featModel, VM, ldM, (double*)tmp, (double*)fm, g_stream)) || (rc = upload_points_aos(centres, S, ldC, (double*)tc, (double*)cen, g_stream)))
+    Stage st{scratch()};
+    double *tmp, *fm; int32_t *duni, *nd;
+    SphereDst d{m->seg_off, m->roff, m->feat_all, nullptr};
+    if ((rc = st.take(3 * (size_t)VM, &tmp)) || (rc = st.take(3 * (size_t)VM, &fm)) || (rc = upload_points_aos(featModel, VM, ldM, tmp, fm, g_stream)) ||
+        (rc = sphere_head(st, "pcreg_sphere_model_create", g, fm, VM, centres, ldC, R_desc, &d, model_rows)))
         return fail(rc);
-    if (hipMemcpyAsync(m->seg_off, off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, g_stream) != hipSuccess ||
-        hipMemcpyAsync(m->roff, roff.data(), sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, g_stream) != hipSuccess) { set_error("copy failed"); return fail(PCREG_E_HIP); }
-    if ((rc = launch_sphere_select_batched((const double*)fm, VM, (const double*)cen, S, R_desc, m->seg_off, (int32_t*)rows, m->feat_all, (int32_t*)nsel, g_stream)))
-        return fail(rc);
-    std::vector<int32_t> h_nsel((size_t)S);
-    if (hipMemcpyAsync(h_nsel.data(), nsel, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream) != hipSuccess ||
-        hipMemcpyAsync(model_rows, rows, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, g_stream) != hipSuccess ||
-        hipStreamSynchronize(g_stream) != hipSuccess) { set_error("pcreg_sphere_model_create: read-back failed"); return fail(PCREG_E_HIP); }
-    for (int i = 0; i < S; ++i)
-        if (h_nsel[i] != num_desc[i]) { set_error("pcreg_sphere_model_create: num_desc[%d] = %d, but the sphere holds %d keypoints (pass pcreg_sphere_counts' values)", i, num_desc[i], h_nsel[i]); return fail(PCREG_E_ARG); }
     // the union of the spheres' rows (ascending) and the lists renumbered into it
     std::vector<int32_t> uni(model_rows, model_rows + tot);
     std::sort(uni.begin(), uni.end());
@@ -1048,14 +1036,13 @@ int pcreg_sphere_model_create(const pcreg_desc_set* model, const double* featMod
     m->VMu = (int)uni.size();
     const double* rM;
     if ((rc = desc_set_rows(model, &rM))) return fail(rc);
-    void* duni;
-    if ((rc = scratch().get(6, sizeof(int32_t) * uni.size(), &duni))) return fail(rc);
+    if ((rc = st.take(uni.size(), &duni)) || (rc = st.take(1, &nd))) return fail(rc);
     if (hipMalloc((void**)&m->desc_u, sizeof(double) * uni.size() * (size_t)D) != hipSuccess) { set_error("pcreg_sphere_model_create: out of device memory"); return fail(PCREG_E_HIP); }
     const int32_t nu = m->VMu;
     if (hipMemcpyAsync(duni, uni.data(), sizeof(int32_t) * uni.size(), hipMemcpyHostToDevice, g_stream) != hipSuccess ||
         hipMemcpyAsync(nd, &nu, sizeof(int32_t), hipMemcpyHostToDevice, g_stream) != hipSuccess ||
         hipMemcpyAsync(m->rows_u, ren.data(), sizeof(int32_t) * (size_t)tot, hipMemcpyHostToDevice, g_stream) != hipSuccess) { set_error("copy failed"); return fail(PCREG_E_HIP); }
-    if ((rc = launch_gather_rows_f64(rM, D, (const int32_t*)duni, (const int32_t*)nd, m->VMu, m->desc_u, g_stream))) return fail(rc);
+    if ((rc = launch_gather_rows_f64(rM, D, duni, nd, m->VMu, m->desc_u, g_stream))) return fail(rc);
     if (hipStreamSynchronize(g_stream) != hipSuccess) { set_error("pcreg_sphere_model_create failed"); return fail(PCREG_E_HIP); }          // the host vectors go out of scope
     *out = m;
     return PCREG_OK;
@@ -1078,61 +1065,18 @@ int pcreg_sphere_sweep_on_model(pcreg_sphere_model* m, const pcreg_desc_set* sur
     const int S = m->S, VS = surface->n, D = m->D, tot = m->tot;
     if (S == 0) return PCREG_OK;
     if (VS == 0 || tot == 0 || m->VMu == 0) { for (int i = 0; i < S; ++i) n_pairs[i] = 0; return PCREG_OK; }
-    const size_t vs = (size_t)VS, ld = (size_t)S * vs;
+    const size_t ld = (size_t)S * (size_t)VS;
     PCREG_ARG(ld <= 0x7FFFFFFFull);
-    void *tmp, *fs, *dp, *dn, *ws, *tidx, *toff, *nt, *p12, *res, *inl, *rws;
-    TRY(scratch().get(0, sizeof(double) * 3 * vs, &tmp));
-    TRY(scratch().get(2, sizeof(double) * 3 * vs, &fs));
-    TRY(scratch().get(6, sizeof(uint32_t) * (size_t)S * vs * 2, &dp));
-    TRY(scratch().get(7, sizeof(int32_t) * (size_t)S, &dn));
-    const size_t wsb = get_matches_segmented_workspace_bytes(VS, m->VMu, D, S, tot, m->n_max);
-    TRY(scratch().get(8, wsb, &ws));
-    TRY(scratch().get(13, sizeof(int32_t) * (3 * (size_t)S + 2), &tidx));
-    toff = (int32_t*)tidx + S; nt = (int32_t*)tidx + 2 * (size_t)S + 1;
-    TRY(scratch().get(14, sizeof(double) * 6 * ld, &p12));
-    TRY(scratch().get(15, sizeof(pcreg_dev_ransac_result) * (size_t)S, &res));
-    TRY(scratch().get(16, sizeof(int32_t) * ld, &inl));
-    const size_t rwsb = ransac_workspace_bytes(coef->iterNum, S, VS);
-    TRY(scratch().get(17, rwsb, &rws));
+    Stage st{scratch()};
+    SweepStage b;
+    TRY(sweep_stage(st, S, VS, VS, get_matches_segmented_workspace_bytes(VS, m->VMu, D, S, tot, m->n_max), coef, &b));
     const double* rS;
     TRY(desc_set_rows(surface, &rS));
-    if (!(m->prep && m->prep_cm == par->change_metric && (!par->change_metric || m->prep_factor == par->metric_factor))) {
-        if (!m->prep) PCREG_HIP(hipMalloc((void**)&m->prep, segmented_prepared_model_bytes(m->VMu, D)));
-        m->prep_cm = -1;
-        TRY(launch_segmented_prepare_model(m->desc_u, m->VMu, D, *par, m->prep, m->prep + (size_t)m->VMu * D, g_stream));
-        m->prep_cm = par->change_metric; m->prep_factor = par->metric_factor;
-    }
-    const SegPreparedModel prep{m->prep, m->prep + (size_t)m->VMu * D, m->VMu, D, m->prep_cm, m->prep_factor};
-    TRY(upload_points_aos(featSurface, VS, ldS, (double*)tmp, (double*)fs, g_stream));
-    TRY(launch_get_matches_segmented(rS, VS, m->desc_u, m->VMu, D, m->rows_u, m->seg_off, S, tot, m->n_max, *par, (uint32_t*)dp, nullptr, (int32_t*)dn,
-                                     ws, wsb, g_stream, &prep));
-    TRY(launch_sweep_plan((const int32_t*)dn, S, putative_thresh, (int32_t*)tidx, (int32_t*)toff, (int32_t*)nt, g_stream));
-    double *p1 = (double*)p12, *p2 = (double*)p12 + 3 * ld;
-    PCREG_HIP(hipMemsetAsync(p12, 0, sizeof(double) * 6 * ld, g_stream));
-    TRY(launch_sweep_gather((const uint32_t*)dp, VS, (const int32_t*)dn, (const int32_t*)tidx, (const int32_t*)toff, (const int32_t*)nt, S, (const double*)fs,
-                            m->feat_all, m->roff, p1, p2, (int)ld, g_stream));
-    PairFetch pf;
-    TRY(pairs_fetch_begin((const int32_t*)dn, S, pf));          // the counts leave in front of the RANSAC launch; the lists are packed while it runs
-    PCREG_HIP(hipMemsetAsync(res, 0, sizeof(pcreg_dev_ransac_result) * (size_t)S, g_stream));
-    TRY(launch_ransac(p1, p2, (int)ld, (const int32_t*)toff, nullptr, VS, S, *coef, nullptr, (pcreg_dev_ransac_result*)res, (int32_t*)inl, nullptr, nullptr,
-                      rws, rwsb, g_stream));
-    std::vector<int32_t> h_tr((size_t)S);
-    std::vector<pcreg_dev_ransac_result> h_res((size_t)S);
-    int32_t h_nt = 0;
-    TRY(pairs_fetch_enqueue(pf, (const uint32_t*)dp, vs, S, 20, pairs_all));
-    PCREG_HIP(hipMemcpyAsync(h_tr.data(), tidx, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(&h_nt, nt, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipMemcpyAsync(h_res.data(), res, sizeof(pcreg_dev_ransac_result) * (size_t)S, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    pairs_fetch_finish(pf, vs, S, pairs_all, n_pairs);
-    *n_trials = h_nt;
-    for (int t = 0; t < h_nt; ++t) {
-        trial[t] = h_tr[t];
-        const pcreg_dev_ransac_result& r = h_res[t];
-        for (int k = 0; k < 16; ++k) T[(size_t)t * 16 + k] = r.failed ? 0.0 : r.T[k];
-        num_success[t] = r.num_success; max_inliers[t] = r.max_inliers; failed[t] = r.failed;
-    }
-    return PCREG_OK;
+    SegPreparedModel prep;
+    TRY(prepared_rows(m->prep, m->desc_u, m->VMu, D, *par, &prep));
+    TRY(upload_points_aos(featSurface, VS, ldS, b.tmp, b.fs, g_stream));
+    TRY(launch_get_matches_segmented(rS, VS, m->desc_u, m->VMu, D, m->rows_u, m->seg_off, S, tot, m->n_max, *par, b.dp, nullptr, b.dn, b.ws, b.wsb, g_stream, &prep));
+    return sweep_tail(st, b, S, VS, m->feat_all, m->roff, putative_thresh, coef, pairs_all, n_pairs, trial, n_trials, T, num_success, max_inliers, failed);
 }
 
 int pcreg_align_points_knn_batched(const double* pts, int total, int ld, const int32_t* offsets, int B, int C1, int C2,
@@ -1144,20 +1088,20 @@ int pcreg_align_points_knn_batched(const double* pts, int total, int ld, const i
     for (int b = 0; b < B; ++b) { int nb = offsets[b + 1] - offsets[b]; PCREG_ARG(nb >= 0); if (nb > max_n) max_n = nb; }
     PCREG_ARG(offsets[0] == 0 && offsets[B] == total);
     size_t tot = (size_t)(total > 0 ? total : 1);
-    void *dp, *da, *doff, *dco, *dc, *dst;
-    TRY(scratch().get(0, sizeof(double) * 3 * tot, &dp));
-    TRY(scratch().get(1, sizeof(double) * 3 * tot, &da));
-    TRY(scratch().get(2, sizeof(int32_t) * ((size_t)B + 1), &doff));
-    TRY(scratch().get(3, sizeof(double) * 9 * (size_t)B, &dco));
-    TRY(scratch().get(4, sizeof(double) * 3 * (size_t)B, &dc));
-    TRY(scratch().get(5, sizeof(int32_t) * (size_t)B, &dst));
-    TRY(upload_cols(pts, total, ld, 3, (double*)dp, g_stream));
+    Stage st{scratch()};
+    double *dp, *da, *dco, *dc; int32_t *doff, *dst;
+    TRY(st.take(3 * tot, &dp));
+    TRY(st.take(3 * tot, &da));
+    TRY(st.take((size_t)B + 1, &doff));
+    TRY(st.take(9 * (size_t)B, &dco));
+    TRY(st.take(3 * (size_t)B, &dc));
+    TRY(st.take((size_t)B, &dst));
+    TRY(upload_cols(pts, total, ld, 3, dp, g_stream));
     PCREG_HIP(hipMemcpyAsync(doff, offsets, sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, g_stream));
     PCREG_HIP(hipMemsetAsync(dco, 0, sizeof(double) * 9 * (size_t)B, g_stream));
     PCREG_HIP(hipMemsetAsync(dc, 0, sizeof(double) * 3 * (size_t)B, g_stream));
     PCREG_HIP(hipMemsetAsync(da, 0, sizeof(double) * 3 * tot, g_stream));
-    TRY(launch_align_points_knn((double*)dp, total, (int32_t*)doff, B, max_n, C1, C2, (double*)da, total, (double*)dco,
-                                (double*)dc, (int32_t*)dst, g_stream));
+    TRY(launch_align_points_knn(dp, total, doff, B, max_n, C1, C2, da, total, dco, dc, dst, g_stream));
     if (total > 0) PCREG_HIP(hipMemcpyAsync(aligned, da, sizeof(double) * 3 * (size_t)total, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(coeff, dco, sizeof(double) * 9 * (size_t)B, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(c, dc, sizeof(double) * 3 * (size_t)B, hipMemcpyDeviceToHost, g_stream));
@@ -1197,21 +1141,20 @@ static int descriptors_host(const double* pts, int P, int ld, const double* samp
                             int single_mode, double* feat, double* desc, int* V) {
     *V = 0;
     if (P == 0 || S == 0) return PCREG_OK;
-    void *dp, *dk, *dfeat, *ddesc, *dcnt, *ws;
+    Stage st{scratch()};
+    double *dp, *dk, *dfeat, *ddesc; int32_t* dV; char* ws;
     size_t wsb = descriptors_workspace_bytes(P, S);
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)P, &dp));
-    TRY(scratch().get(1, sizeof(double) * 3 * (size_t)S, &dk));
-    TRY(scratch().get(2, sizeof(double) * 3 * (size_t)S, &dfeat));
-    TRY(scratch().get(3, sizeof(double) * PCREG_DESC_LEN * (size_t)S, &ddesc));
-    TRY(scratch().get(4, 256, &dcnt));
-    TRY(scratch().get(5, wsb, &ws));
-    int32_t* dV = (int32_t*)dcnt; int32_t* dErr = dV + 1;
-    TRY(upload_cols(pts, P, ld, 3, (double*)dp, g_stream));
-    TRY(upload_cols(sample_pts, S, lds, 3, (double*)dk, g_stream));
-    TRY(launch_descriptors((double*)dp, P, P, (double*)dk, S, S, *options, single_mode, (double*)dfeat, (double*)ddesc, nullptr, nullptr, dV, dErr,
-                           ws, wsb, g_stream));
+    TRY(st.take(3 * (size_t)P, &dp));
+    TRY(st.take(3 * (size_t)S, &dk));
+    TRY(st.take(3 * (size_t)S, &dfeat));
+    TRY(st.take(PCREG_DESC_LEN * (size_t)S, &ddesc));
+    TRY(st.take(2, &dV));                                   // V | the over-capacity flag
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(pts, P, ld, 3, dp, g_stream));
+    TRY(upload_cols(sample_pts, S, lds, 3, dk, g_stream));
+    TRY(launch_descriptors(dp, P, P, dk, S, S, *options, single_mode, dfeat, ddesc, nullptr, nullptr, dV, dV + 1, ws, wsb, g_stream));
     int32_t hv[2] = {0, 0};
-    PCREG_HIP(hipMemcpyAsync(hv, dcnt, sizeof hv, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(hv, dV, sizeof hv, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     if (hv[1] != 0) { set_error("a support holds %d points: more than the %d an LDS-resident support may have (lower max_pts)", hv[1], 8191); return PCREG_E_ARG; }
     if (hv[0] > 0) {
@@ -1570,14 +1513,15 @@ int pcreg_final_stage_limits(const double* pts, int N, int ld, const double* T, 
     if (K < 1) { set_error("pcreg_final_stage_limits: K = %d clusters (at least one)", K); return PCREG_E_ARG; }
     GUARD();
     const size_t n = (size_t)N, k = (size_t)K;
-    void *dp, *dT, *tf, *lim;
-    TRY(scratch().get(0, sizeof(double) * 3 * n, &dp));
-    TRY(scratch().get(1, sizeof(double) * 16 * k, &dT));
-    TRY(scratch().get(2, sizeof(double) * 3 * n * k, &tf));
-    TRY(scratch().get(3, sizeof(double) * 6 * k, &lim));
-    TRY(upload_cols(pts, N, ld, 3, (double*)dp, g_stream));
+    Stage st{scratch()};
+    double *dp, *dT, *tf, *lim;
+    TRY(st.take(3 * n, &dp));
+    TRY(st.take(16 * k, &dT));
+    TRY(st.take(3 * n * k, &tf));
+    TRY(st.take(6 * k, &lim));
+    TRY(upload_cols(pts, N, ld, 3, dp, g_stream));
     PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * k, hipMemcpyHostToDevice, g_stream));
-    TRY(launch_quick_tf_batched((const double*)dp, N, N, (const double*)dT, K, (double*)tf, N, (double*)lim, g_stream));
+    TRY(launch_quick_tf_batched(dp, N, N, dT, K, tf, N, lim, g_stream));
     PCREG_HIP(hipMemcpyAsync(limits, lim, sizeof(double) * 6 * k, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
     return PCREG_OK;
@@ -1631,44 +1575,45 @@ int pcreg_final_stage(const pcreg_desc_set* model, const double* featModel, int 
     const int nbatch = (int)cut.size() - 1;
     for (int b = 0; b < nbatch; ++b) batch_rows = std::max(batch_rows, (size_t)(kp_off[cut[b + 1]] - kp_off[cut[b]]));
 
-    void *tmp, *dp, *dT, *dkp, *fm, *cen, *tf, *feat, *desc, *ws, *ints, *dbl, *dpairs;
+    Stage st{scratch()};
+    double *tmp, *dp, *dT, *dkp, *fm, *cen, *tf, *feat, *desc, *dprec, *dpf; char* ws; int32_t* counters; uint32_t* dpairs;
     const size_t wsb = descriptors_workspace_bytes(N, S_max);
     // int32 block: counters [2K] | n_in [K] | nsel [K] | n_pairs [K] | n_close [K] | empty [K] | best | kp_off [K + 1] | seg_off [K + nbatch]
     const size_t ni = 7 * k1 + 1 + (k1 + 1) + (k1 + (size_t)nbatch);
-    TRY(scratch().get(0, sizeof(double) * 3 * (size_t)std::max({N, VM, K}), &tmp));
-    TRY(scratch().get(1, sizeof(double) * 3 * n, &dp));
-    TRY(scratch().get(2, sizeof(double) * 16 * k1, &dT));
-    TRY(scratch().get(3, sizeof(double) * 3 * tot, &dkp));
-    TRY(scratch().get(4, sizeof(double) * 3 * (size_t)std::max(VM, 1), &fm));
-    TRY(scratch().get(5, sizeof(double) * 3 * k1, &cen));
-    TRY(scratch().get(6, sizeof(double) * 3 * n * k1, &tf));
-    TRY(scratch().get(7, sizeof(double) * 3 * tot, &feat));
-    TRY(scratch().get(8, row_bytes * batch_rows, &desc));
-    TRY(scratch().get(9, wsb, &ws));
-    TRY(scratch().get(10, sizeof(int32_t) * ni, &ints));
-    TRY(scratch().get(11, sizeof(double) * 17 * k1, &dbl));
-    TRY(scratch().get(16, sizeof(uint32_t) * 2 * tot, &dpairs));
-    int32_t* counters = (int32_t*)ints;
+    TRY(st.take(3 * (size_t)std::max({N, VM, K}), &tmp));
+    TRY(st.take(3 * n, &dp));
+    TRY(st.take(16 * k1, &dT));
+    TRY(st.take(3 * tot, &dkp));
+    TRY(st.take(3 * (size_t)std::max(VM, 1), &fm));
+    TRY(st.take(3 * k1, &cen));
+    TRY(st.take(3 * n * k1, &tf));
+    TRY(st.take(3 * tot, &feat));
+    TRY(st.take((size_t)D * batch_rows, &desc));
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(ni, &counters));
+    TRY(st.take(17 * k1, &dprec));                          // precision [K] | T16 [K][16]
+    TRY(st.take(2 * tot, &dpairs));
+    TRY(st.take(3 * n, &dpf));                              // the final surface
     int32_t *n_in = counters + 2 * k1, *nsel = n_in + k1, *n_pairs = nsel + k1, *n_close = n_pairs + k1, *empty = n_close + k1, *dbest = empty + k1;
     int32_t *dkpoff = dbest + 1, *dseg = dkpoff + (k1 + 1);
-    double *dprec = (double*)dbl, *dT16 = dprec + k1;
+    double* dT16 = dprec + k1;
     const double* rM = nullptr;
     if (VM > 0) TRY(desc_set_rows(model, &rM));
     std::vector<int32_t> seg_h(k1 + (size_t)nbatch, 0);       // per batch its running sums
     std::vector<int32_t> h_cnt(2 * k1), h_in(k1), h_res(3 * k1 + 1);
     std::vector<double> h_T16(16 * k1);
-    struct DrainAtExit { ~DrainAtExit() { (void)hipStreamSynchronize(g_stream); } } drain;   // no host array is freed under a pending copy
+    DrainAtExit drain;
 
     // upload; :291 pts_tform = quickTF(ptsSurface, invertTF(transCur)) for every cluster in one launch
-    TRY(upload_cols(pts, N, ld, 3, (double*)dp, g_stream));
+    TRY(upload_cols(pts, N, ld, 3, dp, g_stream));
     PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * k1, hipMemcpyHostToDevice, g_stream));
-    TRY(upload_cols(keypoints, total, total, 3, (double*)dkp, g_stream));
-    TRY(upload_points_aos(featModel, VM, ldM, (double*)tmp, (double*)fm, g_stream));
-    TRY(upload_points_aos(locs, K, K, (double*)tmp, (double*)cen, g_stream));
+    TRY(upload_cols(keypoints, total, total, 3, dkp, g_stream));
+    TRY(upload_points_aos(featModel, VM, ldM, tmp, fm, g_stream));
+    TRY(upload_points_aos(locs, K, K, tmp, cen, g_stream));
     PCREG_HIP(hipMemcpyAsync(dkpoff, kp_off, sizeof(int32_t) * (k1 + 1), hipMemcpyHostToDevice, g_stream));
-    PCREG_HIP(hipMemsetAsync(ints, 0, sizeof(int32_t) * 7 * k1, g_stream));
+    PCREG_HIP(hipMemsetAsync(counters, 0, sizeof(int32_t) * 7 * k1, g_stream));
     PCREG_HIP(hipMemsetAsync(dpairs, 0, sizeof(uint32_t) * 2 * tot, g_stream));
-    TRY(launch_quick_tf_batched((const double*)dp, N, N, (const double*)dT, K, (double*)tf, N, nullptr, g_stream));
+    TRY(launch_quick_tf_batched(dp, N, N, dT, K, tf, N, nullptr, g_stream));
 
     size_t seg_pos = 0;
     for (int b = 0; b < nbatch; ++b) {
@@ -1677,12 +1622,11 @@ int pcreg_final_stage(const pcreg_desc_set* model, const double* featModel, int 
         for (int k = k0; k < kb; ++k) {
             const int S = kp_off[k + 1] - kp_off[k];
             if (S == 0) continue;
-            TRY(launch_descriptors((const double*)tf + (size_t)k * 3 * n, N, N, (const double*)dkp + kp_off[k], S, total, o, 0,
-                                   (double*)feat + (size_t)kp_off[k] * 3, (double*)desc + (size_t)(kp_off[k] - r0) * D, nullptr, nullptr,
-                                   counters + 2 * k, counters + 2 * k + 1, ws, wsb, g_stream));
+            TRY(launch_descriptors(tf + (size_t)k * 3 * n, N, N, dkp + kp_off[k], S, total, o, 0, feat + (size_t)kp_off[k] * 3,
+                                   desc + (size_t)(kp_off[k] - r0) * D, nullptr, nullptr, counters + 2 * k, counters + 2 * k + 1, ws, wsb, g_stream));
         }
         // :319 the model keypoints inside every cluster's sphere, counted
-        if (VM > 0) TRY(launch_sphere_counts((const double*)fm, VM, (const double*)cen + (size_t)k0 * 3, nb, R_desc, n_in + k0, g_stream));
+        if (VM > 0) TRY(launch_sphere_counts(fm, VM, cen + (size_t)k0 * 3, nb, R_desc, n_in + k0, g_stream));
         // ---- the sizes: V_k, the over-capacity flags, the sphere counts (one synchronisation per batch)
         PCREG_HIP(hipMemcpyAsync(h_cnt.data() + 2 * (size_t)k0, counters + 2 * (size_t)k0, sizeof(int32_t) * 2 * nb, hipMemcpyDeviceToHost, g_stream));
         PCREG_HIP(hipMemcpyAsync(h_in.data() + k0, n_in + k0, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, g_stream));
@@ -1701,32 +1645,31 @@ int pcreg_final_stage(const pcreg_desc_set* model, const double* featModel, int 
         const int tot_b = sh[nb];
         int32_t* dsb = dseg + seg_pos;
         seg_pos += (size_t)nb + 1;
-        void *rows, *featCur, *descCur, *mws;
+        // sized from the counts just read: a copy of the walk per batch, so that every batch meets the same four slots
+        Stage bst = st;
+        int32_t* rows; double *featCur, *descCur; char* mws;
         size_t off6[6];
         const size_t mwsb = dev_get_matches_layout(std::max(v_max, 1), std::max(n_max, 1), D, D + 1, off6);
-        TRY(scratch().get(12, sizeof(int32_t) * (size_t)std::max(tot_b, 1), &rows));
-        TRY(scratch().get(13, sizeof(double) * 3 * (size_t)std::max(tot_b, 1), &featCur));
-        TRY(scratch().get(14, row_bytes * (size_t)std::max(n_max, 1), &descCur));
-        TRY(scratch().get(15, mwsb, &mws));
+        TRY(bst.take((size_t)std::max(tot_b, 1), &rows));
+        TRY(bst.take(3 * (size_t)std::max(tot_b, 1), &featCur));
+        TRY(bst.take((size_t)D * (size_t)std::max(n_max, 1), &descCur));
+        TRY(bst.take(mwsb, &mws));
         PCREG_HIP(hipMemcpyAsync(dsb, sh, sizeof(int32_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, g_stream));
-        if (VM > 0) TRY(launch_sphere_select_batched((const double*)fm, VM, (const double*)cen + (size_t)k0 * 3, nb, R_desc, dsb, (int32_t*)rows,
-                                                     (double*)featCur, nsel + k0, g_stream));
+        if (VM > 0) TRY(launch_sphere_select_batched(fm, VM, cen + (size_t)k0 * 3, nb, R_desc, dsb, rows, featCur, nsel + k0, g_stream));
         // :321-344 descCur = descModel_noLRF(mask, :), matches = getMatches(desc, descCur, par)
         for (int k = k0; k < kb; ++k) {
             const int v = h_cnt[2 * k], m = h_in[k];
             if (v == 0 || m == 0) continue;
-            TRY(launch_gather_rows_f64(rM, D, (const int32_t*)rows + sh[k - k0], nsel + k, m, (double*)descCur, g_stream));
-            TRY(dev_get_matches_impl((const double*)desc + (size_t)(kp_off[k] - r0) * D, v, D, descCur, m, D, D, PCREG_LAYOUT_ROW_MAJOR, par,
-                                     (uint32_t*)dpairs + (size_t)kp_off[k] * 2, nullptr, n_pairs + k, mws, mwsb, g_stream));
+            TRY(launch_gather_rows_f64(rM, D, rows + sh[k - k0], nsel + k, m, descCur, g_stream));
+            TRY(dev_get_matches_impl(desc + (size_t)(kp_off[k] - r0) * D, v, D, descCur, m, D, D, PCREG_LAYOUT_ROW_MAJOR, par,
+                                     dpairs + (size_t)kp_off[k] * 2, nullptr, n_pairs + k, mws, mwsb, g_stream));
         }
         // :357-391 the close matches, the precision and the refined transform of every cluster of the batch
-        TRY(launch_final_close_refine_batched((const uint32_t*)dpairs, n_pairs + k0, (const double*)feat, dkpoff + k0, (const double*)featCur, dsb, nb,
-                                              maxDist, n_close + k0, dprec + k0, dT16 + (size_t)k0 * 16, empty + k0, g_stream));
+        TRY(launch_final_close_refine_batched(dpairs, n_pairs + k0, feat, dkpoff + k0, featCur, dsb, nb, maxDist, n_close + k0, dprec + k0,
+                                              dT16 + (size_t)k0 * 16, empty + k0, g_stream));
     }
     // :381-394 the best cluster, invertTF(T_refine), the final surface -- on the device
-    double* dpf;
-    { void* q; TRY(scratch().get(17, sizeof(double) * 3 * n, &q)); dpf = (double*)q; }
-    TRY(launch_final_pick_apply(dprec, dT16, empty, K, (const double*)tf, N, N, dpf, N, dbest, g_stream));
+    TRY(launch_final_pick_apply(dprec, dT16, empty, K, tf, N, N, dpf, N, dbest, g_stream));
     // ---- the results (one synchronisation)
     PCREG_HIP(hipMemcpyAsync(h_res.data(), n_pairs, sizeof(int32_t) * (3 * k1 + 1), hipMemcpyDeviceToHost, g_stream));   // n_pairs | n_close | empty | best
     PCREG_HIP(hipMemcpyAsync(precision, dprec, sizeof(double) * k1, hipMemcpyDeviceToHost, g_stream));

@@ -315,39 +315,34 @@ int pcreg_match_points_sharded_f32(const float* q, int Q, int ldq, const float* 
     hipStream_t st = g_cstream;
     const size_t q4 = (size_t)Q * 4;
     // every buffer of the call, before the first collective
-    void *dq, *dm, *dpack, *dall, *didx, *ddist, *dcnt, *dtable, *dpairs, *ws, *block;
+    Stage cs{g_cs};
+    float *dq, *dm, *ddist; int32_t *dpack, *dall, *didx, *n_pairs, *dtable; uint32_t* dpairs; char *ws, *block;
     const size_t wsb = search_ws_bytes(Q, M_local);
-    CTRY(g_cs.get(0, sizeof(float) * 3 * (size_t)Q, &dq));
-    CTRY(g_cs.get(1, sizeof(float) * 3 * (size_t)(M_local > 0 ? M_local : 1), &dm));
-    CTRY(g_cs.get(2, q4 * 4, &dpack));                        // [2][Q][2] words: indices, then the distances' bit patterns
-    CTRY(g_cs.get(3, q4 * 4 * (size_t)R, &dall));
-    CTRY(g_cs.get(4, q4 * 2, &didx));
-    CTRY(g_cs.get(5, q4 * 2, &ddist));
-    CTRY(g_cs.get(9, 256, &dcnt));
-    CTRY(g_cs.get(10, q4 * 4, &dtable));
-    CTRY(g_cs.get(11, q4 * 2, &dpairs));
-    CTRY(g_cs.get(12, wsb, &ws));
-    CTRY(g_cs.get(13, model_prep_bytes(M_local), &block));
-    int32_t* n_pairs = (int32_t*)dcnt;
-    int32_t* idx_l = (int32_t*)dpack; float* dist_l = (float*)((int32_t*)dpack + 2 * (size_t)Q);
-    if (ldq == Q) PCREG_HIP(hipMemcpyAsync(dq, q, sizeof(float) * 3 * (size_t)Q, hipMemcpyHostToDevice, st));
-    else PCREG_HIP(hipMemcpy2DAsync(dq, sizeof(float) * (size_t)Q, q, sizeof(float) * (size_t)ldq, sizeof(float) * (size_t)Q, 3, hipMemcpyHostToDevice, st));
-    if (M_local > 0) {
-        if (ldm == M_local) PCREG_HIP(hipMemcpyAsync(dm, m_local, sizeof(float) * 3 * (size_t)M_local, hipMemcpyHostToDevice, st));
-        else PCREG_HIP(hipMemcpy2DAsync(dm, sizeof(float) * (size_t)M_local, m_local, sizeof(float) * (size_t)ldm, sizeof(float) * (size_t)M_local, 3, hipMemcpyHostToDevice, st));
-    }
+    CTRY(cs.take(3 * (size_t)Q, &dq));
+    CTRY(cs.take(3 * (size_t)(M_local > 0 ? M_local : 1), &dm));
+    CTRY(cs.take(q4, &dpack));                                // [2][Q][2] words: indices, then the distances' bit patterns
+    CTRY(cs.take(q4 * (size_t)R, &dall));
+    CTRY(cs.take(2 * (size_t)Q, &didx));
+    CTRY(cs.take(2 * (size_t)Q, &ddist));
+    CTRY(cs.take(1, &n_pairs));
+    CTRY(cs.take(q4, &dtable));
+    CTRY(cs.take(2 * (size_t)Q, &dpairs));
+    CTRY(cs.take(wsb, &ws));
+    CTRY(cs.take(model_prep_bytes(M_local), &block));
+    int32_t* idx_l = dpack; float* dist_l = (float*)(dpack + 2 * (size_t)Q);
+    CTRY(upload_cols(q, Q, ldq, 3, dq, st));
+    CTRY(upload_cols(m_local, M_local, ldm, 3, dm, st));
     // 1. prepare this rank's shard, local top-2 (global row numbers) + the query grid, all-gather, merge by (distance, index)
-    const ModelView v = model_view((float*)dm, M_local, M_local > 0 ? M_local : 1, block);
+    const ModelView v = model_view(dm, M_local, M_local > 0 ? M_local : 1, block);
     CTRY(launch_model_prepare(v, st));
-    CTRY(launch_model_search(v, (float*)dq, Q, Q, m_lo, idx_l, dist_l, ws, wsb, true, true, st));
+    CTRY(launch_model_search(v, dq, Q, Q, m_lo, idx_l, dist_l, ws, wsb, true, true, st));
     CTRY(all_gather_words(dpack, dall, q4, st));
-    CTRY(launch_merge_top2_f32((int32_t*)dall, (float*)((int32_t*)dall + 2 * (size_t)Q), R, Q, (int32_t*)didx, (float*)ddist, st, q4));
+    CTRY(launch_merge_top2_f32(dall, (float*)(dall + 2 * (size_t)Q), R, Q, didx, ddist, st, q4));
     // 2. filters on every rank, the Unique verdict and the matched coordinates by the rank that owns the model row;
     //    one integer SUM publishes both; 3. ordered compaction from the summed table
-    CTRY(launch_match_table(v, m_lo, M_total, (float*)dq, Q, Q, (int32_t*)didx, (float*)ddist, thr_abs, max_ratio, unique, ws, wsb, (int32_t*)dtable, st));
+    CTRY(launch_match_table(v, m_lo, M_total, dq, Q, Q, didx, ddist, thr_abs, max_ratio, unique, ws, wsb, dtable, st));
     CTRY(all_reduce_sum_words(dtable, q4, st));
-    CTRY(launch_match_from_table((float*)dq, Q, Q, M_total, (int32_t*)didx, (float*)ddist, thr_abs, max_ratio, (int32_t*)dtable, ws, wsb,
-                                 (uint32_t*)dpairs, nullptr, nullptr, n_pairs, st));
+    CTRY(launch_match_from_table(dq, Q, Q, M_total, didx, ddist, thr_abs, max_ratio, dtable, ws, wsb, dpairs, nullptr, nullptr, n_pairs, st));
     int32_t np = 0;
     PCREG_HIP(hipMemcpyAsync(&np, n_pairs, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     PCREG_HIP(hipStreamSynchronize(st));
@@ -366,33 +361,26 @@ int pcreg_ransac_sharded(const double* pts1, const double* pts2, int n, int ld, 
     hipStream_t st = g_cstream;
     const int R = g_world, cap = n > 0 ? n : 1;
     const int share = (opts->iterNum + R - 1) / R, begin = std::min(g_rank * share, opts->iterNum), count = std::min(share, opts->iterNum - begin);
-    void *d1, *d2, *dn, *dpart, *dall, *dres, *dinl, *ws;
+    Stage cs{g_cs};
+    double *d1, *d2; int32_t *dn, *dinl; pcreg_dev_ransac_part *dpart, *dall; pcreg_dev_ransac_result* dres; char* ws;
     const size_t wsb = pcreg_dev_ransac_workspace(cap, count > 0 ? count : 1);
-    CTRY(g_cs.get(15, sizeof(double) * 3 * (size_t)cap, &d1));
-    CTRY(g_cs.get(16, sizeof(double) * 3 * (size_t)cap, &d2));
-    CTRY(g_cs.get(17, 256, &dn));
-    CTRY(g_cs.get(18, sizeof(pcreg_dev_ransac_part), &dpart));
-    CTRY(g_cs.get(19, sizeof(pcreg_dev_ransac_part) * (size_t)R, &dall));
-    CTRY(g_cs.get(20, sizeof(pcreg_dev_ransac_result), &dres));
-    CTRY(g_cs.get(21, sizeof(int32_t) * (size_t)cap, &dinl));
-    CTRY(g_cs.get(22, wsb, &ws));
-    if (n > 0) {
-        if (ld == n) {
-            PCREG_HIP(hipMemcpyAsync(d1, pts1, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-            PCREG_HIP(hipMemcpyAsync(d2, pts2, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-        } else {
-            PCREG_HIP(hipMemcpy2DAsync(d1, sizeof(double) * (size_t)cap, pts1, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, 3, hipMemcpyHostToDevice, st));
-            PCREG_HIP(hipMemcpy2DAsync(d2, sizeof(double) * (size_t)cap, pts2, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, 3, hipMemcpyHostToDevice, st));
-        }
-    }
+    CTRY(cs.take(3 * (size_t)cap, &d1));
+    CTRY(cs.take(3 * (size_t)cap, &d2));
+    CTRY(cs.take(1, &dn));
+    CTRY(cs.take(1, &dpart));
+    CTRY(cs.take((size_t)R, &dall));
+    CTRY(cs.take(1, &dres));
+    CTRY(cs.take((size_t)cap, &dinl));
+    CTRY(cs.take(wsb, &ws));
+    CTRY(upload_cols(pts1, n, ld, 3, d1, st));                // n > 0: cap == n, the compact matrix
+    CTRY(upload_cols(pts2, n, ld, 3, d2, st));
     const int32_t nh = n;
     PCREG_HIP(hipMemcpyAsync(dn, &nh, sizeof nh, hipMemcpyHostToDevice, st));
     PCREG_HIP(hipMemsetAsync(dpart, 0, sizeof(pcreg_dev_ransac_part), st));
-    CTRY(launch_ransac_partial((double*)d1, (double*)d2, cap, (int32_t*)dn, cap, *opts, nullptr, begin, count, (pcreg_dev_ransac_part*)dpart, ws, wsb, st));
+    CTRY(launch_ransac_partial(d1, d2, cap, dn, cap, *opts, nullptr, begin, count, dpart, ws, wsb, st));
     static_assert(sizeof(pcreg_dev_ransac_part) == 112, "the gathered struct is 112 bytes");
     CTRY(all_gather_words(dpart, dall, sizeof(pcreg_dev_ransac_part) / 4, st));
-    CTRY(launch_ransac_finish((double*)d1, (double*)d2, cap, (int32_t*)dn, cap, *opts, (pcreg_dev_ransac_part*)dall,
-                              (pcreg_dev_ransac_result*)dres, (int32_t*)dinl, st, R));
+    CTRY(launch_ransac_finish(d1, d2, cap, dn, cap, *opts, dall, dres, dinl, st, R));
     pcreg_dev_ransac_result res;
     PCREG_HIP(hipMemcpyAsync(&res, dres, sizeof res, hipMemcpyDeviceToHost, st));
     if (n > 0) PCREG_HIP(hipMemcpyAsync(inlier_idx, dinl, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));

@@ -36,16 +36,25 @@ int  ensure_device();   // PCREG_OK or PCREG_E_NODEVICE / PCREG_E_HIP
 // on MATLAB's interpreter thread).  Slots keep independent
 // buffers alive across one call.
 struct Scratch {
-    static constexpr int kSlots = 24;
+    static constexpr int kSlots = 24;     // the longest chain is pcreg_sphere_sweep's: 14 of its own, 4 of the sphere head, 1 of the pair fetch
     void*  ptr[kSlots]  = {};
     size_t size[kSlots] = {};
     int get(int slot, size_t bytes, void** out);
     void release_all();
 };
 Scratch& scratch();
-// device-tier temporaries: one Scratch per stream, so that calls on different streams may overlap
-// (a stream runs its own kernels in order, which makes the reuse within it safe)
-Scratch& stream_scratch(hipStream_t st);
+// one host-tier call's walk over a Scratch: buffers are taken in order, so a helper that is handed the walk
+// continues behind its caller's buffers and cannot collide with them
+struct Stage {
+    Scratch& s; int next = 0;
+    template <class T> int take(size_t count, T** out) {       // PCREG_OK / PCREG_E_*; count 0 still yields a valid pointer
+        void* p = nullptr;
+        const int rc = s.get(next, count * sizeof(T), &p);
+        if (rc == PCREG_OK) ++next;
+        *out = (T*)p;
+        return rc;
+    }
+};
 
 // Switches.  Two kinds, and NEITHER reads the environment in the default build (a stray variable in a MATLAB worker's
 // environment must not change which kernels run):
@@ -111,6 +120,16 @@ struct WsWalk {
     template <class T> T* take(size_t count, size_t align = 256) { return (T*)take_bytes(align_up(count * sizeof(T), align)); }
     size_t bytes() const { return off; }
 };
+
+// copy an n x cols column-major host matrix (leading dimension ld) to a compact device
+// matrix (leading dimension n)
+template <typename T>
+static int upload_cols(const T* host, int n, int ld, int cols, T* dev, hipStream_t st) {
+    if (n <= 0 || cols <= 0) return PCREG_OK;
+    if (ld == n) { PCREG_HIP(hipMemcpyAsync(dev, host, sizeof(T) * (size_t)n * cols, hipMemcpyHostToDevice, st)); }
+    else PCREG_HIP(hipMemcpy2DAsync(dev, sizeof(T) * (size_t)n, host, sizeof(T) * (size_t)ld, sizeof(T) * (size_t)n, cols, hipMemcpyHostToDevice, st));
+    return PCREG_OK;
+}
 
 // ---- kernel launchers implemented in the .hip files (device pointers, async) --------
 struct RansacDims { int n_cap; int iters; int B; };

@@ -90,6 +90,36 @@ def test_sphere_model_handle_edges(oracle_py):
             pc.sphereSweepOnModel(sm, hS, featS, PAR, 60, OPT, seed=1)
 
 
+def test_sphere_sweep_refuses_wrong_counts(oracle_py):
+    """pcreg_sphere_sweep holds the caller's counts against the spheres' before anything reads the row lists (the head it shares with
+    pcreg_sphere_model_create): one count too small and one too large are refused with the sphere's number, and a correct call
+    afterwards gives the device driver's result."""
+    import pcreg_amd as pc
+    from pcreg_amd._lib import PcregError
+    from pcreg_amd.sweep import SphereSweep
+    featM, descM, featS, descS = _scene()
+    kw = dict(R_desc=9.0, d_spheres=6.0, min_pts=500, putative_thresh=60, seed=3)
+    want = SphereSweep(featM, descM, featS, descS).run(PAR, OPT, **kw)
+    assert len(want["trial"]) >= 1
+    centres = oracle_py.pcUniformSamples(featM, kw["d_spheres"])
+    counts = pc.sphereCounts(featM, centres, kw["R_desc"])
+    keep = counts >= kw["min_pts"]
+    with pc.DescSet(descS) as hS, pc.DescSet(descM) as hM:
+        for d in (-1, 1):
+            wrong = counts[keep].copy(); wrong[1] += d
+            with pytest.raises(PcregError, match="holds"):
+                pc.sphereSweep(hS, hM, featS, featM, centres[keep], wrong, kw["R_desc"], PAR, kw["putative_thresh"], OPT, seed=kw["seed"])
+            got = pc.sphereSweep(hS, hM, featS, featM, centres[keep], counts[keep], kw["R_desc"], PAR, kw["putative_thresh"], OPT, seed=kw["seed"])
+            for k in ("centres", "num_desc", "num_putative", "trial", "statsPutative", "statsSuccess", "statsInliers", "statsRatio"):
+                np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+            for k in ("matches", "model_rows"):
+                assert len(got[k]) == len(want[k])
+                for a, b in zip(got[k], want[k]):
+                    np.testing.assert_array_equal(a, b)
+            for a, b in zip(got["transforms"], want["transforms"]):
+                assert (a is None) == (b is None) and (a is None or np.array_equal(a, b))
+
+
 def test_host_tier_sphere_sweep_equals_the_device_driver(oracle_py):
     """pcreg_sphere_counts + pcreg_sphere_sweep (what MATLAB reaches through pcreg_mex: host arrays, descriptor sets resident) ==
     SphereSweep.run field for field -- counts, row lists, matches, trial spheres, transforms (the same kernels, the same seeds)."""
