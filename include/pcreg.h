@@ -84,7 +84,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * descriptor memory bound of pcreg_final_stage in MB instead of 4 GB, to exercise its batches), "knn_nocull" (the point search
  * visits every model tile), "knn_stats" (counters for pcreg_debug_knn_stats), "ransac_pass2" (the staged RANSAC
  * chain's second scoring pass: 1 always the full pass, 2 always the bounded pass where allowed; 0 chooses by shape),
- * "ransac_stats" (counters for pcreg_debug_ransac_stats); value 0 restores the default.  The library reads NO
+ * "ransac_stats" (counters for pcreg_debug_ransac_stats), "range_sort_cap" (n > 0: the radius search orders segments longer
+ * than n rows by its in-place large-segment path); value 0 restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
 /* With pcreg_debug_set("match_stats", 1): the counters of the certified SAD matcher summed over the calls since the last
@@ -166,6 +167,18 @@ int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int 
 int pcreg_model_knn_f32(pcreg_model* model, const float* q, int Q, int ldq, int k, int32_t* idx, float* dist);
 /* The same without a handle (knnsearch(m, q, 'K', k)): uploads and prepares the model for this call only. */
 int pcreg_knn_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int k, int32_t* idx, float* dist);
+/* MATLAB's [Idx, D] = rangesearch(model, q, r) / findNeighborsInRadius against the handle, with the SQUARED radius r2 = r^2:
+ * model row j belongs to query i iff its fp32 squared distance fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance
+ * never passes, so a non-finite query has an empty segment at a finite r2; with r2 = +inf an overflowed distance passes too).
+ * Query i's rows are seg_off[i] .. seg_off[i + 1] of idx (0-based) / dist (squared), ordered by (distance, row), ties to the
+ * lowest row.  Exact: the same bits as a brute force.  seg_off [Q + 1] is always written (seg_off[Q] = total).  idx / dist
+ * (capacity elements; may be NULL when capacity == 0) are written iff total <= capacity: call once with capacity 0 to size
+ * them.  PCREG_OK in both cases.  r2 NaN or negative, Q above 4 Mi, a negative capacity: PCREG_E_ARG. */
+int pcreg_model_range_f32(pcreg_model* model, const float* q, int Q, int ldq, float r2, int64_t capacity,
+                          int64_t* seg_off, int32_t* idx, float* dist);
+/* The same without a handle (rangesearch(m, q, r)): uploads and prepares the model for this call only. */
+int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float r2, int64_t capacity,
+                           int64_t* seg_off, int32_t* idx, float* dist);
 
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
@@ -392,6 +405,21 @@ int pcreg_dev_model_search_f32(const pcreg_dev_model* model, const float* q, int
 size_t pcreg_dev_model_knn_workspace(int Q, int M, int k);
 int pcreg_dev_model_knn_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, int k, int32_t idx_base, int32_t* idx,
                             float* dist, void* workspace, size_t workspace_bytes, void* stream);
+/* rangesearch(model, q, r) on the device in two calls (count + scan, then fill + order): pcreg_model_range_f32's contract with
+ * r2 = r^2.  Count: counts [Q] and seg_off [Q + 1], the exclusive running sums in 64 bits (seg_off[Q] = total rows).  Fill: idx
+ * / dist [capacity], query i's rows at seg_off[i] .. seg_off[i + 1] in (distance, row) order, idx = idx_base + 0-based row.
+ * The fill never writes outside [seg_off[i], seg_off[i + 1]) intersected with [0, capacity), whatever seg_off holds: a seg_off
+ * made with a smaller radius, or a capacity below the total, truncates segments (which rows remain is then unspecified).
+ * Each call forms its own query order, so the caller may read the total, allocate, and fill later, on any stream; nothing
+ * synchronises.  Q <= 4 Mi per call.  One workspace size serves both calls: 147 712 + 3 * roundup(4 * max(Q, 1), 256) bytes,
+ * i.e. 12 bytes per query, whatever M, r2 and the size of the result.  Tiles are skipped by DESIGN 4.1's rule with the
+ * radius as the bound.  A handle may serve several streams at once, each call with its own workspace. */
+size_t pcreg_dev_model_range_workspace(int Q, int M);
+int pcreg_dev_model_range_count_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2,
+                                    int32_t* counts, int64_t* seg_off, void* workspace, size_t workspace_bytes, void* stream);
+int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2, int32_t idx_base,
+                                   const int64_t* seg_off, int64_t capacity, int32_t* idx, float* dist,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

@@ -11,6 +11,9 @@
 //                                          -> pairs (P x 2 uint32) | 'modelDestroy', handle      (one model, many surfaces)
 //   'modelKnn', handle, queries (single Q x 3), k        -> idx (Q x k int32, 1-based, 0 past M), D2 (Q x k single, squared)
 //                                          (knnsearch(model, Y, 'K', k) against the handle; matlab/knnsearchModel.m)
+//   'modelRange', handle, queries (single Q x 3), r      -> counts (Q x 1 int32), idx (total x 1 int32, 1-based), D2 (total x 1 single,
+//                                          squared): query i's rows follow those of the queries before it, ordered by (distance, row)
+//                                          (rangesearch(model, Y, r) against the handle; matlab/rangesearchModel.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -429,6 +432,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                     for (int j = 0; j < k; ++j) { di[i + (size_t)j * Q] = si[(size_t)i * k + j] + 1; dd[i + (size_t)j * Q] = sd[(size_t)i * k + j]; }
             }
             mxDestroyArray(bi); mxDestroyArray(bd);
+        }
+    } else if (!strcmp(cmd, "modelRange")) {                  // [counts, idx, D2] = pcreg_mex('modelRange', h, single(Y), r): rangesearch(model, Y, r)
+        if (nrhs != 4 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !(mxIsDouble(prhs[3]) || mxIsSingle(prhs[3])) ||
+            mxGetM(prhs[3]) * mxGetN(prhs[3]) != 1 || !(mxGetScalar(prhs[3]) >= 0.0))
+            usage = "modelRange: handle (uint64), queries (single Q x 3), r (a real scalar >= 0)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]);
+            const float r = (float)mxGetScalar(prhs[3]), r2 = r * r;             // single(r) squared once, in single
+            const float* q = (const float*)mxGetData(prhs[2]);
+            mxArray* so = mxCreateNumericMatrix((size_t)Q + 1, 1, mxUINT64_CLASS, mxREAL);    // (8-byte elements: seg_off)
+            int64_t* seg = (int64_t*)mxGetData(so);
+            rc = pcreg_model_range_f32(h, q, Q, Q > 0 ? Q : 1, r2, 0, seg, nullptr, nullptr);       // capacity 0: sizes the result
+            if (rc == PCREG_OK) {
+                const int64_t total = seg[Q];
+                mxArray* oi = mxCreateNumericMatrix((size_t)total, 1, mxINT32_CLASS, mxREAL);
+                mxArray* od = mxCreateNumericMatrix((size_t)total, 1, mxSINGLE_CLASS, mxREAL);
+                int32_t* di = (int32_t*)mxGetData(oi);
+                if (total > 0) rc = pcreg_model_range_f32(h, q, Q, Q, r2, total, seg, di, (float*)mxGetData(od));
+                if (rc == PCREG_OK && seg[Q] != total) rc = PCREG_E_ARG;           // (the model cannot change between the two calls)
+                if (rc == PCREG_OK) {
+                    for (int64_t k = 0; k < total; ++k) di[k] += 1;
+                    plhs[0] = mxCreateNumericMatrix((size_t)Q, 1, mxINT32_CLASS, mxREAL);
+                    int32_t* dc = (int32_t*)mxGetData(plhs[0]);
+                    for (int i = 0; i < Q; ++i) dc[i] = (int32_t)(seg[i + 1] - seg[i]);
+                    plhs[1] = oi; plhs[2] = od;
+                } else { mxDestroyArray(oi); mxDestroyArray(od); }
+            }
+            mxDestroyArray(so);
         }
     } else if (!strcmp(cmd, "descCreate")) {                  // h = pcreg_mex('descCreate', desc): an n x D double descriptor set, uploaded ONCE
         if (nrhs != 2 || !mxIsDouble(prhs[1])) usage = "descCreate: desc (double n x D)";

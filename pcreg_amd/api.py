@@ -606,6 +606,36 @@ def knn_points(query, model, k: int):
     return idx[:Q], dist[:Q]
 
 
+def _range_r2(r2) -> float:
+    r2 = float(np.float32(r2))
+    if not r2 >= 0.0:
+        raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+    return r2
+
+
+def _range_call(call, Q: int):
+    """capacity 0 sizes the result, the second call fills it (the library counts again: the host tier keeps no state)"""
+    seg_off = np.zeros(Q + 1, dtype=np.int64)
+    call(0, seg_off, None, None)
+    total = int(seg_off[Q])
+    idx = np.zeros(total, dtype=np.int32)
+    dist = np.zeros(total, dtype=np.float32)
+    if total:
+        call(total, seg_off, idx.ctypes.data, dist.ctypes.data)
+    return seg_off, idx, dist
+
+
+def rangesearch_points(query, model, r2: float):
+    """rangesearch(model, query, r) in fp32 with r2 = r^2: (seg_off [Q + 1] int64, idx [total] 0-based int32, dist [total]
+    squared float32); query i's rows are seg_off[i] .. seg_off[i + 1], every row with distance <= r2, ordered by (distance,
+    row).  The model is prepared for this call only: keep a Model for repeated searches."""
+    r2 = _range_r2(r2)
+    q, m = _fcol(query, np.float32), _fcol(model, np.float32)
+    Q, M = q.shape[0], m.shape[0]
+    return _range_call(lambda cap, so, i, d: check(lib().pcreg_range_points_f32(q.ctypes.data, Q, max(Q, 1), m.ctypes.data, M, max(M, 1), r2, cap,
+                                                                                so.ctypes.data, i, d)), Q)
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or
@@ -641,6 +671,17 @@ class Model:
         check(lib().pcreg_model_knn_f32(self._h, _ptr(q, C.c_float), C.c_int(Q), C.c_int(max(Q, 1)), C.c_int(k), _ptr(idx, C.c_int32),
                                         _ptr(dist, C.c_float)))
         return idx[:Q], dist[:Q]
+
+    def rangesearch(self, query, r2: float):
+        """rangesearch(model, query, r) against the prepared model with r2 = r^2: (seg_off [Q + 1] int64, idx [total] 0-based
+        int32, dist [total] squared float32), query i's rows at seg_off[i] .. seg_off[i + 1], ordered by (distance, row) -- the
+        bits of a brute-force fp32 search."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        return _range_call(lambda cap, so, i, d: check(lib().pcreg_model_range_f32(self._h, q.ctypes.data, Q, max(Q, 1), r2, cap, so.ctypes.data, i, d)), Q)
 
     def close(self):
         if self._h.value:

@@ -24,6 +24,7 @@ void set_error(const char* fmt, ...) {
 
 constexpr int kKnnMaxK = PCREG_KNN_MAX_K;        // (named here so that no argument message spells the macro)
 constexpr int kKnnMaxQ = 4 << 20;                  // queries per k-nearest call: the top-2 search's limit
+constexpr int kRangeMaxQ = 4 << 20;                // queries per radius-search call: the same limit
 static std::mutex g_mu;
 static int g_device_ok = -1;          // -1 unknown, 0 ok, else error code
 static hipStream_t g_stream = nullptr;
@@ -113,7 +114,7 @@ int pcreg_debug_set(const char* key, int value) {
     static const char* const names[pcreg::kDbgCount] = {"knn_exact", "match_exact", "match_force_fallback", "ransac_fused", "ransac_nolane",
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
-                                                        "knn_stats", "ransac_pass2", "ransac_stats"};
+                                                        "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -350,6 +351,22 @@ int pcreg_dev_model_knn_f32(const pcreg_dev_model* model, const float* q, int Q,
     GUARD();
     return launch_model_knn(model->v, q, Q, ldq, k, idx_base, idx, dist, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_range_workspace(int Q, int M) { return range_ws_bytes(Q, M); }
+int pcreg_dev_model_range_count_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2, int32_t* counts,
+                                    int64_t* seg_off, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && q && counts && seg_off && workspace && Q >= 0 && ldq >= Q && Q <= kRangeMaxQ && r2 >= 0.0f);
+    GUARD();
+    return launch_model_range_count(model->v, q, Q, ldq, r2, counts, seg_off, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2, int32_t idx_base,
+                                   const int64_t* seg_off, int64_t capacity, int32_t* idx, float* dist, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && q && seg_off && workspace && Q >= 0 && ldq >= Q && Q <= kRangeMaxQ && r2 >= 0.0f && capacity >= 0 &&
+              (capacity == 0 || (idx && dist)));
+    GUARD();
+    return launch_model_range_fill(model->v, q, Q, ldq, r2, idx_base, seg_off, capacity, idx, dist, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -465,6 +482,54 @@ int pcreg_knn_points_f32(const float* q, int Q, int ldq, const float* m, int M, 
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return knn_on_view(st, v, q, Q, ldq, k, idx, dist);
+}
+
+// rangesearch on a prepared model: upload the queries, count + scan, read seg_off (the total), then fill + order when the
+// caller's capacity holds the total.  The two result buffers are taken last, and taken (empty) on the count-only path too.
+static int range_on_view(Stage& st, const ModelView& v, const float* q, int Q, int ldq, float r2, int64_t capacity, int64_t* seg_off,
+                         int32_t* idx, float* dist) {
+    float *dq, *dd; int32_t *dc, *di; int64_t* ds; char* ws;
+    const size_t wsb = range_ws_bytes(Q, v.M);
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take((size_t)Q, &dc));
+    TRY(st.take((size_t)Q + 1, &ds));
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    TRY(launch_model_range_count(v, dq, Q, Q, r2, dc, ds, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(seg_off, ds, sizeof(int64_t) * ((size_t)Q + 1), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const int64_t total = seg_off[Q];
+    const bool fill = total > 0 && total <= capacity;
+    TRY(st.take(fill ? (size_t)total : 0, &di));
+    TRY(st.take(fill ? (size_t)total : 0, &dd));
+    if (!fill) return PCREG_OK;
+    TRY(launch_model_range_fill(v, dq, Q, Q, r2, 0, ds, total, di, dd, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_range_f32(pcreg_model* model, const float* q, int Q, int ldq, float r2, int64_t capacity, int64_t* seg_off, int32_t* idx,
+                          float* dist) {
+    PCREG_ARG(model && q && seg_off && Q >= 0 && ldq >= Q && Q <= kRangeMaxQ && r2 >= 0.0f && capacity >= 0 && (capacity == 0 || (idx && dist)));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return range_on_view(st, model->dm->v, q, Q, ldq, r2, capacity, seg_off, idx, dist);
+}
+int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float r2, int64_t capacity, int64_t* seg_off,
+                           int32_t* idx, float* dist) {
+    PCREG_ARG(q && m && seg_off && Q >= 0 && M >= 0 && ldq >= Q && ldm >= M && Q <= kRangeMaxQ && r2 >= 0.0f && capacity >= 0 &&
+              (capacity == 0 || (idx && dist)));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return range_on_view(st, v, q, Q, ldq, r2, capacity, seg_off, idx, dist);
 }
 
 int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float thr_abs,

@@ -85,6 +85,8 @@ enum DebugKey {
     kDbgRansacPass2,           // "ransac_pass2": the staged chain's second scoring pass -- 0 by shape (bounded_pays), 1 always the full pass,
                                // 2 always the bounded pass where it is allowed
     kDbgRansacStats,           // "ransac_stats": the bounded pass counts what it scans (pcreg_debug_ransac_stats)
+    kDbgRangeSortCap,          // "range_sort_cap": n > 0 -- the radius search orders segments longer than n rows by its in-place
+                               // large-segment path (0 = the default capacity)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -184,6 +186,12 @@ int launch_model_knn(const ModelView& v, const float* q, int Q, int ldq, int k, 
                      void* ws, size_t ws_bytes, hipStream_t st);
 int launch_merge_topk_f32(const int32_t* idx_in, const float* dist_in, int R, int Q, int k, size_t rank_stride, int32_t* idx, float* dist,
                           hipStream_t st);
+// rows within a squared radius per query (knn_range.hip): count + scan, then fill + order; one workspace size serves both
+size_t range_ws_bytes(int Q, int M);
+int launch_model_range_count(const ModelView& v, const float* q, int Q, int ldq, float r2, int32_t* counts, int64_t* seg_off, void* ws,
+                             size_t ws_bytes, hipStream_t st);
+int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, float r2, int32_t idx_base, const int64_t* seg_off,
+                            int64_t capacity, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,

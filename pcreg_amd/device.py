@@ -71,6 +71,67 @@ class PreparedModel:
                                             C.c_size_t(ws.numel()), _stream()))
         return idx, dist
 
+    def _range_args(self, q_soa, r2):
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        r2 = float(r2)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        Q = int(q_soa.shape[1])
+        return r2, Q, max(int(lib().pcreg_dev_model_range_workspace(Q, self.M)), 256)
+
+    def _range_ws(self, need, device):
+        ws = getattr(self, "_range_ws_t", None)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = self._range_ws_t = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def rangesearch_count(self, q_soa: torch.Tensor, r2: float, out=None):
+        """The first half of rangesearch(model, q, r) with r2 = r^2, on torch's current stream (pcreg_dev_model_range_count_f32):
+        -> (counts [Q] int32, seg_off [Q + 1] int64, the exclusive running sums; seg_off[Q] is the number of rows).  Nothing
+        synchronises.  The workspace is cached on the model and grown on demand; calls that may overlap on two streams pass
+        buffers of their own, out=(counts, seg_off, ws) with ws of pcreg_dev_model_range_workspace(Q, M) bytes."""
+        r2, Q, need = self._range_args(q_soa, r2)
+        if out is not None:
+            counts, seg_off, ws = out
+        else:
+            counts = torch.empty(Q, dtype=torch.int32, device=q_soa.device)
+            seg_off = torch.empty(Q + 1, dtype=torch.int64, device=q_soa.device)
+            ws = self._range_ws(need, q_soa.device)
+        if Q == 0:                                     # (an empty tensor has no address to pass)
+            seg_off.zero_()
+            return counts, seg_off
+        with torch.cuda.device(q_soa.device):
+            check(lib().pcreg_dev_model_range_count_f32(self.handle, _p(q_soa), Q, max(int(q_soa.stride(0)), Q), r2, _p(counts), _p(seg_off), _p(ws),
+                                                        ws.numel(), _stream()))
+        return counts, seg_off
+
+    def rangesearch_fill(self, q_soa: torch.Tensor, r2: float, seg_off: torch.Tensor, idx: torch.Tensor, dist: torch.Tensor, idx_base: int = 0,
+                         ws=None):
+        """The second half (pcreg_dev_model_range_fill_f32): query i's rows into idx / dist [seg_off[i], seg_off[i + 1]), in
+        (distance, row) order, never outside those bounds or past len(idx).  No synchronisation."""
+        r2, Q, need = self._range_args(q_soa, r2)
+        if ws is None:
+            ws = self._range_ws(need, q_soa.device)
+        if Q == 0 or min(idx.numel(), dist.numel()) == 0:
+            return idx, dist
+        with torch.cuda.device(q_soa.device):
+            check(lib().pcreg_dev_model_range_fill_f32(self.handle, _p(q_soa), Q, max(int(q_soa.stride(0)), Q), r2, int(idx_base), _p(seg_off),
+                                                       min(idx.numel(), dist.numel()), _p(idx), _p(dist), _p(ws), ws.numel(), _stream()))
+        return idx, dist
+
+    def rangesearch(self, q_soa: torch.Tensor, r2: float, idx_base: int = 0):
+        """rangesearch(model, q, r) with r2 = r^2 -> (seg_off [Q + 1] int64, idx [total] int32 = idx_base + 0-based row, dist
+        [total] float32 squared); query i's rows are seg_off[i] .. seg_off[i + 1], ordered by (distance, row).  Reads the total
+        (seg_off[Q]) on the host ONCE, between the count and the fill, to size idx / dist: the only synchronisation."""
+        _, seg_off = self.rangesearch_count(q_soa, r2)
+        total = int(seg_off[-1].item())
+        idx = torch.empty(total, dtype=torch.int32, device=q_soa.device)
+        dist = torch.empty(total, dtype=torch.float32, device=q_soa.device)
+        if total:
+            self.rangesearch_fill(q_soa, r2, seg_off, idx, dist, idx_base)
+        return seg_off, idx, dist
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             lib().pcreg_dev_model_destroy(self.handle)
