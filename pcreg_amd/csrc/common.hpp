@@ -170,6 +170,7 @@ struct SearchWs {
     int32_t* tail_idx; float* tail_dist;
     void* ug_prep; float* ug_part; int32_t* ug_cnt; void* ug_slots; int ug_cells, ug_nparts;
     int32_t* qcnt; int32_t* qperm; float* dk;          // the call's query order (counters, slot -> query) and seed distances
+    int32_t* n_vis; int32_t* vis_list;                 // the visit plan: tiles to visit per query block, [q_blocks] and [q_blocks][n_tiles] (inside tail_idx's slot)
 };
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes);
 size_t search_ws_bytes(int Q, int M);

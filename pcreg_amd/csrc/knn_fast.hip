@@ -10,21 +10,28 @@
 //                                         sorted fp32 copy the rest is built from
 //   P3  prep_model_f16_kernel             sorted rows -> tiles of f16 matrix-core operands, R_m^2, and the seeding grid's cells
 //   P4  tile_box_kernel                   the exact fp32 box of every tile of kT16 sorted rows
-// and a search is SEVEN launches:
+// and a search is SEVEN launches (a 128-KB memset of the query order's counters among them):
 //   S1  seed_query_kernel    a first threshold per query from the model-wide seeding grid and its seed distance dk; clears
 //                            the call's counters and the candidate lists; per-workgroup boxes of the queries (query grid,
-//                            below); counts the queries per parent cell of the ordering grid (after a memset)
-//   S1b exclusive_scan_1wg_kernel, query_order_kernel   the query SLOTS in spatial order (qperm)
-//   S2  knn_candidates_f16_pipe_kernel (knn_mfma16.hip)   per block of 512 query slots, the scores against every model
-//                            tile the block's box and largest dk cannot rule out, on the matrix cores + selection
+//                            below); counts the queries per parent cell of the ordering grid (after the memset) and keeps
+//                            each query's place inside its cell
+//   S1b query_order_ranked_kernel   the query SLOTS in spatial order (qperm); every workgroup derives the cell offsets it
+//                            needs from the counters itself, so no scan launch sits between S1 and the slots
+//   S1c knn_plan_kernel (knn_mfma16.hip)   the visit plan: per block of 512 query slots, ONCE, the box and largest dk of its
+//                            scored queries and the ascending list of the model tiles they cannot rule out
+//   S2  knn_candidates_f16_pipe_kernel (knn_mfma16.hip)   the scores of a block against the tiles of its plan, on the matrix
+//                            cores + selection; the grid keeps W workgroups per block, W_eff = ceil(n_vis / kPlanC) (at most
+//                            W) of them share the plan's positions and the others leave after one word
 //   S3  knn_finalize_kernel  one 8-lane group per query: exact fmaf-chain distances of the listed candidates over the sorted
 //                            copy, (distance, original index) top-2, and the CERTIFICATE: every point outside the lists has
 //                            s >= G (the final threshold word), hence exact d >= G + |q~|^2 - E; proven answers are
 //                            written, the others are listed; fills the query grid (a point of a skipped tile is farther
 //                            than two real model points: DESIGN 4.1, culling)
-//   S4  knn_tail_kernel      the listed queries again, exactly: slices of the model per query when few, the tiled
-//                            all-pairs form when many; per-query / per-tile arrival counters let the last workgroup
-//                            merge, so there is no second launch.  Idle (one read) when the list is empty.
+//   S4  knn_tail_kernel      the listed queries again, exactly.  Few: one workgroup per query culls the tiles with the same
+//                            rule against the query's own dk (the block box shrunk to a point) and scans the rest of the
+//                            sorted copy, (distance, original row) order.  Many: the tiled all-pairs form over the unsorted
+//                            model; a per-tile arrival counter lets the last workgroup merge, so there is no second launch.
+//                            Idle (one read) when the list is empty.
 // By-product: a uniform grid over the QUERIES (boxes in S1, geometry by a surplus workgroup of S2, cells in S3), which
 // the Unique back-check of the match stage walks (knn_points.hip: match_finish_kernel) -- no launches of its own.
 //
@@ -45,9 +52,9 @@ void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* W);
 int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsigned* rm2, void* mtiles, int32_t* seed_cnt,
                           void* seed_slots, hipStream_t st);
 int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
-                              const void* mtiles, const float* tbox, int cull, unsigned* gthr, void* cand_ent, int32_t* cand_cnt,
-                              void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part, int ug_nparts, int ug_cells,
-                              void* ug_prep, int* W_out, hipStream_t st);
+                              const void* mtiles, const float* tbox, int cull, int32_t* n_vis, int32_t* vis_list, unsigned* gthr,
+                              void* cand_ent, int32_t* cand_cnt, void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part,
+                              int ug_nparts, int ug_cells, void* ug_prep, int* W_out, hipStream_t st);
 
 namespace {
 
@@ -205,6 +212,49 @@ __global__ __launch_bounds__(kBlock) void query_order_kernel(const float* __rest
     qperm[atomicAdd(&off[key], 1)] = qi;
 }
 
+// S1b of the two-nearest search in ONE launch, without a scan on the critical path: cnt holds the per-parent-cell counts and
+// rank each query's place inside its cell (both from seed_query_kernel).  Every workgroup sums all kQueryKeys counters
+// itself (L2-resident, 128 per thread) and keeps the exclusive offsets of every 16th in LDS; a query adds the at most 15
+// counters in front of its own cell's.  No atomics: cnt is only read.
+__global__ __launch_bounds__(kBlock) void query_order_ranked_kernel(const float* __restrict__ q, int Q, int ldq, const Prep* __restrict__ prep,
+                                                                    const int32_t* __restrict__ cnt, const int32_t* __restrict__ rank,
+                                                                    int32_t* __restrict__ qperm) {
+    constexpr int kPer = kQueryKeys / kBlock, kSub = kPer / 16;
+    static_assert(kQueryKeys % (kBlock * 16) == 0, "every thread owns whole groups of 16 counters");
+    __shared__ int s_sub[kQueryKeys / 16], s_w[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int4* p = (const int4*)cnt + (size_t)threadIdx.x * (kPer / 4);
+    int sub[kSub], sum = 0;
+#pragma unroll
+    for (int j = 0; j < kSub; ++j) {
+        const int4 a = p[4 * j], b = p[4 * j + 1], c = p[4 * j + 2], d = p[4 * j + 3];
+        sub[j] = sum;
+        sum += (a.x + a.y + a.z + a.w) + (b.x + b.y + b.z + b.w) + (c.x + c.y + c.z + c.w) + (d.x + d.y + d.z + d.w);
+    }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o); if (lane >= o) inc += y; }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int k = 0; k < wave; ++k) run += s_w[k];
+#pragma unroll
+    for (int j = 0; j < kSub; ++j) s_sub[threadIdx.x * kSub + j] = run + sub[j];
+    __syncthreads();
+    const int qi = blockIdx.x * kBlock + threadIdx.x;
+    if (qi >= Q) return;
+    const int key = sort_key(q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq], prep) >> 3;
+    const int4* f = (const int4*)cnt + (size_t)(key >> 4) * 4;
+    const int r = key & 15;
+    int off = s_sub[key >> 4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int4 v = f[i];
+        off += (4 * i < r ? v.x : 0) + (4 * i + 1 < r ? v.y : 0) + (4 * i + 2 < r ? v.z : 0) + (4 * i + 3 < r ? v.w : 0);
+    }
+    qperm[off + rank[qi]] = qi;
+}
+
 // ---- S1. seeding: a first threshold per query from the model-wide grid ------------------------------------------
 // The candidate kernel only touches its sorted lists when a score beats the query's threshold, and a wave pays that
 // slow path whenever ANY of its lanes does.  Starting from +inf every lane does so O(log n) times; starting from "the
@@ -230,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
                                                             const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
                                                             int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
                                                             float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells,
-                                                            float* __restrict__ dk_out, int32_t* __restrict__ qcnt) {
+                                                            float* __restrict__ dk_out, int32_t* __restrict__ qcnt, int32_t* __restrict__ qrank) {
     // housekeeping for the launches that follow
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < (int)(sizeof(SearchCounters) / 4); i += gridDim.x * kBlock) ((int32_t*)ctr)[i] = 0;
     if (ug_cnt) for (int i = blockIdx.x * kBlock + threadIdx.x; i < ug_cells; i += gridDim.x * kBlock) ug_cnt[i] = 0;
@@ -259,7 +309,7 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
     }
     if (live && sub == 0) {
         cand_cnt[qi] = 0;                                     // the query's candidate list starts empty
-        if (qcnt) atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);     // the query order's counts
+        if (qcnt) qrank[qi] = atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);     // the query order's counts, and this query's place in its cell
     }
     if (!seeded) { if (live && sub == 0) { gthr[qi] = 0xFFFFFFFFu; dk_out[qi] = INFINITY; } return; }       // +inf: no hint
     const int nx = prep->nx, ny = prep->ny, nz = prep->nz;
@@ -426,14 +476,16 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
 }
 
 // ---- S4. the unproven queries again, exactly: ONE launch --------------------------------------------------------
-// few (<= kFew): work item = (listed query, slice of the model); all threads of a workgroup stride over the slice.
+// few (<= kFew): work item = listed query, one workgroup each.  Its threads test the tile boxes against the query POINT with
+// the rule of DESIGN 4.1 (D = the query's own dk: two real model points lie within it, every row of a skipped tile is
+// strictly farther), and each wave scans the surviving tiles among the 64 it tested, over the sorted copy, ranking by
+// (distance, perm[row]).  No partials cross workgroups.
 // many: work item = (tile of kTailQ listed queries, chunk of the model); a lane owns four queries, the chunk streams
-// through LDS -- knn2_points_kernel's loop (6 VALU per pair, the oracle's bits).
-// Either way the workgroup that delivers the LAST partial of a query / tile (an arrival counter, cleared by S1) merges
-// the partials by (distance, index) and writes the result.  Partials cross workgroups through device-coherent accesses
-// (relaxed agent-scope atomic stores / loads) and a relaxed counter: no agent-scope fence (it would write back / invalidate
-// the XCD's L2).
-constexpr int kFew = 1024, kFbSlices = 32;
+// through LDS -- knn2_points_kernel's loop (6 VALU per pair, the oracle's bits).  The workgroup that delivers the LAST
+// partial of a tile (an arrival counter, cleared by S1) merges the partials by (distance, index) and writes the result.
+// Partials cross workgroups through device-coherent accesses (relaxed agent-scope atomic stores / loads) and a relaxed
+// counter: no agent-scope fence (it would write back / invalidate the XCD's L2).
+constexpr int kFew = 1024;
 constexpr int kTailGrid = 2048, kTailQ = 4 * kBlock;              // tiled form: 1024 queries per tile
 struct Top2 { float d1, d2; int i1, i2; };
 __device__ __forceinline__ void top2_insert(Top2& t, float d, int j) {
@@ -457,9 +509,10 @@ __device__ __forceinline__ void top2_wave_merge(float& d1, float& d2, int& i1, i
     }
 }
 __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
-    const float* __restrict__ q, int ldq, const float* __restrict__ m, int M, int ldm, int idx_base,
+    const float* __restrict__ q, int ldq, const float* __restrict__ m, int M, int ldm, const float* __restrict__ ms /* sorted copy, ld = M */,
+    const int32_t* __restrict__ perm, const float* __restrict__ tbox, const float* __restrict__ dk, int idx_base,
     const int32_t* __restrict__ flag_list, SearchCounters* __restrict__ ctr,
-    int32_t* __restrict__ part_idx, float* __restrict__ part_dist /* few: [kFew][kFbSlices][2]; many: [S][tiles * kTailQ][2] */,
+    int32_t* __restrict__ part_idx, float* __restrict__ part_dist /* many: [S][tiles * kTailQ][2] */,
     int32_t* __restrict__ idx, float* __restrict__ dist) {
     const int nf = ctr->n_flag;
     if (nf <= 0) return;
@@ -467,47 +520,62 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
     __shared__ int si[kBlock / 64][2];
     __shared__ int s_last;
     __shared__ float4 tile[kMTile];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (nf <= kFew) {
-        const int len = (M + kFbSlices - 1) / kFbSlices;
-        for (int w = blockIdx.x; w < nf * kFbSlices; w += gridDim.x) {
-            const int f = w / kFbSlices, sl = w % kFbSlices;
-            const int j0 = sl * len, j1 = min(M, j0 + len);
+        const int n_tiles = (M + kT16 - 1) / kT16;
+        for (int f = blockIdx.x; f < nf; f += gridDim.x) {
             const int qi = flag_list[f];
             const float qx = q[qi], qy = q[qi + (size_t)ldq], qz = q[qi + 2 * (size_t)ldq];
+            // DESIGN 4.1's rule with the block box shrunk to the query itself and D its own seed distance: two real model
+            // points lie within D, every row of a skipped tile is strictly farther.  No finite D, or a coordinate that
+            // is not finite: every tile is scanned.
+            const float D = dk[qi];
+            const bool cullq = D < INFINITY && fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;
+            const double qd[3] = {(double)qx, (double)qy, (double)qz};
             float d1 = INFINITY, d2 = INFINITY; int i1 = -1, i2 = -1;
-            for (int j = j0 + threadIdx.x; j < j1; j += kBlock) {     // ascending j per thread: strict '<' keeps ties low
-                float dx = qx - m[j], dy = qy - m[j + (size_t)ldm], dz = qz - m[j + 2 * (size_t)ldm];
-                float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                if (d < d2) { if (d < d1) { d2 = d1; i2 = i1; d1 = d; i1 = j; } else { d2 = d; i2 = j; } }
+            for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {            // each thread tests one tile, each wave scans its own survivors
+                const int ct = c0 + threadIdx.x;
+                bool visit = ct < n_tiles;
+                if (visit && cullq) {
+                    const float* bx = tbox + (size_t)ct * 6;
+                    double g2 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double gap = fmax(0.0, fmax((double)bx[c] - qd[c], qd[c] - (double)bx[3 + c]));
+                        g2 += gap * gap;
+                    }
+                    const double u = 5.9604644775390625e-08;
+                    if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D) visit = false;
+                }
+                unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
+                while (bal != 0) {
+                    const int t = c0 + wave * 64 + (int)__builtin_ctzll(bal);
+                    bal &= bal - 1;
+#pragma unroll
+                    for (int r = 0; r < kT16 / 64; ++r) {
+                        const int j = t * kT16 + r * 64 + lane;
+                        if (j < M) {
+                            float dx = qx - ms[j], dy = qy - ms[j + (size_t)M], dz = qz - ms[j + 2 * (size_t)M];
+                            float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                            if (d <= d2 && d < INFINITY) {             // (distance, ORIGINAL row) order; +inf is never an answer
+                                const int oj = perm[j];
+                                if (lex_lt_f(d, oj, d2, i2)) {
+                                    if (lex_lt_f(d, oj, d1, i1)) { d2 = d1; i2 = i1; d1 = d; i1 = oj; } else { d2 = d; i2 = oj; }
+                                }
+                            }
+                        }
+                    }
+                }
             }
             top2_wave_merge(d1, d2, i1, i2);
             __syncthreads();                                          // the previous trip's readers are done with sd / si
             if (lane == 0) { sd[wave][0] = d1; sd[wave][1] = d2; si[wave][0] = i1; si[wave][1] = i2; }
             __syncthreads();
             if (threadIdx.x == 0) {
-                Top2T<float> t{INFINITY, INFINITY, -1, -1};
-                for (int k = 0; k < kBlock / 64; ++k) { top2_insert_lex_t(t, sd[k][0], si[k][0]); top2_insert_lex_t(t, sd[k][1], si[k][1]); }
-                const size_t o = ((size_t)f * kFbSlices + sl) * 2;
-                __hip_atomic_store(&part_idx[o], t.i1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&part_idx[o + 1], t.i2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&part_dist[o], t.d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&part_dist[o + 1], t.d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the four stores above are complete (and device-coherent)
-                const int old = __hip_atomic_fetch_add(&ctr->done[f], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == kFbSlices - 1) {                            // every slice of this query is in: merge
-                    Top2T<float> r{INFINITY, INFINITY, -1, -1};
-                    for (int s2 = 0; s2 < kFbSlices; ++s2) {
-                        const size_t p = ((size_t)f * kFbSlices + s2) * 2;
-                        const int a = __hip_atomic_load(&part_idx[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const int b = __hip_atomic_load(&part_idx[p + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const float da = __hip_atomic_load(&part_dist[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const float db = __hip_atomic_load(&part_dist[p + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        top2_insert_lex_t(r, da, a); top2_insert_lex_t(r, db, b);
-                    }
-                    idx[(size_t)qi * 2] = r.i1 >= 0 ? r.i1 + idx_base : -1; idx[(size_t)qi * 2 + 1] = r.i2 >= 0 ? r.i2 + idx_base : -1;
-                    dist[(size_t)qi * 2] = r.d1; dist[(size_t)qi * 2 + 1] = r.d2;
-                }
+                Top2T<float> r{INFINITY, INFINITY, -1, -1};
+                for (int k = 0; k < kBlock / 64; ++k) { top2_insert_lex_t(r, sd[k][0], si[k][0]); top2_insert_lex_t(r, sd[k][1], si[k][1]); }
+                idx[(size_t)qi * 2] = r.i1 >= 0 ? r.i1 + idx_base : -1; idx[(size_t)qi * 2 + 1] = r.i2 >= 0 ? r.i2 + idx_base : -1;
+                dist[(size_t)qi * 2] = r.d1; dist[(size_t)qi * 2 + 1] = r.d2;
             }
         }
         return;
@@ -679,8 +747,13 @@ SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     s.ctr = w.take_bytes(align_up(sizeof(SearchCounters), 256));
     s.gthr = w.take<unsigned>(qq); s.flag_list = w.take<int32_t>(qq); s.cand_cnt = w.take<int32_t>(qq);
     s.cand_ent = w.take_bytes(align_up(qq * (size_t)(kF16MaxS * KC) * 8, 256));      // the call may see a smaller M than the sizing did
-    const size_t few = (size_t)kFew * kFbSlices * 2, many = (size_t)(kTailGrid + (qq + kTailQ - 1) / kTailQ) * kTailQ * 2;
-    s.tail_idx = w.take<int32_t>(std::max(few, many)); s.tail_dist = w.take<float>(std::max(few, many));
+    // The tail's partials (many-form only; the few-form keeps none) and the visit plan (knn_plan_kernel: per query block the
+    // number of tiles to visit, then their ascending list) share one slot: the plan is dead once the candidate kernel has run,
+    // two launches before the tail writes a partial.
+    const size_t many = (size_t)(kTailGrid + (qq + kTailQ - 1) / kTailQ) * kTailQ * 2;
+    const size_t plan_head = align_up((size_t)q_blocks * 4, 256) / 4, plan = plan_head + (size_t)q_blocks * std::max<size_t>(n_f16_tiles(M), 1);
+    s.tail_idx = w.take<int32_t>(std::max(many, plan)); s.tail_dist = w.take<float>(many);
+    s.n_vis = s.tail_idx; s.vis_list = s.tail_idx ? s.tail_idx + plan_head : nullptr;
     s.ug_cells = (int)ug_cells_cap(Q);
     s.ug_nparts = (int)((qq * 8 + kBlock - 1) / kBlock);
     s.ug_prep = w.take_bytes(256);
@@ -707,16 +780,16 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     if (order) PCREG_HIP(hipMemsetAsync(s.qcnt, 0, (size_t)kQueryKeys * 4, st));
     hipLaunchKernelGGL(seed_query_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, (const int32_t*)v.seed_cnt,
                        (const float4*)v.seed_slots, (v.seeded && v.M > 0) ? 1 : 0, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr,
-                       grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr);
-    if (order) {
-        hipLaunchKernelGGL(exclusive_scan_1wg_kernel, dim3(1), dim3(1024), 0, st, s.qcnt, kQueryKeys);
-        hipLaunchKernelGGL(query_order_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, s.qcnt, s.qperm);
-    }
+                       grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr, s.flag_list);
+    // (a query's place inside its cell waits in flag_list, which is free until knn_finalize_kernel lists the unproven queries)
+    if (order)
+        hipLaunchKernelGGL(query_order_ranked_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep,
+                           (const int32_t*)s.qcnt, (const int32_t*)s.flag_list, s.qperm);
     int W = 1;
     const int variant = PCREG_EXP_ENV("PCREG_KNN_VARIANT", 40);      // 41: timing-only form of the candidate kernel (EXPERIMENTS builds)
     const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS workgroups)
     const int cull = (debug_flag(kDbgKnnNoCull) || PCREG_EXP_ENV("PCREG_KNN_NOCULL", 0)) ? 0 : 1;    // "knn_nocull": visit every tile
-    int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, cull, s.gthr, s.cand_ent, s.cand_cnt, ctr,
+    int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, cull, s.n_vis, s.vis_list, s.gthr, s.cand_ent, s.cand_cnt, ctr,
                                        target_env > 0 ? target_env : kTargetBlocks, variant == 41, timed, grid ? s.ug_part : nullptr,
                                        s.ug_nparts, s.ug_cells, grid ? s.ug_prep : nullptr, &W, st);
     if (rc) return rc;
@@ -738,8 +811,8 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
         fprintf(stderr, "[pcreg] knn fast: Q=%d M=%d W=%d unproven=%d visited tile pairs=%lld of %lld (%.4f)%s\n", Q, v.M, W, nf, nv, qb * nt,
                 qb * nt > 0 ? (double)nv / (double)(qb * nt) : 0.0, cull ? "" : " (culling off)");
     }
-    hipLaunchKernelGGL(knn_tail_kernel, dim3(kTailGrid), dim3(kBlock), 0, st, q, ldq, v.m, v.M, v.ldm, (int)idx_base, (const int32_t*)s.flag_list, ctr,
-                       s.tail_idx, s.tail_dist, idx, dist);
+    hipLaunchKernelGGL(knn_tail_kernel, dim3(kTailGrid), dim3(kBlock), 0, st, q, ldq, v.m, v.M, v.ldm, (const float*)v.ms, (const int32_t*)v.perm,
+                       (const float*)v.tbox, (const float*)s.dk, (int)idx_base, (const int32_t*)s.flag_list, ctr, s.tail_idx, s.tail_dist, idx, dist);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -123,7 +123,7 @@ struct SearchCounters {
     int32_t finished;                // ... and how many of its workgroups are through (the last one clears ticket / status again)
     int32_t pad[29];
     int32_t visited[kVisitSlots];    // (query block, model tile) pairs the candidate kernel scored, spread over words by workgroup
-    int32_t done[kMaxQTiles];        // tail: arrivals per listed query (few) or per tile of listed queries (many)
+    int32_t done[kMaxQTiles];        // tail (many-form): arrivals per tile of listed queries
     int32_t status[kMatchMaxBlocks]; // match_finish_kernel: per-workgroup kept counts (ready bit 31)
 };
 

@@ -133,6 +133,102 @@ __device__ void ug_reduce_boxes(const float* __restrict__ part /*[n][6]*/, int n
     }
 }
 
+// ---- the visit plan: ONE workgroup per query block ------------------------------------------------------------------
+// What the block's box and largest seed distance cannot rule out (culling), computed once per block: the
+// ascending list of the tiles to visit, vis_list[qb * n_tiles + 0 .. n_vis[qb]), and their number.  The candidate kernel's
+// workgroups share the list: workgroup w of the block's first W_eff = plan_live(n_vis, W) walks positions w, w + W_eff, ..
+// and the others leave after reading n_vis.  kPlanC is the tiles-per-workgroup target that sizes W_eff.
+#ifndef PCREG_PLAN_C
+#define PCREG_PLAN_C 4
+#endif
+constexpr int kPlanC = PCREG_PLAN_C;
+__host__ __device__ __forceinline__ int plan_live(int n_vis, int W) {          // live workgroups of a block; 0: nothing to visit
+    if (n_vis <= 0) return 0;
+    const int we = (n_vis + kPlanC - 1) / kPlanC;
+    return we < W ? we : W;
+}
+__global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
+                                                          const float* __restrict__ dk, const float* __restrict__ tbox, int n_tiles, int cull,
+                                                          const Prep* __restrict__ prep, int32_t* __restrict__ n_vis,
+                                                          int32_t* __restrict__ vis_list, SearchCounters* __restrict__ ctr) {
+    __shared__ float s_red[kBlock / 64][8], s_box[8];
+    __shared__ int s_wcnt[kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qb = (int)blockIdx.x;
+    const float sg = prep->sigma, cx = prep->cx, cy = prep->cy, cz = prep->cz;
+    const bool scale_ok = scale_usable(prep);
+    // the block's box and largest seed distance over its SCORED queries (the candidate kernel's own test: a query it does
+    // not score has no say); an unseeded query (+inf) turns culling off for the block
+    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY}, bdk = 0.0f;
+#pragma unroll
+    for (int g = 0; g < 512 / kBlock; ++g) {
+        const int slot = qb * 512 + g * kBlock + tid;
+        if (slot < Q) {
+            const int qi = qperm[slot];
+            const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
+            const float sx = sg * (px - cx), sy = sg * (py - cy), sz = sg * (pz - cz);
+            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
+                blo[0] = fminf(blo[0], px); blo[1] = fminf(blo[1], py); blo[2] = fminf(blo[2], pz);
+                bhi[0] = fmaxf(bhi[0], px); bhi[1] = fmaxf(bhi[1], py); bhi[2] = fmaxf(bhi[2], pz);
+                const float e = dk[qi];
+                bdk = e < INFINITY ? fmaxf(bdk, e) : INFINITY;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { blo[c] = fminf(blo[c], __shfl_xor(blo[c], o)); bhi[c] = fmaxf(bhi[c], __shfl_xor(bhi[c], o)); }
+        bdk = fmaxf(bdk, __shfl_xor(bdk, o));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s_red[wave][c] = blo[c]; s_red[wave][3 + c] = bhi[c]; }
+        s_red[wave][6] = bdk;
+    }
+    __syncthreads();
+    if (tid < 7) {
+        float v = s_red[0][tid];
+#pragma unroll
+        for (int k = 1; k < kBlock / 64; ++k) v = tid < 3 ? fminf(v, s_red[k][tid]) : fmaxf(v, s_red[k][tid]);
+        s_box[tid] = v;
+    }
+    __syncthreads();
+    const float bdk_b = s_box[6];
+    int32_t* list = vis_list + (size_t)qb * n_tiles;
+    int n = 0;
+    // rounds of kBlock tiles: each thread tests one, the visited ones are appended in ascending order
+    for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {
+        const int ct = c0 + tid;
+        bool visit = ct < n_tiles;
+        if (visit && cull != 0 && bdk_b < INFINITY) {
+            // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to
+            // any point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of
+            // 32u, and no bound at all below 1e-30 (subnormal squares)
+            const float* bx = tbox + (size_t)ct * 6;
+            double g2 = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
+                g2 += gap * gap;
+            }
+            const double u = 5.9604644775390625e-08;
+            if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b) visit = false;
+        }
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
+        if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
+        __syncthreads();
+        int base = n;
+#pragma unroll
+        for (int k = 0; k < kBlock / 64; ++k) { base += k < wave ? s_wcnt[k] : 0; n += s_wcnt[k]; }
+        if (visit) list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
+        __syncthreads();                          // s_wcnt is rewritten in the next round
+    }
+    if (tid == 0) {
+        n_vis[qb] = n;
+        if (n > 0) atomicAdd(&ctr->visited[qb % kVisitSlots], n);       // (block, tile) pairs the candidate kernel scores
+    }
+}
+
 // ---- the candidate kernel: software-pipelined ------------------------------------------------------
 // Round 1's loop (git history: knn_candidates_f16_kernel) issued MFMA -> (wait for it) -> min tree -> compare -> branch, so inside one wave the matrix
 // pipe and the VALU strictly alternate (the ISA shows `v_mfma ... s_nop 9 ... v_min3 x8 ... v_cmp ... s_cbranch`)
@@ -155,23 +251,26 @@ __device__ void ug_reduce_boxes(const float* __restrict__ part /*[n][6]*/, int n
 // cross the back edge (tests/test_isa_lint.py checks the emitted ISA for a VGPR read between load and wait).
 template <int QG, bool DRY>   // DRY: timing only (no compare, no lists; PCREG_KNN_VARIANT=41)
 __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2 ? 5 : (QG <= 4 ? 4 : 2)))) void knn_candidates_f16_pipe_kernel(
-    const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm, const float* __restrict__ dk,
-    const uint4* __restrict__ mt, const float* __restrict__ tbox, int n_tiles, int W, int cull,
+    const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
+    const uint4* __restrict__ mt, const int32_t* __restrict__ n_vis, const int32_t* __restrict__ vis_list, int n_tiles, int W,
     const Prep* __restrict__ prep, unsigned* __restrict__ gthr, uint2* __restrict__ cand_ent, int32_t* __restrict__ cand_cnt,
-    int cap, SearchCounters* __restrict__ ctr, const float* __restrict__ ug_part, int ug_nparts, int ug_cells, UgPrep* __restrict__ ug_prep) {
+    int cap, const float* __restrict__ ug_part, int ug_nparts, int ug_cells, UgPrep* __restrict__ ug_prep) {
     static_assert(QG % 2 == 0, "two accumulator tiles alternate: an even number of steps per sub-tile");
     if (blockIdx.x == gridDim.x - 1 && ug_prep != nullptr) {     // the surplus workgroup (the launcher adds it): query-grid geometry
         ug_reduce_boxes(ug_part, ug_nparts, Q, ug_cells, ug_prep);
         return;
     }
+    // workgroup w of query block qb walks positions w, w + W_eff, w + 2 W_eff, .. of the block's visit plan (knn_plan_kernel);
+    // the grid is sized for the exhaustive walk, and a workgroup the plan does not need leaves here, after one word.  With
+    // nothing culled W_eff = W and position = tile (W is a multiple of 8 from 8 on: workgroup b runs on XCD b % 8, so an
+    // XCD reads one eighth of the model, as the chunks did)
+    const int qb = (int)blockIdx.x / W, w = (int)blockIdx.x % W;
+    const int nvis = n_vis[qb], W_eff = plan_live(nvis, W);
+    if (w >= W_eff) return;
     __shared__ __attribute__((aligned(16))) uint4 tile[2][2 * kT16];
-    __shared__ float s_red[kBlock / 64][8], s_box[8];
-    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
+    __shared__ int s_list[kBlock];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, half = lane >> 5;
-    // workgroup w of query block qb walks the block's visited tiles among w, w + W, w + 2W, ..  (W is a multiple of 8 from
-    // 8 on: workgroup b runs on XCD b % 8, so with nothing culled an XCD reads one eighth of the model, as the chunks did)
-    const int qb = (int)blockIdx.x / W, w = (int)blockIdx.x % W;
     // query SLOTS: the call's queries in spatial order (qperm), so that the 512 slots of a block are compact in space
     const int q_base = (qb * (kBlock / 64) + wave) * (QG * 32);
     const float sg = prep->sigma, inv2 = prep->inv_sigma2, sg2 = sg * sg;
@@ -181,7 +280,6 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
     float thr[QG];
     unsigned gseen[QG];
     Cand cand[QG];
-    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY}, bdk = 0.0f;
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
         const int slot = q_base + g * 32 + col;
@@ -192,13 +290,9 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
             const float sx = sg * (px - prep->cx), sy = sg * (py - prep->cy), sz = sg * (pz - prep->cz);
             // a query far outside the prepared model's box (or not finite), or any query of a model whose scale leaves fp32
             // (scale_usable), is not scored here: all-zero operands, no list entries; knn_finalize_kernel applies the same
-            // test and sends it to the exact fallback
+            // test and sends it to the exact fallback (and knn_plan_kernel leaves it out of the block's box)
             if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
                 X = -2.0f * sx; Y = -2.0f * sy; Z = -2.0f * sz; one = 1.0f;
-                blo[0] = fminf(blo[0], px); blo[1] = fminf(blo[1], py); blo[2] = fminf(blo[2], pz);
-                bhi[0] = fmaxf(bhi[0], px); bhi[1] = fmaxf(bhi[1], py); bhi[2] = fmaxf(bhi[2], pz);
-                const float e = dk[qi];
-                bdk = e < INFINITY ? fmaxf(bdk, e) : INFINITY;         // an unseeded query turns culling off for the block
             }
         }
         _Float16 Xh, Xl, Yh, Yl, Zh, Zl;
@@ -209,27 +303,6 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         for (int k = 0; k < KC; ++k) { cand[g].s[k] = INFINITY; cand[g].i[k] = -1; }
         thr[g] = INFINITY; gseen[g] = 0xFFFFFFFFu;
     }
-    // the block's box and largest seed distance over its SCORED queries (culling); every workgroup of the
-    // block reduces the same 512 queries to the same values
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { blo[c] = fminf(blo[c], __shfl_xor(blo[c], o)); bhi[c] = fmaxf(bhi[c], __shfl_xor(bhi[c], o)); }
-        bdk = fmaxf(bdk, __shfl_xor(bdk, o));
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_red[wave][c] = blo[c]; s_red[wave][3 + c] = bhi[c]; }
-        s_red[wave][6] = bdk;
-    }
-    __syncthreads();
-    if (tid < 7) {                                // the block's values stay in LDS: registers are full in the hot loop
-        float v = s_red[0][tid];
-#pragma unroll
-        for (int k = 1; k < kBlock / 64; ++k) v = tid < 3 ? fminf(v, s_red[k][tid]) : fmaxf(v, s_red[k][tid]);
-        s_box[tid] = v;
-    }
-    __syncthreads();
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)&tile[0][0];
     int walked = 0;                               // tiles walked so far (the threshold refresh's cadence)
     const f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -240,37 +313,13 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mt + (size_t)(T) * (2 * kT16) + seg * 64 + lane), \
                                          (__attribute__((address_space(3))) void*)(&tile[BUF][seg * 64]), 16, 0, 0);   \
     }
-    // rounds of kBlock candidate tiles: each thread tests one, the visited ones are listed in LDS in ascending order
-    for (int c0 = w; c0 < n_tiles; c0 += W * kBlock) {
-    {
-        const int ct = c0 + W * tid;
-        bool visit = ct < n_tiles;
-        const float bdk_b = s_box[6];
-        if (visit && cull != 0 && bdk_b < INFINITY) {
-            // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to
-            // any point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of
-            // 32u, and no bound at all below 1e-30 (subnormal squares)
-            const float* bx = tbox + (size_t)ct * 6;
-            double g2 = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
-                g2 += gap * gap;
-            }
-            const double u = 5.9604644775390625e-08;
-            if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b) visit = false;
-        }
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-        if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int k = 0; k < kBlock / 64; ++k) base += k < wave ? s_wcnt[k] : 0;
-        if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
-    }
+    // rounds of kBlock plan positions: the tiles of this workgroup's positions are listed in LDS (ascending, as in the plan)
+    const int my_n = (nvis - w + W_eff - 1) / W_eff;
+    const int32_t* vlist = vis_list + (size_t)qb * n_tiles;
+    for (int r0 = 0; r0 < my_n; r0 += kBlock) {
+    const int ntile = __builtin_amdgcn_readfirstlane(min(kBlock, my_n - r0));
+    if (tid < ntile) s_list[tid] = vlist[w + W_eff * (r0 + tid)];
     __syncthreads();
-    const int ntile = __builtin_amdgcn_readfirstlane(s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3]);
-    if (tid == 0 && ntile > 0) atomicAdd(&ctr->visited[blockIdx.x % kVisitSlots], ntile);
     if (ntile > 0) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[0]), 0) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -467,16 +516,20 @@ int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsi
 
 // The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it).  qperm: query
 // slot -> query row (spatial order); dk: each query's seed distance; tbox: the model tiles' boxes; cull = 0 visits every
-// tile.  ug_*: the query-grid by-product (null: none).  Returns W through W_out; list capacity per query = W * KC.
+// tile.  n_vis [q_blocks], vis_list [q_blocks * n_tiles]: the visit plan, written by knn_plan_kernel (launched here) and read
+// by the candidate kernel.  ug_*: the query-grid by-product (null: none).  Returns W through W_out; list capacity per
+// query = W * KC.
 int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
-                              const void* mtiles, const float* tbox, int cull, unsigned* gthr, void* cand_ent, int32_t* cand_cnt,
-                              void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part, int ug_nparts, int ug_cells,
-                              void* ug_prep, int* W_out, hipStream_t st) {
+                              const void* mtiles, const float* tbox, int cull, int32_t* n_vis, int32_t* vis_list, unsigned* gthr,
+                              void* cand_ent, int32_t* cand_cnt, void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part,
+                              int ug_nparts, int ug_cells, void* ug_prep, int* W_out, hipStream_t st) {
     int q_blocks, W;
     knn_f16_shape(Q, M, target_blocks, &q_blocks, &W);
     *W_out = W;
     if (M <= 0 || Q <= 0) return PCREG_OK;
     const int n_tiles = (M + kT16 - 1) / kT16;
+    hipLaunchKernelGGL(knn_plan_kernel, dim3(q_blocks), dim3(kBlock), 0, st, q, Q, ldq, qperm, dk, tbox, n_tiles, cull, (const Prep*)prep,
+                       n_vis, vis_list, (SearchCounters*)ctr);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_time_on && timed) {
         if (g_time_used == g_time_ev.size()) { hipEvent_t a, b; PCREG_HIP(hipEventCreate(&a)); PCREG_HIP(hipEventCreate(&b)); g_time_ev.emplace_back(a, b); }
@@ -485,8 +538,8 @@ int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qpe
     }
     const int aux = ug_prep != nullptr ? 1 : 0;
 #define PCREG_F16_LAUNCH(QGV, DRYV) hipLaunchKernelGGL((knn_candidates_f16_pipe_kernel<QGV, DRYV>), dim3(q_blocks * W + aux), dim3(kBlock), 0, st, q, Q, ldq, \
-                           qperm, dk, (const uint4*)mtiles, tbox, n_tiles, W, cull, (const Prep*)prep, gthr, (uint2*)cand_ent, cand_cnt, W * KC, \
-                           (SearchCounters*)ctr, ug_part, ug_nparts, ug_cells, (UgPrep*)ug_prep)
+                           qperm, (const uint4*)mtiles, (const int32_t*)n_vis, (const int32_t*)vis_list, n_tiles, W, (const Prep*)prep, gthr, \
+                           (uint2*)cand_ent, cand_cnt, W * KC, ug_part, ug_nparts, ug_cells, (UgPrep*)ug_prep)
 #ifdef PCREG_EXPERIMENTS
     if (dry) PCREG_F16_LAUNCH(4, true); else
 #endif
