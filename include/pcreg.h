@@ -85,7 +85,9 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * visits every model tile), "knn_stats" (counters for pcreg_debug_knn_stats), "ransac_pass2" (the staged RANSAC
  * chain's second scoring pass: 1 always the full pass, 2 always the bounded pass where allowed; 0 chooses by shape),
  * "ransac_stats" (counters for pcreg_debug_ransac_stats), "range_sort_cap" (n > 0: the radius search orders segments longer
- * than n rows by its in-place large-segment path); value 0 restores the default.  The library reads NO
+ * than n rows by its in-place large-segment path), "cluster_noskip" (the clustering walk unites on every hit instead of
+ * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats); value 0
+ * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
 /* With pcreg_debug_set("match_stats", 1): the counters of the certified SAD matcher summed over the calls since the last
@@ -103,6 +105,11 @@ int  pcreg_debug_knn_stats(long long out[4], int reset);
  * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
  * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */
 int  pcreg_debug_ransac_stats(long long out[3], int reset);
+/* With pcreg_debug_set("cluster_stats", 1): the counters of the clustering walk summed over the calls since the last reset --
+ * out[0] calls, [1] hits (scored row pairs within the radius), [2] compare-and-swap attempts on the union-find, [3] attempts
+ * that failed (another lane had merged first).  Off: no extra work.  The read synchronises the device.  (The walk's visited and
+ * nominal (tile, tile) pairs are counted by "knn_stats".) */
+int  pcreg_debug_cluster_stats(long long out[4], int reset);
 
 /* ---- host tier ------------------------------------------------------------------ */
 
@@ -158,6 +165,7 @@ int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M
 typedef struct pcreg_model pcreg_model;
 int pcreg_model_create(const float* m, int M, int ldm, pcreg_model** model);
 int pcreg_model_destroy(pcreg_model* model);
+int pcreg_model_size(const pcreg_model* model, int* M);         /* the number of rows the handle was created with */
 int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int ldq, float thr_abs, float max_ratio,
                                  int unique, uint32_t* pairs, int* P);
 /* MATLAB's [Idx, D] = knnsearch(model, q, 'K', k) / findNearestNeighbors(ptCloud, p, K) against the handle: for each query the
@@ -179,6 +187,18 @@ int pcreg_model_range_f32(pcreg_model* model, const float* q, int Q, int ldq, fl
 /* The same without a handle (rangesearch(m, q, r)): uploads and prepares the model for this call only. */
 int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float r2, int64_t capacity,
                            int64_t* seg_off, int32_t* idx, float* dist);
+/* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
+ * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
+ * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
+ * finite rows passes).  A row with a non-finite coordinate has no neighbour and is a cluster of its own.  Clusters are numbered
+ * 0, 1, .. in ascending order of their smallest row.  label [M]: the cluster of every row; *n_clusters their number (0 for
+ * M = 0).  cl_off [M + 1] / members [M] (both or neither may be NULL; with M = 0 label and members may be): the clusters in CSR form, cluster c is
+ * members[cl_off[c] .. cl_off[c + 1]), 0-based rows ascending; cl_off[0 .. n_clusters] is written.  Exact and deterministic: a
+ * function of (model rows, r2) only.  r2 NaN or negative: PCREG_E_ARG. */
+int pcreg_model_cluster_f32(pcreg_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off, int32_t* members);
+/* The same without a handle (clusterPoints(m, r)): uploads and prepares the cloud for this call only. */
+int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off,
+                             int32_t* members);
 
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
@@ -420,6 +440,18 @@ int pcreg_dev_model_range_count_f32(const pcreg_dev_model* model, const float* q
 int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2, int32_t idx_base,
                                    const int64_t* seg_off, int64_t capacity, int32_t* idx, float* dist,
                                    void* workspace, size_t workspace_bytes, void* stream);
+/* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
+ * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain
+ * (DESIGN 4.11).  label [M], indexed by ORIGINAL row: the 0-based number of the row's cluster, clusters numbered in ascending
+ * order of their smallest row.  n_clusters: one int32 on the device.  first / sizes ([M] each, either may be NULL): first[c]
+ * the smallest row of cluster c and sizes[c] its number of rows for c < n_clusters, ZERO at and past n_clusters.  The result
+ * is a function of (model rows, r2) only.  Nothing synchronises; no workgroup waits for another.  r2 NaN or negative:
+ * PCREG_E_ARG.  Workspace: 2 * roundup(4 * max(M, 1), 256) + roundup(4 * max(ceil(M / 2048), 1), 256) bytes, whatever r2 and
+ * the result.  Tile pairs are skipped by DESIGN 4.1's rule with the radius as the bound.  A handle may serve several streams at
+ * once, each call with its own workspace. */
+size_t pcreg_dev_model_cluster_workspace(int M);
+int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first,
+                                int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

@@ -14,6 +14,11 @@
 //   'modelRange', handle, queries (single Q x 3), r      -> counts (Q x 1 int32), idx (total x 1 int32, 1-based), D2 (total x 1 single,
 //                                          squared): query i's rows follow those of the queries before it, ordered by (distance, row)
 //                                          (rangesearch(model, Y, r) against the handle; matlab/rangesearchModel.m)
+//   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
+//                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
+//                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
+//                                          "distance <= r", numbered by their smallest row (clusterPoints.m:16-45;
+//                                          matlab/clusterPointsModel.m, matlab/clusterPointsFast.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -55,6 +60,32 @@ static bool field_is(const mxArray* s, const char* name, const char* value) {
     if (!f || !mxIsChar(f)) return false;
     char buf[64]; mxGetString(f, buf, sizeof buf);
     return strcmp(buf, value) == 0;
+}
+
+// r of the radius commands: a real double or single scalar >= 0 (NaN refused)
+static bool radius_ok(const mxArray* a) {
+    return (mxIsDouble(a) || mxIsSingle(a)) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 0.0;
+}
+// the three outputs of 'modelCluster' / 'clusterPoints': label (M x 1 int32, 1-based), clOff (C + 1 int32), members (M x 1 int32,
+// 1-based); single(r) is squared once, in single.  Nothing is left allocated on an error.
+static int cluster_on_handle(pcreg_model* h, float r, mxArray* out[3]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    mxArray* ol = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    mxArray* om = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    mxArray* bo = mxCreateNumericMatrix((size_t)M + 1, 1, mxINT32_CLASS, mxREAL);
+    int32_t *lab = (int32_t*)mxGetData(ol), *mem = (int32_t*)mxGetData(om), *off = (int32_t*)mxGetData(bo);
+    int32_t nc = 0;
+    rc = pcreg_model_cluster_f32(h, r * r, lab, &nc, off, mem);
+    if (rc == PCREG_OK) {
+        for (int i = 0; i < M; ++i) { lab[i] += 1; mem[i] += 1; }
+        out[0] = ol; out[2] = om;
+        out[1] = mxCreateNumericMatrix((size_t)nc + 1, 1, mxINT32_CLASS, mxREAL);
+        memcpy(mxGetData(out[1]), off, ((size_t)nc + 1) * sizeof(int32_t));
+    } else { mxDestroyArray(ol); mxDestroyArray(om); }
+    mxDestroyArray(bo);
+    return rc;
 }
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -461,6 +492,24 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 } else { mxDestroyArray(oi); mxDestroyArray(od); }
             }
             mxDestroyArray(so);
+        }
+    } else if (!strcmp(cmd, "modelCluster")) {                // [label, clOff, members] = pcreg_mex('modelCluster', h, r): clusterPoints(model, r)
+        if (nrhs != 3 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2])) usage = "modelCluster: handle (uint64), r (a real scalar >= 0)";
+        else {
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            rc = cluster_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (float)mxGetScalar(prhs[2]), out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "clusterPoints")) {               // [label, clOff, members] = pcreg_mex('clusterPoints', single(pts), r): clusterPoints(pts, r)
+        if (nrhs != 3 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !radius_ok(prhs[2])) usage = "clusterPoints: pts (single M x 3), r (a real scalar >= 0)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = cluster_on_handle(h, (float)mxGetScalar(prhs[2]), out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; }
         }
     } else if (!strcmp(cmd, "descCreate")) {                  // h = pcreg_mex('descCreate', desc): an n x D double descriptor set, uploaded ONCE
         if (nrhs != 2 || !mxIsDouble(prhs[1])) usage = "descCreate: desc (double n x D)";

@@ -52,14 +52,15 @@ class DevRansacResult(C.Structure):
 # every symbol include/pcreg.h declares (tests/test_abi.py checks the two lists agree)
 SYMBOLS = [
     "pcreg_last_error", "pcreg_version", "pcreg_device_count", "pcreg_set_device", "pcreg_device_name", "pcreg_debug_set", "pcreg_debug_match_stats",
-    "pcreg_debug_knn_stats", "pcreg_debug_ransac_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
+    "pcreg_debug_knn_stats", "pcreg_debug_ransac_stats", "pcreg_debug_cluster_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
     "pcreg_estimate_transform", "pcreg_calc_dists", "pcreg_ransac", "pcreg_ransac_batched",
     "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
-    "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
-    "pcreg_model_range_f32", "pcreg_range_points_f32",
+    "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_size", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
+    "pcreg_model_range_f32", "pcreg_range_points_f32", "pcreg_model_cluster_f32", "pcreg_cluster_points_f32",
     "pcreg_dev_model_create", "pcreg_dev_model_destroy", "pcreg_dev_model_search_workspace", "pcreg_dev_model_search_f32",
     "pcreg_dev_model_knn_workspace", "pcreg_dev_model_knn_f32", "pcreg_dev_merge_topk_f32",
     "pcreg_dev_model_range_workspace", "pcreg_dev_model_range_count_f32", "pcreg_dev_model_range_fill_f32",
+    "pcreg_dev_model_cluster_workspace", "pcreg_dev_model_cluster_f32",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
     "pcreg_align_points_knn", "pcreg_align_points_knn_f32", "pcreg_align_points_knn_batched", "pcreg_spatial_histogram_descriptors",
     "pcreg_spatial_histogram_descriptors_f32", "pcreg_spatial_histogram_descriptors_mixed",
@@ -115,6 +116,14 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_range_fill_f32.argtypes = [vp, vp, i, i, f, C.c_int32, vp, i64, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_range_f32.argtypes = [vp, vp, i, i, f, i64, vp, vp, vp]
             L.pcreg_range_points_f32.argtypes = [vp, i, i, vp, i, i, f, i64, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_model_cluster_workspace"):   # (an older build given through PCREG_LIB lacks the clustering)
+            L.pcreg_dev_model_cluster_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_cluster_workspace.argtypes = [C.c_int]
+            vp, i, f = C.c_void_p, C.c_int, C.c_float                            # (a float by value: declared)
+            L.pcreg_dev_model_cluster_f32.argtypes = [vp, f, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_cluster_f32.argtypes = [vp, f, vp, vp, vp, vp]
+            L.pcreg_cluster_points_f32.argtypes = [vp, i, i, f, vp, vp, vp, vp]
+            L.pcreg_debug_cluster_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
         for name, args in (("pcreg_debug_knn_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_ransac_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_dev_model_export", [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),

@@ -636,6 +636,26 @@ def rangesearch_points(query, model, r2: float):
                                                                                 so.ctypes.data, i, d)), Q)
 
 
+def _cluster_call(call, M: int):
+    label = np.zeros(max(M, 1), dtype=np.int32)
+    cl_off = np.zeros(M + 1, dtype=np.int32)
+    members = np.zeros(max(M, 1), dtype=np.int32)
+    nc = C.c_int32(0)
+    call(label.ctypes.data, C.byref(nc), cl_off.ctypes.data, members.ctypes.data)
+    return label[:M], cl_off[:nc.value + 1].copy(), members[:M]
+
+
+def cluster_points(pts, r2: float):
+    """clusterPoints(pts, r) in fp32 with r2 = r^2: (label [M] int32, cl_off [C + 1] int32, members [M] int32), 0-based.  The
+    clusters are the connected components of the graph "squared distance <= r2" over the rows, numbered in ascending order of
+    their smallest row; cluster c is members[cl_off[c] .. cl_off[c + 1]), ascending; a row with a non-finite coordinate is a
+    cluster of its own.  The cloud is prepared for this call only: keep a Model for repeated calls."""
+    r2 = _range_r2(r2)
+    m = _fcol(pts, np.float32)
+    M = m.shape[0]
+    return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_cluster_points_f32(m.ctypes.data, M, max(M, 1), r2, lab, nc, off, mem)), M)
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or
@@ -682,6 +702,14 @@ class Model:
         q = _fcol(query, np.float32)
         Q = q.shape[0]
         return _range_call(lambda cap, so, i, d: check(lib().pcreg_model_range_f32(self._h, q.ctypes.data, Q, max(Q, 1), r2, cap, so.ctypes.data, i, d)), Q)
+
+    def cluster(self, r2: float):
+        """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,
+        members [M] int32), 0-based -- cluster_points' contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_model_cluster_f32(self._h, r2, lab, nc, off, mem)), self.M)
 
     def close(self):
         if self._h.value:

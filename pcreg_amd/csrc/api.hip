@@ -83,7 +83,8 @@ static std::atomic<int> g_debug[kDbgCount];
 int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); }
 // one block of device counters behind a debug key: allocated (zeroed) at the first use while the key is on
 struct Counters { DebugKey key; int n; unsigned long long* dev; };
-static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 4, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr};
+static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 4, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr},
+                g_cluster_stats{kDbgClusterStats, 4, nullptr};
 static unsigned long long* counters_dev(Counters& c) {
     if (!debug_flag(c.key)) return nullptr;
     if (!c.dev) {
@@ -106,6 +107,7 @@ static int counters_read(const Counters& c, long long* out, int reset) {
 unsigned long long* match_stats_dev() { return counters_dev(g_match_stats); }
 unsigned long long* knn_stats_dev() { return counters_dev(g_knn_stats); }
 unsigned long long* ransac_stats_dev() { return counters_dev(g_ransac_stats); }
+unsigned long long* cluster_stats_dev() { return counters_dev(g_cluster_stats); }
 }
 
 extern "C" {
@@ -114,7 +116,8 @@ int pcreg_debug_set(const char* key, int value) {
     static const char* const names[pcreg::kDbgCount] = {"knn_exact", "match_exact", "match_force_fallback", "ransac_fused", "ransac_nolane",
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
-                                                        "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap"};
+                                                        "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap", "cluster_noskip",
+                                                        "cluster_stats"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -125,6 +128,7 @@ int pcreg_debug_set(const char* key, int value) {
 int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counters_read(pcreg::g_match_stats, out, reset); }
 int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset); }
 int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset); }
+int pcreg_debug_cluster_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_cluster_stats, out, reset); }
 
 const char* pcreg_last_error(void) { return g_err; }
 const char* pcreg_version(void) { return "pcreg-hip 0.1 (gfx950)"; }
@@ -367,6 +371,13 @@ int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q,
     return launch_model_range_fill(model->v, q, Q, ldq, r2, idx_base, seg_off, capacity, idx, dist, workspace, workspace_bytes,
                                    (hipStream_t)stream);
 }
+size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
+int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && label && n_clusters && workspace && r2 >= 0.0f);
+    GUARD();
+    return launch_model_cluster(model->v, r2, label, n_clusters, first, sizes, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -437,6 +448,11 @@ int pcreg_model_destroy(pcreg_model* model) {
     if (model->dm) { (void)hipFree(model->dm->block); delete model->dm; }
     (void)hipFree(model->d_m);
     delete model;
+    return PCREG_OK;
+}
+int pcreg_model_size(const pcreg_model* model, int* M) {
+    PCREG_ARG(model && M);
+    *M = model->M;
     return PCREG_OK;
 }
 int pcreg_model_match_points_f32(pcreg_model* model, const float* q, int Q, int ldq, float thr_abs, float max_ratio, int unique,
@@ -530,6 +546,52 @@ int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return range_on_view(st, v, q, Q, ldq, r2, capacity, seg_off, idx, dist);
+}
+
+// clusterPoints on a prepared model: label the rows on the device, read the labels back, and form the CSR lists on the host by
+// one stable counting pass (rows ascend inside a cluster because they are placed in ascending order)
+static int cluster_on_view(Stage& st, const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off, int32_t* members) {
+    const int M = v.M;
+    *n_clusters = 0;
+    if (cl_off) cl_off[0] = 0;
+    if (M == 0) return PCREG_OK;
+    int32_t *dl, *dn; char* ws;
+    const size_t wsb = cluster_ws_bytes(M);
+    TRY(st.take((size_t)M, &dl));
+    TRY(st.take(1, &dn));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_cluster(v, r2, dl, dn, nullptr, nullptr, ws, wsb, g_stream));
+    int32_t nc = 0;
+    PCREG_HIP(hipMemcpyAsync(label, dl, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(&nc, dn, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    *n_clusters = nc;
+    if (!cl_off) return PCREG_OK;
+    for (int c = 0; c <= nc; ++c) cl_off[c] = 0;
+    for (int i = 0; i < M; ++i) ++cl_off[label[i] + 1];
+    for (int c = 0; c < nc; ++c) cl_off[c + 1] += cl_off[c];
+    std::vector<int32_t> at(cl_off, cl_off + nc);
+    for (int i = 0; i < M; ++i) members[at[label[i]]++] = i;
+    return PCREG_OK;
+}
+int pcreg_model_cluster_f32(pcreg_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off, int32_t* members) {
+    PCREG_ARG(model && n_clusters && r2 >= 0.0f && (members || !cl_off || model->M == 0) && (cl_off || !members));
+    PCREG_ARG(model->dm != nullptr && (label || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return cluster_on_view(st, model->dm->v, r2, label, n_clusters, cl_off, members);
+}
+int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off, int32_t* members) {
+    PCREG_ARG(n_clusters && M >= 0 && ldm >= M && (M == 0 || (m && label)) && r2 >= 0.0f && (members || !cl_off || M == 0) && (cl_off || !members));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return cluster_on_view(st, v, r2, label, n_clusters, cl_off, members);
 }
 
 int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float thr_abs,

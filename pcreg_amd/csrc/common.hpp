@@ -87,6 +87,8 @@ enum DebugKey {
     kDbgRansacStats,           // "ransac_stats": the bounded pass counts what it scans (pcreg_debug_ransac_stats)
     kDbgRangeSortCap,          // "range_sort_cap": n > 0 -- the radius search orders segments longer than n rows by its in-place
                                // large-segment path (0 = the default capacity)
+    kDbgClusterNoSkip,         // "cluster_noskip": the clustering walk unites on every hit (no "same root" early-out)
+    kDbgClusterStats,          // "cluster_stats": the clustering walk counts hits and compare-and-swaps (pcreg_debug_cluster_stats)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -101,6 +103,9 @@ unsigned long long* knn_stats_dev();
 // Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
 //   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
 unsigned long long* ransac_stats_dev();
+// Device counters of the clustering walk (knn_cluster.hip), or null while "cluster_stats" is off:
+//   [0] calls   [1] hits   [2] compare-and-swap attempts   [3] failed attempts
+unsigned long long* cluster_stats_dev();
 #ifdef PCREG_EXPERIMENTS
 static inline int pcreg_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline const char* pcreg_env_str(const char* name) { return getenv(name); }
@@ -193,6 +198,10 @@ int launch_model_range_count(const ModelView& v, const float* q, int Q, int ldq,
                              size_t ws_bytes, hipStream_t st);
 int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, float r2, int32_t idx_base, const int64_t* seg_off,
                             int64_t capacity, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
+// connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
+size_t cluster_ws_bytes(int M);
+int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,
+                         size_t ws_bytes, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,

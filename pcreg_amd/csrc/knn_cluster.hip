@@ -1,0 +1,326 @@
+// pcreg_amd/csrc/knn_cluster.hip -- clusterPoints against a PREPARED model: the connected components of the graph in which
+// rows i != j are adjacent iff d = fmaf(dz,dz, fmaf(dy,dy, dx*dx)) <= r2, dx = m_i - m_j in fp32 (the point search's formula;
+// inclusive; a NaN distance never passes; +inf passes r2 = +inf).  A row with a non-finite coordinate has no neighbour.
+// Clusters are numbered in ascending order of their smallest row.  Exact and deterministic by construction.
+//
+// The prepared model (knn_fast.hip) is used as it is: the sorted copy, perm, the tile boxes.
+//   C1  cluster_init_kernel     parent[i] = i (original-row space), the outputs' tails cleared
+//   C2  cluster_walk_kernel     self-join: tile a's rows against every tile b >= a that DESIGN 4.1's rule (D = r2, the box of
+//                               tile a) does not rule out; four lanes per row; on the diagonal only j > i.  A hit unites the
+//                               two ORIGINAL rows in a lock-free union-find: the larger root is hooked under the smaller by a
+//                               compare-and-swap, find jumps pointers on its way.  No workgroup waits for another
+//   C3  cluster_flatten_kernel  parent[i] = root of i (its cluster's smallest row); the roots per chunk of 2048 rows
+//   C4  cluster_number_kernel   every chunk adds the chunks before it and scans its own root flags: the cluster number of every
+//                               root, first[], n_clusters
+//   C5  cluster_label_kernel    label[i] = number[parent[i]]; sizes[] by integer atomicAdd, one per (wave, cluster)
+#include "common.hpp"
+#include "knn_fast_common.hpp"
+#include <cmath>
+
+namespace pcreg {
+
+namespace {
+
+constexpr int kCLanes = 4;                           // lanes per row of tile a
+constexpr int kCRowsPerWg = kBlock / kCLanes;        // 64 rows per workgroup
+constexpr int kCWgPerTile = kT16 / kCRowsPerWg;      // 8 workgroups per tile a
+constexpr int kCChunk = 2048;                        // rows per workgroup of the numbering scan (256 threads x 8)
+static_assert(kT16 % kBlock == 0 && kT16 % (4 * kCLanes) == 0, "tile staging and the unrolled walk");
+
+#define PCREG_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+__device__ __forceinline__ float cluster_d2(float qx, float qy, float qz, float mx, float my, float mz) {
+    const float dx = qx - mx, dy = qy - my, dz = qz - mz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
+}
+
+// ---- the union-find over parent[] (original rows).  Invariant: parent[x] <= x, so the forest is acyclic and a set's root is
+// its smallest row.  Inside the walk every access is a relaxed agent-scope atomic; a stale value is still an ancestor.
+__device__ __forceinline__ int uf_load(int32_t* parent, int x) { return __hip_atomic_load(parent + x, PCREG_RLX_AGENT); }
+// the root of x; every node passed on the way is pointed at its grandparent (only ever an ancestor, only into non-root slots)
+__device__ __forceinline__ int uf_find(int32_t* parent, int x) {
+    int cur = uf_load(parent, x);
+    if (cur != x) {
+        int prev = x, next;
+        while (cur > (next = uf_load(parent, cur))) {
+            __hip_atomic_store(parent + prev, next, PCREG_RLX_AGENT);
+            prev = cur;
+            cur = next;
+        }
+    }
+    return cur;
+}
+// Merges the sets of a and b; returns their common root as of the merge.  A compare-and-swap succeeds only on a slot that is a
+// root at that instant; a failure means another lane hooked that root first, and the loop goes on from the value it wrote: the
+// number of iterations is bounded by the number of merges in the launch.  Nothing spins on anybody's progress.
+__device__ __forceinline__ int uf_unite(int32_t* parent, int a, int b, unsigned long long* stats) {
+    int ra = uf_find(parent, a), rb = uf_find(parent, b);
+    while (ra != rb) {
+        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+        int expected = hi;
+        const bool ok = __hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+        if (stats) { atomicAdd(&stats[2], 1ull); if (!ok) atomicAdd(&stats[3], 1ull); }
+        if (ok) return lo;
+        ra = uf_find(parent, expected);                            // hi had been hooked under `expected` (< hi)
+        rb = lo;
+    }
+    return ra;
+}
+
+// ---- C1 ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void cluster_init_kernel(int M, int32_t* __restrict__ parent, int32_t* __restrict__ first,
+                                                              int32_t* __restrict__ sizes) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M) return;
+    parent[i] = i;
+    if (first) first[i] = 0;
+    if (sizes) sizes[i] = 0;
+}
+
+// ---- C2. the walk -----------------------------------------------------------------------------------------------------
+// Workgroup (tile a, part p) owns sorted rows a * 512 + p * 64 + (tid >> 2); lane sub = tid & 3 of a row scores rows sub,
+// sub + 4, .. of every visited tile b >= a from LDS (x, y, z, original row).  Pair (a, b) is skipped iff G2 > 1e-30 &&
+// G2 (1 - 32u) > r2, G2 the squared gap between the two tile boxes, formed in double: every row pair of a skipped tile pair has
+// a computed d > r2 (DESIGN 4.1 with D = r2 and B = tile a's box).  Tile t + 1 is loaded into registers while tile t is scored.
+// A non-finite row is staged as NaN and its own lanes admit nothing, so it stays a set of its own whatever r2.
+__global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
+                                                              const float* __restrict__ tbox, int n_tiles, int cull, int skip_same, float r2,
+                                                              int32_t* parent, unsigned long long* __restrict__ stats,
+                                                              unsigned long long* __restrict__ cstats) {
+    __shared__ float4 tile[kT16];
+    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ta = blockIdx.x / kCWgPerTile, part = blockIdx.x % kCWgPerTile;
+    if (blockIdx.x == 0 && tid == 0) {
+        if (stats) {
+            atomicAdd(&stats[0], 1ull);
+            atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)(n_tiles + 1) / 2ull);
+        }
+        if (cstats) atomicAdd(&cstats[0], 1ull);
+    }
+    float abox[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
+    // this thread's row
+    const int sub = tid & (kCLanes - 1), rl = part * kCRowsPerWg + tid / kCLanes;      // the row's place inside tile a
+    const int srow = ta * kT16 + rl;
+    const bool in_model = srow < M;
+    const int sr = in_model ? srow : 0;
+    const float qx = ms[sr], qy = ms[sr + (size_t)M], qz = ms[sr + 2 * (size_t)M];
+    const int row_i = perm[sr];
+    const bool live = in_model && finite3(qx, qy, qz);
+    const float rr = live ? r2 : -1.0f;                           // (a dead lane admits nothing: d is never negative)
+    int my_root = row_i;                                          // the last root this lane saw for its row
+    unsigned long long n_hit = 0;
+    const float qnan = __int_as_float(0x7FC00000);                // padding and non-finite rows: d = NaN never passes d <= r2
+    // rounds of kBlock candidate tiles from ta on: each thread tests one, the visited ones are listed in LDS in ascending order
+    for (int c0 = ta; c0 < n_tiles; c0 += kBlock) {
+        __syncthreads();                                          // the previous round's list consumed
+        {
+            const int ct = c0 + tid;
+            bool visit = ct < n_tiles;
+            if (visit && cull != 0 && r2 < INFINITY) {
+                // gaps in double from the float boxes, a relative margin of 32u, no bound below 1e-30
+                const float* bx = tbox + (size_t)ct * 6;
+                double g2 = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double gap = fmax(0.0, fmax((double)bx[c] - (double)abox[3 + c], (double)abox[c] - (double)bx[3 + c]));
+                    g2 += gap * gap;
+                }
+                const double u = 5.9604644775390625e-08;
+                if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)r2) visit = false;
+            }
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
+            if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
+            __syncthreads();
+            int base = 0;
+#pragma unroll
+            for (int w = 0; w < kBlock / 64; ++w) base += w < wave ? s_wcnt[w] : 0;
+            if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
+        }
+        __syncthreads();
+        const int ntile = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        if (stats && part == 0 && tid == 0 && ntile > 0) atomicAdd(&stats[1], (unsigned long long)ntile);
+        constexpr int kRowsPerThread = kT16 / kBlock;
+        float4 pre[kRowsPerThread];
+        auto fetch = [&](int t) {
+            const int r0 = s_list[t] * kT16;
+#pragma unroll
+            for (int u = 0; u < kRowsPerThread; ++u) {
+                const int r = r0 + u * kBlock + tid;
+                pre[u] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
+                if (r < M) {
+                    const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
+                    if (finite3(x, y, z)) pre[u] = make_float4(x, y, z, __int_as_float(perm[r]));
+                }
+            }
+        };
+        if (ntile > 0) fetch(0);
+        for (int t = 0; t < ntile; ++t) {
+            __syncthreads();                                      // the previous tile's readers are done
+#pragma unroll
+            for (int u = 0; u < kRowsPerThread; ++u) tile[u * kBlock + tid] = pre[u];
+            const int above = s_list[t] == ta ? rl : -1;          // on the diagonal only the rows behind this one
+            __syncthreads();
+            if (t + 1 < ntile) fetch(t + 1);
+            for (int r = sub; r < kT16; r += 4 * kCLanes) {
+                float4 p[4]; float d[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    p[u] = tile[r + u * kCLanes];
+                    d[u] = cluster_d2(qx, qy, qz, p[u].x, p[u].y, p[u].z);
+                    d[u] = r + u * kCLanes > above ? d[u] : qnan;
+                }
+                if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (d[u] <= rr) {
+                            const int row_j = __float_as_int(p[u].w);
+                            ++n_hit;
+                            // one load: a row that already points at this lane's root is in its set (sets only merge)
+                            if (skip_same && uf_load(parent, row_j) == my_root) continue;
+                            my_root = uf_unite(parent, my_root, row_j, cstats);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (cstats && n_hit) atomicAdd(&cstats[1], n_hit);
+}
+
+// ---- C3. flatten: parent[i] = the root of i; the number of roots per chunk ----------------------------------------------
+// (the walk is a finished launch: its parent[] is visible.  A thread's store only replaces an ancestor of i by the root, so
+// the threads that pass through i in the same launch still reach the same root.)
+__global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t* parent, int32_t* __restrict__ csum) {
+    __shared__ int s[kBlock / 64];
+    const int base = blockIdx.x * kCChunk;
+    int v = 0;
+    for (int k = threadIdx.x; k < kCChunk; k += kBlock) {
+        const int i = base + k;
+        if (i < M) {
+            int r = uf_load(parent, i);
+            while (true) { const int n = uf_load(parent, r); if (n == r) break; r = n; }
+            __hip_atomic_store(parent + i, r, PCREG_RLX_AGENT);
+            v += r == i ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) csum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+
+// ---- C4. number the roots in row order --------------------------------------------------------------------------------
+// chunk c: the sum of the chunks before it, then thread t scans the root flags of its 8 consecutive rows behind the threads
+// before it; num[i] (roots only) = the roots before row i; the last chunk writes n_clusters
+__global__ __launch_bounds__(kBlock) void cluster_number_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ csum,
+                                                                int32_t* __restrict__ num, int32_t* __restrict__ first,
+                                                                int32_t* __restrict__ n_clusters) {
+    __shared__ int s[kBlock / 64], s_thr[kBlock];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int before = 0;
+    for (int c = tid; c < (int)blockIdx.x; c += kBlock) before += csum[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    if (lane == 0) s[wave] = before;
+    constexpr int kPer = kCChunk / kBlock;
+    const int i0 = blockIdx.x * kCChunk + tid * kPer;
+    int f[kPer], mine = 0;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) { f[u] = i0 + u < M && parent[i0 + u] == i0 + u ? 1 : 0; mine += f[u]; }
+    s_thr[tid] = mine;
+    __syncthreads();
+    int run = s[0] + s[1] + s[2] + s[3];
+    // exclusive scan of the 256 thread sums (Hillis-Steele in LDS)
+    for (int o = 1; o < kBlock; o <<= 1) {
+        const int add = tid >= o ? s_thr[tid - o] : 0;
+        __syncthreads();
+        s_thr[tid] += add;
+        __syncthreads();
+    }
+    run += s_thr[tid] - mine;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+        if (f[u]) { num[i0 + u] = run; if (first) first[run] = i0 + u; }
+        run += f[u];
+        if (i0 + u == M - 1) *n_clusters = run;
+    }
+}
+
+// ---- C5 ---------------------------------------------------------------------------------------------------------------
+// sizes: one atomicAdd per (wave, cluster) -- the lanes of a wave that share a cluster are counted by their leader.  Rows that
+// follow each other mostly share a cluster when clusters are large (a million single adds to ONE word took 11 ms), and when
+// they do not, the adds go to different words anyway.
+__global__ __launch_bounds__(kBlock) void cluster_label_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ num,
+                                                               int32_t* __restrict__ label, int32_t* __restrict__ sizes) {
+    const int i = blockIdx.x * kBlock + threadIdx.x, lane = threadIdx.x & 63;
+    const bool live = i < M;
+    int c = -1;
+    if (live) { c = num[parent[i]]; label[i] = c; }
+    if (!sizes) return;
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(live);
+    while (todo) {                                                // (wave-uniform: every lane sees the same todo)
+        const int lead = __ffsll((long long)todo) - 1;
+        const int cl = __shfl(c, lead);
+        const unsigned long long same = __builtin_amdgcn_ballot_w64(live && c == cl);
+        if (lane == lead) atomicAdd(&sizes[cl], (int)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// Workspace: [parent, M] [cluster number of every root, M] [roots per chunk of 2048 rows]:
+// 2 * roundup(4 * max(M, 1), 256) + roundup(4 * max(ceil(M / 2048), 1), 256) bytes, whatever r2 and the result
+struct ClusterWs { int32_t* parent; int32_t* num; int32_t* csum; };
+ClusterWs cluster_ws_layout(int M, void* base, size_t* bytes) {
+    ClusterWs s{};
+    const size_t mm = (size_t)(M > 0 ? M : 1);
+    WsWalk w(base);
+    s.parent = w.take<int32_t>(mm);
+    s.num = w.take<int32_t>(mm);
+    s.csum = w.take<int32_t>((mm + kCChunk - 1) / kCChunk);
+    *bytes = w.bytes();
+    return s;
+}
+
+}  // namespace
+
+size_t cluster_ws_bytes(int M) {
+    size_t b; (void)cluster_ws_layout(M, nullptr, &b);
+    return b;
+}
+
+int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(r2 >= 0.0f && n_clusters && (label || v.M == 0));
+    size_t need;
+    const ClusterWs s = cluster_ws_layout(v.M, ws, &need);
+    if (ws_bytes < need) { set_error("cluster workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
+    const int M = v.M;
+    if (M == 0) {                                                 // no cluster
+        PCREG_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), st));
+        return PCREG_OK;
+    }
+    const int n_tiles = (M + kT16 - 1) / kT16, chunks = (M + kCChunk - 1) / kCChunk, blocks = (M + kBlock - 1) / kBlock;
+    const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile pair, same bits
+    const int skip_same = debug_flag(kDbgClusterNoSkip) ? 0 : 1; // "cluster_noskip": unite on every hit, same bits
+    hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks), dim3(kBlock), 0, st, M, s.parent, first, sizes);
+    hipLaunchKernelGGL(cluster_walk_kernel, dim3((unsigned)(n_tiles * kCWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
+                       (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, skip_same, r2, s.parent, knn_stats_dev(),
+                       cluster_stats_dev());
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(chunks), dim3(kBlock), 0, st, M, s.parent, s.csum);
+    hipLaunchKernelGGL(cluster_number_kernel, dim3(chunks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.csum, s.num,
+                       first, n_clusters);
+    hipLaunchKernelGGL(cluster_label_kernel, dim3(blocks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.num, label,
+                       sizes);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+}  // namespace pcreg

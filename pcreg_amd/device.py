@@ -132,6 +132,33 @@ class PreparedModel:
             self.rangesearch_fill(q_soa, r2, seg_off, idx, dist, idx_base)
         return seg_off, idx, dist
 
+    def cluster(self, r2: float, out=None):
+        """clusterPoints(model, r) over the model's own rows with r2 = r^2, on torch's current stream
+        (pcreg_dev_model_cluster_f32): -> (label [M] int32, the 0-based cluster of every row; n_clusters [1] int32; first [M]
+        int32, first[c] the smallest row of cluster c; sizes [M] int32, sizes[c] its rows; both zero at and past n_clusters).
+        Clusters are numbered in ascending order of their smallest row.  Nothing synchronises.  The workspace is cached on the
+        model and grown on demand; calls that may overlap on two streams pass buffers of their own, out=(label, n_clusters,
+        first, sizes, ws) with ws of pcreg_dev_model_cluster_workspace(M) bytes."""
+        r2 = float(r2)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_cluster_workspace(M)), 256)
+        if out is not None:
+            label, n_clusters, first, sizes, ws = out
+        else:
+            label, first, sizes = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(3))
+            n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_cluster_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._cluster_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if M == 0:                                     # (an empty tensor has no address to pass)
+            n_clusters.zero_()
+            return label, n_clusters, first, sizes
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_cluster_f32(self.handle, r2, _p(label), _p(n_clusters), _p(first), _p(sizes), _p(ws), ws.numel(), _stream()))
+        return label, n_clusters, first, sizes
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             lib().pcreg_dev_model_destroy(self.handle)

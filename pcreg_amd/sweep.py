@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as _l
 from ._lib import RansacOpts, check, lib
-from .api import _match_opts, invertTF
+from .api import _match_opts, cluster_points, invertTF
 from .device import DescriptorPipeline, _p, _stream
 
 
@@ -368,6 +368,36 @@ class SphereSweep:
         for st, _, _ in self._lanes[:ns]:
             cur.wait_stream(st)
         return self._finish_sweep(centres, num_desc, row_off, rows_all, feat_all, n_sel, pairs_all, n_pairs, options, putative_thresh, seed)
+
+
+def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, thRatio: float = 10, thPutative: float = 170,
+                       r: float | None = None, d_spheres: float = 5.0) -> list:
+    """completeExperimentFast.m:238-248 and :266-288, the link from a sweep's result to FinalStage.run: keep the trials whose
+    statsSuccess / statsInliers / statsRatio (percent) / statsPutative reach the four thresholds, cluster their sphere centres
+    with radius r (default 1.6 * d_spheres, :266) in ONE cluster_points call, and for every cluster return (locCur, transCur):
+    locCur the mean of the cluster's centres in double, transCur the transform of the centre nearest to that mean (the first
+    one on a tie, as MATLAB's min).  -> [(locCur [3], transCur [4, 4])] in the clusters' order, [] without a good sphere.  A trial
+    whose RANSAC failed has no transform and is never kept."""
+    centres = np.asarray(result["centres"], dtype=np.float64).reshape(-1, 3)[np.asarray(result["trial"], dtype=np.int64)]
+    tf = result["transforms"]
+    mask = ((np.asarray(result["statsSuccess"]) >= thSucc) & (np.asarray(result["statsInliers"]) >= thInliers) &
+            (np.asarray(result["statsRatio"]) >= thRatio) & (np.asarray(result["statsPutative"]) >= thPutative) &
+            np.array([t is not None for t in tf], dtype=bool))
+    good = np.nonzero(mask)[0]                                                              # :239
+    if len(good) == 0:
+        return []
+    loc = centres[good]                                                                     # :247
+    r = 1.6 * float(d_spheres) if r is None else float(r)                                   # :266
+    r32 = np.float32(r)
+    _, cl_off, members = cluster_points(loc, r32 * r32)                                     # :267
+    out = []
+    for c in range(len(cl_off) - 1):
+        rows = members[cl_off[c]:cl_off[c + 1]]
+        cur = loc[rows]
+        loc_cur = cur.mean(axis=0)                                                          # :283
+        nearest = int(np.argmin(np.sqrt(((cur - loc_cur) ** 2).sum(axis=1))))               # :286-287, the first minimum
+        out.append((loc_cur, np.asarray(tf[good[rows[nearest]]], dtype=np.float64)))        # :288
+    return out
 
 
 def quickTF_dev(pts_soa: torch.Tensor, TF: np.ndarray) -> torch.Tensor:
