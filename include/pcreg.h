@@ -86,7 +86,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * chain's second scoring pass: 1 always the full pass, 2 always the bounded pass where allowed; 0 chooses by shape),
  * "ransac_stats" (counters for pcreg_debug_ransac_stats), "range_sort_cap" (n > 0: the radius search orders segments longer
  * than n rows by its in-place large-segment path), "cluster_noskip" (the clustering walk unites on every hit instead of
- * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats); value 0
+ * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
+ * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);

@@ -117,7 +117,7 @@ int pcreg_debug_set(const char* key, int value) {
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
                                                         "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap", "cluster_noskip",
-                                                        "cluster_stats"};
+                                                        "cluster_stats", "knn_tail_cap"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }

@@ -89,6 +89,8 @@ enum DebugKey {
                                // large-segment path (0 = the default capacity)
     kDbgClusterNoSkip,         // "cluster_noskip": the clustering walk unites on every hit (no "same root" early-out)
     kDbgClusterStats,          // "cluster_stats": the clustering walk counts hits and compare-and-swaps (pcreg_debug_cluster_stats)
+    kDbgKnnTailCap,            // "knn_tail_cap": n > 0 -- the point search's exact tail (few-form) lists the surviving tiles of n tiles per
+                               // pass instead of its LDS list's capacity
     kDbgCount
 };
 int debug_flag(DebugKey k);

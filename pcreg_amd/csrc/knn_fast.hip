@@ -28,12 +28,15 @@
 //                            written, the others are listed; fills the query grid (a point of a skipped tile is farther
 //                            than two real model points: DESIGN 4.1, culling)
 //   S4  knn_tail_kernel      the listed queries again, exactly.  Few: one workgroup per query culls the tiles with the same
-//                            rule against the query's own dk (the block box shrunk to a point) and scans the rest of the
-//                            sorted copy, (distance, original row) order.  Many: the tiled all-pairs form over the unsorted
+//                            rule against the query's own dk (the block box shrunk to a point), lists the survivors and scans
+//                            them in the sorted copy, dealt over its waves, (distance, original row) order.  Many: the tiled all-pairs form over the unsorted
 //                            model; a per-tile arrival counter lets the last workgroup merge, so there is no second launch.
 //                            Idle (one read) when the list is empty.
 // By-product: a uniform grid over the QUERIES (boxes in S1, geometry by a surplus workgroup of S2, cells in S3), which
 // the Unique back-check of the match stage walks (knn_points.hip: match_finish_kernel) -- no launches of its own.
+//
+// S1, S1c, S3 and S4 are latency-bound (a few MB each): they issue every load of a step before they use the first -- an address
+// that a condition would have guarded is clamped into the array and its value masked ("The small kernels").
 //
 // Rounding bound (u = 2^-24, R_m = max|m~|, r = |q~|), derived in DESIGN.md section 4.1:
 //   E = u*(3 R_m^2 + 16 r R_m + 32.1 (R_m^2 + 2 r R_m) + 4.04 (r + R_m)^2) + 16 u (d2 + |G + r^2|)
@@ -270,6 +273,9 @@ __device__ __forceinline__ int seed_cell(float v, float lo, float inv_h, int n) 
 }
 // eight lanes per query: lane k of the group looks at cells k, k + 8, k + 16, k + 24 of the 27, keeps its
 // own sorted four smallest distances, and three xor-shuffle rounds merge the eight lists
+constexpr int kSeedBatch = 2;     // cells of a lane whose counters and slots are loaded before the first is used (4: 73 VGPRs, the
+                                  // eighth wave per SIMD lost and 3 % slower, docs/BENCH_NOTES.md 2026-10-18)
+static_assert(4 % kSeedBatch == 0, "a lane's four cells in whole batches");
 __device__ __forceinline__ void sort4(float (&d)[4]) {
 #define PCREG_CS(a, b) { const float lo_ = fminf(d[a], d[b]), hi_ = fmaxf(d[a], d[b]); d[a] = lo_; d[b] = hi_; }
     PCREG_CS(0, 1) PCREG_CS(2, 3) PCREG_CS(0, 2) PCREG_CS(1, 3) PCREG_CS(1, 2)
@@ -307,33 +313,56 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
             ug_part[(size_t)blockIdx.x * 6 + threadIdx.x] = r;
         }
     }
-    if (live && sub == 0) {
-        cand_cnt[qi] = 0;                                     // the query's candidate list starts empty
-        if (qcnt) qrank[qi] = atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);     // the query order's counts, and this query's place in its cell
+    if (!seeded) {                                            // +inf: no hint
+        if (live && sub == 0) {
+            cand_cnt[qi] = 0; gthr[qi] = 0xFFFFFFFFu; dk_out[qi] = INFINITY;
+            if (qcnt) qrank[qi] = atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);
+        }
+        return;
     }
-    if (!seeded) { if (live && sub == 0) { gthr[qi] = 0xFFFFFFFFu; dk_out[qi] = INFINITY; } return; }       // +inf: no hint
     const int nx = prep->nx, ny = prep->ny, nz = prep->nz;
     const int cx = seed_cell(qx, prep->gx0, prep->inv_h, nx), cy = seed_cell(qy, prep->gy0, prep->inv_h, ny), cz = seed_cell(qz, prep->gz0, prep->inv_h, nz);
-    float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+    // The lane's four cells first (an excluded one -- past the 27, or outside the grid -- reads the query's own cell and
+    // counts as empty), then the counting atomic, then kSeedBatch cells at a time: their counters and slots with nothing
+    // consumed in between.
+    int cell[4]; bool on[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int c27 = sub + 8 * t;
         const int x = cx + c27 % 3 - 1, y = cy + (c27 / 3) % 3 - 1, z = cz + c27 / 9 - 1;
-        if (c27 < 27 && x >= 0 && x < nx && y >= 0 && y < ny && z >= 0 && z < nz) {
-            const int cell = (z * ny + y) * nx + x;
-            const int n = min(cnt[cell], kSeedSlots);
-            float4 pp[kSeedSlots];
+        on[t] = c27 < 27 && x >= 0 && x < nx && y >= 0 && y < ny && z >= 0 && z < nz;
+        cell[t] = on[t] ? (z * ny + y) * nx + x : (cz * ny + cy) * nx + cx;
+    }
+    // The query order's counts and this query's place in its cell.  The place is stored at the very end: nothing before
+    // needs it, so the atomic's round trip runs alongside the grid loads.  (The query's coordinates are consumed above:
+    // no wait for them can fall behind the atomic and wait for it too.)
+    const int key = sort_key(qx, qy, qz, prep) >> 3;
+    int rank = 0;
+    if (live && sub == 0) {
+        cand_cnt[qi] = 0;                                     // the query's candidate list starts empty
+        if (qcnt) rank = atomicAdd(&qcnt[key], 1);
+    }
+    float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
 #pragma unroll
-            for (int k = 0; k < kSeedSlots; ++k) pp[k] = slots[(size_t)cell * kSeedSlots + k];
+    for (int t0 = 0; t0 < 4; t0 += kSeedBatch) {
+        int n[kSeedBatch]; float4 pp[kSeedBatch][kSeedSlots];
+#pragma unroll
+        for (int t = 0; t < kSeedBatch; ++t) n[t] = cnt[cell[t0 + t]];
+#pragma unroll
+        for (int t = 0; t < kSeedBatch; ++t) {
+#pragma unroll
+            for (int k = 0; k < kSeedSlots; ++k) pp[t][k] = slots[(size_t)cell[t0 + t] * kSeedSlots + k];
+        }
+#pragma unroll
+        for (int t = 0; t < kSeedBatch; ++t) {
+            const int nt = on[t0 + t] ? min(n[t], kSeedSlots) : 0;
 #pragma unroll
             for (int k = 0; k < kSeedSlots; ++k) {
-                if (k < n) {
-                    float ex = qx - pp[k].x, ey = qy - pp[k].y, ez = qz - pp[k].z;
-                    float dd = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-                    if (dd < d[3]) {
-                        if (dd < d[1]) { d[3] = d[2]; d[2] = d[1]; if (dd < d[0]) { d[1] = d[0]; d[0] = dd; } else d[1] = dd; }
-                        else { if (dd < d[2]) { d[3] = d[2]; d[2] = dd; } else d[3] = dd; }
-                    }
+                float ex = qx - pp[t][k].x, ey = qy - pp[t][k].y, ez = qz - pp[t][k].z;
+                float dd = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+                if (k < nt && dd < d[3]) {
+                    if (dd < d[1]) { d[3] = d[2]; d[2] = d[1]; if (dd < d[0]) { d[1] = d[0]; d[0] = dd; } else d[1] = dd; }
+                    else { if (dd < d[2]) { d[3] = d[2]; d[2] = dd; } else d[3] = dd; }
                 }
             }
         }
@@ -362,6 +391,7 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
     }
     gthr[qi] = word;
     dk_out[qi] = dk;                   // the distance itself: two real model points lie within dk of the query (culling)
+    if (qcnt) qrank[qi] = rank;
 }
 
 // ---- S3. exact re-rank + certificate: one 8-lane group per query --------------------------------------------------
@@ -374,6 +404,35 @@ __device__ __forceinline__ bool lex_lt_f(float da, int ia, float db, int ib) {
 // a point was sorted into.  Points past M (tile padding) are skipped.  A query's list: cand_cnt[qi] entries at
 // ent[(size_t)qi * cap + e].
 constexpr int LPQ = 8;
+// A lane keeps its first kOwnEnt entries (e = lane, lane + LPQ, ..: the first LPQ * kOwnEnt of the list) in registers for both
+// passes, all loaded before the first is used; a longer list (cap = W * KC reaches 320) goes on in a loop that reads one entry
+// per trip.  An entry that survives the cut is expanded kRowBatch rows at a time: the coordinate and perm loads of those rows
+// are all issued before the first compare.  A row past M reads row M - 1 instead and is left out of the ranking, so no load
+// leaves ms[0 .. 3M) or perm[0 .. M); the plain loads need no alignment of M.
+constexpr int kOwnEnt = 8;                       // (tests/test_gpu_knn_chains.py builds lists beyond 128 entries: keep LPQ * kOwnEnt below)
+constexpr int kRowBatch = 8;                      // (16: 122 VGPRs and 4 % slower, docs/BENCH_NOTES.md 2026-10-18)
+static_assert(16 % kRowBatch == 0, "an entry's sixteen rows in whole batches");
+__device__ __forceinline__ void expand_entry(int j, float qx, float qy, float qz, const float* __restrict__ ms, int M,
+                                             const int32_t* __restrict__ perm, float& d1, float& d2, int& i1, int& i2) {
+#pragma unroll
+    for (int h = 0; h < 16; h += kRowBatch) {
+        float x[kRowBatch], y[kRowBatch], z[kRowBatch]; int oj[kRowBatch];
+#pragma unroll
+        for (int k = 0; k < kRowBatch; ++k) {
+            const int rr = h + k, jj = min(j + 8 * (rr >> 2) + (rr & 3), M - 1);
+            x[k] = ms[jj]; y[k] = ms[jj + (size_t)M]; z[k] = ms[jj + 2 * (size_t)M]; oj[k] = perm[jj];
+        }
+#pragma unroll
+        for (int k = 0; k < kRowBatch; ++k) {              // ascending rr, (distance, original row) order: as the one-row loop ranked
+            const int rr = h + k;
+            const float dx = qx - x[k], dy = qy - y[k], dz = qz - z[k];
+            const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const bool in2 = j + 8 * (rr >> 2) + (rr & 3) < M && lex_lt_f(d, oj[k], d2, i2), in1 = in2 && lex_lt_f(d, oj[k], d1, i1);
+            d2 = in1 ? d1 : (in2 ? d : d2); i2 = in1 ? i1 : (in2 ? oj[k] : i2);          // (selects: straight-line code)
+            d1 = in1 ? d : d1; i1 = in1 ? oj[k] : i1;
+        }
+    }
+}
 __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const float* __restrict__ q, int Q, int ldq, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm,
     const Prep* __restrict__ prep, const unsigned* __restrict__ rm2_bits, const unsigned* __restrict__ gthr,
@@ -394,7 +453,18 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const uint2* ent = ent_all + (size_t)qi * cap;
     // pass 1: the two smallest approximate scores of the union (values only)
     float a1 = INFINITY, a2 = INFINITY;
-    for (int e = lane; e < total; e += LPQ) {
+    // An entry past the list's end re-reads the last one and is masked.  An empty list (total == 0) reads ent[0] of the
+    // query's own workspace row, which nobody has written, on purpose: in bounds, and masked like the rest.
+    uint2 own[kOwnEnt];
+    const int last = max(total, 1) - 1;
+#pragma unroll
+    for (int k = 0; k < kOwnEnt; ++k) own[k] = ent[min(lane + LPQ * k, last)];
+#pragma unroll
+    for (int k = 0; k < kOwnEnt; ++k) {
+        const float s = __uint_as_float(own[k].y);
+        if (lane + LPQ * k < total && (int)own[k].x >= 0) { if (s < a2) { if (s < a1) { a2 = a1; a1 = s; } else a2 = s; } }
+    }
+    for (int e = lane + LPQ * kOwnEnt; e < total; e += LPQ) {
         const uint2 v = ent[e];
         const float s = __uint_as_float(v.y);
         if ((int)v.x >= 0) { if (s < a2) { if (s < a1) { a2 = a1; a1 = s; } else a2 = s; } }
@@ -422,21 +492,15 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const float cut = (float)((double)a2 + 2.0 * Eab + 16.0 * u * fabs((double)a2 + r2));
     const float cut_up = nextafterf(cut, INFINITY);              // float rounding of the cut must not exclude anything
     float d1 = INFINITY, d2 = INFINITY; int i1 = -1, i2 = -1;
-    for (int e = lane; e < total; e += LPQ) {
+#pragma unroll
+    for (int k = 0; k < kOwnEnt; ++k) {
+        const int j = (int)own[k].x; const float sc = __uint_as_float(own[k].y);
+        if (lane + LPQ * k < total && j >= 0 && (sc <= cut_up || !(a2 < INFINITY))) expand_entry(j, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
+    }
+    for (int e = lane + LPQ * kOwnEnt; e < total; e += LPQ) {
         const uint2 v = ent[e];
         const int j = (int)v.x; const float sc = __uint_as_float(v.y);
-        if (j >= 0 && (sc <= cut_up || !(a2 < INFINITY))) {
-            for (int rr = 0; rr < 16; ++rr) {
-                const int jj = j + 8 * (rr >> 2) + (rr & 3);
-                if (jj >= M) continue;
-                float dx = qx - ms[jj], dy = qy - ms[jj + (size_t)M], dz = qz - ms[jj + 2 * (size_t)M];
-                float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                const int oj = perm[jj];
-                if (lex_lt_f(d, oj, d2, i2)) {
-                    if (lex_lt_f(d, oj, d1, i1)) { d2 = d1; i2 = i1; d1 = d; i1 = oj; } else { d2 = d; i2 = oj; }
-                }
-            }
-        }
+        if (j >= 0 && (sc <= cut_up || !(a2 < INFINITY))) expand_entry(j, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
     }
     // group-shuffle top-2 reduction ordered by (dist, idx); empty slots are (+inf, -1 -> max uint)
 #pragma unroll
@@ -476,10 +540,11 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
 }
 
 // ---- S4. the unproven queries again, exactly: ONE launch --------------------------------------------------------
-// few (<= kFew): work item = listed query, one workgroup each.  Its threads test the tile boxes against the query POINT with
-// the rule of DESIGN 4.1 (D = the query's own dk: two real model points lie within it, every row of a skipped tile is
-// strictly farther), and each wave scans the surviving tiles among the 64 it tested, over the sorted copy, ranking by
-// (distance, perm[row]).  No partials cross workgroups.
+// few (<= kFew): work item = listed query, one workgroup each.  Phase A: its threads test the tile boxes against the query
+// POINT with the rule of DESIGN 4.1 (D = the query's own dk: two real model points lie within it, every row of a skipped tile
+// is strictly farther) and list the surviving tiles in LDS.  Phase B: the survivors' 64-row segments of the sorted copy are
+// dealt over the four waves evenly, ranking by (distance, perm[row]).  Both phases issue a batch of loads before they use the
+// first.  No partials cross workgroups.
 // many: work item = (tile of kTailQ listed queries, chunk of the model); a lane owns four queries, the chunk streams
 // through LDS -- knn2_points_kernel's loop (6 VALU per pair, the oracle's bits).  The workgroup that delivers the LAST
 // partial of a tile (an arrival counter, cleared by S1) merges the partials by (distance, index) and writes the result.
@@ -487,6 +552,8 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
 // counter: no agent-scope fence (it would write back / invalidate the XCD's L2).
 constexpr int kFew = 1024;
 constexpr int kTailGrid = 2048, kTailQ = 4 * kBlock;              // tiled form: 1024 queries per tile
+constexpr int kTailList = 4 * kMTile;            // few-form: tile numbers the survivor list holds (the 16 KB of the many-form's LDS tile)
+constexpr int kTailBoxes = 8, kTailSegs = 8;     // few-form: boxes per thread, and 64-row segments per wave, loaded before the first is used
 struct Top2 { float d1, d2; int i1, i2; };
 __device__ __forceinline__ void top2_insert(Top2& t, float d, int j) {
     // candidates arrive in ascending j, so strict '<' keeps the lowest index
@@ -513,13 +580,14 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
     const int32_t* __restrict__ perm, const float* __restrict__ tbox, const float* __restrict__ dk, int idx_base,
     const int32_t* __restrict__ flag_list, SearchCounters* __restrict__ ctr,
     int32_t* __restrict__ part_idx, float* __restrict__ part_dist /* many: [S][tiles * kTailQ][2] */,
-    int32_t* __restrict__ idx, float* __restrict__ dist) {
+    int32_t* __restrict__ idx, float* __restrict__ dist, int list_cap /* few: tiles per pass, 1 .. kTailList */) {
     const int nf = ctr->n_flag;
     if (nf <= 0) return;
     __shared__ float sd[kBlock / 64][2];
     __shared__ int si[kBlock / 64][2];
-    __shared__ int s_last;
+    __shared__ int s_last, s_nlist;
     __shared__ float4 tile[kMTile];
+    int* const s_list = (int*)tile;                   // few: the surviving tiles of a pass (the many-form's LDS tile is free there)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (nf <= kFew) {
         const int n_tiles = (M + kT16 - 1) / kT16;
@@ -533,35 +601,69 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
             const bool cullq = D < INFINITY && fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY;
             const double qd[3] = {(double)qx, (double)qy, (double)qz};
             float d1 = INFINITY, d2 = INFINITY; int i1 = -1, i2 = -1;
-            for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {            // each thread tests one tile, each wave scans its own survivors
-                const int ct = c0 + threadIdx.x;
-                bool visit = ct < n_tiles;
-                if (visit && cullq) {
-                    const float* bx = tbox + (size_t)ct * 6;
-                    double g2 = 0.0;
+            // A pass covers list_cap tiles, so its survivors always fit the list (one pass for up to 4 * kMTile tiles).
+            for (int c0 = 0; c0 < n_tiles; c0 += list_cap) {
+                const int c1 = min(c0 + list_cap, n_tiles);
+                // phase A: all threads test the pass's tiles, kTailBoxes boxes per thread loaded before the first is judged
+                // (a tile past the end loads the last one's box and is masked); survivors go to the list in any order
+                __syncthreads();                                      // the previous pass's / query's readers are done with the list
+                if (threadIdx.x == 0) s_nlist = cullq ? 0 : c1 - c0;
+                __syncthreads();
+                if (!cullq) {
+                    for (int ct = c0 + threadIdx.x; ct < c1; ct += kBlock) s_list[ct - c0] = ct;
+                } else {
+                    for (int b0 = c0 + threadIdx.x; b0 < c1; b0 += kTailBoxes * kBlock) {
+                        float2 bx[kTailBoxes][3];
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const double gap = fmax(0.0, fmax((double)bx[c] - qd[c], qd[c] - (double)bx[3 + c]));
-                        g2 += gap * gap;
+                        for (int k = 0; k < kTailBoxes; ++k) {
+                            const float2* p = (const float2*)(tbox + (size_t)min(b0 + k * kBlock, c1 - 1) * 6);
+                            bx[k][0] = p[0]; bx[k][1] = p[1]; bx[k][2] = p[2];
+                        }
+#pragma unroll
+                        for (int k = 0; k < kTailBoxes; ++k) {
+                            const int ct = b0 + k * kBlock;
+                            const float lo[3] = {bx[k][0].x, bx[k][0].y, bx[k][1].x}, hi[3] = {bx[k][1].y, bx[k][2].x, bx[k][2].y};
+                            double g2 = 0.0;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                const double gap = fmax(0.0, fmax((double)lo[c] - qd[c], qd[c] - (double)hi[c]));
+                                g2 += gap * gap;
+                            }
+                            const double u = 5.9604644775390625e-08;
+                            if (ct < c1 && !(g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D)) s_list[atomicAdd(&s_nlist, 1)] = ct;
+                        }
                     }
-                    const double u = 5.9604644775390625e-08;
-                    if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D) visit = false;
                 }
-                unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-                while (bal != 0) {
-                    const int t = c0 + wave * 64 + (int)__builtin_ctzll(bal);
-                    bal &= bal - 1;
+                __syncthreads();
+                // phase B: the survivors' 64-row segments dealt over the waves, segment s to wave s % 4; a wave loads the rows
+                // of kTailSegs segments before it compares (a row past M reads row M - 1 and is masked), and their perm words
+                // in one more round only where some lane has a row that can still enter its top two
+                const int n_seg = s_nlist * (kT16 / 64);
+                for (int s0 = wave; s0 < n_seg; s0 += kTailSegs * (kBlock / 64)) {
+                    int j[kTailSegs]; float x[kTailSegs], y[kTailSegs], z[kTailSegs];
 #pragma unroll
-                    for (int r = 0; r < kT16 / 64; ++r) {
-                        const int j = t * kT16 + r * 64 + lane;
-                        if (j < M) {
-                            float dx = qx - ms[j], dy = qy - ms[j + (size_t)M], dz = qz - ms[j + 2 * (size_t)M];
-                            float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                            if (d <= d2 && d < INFINITY) {             // (distance, ORIGINAL row) order; +inf is never an answer
-                                const int oj = perm[j];
-                                if (lex_lt_f(d, oj, d2, i2)) {
-                                    if (lex_lt_f(d, oj, d1, i1)) { d2 = d1; i2 = i1; d1 = d; i1 = oj; } else { d2 = d; i2 = oj; }
-                                }
+                    for (int k = 0; k < kTailSegs; ++k) {
+                        const int s = min(s0 + k * (kBlock / 64), n_seg - 1);
+                        j[k] = s0 + k * (kBlock / 64) < n_seg ? s_list[s / (kT16 / 64)] * kT16 + (s % (kT16 / 64)) * 64 + lane : M;
+                        const int jc = min(j[k], M - 1);
+                        x[k] = ms[jc]; y[k] = ms[jc + (size_t)M]; z[k] = ms[jc + 2 * (size_t)M];
+                    }
+                    float d[kTailSegs]; bool any = false;
+#pragma unroll
+                    for (int k = 0; k < kTailSegs; ++k) {
+                        const float dx = qx - x[k], dy = qy - y[k], dz = qz - z[k];
+                        d[k] = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                        any = any || (j[k] < M && d[k] <= d2 && d[k] < INFINITY);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+                        int oj[kTailSegs];
+#pragma unroll
+                        for (int k = 0; k < kTailSegs; ++k) oj[k] = perm[min(j[k], M - 1)];
+#pragma unroll
+                        for (int k = 0; k < kTailSegs; ++k) {
+                            // (distance, ORIGINAL row) order; +inf is never an answer
+                            if (j[k] < M && d[k] <= d2 && d[k] < INFINITY && lex_lt_f(d[k], oj[k], d2, i2)) {
+                                if (lex_lt_f(d[k], oj[k], d1, i1)) { d2 = d1; i2 = i1; d1 = d[k]; i1 = oj[k]; } else { d2 = d[k]; i2 = oj[k]; }
                             }
                         }
                     }
@@ -811,8 +913,10 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
         fprintf(stderr, "[pcreg] knn fast: Q=%d M=%d W=%d unproven=%d visited tile pairs=%lld of %lld (%.4f)%s\n", Q, v.M, W, nf, nv, qb * nt,
                 qb * nt > 0 ? (double)nv / (double)(qb * nt) : 0.0, cull ? "" : " (culling off)");
     }
+    const int dbg_cap = debug_flag(kDbgKnnTailCap);                  // "knn_tail_cap": n > 0 -- the few-form's passes cover n tiles each, same bits
+    const int tail_cap = dbg_cap > 0 && dbg_cap < kTailList ? dbg_cap : kTailList;
     hipLaunchKernelGGL(knn_tail_kernel, dim3(kTailGrid), dim3(kBlock), 0, st, q, ldq, v.m, v.M, v.ldm, (const float*)v.ms, (const int32_t*)v.perm,
-                       (const float*)v.tbox, (const float*)s.dk, (int)idx_base, (const int32_t*)s.flag_list, ctr, s.tail_idx, s.tail_dist, idx, dist);
+                       (const float*)v.tbox, (const float*)s.dk, (int)idx_base, (const int32_t*)s.flag_list, ctr, s.tail_idx, s.tail_dist, idx, dist, tail_cap);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -194,34 +194,66 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
     }
     __syncthreads();
     const float bdk_b = s_box[6];
+    const double blo_d[3] = {(double)s_box[0], (double)s_box[1], (double)s_box[2]}, bhi_d[3] = {(double)s_box[3], (double)s_box[4], (double)s_box[5]};
     int32_t* list = vis_list + (size_t)qb * n_tiles;
-    int n = 0;
-    // rounds of kBlock tiles: each thread tests one, the visited ones are appended in ascending order
-    for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {
-        const int ct = c0 + tid;
-        bool visit = ct < n_tiles;
-        if (visit && cull != 0 && bdk_b < INFINITY) {
-            // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to
-            // any point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of
-            // 32u, and no bound at all below 1e-30 (subnormal squares)
-            const float* bx = tbox + (size_t)ct * 6;
-            double g2 = 0.0;
+    // Thread t owns the `per` CONSECUTIVE tiles from t * per, so the threads' visited tiles, one thread after the other, are
+    // the ascending list.  Its boxes are loaded kPlanBatch tiles at a time, every load issued before the first test (a tile
+    // past the end loads the last tile's box and is masked out); one workgroup scan of the counts places each thread's run.
+    const int per = (n_tiles + kBlock - 1) / kBlock;
+    const int t0 = min(tid * per, n_tiles), t1 = min(t0 + per, n_tiles);
+    const bool test = cull != 0 && bdk_b < INFINITY;
+    // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to any
+    // point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of 32u, and no
+    // bound at all below 1e-30 (subnormal squares)
+    auto skipped = [&](const float2 a, const float2 b, const float2 c) {       // the box: lo = (a.x, a.y, b.x), hi = (b.y, c.x, c.y)
+        const float lo[3] = {a.x, a.y, b.x}, hi[3] = {b.y, c.x, c.y};
+        double g2 = 0.0;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
-                g2 += gap * gap;
-            }
-            const double u = 5.9604644775390625e-08;
-            if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b) visit = false;
+        for (int d = 0; d < 3; ++d) {
+            const double gap = fmax(0.0, fmax((double)lo[d] - bhi_d[d], blo_d[d] - (double)hi[d]));
+            g2 += gap * gap;
         }
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-        if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
-        __syncthreads();
-        int base = n;
+        const double u = 5.9604644775390625e-08;
+        return g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b;
+    };
+    constexpr int kPlanBatch = 8;
+    // The verdicts of the thread's first 64 tiles; later ones are tested again when the list is written.  That second path
+    // needs per > 64, more than 16 384 tiles (8.4 M rows): no test reaches it.  It applies the same skipped() to the same
+    // box, so it agrees with the count above.
+    unsigned long long keep = 0ull;
+    int cnt = t1 - t0;
+    if (test) {
+        cnt = 0;
+        for (int k0 = 0; k0 < t1 - t0; k0 += kPlanBatch) {
+            float2 bx[kPlanBatch][3];
 #pragma unroll
-        for (int k = 0; k < kBlock / 64; ++k) { base += k < wave ? s_wcnt[k] : 0; n += s_wcnt[k]; }
-        if (visit) list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
-        __syncthreads();                          // s_wcnt is rewritten in the next round
+            for (int k = 0; k < kPlanBatch; ++k) {
+                const float2* p = (const float2*)(tbox + (size_t)min(t0 + k0 + k, n_tiles - 1) * 6);
+                bx[k][0] = p[0]; bx[k][1] = p[1]; bx[k][2] = p[2];
+            }
+#pragma unroll
+            for (int k = 0; k < kPlanBatch; ++k) {
+                const bool visit = t0 + k0 + k < t1 && !skipped(bx[k][0], bx[k][1], bx[k][2]);
+                cnt += visit ? 1 : 0;
+                if (k0 + k < 64) keep |= (unsigned long long)(visit ? 1 : 0) << (k0 + k);
+            }
+        }
+    }
+    int inc = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o); if (lane >= o) inc += y; }
+    if (lane == 63) s_wcnt[wave] = inc;
+    __syncthreads();
+    int pos = inc - cnt, n = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) { pos += k < wave ? s_wcnt[k] : 0; n += s_wcnt[k]; }
+    for (int k = 0; k < t1 - t0; ++k) {
+        bool visit = true;
+        if (test) {
+            if (k < 64) visit = (keep >> k) & 1ull;
+            else { const float2* p = (const float2*)(tbox + (size_t)(t0 + k) * 6); visit = !skipped(p[0], p[1], p[2]); }
+        }
+        if (visit) list[pos++] = t0 + k;
     }
     if (tid == 0) {
         n_vis[qb] = n;
