@@ -201,6 +201,21 @@ int pcreg_model_cluster_f32(pcreg_model* model, float r2, int32_t* label, int32_
 int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off,
                              int32_t* members);
 
+/* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
+ * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
+ * the smallest index represents its run (MATLAB's default 'first').  ia [n]: the 1-based indices of the representatives in sorted
+ * row order, *n_unique of them; C = A(ia, :) is the caller's gather and carries the representative's bits.  n = 0 is valid.  A row
+ * that holds a NaN is refused with PCREG_E_ARG (MATLAB treats every NaN as distinct; the device order does not, see below).  The
+ * result is a pure function of the input. */
+int pcreg_unique_rows3(const double* A, int n, int ld, int32_t* ia, int* n_unique);
+/* completeExperiment.m:440-443 on the stacked putative matches (pts1 / pts2 n x 3 column-major, leading dimension ld):
+ *   [pts1, ia1] = unique(pts1, 'rows'); pts2 = pts2(ia1, :); [pts2, ia2] = unique(pts2, 'rows'); pts1 = pts1(ia2, :);
+ * out1 / out2 (n x 3, leading dimension ldo >= n): the *n_out surviving pairs, sorted by the MODEL point (pts2) -- the order
+ * ransac's sampler indexes; ia [n] or NULL: the composed 1-based index ia1(ia2) of every surviving pair in the input.  NaN rows
+ * on either side: PCREG_E_ARG. */
+int pcreg_aggregate_matches(const double* pts1, const double* pts2, int n, int ld, double* out1, double* out2, int ldo, int32_t* ia,
+                            int* n_out);
+
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
  * than min_points (:17) or the ball fewer than min_points / more than max_points (:31).  pts: N x 3 column-major (ld >= N).
@@ -676,6 +691,33 @@ int pcreg_dev_quick_tf(const double* pts, int n, int ld, const double T[16], dou
  * empty), info[0] = number of inliers, info[1] = 1 if the transform is empty. */
 int pcreg_dev_refine_by_distance(const double* pts1, const double* pts2, const int32_t* n_dev, int cap, int ld,
                                  double maxDist, double* T16, int32_t* info, void* stream);
+
+/* unique(A, 'rows') on the device (pcreg_unique_rows3's contract): A n x 3 doubles column-major with leading
+ * dimension ld >= n_cap, n = *n_dev read on the device (clamped into [0, n_cap]; rows past n are never read), ia [n_cap]
+ * (idx_base-based), n_unique one int32 on the device.  Every double is ordered by an order-preserving u64 image (sign flip, -0
+ * as +0); a NaN is ordered by that image of its bit pattern -- positive NaNs behind +inf, negative ones before -inf, two NaNs equal
+ * iff their bits are -- which is NOT MATLAB's rule; any input terminates and stays in bounds.  A tile sort of 2048 records in LDS,
+ * ceil(log2(n_cap / 2048)) merge passes, head flags + scan + compaction; no workgroup waits for another, nothing synchronises.
+ * Workspace: 2 * (3 * roundup(8 * max(n, 1), 256) + roundup(4 * max(n, 1), 256)) + roundup(4 * max(ceil(n / 2048), 1), 256) bytes
+ * with n = n_cap; a shorter one is PCREG_E_ARG. */
+size_t pcreg_dev_unique_rows3_workspace(int n_cap);
+int pcreg_dev_unique_rows3_f64(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia,
+                               int32_t* n_unique, void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_aggregate_matches on the device as one launch chain: out1 / out2 n_cap x 3 (leading dimension ldo >= n_cap), ia [n_cap]
+ * or NULL (idx_base-based composed index), n_out one int32 on the device.  Workspace:
+ * 2 * roundup(4 * max(n, 1), 256) + 256 + roundup(24 * max(n, 1), 256) + pcreg_dev_unique_rows3_workspace(n) bytes, n = n_cap.
+ * The chain leaves the count after the FIRST unique as one int32 at byte offset 2 * roundup(4 * max(n, 1), 256) of the workspace. */
+size_t pcreg_dev_aggregate_matches_workspace(int n_cap);
+int pcreg_dev_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1,
+                                double* out2, int ldo, int32_t idx_base, int32_t* ia, int32_t* n_out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* T = estimateTransform(pts1(idx, :), pts2(idx, :)) with the index list on the device (completeExperiment.m:458 on ransac's
+ * inlier_idx): rows idx[0 .. *n_idx_dev) (idx_base-based; the count is clamped into [0, cap], every index into the cap rows) of
+ * pts1 / pts2 (cap x 3 column-major, leading dimension ld >= cap).  The arithmetic of pcreg_dev_refine_by_distance with every
+ * listed row counted: 3 rows by the three-point fit, fewer give an empty transform.  T16 and info ([0] rows used, [1] 1 if empty)
+ * as there. */
+int pcreg_dev_estimate_transform_indexed(const double* pts1, const double* pts2, int ld, const int32_t* idx, int32_t idx_base,
+                                         const int32_t* n_idx_dev, int cap, double* T16, int32_t* info, void* stream);
 
 /* The final stage's device pieces, batched over its K clusters (pcreg_final_stage runs on them).
  * pcreg_dev_quick_tf_batched: out copy k (n x 3 column-major, leading dimension ldo, starting at out + 3 k ldo) = [pts, 1] * T_k,

@@ -19,6 +19,10 @@
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
 //                                          "distance <= r", numbered by their smallest row (clusterPoints.m:16-45;
 //                                          matlab/clusterPointsModel.m, matlab/clusterPointsFast.m)
+//   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
+//                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
+//   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
+//                                          completeExperiment.m:440-443, unique over pts1 then over pts2 (matlab/aggregateMatches.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -510,6 +514,45 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = cluster_on_handle(h, (float)mxGetScalar(prhs[2]), out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)
+        if (nrhs != 2 || !mxIsDouble(prhs[1]) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1]))) usage = "uniqueRows3: A (double n x 3)";
+        else {
+            const int n = mxIsEmpty(prhs[1]) ? 0 : (int)mxGetM(prhs[1]);
+            mxArray* tmp = mxCreateNumericMatrix(n > 0 ? n : 1, 1, mxINT32_CLASS, mxREAL);
+            int nu = 0;
+            rc = pcreg_unique_rows3(mxGetPr(prhs[1]), n, n > 0 ? n : 1, (int32_t*)mxGetData(tmp), &nu);
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateDoubleMatrix(nu, nu > 0 ? 1 : 0, mxREAL);
+                const int32_t* src = (const int32_t*)mxGetData(tmp);
+                for (int k = 0; k < nu; ++k) mxGetPr(plhs[0])[k] = (double)src[k];
+            }
+            mxDestroyArray(tmp);
+        }
+    } else if (!strcmp(cmd, "aggregateMatches")) {            // [pts1u, pts2u, ia] = pcreg_mex('aggregateMatches', pts1, pts2)
+        if (nrhs != 3 || !mxIsDouble(prhs[1]) || !mxIsDouble(prhs[2]) || mxGetM(prhs[1]) != mxGetM(prhs[2]) ||
+            (!mxIsEmpty(prhs[1]) && (mxGetN(prhs[1]) != 3 || mxGetN(prhs[2]) != 3)))
+            usage = "aggregateMatches: pts1, pts2 (double n x 3 each, the same n)";
+        else {
+            const int n = mxIsEmpty(prhs[1]) ? 0 : (int)mxGetM(prhs[1]);
+            const size_t ld = n > 0 ? n : 1;
+            mxArray* t1 = mxCreateDoubleMatrix(ld, 3, mxREAL);
+            mxArray* t2 = mxCreateDoubleMatrix(ld, 3, mxREAL);
+            mxArray* ti = mxCreateNumericMatrix(ld, 1, mxINT32_CLASS, mxREAL);
+            int nu = 0;
+            rc = pcreg_aggregate_matches(mxGetPr(prhs[1]), mxGetPr(prhs[2]), n, (int)ld, mxGetPr(t1), mxGetPr(t2), (int)ld, (int32_t*)mxGetData(ti), &nu);
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateDoubleMatrix(nu, 3, mxREAL);
+                if (nlhs > 1) plhs[1] = mxCreateDoubleMatrix(nu, 3, mxREAL);
+                if (nlhs > 2) plhs[2] = mxCreateDoubleMatrix(nu, nu > 0 ? 1 : 0, mxREAL);
+                for (int c = 0; c < 3; ++c)
+                    for (int k = 0; k < nu; ++k) {
+                        mxGetPr(plhs[0])[k + (size_t)c * nu] = mxGetPr(t1)[k + c * ld];
+                        if (nlhs > 1) mxGetPr(plhs[1])[k + (size_t)c * nu] = mxGetPr(t2)[k + c * ld];
+                    }
+                if (nlhs > 2) for (int k = 0; k < nu; ++k) mxGetPr(plhs[2])[k] = (double)((const int32_t*)mxGetData(ti))[k];
+            }
+            mxDestroyArray(t1); mxDestroyArray(t2); mxDestroyArray(ti);
         }
     } else if (!strcmp(cmd, "descCreate")) {                  // h = pcreg_mex('descCreate', desc): an n x D double descriptor set, uploaded ONCE
         if (nrhs != 2 || !mxIsDouble(prhs[1])) usage = "descCreate: desc (double n x D)";

@@ -61,6 +61,8 @@ SYMBOLS = [
     "pcreg_dev_model_knn_workspace", "pcreg_dev_model_knn_f32", "pcreg_dev_merge_topk_f32",
     "pcreg_dev_model_range_workspace", "pcreg_dev_model_range_count_f32", "pcreg_dev_model_range_fill_f32",
     "pcreg_dev_model_cluster_workspace", "pcreg_dev_model_cluster_f32",
+    "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
+    "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
     "pcreg_align_points_knn", "pcreg_align_points_knn_f32", "pcreg_align_points_knn_batched", "pcreg_spatial_histogram_descriptors",
     "pcreg_spatial_histogram_descriptors_f32", "pcreg_spatial_histogram_descriptors_mixed",
@@ -124,6 +126,10 @@ def lib() -> C.CDLL:
             L.pcreg_model_cluster_f32.argtypes = [vp, f, vp, vp, vp, vp]
             L.pcreg_cluster_points_f32.argtypes = [vp, i, i, f, vp, vp, vp, vp]
             L.pcreg_debug_cluster_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+        if hasattr(L, "pcreg_dev_unique_rows3_workspace"):    # (an older build given through PCREG_LIB lacks unique_rows)
+            for name in ("pcreg_dev_unique_rows3_workspace", "pcreg_dev_aggregate_matches_workspace"):
+                getattr(L, name).restype = C.c_size_t
+                getattr(L, name).argtypes = [C.c_int]
         for name, args in (("pcreg_debug_knn_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_ransac_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_dev_model_export", [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),

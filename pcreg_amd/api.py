@@ -656,6 +656,36 @@ def cluster_points(pts, r2: float):
     return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_cluster_points_f32(m.ctypes.data, M, max(M, 1), r2, lab, nc, off, mem)), M)
 
 
+def unique_rows(A):
+    """[C, ia] = unique(A, 'rows') for an n x 3 float64 array: (C [u, 3], ia [u] int32, 0-based).  Rows in lexicographic order by
+    column 1, 2, 3 as numbers (-0 == +0); the first occurrence represents its run and C = A[ia] carries its bits.  A NaN anywhere
+    is refused (PCREG_E_ARG)."""
+    a = _pts3(A, "A")
+    n = a.shape[0]
+    ia = np.zeros(max(n, 1), dtype=np.int32)
+    nu = C.c_int(0)
+    check(lib().pcreg_unique_rows3(_ptr(a, C.c_double), C.c_int(n), C.c_int(max(n, 1)), _ptr(ia, C.c_int32), C.byref(nu)))
+    ia = ia[:nu.value] - 1
+    return np.ascontiguousarray(a[ia]), ia
+
+
+def aggregate_matches(pts1, pts2):
+    """completeExperiment.m:440-443 on stacked putative matches (n x 3 float64 each): unique over pts1, pts2 taken along, unique
+    over that pts2, pts1 taken along -> (pts1u [u, 3], pts2u [u, 3], ia [u] int32, 0-based rows of the input), sorted by pts2u."""
+    p1, p2 = _pts3(pts1, "pts1"), _pts3(pts2, "pts2")
+    n = p1.shape[0]
+    if p2.shape[0] != n:
+        raise ValueError("pts1 and pts2 must have the same number of rows")
+    ld = max(n, 1)
+    o1 = np.zeros((ld, 3), dtype=np.float64, order="F"); o2 = np.zeros((ld, 3), dtype=np.float64, order="F")
+    ia = np.zeros(ld, dtype=np.int32)
+    no = C.c_int(0)
+    check(lib().pcreg_aggregate_matches(_ptr(p1, C.c_double), _ptr(p2, C.c_double), C.c_int(n), C.c_int(ld), _ptr(o1, C.c_double),
+                                        _ptr(o2, C.c_double), C.c_int(ld), _ptr(ia, C.c_int32), C.byref(no)))
+    u = no.value
+    return np.ascontiguousarray(o1[:u]), np.ascontiguousarray(o2[:u]), ia[:u] - 1
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or

@@ -594,6 +594,74 @@ int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* 
     return cluster_on_view(st, v, r2, label, n_clusters, cl_off, members);
 }
 
+// a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)
+static bool has_nan3(const double* a, int n, int ld) {
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < n; ++i)
+            if (a[i + (size_t)c * ld] != a[i + (size_t)c * ld]) return true;
+    return false;
+}
+int pcreg_unique_rows3(const double* A, int n, int ld, int32_t* ia, int* n_unique) {
+    PCREG_ARG(n_unique && n >= 0 && ld >= n && (n == 0 || (A && ia)));
+    PCREG_ARG(!has_nan3(A, n, ld));
+    GUARD();
+    *n_unique = 0;
+    if (n == 0) return PCREG_OK;
+    Stage st{scratch()};
+    double* dA; int32_t *dn, *dia, *dnu; char* ws;
+    const size_t wsb = unique_rows3_ws_bytes(n);
+    TRY(st.take(3 * (size_t)n, &dA));
+    TRY(st.take(1, &dn));
+    TRY(st.take((size_t)n, &dia));
+    TRY(st.take(1, &dnu));
+    TRY(st.take(wsb, &ws));
+    const int32_t n32 = n;
+    TRY(upload_cols(A, n, ld, 3, dA, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dn, &n32, sizeof(int32_t), hipMemcpyHostToDevice, g_stream));
+    TRY(launch_unique_rows3(dA, dn, n, n, 1, dia, dnu, ws, wsb, g_stream));
+    int32_t nu = 0;
+    PCREG_HIP(hipMemcpyAsync(ia, dia, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(&nu, dnu, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    *n_unique = nu;
+    return PCREG_OK;
+}
+int pcreg_aggregate_matches(const double* pts1, const double* pts2, int n, int ld, double* out1, double* out2, int ldo, int32_t* ia, int* n_out) {
+    PCREG_ARG(n_out && n >= 0 && ld >= n && ldo >= n && (n == 0 || (pts1 && pts2 && out1 && out2)));
+    PCREG_ARG(!has_nan3(pts1, n, ld) && !has_nan3(pts2, n, ld));
+    GUARD();
+    *n_out = 0;
+    if (n == 0) return PCREG_OK;
+    Stage st{scratch()};
+    double *d1, *d2, *o1, *o2; int32_t *dn, *dia, *dno; char* ws;
+    const size_t wsb = aggregate_matches_ws_bytes(n);
+    TRY(st.take(3 * (size_t)n, &d1));
+    TRY(st.take(3 * (size_t)n, &d2));
+    TRY(st.take(1, &dn));
+    TRY(st.take(3 * (size_t)n, &o1));
+    TRY(st.take(3 * (size_t)n, &o2));
+    TRY(st.take((size_t)n, &dia));
+    TRY(st.take(1, &dno));
+    TRY(st.take(wsb, &ws));
+    const int32_t n32 = n;
+    TRY(upload_cols(pts1, n, ld, 3, d1, g_stream));
+    TRY(upload_cols(pts2, n, ld, 3, d2, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dn, &n32, sizeof(int32_t), hipMemcpyHostToDevice, g_stream));
+    TRY(launch_aggregate_matches(d1, d2, dn, n, n, o1, o2, n, 1, dia, dno, ws, wsb, g_stream));
+    int32_t no = 0;
+    PCREG_HIP(hipMemcpyAsync(&no, dno, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));                   // the count fixes how many rows come back
+    if (no > 0) {
+        const size_t w = sizeof(double) * (size_t)no;
+        PCREG_HIP(hipMemcpy2DAsync(out1, sizeof(double) * (size_t)ldo, o1, sizeof(double) * (size_t)n, w, 3, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipMemcpy2DAsync(out2, sizeof(double) * (size_t)ldo, o2, sizeof(double) * (size_t)n, w, 3, hipMemcpyDeviceToHost, g_stream));
+        if (ia) PCREG_HIP(hipMemcpyAsync(ia, dia, sizeof(int32_t) * (size_t)no, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipStreamSynchronize(g_stream));
+    }
+    *n_out = no;
+    return PCREG_OK;
+}
+
 int pcreg_match_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float thr_abs,
                            float max_ratio, int unique, uint32_t* pairs, int* P) {
     PCREG_ARG(q && m && pairs && P && Q >= 0 && M >= 0 && ldq >= Q && ldm >= M);
@@ -1613,6 +1681,29 @@ int pcreg_dev_refine_by_distance(const double* pts1, const double* pts2, const i
     PCREG_ARG(pts1 && pts2 && n_dev && T16 && info && cap >= 0 && ld >= cap);
     GUARD();
     return launch_refine_by_distance(pts1, pts2, n_dev, cap, ld, maxDist, T16, info, (hipStream_t)stream);
+}
+size_t pcreg_dev_unique_rows3_workspace(int n_cap) { return unique_rows3_ws_bytes(n_cap); }
+int pcreg_dev_unique_rows3_f64(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(n_dev && n_unique && workspace && n_cap >= 0 && ld >= n_cap && (n_cap == 0 || (A && ia)));
+    PCREG_ARG(workspace_bytes >= unique_rows3_ws_bytes(n_cap));
+    GUARD();
+    return launch_unique_rows3(A, n_dev, n_cap, ld, idx_base, ia, n_unique, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t pcreg_dev_aggregate_matches_workspace(int n_cap) { return aggregate_matches_ws_bytes(n_cap); }
+int pcreg_dev_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1, double* out2,
+                                int ldo, int32_t idx_base, int32_t* ia, int32_t* n_out, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(n_dev && n_out && workspace && n_cap >= 0 && ld >= n_cap && ldo >= n_cap && (n_cap == 0 || (pts1 && pts2 && out1 && out2)));
+    PCREG_ARG(workspace_bytes >= aggregate_matches_ws_bytes(n_cap));
+    GUARD();
+    return launch_aggregate_matches(pts1, pts2, n_dev, n_cap, ld, out1, out2, ldo, idx_base, ia, n_out, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
+}
+int pcreg_dev_estimate_transform_indexed(const double* pts1, const double* pts2, int ld, const int32_t* idx, int32_t idx_base,
+                                         const int32_t* n_idx_dev, int cap, double* T16, int32_t* info, void* stream) {
+    PCREG_ARG(n_idx_dev && T16 && info && cap >= 0 && ld >= cap && (cap == 0 || (pts1 && pts2 && idx)));
+    GUARD();
+    return launch_estimate_transform_indexed(pts1, pts2, ld, idx, idx_base, n_idx_dev, cap, T16, info, (hipStream_t)stream);
 }
 int pcreg_dev_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, void* stream) {
     PCREG_ARG(T_dev && K >= 0 && n >= 0 && ld >= n && ldo >= n && (n == 0 || (pts && out)));

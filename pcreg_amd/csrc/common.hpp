@@ -204,6 +204,13 @@ int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, 
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,
                          size_t ws_bytes, hipStream_t st);
+// unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
+size_t unique_rows3_ws_bytes(int n_cap);
+int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,
+                        size_t ws_bytes, hipStream_t st);
+size_t aggregate_matches_ws_bytes(int n_cap);
+int launch_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1, double* out2, int ldo,
+                             int32_t idx_base, int32_t* ia, int32_t* n_out, void* ws, size_t ws_bytes, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,
@@ -242,6 +249,8 @@ int launch_gather_rows_f64(const double* src, int D, const int32_t* idx, const i
 int launch_quick_tf(const double* pts, int n, int ld, const double T[16], double* out, int ldo, hipStream_t st);
 int launch_refine_by_distance(const double* p1, const double* p2, const int32_t* n_dev, int cap, int ld, double maxDist,
                               double* T16_dev, int32_t* info_dev, hipStream_t st);
+int launch_estimate_transform_indexed(const double* p1, const double* p2, int ld, const int32_t* idx, int32_t idx_base, const int32_t* n_idx_dev,
+                                      int cap, double* T16_dev, int32_t* info_dev, hipStream_t st);
 // the final stage batched over its K clusters (sweep.hip, ransac.hip)
 int launch_quick_tf_batched(const double* pts, int n, int ld, const double* T_dev, int K, double* out, int ldo, double* limits, hipStream_t st);
 int launch_final_close_refine_batched(const uint32_t* pairs, const int32_t* n_pairs, const double* feat, const int32_t* kp_off,

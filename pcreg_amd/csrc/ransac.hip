@@ -3023,7 +3023,8 @@ __global__ __launch_bounds__(64) void estimate_transform_kernel(const double* p1
 // summed per lane then across the wave (wave_sum27), the first three inliers kept for the N == 3 branch.  T16 (lanes < 16) is
 // written here; the number of inliers and whether T is empty are returned to every lane.  PTS: anything with
 // load(i, double[6]) -> (pts1(i,:), pts2(i,:)); both kernels below call this body, so they agree bit for bit.
-template <class PTS>
+// ALL: every row counts (estimateTransform over the rows P presents), the distance is not looked at.
+template <class PTS, bool ALL = false>
 __device__ __forceinline__ void refine_by_distance_wave(const PTS& P, int n, double maxDist, double* s3, double* T16, int& cnt_out, bool& ok_out) {
     const int lane = threadIdx.x;
     double T[12]; bool ok = false;
@@ -3040,7 +3041,7 @@ __device__ __forceinline__ void refine_by_distance_wave(const PTS& P, int n, dou
             const bool act = i < n;
             double q[6]; P.load(act ? i : 0, q);
             const double dx = q[0] - q[3], dy = q[1] - q[4], dz = q[2] - q[5];
-            const bool in = act && sqrt((dx * dx + dy * dy) + dz * dz) < maxDist;
+            const bool in = act && (ALL || sqrt((dx * dx + dy * dy) + dz * dz) < maxDist);
             const unsigned long long bal = __ballot(in);
             if (in) mom_accumulate(acc, q, o);
             if (cnt < 3) {                                   // the N == 3 branch needs the points themselves
@@ -3123,6 +3124,28 @@ __global__ __launch_bounds__(64) void final_close_refine_batched_kernel(const ui
         precision[k] = n > 0 ? (double)cnt / (double)n * 100.0 : __builtin_nan("");     // :373, 0 / 0 = NaN
         empty[k] = ok ? 0 : 1;
     }
+}
+
+// T = estimateTransform(pts1(idx,:), pts2(idx,:)) with idx on the device: rows idx[0 .. *n_idx_dev) (idx_base-based, each clamped
+// into [0, cap) so that a bad list reads in bounds), the wave body above with every listed row counted -- the moment sums over
+// the list in its order, N = 3 by fit_3pt, N < 3 empty.
+struct IndexedPts {
+    const double* g1; const double* g2; int ld; const int32_t* idx; int base, cap;
+    __device__ __forceinline__ void load(int i, double (&p)[6]) const {
+        const int r = min(max(idx[i] - base, 0), cap - 1);
+        p[0] = g1[r]; p[1] = g1[r + (size_t)ld]; p[2] = g1[r + 2 * (size_t)ld];
+        p[3] = g2[r]; p[4] = g2[r + (size_t)ld]; p[5] = g2[r + 2 * (size_t)ld];
+    }
+};
+__global__ __launch_bounds__(64) void estimate_transform_indexed_kernel(const double* p1, const double* p2, int ld, const int32_t* idx, int idx_base,
+                                                                        const int32_t* n_idx_dev, int cap, double* T16,
+                                                                        int32_t* info /*[2]: rows, empty*/) {
+    __shared__ double s3[18];
+    const int n = max(0, min(*n_idx_dev, cap));
+    IndexedPts P{p1, p2, ld, idx, idx_base, cap};
+    int cnt; bool ok;
+    refine_by_distance_wave<IndexedPts, true>(P, n, 0.0, s3, T16, cnt, ok);
+    if (threadIdx.x == 0) { info[0] = cnt; info[1] = ok ? 0 : 1; }
 }
 
 __global__ void calc_dists_kernel(const double* T16, const double* p1, const double* p2, int n, int ld, double* d) {
@@ -3419,6 +3442,13 @@ int launch_estimate_transform(const double* p1, const double* p2, int n, int ld,
 int launch_refine_by_distance(const double* p1, const double* p2, const int32_t* n_dev, int cap, int ld, double maxDist,
                               double* T16_dev, int32_t* info_dev, hipStream_t st) {
     hipLaunchKernelGGL(refine_by_distance_kernel, dim3(1), dim3(64), 0, st, p1, p2, n_dev, cap, ld, maxDist, T16_dev, info_dev);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+int launch_estimate_transform_indexed(const double* p1, const double* p2, int ld, const int32_t* idx, int32_t idx_base, const int32_t* n_idx_dev,
+                                      int cap, double* T16_dev, int32_t* info_dev, hipStream_t st) {
+    hipLaunchKernelGGL(estimate_transform_indexed_kernel, dim3(1), dim3(64), 0, st, p1, p2, ld, idx, (int)idx_base, n_idx_dev, cap, T16_dev, info_dev);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

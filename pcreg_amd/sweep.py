@@ -65,6 +65,8 @@ class SphereSweep:
         run_streams()); the next run allocates them again.  The descriptor sets stay resident."""
         self._seg_ws = None
         self._rs_ws = None
+        self._agg = None
+        self._agg_ws = None
         if hasattr(self, "_lanes"):
             del self._lanes
         self.pipe = DescriptorPipeline(self.dev)
@@ -205,6 +207,7 @@ class SphereSweep:
             self._spheres[skey] = sph
         centres, num_desc, S = sph["centres"], sph["num_desc"], sph["S"]
         if S == 0:
+            self._agg = None
             return dict(centres=centres, num_desc=num_desc, num_putative=np.zeros(0, np.int64), matches=[], model_rows=[], trial=np.zeros(0, np.int64),
                         statsPutative=np.zeros(0, np.int64), statsSuccess=np.zeros(0, np.int64), statsInliers=np.zeros(0, np.int64),
                         statsRatio=np.zeros(0), transforms=[])
@@ -303,11 +306,84 @@ class SphereSweep:
             sp_.append(P); ss.append(r.num_success); si.append(r.max_inliers)
             sr.append(100.0 * r.max_inliers / P if not r.failed else 0.0)
             tf.append(None if r.failed else np.array(r.T[:]).reshape(4, 4, order="F"))
-        return dict(centres=centres, num_desc=num_desc, num_putative=npr,
-                    matches=[pairs_host[i, :npr[i]] for i in range(S)],
-                    model_rows=model_rows, trial=trial,
-                    statsPutative=np.array(sp_, dtype=np.int64), statsSuccess=np.array(ss, dtype=np.int64),
-                    statsInliers=np.array(si, dtype=np.int64), statsRatio=np.array(sr, dtype=np.float64), transforms=tf)
+        out = dict(centres=centres, num_desc=num_desc, num_putative=npr,
+                   matches=[pairs_host[i, :npr[i]] for i in range(S)],
+                   model_rows=model_rows, trial=trial,
+                   statsPutative=np.array(sp_, dtype=np.int64), statsSuccess=np.array(ss, dtype=np.int64),
+                   statsInliers=np.array(si, dtype=np.int64), statsRatio=np.array(sr, dtype=np.float64), transforms=tf)
+        # what aggregate() stacks from: this sweep's resident pairs, their counts, the spheres' keypoints and row offsets, the surface
+        # they were matched against -- private references, dropped by release() and replaced by the next sweep
+        self._agg = dict(result=out, pairs_all=pairs_all, n_pairs=n_pairs, feat_all=feat_all, roff_dev=roff_dev, featS=self.featS, VS=self.VS)
+        return out
+
+    def aggregate(self, result: dict, members, options: dict, seed: int = 0) -> dict:
+        """completeExperiment.m:424-458 on the buffers the last run() / run_streams() left on the device: stack the putative matches
+        of the spheres `members` (indices into result["centres"], e.g. largest_cluster(result)[1]) in that order, pairs in each
+        sphere's own order (:424-437, pcreg_dev_sweep_gather with the members as its list); make them unique twice (:439-443,
+        pcreg_dev_aggregate_matches); ONE ransac on what is left with `options` and `seed` (:446-455, the built-in sampler);
+        T_final = estimateTransform over its inliers (:458, pcreg_dev_estimate_transform_indexed).  ONE host synchronisation: the
+        final read.  `result` must be the dict that sweep returned.  -> dict(n_total, n_unique1, n_unique2, T, inlierIdx (1-based
+        rows of the aggregated pairs), numSuccess, maxInliers, maxInlierRatio (percent), T_final, host_syncs); T and T_final are None
+        where ransac fails (the script stops there)."""
+        from ._lib import DevRansacResult
+        st = getattr(self, "_agg", None)
+        if st is None or result is not st["result"]:
+            raise ValueError("aggregate: `result` is not the result of this object's last run() / run_streams() (or release() dropped its buffers)")
+        L = lib()
+        dev, sp = self.dev, _stream()
+        i32, f64 = torch.int32, torch.float64
+        members = np.asarray(members, dtype=np.int64).reshape(-1)
+        S = len(result["centres"])
+        if len(members) and (members.min() < 0 or members.max() >= S):
+            raise ValueError("aggregate: a member is not a sphere of this sweep")
+        K = len(members)
+        offs = np.zeros(K + 1, dtype=np.int64); offs[1:] = np.cumsum(np.asarray(result["num_putative"], dtype=np.int64)[members])
+        total = int(offs[-1])
+        if total >= 2**31 - 4096:
+            raise ValueError("aggregate: more than 2^31 stacked matches")
+        if total == 0:
+            return dict(n_total=0, n_unique1=0, n_unique2=0, T=None, inlierIdx=np.zeros(0, np.int64), numSuccess=0, maxInliers=0,
+                        maxInlierRatio=0.0, T_final=None, host_syncs=0)
+        VS = st["VS"]
+        # the member list, its offsets, the list's length and the stacked total: one upload
+        ints = torch.from_numpy(np.concatenate([members, offs, [K, total]]).astype(np.int32)).to(dev)
+        m_dev, o_dev, k_dev, n_dev = ints[:K], ints[K:2 * K + 1], ints[2 * K + 1:2 * K + 2], ints[2 * K + 2:]
+        p1 = torch.empty((3, total), dtype=f64, device=dev); p2 = torch.empty((3, total), dtype=f64, device=dev)
+        check(L.pcreg_dev_sweep_gather(_p(st["pairs_all"]), max(VS, 1), _p(st["n_pairs"]), _p(m_dev), _p(o_dev), _p(k_dev), K, _p(st["featS"]),
+                                       _p(st["feat_all"]), _p(st["roff_dev"]), _p(p1), _p(p2), total, sp))           # :424-437
+        u1 = torch.empty((3, total), dtype=f64, device=dev); u2 = torch.empty((3, total), dtype=f64, device=dev)
+        n_out = torch.zeros(1, dtype=i32, device=dev)
+        wsb = L.pcreg_dev_aggregate_matches_workspace(total)
+        rcap = min(total, max(VS, 1))                              # a surface keypoint survives the first unique once: <= VS pairs reach ransac
+        o = RansacOpts(int(options["minPtNum"]), int(options["iterNum"]), float(options["thDist"]), float(options["thInlrRatio"]),
+                       int(bool(options["REFINE"])), 0, int(seed))
+        wsr = L.pcreg_dev_ransac_workspace(rcap, o.iterNum)
+        if getattr(self, "_agg_ws", None) is None or self._agg_ws[0].numel() < wsb or self._agg_ws[1].numel() < wsr:
+            self._agg_ws = (torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev), torch.empty(max(wsr, 256), dtype=torch.uint8, device=dev))
+        ws_a, ws_r = self._agg_ws
+        check(L.pcreg_dev_aggregate_matches(_p(p1), _p(p2), _p(n_dev), total, total, _p(u1), _p(u2), total, 1, None, _p(n_out), _p(ws_a),
+                                            C.c_size_t(ws_a.numel()), sp))                                           # :439-443
+        n1_off = 2 * ((4 * total + 255) // 256 * 256)              # the first unique's count, where include/pcreg.h says the chain leaves it
+        n1 = ws_a[n1_off:n1_off + 4].view(i32)
+        rs = C.sizeof(DevRansacResult)
+        res = torch.zeros(rs // 4, dtype=i32, device=dev)
+        inl = torch.zeros(rcap, dtype=i32, device=dev)
+        check(L.pcreg_dev_ransac(_p(u1), _p(u2), _p(n_out), rcap, total, C.byref(o), None, _p(res), _p(inl), _p(ws_r), C.c_size_t(ws_r.numel()),
+                                 sp))                                                                                # :446-455
+        T16 = torch.zeros(16, dtype=f64, device=dev)
+        info = torch.zeros(2, dtype=i32, device=dev)
+        check(L.pcreg_dev_estimate_transform_indexed(_p(u1), _p(u2), total, _p(inl), 1, _p(res[32:33]), rcap, _p(T16), _p(info), sp))   # :458
+        h = torch.cat([n1, n_out, res, info, T16.view(i32), inl]).cpu().numpy()                                       # ---- the one sync
+        nu1, nu2 = int(h[0]), int(h[1])
+        r = DevRansacResult.from_buffer_copy(h[2:2 + rs // 4].tobytes())
+        empty_final = int(h[3 + rs // 4])
+        Tf = h[4 + rs // 4:36 + rs // 4].copy().view(np.float64).reshape(4, 4, order="F")
+        inliers = h[36 + rs // 4:36 + rs // 4 + r.n_inliers].astype(np.int64)
+        failed = bool(r.failed)
+        return dict(n_total=total, n_unique1=nu1, n_unique2=nu2, T=None if failed else np.array(r.T[:]).reshape(4, 4, order="F"),
+                    inlierIdx=np.zeros(0, np.int64) if failed else inliers, numSuccess=r.num_success, maxInliers=r.max_inliers,
+                    maxInlierRatio=0.0 if failed or nu2 == 0 else 100.0 * r.max_inliers / nu2,
+                    T_final=None if failed or empty_final else Tf, host_syncs=1)
 
     def run_streams(self, par: dict, options: dict, R_desc: float, d_spheres: float = 5.0, min_pts: int = 1400,
                     putative_thresh: int = 170, seed: int = 0, n_streams: int = 8) -> dict:
@@ -335,6 +411,7 @@ class SphereSweep:
                      statsPutative=np.zeros(0, np.int64), statsSuccess=np.zeros(0, np.int64), statsInliers=np.zeros(0, np.int64),
                      statsRatio=np.zeros(0), transforms=[])
         if S == 0:
+            self._agg = None
             return empty
         i32, f64 = torch.int32, torch.float64
         row_off = np.zeros(S + 1, dtype=np.int64); row_off[1:] = np.cumsum(num_desc)
@@ -370,6 +447,17 @@ class SphereSweep:
         return self._finish_sweep(centres, num_desc, row_off, rows_all, feat_all, n_sel, pairs_all, n_pairs, options, putative_thresh, seed)
 
 
+def _good_trials(result: dict, thSucc: float, thInliers: float, thRatio: float, thPutative: float):
+    """:238-239: (the trials' sphere centres, their transforms, the ordinals of the trials that reach the four thresholds and have a
+    transform)"""
+    centres = np.asarray(result["centres"], dtype=np.float64).reshape(-1, 3)[np.asarray(result["trial"], dtype=np.int64)]
+    tf = result["transforms"]
+    mask = ((np.asarray(result["statsSuccess"]) >= thSucc) & (np.asarray(result["statsInliers"]) >= thInliers) &
+            (np.asarray(result["statsRatio"]) >= thRatio) & (np.asarray(result["statsPutative"]) >= thPutative) &
+            np.array([t is not None for t in tf], dtype=bool))
+    return centres, tf, np.nonzero(mask)[0]                                                 # :239
+
+
 def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, thRatio: float = 10, thPutative: float = 170,
                        r: float | None = None, d_spheres: float = 5.0) -> list:
     """completeExperimentFast.m:238-248 and :266-288, the link from a sweep's result to FinalStage.run: keep the trials whose
@@ -378,12 +466,7 @@ def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, t
     locCur the mean of the cluster's centres in double, transCur the transform of the centre nearest to that mean (the first
     one on a tie, as MATLAB's min).  -> [(locCur [3], transCur [4, 4])] in the clusters' order, [] without a good sphere.  A trial
     whose RANSAC failed has no transform and is never kept."""
-    centres = np.asarray(result["centres"], dtype=np.float64).reshape(-1, 3)[np.asarray(result["trial"], dtype=np.int64)]
-    tf = result["transforms"]
-    mask = ((np.asarray(result["statsSuccess"]) >= thSucc) & (np.asarray(result["statsInliers"]) >= thInliers) &
-            (np.asarray(result["statsRatio"]) >= thRatio) & (np.asarray(result["statsPutative"]) >= thPutative) &
-            np.array([t is not None for t in tf], dtype=bool))
-    good = np.nonzero(mask)[0]                                                              # :239
+    centres, tf, good = _good_trials(result, thSucc, thInliers, thRatio, thPutative)
     if len(good) == 0:
         return []
     loc = centres[good]                                                                     # :247
@@ -398,6 +481,26 @@ def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, t
         nearest = int(np.argmin(np.sqrt(((cur - loc_cur) ** 2).sum(axis=1))))               # :286-287, the first minimum
         out.append((loc_cur, np.asarray(tf[good[rows[nearest]]], dtype=np.float64)))        # :288
     return out
+
+
+def largest_cluster(result: dict, thSucc: float = 0, thInliers: float = 28, thRatio: float = 10, thPutative: float = 170,
+                    r: float | None = None, d_spheres: float = 5.0):
+    """completeExperiment.m:379-389: the LARGEST cluster of promising spheres -- promising_clusters' thresholds and clustering (ONE
+    cluster_points call, radius r, default 1.6 * d_spheres); `[~, idx] = max(cluster_size)` takes the first largest, which is the
+    one with the smallest first row.  -> (trials, spheres): the members' trial ordinals (indices into result["trial"] / the stats)
+    and sphere indices (into result["centres"]), int64, in ascending row order; two empty arrays without a good sphere.  A trial
+    whose RANSAC failed is never a member.  `spheres` is what SphereSweep.aggregate takes."""
+    centres, _, good = _good_trials(result, thSucc, thInliers, thRatio, thPutative)
+    if len(good) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    r = 1.6 * float(d_spheres) if r is None else float(r)
+    r32 = np.float32(r)
+    _, cl_off, members = cluster_points(centres[good], r32 * r32)
+    sizes = np.diff(np.asarray(cl_off, dtype=np.int64))
+    c = int(np.argmax(sizes))                                                               # the first maximum, as MATLAB's max
+    rows = np.sort(np.asarray(members[cl_off[c]:cl_off[c + 1]], dtype=np.int64))
+    trials = good[rows].astype(np.int64)
+    return trials, np.asarray(result["trial"], dtype=np.int64)[trials]
 
 
 def quickTF_dev(pts_soa: torch.Tensor, TF: np.ndarray) -> torch.Tensor:
@@ -507,4 +610,4 @@ class FinalStage:
         return out
 
 
-__all__ = ["SphereSweep", "FinalStage", "pcUniformSamples", "quickTF_dev", "refine_by_distance_dev", "invertTF"]
+__all__ = ["SphereSweep", "FinalStage", "pcUniformSamples", "promising_clusters", "largest_cluster", "quickTF_dev", "refine_by_distance_dev", "invertTF"]
