@@ -102,6 +102,11 @@ int  pcreg_debug_match_stats(long long out[8], int reset);
  * pairs (query blocks of 512 x tiles of 512 rows), [3] queries the certificate sent to the exhaustive tail.  Off: no extra
  * work; on: one small launch per search, no host sync.  The read synchronises the device. */
 int  pcreg_debug_knn_stats(long long out[4], int reset);
+/* With pcreg_debug_set("knn_stats", 1): inside the visited tiles the candidate kernel scores 64-row units per wave of 128
+ * queries -- out[0] the (wave, unit) pairs scored, summed over the searches since the last reset, [1] 32 x the
+ * visited (query block, tile) pairs, which is what it scores without the unit rule.  Resets these two only; the read
+ * synchronises the device. */
+int  pcreg_debug_knn_unit_stats(long long out[2], int reset);
 /* With pcreg_debug_set("ransac_stats", 1): the counters of the staged RANSAC chain's bounded second pass summed over the calls
  * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
  * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */

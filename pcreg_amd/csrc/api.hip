@@ -83,7 +83,7 @@ static std::atomic<int> g_debug[kDbgCount];
 int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); }
 // one block of device counters behind a debug key: allocated (zeroed) at the first use while the key is on
 struct Counters { DebugKey key; int n; unsigned long long* dev; };
-static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 4, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr},
+static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 6, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr},
                 g_cluster_stats{kDbgClusterStats, 4, nullptr};
 static unsigned long long* counters_dev(Counters& c) {
     if (!debug_flag(c.key)) return nullptr;
@@ -93,15 +93,17 @@ static unsigned long long* counters_dev(Counters& c) {
     }
     return c.dev;
 }
-static int counters_read(const Counters& c, long long* out, int reset) {
+// words [first, first + count) of the block (count < 0: all of it); a reset clears those words only
+static int counters_read(const Counters& c, long long* out, int reset, int first = 0, int count = -1) {
     PCREG_ARG(out != nullptr);
-    for (int k = 0; k < c.n; ++k) out[k] = 0;
+    if (count < 0) count = c.n - first;
+    for (int k = 0; k < count; ++k) out[k] = 0;
     if (!c.dev) return PCREG_OK;                               // the key was never on
     PCREG_HIP(hipDeviceSynchronize());
     unsigned long long h[8];
-    PCREG_HIP(hipMemcpy(h, c.dev, c.n * sizeof h[0], hipMemcpyDeviceToHost));
-    for (int k = 0; k < c.n; ++k) out[k] = (long long)h[k];
-    if (reset) PCREG_HIP(hipMemset(c.dev, 0, c.n * sizeof h[0]));
+    PCREG_HIP(hipMemcpy(h, c.dev + first, count * sizeof h[0], hipMemcpyDeviceToHost));
+    for (int k = 0; k < count; ++k) out[k] = (long long)h[k];
+    if (reset) PCREG_HIP(hipMemset(c.dev + first, 0, count * sizeof h[0]));
     return PCREG_OK;
 }
 unsigned long long* match_stats_dev() { return counters_dev(g_match_stats); }
@@ -126,7 +128,8 @@ int pcreg_debug_set(const char* key, int value) {
 }
 
 int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counters_read(pcreg::g_match_stats, out, reset); }
-int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset); }
+int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 0, 4); }
+int pcreg_debug_knn_unit_stats(long long out[2], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 4, 2); }
 int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset); }
 int pcreg_debug_cluster_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_cluster_stats, out, reset); }
 

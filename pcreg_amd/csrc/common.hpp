@@ -101,6 +101,7 @@ int debug_flag(DebugKey k);
 unsigned long long* match_stats_dev();
 // Device counters of the point search (knn_fast.hip), or null while "knn_stats" is off:
 //   [0] searches   [1] visited (query block, model tile) pairs   [2] nominal pairs (q_blocks x n_tiles)   [3] queries sent to the tail
+//   [4] (wave, 64-row unit) pairs scored inside the visited tiles   [5] 32 x visited pairs (pcreg_debug_knn_unit_stats reads [4], [5])
 unsigned long long* knn_stats_dev();
 // Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
 //   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
@@ -167,6 +168,7 @@ struct ModelView {
     // the rows in spatial order: perm[sorted row] = row of m, an fp32 SoA copy (ld = M), one box per f16 tile; the
     // ordering grid's counters
     int32_t* perm; float* ms; float* tbox; int32_t* sort_cnt;
+    float* ubox;               // one box per UNIT of 64 consecutive sorted rows, [n_tiles * 8][6]; an empty unit holds (+inf, -inf)
 };
 size_t model_prep_bytes(int M);
 ModelView model_view(const float* m, int M, int ldm, void* block);
@@ -178,6 +180,7 @@ struct SearchWs {
     void* ug_prep; float* ug_part; int32_t* ug_cnt; void* ug_slots; int ug_cells, ug_nparts;
     int32_t* qcnt; int32_t* qperm; float* dk;          // the call's query order (counters, slot -> query) and seed distances
     int32_t* n_vis; int32_t* vis_list;                 // the visit plan: tiles to visit per query block, [q_blocks] and [q_blocks][n_tiles] (inside tail_idx's slot)
+    uint32_t* vis_mask;                                // ... and per list position the units each candidate wave scores, [q_blocks][n_tiles] (same slot)
 };
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes);
 size_t search_ws_bytes(int Q, int M);

@@ -55,7 +55,7 @@ void knn_f16_shape(int Q, int M, int target_blocks, int* q_blocks, int* W);
 int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsigned* rm2, void* mtiles, int32_t* seed_cnt,
                           void* seed_slots, hipStream_t st);
 int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
-                              const void* mtiles, const float* tbox, int cull, int32_t* n_vis, int32_t* vis_list, unsigned* gthr,
+                              const void* mtiles, const float* tbox, const float* ubox, int cull, int32_t* n_vis, int32_t* vis_list, uint32_t* vis_mask, unsigned* gthr,
                               void* cand_ent, int32_t* cand_cnt, void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part,
                               int ug_nparts, int ug_cells, void* ug_prep, int* W_out, hipStream_t st);
 
@@ -179,14 +179,27 @@ __global__ __launch_bounds__(kBlock) void model_order_scatter_kernel(const float
         perm[d] = i; ms[d] = x; ms[d + (size_t)M] = y; ms[d + 2 * (size_t)M] = z;
     }
 }
-// P4: the exact box of each tile of kT16 sorted rows (padding rows excluded); one workgroup per tile
-__global__ __launch_bounds__(kBlock) void tile_box_kernel(const float* __restrict__ ms, int M, float* __restrict__ tbox) {
+// P4: the exact box of each tile of kT16 sorted rows (padding rows excluded), and of each of its UNITS of 64 consecutive rows
+// (ubox [n_tiles * kT16 / 64][6]; a partly filled unit's box covers its existing rows, an empty one holds (+inf, -inf): the
+// unit rule of knn_plan_kernel never keeps it); one workgroup per tile, a wave's pass over 64 rows is one unit
+__global__ __launch_bounds__(kBlock) void tile_box_kernel(const float* __restrict__ ms, int M, float* __restrict__ tbox, float* __restrict__ ubox) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int r = threadIdx.x; r < kT16; r += kBlock) {
         const int i = blockIdx.x * kT16 + r;
+        float ulo[3] = {INFINITY, INFINITY, INFINITY}, uhi[3] = {-INFINITY, -INFINITY, -INFINITY};
         if (i < M) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { const float v = ms[i + (size_t)c * M]; lo[c] = fminf(lo[c], v); hi[c] = fmaxf(hi[c], v); }
+            for (int c = 0; c < 3; ++c) { ulo[c] = uhi[c] = ms[i + (size_t)c * M]; lo[c] = fminf(lo[c], ulo[c]); hi[c] = fmaxf(hi[c], uhi[c]); }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { ulo[c] = fminf(ulo[c], __shfl_xor(ulo[c], o)); uhi[c] = fmaxf(uhi[c], __shfl_xor(uhi[c], o)); }
+        }
+        if ((threadIdx.x & 63) == 0) {
+            float* ub = ubox + ((size_t)blockIdx.x * (kT16 / 64) + (size_t)(r >> 6)) * 6;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { ub[c] = ulo[c]; ub[3 + c] = uhi[c]; }
         }
     }
     __shared__ float s[kBlock / 64][6];
@@ -782,6 +795,7 @@ __global__ void knn_stats_kernel(const SearchCounters* __restrict__ ctr, long lo
     for (int k = 0; k < kVisitSlots; ++k) nv += ctr->visited[k];
     atomicAdd(&stats[0], 1ull); atomicAdd(&stats[1], (unsigned long long)nv);         // (searches on other streams add too)
     atomicAdd(&stats[2], (unsigned long long)nominal); atomicAdd(&stats[3], (unsigned long long)ctr->n_flag);
+    atomicAdd(&stats[4], (unsigned long long)(unsigned)ctr->units); atomicAdd(&stats[5], 32ull * (unsigned long long)nv);
 }
 
 constexpr int kSeedMinM = 16 * 1024;             // below this the lists settle within the first tiles anyway
@@ -794,7 +808,9 @@ size_t seed_cell_cap(int M) { return std::min<size_t>((size_t)kSeedMaxCells, std
 // The prepared block, walked once.  sort_cnt and seed_cnt adjoin (model_bbox_partial_kernel clears both in one go), so the
 // ordering grid's counters take exactly their bytes.
 static size_t n_f16_tiles(int M) { return (size_t)((M > 0 ? M : 0) + kT16 - 1) / kT16; }
-static ModelView model_layout(const float* m, int M, int ldm, void* block, size_t* bytes) {
+static size_t ubox_floats(int M) { return std::max<size_t>(n_f16_tiles(M), 1) * (kT16 / 64) * 6; }
+// own_ubox = false: the caller keeps the units' boxes elsewhere (the search without a handle, below)
+static ModelView model_layout(const float* m, int M, int ldm, void* block, size_t* bytes, bool own_ubox = true) {
     const size_t mm = (size_t)(M > 0 ? M : 1);
     WsWalk w(block);
     ModelView v{};
@@ -812,6 +828,7 @@ static ModelView model_layout(const float* m, int M, int ldm, void* block, size_
     v.perm = w.take<int32_t>(mm);
     v.ms = w.take<float>(mm * 3);                                  // sorted fp32 SoA copy
     v.tbox = w.take<float>(std::max<size_t>(n_f16_tiles(M), 1) * 6);       // one box per f16 tile
+    if (own_ubox) v.ubox = w.take<float>(ubox_floats(M));                  // ... and per unit of 64 rows
     *bytes = w.bytes(); return v;
 }
 size_t model_prep_bytes(int M) { size_t b; (void)model_layout(nullptr, M, 0, nullptr, &b); return b; }
@@ -832,13 +849,14 @@ int launch_model_prepare(const ModelView& v, hipStream_t st) {
     PCREG_HIP(hipGetLastError());
     int rc = launch_prep_model_f16(v.ms, v.M, v.M, v.prep, v.rm2, v.tiles, v.seeded ? v.seed_cnt : nullptr, v.seed_slots, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)n_f16_tiles(v.M)), dim3(kBlock), 0, st, (const float*)v.ms, v.M, v.tbox);
+    hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)n_f16_tiles(v.M)), dim3(kBlock), 0, st, (const float*)v.ms, v.M, v.tbox, v.ubox);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
 
 // ---- the per-call workspace of a search (and of the match stage that follows it) ----------------------------------
 static constexpr int kTargetBlocks = 4096;
+static size_t tail_many(size_t qq) { return (size_t)(kTailGrid + (qq + kTailQ - 1) / kTailQ) * kTailQ * 2; }     // the many-form's partials
 SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     SearchWs s{};
     const size_t qq = (size_t)(Q > 0 ? Q : 1);
@@ -852,10 +870,12 @@ SearchWs search_ws_layout(int Q, int M, void* base, size_t* bytes) {
     // The tail's partials (many-form only; the few-form keeps none) and the visit plan (knn_plan_kernel: per query block the
     // number of tiles to visit, then their ascending list) share one slot: the plan is dead once the candidate kernel has run,
     // two launches before the tail writes a partial.
-    const size_t many = (size_t)(kTailGrid + (qq + kTailQ - 1) / kTailQ) * kTailQ * 2;
-    const size_t plan_head = align_up((size_t)q_blocks * 4, 256) / 4, plan = plan_head + (size_t)q_blocks * std::max<size_t>(n_f16_tiles(M), 1);
+    const size_t many = tail_many(qq);
+    const size_t plan_head = align_up((size_t)q_blocks * 4, 256) / 4, plan_list = (size_t)q_blocks * std::max<size_t>(n_f16_tiles(M), 1),
+                 plan = plan_head + 2 * plan_list;                     // the list, then one unit mask per list position
     s.tail_idx = w.take<int32_t>(std::max(many, plan)); s.tail_dist = w.take<float>(many);
     s.n_vis = s.tail_idx; s.vis_list = s.tail_idx ? s.tail_idx + plan_head : nullptr;
+    s.vis_mask = s.tail_idx ? (uint32_t*)(s.tail_idx + plan_head + plan_list) : nullptr;
     s.ug_cells = (int)ug_cells_cap(Q);
     s.ug_nparts = (int)((qq * 8 + kBlock - 1) / kBlock);
     s.ug_prep = w.take_bytes(256);
@@ -891,7 +911,7 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     const int variant = PCREG_EXP_ENV("PCREG_KNN_VARIANT", 40);      // 41: timing-only form of the candidate kernel (EXPERIMENTS builds)
     const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS workgroups)
     const int cull = (debug_flag(kDbgKnnNoCull) || PCREG_EXP_ENV("PCREG_KNN_NOCULL", 0)) ? 0 : 1;    // "knn_nocull": visit every tile
-    int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, cull, s.n_vis, s.vis_list, s.gthr, s.cand_ent, s.cand_cnt, ctr,
+    int rc = launch_knn_candidates_f16(q, Q, ldq, s.qperm, s.dk, v.M, v.prep, v.tiles, v.tbox, v.ubox, cull, s.n_vis, s.vis_list, s.vis_mask, s.gthr, s.cand_ent, s.cand_cnt, ctr,
                                        target_env > 0 ? target_env : kTargetBlocks, variant == 41, timed, grid ? s.ug_part : nullptr,
                                        s.ug_nparts, s.ug_cells, grid ? s.ug_prep : nullptr, &W, st);
     if (rc) return rc;
@@ -955,7 +975,14 @@ int search_export(const void* ws, size_t ws_bytes, int Q, int M, int32_t* qperm,
 }
 
 // ---- the search without a handle: prepare into the caller's workspace, then search ---------------------------------
-size_t knn2_points_fast_workspace_bytes(int Q, int M) { return search_ws_bytes(Q, M) + model_prep_bytes(M); }
+// The model is prepared and searched within one call here, so the units' boxes (read by knn_plan_kernel only) go where the
+// call's workspace has room that is still unused then: tail_dist, which nothing touches before knn_tail_kernel, three
+// launches after the plan.  Only a model whose boxes outgrow that slot (tens of millions of rows) takes bytes of its own.
+static bool ubox_in_tail(int Q, int M) { return ubox_floats(M) <= tail_many((size_t)(Q > 0 ? Q : 1)); }
+size_t knn2_points_fast_workspace_bytes(int Q, int M) {
+    size_t b; (void)model_layout(nullptr, M, 0, nullptr, &b, !ubox_in_tail(Q, M));
+    return search_ws_bytes(Q, M) + b;
+}
 
 int launch_knn2_points_fast_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int32_t idx_base,
                                 int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st, bool timed) {
@@ -964,7 +991,9 @@ int launch_knn2_points_fast_f32(const float* q, int Q, int ldq, const float* m, 
     const size_t need = knn2_points_fast_workspace_bytes(Q, M);
     if (ws_bytes < need) { set_error("knn (fast) workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
     const size_t sb = search_ws_bytes(Q, M);
-    const ModelView v = model_view(m, M, ldm, (char*)ws + sb);
+    size_t mb;
+    ModelView v = model_layout(m, M, ldm, (char*)ws + sb, &mb, !ubox_in_tail(Q, M));
+    if (!v.ubox) { size_t b2; v.ubox = search_ws_layout(Q, M, ws, &b2).tail_dist; }
     int rc = launch_model_prepare(v, st);
     if (rc) return rc;
     return launch_model_search(v, q, Q, ldq, idx_base, idx, dist, ws, sb, false, timed, st);

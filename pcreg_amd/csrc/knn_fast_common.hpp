@@ -121,7 +121,8 @@ struct SearchCounters {
     int32_t n_flag;                  // unproven queries (knn_finalize_kernel -> knn_tail_kernel)
     int32_t ticket;                  // match_finish_kernel's workgroup tickets
     int32_t finished;                // ... and how many of its workgroups are through (the last one clears ticket / status again)
-    int32_t pad[29];
+    int32_t units;                   // (candidate wave, 64-row unit) pairs the visit plan marks for scoring (knn_plan_kernel)
+    int32_t pad[28];
     int32_t visited[kVisitSlots];    // (query block, model tile) pairs the candidate kernel scored, spread over words by workgroup
     int32_t done[kMaxQTiles];        // tail (many-form): arrivals per tile of listed queries
     int32_t status[kMatchMaxBlocks]; // match_finish_kernel: per-workgroup kept counts (ready bit 31)

@@ -138,6 +138,11 @@ __device__ void ug_reduce_boxes(const float* __restrict__ part /*[n][6]*/, int n
 // ascending list of the tiles to visit, vis_list[qb * n_tiles + 0 .. n_vis[qb]), and their number.  The candidate kernel's
 // workgroups share the list: workgroup w of the block's first W_eff = plan_live(n_vis, W) walks positions w, w + W_eff, ..
 // and the others leave after reading n_vis.  kPlanC is the tiles-per-workgroup target that sizes W_eff.
+// The same rule, one level down, then says what the candidate kernel scores INSIDE a listed tile: vis_mask[qb * n_tiles + p]
+// belongs to list position p, its byte v to candidate wave v (slots [128 v, 128 v + 128) of the block), bit s of the byte to
+// the tile's s-th UNIT of 64 rows.  A bit is clear when the rule skips the unit's box (ubox) against the box and the largest
+// seed distance of that wave's scored queries; a wave with an unseeded query keeps every unit, a wave without a scored query
+// none, and cull == 0 keeps everything.
 #ifndef PCREG_PLAN_C
 #define PCREG_PLAN_C 4
 #endif
@@ -148,20 +153,25 @@ __host__ __device__ __forceinline__ int plan_live(int n_vis, int W) {          /
     return we < W ? we : W;
 }
 __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
-                                                          const float* __restrict__ dk, const float* __restrict__ tbox, int n_tiles, int cull,
+                                                          const float* __restrict__ dk, const float* __restrict__ tbox,
+                                                          const float* __restrict__ ubox, int n_tiles, int cull,
                                                           const Prep* __restrict__ prep, int32_t* __restrict__ n_vis,
-                                                          int32_t* __restrict__ vis_list, SearchCounters* __restrict__ ctr) {
+                                                          int32_t* __restrict__ vis_list, uint32_t* __restrict__ vis_mask,
+                                                          SearchCounters* __restrict__ ctr) {
     __shared__ float s_red[kBlock / 64][8], s_box[8];
     __shared__ int s_wcnt[kBlock / 64];
+    constexpr int kListLds = 2048;                // the head of the block's list stays in LDS for the mask pass (a bench block lists 37-181 tiles)
+    __shared__ int s_tl[kListLds];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qb = (int)blockIdx.x;
     const float sg = prep->sigma, cx = prep->cx, cy = prep->cy, cz = prep->cz;
     const bool scale_ok = scale_usable(prep);
     // the block's box and largest seed distance over its SCORED queries (the candidate kernel's own test: a query it does
-    // not score has no say); an unseeded query (+inf) turns culling off for the block
+    // not score has no say); an unseeded query (+inf) turns culling off for the block.  Wave v reads the slots of candidate
+    // wave v, so that its partial (s_red[v]) is that wave's own box and distance for the unit masks below
     float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY}, bdk = 0.0f;
 #pragma unroll
     for (int g = 0; g < 512 / kBlock; ++g) {
-        const int slot = qb * 512 + g * kBlock + tid;
+        const int slot = qb * 512 + wave * (512 / (kBlock / 64)) + g * 64 + lane;
         if (slot < Q) {
             const int qi = qperm[slot];
             const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
@@ -205,17 +215,19 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
     // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to any
     // point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of 32u, and no
     // bound at all below 1e-30 (subnormal squares)
-    auto skipped = [&](const float2 a, const float2 b, const float2 c) {       // the box: lo = (a.x, a.y, b.x), hi = (b.y, c.x, c.y)
+    auto skipped_by = [](const float2 a, const float2 b, const float2 c,        // the box: lo = (a.x, a.y, b.x), hi = (b.y, c.x, c.y)
+                         const double (&qlo)[3], const double (&qhi)[3], const float D) {
         const float lo[3] = {a.x, a.y, b.x}, hi[3] = {b.y, c.x, c.y};
         double g2 = 0.0;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            const double gap = fmax(0.0, fmax((double)lo[d] - bhi_d[d], blo_d[d] - (double)hi[d]));
+            const double gap = fmax(0.0, fmax((double)lo[d] - qhi[d], qlo[d] - (double)hi[d]));
             g2 += gap * gap;
         }
         const double u = 5.9604644775390625e-08;
-        return g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)bdk_b;
+        return g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D;
     };
+    auto skipped = [&](const float2 a, const float2 b, const float2 c) { return skipped_by(a, b, c, blo_d, bhi_d, bdk_b); };
     constexpr int kPlanBatch = 8;
     // The verdicts of the thread's first 64 tiles; later ones are tested again when the list is written.  That second path
     // needs per > 64, more than 16 384 tiles (8.4 M rows): no test reaches it.  It applies the same skipped() to the same
@@ -253,12 +265,56 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
             if (k < 64) visit = (keep >> k) & 1ull;
             else { const float2* p = (const float2*)(tbox + (size_t)(t0 + k) * 6); visit = !skipped(p[0], p[1], p[2]); }
         }
-        if (visit) list[pos++] = t0 + k;
+        if (visit) {
+            if (pos < kListLds) s_tl[pos] = t0 + k;
+            list[pos++] = t0 + k;
+        }
     }
     if (tid == 0) {
         n_vis[qb] = n;
         if (n > 0) atomicAdd(&ctr->visited[qb % kVisitSlots], n);       // (block, tile) pairs the candidate kernel scores
     }
+    // ---- the unit masks of the n listed tiles.  Lane l of a wave owns bit l % 32 (candidate wave (l % 32) / 8, unit l % 8) of
+    // list position 2 * wave + l / 32 of each group of eight positions; one ballot yields both words.  kMaskBatch groups at a
+    // time: the tile numbers first (from LDS while the list fits there, so that only the box loads are a memory round trip),
+    // then every box, then the tests.
+    uint32_t* mask = vis_mask + (size_t)qb * n_tiles;
+    int units = 0;
+    if (cull == 0) {
+        for (int p = tid; p < n; p += kBlock) mask[p] = 0xFFFFFFFFu;
+        if (tid == 0) units = 32 * n;
+    } else if (n > 0) {
+        __syncthreads();                                                   // the list, written by other threads above
+        constexpr int kUnits = kT16 / 64, kMaskBatch = 8;
+        const bool in_lds = n <= kListLds;
+        static_assert(kUnits == 8 && kBlock / 64 == 4, "a mask word is four waves x eight units");
+        const int bit = lane & 31, cw = bit >> 3, unit = bit & 7, sub = 2 * wave + (lane >> 5);
+        const double wlo[3] = {(double)s_red[cw][0], (double)s_red[cw][1], (double)s_red[cw][2]};
+        const double whi[3] = {(double)s_red[cw][3], (double)s_red[cw][4], (double)s_red[cw][5]};
+        const float wdk = s_red[cw][6];
+        const bool none = !(s_red[cw][0] <= s_red[cw][3]);                 // no scored query in that wave
+        const bool all = !(wdk < INFINITY);                                // an unseeded one: it meets every point
+        for (int p0 = 0; p0 < n; p0 += 8 * kMaskBatch) {
+            int tl[kMaskBatch];
+            float2 bx[kMaskBatch][3];
+#pragma unroll
+            for (int k = 0; k < kMaskBatch; ++k) { const int pp = min(p0 + 8 * k + sub, n - 1); tl[k] = in_lds ? s_tl[min(pp, kListLds - 1)] : list[pp]; }
+#pragma unroll
+            for (int k = 0; k < kMaskBatch; ++k) {
+                const float2* bp = (const float2*)(ubox + ((size_t)tl[k] * kUnits + unit) * 6);
+                bx[k][0] = bp[0]; bx[k][1] = bp[1]; bx[k][2] = bp[2];
+            }
+#pragma unroll
+            for (int k = 0; k < kMaskBatch; ++k) {
+                const int p = p0 + 8 * k + sub;
+                const bool keep = p < n && !none && (all || !skipped_by(bx[k][0], bx[k][1], bx[k][2], wlo, whi, wdk));
+                const unsigned long long both = __builtin_amdgcn_ballot_w64(keep);
+                if (bit == 0 && p < n) mask[p] = (uint32_t)(both >> (lane & 32));
+                units += __popcll(both);
+            }
+        }
+    }
+    if (lane == 0 && units > 0) atomicAdd(&ctr->units, units);
 }
 
 // ---- the candidate kernel: software-pipelined ------------------------------------------------------
@@ -284,8 +340,8 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
 template <int QG, bool DRY>   // DRY: timing only (no compare, no lists; PCREG_KNN_VARIANT=41)
 __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2 ? 5 : (QG <= 4 ? 4 : 2)))) void knn_candidates_f16_pipe_kernel(
     const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
-    const uint4* __restrict__ mt, const int32_t* __restrict__ n_vis, const int32_t* __restrict__ vis_list, int n_tiles, int W,
-    const Prep* __restrict__ prep, unsigned* __restrict__ gthr, uint2* __restrict__ cand_ent, int32_t* __restrict__ cand_cnt,
+    const uint4* __restrict__ mt, const int32_t* __restrict__ n_vis, const int32_t* __restrict__ vis_list,
+    const uint32_t* __restrict__ vis_mask, int n_tiles, int W, const Prep* __restrict__ prep, unsigned* __restrict__ gthr, uint2* __restrict__ cand_ent, int32_t* __restrict__ cand_cnt,
     int cap, const float* __restrict__ ug_part, int ug_nparts, int ug_cells, UgPrep* __restrict__ ug_prep) {
     static_assert(QG % 2 == 0, "two accumulator tiles alternate: an even number of steps per sub-tile");
     if (blockIdx.x == gridDim.x - 1 && ug_prep != nullptr) {     // the surplus workgroup (the launcher adds it): query-grid geometry
@@ -301,6 +357,11 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
     if (w >= W_eff) return;
     __shared__ __attribute__((aligned(16))) uint4 tile[2][2 * kT16];
     __shared__ int s_list[kBlock];
+    __shared__ unsigned s_mask[kBlock];
+    __shared__ int s_keep[kBlock / 64];
+    // the threshold word each lane saw last (read at a refresh and at the end only): in LDS, not in four registers that
+    // would be live across the whole walk
+    __shared__ unsigned s_gseen[QG][kBlock];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, half = lane >> 5;
     // query SLOTS: the call's queries in spatial order (qperm), so that the 512 slots of a block are compact in space
@@ -310,7 +371,6 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
 
     f16x8 bq[QG];
     float thr[QG];
-    unsigned gseen[QG];
     Cand cand[QG];
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
@@ -333,50 +393,73 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         bq[g] = half == 0 ? f16x8{Xh, Xh, Xl, Xl, Yh, Yh, Yl, Yl} : f16x8{Zh, Zh, Zl, Zl, o1, o1, o1, (_Float16)0.0f};
 #pragma unroll
         for (int k = 0; k < KC; ++k) { cand[g].s[k] = INFINITY; cand[g].i[k] = -1; }
-        thr[g] = INFINITY; gseen[g] = 0xFFFFFFFFu;
+        thr[g] = INFINITY; s_gseen[g][threadIdx.x] = 0xFFFFFFFFu;
     }
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)&tile[0][0];
     int walked = 0;                               // tiles walked so far (the threshold refresh's cadence)
     const f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    constexpr int kSubs = kT16 / 32;
-#define PCREG_TILE_DMA(T, BUF)                                                                                     \
+    // of a tile's sixteen 1-KB segments (k-half seg / 8, unit seg % 8) only those of a unit some wave scores (UM: the union
+    // of the mask's four bytes) are fetched.  The segment's address stays a scalar (the empty asm keeps it from being folded
+    // into per-segment vector addresses, which cost eight registers); the lanes add their 16 bytes
+    const unsigned lane_off = (unsigned)lane * 16u;
+#define PCREG_TILE_DMA(T, BUF, UM)                                                                                 \
     _Pragma("unroll") for (int k = 0; k < kT16 / 128; ++k) {                                                        \
         const int seg = k * 4 + wave;                                                                              \
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mt + (size_t)(T) * (2 * kT16) + seg * 64 + lane), \
-                                         (__attribute__((address_space(3))) void*)(&tile[BUF][seg * 64]), 16, 0, 0);   \
+        if (((UM) >> (seg & 7)) & 1u) {                                                                            \
+            const char* sb = (const char*)(mt + (size_t)(T) * (2 * kT16) + seg * 64);                               \
+            asm volatile("" : "+s"(sb));                                                                           \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + lane_off),       \
+                                             (__attribute__((address_space(3))) void*)(&tile[BUF][seg * 64]), 16, 0, 0); \
+        }                                                                                                          \
     }
     // rounds of kBlock plan positions: the tiles of this workgroup's positions are listed in LDS (ascending, as in the plan)
+    // with their unit masks; a position no wave scores a unit of drops out here (no DMA, no barrier round), the others move up
+    static_assert(kT16 == 512 && kBlock == 256, "a mask word is four waves x eight units of 64 rows");
+    auto units_of = [](unsigned m) { return (m | (m >> 8) | (m >> 16) | (m >> 24)) & 0xFFu; };
     const int my_n = (nvis - w + W_eff - 1) / W_eff;
     const int32_t* vlist = vis_list + (size_t)qb * n_tiles;
+    const uint32_t* vmask = vis_mask + (size_t)qb * n_tiles;
     for (int r0 = 0; r0 < my_n; r0 += kBlock) {
-    const int ntile = __builtin_amdgcn_readfirstlane(min(kBlock, my_n - r0));
-    if (tid < ntile) s_list[tid] = vlist[w + W_eff * (r0 + tid)];
+    int tl = 0; unsigned mk = 0u;
+    if (tid < min(kBlock, my_n - r0)) { const int p = w + W_eff * (r0 + tid); tl = vlist[p]; mk = vmask[p]; }
+    const unsigned long long kept = __builtin_amdgcn_ballot_w64(mk != 0u);
+    if (lane == 0) s_keep[wave] = __popcll(kept);
     __syncthreads();
-    if (ntile > 0) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[0]), 0) }
+    int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u)), nk = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) { at += k < wave ? s_keep[k] : 0; nk += s_keep[k]; }
+    const int ntile = __builtin_amdgcn_readfirstlane(nk);
+    if (mk != 0u) { s_list[at] = tl; s_mask[at] = mk; }
+    __syncthreads();
+    if (ntile > 0) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[0]), 0, units_of(__builtin_amdgcn_readfirstlane(s_mask[0]))) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int t = 0; t < ntile; ++t, ++walked) {
         const int tcur = __builtin_amdgcn_readfirstlane(s_list[t]);
-        if (t + 1 < ntile) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[t + 1]), (t + 1) & 1) }
+        // this wave's units of the tile, walked lowest first: rem holds those still to come
+        unsigned rem = (__builtin_amdgcn_readfirstlane(s_mask[t]) >> (8 * wave)) & 0xFFu;
+        if (t + 1 < ntile) { PCREG_TILE_DMA(__builtin_amdgcn_readfirstlane(s_list[t + 1]), (t + 1) & 1, units_of(__builtin_amdgcn_readfirstlane(s_mask[t + 1]))) }
         if ((walked & (kRefresh - 1)) == 0) {     // the block's workgroups share one monotone threshold word per query (unscaled units)
 #pragma unroll
             for (int g = 0; g < QG; ++g) {
                 const int slot = q_base + g * 32 + col;
                 if (slot < Q) {
                     const int qi = qperm[slot];
-                    if (cand[g].s[KC - 1] < INFINITY) { unsigned k = f2ord(cand[g].s[KC - 1] * inv2); if (k < gseen[g]) atomicMin(&gthr[qi], k); }
+                    if (cand[g].s[KC - 1] < INFINITY) { unsigned k = f2ord(cand[g].s[KC - 1] * inv2); if (k < s_gseen[g][threadIdx.x]) atomicMin(&gthr[qi], k); }
                     unsigned gv = __hip_atomic_load(&gthr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    gseen[g] = gv;
+                    s_gseen[g][threadIdx.x] = gv;
                     thr[g] = fminf(fminf(thr[g], ord2f(gv) * sg2), __shfl_xor(thr[g], 32));       // and the sibling half's list
                 }
             }
         }
         const unsigned cur = lds_base + (unsigned)((t & 1) * (2 * kT16) + half * kT16 + col) * 16u;
         const int jt = tcur * kT16 + 4 * half;
+        if (rem != 0u) {                          // (a wave without a unit here goes straight to the tile's barrier)
+        const int n_units = __builtin_popcount(rem);
         f16x8 av;
         {
             u32x4 a0;
-            asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(a0) : "v"(cur) : "memory");
+            asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(a0) : "v"(cur + (unsigned)__builtin_ctz(rem) * 1024u) : "memory");
             av = __builtin_bit_cast(f16x8, a0);
         }
         f32x16 dprev = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bq[0], zero, 0, 0, 0);
@@ -389,7 +472,11 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll 1
-        for (int sub = 0; sub < kSubs; sub += 2) {
+        for (int iu = 0; iu < n_units; ++iu) {     // one unit = two sub-tiles of 32 rows: sub = 2 u and 2 u + 1
+            const int u = __builtin_ctz(rem);
+            rem &= rem - 1u;
+            const int un = rem != 0u ? __builtin_ctz(rem) : u;        // the next unit of this wave's byte (none: this one again)
+            const int sub = 2 * u;
             // ONE threshold test per two sub-tiles: the first step only keeps its minimum (mn0), the second folds it into
             // its tree as the 17th value (8 v_min3, the 16 scores alone take 7 v_min3 + 1 v_min) and tests min(mn0, mn1);
             // the rare path gets mn1 back by issuing that one product again (same operands, same bits)
@@ -397,10 +484,11 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
             float mn0[QG];
 #pragma unroll
             for (int ss = 0; ss < 2; ++ss) {
-                // the next sub-tile's A operand: issued now, waited for in this half's last step (after sub 15 it
-                // fetches sub 15 again: harmless, keeps the body branch-free)
+                // the next sub-tile's A operand: issued now, waited for in this half's last step -- the unit's second
+                // sub-tile, then the first of the wave's next unit (after its last unit it fetches that unit's first
+                // sub-tile again: harmless, keeps the body branch-free)
                 u32x4 an;
-                asm volatile("ds_read_b128 %0, %1" : "=v"(an) : "v"(cur + (unsigned)min(sub + ss + 1, kSubs - 1) * 512u) : "memory");
+                asm volatile("ds_read_b128 %0, %1" : "=v"(an) : "v"(cur + (unsigned)(ss == 0 ? sub + 1 : 2 * un) * 512u) : "memory");
                 f16x8 avn = av;
 #pragma unroll
                 for (int g = 0; g < QG; ++g) {
@@ -410,7 +498,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
                     } else {
                         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(an) :: "memory");
                         avn = __builtin_bit_cast(f16x8, an);
-                        dnext = __builtin_amdgcn_mfma_f32_32x32x16_f16(avn, bq[0], zero, 0, 0, 0);    // after sub 15: a product nobody reads
+                        dnext = __builtin_amdgcn_mfma_f32_32x32x16_f16(avn, bq[0], zero, 0, 0, 0);    // after the last unit: a product nobody reads
                     }
                     const f32x16 d = dprev;
                     const float m0 = fminf(fminf(d[0], d[1]), d[2]), m1 = fminf(fminf(d[3], d[4]), d[5]);
@@ -453,6 +541,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
                 }
             }
         }
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -481,7 +570,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         }
         if (slot < Q && half == 0 && mine.i[0] >= 0) {
             const int qi = qperm[slot];
-            if (mine.s[KC - 1] < INFINITY) { unsigned k = f2ord(mine.s[KC - 1] * inv2); if (k < gseen[g]) atomicMin(&gthr[qi], k); }
+            if (mine.s[KC - 1] < INFINITY) { unsigned k = f2ord(mine.s[KC - 1] * inv2); if (k < s_gseen[g][threadIdx.x]) atomicMin(&gthr[qi], k); }
             int nv = 0;
 #pragma unroll
             for (int k = 0; k < KC; ++k) nv += mine.i[k] >= 0;
@@ -548,20 +637,21 @@ int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsi
 
 // The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it).  qperm: query
 // slot -> query row (spatial order); dk: each query's seed distance; tbox: the model tiles' boxes; cull = 0 visits every
-// tile.  n_vis [q_blocks], vis_list [q_blocks * n_tiles]: the visit plan, written by knn_plan_kernel (launched here) and read
+// tile; ubox: the boxes of the tiles' 64-row units.  n_vis [q_blocks], vis_list and vis_mask [q_blocks * n_tiles]: the visit
+// plan and its unit masks, written by knn_plan_kernel (launched here) and read
 // by the candidate kernel.  ug_*: the query-grid by-product (null: none).  Returns W through W_out; list capacity per
 // query = W * KC.
 int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qperm, const float* dk, int M, const void* prep,
-                              const void* mtiles, const float* tbox, int cull, int32_t* n_vis, int32_t* vis_list, unsigned* gthr,
-                              void* cand_ent, int32_t* cand_cnt, void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part,
+                              const void* mtiles, const float* tbox, const float* ubox, int cull, int32_t* n_vis, int32_t* vis_list,
+                              uint32_t* vis_mask, unsigned* gthr, void* cand_ent, int32_t* cand_cnt, void* ctr, int target_blocks, bool dry, bool timed, const float* ug_part,
                               int ug_nparts, int ug_cells, void* ug_prep, int* W_out, hipStream_t st) {
     int q_blocks, W;
     knn_f16_shape(Q, M, target_blocks, &q_blocks, &W);
     *W_out = W;
     if (M <= 0 || Q <= 0) return PCREG_OK;
     const int n_tiles = (M + kT16 - 1) / kT16;
-    hipLaunchKernelGGL(knn_plan_kernel, dim3(q_blocks), dim3(kBlock), 0, st, q, Q, ldq, qperm, dk, tbox, n_tiles, cull, (const Prep*)prep,
-                       n_vis, vis_list, (SearchCounters*)ctr);
+    hipLaunchKernelGGL(knn_plan_kernel, dim3(q_blocks), dim3(kBlock), 0, st, q, Q, ldq, qperm, dk, tbox, ubox, n_tiles, cull, (const Prep*)prep,
+                       n_vis, vis_list, vis_mask, (SearchCounters*)ctr);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_time_on && timed) {
         if (g_time_used == g_time_ev.size()) { hipEvent_t a, b; PCREG_HIP(hipEventCreate(&a)); PCREG_HIP(hipEventCreate(&b)); g_time_ev.emplace_back(a, b); }
@@ -570,7 +660,7 @@ int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qpe
     }
     const int aux = ug_prep != nullptr ? 1 : 0;
 #define PCREG_F16_LAUNCH(QGV, DRYV) hipLaunchKernelGGL((knn_candidates_f16_pipe_kernel<QGV, DRYV>), dim3(q_blocks * W + aux), dim3(kBlock), 0, st, q, Q, ldq, \
-                           qperm, (const uint4*)mtiles, (const int32_t*)n_vis, (const int32_t*)vis_list, n_tiles, W, (const Prep*)prep, gthr, \
+                           qperm, (const uint4*)mtiles, (const int32_t*)n_vis, (const int32_t*)vis_list, (const uint32_t*)vis_mask, n_tiles, W, (const Prep*)prep, gthr, \
                            (uint2*)cand_ent, cand_cnt, W * KC, ug_part, ug_nparts, ug_cells, (UgPrep*)ug_prep)
 #ifdef PCREG_EXPERIMENTS
     if (dry) PCREG_F16_LAUNCH(4, true); else
