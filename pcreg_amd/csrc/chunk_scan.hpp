@@ -1,0 +1,50 @@
+// pcreg_amd/csrc/chunk_scan.hpp -- the two-launch chunk scan, its one definition: an exclusive scan of one value
+// per element over any number of chunks of kScanChunk elements, a workgroup of kScanBlock threads per chunk, no workgroup
+// waiting for another.  Launch 1: every chunk's sum (chunk_sum).  Launch 2: thread t of chunk c owns the chunk's elements
+// kScanPer t .. kScanPer t + kScanPer - 1 and learns what lies before them (chunk_offset).  T is int32_t or int64_t.
+#pragma once
+#include "common.hpp"
+
+namespace pcreg {
+namespace {
+
+constexpr int kScanBlock = 256;
+constexpr int kScanChunk = 2048;                     // elements per workgroup
+constexpr int kScanPer = kScanChunk / kScanBlock;    // consecutive elements per thread of launch 2
+
+// csum[this chunk] = the sum of the workgroup's v (each thread's sum over its elements, in any assignment)
+template <typename T>
+__device__ __forceinline__ void chunk_sum(T v, T* __restrict__ csum) {
+    __shared__ T s[kScanBlock / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) csum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+
+// the sum of everything before this thread's elements: the chunks before this one, plus `mine` of the threads before this one
+template <typename T>
+__device__ __forceinline__ T chunk_offset(const T* __restrict__ csum, T mine) {
+    __shared__ T s[kScanBlock / 64], s_thr[kScanBlock];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    T before = 0;
+    for (int c = tid; c < (int)blockIdx.x; c += kScanBlock) before += csum[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    if (lane == 0) s[wave] = before;
+    s_thr[tid] = mine;
+    __syncthreads();
+    const T run = s[0] + s[1] + s[2] + s[3];
+    // inclusive scan of the 256 thread sums (Hillis-Steele in LDS)
+    for (int o = 1; o < kScanBlock; o <<= 1) {
+        const T add = tid >= o ? s_thr[tid - o] : 0;
+        __syncthreads();
+        s_thr[tid] += add;
+        __syncthreads();
+    }
+    return run + (s_thr[tid] - mine);
+}
+
+}  // namespace
+}  // namespace pcreg

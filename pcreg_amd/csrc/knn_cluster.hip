@@ -10,29 +10,23 @@
 //                               two ORIGINAL rows in a lock-free union-find: the larger root is hooked under the smaller by a
 //                               compare-and-swap, find jumps pointers on its way.  No workgroup waits for another
 //   C3  cluster_flatten_kernel  parent[i] = root of i (its cluster's smallest row); the roots per chunk of 2048 rows
-//   C4  cluster_number_kernel   every chunk adds the chunks before it and scans its own root flags: the cluster number of every
-//                               root, first[], n_clusters
+//   C4  cluster_number_kernel   the chunk scan's second launch (chunk_scan.hpp): the cluster number of every root, first[],
+//                               n_clusters
 //   C5  cluster_label_kernel    label[i] = number[parent[i]]; sizes[] by integer atomicAdd, one per (wave, cluster)
 #include "common.hpp"
 #include "knn_fast_common.hpp"
+#include "knn_walk.hpp"
+#include "chunk_scan.hpp"
 #include <cmath>
 
 namespace pcreg {
 
 namespace {
 
-constexpr int kCLanes = 4;                           // lanes per row of tile a
-constexpr int kCRowsPerWg = kBlock / kCLanes;        // 64 rows per workgroup
-constexpr int kCWgPerTile = kT16 / kCRowsPerWg;      // 8 workgroups per tile a
-constexpr int kCChunk = 2048;                        // rows per workgroup of the numbering scan (256 threads x 8)
-static_assert(kT16 % kBlock == 0 && kT16 % (4 * kCLanes) == 0, "tile staging and the unrolled walk");
+constexpr int kCWgPerTile = kT16 / kWalkQPerWg;      // 8 workgroups per tile a, 64 of its rows each (the walk's queries)
 
 #define PCREG_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-__device__ __forceinline__ float cluster_d2(float qx, float qy, float qz, float mx, float my, float mz) {
-    const float dx = qx - mx, dy = qy - my, dz = qz - mz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
 }
@@ -83,17 +77,15 @@ __global__ __launch_bounds__(kBlock) void cluster_init_kernel(int M, int32_t* __
 
 // ---- C2. the walk -----------------------------------------------------------------------------------------------------
 // Workgroup (tile a, part p) owns sorted rows a * 512 + p * 64 + (tid >> 2); lane sub = tid & 3 of a row scores rows sub,
-// sub + 4, .. of every visited tile b >= a from LDS (x, y, z, original row).  Pair (a, b) is skipped iff G2 > 1e-30 &&
-// G2 (1 - 32u) > r2, G2 the squared gap between the two tile boxes, formed in double: every row pair of a skipped tile pair has
-// a computed d > r2 (DESIGN 4.1 with D = r2 and B = tile a's box).  Tile t + 1 is loaded into registers while tile t is scored.
+// sub + 4, .. of every visited tile b >= a from LDS (x, y, z, original row).  Pair (a, b) is skipped by DESIGN 4.1's rule with
+// D = r2 and B = tile a's box: every row pair of a skipped tile pair has a computed d > r2.  The walk itself is knn_walk.hpp's.
 // A non-finite row is staged as NaN and its own lanes admit nothing, so it stays a set of its own whatever r2.
 __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
                                                               const float* __restrict__ tbox, int n_tiles, int cull, int skip_same, float r2,
                                                               int32_t* parent, unsigned long long* __restrict__ stats,
                                                               unsigned long long* __restrict__ cstats) {
-    __shared__ float4 tile[kT16];
-    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ WalkLds lds;
+    const int tid = threadIdx.x;
     const int ta = blockIdx.x / kCWgPerTile, part = blockIdx.x % kCWgPerTile;
     if (blockIdx.x == 0 && tid == 0) {
         if (stats) {
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __res
 #pragma unroll
     for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
     // this thread's row
-    const int sub = tid & (kCLanes - 1), rl = part * kCRowsPerWg + tid / kCLanes;      // the row's place inside tile a
+    const int rl = part * kWalkQPerWg + tid / kWalkLanes;         // the row's place inside tile a
     const int srow = ta * kT16 + rl;
     const bool in_model = srow < M;
     const int sr = in_model ? srow : 0;
@@ -116,81 +108,38 @@ __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __res
     const float rr = live ? r2 : -1.0f;                           // (a dead lane admits nothing: d is never negative)
     int my_root = row_i;                                          // the last root this lane saw for its row
     unsigned long long n_hit = 0;
-    const float qnan = __int_as_float(0x7FC00000);                // padding and non-finite rows: d = NaN never passes d <= r2
-    // rounds of kBlock candidate tiles from ta on: each thread tests one, the visited ones are listed in LDS in ascending order
-    for (int c0 = ta; c0 < n_tiles; c0 += kBlock) {
-        __syncthreads();                                          // the previous round's list consumed
-        {
-            const int ct = c0 + tid;
-            bool visit = ct < n_tiles;
-            if (visit && cull != 0 && r2 < INFINITY) {
-                // gaps in double from the float boxes, a relative margin of 32u, no bound below 1e-30
-                const float* bx = tbox + (size_t)ct * 6;
-                double g2 = 0.0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double gap = fmax(0.0, fmax((double)bx[c] - (double)abox[3 + c], (double)abox[c] - (double)bx[3 + c]));
-                    g2 += gap * gap;
-                }
-                const double u = 5.9604644775390625e-08;
-                if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)r2) visit = false;
+    int above = -1;                                               // on the diagonal only the rows behind this one
+    walk_tiles(
+        lds, ta, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
+        [&](int ct) {
+            return !(cull != 0 && r2 < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), r2));
+        },
+        [&](int r) {                                              // a non-finite row is staged as no row at all
+            if (r < M) {
+                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
+                if (finite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
             }
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-            if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
-            __syncthreads();
-            int base = 0;
+            return walk_no_row();
+        },
+        [&](int ct) { above = ct == ta ? rl : -1; },
+        [&](int r, const float4 (&p)[4], float (&d)[4]) {
+            const float qnan = __int_as_float(0x7FC00000);
 #pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) base += w < wave ? s_wcnt[w] : 0;
-            if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
-        }
-        __syncthreads();
-        const int ntile = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        if (stats && part == 0 && tid == 0 && ntile > 0) atomicAdd(&stats[1], (unsigned long long)ntile);
-        constexpr int kRowsPerThread = kT16 / kBlock;
-        float4 pre[kRowsPerThread];
-        auto fetch = [&](int t) {
-            const int r0 = s_list[t] * kT16;
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) {
-                const int r = r0 + u * kBlock + tid;
-                pre[u] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
-                if (r < M) {
-                    const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                    if (finite3(x, y, z)) pre[u] = make_float4(x, y, z, __int_as_float(perm[r]));
-                }
-            }
-        };
-        if (ntile > 0) fetch(0);
-        for (int t = 0; t < ntile; ++t) {
-            __syncthreads();                                      // the previous tile's readers are done
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) tile[u * kBlock + tid] = pre[u];
-            const int above = s_list[t] == ta ? rl : -1;          // on the diagonal only the rows behind this one
-            __syncthreads();
-            if (t + 1 < ntile) fetch(t + 1);
-            for (int r = sub; r < kT16; r += 4 * kCLanes) {
-                float4 p[4]; float d[4];
+            for (int u = 0; u < 4; ++u) d[u] = r + u * kWalkLanes > above ? d[u] : qnan;
+            if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    p[u] = tile[r + u * kCLanes];
-                    d[u] = cluster_d2(qx, qy, qz, p[u].x, p[u].y, p[u].z);
-                    d[u] = r + u * kCLanes > above ? d[u] : qnan;
-                }
-                if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (d[u] <= rr) {
-                            const int row_j = __float_as_int(p[u].w);
-                            ++n_hit;
-                            // one load: a row that already points at this lane's root is in its set (sets only merge)
-                            if (skip_same && uf_load(parent, row_j) == my_root) continue;
-                            my_root = uf_unite(parent, my_root, row_j, cstats);
-                        }
+                    if (d[u] <= rr) {
+                        const int row_j = __float_as_int(p[u].w);
+                        ++n_hit;
+                        // one load: a row that already points at this lane's root is in its set (sets only merge)
+                        if (skip_same && uf_load(parent, row_j) == my_root) continue;
+                        my_root = uf_unite(parent, my_root, row_j, cstats);
                     }
                 }
             }
-        }
-    }
+        },
+        [] {});
     if (cstats && n_hit) atomicAdd(&cstats[1], n_hit);
 }
 
@@ -198,10 +147,9 @@ __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __res
 // (the walk is a finished launch: its parent[] is visible.  A thread's store only replaces an ancestor of i by the root, so
 // the threads that pass through i in the same launch still reach the same root.)
 __global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t* parent, int32_t* __restrict__ csum) {
-    __shared__ int s[kBlock / 64];
-    const int base = blockIdx.x * kCChunk;
-    int v = 0;
-    for (int k = threadIdx.x; k < kCChunk; k += kBlock) {
+    const int base = blockIdx.x * kScanChunk;
+    int32_t v = 0;
+    for (int k = threadIdx.x; k < kScanChunk; k += kBlock) {
         const int i = base + k;
         if (i < M) {
             int r = uf_load(parent, i);
@@ -210,44 +158,22 @@ __global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t*
             v += r == i ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) csum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    chunk_sum(v, csum);
 }
 
 // ---- C4. number the roots in row order --------------------------------------------------------------------------------
-// chunk c: the sum of the chunks before it, then thread t scans the root flags of its 8 consecutive rows behind the threads
-// before it; num[i] (roots only) = the roots before row i; the last chunk writes n_clusters
+// the two-launch chunk scan (chunk_scan.hpp) over the rows' "is a root": num[i] (roots only) = the roots before row i; the last
+// chunk writes n_clusters
 __global__ __launch_bounds__(kBlock) void cluster_number_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ csum,
                                                                 int32_t* __restrict__ num, int32_t* __restrict__ first,
                                                                 int32_t* __restrict__ n_clusters) {
-    __shared__ int s[kBlock / 64], s_thr[kBlock];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int before = 0;
-    for (int c = tid; c < (int)blockIdx.x; c += kBlock) before += csum[c];
+    const int i0 = blockIdx.x * kScanChunk + threadIdx.x * kScanPer;
+    int32_t f[kScanPer], mine = 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
-    if (lane == 0) s[wave] = before;
-    constexpr int kPer = kCChunk / kBlock;
-    const int i0 = blockIdx.x * kCChunk + tid * kPer;
-    int f[kPer], mine = 0;
+    for (int u = 0; u < kScanPer; ++u) { f[u] = i0 + u < M && parent[i0 + u] == i0 + u ? 1 : 0; mine += f[u]; }
+    int32_t run = chunk_offset(csum, mine);
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) { f[u] = i0 + u < M && parent[i0 + u] == i0 + u ? 1 : 0; mine += f[u]; }
-    s_thr[tid] = mine;
-    __syncthreads();
-    int run = s[0] + s[1] + s[2] + s[3];
-    // exclusive scan of the 256 thread sums (Hillis-Steele in LDS)
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const int add = tid >= o ? s_thr[tid - o] : 0;
-        __syncthreads();
-        s_thr[tid] += add;
-        __syncthreads();
-    }
-    run += s_thr[tid] - mine;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
+    for (int u = 0; u < kScanPer; ++u) {
         if (f[u]) { num[i0 + u] = run; if (first) first[run] = i0 + u; }
         run += f[u];
         if (i0 + u == M - 1) *n_clusters = run;
@@ -284,7 +210,7 @@ ClusterWs cluster_ws_layout(int M, void* base, size_t* bytes) {
     WsWalk w(base);
     s.parent = w.take<int32_t>(mm);
     s.num = w.take<int32_t>(mm);
-    s.csum = w.take<int32_t>((mm + kCChunk - 1) / kCChunk);
+    s.csum = w.take<int32_t>((mm + kScanChunk - 1) / kScanChunk);
     *bytes = w.bytes();
     return s;
 }
@@ -307,7 +233,7 @@ int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* 
         PCREG_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), st));
         return PCREG_OK;
     }
-    const int n_tiles = (M + kT16 - 1) / kT16, chunks = (M + kCChunk - 1) / kCChunk, blocks = (M + kBlock - 1) / kBlock;
+    const int n_tiles = (M + kT16 - 1) / kT16, chunks = (M + kScanChunk - 1) / kScanChunk, blocks = (M + kBlock - 1) / kBlock;
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile pair, same bits
     const int skip_same = debug_flag(kDbgClusterNoSkip) ? 0 : 1; // "cluster_noskip": unite on every hit, same bits
     hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks), dim3(kBlock), 0, st, M, s.parent, first, sizes);

@@ -438,8 +438,7 @@ __device__ __forceinline__ void expand_entry(int j, float qx, float qy, float qz
 #pragma unroll
         for (int k = 0; k < kRowBatch; ++k) {              // ascending rr, (distance, original row) order: as the one-row loop ranked
             const int rr = h + k;
-            const float dx = qx - x[k], dy = qy - y[k], dz = qz - z[k];
-            const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const float d = point_d2(qx, qy, qz, x[k], y[k], z[k]);
             const bool in2 = j + 8 * (rr >> 2) + (rr & 3) < M && lex_lt_f(d, oj[k], d2, i2), in1 = in2 && lex_lt_f(d, oj[k], d1, i1);
             d2 = in1 ? d1 : (in2 ? d : d2); i2 = in1 ? i1 : (in2 ? oj[k] : i2);          // (selects: straight-line code)
             d1 = in1 ? d : d1; i1 = in1 ? oj[k] : i1;
@@ -636,14 +635,7 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
                         for (int k = 0; k < kTailBoxes; ++k) {
                             const int ct = b0 + k * kBlock;
                             const float lo[3] = {bx[k][0].x, bx[k][0].y, bx[k][1].x}, hi[3] = {bx[k][1].y, bx[k][2].x, bx[k][2].y};
-                            double g2 = 0.0;
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) {
-                                const double gap = fmax(0.0, fmax((double)lo[c] - qd[c], qd[c] - (double)hi[c]));
-                                g2 += gap * gap;
-                            }
-                            const double u = 5.9604644775390625e-08;
-                            if (ct < c1 && !(g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D)) s_list[atomicAdd(&s_nlist, 1)] = ct;
+                            if (ct < c1 && !cull_skips(cull_gap2(lo, hi, qd, qd), D)) s_list[atomicAdd(&s_nlist, 1)] = ct;
                         }
                     }
                 }
@@ -664,8 +656,7 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
                     float d[kTailSegs]; bool any = false;
 #pragma unroll
                     for (int k = 0; k < kTailSegs; ++k) {
-                        const float dx = qx - x[k], dy = qy - y[k], dz = qz - z[k];
-                        d[k] = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                        d[k] = point_d2(qx, qy, qz, x[k], y[k], z[k]);
                         any = any || (j[k] < M && d[k] <= d2 && d[k] < INFINITY);
                     }
                     if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
@@ -735,10 +726,7 @@ __global__ __launch_bounds__(kBlock) void knn_tail_kernel(
                 for (int r = 0; r < 4; ++r) {
                     float d[4];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float dx = qx[r] - mp[u].x, dy = qy[r] - mp[u].y, dz = qz[r] - mp[u].z;
-                        d[u] = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                    }
+                    for (int u = 0; u < 4; ++u) d[u] = point_d2(qx[r], qy[r], qz[r], mp[u].x, mp[u].y, mp[u].z);
                     const float mn = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
                     if (mn < best[r].d2) {
                         const int j0 = t0 + jb;

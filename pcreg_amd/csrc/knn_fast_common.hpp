@@ -1,6 +1,7 @@
 // pcreg_amd/csrc/knn_fast_common.hpp -- device helpers shared by knn_fast.hip, knn_mfma16.hip and knn_points.hip
 #pragma once
 #include "common.hpp"
+#include "cull_rule.hpp"
 #include <cmath>
 
 namespace pcreg {
@@ -21,6 +22,14 @@ constexpr int kMTile = 1024;                 // model points per LDS tile (16 Ki
 #define PCREG_KT16 512
 #endif
 constexpr int kT16 = PCREG_KT16;              // model points per f16 tile: [2 k-halves][512 points][8 f16] = 16 KiB (768 / 1024 measured in round 3: docs/NOTES_r01_r03.md 4.1)
+
+// The point search's distance, its one definition: d = fmaf(dz,dz, fmaf(dy,dy, dx*dx)), dx = q - m in fp32 -- the bits the oracle
+// produces.  Sign-symmetric (q - m and m - q differ in sign alone, and only squares are used): the query grid's back-check
+// passes its pair in either order.
+__device__ __forceinline__ float point_d2(float qx, float qy, float qz, float mx, float my, float mz) {
+    const float dx = qx - mx, dy = qy - my, dz = qz - mz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
 
 // What a PREPARED MODEL carries besides its f16 tiles (model-only quantities: one model, many query sets --
 // completeExperimentFast.m:131-149): the centre of the model's bounding box, the power-of-two scale that brings its
@@ -88,10 +97,6 @@ static inline size_t ug_cells_cap(int Q) { size_t c = 2 * (size_t)(Q > 0 ? Q : 1
 __device__ __forceinline__ int ug_cell1(float x, float x0, float inv_c, int n) {
     const int c = (int)floorf((x - x0) * inv_c);                     // monotone in x: the range test relies on it
     return min(max(c, 0), n - 1);
-}
-__device__ __forceinline__ float ug_d2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;           // the search's exact formula (sign-symmetric)
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
 }
 // about two cells per query over the occupied extent; flat or degenerate axes get one layer
 __device__ __forceinline__ void ug_make_prep(const float lo[3], const float hi[3], int Q, int cells_cap, UgPrep* prep) {

@@ -17,6 +17,7 @@
 // The merge of per-shard lists (pcreg_dev_merge_topk_f32) is knn_k_merge_kernel<KB>.
 #include "common.hpp"
 #include "knn_fast_common.hpp"
+#include "knn_walk.hpp"
 #include <cmath>
 
 namespace pcreg {
@@ -24,18 +25,9 @@ namespace pcreg {
 namespace {
 
 constexpr int kKnnMaxK = PCREG_KNN_MAX_K;
-constexpr int kKQBlock = 512;                        // query slots per culling block (the top-2 search's unit)
-constexpr int kKLanes = 4;                           // lanes per query
-constexpr int kKQPerWg = kBlock / kKLanes;           // 64 queries per workgroup
-constexpr int kKWgPerBlock = kKQBlock / kKQPerWg;    // 8 workgroups per block
 constexpr int kKSeedWin = 64;                        // sorted rows the seed bound looks at (one per lane of a wave)
 static_assert(kKnnMaxK <= kKSeedWin, "the seed window holds at least k rows");
-static_assert(kT16 % kBlock == 0 && kT16 % (4 * kKLanes) == 0, "tile staging and the unrolled walk");
 
-__device__ __forceinline__ float knn_k_d2(float qx, float qy, float qz, float mx, float my, float mz) {
-    const float dx = qx - mx, dy = qy - my, dz = qz - mz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
 __device__ __forceinline__ bool knn_k_lt(float da, int ia, float db, int ib) {     // (distance, row); -1 (empty) sorts last
     return da < db || (da == db && (unsigned)ia < (unsigned)ib);
 }
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void knn_k_seed_kernel(const float* __restr
     const int r = w0 + lane;
     float d = INFINITY;
     if (r < M) {
-        d = knn_k_d2(qx, qy, qz, ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M]);
+        d = point_d2(qx, qy, qz, ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M]);
         if (!(d == d)) d = INFINITY;
     }
 #pragma unroll
@@ -124,58 +116,27 @@ __global__ __launch_bounds__(kBlock) void knn_k_seed_kernel(const float* __restr
 // sub + 4, .. of every visited tile from LDS (x, y, z, original row) and keeps the KB best (distance, row) pairs it saw.  A
 // row enters a list only when d <= thr, thr = min(dk_k, the k-th entry of any of the query's four lists), each of which bounds
 // the true k-th distance from above; a row farther than that is neither among the k nearest nor tied with the k-th.
-// Tiles are skipped by DESIGN 4.1's rule with D = max dk_k over the block's queries (any +inf turns it off); tile t + 1 is
-// loaded into registers while tile t is scored.
+// Tiles are skipped by DESIGN 4.1's rule with D = max dk_k over the block's queries (any +inf turns it off).  The walk itself
+// is knn_walk.hpp's.
 template <int KB>
 __global__ __launch_bounds__(kBlock) void knn_k_kernel(const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
                                                        const float* __restrict__ dk, const float* __restrict__ ms,
                                                        const int32_t* __restrict__ perm, int M, const float* __restrict__ tbox, int n_tiles,
                                                        int cull, int k, int idx_base, int32_t* __restrict__ idx, float* __restrict__ dist,
                                                        unsigned long long* __restrict__ stats) {
-    __shared__ float4 tile[kT16];
+    __shared__ WalkLds lds;
     __shared__ float s_red[kBlock / 64][7];
     __shared__ float s_box[7];
-    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qb = blockIdx.x / kKWgPerBlock, part = blockIdx.x % kKWgPerBlock;
-    // the block's box and largest dk_k over ALL its queries (every workgroup of the block forms the same values)
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, D = 0.0f;
-    for (int r = tid; r < kKQBlock; r += kBlock) {
-        const int slot = qb * kKQBlock + r;
-        if (slot < Q) {
-            const int qi = qperm[slot];
-            const float p[3] = {q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq]};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], p[c]); hi[c] = fmaxf(hi[c], p[c]); }
-            const float e = dk[qi];
-            D = e < INFINITY ? fmaxf(D, e) : INFINITY;            // +inf (or NaN): no bound, culling off for the block
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], o)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], o)); }
-        D = fmaxf(D, __shfl_xor(D, o));
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_red[wave][c] = lo[c]; s_red[wave][3 + c] = hi[c]; }
-        s_red[wave][6] = D;
-    }
-    __syncthreads();
-    if (tid < 7) {
-        float v = s_red[0][tid];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) v = tid < 3 ? fminf(v, s_red[w][tid]) : fmaxf(v, s_red[w][tid]);
-        s_box[tid] = v;
-    }
+    const int tid = threadIdx.x;
+    const int qb = blockIdx.x / kWalkWgPerBlock, part = blockIdx.x % kWalkWgPerBlock;
+    walk_block_box<7>(s_red, s_box, q, Q, ldq, qperm, dk, qb);    // the block's box and largest dk_k
     if (stats && blockIdx.x == 0 && tid == 0) {
         atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)((Q + kKQBlock - 1) / kKQBlock) * (unsigned long long)n_tiles);
+        atomicAdd(&stats[2], (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
     }
     // this thread's query
-    const int sub = tid & (kKLanes - 1);
-    const int slot = qb * kKQBlock + part * kKQPerWg + (tid / kKLanes);
+    const int sub = tid & (kWalkLanes - 1);
+    const int slot = qb * kWalkQBlock + part * kWalkQPerWg + (tid / kWalkLanes);
     const bool live = slot < Q;
     const int qi = live ? qperm[slot] : 0;
     const float qx = q[qi], qy = q[qi + (size_t)ldq], qz = q[qi + 2 * (size_t)ldq];
@@ -184,73 +145,29 @@ __global__ __launch_bounds__(kBlock) void knn_k_kernel(const float* __restrict__
     float ld[KB]; int li[KB];
 #pragma unroll
     for (int s = 0; s < KB; ++s) { ld[s] = INFINITY; li[s] = -1; }
-    const float qnan = __int_as_float(0x7FC00000);                // padding rows: d = NaN never passes d <= thr
-    // rounds of kBlock candidate tiles: each thread tests one, the visited ones are listed in LDS in ascending order
-    for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {
-        __syncthreads();                                          // s_box written / the previous round's list consumed
-        {
-            const int ct = c0 + tid;
-            bool visit = ct < n_tiles;
+    walk_tiles(
+        lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
+        [&](int ct) {
             const float Db = s_box[6];
-            if (visit && cull != 0 && Db < INFINITY) {
-                // gaps in double from the float boxes, a relative margin of 32u, no bound below 1e-30
-                const float* bx = tbox + (size_t)ct * 6;
-                double g2 = 0.0;
+            return !(cull != 0 && Db < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, s_box, s_box + 3), Db));
+        },
+        [&](int r) { return walk_row(ms, perm, M, r); },
+        [](int) {},
+        [&](int, const float4 (&p)[4], float (&d)[4]) {
+            if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= thr) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
-                    g2 += gap * gap;
-                }
-                const double u = 5.9604644775390625e-08;
-                if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)Db) visit = false;
-            }
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-            if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
-            __syncthreads();
-            int base = 0;
-#pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) base += w < wave ? s_wcnt[w] : 0;
-            if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
-        }
-        __syncthreads();
-        const int ntile = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        if (stats && part == 0 && tid == 0 && ntile > 0) atomicAdd(&stats[1], (unsigned long long)ntile);
-        constexpr int kRowsPerThread = kT16 / kBlock;
-        float4 pre[kRowsPerThread];
-        auto fetch = [&](int t) {
-            const int r0 = s_list[t] * kT16;
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) {
-                const int r = r0 + u * kBlock + tid;
-                if (r < M) pre[u] = make_float4(ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M], __int_as_float(perm[r]));
-                else pre[u] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
-            }
-        };
-        if (ntile > 0) fetch(0);
-        for (int t = 0; t < ntile; ++t) {
-            __syncthreads();                                      // the previous tile's readers are done
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) tile[u * kBlock + tid] = pre[u];
-            __syncthreads();
-            if (t + 1 < ntile) fetch(t + 1);
-            for (int r = sub; r < kT16; r += 4 * kKLanes) {
-                float4 p[4]; float d[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { p[u] = tile[r + u * kKLanes]; d[u] = knn_k_d2(qx, qy, qz, p[u].x, p[u].y, p[u].z); }
-                if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= thr) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (d[u] <= thr) {
-                            klist_insert<KB>(ld, li, d[u], __float_as_int(p[u].w));
-                            thr = fminf(thr, klist_kth<KB>(ld, k));
-                        }
+                for (int u = 0; u < 4; ++u) {
+                    if (d[u] <= thr) {
+                        klist_insert<KB>(ld, li, d[u], __float_as_int(p[u].w));
+                        thr = fminf(thr, klist_kth<KB>(ld, k));
                     }
                 }
             }
+        },
+        [&] {
             thr = fminf(thr, __shfl_xor(thr, 1));                 // the query's four lanes share the tightest bound
             thr = fminf(thr, __shfl_xor(thr, 2));
-        }
-    }
+        });
     klist_merge_xor<KB>(ld, li, 1);
     klist_merge_xor<KB>(ld, li, 2);
     if (live && sub == 0) {
@@ -339,7 +256,7 @@ int launch_model_knn(const ModelView& v, const float* q, int Q, int ldq, int k, 
     const int n_tiles = (v.M + kT16 - 1) / kT16;
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     unsigned long long* stats = knn_stats_dev();                  // "knn_stats": searches, visited, nominal (no tail here)
-    const dim3 grid((unsigned)(((Q + kKQBlock - 1) / kKQBlock) * kKWgPerBlock));
+    const dim3 grid((unsigned)(((Q + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock));
 #define PCREG_KNN_K_LAUNCH(KB_)                                                                                             \
     hipLaunchKernelGGL(knn_k_kernel<KB_>, grid, dim3(kBlock), 0, st, q, Q, ldq, (const int32_t*)s.qperm, (const float*)s.dk, \
                        (const float*)v.ms, (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, k, (int)idx_base,  \

@@ -213,19 +213,11 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
     const int t0 = min(tid * per, n_tiles), t1 = min(t0 + per, n_tiles);
     const bool test = cull != 0 && bdk_b < INFINITY;
     // skip only when a rigorous lower bound of the fp32 fmaf-chain distance from any point of the block's box to any
-    // point of the tile's box exceeds the block's largest seed distance: gaps in double, a relative margin of 32u, and no
-    // bound at all below 1e-30 (subnormal squares)
+    // point of the tile's box exceeds the block's largest seed distance: the rule of cull_rule.hpp
     auto skipped_by = [](const float2 a, const float2 b, const float2 c,        // the box: lo = (a.x, a.y, b.x), hi = (b.y, c.x, c.y)
                          const double (&qlo)[3], const double (&qhi)[3], const float D) {
         const float lo[3] = {a.x, a.y, b.x}, hi[3] = {b.y, c.x, c.y};
-        double g2 = 0.0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const double gap = fmax(0.0, fmax((double)lo[d] - qhi[d], qlo[d] - (double)hi[d]));
-            g2 += gap * gap;
-        }
-        const double u = 5.9604644775390625e-08;
-        return g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)D;
+        return cull_skips(cull_gap2(lo, hi, qlo, qhi), D);
     };
     auto skipped = [&](const float2 a, const float2 b, const float2 c) { return skipped_by(a, b, c, blo_d, bhi_d, bdk_b); };
     constexpr int kPlanBatch = 8;

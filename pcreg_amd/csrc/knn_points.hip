@@ -37,10 +37,6 @@ __device__ __forceinline__ void top2_insert(Top2& t, float d, int j) {
         else { t.d2 = d; t.i2 = j; }
     }
 }
-__device__ __forceinline__ float sqd(float qx, float qy, float qz, const float4& m) {
-    float dx = qx - m.x, dy = qy - m.y, dz = qz - m.z;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
 
 // grid = (query tiles, S model chunks).  part_* layout [S][Q][2].
 template <int QPT_, int UB_>
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void knn2_points_kernel(
             for (int r = 0; r < QPT_; ++r) {
                 float d[UB_];
 #pragma unroll
-                for (int u = 0; u < UB_; ++u) d[u] = sqd(qx[r], qy[r], qz[r], mp[u]);
+                for (int u = 0; u < UB_; ++u) d[u] = point_d2(qx[r], qy[r], qz[r], mp[u].x, mp[u].y, mp[u].z);
                 float mn = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
                 if (UB_ == 8) mn = fminf(mn, fminf(fminf(d[4 % UB_], d[5 % UB_]), fminf(d[6 % UB_], d[7 % UB_])));
                 if (mn < best[r].d2) {
@@ -203,7 +199,7 @@ __global__ __launch_bounds__(kMB) void match_finish_kernel(
                 bool beaten = false, unsure = false;
                 if (mine) {
                     const UgPrep P = *ug_prep;
-                    di = ug_d2(q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq], px, py, pz);
+                    di = point_d2(q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq], px, py, pz);
                     const float r = sqrtf(di) * 1.0001f + 1e-30f;                // covers every point whose rounded distance is <= di
                     const int x0 = ug_cell1(px - r, P.x0, P.inv_c, P.nx), x1 = ug_cell1(px + r, P.x0, P.inv_c, P.nx);
                     const int y0 = ug_cell1(py - r, P.y0, P.inv_c, P.ny), y1 = ug_cell1(py + r, P.y0, P.inv_c, P.ny);
@@ -220,7 +216,7 @@ __global__ __launch_bounds__(kMB) void match_finish_kernel(
                         for (int sl = 0; sl < cn; ++sl) {
                             const float4 t = ug_slots[(size_t)cell * kUgSlots + sl];
                             const int it = __float_as_int(t.w);
-                            const float d = ug_d2(t.x, t.y, t.z, px, py, pz);
+                            const float d = point_d2(t.x, t.y, t.z, px, py, pz);
                             if (d < di || (d == di && it < qi)) { beaten = true; break; }
                         }
                     }
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(kMB) void match_finish_kernel(
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int t = t0 + u * 64 + lane;
-                        const float d = ug_d2(x[u], y[u], z[u], bx, by, bz);
+                        const float d = point_d2(x[u], y[u], z[u], bx, by, bz);
                         bb = bb || (t < Q && (d < bd || (d == bd && t < bi)));
                     }
                     beaten = __any(bb);

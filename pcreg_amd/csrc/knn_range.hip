@@ -13,35 +13,26 @@
 //                                     tiles DESIGN 4.1's rule rules out with D = r2, and walks the others for its 64 queries: four
 //                                     lanes per query.  Count: hits summed over the four lanes.  Fill: a hit takes the next
 //                                     place of the query's segment (an LDS cursor), clamped into the segment and the capacity
-//   R4  count: range_scan_kernel      counts -> seg_off in int64: sums of chunks of 2048, then every chunk adds the chunks
-//                                     before it and scans itself
+//   R4  count: range_scan_kernel      counts -> seg_off in int64: the two-launch chunk scan (chunk_scan.hpp)
 //       fill:  range_sort_wave_kernel one wave per query: segments of up to 64 rows sorted in registers, longer ones listed
 //              range_sort_wg_kernel   one workgroup per listed segment: up to kRangeLdsCap rows in LDS, above that in place in
 //                                     global memory (no memory proportional to the result)
 #include "common.hpp"
 #include "knn_fast_common.hpp"
+#include "knn_walk.hpp"
+#include "chunk_scan.hpp"
 #include <cmath>
 
 namespace pcreg {
 
 namespace {
 
-constexpr int kRQBlock = 512;                        // query slots per culling block (the other point searches' unit)
-constexpr int kRLanes = 4;                           // lanes per query
-constexpr int kRQPerWg = kBlock / kRLanes;           // 64 queries per workgroup
-constexpr int kRWgPerBlock = kRQBlock / kRQPerWg;    // 8 workgroups per block
 constexpr int kRangeMaxQ = kMaxQTiles * 1024;        // 4 Mi queries per call
-constexpr int kScanChunk = 2048;                     // counts per workgroup of the scan (256 threads x 8)
 constexpr int kScanMaxChunks = kRangeMaxQ / kScanChunk;
 constexpr int kRangeLdsCap = 2048;                   // longest segment sorted in LDS (16 KiB of 64-bit keys)
 constexpr int kSortWgGrid = 2048;                    // workgroups of range_sort_wg_kernel (they loop over the list)
-static_assert(kT16 % kBlock == 0 && kT16 % (4 * kRLanes) == 0, "tile staging and the unrolled walk");
 static_assert(kScanMaxChunks <= kScanChunk, "one workgroup sums every chunk before its own");
 
-__device__ __forceinline__ float range_d2(float qx, float qy, float qz, float mx, float my, float mz) {
-    const float dx = qx - mx, dy = qy - my, dz = qz - mz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
 // the part of [seg_off[qi], seg_off[qi + 1]) inside [0, capacity), whatever seg_off holds: 0 <= b <= e <= capacity
 __device__ __forceinline__ void range_segment(const int64_t* __restrict__ seg_off, int qi, int64_t capacity, int64_t& b, int64_t& e) {
     const int64_t s0 = seg_off[qi], s1 = seg_off[qi + 1];
@@ -59,9 +50,9 @@ __global__ __launch_bounds__(kBlock) void range_qcell_kernel(const float* __rest
 
 // ---- R3. the walk -----------------------------------------------------------------------------------------------------
 // Workgroup (block qb, part p) owns slots qb * 512 + p * 64 + (tid >> 2); lane sub = tid & 3 of a query scores rows sub,
-// sub + 4, .. of every visited tile from LDS (x, y, z, original row).  A tile is skipped iff G2 > 1e-30 && G2 (1 - 32u) > r2,
-// G2 the squared gap between the block's box and the tile's, formed in double: every row of a skipped tile has a computed
-// d > r2 for every query of the block (DESIGN 4.1 with D = r2).  Tile t + 1 is loaded into registers while tile t is scored.
+// sub + 4, .. of every visited tile from LDS (x, y, z, original row).  A tile is skipped by DESIGN 4.1's rule with D = r2 and
+// the block's box: every row of a skipped tile has a computed d > r2 for every query of the block.  The walk itself is
+// knn_walk.hpp's.
 // FILL: found[qi] is the number of rows the query HAS (not the number kept); the rows land at seg begin + 0, 1, .. in the order
 // the lanes arrive, and only inside the clamped segment.
 template <bool FILL>
@@ -72,48 +63,21 @@ __global__ __launch_bounds__(kBlock) void range_walk_kernel(const float* __restr
                                                             int64_t capacity, int idx_base, int32_t* __restrict__ idx,
                                                             float* __restrict__ dist, int32_t* __restrict__ found,
                                                             unsigned long long* __restrict__ stats) {
-    __shared__ float4 tile[kT16];
+    __shared__ WalkLds lds;
     __shared__ float s_red[kBlock / 64][6];
     __shared__ float s_box[6];
-    __shared__ int s_list[kBlock], s_wcnt[kBlock / 64];
-    __shared__ int s_cur[kRQPerWg];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qb = blockIdx.x / kRWgPerBlock, part = blockIdx.x % kRWgPerBlock;
-    // the block's box over ALL its queries (every workgroup of the block forms the same values)
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int r = tid; r < kRQBlock; r += kBlock) {
-        const int slot = qb * kRQBlock + r;
-        if (slot < Q) {
-            const int qi = qperm[slot];
-            const float p[3] = {q[qi], q[qi + (size_t)ldq], q[qi + 2 * (size_t)ldq]};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], p[c]); hi[c] = fmaxf(hi[c], p[c]); }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], o)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], o)); }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_red[wave][c] = lo[c]; s_red[wave][3 + c] = hi[c]; }
-    }
-    if (tid < kRQPerWg) s_cur[tid] = 0;
-    __syncthreads();
-    if (tid < 6) {
-        float v = s_red[0][tid];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) v = tid < 3 ? fminf(v, s_red[w][tid]) : fmaxf(v, s_red[w][tid]);
-        s_box[tid] = v;
-    }
+    __shared__ int s_cur[kWalkQPerWg];
+    const int tid = threadIdx.x;
+    const int qb = blockIdx.x / kWalkWgPerBlock, part = blockIdx.x % kWalkWgPerBlock;
+    if (tid < kWalkQPerWg) s_cur[tid] = 0;
+    walk_block_box<6>(s_red, s_box, q, Q, ldq, qperm, nullptr, qb);
     if (stats && blockIdx.x == 0 && tid == 0) {
         atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)((Q + kRQBlock - 1) / kRQBlock) * (unsigned long long)n_tiles);
+        atomicAdd(&stats[2], (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
     }
     // this thread's query
-    const int sub = tid & (kRLanes - 1), ql = tid / kRLanes;
-    const int slot = qb * kRQBlock + part * kRQPerWg + ql;
+    const int sub = tid & (kWalkLanes - 1), ql = tid / kWalkLanes;
+    const int slot = qb * kWalkQBlock + part * kWalkQPerWg + ql;
     const bool live = slot < Q;
     const int qi = live ? qperm[slot] : 0;
     const float qx = q[qi], qy = q[qi + (size_t)ldq], qz = q[qi + 2 * (size_t)ldq];
@@ -121,73 +85,28 @@ __global__ __launch_bounds__(kBlock) void range_walk_kernel(const float* __restr
     int64_t seg_b = 0, seg_e = 0;
     if (FILL && live) range_segment(seg_off, qi, capacity, seg_b, seg_e);
     int cnt = 0;
-    const float qnan = __int_as_float(0x7FC00000);                // padding rows: d = NaN never passes d <= r2
-    // rounds of kBlock candidate tiles: each thread tests one, the visited ones are listed in LDS in ascending order
-    for (int c0 = 0; c0 < n_tiles; c0 += kBlock) {
-        __syncthreads();                                          // s_box written / the previous round's list consumed
-        {
-            const int ct = c0 + tid;
-            bool visit = ct < n_tiles;
-            if (visit && cull != 0 && r2 < INFINITY) {
-                // gaps in double from the float boxes, a relative margin of 32u, no bound below 1e-30
-                const float* bx = tbox + (size_t)ct * 6;
-                double g2 = 0.0;
+    walk_tiles(
+        lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
+        [&](int ct) {
+            return !(cull != 0 && r2 < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, s_box, s_box + 3), r2));
+        },
+        [&](int r) { return walk_row(ms, perm, M, r); },
+        [](int) {},
+        [&](int, const float4 (&p)[4], float (&d)[4]) {
+            if (!FILL) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double gap = fmax(0.0, fmax((double)bx[c] - (double)s_box[3 + c], (double)s_box[c] - (double)bx[3 + c]));
-                    g2 += gap * gap;
-                }
-                const double u = 5.9604644775390625e-08;
-                if (g2 > 1e-30 && g2 * (1.0 - 32.0 * u) > (double)r2) visit = false;
-            }
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(visit);
-            if (lane == 0) s_wcnt[wave] = (int)__popcll(bal);
-            __syncthreads();
-            int base = 0;
+                for (int u = 0; u < 4; ++u) cnt += d[u] <= rr ? 1 : 0;
+            } else if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
 #pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) base += w < wave ? s_wcnt[w] : 0;
-            if (visit) s_list[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = ct;
-        }
-        __syncthreads();
-        const int ntile = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        if (stats && part == 0 && tid == 0 && ntile > 0) atomicAdd(&stats[1], (unsigned long long)ntile);
-        constexpr int kRowsPerThread = kT16 / kBlock;
-        float4 pre[kRowsPerThread];
-        auto fetch = [&](int t) {
-            const int r0 = s_list[t] * kT16;
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) {
-                const int r = r0 + u * kBlock + tid;
-                if (r < M) pre[u] = make_float4(ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M], __int_as_float(perm[r]));
-                else pre[u] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
-            }
-        };
-        if (ntile > 0) fetch(0);
-        for (int t = 0; t < ntile; ++t) {
-            __syncthreads();                                      // the previous tile's readers are done
-#pragma unroll
-            for (int u = 0; u < kRowsPerThread; ++u) tile[u * kBlock + tid] = pre[u];
-            __syncthreads();
-            if (t + 1 < ntile) fetch(t + 1);
-            for (int r = sub; r < kT16; r += 4 * kRLanes) {
-                float4 p[4]; float d[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { p[u] = tile[r + u * kRLanes]; d[u] = range_d2(qx, qy, qz, p[u].x, p[u].y, p[u].z); }
-                if (!FILL) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) cnt += d[u] <= rr ? 1 : 0;
-                } else if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (d[u] <= rr) {
-                            const int64_t at = seg_b + (int64_t)atomicAdd(&s_cur[ql], 1);
-                            if (at < seg_e) { idx[at] = __float_as_int(p[u].w) + idx_base; dist[at] = d[u]; }
-                        }
+                for (int u = 0; u < 4; ++u) {
+                    if (d[u] <= rr) {
+                        const int64_t at = seg_b + (int64_t)atomicAdd(&s_cur[ql], 1);
+                        if (at < seg_e) { idx[at] = __float_as_int(p[u].w) + idx_base; dist[at] = d[u]; }
                     }
                 }
             }
-        }
-    }
+        },
+        [] {});
     if (!FILL) {
         cnt += __shfl_xor(cnt, 1);
         cnt += __shfl_xor(cnt, 2);
@@ -200,45 +119,21 @@ __global__ __launch_bounds__(kBlock) void range_walk_kernel(const float* __restr
 
 // ---- R4 (count). counts -> seg_off, int64 ----------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void range_chunk_sum_kernel(const int32_t* __restrict__ counts, int Q, int64_t* __restrict__ csum) {
-    __shared__ long long s[kBlock / 64];
     const int base = blockIdx.x * kScanChunk;
-    long long v = 0;
-    for (int i = threadIdx.x; i < kScanChunk; i += kBlock) v += base + i < Q ? (long long)counts[base + i] : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) csum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    int64_t v = 0;
+    for (int i = threadIdx.x; i < kScanChunk; i += kBlock) v += base + i < Q ? (int64_t)counts[base + i] : 0;
+    chunk_sum(v, csum);
 }
-// chunk c: the sum of the chunks before it, then thread t scans its 8 consecutive counts behind the threads before it;
-// the last chunk also writes seg_off[Q]
+// thread t of chunk c owns 8 consecutive counts; the last chunk also writes seg_off[Q]
 __global__ __launch_bounds__(kBlock) void range_scan_kernel(const int32_t* __restrict__ counts, int Q, const int64_t* __restrict__ csum,
                                                             int64_t* __restrict__ seg_off) {
-    __shared__ long long s[kBlock / 64], s_thr[kBlock];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long before = 0;
-    for (int c = tid; c < (int)blockIdx.x; c += kBlock) before += csum[c];
+    const int i0 = blockIdx.x * kScanChunk + threadIdx.x * kScanPer;
+    int c[kScanPer]; int64_t mine = 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
-    if (lane == 0) s[wave] = before;
-    constexpr int kPer = kScanChunk / kBlock;
-    const int i0 = blockIdx.x * kScanChunk + tid * kPer;
-    int c[kPer]; long long mine = 0;
+    for (int u = 0; u < kScanPer; ++u) { c[u] = i0 + u < Q ? counts[i0 + u] : 0; mine += c[u]; }
+    int64_t run = chunk_offset(csum, mine);
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) { c[u] = i0 + u < Q ? counts[i0 + u] : 0; mine += c[u]; }
-    s_thr[tid] = mine;
-    __syncthreads();
-    long long run = s[0] + s[1] + s[2] + s[3];
-    // exclusive scan of the 256 thread sums (Hillis-Steele in LDS)
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const long long add = tid >= o ? s_thr[tid - o] : 0;
-        __syncthreads();
-        s_thr[tid] += add;
-        __syncthreads();
-    }
-    run += s_thr[tid] - mine;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
+    for (int u = 0; u < kScanPer; ++u) {
         if (i0 + u < Q) seg_off[i0 + u] = run;
         run += c[u];
         if (i0 + u == Q - 1) seg_off[Q] = run;
@@ -391,7 +286,7 @@ int launch_model_range_count(const ModelView& v, const float* q, int Q, int ldq,
     if (rc) return rc;
     const int n_tiles = (v.M + kT16 - 1) / kT16;
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
-    const dim3 grid((unsigned)(((Q + kRQBlock - 1) / kRQBlock) * kRWgPerBlock));
+    const dim3 grid((unsigned)(((Q + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock));
     hipLaunchKernelGGL(range_walk_kernel<false>, grid, dim3(kBlock), 0, st, q, Q, ldq, (const int32_t*)s.qperm, (const float*)v.ms,
                        (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, r2, counts, (const int64_t*)nullptr, (int64_t)0, 0,
                        (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, knn_stats_dev());
@@ -415,7 +310,7 @@ int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, 
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;
     const int dbg_cap = debug_flag(kDbgRangeSortCap);             // "range_sort_cap": longer segments take the in-place path
     const int cap = dbg_cap > 0 ? std::min(dbg_cap, kRangeLdsCap) : kRangeLdsCap;
-    const dim3 grid((unsigned)(((Q + kRQBlock - 1) / kRQBlock) * kRWgPerBlock));
+    const dim3 grid((unsigned)(((Q + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock));
     hipLaunchKernelGGL(range_walk_kernel<true>, grid, dim3(kBlock), 0, st, q, Q, ldq, (const int32_t*)s.qperm, (const float*)v.ms,
                        (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, r2, (int32_t*)nullptr, seg_off, capacity,
                        (int)idx_base, idx, dist, s.found, knn_stats_dev());

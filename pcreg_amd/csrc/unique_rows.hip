@@ -33,6 +33,7 @@
 // The indexed estimateTransform (pcreg_dev_estimate_transform_indexed) is a kernel of ransac.hip, next to fit_moments / polar_to_T
 // and the wave body of refine_by_distance_kernel it shares: those are file-local device functions.
 #include "common.hpp"
+#include "chunk_scan.hpp"
 
 namespace pcreg {
 
@@ -43,6 +44,7 @@ constexpr int kUT = 2048;                            // records per tile of U1 a
 constexpr int kUBlock = 256;
 constexpr int kUPer = kUT / kUBlock;                 // records per thread
 static_assert((kUT & (kUT - 1)) == 0 && kUT % kUBlock == 0, "the bitonic network and the per-thread runs");
+static_assert(kUT == kScanChunk && kUBlock == kScanBlock, "U3 / U4 are the chunk scan of chunk_scan.hpp");
 
 struct RecBuf { u64* k0; u64* k1; u64* k2; uint32_t* row; };
 
@@ -156,43 +158,23 @@ __device__ __forceinline__ int is_head(const RecBuf& s, int i) {
     return i == 0 || s.k0[i] != s.k0[i - 1] || s.k1[i] != s.k1[i - 1] || s.k2[i] != s.k2[i - 1] ? 1 : 0;
 }
 __global__ __launch_bounds__(kUBlock) void unique_count_kernel(RecBuf s, const int32_t* __restrict__ n_dev, int n_cap, int32_t* __restrict__ csum) {
-    __shared__ int sw[kUBlock / 64];
     const int n = read_n(n_dev, n_cap), base = blockIdx.x * kUT;
     if (base >= n) return;
-    int v = 0;
+    int32_t v = 0;
     for (int e = threadIdx.x; e < kUT; e += kUBlock) v += base + e < n ? is_head(s, base + e) : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) csum[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+    chunk_sum(v, csum);
 }
 // thread t of chunk c owns records c * 2048 + 8 t .. + 7
 __global__ __launch_bounds__(kUBlock) void unique_compact_kernel(RecBuf s, const int32_t* __restrict__ n_dev, int n_cap, const int32_t* __restrict__ csum,
                                                                  int32_t idx_base, int32_t* __restrict__ ia, int32_t* __restrict__ n_unique) {
-    __shared__ int sw[kUBlock / 64], s_thr[kUBlock];
-    const int n = read_n(n_dev, n_cap), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = read_n(n_dev, n_cap), tid = threadIdx.x;
     if (n == 0) { if (blockIdx.x == 0 && tid == 0) *n_unique = 0; return; }
     if (blockIdx.x * kUT >= n) return;
-    int before = 0;
-    for (int c = tid; c < (int)blockIdx.x; c += kUBlock) before += csum[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
-    if (lane == 0) sw[wave] = before;
     const int i0 = blockIdx.x * kUT + tid * kUPer;
-    int f[kUPer], mine = 0;
+    int32_t f[kUPer], mine = 0;
 #pragma unroll
     for (int u = 0; u < kUPer; ++u) { f[u] = i0 + u < n ? is_head(s, i0 + u) : 0; mine += f[u]; }
-    s_thr[tid] = mine;
-    __syncthreads();
-    int run = sw[0] + sw[1] + sw[2] + sw[3];
-    for (int o = 1; o < kUBlock; o <<= 1) {                                        // inclusive scan of the 256 thread sums
-        const int add = tid >= o ? s_thr[tid - o] : 0;
-        __syncthreads();
-        s_thr[tid] += add;
-        __syncthreads();
-    }
-    run += s_thr[tid] - mine;
+    int32_t run = chunk_offset(csum, mine);
 #pragma unroll
     for (int u = 0; u < kUPer; ++u) {
         if (f[u]) ia[run] = (int32_t)s.row[i0 + u] + idx_base;                     // run < the number of heads <= n
