@@ -397,7 +397,7 @@ __device__ bool fit_3pt(const double (&A1)[3][3], const double (&A2)[3][3], doub
     return polar_to_T(H, cd, cm, T);
 }
 
-// Moments of a correspondence set, taken about a fixed origin (o1,o2) so that the
+// Moments of a correspondence set, taken about a fixed origin (o1,o2) inside the data (ransac_origin) so that the
 // centring of estimateTransform.m:55-58 does not cancel digits:
 //   mom[0..2]  = sum(d')      mom[3..5] = sum(m')            (d' = p1-o1, m' = p2-o2)
 //   mom[6..14] = sum(m'_i d'_j), row-major i,j
@@ -513,6 +513,50 @@ struct Pts {
     }
 };
 
+// The ORIGIN of a registration: every RANSAC kernel takes its moment sums, its records and its fp32 coordinates relative to it, so
+// that the centring of estimateTransform.m:55-58 cancels no digits.  That holds only for an origin INSIDE the inliers: about an
+// origin D inlier extents away the centred part of sum m (x) d survives a cancellation of ~D^2.  A fixed row may be an invalid
+// point of a georeferenced cloud, millions of extents away.  So the origin is a row of the BULK of the
+// data: of kOrgRows rows spread evenly over the registration, the one whose distance from row 0 (both point sets together) is the
+// median of the kOrgRows distances.  While more than half of those rows lie in the bulk this is one of them, wherever row 0 lies:
+// seen from a row 0 inside the bulk the far rows have the largest distances, seen from a far row 0 the bulk's distances cluster
+// (and hold the median) while row 0 itself has distance 0.  A pure function of the data -- every wave of every kernel derives the
+// same row, with one round of loads and one rank loop -- and a row of the input (no rounding).
+// Called by a full wave; the result is wave-uniform (SGPRs).
+// r2 (optional): the medians of those rows' squared distances from the origin in pts1 and in pts2 -- the data's own scale, which
+// a far row cannot move either (the staged chain sizes its records' grid by it, kGridReach).
+constexpr int kOrgRows = 31;
+__device__ __forceinline__ int wave_median_lane(double x, int lane) {          // the lane (< kOrgRows) that holds the median of lanes 0 .. kOrgRows - 1
+    int rank = 0;                                            // of (value, lane) among those lanes: a permutation, ties included
+#pragma unroll
+    for (int j = 0; j < kOrgRows; ++j) {
+        const double v = rdlane(x, j);
+        rank += (v < x || (v == x && j < lane)) ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(rank == kOrgRows / 2 && lane < kOrgRows);
+    return m ? __ffsll((long long)m) - 1 : 0;                // (m == 0: a NaN among the rows; such input has no fit anyway)
+}
+template <class PTS>
+__device__ __forceinline__ void ransac_origin(const PTS& P, int n, double (&o)[6], double* r2 = nullptr) {
+    const int lane = threadIdx.x & 63;
+    const int k = min(lane, kOrgRows - 1);
+    double q[6], z[6];
+    P.load((int)(((long long)k * (n - 1)) / (kOrgRows - 1)), q);
+    P.load(0, z);
+    double key = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) key = fma(q[c] - z[c], q[c] - z[c], key);
+    const int src = wave_median_lane(key, lane);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o[c] = rdlane(q[c], src);
+    if (r2) {
+        const double d0 = q[0] - o[0], d1 = q[1] - o[1], d2 = q[2] - o[2], m0 = q[3] - o[3], m1 = q[4] - o[4], m2 = q[5] - o[5];
+        const double k1 = d0 * d0 + d1 * d1 + d2 * d2, k2 = m0 * m0 + m1 * m1 + m2 * m2;
+        r2[0] = rdlane(k1, wave_median_lane(k1, lane));
+        r2[1] = rdlane(k2, wave_median_lane(k2, lane));
+    }
+}
+
 // calcDists (getInliersRANSAC.m:50-53) in the canonical FMA order shared with the oracle.
 __device__ __forceinline__ double sqdist(const double (&p)[6], const double (&T)[12]) {
     double tx = fma(p[3], T[0], fma(p[4], T[1], fma(p[5], T[2],  T[3])));
@@ -602,9 +646,7 @@ __device__ __forceinline__ void ransac_hyp_body(const RansacArgs& a, double* __r
         return;
     }
     double o[6];
-    P.load(0, o);   // fixed origin for the refit moments
-#pragma unroll
-    for (int c = 0; c < 6; ++c) o[c] = rdlane(o[c], 0);     // the same six numbers in every lane: SGPRs, not 12 of the kernel's 177 VGPRs
+    ransac_origin(P, n, o);   // fixed origin for the refit moments: the same six numbers in every lane (SGPRs, not 12 of the kernel's 177 VGPRs)
 
     // ---- phase 0: minimal-sample fit, one hypothesis per lane (ransac.m:42-45)
     double T1[12];
@@ -857,7 +899,7 @@ __global__ __launch_bounds__(kTBlock) void ransac_hyp_tiled_kernel(RansacArgs a)
         return;
     }
     double o[6];
-    P.load(0, o);
+    ransac_origin(P, n, o);
 
     // ---- phase 0: sample fits, one hypothesis per lane
     double T1[12];
@@ -1051,12 +1093,19 @@ struct BCtr {
 };
 constexpr int kBCtrClearWords = (int)(offsetof(BCtr, seed_h) / 4);
 
+// The records' fixed-point grid (rs_rec_exp) reaches kGridReach median distances from the origin (ransac_origin's r2), not as
+// far as the farthest correspondence: rows beyond it are OFF THE GRID -- zero records, listed (up to kOffGridMax of them, in the
+// words behind n_pass) by rs_digits_body -- and rs_pass1_body sends every refit whose inlier mask holds one to the dense fp64
+// sums; more than kOffGridMax such rows send EVERY refit there -- a cliff, not a slope: such a registration leaves the
+// matrix-core path altogether.
+constexpr double kGridReach = 16.0;
+constexpr int kOffGridMax = 62;
 struct StagedArgs {
     RansacArgs a;
     double* T1; unsigned char* v1; unsigned char* pass1; unsigned char* v2;
     unsigned char* cert;         // rank of the inlier set certified from the sample alone (rs_fit1 + rs_pass1)
     double* certq;               // [iters][2]: the sample's singular-value bounds / tolerance factor (0: no certificate)
-    double* bounds;              // [4]: max |pts1 row|^2, max |pts2 row|^2, the same of the rows relative to correspondence 0
+    double* bounds;              // [4]: max |pts1 row|^2, max |pts2 row|^2, the same of the rows relative to the origin; [4 .. 9]: the origin (ransac_origin)
     void* sel_ctr;               // SelCtr of ransac_select_multi_kernel (cleared by rs_stage1_kernel)
     double* bpart;               // [record workgroups][4]: their maxima (rs_stage1_kernel -> rs_stage2_kernel; no atomics, no clearing)
     int n_rec_blocks;
@@ -1067,16 +1116,16 @@ struct StagedArgs {
     // mask, the moments are then sums of per-correspondence records under that mask
     unsigned long long* masks;   // [iters][nslots_cap]: bit (i & 63) of word i / 64 = correspondence i is an inlier
     int nslots_cap;              // ceil(n_cap / kSPts) * kSPts / 64
-    double* rec;                 // [nslots_cap * 64][kRec]: d(3) m(3) m (x) d (9) relative to correspondence 0
+    double* rec;                 // [nslots_cap * 64][kRec]: d(3) m(3) m (x) d (9) relative to the origin
     double* mpart;               // [chunks][iters][15] partial moments
     uint4* dig;                  // [nslots_cap * 2 k-steps][4 tiles][64 lanes] x 16 int8: the records' base-128 digits (rs_digits_kernel)
     int32_t* pass_list;          // hypotheses on this path, arrival order
-    int32_t* n_pass;
+    int32_t* n_pass;             // [0] refits listed; [1] correspondences off the records' grid, [2 .. 2 + kOffGridMax) their indices
     unsigned char* dense;        // [iters] refit needs rs_moments_kernel (rank not certified, or the N == 3 branch)
     int use_lane;
     // fp32-screened scoring (rs_score32_kernel): centred single-precision copies of the correspondences and of
     // the transforms; a hypothesis with any distance within +-E of thDist is re-scored in fp64 by the same wave
-    float* c32;                  // [6][n32]: p1 - o1 (x,y,z), p2 - o2 (x,y,z) rounded to fp32, o = correspondence 0
+    float* c32;                  // [6][n32]: p1 - o1 (x,y,z), p2 - o2 (x,y,z) rounded to fp32, o = the origin (ransac_origin)
     int n32;                     // row length of c32
     float* T32a; float* T32b;    // [iters][16]: R (9, rows), t' (3), thlo, thhi, 2 pad -- sample fits / refits
     int use_f32;
@@ -1089,13 +1138,31 @@ struct StagedArgs {
 };
 
 __device__ __forceinline__ int staged_n(const RansacArgs& a) { return min(a.n_dev ? *a.n_dev : a.n_cap, a.n_cap); }
+// the registration's origin (ransac_origin), left in sa.bounds[4 .. 9] by rs_stage1_kernel for every later stage
+__device__ __forceinline__ void staged_origin(const StagedArgs& sa, double (&o)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o[c] = sa.bounds[4 + c];
+}
 
-// per-correspondence records of the moment sums (mom_core's fifteen terms), relative to correspondence 0
+// per-correspondence records of the moment sums (mom_core's fifteen terms), relative to the origin (ransac_origin)
 __device__ __forceinline__ void rs_records_body(const StagedArgs& sa, int block) {
     const RansacArgs& a = sa.a;
     const int n = staged_n(a);
     const int i = block * 256 + threadIdx.x;
     double m1 = 0.0, m2 = 0.0, c1m = 0.0, c2m = 0.0;
+    double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g2[2] = {0.0, 0.0};
+    if (n >= 1) {                                               // (workgroup-uniform) every wave derives the origin; the first leaves it for the later stages
+        const Pts<false> P0{a.p1, a.p2, a.ld, nullptr, n};
+        ransac_origin(P0, n, o, g2);
+        g2[0] *= kGridReach * kGridReach; g2[1] *= kGridReach * kGridReach;
+        if (block == 0 && threadIdx.x < 8) {
+            double v = 0.0;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v = (int)threadIdx.x == c ? o[c] : v;
+            if (threadIdx.x >= 6) v = g2[threadIdx.x - 6];
+            sa.bounds[4 + threadIdx.x] = v;                     // [4 .. 9] the origin, [10], [11] the reach of the records' grid, squared
+        }
+    }
     if (i >= n && sa.use_lane && i < sa.nslots_cap * 64) {      // padding records must be finite: the sums multiply them by 0
         double* r = sa.rec + (size_t)i * kRec;
 #pragma unroll
@@ -1103,11 +1170,11 @@ __device__ __forceinline__ void rs_records_body(const StagedArgs& sa, int block)
     }
     if (i < n) {
         Pts<false> P{a.p1, a.p2, a.ld, nullptr, n};
-        double o[6], q[6];
-        P.load(0, o); P.load(i, q);
+        double q[6];
+        P.load(i, q);
         m1 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
         m2 = q[3] * q[3] + q[4] * q[4] + q[5] * q[5];
-        if (sa.use_f32 || sa.use_lane) {                // bounds of the rows relative to correspondence 0: the fp32 screen's and the digit grid's
+        if (sa.use_f32 || sa.use_lane) {                // bounds of the rows relative to the origin: the fp32 screen's and the digit grid's
             double v[6];
 #pragma unroll
             for (int c = 0; c < 6; ++c) { v[c] = q[c] - o[c]; if (sa.use_f32) sa.c32[(size_t)c * sa.n32 + i] = (float)v[c]; }
@@ -1122,6 +1189,11 @@ __device__ __forceinline__ void rs_records_body(const StagedArgs& sa, int block)
             r[6] = m0 * d0; r[7] = m0 * d1; r[8] = m0 * d2;
             r[9] = m1_ * d0; r[10] = m1_ * d1; r[11] = m1_ * d2;
             r[12] = m2_ * d0; r[13] = m2_ * d1; r[14] = m2_ * d2; r[15] = 0.0;
+            if (c1m > g2[0] || c2m > g2[1]) {               // off the grid (rs_rec_exp): adds nothing there; r[15] marks it for rs_digits_body's list
+#pragma unroll
+                for (int e = 0; e < 15; ++e) r[e] = 0.0;
+                r[15] = 1.0;
+            }
         }
     }
     // max squared row norms of both point sets (the only global quantity the rank certificate needs):
@@ -1220,7 +1292,7 @@ __device__ __forceinline__ void rs_fit1_body(const StagedArgs& sa, int block) {
 __global__ __launch_bounds__(256) void rs_stage1_kernel(StagedArgs sa, int n_fit) {
     if ((int)blockIdx.x < n_fit) {
         if (blockIdx.x == 0) {
-            if (threadIdx.x == 0) *sa.n_pass = 0;
+            if (threadIdx.x < 2) sa.n_pass[threadIdx.x] = 0;       // the refit list's counter and the off-grid list's (filled by stage 2)
             if (threadIdx.x < 64 + 2) ((int32_t*)sa.sel_ctr)[threadIdx.x] = 0;
             if (sa.bctr && threadIdx.x < kBCtrClearWords) ((int32_t*)sa.bctr)[threadIdx.x] = 0;
         }
@@ -1253,7 +1325,16 @@ __device__ __forceinline__ void rs_pass1_body(const StagedArgs& sa, int h) {
     const bool cert = a.refine && sa.certq[2 * (size_t)h] > sqrt(sa.bounds[0]) * (1.0 + 1e-12) &&
                       sa.certq[2 * (size_t)h + 1] > sqrt(sa.bounds[1]) * (1.0 + 1e-12);
     sa.cert[h] = cert;
-    const bool lane_path = sa.use_lane && a.refine && pass && cert && c >= 4;
+    bool lane_path = sa.use_lane && a.refine && pass && cert && c >= 4;
+    if (lane_path && (sa.bounds[2] > sa.bounds[10] || sa.bounds[3] > sa.bounds[11])) {
+        // some correspondence lies off the records' grid (its record is zero): a refit whose inliers include one sums in fp64
+        const int no = sa.n_pass[1];
+        if (no > kOffGridMax) lane_path = false;
+        for (int k = 0; k < min(no, kOffGridMax) && lane_path; ++k) {
+            const int r = sa.n_pass[2 + k];
+            if ((sa.masks[(size_t)h * sa.nslots_cap + (r >> 6)] >> (r & 63)) & 1ull) lane_path = false;
+        }
+    }
     sa.dense[h] = pass && !lane_path;
     if (lane_path) sa.pass_list[atomicAdd(sa.n_pass, 1)] = h;
     if (!a.refine) {
@@ -1349,7 +1430,7 @@ __global__ __launch_bounds__(kSW * 64) void rs_score_kernel(StagedArgs sa, const
 }
 
 // ---- fp32-screened scoring ---------------------------------------------------------------------------------
-// calcDists in single precision on coordinates relative to correspondence 0: with a = p1 - o1, b = p2 - o2 and
+// calcDists in single precision on coordinates relative to the origin (ransac_origin): with a = p1 - o1, b = p2 - o2 and
 // t' = t + R o2 - o1 the residual is a - (R b + t').  Rounding analysis (u = 2^-24, A = max|a|, B = max|b|,
 // rho = largest row norm of R, tau = max|t'_c|): every component of R b + t' carries at most 5.1 u (B rho + tau)
 // (two input roundings per product, one for t', three FMA roundings), so each residual component is off by at
@@ -1419,8 +1500,7 @@ __global__ __launch_bounds__(256) void rs_stage2_kernel(StagedArgs sa, const dou
     if (h >= a.iters || !sa.use_f32) return;
     const int n = staged_n(a);
     if (n < 1) return;
-    Pts<false> P{a.p1, a.p2, a.ld, nullptr, n};
-    double o[6]; P.load(0, o);
+    double o[6]; staged_origin(sa, o);
     double T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = TT[(size_t)h * 12 + k];
@@ -1826,7 +1906,7 @@ __global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned 
 // ================================================================ hypothesis kernel, fp32-screened (LDS-resident)
 // ransac_hyp_kernel's arithmetic with rs_score32_kernel's screen in front of both scoring passes (round 4): the registrations
 // the reference really runs (n = 170 - 2000 putative matches, completeExperimentFast.m:166,205-206) stay in LDS and were scored
-// in fp64 only.  Per workgroup the correspondences are staged ONCE, relative to correspondence 0 (a = p1 - o1, b = p2 - o2):
+// in fp64 only.  Per workgroup the correspondences are staged ONCE, relative to the origin (a = p1 - o1, b = p2 - o2):
 //   c64[np / 64][6][64]      the fp64 differences (exactly mom_core's d', m': the refit sums read them back),
 //   c32[np / 128][6][2][64]  their fp32 roundings (the screen's operands), a pad lane holds NaN and scores nothing,
 // np = n rounded up to 128.  A wave owns up to 64 hypotheses (sample fits one per lane as before) and walks them four at a
@@ -2093,6 +2173,7 @@ __device__ __forceinline__ void ransac_hyp32_body(const RansacArgs& a, char* __r
     double* c64 = (double*)smem;
     float* c32 = (float*)(c64 + (size_t)6 * np);
     double* s_mx = (double*)(c32 + (size_t)6 * np);          // [NW][4]
+    double* s_org = s_mx + NW * 4;                           // [6]: the registration's origin (ransac_origin)
     if (n < a.m || n < 3) {   // randperm(ptNum)(1:minPtNum) would throw; report nothing found
         const int p = wbase + lane;
         if (wbase < a.iters && lane < min(a.hpw, a.iters - wbase)) { a.cnt1[hyp0 + p] = 0; a.cnt2[hyp0 + p] = 0; a.has[hyp0 + p] = 0; }
@@ -2102,7 +2183,13 @@ __device__ __forceinline__ void ransac_hyp32_body(const RansacArgs& a, char* __r
     // ---- stage the differences, their fp32 roundings and the four maxima the screen and the rank certificate need
     {
         double o[6];
-        P.load(0, o);
+        ransac_origin(P, n, o);
+        if (threadIdx.x < 6) {
+            double v = 0.0;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v = (int)threadIdx.x == c ? o[c] : v;
+            s_org[threadIdx.x] = v;
+        }
         double mx[4] = {0.0, 0.0, 0.0, 0.0};
         for (int i = threadIdx.x; i < np; i += NW * 64) {
             double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -2135,7 +2222,7 @@ __device__ __forceinline__ void ransac_hyp32_body(const RansacArgs& a, char* __r
     __syncthreads();
     if (wbase >= a.iters) return;
     // the workgroup's maxima: sqrt(max |p1 row|^2), sqrt(max |p2 row|^2) (rank certificate), the same of the differences (screen).
-    // Folded where they are used (three places) rather than kept in eight SGPRs across the scoring loops; likewise correspondence 0.
+    // Folded where they are used (three places) rather than kept in eight SGPRs across the scoring loops; likewise the origin (s_org).
     auto bound = [&](int k) {
         double m = s_mx[k];
 #pragma unroll
@@ -2221,7 +2308,8 @@ __device__ __forceinline__ void ransac_hyp32_body(const RansacArgs& a, char* __r
         }
         float t16[16];
         double o[6];
-        P.load(0, o);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) o[c] = s_org[c];
         make_t32(T1, o, bound(2), bound(3), a.thDist, t16, true);
 #pragma unroll
         for (int k = 0; k < 14; ++k) T32[k] = t16[k];
@@ -2307,9 +2395,8 @@ __device__ __forceinline__ void ransac_hyp32_body(const RansacArgs& a, char* __r
     bool v2 = false;
     {
         double o[6];
-        P.load(0, o);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) o[c] = rdlane(o[c], 0);
+        for (int c = 0; c < 6; ++c) o[c] = rdlane(s_org[c], 0);
 #ifdef NO_DENSE
         unsigned long long dense = 0;
 #else
@@ -2405,9 +2492,8 @@ __global__ __launch_bounds__(kTBlock) void rs_moments_kernel(StagedArgs sa) {
     const double* g1 = a.p1; const double* g2 = a.p2;
     const int nh = max(0, min(a.hpw, a.iters - wbase));
     if (n < a.m || n < 3) return;                                   // block-uniform
-    Pts<false> P{g1, g2, a.ld, nullptr, n};
     double o[6];
-    P.load(0, o);
+    staged_origin(sa, o);
     const double th = a.thDist;
     // lane l < nh owns hypothesis wbase + l: its transform and inlier count
     double T1[12];
@@ -2477,8 +2563,13 @@ __device__ __forceinline__ double rs_pair(int lo, int hi) { return __builtin_bit
 // fixed-point grid per column (2^E_c above the column's bound) and cut into eight balanced base-128 digits (int8); the
 // masks expand to 0/1 bytes; v_mfma_i32_32x32x32_i8 adds digit columns in int32 without any rounding; the eight digit sums
 // of a column are recombined in fp64 (two exact 4-digit halves, ONE rounding).  The result is the correctly rounded
-// masked sum of records truncated at 2^-57 of their column's bound: closer to the true sum than fp64 adds in any order
-// (whose error grows with the 32 k terms), at the int8 matrix rate instead of 15 fp64 FMAs per pair -- the lane-per-
+// masked sum of records rounded to 2^-57 of their column's bound.  That bound is the smaller of the column's maximum and the
+// grid's reach, kGridReach median distances from the origin (ransac_origin): it follows the bulk of the data, so one far
+// correspondence that no hypothesis accepts does not coarsen the grid for all of them.  Against records of the inliers' own size the grid is
+// finer than fp64 adds in any order (whose error grows with the 32 k terms); inliers that are kGridReach times smaller than
+// the reach lose up to 2 log2(kGridReach) = 8 of the 57 bits in the product columns, which tests/test_gpu_ransac_refit.py
+// holds against an extended-precision reference.  A correspondence beyond the reach has a zero record, and a refit that
+// counts it among its inliers takes the dense fp64 sums instead (rs_pass1_body).  At the int8 matrix rate instead of 15 fp64 FMAs per pair -- the lane-per-
 // hypothesis fp64 kernel this replaces took 247 us of the step's 2.2 ms.
 // eight digits per record column; digit p of column c sits in tile p % 4, column 2 c + p / 4 of the B operand
 constexpr int kMmRows = 64;                   // hypotheses per wave (two 32-row tiles)
@@ -2486,9 +2577,10 @@ constexpr int kMmWaves = 4;                   // waves per workgroup: 256 hypoth
 typedef int rs_v4i __attribute__((ext_vector_type(4)));
 typedef int rs_v16i __attribute__((ext_vector_type(16)));
 
-// exponent of the fixed-point grid of record column c: |record| < 2^(E - 1)  (bounds[2], [3] = max |p1 - o1|^2, |p2 - o2|^2)
-__device__ __forceinline__ int rs_rec_exp(const double* __restrict__ bounds, int c) {
-    const double D = sqrt(bounds[2]), M = sqrt(bounds[3]);
+// exponent of the fixed-point grid of record column c: |record| < 2^(E - 1) for every correspondence ON the grid, i.e. within
+// the reach (reach2 = sa.bounds[10], [11]) of the origin; bounds[2], [3] = max |p1 - o1|^2, |p2 - o2|^2 over all of them
+__device__ __forceinline__ int rs_rec_exp(const double* __restrict__ bounds, const double* __restrict__ reach2, int c) {
+    const double D = sqrt(fmin(bounds[2], reach2[0])), M = sqrt(fmin(bounds[3], reach2[1]));
     double b = c < 3 ? D : (c < 6 ? M : D * M);
     b *= 1.0000001;                           // the records' own rounding
     return (b > 0.0 && b < INFINITY) ? ilogb(b) + 2 : 0;
@@ -2501,8 +2593,17 @@ __device__ __forceinline__ void rs_digits_body(const StagedArgs& sa, uint4* __re
     const int col = lane & 31, half = lane >> 5;
     const int c = col >> 1, pd = tile + 4 * (col & 1);
     unsigned w[4] = {0u, 0u, 0u, 0u};
+    if (c == 15 && pd == 0 && (bounds[2] > sa.bounds[10] || bounds[3] > sa.bounds[11])) {      // an idle lane lists its 16 rows' off-grid marks
+        const double* r = sa.rec + (size_t)(kstep * 32 + half * 16) * kRec + 15;
+        for (int bb = 0; bb < 16; ++bb) {
+            if (r[(size_t)bb * kRec] != 0.0) {
+                const int k = atomicAdd(sa.n_pass + 1, 1);
+                if (k < kOffGridMax) sa.n_pass[2 + k] = kstep * 32 + half * 16 + bb;
+            }
+        }
+    }
     if (c < 15) {
-        const int E = rs_rec_exp(bounds, c);
+        const int E = rs_rec_exp(bounds, sa.bounds + 10, c);
         const double* r = sa.rec + (size_t)(kstep * 32 + half * 16) * kRec + c;
 #pragma unroll
         for (int bb = 0; bb < 16; ++bb) {
@@ -2591,7 +2692,7 @@ __global__ __launch_bounds__(kMmWaves * 64, 2) void rs_moments_mfma_kernel(Stage
     // of record column hrow / 2; the odd neighbour's half is 128^-4 times smaller.  The sums go through LDS (the digit stages are
     // done with) so that a hypothesis' fifteen doubles leave as one 120-byte run.
     const int c = hrow >> 1;
-    const int E = c < 15 ? rs_rec_exp(sa.bounds, c) : 0;
+    const int E = c < 15 ? rs_rec_exp(sa.bounds, sa.bounds + 10, c) : 0;
     double* s_out = (double*)&s_b[0][0] + (size_t)wave * (kMmRows * 15);             // 4 waves x 64 rows x 15 doubles = 30 KB of the 32
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -2624,8 +2725,7 @@ __global__ __launch_bounds__(64) void rs_fit2_kernel(StagedArgs sa) {
     for (int k = 0; k < 12; ++k) T2[k] = 0.0;
     if (sa.pass1[h]) {
         const int n = staged_n(a);
-        Pts<false> P{a.p1, a.p2, a.ld, nullptr, n};
-        double o[6]; P.load(0, o);
+        double o[6]; staged_origin(sa, o);
         double mom[27];
         const int c1 = a.cnt1[h];
         if (!sa.dense[h]) {                         // the chunk partials of rs_moments_mfma_kernel, in chunk order
@@ -2658,9 +2758,7 @@ __global__ __launch_bounds__(64) void rs_fit2_kernel(StagedArgs sa) {
     for (int k = 0; k < 12; ++k) a.TF[(size_t)h * 12 + k] = T2[k];
     sa.v2[h] = v2;
     if (sa.use_f32 && v2) {
-        const int n32_ = staged_n(a);
-        Pts<false> P32{a.p1, a.p2, a.ld, nullptr, n32_};
-        double o32[6]; P32.load(0, o32);
+        double o32[6]; staged_origin(sa, o32);
         make_t32(T2, o32, sqrt(sa.bounds[2]) * (1.0 + 1e-12), sqrt(sa.bounds[3]) * (1.0 + 1e-12), a.thDist, sa.T32b + (size_t)h * 16);
     }
 }
@@ -3227,7 +3325,7 @@ constexpr int kHyp32NClasses = 2;
 constexpr int kHyp32Classes[kHyp32NClasses] = {1024, 2048};
 constexpr int kHyp32Waves[kHyp32NClasses] = {8, 16};
 constexpr int kHyp32BatchCap = 3242;            // batches of a larger capacity run on the tiled kernel, as before round 4
-static size_t hyp32_lds_bytes(int n, int nw) { return (size_t)((n + 127) / 128 * 128) * 72 + (size_t)nw * 4 * sizeof(double); }
+static size_t hyp32_lds_bytes(int n, int nw) { return (size_t)((n + 127) / 128 * 128) * 72 + ((size_t)nw * 4 + 6) * sizeof(double); }
 template <int NW>
 static int launch_hyp32(const RansacArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     static bool attr_set = false;
