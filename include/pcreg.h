@@ -87,7 +87,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * "ransac_stats" (counters for pcreg_debug_ransac_stats), "range_sort_cap" (n > 0: the radius search orders segments longer
  * than n rows by its in-place large-segment path), "cluster_noskip" (the clustering walk unites on every hit instead of
  * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
- * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass); value 0
+ * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass), "score_batch_slots"
+ * (n > 0: pcreg_dev_model_score_f32 batches whole transforms under n query slots instead of 4 Mi, one transform at least); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -193,6 +194,24 @@ int pcreg_model_range_f32(pcreg_model* model, const float* q, int Q, int ldq, fl
 /* The same without a handle (rangesearch(m, q, r)): uploads and prepares the model for this call only. */
 int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, float r2, int64_t capacity,
                            int64_t* seg_off, int32_t* idx, float* dist);
+/* How well do B candidate transforms put a cloud on the model?  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- a prepared model; Q query points q in fp32, column-major with leading dimension ldq; B transforms T of 16 doubles
+ * each, column-major 4 x 4, used as quickTF.m uses them ([q, 1] * T); a squared radius r2 >= 0 (+inf allowed).
+ * Per pair (b, i): the TRANSFORMED QUERY is q[i] widened to double, ((x*T[4j] + y*T[4j+1]) + z*T[4j+2]) + T[4j+3] for j = 0, 1, 2
+ * (left to right, no contraction: quick_tf's arithmetic), each coordinate rounded once to fp32.  With the point search's
+ * distance d = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) it has THE NEAREST ROW WITHIN THE RADIUS: the model row with the smallest d among
+ * the rows with d <= r2 (inclusive), ties to the lowest original row; a NaN d never passes, an overflowed d passes r2 = +inf
+ * only.  idx[b * Q + i] is that row (0-based) or -1 when there is none, dist[b * Q + i] its d or +inf: the same bits as a
+ * brute force.  A transform whose 16 numbers are all zero is the EMPTY transform a failed ransac leaves (ransac.hip: ransac_emit_result
+ * and the last slice of ransac_select_multi_kernel store 0.0 into all 16 entries of T when `failed` is set): it scores nothing, every idx -1 and every dist +inf.
+ * Per transform b: n_close[b] the number of i with a row, sum_d2[b] the sum of their d in double -- a function of the inputs
+ * only (a fixed order: chunks of 2048 queries in query order through a fixed tree, then the chunks ascending; no
+ * floating-point atomic), the same bits on every call.  Fitness is n_close / Q and the inlier RMSE sqrt(sum_d2 / n_close):
+ * the callers' arithmetic.  idx and dist may be NULL (each on its own); then only 12 B bytes come back.
+ * Q = 0: n_close and sum_d2 are 0 for every b.  B = 0: nothing is written.  A model without rows: every query misses.
+ * PCREG_E_ARG: r2 NaN or negative, Q above 4 Mi, a negative B or Q, ldq < Q. */
+int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                          int32_t* n_close, double* sum_d2, int32_t* idx, float* dist);
 /* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
  * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
@@ -461,6 +480,20 @@ int pcreg_dev_model_range_count_f32(const pcreg_dev_model* model, const float* q
 int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, float r2, int32_t idx_base,
                                    const int64_t* seg_off, int64_t capacity, int32_t* idx, float* dist,
                                    void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_score_f32's contract on the device: q, T_dev [B][16], n_close [B], sum_d2 [B] and idx / dist [B][Q]
+ * (or NULL) are device pointers.  Nothing synchronises; no workgroup waits for another.  The B * Q transformed queries go
+ * through the walk in batches of whole transforms of at most 4 Mi query slots, each batch in ONE spatial order; tiles are
+ * skipped by DESIGN 4.1's rule with the radius as the bound.  No result depends on the batching.  Workspace, with
+ * nb = max(1, min(B, floor(4 Mi / max(Q, 1)))), S = max(nb * Q, 1) and P = nb * max(ceil(Q / 2048), 1):
+ * 131 328 + roundup(12 S, 256) + 2 roundup(4 S, 256) + roundup(8 P, 256) + roundup(4 P, 256) bytes, O(min(B Q, 4 Mi)) whatever
+ * M, r2 and the result.  A workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams at once, each
+ * call with its own workspace. */
+size_t pcreg_dev_model_score_workspace(int Q, int B, int M);
+int pcreg_dev_model_score_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                              const double* T_dev /* [B][16] on the device */, int B, float r2,
+                              int32_t* n_close /* [B] */, double* sum_d2 /* [B] */,
+                              int32_t* idx /* [B][Q] or NULL */, float* dist /* [B][Q] or NULL */,
+                              void* workspace, size_t workspace_bytes, void* stream);
 /* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain
  * (DESIGN 4.11).  label [M], indexed by ORIGINAL row: the 0-based number of the row's cluster, clusters numbered in ascending

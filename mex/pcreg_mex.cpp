@@ -14,6 +14,11 @@
 //   'modelRange', handle, queries (single Q x 3), r      -> counts (Q x 1 int32), idx (total x 1 int32, 1-based), D2 (total x 1 single,
 //                                          squared): query i's rows follow those of the queries before it, ordered by (distance, row)
 //                                          (rangesearch(model, Y, r) against the handle; matlab/rangesearchModel.m)
+//   'modelScore', handle, pts (single Q x 3), T (double 4 x 4 x B), maxDist -> nClose (B x 1 int32), sumD2 (B x 1 double), idx (Q x B
+//                                          int32, 1-based, 0 for none), D2 (Q x B single, squared; Inf for none): per transform
+//                                          the rows of pts with a model row within maxDist of [pts, 1] * T(:, :, b) and the sum of
+//                                          their squared distances; an all-zero T(:, :, b) scores nothing; the last two outputs
+//                                          are built only when asked for (matlab/scoreTransformsModel.m)
 //   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
 //                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
@@ -496,6 +501,28 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 } else { mxDestroyArray(oi); mxDestroyArray(od); }
             }
             mxDestroyArray(so);
+        }
+    } else if (!strcmp(cmd, "modelScore")) {                  // [nClose, sumD2, idx, D2] = pcreg_mex('modelScore', h, single(pts), T, maxDist)
+        if (nrhs != 5 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !radius_ok(prhs[4]))
+            usage = "modelScore: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool rows = nlhs > 2;
+            mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+            mxArray* oi = rows ? mxCreateNumericMatrix((size_t)Q, (size_t)B, mxINT32_CLASS, mxREAL) : nullptr;      // [B][Q] row-major = Q x B
+            mxArray* od = rows ? mxCreateNumericMatrix((size_t)Q, (size_t)B, mxSINGLE_CLASS, mxREAL) : nullptr;
+            int32_t* di = rows ? (int32_t*)mxGetData(oi) : nullptr;
+            if (B > 0) rc = pcreg_model_score_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2, (int32_t*)mxGetData(on),
+                                                  mxGetPr(os), di, rows ? (float*)mxGetData(od) : nullptr);
+            if (rc == PCREG_OK) {
+                for (size_t k = 0; rows && k < (size_t)Q * (size_t)B; ++k) di[k] += 1;
+                plhs[0] = on; plhs[1] = os;
+                if (rows) { plhs[2] = oi; plhs[3] = od; }
+            } else { mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(oi); mxDestroyArray(od); }
         }
     } else if (!strcmp(cmd, "modelCluster")) {                // [label, clOff, members] = pcreg_mex('modelCluster', h, r): clusterPoints(model, r)
         if (nrhs != 3 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2])) usage = "modelCluster: handle (uint64), r (a real scalar >= 0)";

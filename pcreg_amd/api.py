@@ -686,6 +686,27 @@ def aggregate_matches(pts1, pts2):
     return np.ascontiguousarray(o1[:u]), np.ascontiguousarray(o2[:u]), ia[:u] - 1
 
 
+def _transforms16(T) -> np.ndarray:
+    """[B, 16] float64, each transform column-major: from a [B, 4, 4] array, one 4 x 4 matrix, or a sequence of 4 x 4 matrices
+    in which None (or an empty array: MATLAB's []) stands for the empty transform, sixteen zeros"""
+    if isinstance(T, np.ndarray) and T.ndim == 2:
+        T = T[None]
+    mats = [np.zeros((4, 4)) if t is None or np.size(t) == 0 else np.asarray(t, dtype=np.float64) for t in T]
+    if any(m.shape != (4, 4) for m in mats):
+        raise ValueError("every transform is a 4 x 4 matrix (or None: the empty transform)")
+    return np.ascontiguousarray([m.ravel(order="F") for m in mats], dtype=np.float64).reshape(-1, 16)
+
+
+def score_summary(n_close, sum_d2, Q: int) -> dict:
+    """the callers' arithmetic on a scoring call's counts and sums: fitness = n_close / Q (0 without queries), rmse =
+    sqrt(sum_d2 / n_close) (NaN where nothing is close)"""
+    n_close, sum_d2 = np.asarray(n_close, dtype=np.int32), np.asarray(sum_d2, dtype=np.float64)
+    fitness = n_close / float(Q) if Q > 0 else np.zeros(len(n_close))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rmse = np.where(n_close > 0, np.sqrt(sum_d2 / np.maximum(n_close, 1)), np.nan)
+    return dict(n_close=n_close, sum_d2=sum_d2, fitness=fitness, rmse=rmse)
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or
@@ -732,6 +753,32 @@ class Model:
         q = _fcol(query, np.float32)
         Q = q.shape[0]
         return _range_call(lambda cap, so, i, d: check(lib().pcreg_model_range_f32(self._h, q.ctypes.data, Q, max(Q, 1), r2, cap, so.ctypes.data, i, d)), Q)
+
+    def score_transforms(self, query, T, r2: float, rows: bool = False):
+        """How well B transforms put `query` (Q x 3) on the prepared model (pcreg_model_score_f32).  T: a [B, 4, 4] array or a
+        sequence of 4 x 4 matrices used as quickTF uses them, None or an all-zero matrix being the empty transform (it scores
+        nothing); r2 the squared radius -> dict(n_close [B] int32, the queries with a model row within r2 of their
+        transformed place; sum_d2 [B] float64, the sum of those squared distances; fitness = n_close / Q; rmse =
+        sqrt(sum_d2 / n_close), NaN where nothing is close), and with rows=True also idx [B, Q] int32 (0-based, -1 for none)
+        and dist [B, Q] float32 (squared, +inf for none) -- the bits of a brute-force fp32 search."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        n_close = np.zeros(max(B, 1), dtype=np.int32)
+        sum_d2 = np.zeros(max(B, 1), dtype=np.float64)
+        idx = np.zeros((B, Q), dtype=np.int32) if rows else None
+        dist = np.zeros((B, Q), dtype=np.float32) if rows else None
+        check(lib().pcreg_model_score_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                          n_close.ctypes.data, sum_d2.ctypes.data, idx.ctypes.data if rows and B * Q else None,
+                                          dist.ctypes.data if rows and B * Q else None))
+        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        if rows:
+            res.update(idx=idx, dist=dist)
+        return res
 
     def cluster(self, r2: float):
         """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,

@@ -25,6 +25,7 @@ void set_error(const char* fmt, ...) {
 constexpr int kKnnMaxK = PCREG_KNN_MAX_K;        // (named here so that no argument message spells the macro)
 constexpr int kKnnMaxQ = 4 << 20;                  // queries per k-nearest call: the top-2 search's limit
 constexpr int kRangeMaxQ = 4 << 20;                // queries per radius-search call: the same limit
+constexpr int kScoreMaxQ = 4 << 20;                // queries per transform-scoring call: the same limit
 static std::mutex g_mu;
 static int g_device_ok = -1;          // -1 unknown, 0 ok, else error code
 static hipStream_t g_stream = nullptr;
@@ -119,7 +120,7 @@ int pcreg_debug_set(const char* key, int value) {
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
                                                         "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap", "cluster_noskip",
-                                                        "cluster_stats", "knn_tail_cap"};
+                                                        "cluster_stats", "knn_tail_cap", "score_batch_slots"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -374,6 +375,16 @@ int pcreg_dev_model_range_fill_f32(const pcreg_dev_model* model, const float* q,
     return launch_model_range_fill(model->v, q, Q, ldq, r2, idx_base, seg_off, capacity, idx, dist, workspace, workspace_bytes,
                                    (hipStream_t)stream);
 }
+size_t pcreg_dev_model_score_workspace(int Q, int B, int M) { return score_ws_bytes(Q, B, M); }
+int pcreg_dev_model_score_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                              int32_t* n_close, double* sum_d2, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && n_close && sum_d2)));
+    PCREG_ARG(workspace_bytes >= score_ws_bytes(Q, B, 0));                   // (the size does not depend on M)
+    GUARD();
+    return launch_model_score(model->v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, workspace, workspace_bytes, (hipStream_t)stream);
+}
 size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -549,6 +560,37 @@ int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return range_on_view(st, v, q, Q, ldq, r2, capacity, seg_off, idx, dist);
+}
+
+// B transforms scored against a prepared model: upload the queries and the transforms, score, read the 12 B bytes of counts
+// and sums back, and the [B][Q] rows and distances when the caller asked for them
+int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int32_t* n_close,
+                          double* sum_d2, int32_t* idx, float* dist) {
+    PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && n_close && sum_d2)));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const ModelView& v = model->dm->v;
+    const size_t wsb = score_ws_bytes(Q, B, v.M), bq = (size_t)B * Q;
+    float *dq, *dd; double *dT, *ds; int32_t *dn, *di; char* ws;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * (size_t)B, &dT));
+    TRY(st.take((size_t)B, &dn));
+    TRY(st.take((size_t)B, &ds));
+    TRY(st.take(idx ? bq : 0, &di));
+    TRY(st.take(dist ? bq : 0, &dd));
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * (size_t)B, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_model_score(v, dq, Q, Q, dT, B, r2, dn, ds, idx ? di : nullptr, dist ? dd : nullptr, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(n_close, dn, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(sum_d2, ds, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
+    if (idx && bq) PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * bq, hipMemcpyDeviceToHost, g_stream));
+    if (dist && bq) PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * bq, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
 }
 
 // clusterPoints on a prepared model: label the rows on the device, read the labels back, and form the CSR lists on the host by

@@ -91,6 +91,8 @@ enum DebugKey {
     kDbgClusterStats,          // "cluster_stats": the clustering walk counts hits and compare-and-swaps (pcreg_debug_cluster_stats)
     kDbgKnnTailCap,            // "knn_tail_cap": n > 0 -- the point search's exact tail (few-form) lists the surviving tiles of n tiles per
                                // pass instead of its LDS list's capacity
+    kDbgScoreBatchSlots,       // "score_batch_slots": n > 0 -- the transform scoring batches whole transforms under n query slots instead
+                               // of 4 Mi (at least one transform a batch), to reach its batch loop at a small size
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -203,6 +205,13 @@ int launch_model_range_count(const ModelView& v, const float* q, int Q, int ldq,
                              size_t ws_bytes, hipStream_t st);
 int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, float r2, int32_t idx_base, const int64_t* seg_off,
                             int64_t capacity, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
+// the radius search's R1 alone: the per-parent-cell counts of the queries, into a cleared qcnt [kQueryKeys + 64] (knn_range.hip)
+int launch_query_cells(const ModelView& v, const float* q, int Q, int ldq, int32_t* qcnt, hipStream_t st);
+// B transforms of one query cloud scored against the model (knn_score.hip): per transform the queries with a row within r2 and
+// the sum of their squared distances; idx / dist [B][Q] (either may be null) the nearest such row, -1 / +inf for none
+size_t score_ws_bytes(int Q, int B, int M);
+int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
+                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
 // connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,

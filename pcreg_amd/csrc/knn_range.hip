@@ -256,11 +256,21 @@ RangeWs range_ws_layout(int Q, void* base, size_t* bytes) {
     return s;
 }
 
+}  // namespace
+
+// R1: qcnt (kQueryKeys counters and the 256 bytes behind them) cleared, then the counts
+int launch_query_cells(const ModelView& v, const float* q, int Q, int ldq, int32_t* qcnt, hipStream_t st) {
+    PCREG_HIP(hipMemsetAsync(qcnt, 0, (size_t)kQueryKeys * 4 + 256, st));
+    hipLaunchKernelGGL(range_qcell_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, qcnt);
+    return PCREG_OK;
+}
+
+namespace {
+
 // R1 + R2 of either call
 int range_order(const ModelView& v, const float* q, int Q, int ldq, const RangeWs& s, hipStream_t st) {
-    PCREG_HIP(hipMemsetAsync(s.qcnt, 0, (size_t)kQueryKeys * 4 + 256, st));
-    hipLaunchKernelGGL(range_qcell_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, s.qcnt);
-    return launch_query_order(v, q, Q, ldq, s.qcnt, s.qperm, st);
+    const int rc = launch_query_cells(v, q, Q, ldq, s.qcnt, st);
+    return rc ? rc : launch_query_order(v, q, Q, ldq, s.qcnt, s.qperm, st);
 }
 
 }  // namespace

@@ -1,0 +1,222 @@
+// pcreg_amd/csrc/knn_score.hip -- score B candidate transforms of one query cloud against a PREPARED model: per transform the
+// number of queries with a model row within a squared distance r2 and the sum of those squared distances (fitness and inlier
+// RMSE are the caller's arithmetic on them), and on request the nearest row and its distance per (transform, query).
+//
+// Contract (include/pcreg.h): the transformed query is quick_tf_kernel's arithmetic in double on the widened fp32
+// query, rounded once to fp32; the nearest row is the one with the smallest d = fmaf(dz,dz, fmaf(dy,dy, dx*dx)) among the rows
+// with d <= r2 (inclusive; NaN never passes; +inf passes r2 = +inf only), ties to the lowest original row.  An all-zero
+// transform (what a failed ransac leaves) scores nothing.  Exact by construction: every distance is the fp32 chain itself.
+//
+// The prepared model (knn_fast.hip) is used as it is.  Per batch of whole transforms (at most 4 Mi query slots):
+//   C1  score_transform_kernel        the batch's transformed queries, one fp32 SoA [3][nb Q]; an empty transform's are NaN
+//   C2  launch_query_cells + launch_query_order   ALL the batch's slots in one spatial order (knn_range.hip, knn_fast.hip)
+//   C3  score_walk_kernel             range_walk_kernel's block box and visit rule (D = r2); four lanes per query keep their best
+//                                     (d, row), combined by two shuffles; the result goes to slot [b][i]
+//   C4  score_reduce_kernel           per (transform, chunk of 2048 queries): count and sum in query order, a fixed tree
+//       score_total_kernel            per transform: its chunks in ascending order
+// sum_d2 is a function of the inputs alone: no floating-point atomic, and no term's place depends on the batch or the walk.
+#include "common.hpp"
+#include "knn_fast_common.hpp"
+#include "knn_walk.hpp"
+#include "chunk_scan.hpp"
+#include <climits>
+#include <cmath>
+
+namespace pcreg {
+
+namespace {
+
+constexpr int kScoreMaxSlots = kMaxQTiles * 1024;    // 4 Mi query slots per walk (and queries per call)
+static_assert(kScanBlock == kBlock, "score_reduce_kernel's threads own kScanPer consecutive queries each");
+
+// ---- C1. the transformed queries ----------------------------------------------------------------------------------------
+// slot s = bl * Q + i of the batch: [q_i, 1] * T_bl as quick_tf_kernel forms it (sweep.hip; -ffp-contract=off), rounded once
+__global__ __launch_bounds__(kBlock) void score_transform_kernel(const float* __restrict__ q, int Q, int ldq, const double* __restrict__ T,
+                                                                 int n_slots, float* __restrict__ tq) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_slots) return;
+    const int bl = s / Q, i = s - bl * Q;
+    double t[16];
+    bool empty = true;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { t[e] = T[(size_t)bl * 16 + e]; empty = empty && t[e] == 0.0; }
+    const double x = (double)q[i], y = (double)q[i + (size_t)ldq], z = (double)q[i + 2 * (size_t)ldq];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double v = ((x * t[4 * j] + y * t[4 * j + 1]) + z * t[4 * j + 2]) + t[4 * j + 3];
+        tq[s + (size_t)j * n_slots] = empty ? __int_as_float(0x7FC00000) : (float)v;
+    }
+}
+
+// ---- C3. the walk -------------------------------------------------------------------------------------------------------
+// range_walk_kernel's shape (knn_range.hip): workgroup (block qb, part p) owns slots qb * 512 + p * 64 + (tid >> 2), lane sub of
+// a query scores rows sub, sub + 4, .. of every visited tile.  A tile is skipped by DESIGN 4.1's rule with D = r2 and the block's
+// box: every row of a skipped tile has a computed d > r2 for every query of the block, so it holds no answer.  A lane admits
+// d <= bnd, bnd = r2 until its first hit and its best d afterwards (still inclusive: an equal d with a lower row must win).
+// best[slot's query] = the d of a hit, NaN for a miss (a hit's d is never NaN; with r2 = +inf it may be +inf).
+__global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restrict__ q, int Q, const int32_t* __restrict__ qperm,
+                                                            const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
+                                                            const float* __restrict__ tbox, int n_tiles, int cull, float r2,
+                                                            float* __restrict__ best, int32_t* __restrict__ idx, float* __restrict__ dist,
+                                                            unsigned long long* __restrict__ stats) {
+    __shared__ WalkLds lds;
+    __shared__ float s_red[kBlock / 64][6];
+    __shared__ float s_box[6];
+    const int tid = threadIdx.x;
+    const int qb = blockIdx.x / kWalkWgPerBlock, part = blockIdx.x % kWalkWgPerBlock;
+    walk_block_box<6>(s_red, s_box, q, Q, Q, qperm, nullptr, qb);
+    if (stats && blockIdx.x == 0 && tid == 0) {
+        atomicAdd(&stats[0], 1ull);
+        atomicAdd(&stats[2], (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
+    }
+    const int sub = tid & (kWalkLanes - 1), ql = tid / kWalkLanes;
+    const int slot = qb * kWalkQBlock + part * kWalkQPerWg + ql;
+    const bool live = slot < Q;
+    const int qi = live ? qperm[slot] : 0;
+    const float qx = q[qi], qy = q[qi + (size_t)Q], qz = q[qi + 2 * (size_t)Q];
+    float bnd = live ? r2 : -1.0f;                                // (a dead lane admits nothing: d is never negative)
+    float bd = INFINITY; int br = INT_MAX;                        // the lane's best; br == INT_MAX: none yet
+    walk_tiles(
+        lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
+        [&](int ct) {
+            return !(cull != 0 && r2 < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, s_box, s_box + 3), r2));
+        },
+        [&](int r) { return walk_row(ms, perm, M, r); },
+        [](int) {},
+        [&](int, const float4 (&p)[4], float (&d)[4]) {
+            if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= bnd) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int row = __float_as_int(p[u].w);
+                    if (d[u] <= bnd && (d[u] < bd || row < br)) { bd = d[u]; br = row; bnd = bd; }
+                }
+            }
+        },
+        [] {});
+#pragma unroll
+    for (int o = 1; o < kWalkLanes; o <<= 1) {
+        const float od = __shfl_xor(bd, o);
+        const int orow = __shfl_xor(br, o);
+        if (od < bd || (od == bd && orow < br)) { bd = od; br = orow; }
+    }
+    if (live && sub == 0) {
+        const bool hit = br != INT_MAX;
+        best[qi] = hit ? bd : __int_as_float(0x7FC00000);
+        if (idx) idx[qi] = hit ? br : -1;
+        if (dist) dist[qi] = hit ? bd : INFINITY;
+    }
+}
+
+// every (transform, query) of a model without rows: a miss
+__global__ __launch_bounds__(kBlock) void score_miss_kernel(size_t n, int32_t* __restrict__ idx, float* __restrict__ dist) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        if (idx) idx[i] = -1;
+        if (dist) dist[i] = INFINITY;
+    }
+}
+
+// ---- C4. count and sum --------------------------------------------------------------------------------------------------
+// workgroup bl * chunks + c: queries c * 2048 .. of the batch's transform bl.  Thread t adds its kScanPer consecutive queries in
+// query order, then chunk_sum's tree (chunk_scan.hpp): one fixed order per chunk, whatever the batch
+__global__ __launch_bounds__(kBlock) void score_reduce_kernel(const float* __restrict__ best, int Q, int chunks, double* __restrict__ psum,
+                                                              int32_t* __restrict__ pcnt) {
+    const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
+    const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
+    double sum = 0.0; int32_t cnt = 0;
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        if (i0 + u < Q) {
+            const float d = best[(size_t)bl * Q + i0 + u];
+            if (d == d) { sum += (double)d; ++cnt; }
+        }
+    }
+    chunk_sum(sum, psum);
+    chunk_sum(cnt, pcnt);
+}
+// thread bl: transform bl's chunks in ascending order
+__global__ __launch_bounds__(kBlock) void score_total_kernel(const double* __restrict__ psum, const int32_t* __restrict__ pcnt, int nb, int chunks,
+                                                             int32_t* __restrict__ n_close, double* __restrict__ sum_d2) {
+    const int bl = blockIdx.x * kBlock + threadIdx.x;
+    if (bl >= nb) return;
+    double sum = 0.0; int32_t cnt = 0;
+    for (int c = 0; c < chunks; ++c) { sum += psum[(size_t)bl * chunks + c]; cnt += pcnt[(size_t)bl * chunks + c]; }
+    n_close[bl] = cnt;
+    sum_d2[bl] = sum;
+}
+
+// whole transforms per batch under a cap of `slots` query slots (at least one: Q <= kScoreMaxSlots)
+int score_batch(int Q, int B, int slots) {
+    const int per = slots / (Q > 0 ? Q : 1);
+    return std::max(1, std::min(B, per));
+}
+int score_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk); }
+
+// Workspace, S = max(nb Q, 1) slots and P = nb max(ceil(Q / 2048), 1) partials of a full batch of nb = max(1, min(B, floor(4 Mi /
+// max(Q, 1)))) transforms: [per-parent-cell counters] [transformed queries, 3 S] [slot -> query, S] [best d per slot, S]
+// [chunk sums, P] [chunk counts, P]:
+// 131 328 + roundup(12 S, 256) + 2 roundup(4 S, 256) + roundup(8 P, 256) + roundup(4 P, 256) bytes
+struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; };
+ScoreWs score_ws_layout(int Q, int B, void* base, size_t* bytes) {
+    ScoreWs s{};
+    const int nb = score_batch(Q, B, kScoreMaxSlots);
+    const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * score_chunks(Q);
+    WsWalk w(base);
+    s.qcnt = (int32_t*)w.take_bytes((size_t)kQueryKeys * 4 + 256);
+    s.tq = w.take<float>(3 * S);
+    s.qperm = w.take<int32_t>(S);
+    s.best = w.take<float>(S);
+    s.psum = w.take<double>(P);
+    s.pcnt = w.take<int32_t>(P);
+    *bytes = w.bytes();
+    return s;
+}
+
+}  // namespace
+
+size_t score_ws_bytes(int Q, int B, int M) {
+    (void)M;                                       // O(min(B Q, 4 Mi)) bytes, whatever M, r2 and the result
+    if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
+    size_t b; (void)score_ws_layout(Q, B, nullptr, &b);
+    return b;
+}
+
+int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
+                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxSlots && r2 >= 0.0f);
+    size_t need;
+    const ScoreWs s = score_ws_layout(Q, B, ws, &need);
+    if (ws_bytes < need) { set_error("bad argument: score workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_ARG; }
+    if (B == 0) return PCREG_OK;
+    if (Q == 0 || v.M == 0) {                                     // every query misses
+        PCREG_HIP(hipMemsetAsync(n_close, 0, sizeof(int32_t) * (size_t)B, st));
+        PCREG_HIP(hipMemsetAsync(sum_d2, 0, sizeof(double) * (size_t)B, st));
+        const size_t n = (size_t)B * Q;
+        if (n > 0 && (idx || dist)) {
+            hipLaunchKernelGGL(score_miss_kernel, dim3((unsigned)std::min((n + kBlock - 1) / kBlock, (size_t)4096)), dim3(kBlock), 0, st, n, idx, dist);
+            PCREG_HIP(hipGetLastError());
+        }
+        return PCREG_OK;
+    }
+    const int dbg_slots = debug_flag(kDbgScoreBatchSlots);        // "score_batch_slots": a lower cap, same results
+    const int nb_max = score_batch(Q, B, dbg_slots > 0 ? std::min(dbg_slots, kScoreMaxSlots) : kScoreMaxSlots);
+    const int n_tiles = (v.M + kT16 - 1) / kT16, chunks = score_chunks(Q);
+    const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
+    for (int b0 = 0; b0 < B; b0 += nb_max) {
+        const int nb = std::min(nb_max, B - b0), S = nb * Q;
+        const size_t at = (size_t)b0 * Q;
+        hipLaunchKernelGGL(score_transform_kernel, dim3((S + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, T_dev + (size_t)b0 * 16, S, s.tq);
+        int rc = launch_query_cells(v, s.tq, S, S, s.qcnt, st);
+        if (!rc) rc = launch_query_order(v, s.tq, S, S, s.qcnt, s.qperm, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(score_walk_kernel, dim3((unsigned)(((S + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock)), dim3(kBlock), 0, st,
+                           (const float*)s.tq, S, (const int32_t*)s.qperm, (const float*)v.ms, (const int32_t*)v.perm, v.M, (const float*)v.tbox,
+                           n_tiles, cull, r2, s.best, idx ? idx + at : nullptr, dist ? dist + at : nullptr, knn_stats_dev());
+        hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, Q, chunks, s.psum, s.pcnt);
+        hipLaunchKernelGGL(score_total_kernel, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, nb,
+                           chunks, n_close + b0, sum_d2 + b0);
+        PCREG_HIP(hipGetLastError());
+    }
+    return PCREG_OK;
+}
+
+}  // namespace pcreg

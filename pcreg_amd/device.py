@@ -132,6 +132,42 @@ class PreparedModel:
             self.rangesearch_fill(q_soa, r2, seg_off, idx, dist, idx_base)
         return seg_off, idx, dist
 
+    def score_transforms(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, rows: bool = False, out=None):
+        """How well B transforms put a cloud on the model, on torch's current stream (pcreg_dev_model_score_f32): q_soa a [3, Q]
+        float32 tensor with contiguous rows, T_dev a contiguous float64 tensor of B x 16 numbers (each transform column-major
+        4 x 4, used as quickTF uses it; all zeros: the empty transform, which scores nothing), r2 the squared radius ->
+        (n_close [B] int32, the queries with a model row within r2 of their transformed place; sum_d2 [B] float64, the sum of
+        those squared distances), and with rows=True also (idx [B, Q] int32, the nearest such row, -1 for none; dist [B, Q]
+        float32, +inf for none).  Fitness is n_close / Q and the inlier RMSE sqrt(sum_d2 / n_close).  Nothing synchronises.
+        The workspace is cached on the model and grown on demand; calls that may overlap on two streams pass buffers of
+        their own, out=(n_close, sum_d2, idx, dist, ws) with ws of pcreg_dev_model_score_workspace(Q, B, M) bytes (idx and
+        dist None without rows)."""
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
+            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        r2 = float(r2)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
+        need = max(int(lib().pcreg_dev_model_score_workspace(Q, B, self.M)), 256)
+        if out is not None:
+            n_close, sum_d2, idx, dist, ws = out
+        else:
+            n_close = torch.empty(B, dtype=torch.int32, device=dev)
+            sum_d2 = torch.empty(B, dtype=torch.float64, device=dev)
+            idx = torch.empty((B, Q), dtype=torch.int32, device=dev) if rows else None
+            dist = torch.empty((B, Q), dtype=torch.float32, device=dev) if rows else None
+            ws = getattr(self, "_score_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._score_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if B:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                check(lib().pcreg_dev_model_score_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(T_dev), B, r2,
+                                                      _p(n_close), _p(sum_d2), _p(idx) if idx is not None and Q else None,
+                                                      _p(dist) if dist is not None and Q else None, _p(ws), ws.numel(), _stream()))
+        return (n_close, sum_d2, idx, dist) if rows else (n_close, sum_d2)
+
     def cluster(self, r2: float, out=None):
         """clusterPoints(model, r) over the model's own rows with r2 = r^2, on torch's current stream
         (pcreg_dev_model_cluster_f32): -> (label [M] int32, the 0-based cluster of every row; n_clusters [1] int32; first [M]

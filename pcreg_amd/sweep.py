@@ -16,8 +16,8 @@ import torch
 
 from . import _lib as _l
 from ._lib import RansacOpts, check, lib
-from .api import _match_opts, cluster_points, invertTF
-from .device import DescriptorPipeline, _p, _stream
+from .api import _match_opts, _transforms16, cluster_points, invertTF, score_summary
+from .device import DescriptorPipeline, PreparedModel, _p, _stream
 
 
 def pcUniformSamples(pts, d: float, limits=None) -> np.ndarray:
@@ -501,6 +501,24 @@ def largest_cluster(result: dict, thSucc: float = 0, thInliers: float = 28, thRa
     rows = np.sort(np.asarray(members[cl_off[c]:cl_off[c + 1]], dtype=np.int64))
     trials = good[rows].astype(np.int64)
     return trials, np.asarray(result["trial"], dtype=np.int64)[trials]
+
+
+def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float) -> dict:
+    """Every trial of a sweep's result scored on the dense clouds (PreparedModel.score_transforms): put the surface ([3, Q]
+    float32) on the prepared dense model with invertTF(transforms[t]) -- ransac's transforms map model onto surface -- and count
+    the surface points with a model point within max_dist.  A failed trial (None) is the empty transform and scores nothing.
+    -> dict(n_close [n] int32, sum_d2 [n] float64, fitness = n_close / Q, rmse = sqrt(sum_d2 / n_close), NaN where nothing is
+    close), aligned with result["trial"].  One upload (the [n][16] block) and one read (12 bytes per trial); the radius is
+    squared once in single, and the comparison is the point search's: fp32, inclusive."""
+    tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
+    Q, n = int(surface_soa.shape[1]), len(tf)
+    if n == 0:
+        return score_summary(np.zeros(0, np.int32), np.zeros(0), Q)
+    T_dev = torch.from_numpy(_transforms16(tf)).to(surface_soa.device)
+    r2 = float(np.float32(max_dist) * np.float32(max_dist))
+    n_close, sum_d2 = model.score_transforms(surface_soa, T_dev, r2)
+    both = torch.cat([sum_d2.view(torch.int32), n_close]).cpu().numpy()
+    return score_summary(both[2 * n:], both[:2 * n].view(np.float64), Q)
 
 
 def quickTF_dev(pts_soa: torch.Tensor, TF: np.ndarray) -> torch.Tensor:
