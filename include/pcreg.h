@@ -88,7 +88,7 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * than n rows by its in-place large-segment path), "cluster_noskip" (the clustering walk unites on every hit instead of
  * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
  * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass), "score_batch_slots"
- * (n > 0: pcreg_dev_model_score_f32 batches whole transforms under n query slots instead of 4 Mi, one transform at least); value 0
+ * (n > 0: pcreg_dev_model_score_f32 and pcreg_dev_model_refit_f32 batch whole transforms under n query slots instead of 4 Mi, one transform at least); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -212,6 +212,34 @@ int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M
  * PCREG_E_ARG: r2 NaN or negative, Q above 4 Mi, a negative B or Q, ldq < Q. */
 int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
                           int32_t* n_close, double* sum_d2, int32_t* idx, float* dist);
+/* Refit B candidate transforms on their close dense pairs: completeExperimentFast.m:383-394's T_refine on the whole cloud, for every
+ * candidate at once.  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- those of pcreg_model_score_f32 (a prepared model, Q fp32 points column-major with ldq, B transforms of 16 doubles used
+ * as quickTF.m uses them, a squared radius r2 >= 0, +inf allowed).
+ * THE PAIRS of transform b are exactly scoring's: for every query i whose TRANSFORMED QUERY p' (that contract: double arithmetic
+ * without contraction, rounded once to fp32) has a NEAREST ROW WITHIN THE RADIUS (d <= r2 inclusive, ties to the lowest original
+ * row, a NaN d never passes), the pair (that model row, p'), taken in ascending i, both sides widened to double.
+ * Per transform b:  n_close[b] and sum_d2[b] are THE SAME BITS pcreg_model_score_f32 returns for the same inputs.
+ * T_step[b] = estimateTransform(pts1 = the model rows, pts2 = the moved points), this library's estimateTransform
+ * ([pts2, 1] * T = [pts1, 1]; the rank test of estimateTransform.m:11-14; exactly three pairs by the synthetic fourth point of
+ * :18-37; more by the moments of the pairs; no reflection fix), so that quickTF(quickTF(q, T[b]), T_step[b]) lies on the model --
+ * the map the reference obtains as invertTF(T_refine) at :391-394 (the arguments in this order save the inversion).
+ * T_out[b] = T[b] * T_step[b] in double, entry (r, c) -- at [r + 4 c] of the 16 -- being
+ * ((T(r,0) S(0,c) + T(r,1) S(1,c)) + T(r,2) S(2,c)) + T(r,3) S(3,c), left to right, no contraction.
+ * empty[b] = 1 and all 16 entries of T_step[b] and of T_out[b] are 0.0 when estimateTransform is empty (the rank test fails, or
+ * the rotation is undefined), when there are fewer than three pairs, or when T[b] is itself the empty (all-zero) transform: the
+ * form in which a failed ransac and pcreg_refine_by_distance report a failed fit, so a failed candidate stays failed when the
+ * step is repeated.  Otherwise empty[b] = 0.
+ * Everything is a function of the inputs only: the moment sums take a fixed order (per chunk of 2048 queries in query order
+ * through a fixed tree, then the chunks ascending, as sum_d2 does), shifted by one origin per model (the middle of the model's
+ * bounding box as the handle holds it in fp32, for both sides); no floating-point atomic; batching, culling and the order in
+ * which the walk meets the queries change nothing.
+ * Q = 0 or a model without rows: every transform is empty, the counts 0.  B = 0: nothing is written.
+ * THIS entry runs `steps` >= 1 such steps on the device, each step's T_out the next one's T, with one upload and one read:
+ * T_out is the last step's, and so are n_close, sum_d2 and empty -- the counts therefore describe the transform that went INTO
+ * the last step (T itself when steps = 1), not T_out.  PCREG_E_ARG: pcreg_model_score_f32's cases, and steps < 1. */
+int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                          int steps, double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* empty);
 /* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
  * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
@@ -493,6 +521,22 @@ int pcreg_dev_model_score_f32(const pcreg_dev_model* model, const float* q, int 
                               const double* T_dev /* [B][16] on the device */, int B, float r2,
                               int32_t* n_close /* [B] */, double* sum_d2 /* [B] */,
                               int32_t* idx /* [B][Q] or NULL */, float* dist /* [B][Q] or NULL */,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* ONE step of pcreg_model_refit_f32's contract on the device: q, T_dev [B][16], T_out [B][16], T_step [B][16] (or
+ * NULL: not wanted), n_close [B], sum_d2 [B] and empty [B] are device pointers.  T_out may not alias T_dev (a caller that
+ * repeats the step alternates two blocks).  Nothing synchronises; no workgroup waits for another.  The chain is
+ * pcreg_dev_model_score_f32's -- the same batches of whole transforms, the same walk and culling rule, with the winning row's
+ * coordinates kept per query slot -- followed per batch by the moments per (transform, chunk of 2048 queries) and the fit per
+ * transform.  No result depends on the batching.  Workspace, with nb, S and P as for pcreg_dev_model_score_workspace: that
+ * layout followed by the winning rows' coordinates and the chunk moments,
+ * 131 328 + 2 roundup(12 S, 256) + 2 roundup(4 S, 256) + roundup(8 P, 256) + roundup(4 P, 256) + roundup(216 P, 256) bytes.  A
+ * workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams at once, each call with its own workspace.
+ * The debug keys "score_batch_slots" and "knn_nocull" act on this chain as on scoring's. */
+size_t pcreg_dev_model_refit_workspace(int Q, int B, int M);
+int pcreg_dev_model_refit_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                              const double* T_dev /* [B][16] on the device */, int B, float r2,
+                              double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                              int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* empty /* [B] */,
                               void* workspace, size_t workspace_bytes, void* stream);
 /* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain

@@ -19,6 +19,12 @@
 //                                          the rows of pts with a model row within maxDist of [pts, 1] * T(:, :, b) and the sum of
 //                                          their squared distances; an all-zero T(:, :, b) scores nothing; the last two outputs
 //                                          are built only when asked for (matlab/scoreTransformsModel.m)
+//   'modelRefit', handle, pts (single Q x 3), T (double 4 x 4 x B), maxDist, steps -> Tout (double 4 x 4 x B), nClose (B x 1 int32),
+//                                          sumD2 (B x 1 double): every T(:, :, b) refitted `steps` times on the rows of pts with a
+//                                          model row within maxDist of their moved place -- T <- T * estimateTransform(model rows,
+//                                          moved points); a zero page where there is no fit (fewer than three pairs, an empty
+//                                          estimateTransform, an all-zero T(:, :, b)); nClose / sumD2 are 'modelScore''s for the
+//                                          transform that went into the last step (matlab/refitTransformsModel.m)
 //   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
 //                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
@@ -523,6 +529,30 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 plhs[0] = on; plhs[1] = os;
                 if (rows) { plhs[2] = oi; plhs[3] = od; }
             } else { mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(oi); mxDestroyArray(od); }
+        }
+    } else if (!strcmp(cmd, "modelRefit")) {                  // [Tout, nClose, sumD2] = pcreg_mex('modelRefit', h, single(pts), T, maxDist, steps)
+        if (nrhs != 6 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !radius_ok(prhs[4]) || !mxIsDouble(prhs[5]) ||
+            mxGetM(prhs[5]) * mxGetN(prhs[5]) != 1 || !(mxGetScalar(prhs[5]) >= 1.0) || !(mxGetScalar(prhs[5]) <= 1e6) ||
+            mxGetScalar(prhs[5]) != (double)(int)mxGetScalar(prhs[5]))
+            usage = "modelRefit: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), steps (a whole number >= 1)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const mwSize dims[3] = {4, 4, (mwSize)B};
+            mxArray* ot = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+            mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+            mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+            if (B > 0) rc = pcreg_model_refit_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2, (int)mxGetScalar(prhs[5]),
+                                                  mxGetPr(ot), (int32_t*)mxGetData(on), mxGetPr(os), (int32_t*)mxGetData(oe));
+            mxDestroyArray(oe);
+            if (rc == PCREG_OK) {
+                plhs[0] = ot;
+                if (nlhs > 1) plhs[1] = on; else mxDestroyArray(on);
+                if (nlhs > 2) plhs[2] = os; else mxDestroyArray(os);
+            } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); }
         }
     } else if (!strcmp(cmd, "modelCluster")) {                // [label, clOff, members] = pcreg_mex('modelCluster', h, r): clusterPoints(model, r)
         if (nrhs != 3 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2])) usage = "modelCluster: handle (uint64), r (a real scalar >= 0)";

@@ -780,6 +780,32 @@ class Model:
             res.update(idx=idx, dist=dist)
         return res
 
+    def refit_transforms(self, query, T, r2: float, steps: int = 1):
+        """B transforms refitted on their close pairs against the prepared model, `steps` times over (pcreg_model_refit_f32): per
+        step, T_step = estimateTransform(model rows, moved points) over the points of `query` (Q x 3) with a model row within
+        r2 of their transformed place, and T <- T * T_step.  T as score_transforms takes it -> dict(T [B, 4, 4] float64, the
+        refitted transforms, used as quickTF uses them, a zero matrix where there is no fit; empty [B] bool; n_close, sum_d2,
+        fitness, rmse as score_transforms gives them for the transform that went INTO the last step)."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        out = np.zeros((max(B, 1), 16), dtype=np.float64)
+        n_close = np.zeros(max(B, 1), dtype=np.int32)
+        sum_d2 = np.zeros(max(B, 1), dtype=np.float64)
+        empty = np.zeros(max(B, 1), dtype=np.int32)
+        check(lib().pcreg_model_refit_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                          out.ctypes.data, n_close.ctypes.data, sum_d2.ctypes.data, empty.ctypes.data))
+        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0)
+        return res
+
     def cluster(self, r2: float):
         """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,
         members [M] int32), 0-based -- cluster_points' contract."""

@@ -385,6 +385,17 @@ int pcreg_dev_model_score_f32(const pcreg_dev_model* model, const float* q, int 
     GUARD();
     return launch_model_score(model->v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_refit_workspace(int Q, int B, int M) { return refit_ws_bytes(Q, B, M); }
+int pcreg_dev_model_refit_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                              double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* empty, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_ws_bytes(Q, B, 0));                   // (the size does not depend on M)
+    GUARD();
+    return launch_model_refit(model->v, q, Q, ldq, T_dev, B, r2, T_out, T_step, n_close, sum_d2, empty, workspace, workspace_bytes,
+                              (hipStream_t)stream);
+}
 size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -590,6 +601,44 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     if (idx && bq) PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * bq, hipMemcpyDeviceToHost, g_stream));
     if (dist && bq) PCREG_HIP(hipMemcpyAsync(dist, dd, sizeof(float) * bq, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+
+// B transforms refitted `steps` times on their close pairs: upload the queries and the transforms, run the steps on the device,
+// each step's T_out the next one's input (two blocks in turn: a step may not write over its input), and read ONE block back --
+// the last step's [T_out 16 B doubles][sum_d2 B doubles][n_close B int32][empty B int32]
+int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps, double* T_out,
+                          int32_t* n_close, double* sum_d2, int32_t* empty) {
+    PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && empty)));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const ModelView& v = model->dm->v;
+    const size_t wsb = refit_ws_bytes(Q, B, v.M), nB = (size_t)B;
+    float* dq; double *dT, *dout; char* ws;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * nB, &dT));
+    TRY(st.take(2 * (17 * nB + nB), &dout));                               // two result blocks of 18 B doubles' room (17 B and 2 B int32)
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    const double* in = dT;
+    double* blk = dout;
+    for (int s = 0; s < steps; ++s) {
+        blk = dout + (size_t)(s & 1) * 18 * nB;
+        TRY(launch_model_refit(v, dq, Q, Q, in, B, r2, blk, nullptr, (int32_t*)(blk + 17 * nB), blk + 16 * nB, (int32_t*)(blk + 17 * nB) + nB, ws, wsb,
+                               g_stream));
+        in = blk;
+    }
+    std::vector<double> host(18 * nB);
+    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 18 * nB, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
+    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
+    memcpy(n_close, host.data() + 17 * nB, sizeof(int32_t) * nB);
+    memcpy(empty, (const int32_t*)(host.data() + 17 * nB) + nB, sizeof(int32_t) * nB);
     return PCREG_OK;
 }
 

@@ -212,6 +212,16 @@ int launch_query_cells(const ModelView& v, const float* q, int Q, int ldq, int32
 size_t score_ws_bytes(int Q, int B, int M);
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
                        double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
+// the same B transforms each refitted on its close pairs (knn_score.hip): T_step = estimateTransform(model rows, moved
+// points) over the queries with a row within r2, T_out = T * T_step, empty[b] = 1 and zeros where there is no fit; n_close and
+// sum_d2 are launch_model_score's bits.  T_step may be null; T_out may not alias T_dev
+size_t refit_ws_bytes(int Q, int B, int M);
+int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
+                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
+// ... its last step per batch of nb transforms (ransac.hip, where fit_moments and fit_3pt live): chunk moments pmom [nb][chunks][27]
+// about origin[0..2], the batch's per-slot buffers best / tq / win (ld S), n_close [nb] already totalled
+int launch_refit_finish(const double* pmom, const int32_t* n_close, const float* best, const float* tq, const float* win, int Q, int S, int chunks,
+                        int nb, const float* origin, const double* T_in, double* T_out, double* T_step, int32_t* empty, hipStream_t st);
 // connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,

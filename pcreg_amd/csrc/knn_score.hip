@@ -15,10 +15,17 @@
 //   C4  score_reduce_kernel           per (transform, chunk of 2048 queries): count and sum in query order, a fixed tree
 //       score_total_kernel            per transform: its chunks in ascending order
 // sum_d2 is a function of the inputs alone: no floating-point atomic, and no term's place depends on the batch or the walk.
+//
+// The refit (pcreg_model_refit_f32's contract) is the same chain with the walk's other instantiation, which also
+// keeps the winning row's coordinates per slot, and two more steps per batch:
+//   C5  refit_moments_kernel          per (transform, chunk of 2048 queries): the 27 moments of (model row, moved point) over the
+//                                     chunk's hits in query order, shifted by the middle of the model's box; a fixed tree
+//   C6  launch_refit_finish           per transform (ransac.hip): the chunks ascending, fit_moments / fit_3pt, T * T_step
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
 #include "chunk_scan.hpp"
+#include "moments.hpp"
 #include <climits>
 #include <cmath>
 
@@ -54,11 +61,14 @@ __global__ __launch_bounds__(kBlock) void score_transform_kernel(const float* __
 // box: every row of a skipped tile has a computed d > r2 for every query of the block, so it holds no answer.  A lane admits
 // d <= bnd, bnd = r2 until its first hit and its best d afterwards (still inclusive: an equal d with a lower row must win).
 // best[slot's query] = the d of a hit, NaN for a miss (a hit's d is never NaN; with r2 = +inf it may be +inf).
+// XYZ (the refit): the lane holds the row's float4 when it wins, so the winner's coordinates travel with (d, row) through the
+// lane's updates and the two shuffles into win [3][Q] -- no gather through the inverse of perm afterwards.  A miss's are 0.
+template <bool XYZ>
 __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restrict__ q, int Q, const int32_t* __restrict__ qperm,
                                                             const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
                                                             const float* __restrict__ tbox, int n_tiles, int cull, float r2,
                                                             float* __restrict__ best, int32_t* __restrict__ idx, float* __restrict__ dist,
-                                                            unsigned long long* __restrict__ stats) {
+                                                            float* __restrict__ win, unsigned long long* __restrict__ stats) {
     __shared__ WalkLds lds;
     __shared__ float s_red[kBlock / 64][6];
     __shared__ float s_box[6];
@@ -76,6 +86,7 @@ __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restr
     const float qx = q[qi], qy = q[qi + (size_t)Q], qz = q[qi + 2 * (size_t)Q];
     float bnd = live ? r2 : -1.0f;                                // (a dead lane admits nothing: d is never negative)
     float bd = INFINITY; int br = INT_MAX;                        // the lane's best; br == INT_MAX: none yet
+    float bx = 0.0f, by = 0.0f, bz = 0.0f;                        // XYZ: its coordinates
     walk_tiles(
         lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
         [&](int ct) {
@@ -88,7 +99,10 @@ __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restr
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int row = __float_as_int(p[u].w);
-                    if (d[u] <= bnd && (d[u] < bd || row < br)) { bd = d[u]; br = row; bnd = bd; }
+                    if (d[u] <= bnd && (d[u] < bd || row < br)) {
+                        bd = d[u]; br = row; bnd = bd;
+                        if constexpr (XYZ) { bx = p[u].x; by = p[u].y; bz = p[u].z; }
+                    }
                 }
             }
         },
@@ -97,6 +111,10 @@ __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restr
     for (int o = 1; o < kWalkLanes; o <<= 1) {
         const float od = __shfl_xor(bd, o);
         const int orow = __shfl_xor(br, o);
+        if constexpr (XYZ) {
+            const float ox = __shfl_xor(bx, o), oy = __shfl_xor(by, o), oz = __shfl_xor(bz, o);
+            if (od < bd || (od == bd && orow < br)) { bx = ox; by = oy; bz = oz; }
+        }
         if (od < bd || (od == bd && orow < br)) { bd = od; br = orow; }
     }
     if (live && sub == 0) {
@@ -104,6 +122,7 @@ __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restr
         best[qi] = hit ? bd : __int_as_float(0x7FC00000);
         if (idx) idx[qi] = hit ? br : -1;
         if (dist) dist[qi] = hit ? bd : INFINITY;
+        if constexpr (XYZ) { win[qi] = bx; win[qi + (size_t)Q] = by; win[qi + 2 * (size_t)Q] = bz; }
     }
 }
 
@@ -144,6 +163,52 @@ __global__ __launch_bounds__(kBlock) void score_total_kernel(const double* __res
     sum_d2[bl] = sum;
 }
 
+// ---- C5. the refit's moments --------------------------------------------------------------------------------------------
+// workgroup bl * chunks + c, as score_reduce_kernel: thread t adds the hits among its kScanPer consecutive queries in query order
+// into mom_accumulate's 27 sums (moments.hpp) of p = (model row, moved point), both widened to double; then wave_sum27's tree in
+// each wave and the four waves in ascending order.  The shifted sums are taken about ONE origin for both sides, the same for
+// every chunk, batch and call on a model: the middle of the model's box (Prep::cx, cy, cz), which the moved points lie around
+// when the transform is any good.  (The shift only keeps digits; fit_moments adds it back.)
+__global__ __launch_bounds__(kBlock) void refit_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
+                                                               int Q, int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ pmom) {
+    __shared__ double s_m[kBlock / 64][27];
+    const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
+    const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
+    const double ox = (double)prep->cx, oy = (double)prep->cy, oz = (double)prep->cz;
+    const double o[6] = {ox, oy, oz, ox, oy, oz};
+    double acc[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        if (i0 + u < Q) {
+            const size_t s = (size_t)bl * Q + i0 + u;
+            const float d = best[s];
+            if (d == d) {
+                const double p[6] = {(double)win[s], (double)win[s + (size_t)S], (double)win[s + 2 * (size_t)S],
+                                     (double)tq[s],  (double)tq[s + (size_t)S],  (double)tq[s + 2 * (size_t)S]};
+                mom_accumulate(acc, p, o);
+            }
+        }
+    }
+    wave_sum27(acc);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 27) {
+        const int k = threadIdx.x;
+        pmom[(size_t)blockIdx.x * 27 + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
+    }
+}
+// a call without pairs (Q = 0 or a model without rows): every transform is empty
+__global__ __launch_bounds__(kBlock) void refit_empty_kernel(int B, double* __restrict__ T_out, double* __restrict__ T_step, int32_t* __restrict__ empty) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < 16 * B) { T_out[i] = 0.0; if (T_step) T_step[i] = 0.0; }
+    if (i < B) empty[i] = 1;
+}
+
 // whole transforms per batch under a cap of `slots` query slots (at least one: Q <= kScoreMaxSlots)
 int score_batch(int Q, int B, int slots) {
     const int per = slots / (Q > 0 ? Q : 1);
@@ -155,8 +220,9 @@ int score_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk);
 // max(Q, 1)))) transforms: [per-parent-cell counters] [transformed queries, 3 S] [slot -> query, S] [best d per slot, S]
 // [chunk sums, P] [chunk counts, P]:
 // 131 328 + roundup(12 S, 256) + 2 roundup(4 S, 256) + roundup(8 P, 256) + roundup(4 P, 256) bytes
-struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; };
-ScoreWs score_ws_layout(int Q, int B, void* base, size_t* bytes) {
+// The refit's is that followed by [winning rows' coordinates, 3 S] [chunk moments, 27 P]: + roundup(12 S, 256) + roundup(216 P, 256)
+struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; };
+ScoreWs score_ws_layout(int Q, int B, bool refit, void* base, size_t* bytes) {
     ScoreWs s{};
     const int nb = score_batch(Q, B, kScoreMaxSlots);
     const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * score_chunks(Q);
@@ -167,25 +233,24 @@ ScoreWs score_ws_layout(int Q, int B, void* base, size_t* bytes) {
     s.best = w.take<float>(S);
     s.psum = w.take<double>(P);
     s.pcnt = w.take<int32_t>(P);
+    if (refit) {
+        s.win = w.take<float>(3 * S);
+        s.pmom = w.take<double>(27 * P);
+    }
     *bytes = w.bytes();
     return s;
 }
 
-}  // namespace
+// what the refit adds to a scoring call: the outputs per transform (T_step may be null)
+struct RefitOut { double* T_out; double* T_step; int32_t* empty; };
 
-size_t score_ws_bytes(int Q, int B, int M) {
-    (void)M;                                       // O(min(B Q, 4 Mi)) bytes, whatever M, r2 and the result
-    if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
-    size_t b; (void)score_ws_layout(Q, B, nullptr, &b);
-    return b;
-}
-
-int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
-                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
+// the chain of either call; `refit` null: scoring
+int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close, double* sum_d2,
+                int32_t* idx, float* dist, const RefitOut* refit, void* ws, size_t ws_bytes, hipStream_t st) {
     PCREG_ARG(Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxSlots && r2 >= 0.0f);
     size_t need;
-    const ScoreWs s = score_ws_layout(Q, B, ws, &need);
-    if (ws_bytes < need) { set_error("bad argument: score workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_ARG; }
+    const ScoreWs s = score_ws_layout(Q, B, refit != nullptr, ws, &need);
+    if (ws_bytes < need) { set_error("bad argument: %s workspace too small: %zu < %zu", refit ? "refit" : "score", ws_bytes, need); return PCREG_E_ARG; }
     if (B == 0) return PCREG_OK;
     if (Q == 0 || v.M == 0) {                                     // every query misses
         PCREG_HIP(hipMemsetAsync(n_close, 0, sizeof(int32_t) * (size_t)B, st));
@@ -193,6 +258,11 @@ int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const
         const size_t n = (size_t)B * Q;
         if (n > 0 && (idx || dist)) {
             hipLaunchKernelGGL(score_miss_kernel, dim3((unsigned)std::min((n + kBlock - 1) / kBlock, (size_t)4096)), dim3(kBlock), 0, st, n, idx, dist);
+            PCREG_HIP(hipGetLastError());
+        }
+        if (refit) {
+            hipLaunchKernelGGL(refit_empty_kernel, dim3((unsigned)((16 * (size_t)B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, B, refit->T_out, refit->T_step,
+                               refit->empty);
             PCREG_HIP(hipGetLastError());
         }
         return PCREG_OK;
@@ -208,15 +278,55 @@ int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const
         int rc = launch_query_cells(v, s.tq, S, S, s.qcnt, st);
         if (!rc) rc = launch_query_order(v, s.tq, S, S, s.qcnt, s.qperm, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(score_walk_kernel, dim3((unsigned)(((S + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock)), dim3(kBlock), 0, st,
-                           (const float*)s.tq, S, (const int32_t*)s.qperm, (const float*)v.ms, (const int32_t*)v.perm, v.M, (const float*)v.tbox,
-                           n_tiles, cull, r2, s.best, idx ? idx + at : nullptr, dist ? dist + at : nullptr, knn_stats_dev());
+        const dim3 walk_grid((unsigned)(((S + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock));
+        if (refit)
+            hipLaunchKernelGGL(score_walk_kernel<true>, walk_grid, dim3(kBlock), 0, st, (const float*)s.tq, S, (const int32_t*)s.qperm, (const float*)v.ms,
+                               (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, r2, s.best, idx ? idx + at : nullptr,
+                               dist ? dist + at : nullptr, s.win, knn_stats_dev());
+        else
+            hipLaunchKernelGGL(score_walk_kernel<false>, walk_grid, dim3(kBlock), 0, st, (const float*)s.tq, S, (const int32_t*)s.qperm, (const float*)v.ms,
+                               (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, r2, s.best, idx ? idx + at : nullptr,
+                               dist ? dist + at : nullptr, (float*)nullptr, knn_stats_dev());
         hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, Q, chunks, s.psum, s.pcnt);
         hipLaunchKernelGGL(score_total_kernel, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, nb,
                            chunks, n_close + b0, sum_d2 + b0);
+        if (refit) {
+            hipLaunchKernelGGL(refit_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
+                               (const float*)s.win, Q, S, chunks, (const Prep*)v.prep, s.pmom);
+            PCREG_HIP(hipGetLastError());
+            rc = launch_refit_finish(s.pmom, n_close + b0, s.best, s.tq, s.win, Q, S, chunks, nb, &((const Prep*)v.prep)->cx, T_dev + (size_t)b0 * 16,
+                                     refit->T_out + (size_t)b0 * 16, refit->T_step ? refit->T_step + (size_t)b0 * 16 : nullptr, refit->empty + b0, st);
+            if (rc) return rc;
+        }
         PCREG_HIP(hipGetLastError());
     }
     return PCREG_OK;
+}
+
+}  // namespace
+
+size_t score_ws_bytes(int Q, int B, int M) {
+    (void)M;                                       // O(min(B Q, 4 Mi)) bytes, whatever M, r2 and the result
+    if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
+    size_t b; (void)score_ws_layout(Q, B, false, nullptr, &b);
+    return b;
+}
+size_t refit_ws_bytes(int Q, int B, int M) {
+    (void)M;
+    if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
+    size_t b; (void)score_ws_layout(Q, B, true, nullptr, &b);
+    return b;
+}
+
+int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
+                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, ws, ws_bytes, st);
+}
+
+int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
+                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
+    const RefitOut out{T_out, T_step, empty};
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, ws, ws_bytes, st);
 }
 
 }  // namespace pcreg

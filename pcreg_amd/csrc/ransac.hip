@@ -19,6 +19,7 @@
 //     moments per passing hypothesis followed by a second lane-parallel SVD.
 // No data leaves the chip between the sample fit and the final inlier list.
 #include "common.hpp"
+#include "moments.hpp"
 #include <cfloat>
 #include <cstddef>
 #include <cstdio>
@@ -47,46 +48,7 @@ struct RansacArgs {
     double* msc;                // ransac_hyp32_kernel: [B*iters][16] the fifteen refit sums of a hypothesis
 };
 
-// ---------------------------------------------------------------- lane utilities
-__device__ __forceinline__ double rdlane(double v, int l) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// wave_sum of 27 values at once, the same bits as 27 calls.  wave_sum's butterfly adds lane l and lane l ^ o for o = 32, 16, ..., 1;
-// after every step the two partners hold the same bits (fp addition commutes), so only ONE of them needs to go on with a given
-// value: at distance 32 the lower half-wave keeps values 0-13 and the upper one 14-26, each sending the other its remaining
-// half, and so on down -- 14 + 7 + 4 + 2 + 1 + 1 = 29 exchanged doubles instead of 27 x 6 = 162.  Value k ends in the lanes whose
-// bits 5..1 spell its path (k = 14 b5 + 7 b4 + 4 b3 + 2 b2 + b1) and is broadcast from there with v_readlane.
-__device__ __forceinline__ void wave_sum27(double (&v)[27]) {
-    const int lane = threadIdx.x & 63;
-    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
-    double k1[14], k2[8], k3[4], k4[2];
-#pragma unroll
-    for (int j = 0; j < 14; ++j) {
-        const double hi = 14 + j < 27 ? v[14 + j < 27 ? 14 + j : 26] : 0.0;
-        k1[j] = (b5 ? hi : v[j]) + __shfl_xor(b5 ? v[j] : hi, 32);
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) k2[j] = (b4 ? k1[7 + j] : k1[j]) + __shfl_xor(b4 ? k1[j] : k1[7 + j], 16);
-    k2[7] = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k3[j] = (b3 ? k2[4 + j] : k2[j]) + __shfl_xor(b3 ? k2[j] : k2[4 + j], 8);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) k4[j] = (b2 ? k3[2 + j] : k3[j]) + __shfl_xor(b2 ? k3[j] : k3[2 + j], 4);
-    double k5 = (b1 ? k4[1] : k4[0]) + __shfl_xor(b1 ? k4[0] : k4[1], 2);
-    k5 += __shfl_xor(k5, 1);
-#pragma unroll
-    for (int k = 0; k < 27; ++k) {
-        const int c5 = k >= 14, r5 = k - 14 * c5, c4 = r5 >= 7, r4 = r5 - 7 * c4, c3 = r4 >= 4, r3 = r4 - 4 * c3, c2 = r3 >= 2, c1 = r3 - 2 * c2;
-        v[k] = rdlane(k5, 32 * c5 + 16 * c4 + 8 * c3 + 4 * c2 + 2 * c1);
-    }
-}
+// ---------------------------------------------------------------- lane utilities (rdlane, wave_sum, wave_sum27: moments.hpp)
 __device__ __forceinline__ double ulp_at(double x) {   // MATLAB eps(x)
     x = fabs(x);
     return __longlong_as_double(__double_as_longlong(x) + 1) - x;
@@ -395,32 +357,6 @@ __device__ bool fit_3pt(const double (&A1)[3][3], const double (&A2)[3][3], doub
             H[i][j] = acc;
         }
     return polar_to_T(H, cd, cm, T);
-}
-
-// Moments of a correspondence set, taken about a fixed origin (o1,o2) inside the data (ransac_origin) so that the
-// centring of estimateTransform.m:55-58 does not cancel digits:
-//   mom[0..2]  = sum(d')      mom[3..5] = sum(m')            (d' = p1-o1, m' = p2-o2)
-//   mom[6..14] = sum(m'_i d'_j), row-major i,j
-//   mom[15..20]= raw Gram of p1 (xx,xy,xz,yy,yz,zz), mom[21..26] = raw Gram of p2.
-__device__ __forceinline__ void mom_core(double (&mom)[27], const double (&p)[6], const double (&o)[6]) {
-    double d0 = p[0] - o[0], d1 = p[1] - o[1], d2 = p[2] - o[2];
-    double m0 = p[3] - o[3], m1 = p[4] - o[4], m2 = p[5] - o[5];
-    mom[0] += d0; mom[1] += d1; mom[2] += d2; mom[3] += m0; mom[4] += m1; mom[5] += m2;
-    mom[6]  = fma(m0, d0, mom[6]);  mom[7]  = fma(m0, d1, mom[7]);  mom[8]  = fma(m0, d2, mom[8]);
-    mom[9]  = fma(m1, d0, mom[9]);  mom[10] = fma(m1, d1, mom[10]); mom[11] = fma(m1, d2, mom[11]);
-    mom[12] = fma(m2, d0, mom[12]); mom[13] = fma(m2, d1, mom[13]); mom[14] = fma(m2, d2, mom[14]);
-}
-// the raw Grams only feed the rank test of estimateTransform.m:11-14
-__device__ __forceinline__ void mom_gram(double (&mom)[27], const double (&p)[6]) {
-    mom[15] = fma(p[0], p[0], mom[15]); mom[16] = fma(p[0], p[1], mom[16]); mom[17] = fma(p[0], p[2], mom[17]);
-    mom[18] = fma(p[1], p[1], mom[18]); mom[19] = fma(p[1], p[2], mom[19]); mom[20] = fma(p[2], p[2], mom[20]);
-    mom[21] = fma(p[3], p[3], mom[21]); mom[22] = fma(p[3], p[4], mom[22]); mom[23] = fma(p[3], p[5], mom[23]);
-    mom[24] = fma(p[4], p[4], mom[24]); mom[25] = fma(p[4], p[5], mom[25]); mom[26] = fma(p[5], p[5], mom[26]);
-}
-__device__ __forceinline__ void mom_accumulate(double (&mom)[27], const double (&p)[6],
-                                               const double (&o)[6]) {
-    mom_core(mom, p, o);
-    mom_gram(mom, p);
 }
 
 // The same decision with the eigenvectors of the two smaller singular values and a flag: a singular value below ~1e-7
@@ -3246,6 +3182,81 @@ __global__ __launch_bounds__(64) void estimate_transform_indexed_kernel(const do
     if (threadIdx.x == 0) { info[0] = cnt; info[1] = ok ? 0 : 1; }
 }
 
+// The refit of a candidate transform on its close dense pairs (knn_score.hip), its last step: one wave per transform
+// bl of the batch.  pts1 = the winning model rows, pts2 = the moved points, over the slots with a hit (best == best) in query
+// order.  cnt > 3: the chunks' moments added in ascending order, fit_moments about the origin they were taken about (origin[0..2],
+// both sides).  cnt == 3: the three pairs collected from the per-slot buffers in query order, fit_3pt.  T_step in T16's layout;
+// T_out = T_in * T_step, every entry ((T(r,0) S(0,c) + T(r,1) S(1,c)) + T(r,2) S(2,c)) + T(r,3) S(3,c) (no contraction: the build's
+// flag).  A failed fit, cnt < 3 or an all-zero T_in: empty = 1 and 32 zeros.
+__global__ __launch_bounds__(64) void refit_finish_kernel(const double* __restrict__ pmom, const int32_t* __restrict__ n_close, const float* __restrict__ best,
+                                                          const float* __restrict__ tq, const float* __restrict__ win, int Q, int S, int chunks,
+                                                          const float* __restrict__ origin, const double* __restrict__ T_in, double* __restrict__ T_out,
+                                                          double* __restrict__ T_step, int32_t* __restrict__ empty) {
+    __shared__ double s3[18], s_S[16];
+    const int bl = blockIdx.x, lane = threadIdx.x;
+    const int cnt = n_close[bl];
+    double T[12]; bool ok = false;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = 0.0;
+    bool in_empty = true;
+    for (int e = 0; e < 16; ++e) in_empty = in_empty && T_in[(size_t)bl * 16 + e] == 0.0;
+    if (cnt == 3) {
+        int got = 0;
+        for (int i0 = 0; i0 < Q && got < 3; i0 += 64) {
+            const int i = i0 + lane;
+            const size_t s = (size_t)bl * Q + (i < Q ? i : 0);
+            const float d = best[s];
+            const bool in = i < Q && d == d;
+            const unsigned long long bal = __ballot(in);
+            const int r3 = got + __popcll(bal & ((1ull << lane) - 1ull));
+            if (in && r3 < 3) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { s3[r3 * 6 + c] = (double)win[s + (size_t)c * S]; s3[r3 * 6 + 3 + c] = (double)tq[s + (size_t)c * S]; }
+            }
+            got += __popcll(bal);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        double A1[3][3], A2[3][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { A1[j][c] = s3[j * 6 + c]; A2[j][c] = s3[j * 6 + 3 + c]; }
+        ok = fit_3pt(A1, A2, T);
+    } else if (cnt > 3) {
+        double mom[27];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) mom[k] = 0.0;
+        for (int c = 0; c < chunks; ++c) {
+#pragma unroll
+            for (int k = 0; k < 27; ++k) mom[k] += pmom[((size_t)bl * chunks + c) * 27 + k];
+        }
+        const double ox = (double)origin[0], oy = (double)origin[1], oz = (double)origin[2];
+        const double o[6] = {ox, oy, oz, ox, oy, oz};
+        ok = fit_moments(cnt, mom, o, T);
+    }
+    ok = ok && !in_empty;
+    if (lane < 16) {
+        const int k = lane & 3, j = lane >> 2;
+        double v = 0.0;
+        if (ok) {
+            double tv = 0.0;
+#pragma unroll
+            for (int e = 0; e < 12; ++e) if (e == j * 4 + k) tv = T[e];
+            v = (j < 3) ? tv : (k == 3 ? 1.0 : 0.0);
+        }
+        s_S[k + 4 * j] = v;
+        if (T_step) T_step[(size_t)bl * 16 + k + 4 * j] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    if (lane < 16) {
+        const int r = lane & 3, c = lane >> 2;
+        const double* Ti = T_in + (size_t)bl * 16;
+        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
+        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
+    }
+    if (lane == 0) empty[bl] = ok ? 0 : 1;
+}
+
 __global__ void calc_dists_kernel(const double* T16, const double* p1, const double* p2, int n, int ld, double* d) {
     double T[12];
 #pragma unroll
@@ -3547,6 +3558,14 @@ int launch_refine_by_distance(const double* p1, const double* p2, const int32_t*
 int launch_estimate_transform_indexed(const double* p1, const double* p2, int ld, const int32_t* idx, int32_t idx_base, const int32_t* n_idx_dev,
                                       int cap, double* T16_dev, int32_t* info_dev, hipStream_t st) {
     hipLaunchKernelGGL(estimate_transform_indexed_kernel, dim3(1), dim3(64), 0, st, p1, p2, ld, idx, (int)idx_base, n_idx_dev, cap, T16_dev, info_dev);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+int launch_refit_finish(const double* pmom, const int32_t* n_close, const float* best, const float* tq, const float* win, int Q, int S, int chunks,
+                        int nb, const float* origin, const double* T_in, double* T_out, double* T_step, int32_t* empty, hipStream_t st) {
+    if (nb <= 0) return PCREG_OK;
+    hipLaunchKernelGGL(refit_finish_kernel, dim3(nb), dim3(64), 0, st, pmom, n_close, best, tq, win, Q, S, chunks, origin, T_in, T_out, T_step, empty);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
