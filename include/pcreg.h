@@ -252,6 +252,34 @@ int pcreg_model_cluster_f32(pcreg_model* model, float r2, int32_t* label, int32_
 /* The same without a handle (clusterPoints(m, r)): uploads and prepares the cloud for this call only. */
 int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off,
                              int32_t* members);
+/* The surface normal of every row of the model from its k nearest rows (MATLAB's pcnormals(ptCloud, k); the third PCA axis
+ * AlignPoints_KNN.m:29-34 takes of a neighbourhood).  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- a prepared model of M rows; k with 3 <= k <= PCREG_KNN_MAX_K; a viewpoint of three doubles on the host, or NULL.
+ * THE NEIGHBOURHOOD of row i is what pcreg_model_knn_f32 returns for query = row i and the same k: the k model rows with the
+ * smallest fp32 fmaf(dz,dz,fmaf(dy,dy,dx*dx)), ordered by (distance, original row), ties to the lowest row; row i itself is in
+ * it at distance 0.  A row with a non-finite coordinate is never a neighbour (nor is a row whose computed distance overflows to
+ * +inf), and its own neighbourhood is empty.  n <= k is the number of neighbours found; n < k only when the model has fewer than
+ * k finite rows.
+ * THE ARITHMETIC is double throughout, on the widened fp32 coordinates, without contraction, the neighbours taken in (distance,
+ * row) order: (1) the mean, each coordinate summed in that order and divided by n; (2) the six sums xx, xy, xz, yy, yz, zz of
+ * the products of the centred coordinates, in that order, NOT divided by n; (3) the library's cyclic Jacobi on that symmetric
+ * matrix (jacobi_sym3, as it is); (4) the eigenvector column of the smallest of the three diagonal entries, ties to the lowest
+ * index; (5) each component rounded once to fp32, not renormalised.
+ * THE SIGN is decided on the rounded components, widened again.  With a viewpoint v and p the row:
+ * s = ((nx*(vx-px) + ny*(vy-py)) + nz*(vz-pz)) in double, and the normal is negated iff s < 0.  Without one: the component of
+ * largest magnitude, the first of equals in x, y, z order, is made non-negative.  Negation is exact, so the two forms differ by
+ * sign only, bit for bit.
+ * variation[i] (may be NULL) = lambda_min / ((lambda_0 + lambda_1) + lambda_2) of the diagonal Jacobi leaves, rounded to fp32:
+ * the surface variation by which a caller judges a normal.
+ * Normal and variation are NaN when n < 3 (so for a non-finite row) and when the trace is not positive (coincident neighbours).
+ * A collinear neighbourhood gets whatever Jacobi gives: deterministic, judged by the caller through the variation.
+ * normals: M x 3 fp32 column-major with leading dimension ldn >= M, indexed by ORIGINAL row; variation [M].  M = 0 writes nothing.
+ * The result is a function of (model rows, k, viewpoint) only: no floating-point atomic; culling, the call and the stream change
+ * no bit.  PCREG_E_ARG: k outside 3 .. PCREG_KNN_MAX_K, ldn < M. */
+int pcreg_model_normals_f32(pcreg_model* model, int k, const double* viewpoint /* host, 3 or NULL */, float* normals, int ldn,
+                            float* variation /* or NULL */);
+/* The same without a handle (pcnormals(m, k)): uploads and prepares the cloud for this call only. */
+int pcreg_point_normals_f32(const float* m, int M, int ldm, int k, const double* viewpoint, float* normals, int ldn, float* variation);
 
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
@@ -550,6 +578,15 @@ int pcreg_dev_model_refit_f32(const pcreg_dev_model* model, const float* q, int 
 size_t pcreg_dev_model_cluster_workspace(int M);
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first,
                                 int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_normals_f32's contract on the device: normals [3 * ldn] and variation [M] (or NULL) are device
+ * pointers, the viewpoint stays on the host (it travels as kernel arguments).  Two launches: the seed bound of every sorted row,
+ * then one walk in which a workgroup owns 64 rows of a tile, keeps their k-lists in registers and finishes each row's normal
+ * itself; tiles are skipped by DESIGN 4.1's rule with the k-th-neighbour bound.  The queries are the model's own sorted copy, so
+ * any M a model can hold is served in one call.  Nothing synchronises; no workgroup waits for another.  Workspace: the seed bounds,
+ * roundup(4 * max(M, 1), 256) bytes, whatever k.  A handle may serve several streams at once, each call with its own workspace. */
+size_t pcreg_dev_model_normals_workspace(int M, int k);
+int pcreg_dev_model_normals_f32(const pcreg_dev_model* model, int k, const double* viewpoint /* host, 3 or NULL */, float* normals,
+                                int ldn, float* variation /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

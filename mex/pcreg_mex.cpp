@@ -30,6 +30,13 @@
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
 //                                          "distance <= r", numbered by their smallest row (clusterPoints.m:16-45;
 //                                          matlab/clusterPointsModel.m, matlab/clusterPointsFast.m)
+//   'modelNormals', handle, k, viewpoint | 'pointNormals', pts (single M x 3), k, viewpoint -> normals (M x 3 single), variation
+//                                          (M x 1 single): the normal of every row from its k nearest rows (3 <= k <= 32, the row
+//                                          itself among them), the eigenvector of the smallest eigenvalue of their scatter in
+//                                          double; viewpoint [] (the component of largest magnitude is made non-negative) or a
+//                                          double 1 x 3 the normals point towards, always passed; variation = lambda_min / the
+//                                          sum of the three eigenvalues, built only when asked for; NaN rows where there is no
+//                                          normal (matlab/pcnormalsModel.m, matlab/pcnormalsFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -100,6 +107,27 @@ static int cluster_on_handle(pcreg_model* h, float r, mxArray* out[3]) {
         memcpy(mxGetData(out[1]), off, ((size_t)nc + 1) * sizeof(int32_t));
     } else { mxDestroyArray(ol); mxDestroyArray(om); }
     mxDestroyArray(bo);
+    return rc;
+}
+
+// k and viewpoint of the normals commands: a real double scalar, whole, 3 .. PCREG_KNN_MAX_K; [] or three doubles
+static bool normals_k_ok(const mxArray* a) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 3.0 && mxGetScalar(a) <= (double)PCREG_KNN_MAX_K &&
+           mxGetScalar(a) == (double)(int)mxGetScalar(a);
+}
+static bool viewpoint_ok(const mxArray* a) { return mxIsEmpty(a) || (mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 3); }
+// the outputs of 'modelNormals' / 'pointNormals': normals (M x 3 single) and, with want_var, variation (M x 1 single).  Nothing is
+// left allocated on an error.
+static int normals_on_handle(pcreg_model* h, int k, const mxArray* vp, bool want_var, mxArray* out[2]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    mxArray* on = mxCreateNumericMatrix((size_t)M, 3, mxSINGLE_CLASS, mxREAL);
+    mxArray* ov = want_var ? mxCreateNumericMatrix((size_t)M, 1, mxSINGLE_CLASS, mxREAL) : nullptr;
+    rc = pcreg_model_normals_f32(h, k, mxIsEmpty(vp) ? nullptr : mxGetPr(vp), (float*)mxGetData(on), M > 0 ? M : 1,
+                                 ov ? (float*)mxGetData(ov) : nullptr);
+    if (rc == PCREG_OK) { out[0] = on; out[1] = ov; }
+    else { mxDestroyArray(on); if (ov) mxDestroyArray(ov); }
     return rc;
 }
 
@@ -571,6 +599,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = cluster_on_handle(h, (float)mxGetScalar(prhs[2]), out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "modelNormals")) {                // [normals, variation] = pcreg_mex('modelNormals', h, k, viewpoint)
+        if (nrhs != 4 || !mxIsUint64(prhs[1]) || !normals_k_ok(prhs[2]) || !viewpoint_ok(prhs[3]))
+            usage = "modelNormals: handle (uint64), k (a whole number 3 .. 32), viewpoint ([] or double 1 x 3)";
+        else {
+            mxArray* out[2] = {nullptr, nullptr};
+            rc = normals_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (int)mxGetScalar(prhs[2]), prhs[3], nlhs > 1, out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
+        }
+    } else if (!strcmp(cmd, "pointNormals")) {                // [normals, variation] = pcreg_mex('pointNormals', single(pts), k, viewpoint)
+        if (nrhs != 4 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !normals_k_ok(prhs[2]) || !viewpoint_ok(prhs[3]))
+            usage = "pointNormals: pts (single M x 3), k (a whole number 3 .. 32), viewpoint ([] or double 1 x 3)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[2] = {nullptr, nullptr};
+            if (rc == PCREG_OK) rc = normals_on_handle(h, (int)mxGetScalar(prhs[2]), prhs[3], nlhs > 1, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
         }
     } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)
         if (nrhs != 2 || !mxIsDouble(prhs[1]) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1]))) usage = "uniqueRows3: A (double n x 3)";

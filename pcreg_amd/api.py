@@ -656,6 +656,38 @@ def cluster_points(pts, r2: float):
     return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_cluster_points_f32(m.ctypes.data, M, max(M, 1), r2, lab, nc, off, mem)), M)
 
 
+def _normals_args(k, viewpoint):
+    k = int(k)
+    if not 3 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must lie in [3, {KNN_MAX_K}], got {k}")
+    vp = None
+    if viewpoint is not None:
+        vp = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float64).ravel())
+        if vp.shape != (3,):
+            raise ValueError("viewpoint is three numbers or None")
+    return k, vp
+
+
+def _normals_call(call, M: int, vp, variation: bool):
+    nrm = np.zeros((max(M, 1), 3), dtype=np.float32, order="F")
+    var = np.zeros(max(M, 1), dtype=np.float32) if variation else None
+    call(vp.ctypes.data if vp is not None else None, nrm.ctypes.data, max(M, 1), var.ctypes.data if variation else None)
+    return (nrm[:M], var[:M]) if variation else nrm[:M]
+
+
+def point_normals(pts, k: int, viewpoint=None, variation: bool = False):
+    """pcnormals(pts, k) in this library's rule (pcreg_model_normals_f32's contract): the normal of every row [M, 3] float32,
+    the eigenvector of the smallest eigenvalue of the scatter of the row's k nearest rows (3 <= k <= 32, the row itself among
+    them), taken in double.  viewpoint (three numbers): the normal points towards it; None: its component of largest magnitude
+    is non-negative.  variation=True also returns lambda_min / (lambda_0 + lambda_1 + lambda_2) [M] float32.  NaN for a
+    non-finite row, fewer than three finite rows, coincident neighbours.  The cloud is prepared for this call only: keep a Model
+    for repeated calls."""
+    k, vp = _normals_args(k, viewpoint)
+    m = _fcol(pts, np.float32)
+    M = m.shape[0]
+    return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_point_normals_f32(m.ctypes.data, M, max(M, 1), k, v, n, ldn, va)), M, vp, variation)
+
+
 def unique_rows(A):
     """[C, ia] = unique(A, 'rows') for an n x 3 float64 array: (C [u, 3], ia [u] int32, 0-based).  Rows in lexicographic order by
     column 1, 2, 3 as numbers (-0 == +0); the first occurrence represents its run and C = A[ia] carries its bits.  A NaN anywhere
@@ -813,6 +845,14 @@ class Model:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
         return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_model_cluster_f32(self._h, r2, lab, nc, off, mem)), self.M)
+
+    def normals(self, k: int, viewpoint=None, variation: bool = False):
+        """The surface normal of every row of the prepared model from its k nearest rows: normals [M, 3] float32, and with
+        variation=True also the surface variation [M] float32 -- point_normals' contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        k, vp = _normals_args(k, viewpoint)
+        return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_model_normals_f32(self._h, k, v, n, ldn, va)), self.M, vp, variation)
 
     def close(self):
         if self._h.value:

@@ -403,6 +403,13 @@ int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t*
     GUARD();
     return launch_model_cluster(model->v, r2, label, n_clusters, first, sizes, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_normals_workspace(int M, int k) { return normals_ws_bytes(M, k); }
+int pcreg_dev_model_normals_f32(const pcreg_dev_model* model, int k, const double* viewpoint, float* normals, int ldn, float* variation,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && k >= 3 && k <= kKnnMaxK && ldn >= model->v.M && (normals || model->v.M == 0));
+    GUARD();
+    return launch_model_normals(model->v, k, viewpoint, normals, ldn, variation, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -686,6 +693,43 @@ int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* 
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return cluster_on_view(st, v, r2, label, n_clusters, cl_off, members);
+}
+
+// normals of a prepared model's own rows: compute on the device (compact, ld = M), read back into the caller's leading dimension
+static int normals_on_view(Stage& st, const ModelView& v, int k, const double* viewpoint, float* normals, int ldn, float* variation) {
+    const int M = v.M;
+    if (M == 0) return PCREG_OK;
+    float *dn, *dv; char* ws;
+    const size_t wsb = normals_ws_bytes(M, k);
+    TRY(st.take(3 * (size_t)M, &dn));
+    TRY(st.take(variation ? (size_t)M : 0, &dv));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_normals(v, k, viewpoint, dn, M, variation ? dv : nullptr, ws, wsb, g_stream));
+    if (ldn == M) PCREG_HIP(hipMemcpyAsync(normals, dn, sizeof(float) * 3 * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    else PCREG_HIP(hipMemcpy2DAsync(normals, sizeof(float) * (size_t)ldn, dn, sizeof(float) * (size_t)M, sizeof(float) * (size_t)M, 3,
+                                    hipMemcpyDeviceToHost, g_stream));
+    if (variation) PCREG_HIP(hipMemcpyAsync(variation, dv, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_normals_f32(pcreg_model* model, int k, const double* viewpoint, float* normals, int ldn, float* variation) {
+    PCREG_ARG(model && k >= 3 && k <= kKnnMaxK && ldn >= model->M && (normals || model->M == 0));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return normals_on_view(st, model->dm->v, k, viewpoint, normals, ldn, variation);
+}
+int pcreg_point_normals_f32(const float* m, int M, int ldm, int k, const double* viewpoint, float* normals, int ldn, float* variation) {
+    PCREG_ARG(M >= 0 && ldm >= M && k >= 3 && k <= kKnnMaxK && ldn >= M && (M == 0 || (m && normals)));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return normals_on_view(st, v, k, viewpoint, normals, ldn, variation);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -226,6 +226,11 @@ int launch_refit_finish(const double* pmom, const int32_t* n_close, const float*
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,
                          size_t ws_bytes, hipStream_t st);
+// the surface normal of every model row from its k nearest rows (knn_normals.hip): normals [3][ldn] and variation [M]
+// (or null) by ORIGINAL row; viewpoint: three host doubles or null
+size_t normals_ws_bytes(int M, int k);
+int launch_model_normals(const ModelView& v, int k, const double* viewpoint, float* normals, int ldn, float* variation, void* ws,
+                         size_t ws_bytes, hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
+#include "knn_klist.hpp"
 #include <cmath>
 
 namespace pcreg {
@@ -27,53 +28,6 @@ namespace {
 constexpr int kKnnMaxK = PCREG_KNN_MAX_K;
 constexpr int kKSeedWin = 64;                        // sorted rows the seed bound looks at (one per lane of a wave)
 static_assert(kKnnMaxK <= kKSeedWin, "the seed window holds at least k rows");
-
-__device__ __forceinline__ bool knn_k_lt(float da, int ia, float db, int ib) {     // (distance, row); -1 (empty) sorts last
-    return da < db || (da == db && (unsigned)ia < (unsigned)ib);
-}
-// sorted insertion by a KB-stage compare-exchange chain (an entry that beats none falls off the end)
-template <int KB>
-__device__ __forceinline__ void klist_insert(float (&ld)[KB], int (&li)[KB], float d, int j) {
-    float x = d; int xi = j;
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-        const bool lt = knn_k_lt(x, xi, ld[s], li[s]);
-        const float lo = lt ? x : ld[s], hi = lt ? ld[s] : x;
-        const int loi = lt ? xi : li[s], hii = lt ? li[s] : xi;
-        ld[s] = lo; li[s] = loi; x = hi; xi = hii;
-    }
-}
-template <int KB>
-__device__ __forceinline__ float klist_kth(const float (&ld)[KB], int k) {
-    float v = ld[0];
-#pragma unroll
-    for (int s = 1; s < KB; ++s) v = s == k - 1 ? ld[s] : v;
-    return v;
-}
-// the KB smallest of two sorted lists (the partner lane's arrives by xor shuffle): c_s = min(a_s, b_{KB-1-s}) is bitonic,
-// a half-cleaner cascade sorts it; both lanes of the pair end with the same list
-template <int KB>
-__device__ __forceinline__ void klist_merge_xor(float (&ld)[KB], int (&li)[KB], int o) {
-    float od[KB]; int oi[KB];
-#pragma unroll
-    for (int s = 0; s < KB; ++s) { od[s] = __shfl_xor(ld[s], o); oi[s] = __shfl_xor(li[s], o); }
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-        if (knn_k_lt(od[KB - 1 - s], oi[KB - 1 - s], ld[s], li[s])) { ld[s] = od[KB - 1 - s]; li[s] = oi[KB - 1 - s]; }
-    }
-#pragma unroll
-    for (int h = KB / 2; h > 0; h >>= 1) {
-#pragma unroll
-        for (int s = 0; s < KB; ++s) {
-            if ((s & h) == 0) {
-                const bool sw = knn_k_lt(ld[s + h], li[s + h], ld[s], li[s]);
-                const float a = sw ? ld[s + h] : ld[s], b = sw ? ld[s] : ld[s + h];
-                const int ia = sw ? li[s + h] : li[s], ib = sw ? li[s] : li[s + h];
-                ld[s] = a; ld[s + h] = b; li[s] = ia; li[s + h] = ib;
-            }
-        }
-    }
-}
 
 // ---- K1. seed bound: one wave per query ----------------------------------------------------------------------------
 // After model_order_scatter_kernel's atomics sort_cnt[c] is the END row of ordering cell c (and the start of c + 1).  The

@@ -240,6 +240,38 @@ class PreparedModel:
             check(lib().pcreg_dev_model_cluster_f32(self.handle, r2, _p(label), _p(n_clusters), _p(first), _p(sizes), _p(ws), ws.numel(), _stream()))
         return label, n_clusters, first, sizes
 
+    def normals(self, k: int, viewpoint=None, variation: bool = False, out=None):
+        """The surface normal of every row of the model from its k nearest rows (3 <= k <= 32), on torch's current stream
+        (pcreg_dev_model_normals_f32; the contract is pcreg_model_normals_f32's): -> normals, a [3, M] float32 tensor (row c the
+        c-th component of every row's normal: column-major M x 3, by ORIGINAL row), and with variation=True (normals, variation
+        [M] float32).  viewpoint: three host numbers, the normals point towards it; None: the component of largest magnitude is
+        non-negative.  NaN for a non-finite row, fewer than three finite rows, coincident neighbours.  Nothing synchronises.  The
+        workspace is cached on the model and grown on demand; calls that may overlap on two streams pass buffers of their own,
+        out=(normals, variation, ws) with ws of pcreg_dev_model_normals_workspace(M, k) bytes (variation None when not wanted)."""
+        k = int(k)
+        if not 3 <= k <= _l.KNN_MAX_K:
+            raise ValueError(f"k must lie in [3, {_l.KNN_MAX_K}], got {k}")
+        vp = None
+        if viewpoint is not None:
+            vp = (C.c_double * 3)(*[float(x) for x in viewpoint])
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_normals_workspace(M, k)), 256)
+        if out is not None:
+            nrm, var, ws = out
+            if nrm.dtype != torch.float32 or nrm.dim() != 2 or nrm.shape[0] != 3 or nrm.shape[1] != M or (M and nrm.stride(1) != 1):
+                raise TypeError("normals are a [3, M] float32 tensor with contiguous rows (the row stride is the leading dimension)")
+        else:
+            nrm = torch.empty((3, M), dtype=torch.float32, device=dev)
+            var = torch.empty(M, dtype=torch.float32, device=dev) if variation else None
+            ws = getattr(self, "_normals_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._normals_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if M:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                check(lib().pcreg_dev_model_normals_f32(self.handle, k, vp, _p(nrm), max(int(nrm.stride(0)), M), _p(var) if var is not None else None,
+                                                        _p(ws), ws.numel(), _stream()))
+        return (nrm, var) if variation else nrm
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             lib().pcreg_dev_model_destroy(self.handle)
