@@ -240,6 +240,65 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
  * the last step (T itself when steps = 1), not T_out.  PCREG_E_ARG: pcreg_model_score_f32's cases, and steps < 1. */
 int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
                           int steps, double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* empty);
+/* Refit B candidate transforms by ONE LINEARISED POINT-TO-PLANE STEP on their close dense pairs (`steps` of them in this entry):
+ * what pcreg_model_refit_f32 does with estimateTransform, done with the planes through the model rows instead, so that a pair may
+ * be the wrong partner ALONG the surface as long as it is nearly the right one ACROSS it.  A step, not an ICP policy: no
+ * convergence test, no weighting, no robust kernel.  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- those of pcreg_model_refit_f32 (a prepared model, Q fp32 points column-major with ldq, B transforms of 16 doubles used
+ * as quickTF.m uses them, a squared radius r2 >= 0, +inf allowed), and NORMALS: M x 3 fp32 column-major with leading dimension
+ * ldn >= M, indexed by ORIGINAL row -- exactly what pcreg_model_normals_f32 and pcreg_dev_model_normals_f32 write.  A normal is
+ * used as it is: not renormalised, no variation threshold.  A row with any non-finite normal component offers no plane (so a
+ * caller drops the rows it distrusts by setting them to NaN).  THE SIGN of a normal cannot matter: every sum below is even in n,
+ * and negating n negates products and sums exactly, so the outputs are the same bits.
+ * THE PAIRS of transform b are exactly scoring's (pcreg_model_score_f32, pcreg_model_refit_f32): query i has a pair when its
+ * TRANSFORMED QUERY p' (double arithmetic without contraction, rounded once to fp32) has a NEAREST ROW WITHIN THE RADIUS (d <= r2
+ * inclusive, ties to the lowest original row, a NaN d never passes).  n_close[b] and sum_d2[b] are THE SAME BITS
+ * pcreg_model_score_f32 returns.  A PLANE PAIR is a pair whose row has three finite normal components; n_plane[b] their number.
+ * PER PLANE PAIR, in double on the widened fp32 values, without contraction except where fma is written; o the origin
+ * pcreg_model_refit_f32 uses (the middle of the model's bounding box as the handle holds it in fp32: 0.5f * lo + 0.5f * hi per coordinate), m the model row, p = p' the
+ * moved point, n the normal:
+ *   e = p - m (by component);  r = (n_x e_x + n_y e_y) + n_z e_z;  u = p - o;
+ *   c = u x n:  c_x = u_y n_z - u_z n_y,  c_y = u_z n_x - u_x n_z,  c_z = u_x n_y - u_y n_x;   J = (c_x, c_y, c_z, n_x, n_y, n_z).
+ * THE 28 SUMS, each acc = fma(a, b, acc) over the plane pairs in ascending query order:
+ *   [0..20] A_ij = sum J_i J_j for i <= j, the upper triangle row-major (A_00 A_01 .. A_05 A_11 .. A_55);
+ *   [21..26] g_i = sum J_i r;   [27] rr = sum r r.
+ * Their order is sum_d2's and the refit's moments': a thread adds its 8 consecutive queries in query order; the wave's butterfly
+ * (lane l + lane l ^ o for o = 32, 16, .., 1) follows; the four waves of a chunk of 2048 queries are added in ascending order,
+ * ((w0 + w1) + w2) + w3; the chunks are added in ascending order starting from 0.  No floating-point atomic; batching, culling and
+ * the order in which the walk meets the queries change nothing.
+ * THE FIT minimises sum (r + w . c + t . n)^2 over the small rotation vector w and the translation t: A x = -g, x = (w, t).  In
+ * double, without contraction, in this order:
+ *   1. s_i = sqrt(A_ii), i = 0 .. 5.
+ *   2. C_ij = A_ij / (s_i * s_j) for i != j (the product first, j < i: A_ji / (s_j * s_i)); C_ii = 1.
+ *   3. Cholesky C = L L^T row by row: for i = 0 .. 5 { for j = 0 .. i-1 { v = C_ij; for k = 0 .. j-1: v = v - L_ik * L_jk;
+ *      L_ij = v / L_jj }  p_i = 1; for k = 0 .. i-1: p_i = p_i - L_ik * L_ik;  L_ii = sqrt(p_i) }.
+ *   4. L y = -g / s: for i = 0 .. 5 { v = (-g_i) / s_i; for k = 0 .. i-1: v = v - L_ik * y_k;  y_i = v / L_ii }.
+ *   5. L^T z = y: for i = 5 .. 0 { v = y_i; for k = i+1 .. 5: v = v - L_ki * z_k;  z_i = v / L_ii }.
+ *   6. x_i = z_i / s_i.
+ * THE ROTATION is exact (a rigid motion whatever the size of w) and uses only + - * / sqrt: the Cayley / quaternion form
+ *   h = w / 2;  S = sqrt(1 + ((h_x h_x + h_y h_y) + h_z h_z));  (a, b, c, d) = (1 / S, h_x / S, h_y / S, h_z / S);
+ *   R00 = 1 - 2 (c c + d d)   R01 = 2 (b c - a d)       R02 = 2 (b d + a c)
+ *   R10 = 2 (b c + a d)       R11 = 1 - 2 (b b + d d)   R12 = 2 (c d - a b)
+ *   R20 = 2 (b d - a c)       R21 = 2 (c d + a b)       R22 = 1 - 2 (b b + c c).
+ * THE STEP moves p to R (p - o) + o + t.  In the library's layout (new_j = x T[4j] + y T[4j+1] + z T[4j+2] + T[4j+3]):
+ *   T_step[4j + i] = R(j, i);   T_step[4j + 3] = (o_j + t_j) - ((R(j,0) o_x + R(j,1) o_y) + R(j,2) o_z);
+ *   T_step[12..14] = 0, T_step[15] = 1;   T_out = T * T_step by pcreg_model_refit_f32's product.
+ * OUTPUTS per transform: T_out, (at the device tier) T_step, n_close, sum_d2, n_plane, sum_res2 = rr, empty.  The plane RMSE of
+ * the transform that went in is sqrt(sum_res2 / n_plane): the caller's arithmetic.
+ * EMPTY: empty[b] = 1 and all 32 numbers of T_step[b] and T_out[b] are 0.0 when T[b] is the all-zero transform; when n_plane < 6;
+ * when some A_ii is not a finite number above 0; when some pivot p_i is not above 2^-26 (below that the solve has lost half of a
+ * double's digits, and a direction the planes do not constrain must not be invented: for a flat model in-plane sliding has
+ * A_ii = 0, for parallel planes a pivot vanishes); when x or T_step is not finite.  A failed candidate stays failed when the step
+ * is repeated.  Otherwise empty[b] = 0.  The counts and sums are reported either way.
+ * Q = 0 or a model without rows: every transform is empty, the counts and sums 0.  B = 0: nothing is written.
+ * THIS entry runs `steps` >= 1 such steps on the device with one upload and one read, as pcreg_model_refit_f32 does: T_out is the
+ * last step's, and the counts, sum_res2 and empty describe the transform that went INTO the last step.  normals == NULL: the
+ * normals are computed once on the device by pcreg_model_normals_f32's chain with this k (its range) and no viewpoint (the sign is
+ * immaterial); ldn is ignored.  normals given: k is ignored and they are uploaded once, whatever `steps`.
+ * PCREG_E_ARG: pcreg_model_refit_f32's cases; ldn < M with normals given; k outside 3 .. PCREG_KNN_MAX_K with normals NULL. */
+int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                                int steps, const float* normals /* host M x 3, or NULL */, int ldn, int k, double* T_out /* [B][16] */,
+                                int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty);
 /* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
  * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
@@ -566,6 +625,25 @@ int pcreg_dev_model_refit_f32(const pcreg_dev_model* model, const float* q, int 
                               double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
                               int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* empty /* [B] */,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* ONE step of pcreg_model_refit_plane_f32's contract on the device: q, T_dev [B][16], normals_dev [3 * ldn],
+ * T_out [B][16], T_step [B][16] (or NULL: not wanted), n_close, sum_d2, n_plane, sum_res2 and empty [B] are device pointers.
+ * normals_dev is what pcreg_dev_model_normals_f32 writes and may not be NULL; T_out may not alias T_dev.  Nothing synchronises;
+ * no workgroup waits for another.  The chain is pcreg_dev_model_refit_f32's up to the walk, which also keeps the winning ORIGINAL
+ * row per query slot; then per batch the 28 sums per (transform, chunk of 2048 queries), the normals gathered by that row, and
+ * the fit per transform.  No result depends on the batching.  Workspace, with nb, S and P as for
+ * pcreg_dev_model_score_workspace: the refit's layout followed by the winning row per slot and the chunk plane counts, with 28
+ * instead of 27 chunk sums,
+ * 131 328 + 2 roundup(12 S, 256) + 3 roundup(4 S, 256) + roundup(8 P, 256) + 2 roundup(4 P, 256) + roundup(224 P, 256) bytes.  A
+ * workspace shorter than that is PCREG_E_ARG too, and so are ldn < M and normals_dev NULL.  A handle may serve several streams at
+ * once, each call with its own workspace.  The debug keys "score_batch_slots" and "knn_nocull" act on this chain as on scoring's. */
+size_t pcreg_dev_model_refit_plane_workspace(int Q, int B, int M);
+int pcreg_dev_model_refit_plane_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                    const double* T_dev /* [B][16] on the device */, int B, float r2,
+                                    const float* normals_dev /* [3][ldn] */, int ldn,
+                                    double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                                    int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_plane /* [B] */,
+                                    double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 /* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain
  * (DESIGN 4.11).  label [M], indexed by ORIGINAL row: the 0-based number of the row's cluster, clusters numbered in ascending

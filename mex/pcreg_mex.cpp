@@ -25,6 +25,14 @@
 //                                          moved points); a zero page where there is no fit (fewer than three pairs, an empty
 //                                          estimateTransform, an all-zero T(:, :, b)); nClose / sumD2 are 'modelScore''s for the
 //                                          transform that went into the last step (matlab/refitTransformsModel.m)
+//   'modelRefitPlane', handle, pts (single Q x 3), T (double 4 x 4 x B), maxDist, steps, normals (single M x 3 | []), k -> Tout (double
+//                                          4 x 4 x B), nClose (B x 1 int32), sumD2 (B x 1 double), nPlane (B x 1 int32), sumRes2 (B x 1
+//                                          double): 'modelRefit' with the linearised point-to-plane step in estimateTransform's
+//                                          place; normals by model row as 'modelNormals' returns them (a row with a NaN offers no
+//                                          plane, the sign is immaterial), or [] to compute them once with k (3 .. 32); a zero
+//                                          page where there is no fit (fewer than six planes, a direction the planes leave free, an
+//                                          all-zero T(:, :, b)); the counts and sums are those of the transform that went into the
+//                                          last step, sqrt(sumRes2 ./ double(nPlane)) its plane RMSE (matlab/refitPlaneModel.m)
 //   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
 //                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
@@ -581,6 +589,44 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 if (nlhs > 1) plhs[1] = on; else mxDestroyArray(on);
                 if (nlhs > 2) plhs[2] = os; else mxDestroyArray(os);
             } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); }
+        }
+    } else if (!strcmp(cmd, "modelRefitPlane")) {             // [Tout, nClose, sumD2, nPlane, sumRes2] = pcreg_mex('modelRefitPlane', h, single(pts), T, maxDist, steps, normals, k)
+        if (nrhs != 8 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !radius_ok(prhs[4]) || !mxIsDouble(prhs[5]) ||
+            mxGetM(prhs[5]) * mxGetN(prhs[5]) != 1 || !(mxGetScalar(prhs[5]) >= 1.0) || !(mxGetScalar(prhs[5]) <= 1e6) ||
+            mxGetScalar(prhs[5]) != (double)(int)mxGetScalar(prhs[5]) || (!mxIsEmpty(prhs[6]) && (!mxIsSingle(prhs[6]) || mxGetN(prhs[6]) != 3)) ||
+            !normals_k_ok(prhs[7]))
+            usage = "modelRefitPlane: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), steps (a whole number >= 1), "
+                    "normals (single M x 3, or [] to compute them), k (a whole number 3 .. 32)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool given = !mxIsEmpty(prhs[6]);
+            int M = 0;
+            rc = pcreg_model_size(h, &M);
+            if (rc == PCREG_OK && given && (int)mxGetM(prhs[6]) != M) usage = "modelRefitPlane: normals must have one row per model row";
+            else if (rc == PCREG_OK) {
+                const mwSize dims[3] = {4, 4, (mwSize)B};
+                mxArray* ot = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+                mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+                mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+                mxArray* op = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+                mxArray* og = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+                mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+                if (B > 0) rc = pcreg_model_refit_plane_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2,
+                                                            (int)mxGetScalar(prhs[5]), given ? (const float*)mxGetData(prhs[6]) : nullptr, M > 0 ? M : 1,
+                                                            (int)mxGetScalar(prhs[7]), mxGetPr(ot), (int32_t*)mxGetData(on), mxGetPr(os),
+                                                            (int32_t*)mxGetData(op), mxGetPr(og), (int32_t*)mxGetData(oe));
+                mxDestroyArray(oe);
+                if (rc == PCREG_OK) {
+                    plhs[0] = ot;
+                    if (nlhs > 1) plhs[1] = on; else mxDestroyArray(on);
+                    if (nlhs > 2) plhs[2] = os; else mxDestroyArray(os);
+                    if (nlhs > 3) plhs[3] = op; else mxDestroyArray(op);
+                    if (nlhs > 4) plhs[4] = og; else mxDestroyArray(og);
+                } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(op); mxDestroyArray(og); }
+            }
         }
     } else if (!strcmp(cmd, "modelCluster")) {                // [label, clOff, members] = pcreg_mex('modelCluster', h, r): clusterPoints(model, r)
         if (nrhs != 3 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2])) usage = "modelCluster: handle (uint64), r (a real scalar >= 0)";

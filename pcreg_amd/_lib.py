@@ -64,6 +64,7 @@ SYMBOLS = [
     "pcreg_model_score_f32", "pcreg_dev_model_score_workspace", "pcreg_dev_model_score_f32",
     "pcreg_model_refit_f32", "pcreg_dev_model_refit_workspace", "pcreg_dev_model_refit_f32",
     "pcreg_model_normals_f32", "pcreg_point_normals_f32", "pcreg_dev_model_normals_workspace", "pcreg_dev_model_normals_f32",
+    "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
@@ -148,6 +149,12 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_normals_f32.argtypes = [vp, i, vp, vp, i, vp, vp, C.c_size_t, vp]
             L.pcreg_model_normals_f32.argtypes = [vp, i, vp, vp, i, vp]
             L.pcreg_point_normals_f32.argtypes = [vp, i, i, i, vp, vp, i, vp]
+        if hasattr(L, "pcreg_dev_model_refit_plane_workspace"):   # (an older build given through PCREG_LIB lacks the plane refit)
+            L.pcreg_dev_model_refit_plane_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_refit_plane_workspace.argtypes = [C.c_int] * 3
+            vp, i, f = C.c_void_p, C.c_int, C.c_float
+            L.pcreg_dev_model_refit_plane_f32.argtypes = [vp, vp, i, i, vp, i, f, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_refit_plane_f32.argtypes = [vp, vp, i, i, vp, i, f, i, vp, i, i, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_unique_rows3_workspace"):    # (an older build given through PCREG_LIB lacks unique_rows)
             for name in ("pcreg_dev_unique_rows3_workspace", "pcreg_dev_aggregate_matches_workspace"):
                 getattr(L, name).restype = C.c_size_t

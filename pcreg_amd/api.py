@@ -838,6 +838,46 @@ class Model:
         res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0)
         return res
 
+    def refit_plane(self, query, T, r2: float, steps: int = 1, normals=None, k: int = 6):
+        """B transforms refitted by the linearised point-to-plane step against the prepared model, `steps` times over
+        (pcreg_model_refit_plane_f32, whose contract this is): the pairs are refit_transforms', the residual of a pair is its
+        distance from the plane through the model row, and T <- T * T_step.  normals: [M, 3] float32 by original row, as
+        Model.normals returns them (a row with a non-finite component offers no plane; the sign is immaterial), or None to
+        compute them once on the device from the k nearest rows (6 is MATLAB's pcnormals default).  -> refit_transforms' dict
+        plus n_plane [B] int32, the pairs with a plane; sum_res2 [B] float64, the sum of their squared plane residuals;
+        plane_rmse = sqrt(sum_res2 / n_plane), NaN where there is none -- all for the transform that went INTO the last step.
+        empty is also set where fewer than six planes, or planes that leave a direction free, give no fit."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        nrm = None
+        if normals is not None:
+            nrm = _fcol(normals, np.float32)
+            if nrm.shape[0] != self.M:
+                raise ValueError(f"normals are [M, 3] with M = {self.M} rows, got {nrm.shape[0]}")
+        else:
+            k, _ = _normals_args(k, None)
+        out = np.zeros((max(B, 1), 16), dtype=np.float64)
+        n_close, n_plane, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(3))
+        sum_d2, sum_res2 = (np.zeros(max(B, 1), dtype=np.float64) for _ in range(2))
+        check(lib().pcreg_model_refit_plane_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                                nrm.ctypes.data if nrm is not None else None, max(self.M, 1), int(k), out.ctypes.data,
+                                                n_close.ctypes.data, sum_d2.ctypes.data, n_plane.ctypes.data, sum_res2.ctypes.data,
+                                                empty.ctypes.data))
+        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            plane_rmse = np.where(n_plane[:B] > 0, np.sqrt(sum_res2[:B] / n_plane[:B]), np.nan)
+        res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, n_plane=n_plane[:B],
+                   sum_res2=sum_res2[:B], plane_rmse=plane_rmse)
+        return res
+
     def cluster(self, r2: float):
         """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,
         members [M] int32), 0-based -- cluster_points' contract."""

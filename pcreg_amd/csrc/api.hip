@@ -396,6 +396,18 @@ int pcreg_dev_model_refit_f32(const pcreg_dev_model* model, const float* q, int 
     return launch_model_refit(model->v, q, Q, ldq, T_dev, B, r2, T_out, T_step, n_close, sum_d2, empty, workspace, workspace_bytes,
                               (hipStream_t)stream);
 }
+size_t pcreg_dev_model_refit_plane_workspace(int Q, int B, int M) { return refit_plane_ws_bytes(Q, B, M); }
+int pcreg_dev_model_refit_plane_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                    const float* normals, int ldn, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
+                                    int32_t* n_plane, double* sum_res2, int32_t* empty, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && normals && ldn >= 0);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && n_plane && sum_res2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_plane_ws_bytes(Q, B, 0));             // (the size does not depend on M)
+    PCREG_ARG(ldn >= model->v.M);                                            // (host data of the handle: refused before the device, as the rest)
+    GUARD();
+    return launch_model_refit_plane(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty,
+                                    workspace, workspace_bytes, (hipStream_t)stream);
+}
 size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -646,6 +658,55 @@ int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
     memcpy(n_close, host.data() + 17 * nB, sizeof(int32_t) * nB);
     memcpy(empty, (const int32_t*)(host.data() + 17 * nB) + nB, sizeof(int32_t) * nB);
+    return PCREG_OK;
+}
+
+// B transforms refitted `steps` times by the point-to-plane step: pcreg_model_refit_f32's staging, with the normals uploaded once
+// (or computed once on the device by the normals chain, k nearest rows and no viewpoint) before the first step, and ONE block read
+// back -- the last step's [T_out 16 B doubles][sum_d2 B][sum_res2 B][n_close B int32][n_plane B int32][empty B int32]
+int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
+                                const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_plane,
+                                double* sum_res2, int32_t* empty) {
+    PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && n_plane && sum_res2 && empty)));
+    PCREG_ARG(normals ? ldn >= 0 : (k >= 3 && k <= kKnnMaxK));
+    PCREG_ARG(model->dm != nullptr && (!normals || ldn >= model->M));
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const ModelView& v = model->dm->v;
+    const int M = v.M;
+    const size_t wsb = refit_plane_ws_bytes(Q, B, M), nwsb = normals || M == 0 ? 0 : normals_ws_bytes(M, k), nB = (size_t)B;
+    float *dq, *dn; double *dT, *dout; char *ws, *nws;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * nB, &dT));
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
+    TRY(st.take(2 * 20 * nB, &dout));                                      // two result blocks of 20 B doubles' room (18 B and 3 B int32)
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(nwsb, &nws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
+    else if (M > 0) TRY(launch_model_normals(v, k, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
+    const double* in = dT;
+    double* blk = dout;
+    for (int s = 0; s < steps; ++s) {
+        blk = dout + (size_t)(s & 1) * 20 * nB;
+        int32_t* ib = (int32_t*)(blk + 18 * nB);
+        TRY(launch_model_refit_plane(v, dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, blk, nullptr, ib, blk + 16 * nB, ib + nB, blk + 17 * nB, ib + 2 * nB, ws,
+                                     wsb, g_stream));
+        in = blk;
+    }
+    std::vector<double> host(20 * nB);
+    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 20 * nB, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const int32_t* hi = (const int32_t*)(host.data() + 18 * nB);
+    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
+    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
+    memcpy(sum_res2, host.data() + 17 * nB, sizeof(double) * nB);
+    memcpy(n_close, hi, sizeof(int32_t) * nB);
+    memcpy(n_plane, hi + nB, sizeof(int32_t) * nB);
+    memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
     return PCREG_OK;
 }
 

@@ -222,6 +222,12 @@ int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const
 // about origin[0..2], the batch's per-slot buffers best / tq / win (ld S), n_close [nb] already totalled
 int launch_refit_finish(const double* pmom, const int32_t* n_close, const float* best, const float* tq, const float* win, int Q, int S, int chunks,
                         int nb, const float* origin, const double* T_in, double* T_out, double* T_step, int32_t* empty, hipStream_t st);
+// the same chain with the point-to-plane fit in estimateTransform's place (knn_score.hip, plane_fit.hpp): normals
+// [3][ldn] on the device by ORIGINAL row; n_plane the pairs whose row has a finite normal, sum_res2 their squared plane residuals
+size_t refit_plane_ws_bytes(int Q, int B, int M);
+int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
+                             double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty,
+                             void* ws, size_t ws_bytes, hipStream_t st);
 // connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,

@@ -21,11 +21,18 @@
 //   C5  refit_moments_kernel          per (transform, chunk of 2048 queries): the 27 moments of (model row, moved point) over the
 //                                     chunk's hits in query order, shifted by the middle of the model's box; a fixed tree
 //   C6  launch_refit_finish           per transform (ransac.hip): the chunks ascending, fit_moments / fit_3pt, T * T_step
+//
+// The point-to-plane refit (pcreg_model_refit_plane_f32's contract) is the refit's chain up to C4 with the walk's
+// `idx` pointed at a workspace block, so the winning ORIGINAL row per slot is kept beside its coordinates, and then
+//   P5  plane_moments_kernel          per (transform, chunk of 2048 queries): the 28 sums of the plane pairs in query order -- a
+//                                     hit whose row has a finite normal, gathered by that row -- and their number; a fixed tree
+//   P6  plane_finish_kernel           per transform: the chunks ascending, plane_fit (plane_fit.hpp), T * T_step
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
 #include "chunk_scan.hpp"
 #include "moments.hpp"
+#include "plane_fit.hpp"
 #include <climits>
 #include <cmath>
 
@@ -202,11 +209,141 @@ __global__ __launch_bounds__(kBlock) void refit_moments_kernel(const float* __re
         pmom[(size_t)blockIdx.x * 27 + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
     }
 }
-// a call without pairs (Q = 0 or a model without rows): every transform is empty
-__global__ __launch_bounds__(kBlock) void refit_empty_kernel(int B, double* __restrict__ T_out, double* __restrict__ T_step, int32_t* __restrict__ empty) {
+// a call without pairs (Q = 0 or a model without rows): every transform is empty; n_plane / sum_res2: the plane refit's, or null
+__global__ __launch_bounds__(kBlock) void refit_empty_kernel(int B, double* __restrict__ T_out, double* __restrict__ T_step, int32_t* __restrict__ empty,
+                                                             int32_t* __restrict__ n_plane, double* __restrict__ sum_res2) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < 16 * B) { T_out[i] = 0.0; if (T_step) T_step[i] = 0.0; }
-    if (i < B) empty[i] = 1;
+    if (i < B) {
+        empty[i] = 1;
+        if (n_plane) n_plane[i] = 0;
+        if (sum_res2) sum_res2[i] = 0.0;
+    }
+}
+
+// ---- P5. the plane refit's sums -----------------------------------------------------------------------------------------
+// workgroup bl * chunks + c and thread t as refit_moments_kernel.  A hit (best == best) with the winning original row `row` is a
+// PLANE PAIR when normals[row], normals[row + ldn], normals[row + 2 ldn] are all finite.  The eight (best, row) loads of a thread
+// are issued first and the 24 gathers they address next, so the dependent loads are in flight together; then, in query order and
+// in double on the widened values without contraction: e = p - m, r = (n_x e_x + n_y e_y) + n_z e_z, u = p - o, c = u x n,
+// J = (c, n), and the 28 sums by fma -- A_ij (i <= j, row-major), g_i = J_i r, rr.  wave_sum27 for the first 27 and wave_sum for rr
+// (the same bits as 28 wave_sums), the four waves in ascending order; the number of plane pairs through chunk_sum.
+__global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
+                                                               const int32_t* __restrict__ prow, const float* __restrict__ normals, int ldn, int M, int Q,
+                                                               int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ psums,
+                                                               int32_t* __restrict__ pplane) {
+    __shared__ double s_m[kBlock / 64][kPlaneSums];
+    const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
+    const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
+    const double ox = (double)prep->cx, oy = (double)prep->cy, oz = (double)prep->cz;
+    int row[kScanPer];
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        row[u] = -1;
+        if (i0 + u < Q) {
+            const size_t s = (size_t)bl * Q + i0 + u;
+            const float d = best[s];
+            const int r = prow[s];
+            if (d == d && (unsigned)r < (unsigned)M) row[u] = r;      // (a hit's row is a model row: the walk wrote it)
+        }
+    }
+    float nx[kScanPer], ny[kScanPer], nz[kScanPer];
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        const int r = row[u] >= 0 ? row[u] : 0;
+        const float qnan = __int_as_float(0x7FC00000);
+        nx[u] = row[u] >= 0 ? normals[r] : qnan;
+        ny[u] = row[u] >= 0 ? normals[r + (size_t)ldn] : qnan;
+        nz[u] = row[u] >= 0 ? normals[r + 2 * (size_t)ldn] : qnan;
+    }
+    double acc[27], rr = 0.0;
+    int32_t cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        const double n0 = (double)nx[u], n1 = (double)ny[u], n2 = (double)nz[u];
+        if (plane_finite(n0) && plane_finite(n1) && plane_finite(n2)) {       // (a miss's are NaN)
+            const size_t s = (size_t)bl * Q + i0 + u;
+            const double m0 = (double)win[s], m1 = (double)win[s + (size_t)S], m2 = (double)win[s + 2 * (size_t)S];
+            const double p0 = (double)tq[s], p1 = (double)tq[s + (size_t)S], p2 = (double)tq[s + 2 * (size_t)S];
+            const double e0 = p0 - m0, e1 = p1 - m1, e2 = p2 - m2;
+            const double r = (n0 * e0 + n1 * e1) + n2 * e2;
+            const double u0 = p0 - ox, u1 = p1 - oy, u2 = p2 - oz;
+            const double J[6] = {u1 * n2 - u2 * n1, u2 * n0 - u0 * n2, u0 * n1 - u1 * n0, n0, n1, n2};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+#pragma unroll
+                for (int j = i; j < 6; ++j) acc[plane_tri(i, j)] = fma(J[i], J[j], acc[plane_tri(i, j)]);
+                acc[21 + i] = fma(J[i], r, acc[21 + i]);
+            }
+            rr = fma(r, r, rr);
+            ++cnt;
+        }
+    }
+    wave_sum27(acc);
+    rr = wave_sum(rr);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
+        s_m[threadIdx.x >> 6][27] = rr;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneSums) {
+        const int k = threadIdx.x;
+        psums[(size_t)blockIdx.x * kPlaneSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
+    }
+    chunk_sum(cnt, pplane);
+}
+
+// ---- P6. the plane refit's fit ------------------------------------------------------------------------------------------
+// one wave per transform bl of the batch: lane k < 28 adds sum k over the chunks in ascending order, lane 28 the plane counts;
+// every lane then runs plane_fit on the same 28 numbers about the origin the sums were taken about.  T_out = T_in * T_step by
+// refit_finish_kernel's product (ransac.hip).  No fit, or an all-zero T_in: empty = 1 and 32 zeros.
+__global__ __launch_bounds__(64) void plane_finish_kernel(const double* __restrict__ psums, const int32_t* __restrict__ pplane, int chunks,
+                                                          const Prep* __restrict__ prep, const double* __restrict__ T_in, double* __restrict__ T_out,
+                                                          double* __restrict__ T_step, int32_t* __restrict__ n_plane, double* __restrict__ sum_res2,
+                                                          int32_t* __restrict__ empty) {
+    __shared__ double s_sum[kPlaneSums], s_S[16];
+    __shared__ int32_t s_cnt;
+    const int bl = blockIdx.x, lane = threadIdx.x;
+    if (lane < kPlaneSums) {
+        double v = 0.0;
+        for (int c = 0; c < chunks; ++c) v += psums[((size_t)bl * chunks + c) * kPlaneSums + lane];
+        s_sum[lane] = v;
+    } else if (lane == kPlaneSums) {
+        int32_t n = 0;
+        for (int c = 0; c < chunks; ++c) n += pplane[(size_t)bl * chunks + c];
+        s_cnt = n;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    double sums[kPlaneSums];
+#pragma unroll
+    for (int k = 0; k < kPlaneSums; ++k) sums[k] = s_sum[k];
+    const int cnt = s_cnt;
+    bool in_empty = true;
+    for (int e = 0; e < 16; ++e) in_empty = in_empty && T_in[(size_t)bl * 16 + e] == 0.0;
+    const double o[3] = {(double)prep->cx, (double)prep->cy, (double)prep->cz};
+    double T[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) T[e] = 0.0;
+    const bool ok = !in_empty && plane_fit(sums, cnt, o, T);
+    if (lane < 16) {
+        double v = 0.0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) if (e == lane) v = T[e];
+        v = ok ? v : 0.0;
+        s_S[lane] = v;
+        if (T_step) T_step[(size_t)bl * 16 + lane] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    if (lane < 16) {
+        const int r = lane & 3, c = lane >> 2;
+        const double* Ti = T_in + (size_t)bl * 16;
+        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
+        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
+    }
+    if (lane == 0) { empty[bl] = ok ? 0 : 1; n_plane[bl] = cnt; sum_res2[bl] = sums[27]; }
 }
 
 // whole transforms per batch under a cap of `slots` query slots (at least one: Q <= kScoreMaxSlots)
@@ -221,8 +358,11 @@ int score_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk);
 // [chunk sums, P] [chunk counts, P]:
 // 131 328 + roundup(12 S, 256) + 2 roundup(4 S, 256) + roundup(8 P, 256) + roundup(4 P, 256) bytes
 // The refit's is that followed by [winning rows' coordinates, 3 S] [chunk moments, 27 P]: + roundup(12 S, 256) + roundup(216 P, 256)
-struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; };
-ScoreWs score_ws_layout(int Q, int B, bool refit, void* base, size_t* bytes) {
+// The plane refit's is the refit's with 28 chunk sums instead of 27, followed by [winning row per slot, S] [chunk plane counts, P]:
+// + roundup(12 S, 256) + roundup(224 P, 256) + roundup(4 S, 256) + roundup(4 P, 256)
+enum ScoreMode { kModeScore = 0, kModeRefit = 1, kModePlane = 2 };
+struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; int32_t* prow; int32_t* pplane; };
+ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes) {
     ScoreWs s{};
     const int nb = score_batch(Q, B, kScoreMaxSlots);
     const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * score_chunks(Q);
@@ -233,9 +373,13 @@ ScoreWs score_ws_layout(int Q, int B, bool refit, void* base, size_t* bytes) {
     s.best = w.take<float>(S);
     s.psum = w.take<double>(P);
     s.pcnt = w.take<int32_t>(P);
-    if (refit) {
+    if (mode != kModeScore) {
         s.win = w.take<float>(3 * S);
-        s.pmom = w.take<double>(27 * P);
+        s.pmom = w.take<double>((mode == kModePlane ? (size_t)kPlaneSums : (size_t)27) * P);
+    }
+    if (mode == kModePlane) {
+        s.prow = w.take<int32_t>(S);
+        s.pplane = w.take<int32_t>(P);
     }
     *bytes = w.bytes();
     return s;
@@ -243,14 +387,19 @@ ScoreWs score_ws_layout(int Q, int B, bool refit, void* base, size_t* bytes) {
 
 // what the refit adds to a scoring call: the outputs per transform (T_step may be null)
 struct RefitOut { double* T_out; double* T_step; int32_t* empty; };
+// ... and what the plane refit takes and gives beyond that: a normal per ORIGINAL row, the plane pairs and their squared residuals
+struct PlaneIo { const float* normals; int ldn; int32_t* n_plane; double* sum_res2; };
 
-// the chain of either call; `refit` null: scoring
+// the chain of every call; `refit` null: scoring; `plane` (with refit) non-null: the point-to-plane fit instead of estimateTransform
 int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close, double* sum_d2,
-                int32_t* idx, float* dist, const RefitOut* refit, void* ws, size_t ws_bytes, hipStream_t st) {
+                int32_t* idx, float* dist, const RefitOut* refit, const PlaneIo* plane, void* ws, size_t ws_bytes, hipStream_t st) {
     PCREG_ARG(Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxSlots && r2 >= 0.0f);
     size_t need;
-    const ScoreWs s = score_ws_layout(Q, B, refit != nullptr, ws, &need);
-    if (ws_bytes < need) { set_error("bad argument: %s workspace too small: %zu < %zu", refit ? "refit" : "score", ws_bytes, need); return PCREG_E_ARG; }
+    const ScoreWs s = score_ws_layout(Q, B, plane ? kModePlane : refit ? kModeRefit : kModeScore, ws, &need);
+    if (ws_bytes < need) {
+        set_error("bad argument: %s workspace too small: %zu < %zu", plane ? "plane refit" : refit ? "refit" : "score", ws_bytes, need);
+        return PCREG_E_ARG;
+    }
     if (B == 0) return PCREG_OK;
     if (Q == 0 || v.M == 0) {                                     // every query misses
         PCREG_HIP(hipMemsetAsync(n_close, 0, sizeof(int32_t) * (size_t)B, st));
@@ -262,18 +411,19 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
         }
         if (refit) {
             hipLaunchKernelGGL(refit_empty_kernel, dim3((unsigned)((16 * (size_t)B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, B, refit->T_out, refit->T_step,
-                               refit->empty);
+                               refit->empty, plane ? plane->n_plane : nullptr, plane ? plane->sum_res2 : nullptr);
             PCREG_HIP(hipGetLastError());
         }
         return PCREG_OK;
     }
+    if (plane) idx = s.prow;                                      // the winning row per slot of ONE batch (S entries: only the walk may write it)
     const int dbg_slots = debug_flag(kDbgScoreBatchSlots);        // "score_batch_slots": a lower cap, same results
     const int nb_max = score_batch(Q, B, dbg_slots > 0 ? std::min(dbg_slots, kScoreMaxSlots) : kScoreMaxSlots);
     const int n_tiles = (v.M + kT16 - 1) / kT16, chunks = score_chunks(Q);
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     for (int b0 = 0; b0 < B; b0 += nb_max) {
         const int nb = std::min(nb_max, B - b0), S = nb * Q;
-        const size_t at = (size_t)b0 * Q;
+        const size_t at = plane ? 0 : (size_t)b0 * Q;             // (the caller's [B][Q] tables take the batch at b0; the workspace block is per batch)
         hipLaunchKernelGGL(score_transform_kernel, dim3((S + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, T_dev + (size_t)b0 * 16, S, s.tq);
         int rc = launch_query_cells(v, s.tq, S, S, s.qcnt, st);
         if (!rc) rc = launch_query_order(v, s.tq, S, S, s.qcnt, s.qperm, st);
@@ -290,7 +440,15 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
         hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, Q, chunks, s.psum, s.pcnt);
         hipLaunchKernelGGL(score_total_kernel, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, nb,
                            chunks, n_close + b0, sum_d2 + b0);
-        if (refit) {
+        if (plane) {
+            hipLaunchKernelGGL(plane_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
+                               (const float*)s.win, (const int32_t*)s.prow, plane->normals, plane->ldn, v.M, Q, S, chunks, (const Prep*)v.prep, s.pmom,
+                               s.pplane);
+            PCREG_HIP(hipGetLastError());
+            hipLaunchKernelGGL(plane_finish_kernel, dim3(nb), dim3(64), 0, st, (const double*)s.pmom, (const int32_t*)s.pplane, chunks, (const Prep*)v.prep,
+                               T_dev + (size_t)b0 * 16, refit->T_out + (size_t)b0 * 16, refit->T_step ? refit->T_step + (size_t)b0 * 16 : nullptr,
+                               plane->n_plane + b0, plane->sum_res2 + b0, refit->empty + b0);
+        } else if (refit) {
             hipLaunchKernelGGL(refit_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
                                (const float*)s.win, Q, S, chunks, (const Prep*)v.prep, s.pmom);
             PCREG_HIP(hipGetLastError());
@@ -308,25 +466,40 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
 size_t score_ws_bytes(int Q, int B, int M) {
     (void)M;                                       // O(min(B Q, 4 Mi)) bytes, whatever M, r2 and the result
     if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
-    size_t b; (void)score_ws_layout(Q, B, false, nullptr, &b);
+    size_t b; (void)score_ws_layout(Q, B, kModeScore, nullptr, &b);
     return b;
 }
 size_t refit_ws_bytes(int Q, int B, int M) {
     (void)M;
     if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
-    size_t b; (void)score_ws_layout(Q, B, true, nullptr, &b);
+    size_t b; (void)score_ws_layout(Q, B, kModeRefit, nullptr, &b);
+    return b;
+}
+size_t refit_plane_ws_bytes(int Q, int B, int M) {
+    (void)M;
+    if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
+    size_t b; (void)score_ws_layout(Q, B, kModePlane, nullptr, &b);
     return b;
 }
 
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
                        double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, nullptr, ws, ws_bytes, st);
 }
 
 int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
                        int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
     const RefitOut out{T_out, T_step, empty};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, nullptr, ws, ws_bytes, st);
+}
+
+int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
+                             double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty,
+                             void* ws, size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(ldn >= v.M && (normals || v.M == 0));
+    const RefitOut out{T_out, T_step, empty};
+    const PlaneIo plane{normals, ldn, n_plane, sum_res2};
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, ws, ws_bytes, st);
 }
 
 }  // namespace pcreg

@@ -521,21 +521,26 @@ def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, 
     return score_summary(both[2 * n:], both[:2 * n].view(np.float64), Q)
 
 
-def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1):
+def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None):
     """Every trial of a sweep's result refitted on the dense clouds (PreparedModel.refit_transforms): completeExperimentFast.m:383-394's
     T_refine with the dense surface ([3, Q] float32) and the prepared dense model in the place of a cluster's re-matched
     keypoints, `steps` times over.  The orientation is score_trials': invertTF(transforms[t]) puts the surface on the model and
     is what gets refitted, and invertTF of the result comes back, so a refined transform maps the model onto the surface as
     ransac's do.  -> (transforms, summary): a list aligned with result["trial"], None for a failed trial and for one whose
     refit is empty; score_trials' dict for the pairs of the last step (the transform that went into it).  One upload and one
-    read, whatever `steps`; the radius is squared once in single."""
+    read, whatever `steps`; the radius is squared once in single.  normals (the [3, M] tensor PreparedModel.normals returns): the
+    steps are point-to-plane steps (PreparedModel.refit_plane) instead of estimateTransform steps -- the same orientation, the same
+    outputs, a trial whose planes give no fit None."""
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
     Q, n = int(surface_soa.shape[1]), len(tf)
     if n == 0:
         return [], score_summary(np.zeros(0, np.int32), np.zeros(0), Q)
     T_dev = torch.from_numpy(_transforms16(tf)).to(surface_soa.device)
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
-    T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
+    if normals is None:
+        T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
+    else:
+        T_out, _step, n_close, sum_d2, _n_plane, _res2, empty = model.refit_plane(surface_soa, T_dev, r2, normals, steps=steps)
     both = torch.cat([T_out.reshape(-1).view(torch.int32), sum_d2.view(torch.int32), n_close, empty]).cpu().numpy()
     mats = both[:32 * n].view(np.float64).reshape(n, 4, 4).transpose(0, 2, 1)
     gone = both[35 * n:] != 0
