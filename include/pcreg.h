@@ -970,7 +970,19 @@ int pcreg_ransac_sharded(const double* pts1, const double* pts2, int n, int ld, 
 /* ---- on-disk formats of the drivers (host code, no device needed) --------------------------
  * .pcd clouds (pcread / pcwrite, completeExperimentFast.m:12-13,30,403): ascii, binary and
  * binary_compressed (LZF) files are read; x/y/z may be float or double, rgb/rgba is returned as
- * the packed 0x00RRGGBB word.  xyz is n x 3 column-major (ld >= n), like pointCloud.Location. */
+ * the packed 0x00RRGGBB word.  xyz is n x 3 column-major (ld >= n), like pointCloud.Location.
+ * x/y/z may have any TYPE / SIZE of the format (I, U: 1, 2, 4, 8 bytes; F: 4, 8), each value converted
+ * to float once, from its own type; fields this library does not know are skipped.
+ * A file is untrusted input: a malformed one is refused with PCREG_E_ARG and a message that names
+ * it, never read past its end, and no exception leaves these functions.  pcreg_pcd_info validates the
+ * whole header (list lengths, types, sizes, COUNT >= 1, x / y / z present once, rgb / rgba one 4-byte
+ * word, WIDTH * HEIGHT and POINTS within 0 .. INT_MAX) and reports a count only if the file is large
+ * enough to hold that many points (binary: points * point size; ascii: two bytes a value;
+ * binary_compressed: the two stored sizes against the header and the file), so a caller may allocate
+ * from it.  Limits: a header line of at most 1 MiB, a COUNT of at most 16 Mi, a point of at most
+ * 16 MiB.  pcreg_pcd_read refuses what only the payload shows: a corrupt LZF stream, an ascii token
+ * that is no number (nan and inf are numbers), an ascii integer that its I / U field of that size
+ * does not hold (a sign on a U value included). */
 int pcreg_pcd_info(const char* path, int* n_points, int* has_rgb);
 int pcreg_pcd_read(const char* path, float* xyz, int ld, uint32_t* rgb /* n or NULL */, int n);
 int pcreg_pcd_write(const char* path, const float* xyz, int n, int ld, const uint32_t* rgb /* or NULL */,
@@ -979,7 +991,17 @@ int pcreg_pcd_write(const char* path, const float* xyz, int n, int ld, const uin
 /* .mat descriptor caches (load, completeExperimentFast.m:21-24,312-313): one real numeric
  * variable of a Level-5 MAT-file (save -v6 / -v7, zlib-compressed elements included; v7.3 = HDF5
  * is not supported) as column-major doubles.  name NULL or "" = the first numeric array.  Call
- * with out == NULL for the shape (dimensions beyond the second are folded into cols). */
+ * with out == NULL for the shape (dimensions beyond the second are folded into cols).  The data
+ * element may be of any numeric type (MATLAB stores whole-numbered doubles as the smallest integer
+ * type that holds them); a 64-bit integer is rounded to double once.
+ * Every tag is read inside the bytes that remain, and no exception leaves the function.  The file
+ * as a whole is refused (PCREG_E_ARG, a message that names it) when it is no little-endian Level-5
+ * file (version 4 and big-endian files included), when an element runs past its end, when a
+ * compressed element does not inflate or does not begin with a matrix.  A variable is refused only
+ * when it is the one asked for: a cell, struct, char, sparse, complex or object variable -- an
+ * opaque string / table / datetime object included -- is passed over on the way to another, and so
+ * is a numeric one that cannot be returned: fewer than two dimensions, a negative one, rows, cols
+ * or rows * cols beyond INT_MAX, fewer data than the shape, data of no numeric type. */
 int pcreg_mat_read_double(const char* path, const char* name, double* out, int* rows, int* cols);
 
 #ifdef __cplusplus
