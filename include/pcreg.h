@@ -355,6 +355,27 @@ int pcreg_unique_rows3(const double* A, int n, int ld, int32_t* ia, int* n_uniqu
 int pcreg_aggregate_matches(const double* pts1, const double* pts2, int n, int ld, double* out1, double* out2, int ldo, int32_t* ia,
                             int* n_out);
 
+/* Voxel-grid average downsampling (MATLAB's pcdownsample(pc, 'gridAverage', step); what made the _DS3 clouds of
+ * completeExperimentFast.m:13).  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- pts: n x 3 fp32 column-major with leading dimension ld >= n; step: a double on the host, finite and > 0.
+ * A ROW IS LIVE when its three coordinates are finite; a dead row belongs to no voxel.
+ * THE GRID: all grid arithmetic is double on the widened fp32 values, IEEE subtraction and division, no contraction, no reciprocal.
+ * lo[d] is the fp32 minimum of coordinate d over the live rows; the cell of a live row is
+ * c[d] = (int64) floor(((double)x[d] - (double)lo[d]) / step).  A cloud whose largest cell index along an axis is >= 2^21 is refused.
+ * A VOXEL is a distinct (c0, c1, c2).  The output rows are the voxels in ascending lexicographic order of (c0, c1, c2), column 0
+ * most significant -- the order of unique(cells, 'rows').
+ * THE MEAN, per voxel and per coordinate: a double sum of the widened coordinates of its rows, taken in ascending original row
+ * order, starting from 0.0; divided by the count in double; rounded once to fp32.
+ * outputs -- out: capacity n x 3 column-major with leading dimension ldo >= n, the first *n_out rows are written; count [n_out]
+ * (or NULL): the rows of every voxel; label [n] (or NULL): the 1-based output row of every input row, 0 for a dead row (the hook by
+ * which a caller averages colours or normals alongside); *n_out.  n = 0, or no live row, gives *n_out = 0 and writes nothing else.
+ * The result is a pure function of (pts, step): no floating-point atomic; the order in which workgroups run, the stream and the
+ * workspace's previous contents change no bit.
+ * PCREG_E_ARG before anything runs: step not finite or <= 0, ld < n, ldo < n, n < 0, pts / out NULL with n > 0, n_out NULL; and,
+ * after the device has found it, a cloud with 2^21 or more cells along an axis (nothing is written, *n_out = 0). */
+int pcreg_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count /* or NULL */,
+                              int32_t* label /* or NULL */, int* n_out);
+
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
  * than min_points (:17) or the ball fewer than min_points / more than max_points (:31).  pts: N x 3 column-major (ld >= N).
@@ -908,6 +929,21 @@ size_t pcreg_dev_aggregate_matches_workspace(int n_cap);
 int pcreg_dev_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1,
                                 double* out2, int ldo, int32_t idx_base, int32_t* ia, int32_t* n_out, void* workspace,
                                 size_t workspace_bytes, void* stream);
+/* pcreg_downsample_grid_f32's contract on the device: pts, out [3 * ldo], count [n] or NULL, label [n] or NULL are
+ * device pointers; n_out and info one int32 each on the device.  The device cannot know of the 2^21-cell refusal without a read:
+ * info = 0 when the cloud is fine, 1 when it is refused, then with n_out = 0 and nothing else written.  Nothing synchronises and
+ * nothing is read on the host; the launch chain depends on n alone.  Limits per chunk of 2048 rows and one reducing workgroup,
+ * (u64 key, u32 row) records, a stable least-significant-digit radix sort over ping-pong buffers (8-bit digits; only the passes
+ * under the used key bits move data), head flags + chunk scan, one thread per voxel for the ordered means.
+ * Workspace, with nn = max(n, 1) and chunks = ceil(nn / 2048):
+ *   256 + roundup(24 * chunks, 256) + roundup(4 * chunks, 256) + 2 * (roundup(8 * nn, 256) + roundup(4 * nn, 256))
+ *       + roundup(1024 * chunks, 256) + 1024 + roundup(4 * chunks, 256) + roundup(4 * nn, 256) bytes;
+ * a shorter one is PCREG_E_ARG, and so are pcreg_downsample_grid_f32's argument cases and a NULL n_out, info or workspace.
+ * pcreg_dev_downsample_grid_chunk: the records one workgroup of the sort handles (2048), for tests that straddle it. */
+size_t pcreg_dev_downsample_grid_workspace(int n);
+int pcreg_dev_downsample_grid_chunk(void);
+int pcreg_dev_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label,
+                                  int32_t* n_out, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 /* T = estimateTransform(pts1(idx, :), pts2(idx, :)) with the index list on the device (completeExperiment.m:458 on ransac's
  * inlier_idx): rows idx[0 .. *n_idx_dev) (idx_base-based; the count is clamped into [0, cap], every index into the cap rows) of
  * pts1 / pts2 (cap x 3 column-major, leading dimension ld >= cap).  The arithmetic of pcreg_dev_refine_by_distance with every

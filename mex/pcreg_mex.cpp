@@ -49,6 +49,12 @@
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
 //                                          completeExperiment.m:440-443, unique over pts1 then over pts2 (matlab/aggregateMatches.m)
+//   'downsampleGrid', pts (single n x 3), gridStep          -> ptsOut (u x 3 single), counts (u x 1 int32), labels (n x 1 int32):
+//                                          pcdownsample(pc, 'gridAverage', gridStep) -- the mean of the rows of every occupied
+//                                          cell floor((x - min) / gridStep), cells and sums in double, the voxels in ascending
+//                                          (c1, c2, c3) order; counts the rows of every voxel, labels the 1-based output row of
+//                                          every input row, 0 for a row with a NaN or Inf; the last two are built only when asked
+//                                          for; the input keeps its class, a double cloud is refused (matlab/pcdownsampleFast.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -704,6 +710,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 if (nlhs > 2) for (int k = 0; k < nu; ++k) mxGetPr(plhs[2])[k] = (double)((const int32_t*)mxGetData(ti))[k];
             }
             mxDestroyArray(t1); mxDestroyArray(t2); mxDestroyArray(ti);
+        }
+    } else if (!strcmp(cmd, "downsampleGrid")) {              // [ptsOut, counts, labels] = pcreg_mex('downsampleGrid', single(pts), gridStep)
+        if (nrhs == 3 && mxIsDouble(prhs[1]) && !mxIsEmpty(prhs[1]))
+            usage = "downsampleGrid: the cloud must be single -- pass single(pts); the result keeps the class of the input";
+        else if (nrhs != 3 || !(mxIsSingle(prhs[1]) || mxIsEmpty(prhs[1])) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1])) || !mxIsDouble(prhs[2]) ||
+                 mxGetM(prhs[2]) * mxGetN(prhs[2]) != 1 || !(mxGetScalar(prhs[2]) > 0.0) || !(mxGetScalar(prhs[2]) <= 1.7976931348623157e308))
+            usage = "downsampleGrid: pts (single n x 3), gridStep (a finite double scalar > 0)";
+        else {
+            const int n = mxIsEmpty(prhs[1]) ? 0 : (int)mxGetM(prhs[1]);
+            const size_t ld = n > 0 ? n : 1;
+            mxArray* to = mxCreateNumericMatrix(ld, 3, mxSINGLE_CLASS, mxREAL);
+            mxArray* tc = mxCreateNumericMatrix(ld, 1, mxINT32_CLASS, mxREAL);
+            mxArray* tl = mxCreateNumericMatrix((size_t)n, n > 0 ? 1 : 0, mxINT32_CLASS, mxREAL);
+            int u = 0;
+            rc = pcreg_downsample_grid_f32(n > 0 ? (const float*)mxGetData(prhs[1]) : nullptr, n, (int)ld, mxGetScalar(prhs[2]), (float*)mxGetData(to),
+                                           (int)ld, nlhs > 1 ? (int32_t*)mxGetData(tc) : nullptr, nlhs > 2 && n > 0 ? (int32_t*)mxGetData(tl) : nullptr, &u);
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateNumericMatrix((size_t)u, 3, mxSINGLE_CLASS, mxREAL);
+                for (int c = 0; c < 3; ++c)
+                    if (u > 0) memcpy((float*)mxGetData(plhs[0]) + (size_t)c * u, (const float*)mxGetData(to) + c * ld, (size_t)u * sizeof(float));
+                if (nlhs > 1) {
+                    plhs[1] = mxCreateNumericMatrix((size_t)u, u > 0 ? 1 : 0, mxINT32_CLASS, mxREAL);
+                    if (u > 0) memcpy(mxGetData(plhs[1]), mxGetData(tc), (size_t)u * sizeof(int32_t));
+                }
+                if (nlhs > 2) { plhs[2] = tl; tl = nullptr; }             // (no live row: the library wrote nothing, the zeros stand)
+            }
+            mxDestroyArray(to); mxDestroyArray(tc);
+            if (tl) mxDestroyArray(tl);
         }
     } else if (!strcmp(cmd, "descCreate")) {                  // h = pcreg_mex('descCreate', desc): an n x D double descriptor set, uploaded ONCE
         if (nrhs != 2 || !mxIsDouble(prhs[1])) usage = "descCreate: desc (double n x D)";

@@ -67,6 +67,7 @@ SYMBOLS = [
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
+    "pcreg_downsample_grid_f32", "pcreg_dev_downsample_grid_workspace", "pcreg_dev_downsample_grid_chunk", "pcreg_dev_downsample_grid_f32",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
     "pcreg_align_points_knn", "pcreg_align_points_knn_f32", "pcreg_align_points_knn_batched", "pcreg_spatial_histogram_descriptors",
     "pcreg_spatial_histogram_descriptors_f32", "pcreg_spatial_histogram_descriptors_mixed",
@@ -159,6 +160,13 @@ def lib() -> C.CDLL:
             for name in ("pcreg_dev_unique_rows3_workspace", "pcreg_dev_aggregate_matches_workspace"):
                 getattr(L, name).restype = C.c_size_t
                 getattr(L, name).argtypes = [C.c_int]
+        if hasattr(L, "pcreg_dev_downsample_grid_workspace"):  # (an older build given through PCREG_LIB lacks the downsampling)
+            L.pcreg_dev_downsample_grid_workspace.restype = C.c_size_t
+            L.pcreg_dev_downsample_grid_workspace.argtypes = [C.c_int]
+            L.pcreg_dev_downsample_grid_chunk.argtypes = []
+            vp, i, d = C.c_void_p, C.c_int, C.c_double                           # (a double by value: declared)
+            L.pcreg_dev_downsample_grid_f32.argtypes = [vp, i, i, d, vp, i, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_downsample_grid_f32.argtypes = [vp, i, i, d, vp, i, vp, vp, vp]
         for name, args in (("pcreg_debug_knn_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_knn_unit_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_ransac_stats", [C.POINTER(C.c_longlong), C.c_int]),

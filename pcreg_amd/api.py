@@ -718,6 +718,30 @@ def aggregate_matches(pts1, pts2):
     return np.ascontiguousarray(o1[:u]), np.ascontiguousarray(o2[:u]), ia[:u] - 1
 
 
+def pcdownsample(pts, step: float):
+    """pcdownsample(pc, 'gridAverage', step) for an n x 3 float32 cloud (pcreg_downsample_grid_f32's contract): (out [n_out, 3]
+    float32, count [n_out] int32, label [n] int32).  A voxel is a distinct cell floor((x - lo) / step) of the grid that starts at the
+    minimum of the finite rows, taken in double; the output rows are the voxels in ascending (c0, c1, c2) order, each the mean of
+    its rows, summed in double in ascending row order and rounded once; count their number of rows; label the 0-based output row
+    of every input row, -1 for a row with a non-finite coordinate (it belongs to no voxel).  A cloud that spans 2^21 or more
+    cells along an axis is refused (PCREG_E_ARG)."""
+    step = float(step)
+    if not (math.isfinite(step) and step > 0.0):
+        raise ValueError(f"step must be a finite number > 0, got {step}")
+    p = _fcol(pts, np.float32)
+    if p.shape[1] != 3:
+        raise ValueError("pts must be N x 3")
+    n = p.shape[0]
+    ld = max(n, 1)
+    out = np.zeros((ld, 3), dtype=np.float32, order="F")
+    count = np.zeros(ld, dtype=np.int32)
+    label = np.zeros(ld, dtype=np.int32)
+    no = C.c_int(0)
+    check(lib().pcreg_downsample_grid_f32(p.ctypes.data, n, ld, step, out.ctypes.data, ld, count.ctypes.data, label.ctypes.data, C.byref(no)))
+    u = no.value
+    return np.ascontiguousarray(out[:u]), count[:u].copy(), label[:n] - 1
+
+
 def _transforms16(T) -> np.ndarray:
     """[B, 16] float64, each transform column-major: from a [B, 4, 4] array, one 4 x 4 matrix, or a sequence of 4 x 4 matrices
     in which None (or an empty array: MATLAB's []) stands for the empty transform, sixteen zeros"""

@@ -825,6 +825,36 @@ int pcreg_unique_rows3(const double* A, int n, int ld, int32_t* ia, int* n_uniqu
     *n_unique = nu;
     return PCREG_OK;
 }
+// pcdownsample(pts, 'gridAverage', step): one upload, the chain, one read of (n_out, info), then one read of the results
+int pcreg_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int* n_out) {
+    PCREG_ARG(n_out && n >= 0 && ld >= n && ldo >= n && std::isfinite(step) && step > 0.0 && (n == 0 || (pts && out)));
+    GUARD();
+    *n_out = 0;
+    if (n == 0) return PCREG_OK;
+    Stage st{scratch()};
+    float *dp, *dout; int32_t *dcount, *dlabel, *dword; char* ws;
+    const size_t wsb = downsample_grid_ws_bytes(n);
+    TRY(st.take(3 * (size_t)n, &dp));
+    TRY(st.take(3 * (size_t)n, &dout));
+    TRY(st.take(count ? (size_t)n : 0, &dcount));
+    TRY(st.take(label ? (size_t)n : 0, &dlabel));
+    TRY(st.take(2, &dword));                                    // n_out, info
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(pts, n, ld, 3, dp, g_stream));
+    TRY(launch_downsample_grid(dp, n, n, step, dout, n, count ? dcount : nullptr, label ? dlabel : nullptr, dword, dword + 1, ws, wsb, g_stream));
+    int32_t word[2] = {0, 0};
+    PCREG_HIP(hipMemcpyAsync(word, dword, sizeof word, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    if (word[1] != 0) { set_error("bad argument: the cloud spans 2^21 or more cells of this step along an axis"); return PCREG_E_ARG; }
+    const size_t no = (size_t)word[0];
+    if (no == 0) return PCREG_OK;                                // no live row: nothing else is written
+    PCREG_HIP(hipMemcpy2DAsync(out, sizeof(float) * (size_t)ldo, dout, sizeof(float) * (size_t)n, sizeof(float) * no, 3, hipMemcpyDeviceToHost, g_stream));
+    if (count) PCREG_HIP(hipMemcpyAsync(count, dcount, sizeof(int32_t) * no, hipMemcpyDeviceToHost, g_stream));
+    if (label) PCREG_HIP(hipMemcpyAsync(label, dlabel, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    *n_out = word[0];
+    return PCREG_OK;
+}
 int pcreg_aggregate_matches(const double* pts1, const double* pts2, int n, int ld, double* out1, double* out2, int ldo, int32_t* ia, int* n_out) {
     PCREG_ARG(n_out && n >= 0 && ld >= n && ldo >= n && (n == 0 || (pts1 && pts2 && out1 && out2)));
     PCREG_ARG(!has_nan3(pts1, n, ld) && !has_nan3(pts2, n, ld));
@@ -1888,6 +1918,15 @@ int pcreg_dev_unique_rows3_f64(const double* A, const int32_t* n_dev, int n_cap,
     PCREG_ARG(workspace_bytes >= unique_rows3_ws_bytes(n_cap));
     GUARD();
     return launch_unique_rows3(A, n_dev, n_cap, ld, idx_base, ia, n_unique, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t pcreg_dev_downsample_grid_workspace(int n) { return downsample_grid_ws_bytes(n); }
+int pcreg_dev_downsample_grid_chunk(void) { return downsample_grid_chunk(); }
+int pcreg_dev_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int32_t* n_out,
+                                  int32_t* info, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(n_out && info && workspace && n >= 0 && ld >= n && ldo >= n && std::isfinite(step) && step > 0.0 && (n == 0 || (pts && out)));
+    PCREG_ARG(workspace_bytes >= downsample_grid_ws_bytes(n));
+    GUARD();
+    return launch_downsample_grid(pts, n, ld, step, out, ldo, count, label, n_out, info, workspace, workspace_bytes, (hipStream_t)stream);
 }
 size_t pcreg_dev_aggregate_matches_workspace(int n_cap) { return aggregate_matches_ws_bytes(n_cap); }
 int pcreg_dev_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1, double* out2,

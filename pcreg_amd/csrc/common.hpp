@@ -244,6 +244,12 @@ int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld
 size_t aggregate_matches_ws_bytes(int n_cap);
 int launch_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1, double* out2, int ldo,
                              int32_t idx_base, int32_t* ia, int32_t* n_out, void* ws, size_t ws_bytes, hipStream_t st);
+// pcdownsample(pc, 'gridAverage', step) of n x 3 fp32 rows (downsample.hip): limits, keys, a stable radix sort of (key, row)
+// records, heads + chunk scan, ordered means.  n_out and info are single device words; count and label may be null
+size_t downsample_grid_ws_bytes(int n);
+int downsample_grid_chunk();                        // records per workgroup of the sort (the tests' T)
+int launch_downsample_grid(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int32_t* n_out,
+                           int32_t* info, void* ws, size_t ws_bytes, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,

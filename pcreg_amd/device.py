@@ -338,6 +338,44 @@ _dropped: list = []            # handles replaced by as_prepared(): freed later,
 _reprepared = 0
 
 
+def downsample_grid(points_soa: torch.Tensor, step: float, stream=None, out=None):
+    """pcdownsample(pc, 'gridAverage', step) on a resident cloud (pcreg_dev_downsample_grid_f32; the contract is
+    pcreg_downsample_grid_f32's): points_soa a [3, n] float32 tensor with contiguous rows -> (out [3, n] float32 of which the
+    first n_out columns are written, count [n] int32 likewise, label [n] int32: the 1-based output column of every input row, 0
+    for a row with a non-finite coordinate; n_out, info: one int32 tensor each on the device).  info is 1 when the cloud spans
+    2^21 or more cells along an axis; then n_out is 0 and nothing else is written.  Runs on `stream` (a torch.cuda.Stream) or
+    torch's current stream; nothing synchronises -- the one read is the caller's:
+
+        out, count, label, n_out, info = downsample_grid(soa(cloud), 0.5)
+        u = int(n_out.item())                                   # the only trip to the host
+        coarse = PreparedModel(out[:, :u])                      # a view: the row stride stays n
+
+    Buffers are allocated per call; calls that reuse theirs pass out=(out, count, label, n_out, info, ws) with ws of
+    pcreg_dev_downsample_grid_workspace(n) bytes."""
+    if points_soa.dtype != torch.float32 or points_soa.dim() != 2 or points_soa.shape[0] != 3 or (points_soa.shape[1] and points_soa.stride(1) != 1):
+        raise TypeError("a cloud is a [3, n] float32 tensor with contiguous rows (column-major n x 3)")
+    step = float(step)
+    if not (step > 0.0 and step != float("inf")):
+        raise ValueError(f"step must be a finite number > 0, got {step}")
+    n, dev = int(points_soa.shape[1]), points_soa.device
+    need = max(int(lib().pcreg_dev_downsample_grid_workspace(n)), 256)
+    if out is not None:
+        o, count, label, n_out, info, ws = out
+    else:
+        o = torch.empty((3, n), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        label = torch.empty(n, dtype=torch.int32, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    st = C.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    with torch.cuda.device(dev):
+        check(lib().pcreg_dev_downsample_grid_f32(_p(points_soa) if n else None, n, max(int(points_soa.stride(0)), n) if n else 1, step,
+                                                  _p(o) if n else None, max(int(o.stride(0)), n) if n else 1, _p(count) if n else None,
+                                                  _p(label) if n else None, _p(n_out), _p(info), _p(ws), C.c_size_t(ws.numel()), st))
+    return o, count, label, n_out, info
+
+
 def release_dropped() -> None:
     """Free the prepared models that as_prepared() replaced (pcreg_dev_model_destroy synchronises the device: not something to
     do between two launches of a hot loop, which is where a replaced cache entry used to die)."""
