@@ -339,6 +339,39 @@ int pcreg_model_normals_f32(pcreg_model* model, int k, const double* viewpoint /
                             float* variation /* or NULL */);
 /* The same without a handle (pcnormals(m, k)): uploads and prepares the cloud for this call only. */
 int pcreg_point_normals_f32(const float* m, int M, int ldm, int k, const double* viewpoint, float* normals, int ldn, float* variation);
+/* Statistical outlier removal over the rows of the model (MATLAB's pcdenoise(ptCloud, 'NumNeighbors', k, 'Threshold', t); PCL's
+ * StatisticalOutlierRemoval).  THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- a prepared model of M rows; k = NumNeighbors with 1 <= k <= PCREG_KNN_MAX_K - 1 (the list holds k + 1 entries, the
+ * row itself among them); threshold t, a finite double >= 0.
+ * THE NEIGHBOURHOOD of row i is what pcreg_model_knn_f32 returns for query = row i with k + 1: the k + 1 smallest fp32
+ * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) among the finite rows, the first of them always 0 (the row itself, or a coincident row).  A row
+ * with a non-finite coordinate is never a neighbour and has none; a distance that overflows to +inf is no neighbour.  Only the
+ * multiset of the distances matters, not which row a tied distance belongs to.  n <= k + 1 is the number found; n < k + 1 only
+ * when the model has fewer than k + 1 finite rows.
+ * THE MEAN DISTANCE d_i, in double without contraction: each of the n squared distances widened to double, its double square
+ * root (correctly rounded), the roots added in ascending order from 0.0 (the leading 0 adds nothing, which is how MATLAB drops
+ * the first column), the sum divided by (double)(n - 1).  n <= 1, and so a non-finite row, gives d_i = NaN.
+ * THE STATISTIC.  nf: the rows with a finite d_i.  mu: their sum / nf.  sd: MATLAB's std, two passes --
+ * sqrt(sum of (d_i - mu)^2 / (nf - 1)), 0 when nf = 1.  thr = mu + t * sd (a product, then a sum).  nf = 0 gives mu, sd and thr NaN.
+ * THE ORDER OF THE TWO SUMS is a function of M alone.  The rows are cut into chunks of 2048 consecutive ORIGINAL rows.  Inside a
+ * chunk, part p (0 .. 255) adds its terms for rows 8 p .. 8 p + 7 of the chunk in ascending order from 0.0, a row that is not
+ * finite (or past M) adding nothing; the 256 parts are added by the TREE: within each group of 64 consecutive parts, pairwise at
+ * distance 32, then 16, 8, 4, 2, 1 (every part ends with its group's sum), then the four group sums as (g0 + g1) + (g2 + g3).
+ * The chunk sums are added likewise: part p adds chunks p, p + 256, ... in ascending order from 0.0, then the same tree.  No
+ * floating-point atomic anywhere.
+ * THE RESULT.  Row i is an inlier iff d_i <= thr on the RETURNED doubles (NaN on either side: no inlier), so a caller restates
+ * the mask to the bit from mean_dist and stats[0].
+ * outputs, each may be NULL -- mean_dist [M], by ORIGINAL row; inliers [capacity M]: the 0-based original rows of the inliers,
+ * ascending, *n_inliers of them (inliers given needs n_inliers; n_inliers alone counts); stats [4] = {thr, mu, sd, (double) nf}.
+ * M = 0 writes *n_inliers = 0, stats = {NaN, NaN, NaN, 0} and nothing else.
+ * The result is a function of (model rows, k, t) only: culling, the call, the stream and the workspace's previous contents change
+ * no bit.  PCREG_E_ARG: k outside 1 .. PCREG_KNN_MAX_K - 1, t negative or not finite, model NULL, inliers without n_inliers. */
+int pcreg_model_denoise_f32(pcreg_model* model, int k, double threshold, double* mean_dist /* [M] or NULL */,
+                            int32_t* inliers /* [M] or NULL */, int32_t* n_inliers /* or NULL */, double* stats /* [4] or NULL */);
+/* The same without a handle (pcdenoise(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG: M < 0,
+ * ldm < M, m NULL with M > 0. */
+int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double threshold, double* mean_dist, int32_t* inliers,
+                            int32_t* n_inliers, double* stats);
 
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
@@ -686,6 +719,18 @@ int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t*
 size_t pcreg_dev_model_normals_workspace(int M, int k);
 int pcreg_dev_model_normals_f32(const pcreg_dev_model* model, int k, const double* viewpoint /* host, 3 or NULL */, float* normals,
                                 int ldn, float* variation /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_denoise_f32's contract on the device: mean_dist [M], inliers [M], n_inliers (one int32) and stats [4]
+ * are device pointers, each may be NULL as there.  Six launches: the seed bound of every sorted row with k + 1; the normals' walk
+ * with a list of distances alone, each row's mean distance finished in registers; the chunk sums; mu and the chunk deviations; sd,
+ * thr and the chunk inlier counts; the ascending scatter and the count (skipped without n_inliers).  Nothing synchronises; no
+ * workgroup waits for another.  Workspace, with R = max(M, 1) and C = max(ceil(M / 2048), 1):
+ * roundup(4 R, 256) + roundup(8 R, 256) + 2 roundup(8 C, 256) + 2 roundup(4 C, 256) + 256 bytes, whatever k; a workspace shorter
+ * than that is PCREG_E_ARG too.  A handle may serve several streams at once, each call with its own workspace.  The debug keys
+ * "knn_nocull" and "knn_stats" act on the walk as on the normals'. */
+size_t pcreg_dev_model_denoise_workspace(int M, int k);
+int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double threshold, double* mean_dist /* or NULL */,
+                                int32_t* inliers /* or NULL */, int32_t* n_inliers /* or NULL */, double* stats /* [4] or NULL */,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

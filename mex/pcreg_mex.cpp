@@ -45,6 +45,13 @@
 //                                          double 1 x 3 the normals point towards, always passed; variation = lambda_min / the
 //                                          sum of the three eigenvalues, built only when asked for; NaN rows where there is no
 //                                          normal (matlab/pcnormalsModel.m, matlab/pcnormalsFast.m)
+//   'modelDenoise', handle, k, threshold | 'pointDenoise', pts (single M x 3), k, threshold -> inlierIndices (n x 1 uint32, 1-based,
+//                                          ascending, as pcdenoise returns them), meanDist (M x 1 double), thr (double scalar):
+//                                          pcdenoise(ptCloud, 'NumNeighbors', k, 'Threshold', threshold) -- meanDist the mean
+//                                          distance of every row to its k nearest other rows (1 <= k <= 31), NaN for a row with a
+//                                          NaN or Inf; thr = mean + threshold * std of the finite ones; a row is an inlier iff
+//                                          meanDist <= thr; the last two outputs are built only when asked for
+//                                          (matlab/pcdenoiseModel.m, matlab/pcdenoiseFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -142,6 +149,37 @@ static int normals_on_handle(pcreg_model* h, int k, const mxArray* vp, bool want
                                  ov ? (float*)mxGetData(ov) : nullptr);
     if (rc == PCREG_OK) { out[0] = on; out[1] = ov; }
     else { mxDestroyArray(on); if (ov) mxDestroyArray(ov); }
+    return rc;
+}
+
+// k and threshold of the denoise commands: a real double scalar, whole, 1 .. PCREG_KNN_MAX_K - 1; a finite real double scalar >= 0
+static bool denoise_k_ok(const mxArray* a) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 1.0 && mxGetScalar(a) <= (double)(PCREG_KNN_MAX_K - 1) &&
+           mxGetScalar(a) == (double)(int)mxGetScalar(a);
+}
+static bool denoise_t_ok(const mxArray* a) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 0.0 && mxGetScalar(a) <= 1.7976931348623157e308;
+}
+// the outputs of 'modelDenoise' / 'pointDenoise': inlierIndices (n x 1 uint32, 1-based), and with nout > 1 meanDist (M x 1 double),
+// with nout > 2 thr.  Nothing is left allocated on an error.
+static int denoise_on_handle(pcreg_model* h, int k, double t, int nout, mxArray* out[3]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    mxArray* ti = mxCreateNumericMatrix((size_t)(M > 0 ? M : 1), 1, mxINT32_CLASS, mxREAL);
+    mxArray* om = nout > 1 ? mxCreateDoubleMatrix((size_t)M, 1, mxREAL) : nullptr;
+    int32_t n = 0;
+    double stats[4] = {0.0, 0.0, 0.0, 0.0};
+    rc = pcreg_model_denoise_f32(h, k, t, om && M > 0 ? mxGetPr(om) : nullptr, (int32_t*)mxGetData(ti), &n, stats);
+    if (rc == PCREG_OK) {
+        out[0] = mxCreateNumericMatrix((size_t)n, 1, mxUINT32_CLASS, mxREAL);
+        const int32_t* src = (const int32_t*)mxGetData(ti);
+        uint32_t* dst = (uint32_t*)mxGetData(out[0]);
+        for (int32_t i = 0; i < n; ++i) dst[i] = (uint32_t)src[i] + 1u;
+        out[1] = om;
+        if (nout > 2) out[2] = mxCreateDoubleScalar(stats[0]);
+    } else if (om) mxDestroyArray(om);
+    mxDestroyArray(ti);
     return rc;
 }
 
@@ -671,6 +709,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = normals_on_handle(h, (int)mxGetScalar(prhs[2]), prhs[3], nlhs > 1, out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
+        }
+    } else if (!strcmp(cmd, "modelDenoise")) {                // [inlierIndices, meanDist, thr] = pcreg_mex('modelDenoise', h, k, threshold)
+        if (nrhs != 4 || !mxIsUint64(prhs[1]) || !denoise_k_ok(prhs[2]) || !denoise_t_ok(prhs[3]))
+            usage = "modelDenoise: handle (uint64), k (a whole number 1 .. 31), threshold (a finite double scalar >= 0)";
+        else {
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            rc = denoise_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), nlhs, out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "pointDenoise")) {                // [inlierIndices, meanDist, thr] = pcreg_mex('pointDenoise', single(pts), k, threshold)
+        if (nrhs != 4 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !denoise_k_ok(prhs[2]) || !denoise_t_ok(prhs[3]))
+            usage = "pointDenoise: pts (single M x 3), k (a whole number 1 .. 31), threshold (a finite double scalar >= 0)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = denoise_on_handle(h, (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
         }
     } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)
         if (nrhs != 2 || !mxIsDouble(prhs[1]) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1]))) usage = "uniqueRows3: A (double n x 3)";

@@ -688,6 +688,39 @@ def point_normals(pts, k: int, viewpoint=None, variation: bool = False):
     return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_point_normals_f32(m.ctypes.data, M, max(M, 1), k, v, n, ldn, va)), M, vp, variation)
 
 
+def _denoise_args(k, threshold):
+    k, threshold = int(k), float(threshold)
+    if not 1 <= k <= KNN_MAX_K - 1:
+        raise ValueError(f"k (NumNeighbors) must lie in [1, {KNN_MAX_K - 1}], got {k}")
+    if not (math.isfinite(threshold) and threshold >= 0.0):
+        raise ValueError(f"threshold must be a finite number >= 0, got {threshold}")
+    return k, threshold
+
+
+def _denoise_call(call, M: int) -> dict:
+    md = np.zeros(max(M, 1), dtype=np.float64)
+    inl = np.zeros(max(M, 1), dtype=np.int32)
+    n = C.c_int32(0)
+    stats = np.zeros(4, dtype=np.float64)
+    call(md.ctypes.data, inl.ctypes.data, C.byref(n), stats.ctypes.data)
+    return dict(inliers=inl[:n.value].copy(), mean_dist=md[:M], thr=float(stats[0]), mean=float(stats[1]), std=float(stats[2]),
+                n_finite=int(stats[3]))
+
+
+def point_denoise(pts, k: int = 4, threshold: float = 1.0) -> dict:
+    """pcdenoise(pts, 'NumNeighbors', k, 'Threshold', threshold) (pcreg_model_denoise_f32's contract): a dict with mean_dist [M]
+    float64, the mean distance of every row to its k nearest other rows (1 <= k <= 31; NaN for a non-finite row and where fewer
+    than two finite rows exist); mean, std and n_finite of the finite ones; thr = mean + threshold * std; inliers, the 0-based
+    rows with mean_dist <= thr, ascending int32 (pts[inliers] is the denoised cloud).  The cloud is prepared for this call only:
+    keep a Model for repeated calls."""
+    k, threshold = _denoise_args(k, threshold)
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    return _denoise_call(lambda md, inl, n, st: check(lib().pcreg_point_denoise_f32(m.ctypes.data, M, max(M, 1), k, threshold, md, inl, n, st)), M)
+
+
 def unique_rows(A):
     """[C, ia] = unique(A, 'rows') for an n x 3 float64 array: (C [u, 3], ia [u] int32, 0-based).  Rows in lexicographic order by
     column 1, 2, 3 as numbers (-0 == +0); the first occurrence represents its run and C = A[ia] carries its bits.  A NaN anywhere
@@ -917,6 +950,14 @@ class Model:
             raise ValueError("the model handle is closed")
         k, vp = _normals_args(k, viewpoint)
         return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_model_normals_f32(self._h, k, v, n, ldn, va)), self.M, vp, variation)
+
+    def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
+        """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold
+        mean + threshold * std, and the rows at or below it -- point_denoise's dict."""
+        if self._h is None:
+            raise RuntimeError("model handle closed")
+        k, threshold = _denoise_args(k, threshold)
+        return _denoise_call(lambda md, inl, n, st: check(lib().pcreg_model_denoise_f32(self._h, k, threshold, md, inl, n, st)), self.M)
 
     def close(self):
         if self._h.value:

@@ -422,6 +422,14 @@ int pcreg_dev_model_normals_f32(const pcreg_dev_model* model, int k, const doubl
     GUARD();
     return launch_model_normals(model->v, k, viewpoint, normals, ldn, variation, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_denoise_workspace(int M, int k) { return denoise_ws_bytes(M, k); }
+int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers,
+                                double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && k >= 1 && k <= kKnnMaxK - 1 && std::isfinite(threshold) && threshold >= 0.0 && (n_inliers || !inliers));
+    PCREG_ARG(workspace_bytes >= denoise_ws_bytes(0, k));                    // (the smallest any model needs; the launcher checks this model's)
+    GUARD();
+    return launch_model_denoise(model->v, k, threshold, mean_dist, inliers, n_inliers, stats, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -791,6 +799,58 @@ int pcreg_point_normals_f32(const float* m, int M, int ldm, int k, const double*
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return normals_on_view(st, v, k, viewpoint, normals, ldn, variation);
+}
+
+// pcdenoise on a prepared model's own rows: the chain on the device, ONE read of the count and the statistic (with the mean
+// distances behind them), then the inlier rows the count names
+static int denoise_on_view(Stage& st, const ModelView& v, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers,
+                           double* stats) {
+    const int M = v.M;
+    if (n_inliers) *n_inliers = 0;
+    if (M == 0) {
+        if (stats) { stats[0] = stats[1] = stats[2] = std::nan(""); stats[3] = 0.0; }
+        return PCREG_OK;
+    }
+    double *dmd, *dstats; int32_t *dinl, *dn; char* ws;
+    const size_t wsb = denoise_ws_bytes(M, k);
+    TRY(st.take(mean_dist ? (size_t)M : 0, &dmd));
+    TRY(st.take(inliers ? (size_t)M : 0, &dinl));
+    TRY(st.take(1, &dn));
+    TRY(st.take(4, &dstats));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_denoise(v, k, threshold, mean_dist ? dmd : nullptr, inliers ? dinl : nullptr, n_inliers ? dn : nullptr, dstats, ws, wsb, g_stream));
+    int32_t n = 0;
+    if (n_inliers) PCREG_HIP(hipMemcpyAsync(&n, dn, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    if (stats) PCREG_HIP(hipMemcpyAsync(stats, dstats, sizeof(double) * 4, hipMemcpyDeviceToHost, g_stream));
+    if (mean_dist) PCREG_HIP(hipMemcpyAsync(mean_dist, dmd, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));                   // the count fixes how many rows come back
+    if (inliers && n > 0) {
+        PCREG_HIP(hipMemcpyAsync(inliers, dinl, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipStreamSynchronize(g_stream));
+    }
+    if (n_inliers) *n_inliers = n;
+    return PCREG_OK;
+}
+int pcreg_model_denoise_f32(pcreg_model* model, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers, double* stats) {
+    PCREG_ARG(model && k >= 1 && k <= kKnnMaxK - 1 && std::isfinite(threshold) && threshold >= 0.0 && (n_inliers || !inliers));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return denoise_on_view(st, model->dm->v, k, threshold, mean_dist, inliers, n_inliers, stats);
+}
+int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers,
+                            double* stats) {
+    PCREG_ARG(M >= 0 && ldm >= M && k >= 1 && k <= kKnnMaxK - 1 && std::isfinite(threshold) && threshold >= 0.0 && (M == 0 || m) &&
+              (n_inliers || !inliers));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return denoise_on_view(st, v, k, threshold, mean_dist, inliers, n_inliers, stats);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -237,6 +237,11 @@ int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* 
 size_t normals_ws_bytes(int M, int k);
 int launch_model_normals(const ModelView& v, int k, const double* viewpoint, float* normals, int ldn, float* variation, void* ws,
                          size_t ws_bytes, hipStream_t st);
+// statistical outlier removal over the model's own rows (knn_denoise.hip): mean_dist [M] by ORIGINAL row, inliers
+// [<= M] ascending with n_inliers, stats [4] = thr, mu, sd, nf -- device pointers, each may be null (inliers needs n_inliers)
+size_t denoise_ws_bytes(int M, int k);
+int launch_model_denoise(const ModelView& v, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers, double* stats,
+                         void* ws, size_t ws_bytes, hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

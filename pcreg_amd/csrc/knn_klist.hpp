@@ -1,4 +1,4 @@
-// pcreg_amd/csrc/knn_klist.hpp -- the k-list of the exact k-nearest walks (knn_k.hip, knn_normals.hip): a sorted list of KB
+// pcreg_amd/csrc/knn_klist.hpp -- the k-list of the exact k-nearest walks (knn_k.hip, knn_normals.hip, knn_denoise.hip): a sorted list of KB
 // (distance, row) pairs in registers, ordered by (distance, row) with the empty entry (-1) last; insertion, the k-th entry,
 // and the merge with a partner lane's list.
 #pragma once
@@ -52,6 +52,41 @@ __device__ __forceinline__ void klist_merge_xor(float (&ld)[KB], int (&li)[KB], 
             }
         }
     }
+}
+
+// The same two on distances ALONE, for a walk that needs the multiset of the k smallest distances and not their rows
+// (knn_denoise.hip): half the list registers; equal distances are interchangeable, so no tie rule is needed.
+template <int KB>
+__device__ __forceinline__ void klist_insert(float (&ld)[KB], float d) {
+    float x = d;
+#pragma unroll
+    for (int s = 0; s < KB; ++s) {
+        const float lo = fminf(x, ld[s]), hi = fmaxf(x, ld[s]);
+        ld[s] = lo; x = hi;
+    }
+}
+// a bitonic list into ascending order: the half-cleaner cascade
+template <int KB>
+__device__ __forceinline__ void klist_sort_bitonic(float (&ld)[KB]) {
+#pragma unroll
+    for (int h = KB / 2; h > 0; h >>= 1) {
+#pragma unroll
+        for (int s = 0; s < KB; ++s) {
+            if ((s & h) == 0) {
+                const float a = fminf(ld[s], ld[s + h]), b = fmaxf(ld[s], ld[s + h]);
+                ld[s] = a; ld[s + h] = b;
+            }
+        }
+    }
+}
+template <int KB>
+__device__ __forceinline__ void klist_merge_xor(float (&ld)[KB], int o) {
+    float od[KB];
+#pragma unroll
+    for (int s = 0; s < KB; ++s) od[s] = __shfl_xor(ld[s], o);
+#pragma unroll
+    for (int s = 0; s < KB; ++s) ld[s] = fminf(ld[s], od[KB - 1 - s]);
+    klist_sort_bitonic<KB>(ld);
 }
 
 }  // namespace

@@ -3,7 +3,7 @@
 //
 // The prepared model (knn_fast.hip) is used as it is: the sorted fp32 copy, perm, the tile boxes.  The queries are the sorted
 // copy itself, so there is no query order and no limit on M.  A call is two launches:
-//   N1  normals_seed_kernel      one wave per sorted row: the k-th smallest distance over the window of 64 consecutive sorted
+//   N1  normals_seed_kernel      (knn_selfjoin.hpp) one wave per sorted row: the k-th smallest distance over the window of 64 consecutive sorted
 //                                rows around it (k distinct finite rows lie within that distance: an upper bound of the true
 //                                k-th distance; fewer than k finite rows leave +inf).  A non-finite row gets 0: it admits nothing
 //   N2  normals_walk_kernel<KB>  cluster_walk_kernel's shape with knn_k_kernel's body: workgroup (tile a, part p) owns 64 sorted
@@ -14,10 +14,7 @@
 //                                the model's own array and computes mean, sums, Jacobi, sign in double, all four lanes alike
 //                                (no lane waits for another, nothing is shared), and lane 0 stores to the original-row slot
 // Nothing is added across threads: the result is a function of (model rows, k, viewpoint) alone.
-#include "common.hpp"
-#include "knn_fast_common.hpp"
-#include "knn_walk.hpp"
-#include "knn_klist.hpp"
+#include "knn_selfjoin.hpp"
 #include "wave_math.hpp"
 #include <cmath>
 
@@ -25,55 +22,7 @@ namespace pcreg {
 
 namespace {
 
-constexpr int kNKnnMaxK = PCREG_KNN_MAX_K;
-constexpr int kNSeedWin = 64;                        // sorted rows the seed bound looks at (one per lane of a wave)
-constexpr int kNWgPerTile = kT16 / kWalkQPerWg;      // 8 workgroups per tile a, 64 of its rows each
-static_assert(kNKnnMaxK <= kNSeedWin, "the seed window holds at least k rows");
-
-__device__ __forceinline__ bool nfinite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
-}
-
-// The k-th entry of a sorted list, as klist_kth gives it: the smallest entry at or behind place k - 1.  klist_kth's chain of
-// selects between list entries is folded by the compiler into ONE load at a computed address, which keeps the whole list in
-// memory (LDS up to KB = 8, 80 / 144 bytes of scratch at KB = 16 / 32); a select against a constant cannot be folded that way.
-template <int KB>
-__device__ __forceinline__ float klist_kth_reg(const float (&ld)[KB], int k) {
-    float v = INFINITY;
-#pragma unroll
-    for (int s = 0; s < KB; ++s) v = fminf(v, s >= k - 1 ? ld[s] : INFINITY);
-    return v;
-}
-
-// ---- N1. seed bound: one wave per sorted row -------------------------------------------------------------------------
-// The window: 64 consecutive sorted rows centred on the row, clamped into [0, M); it holds the row itself.  Its k-th smallest
-// distance (bitonic sort across the wave) bounds the true k-th distance from above; a NaN or infinite distance (a non-finite
-// row of the window) counts as +inf, so the bound never shrinks below a finite row's distance.
-__global__ __launch_bounds__(kBlock) void normals_seed_kernel(const float* __restrict__ ms, int M, int k, float* __restrict__ dk) {
-    const int lane = threadIdx.x & 63;
-    const long long sr = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (sr >= M) return;                                        // (wave-uniform)
-    const float qx = ms[sr], qy = ms[sr + (size_t)M], qz = ms[sr + 2 * (size_t)M];
-    int w0 = (int)sr - kNSeedWin / 2;
-    w0 = min(w0, M - kNSeedWin); w0 = max(w0, 0);
-    const int r = w0 + lane;
-    float d = INFINITY;
-    if (r < M) {
-        d = point_d2(qx, qy, qz, ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M]);
-        if (!(d == d)) d = INFINITY;
-    }
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const float o = __shfl_xor(d, stride);
-            const bool up = (lane & size) == 0, lower = (lane & stride) == 0;
-            d = (lower == up) ? fminf(d, o) : fmaxf(d, o);
-        }
-    }
-    const float v = __shfl(d, k - 1);
-    if (lane == 0) dk[sr] = nfinite3(qx, qy, qz) ? v : 0.0f;
-}
+// N1, normals_seed_kernel, and the helpers shared with the denoising walk live in knn_selfjoin.hpp.
 
 // ---- N2. the walk and the normal ---------------------------------------------------------------------------------------
 // A row enters a list only when d <= thr, thr = min(seed, the k-th entry of any of the row's four lists), each of which bounds
@@ -87,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void normals_walk_kernel(const float* __res
                                                               float* __restrict__ variation, unsigned long long* __restrict__ stats) {
     __shared__ WalkLds lds;
     __shared__ float s_red[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int ta = blockIdx.x / kNWgPerTile, part = blockIdx.x % kNWgPerTile;
     if (stats && blockIdx.x == 0 && tid == 0) {
         atomicAdd(&stats[0], 1ull);
@@ -97,19 +46,7 @@ __global__ __launch_bounds__(kBlock) void normals_walk_kernel(const float* __res
     float abox[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
-    float D = 0.0f;
-    for (int r = tid; r < kT16; r += kBlock) {
-        const long long s = (long long)ta * kT16 + r;
-        if (s < M) {
-            const float e = dk[s];
-            D = e < INFINITY ? fmaxf(D, e) : INFINITY;            // +inf (or NaN): no bound, culling off for the block
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) D = fmaxf(D, __shfl_xor(D, o));
-    if (lane == 0) s_red[wave] = D;
-    __syncthreads();
-    D = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    const float D = selfjoin_tile_bound(dk, ta, M, s_red);
     // this thread's row
     const int rl = part * kWalkQPerWg + tid / kWalkLanes;         // the row's place inside tile a
     const long long srow = (long long)ta * kT16 + rl;

@@ -8,6 +8,7 @@ contiguous tensors, i.e. MATLAB's column-major N x 3 with ld = N.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -321,6 +322,40 @@ class PreparedModel:
                 check(lib().pcreg_dev_model_normals_f32(self.handle, k, vp, _p(nrm), max(int(nrm.stride(0)), M), _p(var) if var is not None else None,
                                                         _p(ws), ws.numel(), _stream()))
         return (nrm, var) if variation else nrm
+
+    def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
+        """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
+        (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]
+        float64 by ORIGINAL row; inliers, an [M] int32 tensor whose first n_inliers [1] int32 entries are the 0-based rows with
+        mean_dist <= thr, ascending (the rest is not written); stats [4] float64 = thr, mean, std, n_finite, also under the
+        names thr, mean, std and n_finite as views of it.  Nothing synchronises: the caller reads n_inliers when it needs it.
+        The workspace is cached on the model and grown on demand; calls that may overlap on two streams pass buffers of their
+        own, out=(mean_dist, inliers, n_inliers, stats, ws) with ws of pcreg_dev_model_denoise_workspace(M, k) bytes."""
+        k, threshold = int(k), float(threshold)
+        if not 1 <= k <= _l.KNN_MAX_K - 1:
+            raise ValueError(f"k (NumNeighbors) must lie in [1, {_l.KNN_MAX_K - 1}], got {k}")
+        if not (math.isfinite(threshold) and threshold >= 0.0):
+            raise ValueError(f"threshold must be a finite number >= 0, got {threshold}")
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_denoise_workspace(M, k)), 256)
+        if out is not None:
+            md, inl, n_inl, stats, ws = out
+        else:
+            md = torch.empty(M, dtype=torch.float64, device=dev)
+            inl = torch.empty(M, dtype=torch.int32, device=dev)
+            n_inl = torch.empty(1, dtype=torch.int32, device=dev)
+            stats = torch.empty(4, dtype=torch.float64, device=dev)
+            ws = getattr(self, "_denoise_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._denoise_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda t: _p(t) if t is not None and t.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_denoise_f32(self.handle, k, threshold, opt(md), opt(inl), opt(n_inl), opt(stats), _p(ws), ws.numel(),
+                                                    _stream()))
+        res = dict(mean_dist=md, inliers=inl, n_inliers=n_inl, stats=stats)
+        if stats is not None:
+            res.update(thr=stats[0], mean=stats[1], std=stats[2], n_finite=stats[3])
+        return res
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
