@@ -1071,7 +1071,16 @@ struct StagedArgs {
     int32_t* perm;               // [n32]
     unsigned char* bkt;          // [n32]
     void* bctr;                  // BCtr
+#ifdef PCREG_EXPERIMENTS
+    int noband;                  // PCREG_RANSAC_NOBAND=1, TIMING ONLY (wrong counts): the screen's band branch never runs -- what the
+                                 // fp64 re-scores cost in rs_score32 / rs_bprep / rs_bounded is the difference to a run without it
+#endif
 };
+#ifdef PCREG_EXPERIMENTS
+#define PCREG_NOBAND(sa) ((sa).noband != 0)
+#else
+#define PCREG_NOBAND(sa) false
+#endif
 
 __device__ __forceinline__ int staged_n(const RansacArgs& a) { return min(a.n_dev ? *a.n_dev : a.n_cap, a.n_cap); }
 // the registration's origin (ransac_origin), left in sa.bounds[4 .. 9] by rs_stage1_kernel for every later stage
@@ -1452,8 +1461,14 @@ __device__ __forceinline__ float sqdist32(const float (&p)[6], const float (&T)[
 }
 
 // rs_score_kernel with the fp32 screen in front: same grid, same partial counts, same masks.  No branch per slot:
-// the eight slots of a hypothesis are screened straight through, the "somebody is in the band" masks are OR-ed,
-// and only then does the wave decide whether to redo the hypothesis in fp64.
+// the eight slots of a hypothesis are screened straight through, "somebody of slot s is in the band" (the two ballots of the
+// slot differ) goes into bit s of a scalar mask, and only then does the wave decide whether anything is redone in fp64.
+// A band hit (5 % of the units on the benchmark) costs one trip of a rolled loop per SET BIT (one slot in 180): the six raw
+// fp64 coordinates of the slot in one round trip, one fp64 sqdist, one ballot, selected into b[s].  Until 2026-10-19 the loop
+// walked all eight slots and found the band slots again by re-reading each slot's fp32 row and repeating its sqdist32 and
+// both ballots: 119 instructions and a dependent round trip per trip, eight trips a hit, against 72 per band slot now
+// (172.9 -> 151.9 us per pass at the benchmark's shape; with the band branch compiled out, PCREG_RANSAC_NOBAND, 148.5).
+// The fp32 row's SGPRs are dead inside the loop, so T64's scalar load reuses them (SGPR spills 31 -> 8).
 typedef int rs_i32x16 __attribute__((ext_vector_type(16)));
 template <bool EMIT>
 __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, const double* __restrict__ TT,
@@ -1499,29 +1514,24 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
             float T[12];                                                                                           \
             _Pragma("unroll") for (int k = 0; k < 12; ++k) { const int w_ = R[k]; T[k] = __int_as_float(w_); }                 \
             const int wlo_ = R[12], whi_ = R[13]; const float thlo = __int_as_float(wlo_), thhi = __int_as_float(whi_);          \
-            unsigned long long b[kSS], band = 0ull;                                                                \
+            unsigned long long b[kSS]; unsigned band = 0u;                                                         \
             _Pragma("unroll") for (int s = 0; s < kSS; ++s) {                                                      \
                 const float d = sqdist32(q[s], T);                                                                 \
                 b[s] = __ballot(d < thlo);                                                                         \
-                band |= __ballot(d <= thhi) ^ b[s];     /* nested sets: they differ iff somebody is in the band */  \
+                band |= (__ballot(d <= thhi) ^ b[s]) != 0ull ? 1u << s : 0u;   /* nested sets: they differ iff somebody of slot s is in the band */ \
             }                                                                                                      \
-            if (band != 0ull) {      /* 5 % of the (hypothesis, 512 correspondences) units on the benchmark: the SLOTS with somebody in */ \
-                double T64[12];      /* the band (one in 180) again, fp64 on the raw coordinates -- round 2 redid all eight.  The loop stays  */ \
-                _Pragma("unroll") for (int k = 0; k < 12; ++k) T64[k] = TT[(size_t)(H) * 12 + k];   /* rolled (unrolled, its eight branches */ \
-                _Pragma("unroll 1") for (int s = 0; s < kSS; ++s) {      /* pushed the kernel from 75 to 171 VGPRs), so a slot's fp32 values are */ \
-                    const int i = ibase + s * 64;                        /* read again rather than indexed out of q[][] with a runtime s         */ \
+            if (band != 0u && !PCREG_NOBAND(sa)) {      /* 5 % of the (hypothesis, 512 correspondences) units on the benchmark: the SLOTS with somebody in */ \
+                double T64[12];      /* the band (one in 180) again, fp64 on the raw coordinates.  The screen's own ballots say which slots: bit s of */ \
+                _Pragma("unroll") for (int k = 0; k < 12; ++k) T64[k] = TT[(size_t)(H) * 12 + k];   /* `band`.  The loop walks the set bits only, rolled */ \
+                _Pragma("unroll 1") for (unsigned m = band; m != 0u; m &= m - 1u) {    /* (unrolled, its eight branches pushed the kernel from 75 to  */ \
+                    const int s = __builtin_ctz(m);                      /* 171 VGPRs); a trip needs nothing of the slot's fp32 row: six fp64 loads in */ \
+                    const int i = ibase + s * 64;                        /* one round trip, one sqdist, one ballot                                      */ \
                     const bool act = i < n;                                                                        \
                     const int ii = act ? i : 0;                                                                    \
-                    float qq[6];                                                                                   \
-                    _Pragma("unroll") for (int c = 0; c < 6; ++c) qq[c] = sa.c32[(size_t)c * sa.n32 + ii];         \
-                    if (!act) qq[0] = __builtin_nanf("");                                                          \
-                    const float d = sqdist32(qq, T);                                                               \
-                    if ((__ballot(d <= thhi) ^ __ballot(d < thlo)) != 0ull) {                /* wave-uniform */     \
-                        double p[6];                                                                               \
-                        _Pragma("unroll") for (int c = 0; c < 3; ++c) { p[c] = a.p1[ii + (size_t)c * a.ld]; p[3 + c] = a.p2[ii + (size_t)c * a.ld]; } \
-                        const unsigned long long bb = __ballot((sqdist(p, T64) < th) & act);                       \
-                        _Pragma("unroll") for (int s2 = 0; s2 < kSS; ++s2) if (s2 == s) b[s2] = bb;                \
-                    }                                                                                              \
+                    double p[6];                                                                                   \
+                    _Pragma("unroll") for (int c = 0; c < 3; ++c) { p[c] = a.p1[ii + (size_t)c * a.ld]; p[3 + c] = a.p2[ii + (size_t)c * a.ld]; } \
+                    const unsigned long long bb = __ballot((sqdist(p, T64) < th) & act);                           \
+                    _Pragma("unroll") for (int s2 = 0; s2 < kSS; ++s2) if (s2 == s) b[s2] = bb;                    \
                 }                                                                                                  \
             }                                                                                                      \
             int cnt = 0;                                                                                           \
@@ -1603,7 +1613,14 @@ __device__ __forceinline__ int rs_block_count(const StagedArgs& sa, const float*
         b[s] = __ballot(d < thlo);
         band |= __ballot(d <= thhi) ^ b[s];
     }
-    if (band != 0ull) {                                  // wave-uniform; the rolled loop as in rs_score32_kernel
+    // wave-uniform.  The rolled loop still walks all eight slots and re-reads each slot's fp32 row to find the band slots, as
+    // rs_score32_kernel did until 2026-10-19.  Walking only the set bits of a per-slot mask was tried here in three forms (mask
+    // built in the screen; the eight xor words kept and the mask built after a hit; the mask recomputed from q[][] after a
+    // hit) and measured on the serial line: rs_bounded_kernel 97.6 - 102.0 us in every form against 90.7 - 92.5, rs_bprep_kernel
+    // unchanged (23.0 - 23.7 -> 23.2 - 24.3).  Not kept: the bounded walk is one wave per SIMD running this screen once per
+    // (refit, block), hit or not; the screen grew in every form (130 -> 133 / 156 instructions) and hits are too rare there to
+    // pay that back (docs/BENCH_NOTES.md, 2026-10-19).
+    if (band != 0ull && !PCREG_NOBAND(sa)) {
         double T64[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) T64[k] = a.TF[(size_t)h * 12 + k];
@@ -3408,6 +3425,9 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         sel_ctr = sa.sel_ctr;
         sa.use_lane = a.refine && !debug_flag(kDbgRansacNoLane);
         sa.use_f32 = !debug_flag(kDbgRansacF64Score);
+#ifdef PCREG_EXPERIMENTS
+        sa.noband = PCREG_EXP_ENV("PCREG_RANSAC_NOBAND", 0);
+#endif
         int pb = (n_cap + kSPts - 1) / kSPts; if (pb > kSMaxPB) pb = kSMaxPB; if (pb < 1) pb = 1;
         sa.pb = pb;
         int hpw = (int)((total + 250LL * kTW - 1) / (250LL * kTW));
