@@ -372,6 +372,48 @@ int pcreg_model_denoise_f32(pcreg_model* model, int k, double threshold, double*
  * ldm < M, m NULL with M > 0. */
 int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double threshold, double* mean_dist, int32_t* inliers,
                             int32_t* n_inliers, double* stats);
+/* The FPFH descriptor of every row of the model (MATLAB's extractFPFHFeatures(ptCloud, 'NumNeighbors', k)): 33 numbers a row from
+ * its k nearest rows and a normal per row.  The name and the pair features are Rusu's (Fast Point Feature Histograms, ICRA 2009);
+ * the weighting and the normalisation have the form common implementations use.  THE CONTRACT of every tier (device, host, MEX,
+ * Python) is THIS TEXT, not any library's source; MATLAB's bits are not knowable here.
+ * inputs -- a prepared model of M fp32 rows; k with 3 <= k <= PCREG_KNN_MAX_K; normals, M x 3 fp32 column-major with ldn >= M, by
+ * ORIGINAL row, exactly what pcreg_model_normals_f32 writes, used as they are (not renormalised).  Unlike the plane refit, THE SIGN
+ * of a normal matters here: orient the normals with a viewpoint.
+ * THE NEIGHBOURHOOD of row i is what pcreg_model_knn_f32 returns for query = row i with this k, in its (distance, original row)
+ * order.  The NEIGHBOURS of i are the list entries with a row and a finite fp32 squared distance d2 > 0: entries at distance 0 (the
+ * row itself, coincident rows) are not neighbours.  A row with a non-finite coordinate is never a neighbour and has no
+ * neighbourhood.  At most k - 1 <= 31 neighbours: the row itself takes a place of its list.
+ * THE PAIR (i, j), j a neighbour of i.  All arithmetic is double on the widened fp32 values, without contraction; every three-term
+ * sum is (x + y) + z; sqrt and division are correctly rounded.  d = p_j - p_i; len = sqrt((dx dx + dy dy) + dz dz);
+ * a_i = ((n_i.x dx + n_i.y dy) + n_i.z dz) / len; a_j the same with n_j.  If |a_i| < |a_j| (strictly) the source is j: ns = n_j,
+ * nt = n_i, d <- -d, f3 = -a_j; otherwise, a tie included, the source is i: ns = n_i, nt = n_j, f3 = a_i.  v = d x ns;
+ * vl = sqrt(v . v); v <- v / vl componentwise; w = ns x v; f2 = v . nt; f1 = atan2(w . nt, ns . nt).
+ * The pair CONTRIBUTES unless len or vl is not > 0, or any of f1, f2, f3 is NaN, or either normal has a non-finite component.
+ * Bins, eleven a feature: b1 = floor(11 ((f1 + pi) / (2 pi))), b2 = floor(11 ((f2 + 1) 0.5)), b3 = floor(11 ((f3 + 1) 0.5)), each
+ * clamped to 0 .. 10 (pi the double nearest to it).
+ * SPFH of row i: integer counts c_i[33], f1's eleven bins, then f2's, then f3's, over the contributing pairs; m_i their number (the
+ * sum of the first eleven counts, and of each other eleven).
+ * FPFH of row i: acc[b] = the sum over the neighbours j of i, in list order, with m_j > 0, of (c_j[b] / m_j) / d2_ij, d2_ij the
+ * list's fp32 SQUARED distance widened to double (the conventional weight: the inverse of the squared distance, as the common
+ * implementations take it); the row's own SPFH is not added.  Per feature f: S_f = the sum of its eleven acc in bin order from the
+ * first; S_f > 0: out[b] = (acc[b] / S_f) * 100 (the division first, so a histogram of one bin is exactly 100); otherwise out[b] = 0.
+ * A row with a non-finite coordinate gets 33 NaN; a row whose neighbourhood yields nothing gets 33 zeros (fewer than 2 finite
+ * distinct rows, all rows coincident).
+ * outputs -- fpfh: M x 33 double column-major with ldf >= M, by ORIGINAL row; spfh (may be NULL): the SPFH counts, uint8 [M][33]
+ * ROW-major by original row.  M = 0 writes nothing.
+ * normals == NULL: they are computed in the call by pcreg_model_normals_f32's chain with k_normals (its range) and the viewpoint
+ * (three host doubles or NULL); ldn is ignored.  normals given: they are uploaded once; k_normals and viewpoint are ignored.
+ * The result is a function of (model rows, normals, k) only: no floating-point atomic, no sum across threads; culling, the call,
+ * the stream and the workspace's previous contents change no bit.  PCREG_E_ARG, before anything runs: k outside
+ * 3 .. PCREG_KNN_MAX_K; ldn < M with normals given; k_normals outside its range with normals NULL; ldf < M; model NULL; fpfh NULL
+ * with M > 0. */
+int pcreg_model_fpfh_f32(pcreg_model* model, int k, const float* normals /* host M x 3, or NULL */, int ldn, int k_normals,
+                         const double* viewpoint /* host, 3 or NULL */, double* fpfh /* M x 33, ld ldf */, int ldf,
+                         uint8_t* spfh /* [M][33] or NULL */);
+/* The same without a handle (extractFPFHFeatures(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG:
+ * M < 0, ldm < M, m NULL with M > 0. */
+int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* normals, int ldn, int k_normals, const double* viewpoint,
+                         double* fpfh, int ldf, uint8_t* spfh);
 
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
@@ -731,6 +773,19 @@ size_t pcreg_dev_model_denoise_workspace(int M, int k);
 int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double threshold, double* mean_dist /* or NULL */,
                                 int32_t* inliers /* or NULL */, int32_t* n_inliers /* or NULL */, double* stats /* [4] or NULL */,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_fpfh_f32's contract on the device: normals_dev [3 * ldn] (what pcreg_dev_model_normals_f32 writes; may
+ * not be NULL with M > 0), fpfh [M][33] double and spfh [M][33] uint8 (or NULL) are device pointers, both ROW-major by original row
+ * -- fpfh is what pcreg_dev_get_matches takes as row-major descriptors with D = 33.  Three launches: the seed bound of every sorted
+ * row; the normals' walk, whose epilogue stores each row's list to an [M][k] table, gathers the neighbours' coordinates and normals
+ * and counts the pair features; one thread per (row, feature) that weights the neighbours' counts in list order.  Nothing
+ * synchronises; no workgroup waits for another.  Workspace, with R = max(M, 1):
+ * roundup(4 R, 256) + 2 roundup(4 R k, 256) + roundup(33 R, 256) bytes; a workspace shorter than that is PCREG_E_ARG too, and so is
+ * ldn < M.  A handle may serve several streams at once, each call with its own workspace.  The debug keys "knn_nocull" and
+ * "knn_stats" act on the walk as on the normals'. */
+size_t pcreg_dev_model_fpfh_workspace(int M, int k);
+int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* normals_dev /* [3][ldn] */, int ldn,
+                             double* fpfh /* [M][33] */, uint8_t* spfh /* [M][33] or NULL */, void* workspace, size_t workspace_bytes,
+                             void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

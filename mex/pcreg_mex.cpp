@@ -52,6 +52,16 @@
 //                                          NaN or Inf; thr = mean + threshold * std of the finite ones; a row is an inlier iff
 //                                          meanDist <= thr; the last two outputs are built only when asked for
 //                                          (matlab/pcdenoiseModel.m, matlab/pcdenoiseFast.m)
+//   'modelFpfh', handle, k, normals (single M x 3 | []), kNormals, viewpoint | 'pointFpfh', pts (single M x 3), k, normals, kNormals,
+//                                          viewpoint -> features (M x 33 double), spfh (M x 33 uint8):
+//                                          extractFPFHFeatures(ptCloud, 'NumNeighbors', k) in this library's rule -- the FPFH
+//                                          descriptor of every row from its k nearest rows (3 <= k <= 32, the row itself among
+//                                          them) and a normal per row; normals by model row as 'modelNormals' returns them (THE
+//                                          SIGN matters: orient them with a viewpoint), or [] to compute them in the call from the
+//                                          kNormals nearest rows (3 .. 32, always passed) and the viewpoint ([] or double 1 x 3,
+//                                          always passed); each of a row's three histograms adds up to 100 or is all zero, a row
+//                                          with a NaN or Inf is NaN; spfh, the integer pair counts, is built only when asked for
+//                                          (matlab/extractFPFHModel.m, matlab/extractFPFHFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -149,6 +159,34 @@ static int normals_on_handle(pcreg_model* h, int k, const mxArray* vp, bool want
                                  ov ? (float*)mxGetData(ov) : nullptr);
     if (rc == PCREG_OK) { out[0] = on; out[1] = ov; }
     else { mxDestroyArray(on); if (ov) mxDestroyArray(ov); }
+    return rc;
+}
+
+// the outputs of 'modelFpfh' / 'pointFpfh': features (M x 33 double) and, with want_spfh, the counts (M x 33 uint8; the library's
+// rows of 33 are turned into MATLAB's columns).  nrm: single M x 3 or [].  Nothing is left allocated on an error; *usage is set when
+// the normals have another number of rows than the model.
+static int fpfh_on_handle(pcreg_model* h, int k, const mxArray* nrm, int k_normals, const mxArray* vp, bool want_spfh, mxArray* out[2],
+                          const char** usage) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    const bool given = !mxIsEmpty(nrm);
+    if (given && (int)mxGetM(nrm) != M) { *usage = "Fpfh: normals must have one row per row of the cloud"; return PCREG_OK; }
+    mxArray* of = mxCreateDoubleMatrix((size_t)M, 33, mxREAL);
+    mxArray* tc = want_spfh ? mxCreateNumericMatrix(33, (size_t)(M > 0 ? M : 1), mxUINT8_CLASS, mxREAL) : nullptr;
+    rc = pcreg_model_fpfh_f32(h, k, given ? (const float*)mxGetData(nrm) : nullptr, M > 0 ? M : 1, k_normals, mxIsEmpty(vp) ? nullptr : mxGetPr(vp),
+                              mxGetPr(of), M > 0 ? M : 1, tc ? (uint8_t*)mxGetData(tc) : nullptr);
+    if (rc == PCREG_OK) {
+        out[0] = of;
+        if (tc) {
+            out[1] = mxCreateNumericMatrix((size_t)M, 33, mxUINT8_CLASS, mxREAL);
+            const uint8_t* src = (const uint8_t*)mxGetData(tc);
+            uint8_t* dst = (uint8_t*)mxGetData(out[1]);
+            for (int i = 0; i < M; ++i)
+                for (int b = 0; b < 33; ++b) dst[(size_t)i + (size_t)b * (size_t)M] = src[(size_t)i * 33 + b];
+        }
+    } else mxDestroyArray(of);
+    if (tc) mxDestroyArray(tc);
     return rc;
 }
 
@@ -709,6 +747,33 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = normals_on_handle(h, (int)mxGetScalar(prhs[2]), prhs[3], nlhs > 1, out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
+        }
+    } else if (!strcmp(cmd, "modelFpfh")) {                   // [features, spfh] = pcreg_mex('modelFpfh', h, k, normals, kNormals, viewpoint)
+        if (nrhs != 6 || !mxIsUint64(prhs[1]) || !normals_k_ok(prhs[2]) || (!mxIsEmpty(prhs[3]) && (!mxIsSingle(prhs[3]) || mxGetN(prhs[3]) != 3)) ||
+            !normals_k_ok(prhs[4]) || !viewpoint_ok(prhs[5]))
+            usage = "modelFpfh: handle (uint64), k (a whole number 3 .. 32), normals (single M x 3, or [] to compute them), kNormals (a whole number "
+                    "3 .. 32), viewpoint ([] or double 1 x 3)";
+        else {
+            mxArray* out[2] = {nullptr, nullptr};
+            rc = fpfh_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (int)mxGetScalar(prhs[2]), prhs[3], (int)mxGetScalar(prhs[4]),
+                                prhs[5], nlhs > 1, out, &usage);
+            if (usage) usage = "modelFpfh: normals must have one row per model row";
+            if (rc == PCREG_OK && !usage) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
+        }
+    } else if (!strcmp(cmd, "pointFpfh")) {                   // [features, spfh] = pcreg_mex('pointFpfh', single(pts), k, normals, kNormals, viewpoint)
+        if (nrhs != 6 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !normals_k_ok(prhs[2]) ||
+            (!mxIsEmpty(prhs[3]) && (!mxIsSingle(prhs[3]) || mxGetN(prhs[3]) != 3)) || !normals_k_ok(prhs[4]) || !viewpoint_ok(prhs[5]))
+            usage = "pointFpfh: pts (single M x 3), k (a whole number 3 .. 32), normals (single M x 3, or [] to compute them), kNormals (a whole number "
+                    "3 .. 32), viewpoint ([] or double 1 x 3)";
+        else if (!mxIsEmpty(prhs[3]) && mxGetM(prhs[3]) != mxGetM(prhs[1])) usage = "pointFpfh: normals must have one row per row of pts";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[2] = {nullptr, nullptr};
+            if (rc == PCREG_OK) rc = fpfh_on_handle(h, (int)mxGetScalar(prhs[2]), prhs[3], (int)mxGetScalar(prhs[4]), prhs[5], nlhs > 1, out, &usage);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK && !usage) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
         }
     } else if (!strcmp(cmd, "modelDenoise")) {                // [inlierIndices, meanDist, thr] = pcreg_mex('modelDenoise', h, k, threshold)
         if (nrhs != 4 || !mxIsUint64(prhs[1]) || !denoise_k_ok(prhs[2]) || !denoise_t_ok(prhs[3]))

@@ -66,6 +66,7 @@ SYMBOLS = [
     "pcreg_model_normals_f32", "pcreg_point_normals_f32", "pcreg_dev_model_normals_workspace", "pcreg_dev_model_normals_f32",
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
+    "pcreg_model_fpfh_f32", "pcreg_point_fpfh_f32", "pcreg_dev_model_fpfh_workspace", "pcreg_dev_model_fpfh_f32",
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_downsample_grid_f32", "pcreg_dev_downsample_grid_workspace", "pcreg_dev_downsample_grid_chunk", "pcreg_dev_downsample_grid_f32",
@@ -158,6 +159,13 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_denoise_f32.argtypes = [vp, i, d, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_denoise_f32.argtypes = [vp, i, d, vp, vp, vp, vp]
             L.pcreg_point_denoise_f32.argtypes = [vp, i, i, i, d, vp, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_model_fpfh_workspace"):      # (an older build given through PCREG_LIB lacks the FPFH)
+            L.pcreg_dev_model_fpfh_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_fpfh_workspace.argtypes = [C.c_int] * 2
+            vp, i = C.c_void_p, C.c_int
+            L.pcreg_dev_model_fpfh_f32.argtypes = [vp, i, vp, i, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_fpfh_f32.argtypes = [vp, i, vp, i, i, vp, vp, i, vp]
+            L.pcreg_point_fpfh_f32.argtypes = [vp, i, i, i, vp, i, i, vp, vp, i, vp]
         if hasattr(L, "pcreg_dev_model_refit_plane_workspace"):   # (an older build given through PCREG_LIB lacks the plane refit)
             L.pcreg_dev_model_refit_plane_workspace.restype = C.c_size_t
             L.pcreg_dev_model_refit_plane_workspace.argtypes = [C.c_int] * 3

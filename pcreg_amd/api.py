@@ -688,6 +688,43 @@ def point_normals(pts, k: int, viewpoint=None, variation: bool = False):
     return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_point_normals_f32(m.ctypes.data, M, max(M, 1), k, v, n, ldn, va)), M, vp, variation)
 
 
+def _fpfh_args(M: int, k, normals, k_normals, viewpoint):
+    k = int(k)
+    if not 3 <= k <= KNN_MAX_K:
+        raise ValueError(f"k (NumNeighbors) must lie in [3, {KNN_MAX_K}], got {k}")
+    if normals is not None:
+        nrm = _fcol(normals, np.float32)
+        if nrm.ndim != 2 or nrm.shape != (M, 3):
+            raise ValueError(f"normals are [M, 3] with M = {M} rows, got {nrm.shape}")
+        return k, nrm, k, None                  # (k_normals is ignored with normals given; M = 0 has no address to pass)
+    kn, vp = _normals_args(k if k_normals is None else k_normals, viewpoint)
+    return k, None, kn, vp
+
+
+def _fpfh_call(call, M: int, nrm, vp, spfh: bool):
+    out = np.zeros((max(M, 1), 33), dtype=np.float64, order="F")
+    cnt = np.zeros((max(M, 1), 33), dtype=np.uint8) if spfh else None
+    call(nrm.ctypes.data if nrm is not None and M else None, max(M, 1), vp.ctypes.data if vp is not None else None, out.ctypes.data, max(M, 1),
+         cnt.ctypes.data if spfh else None)
+    return (out[:M], cnt[:M]) if spfh else out[:M]
+
+
+def point_fpfh(pts, k: int, normals=None, k_normals=None, viewpoint=None, spfh: bool = False):
+    """extractFPFHFeatures(pts, 'NumNeighbors', k) in this library's rule (pcreg_model_fpfh_f32's contract): the 33-number FPFH
+    descriptor of every row, [M, 33] float64, from its k nearest rows (3 <= k <= 32, the row itself among them) and a normal per
+    row.  normals: [M, 3] float32 by row, as point_normals returns them -- their SIGN matters, orient them with a viewpoint; None:
+    computed in the call from the k_normals nearest rows (default k) and the viewpoint.  Each of the three histograms of a row adds
+    up to 100 (or is all zero); a non-finite row is NaN.  spfh=True also returns the SPFH counts [M, 33] uint8.  The cloud is
+    prepared for this call only: keep a Model for repeated calls."""
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    k, nrm, kn, vp = _fpfh_args(M, k, normals, k_normals, viewpoint)
+    return _fpfh_call(lambda n, ldn, v, o, ldf, c: check(lib().pcreg_point_fpfh_f32(m.ctypes.data, M, max(M, 1), k, n, ldn, kn, v, o, ldf, c)),
+                      M, nrm, vp, spfh)
+
+
 def _denoise_args(k, threshold):
     k, threshold = int(k), float(threshold)
     if not 1 <= k <= KNN_MAX_K - 1:
@@ -950,6 +987,15 @@ class Model:
             raise ValueError("the model handle is closed")
         k, vp = _normals_args(k, viewpoint)
         return _normals_call(lambda v, n, ldn, va: check(lib().pcreg_model_normals_f32(self._h, k, v, n, ldn, va)), self.M, vp, variation)
+
+    def fpfh(self, k: int, normals=None, k_normals=None, viewpoint=None, spfh: bool = False):
+        """The FPFH descriptor of every row of the prepared model from its k nearest rows and a normal per row: [M, 33] float64,
+        and with spfh=True also the SPFH counts [M, 33] uint8 -- point_fpfh's contract.  normals: what Model.normals returns
+        (oriented: the sign matters), or None to compute them in the call with k_normals (default k) and the viewpoint."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        k, nrm, kn, vp = _fpfh_args(self.M, k, normals, k_normals, viewpoint)
+        return _fpfh_call(lambda n, ldn, v, o, ldf, c: check(lib().pcreg_model_fpfh_f32(self._h, k, n, ldn, kn, v, o, ldf, c)), self.M, nrm, vp, spfh)
 
     def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
         """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold

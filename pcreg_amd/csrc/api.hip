@@ -430,6 +430,14 @@ int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double thre
     GUARD();
     return launch_model_denoise(model->v, k, threshold, mean_dist, inliers, n_inliers, stats, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_fpfh_workspace(int M, int k) { return fpfh_ws_bytes(M, k); }
+int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* normals, int ldn, double* fpfh, uint8_t* spfh, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && k >= 3 && k <= kKnnMaxK && ldn >= model->v.M && ((normals && fpfh) || model->v.M == 0));
+    PCREG_ARG(workspace_bytes >= fpfh_ws_bytes(model->v.M, k));
+    GUARD();
+    return launch_model_fpfh(model->v, k, normals, ldn, fpfh, spfh, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -851,6 +859,54 @@ int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double thresh
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return denoise_on_view(st, v, k, threshold, mean_dist, inliers, n_inliers, stats);
+}
+
+// FPFH of a prepared model's own rows: the normals uploaded once (or computed by the normals chain with k_normals and the
+// viewpoint), the chain on the device, ONE read of the [M][33] block (and the counts), transposed into the caller's columns
+static int fpfh_on_view(Stage& st, const ModelView& v, int k, const float* normals, int ldn, int k_normals, const double* viewpoint, double* fpfh,
+                        int ldf, uint8_t* spfh) {
+    const int M = v.M;
+    if (M == 0) return PCREG_OK;
+    float* dn; double* dout; uint8_t* dsp; char *ws, *nws;
+    const size_t wsb = fpfh_ws_bytes(M, k), nwsb = normals ? 0 : normals_ws_bytes(M, k_normals), n33 = 33 * (size_t)M;
+    TRY(st.take(3 * (size_t)M, &dn));
+    TRY(st.take(n33, &dout));
+    TRY(st.take(spfh ? n33 : 0, &dsp));
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(nwsb, &nws));
+    if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
+    else TRY(launch_model_normals(v, k_normals, viewpoint, dn, M, nullptr, nws, nwsb, g_stream));
+    TRY(launch_model_fpfh(v, k, dn, M, dout, spfh ? dsp : nullptr, ws, wsb, g_stream));
+    std::vector<double> host(n33);
+    PCREG_HIP(hipMemcpyAsync(host.data(), dout, sizeof(double) * n33, hipMemcpyDeviceToHost, g_stream));
+    if (spfh) PCREG_HIP(hipMemcpyAsync(spfh, dsp, n33, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    for (int b = 0; b < 33; ++b)
+        for (int i = 0; i < M; ++i) fpfh[(size_t)i + (size_t)b * (size_t)ldf] = host[(size_t)i * 33 + b];
+    return PCREG_OK;
+}
+int pcreg_model_fpfh_f32(pcreg_model* model, int k, const float* normals, int ldn, int k_normals, const double* viewpoint, double* fpfh, int ldf,
+                         uint8_t* spfh) {
+    PCREG_ARG(model && k >= 3 && k <= kKnnMaxK && ldf >= model->M && (fpfh || model->M == 0));
+    PCREG_ARG(normals ? ldn >= model->M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return fpfh_on_view(st, model->dm->v, k, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh);
+}
+int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* normals, int ldn, int k_normals, const double* viewpoint,
+                         double* fpfh, int ldf, uint8_t* spfh) {
+    PCREG_ARG(M >= 0 && ldm >= M && k >= 3 && k <= kKnnMaxK && ldf >= M && (M == 0 || (m && fpfh)));
+    PCREG_ARG(normals ? ldn >= M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return fpfh_on_view(st, v, k, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -242,6 +242,11 @@ int launch_model_normals(const ModelView& v, int k, const double* viewpoint, flo
 size_t denoise_ws_bytes(int M, int k);
 int launch_model_denoise(const ModelView& v, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers, double* stats,
                          void* ws, size_t ws_bytes, hipStream_t st);
+// the FPFH descriptor of every model row from its k nearest rows and a normal per row (knn_fpfh.hip): normals [3][ldn]
+// on the device by ORIGINAL row; fpfh [M][33] doubles and spfh [M][33] uint8 counts (or null), row-major by ORIGINAL row
+size_t fpfh_ws_bytes(int M, int k);
+int launch_model_fpfh(const ModelView& v, int k, const float* normals, int ldn, double* fpfh, uint8_t* spfh, void* ws, size_t ws_bytes,
+                      hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

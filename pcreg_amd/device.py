@@ -323,6 +323,40 @@ class PreparedModel:
                                                         _p(ws), ws.numel(), _stream()))
         return (nrm, var) if variation else nrm
 
+    def fpfh(self, k: int, normals: torch.Tensor, spfh: bool = False, out=None):
+        """The FPFH descriptor of every row of the model from its k nearest rows (3 <= k <= 32) and a normal per row, on torch's
+        current stream (pcreg_dev_model_fpfh_f32; the contract is pcreg_model_fpfh_f32's): normals the [3, M] float32 tensor
+        PreparedModel.normals returns (by ORIGINAL row; THE SIGN matters: orient them with a viewpoint) -> fpfh, an [M, 33] float64
+        tensor, row-major by ORIGINAL row (what pcreg_dev_get_matches takes as row-major descriptors), and with spfh=True (fpfh,
+        counts [M, 33] uint8).  A non-finite row is NaN.  Nothing synchronises.  The workspace is cached on the model and grown on
+        demand; calls that may overlap on two streams pass buffers of their own, out=(fpfh, counts, ws) with ws of
+        pcreg_dev_model_fpfh_workspace(M, k) bytes (counts None when not wanted)."""
+        k = int(k)
+        if not 3 <= k <= _l.KNN_MAX_K:
+            raise ValueError(f"k (NumNeighbors) must lie in [3, {_l.KNN_MAX_K}], got {k}")
+        dev, M = self.tensor.device, self.M
+        if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
+                or normals.device != dev):
+            raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the model's device (the row stride is the leading dimension)")
+        need = max(int(lib().pcreg_dev_model_fpfh_workspace(M, k)), 256)
+        if out is not None:
+            desc, cnt, ws = out
+            if desc.dtype != torch.float64 or desc.shape != (M, 33) or not desc.is_contiguous():
+                raise TypeError("fpfh is a contiguous [M, 33] float64 tensor")
+            if cnt is not None and (cnt.dtype != torch.uint8 or cnt.shape != (M, 33) or not cnt.is_contiguous()):
+                raise TypeError("the SPFH counts are a contiguous [M, 33] uint8 tensor")
+        else:
+            desc = torch.empty((M, 33), dtype=torch.float64, device=dev)
+            cnt = torch.empty((M, 33), dtype=torch.uint8, device=dev) if spfh else None
+            ws = getattr(self, "_fpfh_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fpfh_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if M:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                check(lib().pcreg_dev_model_fpfh_f32(self.handle, k, _p(normals), max(int(normals.stride(0)), M), _p(desc),
+                                                     _p(cnt) if cnt is not None else None, _p(ws), ws.numel(), _stream()))
+        return (desc, cnt) if spfh else desc
+
     def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
         """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
         (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]
