@@ -414,6 +414,45 @@ int pcreg_model_fpfh_f32(pcreg_model* model, int k, const float* normals /* host
  * M < 0, ldm < M, m NULL with M > 0. */
 int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* normals, int ldn, int k_normals, const double* viewpoint,
                          double* fpfh, int ldf, uint8_t* spfh);
+/* ISS keypoints of the rows of the model (MATLAB's detectISSFeatures(ptCloud, 'SalientRadius', rs, 'NonMaxRadius', rn, 'Threshold21',
+ * g21, 'Threshold32', g32, 'MinNeighbors', n); Zhong's Intrinsic Shape Signatures, ICCV Workshops 2009; PCL's ISSKeypoint3D, Open3D's
+ * compute_iss_keypoints).  THE CONTRACT of every tier (device, host, MEX, Python) is THIS TEXT, not any library's
+ * source; MATLAB's bits are not knowable here.
+ * inputs -- a prepared model of M fp32 rows, M < 2^26; r2_salient and r2_nonmax, SQUARED radii as floats, each finite, normal and
+ * > 0 (a wrapper that takes radii squares them in double and rounds the square once to single); gamma21 and gamma32, finite doubles
+ * > 0; min_neighbors >= 1.
+ * THE NEIGHBOURHOOD of row i at r2 is every row j, i itself included, with d = fmaf(dz, dz, fmaf(dy, dy, dx*dx)) <= r2, dx = m_j - m_i
+ * in fp32: the predicate of pcreg_model_range_f32 and pcreg_model_cluster_f32, inclusive, and NaN never passes.  A row with a
+ * non-finite coordinate is in no neighbourhood and has none: its n = 0, its eigenvalues are NaN, its saliency is 0.
+ * THE EXACT SCATTER.  Let e2 be the binary exponent of r2_salient (frexp: r2 = f 2^e2, f in [0.5, 1)) and e = ceil(e2 / 2).  Per
+ * neighbour and component q = rint(dx 2^(18 - e)), round-to-nearest-even of the exactly scaled fp32 difference, so |q| <= 2^18 + 1.
+ * Over the neighbourhood n, S1[3] = sum q and S2[6] = sum q_a q_b are integers, summed exactly in 64 bits (M < 2^26 keeps them
+ * there).  N = n S2 - S1 S1^T is formed exactly and each of its six entries is rounded ONCE to double.  Nothing here depends on the
+ * order of summation.
+ * THE EIGENVALUES.  mu1 >= mu2 >= mu3 are the eigenvalues of N in double by cyclic Jacobi, sorted.  Reported:
+ * lambda_c = (mu_c / (double)(n n)) * 4^-(18 - e), in that order of operations -- the eigenvalues of the covariance about the
+ * neighbourhood's mean, in the model's units.
+ * THE CANDIDATE.  Row i is a candidate iff n >= min_neighbors and mu2 < gamma21 * mu1 and mu3 < gamma32 * mu2 and mu3 > 0 (products
+ * in double, no division).  Saliency s_i = lambda_3 for a candidate, else 0.  A neighbourhood in a coordinate plane or on a
+ * coordinate axis gives mu3 == 0 exactly: the integer sums have exact zeros there.
+ * THE KEYPOINT.  Row i is a keypoint iff s_i > 0 and no row j != i of its r2_nonmax neighbourhood has s_j > s_i, or s_j == s_i with
+ * j < i (original rows).  Coincident rows are neighbours of each other.  A caller restates the list to the bit from the returned
+ * saliencies and the fp32 predicate.
+ * outputs -- n_neighbors [M] int32; eig [M][3] double ROW-major, descending (may be NULL); saliency [M] double; keypoints [capacity
+ * M]: the 0-based original rows of the keypoints, ascending, *n_keypoints of them (keypoints given needs n_keypoints; n_keypoints
+ * alone counts; both NULL skips the suppression).  M = 0 writes *n_keypoints = 0 and nothing else.
+ * The result is a function of (model rows, parameters) only: the in-cell order of the prepared model, culling, the call, the stream
+ * and the workspace's previous contents change no bit, and a permutation of the rows permutes the per-row outputs.
+ * PCREG_E_ARG, before anything runs: a radius that is zero, negative, subnormal, infinite or NaN; a gamma that is not finite or not
+ * > 0; min_neighbors < 1; M >= 2^26; model NULL; n_neighbors or saliency NULL with M > 0; keypoints without n_keypoints. */
+int pcreg_model_iss_f32(pcreg_model* model, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
+                        int32_t* n_neighbors /* [M] */, double* eig /* [M][3] or NULL */, double* saliency /* [M] */,
+                        int32_t* keypoints /* [M] or NULL */, int32_t* n_keypoints /* or NULL */);
+/* The same without a handle (detectISSFeatures(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG:
+ * M < 0, ldm < M, m NULL with M > 0. */
+int pcreg_point_iss_f32(const float* m, int M, int ldm, float r2_salient, float r2_nonmax, double gamma21, double gamma32,
+                        int min_neighbors, int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints,
+                        int32_t* n_keypoints);
 
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
@@ -786,6 +825,20 @@ size_t pcreg_dev_model_fpfh_workspace(int M, int k);
 int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* normals_dev /* [3][ldn] */, int ldn,
                              double* fpfh /* [M][33] */, uint8_t* spfh /* [M][33] or NULL */, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* pcreg_model_iss_f32's contract on the device: n_neighbors [M], eig [M][3] (or NULL), saliency [M], keypoints [M] and
+ * n_keypoints (one int32) are device pointers, NULL as there.  Four launches: the self-join walk over all tiles with the integer
+ * scatter, whose epilogue finishes each row's eigenvalues and saliency itself; the same walk at r2_nonmax over the rows with a
+ * saliency, a flag byte per row; the two launches of the chunk scan that list the flagged rows ascending (the last three skipped
+ * without n_keypoints).  Tiles are skipped by DESIGN 4.1's rule with D = the squared radius and the box of the workgroup's tile.
+ * Nothing synchronises; no workgroup waits for another.  Workspace, with R = max(M, 1) and C = max(ceil(M / 2048), 1):
+ * roundup(R, 256) + roundup(4 C, 256) bytes; a workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams
+ * at once, each call with its own workspace.  The debug keys "knn_nocull" and "knn_stats" act on both walks as on the normals'
+ * (each walk counts as one search of n_tiles^2 nominal visits). */
+size_t pcreg_dev_model_iss_workspace(int M);
+int pcreg_dev_model_iss_f32(const pcreg_dev_model* model, float r2_salient, float r2_nonmax, double gamma21, double gamma32,
+                            int min_neighbors, int32_t* n_neighbors, double* eig /* or NULL */, double* saliency,
+                            int32_t* keypoints /* or NULL */, int32_t* n_keypoints /* or NULL */, void* workspace,
+                            size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

@@ -62,6 +62,14 @@
 //                                          always passed); each of a row's three histograms adds up to 100 or is all zero, a row
 //                                          with a NaN or Inf is NaN; spfh, the integer pair counts, is built only when asked for
 //                                          (matlab/extractFPFHModel.m, matlab/extractFPFHFast.m)
+//   'modelIss', handle, r2Salient, r2NonMax, threshold21, threshold32, minNeighbors | 'pointIss', pts (single M x 3), r2Salient, ... ->
+//                                          keypoints (n x 1 uint32, 1-based, ascending), saliency (M x 1 double), eig (M x 3 double,
+//                                          descending along a row), nNeighbors (M x 1 int32): detectISSFeatures(ptCloud, ...) in this
+//                                          library's rule (pcreg_model_iss_f32) -- r2Salient and r2NonMax are single scalars, the
+//                                          SQUARED radii (the wrappers square the radius in double and round once: single(r^2));
+//                                          threshold21 / threshold32 finite doubles > 0; minNeighbors a whole number >= 1; all
+//                                          always passed; the last three outputs are built only when asked for
+//                                          (matlab/detectISSModel.m, matlab/detectISSFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -218,6 +226,55 @@ static int denoise_on_handle(pcreg_model* h, int k, double t, int nout, mxArray*
         if (nout > 2) out[2] = mxCreateDoubleScalar(stats[0]);
     } else if (om) mxDestroyArray(om);
     mxDestroyArray(ti);
+    return rc;
+}
+
+// the parameters of the ISS commands, prhs[0 .. 4]: two single scalars (finite, normal, > 0), two double scalars (finite, > 0), a
+// whole double >= 1
+static bool iss_args_ok(const mxArray* const* a) {
+    for (int i = 0; i < 2; ++i) {
+        if (!mxIsSingle(a[i]) || mxGetM(a[i]) * mxGetN(a[i]) != 1) return false;
+        const float v = *(const float*)mxGetData(a[i]);
+        if (!(v >= 1.17549435e-38f && v <= 3.40282347e+38f)) return false;
+    }
+    for (int i = 2; i < 4; ++i)
+        if (!mxIsDouble(a[i]) || mxGetM(a[i]) * mxGetN(a[i]) != 1 || !(mxGetScalar(a[i]) > 0.0 && mxGetScalar(a[i]) <= 1.7976931348623157e308)) return false;
+    return mxIsDouble(a[4]) && mxGetM(a[4]) * mxGetN(a[4]) == 1 && mxGetScalar(a[4]) >= 1.0 && mxGetScalar(a[4]) <= 2147483647.0 &&
+           mxGetScalar(a[4]) == (double)(int)mxGetScalar(a[4]);
+}
+// the outputs of 'modelIss' / 'pointIss': keypoints (n x 1 uint32, 1-based), and with nout > 1 saliency (M x 1 double), with nout > 2
+// eig (M x 3 double: the library's rows transposed into MATLAB's columns), with nout > 3 nNeighbors (M x 1 int32).  Nothing is left
+// allocated on an error.
+static int iss_on_handle(pcreg_model* h, const mxArray* const* a, int nout, mxArray* out[4]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    const size_t R = (size_t)(M > 0 ? M : 1);
+    mxArray* tk = mxCreateNumericMatrix(R, 1, mxINT32_CLASS, mxREAL);
+    mxArray* te = nout > 2 ? mxCreateDoubleMatrix(3, R, mxREAL) : nullptr;      // [M][3] row-major is 3 x M column-major
+    mxArray* os = mxCreateDoubleMatrix((size_t)M, 1, mxREAL);
+    mxArray* on = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    int32_t n = 0;
+    rc = pcreg_model_iss_f32(h, *(const float*)mxGetData(a[0]), *(const float*)mxGetData(a[1]), mxGetScalar(a[2]), mxGetScalar(a[3]),
+                             (int)mxGetScalar(a[4]), M > 0 ? (int32_t*)mxGetData(on) : nullptr, te ? mxGetPr(te) : nullptr,
+                             M > 0 ? mxGetPr(os) : nullptr, (int32_t*)mxGetData(tk), &n);
+    if (rc == PCREG_OK) {
+        out[0] = mxCreateNumericMatrix((size_t)n, 1, mxUINT32_CLASS, mxREAL);
+        const int32_t* src = (const int32_t*)mxGetData(tk);
+        uint32_t* dst = (uint32_t*)mxGetData(out[0]);
+        for (int32_t i = 0; i < n; ++i) dst[i] = (uint32_t)src[i] + 1u;
+        if (nout > 2) {
+            out[2] = mxCreateDoubleMatrix((size_t)M, 3, mxREAL);
+            const double* e = mxGetPr(te);
+            double* d = mxGetPr(out[2]);
+            for (int c = 0; c < 3; ++c)
+                for (int i = 0; i < M; ++i) d[(size_t)i + (size_t)c * (size_t)M] = e[(size_t)i * 3 + c];
+        }
+    }
+    if (rc == PCREG_OK && nout > 1) out[1] = os; else mxDestroyArray(os);
+    if (rc == PCREG_OK && nout > 3) out[3] = on; else mxDestroyArray(on);
+    if (te) mxDestroyArray(te);
+    mxDestroyArray(tk);
     return rc;
 }
 
@@ -794,6 +851,28 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = denoise_on_handle(h, (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), nlhs, out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "modelIss")) {                    // [keypoints, saliency, eig, nNeighbors] = pcreg_mex('modelIss', h, r2s, r2n, t21, t32, minNb)
+        if (nrhs != 7 || !mxIsUint64(prhs[1]) || !iss_args_ok(prhs + 2))
+            usage = "modelIss: handle (uint64), r2Salient and r2NonMax (single scalars, the squared radii: finite, normal, > 0), threshold21 and "
+                    "threshold32 (finite double scalars > 0), minNeighbors (a whole number >= 1)";
+        else {
+            mxArray* out[4] = {nullptr, nullptr, nullptr, nullptr};
+            rc = iss_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), prhs + 2, nlhs, out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; if (out[3]) plhs[3] = out[3]; }
+        }
+    } else if (!strcmp(cmd, "pointIss")) {                    // [keypoints, saliency, eig, nNeighbors] = pcreg_mex('pointIss', single(pts), r2s, r2n, t21, t32, minNb)
+        if (nrhs != 7 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !iss_args_ok(prhs + 2))
+            usage = "pointIss: pts (single M x 3), r2Salient and r2NonMax (single scalars, the squared radii: finite, normal, > 0), threshold21 and "
+                    "threshold32 (finite double scalars > 0), minNeighbors (a whole number >= 1)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[4] = {nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = iss_on_handle(h, prhs + 2, nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; if (out[3]) plhs[3] = out[3]; }
         }
     } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)
         if (nrhs != 2 || !mxIsDouble(prhs[1]) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1]))) usage = "uniqueRows3: A (double n x 3)";

@@ -67,6 +67,7 @@ SYMBOLS = [
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
     "pcreg_model_fpfh_f32", "pcreg_point_fpfh_f32", "pcreg_dev_model_fpfh_workspace", "pcreg_dev_model_fpfh_f32",
+    "pcreg_model_iss_f32", "pcreg_point_iss_f32", "pcreg_dev_model_iss_workspace", "pcreg_dev_model_iss_f32",
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_downsample_grid_f32", "pcreg_dev_downsample_grid_workspace", "pcreg_dev_downsample_grid_chunk", "pcreg_dev_downsample_grid_f32",
@@ -166,6 +167,13 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_fpfh_f32.argtypes = [vp, i, vp, i, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_fpfh_f32.argtypes = [vp, i, vp, i, i, vp, vp, i, vp]
             L.pcreg_point_fpfh_f32.argtypes = [vp, i, i, i, vp, i, i, vp, vp, i, vp]
+        if hasattr(L, "pcreg_dev_model_iss_workspace"):       # (an older build given through PCREG_LIB lacks the ISS keypoints)
+            L.pcreg_dev_model_iss_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_iss_workspace.argtypes = [C.c_int]
+            vp, i, f, d = C.c_void_p, C.c_int, C.c_float, C.c_double             # (floats and doubles by value: declared)
+            L.pcreg_dev_model_iss_f32.argtypes = [vp, f, f, d, d, i, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_iss_f32.argtypes = [vp, f, f, d, d, i, vp, vp, vp, vp, vp]
+            L.pcreg_point_iss_f32.argtypes = [vp, i, i, f, f, d, d, i, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_model_refit_plane_workspace"):   # (an older build given through PCREG_LIB lacks the plane refit)
             L.pcreg_dev_model_refit_plane_workspace.restype = C.c_size_t
             L.pcreg_dev_model_refit_plane_workspace.argtypes = [C.c_int] * 3

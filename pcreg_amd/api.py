@@ -725,6 +725,51 @@ def point_fpfh(pts, k: int, normals=None, k_normals=None, viewpoint=None, spfh: 
                       M, nrm, vp, spfh)
 
 
+def iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors):
+    """The ISS parameters as the C tiers take them: each radius squared in double and the square rounded once to float32 (the
+    rule pcreg_model_iss_f32 states for wrappers that take radii), the thresholds as doubles, min_neighbors as an int."""
+    r2 = []
+    for name, r in (("salient_radius", salient_radius), ("nonmax_radius", nonmax_radius)):
+        r = float(r)
+        with np.errstate(over="ignore"):
+            sq = np.float32(r * r) if math.isfinite(r) and r > 0.0 else np.float32(np.nan)
+        if not (np.isfinite(sq) and sq >= np.finfo(np.float32).tiny):
+            raise ValueError(f"{name} must be a finite number > 0 whose square is a normal float32, got {r}")
+        r2.append(float(sq))
+    g21, g32, mn = float(gamma21), float(gamma32), int(min_neighbors)
+    for name, g in (("gamma21", g21), ("gamma32", g32)):
+        if not (math.isfinite(g) and g > 0.0):
+            raise ValueError(f"{name} must be a finite number > 0, got {g}")
+    if mn < 1:
+        raise ValueError(f"min_neighbors must be at least 1, got {mn}")
+    return r2[0], r2[1], g21, g32, mn
+
+
+def _iss_call(call, M: int) -> dict:
+    nn = np.zeros(max(M, 1), dtype=np.int32)
+    eig = np.zeros((max(M, 1), 3), dtype=np.float64)
+    sal = np.zeros(max(M, 1), dtype=np.float64)
+    kp = np.zeros(max(M, 1), dtype=np.int32)
+    n = C.c_int32(0)
+    call(nn.ctypes.data, eig.ctypes.data, sal.ctypes.data, kp.ctypes.data, C.byref(n))
+    return dict(keypoints=kp[:n.value].copy(), n_neighbors=nn[:M], eig=eig[:M], saliency=sal[:M])
+
+
+def point_iss(pts, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma32: float = 0.975, min_neighbors: int = 5) -> dict:
+    """detectISSFeatures(pts, 'SalientRadius', .., 'NonMaxRadius', .., 'Threshold21', .., 'Threshold32', .., 'MinNeighbors', ..) in
+    this library's rule (pcreg_model_iss_f32's contract): a dict with keypoints, the 0-based rows of the ISS keypoints, ascending
+    int32 (pts[keypoints] are the points); n_neighbors [M] int32, the rows within salient_radius of every row, itself included;
+    eig [M, 3] float64, the eigenvalues of that neighbourhood's covariance, descending (NaN for a non-finite row); saliency [M]
+    float64, the smallest eigenvalue of a row that passes the two ratio tests and has min_neighbors rows, else 0.  The radii are
+    squared in double and rounded once to float32.  The cloud is prepared for this call only: keep a Model for repeated calls."""
+    a = iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors)
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    return _iss_call(lambda nn, e, s, kp, n: check(lib().pcreg_point_iss_f32(m.ctypes.data, M, max(M, 1), *a, nn, e, s, kp, n)), M)
+
+
 def _denoise_args(k, threshold):
     k, threshold = int(k), float(threshold)
     if not 1 <= k <= KNN_MAX_K - 1:
@@ -996,6 +1041,14 @@ class Model:
             raise ValueError("the model handle is closed")
         k, nrm, kn, vp = _fpfh_args(self.M, k, normals, k_normals, viewpoint)
         return _fpfh_call(lambda n, ldn, v, o, ldf, c: check(lib().pcreg_model_fpfh_f32(self._h, k, n, ldn, kn, v, o, ldf, c)), self.M, nrm, vp, spfh)
+
+    def iss_keypoints(self, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma32: float = 0.975, min_neighbors: int = 5) -> dict:
+        """The ISS keypoints of the prepared model's own rows, with the neighbour count, the eigenvalues and the saliency of every
+        row -- point_iss's dict and contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        a = iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors)
+        return _iss_call(lambda nn, e, s, kp, n: check(lib().pcreg_model_iss_f32(self._h, *a, nn, e, s, kp, n)), self.M)
 
     def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
         """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold

@@ -438,6 +438,16 @@ int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* n
     GUARD();
     return launch_model_fpfh(model->v, k, normals, ldn, fpfh, spfh, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_iss_workspace(int M) { return iss_ws_bytes(M); }
+int pcreg_dev_model_iss_f32(const pcreg_dev_model* model, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
+                            int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints, int32_t* n_keypoints, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && iss_args_ok(r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors) && (n_keypoints || !keypoints));
+    PCREG_ARG(workspace_bytes >= iss_ws_bytes(0));                           // (the smallest any model needs; the launcher checks this model's)
+    GUARD();
+    return launch_model_iss(model->v, r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, keypoints, n_keypoints,
+                            workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -907,6 +917,59 @@ int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* nor
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return fpfh_on_view(st, v, k, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh);
+}
+
+// ISS keypoints of a prepared model's own rows: the chain on the device, ONE read of the count (with the per-row outputs behind
+// it), then the keypoint rows the count names
+static int iss_on_view(Stage& st, const ModelView& v, float r2s, float r2n, double g21, double g32, int min_nb, int32_t* n_neighbors, double* eig,
+                       double* saliency, int32_t* keypoints, int32_t* n_keypoints) {
+    const int M = v.M;
+    if (n_keypoints) *n_keypoints = 0;
+    if (M == 0) return PCREG_OK;
+    double *deig, *dsal; int32_t *dnn, *dkp, *dn; char* ws;
+    const size_t wsb = iss_ws_bytes(M);
+    TRY(st.take((size_t)M, &dnn));
+    TRY(st.take(eig ? 3 * (size_t)M : 0, &deig));
+    TRY(st.take((size_t)M, &dsal));
+    TRY(st.take(keypoints ? (size_t)M : 0, &dkp));
+    TRY(st.take(1, &dn));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_iss(v, r2s, r2n, g21, g32, min_nb, dnn, eig ? deig : nullptr, dsal, keypoints ? dkp : nullptr, n_keypoints ? dn : nullptr, ws, wsb,
+                         g_stream));
+    int32_t n = 0;
+    if (n_keypoints) PCREG_HIP(hipMemcpyAsync(&n, dn, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(n_neighbors, dnn, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(saliency, dsal, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    if (eig) PCREG_HIP(hipMemcpyAsync(eig, deig, sizeof(double) * 3 * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));                   // the count fixes how many rows come back
+    if (keypoints && n > 0) {
+        PCREG_HIP(hipMemcpyAsync(keypoints, dkp, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipStreamSynchronize(g_stream));
+    }
+    if (n_keypoints) *n_keypoints = n;
+    return PCREG_OK;
+}
+int pcreg_model_iss_f32(pcreg_model* model, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
+                        int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints, int32_t* n_keypoints) {
+    PCREG_ARG(model && iss_args_ok(r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors) && (n_keypoints || !keypoints));
+    PCREG_ARG(model->dm != nullptr && model->M < iss_max_rows() && ((n_neighbors && saliency) || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return iss_on_view(st, model->dm->v, r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, keypoints, n_keypoints);
+}
+int pcreg_point_iss_f32(const float* m, int M, int ldm, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
+                        int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints, int32_t* n_keypoints) {
+    PCREG_ARG(M >= 0 && ldm >= M && M < iss_max_rows() && iss_args_ok(r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors) &&
+              (M == 0 || (m && n_neighbors && saliency)) && (n_keypoints || !keypoints));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return iss_on_view(st, v, r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, keypoints, n_keypoints);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -247,6 +247,15 @@ int launch_model_denoise(const ModelView& v, int k, double threshold, double* me
 size_t fpfh_ws_bytes(int M, int k);
 int launch_model_fpfh(const ModelView& v, int k, const float* normals, int ldn, double* fpfh, uint8_t* spfh, void* ws, size_t ws_bytes,
                       hipStream_t st);
+// ISS keypoints of the model's own rows (knn_iss.hip): n_neighbors [M], eig [M][3] (or null) and saliency [M] by ORIGINAL
+// row, keypoints [<= M] ascending with n_keypoints (both may be null; keypoints needs n_keypoints) -- device pointers.  iss_args_ok
+// and iss_max_rows are the argument rules every tier checks before it touches the device
+size_t iss_ws_bytes(int M);
+bool iss_args_ok(float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors);
+int iss_max_rows();
+int launch_model_iss(const ModelView& v, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
+                     int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints, int32_t* n_keypoints, void* ws, size_t ws_bytes,
+                     hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

@@ -357,6 +357,36 @@ class PreparedModel:
                                                      _p(cnt) if cnt is not None else None, _p(ws), ws.numel(), _stream()))
         return (desc, cnt) if spfh else desc
 
+    def iss_keypoints(self, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma32: float = 0.975, min_neighbors: int = 5,
+                      eig: bool = True, out=None):
+        """The ISS keypoints of the model's own rows on torch's current stream (pcreg_dev_model_iss_f32; the contract is
+        pcreg_model_iss_f32's; the radii are squared in double and rounded once to float32): -> a dict of device tensors --
+        n_neighbors [M] int32, eig [M, 3] float64 descending (None with eig=False) and saliency [M] float64 by ORIGINAL row;
+        keypoints, an [M] int32 tensor whose first n_keypoints [1] int32 entries are the 0-based keypoint rows, ascending (the
+        rest is not written).  Nothing synchronises: the caller reads n_keypoints when it needs it, and
+        fpfh[keypoints[:n].long()] feeds pcreg_dev_get_matches without a trip through the host.  The workspace is cached on the
+        model and grown on demand; calls that may overlap on two streams pass buffers of their own,
+        out=(n_neighbors, eig, saliency, keypoints, n_keypoints, ws) with ws of pcreg_dev_model_iss_workspace(M) bytes."""
+        from .api import iss_args
+        a = iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors)
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_iss_workspace(M)), 256)
+        if out is not None:
+            nn, ev, sal, kp, n_kp, ws = out
+        else:
+            nn = torch.empty(M, dtype=torch.int32, device=dev)
+            ev = torch.empty((M, 3), dtype=torch.float64, device=dev) if eig else None
+            sal = torch.empty(M, dtype=torch.float64, device=dev)
+            kp = torch.empty(M, dtype=torch.int32, device=dev)
+            n_kp = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_iss_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._iss_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda t: _p(t) if t is not None and t.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_iss_f32(self.handle, *a, opt(nn), opt(ev), opt(sal), opt(kp), opt(n_kp), _p(ws), ws.numel(), _stream()))
+        return dict(n_neighbors=nn, eig=ev, saliency=sal, keypoints=kp, n_keypoints=n_kp)
+
     def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
         """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
         (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]
