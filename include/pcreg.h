@@ -454,6 +454,60 @@ int pcreg_point_iss_f32(const float* m, int M, int ldm, float r2_salient, float 
                         int min_neighbors, int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints,
                         int32_t* n_keypoints);
 
+/* MSAC plane fitting and plane extraction over the rows of the model (MATLAB's pcfitplane(ptCloud, maxDistance[, referenceVector,
+ * maxAngularDistance]) and the loop that follows it: fit, take the inliers out, fit again -- up to max_planes times in one call).
+ * THE CONTRACT of every tier (device, host, MEX, Python) is THIS TEXT; MATLAB's bits are not knowable here
+ * (INTEGRATION.md).
+ * inputs -- a prepared model of M fp32 rows, M < 2^26; max_distance t, a float, finite, normal and > 0, whose square
+ * t2 = fl32(t * t) is a normal float too; s = (float)(2^20 / (double)t2); ref_vec, three doubles or NULL, and with it max_angle in
+ * (0, pi/2] radians (ignored without it); max_planes P in 1 .. 64; n_trials B in 1 .. 2^20; min_inliers >= 3; seed; samples, int32
+ * [P][B][3] or NULL: 1-BASED original rows at this tier.
+ * ALIVE ROWS.  Initially the rows whose three coordinates are finite.  A non-finite row is never alive, never an inlier, label 0.
+ * THE QUANTISATION SCALE.  D is the largest axis extent (hi - lo of the fp32 limits, in double) of the finite rows and e frexp's
+ * exponent of D (D = f 2^e, f in [0.5, 1)).  D == 0 or no finite row: every trial is void and there is no plane.
+ * ROUND p = 0 .. P - 1, over the alive set A_p listed ascending by original row, nA rows.
+ * Trial b has rows i_j, j = 0 .. 2: from samples[p][b][j] when the table is given, else i_j = A_p[h_j % nA] with
+ * h_j = splitmix64(seed ^ splitmix64(((uint64)p * B + b) * 4 + j)) and splitmix64(x): x += 0x9E3779B97F4A7C15; z = x;
+ * z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31), all modulo 2^64.
+ * A trial is VOID if an index is out of range, a row is not alive, two indices are equal, or, with a = p1 - p0 and b = p2 - p0 in
+ * double and c = a x b, each component fl(fl(a_u b_v) - fl(a_v b_u)) in double without contraction, L2 = (cx cx + cy cy) + cz cz is
+ * not > 0 or not finite.  n = c / sqrt(L2), three divisions.  THE SIGN of n: with ref_vec, dot = (nx rx + ny ry) + nz rz, n is
+ * negated when dot < 0, and the trial is void when |dot| / |ref| < cos(max_angle), |ref| = sqrt((rx rx + ry ry) + rz rz);
+ * without it, n is negated so that its component of largest magnitude is positive, the first in x, y, z order winning a tie.
+ * SCORING, per alive row, in fp32: nf = (float)n; d = row - p0 componentwise; r = fmaf(nf.z, d.z, fmaf(nf.y, d.y, nf.x * d.x));
+ * r2 = r * r; the row is an inlier iff r2 <= t2 (NaN never passes); q = min(2^20, (int)rintf(r2 * s)) for an inlier, 2^20
+ * otherwise.  cost_b is the sum of q and count_b the number of inliers: integers, so no bit depends on the order of summation.
+ * THE BEST TRIAL is, among the non-void trials with count >= 3, the one of smallest cost, ties to the smallest b.  No such trial,
+ * or its count < min_inliers: extraction ends with n_planes = p.  The diagnostics of that last round are still recorded
+ * (best_trial = -1, cost and count 0 where no trial was eligible).
+ * THE REFIT, on the best trial's inliers: g = rint((double)d * 2^(17 - e)) per component (|g| <= 2^17); n, S1[3] = sum g and
+ * S2[6] = sum g_a g_b are 64-bit integers; N = n S2 - S1 S1^T exactly in 128 bits, each entry rounded once to double
+ * (pcreg_model_iss_f32's construction).  The normal is the eigenvector of N's smallest eigenvalue by cyclic Jacobi in double
+ * (the first of equal eigenvalues in x, y, z order of the rotated diagonal), signed by the rule above; the angle test is not
+ * repeated.  centre = (double)p0 + ((double)S1 / (double)n) * 2^-(17 - e); d4 = -((nx cx + ny cy) + nz cz).
+ * THE FINAL CLASSIFICATION, over the alive rows: the same fp32 chain with (float)normal and row - (float)centre.  The passing
+ * rows get label p + 1 and leave the alive set; count_p is their number, Q_p the sum of their q, and
+ * rmse_p = sqrt(((double)Q_p / count_p) * ((double)t2 * 2^-20)).
+ * outputs -- labels [M] int32 by original row (0: no plane); planes [P][4] double ROW-major (nx, ny, nz, d4); centres [P][3];
+ * counts [P] int32; rmse [P]; *n_planes; the diagnostics best_trial [P] int32 (0-based), best_cost [P] int64, best_count [P] int32,
+ * each may be NULL.  Entries of rounds that did not run are zero.  M = 0 writes *n_planes = 0 and zeros.
+ * The result is a function of (original rows, parameters) only: the call, the stream and the workspace's previous contents
+ * change no bit.
+ * PCREG_E_ARG, before anything runs: M >= 2^26; t or t2 zero, negative, subnormal, infinite or NaN; P, B or min_inliers out of
+ * range; ref_vec not finite or zero; max_angle out of range with ref_vec; model or n_planes NULL; labels, planes, centres, counts
+ * or rmse NULL with M > 0; a sample table entry is never an error (the trial is void). */
+int pcreg_model_fit_planes_f32(pcreg_model* model, float max_distance, const double* ref_vec /* [3] or NULL */, double max_angle,
+                               int max_planes, int n_trials, int min_inliers, uint64_t seed, const int32_t* samples /* [P][B][3] or NULL */,
+                               int32_t* labels /* [M] */, double* planes /* [P][4] */, double* centres /* [P][3] */,
+                               int32_t* counts /* [P] */, double* rmse /* [P] */, int32_t* n_planes, int32_t* best_trial /* or NULL */,
+                               int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */);
+/* The same without a handle (pcfitplane(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG:
+ * M < 0, ldm < M, m NULL with M > 0. */
+int pcreg_point_fit_planes_f32(const float* m, int M, int ldm, float max_distance, const double* ref_vec, double max_angle, int max_planes,
+                               int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* planes,
+                               double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial,
+                               int64_t* best_cost, int32_t* best_count);
+
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
  * the smallest index represents its run (MATLAB's default 'first').  ia [n]: the 1-based indices of the representatives in sorted
@@ -839,6 +893,24 @@ int pcreg_dev_model_iss_f32(const pcreg_dev_model* model, float r2_salient, floa
                             int min_neighbors, int32_t* n_neighbors, double* eig /* or NULL */, double* saliency,
                             int32_t* keypoints /* or NULL */, int32_t* n_keypoints /* or NULL */, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* pcreg_model_fit_planes_f32's contract on the device: samples [P][B][3] (or NULL), labels, planes, centres, counts,
+ * rmse, n_planes (one int32) and the diagnostics are device pointers, NULL as there; ref_vec is three HOST doubles or NULL; a sample
+ * s names original row s - idx_base.  The rows are read through the pointer the handle was created on.  Two launches (reset; alive
+ * bytes, labels and the box of the finite rows), then nine per round: the two launches of the chunk scan that list the alive rows
+ * with their coordinates, the hypotheses, the scoring (lane = trial over 2048 staged rows, one integer atomic pair per chunk and
+ * trial), the selection, the refit scatter, its 128-bit epilogue, the classification and the round's totals.  A device word says
+ * that extraction has ended; every later launch reads it and returns.  Nothing synchronises, nothing is cleared by a memset, no
+ * workgroup waits for another.  Workspace, with R = max(M, 1), C = max(ceil(M / 2048), 1) and T = n_trials:
+ * 6400 + roundup(R, 256) + roundup(4 C, 256) + 4 roundup(4 R, 256) + 2 roundup(12 T, 256) + roundup(T, 256) + roundup(8 T, 256) +
+ * roundup(4 T, 256) bytes; a workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams at once, each call
+ * with its own workspace. */
+size_t pcreg_dev_model_fit_planes_workspace(int M, int n_trials);
+int pcreg_dev_model_fit_planes_f32(const pcreg_dev_model* model, float max_distance, const double* ref_vec /* host [3] or NULL */,
+                                   double max_angle, int max_planes, int n_trials, int min_inliers, uint64_t seed,
+                                   const int32_t* samples /* or NULL */, int32_t idx_base, int32_t* labels, double* planes, double* centres,
+                                   int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial /* or NULL */,
+                                   int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

@@ -70,6 +70,17 @@
 //                                          threshold21 / threshold32 finite doubles > 0; minNeighbors a whole number >= 1; all
 //                                          always passed; the last three outputs are built only when asked for
 //                                          (matlab/detectISSModel.m, matlab/detectISSFast.m)
+//   'modelPlanes', handle, maxDistance, refVec, maxAngle, maxPlanes, nTrials, minInliers, seed, samples | 'pointPlanes', pts (single
+//                                          M x 3), maxDistance, ... -> labels (M x 1 int32: plane p's rows carry p, 0 is no plane),
+//                                          planes (n x 4 double: nx ny nz d), centres (n x 3 double), counts (n x 1 int32), rmse (n x 1
+//                                          double), diag (maxPlanes x 3 double: every round's winning trial, 1-based and 0 for none, its
+//                                          MSAC cost and its inlier count): pcfitplane and the fit / remove / fit-again loop in this
+//                                          library's rule (pcreg_model_fit_planes_f32) -- maxDistance a single scalar (finite, normal,
+//                                          > 0); refVec [] or a double 1 x 3; maxAngle a double scalar in RADIANS, in (0, pi/2] with a
+//                                          refVec; maxPlanes 1 .. 64, nTrials 1 .. 2^20, minInliers >= 3 and seed >= 0 whole doubles;
+//                                          samples [] or int32 3 x (nTrials * maxPlanes), 1-based rows, column p * nTrials + b the trial
+//                                          b of round p; all always passed; outputs after the first are built only when asked for
+//                                          (matlab/fitPlanesModel.m, matlab/fitPlanesFast.m, matlab/pcfitplaneFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -108,6 +119,8 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <cmath>
+#include <vector>
 #include "../include/pcreg.h"
 
 static double field(const mxArray* s, const char* name, double dflt, bool* missing = nullptr) {
@@ -275,6 +288,78 @@ static int iss_on_handle(pcreg_model* h, const mxArray* const* a, int nout, mxAr
     if (rc == PCREG_OK && nout > 3) out[3] = on; else mxDestroyArray(on);
     if (te) mxDestroyArray(te);
     mxDestroyArray(tk);
+    return rc;
+}
+
+// the parameters of the plane commands, prhs[0 .. 7]: maxDistance (single scalar, finite, normal, > 0), refVec ([] or double 1 x 3, finite, not zero),
+// maxAngle (double scalar), maxPlanes, nTrials, minInliers, seed (whole doubles in range), samples ([] or int32 3 x nTrials * maxPlanes)
+static bool whole_in(const mxArray* a, double lo, double hi) {
+    if (!mxIsDouble(a) || mxGetM(a) * mxGetN(a) != 1) return false;
+    const double v = mxGetScalar(a);
+    return v >= lo && v <= hi && v == std::floor(v);
+}
+static bool planes_args_ok(const mxArray* const* a) {
+    if (!mxIsSingle(a[0]) || mxGetM(a[0]) * mxGetN(a[0]) != 1) return false;
+    const float t = *(const float*)mxGetData(a[0]);
+    if (!(t >= 1.17549435e-38f && t <= 3.40282347e+38f)) return false;
+    if (!(mxIsEmpty(a[1]) || (mxIsDouble(a[1]) && mxGetM(a[1]) * mxGetN(a[1]) == 3))) return false;
+    if (!mxIsEmpty(a[1])) {                                       // finite and not all zero
+        const double* r = mxGetPr(a[1]);
+        for (int c = 0; c < 3; ++c) if (!(std::fabs(r[c]) <= 1.7976931348623157e308)) return false;
+        if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) return false;
+    }
+    if (!mxIsDouble(a[2]) || mxGetM(a[2]) * mxGetN(a[2]) != 1) return false;
+    if (!mxIsEmpty(a[1]) && !(mxGetScalar(a[2]) > 0.0 && mxGetScalar(a[2]) <= 1.5707963267948966)) return false;
+    if (!whole_in(a[3], 1.0, 64.0) || !whole_in(a[4], 1.0, 1048576.0) || !whole_in(a[5], 3.0, 2147483647.0) ||
+        !whole_in(a[6], 0.0, 9007199254740992.0))
+        return false;
+    if (mxIsEmpty(a[7])) return true;
+    return mxIsInt32(a[7]) && mxGetM(a[7]) == 3 && mxGetN(a[7]) == (size_t)mxGetScalar(a[3]) * (size_t)mxGetScalar(a[4]);
+}
+// the outputs of 'modelPlanes' / 'pointPlanes' (see the head of this file).  Nothing is left allocated on an error.
+static int planes_on_handle(pcreg_model* h, const mxArray* const* a, int nout, mxArray* out[6]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    const int P = (int)mxGetScalar(a[3]);
+    mxArray* ol = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    std::vector<double> planes(4 * (size_t)P), centres(3 * (size_t)P), rmse((size_t)P);
+    std::vector<int32_t> counts((size_t)P), bt((size_t)P), bn((size_t)P);
+    std::vector<int64_t> bc((size_t)P);
+    int32_t n = 0;
+    rc = pcreg_model_fit_planes_f32(h, *(const float*)mxGetData(a[0]), mxIsEmpty(a[1]) ? nullptr : mxGetPr(a[1]), mxGetScalar(a[2]), P,
+                                    (int)mxGetScalar(a[4]), (int)mxGetScalar(a[5]), (uint64_t)mxGetScalar(a[6]),
+                                    mxIsEmpty(a[7]) ? nullptr : (const int32_t*)mxGetData(a[7]), M > 0 ? (int32_t*)mxGetData(ol) : nullptr,
+                                    planes.data(), centres.data(), counts.data(), rmse.data(), &n, bt.data(), bc.data(), bn.data());
+    if (rc != PCREG_OK) { mxDestroyArray(ol); return rc; }
+    out[0] = ol;
+    if (nout > 1) {                                               // the library's rows transposed into MATLAB's columns
+        out[1] = mxCreateDoubleMatrix((size_t)n, 4, mxREAL);
+        for (int c = 0; c < 4; ++c) for (int i = 0; i < n; ++i) mxGetPr(out[1])[(size_t)i + (size_t)c * (size_t)n] = planes[(size_t)i * 4 + c];
+    }
+    if (nout > 2) {
+        out[2] = mxCreateDoubleMatrix((size_t)n, 3, mxREAL);
+        for (int c = 0; c < 3; ++c) for (int i = 0; i < n; ++i) mxGetPr(out[2])[(size_t)i + (size_t)c * (size_t)n] = centres[(size_t)i * 3 + c];
+    }
+    if (nout > 3) {
+        out[3] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        for (int i = 0; i < n; ++i) ((int32_t*)mxGetData(out[3]))[i] = counts[(size_t)i];
+    }
+    if (nout > 4) {
+        out[4] = mxCreateDoubleMatrix((size_t)n, 1, mxREAL);
+        for (int i = 0; i < n; ++i) mxGetPr(out[4])[i] = rmse[(size_t)i];
+    }
+    if (nout > 5) {
+        out[5] = mxCreateDoubleMatrix((size_t)P, 3, mxREAL);
+        double* d = mxGetPr(out[5]);
+        const bool ran_more = n < P;                              // round n ran too and ended the extraction: its diagnostics are real
+        for (int i = 0; i < P; ++i) {
+            const bool ran = i < n || (ran_more && i == n && M > 0);
+            d[i] = ran ? (double)bt[(size_t)i] + 1.0 : 0.0;
+            d[(size_t)i + (size_t)P] = (double)bc[(size_t)i];
+            d[(size_t)i + 2 * (size_t)P] = (double)bn[(size_t)i];
+        }
+    }
     return rc;
 }
 
@@ -873,6 +958,44 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = iss_on_handle(h, prhs + 2, nlhs, out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; if (out[3]) plhs[3] = out[3]; }
+        }
+    } else if (!strcmp(cmd, "modelPlanes")) {                 // [labels, planes, centres, counts, rmse, diag] = pcreg_mex('modelPlanes', h, t, ref, ang, P, B, minInl, seed, samples)
+        if (nrhs != 10 || !mxIsUint64(prhs[1]) || !planes_args_ok(prhs + 2))
+            usage = "modelPlanes: handle (uint64), maxDistance (a single scalar: finite, normal, > 0), refVec ([] or a finite non-zero double 1 x 3), maxAngle (a double "
+                    "scalar, radians, in (0, pi/2] with a refVec), maxPlanes (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 3), seed (a whole number "
+                    ">= 0), samples ([] or int32 3 x nTrials * maxPlanes)";
+        else {
+            mxArray* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            rc = planes_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), prhs + 2, nlhs, out);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+            }
+        }
+    } else if (!strcmp(cmd, "pointPlanes")) {                 // [labels, planes, centres, counts, rmse, diag] = pcreg_mex('pointPlanes', single(pts), t, ref, ang, P, B, minInl, seed, samples)
+        if (nrhs != 10 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !planes_args_ok(prhs + 2))
+            usage = "pointPlanes: pts (single M x 3), maxDistance (a single scalar: finite, normal, > 0), refVec ([] or a finite non-zero double 1 x 3), maxAngle (a double "
+                    "scalar, radians, in (0, pi/2] with a refVec), maxPlanes (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 3), seed (a whole number "
+                    ">= 0), samples ([] or int32 3 x nTrials * maxPlanes)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = planes_on_handle(h, prhs + 2, nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+            }
         }
     } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)
         if (nrhs != 2 || !mxIsDouble(prhs[1]) || (mxGetN(prhs[1]) != 3 && !mxIsEmpty(prhs[1]))) usage = "uniqueRows3: A (double n x 3)";

@@ -770,6 +770,77 @@ def point_iss(pts, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma3
     return _iss_call(lambda nn, e, s, kp, n: check(lib().pcreg_point_iss_f32(m.ctypes.data, M, max(M, 1), *a, nn, e, s, kp, n)), M)
 
 
+def planes_args(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed):
+    """The plane extraction's parameters as the C tiers take them (pcreg_model_fit_planes_f32's rules): max_distance as a float32
+    whose fp32 square is a normal number, ref_vec as three contiguous float64 or None, and the ranges of the counts."""
+    t = np.float32(max_distance)
+    tiny = np.finfo(np.float32).tiny
+    with np.errstate(over="ignore", under="ignore"):
+        t2 = t * t
+    if not (np.isfinite(t) and t >= tiny and np.isfinite(t2) and t2 >= tiny):
+        raise ValueError(f"max_distance must be a finite number > 0 whose float32 square is a normal number, got {max_distance}")
+    rv = None
+    ang = 0.0
+    if ref_vec is not None:
+        rv = np.ascontiguousarray(np.asarray(ref_vec, np.float64).reshape(-1))
+        if rv.shape != (3,) or not np.isfinite(rv).all() or not rv.any() or not math.isfinite(float(rv @ rv)):
+            raise ValueError("ref_vec must be three finite numbers, not all zero")
+        ang = float(max_angle)
+        if not (0.0 < ang <= math.pi / 2):
+            raise ValueError(f"max_angle must lie in (0, pi/2] radians, got {max_angle}")
+    P, B, mi = int(max_planes), int(n_trials), int(min_inliers)
+    if not 1 <= P <= 64:
+        raise ValueError(f"max_planes must lie in 1 .. 64, got {P}")
+    if not 1 <= B <= 1 << 20:
+        raise ValueError(f"n_trials must lie in 1 .. 2^20, got {B}")
+    if mi < 3:
+        raise ValueError(f"min_inliers must be at least 3, got {mi}")
+    return float(t), rv, ang, P, B, mi, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _planes_samples(samples, P, B):
+    if samples is None:
+        return None
+    smp = np.ascontiguousarray(np.asarray(samples, np.int32))
+    if smp.shape != (P, B, 3):
+        raise ValueError(f"samples must be [max_planes, n_trials, 3] = {(P, B, 3)}, got {smp.shape}")
+    return smp
+
+
+def _planes_call(call, M: int, P: int) -> dict:
+    labels = np.zeros(max(M, 1), dtype=np.int32)
+    planes = np.zeros((P, 4), dtype=np.float64)
+    centres = np.zeros((P, 3), dtype=np.float64)
+    counts = np.zeros(P, dtype=np.int32)
+    rmse = np.zeros(P, dtype=np.float64)
+    bt = np.zeros(P, dtype=np.int32)
+    bc = np.zeros(P, dtype=np.int64)
+    bn = np.zeros(P, dtype=np.int32)
+    n = C.c_int32(0)
+    call(labels.ctypes.data, planes.ctypes.data, centres.ctypes.data, counts.ctypes.data, rmse.ctypes.data, C.byref(n), bt.ctypes.data,
+         bc.ctypes.data, bn.ctypes.data)
+    return dict(n_planes=int(n.value), labels=labels[:M], planes=planes, centres=centres, counts=counts, rmse=rmse, best_trial=bt,
+                best_cost=bc, best_count=bn)
+
+
+def point_fit_planes(pts, max_distance, ref_vec=None, max_angle=math.pi / 2, max_planes: int = 1, n_trials: int = 1000,
+                     min_inliers: int = 3, seed: int = 0, samples=None) -> dict:
+    """pcfitplane(pts, maxDistance[, referenceVector, maxAngularDistance]) and the fit / remove / fit-again loop, up to max_planes
+    times in one call, in this library's rule (pcreg_model_fit_planes_f32's contract): a dict with n_planes; labels [M] int32 (plane
+    p's rows carry p + 1, 0 is no plane); planes [P, 4] float64 (nx, ny, nz, d); centres [P, 3]; counts [P]; rmse [P]; and the
+    diagnostics best_trial / best_cost / best_count [P] of every round's winning MSAC trial.  max_angle is in RADIANS.  samples,
+    int32 [max_planes, n_trials, 3], replaces the sampler with the caller's 1-BASED rows.  The cloud is prepared for this call only:
+    keep a Model for repeated calls."""
+    t, rv, ang, P, B, mi, sd = planes_args(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed)
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    smp = _planes_samples(samples, P, B)
+    return _planes_call(lambda *o: check(lib().pcreg_point_fit_planes_f32(m.ctypes.data, M, max(M, 1), t, rv.ctypes.data if rv is not None else None,
+                                                                          ang, P, B, mi, sd, smp.ctypes.data if smp is not None else None, *o)), M, P)
+
+
 def _denoise_args(k, threshold):
     k, threshold = int(k), float(threshold)
     if not 1 <= k <= KNN_MAX_K - 1:
@@ -1049,6 +1120,16 @@ class Model:
             raise ValueError("the model handle is closed")
         a = iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors)
         return _iss_call(lambda nn, e, s, kp, n: check(lib().pcreg_model_iss_f32(self._h, *a, nn, e, s, kp, n)), self.M)
+
+    def fit_planes(self, max_distance, ref_vec=None, max_angle=math.pi / 2, max_planes: int = 1, n_trials: int = 1000,
+                   min_inliers: int = 3, seed: int = 0, samples=None) -> dict:
+        """MSAC plane fitting and extraction over the prepared model's own rows -- point_fit_planes's dict and contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        t, rv, ang, P, B, mi, sd = planes_args(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed)
+        smp = _planes_samples(samples, P, B)
+        return _planes_call(lambda *o: check(lib().pcreg_model_fit_planes_f32(self._h, t, rv.ctypes.data if rv is not None else None, ang, P, B, mi,
+                                                                              sd, smp.ctypes.data if smp is not None else None, *o)), self.M, P)
 
     def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
         """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold

@@ -448,6 +448,18 @@ int pcreg_dev_model_iss_f32(const pcreg_dev_model* model, float r2_salient, floa
     return launch_model_iss(model->v, r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, keypoints, n_keypoints,
                             workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_fit_planes_workspace(int M, int n_trials) { return planes_ws_bytes(M, n_trials); }
+int pcreg_dev_model_fit_planes_f32(const pcreg_dev_model* model, float max_distance, const double* ref_vec, double max_angle, int max_planes,
+                                   int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t idx_base, int32_t* labels,
+                                   double* planes, double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial,
+                                   int64_t* best_cost, int32_t* best_count, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && n_planes && planes_args_ok(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers));
+    PCREG_ARG(workspace_bytes >= planes_ws_bytes(0, n_trials));                // (the smallest any model needs; the launcher checks this model's)
+    GUARD();
+    return launch_model_fit_planes(model->v, max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed, samples, idx_base, labels,
+                                   planes, centres, counts, rmse, n_planes, best_trial, best_cost, best_count, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -970,6 +982,81 @@ int pcreg_point_iss_f32(const float* m, int M, int ldm, float r2_salient, float 
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return iss_on_view(st, v, r2_salient, r2_nonmax, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, keypoints, n_keypoints);
+}
+
+// plane extraction on a prepared model's own rows: the chain on the device, then ONE read of everything
+static int planes_on_view(Stage& st, const ModelView& v, float t, const double* ref_vec, double max_angle, int P, int B, int min_inliers,
+                          uint64_t seed, const int32_t* samples, int32_t* labels, double* planes, double* centres, int32_t* counts, double* rmse,
+                          int32_t* n_planes, int32_t* best_trial, int64_t* best_cost, int32_t* best_count) {
+    const int M = v.M;
+    *n_planes = 0;
+    if (M == 0) {
+        for (int i = 0; i < P; ++i) {
+            if (planes) for (int c = 0; c < 4; ++c) planes[4 * i + c] = 0.0;
+            if (centres) for (int c = 0; c < 3; ++c) centres[3 * i + c] = 0.0;
+            if (counts) counts[i] = 0;
+            if (rmse) rmse[i] = 0.0;
+            if (best_trial) best_trial[i] = 0;
+            if (best_cost) best_cost[i] = 0;
+            if (best_count) best_count[i] = 0;
+        }
+        return PCREG_OK;
+    }
+    int32_t *dlab, *dcnt, *dnp, *dbt, *dbn, *dsmp; double *dpl, *dce, *drm; int64_t* dbc; char* ws;
+    const size_t wsb = planes_ws_bytes(M, B), ns = samples ? (size_t)P * (size_t)B * 3 : 0;
+    TRY(st.take((size_t)M, &dlab));
+    TRY(st.take(4 * (size_t)P, &dpl));
+    TRY(st.take(3 * (size_t)P, &dce));
+    TRY(st.take((size_t)P, &dcnt));
+    TRY(st.take((size_t)P, &drm));
+    TRY(st.take(1, &dnp));
+    TRY(st.take((size_t)P, &dbt));
+    TRY(st.take((size_t)P, &dbc));
+    TRY(st.take((size_t)P, &dbn));
+    TRY(st.take(ns, &dsmp));
+    TRY(st.take(wsb, &ws));
+    if (samples) PCREG_HIP(hipMemcpyAsync(dsmp, samples, sizeof(int32_t) * ns, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_model_fit_planes(v, t, ref_vec, max_angle, P, B, min_inliers, seed, samples ? dsmp : nullptr, 1, dlab, dpl, dce, dcnt, drm, dnp, dbt,
+                                dbc, dbn, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(labels, dlab, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(planes, dpl, sizeof(double) * 4 * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(centres, dce, sizeof(double) * 3 * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(counts, dcnt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(rmse, drm, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(n_planes, dnp, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    if (best_trial) PCREG_HIP(hipMemcpyAsync(best_trial, dbt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_cost) PCREG_HIP(hipMemcpyAsync(best_cost, dbc, sizeof(int64_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_count) PCREG_HIP(hipMemcpyAsync(best_count, dbn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_fit_planes_f32(pcreg_model* model, float max_distance, const double* ref_vec, double max_angle, int max_planes, int n_trials,
+                               int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* planes, double* centres,
+                               int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial, int64_t* best_cost, int32_t* best_count) {
+    PCREG_ARG(model && n_planes && planes_args_ok(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers));
+    PCREG_ARG(model->dm != nullptr && model->M < planes_max_rows() && ((labels && planes && centres && counts && rmse) || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return planes_on_view(st, model->dm->v, max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed, samples, labels, planes,
+                          centres, counts, rmse, n_planes, best_trial, best_cost, best_count);
+}
+int pcreg_point_fit_planes_f32(const float* m, int M, int ldm, float max_distance, const double* ref_vec, double max_angle, int max_planes,
+                               int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* planes,
+                               double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial, int64_t* best_cost,
+                               int32_t* best_count) {
+    PCREG_ARG(M >= 0 && ldm >= M && M < planes_max_rows() && n_planes &&
+              planes_args_ok(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers) &&
+              (M == 0 || (m && labels && planes && centres && counts && rmse)));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return planes_on_view(st, v, max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed, samples, labels, planes, centres, counts,
+                          rmse, n_planes, best_trial, best_cost, best_count);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -256,6 +256,17 @@ int iss_max_rows();
 int launch_model_iss(const ModelView& v, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
                      int32_t* n_neighbors, double* eig, double* saliency, int32_t* keypoints, int32_t* n_keypoints, void* ws, size_t ws_bytes,
                      hipStream_t st);
+// MSAC plane fitting and extraction over the model's own rows (knn_planes.hip): labels [M] by ORIGINAL row, planes [P][4],
+// centres [P][3], counts [P], rmse [P], n_planes and the diagnostics best_trial / best_cost / best_count [P] (each may be null) --
+// device pointers; ref_vec three HOST doubles or null; samples [P][B][3] on the device or null.  planes_args_ok and planes_max_rows
+// are the argument rules every tier checks before it touches the device
+size_t planes_ws_bytes(int M, int B);
+bool planes_args_ok(float max_distance, const double* ref_vec, double max_angle, int max_planes, int n_trials, int min_inliers);
+int planes_max_rows();
+int launch_model_fit_planes(const ModelView& v, float max_distance, const double* ref_vec, double max_angle, int max_planes, int n_trials,
+                            int min_inliers, unsigned long long seed, const int32_t* samples, int32_t idx_base, int32_t* labels,
+                            double* planes, double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial,
+                            int64_t* best_cost, int32_t* best_count, void* ws, size_t ws_bytes, hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

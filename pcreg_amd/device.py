@@ -387,6 +387,45 @@ class PreparedModel:
             check(lib().pcreg_dev_model_iss_f32(self.handle, *a, opt(nn), opt(ev), opt(sal), opt(kp), opt(n_kp), _p(ws), ws.numel(), _stream()))
         return dict(n_neighbors=nn, eig=ev, saliency=sal, keypoints=kp, n_keypoints=n_kp)
 
+    def fit_planes(self, max_distance, ref_vec=None, max_angle=math.pi / 2, max_planes: int = 1, n_trials: int = 1000,
+                   min_inliers: int = 3, seed: int = 0, samples=None, idx_base: int = 0, out=None):
+        """MSAC plane fitting and extraction over the model's own rows on torch's current stream (pcreg_dev_model_fit_planes_f32; the
+        contract is pcreg_model_fit_planes_f32's): -> a dict of device tensors -- labels [M] int32 (plane p's rows carry p + 1),
+        planes [P, 4] float64, centres [P, 3], counts [P] int32, rmse [P], n_planes [1] int32 and the diagnostics best_trial,
+        best_cost (int64), best_count [P].  samples is an int32 device tensor [max_planes, n_trials, 3] of rows counted from idx_base,
+        or None for the sampler.  Nothing synchronises: the caller reads n_planes when it needs it.  The workspace is cached on the
+        model and grown on demand; calls that may overlap on two streams pass buffers of their own, out=(labels, planes, centres,
+        counts, rmse, n_planes, best_trial, best_cost, best_count, ws) with ws of pcreg_dev_model_fit_planes_workspace(M, n_trials)
+        bytes."""
+        from .api import planes_args
+        t, rv, ang, P, B, mi, sd = planes_args(max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed)
+        dev, M = self.tensor.device, self.M
+        if samples is not None and (samples.dtype != torch.int32 or tuple(samples.shape) != (P, B, 3) or not samples.is_contiguous()
+                                    or samples.device != dev):
+            raise ValueError(f"samples must be a contiguous int32 tensor {(P, B, 3)} on the model's device")
+        need = max(int(lib().pcreg_dev_model_fit_planes_workspace(M, B)), 256)
+        if out is not None:
+            lab, pl, ce, cnt, rm, n_pl, bt, bc, bn, ws = out
+        else:
+            lab = torch.empty(M, dtype=torch.int32, device=dev)
+            pl = torch.empty((P, 4), dtype=torch.float64, device=dev)
+            ce = torch.empty((P, 3), dtype=torch.float64, device=dev)
+            cnt = torch.empty(P, dtype=torch.int32, device=dev)
+            rm = torch.empty(P, dtype=torch.float64, device=dev)
+            n_pl = torch.empty(1, dtype=torch.int32, device=dev)
+            bt = torch.empty(P, dtype=torch.int32, device=dev)
+            bc = torch.empty(P, dtype=torch.int64, device=dev)
+            bn = torch.empty(P, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_planes_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._planes_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda x: _p(x) if x is not None and x.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_fit_planes_f32(self.handle, t, rv.ctypes.data if rv is not None else None, ang, P, B, mi, sd, opt(samples),
+                                                       int(idx_base), opt(lab), opt(pl), opt(ce), opt(cnt), opt(rm), opt(n_pl), opt(bt), opt(bc),
+                                                       opt(bn), _p(ws), ws.numel(), _stream()))
+        return dict(labels=lab, planes=pl, centres=ce, counts=cnt, rmse=rm, n_planes=n_pl, best_trial=bt, best_cost=bc, best_count=bn)
+
     def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
         """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
         (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]

@@ -1,0 +1,347 @@
+"""MSAC plane fitting and extraction on a prepared model (knn_planes.hip) on the GPU against tests/planes_ref.py.
+
+Per round, from the alive set the returned labels imply: best_trial, best_cost and best_count EQUAL to the reference (exact fmaf
+chain, integer sums); centres equal bit for bit (p0 and exact integer sums); the returned normal within
+asin(64 eps ||N||_F / (mu2 - mu3)) of numpy.linalg.eigh's (DESIGN 4.20's backward-error constant of the Jacobi through Davis-Kahan);
+planes[:, 3] the formula on the returned normal and centre; labels, counts and rmse EQUAL to the classification restated from the
+RETURNED plane and centre.  No row is excluded anywhere.  Then the sample table, the reference vector, the edges, the knife edge,
+determinism, the tiers and the workspace."""
+import ctypes as C
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import planes_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _soa(x):
+    x = np.asarray(x, np.float32).reshape(-1, 3)
+    t = torch.empty((3, len(x)), dtype=torch.float32, device=_dev())
+    if len(x):
+        t.copy_(torch.from_numpy(np.array(x.T, order="C")))
+    return t
+
+
+def _prepared(model):
+    from pcreg_amd.device import PreparedModel
+    t = _soa(model)
+    return PreparedModel(t), t
+
+
+def _host(res):
+    """a PreparedModel.fit_planes dict as numpy"""
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    out["n_planes"] = int(out["n_planes"][0])
+    return out
+
+
+def _run(pm, t, samples=None, **kw):
+    if samples is not None:
+        samples = torch.from_numpy(np.ascontiguousarray(samples, np.int32)).to(_dev())
+    return _host(pm.fit_planes(t, samples=samples, **kw))
+
+
+def _fit(model, t, **kw):
+    pm, _t = _prepared(model)
+    try:
+        return _run(pm, t, **kw)
+    finally:
+        pm.close()
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, np.float64)).view(np.uint64)
+
+
+KEYS_F, KEYS_I = ("planes", "centres", "rmse"), ("labels", "counts", "best_trial", "best_cost", "best_count")
+
+
+def _same(a, b):
+    return (a["n_planes"] == b["n_planes"] and all(np.array_equal(_bits(a[k]), _bits(b[k])) for k in KEYS_F)
+            and all(np.array_equal(a[k], b[k]) for k in KEYS_I))
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(M):
+    a = ref.scene(M)
+    a.setflags(write=False)
+    return a
+
+
+def _check(model, got, t, max_planes, n_trials, min_inliers=3, seed=0, samples=None, ref_vec=None, max_angle=math.pi / 2, what=""):
+    """every round against the reference, from the alive set the returned labels imply -> the worst share of the normal's bound"""
+    m = np.asarray(model, np.float32).reshape(-1, 3)
+    P = max_planes
+    fin = ref.finite_rows(m)
+    e = ref.exponent(m)
+    lab = got["labels"]
+    assert lab.dtype == np.int32 and lab.shape == (len(m),) and not lab[~fin].any() and lab.min(initial=0) >= 0
+    assert got["planes"].shape == (P, 4) and got["centres"].shape == (P, 3) and got["best_cost"].dtype == np.int64
+    if len(m) == 0:                                                      # no round runs: zeros everywhere
+        assert got["n_planes"] == 0 and not any(got[k].any() for k in KEYS_F + KEYS_I)
+        return 0.0
+    worst = 0.0
+    n_seen = P
+    for p in range(P):
+        alive = fin & ((lab == 0) | (lab > p))
+        r = ref.round_(m, alive, p, t, n_trials, min_inliers, seed, None if samples is None else np.asarray(samples)[p], ref_vec, max_angle, e)
+        assert (got["best_trial"][p], int(got["best_cost"][p]), got["best_count"][p]) == (r["best_trial"], r["best_cost"], r["best_count"]), (what, p)
+        if r["stop"]:
+            print(f"{what} round {p}: stop, best trial {r['best_trial']} count {r['best_count']}")
+            n_seen = p
+            break
+        assert np.array_equal(_bits(got["centres"][p]), _bits(r["centre"])), (what, p)
+        nrm = got["planes"][p, :3]
+        ang, bound = ref.angle(nrm, r["normal"]), ref.normal_bound(r)
+        print(f"{what} round {p}: best trial {r['best_trial']} count {r['best_count']} cost {r['best_cost']}, refit n {r['n']}, max |g| {r['max_g']}, "
+              f"eigen-gap {(r['mu'][1] - r['mu'][0]) / r['normN']:.3f}, normal angle {ang:.3e} of bound {bound:.3e} ({ang / bound:.4f})")
+        assert ang <= bound and float(np.dot(nrm, r["normal"])) > 0, (what, p, ang, bound)
+        assert abs(float(np.linalg.norm(nrm)) - 1.0) < 1e-14 and not ref.sign_flip(nrm, ref_vec), (what, p)
+        worst = max(worst, ang / bound)
+        assert _bits(got["planes"][p, 3]) == _bits(ref.plane_d(nrm, got["centres"][p])), (what, p)
+        c = ref.classify(m, alive, nrm, got["centres"][p], t)
+        assert np.array_equal(lab == p + 1, c["mask"]), (what, p)
+        assert got["counts"][p] == c["count"] and _bits(got["rmse"][p]) == _bits(c["rmse"]), (what, p)
+    assert got["n_planes"] == n_seen, what
+    z = slice(n_seen, P)
+    assert not got["planes"][z].any() and not got["centres"][z].any() and not got["counts"][z].any() and not got["rmse"][z].any(), what
+    assert lab.max(initial=0) <= n_seen
+    zz = slice(min(n_seen + 1, P), P)                                    # the stopping round records its diagnostics
+    assert not got["best_trial"][zz].any() and not got["best_cost"][zz].any() and not got["best_count"][zz].any(), what
+    return worst
+
+
+# ---- 1. the scene ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M, B, mi", [(1030, 128, 40), (4096, 256, 200)])
+def test_scene_against_the_reference(M, B, mi):
+    """three noisy planes, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks"""
+    m = _scene(M)
+    got = _fit(m, 0.08, max_planes=5, n_trials=B, min_inliers=mi, seed=7)
+    share = _check(m, got, 0.08, 5, B, mi, 7, what=f"scene M = {M}")
+    assert got["n_planes"] == 3 and share < 1.0
+    assert 3 <= got["best_count"][3] < mi
+    want = np.array([0.40, 0.25, 0.15]) * M
+    assert (np.abs(np.sort(got["counts"][:3])[::-1] - want) < 0.05 * M).all() and (got["rmse"][:3] < 0.04).all()
+
+
+# ---- 2. a caller's sample table ---------------------------------------------------------------------------------------------------------
+def test_sample_table_with_void_trials():
+    m = _scene(1030)
+    rng = np.random.default_rng(21)
+    P, B = 3, 256
+    smp = rng.integers(0, len(m), (P, B, 3)).astype(np.int32)
+    smp[:, 0] = [5, 5, 9]                                                 # an equal pair
+    smp[:, 1] = [1, 2, len(m)]                                            # an index out of range
+    smp[:, 2] = [-1, 4, 6]
+    first = _fit(m, 0.08, max_planes=1, n_trials=B, min_inliers=40, samples=smp[:1])
+    gone = int(np.flatnonzero(first["labels"] == 1)[0])
+    smp[1:, 3] = [gone, 7, 8]                                             # a row the first round removed
+    got = _fit(m, 0.08, max_planes=P, n_trials=B, min_inliers=40, samples=smp)
+    _check(m, got, 0.08, P, B, 40, samples=smp, what="sample table")
+    assert got["n_planes"] >= 2 and np.array_equal(got["labels"] == 1, first["labels"] == 1)
+    assert not np.isin(got["best_trial"][:got["n_planes"]], [0, 1, 2]).any()
+    # ... and with a base of 1, as the host tiers pass it
+    pm, _t = _prepared(m)
+    try:
+        one = _run(pm, 0.08, max_planes=P, n_trials=B, min_inliers=40, samples=smp + 1, idx_base=1)
+    finally:
+        pm.close()
+    assert _same(one, got)
+    void = np.full((1, 4, 3), 3, np.int32)                                # every trial void: no plane, trial -1
+    none = _fit(m, 0.08, n_trials=4, samples=void)
+    assert none["n_planes"] == 0 and none["best_trial"][0] == -1 and not none["labels"].any()
+
+
+# ---- 3. a reference vector ------------------------------------------------------------------------------------------------------------
+def test_ref_vec_selects_the_second_plane_first():
+    m = _scene(1030)
+    free = _fit(m, 0.08, max_planes=2, n_trials=128, min_inliers=40, seed=7)
+    second = free["planes"][1, :3]
+    kw = dict(ref_vec=list(-3.0 * second), max_angle=math.radians(8))
+    got = _fit(m, 0.08, max_planes=2, n_trials=512, min_inliers=40, seed=7, **kw)
+    _check(m, got, 0.08, 2, 512, 40, 7, what="ref_vec", **kw)
+    assert got["n_planes"] >= 1 and abs(int(got["counts"][0]) - int(free["counts"][1])) <= 0.02 * len(m)
+    assert float(np.dot(got["planes"][0, :3], second)) < -0.99            # signed towards the reference vector
+    none = _fit(m, 0.08, n_trials=64, seed=7, ref_vec=[0.577, 0.577, -0.577], max_angle=math.radians(3))
+    _check(m, none, 0.08, 1, 64, 3, 7, ref_vec=[0.577, 0.577, -0.577], max_angle=math.radians(3), what="ref_vec rejects all")
+    assert none["n_planes"] == 0
+
+
+# ---- 4. edges ----------------------------------------------------------------------------------------------------------------------------
+def test_non_finite_rows():
+    m = np.array(_scene(1030))
+    bad = [0, 17, 511, 512, 1029]
+    m[bad[0]] = [np.nan, 50, 90]
+    m[bad[1]] = [100, np.inf, 90]
+    m[bad[2]] = [100, 50, -np.inf]
+    m[bad[3]] = [np.nan, np.nan, np.nan]
+    m[bad[4]] = [np.inf, np.nan, 95]
+    got = _fit(m, 0.08, max_planes=4, n_trials=128, min_inliers=40, seed=7)
+    _check(m, got, 0.08, 4, 128, 40, 7, what="non-finite rows")
+    assert got["n_planes"] == 3 and not got["labels"][bad].any()
+    smp = np.array([[[bad[0], 3, 4], [3, bad[4], 4], [3, 4, 5]]], np.int32)
+    s = _fit(m, 0.08, n_trials=3, samples=smp)
+    _check(m, s, 0.08, 1, 3, samples=smp, what="non-finite samples")
+    assert s["best_trial"][0] == 2
+
+
+@pytest.mark.parametrize("M", [0, 2, 3])
+def test_few_rows(M):
+    m = (np.eye(3, dtype=np.float32) + 5)[:M]
+    got = _fit(m, 0.1, max_planes=2, n_trials=32, seed=2)
+    _check(m, got, 0.1, 2, 32, 3, 2, what=f"M = {M}")
+    assert got["n_planes"] == (1 if M == 3 else 0) and got["labels"].shape == (M,)
+    if M == 3:
+        assert got["counts"][0] == 3 and (got["labels"] == 1).all() and got["best_count"][1] == 0 and got["best_trial"][1] == -1
+
+
+def test_coincident_rows():
+    m = np.full((700, 3), 2.5, np.float32)
+    got = _fit(m, 0.1, max_planes=2, n_trials=64)
+    _check(m, got, 0.1, 2, 64, what="coincident")
+    assert got["n_planes"] == 0 and got["best_trial"][0] == -1 and not got["labels"].any()
+
+
+def _knife_t():
+    """a float32 t whose neighbours' squares are the floats next to t2 = fl(t t): r2 one ulp either side of t2"""
+    t = np.float32(0.09)
+    up, dn = np.float32(np.inf), np.float32(-np.inf)
+    for _ in range(100000):
+        t2 = np.float32(t * t)
+        a, b = np.nextafter(t, up), np.nextafter(t, dn)
+        if np.float32(a * a) == np.nextafter(t2, up) and np.float32(b * b) == np.nextafter(t2, dn):
+            return t
+        t = a
+    raise AssertionError("no such t")
+
+
+def test_knife_edge_rows():
+    """a lattice in z = 0 and, in pairs above and below it, rows at |z| = t (r2 == t2: inliers), one float below (inliers) and one
+    float above (outliers): the pairs keep the refit's plane exactly z = 0, so the final classification meets the same edge"""
+    t = _knife_t()
+    up, dn = np.float32(np.inf), np.float32(-np.inf)
+    g = np.arange(32, dtype=np.float32)
+    lat = np.column_stack([np.repeat(g, 32), np.tile(g, 32), np.zeros(1024, np.float32)])
+    zs = [t, np.nextafter(t, dn), np.nextafter(t, up)]
+    knife = np.array([[3 + 5 * k, 7 + 2 * k, s * z] for k, z in enumerate(zs) for s in (1, -1)], np.float32)
+    m = np.vstack([lat, knife])
+    smp = np.array([[[0, 1, 32]]], np.int32)
+    got = _fit(m, float(t), n_trials=1, samples=smp)
+    _check(m, got, float(t), 1, 1, samples=smp, what="knife edge")
+    assert np.array_equal(got["planes"][0], [0.0, 0.0, 1.0, 0.0]) and got["centres"][0, 2] == 0.0
+    assert list(got["labels"][1024:]) == [1, 1, 1, 1, 0, 0] and got["counts"][0] == 1028 and got["best_count"][0] == 1028
+    t2, s = ref.thresholds(t)
+    q = [int(ref.q_of(np.float32(z * z), s)) for z in zs[:2]]
+    assert q[0] == ref.QMAX and got["best_cost"][0] == 2 * (q[0] + q[1]) + 2 * ref.QMAX
+
+
+# ---- 5. identical bits ---------------------------------------------------------------------------------------------------------------
+def test_identical_bits_across_calls_streams_and_a_shuffle():
+    from pcreg_amd._lib import lib
+    m = _scene(4096)
+    M, P, B = len(m), 4, 256
+    kw = dict(max_planes=P, n_trials=B, min_inliers=200, seed=11)
+    pm, _t = _prepared(m)
+    try:
+        a = _run(pm, 0.08, **kw)
+        b = _run(pm, 0.08, **kw)
+        assert _same(a, b) and a["n_planes"] == 3
+        need = max(int(lib().pcreg_dev_model_fit_planes_workspace(M, B)), 256)
+        i32, f64 = torch.int32, torch.float64
+        outs = [(torch.full((M,), -7, dtype=i32, device=_dev()), torch.full((P, 4), -7.0, dtype=f64, device=_dev()),
+                 torch.full((P, 3), -7.0, dtype=f64, device=_dev()), torch.full((P,), -7, dtype=i32, device=_dev()),
+                 torch.full((P,), -7.0, dtype=f64, device=_dev()), torch.full((1,), -7, dtype=i32, device=_dev()),
+                 torch.full((P,), -7, dtype=i32, device=_dev()), torch.full((P,), -7, dtype=torch.int64, device=_dev()),
+                 torch.full((P,), -7, dtype=i32, device=_dev()), torch.full((need,), 0x5A, dtype=torch.uint8, device=_dev()))
+                for _ in range(2)]
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        torch.cuda.synchronize()
+        for s, o in ((s1, outs[0]), (s2, outs[1])):
+            with torch.cuda.stream(s):
+                pm.fit_planes(0.08, out=o, **kw)
+        torch.cuda.synchronize()
+        names = ("labels", "planes", "centres", "counts", "rmse", "n_planes", "best_trial", "best_cost", "best_count")
+        for o in outs:
+            assert _same(_host(dict(zip(names, o[:9]))), a)
+    finally:
+        pm.close()
+    # a shuffled copy with the sample table mapped through the permutation: the integer sums know no order
+    rng = np.random.default_rng(17)
+    smp = rng.integers(0, M, (P, B, 3)).astype(np.int32)
+    c = _fit(m, 0.08, samples=smp, **kw)
+    perm = rng.permutation(M)                                          # row j of the copy is row perm[j] of the model
+    back = np.empty(M, np.int64)
+    back[perm] = np.arange(M)
+    d = _fit(m[perm], 0.08, samples=back[smp].astype(np.int32), **kw)
+    assert c["n_planes"] >= 2 and np.array_equal(d["labels"][back], c["labels"])       # (256 random triples seldom hit the 15 % plane)
+    d2 = dict(d, labels=c["labels"])
+    assert _same(d2, c)
+
+
+# ---- 6. tiers, workspace -----------------------------------------------------------------------------------------------------------------
+def test_host_tiers_equal_the_device_tier():
+    import pcreg_amd as pc
+    m = _scene(1030)
+    rng = np.random.default_rng(4)
+    smp = rng.integers(0, len(m), (2, 64, 3)).astype(np.int32)
+    for kw in (dict(max_planes=5, n_trials=128, min_inliers=40, seed=7),
+               dict(max_planes=2, n_trials=64, min_inliers=40, ref_vec=[1.0, 0.2, 0.1], max_angle=0.2, seed=3),
+               dict(max_planes=2, n_trials=64, min_inliers=40, samples=smp)):
+        want = _fit(m, 0.08, **kw)
+        if "samples" in kw:
+            kw = dict(kw, samples=smp + 1)                               # the host tiers take 1-based rows
+        with pc.Model(m) as h:
+            a = h.fit_planes(0.08, **kw)
+        b = pc.point_fit_planes(m, 0.08, **kw)
+        for got in (a, b):
+            assert got["labels"].dtype == np.int32 and got["planes"].shape == (kw["max_planes"], 4)
+            assert _same(got, want)
+    e = pc.point_fit_planes(np.zeros((0, 3)), 0.1, max_planes=3)
+    assert e["n_planes"] == 0 and e["labels"].shape == (0,) and not e["planes"].any() and not e["best_count"].any()
+    with pytest.raises(ValueError):
+        pc.point_fit_planes(m, 0.0)
+
+
+def test_workspace_size_is_exact():
+    """one byte short is refused as a bad argument; a canary behind the reported size survives"""
+    from pcreg_amd import _lib as _l
+    L = _l.lib()
+    m = _scene(4096)
+    M, P, B = len(m), 4, 256
+    pm, _t = _prepared(m)
+    try:
+        want = _run(pm, 0.08, max_planes=P, n_trials=B, min_inliers=200, seed=11)
+        need = int(L.pcreg_dev_model_fit_planes_workspace(M, B))
+        i32, f64 = torch.int32, torch.float64
+        lab = torch.full((M,), -7, dtype=i32, device=_dev())
+        pl, ce = torch.full((P, 4), -7.0, dtype=f64, device=_dev()), torch.full((P, 3), -7.0, dtype=f64, device=_dev())
+        cnt, rm = torch.full((P,), -7, dtype=i32, device=_dev()), torch.full((P,), -7.0, dtype=f64, device=_dev())
+        n = torch.full((1,), -7, dtype=i32, device=_dev())
+        bt, bc, bn = (torch.full((P,), -7, dtype=d, device=_dev()) for d in (i32, torch.int64, i32))
+        ws = torch.full((need + 256,), 0xA5, dtype=torch.uint8, device=_dev())
+        args = (pm.handle, 0.08, None, 0.0, P, B, 200, 11, None, 0, _p(lab), _p(pl), _p(ce), _p(cnt), _p(rm), _p(n), _p(bt), _p(bc), _p(bn), _p(ws))
+        assert L.pcreg_dev_model_fit_planes_f32(*args, C.c_size_t(need - 1), None) == _l.PCREG_E_ARG
+        assert b"bad argument" in L.pcreg_last_error()
+        torch.cuda.synchronize()
+        assert (lab == -7).all().item() and (n == -7).all().item()
+        _l.check(L.pcreg_dev_model_fit_planes_f32(*args, C.c_size_t(need), None))
+        torch.cuda.synchronize()
+        assert (ws[need:] == 0xA5).all().item()
+        got = _host(dict(labels=lab, planes=pl, centres=ce, counts=cnt, rmse=rm, n_planes=n, best_trial=bt, best_cost=bc, best_count=bn))
+        assert _same(got, want)
+    finally:
+        pm.close()
