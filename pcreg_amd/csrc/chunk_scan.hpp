@@ -2,6 +2,7 @@
 // per element over any number of chunks of kScanChunk elements, a workgroup of kScanBlock threads per chunk, no workgroup
 // waiting for another.  Launch 1: every chunk's sum (chunk_sum).  Launch 2: thread t of chunk c owns the chunk's elements
 // kScanPer t .. kScanPer t + kScanPer - 1 and learns what lies before them (chunk_offset).  T is int32_t or int64_t.
+// On top of the two: the compaction of a per-row predicate into an ascending row list (chunk_pred_count, chunk_pred_emit).
 #pragma once
 #include "common.hpp"
 
@@ -45,6 +46,35 @@ __device__ __forceinline__ T chunk_offset(const T* __restrict__ csum, T mine) {
     }
     return run + (s_thr[tid] - mine);
 }
+
+// ---- the compaction of a predicate pred(i) on rows 0 .. n - 1 into an ascending row list, on the scan's two launches ----------
+// this thread's rows with pred
+template <class Pred>
+__device__ __forceinline__ int32_t chunk_pred_mine(int n, Pred pred) {
+    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
+    int32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kScanPer; ++j) c += (i0 + j < n && pred(i0 + j)) ? 1 : 0;
+    return c;
+}
+// launch 1: csum[this chunk] = the chunk's rows with pred
+template <class Pred>
+__device__ __forceinline__ void chunk_pred_count(int n, int32_t* __restrict__ csum, Pred pred) {
+    chunk_sum<int32_t>(chunk_pred_mine(n, pred), csum);
+}
+// launch 2: emit(at, i) for each of this thread's rows i with pred, ascending, at = the number of such rows before i.  Returns at
+// behind the thread's last row: what the last thread of the last chunk holds is the list's length.
+template <class Pred, class Emit>
+__device__ __forceinline__ int32_t chunk_pred_emit(int n, const int32_t* __restrict__ csum, Pred pred, Emit emit) {
+    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
+    int32_t at = chunk_offset<int32_t>(csum, chunk_pred_mine(n, pred));
+#pragma unroll
+    for (int j = 0; j < kScanPer; ++j) {
+        if (i0 + j < n && pred(i0 + j)) { emit(at, i0 + j); ++at; }
+    }
+    return at;
+}
+__device__ __forceinline__ bool chunk_is_last_thread() { return blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanBlock - 1; }
 
 }  // namespace
 }  // namespace pcreg

@@ -23,13 +23,7 @@ namespace pcreg {
 
 namespace {
 
-constexpr int kCWgPerTile = kT16 / kWalkQPerWg;      // 8 workgroups per tile a, 64 of its rows each (the walk's queries)
-
 #define PCREG_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
-}
 
 // ---- the union-find over parent[] (original rows).  Invariant: parent[x] <= x, so the forest is acyclic and a set's root is
 // its smallest row.  Inside the walk every access is a relaxed agent-scope atomic; a stale value is still an ancestor.
@@ -78,50 +72,29 @@ __global__ __launch_bounds__(kBlock) void cluster_init_kernel(int M, int32_t* __
 // ---- C2. the walk -----------------------------------------------------------------------------------------------------
 // Workgroup (tile a, part p) owns sorted rows a * 512 + p * 64 + (tid >> 2); lane sub = tid & 3 of a row scores rows sub,
 // sub + 4, .. of every visited tile b >= a from LDS (x, y, z, original row).  Pair (a, b) is skipped by DESIGN 4.1's rule with
-// D = r2 and B = tile a's box: every row pair of a skipped tile pair has a computed d > r2.  The walk itself is knn_walk.hpp's.
+// D = r2 and B = tile a's box: every row pair of a skipped tile pair has a computed d > r2.  The walk itself is knn_walk.hpp's,
+// and so are the row prologue (walk_self_row), the staging rule (walk_row_finite) and the visit rule (walk_visits).
 // A non-finite row is staged as NaN and its own lanes admit nothing, so it stays a set of its own whatever r2.
 __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
                                                               const float* __restrict__ tbox, int n_tiles, int cull, int skip_same, float r2,
                                                               int32_t* parent, unsigned long long* __restrict__ stats,
                                                               unsigned long long* __restrict__ cstats) {
     __shared__ WalkLds lds;
-    const int tid = threadIdx.x;
-    const int ta = blockIdx.x / kCWgPerTile, part = blockIdx.x % kCWgPerTile;
-    if (blockIdx.x == 0 && tid == 0) {
-        if (stats) {
-            atomicAdd(&stats[0], 1ull);
-            atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)(n_tiles + 1) / 2ull);
-        }
-        if (cstats) atomicAdd(&cstats[0], 1ull);
-    }
+    const int ta = blockIdx.x / kWalkWgPerTile, part = blockIdx.x % kWalkWgPerTile;
+    walk_count_search(stats, (unsigned long long)n_tiles * (unsigned long long)(n_tiles + 1) / 2ull);
+    if (cstats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cstats[0], 1ull);
     float abox[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
-    // this thread's row
-    const int rl = part * kWalkQPerWg + tid / kWalkLanes;         // the row's place inside tile a
-    const int srow = ta * kT16 + rl;
-    const bool in_model = srow < M;
-    const int sr = in_model ? srow : 0;
-    const float qx = ms[sr], qy = ms[sr + (size_t)M], qz = ms[sr + 2 * (size_t)M];
-    const int row_i = perm[sr];
-    const bool live = in_model && finite3(qx, qy, qz);
-    const float rr = live ? r2 : -1.0f;                           // (a dead lane admits nothing: d is never negative)
-    int my_root = row_i;                                          // the last root this lane saw for its row
+    walk_tile_box(tbox, ta, abox);
+    const WalkSelfRow q = walk_self_row(ms, perm, M, ta, part);
+    const float rr = q.live ? r2 : -1.0f;                         // (a dead lane admits nothing: d is never negative)
+    int my_root = q.row_i;                                        // the last root this lane saw for its row
     unsigned long long n_hit = 0;
     int above = -1;                                               // on the diagonal only the rows behind this one
     walk_tiles(
-        lds, ta, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
-        [&](int ct) {
-            return !(cull != 0 && r2 < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), r2));
-        },
-        [&](int r) {                                              // a non-finite row is staged as no row at all
-            if (r < M) {
-                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                if (finite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
-            }
-            return walk_no_row();
-        },
-        [&](int ct) { above = ct == ta ? rl : -1; },
+        lds, ta, n_tiles, q.qx, q.qy, q.qz, part == 0 ? stats : nullptr,
+        [&](int ct) { return walk_visits(tbox, ct, abox, r2, cull); },
+        [&](int r) { return walk_row_finite(ms, perm, M, r); },
+        [&](int ct) { above = ct == ta ? q.rl : -1; },
         [&](int r, const float4 (&p)[4], float (&d)[4]) {
             const float qnan = __int_as_float(0x7FC00000);
 #pragma unroll
@@ -237,7 +210,7 @@ int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* 
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile pair, same bits
     const int skip_same = debug_flag(kDbgClusterNoSkip) ? 0 : 1; // "cluster_noskip": unite on every hit, same bits
     hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks), dim3(kBlock), 0, st, M, s.parent, first, sizes);
-    hipLaunchKernelGGL(cluster_walk_kernel, dim3((unsigned)(n_tiles * kCWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
+    hipLaunchKernelGGL(cluster_walk_kernel, dim3((unsigned)(n_tiles * kWalkWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
                        (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, skip_same, r2, s.parent, knn_stats_dev(),
                        cluster_stats_dev());
     hipLaunchKernelGGL(cluster_flatten_kernel, dim3(chunks), dim3(kBlock), 0, st, M, s.parent, s.csum);

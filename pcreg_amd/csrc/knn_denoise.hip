@@ -10,7 +10,7 @@
 //   D3  denoise_chunk_sum_kernel   per chunk of 2048 original rows: the finite d_i and their sum
 //   D4  denoise_chunk_dev_kernel   every workgroup adds the chunk sums (mu), then its chunk's sum of (d_i - mu)^2
 //   D5  denoise_thr_count_kernel   every workgroup adds the chunk deviations (sd, thr), then counts its chunk's d_i <= thr
-//   D6  denoise_scatter_kernel     chunk_scan.hpp's second launch: the inlier rows ascending, and their number
+//   D6  denoise_scatter_kernel     chunk_scan.hpp's predicate compaction (D5 counts): the inlier rows ascending, and their number
 // THE ORDER of every floating-point sum is block_tree_sum's, a function of the number of terms alone; there is no atomic on a
 // floating-point value.  Nothing synchronises; no workgroup waits for another.
 #include "knn_selfjoin.hpp"
@@ -22,7 +22,8 @@ namespace pcreg {
 namespace {
 
 // ---- D2. the walk and the mean distance -----------------------------------------------------------------------------------
-// normals_walk_kernel's prologue, walk_tiles calls and culling rule with k1 = k + 1 in k's place; the list keeps distances only.
+// selfjoin_klist_walk's prologue, staging rule and visit rule (knn_walk.hpp, knn_selfjoin.hpp) with k1 = k + 1 in k's place; the
+// list is this kernel's own: distances only, the k1-th entry in a fixed register.
 // A row enters a list only when d <= thr, thr = min(seed, the k1-th entry of any of the row's four lists).
 template <int KB>
 __global__ __launch_bounds__(kBlock) void denoise_walk_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
@@ -31,25 +32,13 @@ __global__ __launch_bounds__(kBlock) void denoise_walk_kernel(const float* __res
                                                               unsigned long long* __restrict__ stats) {
     __shared__ WalkLds lds;
     __shared__ float s_red[kBlock / 64];
-    const int tid = threadIdx.x;
-    const int ta = blockIdx.x / kNWgPerTile, part = blockIdx.x % kNWgPerTile;
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)n_tiles);
-    }
+    const int ta = blockIdx.x / kWalkWgPerTile, part = blockIdx.x % kWalkWgPerTile;
+    walk_count_search(stats, (unsigned long long)n_tiles * (unsigned long long)n_tiles);
     float abox[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
+    walk_tile_box(tbox, ta, abox);
     const float D = selfjoin_tile_bound(dk, ta, M, s_red);
-    // this thread's row
-    const int rl = part * kWalkQPerWg + tid / kWalkLanes;         // the row's place inside tile a
-    const long long srow = (long long)ta * kT16 + rl;
-    const bool in_model = srow < M;
-    const size_t sr = in_model ? (size_t)srow : 0;
-    const float qx = ms[sr], qy = ms[sr + (size_t)M], qz = ms[sr + 2 * (size_t)M];
-    const int row_i = perm[sr];
-    float thr = in_model ? dk[sr] : -INFINITY;                    // (a dead lane admits nothing)
-    if (!(thr == thr)) thr = INFINITY;
+    const WalkSelfRow q = walk_self_row(ms, perm, M, ta, part);
+    float thr = selfjoin_row_bound(dk, q);
     // The list holds k1 live places at its END: the KB - k1 places in front are filled with -inf, which no distance (>= 0) moves, so
     // the k1-th smallest distance seen is always the LAST entry -- a fixed register, where klist_kth_reg's select per entry against
     // the uniform k keeps 2 KB scalar registers of masks alive through the walk (KB = 32 spilled 8 of them).
@@ -57,17 +46,9 @@ __global__ __launch_bounds__(kBlock) void denoise_walk_kernel(const float* __res
 #pragma unroll
     for (int s = 0; s < KB; ++s) ld[s] = s < KB - k1 ? -INFINITY : INFINITY;
     walk_tiles(
-        lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
-        [&](int ct) {
-            return !(cull != 0 && D < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), D));
-        },
-        [&](int r) {                                              // a non-finite row is staged as no row at all
-            if (r < M) {
-                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                if (nfinite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
-            }
-            return walk_no_row();
-        },
+        lds, 0, n_tiles, q.qx, q.qy, q.qz, part == 0 ? stats : nullptr,
+        [&](int ct) { return walk_visits(tbox, ct, abox, D, cull); },
+        [&](int r) { return walk_row_finite(ms, perm, M, r); },
         [](int) {},
         [&](int, const float4 (&)[4], float (&d)[4]) {
             if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= thr) {
@@ -104,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void denoise_walk_kernel(const float* __res
     }
     const double qnan = __longlong_as_double(0x7FF8000000000000ll);
     const double d = n >= 2 ? sum / (double)(n - 1) : qnan;
-    if (in_model && (tid & (kWalkLanes - 1)) == 0) mean_dist[row_i] = d;
+    if (q.in_model && (threadIdx.x & (kWalkLanes - 1)) == 0) mean_dist[q.row_i] = d;
 }
 
 // ---- D3 .. D6. the statistic, the mask and the compaction -------------------------------------------------------------------
@@ -170,13 +151,6 @@ __global__ __launch_bounds__(kScanBlock) void denoise_chunk_dev_kernel(const dou
     }
 }
 
-__device__ __forceinline__ int32_t denoise_count8(const double* __restrict__ md, int M, long long i0, double thr) {
-    int32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) c += (i0 + j < M && md[i0 + j] <= thr) ? 1 : 0;     // (NaN on either side: no inlier)
-    return c;
-}
-
 __global__ __launch_bounds__(kScanBlock) void denoise_thr_count_kernel(const double* __restrict__ md, int M, int n_chunks, double t,
                                                                        const double* __restrict__ pdev, double* __restrict__ scal,
                                                                        int32_t* __restrict__ pin, double* __restrict__ stats_out) {
@@ -186,8 +160,7 @@ __global__ __launch_bounds__(kScanBlock) void denoise_thr_count_kernel(const dou
     const double qnan = __longlong_as_double(0x7FF8000000000000ll);
     const double sd = nf >= 2.0 ? __dsqrt_rn(ssd / (nf - 1.0)) : nf == 1.0 ? 0.0 : qnan;
     const double thr = mu + t * sd;
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    chunk_sum<int32_t>(denoise_count8(md, M, i0, thr), pin);
+    chunk_pred_count(M, pin, [&](long long i) { return md[i] <= thr; });          // (NaN on either side: no inlier)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         scal[2] = thr;
         if (stats_out) { stats_out[0] = thr; stats_out[1] = mu; stats_out[2] = sd; stats_out[3] = nf; }
@@ -198,15 +171,9 @@ __global__ __launch_bounds__(kScanBlock) void denoise_scatter_kernel(const doubl
                                                                      const int32_t* __restrict__ pin, int32_t* __restrict__ inliers,
                                                                      int32_t* __restrict__ n_inliers) {
     const double thr = scal[2];
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    const int32_t mine = denoise_count8(md, M, i0, thr);
-    int32_t at = chunk_offset<int32_t>(pin, mine);
-    if (inliers) {
-#pragma unroll
-        for (int j = 0; j < kScanPer; ++j)
-            if (i0 + j < M && md[i0 + j] <= thr) inliers[at++] = (int32_t)(i0 + j);
-    } else at += mine;
-    if (n_inliers && blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanBlock - 1) *n_inliers = at;
+    const int32_t at = chunk_pred_emit(M, pin, [&](long long i) { return md[i] <= thr; },
+                                       [&](int32_t at, long long i) { if (inliers) inliers[at] = (int32_t)i; });      // (no list: count only)
+    if (n_inliers && chunk_is_last_thread()) *n_inliers = at;
 }
 
 // M = 0: no row, no statistic
@@ -215,8 +182,6 @@ __global__ void denoise_empty_kernel(int32_t* __restrict__ n_inliers, double* __
     if (n_inliers) *n_inliers = 0;
     if (stats_out) { stats_out[0] = qnan; stats_out[1] = qnan; stats_out[2] = qnan; stats_out[3] = 0.0; }
 }
-
-int dkb_of(int k1) { return k1 <= 4 ? 4 : k1 <= 8 ? 8 : k1 <= 16 ? 16 : 32; }
 
 // Workspace, with R = max(M, 1) and C = max(ceil(M / 2048), 1): [seed bound of every sorted row, R floats][mean distance by original
 // row, R doubles (used when the caller wants none)][chunk sums, C doubles][chunk deviations, C doubles][chunk finite counts, C
@@ -264,19 +229,11 @@ int launch_model_denoise(const ModelView& v, int k, double threshold, double* me
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     unsigned long long* kstats = knn_stats_dev();                 // "knn_stats": searches, visited, nominal (n_tiles^2)
     double* md = mean_dist ? mean_dist : s.md;
-    hipLaunchKernelGGL(normals_seed_kernel, dim3((unsigned)((M + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, (const float*)v.ms, M, k1,
-                       s.dk);
-    const dim3 grid((unsigned)n_tiles * kNWgPerTile);
-#define PCREG_DENOISE_LAUNCH(KB_)                                                                                              \
-    hipLaunchKernelGGL(denoise_walk_kernel<KB_>, grid, dim3(kBlock), 0, st, (const float*)v.ms, (const int32_t*)v.perm, M,     \
-                       (const float*)v.tbox, n_tiles, cull, k1, (const float*)s.dk, md, kstats)
-    switch (dkb_of(k1)) {
-        case 4: PCREG_DENOISE_LAUNCH(4); break;
-        case 8: PCREG_DENOISE_LAUNCH(8); break;
-        case 16: PCREG_DENOISE_LAUNCH(16); break;
-        default: PCREG_DENOISE_LAUNCH(32); break;
-    }
-#undef PCREG_DENOISE_LAUNCH
+    launch_selfjoin_seed(v, k1, s.dk, st);
+    klist_dispatch<kSelfKbMin>(k1, [&](auto kb) {
+        hipLaunchKernelGGL(denoise_walk_kernel<kb.value>, dim3((unsigned)n_tiles * kWalkWgPerTile), dim3(kBlock), 0, st, (const float*)v.ms,
+                           (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, k1, (const float*)s.dk, md, kstats);
+    });
     const dim3 cgrid((unsigned)s.n_chunks), cblock(kScanBlock);
     hipLaunchKernelGGL(denoise_chunk_sum_kernel, cgrid, cblock, 0, st, (const double*)md, M, s.psum, s.pcnt);
     hipLaunchKernelGGL(denoise_chunk_dev_kernel, cgrid, cblock, 0, st, (const double*)md, M, s.n_chunks, (const double*)s.psum,

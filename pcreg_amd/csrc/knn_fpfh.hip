@@ -4,7 +4,7 @@
 //
 // The prepared model (knn_fast.hip) is used as it is, as the normals use it (knn_normals.hip).  A call is three launches:
 //   F1  normals_seed_kernel    (knn_selfjoin.hpp) the seed bound of every sorted row with k
-//   F2  fpfh_spfh_kernel<KB>   normals_walk_kernel's prologue, walk, culling rule and (distance, row) k-lists.  After the two merges every
+//   F2  fpfh_spfh_kernel<KB>   selfjoin_klist_walk<KB> (knn_selfjoin.hpp), the walk the normals use.  After it every
 //                              lane of a row holds the row's list; the lanes store it, rows and fp32 squared distances, to the [M][k]
 //                              table of the ORIGINAL row; then lane `sub` of the row takes list entries sub, sub + 4, ...: it gathers
 //                              the neighbour's coordinates and normal by original row, forms the pair features in double and counts
@@ -74,7 +74,6 @@ __device__ __forceinline__ void klist_advance(float (&ld)[KB], int (&li)[KB], bo
 }
 
 // ---- F2. the walk and the SPFH counts ------------------------------------------------------------------------------------
-// A row enters a list only when d <= thr, thr = min(seed, the k-th entry of any of the row's four lists): normals_walk_kernel's rule.
 template <int KB>
 __global__ __launch_bounds__(kBlock) void fpfh_spfh_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
                                                            const float* __restrict__ m, int ldm, const float* __restrict__ tbox,
@@ -82,64 +81,13 @@ __global__ __launch_bounds__(kBlock) void fpfh_spfh_kernel(const float* __restri
                                                            const float* __restrict__ normals, int ldn, int32_t* __restrict__ lrow,
                                                            float* __restrict__ ldist, uint8_t* __restrict__ spfh,
                                                            unsigned long long* __restrict__ stats) {
-    __shared__ WalkLds lds;
-    __shared__ float s_red[kBlock / 64];
-    const int tid = threadIdx.x;
-    const int ta = blockIdx.x / kNWgPerTile, part = blockIdx.x % kNWgPerTile;
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)n_tiles);
-    }
-    // the block's box is tile a's; its bound the largest seed over ALL of tile a's rows (every workgroup forms the same value)
-    float abox[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
-    const float D = selfjoin_tile_bound(dk, ta, M, s_red);
-    // this thread's row
-    const int rl = part * kWalkQPerWg + tid / kWalkLanes;         // the row's place inside tile a
-    const long long srow = (long long)ta * kT16 + rl;
-    const bool in_model = srow < M;
-    const size_t sr = in_model ? (size_t)srow : 0;
-    const float qx = ms[sr], qy = ms[sr + (size_t)M], qz = ms[sr + 2 * (size_t)M];
-    const int row_i = perm[sr];
-    float thr = in_model ? dk[sr] : -INFINITY;                    // (a dead lane admits nothing)
-    if (!(thr == thr)) thr = INFINITY;
     float ld[KB]; int li[KB];
-#pragma unroll
-    for (int s = 0; s < KB; ++s) { ld[s] = INFINITY; li[s] = -1; }
-    walk_tiles(
-        lds, 0, n_tiles, qx, qy, qz, part == 0 ? stats : nullptr,
-        [&](int ct) {
-            return !(cull != 0 && D < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), D));
-        },
-        [&](int r) {                                              // a non-finite row is staged as no row at all
-            if (r < M) {
-                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                if (nfinite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
-            }
-            return walk_no_row();
-        },
-        [](int) {},
-        [&](int, const float4 (&p)[4], float (&d)[4]) {
-            if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= thr) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (d[u] <= thr) {
-                        klist_insert<KB>(ld, li, d[u], __float_as_int(p[u].w));
-                        thr = fminf(thr, klist_kth_reg<KB>(ld, k));
-                    }
-                }
-            }
-        },
-        [&] {
-            thr = fminf(thr, __shfl_xor(thr, 1));                 // the row's four lanes share the tightest bound
-            thr = fminf(thr, __shfl_xor(thr, 2));
-        });
-    klist_merge_xor<KB>(ld, li, 1);
-    klist_merge_xor<KB>(ld, li, 2);
+    const WalkSelfRow q = selfjoin_klist_walk<KB>(ms, perm, M, tbox, n_tiles, cull, k, dk, stats, ld, li);
+    const int row_i = q.row_i;
+    const bool in_model = q.in_model;
 
     // ---- the epilogue: every lane of the row holds the row's list, (distance, row) ascending ----
-    const int sub = tid & (kWalkLanes - 1);
+    const int sub = threadIdx.x & (kWalkLanes - 1);
     // 1. the list to the table of the original row: lane sub stores places sub, sub + 4, ...
     if (in_model) {
         const size_t at = (size_t)row_i * (size_t)k;
@@ -151,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void fpfh_spfh_kernel(const float* __restri
     // 2. lane sub's entries to the head of its list: place sub first, then every fourth
     klist_advance<KB, 1>(ld, li, (sub & 1) != 0);
     klist_advance<KB, 2>(ld, li, (sub & 2) != 0);
-    const double pix = (double)qx, piy = (double)qy, piz = (double)qz;
+    const double pix = (double)q.qx, piy = (double)q.qy, piz = (double)q.qz;
     const size_t ri = (size_t)row_i;
     const double nix = (double)normals[ri], niy = (double)normals[ri + (size_t)ldn], niz = (double)normals[ri + 2 * (size_t)ldn];
     // 3. the pairs, one list entry a trip (k is uniform); a histogram is eleven 5-bit counts in one word: no indexed private array
@@ -198,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void fpfh_weight_kernel(const float* __rest
     if (row >= M) return;
     const int f = (int)(g - 3 * row);
     const size_t r = (size_t)row;
-    const bool finite = nfinite3(m[r], m[r + (size_t)ldm], m[r + 2 * (size_t)ldm]);
+    const bool finite = finite3(m[r], m[r + (size_t)ldm], m[r + 2 * (size_t)ldm]);
     double acc[kFpfhBins];
 #pragma unroll
     for (int b = 0; b < kFpfhBins; ++b) acc[b] = 0.0;
@@ -226,8 +174,6 @@ __global__ __launch_bounds__(kBlock) void fpfh_weight_kernel(const float* __rest
 #pragma unroll
     for (int b = 0; b < kFpfhBins; ++b) o[b] = !finite ? qnan : S > 0.0 ? (acc[b] / S) * 100.0 : 0.0;
 }
-
-int fkb_of(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32; }
 
 // Workspace, with R = max(M, 1): [seed bound of every sorted row, R floats][the lists' rows by original row, R k int32][their fp32
 // squared distances, R k floats][the SPFH counts, 33 R bytes (used when the caller wants none)]:
@@ -264,19 +210,12 @@ int launch_model_fpfh(const ModelView& v, int k, const float* normals, int ldn, 
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     unsigned long long* stats = knn_stats_dev();                  // "knn_stats": searches, visited, nominal (n_tiles^2)
     uint8_t* counts = spfh ? spfh : s.spfh;
-    hipLaunchKernelGGL(normals_seed_kernel, dim3((unsigned)((M + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, (const float*)v.ms, M, k,
-                       s.dk);
-    const dim3 grid((unsigned)n_tiles * kNWgPerTile);
-#define PCREG_FPFH_LAUNCH(KB_)                                                                                                 \
-    hipLaunchKernelGGL(fpfh_spfh_kernel<KB_>, grid, dim3(kBlock), 0, st, (const float*)v.ms, (const int32_t*)v.perm, M, v.m, v.ldm, \
-                       (const float*)v.tbox, n_tiles, cull, k, (const float*)s.dk, normals, ldn, s.lrow, s.ldist, counts, stats)
-    switch (fkb_of(k)) {
-        case 4: PCREG_FPFH_LAUNCH(4); break;
-        case 8: PCREG_FPFH_LAUNCH(8); break;
-        case 16: PCREG_FPFH_LAUNCH(16); break;
-        default: PCREG_FPFH_LAUNCH(32); break;
-    }
-#undef PCREG_FPFH_LAUNCH
+    launch_selfjoin_seed(v, k, s.dk, st);
+    klist_dispatch<kSelfKbMin>(k, [&](auto kb) {
+        hipLaunchKernelGGL(fpfh_spfh_kernel<kb.value>, dim3((unsigned)n_tiles * kWalkWgPerTile), dim3(kBlock), 0, st, (const float*)v.ms,
+                           (const int32_t*)v.perm, M, v.m, v.ldm, (const float*)v.tbox, n_tiles, cull, k, (const float*)s.dk, normals, ldn, s.lrow,
+                           s.ldist, counts, stats);
+    });
     const unsigned long long threads = 3ull * (unsigned long long)M;
     hipLaunchKernelGGL(fpfh_weight_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, v.m, v.ldm, M, k,
                        (const int32_t*)s.lrow, (const float*)s.ldist, (const uint8_t*)counts, fpfh);

@@ -11,8 +11,9 @@
 //   I2  iss_nonmax_kernel    the same walk with D = r2_nonmax, for the rows with a saliency > 0: a hit gathers the neighbour's
 //                            saliency and applies the rule on the bit patterns (saliencies are >= 0: their order is their bits');
 //                            the four lanes are OR-ed into one flag byte per original row
-//   I3  iss_count_kernel     chunk_scan.hpp's first launch: the flags of every chunk of 2048 original rows
-//   I4  iss_list_kernel      its second launch: the keypoint rows ascending, and their number
+//   I3  iss_count_kernel     chunk_scan.hpp's predicate compaction over the flags: the count of every chunk of 2048 original rows
+//   I4  iss_list_kernel      ... and the keypoint rows ascending, and their number
+// The walks' row prologue, staging rule and visit rule are knn_walk.hpp's (walk_self_row, walk_row_finite, walk_visits).
 // Every sum across hits is an INTEGER sum: no order of summation, no floating-point atomic.  Nothing synchronises; no workgroup
 // waits for another.
 #include "common.hpp"
@@ -26,12 +27,7 @@ namespace pcreg {
 
 namespace {
 
-constexpr int kIWgPerTile = kT16 / kWalkQPerWg;      // 8 workgroups per tile a, 64 of its rows each (the walk's queries)
 constexpr int kIssMaxM = 1 << 26;                    // below it no sum overflows: |q| <= 2^18 + 1, so |S2| < 2^26 (2^18 + 1)^2 < 2^63
-
-__device__ __forceinline__ bool ifinite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
-}
 
 // a 128-bit integer rounded ONCE to double (to nearest, ties to even).  The top 64 bits of |v| with the bits below them folded
 // into the lowest one: 64 > 53 + 2, so the sticky bit never reaches the rounding position and the u64 -> double conversion
@@ -51,20 +47,6 @@ __device__ __forceinline__ double i128_to_double(__int128 v) {
     return neg ? -r : r;
 }
 
-// this thread's row of tile ta, as the walks take it
-struct IssRow { float qx, qy, qz; int row_i; bool in_model, live; };
-__device__ __forceinline__ IssRow iss_row(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M, int ta, int part) {
-    IssRow q;
-    const int rl = part * kWalkQPerWg + (int)threadIdx.x / kWalkLanes;      // the row's place inside tile a
-    const long long srow = (long long)ta * kT16 + rl;
-    q.in_model = srow < M;
-    const size_t sr = q.in_model ? (size_t)srow : 0;
-    q.qx = ms[sr]; q.qy = ms[sr + (size_t)M]; q.qz = ms[sr + 2 * (size_t)M];
-    q.row_i = perm[sr];
-    q.live = q.in_model && ifinite3(q.qx, q.qy, q.qz);
-    return q;
-}
-
 // ---- I1. the scatter ------------------------------------------------------------------------------------------------------
 // scale = 2^(18 - e) as a float and back = 4^-(18 - e) as a double, e from r2 on the host (launch_model_iss).  dx * scale is exact
 // (a power of two; a product below the normal range rounds to an integer 0 either way), rintf rounds to nearest even.
@@ -75,30 +57,19 @@ __global__ __launch_bounds__(kBlock) void iss_scatter_kernel(const float* __rest
                                                              double* __restrict__ sal, unsigned long long* __restrict__ stats) {
     __shared__ WalkLds lds;
     const int tid = threadIdx.x;
-    const int ta = blockIdx.x / kIWgPerTile, part = blockIdx.x % kIWgPerTile;
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)n_tiles);
-    }
+    const int ta = blockIdx.x / kWalkWgPerTile, part = blockIdx.x % kWalkWgPerTile;
+    walk_count_search(stats, (unsigned long long)n_tiles * (unsigned long long)n_tiles);
+    __builtin_assume(r2 < INFINITY);                              // (iss_args_ok: walk_visits' guard for an infinite D folds away)
     float abox[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
-    const IssRow q = iss_row(ms, perm, M, ta, part);
+    walk_tile_box(tbox, ta, abox);
+    const WalkSelfRow q = walk_self_row(ms, perm, M, ta, part);
     const float rr = q.live ? r2 : -1.0f;                         // (a dead lane admits nothing: d is never negative)
     int n = 0;
     long long s1x = 0, s1y = 0, s1z = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
     walk_tiles(
         lds, 0, n_tiles, q.qx, q.qy, q.qz, part == 0 ? stats : nullptr,
-        [&](int ct) {
-            return !(cull != 0 && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), r2));
-        },
-        [&](int r) {                                              // a non-finite row is staged as no row at all
-            if (r < M) {
-                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                if (ifinite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
-            }
-            return walk_no_row();
-        },
+        [&](int ct) { return walk_visits(tbox, ct, abox, r2, cull); },
+        [&](int r) { return walk_row_finite(ms, perm, M, r); },
         [](int) {},
         [&](int, const float4 (&p)[4], float (&d)[4]) {
             if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
@@ -168,15 +139,12 @@ __global__ __launch_bounds__(kBlock) void iss_nonmax_kernel(const float* __restr
                                                             unsigned long long* __restrict__ stats) {
     __shared__ WalkLds lds;
     const int tid = threadIdx.x;
-    const int ta = blockIdx.x / kIWgPerTile, part = blockIdx.x % kIWgPerTile;
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)n_tiles * (unsigned long long)n_tiles);
-    }
+    const int ta = blockIdx.x / kWalkWgPerTile, part = blockIdx.x % kWalkWgPerTile;
+    walk_count_search(stats, (unsigned long long)n_tiles * (unsigned long long)n_tiles);
+    __builtin_assume(r2 < INFINITY);                              // (iss_args_ok: walk_visits' guard for an infinite D folds away)
     float abox[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) abox[c] = tbox[(size_t)ta * 6 + c];
-    const IssRow q = iss_row(ms, perm, M, ta, part);
+    walk_tile_box(tbox, ta, abox);
+    const WalkSelfRow q = walk_self_row(ms, perm, M, ta, part);
     const unsigned long long s_i = q.live ? sal[q.row_i] : 0ull;
     const bool work = s_i != 0ull;                                // a row with s == 0 is no keypoint whatever its neighbours
     const int any = __syncthreads_or(work ? 1 : 0);               // (uniform: a workgroup without such a row visits nothing)
@@ -184,16 +152,8 @@ __global__ __launch_bounds__(kBlock) void iss_nonmax_kernel(const float* __restr
     int beaten = 0;
     walk_tiles(
         lds, 0, n_tiles, q.qx, q.qy, q.qz, part == 0 ? stats : nullptr,
-        [&](int ct) {
-            return any != 0 && !(cull != 0 && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, abox, abox + 3), r2));
-        },
-        [&](int r) {
-            if (r < M) {
-                const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
-                if (ifinite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
-            }
-            return walk_no_row();
-        },
+        [&](int ct) { return any != 0 && walk_visits(tbox, ct, abox, r2, cull); },
+        [&](int r) { return walk_row_finite(ms, perm, M, r); },
         [](int) {},
         [&](int, const float4 (&p)[4], float (&d)[4]) {
             if (fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= rr) {
@@ -213,28 +173,15 @@ __global__ __launch_bounds__(kBlock) void iss_nonmax_kernel(const float* __restr
     if (q.in_model && (tid & (kWalkLanes - 1)) == 0) flag[q.row_i] = (work && !beaten) ? 1 : 0;
 }
 
-// ---- I3, I4. the compaction: thread t of chunk c owns original rows 2048 c + 8 t .. + 7 (chunk_scan.hpp's assignment) ---------
-__device__ __forceinline__ int32_t iss_count8(const uint8_t* __restrict__ flag, int M, long long i0) {
-    int32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) c += (i0 + j < M && flag[i0 + j]) ? 1 : 0;
-    return c;
-}
+// ---- I3, I4. the compaction of the flags (chunk_scan.hpp's predicate compaction over the original rows) ------------------------
 __global__ __launch_bounds__(kScanBlock) void iss_count_kernel(const uint8_t* __restrict__ flag, int M, int32_t* __restrict__ pin) {
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    chunk_sum<int32_t>(iss_count8(flag, M, i0), pin);
+    chunk_pred_count(M, pin, [&](long long i) { return flag[i] != 0; });
 }
 __global__ __launch_bounds__(kScanBlock) void iss_list_kernel(const uint8_t* __restrict__ flag, int M, const int32_t* __restrict__ pin,
                                                               int32_t* __restrict__ keypoints, int32_t* __restrict__ n_keypoints) {
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    const int32_t mine = iss_count8(flag, M, i0);
-    int32_t at = chunk_offset<int32_t>(pin, mine);
-    if (keypoints) {
-#pragma unroll
-        for (int j = 0; j < kScanPer; ++j)
-            if (i0 + j < M && flag[i0 + j]) keypoints[at++] = (int32_t)(i0 + j);
-    } else at += mine;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanBlock - 1) *n_keypoints = at;
+    const int32_t at = chunk_pred_emit(M, pin, [&](long long i) { return flag[i] != 0; },
+                                       [&](int32_t at, long long i) { if (keypoints) keypoints[at] = (int32_t)i; });   // (no list: count only)
+    if (chunk_is_last_thread()) *n_keypoints = at;
 }
 
 // M = 0: no row, no keypoint
@@ -290,7 +237,7 @@ int launch_model_iss(const ModelView& v, float r2_salient, float r2_nonmax, doub
     const int n_tiles = (M + kT16 - 1) / kT16;
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     unsigned long long* kstats = knn_stats_dev();                 // "knn_stats": searches, visited, nominal (n_tiles^2), per walk
-    const dim3 grid((unsigned)n_tiles * kIWgPerTile);
+    const dim3 grid((unsigned)n_tiles * kWalkWgPerTile);
     hipLaunchKernelGGL(iss_scatter_kernel, grid, dim3(kBlock), 0, st, (const float*)v.ms, (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles,
                        cull, r2_salient, scale, back, gamma21, gamma32, min_neighbors, n_neighbors, eig, saliency, kstats);
     if (n_keypoints) {

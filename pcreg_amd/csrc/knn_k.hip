@@ -84,10 +84,7 @@ __global__ __launch_bounds__(kBlock) void knn_k_kernel(const float* __restrict__
     const int tid = threadIdx.x;
     const int qb = blockIdx.x / kWalkWgPerBlock, part = blockIdx.x % kWalkWgPerBlock;
     walk_block_box<7>(s_red, s_box, q, Q, ldq, qperm, dk, qb);    // the block's box and largest dk_k
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
-    }
+    walk_count_search(stats, (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
     // this thread's query
     const int sub = tid & (kWalkLanes - 1);
     const int slot = qb * kWalkQBlock + part * kWalkQPerWg + (tid / kWalkLanes);
@@ -168,8 +165,6 @@ __global__ __launch_bounds__(256) void knn_k_merge_kernel(const int32_t* __restr
     }
 }
 
-int kb_of(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32; }
-
 struct KnnKWs { int32_t* qcnt; int32_t* qperm; float* dk; };
 KnnKWs knn_k_ws_layout(int Q, void* base, size_t* bytes) {
     KnnKWs s{};
@@ -211,19 +206,10 @@ int launch_model_knn(const ModelView& v, const float* q, int Q, int ldq, int k, 
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     unsigned long long* stats = knn_stats_dev();                  // "knn_stats": searches, visited, nominal (no tail here)
     const dim3 grid((unsigned)(((Q + kWalkQBlock - 1) / kWalkQBlock) * kWalkWgPerBlock));
-#define PCREG_KNN_K_LAUNCH(KB_)                                                                                             \
-    hipLaunchKernelGGL(knn_k_kernel<KB_>, grid, dim3(kBlock), 0, st, q, Q, ldq, (const int32_t*)s.qperm, (const float*)s.dk, \
-                       (const float*)v.ms, (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, k, (int)idx_base,  \
-                       idx, dist, stats)
-    switch (kb_of(k)) {
-        case 1: PCREG_KNN_K_LAUNCH(1); break;
-        case 2: PCREG_KNN_K_LAUNCH(2); break;
-        case 4: PCREG_KNN_K_LAUNCH(4); break;
-        case 8: PCREG_KNN_K_LAUNCH(8); break;
-        case 16: PCREG_KNN_K_LAUNCH(16); break;
-        default: PCREG_KNN_K_LAUNCH(32); break;
-    }
-#undef PCREG_KNN_K_LAUNCH
+    klist_dispatch<1>(k, [&](auto kb) {
+        hipLaunchKernelGGL(knn_k_kernel<kb.value>, grid, dim3(kBlock), 0, st, q, Q, ldq, (const int32_t*)s.qperm, (const float*)s.dk,
+                           (const float*)v.ms, (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, k, (int)idx_base, idx, dist, stats);
+    });
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }
@@ -234,14 +220,9 @@ int launch_merge_topk_f32(const int32_t* idx_in, const float* dist_in, int R, in
     if (Q == 0) return PCREG_OK;
     const size_t stride = rank_stride ? rank_stride : (size_t)Q * k;
     const dim3 grid((unsigned)((Q + 255) / 256));
-    switch (kb_of(k)) {
-        case 1: hipLaunchKernelGGL(knn_k_merge_kernel<1>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-        case 2: hipLaunchKernelGGL(knn_k_merge_kernel<2>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-        case 4: hipLaunchKernelGGL(knn_k_merge_kernel<4>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-        case 8: hipLaunchKernelGGL(knn_k_merge_kernel<8>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-        case 16: hipLaunchKernelGGL(knn_k_merge_kernel<16>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-        default: hipLaunchKernelGGL(knn_k_merge_kernel<32>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist); break;
-    }
+    klist_dispatch<1>(k, [&](auto kb) {
+        hipLaunchKernelGGL(knn_k_merge_kernel<kb.value>, grid, dim3(256), 0, st, idx_in, dist_in, R, Q, k, stride, idx, dist);
+    });
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

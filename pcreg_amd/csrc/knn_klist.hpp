@@ -1,11 +1,21 @@
 // pcreg_amd/csrc/knn_klist.hpp -- the k-list of the exact k-nearest walks (knn_k.hip, knn_normals.hip, knn_denoise.hip): a sorted list of KB
 // (distance, row) pairs in registers, ordered by (distance, row) with the empty entry (-1) last; insertion, the k-th entry,
-// and the merge with a partner lane's list.
+// and the merge with a partner lane's list; and the host's dispatch from k to KB (klist_dispatch).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace pcreg {
 namespace {
+
+// The one dispatch on the list size that serves k: f(std::integral_constant<int, KB>{}) with KB the smallest of KB_MIN, 2 KB_MIN,
+// .., 32 that is >= k (k <= PCREG_KNN_MAX_K = 32).  Only those sizes are instantiated.
+template <int KB_MIN, class F>
+inline void klist_dispatch(int k, F&& f) {
+    if constexpr (KB_MIN >= 32) f(std::integral_constant<int, 32>{});
+    else if (k <= KB_MIN) f(std::integral_constant<int, KB_MIN>{});
+    else klist_dispatch<2 * KB_MIN>(k, f);
+}
 
 __device__ __forceinline__ bool knn_k_lt(float da, int ia, float db, int ib) {     // (distance, row); -1 (empty) sorts last
     return da < db || (da == db && (unsigned)ia < (unsigned)ib);

@@ -22,6 +22,7 @@
 // Every sum across rows is an INTEGER sum: no order of summation, no floating-point atomic.  A device word says that extraction has
 // ended; every later launch reads it and returns.  Nothing synchronises; no workgroup waits for another.
 #include "common.hpp"
+#include "knn_walk.hpp"                              // finite3
 #include "chunk_scan.hpp"
 #include "wave_math.hpp"
 #include <cmath>
@@ -48,9 +49,6 @@ struct PlState {
     unsigned long long tot[kPlMaxPlanes][2];         // per round: count_p, Q_p
 };
 
-__device__ __forceinline__ bool pfinite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
-}
 // ransac.hip's sampler hash
 __device__ __forceinline__ unsigned long long pl_splitmix64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull; unsigned long long z = x;
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(kPlBlock) void pl_init_kernel(const float* __restri
         const long long i = (long long)blockIdx.x * kPlChunk + (long long)j * kPlBlock + threadIdx.x;
         if (i < M) {
             const float x = m[i], y = m[i + (size_t)ldm], z = m[i + 2 * (size_t)ldm];
-            const bool fin = pfinite3(x, y, z);
+            const bool fin = finite3(x, y, z);
             alive[i] = fin ? 1 : 0;
             labels[i] = 0;
             if (fin) {
@@ -176,37 +174,22 @@ __global__ __launch_bounds__(kPlBlock) void pl_init_kernel(const float* __restri
     }
 }
 
-// ---- A1, A2. the alive list: thread t of chunk c owns original rows 2048 c + 8 t .. + 7 (chunk_scan.hpp's assignment) -------------
-__device__ __forceinline__ int32_t pl_count8(const uint8_t* __restrict__ alive, int M, long long i0) {
-    int32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) c += (i0 + j < M && alive[i0 + j]) ? 1 : 0;
-    return c;
-}
+// ---- A1, A2. the alive list (chunk_scan.hpp's predicate compaction over the original rows) ------------------------------------------
 __global__ __launch_bounds__(kScanBlock) void pl_count_kernel(const PlState* __restrict__ st, const uint8_t* __restrict__ alive, int M,
                                                               int32_t* __restrict__ pin) {
     if (st->done) return;
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    chunk_sum<int32_t>(pl_count8(alive, M, i0), pin);
+    chunk_pred_count(M, pin, [&](long long i) { return alive[i] != 0; });
 }
 __global__ __launch_bounds__(kScanBlock) void pl_list_kernel(PlState* __restrict__ st, const uint8_t* __restrict__ alive,
                                                              const float* __restrict__ m, int M, int ldm, const int32_t* __restrict__ pin,
                                                              int32_t* __restrict__ A, float* __restrict__ cx, float* __restrict__ cy,
                                                              float* __restrict__ cz) {
     if (st->done) return;
-    const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
-    const int32_t mine = pl_count8(alive, M, i0);
-    int32_t at = chunk_offset<int32_t>(pin, mine);
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) {
-        const long long i = i0 + j;
-        if (i < M && alive[i]) {
-            A[at] = (int32_t)i;
-            cx[at] = m[i]; cy[at] = m[i + (size_t)ldm]; cz[at] = m[i + 2 * (size_t)ldm];
-            ++at;
-        }
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanBlock - 1) st->nA = at;
+    const int32_t at = chunk_pred_emit(M, pin, [&](long long i) { return alive[i] != 0; }, [&](int32_t at, long long i) {
+        A[at] = (int32_t)i;
+        cx[at] = m[i]; cy[at] = m[i + (size_t)ldm]; cz[at] = m[i + 2 * (size_t)ldm];
+    });
+    if (chunk_is_last_thread()) st->nA = at;
 }
 
 // ---- H. the hypotheses ---------------------------------------------------------------------------------------------------------------

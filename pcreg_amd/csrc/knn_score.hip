@@ -82,10 +82,7 @@ __global__ __launch_bounds__(kBlock) void score_walk_kernel(const float* __restr
     const int tid = threadIdx.x;
     const int qb = blockIdx.x / kWalkWgPerBlock, part = blockIdx.x % kWalkWgPerBlock;
     walk_block_box<6>(s_red, s_box, q, Q, Q, qperm, nullptr, qb);
-    if (stats && blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&stats[0], 1ull);
-        atomicAdd(&stats[2], (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
-    }
+    walk_count_search(stats, (unsigned long long)((Q + kWalkQBlock - 1) / kWalkQBlock) * (unsigned long long)n_tiles);
     const int sub = tid & (kWalkLanes - 1), ql = tid / kWalkLanes;
     const int slot = qb * kWalkQBlock + part * kWalkQPerWg + ql;
     const bool live = slot < Q;

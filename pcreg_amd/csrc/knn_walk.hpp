@@ -1,5 +1,9 @@
-// pcreg_amd/csrc/knn_walk.hpp -- the exact tile walk of the point search, its one definition: knn_k_kernel,
-// range_walk_kernel and cluster_walk_kernel are a prologue, walk_tiles with their four lambdas, and an epilogue.
+// pcreg_amd/csrc/knn_walk.hpp -- the exact tile walk of the point search, its one definition: every walk kernel is
+// a prologue, walk_tiles with its lambdas, and an epilogue.  What the self-joins' prologues and lambdas have in common is here
+// as well, once: the finite test, what a row is staged as (walk_row, walk_row_finite), the visit rule (walk_visits), the
+// "knn_stats" header (walk_count_search), tile a's box (walk_tile_box) and this thread's row (walk_self_row).  The three
+// query-side kernels (knn_k.hip, knn_range.hip, knn_score.hip) share the header and still write their query prologue and visit
+// rule out: docs/BENCH_NOTES.md, 2026-10-20, has why.
 //
 // A workgroup of kBlock threads serves kWalkQPerWg queries, kWalkLanes lanes each; kWalkWgPerBlock workgroups share a culling
 // block of kWalkQBlock query slots (a model tile, for the self-join) and every one of them forms the block's box for itself.
@@ -32,6 +36,63 @@ __device__ __forceinline__ float4 walk_no_row() {
 // sorted row r as the walk stages it
 __device__ __forceinline__ float4 walk_row(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M, int r) {
     return r < M ? make_float4(ms[r], ms[r + (size_t)M], ms[r + 2 * (size_t)M], __int_as_float(perm[r])) : walk_no_row();
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
+}
+// ... and as the self-joins stage it: a non-finite row is no row at all, so it is nobody's neighbour
+__device__ __forceinline__ float4 walk_row_finite(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M, int r) {
+    if (r < M) {
+        const float x = ms[r], y = ms[r + (size_t)M], z = ms[r + 2 * (size_t)M];
+        if (finite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
+    }
+    return walk_no_row();
+}
+
+// The visit rule: tile ct is scored unless DESIGN 4.1's rule (cull_rule.hpp) skips it for the box (lo xyz, hi xyz) and the
+// bound D; culling switched off, or no finite D, visits every tile.
+__device__ __forceinline__ bool walk_visits(const float* __restrict__ tbox, int ct, const float* box, float D, int cull) {
+    return !(cull != 0 && D < INFINITY && cull_skips(cull_gap2(tbox + (size_t)ct * 6, tbox + (size_t)ct * 6 + 3, box, box + 3), D));
+}
+
+// The search header of "knn_stats" (stats or null): one search more, and the (block, tile) pairs it would visit without the rule.
+// walk_tiles adds the pairs visited.
+__device__ __forceinline__ void walk_count_search(unsigned long long* __restrict__ stats, unsigned long long nominal) {
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd(&stats[0], 1ull);
+        atomicAdd(&stats[2], nominal);
+    }
+}
+
+// ---- this thread's row in a self-join ---------------------------------------------------------------------------------
+// The queries are the model's own sorted rows, a culling block is tile ta and its box the tile's.  Workgroup
+// (ta, part) of the kWalkWgPerTile of a tile owns sorted rows ta * kT16 + part * 64 + (tid >> 2).  A thread past the model's end
+// reads row 0 and stores nothing; how its lanes are kept from admitting a row is the caller's (live, or a bound below zero).
+constexpr int kWalkWgPerTile = kT16 / kWalkQPerWg;         // 8 workgroups per tile a, 64 of its rows each
+struct WalkSelfRow {
+    float qx, qy, qz;
+    int row_i;                                             // the ORIGINAL row
+    size_t sr;                                             // the sorted row (0 past the model's end)
+    int rl;                                                // its place inside tile a
+    bool in_model, live;                                   // live: in the model and finite
+};
+// tile ta's box (lo xyz, hi xyz), the self-join's culling box.  A call of its own, not a part of walk_self_row: a kernel with a
+// tile bound loads the box in front of the bound's barrier and its row behind it (both in one call cost the normals 0.8 %)
+__device__ __forceinline__ void walk_tile_box(const float* __restrict__ tbox, int ta, float (&box)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) box[c] = tbox[(size_t)ta * 6 + c];
+}
+__device__ __forceinline__ WalkSelfRow walk_self_row(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M, int ta,
+                                                     int part) {
+    WalkSelfRow q;
+    q.rl = part * kWalkQPerWg + (int)threadIdx.x / kWalkLanes;
+    const long long srow = (long long)ta * kT16 + q.rl;
+    q.in_model = srow < M;
+    q.sr = q.in_model ? (size_t)srow : 0;
+    q.qx = ms[q.sr]; q.qy = ms[q.sr + (size_t)M]; q.qz = ms[q.sr + 2 * (size_t)M];
+    q.row_i = perm[q.sr];
+    q.live = q.in_model && finite3(q.qx, q.qy, q.qz);
+    return q;
 }
 
 // The box of culling block qb over ALL its queries, and with N == 7 the largest dk over them (+inf or NaN: no bound), into
