@@ -284,17 +284,22 @@ __device__ __forceinline__ int seed_cell(float v, float lo, float inv_h, int n) 
     int c = (int)floorf((v - lo) * inv_h);
     return c < 0 ? 0 : (c >= n ? n - 1 : c);
 }
-// eight lanes per query: lane k of the group looks at cells k, k + 8, k + 16, k + 24 of the 27, keeps its
-// own sorted four smallest distances, and three xor-shuffle rounds merge the eight lists
-constexpr int kSeedBatch = 2;     // cells of a lane whose counters and slots are loaded before the first is used (4: 73 VGPRs, the
-                                  // eighth wave per SIMD lost and 3 % slower, docs/BENCH_NOTES.md 2026-10-18)
-static_assert(4 % kSeedBatch == 0, "a lane's four cells in whole batches");
+// eight lanes per query, two quads: in round r the quads look at cells 2r and 2r + 1 of the 27, and lane k of a quad at slot
+// k of its quad's cell, so the four slots of a cell (one 64-byte line) arrive through ONE load instruction of four adjacent
+// lanes and a wave's load touches 16 lines, not 64.  14 rounds (the last with one live cell), one distance per lane and
+// round, every (cell, slot) pair exactly once; a lane keeps its own sorted four smallest distances, and three xor-shuffle
+// rounds merge the eight lists.
+constexpr int kSeedRounds = (27 + 1) / 2;
+__host__ __device__ constexpr int seed_offsets(int c27) { return (c27 % 3) | (((c27 / 3) % 3) << 2) | ((c27 / 9) << 4); }
+constexpr int kSeedBatch = 7;     // rounds whose counters and slots are loaded before the first is used (64 VGPRs: the kernel is
+                                  // pinned to eight waves per SIMD, one residency round)
+static_assert(kSeedSlots == 4 && kSeedRounds % kSeedBatch == 0, "a quad per cell, the rounds in whole batches");
 __device__ __forceinline__ void sort4(float (&d)[4]) {
 #define PCREG_CS(a, b) { const float lo_ = fminf(d[a], d[b]), hi_ = fmaxf(d[a], d[b]); d[a] = lo_; d[b] = hi_; }
     PCREG_CS(0, 1) PCREG_CS(2, 3) PCREG_CS(0, 2) PCREG_CS(1, 3) PCREG_CS(1, 2)
 #undef PCREG_CS
 }
-__global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restrict__ q, int Q, int ldq,
+__global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __restrict__ q, int Q, int ldq,
                                                             const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
                                                             const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
                                                             int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
@@ -335,16 +340,19 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
     }
     const int nx = prep->nx, ny = prep->ny, nz = prep->nz;
     const int cx = seed_cell(qx, prep->gx0, prep->inv_h, nx), cy = seed_cell(qy, prep->gy0, prep->inv_h, ny), cz = seed_cell(qz, prep->gz0, prep->inv_h, nz);
-    // The lane's four cells first (an excluded one -- past the 27, or outside the grid -- reads the query's own cell and
-    // counts as empty), then the counting atomic, then kSeedBatch cells at a time: their counters and slots with nothing
-    // consumed in between.
-    int cell[4]; bool on[4];
+    // The quad's cell of every round first, in straight-line code (an excluded one -- past the 27, or outside the grid --
+    // reads the query's own cell and counts as empty), then the counting atomic, then kSeedBatch rounds at a time: the
+    // cells' counters (one address for the quad) and the lane's slots with nothing consumed in between.
+    const int quad = sub >> 2, slot = sub & 3, own = (cz * ny + cy) * nx + cx;
+    int cell[kSeedRounds]; unsigned on = 0;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int c27 = sub + 8 * t;
-        const int x = cx + c27 % 3 - 1, y = cy + (c27 / 3) % 3 - 1, z = cz + c27 / 9 - 1;
-        on[t] = c27 < 27 && x >= 0 && x < nx && y >= 0 && y < ny && z >= 0 && z < nz;
-        cell[t] = on[t] ? (z * ny + y) * nx + x : (cz * ny + cy) * nx + cx;
+    for (int r = 0; r < kSeedRounds; ++r) {
+        const int a = 2 * r, b = a + 1;                       // the two quads' cells of this round: compile-time numbers, their
+        const int o = quad ? seed_offsets(b) : seed_offsets(a);     // offsets in the 3 x 3 x 3 block as one literal each
+        const int x = cx + (o & 3) - 1, y = cy + ((o >> 2) & 3) - 1, z = cz + (o >> 4) - 1;
+        const bool ok = (b < 27 || !quad) & ((unsigned)x < (unsigned)nx) & ((unsigned)y < (unsigned)ny) & ((unsigned)z < (unsigned)nz);
+        cell[r] = ok ? (z * ny + y) * nx + x : own;
+        on |= (unsigned)ok << r;
     }
     // The query order's counts and this query's place in its cell.  The place is stored at the very end: nothing before
     // needs it, so the atomic's round trip runs alongside the grid loads.  (The query's coordinates are consumed above:
@@ -357,27 +365,21 @@ __global__ __launch_bounds__(kBlock) void seed_query_kernel(const float* __restr
     }
     float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
 #pragma unroll
-    for (int t0 = 0; t0 < 4; t0 += kSeedBatch) {
-        int n[kSeedBatch]; float4 pp[kSeedBatch][kSeedSlots];
+    for (int r0 = 0; r0 < kSeedRounds; r0 += kSeedBatch) {
+        int n[kSeedBatch]; float4 pp[kSeedBatch];
 #pragma unroll
-        for (int t = 0; t < kSeedBatch; ++t) n[t] = cnt[cell[t0 + t]];
+        for (int t = 0; t < kSeedBatch; ++t) n[t] = cnt[cell[r0 + t]];
 #pragma unroll
-        for (int t = 0; t < kSeedBatch; ++t) {
-#pragma unroll
-            for (int k = 0; k < kSeedSlots; ++k) pp[t][k] = slots[(size_t)cell[t0 + t] * kSeedSlots + k];
-        }
+        for (int t = 0; t < kSeedBatch; ++t) pp[t] = slots[(size_t)cell[r0 + t] * kSeedSlots + slot];
 #pragma unroll
         for (int t = 0; t < kSeedBatch; ++t) {
-            const int nt = on[t0 + t] ? min(n[t], kSeedSlots) : 0;
+            const float ex = qx - pp[t].x, ey = qy - pp[t].y, ez = qz - pp[t].z;
+            const float dd = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+            // sorted insertion in straight-line code; a distance that does not count (a NaN among them) enters as +inf
+            const bool counts = ((on >> (r0 + t)) & 1) & (slot < min(n[t], kSeedSlots)) & (dd < d[3]);      // (&: no branch to sink a load into)
+            float c = counts ? dd : INFINITY;
 #pragma unroll
-            for (int k = 0; k < kSeedSlots; ++k) {
-                float ex = qx - pp[t][k].x, ey = qy - pp[t][k].y, ez = qz - pp[t][k].z;
-                float dd = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-                if (k < nt && dd < d[3]) {
-                    if (dd < d[1]) { d[3] = d[2]; d[2] = d[1]; if (dd < d[0]) { d[1] = d[0]; d[0] = dd; } else d[1] = dd; }
-                    else { if (dd < d[2]) { d[3] = d[2]; d[2] = dd; } else d[3] = dd; }
-                }
-            }
+            for (int k = 0; k < 4; ++k) { const float lo = fminf(d[k], c); c = fmaxf(d[k], c); d[k] = lo; }
         }
     }
 #pragma unroll
@@ -419,31 +421,52 @@ __device__ __forceinline__ bool lex_lt_f(float da, int ia, float db, int ib) {
 constexpr int LPQ = 8;
 // A lane keeps its first kOwnEnt entries (e = lane, lane + LPQ, ..: the first LPQ * kOwnEnt of the list) in registers for both
 // passes, all loaded before the first is used; a longer list (cap = W * KC reaches 320) goes on in a loop that reads one entry
-// per trip.  An entry that survives the cut is expanded kRowBatch rows at a time: the coordinate and perm loads of those rows
-// are all issued before the first compare.  A row past M reads row M - 1 instead and is left out of the ranking, so no load
-// leaves ms[0 .. 3M) or perm[0 .. M); the plain loads need no alignment of M.
+// per lane and trip.  Pass 2 is the GROUP's work: every lane flags which of its entries survive the cut, and the group walks
+// the flagged entries of a trip (an 8-bit slice of a ballot) kEntBatch at a time, the wave as long as its longest group.  The
+// owner's first row j is broadcast and lane r ranks rows rr = r and rr = r + 8 of the sixteen, so lanes 0-3 and 4-7 read
+// the four-row runs j .., j + 8 .. (and j + 16 .., j + 24 ..) as 16 contiguous bytes each: eight loads per lane and entry,
+// all issued before the first compare.  A row past M reads row M - 1 instead and is left out of the ranking, so no load
+// leaves ms[0 .. 3M) or perm[0 .. M); the plain loads need no alignment of M.  Every lane keeps its own top two; (distance,
+// original row) is a total order over distinct rows, so the group reduction's result does not depend on who saw which row.
 constexpr int kOwnEnt = 8;                       // (tests/test_gpu_knn_chains.py builds lists beyond 128 entries: keep LPQ * kOwnEnt below)
-constexpr int kRowBatch = 8;                      // (16: 122 VGPRs and 4 % slower, docs/BENCH_NOTES.md 2026-10-18)
-static_assert(16 % kRowBatch == 0, "an entry's sixteen rows in whole batches");
-__device__ __forceinline__ void expand_entry(int j, float qx, float qy, float qz, const float* __restrict__ ms, int M,
-                                             const int32_t* __restrict__ perm, float& d1, float& d2, int& i1, int& i2) {
+constexpr int kEntBatch = 1;                      // flagged entries of a group whose rows are loaded before the first is ranked (2: 71 VGPRs,
+                                                  // 13.6 us against 13.0, docs/BENCH_NOTES.md 2026-10-20)
+__device__ __forceinline__ void expand_flagged(unsigned flagged, int j_own, int lane, float qx, float qy, float qz,
+                                               const float* __restrict__ ms, int M, const int32_t* __restrict__ perm,
+                                               float& d1, float& d2, int& i1, int& i2) {
+    // `flagged`: the group's lanes whose entry of this trip (first row j_own) is to be expanded; the same word in all eight
+    const int r0 = 8 * (lane >> 2) + (lane & 3);                // row rr = lane of an entry; rr = lane + 8 is 16 rows on
+    while (flagged) {
+        int j[kEntBatch]; bool have[kEntBatch];
+        float x[kEntBatch][2], y[kEntBatch][2], z[kEntBatch][2]; int oj[kEntBatch][2];
 #pragma unroll
-    for (int h = 0; h < 16; h += kRowBatch) {
-        float x[kRowBatch], y[kRowBatch], z[kRowBatch]; int oj[kRowBatch];
+        for (int t = 0; t < kEntBatch; ++t) {                 // (past the last flagged entry: the first one again, masked)
+            have[t] = flagged != 0;
+            const int owner = have[t] ? __builtin_ctz(flagged) : 0;
+            flagged &= flagged - 1;
+            j[t] = __shfl(j_own, owner, LPQ);
+            if (t > 0 && !have[t]) j[t] = j[0];
 #pragma unroll
-        for (int k = 0; k < kRowBatch; ++k) {
-            const int rr = h + k, jj = min(j + 8 * (rr >> 2) + (rr & 3), M - 1);
-            x[k] = ms[jj]; y[k] = ms[jj + (size_t)M]; z[k] = ms[jj + 2 * (size_t)M]; oj[k] = perm[jj];
+            for (int h = 0; h < 2; ++h) {
+                const int jj = min(j[t] + r0 + 16 * h, M - 1);
+                x[t][h] = ms[jj]; y[t][h] = ms[jj + (size_t)M]; z[t][h] = ms[jj + 2 * (size_t)M]; oj[t][h] = perm[jj];
+            }
         }
 #pragma unroll
-        for (int k = 0; k < kRowBatch; ++k) {              // ascending rr, (distance, original row) order: as the one-row loop ranked
-            const int rr = h + k;
-            const float d = point_d2(qx, qy, qz, x[k], y[k], z[k]);
-            const bool in2 = j + 8 * (rr >> 2) + (rr & 3) < M && lex_lt_f(d, oj[k], d2, i2), in1 = in2 && lex_lt_f(d, oj[k], d1, i1);
-            d2 = in1 ? d1 : (in2 ? d : d2); i2 = in1 ? i1 : (in2 ? oj[k] : i2);          // (selects: straight-line code)
-            d1 = in1 ? d : d1; i1 = in1 ? oj[k] : i1;
+        for (int t = 0; t < kEntBatch; ++t) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float d = point_d2(qx, qy, qz, x[t][h], y[t][h], z[t][h]);
+                const bool in2 = have[t] && j[t] + r0 + 16 * h < M && lex_lt_f(d, oj[t][h], d2, i2), in1 = in2 && lex_lt_f(d, oj[t][h], d1, i1);
+                d2 = in1 ? d1 : (in2 ? d : d2); i2 = in1 ? i1 : (in2 ? oj[t][h] : i2);      // (selects: straight-line code)
+                d1 = in1 ? d : d1; i1 = in1 ? oj[t][h] : i1;
+            }
         }
     }
+}
+// the group's 8-bit slice of a wave's ballot
+__device__ __forceinline__ unsigned group_flags(bool f) {
+    return (unsigned)(__ballot(f) >> (threadIdx.x & 63 & ~(LPQ - 1))) & ((1u << LPQ) - 1);
 }
 __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const float* __restrict__ q, int Q, int ldq, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm,
@@ -504,15 +527,16 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const float cut = (float)((double)a2 + 2.0 * Eab + 16.0 * u * fabs((double)a2 + r2));
     const float cut_up = nextafterf(cut, INFINITY);              // float rounding of the cut must not exclude anything
     float d1 = INFINITY, d2 = INFINITY; int i1 = -1, i2 = -1;
+    const bool all = !(a2 < INFINITY);                            // fewer than two scores: no cut
 #pragma unroll
     for (int k = 0; k < kOwnEnt; ++k) {
         const int j = (int)own[k].x; const float sc = __uint_as_float(own[k].y);
-        if (lane + LPQ * k < total && j >= 0 && (sc <= cut_up || !(a2 < INFINITY))) expand_entry(j, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
+        expand_flagged(group_flags(lane + LPQ * k < total && j >= 0 && (sc <= cut_up || all)), j, lane, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
     }
-    for (int e = lane + LPQ * kOwnEnt; e < total; e += LPQ) {
-        const uint2 v = ent[e];
+    for (int e0 = LPQ * kOwnEnt; e0 < total; e0 += LPQ) {        // (the trip count is the group's: every lane of it takes part in the ballot)
+        const uint2 v = ent[min(e0 + lane, last)];
         const int j = (int)v.x; const float sc = __uint_as_float(v.y);
-        if (j >= 0 && (sc <= cut_up || !(a2 < INFINITY))) expand_entry(j, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
+        expand_flagged(group_flags(e0 + lane < total && j >= 0 && (sc <= cut_up || all)), j, lane, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
     }
     // group-shuffle top-2 reduction ordered by (dist, idx); empty slots are (+inf, -1 -> max uint)
 #pragma unroll
