@@ -508,6 +508,70 @@ int pcreg_point_fit_planes_f32(const float* m, int M, int ldm, float max_distanc
                                double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial,
                                int64_t* best_cost, int32_t* best_count);
 
+/* MSAC sphere fitting and sphere extraction over the rows of the model (MATLAB's pcfitsphere(ptCloud, maxDistance) and the loop over
+ * it: fit, take the inliers out, fit again -- up to max_spheres times in one call; the fiducial markers and ball tips of a scan).
+ * THE CONTRACT of every tier (device, host, MEX, Python) is THIS TEXT; MATLAB's bits are not knowable here
+ * (INTEGRATION.md).
+ * inputs -- a prepared model of M fp32 rows, M < 2^26; max_distance t under pcreg_model_fit_planes_f32's rules (a float, finite,
+ * normal and > 0, whose square t2 = fl32(t * t) is a normal float too; s = (float)(2^20 / (double)t2)); min_radius and max_radius,
+ * floats with 0 <= min_radius <= max_radius, max_radius may be +inf, both compared as floats; max_spheres P in 1 .. 64; n_trials B
+ * in 1 .. 2^20; min_inliers >= 4; seed; samples, int32 [P][B][4] or NULL: 1-BASED original rows at this tier.
+ * ALIVE ROWS.  Initially the rows whose three coordinates are finite.  A non-finite row is never alive, never an inlier, label 0.
+ * THE QUANTISATION SCALE.  D is the largest axis extent (hi - lo of the fp32 limits, in double) of the finite rows and e frexp's
+ * exponent of D (D = f 2^e, f in [0.5, 1)); e = 0 where D == 0 or there is no finite row.
+ * ROUND p = 0 .. P - 1, over the alive set A_p listed ascending by original row, nA rows.
+ * Trial b has rows i_j, j = 0 .. 3: from samples[p][b][j] when the table is given, else i_j = A_p[h_j % nA] with
+ * h_j = splitmix64(seed ^ splitmix64(((uint64)p * B + b) * 4 + j)), splitmix64 as at pcreg_model_fit_planes_f32.
+ * THE TRIAL'S SPHERE, the circumsphere of its four rows p_0 .. p_3, in double, every step ONE correctly rounded operation, no
+ * contraction, in this order: d_i = (double)p_i - (double)p_0, i = 1, 2, 3; b_i = (d_ix d_ix + d_iy d_iy) + d_iz d_iz; the cross
+ * products X1 = d_2 x d_3, X2 = d_3 x d_1, X3 = d_1 x d_2, each component fl(fl(a_u c_v) - fl(a_v c_u)) of a x c;
+ * det = (d_1x X1x + d_1y X1y) + d_1z X1z; u = ((b_1 X1 + b_2 X2) + b_3 X3) / (2 det) component by component;
+ * R2 = (ux ux + uy uy) + uz uz; R = sqrt(R2); in fp32 cf = (float)((double)p_0 + u) and Rf = (float)R.
+ * A trial is VOID if an index is out of range, a row is not alive, any two of the four indices are equal, det is zero or not
+ * finite, a component of u, R, a component of cf or Rf is not finite, or Rf < min_radius or Rf > max_radius.
+ * SCORING, per alive row, in fp32: d = row - cf componentwise; d2 = fmaf(d.z, d.z, fmaf(d.y, d.y, d.x * d.x)); rho = the correctly
+ * rounded fp32 square root of d2; r = rho - Rf; r2 = r * r; the row is an inlier iff r2 <= t2 (NaN never passes);
+ * q = min(2^20, (int)rintf(r2 * s)) for an inlier, 2^20 otherwise.  cost_b is the sum of q and count_b the number of inliers:
+ * integers, so no bit depends on the order of summation.
+ * THE BEST TRIAL is, among the non-void trials with count >= 4, the one of smallest cost, ties to the smallest b.  No such trial,
+ * or its count < min_inliers: extraction ends with n_spheres = p.  The diagnostics of that last round are still recorded
+ * (best_trial = -1, cost and count 0 where no trial was eligible).
+ * THE REFIT, on the best trial's inliers: g = rint((double)(row - p_0) * 2^(17 - e)) per component, the difference taken in fp32
+ * (|g| <= 2^17); w = gx gx + gy gy + gz gz < 2^36, split as w = w_hi 2^18 + w_lo; seventeen signed 64-bit sums: n, S1[3] = sum g,
+ * S2[6] = sum g_a g_b, sum w, sum g w_lo [3] and sum g w_hi [3] (each below 2^61 at 2^26 rows).  sum g w is recombined in 128 bits;
+ * N = n S2 - S1 S1^T and h = n (sum g w) - S1 (sum w) exactly in 128 bits, each entry rounded once to double.  N a = h is solved by
+ * the 3 x 3 Cholesky factorisation of pcreg_amd/csrc/sphere_fit.hpp, in the order written there: L00 = sqrt(N00); L10 = N01 / L00;
+ * L20 = N02 / L00; L11 = sqrt(N11 - L10 L10); L21 = (N12 - L20 L10) / L11; L22 = sqrt((N22 - L20 L20) - L21 L21); y0 = h0 / L00;
+ * y1 = (h1 - L10 y0) / L11; y2 = ((h2 - L20 y0) - L21 y1) / L22; a2 = y2 / L22; a1 = (y1 - L21 a2) / L11;
+ * a0 = ((y0 - L10 a1) - L20 a2) / L00.  Then c_g = a / 2; beta = ((double)sum w - ((a0 S1x + a1 S1y) + a2 S1z)) / n;
+ * R_g^2 = beta + ((c_gx c_gx + c_gy c_gy) + c_gz c_gz); centre = (double)p_0 + c_g 2^-(17 - e); R = sqrt(R_g^2) 2^-(17 - e).
+ * The refit is USED iff every radicand of the factorisation is a finite number above 0, R_g^2 is a finite number above 0, centre
+ * and R are finite and min_radius <= (float)R <= max_radius.  Otherwise the round's sphere is the trial's own ((double)cf,
+ * (double)Rf) and refit_used[p] = 0.
+ * THE FINAL CLASSIFICATION, over the alive rows: the scoring chain with (float)centre and (float)R.  The passing rows get label
+ * p + 1 and leave the alive set; count_p is their number, Q_p the sum of their q, and
+ * rmse_p = sqrt(((double)Q_p / count_p) * ((double)t2 * 2^-20)).
+ * outputs -- labels [M] int32 by original row (0: no sphere); spheres [P][4] double ROW-major (cx, cy, cz, R); counts [P] int32;
+ * rmse [P]; refit_used [P] int32; *n_spheres; the diagnostics best_trial [P] int32 (0-based), best_cost [P] int64, best_count [P]
+ * int32, each may be NULL.  Entries of rounds that did not run are zero.  M = 0 writes *n_spheres = 0 and zeros.
+ * Every sum across rows is an integer sum, so every output is the same bits on every call and on every stream, whatever the
+ * workspace held before; under a caller's sample table (mapped with the rows) they are also the same bits for ANY ORDER OF THE
+ * ROWS, labels following their rows.
+ * PCREG_E_ARG, before anything runs: M >= 2^26; t or t2 zero, negative, subnormal, infinite or NaN; min_radius negative or NaN,
+ * max_radius below min_radius or NaN; P, B or min_inliers out of range; model or n_spheres NULL; labels, spheres, counts, rmse or
+ * refit_used NULL with M > 0; a sample table entry is never an error (the trial is void). */
+int pcreg_model_fit_spheres_f32(pcreg_model* model, float max_distance, float min_radius, float max_radius, int max_spheres, int n_trials,
+                                int min_inliers, uint64_t seed, const int32_t* samples /* [P][B][4] or NULL */, int32_t* labels /* [M] */,
+                                double* spheres /* [P][4] */, int32_t* counts /* [P] */, double* rmse /* [P] */,
+                                int32_t* refit_used /* [P] */, int32_t* n_spheres, int32_t* best_trial /* or NULL */,
+                                int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */);
+/* The same without a handle (pcfitsphere(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG:
+ * M < 0, ldm < M, m NULL with M > 0. */
+int pcreg_point_fit_spheres_f32(const float* m, int M, int ldm, float max_distance, float min_radius, float max_radius, int max_spheres,
+                                int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* spheres,
+                                int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial,
+                                int64_t* best_cost, int32_t* best_count);
+
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
  * the smallest index represents its run (MATLAB's default 'first').  ia [n]: the 1-based indices of the representatives in sorted
@@ -911,6 +975,24 @@ int pcreg_dev_model_fit_planes_f32(const pcreg_dev_model* model, float max_dista
                                    int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial /* or NULL */,
                                    int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* pcreg_model_fit_spheres_f32's contract on the device: samples [P][B][4] (or NULL), labels, spheres, counts, rmse,
+ * refit_used, n_spheres (one int32) and the diagnostics are device pointers, NULL as there; a sample s names original row
+ * s - idx_base.  The rows are read through the pointer the handle was created on.  Two launches (reset; alive bytes, labels and the
+ * box of the finite rows), then nine per round: the two launches of the chunk scan that list the alive rows with their coordinates,
+ * the hypotheses, the scoring (lane = trial over 2048 staged rows, one integer atomic pair per chunk and trial), the selection, the
+ * refit's seventeen integer sums (one set of atomics a workgroup), its 128-bit epilogue with the solve, the classification and the
+ * round's totals.  A device word says that extraction has ended; every later launch reads it and returns.  Nothing synchronises,
+ * nothing is cleared by a memset, no floating-point atomic, no workgroup waits for another.  Workspace, with R = max(M, 1),
+ * C = max(ceil(M / 2048), 1) and T = n_trials:
+ * 9984 + roundup(R, 256) + roundup(4 C, 256) + 4 roundup(4 R, 256) + roundup(12 T, 256) + roundup(16 T, 256) + roundup(T, 256) +
+ * roundup(8 T, 256) + roundup(4 T, 256) bytes; a workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams
+ * at once, each call with its own workspace. */
+size_t pcreg_dev_model_fit_spheres_workspace(int M, int n_trials);
+int pcreg_dev_model_fit_spheres_f32(const pcreg_dev_model* model, float max_distance, float min_radius, float max_radius, int max_spheres,
+                                    int n_trials, int min_inliers, uint64_t seed, const int32_t* samples /* or NULL */, int32_t idx_base,
+                                    int32_t* labels, double* spheres, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres,
+                                    int32_t* best_trial /* or NULL */, int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

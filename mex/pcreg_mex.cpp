@@ -81,6 +81,18 @@
 //                                          samples [] or int32 3 x (nTrials * maxPlanes), 1-based rows, column p * nTrials + b the trial
 //                                          b of round p; all always passed; outputs after the first are built only when asked for
 //                                          (matlab/fitPlanesModel.m, matlab/fitPlanesFast.m, matlab/pcfitplaneFast.m)
+//   'modelFitSpheres', handle, maxDistance, minRadius, maxRadius, maxSpheres, nTrials, minInliers, seed, samples | 'pointFitSpheres',
+//                                          pts (single M x 3), maxDistance, ... -> labels (M x 1 int32: sphere p's rows carry p, 0 is no
+//                                          sphere), spheres (n x 4 double: cx cy cz R), counts (n x 1 int32), rmse (n x 1 double),
+//                                          refitUsed (n x 1 int32: 0 where the round kept its winning trial's own sphere), diag
+//                                          (maxSpheres x 3 double: every round's winning trial, 1-based and 0 for none, its MSAC cost and
+//                                          its inlier count): pcfitsphere and the fit / remove / fit-again loop in this library's rule
+//                                          (pcreg_model_fit_spheres_f32) -- maxDistance a single scalar (finite, normal, > 0); minRadius
+//                                          and maxRadius single scalars, 0 <= minRadius <= maxRadius, maxRadius may be Inf; maxSpheres
+//                                          1 .. 64, nTrials 1 .. 2^20, minInliers >= 4 and seed >= 0 whole doubles; samples [] or int32
+//                                          4 x (nTrials * maxSpheres), 1-based rows, column p * nTrials + b the trial b of round p; all
+//                                          always passed; outputs after the first are built only when asked for
+//                                          (matlab/fitSpheresModel.m, matlab/fitSpheresFast.m, matlab/pcfitsphereFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -348,6 +360,68 @@ static int planes_on_handle(pcreg_model* h, const mxArray* const* a, int nout, m
     if (nout > 4) {
         out[4] = mxCreateDoubleMatrix((size_t)n, 1, mxREAL);
         for (int i = 0; i < n; ++i) mxGetPr(out[4])[i] = rmse[(size_t)i];
+    }
+    if (nout > 5) {
+        out[5] = mxCreateDoubleMatrix((size_t)P, 3, mxREAL);
+        double* d = mxGetPr(out[5]);
+        const bool ran_more = n < P;                              // round n ran too and ended the extraction: its diagnostics are real
+        for (int i = 0; i < P; ++i) {
+            const bool ran = i < n || (ran_more && i == n && M > 0);
+            d[i] = ran ? (double)bt[(size_t)i] + 1.0 : 0.0;
+            d[(size_t)i + (size_t)P] = (double)bc[(size_t)i];
+            d[(size_t)i + 2 * (size_t)P] = (double)bn[(size_t)i];
+        }
+    }
+    return rc;
+}
+
+// the parameters of the sphere commands, prhs[0 .. 7]: maxDistance (single scalar, finite, normal, > 0), minRadius and maxRadius (single
+// scalars, 0 <= minRadius <= maxRadius), maxSpheres, nTrials, minInliers, seed (whole doubles in range), samples ([] or int32 4 x nTrials *
+// maxSpheres)
+static bool fit_spheres_args_ok(const mxArray* const* a) {
+    for (int k = 0; k < 3; ++k)
+        if (!mxIsSingle(a[k]) || mxGetM(a[k]) * mxGetN(a[k]) != 1) return false;
+    const float t = *(const float*)mxGetData(a[0]), r0 = *(const float*)mxGetData(a[1]), r1 = *(const float*)mxGetData(a[2]);
+    if (!(t >= 1.17549435e-38f && t <= 3.40282347e+38f)) return false;
+    if (!(r0 >= 0.0f && r0 <= r1)) return false;                   // (a NaN fails)
+    if (!whole_in(a[3], 1.0, 64.0) || !whole_in(a[4], 1.0, 1048576.0) || !whole_in(a[5], 4.0, 2147483647.0) ||
+        !whole_in(a[6], 0.0, 9007199254740992.0))
+        return false;
+    if (mxIsEmpty(a[7])) return true;
+    return mxIsInt32(a[7]) && mxGetM(a[7]) == 4 && mxGetN(a[7]) == (size_t)mxGetScalar(a[3]) * (size_t)mxGetScalar(a[4]);
+}
+// the outputs of 'modelFitSpheres' / 'pointFitSpheres' (see the head of this file).  Nothing is left allocated on an error.
+static int fit_spheres_on_handle(pcreg_model* h, const mxArray* const* a, int nout, mxArray* out[6]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    const int P = (int)mxGetScalar(a[3]);
+    mxArray* ol = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    std::vector<double> spheres(4 * (size_t)P), rmse((size_t)P);
+    std::vector<int32_t> counts((size_t)P), used((size_t)P), bt((size_t)P), bn((size_t)P);
+    std::vector<int64_t> bc((size_t)P);
+    int32_t n = 0;
+    rc = pcreg_model_fit_spheres_f32(h, *(const float*)mxGetData(a[0]), *(const float*)mxGetData(a[1]), *(const float*)mxGetData(a[2]), P,
+                                     (int)mxGetScalar(a[4]), (int)mxGetScalar(a[5]), (uint64_t)mxGetScalar(a[6]),
+                                     mxIsEmpty(a[7]) ? nullptr : (const int32_t*)mxGetData(a[7]), M > 0 ? (int32_t*)mxGetData(ol) : nullptr,
+                                     spheres.data(), counts.data(), rmse.data(), used.data(), &n, bt.data(), bc.data(), bn.data());
+    if (rc != PCREG_OK) { mxDestroyArray(ol); return rc; }
+    out[0] = ol;
+    if (nout > 1) {                                               // the library's rows transposed into MATLAB's columns
+        out[1] = mxCreateDoubleMatrix((size_t)n, 4, mxREAL);
+        for (int c = 0; c < 4; ++c) for (int i = 0; i < n; ++i) mxGetPr(out[1])[(size_t)i + (size_t)c * (size_t)n] = spheres[(size_t)i * 4 + c];
+    }
+    if (nout > 2) {
+        out[2] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        for (int i = 0; i < n; ++i) ((int32_t*)mxGetData(out[2]))[i] = counts[(size_t)i];
+    }
+    if (nout > 3) {
+        out[3] = mxCreateDoubleMatrix((size_t)n, 1, mxREAL);
+        for (int i = 0; i < n; ++i) mxGetPr(out[3])[i] = rmse[(size_t)i];
+    }
+    if (nout > 4) {
+        out[4] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        for (int i = 0; i < n; ++i) ((int32_t*)mxGetData(out[4]))[i] = used[(size_t)i];
     }
     if (nout > 5) {
         out[5] = mxCreateDoubleMatrix((size_t)P, 3, mxREAL);
@@ -987,6 +1061,44 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
             mxArray* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
             if (rc == PCREG_OK) rc = planes_on_handle(h, prhs + 2, nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+            }
+        }
+    } else if (!strcmp(cmd, "modelFitSpheres")) {             // [labels, spheres, counts, rmse, refitUsed, diag] = pcreg_mex('modelFitSpheres', h, t, rmin, rmax, P, B, minInl, seed, samples)
+        if (nrhs != 10 || !mxIsUint64(prhs[1]) || !fit_spheres_args_ok(prhs + 2))
+            usage = "modelFitSpheres: handle (uint64), maxDistance (a single scalar: finite, normal, > 0), minRadius and maxRadius (single scalars, 0 <= minRadius <= maxRadius), "
+                    "maxSpheres (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 4), seed (a whole number >= 0), samples ([] or int32 4 x nTrials * "
+                    "maxSpheres)";
+        else {
+            mxArray* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            rc = fit_spheres_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), prhs + 2, nlhs, out);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+            }
+        }
+    } else if (!strcmp(cmd, "pointFitSpheres")) {             // [labels, spheres, counts, rmse, refitUsed, diag] = pcreg_mex('pointFitSpheres', single(pts), t, rmin, rmax, P, B, minInl, seed, samples)
+        if (nrhs != 10 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !fit_spheres_args_ok(prhs + 2))
+            usage = "pointFitSpheres: pts (single M x 3), maxDistance (a single scalar: finite, normal, > 0), minRadius and maxRadius (single scalars, 0 <= minRadius <= maxRadius), "
+                    "maxSpheres (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 4), seed (a whole number >= 0), samples ([] or int32 4 x nTrials * "
+                    "maxSpheres)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = fit_spheres_on_handle(h, prhs + 2, nlhs, out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) {
                 plhs[0] = out[0];

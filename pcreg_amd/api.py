@@ -841,6 +841,73 @@ def point_fit_planes(pts, max_distance, ref_vec=None, max_angle=math.pi / 2, max
                                                                           ang, P, B, mi, sd, smp.ctypes.data if smp is not None else None, *o)), M, P)
 
 
+def fit_spheres_args(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed):
+    """The sphere extraction's parameters as the C tiers take them (pcreg_model_fit_spheres_f32's rules): max_distance as a float32
+    whose fp32 square is a normal number, the radius bounds as float32 with 0 <= min_radius <= max_radius (max_radius may be inf),
+    and the ranges of the counts."""
+    t = np.float32(max_distance)
+    tiny = np.finfo(np.float32).tiny
+    with np.errstate(over="ignore", under="ignore"):
+        t2 = t * t
+    if not (np.isfinite(t) and t >= tiny and np.isfinite(t2) and t2 >= tiny):
+        raise ValueError(f"max_distance must be a finite number > 0 whose float32 square is a normal number, got {max_distance}")
+    with np.errstate(over="ignore"):
+        r0, r1 = np.float32(min_radius), np.float32(max_radius)
+    if not (r0 >= 0 and r0 <= r1):
+        raise ValueError(f"the radius bounds must satisfy 0 <= min_radius <= max_radius, got {min_radius}, {max_radius}")
+    P, B, mi = int(max_spheres), int(n_trials), int(min_inliers)
+    if not 1 <= P <= 64:
+        raise ValueError(f"max_spheres must lie in 1 .. 64, got {P}")
+    if not 1 <= B <= 1 << 20:
+        raise ValueError(f"n_trials must lie in 1 .. 2^20, got {B}")
+    if mi < 4:
+        raise ValueError(f"min_inliers must be at least 4, got {mi}")
+    return float(t), float(r0), float(r1), P, B, mi, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _fit_spheres_samples(samples, P, B):
+    if samples is None:
+        return None
+    smp = np.ascontiguousarray(np.asarray(samples, np.int32))
+    if smp.shape != (P, B, 4):
+        raise ValueError(f"samples must be [max_spheres, n_trials, 4] = {(P, B, 4)}, got {smp.shape}")
+    return smp
+
+
+def _fit_spheres_call(call, M: int, P: int) -> dict:
+    labels = np.zeros(max(M, 1), dtype=np.int32)
+    spheres = np.zeros((P, 4), dtype=np.float64)
+    counts = np.zeros(P, dtype=np.int32)
+    rmse = np.zeros(P, dtype=np.float64)
+    used = np.zeros(P, dtype=np.int32)
+    bt = np.zeros(P, dtype=np.int32)
+    bc = np.zeros(P, dtype=np.int64)
+    bn = np.zeros(P, dtype=np.int32)
+    n = C.c_int32(0)
+    call(labels.ctypes.data, spheres.ctypes.data, counts.ctypes.data, rmse.ctypes.data, used.ctypes.data, C.byref(n), bt.ctypes.data,
+         bc.ctypes.data, bn.ctypes.data)
+    return dict(n_spheres=int(n.value), labels=labels[:M], spheres=spheres, counts=counts, rmse=rmse, refit_used=used, best_trial=bt,
+                best_cost=bc, best_count=bn)
+
+
+def point_fit_spheres(pts, max_distance, min_radius: float = 0.0, max_radius: float = math.inf, max_spheres: int = 1,
+                      n_trials: int = 1000, min_inliers: int = 4, seed: int = 0, samples=None) -> dict:
+    """pcfitsphere(pts, maxDistance) and the fit / remove / fit-again loop, up to max_spheres times in one call, in this library's
+    rule (pcreg_model_fit_spheres_f32's contract): a dict with n_spheres; labels [M] int32 (sphere p's rows carry p + 1, 0 is no
+    sphere); spheres [P, 4] float64 (cx, cy, cz, R); counts [P]; rmse [P]; refit_used [P] (0: the round kept its winning trial's own
+    sphere); and the diagnostics best_trial / best_cost / best_count [P] of every round's winning MSAC trial.  Only trial spheres
+    with min_radius <= R <= max_radius count.  samples, int32 [max_spheres, n_trials, 4], replaces the sampler with the caller's
+    1-BASED rows.  The cloud is prepared for this call only: keep a Model for repeated calls."""
+    t, r0, r1, P, B, mi, sd = fit_spheres_args(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed)
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    smp = _fit_spheres_samples(samples, P, B)
+    return _fit_spheres_call(lambda *o: check(lib().pcreg_point_fit_spheres_f32(m.ctypes.data, M, max(M, 1), t, r0, r1, P, B, mi, sd,
+                                                                                smp.ctypes.data if smp is not None else None, *o)), M, P)
+
+
 def _denoise_args(k, threshold):
     k, threshold = int(k), float(threshold)
     if not 1 <= k <= KNN_MAX_K - 1:
@@ -1130,6 +1197,16 @@ class Model:
         smp = _planes_samples(samples, P, B)
         return _planes_call(lambda *o: check(lib().pcreg_model_fit_planes_f32(self._h, t, rv.ctypes.data if rv is not None else None, ang, P, B, mi,
                                                                               sd, smp.ctypes.data if smp is not None else None, *o)), self.M, P)
+
+    def fit_spheres(self, max_distance, min_radius: float = 0.0, max_radius: float = math.inf, max_spheres: int = 1,
+                    n_trials: int = 1000, min_inliers: int = 4, seed: int = 0, samples=None) -> dict:
+        """MSAC sphere fitting and extraction over the prepared model's own rows -- point_fit_spheres's dict and contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        t, r0, r1, P, B, mi, sd = fit_spheres_args(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed)
+        smp = _fit_spheres_samples(samples, P, B)
+        return _fit_spheres_call(lambda *o: check(lib().pcreg_model_fit_spheres_f32(self._h, t, r0, r1, P, B, mi, sd,
+                                                                                    smp.ctypes.data if smp is not None else None, *o)), self.M, P)
 
     def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
         """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold

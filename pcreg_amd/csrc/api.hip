@@ -460,6 +460,19 @@ int pcreg_dev_model_fit_planes_f32(const pcreg_dev_model* model, float max_dista
                                    planes, centres, counts, rmse, n_planes, best_trial, best_cost, best_count, workspace, workspace_bytes,
                                    (hipStream_t)stream);
 }
+size_t pcreg_dev_model_fit_spheres_workspace(int M, int n_trials) { return fit_spheres_ws_bytes(M, n_trials); }
+int pcreg_dev_model_fit_spheres_f32(const pcreg_dev_model* model, float max_distance, float min_radius, float max_radius, int max_spheres,
+                                    int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t idx_base, int32_t* labels,
+                                    double* spheres, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres,
+                                    int32_t* best_trial, int64_t* best_cost, int32_t* best_count, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    PCREG_ARG(model && workspace && n_spheres && fit_spheres_args_ok(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers));
+    PCREG_ARG(workspace_bytes >= fit_spheres_ws_bytes(0, n_trials));           // (the smallest any model needs; the launcher checks this model's)
+    GUARD();
+    return launch_model_fit_spheres(model->v, max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed, samples, idx_base,
+                                    labels, spheres, counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -1057,6 +1070,83 @@ int pcreg_point_fit_planes_f32(const float* m, int M, int ldm, float max_distanc
     TRY(launch_model_prepare(v, g_stream));
     return planes_on_view(st, v, max_distance, ref_vec, max_angle, max_planes, n_trials, min_inliers, seed, samples, labels, planes, centres, counts,
                           rmse, n_planes, best_trial, best_cost, best_count);
+}
+
+// sphere extraction on a prepared model's own rows: the chain on the device, then ONE read of everything
+static int fit_spheres_on_view(Stage& st, const ModelView& v, float t, float min_radius, float max_radius, int P, int B, int min_inliers,
+                               uint64_t seed, const int32_t* samples, int32_t* labels, double* spheres, int32_t* counts, double* rmse,
+                               int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial, int64_t* best_cost, int32_t* best_count) {
+    const int M = v.M;
+    *n_spheres = 0;
+    if (M == 0) {
+        for (int i = 0; i < P; ++i) {
+            if (spheres) for (int c = 0; c < 4; ++c) spheres[4 * i + c] = 0.0;
+            if (counts) counts[i] = 0;
+            if (rmse) rmse[i] = 0.0;
+            if (refit_used) refit_used[i] = 0;
+            if (best_trial) best_trial[i] = 0;
+            if (best_cost) best_cost[i] = 0;
+            if (best_count) best_count[i] = 0;
+        }
+        return PCREG_OK;
+    }
+    int32_t *dlab, *dcnt, *dru, *dnp, *dbt, *dbn, *dsmp; double *dsp, *drm; int64_t* dbc; char* ws;
+    const size_t wsb = fit_spheres_ws_bytes(M, B), ns = samples ? (size_t)P * (size_t)B * 4 : 0;
+    TRY(st.take((size_t)M, &dlab));
+    TRY(st.take(4 * (size_t)P, &dsp));
+    TRY(st.take((size_t)P, &dcnt));
+    TRY(st.take((size_t)P, &drm));
+    TRY(st.take((size_t)P, &dru));
+    TRY(st.take(1, &dnp));
+    TRY(st.take((size_t)P, &dbt));
+    TRY(st.take((size_t)P, &dbc));
+    TRY(st.take((size_t)P, &dbn));
+    TRY(st.take(ns, &dsmp));
+    TRY(st.take(wsb, &ws));
+    if (samples) PCREG_HIP(hipMemcpyAsync(dsmp, samples, sizeof(int32_t) * ns, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_model_fit_spheres(v, t, min_radius, max_radius, P, B, min_inliers, seed, samples ? dsmp : nullptr, 1, dlab, dsp, dcnt, drm, dru, dnp,
+                                 dbt, dbc, dbn, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(labels, dlab, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(spheres, dsp, sizeof(double) * 4 * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(counts, dcnt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(rmse, drm, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(refit_used, dru, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(n_spheres, dnp, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    if (best_trial) PCREG_HIP(hipMemcpyAsync(best_trial, dbt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_cost) PCREG_HIP(hipMemcpyAsync(best_cost, dbc, sizeof(int64_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_count) PCREG_HIP(hipMemcpyAsync(best_count, dbn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_fit_spheres_f32(pcreg_model* model, float max_distance, float min_radius, float max_radius, int max_spheres, int n_trials,
+                                int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* spheres, int32_t* counts,
+                                double* rmse, int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial, int64_t* best_cost,
+                                int32_t* best_count) {
+    PCREG_ARG(model && n_spheres && fit_spheres_args_ok(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers));
+    PCREG_ARG(model->dm != nullptr && model->M < fit_spheres_max_rows() &&
+              ((labels && spheres && counts && rmse && refit_used) || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return fit_spheres_on_view(st, model->dm->v, max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed, samples, labels,
+                               spheres, counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count);
+}
+int pcreg_point_fit_spheres_f32(const float* m, int M, int ldm, float max_distance, float min_radius, float max_radius, int max_spheres,
+                                int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* spheres,
+                                int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial,
+                                int64_t* best_cost, int32_t* best_count) {
+    PCREG_ARG(M >= 0 && ldm >= M && M < fit_spheres_max_rows() && n_spheres &&
+              fit_spheres_args_ok(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers) &&
+              (M == 0 || (m && labels && spheres && counts && rmse && refit_used)));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return fit_spheres_on_view(st, v, max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed, samples, labels, spheres,
+                               counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

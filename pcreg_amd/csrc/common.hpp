@@ -267,6 +267,17 @@ int launch_model_fit_planes(const ModelView& v, float max_distance, const double
                             int min_inliers, unsigned long long seed, const int32_t* samples, int32_t idx_base, int32_t* labels,
                             double* planes, double* centres, int32_t* counts, double* rmse, int32_t* n_planes, int32_t* best_trial,
                             int64_t* best_cost, int32_t* best_count, void* ws, size_t ws_bytes, hipStream_t st);
+// MSAC sphere fitting and extraction over the model's own rows (knn_fitsphere.hip): labels [M] by ORIGINAL row, spheres
+// [P][4] (cx, cy, cz, R), counts [P], rmse [P], refit_used [P], n_spheres and the diagnostics best_trial / best_cost / best_count [P]
+// (each may be null) -- device pointers; samples [P][B][4] on the device or null.  fit_spheres_args_ok and fit_spheres_max_rows are
+// the argument rules every tier checks before it touches the device
+size_t fit_spheres_ws_bytes(int M, int B);
+bool fit_spheres_args_ok(float max_distance, float min_radius, float max_radius, int max_spheres, int n_trials, int min_inliers);
+int fit_spheres_max_rows();
+int launch_model_fit_spheres(const ModelView& v, float max_distance, float min_radius, float max_radius, int max_spheres, int n_trials,
+                             int min_inliers, unsigned long long seed, const int32_t* samples, int32_t idx_base, int32_t* labels,
+                             double* spheres, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial,
+                             int64_t* best_cost, int32_t* best_count, void* ws, size_t ws_bytes, hipStream_t st);
 // unique(A, 'rows') of n x 3 doubles and the aggregation of matches on it (unique_rows.hip): tile sort, merge passes, compaction
 size_t unique_rows3_ws_bytes(int n_cap);
 int launch_unique_rows3(const double* A, const int32_t* n_dev, int n_cap, int ld, int32_t idx_base, int32_t* ia, int32_t* n_unique, void* ws,

@@ -426,6 +426,45 @@ class PreparedModel:
                                                        opt(bn), _p(ws), ws.numel(), _stream()))
         return dict(labels=lab, planes=pl, centres=ce, counts=cnt, rmse=rm, n_planes=n_pl, best_trial=bt, best_cost=bc, best_count=bn)
 
+    def fit_spheres(self, max_distance, min_radius: float = 0.0, max_radius: float = math.inf, max_spheres: int = 1,
+                    n_trials: int = 1000, min_inliers: int = 4, seed: int = 0, samples=None, idx_base: int = 0, out=None):
+        """MSAC sphere fitting and extraction over the model's own rows on torch's current stream (pcreg_dev_model_fit_spheres_f32;
+        the contract is pcreg_model_fit_spheres_f32's): -> a dict of device tensors -- labels [M] int32 (sphere p's rows carry
+        p + 1), spheres [P, 4] float64 (cx, cy, cz, R), counts [P] int32, rmse [P], refit_used [P] int32, n_spheres [1] int32 and
+        the diagnostics best_trial, best_cost (int64), best_count [P].  samples is an int32 device tensor [max_spheres, n_trials, 4]
+        of rows counted from idx_base, or None for the sampler.  Nothing synchronises: the caller reads n_spheres when it needs it.
+        The workspace is cached on the model and grown on demand; calls that may overlap on two streams pass buffers of their own,
+        out=(labels, spheres, counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count, ws) with ws of
+        pcreg_dev_model_fit_spheres_workspace(M, n_trials) bytes."""
+        from .api import fit_spheres_args
+        t, r0, r1, P, B, mi, sd = fit_spheres_args(max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed)
+        dev, M = self.tensor.device, self.M
+        if samples is not None and (samples.dtype != torch.int32 or tuple(samples.shape) != (P, B, 4) or not samples.is_contiguous()
+                                    or samples.device != dev):
+            raise ValueError(f"samples must be a contiguous int32 tensor {(P, B, 4)} on the model's device")
+        need = max(int(lib().pcreg_dev_model_fit_spheres_workspace(M, B)), 256)
+        if out is not None:
+            lab, sp, cnt, rm, used, n_sp, bt, bc, bn, ws = out
+        else:
+            lab = torch.empty(M, dtype=torch.int32, device=dev)
+            sp = torch.empty((P, 4), dtype=torch.float64, device=dev)
+            cnt = torch.empty(P, dtype=torch.int32, device=dev)
+            rm = torch.empty(P, dtype=torch.float64, device=dev)
+            used = torch.empty(P, dtype=torch.int32, device=dev)
+            n_sp = torch.empty(1, dtype=torch.int32, device=dev)
+            bt = torch.empty(P, dtype=torch.int32, device=dev)
+            bc = torch.empty(P, dtype=torch.int64, device=dev)
+            bn = torch.empty(P, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_fit_spheres_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fit_spheres_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda x: _p(x) if x is not None and x.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_fit_spheres_f32(self.handle, t, r0, r1, P, B, mi, sd, opt(samples), int(idx_base), opt(lab), opt(sp),
+                                                        opt(cnt), opt(rm), opt(used), opt(n_sp), opt(bt), opt(bc), opt(bn), _p(ws), ws.numel(),
+                                                        _stream()))
+        return dict(labels=lab, spheres=sp, counts=cnt, rmse=rm, refit_used=used, n_spheres=n_sp, best_trial=bt, best_cost=bc, best_count=bn)
+
     def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
         """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
         (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]
