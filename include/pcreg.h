@@ -572,6 +572,90 @@ int pcreg_point_fit_spheres_f32(const float* m, int M, int ldm, float max_distan
                                 int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres, int32_t* best_trial,
                                 int64_t* best_cost, int32_t* best_count);
 
+/* MSAC cylinder fitting and cylinder extraction over the rows of the model and their normals (MATLAB's pcfitcylinder(ptCloud,
+ * maxDistance[, referenceVector, maxAngularDistance]) and the loop over it: fit, take the inliers out, fit again -- up to
+ * max_cylinders times in one call; the instrument shafts, sleeves, trocars and rods of a scan).  THE CONTRACT of every tier (device,
+ * host, MEX, Python) is THIS TEXT; MATLAB's bits are not knowable here.
+ * inputs -- a prepared model of M fp32 rows, M < 2^26; max_distance t, t2 and s, min_radius and max_radius, max_cylinders P in
+ * 1 .. 64, n_trials B in 1 .. 2^20, min_inliers >= 4 and seed under pcreg_model_fit_spheres_f32's rules; ref_vec (three doubles or
+ * NULL) and max_angle (radians) under pcreg_model_fit_planes_f32's rules (finite, nonzero, 0 < max_angle <= pi / 2; max_angle is
+ * not read without ref_vec): here they bound the AXIS; normals, host M x 3 fp32 column-major with leading dimension ldn >= M, or
+ * NULL: then they are computed once in the call by pcreg_model_normals_f32's chain with k_normals (3 .. 32) and no viewpoint;
+ * samples, int32 [P][B][2] or NULL: 1-BASED original rows at this tier.
+ * ALIVE ROWS, THE QUANTISATION SCALE e and THE ROUND STRUCTURE are pcreg_model_fit_spheres_f32's: initially the rows whose three
+ * coordinates are finite; e frexp's exponent of the largest axis extent of the finite rows; round p = 0 .. P - 1 over the alive set
+ * A_p listed ascending by original row, nA rows.
+ * USABLE NORMALS.  A row's normal is usable iff its three components are finite and each is at most 2 in magnitude.  The normals
+ * are used as given, not renormalised.  A row with an unusable normal stays alive and may be an inlier (scoring reads no normal);
+ * it is void as a sample and is left out of the axis sums.
+ * Trial b has rows i_0, i_1: from samples[p][b][j] when the table is given, else i_j = A_p[h_j % nA] with
+ * h_j = splitmix64(seed ^ splitmix64(((uint64)p * B + b) * 4 + j)), j = 0, 1, splitmix64 as at pcreg_model_fit_planes_f32.
+ * THE TRIAL'S CYLINDER, from p_0, p_1 and their normals n_0, n_1 widened to double, every step ONE correctly rounded operation, no
+ * contraction, in this order: W = n_0 x n_1, each component fl(fl(a b) - fl(c d)); L2 = (Wx Wx + Wy Wy) + Wz Wz; w = W / sqrt(L2),
+ * three divisions; THE SIGN of w: with ref_vec, dot = (wx rx + wy ry) + wz rz, w is negated when dot < 0, and the trial is void
+ * when |dot| / |ref| < cos(max_angle) (|ref| = sqrt((rx rx + ry ry) + rz rz)); without it the component of largest magnitude is
+ * made positive, the first of equals in x, y, z order.  d = p_1 - p_0; m = d x n_1; num = (mx Wx + my Wy) + mz Wz with the
+ * UNSIGNED W; s = num / L2; the axis point a = p_0 + s n_0 component by component, fl(p + fl(s n));
+ * R = |s| sqrt((n_0x n_0x + n_0y n_0y) + n_0z n_0z); in fp32 af = (float)a, wf = (float)w, Rf = (float)R.
+ * A trial is VOID if an index is out of range, a row is not alive, the two indices are equal, a normal is unusable, L2 is not a
+ * finite number above 0, any of s, a, R, af, wf, Rf is not finite, Rf < min_radius or Rf > max_radius, or the angle test fails.
+ * THE SIGN OF A NORMAL CHANGES NO BIT of any of this: negation is exact, W and num change sign together or not at all, and the
+ * refit below takes only products of two components of one normal.
+ * SCORING, per alive row, in fp32: d = row - af componentwise; the cross product with the axis cx = fmaf(d.y, wf.z, -(d.z * wf.y)),
+ * cy = fmaf(d.z, wf.x, -(d.x * wf.z)), cz = fmaf(d.x, wf.y, -(d.y * wf.x)); c2 = fmaf(cz, cz, fmaf(cy, cy, cx * cx)); rho = the
+ * correctly rounded fp32 square root of c2; r = rho - Rf; r2 = r * r; the row is an inlier iff r2 <= t2 (NaN never passes);
+ * q = min(2^20, (int)rintf(r2 * s)) for an inlier, 2^20 otherwise.  cost_b is the sum of q and count_b the number of inliers.
+ * THE BEST TRIAL and THE STOP RULE are pcreg_model_fit_spheres_f32's: among the non-void trials with count >= 4 the one of smallest
+ * cost, ties to the smallest b; no such trial, or its count < min_inliers: extraction ends with n_cylinders = p, the diagnostics of
+ * that last round still recorded (best_trial = -1, cost and count 0 where no trial was eligible).
+ * THE REFIT, in two exact passes over the best trial's inliers (pcreg_amd/csrc/cylinder_fit.hpp, in the order written there).
+ * PASS 1, THE AXIS, over the inliers with a usable normal: gn = rint((double)n_c 2^16) per component (|gn| <= 2^17); their number
+ * n_n and the six sums of gn_a gn_b (xx xy xz yy yz zz) are signed 64-bit integers (each below 2^60 at 2^26 rows), each rounded
+ * once to double; the library's cyclic Jacobi on that matrix, without centring (a cylinder's normals are perpendicular to its axis,
+ * so the axis minimises sum (n . w)^2), in cylinder_fit.hpp's form: jacobi_sym3's sweeps, operation for operation, with the
+ * cosine of a rotation c = 1 / sqrt(t t + 1) as two correctly rounded operations; the eigenvector column of the smallest diagonal
+ * entry, ties to the lowest index; signed by the rule above (the angle test is not repeated).  The basis of the cross-section: e_k
+ * the coordinate axis of w's smallest-magnitude component, first of equals; u = (w x e_k) / |w x e_k|; v = w x u.
+ * PASS 2, THE CIRCLE, over all inliers: g = rint((double)(row - p_0) 2^(17 - e)) per component, the difference taken in fp32;
+ * X = (gx ux + gy uy) + gz uz and Y likewise with v, in double without contraction; xi = rint(X), yi = rint(Y);
+ * w2 = xi xi + yi yi < 2^36, split as w2 = w_hi 2^18 + w_lo; eleven signed 64-bit sums: n, sum xi, sum yi, sum xi xi, sum xi yi,
+ * sum yi yi, sum w2, sum xi w_lo, sum xi w_hi, sum yi w_lo, sum yi w_hi.  N = n S2 - S1 S1^T (2 x 2) and
+ * h = n (sum xi w2, sum yi w2) - S1 (sum w2) exactly in 128 bits, each entry rounded once to double.  N a = h by the 2 x 2
+ * Cholesky factorisation: L00 = sqrt(N00); L10 = N01 / L00; L11 = sqrt(N11 - L10 L10); y0 = h0 / L00; y1 = (h1 - L10 y0) / L11;
+ * a1 = y1 / L11; a0 = (y0 - L10 a1) / L00.  Then c2 = a / 2; beta = ((double)sum w2 - (a0 S1x + a1 S1y)) / n;
+ * R_g^2 = beta + (c2x c2x + c2y c2y); centre = (double)p_0 + (c2x u + c2y v) 2^-(17 - e); R = sqrt(R_g^2) 2^-(17 - e).
+ * The refit is USED iff n_n >= 2, Jacobi's output, every radicand and R_g^2 are finite and the radicands and R_g^2 above 0,
+ * centre, w and R are finite and min_radius <= (float)R <= max_radius.  Otherwise the round's cylinder is the trial's own
+ * ((double)af, (double)wf, (double)Rf) and refit_used[p] = 0.
+ * THE FINAL CLASSIFICATION, over the alive rows: the scoring chain with (float)centre, (float)w and (float)R.  The passing rows get
+ * label p + 1 and leave the alive set; count_p is their number, Q_p the sum of their q,
+ * rmse_p = sqrt(((double)Q_p / count_p) * ((double)t2 * 2^-20)); h = fmaf(d.z, wf.z, fmaf(d.y, wf.y, d.x * wf.x)) of the passing
+ * rows gives h_lo and h_hi, its minimum and maximum (NaN, like rmse, where count_p is 0).
+ * outputs -- labels [M] int32 by original row (0: no cylinder); cylinders [P][7] double ROW-major (cx, cy, cz, wx, wy, wz, R);
+ * extents [P][2] double ((double)h_lo, (double)h_hi): the end points of the axis are c + h_lo w and c + h_hi w; counts [P] int32;
+ * rmse [P]; refit_used [P] int32; *n_cylinders; the diagnostics best_trial [P] int32 (0-based), best_cost [P] int64, best_count
+ * [P] int32, each may be NULL.  Entries of rounds that did not run are zero.  M = 0 writes *n_cylinders = 0 and zeros.
+ * Every sum across rows is an integer sum and min / max do not depend on order, so every output is the same bits on every call and
+ * on every stream, whatever the workspace held before; under a caller's sample table (mapped with the rows) they are also the same
+ * bits for ANY ORDER OF THE ROWS, labels following their rows.
+ * PCREG_E_ARG, before anything runs: pcreg_model_fit_spheres_f32's cases (with cylinders, extents among the outputs that may not
+ * be NULL with M > 0); ref_vec with a non-finite component or of zero length, or max_angle outside (0, pi / 2] with ref_vec given;
+ * normals given with ldn < M, normals NULL with k_normals outside 3 .. 32; a sample table entry is never an error. */
+int pcreg_model_fit_cylinders_f32(pcreg_model* model, float max_distance, float min_radius, float max_radius,
+                                  const double* ref_vec /* 3 or NULL */, double max_angle, const float* normals /* M x 3 or NULL */,
+                                  int ldn, int k_normals, int max_cylinders, int n_trials, int min_inliers, uint64_t seed,
+                                  const int32_t* samples /* [P][B][2] or NULL */, int32_t* labels /* [M] */,
+                                  double* cylinders /* [P][7] */, double* extents /* [P][2] */, int32_t* counts /* [P] */,
+                                  double* rmse /* [P] */, int32_t* refit_used /* [P] */, int32_t* n_cylinders,
+                                  int32_t* best_trial /* or NULL */, int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */);
+/* The same without a handle (pcfitcylinder(m, ...)): uploads and prepares the cloud for this call only.  Also PCREG_E_ARG:
+ * M < 0, ldm < M, m NULL with M > 0. */
+int pcreg_point_fit_cylinders_f32(const float* m, int M, int ldm, float max_distance, float min_radius, float max_radius,
+                                  const double* ref_vec, double max_angle, const float* normals, int ldn, int k_normals, int max_cylinders,
+                                  int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* cylinders,
+                                  double* extents, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_cylinders,
+                                  int32_t* best_trial, int64_t* best_cost, int32_t* best_count);
+
 /* [C, ia] = unique(A, 'rows') for n x 3 doubles (column-major, leading dimension ld >= n), the primitive of completeExperiment.m:439-443.
  * Rows are ordered lexicographically by column 1, 2, 3 as numbers (-0 == +0, -inf < finite < +inf); among equal rows the one with
  * the smallest index represents its run (MATLAB's default 'first').  ia [n]: the 1-based indices of the representatives in sorted
@@ -993,6 +1077,28 @@ int pcreg_dev_model_fit_spheres_f32(const pcreg_dev_model* model, float max_dist
                                     int32_t* labels, double* spheres, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_spheres,
                                     int32_t* best_trial /* or NULL */, int64_t* best_cost /* or NULL */, int32_t* best_count /* or NULL */,
                                     void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_fit_cylinders_f32's contract on the device: normals_dev [3][ldn] fp32 by original row, ldn >= M, as
+ * pcreg_dev_model_normals_f32 writes it (never NULL with M > 0); samples [P][B][2] (or NULL), labels, cylinders, extents, counts,
+ * rmse, refit_used, n_cylinders (one int32) and the diagnostics are device pointers, NULL as there; ref_vec is three HOST doubles
+ * or NULL; a sample s names original row s - idx_base.  The rows are read through the pointer the handle was created on.  Two
+ * launches (reset; alive bytes, usable-normal bytes, labels and the box of the finite rows), then eleven per round: the two
+ * launches of the chunk scan that list the alive rows with their coordinates, the hypotheses, the scoring (lane = trial over 2048
+ * staged rows, one integer atomic pair per chunk and trial), the selection, the axis pass' seven integer sums, the basis (Jacobi,
+ * w, u, v), the circle pass' eleven integer sums (one set of atomics a workgroup each), the 128-bit epilogue with the solve, the
+ * classification with the extent along the axis, and the round's totals.  A device word says that extraction has ended; every later
+ * launch reads it and returns.  Nothing synchronises, nothing is cleared by a memset, no floating-point atomic, no workgroup waits
+ * for another.  Workspace, with R = max(M, 1), C = max(ceil(M / 2048), 1) and T = n_trials:
+ * 11008 + 2 roundup(R, 256) + roundup(4 C, 256) + 4 roundup(4 R, 256) + roundup(12 T, 256) + roundup(28 T, 256) + roundup(T, 256) +
+ * roundup(8 T, 256) + roundup(4 T, 256) bytes; a workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams
+ * at once, each call with its own workspace. */
+size_t pcreg_dev_model_fit_cylinders_workspace(int M, int n_trials);
+int pcreg_dev_model_fit_cylinders_f32(const pcreg_dev_model* model, float max_distance, float min_radius, float max_radius,
+                                      const double* ref_vec /* 3 host doubles or NULL */, double max_angle, const float* normals_dev,
+                                      int ldn, int max_cylinders, int n_trials, int min_inliers, uint64_t seed,
+                                      const int32_t* samples /* or NULL */, int32_t idx_base, int32_t* labels, double* cylinders,
+                                      double* extents, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_cylinders,
+                                      int32_t* best_trial /* or NULL */, int64_t* best_cost /* or NULL */,
+                                      int32_t* best_count /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* matchFeatures' filter chain on that top-2 in ONE launch: threshold, ratio test, Unique back-check, ordered compaction
  * into 1-based pairs [k][2] and the matched coordinates pts1 / pts2 (n x 3 column-major doubles, ld = Q; both NULL to
  * skip) -- completeExperimentFast.m:205-206.  The handle holds the WHOLE model (one rank). */

@@ -93,6 +93,22 @@
 //                                          4 x (nTrials * maxSpheres), 1-based rows, column p * nTrials + b the trial b of round p; all
 //                                          always passed; outputs after the first are built only when asked for
 //                                          (matlab/fitSpheresModel.m, matlab/fitSpheresFast.m, matlab/pcfitsphereFast.m)
+//   'modelFitCylinders', handle, maxDistance, minRadius, maxRadius, refVec, maxAngle, normals, kNormals, maxCylinders, nTrials,
+//                                          minInliers, seed, samples | 'pointFitCylinders', pts (single M x 3), maxDistance, ... ->
+//                                          labels (M x 1 int32: cylinder p's rows carry p, 0 is no cylinder), cylinders (n x 7 double:
+//                                          cx cy cz wx wy wz R), extents (n x 2 double: h_lo h_hi along the axis from the centre),
+//                                          counts (n x 1 int32), rmse (n x 1 double), refitUsed (n x 1 int32: 0 where the round kept its
+//                                          winning trial's own cylinder), diag (maxCylinders x 3 double: every round's winning trial,
+//                                          1-based and 0 for none, its MSAC cost and its inlier count): pcfitcylinder and the fit /
+//                                          remove / fit-again loop in this library's rule (pcreg_model_fit_cylinders_f32) --
+//                                          maxDistance, minRadius, maxRadius as in 'modelFitSpheres'; refVec [] or a double 1 x 3 (finite,
+//                                          not all zero) and maxAngle a double scalar in RADIANS, in (0, pi / 2] when refVec is given:
+//                                          they bound the axis; normals single M x 3 or [] (then computed in the call from the kNormals
+//                                          nearest rows, a whole double 3 .. 32, always passed); maxCylinders 1 .. 64, nTrials 1 .. 2^20,
+//                                          minInliers >= 4 and seed >= 0 whole doubles; samples [] or int32 2 x (nTrials * maxCylinders),
+//                                          1-based rows, column p * nTrials + b the trial b of round p; all always passed; outputs after
+//                                          the first are built only when asked for (matlab/fitCylindersModel.m,
+//                                          matlab/fitCylindersFast.m, matlab/pcfitcylinderFast.m)
 //   'uniqueRows3', A (double n x 3)                        -> ia (u x 1 double, 1-based): [C, ia] = unique(A, 'rows'), C = A(ia, :)
 //                                          (rows ordered by column 1, 2, 3; first occurrences; NaN refused; matlab/uniqueRowsFast.m)
 //   'aggregateMatches', pts1, pts2 (double n x 3 each)   -> pts1u, pts2u (u x 3), ia (u x 1 double, 1-based rows of the input):
@@ -426,6 +442,84 @@ static int fit_spheres_on_handle(pcreg_model* h, const mxArray* const* a, int no
     if (nout > 5) {
         out[5] = mxCreateDoubleMatrix((size_t)P, 3, mxREAL);
         double* d = mxGetPr(out[5]);
+        const bool ran_more = n < P;                              // round n ran too and ended the extraction: its diagnostics are real
+        for (int i = 0; i < P; ++i) {
+            const bool ran = i < n || (ran_more && i == n && M > 0);
+            d[i] = ran ? (double)bt[(size_t)i] + 1.0 : 0.0;
+            d[(size_t)i + (size_t)P] = (double)bc[(size_t)i];
+            d[(size_t)i + 2 * (size_t)P] = (double)bn[(size_t)i];
+        }
+    }
+    return rc;
+}
+
+// the parameters of the cylinder commands, prhs[0 .. 11]: maxDistance, minRadius, maxRadius (single scalars as for the spheres), refVec
+// ([] or three finite doubles, not all zero), maxAngle (a double scalar, in (0, pi / 2] with refVec), normals ([] or single M x 3),
+// kNormals (3 .. 32), maxCylinders, nTrials, minInliers, seed (whole doubles in range), samples ([] or int32 2 x nTrials * maxCylinders)
+static bool fit_cylinders_args_ok(const mxArray* const* a, size_t M) {
+    for (int k = 0; k < 3; ++k)
+        if (!mxIsSingle(a[k]) || mxGetM(a[k]) * mxGetN(a[k]) != 1) return false;
+    const float t = *(const float*)mxGetData(a[0]), r0 = *(const float*)mxGetData(a[1]), r1 = *(const float*)mxGetData(a[2]);
+    if (!(t >= 1.17549435e-38f && t <= 3.40282347e+38f)) return false;
+    if (!(r0 >= 0.0f && r0 <= r1)) return false;                   // (a NaN fails)
+    if (!(mxIsEmpty(a[3]) || (mxIsDouble(a[3]) && mxGetM(a[3]) * mxGetN(a[3]) == 3))) return false;
+    if (!mxIsEmpty(a[3])) {                                       // finite and not all zero
+        const double* r = mxGetPr(a[3]);
+        for (int c = 0; c < 3; ++c) if (!(std::fabs(r[c]) <= 1.7976931348623157e308)) return false;
+        if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) return false;
+    }
+    if (!mxIsDouble(a[4]) || mxGetM(a[4]) * mxGetN(a[4]) != 1) return false;
+    if (!mxIsEmpty(a[3]) && !(mxGetScalar(a[4]) > 0.0 && mxGetScalar(a[4]) <= 1.5707963267948966)) return false;
+    if (!(mxIsEmpty(a[5]) || (mxIsSingle(a[5]) && mxGetM(a[5]) == M && mxGetN(a[5]) == 3))) return false;
+    if (!whole_in(a[6], 3.0, 32.0) || !whole_in(a[7], 1.0, 64.0) || !whole_in(a[8], 1.0, 1048576.0) ||
+        !whole_in(a[9], 4.0, 2147483647.0) || !whole_in(a[10], 0.0, 9007199254740992.0))
+        return false;
+    if (mxIsEmpty(a[11])) return true;
+    return mxIsInt32(a[11]) && mxGetM(a[11]) == 2 && mxGetN(a[11]) == (size_t)mxGetScalar(a[7]) * (size_t)mxGetScalar(a[8]);
+}
+// the outputs of 'modelFitCylinders' / 'pointFitCylinders' (see the head of this file).  Nothing is left allocated on an error.
+static int fit_cylinders_on_handle(pcreg_model* h, const mxArray* const* a, int nout, mxArray* out[7]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    if (!mxIsEmpty(a[5]) && mxGetM(a[5]) != (size_t)M) return PCREG_E_ARG;           // (a handle's rows are known only here)
+    const int P = (int)mxGetScalar(a[7]);
+    mxArray* ol = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    std::vector<double> cyl(7 * (size_t)P), ext(2 * (size_t)P), rmse((size_t)P);
+    std::vector<int32_t> counts((size_t)P), used((size_t)P), bt((size_t)P), bn((size_t)P);
+    std::vector<int64_t> bc((size_t)P);
+    int32_t n = 0;
+    rc = pcreg_model_fit_cylinders_f32(h, *(const float*)mxGetData(a[0]), *(const float*)mxGetData(a[1]), *(const float*)mxGetData(a[2]),
+                                       mxIsEmpty(a[3]) ? nullptr : mxGetPr(a[3]), mxGetScalar(a[4]),
+                                       mxIsEmpty(a[5]) ? nullptr : (const float*)mxGetData(a[5]), M > 0 ? M : 1, (int)mxGetScalar(a[6]), P,
+                                       (int)mxGetScalar(a[8]), (int)mxGetScalar(a[9]), (uint64_t)mxGetScalar(a[10]),
+                                       mxIsEmpty(a[11]) ? nullptr : (const int32_t*)mxGetData(a[11]), M > 0 ? (int32_t*)mxGetData(ol) : nullptr,
+                                       cyl.data(), ext.data(), counts.data(), rmse.data(), used.data(), &n, bt.data(), bc.data(), bn.data());
+    if (rc != PCREG_OK) { mxDestroyArray(ol); return rc; }
+    out[0] = ol;
+    if (nout > 1) {                                               // the library's rows transposed into MATLAB's columns
+        out[1] = mxCreateDoubleMatrix((size_t)n, 7, mxREAL);
+        for (int c = 0; c < 7; ++c) for (int i = 0; i < n; ++i) mxGetPr(out[1])[(size_t)i + (size_t)c * (size_t)n] = cyl[(size_t)i * 7 + c];
+    }
+    if (nout > 2) {
+        out[2] = mxCreateDoubleMatrix((size_t)n, 2, mxREAL);
+        for (int c = 0; c < 2; ++c) for (int i = 0; i < n; ++i) mxGetPr(out[2])[(size_t)i + (size_t)c * (size_t)n] = ext[(size_t)i * 2 + c];
+    }
+    if (nout > 3) {
+        out[3] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        for (int i = 0; i < n; ++i) ((int32_t*)mxGetData(out[3]))[i] = counts[(size_t)i];
+    }
+    if (nout > 4) {
+        out[4] = mxCreateDoubleMatrix((size_t)n, 1, mxREAL);
+        for (int i = 0; i < n; ++i) mxGetPr(out[4])[i] = rmse[(size_t)i];
+    }
+    if (nout > 5) {
+        out[5] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        for (int i = 0; i < n; ++i) ((int32_t*)mxGetData(out[5]))[i] = used[(size_t)i];
+    }
+    if (nout > 6) {
+        out[6] = mxCreateDoubleMatrix((size_t)P, 3, mxREAL);
+        double* d = mxGetPr(out[6]);
         const bool ran_more = n < P;                              // round n ran too and ended the extraction: its diagnostics are real
         for (int i = 0; i < P; ++i) {
             const bool ran = i < n || (ran_more && i == n && M > 0);
@@ -1107,6 +1201,48 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 if (out[3]) plhs[3] = out[3];
                 if (out[4]) plhs[4] = out[4];
                 if (out[5]) plhs[5] = out[5];
+            }
+        }
+    } else if (!strcmp(cmd, "modelFitCylinders")) {           // [labels, cylinders, extents, counts, rmse, refitUsed, diag] = pcreg_mex('modelFitCylinders', h, t, rmin, rmax, refVec, maxAngle, normals, kNormals, P, B, minInl, seed, samples)
+        if (nrhs != 14 || !mxIsUint64(prhs[1]) || !fit_cylinders_args_ok(prhs + 2, mxIsEmpty(prhs[7]) ? 0 : mxGetM(prhs[7])))
+            usage = "modelFitCylinders: handle (uint64), maxDistance (a single scalar: finite, normal, > 0), minRadius and maxRadius (single scalars, 0 <= minRadius <= maxRadius), "
+                    "refVec ([] or a double 1 x 3, finite, not all zero), maxAngle (a double scalar, radians, in (0, pi/2] with refVec), normals ([] or single M x 3), "
+                    "kNormals (3 .. 32), maxCylinders (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 4), seed (a whole number >= 0), samples ([] or int32 "
+                    "2 x nTrials * maxCylinders)";
+        else {
+            mxArray* out[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            rc = fit_cylinders_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), prhs + 2, nlhs, out);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+                if (out[6]) plhs[6] = out[6];
+            }
+        }
+    } else if (!strcmp(cmd, "pointFitCylinders")) {           // [labels, cylinders, extents, counts, rmse, refitUsed, diag] = pcreg_mex('pointFitCylinders', single(pts), t, rmin, rmax, refVec, maxAngle, normals, kNormals, P, B, minInl, seed, samples)
+        if (nrhs != 14 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !fit_cylinders_args_ok(prhs + 2, mxGetM(prhs[1])))
+            usage = "pointFitCylinders: pts (single M x 3), maxDistance (a single scalar: finite, normal, > 0), minRadius and maxRadius (single scalars, 0 <= minRadius <= maxRadius), "
+                    "refVec ([] or a double 1 x 3, finite, not all zero), maxAngle (a double scalar, radians, in (0, pi/2] with refVec), normals ([] or single M x 3), "
+                    "kNormals (3 .. 32), maxCylinders (1 .. 64), nTrials (1 .. 2^20), minInliers (>= 4), seed (a whole number >= 0), samples ([] or int32 "
+                    "2 x nTrials * maxCylinders)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = fit_cylinders_on_handle(h, prhs + 2, nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) {
+                plhs[0] = out[0];
+                if (out[1]) plhs[1] = out[1];
+                if (out[2]) plhs[2] = out[2];
+                if (out[3]) plhs[3] = out[3];
+                if (out[4]) plhs[4] = out[4];
+                if (out[5]) plhs[5] = out[5];
+                if (out[6]) plhs[6] = out[6];
             }
         }
     } else if (!strcmp(cmd, "uniqueRows3")) {                 // ia = pcreg_mex('uniqueRows3', A): [C, ia] = unique(A, 'rows') with C = A(ia, :)

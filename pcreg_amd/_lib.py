@@ -70,6 +70,7 @@ SYMBOLS = [
     "pcreg_model_iss_f32", "pcreg_point_iss_f32", "pcreg_dev_model_iss_workspace", "pcreg_dev_model_iss_f32",
     "pcreg_model_fit_planes_f32", "pcreg_point_fit_planes_f32", "pcreg_dev_model_fit_planes_workspace", "pcreg_dev_model_fit_planes_f32",
     "pcreg_model_fit_spheres_f32", "pcreg_point_fit_spheres_f32", "pcreg_dev_model_fit_spheres_workspace", "pcreg_dev_model_fit_spheres_f32",
+    "pcreg_model_fit_cylinders_f32", "pcreg_point_fit_cylinders_f32", "pcreg_dev_model_fit_cylinders_workspace", "pcreg_dev_model_fit_cylinders_f32",
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_downsample_grid_f32", "pcreg_dev_downsample_grid_workspace", "pcreg_dev_downsample_grid_chunk", "pcreg_dev_downsample_grid_f32",
@@ -190,6 +191,13 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_fit_spheres_f32.argtypes = [vp, f, f, f, i, i, i, u64, vp, i] + [vp] * 9 + [vp, C.c_size_t, vp]
             L.pcreg_model_fit_spheres_f32.argtypes = [vp, f, f, f, i, i, i, u64, vp] + [vp] * 9
             L.pcreg_point_fit_spheres_f32.argtypes = [vp, i, i, f, f, f, i, i, i, u64, vp] + [vp] * 9
+        if hasattr(L, "pcreg_dev_model_fit_cylinders_workspace"):   # (an older build given through PCREG_LIB lacks the cylinder extraction)
+            L.pcreg_dev_model_fit_cylinders_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_fit_cylinders_workspace.argtypes = [C.c_int, C.c_int]
+            vp, i, f, d, u64 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_uint64
+            L.pcreg_dev_model_fit_cylinders_f32.argtypes = [vp, f, f, f, vp, d, vp, i, i, i, i, u64, vp, i] + [vp] * 10 + [vp, C.c_size_t, vp]
+            L.pcreg_model_fit_cylinders_f32.argtypes = [vp, f, f, f, vp, d, vp, i, i, i, i, i, u64, vp] + [vp] * 10
+            L.pcreg_point_fit_cylinders_f32.argtypes = [vp, i, i, f, f, f, vp, d, vp, i, i, i, i, i, u64, vp] + [vp] * 10
         if hasattr(L, "pcreg_dev_model_refit_plane_workspace"):   # (an older build given through PCREG_LIB lacks the plane refit)
             L.pcreg_dev_model_refit_plane_workspace.restype = C.c_size_t
             L.pcreg_dev_model_refit_plane_workspace.argtypes = [C.c_int] * 3

@@ -908,6 +908,80 @@ def point_fit_spheres(pts, max_distance, min_radius: float = 0.0, max_radius: fl
                                                                                 smp.ctypes.data if smp is not None else None, *o)), M, P)
 
 
+def fit_cylinders_args(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders, n_trials, min_inliers, seed):
+    """The cylinder extraction's parameters as the C tiers take them (pcreg_model_fit_cylinders_f32's rules): fit_spheres_args' for
+    the distance, the radius bounds and the counts, planes_args' for ref_vec (three contiguous float64 or None) and max_angle."""
+    t, r0, r1, P, B, mi, sd = fit_spheres_args(max_distance, min_radius, max_radius, 1, n_trials, min_inliers, seed)
+    _, rv, ang, _, _, _, _ = planes_args(max_distance, ref_vec, max_angle, 1, 1, 3, 0)
+    P = int(max_cylinders)
+    if not 1 <= P <= 64:
+        raise ValueError(f"max_cylinders must lie in 1 .. 64, got {P}")
+    return t, r0, r1, rv, ang, P, B, mi, sd
+
+
+def _fit_cylinders_normals(M: int, normals, k_normals):
+    """-> (normals [M, 3] float32 column-major or None, k_normals): given normals are used as they are"""
+    if normals is not None:
+        nrm = _fcol(normals, np.float32)
+        if nrm.ndim != 2 or nrm.shape != (M, 3):
+            raise ValueError(f"normals are [M, 3] with M = {M} rows, got {nrm.shape}")
+        return nrm, 3
+    kn = int(k_normals)
+    if not 3 <= kn <= KNN_MAX_K:
+        raise ValueError(f"k_normals must lie in [3, {KNN_MAX_K}], got {kn}")
+    return None, kn
+
+
+def _fit_cylinders_samples(samples, P, B):
+    if samples is None:
+        return None
+    smp = np.ascontiguousarray(np.asarray(samples, np.int32))
+    if smp.shape != (P, B, 2):
+        raise ValueError(f"samples must be [max_cylinders, n_trials, 2] = {(P, B, 2)}, got {smp.shape}")
+    return smp
+
+
+def _fit_cylinders_call(call, M: int, P: int) -> dict:
+    labels = np.zeros(max(M, 1), dtype=np.int32)
+    cyl = np.zeros((P, 7), dtype=np.float64)
+    ext = np.zeros((P, 2), dtype=np.float64)
+    counts = np.zeros(P, dtype=np.int32)
+    rmse = np.zeros(P, dtype=np.float64)
+    used = np.zeros(P, dtype=np.int32)
+    bt = np.zeros(P, dtype=np.int32)
+    bc = np.zeros(P, dtype=np.int64)
+    bn = np.zeros(P, dtype=np.int32)
+    n = C.c_int32(0)
+    call(labels.ctypes.data, cyl.ctypes.data, ext.ctypes.data, counts.ctypes.data, rmse.ctypes.data, used.ctypes.data, C.byref(n),
+         bt.ctypes.data, bc.ctypes.data, bn.ctypes.data)
+    return dict(n_cylinders=int(n.value), labels=labels[:M], cylinders=cyl, extents=ext, counts=counts, rmse=rmse, refit_used=used,
+                best_trial=bt, best_cost=bc, best_count=bn)
+
+
+def point_fit_cylinders(pts, max_distance, min_radius: float = 0.0, max_radius: float = math.inf, ref_vec=None, max_angle=math.pi / 2,
+                        normals=None, k_normals: int = 12, max_cylinders: int = 1, n_trials: int = 1000, min_inliers: int = 4,
+                        seed: int = 0, samples=None) -> dict:
+    """pcfitcylinder(pts, maxDistance[, referenceVector, maxAngularDistance]) and the fit / remove / fit-again loop, up to
+    max_cylinders times in one call, in this library's rule (pcreg_model_fit_cylinders_f32's contract): a dict with n_cylinders;
+    labels [M] int32 (cylinder p's rows carry p + 1, 0 is no cylinder); cylinders [P, 7] float64 (cx, cy, cz, wx, wy, wz, R: a point
+    of the axis, its unit direction, the radius); extents [P, 2] (h_lo, h_hi: the axis runs from c + h_lo w to c + h_hi w); counts
+    [P]; rmse [P]; refit_used [P] (0: the round kept its winning trial's own cylinder); and the diagnostics best_trial / best_cost /
+    best_count [P].  normals: [M, 3] float32 by row, used as given (their sign does not matter); None: computed in the call from
+    the k_normals nearest rows.  ref_vec / max_angle (radians) bound the axis.  samples, int32 [max_cylinders, n_trials, 2],
+    replaces the sampler with the caller's 1-BASED rows.  The cloud is prepared for this call only: keep a Model for repeated calls."""
+    t, r0, r1, rv, ang, P, B, mi, sd = fit_cylinders_args(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders, n_trials,
+                                                          min_inliers, seed)
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    nrm, kn = _fit_cylinders_normals(M, normals, k_normals)
+    smp = _fit_cylinders_samples(samples, P, B)
+    return _fit_cylinders_call(lambda *o: check(lib().pcreg_point_fit_cylinders_f32(
+        m.ctypes.data, M, max(M, 1), t, r0, r1, rv.ctypes.data if rv is not None else None, ang, nrm.ctypes.data if nrm is not None and M else None,
+        max(M, 1), kn, P, B, mi, sd, smp.ctypes.data if smp is not None else None, *o)), M, P)
+
+
 def _denoise_args(k, threshold):
     k, threshold = int(k), float(threshold)
     if not 1 <= k <= KNN_MAX_K - 1:
@@ -1207,6 +1281,22 @@ class Model:
         smp = _fit_spheres_samples(samples, P, B)
         return _fit_spheres_call(lambda *o: check(lib().pcreg_model_fit_spheres_f32(self._h, t, r0, r1, P, B, mi, sd,
                                                                                     smp.ctypes.data if smp is not None else None, *o)), self.M, P)
+
+    def fit_cylinders(self, max_distance, min_radius: float = 0.0, max_radius: float = math.inf, ref_vec=None, max_angle=math.pi / 2,
+                      normals=None, k_normals: int = 12, max_cylinders: int = 1, n_trials: int = 1000, min_inliers: int = 4,
+                      seed: int = 0, samples=None) -> dict:
+        """MSAC cylinder fitting and extraction over the prepared model's own rows -- point_fit_cylinders's dict and contract.
+        normals: what Model.normals returns, or None to compute them in the call with k_normals."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        t, r0, r1, rv, ang, P, B, mi, sd = fit_cylinders_args(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders,
+                                                              n_trials, min_inliers, seed)
+        M = self.M
+        nrm, kn = _fit_cylinders_normals(M, normals, k_normals)
+        smp = _fit_cylinders_samples(samples, P, B)
+        return _fit_cylinders_call(lambda *o: check(lib().pcreg_model_fit_cylinders_f32(
+            self._h, t, r0, r1, rv.ctypes.data if rv is not None else None, ang, nrm.ctypes.data if nrm is not None and M else None, max(M, 1),
+            kn, P, B, mi, sd, smp.ctypes.data if smp is not None else None, *o)), M, P)
 
     def denoise(self, k: int = 4, threshold: float = 1.0) -> dict:
         """pcdenoise on the prepared model's own rows: the mean distance of every row to its k nearest other rows, the threshold

@@ -473,6 +473,22 @@ int pcreg_dev_model_fit_spheres_f32(const pcreg_dev_model* model, float max_dist
                                     labels, spheres, counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count, workspace,
                                     workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_fit_cylinders_workspace(int M, int n_trials) { return fit_cylinders_ws_bytes(M, n_trials); }
+int pcreg_dev_model_fit_cylinders_f32(const pcreg_dev_model* model, float max_distance, float min_radius, float max_radius,
+                                      const double* ref_vec, double max_angle, const float* normals_dev, int ldn, int max_cylinders,
+                                      int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t idx_base,
+                                      int32_t* labels, double* cylinders, double* extents, int32_t* counts, double* rmse,
+                                      int32_t* refit_used, int32_t* n_cylinders, int32_t* best_trial, int64_t* best_cost,
+                                      int32_t* best_count, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && n_cylinders &&
+              fit_cylinders_args_ok(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders, n_trials, min_inliers));
+    PCREG_ARG(normals_dev || model->v.M == 0);
+    PCREG_ARG(workspace_bytes >= fit_cylinders_ws_bytes(0, n_trials));         // (the smallest any model needs; the launcher checks this model's)
+    GUARD();
+    return launch_model_fit_cylinders(model->v, max_distance, min_radius, max_radius, ref_vec, max_angle, normals_dev, ldn, max_cylinders,
+                                      n_trials, min_inliers, seed, samples, idx_base, labels, cylinders, extents, counts, rmse, refit_used,
+                                      n_cylinders, best_trial, best_cost, best_count, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int pcreg_dev_model_match_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const int32_t* idx, const float* dist,
                               float thr_abs, float max_ratio, int unique, void* workspace, size_t workspace_bytes, uint32_t* pairs,
                               double* pts1, double* pts2, int32_t* n_pairs, void* stream) {
@@ -1147,6 +1163,101 @@ int pcreg_point_fit_spheres_f32(const float* m, int M, int ldm, float max_distan
     TRY(launch_model_prepare(v, g_stream));
     return fit_spheres_on_view(st, v, max_distance, min_radius, max_radius, max_spheres, n_trials, min_inliers, seed, samples, labels, spheres,
                                counts, rmse, refit_used, n_spheres, best_trial, best_cost, best_count);
+}
+
+// cylinder extraction on a prepared model's own rows: the normals uploaded once (or computed by the normals chain with k_normals and
+// no viewpoint), the chain on the device, then ONE read of everything
+static int fit_cylinders_on_view(Stage& st, const ModelView& v, float t, float min_radius, float max_radius, const double* ref_vec,
+                                 double max_angle, const float* normals, int ldn, int k_normals, int P, int B, int min_inliers,
+                                 uint64_t seed, const int32_t* samples, int32_t* labels, double* cylinders, double* extents,
+                                 int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_cylinders, int32_t* best_trial,
+                                 int64_t* best_cost, int32_t* best_count) {
+    const int M = v.M;
+    *n_cylinders = 0;
+    if (M == 0) {
+        for (int i = 0; i < P; ++i) {
+            if (cylinders) for (int c = 0; c < 7; ++c) cylinders[7 * i + c] = 0.0;
+            if (extents) { extents[2 * i] = 0.0; extents[2 * i + 1] = 0.0; }
+            if (counts) counts[i] = 0;
+            if (rmse) rmse[i] = 0.0;
+            if (refit_used) refit_used[i] = 0;
+            if (best_trial) best_trial[i] = 0;
+            if (best_cost) best_cost[i] = 0;
+            if (best_count) best_count[i] = 0;
+        }
+        return PCREG_OK;
+    }
+    int32_t *dlab, *dcnt, *dru, *dnp, *dbt, *dbn, *dsmp; double *dcy, *dex, *drm; int64_t* dbc; float* dn; char *ws, *nws;
+    const size_t wsb = fit_cylinders_ws_bytes(M, B), nwsb = normals ? 0 : normals_ws_bytes(M, k_normals);
+    const size_t ns = samples ? (size_t)P * (size_t)B * 2 : 0;
+    TRY(st.take(3 * (size_t)M, &dn));
+    TRY(st.take((size_t)M, &dlab));
+    TRY(st.take(7 * (size_t)P, &dcy));
+    TRY(st.take(2 * (size_t)P, &dex));
+    TRY(st.take((size_t)P, &dcnt));
+    TRY(st.take((size_t)P, &drm));
+    TRY(st.take((size_t)P, &dru));
+    TRY(st.take(1, &dnp));
+    TRY(st.take((size_t)P, &dbt));
+    TRY(st.take((size_t)P, &dbc));
+    TRY(st.take((size_t)P, &dbn));
+    TRY(st.take(ns, &dsmp));
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(nwsb, &nws));
+    if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
+    else TRY(launch_model_normals(v, k_normals, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
+    if (samples) PCREG_HIP(hipMemcpyAsync(dsmp, samples, sizeof(int32_t) * ns, hipMemcpyHostToDevice, g_stream));
+    TRY(launch_model_fit_cylinders(v, t, min_radius, max_radius, ref_vec, max_angle, dn, M, P, B, min_inliers, seed, samples ? dsmp : nullptr, 1,
+                                   dlab, dcy, dex, dcnt, drm, dru, dnp, dbt, dbc, dbn, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(labels, dlab, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(cylinders, dcy, sizeof(double) * 7 * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(extents, dex, sizeof(double) * 2 * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(counts, dcnt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(rmse, drm, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(refit_used, dru, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(n_cylinders, dnp, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    if (best_trial) PCREG_HIP(hipMemcpyAsync(best_trial, dbt, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_cost) PCREG_HIP(hipMemcpyAsync(best_cost, dbc, sizeof(int64_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    if (best_count) PCREG_HIP(hipMemcpyAsync(best_count, dbn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
+}
+int pcreg_model_fit_cylinders_f32(pcreg_model* model, float max_distance, float min_radius, float max_radius, const double* ref_vec,
+                                  double max_angle, const float* normals, int ldn, int k_normals, int max_cylinders, int n_trials,
+                                  int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* cylinders,
+                                  double* extents, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_cylinders,
+                                  int32_t* best_trial, int64_t* best_cost, int32_t* best_count) {
+    PCREG_ARG(model && n_cylinders &&
+              fit_cylinders_args_ok(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders, n_trials, min_inliers));
+    PCREG_ARG(normals ? ldn >= model->M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    PCREG_ARG(model->dm != nullptr && model->M < fit_cylinders_max_rows() &&
+              ((labels && cylinders && extents && counts && rmse && refit_used) || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return fit_cylinders_on_view(st, model->dm->v, max_distance, min_radius, max_radius, ref_vec, max_angle, normals, ldn, k_normals,
+                                 max_cylinders, n_trials, min_inliers, seed, samples, labels, cylinders, extents, counts, rmse, refit_used,
+                                 n_cylinders, best_trial, best_cost, best_count);
+}
+int pcreg_point_fit_cylinders_f32(const float* m, int M, int ldm, float max_distance, float min_radius, float max_radius,
+                                  const double* ref_vec, double max_angle, const float* normals, int ldn, int k_normals, int max_cylinders,
+                                  int n_trials, int min_inliers, uint64_t seed, const int32_t* samples, int32_t* labels, double* cylinders,
+                                  double* extents, int32_t* counts, double* rmse, int32_t* refit_used, int32_t* n_cylinders,
+                                  int32_t* best_trial, int64_t* best_cost, int32_t* best_count) {
+    PCREG_ARG(M >= 0 && ldm >= M && M < fit_cylinders_max_rows() && n_cylinders &&
+              fit_cylinders_args_ok(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders, n_trials, min_inliers) &&
+              (M == 0 || (m && labels && cylinders && extents && counts && rmse && refit_used)));
+    PCREG_ARG(normals ? ldn >= M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return fit_cylinders_on_view(st, v, max_distance, min_radius, max_radius, ref_vec, max_angle, normals, ldn, k_normals, max_cylinders,
+                                 n_trials, min_inliers, seed, samples, labels, cylinders, extents, counts, rmse, refit_used, n_cylinders,
+                                 best_trial, best_cost, best_count);
 }
 
 // a NaN anywhere in an n x 3 column-major matrix (the host tier's unique refuses it: MATLAB's unique keeps every NaN row apart)

@@ -465,6 +465,56 @@ class PreparedModel:
                                                         _stream()))
         return dict(labels=lab, spheres=sp, counts=cnt, rmse=rm, refit_used=used, n_spheres=n_sp, best_trial=bt, best_cost=bc, best_count=bn)
 
+    def fit_cylinders(self, max_distance, normals: torch.Tensor, min_radius: float = 0.0, max_radius: float = math.inf, ref_vec=None,
+                      max_angle=math.pi / 2, max_cylinders: int = 1, n_trials: int = 1000, min_inliers: int = 4, seed: int = 0,
+                      samples=None, idx_base: int = 0, out=None):
+        """MSAC cylinder fitting and extraction over the model's own rows on torch's current stream
+        (pcreg_dev_model_fit_cylinders_f32; the contract is pcreg_model_fit_cylinders_f32's): normals the [3, M] float32 tensor
+        PreparedModel.normals returns (by ORIGINAL row; their sign does not matter) -> a dict of device tensors -- labels [M] int32
+        (cylinder p's rows carry p + 1), cylinders [P, 7] float64 (cx, cy, cz, wx, wy, wz, R), extents [P, 2] float64 (h_lo, h_hi
+        along the axis from the centre), counts [P] int32, rmse [P], refit_used [P] int32, n_cylinders [1] int32 and the diagnostics
+        best_trial, best_cost (int64), best_count [P].  ref_vec (three host numbers) and max_angle (radians) bound the axis.
+        samples is an int32 device tensor [max_cylinders, n_trials, 2] of rows counted from idx_base, or None for the sampler.
+        Nothing synchronises: the caller reads n_cylinders when it needs it.  The workspace is cached on the model and grown on
+        demand; calls that may overlap on two streams pass buffers of their own, out=(labels, cylinders, extents, counts, rmse,
+        refit_used, n_cylinders, best_trial, best_cost, best_count, ws) with ws of pcreg_dev_model_fit_cylinders_workspace(M,
+        n_trials) bytes."""
+        from .api import fit_cylinders_args
+        t, r0, r1, rv, ang, P, B, mi, sd = fit_cylinders_args(max_distance, min_radius, max_radius, ref_vec, max_angle, max_cylinders,
+                                                              n_trials, min_inliers, seed)
+        dev, M = self.tensor.device, self.M
+        if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
+                or normals.device != dev):
+            raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the model's device (the row stride is the leading dimension)")
+        if samples is not None and (samples.dtype != torch.int32 or tuple(samples.shape) != (P, B, 2) or not samples.is_contiguous()
+                                    or samples.device != dev):
+            raise ValueError(f"samples must be a contiguous int32 tensor {(P, B, 2)} on the model's device")
+        need = max(int(lib().pcreg_dev_model_fit_cylinders_workspace(M, B)), 256)
+        if out is not None:
+            lab, cy, ex, cnt, rm, used, n_cy, bt, bc, bn, ws = out
+        else:
+            lab = torch.empty(M, dtype=torch.int32, device=dev)
+            cy = torch.empty((P, 7), dtype=torch.float64, device=dev)
+            ex = torch.empty((P, 2), dtype=torch.float64, device=dev)
+            cnt = torch.empty(P, dtype=torch.int32, device=dev)
+            rm = torch.empty(P, dtype=torch.float64, device=dev)
+            used = torch.empty(P, dtype=torch.int32, device=dev)
+            n_cy = torch.empty(1, dtype=torch.int32, device=dev)
+            bt = torch.empty(P, dtype=torch.int32, device=dev)
+            bc = torch.empty(P, dtype=torch.int64, device=dev)
+            bn = torch.empty(P, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_fit_cylinders_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fit_cylinders_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda x: _p(x) if x is not None and x.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_fit_cylinders_f32(self.handle, t, r0, r1, rv.ctypes.data if rv is not None else None, ang, opt(normals),
+                                                          max(int(normals.stride(0)), M), P, B, mi, sd, opt(samples), int(idx_base), opt(lab),
+                                                          opt(cy), opt(ex), opt(cnt), opt(rm), opt(used), opt(n_cy), opt(bt), opt(bc), opt(bn),
+                                                          _p(ws), ws.numel(), _stream()))
+        return dict(labels=lab, cylinders=cy, extents=ex, counts=cnt, rmse=rm, refit_used=used, n_cylinders=n_cy, best_trial=bt, best_cost=bc,
+                    best_count=bn)
+
     def denoise(self, k: int = 4, threshold: float = 1.0, out=None):
         """pcdenoise(model, 'NumNeighbors', k, 'Threshold', threshold) over the model's own rows, on torch's current stream
         (pcreg_dev_model_denoise_f32; the contract is pcreg_model_denoise_f32's): -> a dict of device tensors -- mean_dist [M]
