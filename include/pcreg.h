@@ -88,7 +88,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * than n rows by its in-place large-segment path), "cluster_noskip" (the clustering walk unites on every hit instead of
  * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
  * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass), "score_batch_slots"
- * (n > 0: pcreg_dev_model_score_f32 and pcreg_dev_model_refit_f32 batch whole transforms under n query slots instead of 4 Mi, one transform at least); value 0
+ * (n > 0: pcreg_dev_model_score_f32 and pcreg_dev_model_refit_f32 batch whole transforms under n query slots instead of 4 Mi, one transform at least), "fpfh_radius_lanes" (4 or 16: the radius FPFH counts a
+ * row's pairs with that many lanes instead of 64); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -414,6 +415,41 @@ int pcreg_model_fpfh_f32(pcreg_model* model, int k, const float* normals /* host
  * M < 0, ldm < M, m NULL with M > 0. */
 int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* normals, int ldn, int k_normals, const double* viewpoint,
                          double* fpfh, int ldf, uint8_t* spfh);
+/* The FPFH descriptor of every row of the model from the rows within a radius (MATLAB's extractFPFHFeatures(ptCloud, 'Radius', r),
+ * and with max_neighbors its 'NumNeighbors' beyond the k-nearest list's PCREG_KNN_MAX_K: the n nearest rows within the radius).  THE
+ * CONTRACT of every tier (device, host, MEX, Python) is THIS TEXT; everything it does not restate is
+ * pcreg_model_fpfh_f32's above: the normals and their sign, the pair features and their arithmetic, the bins, S_f, the output.
+ * inputs -- a prepared model of M fp32 rows, M <= 4 Mi (the radius search's queries per call: this call sends the rows as ONE
+ * batch); r2, the SQUARED radius as pcreg_model_range_f32 takes it (a float >= 0; +inf allowed); max_neighbors n >= 0; normals as
+ * pcreg_model_fpfh_f32 takes them.
+ * THE NEIGHBOURHOOD of row i is what pcreg_model_range_f32 returns for query = row i at r2, in its (distance, original row) order:
+ * the radius is inclusive and the distances are the fp32 chain's.  The NEIGHBOURS of i are the entries with a finite squared
+ * distance d2 > 0: the row itself and coincident rows are not neighbours, and they do not count against n.  With n > 0 only the
+ * first n neighbours in that order COUNT (the n nearest within the radius; a row with fewer uses what is there); with n = 0 all of
+ * them count.  A row with a non-finite coordinate has no neighbourhood and is nobody's neighbour.
+ * SPFH of row i: the integer counts c_i[33] over the contributing pairs (i, j), j a counted neighbour; m_i their number.  A count
+ * may reach M - 1, so the counts are uint32.
+ * FPFH of row i: acc[b] = the sum over the counted neighbours j of i with m_j > 0, in list order, of (c_j[b] / m_j) / d2_ij; S_f,
+ * out[b] = (acc[b] / S_f) * 100, 33 NaN for a row with a non-finite coordinate and 33 zeros for an empty neighbourhood (r2 = 0
+ * included) exactly as there.  With a radius that covers the cloud, no coincident rows and n = k - 1 the result is
+ * pcreg_model_fpfh_f32's at k, bit for bit.
+ * outputs -- fpfh: M x 33 double column-major with ldf >= M, by ORIGINAL row; spfh (may be NULL): the SPFH counts, uint32 [M][33]
+ * ROW-major by original row; n_neighbors (may be NULL): int32 [M], the neighbours counted for row i, 0 for a non-finite row.
+ * M = 0 writes nothing.  normals == NULL / given: as pcreg_model_fpfh_f32.
+ * The call counts the neighbourhoods, reads their total once, and holds the lists on the device: 8 bytes per (row, neighbour) pair
+ * within the radius (max_neighbors does not shrink that).  When the device cannot hold them the call returns PCREG_E_HIP and
+ * pcreg_last_error() names the total.
+ * The result is a function of (model rows, normals, r2, max_neighbors) only: no floating-point atomic, no floating-point sum
+ * across threads; culling, the call, the stream and the workspace's previous contents change no bit.  PCREG_E_ARG, before anything
+ * runs: r2 NaN or negative; max_neighbors < 0; M > 4 Mi; ldn < M with normals given; k_normals outside 3 .. PCREG_KNN_MAX_K with
+ * normals NULL; ldf < M; model NULL; fpfh NULL with M > 0. */
+int pcreg_model_fpfh_radius_f32(pcreg_model* model, float r2, int max_neighbors, const float* normals /* host M x 3, or NULL */, int ldn,
+                                int k_normals, const double* viewpoint /* host, 3 or NULL */, double* fpfh /* M x 33, ld ldf */, int ldf,
+                                uint32_t* spfh /* [M][33] or NULL */, int32_t* n_neighbors /* [M] or NULL */);
+/* The same without a handle: uploads and prepares the cloud for this call only.  Also PCREG_E_ARG: M < 0, ldm < M, m NULL with
+ * M > 0. */
+int pcreg_point_fpfh_radius_f32(const float* m, int M, int ldm, float r2, int max_neighbors, const float* normals, int ldn, int k_normals,
+                                const double* viewpoint, double* fpfh, int ldf, uint32_t* spfh, int32_t* n_neighbors);
 /* ISS keypoints of the rows of the model (MATLAB's detectISSFeatures(ptCloud, 'SalientRadius', rs, 'NonMaxRadius', rn, 'Threshold21',
  * g21, 'Threshold32', g32, 'MinNeighbors', n); Zhong's Intrinsic Shape Signatures, ICCV Workshops 2009; PCL's ISSKeypoint3D, Open3D's
  * compute_iss_keypoints).  THE CONTRACT of every tier (device, host, MEX, Python) is THIS TEXT, not any library's
@@ -1027,6 +1063,29 @@ size_t pcreg_dev_model_fpfh_workspace(int M, int k);
 int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* normals_dev /* [3][ldn] */, int ldn,
                              double* fpfh /* [M][33] */, uint8_t* spfh /* [M][33] or NULL */, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* pcreg_model_fpfh_radius_f32's contract on the device, in TWO calls, because the size of the lists is data; neither
+ * synchronises.  pcreg_dev_model_fpfh_radius_count_f32 is pcreg_dev_model_range_count_f32 with the model's own rows as the
+ * queries: counts [M] int32 and seg_off [M + 1] int64 on the device; its workspace is pcreg_dev_model_fpfh_radius_workspace(M, 0)
+ * bytes.  The caller reads seg_off[M], the total, takes a workspace of pcreg_dev_model_fpfh_radius_workspace(M, capacity) bytes with
+ * capacity >= the total, and calls pcreg_dev_model_fpfh_radius_f32 with the same r2 and seg_off: the radius search's fill writes
+ * the lists (0-based rows) into the workspace, one kernel counts the pairs of every row's counted window (a wave of 64 lanes a row, LDS
+ * integer atomics), one thread per (row, bin) weights the neighbours' counts in list order.  normals_dev [3 * ldn] (may not be NULL
+ * with M > 0), fpfh [M][33] double, spfh [M][33] uint32 (or NULL) and n_neighbors [M] int32 (or NULL) are device pointers, ROW-major
+ * by original row -- fpfh is what pcreg_dev_get_matches takes as row-major descriptors with D = 33.  A capacity below the total
+ * truncates segments as pcreg_dev_model_range_fill_f32 documents: the descriptors of the truncated rows, and of rows that have
+ * them as neighbours, are then unspecified, and nothing is written outside the outputs and the workspace.  Workspace, with
+ * R = max(M, 1) and C = capacity: pcreg_dev_model_range_workspace(M, M) + 2 roundup(4 C, 256) + roundup(4 R, 256) +
+ * roundup(132 R, 256) bytes; a workspace shorter than that is PCREG_E_ARG too, and so are ldn < M, M > 4 Mi, a negative capacity or
+ * max_neighbors, r2 NaN or negative.  A handle may serve several streams at once, each call with its own workspace.  The debug
+ * keys "knn_nocull", "knn_stats" and "range_sort_cap" act on the radius search as there; "fpfh_radius_lanes" (4, 16) changes the
+ * lanes per row of the counting kernel and no bit. */
+size_t pcreg_dev_model_fpfh_radius_workspace(int M, int64_t capacity);
+int pcreg_dev_model_fpfh_radius_count_f32(const pcreg_dev_model* model, float r2, int32_t* counts /* [M] */, int64_t* seg_off /* [M + 1] */,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int pcreg_dev_model_fpfh_radius_f32(const pcreg_dev_model* model, float r2, int max_neighbors, const float* normals_dev /* [3][ldn] */, int ldn,
+                                    const int64_t* seg_off /* [M + 1] */, int64_t capacity, double* fpfh /* [M][33] */,
+                                    uint32_t* spfh /* [M][33] or NULL */, int32_t* n_neighbors /* [M] or NULL */, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 /* pcreg_model_iss_f32's contract on the device: n_neighbors [M], eig [M][3] (or NULL), saliency [M], keypoints [M] and
  * n_keypoints (one int32) are device pointers, NULL as there.  Four launches: the self-join walk over all tiles with the integer
  * scatter, whose epilogue finishes each row's eigenvalues and saliency itself; the same walk at r2_nonmax over the rows with a

@@ -62,6 +62,17 @@
 //                                          always passed); each of a row's three histograms adds up to 100 or is all zero, a row
 //                                          with a NaN or Inf is NaN; spfh, the integer pair counts, is built only when asked for
 //                                          (matlab/extractFPFHModel.m, matlab/extractFPFHFast.m)
+//   'modelFpfhRadius', handle, r2, maxNeighbors, normals (single M x 3 | []), kNormals, viewpoint | 'pointFpfhRadius', pts (single
+//                                          M x 3), r2, maxNeighbors, normals, kNormals, viewpoint -> features (M x 33 double), spfh
+//                                          (M x 33 uint32), nNeighbors (M x 1 int32): extractFPFHFeatures(ptCloud, 'Radius', r) in
+//                                          this library's rule (pcreg_model_fpfh_radius_f32) -- the FPFH descriptor of every row
+//                                          from the rows within the radius and a normal per row; r2 a single scalar >= 0 (Inf
+//                                          allowed), the SQUARED radius (the wrappers square the radius in double and round once:
+//                                          single(r^2)); maxNeighbors a whole number >= 0, the n nearest rows within the radius
+//                                          that count (0: all of them; 'NumNeighbors' beyond 32); normals, kNormals and viewpoint
+//                                          as 'modelFpfh' takes them, always passed; at most 4 Mi rows; spfh, the integer pair
+//                                          counts, and nNeighbors, the neighbours counted per row, are built only when asked for
+//                                          (matlab/extractFPFHRadiusModel.m, matlab/extractFPFHRadiusFast.m)
 //   'modelIss', handle, r2Salient, r2NonMax, threshold21, threshold32, minNeighbors | 'pointIss', pts (single M x 3), r2Salient, ... ->
 //                                          keypoints (n x 1 uint32, 1-based, ascending), saliency (M x 1 double), eig (M x 3 double,
 //                                          descending along a row), nNeighbors (M x 1 int32): detectISSFeatures(ptCloud, ...) in this
@@ -235,6 +246,44 @@ static int fpfh_on_handle(pcreg_model* h, int k, const mxArray* nrm, int k_norma
                 for (int b = 0; b < 33; ++b) dst[(size_t)i + (size_t)b * (size_t)M] = src[(size_t)i * 33 + b];
         }
     } else mxDestroyArray(of);
+    if (tc) mxDestroyArray(tc);
+    return rc;
+}
+
+// r2 and maxNeighbors of the radius FPFH commands: a real single scalar >= 0 (Inf allowed, NaN not); a real double scalar, whole,
+// 0 .. 2^31 - 1
+static bool fpfh_radius_args_ok(const mxArray* r2, const mxArray* n) {
+    if (!mxIsSingle(r2) || mxGetM(r2) * mxGetN(r2) != 1 || !(*(const float*)mxGetData(r2) >= 0.0f)) return false;
+    return mxIsDouble(n) && mxGetM(n) * mxGetN(n) == 1 && mxGetScalar(n) >= 0.0 && mxGetScalar(n) <= 2147483647.0 &&
+           mxGetScalar(n) == (double)(int)mxGetScalar(n);
+}
+// the outputs of 'modelFpfhRadius' / 'pointFpfhRadius': features (M x 33 double), with nout > 1 the counts (M x 33 uint32; the
+// library's rows of 33 are turned into MATLAB's columns), with nout > 2 nNeighbors (M x 1 int32).  nrm: single M x 3 or [].  Nothing is
+// left allocated on an error; *usage is set when the normals have another number of rows than the model.
+static int fpfh_radius_on_handle(pcreg_model* h, float r2, int max_neighbors, const mxArray* nrm, int k_normals, const mxArray* vp, int nout,
+                                 mxArray* out[3], const char** usage) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    const bool given = !mxIsEmpty(nrm);
+    if (given && (int)mxGetM(nrm) != M) { *usage = "FpfhRadius: normals must have one row per row of the cloud"; return PCREG_OK; }
+    mxArray* of = mxCreateDoubleMatrix((size_t)M, 33, mxREAL);
+    mxArray* tc = nout > 1 ? mxCreateNumericMatrix(33, (size_t)(M > 0 ? M : 1), mxUINT32_CLASS, mxREAL) : nullptr;
+    mxArray* on = nout > 2 ? mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL) : nullptr;
+    rc = pcreg_model_fpfh_radius_f32(h, r2, max_neighbors, given ? (const float*)mxGetData(nrm) : nullptr, M > 0 ? M : 1, k_normals,
+                                     mxIsEmpty(vp) ? nullptr : mxGetPr(vp), mxGetPr(of), M > 0 ? M : 1, tc ? (uint32_t*)mxGetData(tc) : nullptr,
+                                     on ? (int32_t*)mxGetData(on) : nullptr);
+    if (rc == PCREG_OK) {
+        out[0] = of;
+        if (tc) {
+            out[1] = mxCreateNumericMatrix((size_t)M, 33, mxUINT32_CLASS, mxREAL);
+            const uint32_t* src = (const uint32_t*)mxGetData(tc);
+            uint32_t* dst = (uint32_t*)mxGetData(out[1]);
+            for (int i = 0; i < M; ++i)
+                for (int b = 0; b < 33; ++b) dst[(size_t)i + (size_t)b * (size_t)M] = src[(size_t)i * 33 + b];
+        }
+        out[2] = on;
+    } else { mxDestroyArray(of); if (on) mxDestroyArray(on); }
     if (tc) mxDestroyArray(tc);
     return rc;
 }
@@ -1084,6 +1133,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = fpfh_on_handle(h, (int)mxGetScalar(prhs[2]), prhs[3], (int)mxGetScalar(prhs[4]), prhs[5], nlhs > 1, out, &usage);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK && !usage) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; }
+        }
+    } else if (!strcmp(cmd, "modelFpfhRadius")) {             // [features, spfh, nNeighbors] = pcreg_mex('modelFpfhRadius', h, r2, maxNeighbors, normals, kNormals, viewpoint)
+        if (nrhs != 7 || !mxIsUint64(prhs[1]) || !fpfh_radius_args_ok(prhs[2], prhs[3]) ||
+            (!mxIsEmpty(prhs[4]) && (!mxIsSingle(prhs[4]) || mxGetN(prhs[4]) != 3)) || !normals_k_ok(prhs[5]) || !viewpoint_ok(prhs[6]))
+            usage = "modelFpfhRadius: handle (uint64), r2 (a single scalar >= 0, the squared radius), maxNeighbors (a whole number >= 0), normals "
+                    "(single M x 3, or [] to compute them), kNormals (a whole number 3 .. 32), viewpoint ([] or double 1 x 3)";
+        else {
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            rc = fpfh_radius_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), *(const float*)mxGetData(prhs[2]),
+                                       (int)mxGetScalar(prhs[3]), prhs[4], (int)mxGetScalar(prhs[5]), prhs[6], nlhs, out, &usage);
+            if (usage) usage = "modelFpfhRadius: normals must have one row per model row";
+            if (rc == PCREG_OK && !usage) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "pointFpfhRadius")) {             // [features, spfh, nNeighbors] = pcreg_mex('pointFpfhRadius', single(pts), r2, maxNeighbors, normals, kNormals, viewpoint)
+        if (nrhs != 7 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !fpfh_radius_args_ok(prhs[2], prhs[3]) ||
+            (!mxIsEmpty(prhs[4]) && (!mxIsSingle(prhs[4]) || mxGetN(prhs[4]) != 3)) || !normals_k_ok(prhs[5]) || !viewpoint_ok(prhs[6]))
+            usage = "pointFpfhRadius: pts (single M x 3), r2 (a single scalar >= 0, the squared radius), maxNeighbors (a whole number >= 0), normals "
+                    "(single M x 3, or [] to compute them), kNormals (a whole number 3 .. 32), viewpoint ([] or double 1 x 3)";
+        else if (!mxIsEmpty(prhs[4]) && mxGetM(prhs[4]) != mxGetM(prhs[1])) usage = "pointFpfhRadius: normals must have one row per row of pts";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[3] = {nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = fpfh_radius_on_handle(h, *(const float*)mxGetData(prhs[2]), (int)mxGetScalar(prhs[3]), prhs[4], (int)mxGetScalar(prhs[5]),
+                                                           prhs[6], nlhs, out, &usage);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK && !usage) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
         }
     } else if (!strcmp(cmd, "modelDenoise")) {                // [inlierIndices, meanDist, thr] = pcreg_mex('modelDenoise', h, k, threshold)
         if (nrhs != 4 || !mxIsUint64(prhs[1]) || !denoise_k_ok(prhs[2]) || !denoise_t_ok(prhs[3]))

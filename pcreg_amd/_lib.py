@@ -67,6 +67,8 @@ SYMBOLS = [
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
     "pcreg_model_fpfh_f32", "pcreg_point_fpfh_f32", "pcreg_dev_model_fpfh_workspace", "pcreg_dev_model_fpfh_f32",
+    "pcreg_model_fpfh_radius_f32", "pcreg_point_fpfh_radius_f32", "pcreg_dev_model_fpfh_radius_workspace", "pcreg_dev_model_fpfh_radius_count_f32",
+    "pcreg_dev_model_fpfh_radius_f32",
     "pcreg_model_iss_f32", "pcreg_point_iss_f32", "pcreg_dev_model_iss_workspace", "pcreg_dev_model_iss_f32",
     "pcreg_model_fit_planes_f32", "pcreg_point_fit_planes_f32", "pcreg_dev_model_fit_planes_workspace", "pcreg_dev_model_fit_planes_f32",
     "pcreg_model_fit_spheres_f32", "pcreg_point_fit_spheres_f32", "pcreg_dev_model_fit_spheres_workspace", "pcreg_dev_model_fit_spheres_f32",
@@ -170,6 +172,14 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_fpfh_f32.argtypes = [vp, i, vp, i, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_fpfh_f32.argtypes = [vp, i, vp, i, i, vp, vp, i, vp]
             L.pcreg_point_fpfh_f32.argtypes = [vp, i, i, i, vp, i, i, vp, vp, i, vp]
+        if hasattr(L, "pcreg_dev_model_fpfh_radius_workspace"):   # (an older build given through PCREG_LIB lacks the radius FPFH)
+            L.pcreg_dev_model_fpfh_radius_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_fpfh_radius_workspace.argtypes = [C.c_int, C.c_int64]
+            vp, i, f, i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64            # (floats and 64-bit integers by value: declared)
+            L.pcreg_dev_model_fpfh_radius_count_f32.argtypes = [vp, f, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_dev_model_fpfh_radius_f32.argtypes = [vp, f, i, vp, i, vp, i64, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_fpfh_radius_f32.argtypes = [vp, f, i, vp, i, i, vp, vp, i, vp, vp]
+            L.pcreg_point_fpfh_radius_f32.argtypes = [vp, i, i, f, i, vp, i, i, vp, vp, i, vp, vp]
         if hasattr(L, "pcreg_dev_model_iss_workspace"):       # (an older build given through PCREG_LIB lacks the ISS keypoints)
             L.pcreg_dev_model_iss_workspace.restype = C.c_size_t
             L.pcreg_dev_model_iss_workspace.argtypes = [C.c_int]

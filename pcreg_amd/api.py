@@ -725,6 +725,60 @@ def point_fpfh(pts, k: int, normals=None, k_normals=None, viewpoint=None, spfh: 
                       M, nrm, vp, spfh)
 
 
+FPFH_RADIUS_MAX_ROWS = 4 << 20             # rows per radius-FPFH call: the radius search's queries per call, one batch
+
+
+def _fpfh_radius_args(M: int, radius, max_neighbors, normals, k_normals, viewpoint):
+    """-> (r2, max_neighbors, normals or None, k_normals, viewpoint): the radius squared in double and the square rounded once to
+    float32 (a number >= 0; +inf allowed), the rest as the C tiers take them"""
+    r = float(radius)
+    if not r >= 0.0:
+        raise ValueError(f"radius must be a number >= 0, got {r}")
+    with np.errstate(over="ignore"):
+        r2 = float(np.float32(r * r))
+    n = int(max_neighbors)
+    if n < 0:
+        raise ValueError(f"max_neighbors must be >= 0 (0: every row within the radius), got {n}")
+    if M > FPFH_RADIUS_MAX_ROWS:
+        raise ValueError(f"the radius FPFH takes at most {FPFH_RADIUS_MAX_ROWS} rows a call, got {M}")
+    if normals is not None:
+        nrm = _fcol(normals, np.float32)
+        if nrm.ndim != 2 or nrm.shape != (M, 3):
+            raise ValueError(f"normals are [M, 3] with M = {M} rows, got {nrm.shape}")
+        return r2, n, nrm, 3, None              # (k_normals is ignored with normals given)
+    kn, vp = _normals_args(k_normals, viewpoint)
+    return r2, n, None, kn, vp
+
+
+def _fpfh_radius_call(call, M: int, nrm, vp, counts: bool, n_neighbors: bool):
+    out = np.zeros((max(M, 1), 33), dtype=np.float64, order="F")
+    cnt = np.zeros((max(M, 1), 33), dtype=np.uint32) if counts else None
+    nn = np.zeros(max(M, 1), dtype=np.int32) if n_neighbors else None
+    call(nrm.ctypes.data if nrm is not None and M else None, max(M, 1), vp.ctypes.data if vp is not None else None, out.ctypes.data, max(M, 1),
+         cnt.ctypes.data if counts else None, nn.ctypes.data if n_neighbors else None)
+    res = (out[:M],) + ((cnt[:M],) if counts else ()) + ((nn[:M],) if n_neighbors else ())
+    return res if len(res) > 1 else res[0]
+
+
+def point_fpfh_radius(pts, radius, normals=None, max_neighbors: int = 0, k_normals: int = 6, viewpoint=None, counts: bool = False,
+                      n_neighbors: bool = False):
+    """extractFPFHFeatures(pts, 'Radius', radius) in this library's rule (pcreg_model_fpfh_radius_f32's contract): the 33-number
+    FPFH descriptor of every row, [M, 33] float64, from the rows within the radius (inclusive, fp32 distances) and a normal per
+    row.  max_neighbors = n > 0 counts only the n nearest of them ('NumNeighbors' beyond the k-nearest form's 32: MATLAB's default
+    of 50 is max_neighbors=50 with a radius wide enough; a row with fewer rows inside the radius uses what is there); 0 counts
+    all.  normals: [M, 3] float32 by row, as point_normals returns them -- their SIGN matters; None: computed in the call from the
+    k_normals nearest rows and the viewpoint.  counts=True also returns the SPFH counts [M, 33] uint32, n_neighbors=True the
+    neighbours counted per row [M] int32, in that order.  The lists take 8 bytes per (row, neighbour) pair within the radius on
+    the device; at most 4 Mi rows a call.  The cloud is prepared for this call only: keep a Model for repeated calls."""
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    r2, n, nrm, kn, vp = _fpfh_radius_args(M, radius, max_neighbors, normals, k_normals, viewpoint)
+    return _fpfh_radius_call(lambda a, ldn, v, o, ldf, c, nn: check(lib().pcreg_point_fpfh_radius_f32(m.ctypes.data, M, max(M, 1), r2, n, a, ldn, kn, v,
+                                                                                                      o, ldf, c, nn)), M, nrm, vp, counts, n_neighbors)
+
+
 def iss_args(salient_radius, nonmax_radius, gamma21, gamma32, min_neighbors):
     """The ISS parameters as the C tiers take them: each radius squared in double and the square rounded once to float32 (the
     rule pcreg_model_iss_f32 states for wrappers that take radii), the thresholds as doubles, min_neighbors as an int."""
@@ -1253,6 +1307,18 @@ class Model:
             raise ValueError("the model handle is closed")
         k, nrm, kn, vp = _fpfh_args(self.M, k, normals, k_normals, viewpoint)
         return _fpfh_call(lambda n, ldn, v, o, ldf, c: check(lib().pcreg_model_fpfh_f32(self._h, k, n, ldn, kn, v, o, ldf, c)), self.M, nrm, vp, spfh)
+
+    def fpfh_radius(self, radius, normals=None, max_neighbors: int = 0, k_normals: int = 6, viewpoint=None, counts: bool = False,
+                    n_neighbors: bool = False):
+        """The FPFH descriptor of every row of the prepared model from the rows within the radius (at most the max_neighbors
+        nearest of them; 0: all) and a normal per row: [M, 33] float64, with counts=True also the SPFH counts [M, 33] uint32 and
+        with n_neighbors=True the neighbours counted per row [M] int32 -- point_fpfh_radius's contract.  normals: what
+        Model.normals returns (oriented: the sign matters), or None to compute them in the call with k_normals and the viewpoint."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2, n, nrm, kn, vp = _fpfh_radius_args(self.M, radius, max_neighbors, normals, k_normals, viewpoint)
+        return _fpfh_radius_call(lambda a, ldn, v, o, ldf, c, nn: check(lib().pcreg_model_fpfh_radius_f32(self._h, r2, n, a, ldn, kn, v, o, ldf, c, nn)),
+                                 self.M, nrm, vp, counts, n_neighbors)
 
     def iss_keypoints(self, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma32: float = 0.975, min_neighbors: int = 5) -> dict:
         """The ISS keypoints of the prepared model's own rows, with the neighbour count, the eigenvalues and the saliency of every

@@ -120,7 +120,7 @@ int pcreg_debug_set(const char* key, int value) {
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
                                                         "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap", "cluster_noskip",
-                                                        "cluster_stats", "knn_tail_cap", "score_batch_slots"};
+                                                        "cluster_stats", "knn_tail_cap", "score_batch_slots", "fpfh_radius_lanes"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -437,6 +437,24 @@ int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* n
     PCREG_ARG(workspace_bytes >= fpfh_ws_bytes(model->v.M, k));
     GUARD();
     return launch_model_fpfh(model->v, k, normals, ldn, fpfh, spfh, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t pcreg_dev_model_fpfh_radius_workspace(int M, int64_t capacity) { return fpfh_radius_ws_bytes(M, capacity); }
+int pcreg_dev_model_fpfh_radius_count_f32(const pcreg_dev_model* model, float r2, int32_t* counts, int64_t* seg_off, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && seg_off && (counts || model->v.M == 0) && r2 >= 0.0f && model->v.M <= fpfh_radius_max_rows());
+    PCREG_ARG(workspace_bytes >= fpfh_radius_ws_bytes(model->v.M, 0));
+    GUARD();
+    return launch_model_fpfh_radius_count(model->v, r2, counts, seg_off, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int pcreg_dev_model_fpfh_radius_f32(const pcreg_dev_model* model, float r2, int max_neighbors, const float* normals, int ldn, const int64_t* seg_off,
+                                    int64_t capacity, double* fpfh, uint32_t* spfh, int32_t* n_neighbors, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    PCREG_ARG(model && workspace && seg_off && r2 >= 0.0f && max_neighbors >= 0 && capacity >= 0 && model->v.M <= fpfh_radius_max_rows() &&
+              ldn >= model->v.M && ((normals && fpfh) || model->v.M == 0));
+    PCREG_ARG(workspace_bytes >= fpfh_radius_ws_bytes(model->v.M, capacity));
+    GUARD();
+    return launch_model_fpfh_radius(model->v, r2, max_neighbors, normals, ldn, seg_off, capacity, fpfh, spfh, n_neighbors, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
 }
 size_t pcreg_dev_model_iss_workspace(int M) { return iss_ws_bytes(M); }
 int pcreg_dev_model_iss_f32(const pcreg_dev_model* model, float r2_salient, float r2_nonmax, double gamma21, double gamma32, int min_neighbors,
@@ -958,6 +976,70 @@ int pcreg_point_fpfh_f32(const float* m, int M, int ldm, int k, const float* nor
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return fpfh_on_view(st, v, k, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh);
+}
+
+// FPFH from radius neighbourhoods on a prepared model: the normals uploaded once (or computed by the normals chain), the count,
+// ONE read of the total, then the lists' workspace is taken (last: its size is data) and fill + R1 + R2 run; ONE read of the
+// [M][33] block (and the counts asked for), transposed into the caller's columns
+static int fpfh_radius_on_view(Stage& st, const ModelView& v, float r2, int max_neighbors, const float* normals, int ldn, int k_normals,
+                               const double* viewpoint, double* fpfh, int ldf, uint32_t* spfh, int32_t* n_neighbors) {
+    const int M = v.M;
+    if (M == 0) return PCREG_OK;
+    float* dn; double* dout; uint32_t* dsp; int32_t *dc, *dnn; int64_t* ds; char *cws, *nws, *ws;
+    const size_t cwsb = fpfh_radius_ws_bytes(M, 0), nwsb = normals ? 0 : normals_ws_bytes(M, k_normals), n33 = 33 * (size_t)M;
+    TRY(st.take(3 * (size_t)M, &dn));
+    TRY(st.take(n33, &dout));
+    TRY(st.take(spfh ? n33 : 0, &dsp));
+    TRY(st.take(n_neighbors ? (size_t)M : 0, &dnn));
+    TRY(st.take((size_t)M, &dc));
+    TRY(st.take((size_t)M + 1, &ds));
+    TRY(st.take(cwsb, &cws));
+    TRY(st.take(nwsb, &nws));
+    if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
+    else TRY(launch_model_normals(v, k_normals, viewpoint, dn, M, nullptr, nws, nwsb, g_stream));
+    TRY(launch_model_fpfh_radius_count(v, r2, dc, ds, cws, cwsb, g_stream));
+    int64_t total = 0;
+    PCREG_HIP(hipMemcpyAsync(&total, ds + M, sizeof(int64_t), hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const size_t wsb = fpfh_radius_ws_bytes(M, total);
+    const int rc = st.take(wsb, &ws);
+    if (rc) {
+        (void)hipGetLastError();
+        set_error("out of device memory: the radius neighbourhoods hold %lld (row, neighbour) pairs in all and need %zu bytes", (long long)total, wsb);
+        return rc;
+    }
+    TRY(launch_model_fpfh_radius(v, r2, max_neighbors, dn, M, ds, total, dout, spfh ? dsp : nullptr, n_neighbors ? dnn : nullptr, ws, wsb, g_stream));
+    std::vector<double> host(n33);
+    PCREG_HIP(hipMemcpyAsync(host.data(), dout, sizeof(double) * n33, hipMemcpyDeviceToHost, g_stream));
+    if (spfh) PCREG_HIP(hipMemcpyAsync(spfh, dsp, sizeof(uint32_t) * n33, hipMemcpyDeviceToHost, g_stream));
+    if (n_neighbors) PCREG_HIP(hipMemcpyAsync(n_neighbors, dnn, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    for (int b = 0; b < 33; ++b)
+        for (int i = 0; i < M; ++i) fpfh[(size_t)i + (size_t)b * (size_t)ldf] = host[(size_t)i * 33 + b];
+    return PCREG_OK;
+}
+int pcreg_model_fpfh_radius_f32(pcreg_model* model, float r2, int max_neighbors, const float* normals, int ldn, int k_normals,
+                                const double* viewpoint, double* fpfh, int ldf, uint32_t* spfh, int32_t* n_neighbors) {
+    PCREG_ARG(model && r2 >= 0.0f && max_neighbors >= 0 && model->M <= fpfh_radius_max_rows() && ldf >= model->M && (fpfh || model->M == 0));
+    PCREG_ARG(normals ? ldn >= model->M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return fpfh_radius_on_view(st, model->dm->v, r2, max_neighbors, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh, n_neighbors);
+}
+int pcreg_point_fpfh_radius_f32(const float* m, int M, int ldm, float r2, int max_neighbors, const float* normals, int ldn, int k_normals,
+                                const double* viewpoint, double* fpfh, int ldf, uint32_t* spfh, int32_t* n_neighbors) {
+    PCREG_ARG(M >= 0 && ldm >= M && r2 >= 0.0f && max_neighbors >= 0 && M <= fpfh_radius_max_rows() && ldf >= M && (M == 0 || (m && fpfh)));
+    PCREG_ARG(normals ? ldn >= M : (k_normals >= 3 && k_normals <= kKnnMaxK));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return fpfh_radius_on_view(st, v, r2, max_neighbors, normals, ldn, k_normals, viewpoint, fpfh, ldf, spfh, n_neighbors);
 }
 
 // ISS keypoints of a prepared model's own rows: the chain on the device, ONE read of the count (with the per-row outputs behind

@@ -93,6 +93,8 @@ enum DebugKey {
                                // pass instead of its LDS list's capacity
     kDbgScoreBatchSlots,       // "score_batch_slots": n > 0 -- the transform scoring batches whole transforms under n query slots instead
                                // of 4 Mi (at least one transform a batch), to reach its batch loop at a small size
+    kDbgFpfhRadiusLanes,       // "fpfh_radius_lanes": 4 or 16 -- the radius FPFH's SPFH kernel walks a row's segment with that many lanes
+                               // instead of 64 (a wave); the counts are integers, so every setting gives the same bits
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -247,6 +249,15 @@ int launch_model_denoise(const ModelView& v, int k, double threshold, double* me
 size_t fpfh_ws_bytes(int M, int k);
 int launch_model_fpfh(const ModelView& v, int k, const float* normals, int ldn, double* fpfh, uint8_t* spfh, void* ws, size_t ws_bytes,
                       hipStream_t st);
+// the FPFH descriptor of every model row from the rows within a squared radius (knn_fpfh_radius.hip): the count call is
+// the radius search's with the model's own rows as the queries; the second call fills the lists into the workspace and runs the
+// two kernels.  normals [3][ldn] by ORIGINAL row; fpfh [M][33] doubles, spfh [M][33] uint32 counts (or null) and n_neighbors [M]
+// (or null), row-major by ORIGINAL row.  fpfh_radius_max_rows is the per-call row limit every tier checks before the device
+size_t fpfh_radius_ws_bytes(int M, int64_t capacity);
+int fpfh_radius_max_rows();
+int launch_model_fpfh_radius_count(const ModelView& v, float r2, int32_t* counts, int64_t* seg_off, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_model_fpfh_radius(const ModelView& v, float r2, int max_neighbors, const float* normals, int ldn, const int64_t* seg_off,
+                             int64_t capacity, double* fpfh, uint32_t* spfh, int32_t* n_neighbors, void* ws, size_t ws_bytes, hipStream_t st);
 // ISS keypoints of the model's own rows (knn_iss.hip): n_neighbors [M], eig [M][3] (or null) and saliency [M] by ORIGINAL
 // row, keypoints [<= M] ascending with n_keypoints (both may be null; keypoints needs n_keypoints) -- device pointers.  iss_args_ok
 // and iss_max_rows are the argument rules every tier checks before it touches the device

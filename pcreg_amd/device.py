@@ -357,6 +357,73 @@ class PreparedModel:
                                                      _p(cnt) if cnt is not None else None, _p(ws), ws.numel(), _stream()))
         return (desc, cnt) if spfh else desc
 
+    def fpfh_radius_count(self, r2: float, out=None):
+        """The first of the radius FPFH's two calls, on torch's current stream (pcreg_dev_model_fpfh_radius_count_f32): the rows
+        within the SQUARED radius r2 of every row of the model, the row itself included -> (counts [M] int32, seg_off [M + 1]
+        int64).  Nothing synchronises: the caller reads seg_off[M], the total, sizes the lists with it and calls fpfh_radius.
+        out=(counts, seg_off, ws) with ws of pcreg_dev_model_fpfh_radius_workspace(M, 0) bytes for calls that may overlap."""
+        r2 = float(r2)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_fpfh_radius_workspace(M, 0)), 256)
+        if out is not None:
+            counts, seg_off, ws = out
+        else:
+            counts = torch.empty(M, dtype=torch.int32, device=dev)
+            seg_off = torch.empty(M + 1, dtype=torch.int64, device=dev)
+            ws = getattr(self, "_fpfh_radius_cws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fpfh_radius_cws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_fpfh_radius_count_f32(self.handle, r2, _p(counts) if M else None, _p(seg_off), _p(ws), ws.numel(), _stream()))
+        return counts, seg_off
+
+    def fpfh_radius(self, r2: float, normals: torch.Tensor, seg_off: torch.Tensor, capacity: int, max_neighbors: int = 0, spfh: bool = False,
+                    out=None):
+        """The second call (pcreg_dev_model_fpfh_radius_f32; the contract is pcreg_model_fpfh_radius_f32's): r2 and seg_off as
+        fpfh_radius_count took and returned them, capacity >= seg_off[M] (the host's copy of the total: a smaller one truncates
+        segments and leaves those rows' descriptors unspecified), normals the [3, M] float32 tensor PreparedModel.normals
+        returns, max_neighbors = n > 0 to count only the n nearest rows within the radius -> (fpfh [M, 33] float64, n_neighbors [M]
+        int32), and with spfh=True (fpfh, counts [M, 33], n_neighbors), row-major by ORIGINAL row; the counts are the library's uint32 in
+        an int32 tensor (a count is below M).  Nothing synchronises.  The
+        workspace (8 bytes per list entry and the rest) is cached on the model and grown on demand; calls that may overlap on two
+        streams pass buffers of their own, out=(fpfh, counts, n_neighbors, ws) with ws of
+        pcreg_dev_model_fpfh_radius_workspace(M, capacity) bytes (counts and n_neighbors None when not wanted)."""
+        r2, n, capacity = float(r2), int(max_neighbors), int(capacity)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        if n < 0 or capacity < 0:
+            raise ValueError(f"max_neighbors and capacity must be >= 0, got {n} and {capacity}")
+        dev, M = self.tensor.device, self.M
+        if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
+                or normals.device != dev):
+            raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the model's device (the row stride is the leading dimension)")
+        if seg_off.dtype != torch.int64 or seg_off.shape != (M + 1,) or not seg_off.is_contiguous() or seg_off.device != dev:
+            raise TypeError("seg_off is the contiguous [M + 1] int64 tensor fpfh_radius_count returns")
+        need = max(int(lib().pcreg_dev_model_fpfh_radius_workspace(M, capacity)), 256)
+        if out is not None:
+            desc, cnt, nn, ws = out
+            if desc.dtype != torch.float64 or desc.shape != (M, 33) or not desc.is_contiguous():
+                raise TypeError("fpfh is a contiguous [M, 33] float64 tensor")
+            if cnt is not None and (cnt.dtype != torch.int32 or cnt.shape != (M, 33) or not cnt.is_contiguous()):
+                raise TypeError("the SPFH counts are a contiguous [M, 33] int32 tensor")
+            if nn is not None and (nn.dtype != torch.int32 or nn.shape != (M,) or not nn.is_contiguous()):
+                raise TypeError("n_neighbors is a contiguous [M] int32 tensor")
+        else:
+            desc = torch.empty((M, 33), dtype=torch.float64, device=dev)
+            cnt = torch.empty((M, 33), dtype=torch.int32, device=dev) if spfh else None
+            nn = torch.empty(M, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_fpfh_radius_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fpfh_radius_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if M:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                check(lib().pcreg_dev_model_fpfh_radius_f32(self.handle, r2, n, _p(normals), max(int(normals.stride(0)), M), _p(seg_off), capacity,
+                                                            _p(desc), _p(cnt) if cnt is not None else None, _p(nn) if nn is not None else None,
+                                                            _p(ws), ws.numel(), _stream()))
+        return (desc, cnt, nn) if spfh else (desc, nn)
+
     def iss_keypoints(self, salient_radius, nonmax_radius, gamma21: float = 0.975, gamma32: float = 0.975, min_neighbors: int = 5,
                       eig: bool = True, out=None):
         """The ISS keypoints of the model's own rows on torch's current stream (pcreg_dev_model_iss_f32; the contract is
