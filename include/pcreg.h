@@ -89,7 +89,7 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
  * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass), "score_batch_slots"
  * (n > 0: pcreg_dev_model_score_f32 and pcreg_dev_model_refit_f32 batch whole transforms under n query slots instead of 4 Mi, one transform at least), "fpfh_radius_lanes" (4 or 16: the radius FPFH counts a
- * row's pairs with that many lanes instead of 64); value 0
+ * row's pairs with that many lanes instead of 64), "desc_stats" (counters for pcreg_debug_desc_stats); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -118,6 +118,19 @@ int  pcreg_debug_ransac_stats(long long out[3], int reset);
  * that failed (another lane had merged first).  Off: no extra work.  The read synchronises the device.  (The walk's visited and
  * nominal (tile, tile) pairs are counted by "knn_stats".) */
 int  pcreg_debug_cluster_stats(long long out[4], int reset);
+/* With pcreg_debug_set("desc_stats", 1): which of its rarely taken branches the descriptor kernel took, summed over the
+ * keypoints of the calls since the last reset -- out[0] keypoints that passed the size gates and reached the K-nearest
+ * selection, [1] selections that fell back to the bisection (more than 256 keys in the K-th key's bin), [2] selections that
+ * counted the tie group with a pass over every key (the group straddles a bin border, or the bin is crowded), [3] selections
+ * that ranked a tie group by original index (part of it is kept), [4] keypoints whose sign votes were all retaken in fp64
+ * (more than 128 votes fp32 could not certify), [5] keypoints whose whole support was binned again in fp64 (more than 128
+ * deferred points), [6] points that took the literal sqrt / acos / atan2 path, [7] (wave, 64-candidate chunk) pairs re-tested
+ * past the kept ballots, [8] the grid subdivision of the LAST call, fx << 16 | fy << 8 | fz (stored, not added), [9] deferred
+ * points binned one by one in fp64 (supports with at most 128 of them: the others count in [5]).  While the key is on the
+ * descriptor calls run a second instantiation of the kernel that holds the counting code (same source, same results); off,
+ * they run the default one, which holds none.  The read synchronises the device.  The tests use the counters to prove that a
+ * scene reached the branch it was built for, and run every such scene on both instantiations. */
+int  pcreg_debug_desc_stats(long long out[10], int reset);
 
 /* ---- host tier ------------------------------------------------------------------ */
 

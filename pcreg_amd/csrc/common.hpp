@@ -95,6 +95,7 @@ enum DebugKey {
                                // of 4 Mi (at least one transform a batch), to reach its batch loop at a small size
     kDbgFpfhRadiusLanes,       // "fpfh_radius_lanes": 4 or 16 -- the radius FPFH's SPFH kernel walks a row's segment with that many lanes
                                // instead of 64 (a wave); the counts are integers, so every setting gives the same bits
+    kDbgDescStats,             // "desc_stats": the descriptor kernel counts the rare branches it takes (pcreg_debug_desc_stats)
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -113,6 +114,14 @@ unsigned long long* ransac_stats_dev();
 // Device counters of the clustering walk (knn_cluster.hip), or null while "cluster_stats" is off:
 //   [0] calls   [1] hits   [2] compare-and-swap attempts   [3] failed attempts
 unsigned long long* cluster_stats_dev();
+// Device counters of the descriptor kernel (descriptors.hip), or null while "desc_stats" is off -- keypoints that:
+//   [0] reached the K-nearest selection   [1] selected by bisection (a crowded bin)   [2] counted the tie group with the full pass
+//   [3] ranked a tie group by original index   [4] retook every vote in fp64   [5] were re-binned literally (> 128 deferred points);
+//   [6] points that reached bin_literal   [7] (wave, chunk) pairs re-tested past the kept ballots
+//   [8] the last call's grid subdivision, fx << 16 | fy << 8 | fz (stored, not added)
+//   [9] deferred points binned one by one in fp64 (the supports with at most 128 of them)
+// While the key is on, launch_descriptors runs desc_kernel's counting instantiation; the default one holds no counting code.
+unsigned long long* desc_stats_dev();
 #ifdef PCREG_EXPERIMENTS
 static inline int pcreg_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline const char* pcreg_env_str(const char* name) { return getenv(name); }

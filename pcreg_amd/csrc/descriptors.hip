@@ -45,6 +45,8 @@ constexpr int kSortTile = 2048;            // points per counting-sort tile
 constexpr int kMaxCells = 1 << 16;
 constexpr int NR = 10, NT = 7, NP = 14, ND = NR * NT * NP;
 static_assert(NT == 7, "bin_fast32 folds the seven theta bins about pi / 2");
+// words of the "desc_stats" counters (common.hpp: desc_stats_dev): which of desc_kernel's rare branches a call took
+enum { kDsSelect = 0, kDsBisect, kDsRecount, kDsTieRank, kDsVote64, kDsRebin, kDsLiteral, kDsRetest, kDsSubdiv, kDsDeferred };
 
 struct Grid {
     double ox, oy, oz;                     // origin
@@ -89,7 +91,8 @@ __global__ __launch_bounds__(kBlock) void bbox_partial_d_kernel(const double* __
         part[blockIdx.x * 6 + threadIdx.x] = v;
     }
 }
-__global__ void grid_setup_kernel(const double* __restrict__ part, int nparts, double R, Grid* __restrict__ g, int force_opt) {
+__global__ void grid_setup_kernel(const double* __restrict__ part, int nparts, double R, Grid* __restrict__ g, int force_opt,
+                                  unsigned long long* __restrict__ stats /* desc_stats_dev() */) {
     if (threadIdx.x != 0) return;
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int b = 0; b < nparts; ++b)
@@ -119,6 +122,7 @@ __global__ void grid_setup_kernel(const double* __restrict__ part, int nparts, d
     g->nx = (int)(floor((hi[0] - lo[0]) * g->invx) + 1); g->ny = (int)(floor((hi[1] - lo[1]) * g->invy) + 1); g->nz = (int)(floor((hi[2] - lo[2]) * g->invz) + 1);
     g->ncells = g->nx * g->ny * g->nz;
     g->L = fmax(hi[0] - lo[0], fmax(hi[1] - lo[1], hi[2] - lo[2]));
+    if (stats) stats[kDsSubdiv] = (unsigned long long)(g->fx << 16 | g->fy << 8 | g->fz);     // stored, not added: the last call's
 }
 
 // ---- grid: deterministic counting sort ------------------------------------------------------
@@ -298,14 +302,18 @@ __host__ __device__ inline double sqrt_threshold(double r) {
 //         WHICH keypoints survive and which points form a support; the support's coordinates are MATLAB's single pts_rel
 //         values.  Everything after that (mean, pca, the histogram) stays in double on those values: the summation order of
 //         MATLAB's single mean / pca is not knowable.
-template <int SM>
+// ST = true: the instantiation that counts into `stats` ("desc_stats" on).  The kernel is bound by VALU issue at 127 of 128
+// vector registers and already spills scalars: a pointer kept live, or fetched where it is used, cost 0.2 to 0.8 % of the
+// descriptor stage in every form measured (docs/BENCH_NOTES.md), so the default instantiation (ST = false) holds no counting code
+// at all -- its registers, spills and scratch are those of the kernel without the hook -- and the tests run every scene on both.
+template <int SM, bool ST>
 __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
     const double* __restrict__ sx, const double* __restrict__ sy, const double* __restrict__ sz,
     const float4* __restrict__ f4,
     const int32_t* __restrict__ sorted_idx, const int32_t* __restrict__ cell_start, const Grid* __restrict__ gp,
     const double* __restrict__ kp, const int32_t* __restrict__ perm, int S, int ldk, pcreg_desc_opts o, const Edges* __restrict__ edp, Edges32 e32, double R2T,
     int kp_single, int cap, int dbg_stop, int xcd_chunk, void* __restrict__ rows_out /*[S][ND] u32 or u16*/, int rows_u16,
-    int32_t* __restrict__ valid, int32_t* __restrict__ err) {
+    int32_t* __restrict__ valid, int32_t* __restrict__ err, unsigned long long* __restrict__ stats /* ST only: the "desc_stats" counters */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* lpos = reinterpret_cast<int*>(smem);                           // [cap] position in the sorted arrays
     __shared__ double s_redn[4 * 9];
@@ -328,6 +336,8 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
     // the fp64 bin edges stay in device memory: the literal path indexes them dynamically (hist_loc), and a by-value struct
     // would be copied to scratch by every workgroup for it (496 B per lane at kernel entry: measured 1 ms per 100 k keypoints)
     const Edges& ed = *edp;
+    // the "desc_stats" counters: one thread at a block-uniform point (but the literal count, per point, and the re-test count, per wave)
+    auto stat_add = [&](int word, unsigned long long v) { if constexpr (ST) atomicAdd(&stats[word], v); else { (void)word; (void)v; } };
     // workgroups are dealt round-robin over the 8 XCDs: XCD x walks its own eighth of the cell-ordered keypoints, so its
     // L2 holds the few cells its ~128 concurrent keypoints share instead of a slice of everybody's (PCREG_DESC_XCD=0: off)
     int slot = blockIdx.x;
@@ -518,6 +528,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
                 float X = 0.0f, Y = 0.0f, Z = 0.0f;
                 if (SM) { const float4 t4 = ldf4(off); X = t4.x; Y = t4.y; Z = t4.z; }
                 bal = __builtin_amdgcn_ballot_w64(j < end && inside(off, X, Y, Z, X - cxf, Y - cyf, Z - czf));
+                if (lane == 0) stat_add(kDsRetest, 1ull);
             }
             // the list holds BYTE offsets into the double columns (8 x the sorted position)
             if (__builtin_amdgcn_inverse_ballot_w64(bal))
@@ -557,6 +568,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
     const bool all = o.k >= 1.0;
     const int K = all ? n : (int)floor(n * o.k + 0.5);
     if (K < 2) return;
+    if (tid == 0) stat_add(kDsSelect, 1ull);
     bsum_n<3>(a3, s_redn);                          // summed while the candidates streamed by (collection pass 1)
     const double gx = a3[0] / n, gy = a3[1] / n, gz = a3[2] / n;
     if (!all) {
@@ -635,6 +647,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
             __syncthreads();
             vK = s_vk;
         } else {                                     // crowded bin (many equal distances): plain bisection on the keys
+            if (tid == 0) stat_add(kDsBisect, 1ull);
             unsigned long long blo = lo, bhi = hi;
             while (blo < bhi) {
                 const unsigned long long mid = blo + ((bhi - blo) >> 1);
@@ -668,6 +681,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
             __syncthreads();
             n_less = below + (t & 0xFFFF); n_eq = t >> 16;
         } else {
+            if (tid == 0) stat_add(kDsRecount, 1ull);
             int c1 = 0, c2 = 0;
             PCREG_MY_KEYS(c1 += k < t_lo; c2 += (k >= t_lo && k < t_hi);)
             n_less = bsum_i(c1, s_redi); n_eq = bsum_i(c2, s_redi);
@@ -679,6 +693,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
         if (n_eq == take_eq) {                       // the whole tie group is kept (nearly always a group of one): one comparison per key
             PCREG_MY_KEYS(sm |= (k < t_hi ? 1u : 0u) << pr;)
         } else {
+        if (tid == 0) stat_add(kDsTieRank, 1ull);
         PCREG_MY_KEYS(
             const unsigned long long key = k;
             bool sel = key < t_lo;
@@ -874,6 +889,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
                 votes += ((x * cu[0] + y * cu[3] + z * cu[6]) > 0 ? 1 : 0) + ((x * cu[2] + y * cu[5] + z * cu[8]) > 0 ? 1 << 16 : 0);
             }
         } else {                                    // (never seen: a support whose kept points all sit on the frame's planes) all votes in fp64
+            if (tid == 0) stat_add(kDsVote64, 1ull);
             votes = 0;
             PCREG_MY_PTS(
                 if (psel) {
@@ -913,6 +929,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
     if (permuted) {
         // the deferred points: literally, in the final frame, into the bins of the UNPERMUTED histogram's image
         const int ndef = s_ndef;
+        if (tid == 0 && ndef > 0) stat_add(kDsDeferred, (unsigned long long)ndef);
         unsigned* s_fin = reinterpret_cast<unsigned*>(&s_mask[0][0]);     // the collection's ballots are dead: 6 KiB >= 980 words
         static_assert(sizeof(unsigned long long) * 4 * kMaskCap >= sizeof(unsigned) * ND, "s_fin aliases s_mask");
         if (tid < NT * NP) {                         // one (theta, phi) run of NR radial bins per thread: no division per bin
@@ -930,7 +947,7 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
             double x = px, y = py, z = pz;
             if (o.ALIGN_POINTS) { x = px * cu[0] + py * cu[3] + pz * cu[6]; y = px * cu[1] + py * cu[4] + pz * cu[7]; z = px * cu[2] + py * cu[5] + pz * cu[8]; }
             bool safe64; int bb = bin_fast64(x, y, z, safe64);
-            if (!safe64) bb = bin_literal(x, y, z);
+            if (!safe64) { bb = bin_literal(x, y, z); stat_add(kDsLiteral, 1ull); }
             if (bb >= 0) atomicAdd(&s_fin[bb], 1u);
         }
         __syncthreads();
@@ -941,11 +958,12 @@ __global__ __launch_bounds__(kBlock, 4) void desc_kernel(
             for (int i = tid; i < ND / 2; i += kBlock) row[i] = (s_fin[2 * i] & 0xFFFFu) | (s_fin[2 * i + 1] << 16);
         } else { uint32_t* row = (uint32_t*)rows_out + (size_t)s * ND; for (int i = tid; i < ND; i += kBlock) row[i] = s_fin[i]; }
     } else {
+        if (tid == 0) stat_add(kDsRebin, 1ull);
         PCREG_MY_PTS(
             double x = px; double y = py; double z = pz;
             if (o.ALIGN_POINTS) { x = px * cu[0] + py * cu[3] + pz * cu[6]; y = px * cu[1] + py * cu[4] + pz * cu[7]; z = px * cu[2] + py * cu[5] + pz * cu[8]; }
             bool safe64; int bb = bin_fast64(x, y, z, safe64);
-            if (!safe64) bb = bin_literal(x, y, z);
+            if (!safe64) { bb = bin_literal(x, y, z); stat_add(kDsLiteral, 1ull); }
             if (bb >= 0) atomicAdd(&s_cnt[bb], 1u);)
         __syncthreads();
         if (rows_u16) { uint16_t* row = (uint16_t*)rows_out + (size_t)s * ND; for (int i = tid; i < ND; i += kBlock) row[i] = (uint16_t)s_cnt[i]; }
@@ -1063,9 +1081,10 @@ int launch_descriptors(const double* pts, int P, int ld, const double* kp, int S
     size_t need; const DescWs L = desc_ws_layout(P, S, ws, &need);
     if (ws_bytes < need) { set_error("descriptor workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
     const int tiles = L.tiles;
+    unsigned long long* const stats = desc_stats_dev();       // null while "desc_stats" is off
     int nb = (P + kBlock * 16 - 1) / (kBlock * 16); if (nb > 512) nb = 512; if (nb < 1) nb = 1;
     hipLaunchKernelGGL(bbox_partial_d_kernel, dim3(nb), dim3(kBlock), 0, st, pts, P, ld, L.bpart);
-    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, L.bpart, nb, o.R, L.grid, PCREG_EXP_ENV("PCREG_DESC_SUBDIV", -1));
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, L.bpart, nb, o.R, L.grid, PCREG_EXP_ENV("PCREG_DESC_SUBDIV", -1), stats);
     PCREG_HIP(hipMemsetAsync(L.counts, 0, (size_t)tiles * kMaxCells * 4, st));
     hipLaunchKernelGGL(grid_count_kernel, dim3(tiles), dim3(kBlock), 0, st, pts, P, ld, L.grid, L.cell_id, L.counts);
     hipLaunchKernelGGL(grid_cell_prefix_kernel, dim3((kMaxCells + 1 + 255) / 256), dim3(256), 0, st, L.counts, tiles, L.grid, L.cell_total);
@@ -1097,15 +1116,14 @@ int launch_descriptors(const double* pts, int P, int ld, const double* kp, int S
     hipLaunchKernelGGL(edges_store_kernel, dim3(1), dim3(1), 0, st, ed, L.edges_dev);
     void* rows_out = rows_u16 ? (void*)rows_u16 : (void*)L.stage;
     const int dbg = PCREG_EXP_ENV("PCREG_DESC_STOP", 0);
-    if (single_mode) {
-        PCREG_HIP(hipFuncSetAttribute((const void*)desc_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(desc_kernel<1>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, L.sx, L.sy, L.sz, (const float4*)L.f4, L.sorted_idx, L.cell_start, L.grid, kp, L.perm,
-                           S, ldk, o, (const Edges*)L.edges_dev, e32, R2T, single_mode == 1 ? 1 : 0, cap, dbg, xcd_chunk, rows_out, 1, L.valid, err_dev);
-    } else {
-        PCREG_HIP(hipFuncSetAttribute((const void*)desc_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(desc_kernel<0>, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, L.sx, L.sy, L.sz, (const float4*)L.f4, L.sorted_idx, L.cell_start, L.grid, kp, L.perm,
-                           S, ldk, o, (const Edges*)L.edges_dev, e32, R2T, 0, cap, dbg, xcd_chunk, rows_out, 1, L.valid, err_dev);
-    }
+    auto launch = [&](auto kernel, int kp_single) -> int {
+        PCREG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(xcd_chunk ? 8 * xcd_chunk : S), dim3(kBlock), lds, st, L.sx, L.sy, L.sz, (const float4*)L.f4, L.sorted_idx, L.cell_start, L.grid, kp, L.perm,
+                           S, ldk, o, (const Edges*)L.edges_dev, e32, R2T, kp_single, cap, dbg, xcd_chunk, rows_out, 1, L.valid, err_dev, stats);
+        return PCREG_OK;
+    };
+    if (single_mode) { if (int rc = stats ? launch(desc_kernel<1, true>, single_mode == 1 ? 1 : 0) : launch(desc_kernel<1, false>, single_mode == 1 ? 1 : 0)) return rc; }
+    else if (int rc = stats ? launch(desc_kernel<0, true>, 0) : launch(desc_kernel<0, false>, 0)) return rc;
     PCREG_HIP(hipGetLastError());
     const int nbs = (S + 255) / 256;
     hipLaunchKernelGGL(desc_count_kernel, dim3(nbs), dim3(256), 0, st, L.valid, S, L.bcnt);
