@@ -89,7 +89,11 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * skipping a hit whose row already shows the lane's root), "cluster_stats" (counters for pcreg_debug_cluster_stats),
  * "knn_tail_cap" (n > 0: the point search's exact tail lists the surviving tiles of n tiles per pass), "score_batch_slots"
  * (n > 0: pcreg_dev_model_score_f32 and pcreg_dev_model_refit_f32 batch whole transforms under n query slots instead of 4 Mi, one transform at least), "fpfh_radius_lanes" (4 or 16: the radius FPFH counts a
- * row's pairs with that many lanes instead of 64), "desc_stats" (counters for pcreg_debug_desc_stats); value 0
+ * row's pairs with that many lanes instead of 64), "desc_stats" (counters for pcreg_debug_desc_stats), "knn_direct"
+ * (1: the two-nearest search sends every query through the tile walk instead of answering the seeded queries with a small
+ * cell range from their ordering-grid cells; while "knn_stats" is on every query takes the walk as well, because those counters
+ * are defined over the walk of the whole query set), "knn_direct_stats" (counters for pcreg_debug_knn_direct_stats; it forces
+ * nothing); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -109,6 +113,11 @@ int  pcreg_debug_knn_stats(long long out[4], int reset);
  * visited (query block, tile) pairs, which is what it scores without the unit rule.  Resets these two only; the read
  * synchronises the device. */
 int  pcreg_debug_knn_unit_stats(long long out[2], int reset);
+/* With pcreg_debug_set("knn_direct_stats", 1): the direct answers of the two-nearest search summed over the
+ * searches since the last reset -- out[0] searches, [1] queries that were eligible and answered from their ordering-grid
+ * cells, [2] the rows ranked for them.  The key does not change which path a query takes.  Off: no extra work; on: one small
+ * launch per search, no host sync.  The read synchronises the device. */
+int  pcreg_debug_knn_direct_stats(long long out[3], int reset);
 /* With pcreg_debug_set("ransac_stats", 1): the counters of the staged RANSAC chain's bounded second pass summed over the calls
  * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
  * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */

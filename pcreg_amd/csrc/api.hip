@@ -85,7 +85,8 @@ int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); 
 // one block of device counters behind a debug key: allocated (zeroed) at the first use while the key is on
 struct Counters { DebugKey key; int n; unsigned long long* dev; };
 static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 6, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr},
-                g_cluster_stats{kDbgClusterStats, 4, nullptr}, g_desc_stats{kDbgDescStats, 10, nullptr};
+                g_cluster_stats{kDbgClusterStats, 4, nullptr}, g_desc_stats{kDbgDescStats, 10, nullptr},
+                g_knn_direct_stats{kDbgKnnDirectStats, 3, nullptr};
 static unsigned long long* counters_dev(Counters& c) {
     if (!debug_flag(c.key)) return nullptr;
     if (!c.dev) {
@@ -112,6 +113,7 @@ unsigned long long* knn_stats_dev() { return counters_dev(g_knn_stats); }
 unsigned long long* ransac_stats_dev() { return counters_dev(g_ransac_stats); }
 unsigned long long* cluster_stats_dev() { return counters_dev(g_cluster_stats); }
 unsigned long long* desc_stats_dev() { return counters_dev(g_desc_stats); }
+unsigned long long* knn_direct_stats_dev() { return counters_dev(g_knn_direct_stats); }
 }
 
 extern "C" {
@@ -121,7 +123,12 @@ int pcreg_debug_set(const char* key, int value) {
                                                         "ransac_f64score", "ransac_resident_f64", "align_times", "align_shape", "seg_debug",
                                                         "seg_batched", "seg_wave_finalize", "match_stats", "final_batch_mb", "knn_nocull",
                                                         "knn_stats", "ransac_pass2", "ransac_stats", "range_sort_cap", "cluster_noskip",
-                                                        "cluster_stats", "knn_tail_cap", "score_batch_slots", "fpfh_radius_lanes", "desc_stats"};
+                                                        "cluster_stats", "knn_tail_cap", "score_batch_slots", "fpfh_radius_lanes", "desc_stats",
+                                                        // "knn_direct": 0 (the default) answers eligible queries from their ordering-grid
+                                                        // cells, 1 sends every query through the tile walk (same bits: the A/B of one
+                                                        // binary).  While "knn_stats" is on every query takes the walk too: those counters
+                                                        // are defined over the walk of the whole query set.  "knn_direct_stats" only counts.
+                                                        "knn_direct", "knn_direct_stats"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -132,6 +139,7 @@ int pcreg_debug_set(const char* key, int value) {
 int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counters_read(pcreg::g_match_stats, out, reset); }
 int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 0, 4); }
 int pcreg_debug_knn_unit_stats(long long out[2], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 4, 2); }
+int pcreg_debug_knn_direct_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_knn_direct_stats, out, reset); }
 int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset); }
 int pcreg_debug_cluster_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_cluster_stats, out, reset); }
 int pcreg_debug_desc_stats(long long out[10], int reset) {     // (a read stages 8 words: the last two with a second one)

@@ -96,6 +96,9 @@ enum DebugKey {
     kDbgFpfhRadiusLanes,       // "fpfh_radius_lanes": 4 or 16 -- the radius FPFH's SPFH kernel walks a row's segment with that many lanes
                                // instead of 64 (a wave); the counts are integers, so every setting gives the same bits
     kDbgDescStats,             // "desc_stats": the descriptor kernel counts the rare branches it takes (pcreg_debug_desc_stats)
+    kDbgKnnDirect,             // "knn_direct": 0 = the two-nearest search answers the seeded queries with a small cell range from their
+                               // ordering-grid cells (knn_direct_kernel), 1 = every query takes the tile walk; same bits
+    kDbgKnnDirectStats,        // "knn_direct_stats": the direct answers are counted (pcreg_debug_knn_direct_stats); forces nothing
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -108,6 +111,9 @@ unsigned long long* match_stats_dev();
 //   [0] searches   [1] visited (query block, model tile) pairs   [2] nominal pairs (q_blocks x n_tiles)   [3] queries sent to the tail
 //   [4] (wave, 64-row unit) pairs scored inside the visited tiles   [5] 32 x visited pairs (pcreg_debug_knn_unit_stats reads [4], [5])
 unsigned long long* knn_stats_dev();
+// Device counters of the direct answers (knn_fast.hip: knn_direct_kernel), or null while "knn_direct_stats" is off:
+//   [0] two-nearest searches   [1] queries answered from their ordering-grid cells   [2] rows ranked for them
+unsigned long long* knn_direct_stats_dev();
 // Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
 //   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
 unsigned long long* ransac_stats_dev();

@@ -10,11 +10,14 @@
 //                                         sorted fp32 copy the rest is built from
 //   P3  prep_model_f16_kernel             sorted rows -> tiles of f16 matrix-core operands, R_m^2, and the seeding grid's cells
 //   P4  tile_box_kernel                   the exact fp32 box of every tile of kT16 sorted rows
-// and a search is SEVEN launches (a 128-KB memset of the query order's counters among them):
+// and a search is EIGHT launches (a 128-KB memset of the query order's counters among them):
 //   S1  seed_query_kernel    a first threshold per query from the model-wide seeding grid and its seed distance dk; clears
 //                            the call's counters and the candidate lists; per-workgroup boxes of the queries (query grid,
 //                            below); counts the queries per parent cell of the ordering grid (after the memset) and keeps
 //                            each query's place inside its cell
+//   S1d knn_direct_kernel    a seeded query whose dk-box covers few ordering-grid cells with few rows is answered exactly from
+//                            those cells of the sorted copy and marked (direct_rule.hpp; DESIGN 4.1, "Direct answers"); S1c
+//                            and S2 do not score a marked query, S3 only enters it into the query grid
 //   S1b query_order_ranked_kernel   the query SLOTS in spatial order (qperm); every workgroup derives the cell offsets it
 //                            needs from the counters itself, so no scan launch sits between S1 and the slots
 //   S1c knn_plan_kernel (knn_mfma16.hip)   the visit plan: per block of 512 query slots, ONCE, the box and largest dk of its
@@ -468,6 +471,117 @@ __device__ __forceinline__ void expand_flagged(unsigned flagged, int j_own, int 
 __device__ __forceinline__ unsigned group_flags(bool f) {
     return (unsigned)(__ballot(f) >> (threadIdx.x & 63 & ~(LPQ - 1))) & ((1u << LPQ) - 1);
 }
+// group-shuffle top-2 reduction of the LPQ lanes' sorted pairs, ordered by (dist, idx); empty slots are (+inf, -1 -> max uint)
+__device__ __forceinline__ void group_top2_merge(float& d1, float& d2, int& i1, int& i2) {
+#pragma unroll
+    for (int o = LPQ / 2; o > 0; o >>= 1) {
+        float e1 = __shfl_xor(d1, o), e2 = __shfl_xor(d2, o);
+        int j1 = __shfl_xor(i1, o), j2 = __shfl_xor(i2, o);
+        // merge two sorted pairs
+        bool first_mine = lex_lt_f(d1, i1, e1, j1);
+        float w1 = first_mine ? d1 : e1; int k1 = first_mine ? i1 : j1;
+        float x2 = first_mine ? d2 : d1; int y2 = first_mine ? i2 : i1;      // my next
+        float x3 = first_mine ? e1 : e2; int y3 = first_mine ? j1 : j2;      // other's next
+        bool sec_mine = lex_lt_f(x2, y2, x3, y3);
+        d1 = w1; i1 = k1; d2 = sec_mine ? x2 : x3; i2 = sec_mine ? y2 : y3;
+    }
+}
+
+// ---- S1d. direct answers: one 8-lane group per seeded query ("Direct answers") ------------------------
+// The rule of direct_rule.hpp: every row within the query's seed distance dk lies in the box of ordering-grid cells
+// [cell(q - rho), cell(q + rho)], so the top two by (distance, original row) over those cells' rows are the search's answer.
+// sort_cnt[key] is the END row of cell `key` in the sorted copy (the counting sort leaves it so; its start is the end of
+// key - 1).  A group whose range holds more than kDirectCells cells, or whose cells hold more than kDirectRows rows, or
+// whose query has no finite dk or coordinates, writes nothing: the verdict is the group's, formed before any store.
+// Lane l owns cells l, l + 8, .. of the range (x fastest); all their counters are loaded before the first is used.  The cells'
+// rows, concatenated in cell order, are dealt over the lanes -- row r of the concatenation to lane r % 8 -- kDirectBatch
+// per lane and trip, every load of a trip (x, y, z, perm) issued before the first compare; a row past the end reads the
+// first row of the range and is masked.  The (start, end) table of a group's cells lives in LDS.
+constexpr int kDirectBatch = 4;
+constexpr int kDirectSlots = (kDirectCells + LPQ - 1) / LPQ;              // cells per lane
+__global__ __launch_bounds__(kBlock) void knn_direct_kernel(
+    const float* __restrict__ q, int Q, int ldq, const float* __restrict__ dk, const Prep* __restrict__ prep,
+    const int32_t* __restrict__ sort_cnt, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm, int idx_base,
+    int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr) {
+    constexpr int kGroups = kBlock / LPQ, kTab = LPQ * kDirectSlots;
+    __shared__ int s_end[kGroups][kTab], s_off[kGroups][kTab];          // per cell: end in the concatenation, sorted row - position
+    __shared__ int s_n[2];
+    const int lane = threadIdx.x & (LPQ - 1), grp = threadIdx.x / LPQ;
+    const int qi = blockIdx.x * kGroups + grp;
+    const bool live = qi < Q;
+    const int qq = live ? qi : 0;
+    if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
+    const float qx = q[qq], qy = q[qq + (size_t)ldq], qz = q[qq + 2 * (size_t)ldq], D = dk[qq];
+    const float qv[3] = {qx, qy, qz}, s0[3] = {prep->sx0, prep->sy0, prep->sz0};
+    DirectRange R;
+    bool ok = direct_range(qv, D, s0, prep->inv_s, (1 << kSortBits) - 1, &R) && live;
+    if (!ok) { for (int c = 0; c < 3; ++c) R.lo[c] = R.hi[c] = 0; }
+    const int nx = R.hi[0] - R.lo[0] + 1, ny = R.hi[1] - R.lo[1] + 1;
+    const int ncell = direct_cells(R);
+    ok = ok && ncell <= kDirectCells;
+    // the ends of the lane's cells and of the cells in front of them (key 0 has none: masked)
+    int e0[kDirectSlots], e1[kDirectSlots]; bool has[kDirectSlots], first[kDirectSlots];
+#pragma unroll
+    for (int k = 0; k < kDirectSlots; ++k) {
+        const int c = lane + LPQ * k;
+        has[k] = ok && c < ncell;
+        const int cc = has[k] ? c : 0;
+        const int ix = R.lo[0] + cc % nx, iy = R.lo[1] + (cc / nx) % ny, iz = R.lo[2] + cc / (nx * ny);
+        const int key = (int)(morton_spread((unsigned)ix) | (morton_spread((unsigned)iy) << 1) | (morton_spread((unsigned)iz) << 2));
+        first[k] = key == 0;
+        e0[k] = sort_cnt[max(key - 1, 0)]; e1[k] = sort_cnt[key];
+    }
+    // the concatenation's prefix over the cells in order c = lane + 8 k: a group scan per slot, the carry across slots
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < kDirectSlots; ++k) {
+        const int start = first[k] ? 0 : e0[k], n = has[k] ? max(e1[k] - start, 0) : 0;
+        int inc = n;
+#pragma unroll
+        for (int o = 1; o < LPQ; o <<= 1) { const int y = __shfl_up(inc, o, LPQ); if (lane >= o) inc += y; }
+        const int end = total + inc;
+        s_end[grp][lane + LPQ * k] = end;
+        s_off[grp][lane + LPQ * k] = start - (end - n);
+        total += __shfl(inc, LPQ - 1, LPQ);
+    }
+    ok = ok && total <= kDirectRows;                      // the group's verdict: total is the same in its eight lanes
+    const int rows = ok ? total : 0;
+    __syncthreads();                                      // the tables (and the block's two counters, cleared above)
+    float d1 = INFINITY, d2 = INFINITY; int i1 = -1, i2 = -1;
+    int c = 0;                                            // the cell of the lane's current row: it only moves forward
+    for (int r0 = 0; r0 < rows; r0 += LPQ * kDirectBatch) {
+        float x[kDirectBatch], y[kDirectBatch], z[kDirectBatch]; int oj[kDirectBatch]; bool in[kDirectBatch];
+#pragma unroll
+        for (int t = 0; t < kDirectBatch; ++t) {
+            const int r = r0 + LPQ * t + lane;
+            in[t] = r < rows;
+            const int rr = in[t] ? r : 0;
+            if (in[t]) while (c < ncell - 1 && rr >= s_end[grp][c]) ++c;
+            const int row = min(max(rr + s_off[grp][in[t] ? c : 0], 0), M - 1);
+            x[t] = ms[row]; y[t] = ms[row + (size_t)M]; z[t] = ms[row + 2 * (size_t)M]; oj[t] = perm[row];
+        }
+#pragma unroll
+        for (int t = 0; t < kDirectBatch; ++t) {
+            const float d = point_d2(qx, qy, qz, x[t], y[t], z[t]);
+            const bool in2 = in[t] && lex_lt_f(d, oj[t], d2, i2), in1 = in2 && lex_lt_f(d, oj[t], d1, i1);
+            d2 = in1 ? d1 : (in2 ? d : d2); i2 = in1 ? i1 : (in2 ? oj[t] : i2);      // (selects: straight-line code)
+            d1 = in1 ? d : d1; i1 = in1 ? oj[t] : i1;
+        }
+    }
+    group_top2_merge(d1, d2, i1, i2);
+    // Two real rows lie within dk, so both answers exist; were a prepared block ever inconsistent with that, the query would
+    // simply take the walk.
+    ok = ok && i2 >= 0;
+    if (ok && lane == 0) {
+        idx[(size_t)qi * 2] = i1 + idx_base; idx[(size_t)qi * 2 + 1] = i2 + idx_base;
+        dist[(size_t)qi * 2] = d1; dist[(size_t)qi * 2 + 1] = d2;
+        cand_cnt[qi] = kDirectMark;
+        atomicAdd(&s_n[0], 1); atomicAdd(&s_n[1], rows);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n[0] > 0) { atomicAdd(&ctr->n_direct, s_n[0]); atomicAdd(&ctr->direct_rows, s_n[1]); }
+}
+
 __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
     const float* __restrict__ q, int Q, int ldq, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm,
     const Prep* __restrict__ prep, const unsigned* __restrict__ rm2_bits, const unsigned* __restrict__ gthr,
@@ -484,7 +598,9 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
         const int s = atomicAdd(&ug_cnt[cell], 1);
         if (s < kUgSlots) ug_slots[(size_t)cell * kUgSlots + s] = make_float4(qx, qy, qz, __int_as_float(qi));
     }
-    const int total = min(cand_cnt[qi], cap);
+    const int listed = cand_cnt[qi];
+    if (direct_answered(listed)) return;       // knn_direct_kernel wrote its answer (the whole group leaves: one query, one word)
+    const int total = min(listed, cap);
     const uint2* ent = ent_all + (size_t)qi * cap;
     // pass 1: the two smallest approximate scores of the union (values only)
     float a1 = INFINITY, a2 = INFINITY;
@@ -538,19 +654,7 @@ __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
         const int j = (int)v.x; const float sc = __uint_as_float(v.y);
         expand_flagged(group_flags(e0 + lane < total && j >= 0 && (sc <= cut_up || all)), j, lane, qx, qy, qz, ms, M, perm, d1, d2, i1, i2);
     }
-    // group-shuffle top-2 reduction ordered by (dist, idx); empty slots are (+inf, -1 -> max uint)
-#pragma unroll
-    for (int o = LPQ / 2; o > 0; o >>= 1) {
-        float e1 = __shfl_xor(d1, o), e2 = __shfl_xor(d2, o);
-        int j1 = __shfl_xor(i1, o), j2 = __shfl_xor(i2, o);
-        // merge two sorted pairs
-        bool first_mine = lex_lt_f(d1, i1, e1, j1);
-        float w1 = first_mine ? d1 : e1; int k1 = first_mine ? i1 : j1;
-        float x2 = first_mine ? d2 : d1; int y2 = first_mine ? i2 : i1;      // my next
-        float x3 = first_mine ? e1 : e2; int y3 = first_mine ? j1 : j2;      // other's next
-        bool sec_mine = lex_lt_f(x2, y2, x3, y3);
-        d1 = w1; i1 = k1; d2 = sec_mine ? x2 : x3; i2 = sec_mine ? y2 : y3;
-    }
+    group_top2_merge(d1, d2, i1, i2);
     // certificate
     const unsigned gword = gthr[qi];
     const float G = ord2f(gword);
@@ -810,7 +914,14 @@ __global__ void knn_stats_kernel(const SearchCounters* __restrict__ ctr, long lo
     atomicAdd(&stats[4], (unsigned long long)(unsigned)ctr->units); atomicAdd(&stats[5], 32ull * (unsigned long long)nv);
 }
 
-constexpr int kSeedMinM = 16 * 1024;             // below this the lists settle within the first tiles anyway
+// pcreg_debug_set("knn_direct_stats", 1): this search's direct answers added to the process-wide sums (after S1d)
+__global__ void knn_direct_stats_kernel(const SearchCounters* __restrict__ ctr, unsigned long long* __restrict__ stats) {
+    if (threadIdx.x != 0) return;
+    atomicAdd(&stats[0], 1ull); atomicAdd(&stats[1], (unsigned long long)(unsigned)ctr->n_direct);
+    atomicAdd(&stats[2], (unsigned long long)(unsigned)ctr->direct_rows);
+}
+
+constexpr int kSeedMinM = 16 * 1024;            // below this the lists settle within the first tiles anyway
 // the grid is sized on the device (about M/2 cells plus the margin layer); this is the capacity it may use
 size_t seed_cell_cap(int M) { return std::min<size_t>((size_t)kSeedMaxCells, std::max<size_t>(4096, (size_t)M)); }
 
@@ -916,6 +1027,15 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
                        (const float4*)v.seed_slots, (v.seeded && v.M > 0) ? 1 : 0, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr,
                        grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr, s.flag_list);
     // (a query's place inside its cell waits in flag_list, which is free until knn_finalize_kernel lists the unproven queries)
+    // S1d: the seeded queries whose cell range is small are answered here and marked; the launches below skip them.  Not
+    // with "knn_direct" = 1 (every query takes the tile walk: the A/B of one binary), and not while "knn_stats" collects: its
+    // counters are defined over the walk of the whole query set.
+    if (v.seeded && v.M > 0 && debug_flag(kDbgKnnDirect) == 0 && debug_flag(kDbgKnnStats) == 0)
+        hipLaunchKernelGGL(knn_direct_kernel, dim3((Q + kBlock / LPQ - 1) / (kBlock / LPQ)), dim3(kBlock), 0, st, q, Q, ldq, (const float*)s.dk,
+                           (const Prep*)v.prep, (const int32_t*)v.sort_cnt, (const float*)v.ms, v.M, (const int32_t*)v.perm, (int)idx_base, idx, dist,
+                           s.cand_cnt, ctr);
+    if (unsigned long long* dstats = knn_direct_stats_dev())
+        hipLaunchKernelGGL(knn_direct_stats_kernel, dim3(1), dim3(64), 0, st, (const SearchCounters*)ctr, dstats);
     if (order)
         hipLaunchKernelGGL(query_order_ranked_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep,
                            (const int32_t*)s.qcnt, (const int32_t*)s.flag_list, s.qperm);

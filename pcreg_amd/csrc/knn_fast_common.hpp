@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "cull_rule.hpp"
+#include "direct_rule.hpp"
 #include <cmath>
 
 namespace pcreg {
@@ -55,9 +56,9 @@ __device__ __forceinline__ unsigned morton_spread(unsigned v) {           // bit
 __device__ __forceinline__ int sort_key(float x, float y, float z, const Prep* __restrict__ p) {
     const float top = (float)((1 << kSortBits) - 1);
     // clamped into the grid before the conversion (NaN -> 0: fmaxf returns the number)
-    const unsigned ix = (unsigned)fminf(fmaxf(floorf((x - p->sx0) * p->inv_s), 0.0f), top);
-    const unsigned iy = (unsigned)fminf(fmaxf(floorf((y - p->sy0) * p->inv_s), 0.0f), top);
-    const unsigned iz = (unsigned)fminf(fmaxf(floorf((z - p->sz0) * p->inv_s), 0.0f), top);
+    const unsigned ix = (unsigned)order_cell(x, p->sx0, p->inv_s, top);      // (direct_rule.hpp: the direct answers walk the same cells)
+    const unsigned iy = (unsigned)order_cell(y, p->sy0, p->inv_s, top);
+    const unsigned iz = (unsigned)order_cell(z, p->sz0, p->inv_s, top);
     return (int)(morton_spread(ix) | (morton_spread(iy) << 1) | (morton_spread(iz) << 2));
 }
 // A query whose scaled coordinate leaves this range is not scored on the matrix cores (its f16 operands would
@@ -127,11 +128,20 @@ struct SearchCounters {
     int32_t ticket;                  // match_finish_kernel's workgroup tickets
     int32_t finished;                // ... and how many of its workgroups are through (the last one clears ticket / status again)
     int32_t units;                   // (candidate wave, 64-row unit) pairs the visit plan marks for scoring (knn_plan_kernel)
-    int32_t pad[28];
+    int32_t n_direct;                // queries knn_direct_kernel answered from their ordering-grid cells
+    int32_t direct_rows;             // ... and the rows it ranked for them
+    int32_t pad[26];
     int32_t visited[kVisitSlots];    // (query block, model tile) pairs the candidate kernel scored, spread over words by workgroup
     int32_t done[kMaxQTiles];        // tail (many-form): arrivals per tile of listed queries
     int32_t status[kMatchMaxBlocks]; // match_finish_kernel: per-workgroup kept counts (ready bit 31)
 };
+
+// The mark of a query that knn_direct_kernel has answered ("Direct answers"): its cand_cnt word, which
+// seed_query_kernel sets to 0 in every call and the candidate kernel only ever adds list lengths to, is negative.  The plan
+// and the candidate kernel do not score such a query (so nothing is ever added to its word), knn_finalize_kernel leaves its
+// answer alone.
+constexpr int32_t kDirectMark = (int32_t)0x80000000;
+__device__ __forceinline__ bool direct_answered(int32_t cand_cnt_word) { return cand_cnt_word < 0; }
 
 // ---- 2. candidate generation -------------------------------------------------------------
 struct Cand { float s[KC]; int i[KC]; };

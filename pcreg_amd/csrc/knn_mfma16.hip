@@ -142,7 +142,8 @@ __device__ void ug_reduce_boxes(const float* __restrict__ part /*[n][6]*/, int n
 // belongs to list position p, its byte v to candidate wave v (slots [128 v, 128 v + 128) of the block), bit s of the byte to
 // the tile's s-th UNIT of 64 rows.  A bit is clear when the rule skips the unit's box (ubox) against the box and the largest
 // seed distance of that wave's scored queries; a wave with an unseeded query keeps every unit, a wave without a scored query
-// none, and cull == 0 keeps everything.
+// none, and cull == 0 keeps everything.  A query that knn_direct_kernel has answered (direct_answered: knn_fast_common.hpp)
+// is not scored: a block or a wave whose queries are all answered or unscorable has an empty box and lists nothing.
 #ifndef PCREG_PLAN_C
 #define PCREG_PLAN_C 4
 #endif
@@ -153,7 +154,8 @@ __host__ __device__ __forceinline__ int plan_live(int n_vis, int W) {          /
     return we < W ? we : W;
 }
 __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restrict__ q, int Q, int ldq, const int32_t* __restrict__ qperm,
-                                                          const float* __restrict__ dk, const float* __restrict__ tbox,
+                                                          const float* __restrict__ dk, const int32_t* __restrict__ cand_cnt,
+                                                          const float* __restrict__ tbox,
                                                           const float* __restrict__ ubox, int n_tiles, int cull,
                                                           const Prep* __restrict__ prep, int32_t* __restrict__ n_vis,
                                                           int32_t* __restrict__ vis_list, uint32_t* __restrict__ vis_mask,
@@ -163,6 +165,10 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
     constexpr int kListLds = 2048;                // the head of the block's list stays in LDS for the mask pass (a bench block lists 37-181 tiles)
     __shared__ int s_tl[kListLds];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qb = (int)blockIdx.x;
+    if (ctr->n_direct == Q) {                     // knn_direct_kernel answered every query: no block has anything to visit
+        if (tid == 0) n_vis[qb] = 0;
+        return;
+    }
     const float sg = prep->sigma, cx = prep->cx, cy = prep->cy, cz = prep->cz;
     const bool scale_ok = scale_usable(prep);
     // the block's box and largest seed distance over its SCORED queries (the candidate kernel's own test: a query it does
@@ -176,7 +182,8 @@ __global__ __launch_bounds__(kBlock) void knn_plan_kernel(const float* __restric
             const int qi = qperm[slot];
             const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
             const float sx = sg * (px - cx), sy = sg * (py - cy), sz = sg * (pz - cz);
-            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
+            // (a query knn_direct_kernel has answered is not scored either: it has no say in the boxes and distances)
+            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax && !direct_answered(cand_cnt[qi])) {
                 blo[0] = fminf(blo[0], px); blo[1] = fminf(blo[1], py); blo[2] = fminf(blo[2], pz);
                 bhi[0] = fmaxf(bhi[0], px); bhi[1] = fmaxf(bhi[1], py); bhi[2] = fmaxf(bhi[2], pz);
                 const float e = dk[qi];
@@ -368,6 +375,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
     for (int g = 0; g < QG; ++g) {
         const int slot = q_base + g * 32 + col;
         float X = 0.0f, Y = 0.0f, Z = 0.0f, one = 0.0f;
+        bool answered = false;
         if (slot < Q) {
             const int qi = qperm[slot];
             const float px = q[qi], py = q[qi + (size_t)ldq], pz = q[qi + 2 * (size_t)ldq];
@@ -375,7 +383,10 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
             // a query far outside the prepared model's box (or not finite), or any query of a model whose scale leaves fp32
             // (scale_usable), is not scored here: all-zero operands, no list entries; knn_finalize_kernel applies the same
             // test and sends it to the exact fallback (and knn_plan_kernel leaves it out of the block's box)
-            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax) {
+            // A query knn_direct_kernel has answered is not scored either, and its threshold starts at -inf: no score is ever
+            // below it, so it lists nothing and its (negative) cand_cnt word is never added to.
+            answered = direct_answered(cand_cnt[qi]);
+            if (scale_ok && fabsf(sx) <= kQueryScaledMax && fabsf(sy) <= kQueryScaledMax && fabsf(sz) <= kQueryScaledMax && !answered) {
                 X = -2.0f * sx; Y = -2.0f * sy; Z = -2.0f * sz; one = 1.0f;
             }
         }
@@ -385,7 +396,7 @@ __global__ __launch_bounds__(kBlock, kT16 > 768 ? 2 : (kT16 > 512 ? 3 : (QG <= 2
         bq[g] = half == 0 ? f16x8{Xh, Xh, Xl, Xl, Yh, Yh, Yl, Yl} : f16x8{Zh, Zh, Zl, Zl, o1, o1, o1, (_Float16)0.0f};
 #pragma unroll
         for (int k = 0; k < KC; ++k) { cand[g].s[k] = INFINITY; cand[g].i[k] = -1; }
-        thr[g] = INFINITY; s_gseen[g][threadIdx.x] = 0xFFFFFFFFu;
+        thr[g] = answered ? -INFINITY : INFINITY; s_gseen[g][threadIdx.x] = 0xFFFFFFFFu;
     }
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)&tile[0][0];
     int walked = 0;                               // tiles walked so far (the threshold refresh's cadence)
@@ -627,7 +638,7 @@ int launch_prep_model_f16(const float* m, int M, int ldm, const void* prep, unsi
     return PCREG_OK;
 }
 
-// The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it).  qperm: query
+// The candidate stage against a prepared model.  cand_cnt [Q] must be zero (seed_query_kernel clears it) or hold the mark of a directly answered query (kDirectMark), which is not scored.  qperm: query
 // slot -> query row (spatial order); dk: each query's seed distance; tbox: the model tiles' boxes; cull = 0 visits every
 // tile; ubox: the boxes of the tiles' 64-row units.  n_vis [q_blocks], vis_list and vis_mask [q_blocks * n_tiles]: the visit
 // plan and its unit masks, written by knn_plan_kernel (launched here) and read
@@ -642,7 +653,7 @@ int launch_knn_candidates_f16(const float* q, int Q, int ldq, const int32_t* qpe
     *W_out = W;
     if (M <= 0 || Q <= 0) return PCREG_OK;
     const int n_tiles = (M + kT16 - 1) / kT16;
-    hipLaunchKernelGGL(knn_plan_kernel, dim3(q_blocks), dim3(kBlock), 0, st, q, Q, ldq, qperm, dk, tbox, ubox, n_tiles, cull, (const Prep*)prep,
+    hipLaunchKernelGGL(knn_plan_kernel, dim3(q_blocks), dim3(kBlock), 0, st, q, Q, ldq, qperm, dk, (const int32_t*)cand_cnt, tbox, ubox, n_tiles, cull, (const Prep*)prep,
                        n_vis, vis_list, vis_mask, (SearchCounters*)ctr);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_time_on && timed) {
