@@ -29,24 +29,6 @@ namespace {
 
 constexpr int kIssMaxM = 1 << 26;                    // below it no sum overflows: |q| <= 2^18 + 1, so |S2| < 2^26 (2^18 + 1)^2 < 2^63
 
-// a 128-bit integer rounded ONCE to double (to nearest, ties to even).  The top 64 bits of |v| with the bits below them folded
-// into the lowest one: 64 > 53 + 2, so the sticky bit never reaches the rounding position and the u64 -> double conversion
-// (correctly rounded) rounds the whole number; the power of two is exact.
-__device__ __forceinline__ double i128_to_double(__int128 v) {
-    const bool neg = v < 0;
-    const unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
-    const unsigned long long hi = (unsigned long long)(u >> 64), lo = (unsigned long long)u;
-    double r;
-    if (hi == 0) r = (double)lo;
-    else {
-        const int sh = __clzll((long long)hi);                   // 0 .. 63
-        const unsigned long long top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
-        const unsigned long long rest = sh ? lo << sh : lo;
-        r = ldexp((double)(top | (rest ? 1ull : 0ull)), 64 - sh);
-    }
-    return neg ? -r : r;
-}
-
 // ---- I1. the scatter ------------------------------------------------------------------------------------------------------
 // scale = 2^(18 - e) as a float and back = 4^-(18 - e) as a double, e from r2 on the host (launch_model_iss).  dx * scale is exact
 // (a power of two; a product below the normal range rounds to an integer 0 either way), rintf rounds to nearest even.

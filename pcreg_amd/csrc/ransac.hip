@@ -20,6 +20,7 @@
 // No data leaves the chip between the sample fit and the final inlier list.
 #include "common.hpp"
 #include "moments.hpp"
+#include "wave_math.hpp"                             // splitmix64
 #include <cfloat>
 #include <cstddef>
 #include <cstdio>
@@ -55,12 +56,6 @@ __device__ __forceinline__ double ulp_at(double x) {   // MATLAB eps(x)
 }
 __device__ __forceinline__ int matlab_round_i(double x) {   // ransac.m:28
     return (int)(x >= 0 ? floor(x + 0.5) : -floor(-x + 0.5));
-}
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull; unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 // ---------------------------------------------------------------- 3x3 kernels (per lane)

@@ -11,6 +11,8 @@
 // square root (t = sgn * |h| / (|d| + sqrt(d^2 + h^2)) with d = a_qq - a_pp, h = 2 a_pq is the textbook
 // t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) with theta = d / h multiplied through by |h|), and the closed-form
 // update of the symmetric matrix (a_pp -= t a_pq, a_qq += t a_pq, two entries rotated) instead of two 3 x 3 products.
+//
+// splitmix64, i128_to_double: the two integer helpers that more than one file needs, their one definition.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -80,6 +82,32 @@ __device__ __forceinline__ int wave_scan_incl_i(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);      // row_bcast:15 -> rows 1 and 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 -> rows 2 and 3
     return v;
+}
+
+// the sampler hash of RANSAC and of the MSAC fitters (include/pcreg.h publishes it)
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull; unsigned long long z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// a 128-bit integer rounded ONCE to double (to nearest, ties to even).  The top 64 bits of |v| with the bits below
+// them folded into the lowest one: 64 > 53 + 2, so the sticky bit never reaches the rounding position and the u64 -> double
+// conversion (correctly rounded) rounds the whole number; the power of two is exact.
+__device__ __forceinline__ double i128_to_double(__int128 v) {
+    const bool neg = v < 0;
+    const unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    const unsigned long long hi = (unsigned long long)(u >> 64), lo = (unsigned long long)u;
+    double r;
+    if (hi == 0) r = (double)lo;
+    else {
+        const int sh = __clzll((long long)hi);                   // 0 .. 63
+        const unsigned long long top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+        const unsigned long long rest = sh ? lo << sh : lo;
+        r = ldexp((double)(top | (rest ? 1ull : 0ull)), 64 - sh);
+    }
+    return neg ? -r : r;
 }
 
 // a = {a00, a01, a02, a11, a12, a22} (in/out: the diagonal ends up in a[0], a[3], a[5]); V row-major 3 x 3, columns =

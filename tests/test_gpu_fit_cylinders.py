@@ -135,9 +135,10 @@ def _check(model, nrm, got, t, max_cylinders, n_trials, min_inliers=4, seed=0, s
 
 
 # ---- 1. the scene ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M, B, mi", ref.SCENES)
+@pytest.mark.parametrize("M, B, mi", (*ref.SCENES, (2051, 300, 100)))
 def test_scene_against_the_reference(M, B, mi):
-    """two noisy cylinders, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks"""
+    """two noisy cylinders, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks; 2051 a
+    second chunk of 3 rows (the scoring reads a NaN-staged fourth), B = 300 a partial second trial block (the clamped lanes b >= B)"""
     m, nrm, _ = _scene(M)
     kw = dict(max_radius=RMAX, max_cylinders=ref.SCENE_P, n_trials=B, min_inliers=mi, seed=ref.SCENE_SEED)
     got = _fit(m, nrm, T, **kw)

@@ -135,9 +135,10 @@ def _check(model, got, t, max_spheres, n_trials, min_inliers=4, seed=0, samples=
 
 
 # ---- 1. the scene ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M, B, mi", ref.SCENES)
+@pytest.mark.parametrize("M, B, mi", (*ref.SCENES, (2051, 300, 100)))
 def test_scene_against_the_reference(M, B, mi):
-    """three noisy spheres, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks"""
+    """three noisy spheres, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks; 2051 a
+    second chunk of 3 rows (the scoring reads a NaN-staged fourth), B = 300 a partial second trial block (the clamped lanes b >= B)"""
     m = _scene(M)
     got = _fit(m, T, max_spheres=ref.SCENE_P, n_trials=B, min_inliers=mi, seed=ref.SCENE_SEED)
     _check(m, got, T, ref.SCENE_P, B, mi, ref.SCENE_SEED, what=f"scene M = {M}")

@@ -126,9 +126,10 @@ def _check(model, got, t, max_planes, n_trials, min_inliers=3, seed=0, samples=N
 
 
 # ---- 1. the scene ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M, B, mi", [(1030, 128, 40), (4096, 256, 200)])
+@pytest.mark.parametrize("M, B, mi", [(1030, 128, 40), (4096, 256, 200), (2051, 300, 100)])
 def test_scene_against_the_reference(M, B, mi):
-    """three noisy planes, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks"""
+    """three noisy planes, then a stop: M = 1030 is two 512-row tiles and a 6-row tail (one scoring chunk), 4096 two chunks; 2051 a
+    second chunk of 3 rows (the scoring reads a NaN-staged fourth), B = 300 a partial second trial block (the clamped lanes b >= B)"""
     m = _scene(M)
     got = _fit(m, 0.08, max_planes=5, n_trials=B, min_inliers=mi, seed=7)
     share = _check(m, got, 0.08, 5, B, mi, 7, what=f"scene M = {M}")
