@@ -93,7 +93,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * (1: the two-nearest search sends every query through the tile walk instead of answering the seeded queries with a small
  * cell range from their ordering-grid cells; while "knn_stats" is on every query takes the walk as well, because those counters
  * are defined over the walk of the whole query set), "knn_direct_stats" (counters for pcreg_debug_knn_direct_stats; it forces
- * nothing); value 0
+ * nothing), "knn_seed_fused" (1: the two-nearest search seeds and answers directly in two launches instead of one; same
+ * bits); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);

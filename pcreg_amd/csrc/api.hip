@@ -128,7 +128,9 @@ int pcreg_debug_set(const char* key, int value) {
                                                         // cells, 1 sends every query through the tile walk (same bits: the A/B of one
                                                         // binary).  While "knn_stats" is on every query takes the walk too: those counters
                                                         // are defined over the walk of the whole query set.  "knn_direct_stats" only counts.
-                                                        "knn_direct", "knn_direct_stats"};
+                                                        // "knn_seed_fused": 0 (the default) seeds and answers directly in one launch, 1 in
+                                                        // two (same bits: the A/B of one binary).
+                                                        "knn_direct", "knn_direct_stats", "knn_seed_fused"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }

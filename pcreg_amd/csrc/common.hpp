@@ -99,6 +99,8 @@ enum DebugKey {
     kDbgKnnDirect,             // "knn_direct": 0 = the two-nearest search answers the seeded queries with a small cell range from their
                                // ordering-grid cells (knn_direct_kernel), 1 = every query takes the tile walk; same bits
     kDbgKnnDirectStats,        // "knn_direct_stats": the direct answers are counted (pcreg_debug_knn_direct_stats); forces nothing
+    kDbgKnnSeedFused,          // "knn_seed_fused": 0 = seeding and the direct answers are one launch (seed_direct_kernel), 1 = two launches
+                               // (seed_query_kernel, knn_direct_kernel); same bits
     kDbgCount
 };
 int debug_flag(DebugKey k);

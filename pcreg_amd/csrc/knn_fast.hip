@@ -10,16 +10,21 @@
 //                                         sorted fp32 copy the rest is built from
 //   P3  prep_model_f16_kernel             sorted rows -> tiles of f16 matrix-core operands, R_m^2, and the seeding grid's cells
 //   P4  tile_box_kernel                   the exact fp32 box of every tile of kT16 sorted rows
-// and a search is EIGHT launches (a 128-KB memset of the query order's counters among them):
-//   S1  seed_query_kernel    a first threshold per query from the model-wide seeding grid and its seed distance dk; clears
+// and a search is SEVEN launches (a 128-KB memset of the query order's counters among them):
+//   S1 + S1d  seed_direct_kernel   for a seeded model, both phases in one launch and one 8-lane group per query:
+//     S1  (seed_body)        a first threshold per query from the model-wide seeding grid and its seed distance dk; clears
 //                            the call's counters and the candidate lists; per-workgroup boxes of the queries (query grid,
 //                            below); counts the queries per parent cell of the ordering grid (after the memset) and keeps
 //                            each query's place inside its cell
-//   S1d knn_direct_kernel    a seeded query whose dk-box covers few ordering-grid cells with few rows is answered exactly from
+//     S1d (direct_body)      a seeded query whose dk-box covers few ordering-grid cells with few rows is answered exactly from
 //                            those cells of the sorted copy and marked (direct_rule.hpp; DESIGN 4.1, "Direct answers"); S1c
-//                            and S2 do not score a marked query, S3 only enters it into the query grid
-//   S1b query_order_ranked_kernel   the query SLOTS in spatial order (qperm); every workgroup derives the cell offsets it
-//                            needs from the counters itself, so no scan launch sits between S1 and the slots
+//                            and S2 do not score a marked query, S3 only enters it into the query grid.  Every workgroup
+//                            leaves its (answered, rows) pair in a slot of its own; S1b sums them
+//             seed_query_kernel alone runs S1 where there is no direct phase (no seeding grid, "knn_direct" = 1, "knn_stats"),
+//             and seed_query_kernel + knn_direct_kernel are the same two bodies in two launches ("knn_seed_fused" = 1)
+//   S1b query_order_ranked_kernel   publishes the direct phase's sums (ctr->n_direct, direct_rows) and leaves when every query
+//                            has been answered; else the query SLOTS in spatial order (qperm); every workgroup derives the cell
+//                            offsets it needs from the counters itself, so no scan launch sits between S1 and the slots
 //   S1c knn_plan_kernel (knn_mfma16.hip)   the visit plan: per block of 512 query slots, ONCE, the box and largest dk of its
 //                            scored queries and the ascending list of the model tiles they cannot rule out
 //   S2  knn_candidates_f16_pipe_kernel (knn_mfma16.hip)   the scores of a block against the tiles of its plan, on the matrix
@@ -235,13 +240,40 @@ __global__ __launch_bounds__(kBlock) void query_order_kernel(const float* __rest
 // rank each query's place inside its cell (both from seed_query_kernel).  Every workgroup sums all kQueryKeys counters
 // itself (L2-resident, 128 per thread) and keeps the exclusive offsets of every 16th in LDS; a query adds the at most 15
 // counters in front of its own cell's.  No atomics: cnt is only read.
+//
+// The direct answers' count is summed here as well.  The workgroups of the direct phase (direct_body, below) leave their
+// (answered, rows) pairs in dparts [nparts] with plain stores -- null when no direct phase ran: nothing was answered -- and
+// this launch is the first one after them: workgroup 0 publishes the two sums in ctr->n_direct / ctr->direct_rows, where
+// knn_plan_kernel, knn_direct_stats_kernel and the tests read them as before.  When every query has been answered nobody
+// reads qperm in this call and the kernel leaves before it sums a counter.  The readers of qperm, all in
+// launch_model_search: knn_plan_kernel (leaves on n_direct == Q before its first qperm read), knn_candidates_f16_pipe_kernel
+// (reads n_vis[qb] = 0 first and leaves; its surplus workgroup reads ug_part only), and nobody else -- knn_finalize_kernel
+// and knn_tail_kernel take no qperm.  search_export (a test hook) then copies the slots of an earlier call.
+// Every workgroup forms the sum itself while the pairs are few (kDirectPartsAll: 16 KB, an eighth of the counters it would
+// sum otherwise); beyond that only workgroup 0 does, and the others write their slots as if somebody read them.
+constexpr int kDirectPartsAll = 2048;
 __global__ __launch_bounds__(kBlock) void query_order_ranked_kernel(const float* __restrict__ q, int Q, int ldq, const Prep* __restrict__ prep,
                                                                     const int32_t* __restrict__ cnt, const int32_t* __restrict__ rank,
-                                                                    int32_t* __restrict__ qperm) {
+                                                                    int32_t* __restrict__ qperm, const int2* __restrict__ dparts, int nparts,
+                                                                    SearchCounters* __restrict__ ctr) {
     constexpr int kPer = kQueryKeys / kBlock, kSub = kPer / 16;
     static_assert(kQueryKeys % (kBlock * 16) == 0, "every thread owns whole groups of 16 counters");
     __shared__ int s_sub[kQueryKeys / 16], s_w[kBlock / 64];
+    __shared__ int s_dir[kBlock / 64][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (dparts != nullptr && (nparts <= kDirectPartsAll || blockIdx.x == 0)) {
+        int nd = 0, nr = 0;
+        for (int i = threadIdx.x; i < nparts; i += kBlock) { const int2 v = dparts[i]; nd += v.x; nr += v.y; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { nd += __shfl_xor(nd, o); nr += __shfl_xor(nr, o); }
+        if (lane == 0) { s_dir[wave][0] = nd; s_dir[wave][1] = nr; }
+        __syncthreads();
+        nd = 0; nr = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) { nd += s_dir[w][0]; nr += s_dir[w][1]; }
+        if (blockIdx.x == 0 && threadIdx.x == 0) { ctr->n_direct = nd; ctr->direct_rows = nr; }
+        if (nparts <= kDirectPartsAll && nd == Q) return;
+    }
     const int4* p = (const int4*)cnt + (size_t)threadIdx.x * (kPer / 4);
     int sub[kSub], sum = 0;
 #pragma unroll
@@ -302,12 +334,19 @@ __device__ __forceinline__ void sort4(float (&d)[4]) {
     PCREG_CS(0, 1) PCREG_CS(2, 3) PCREG_CS(0, 2) PCREG_CS(1, 3) PCREG_CS(1, 2)
 #undef PCREG_CS
 }
-__global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __restrict__ q, int Q, int ldq,
-                                                            const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
-                                                            const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
-                                                            int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
-                                                            float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells,
-                                                            float* __restrict__ dk_out, int32_t* __restrict__ qcnt, int32_t* __restrict__ qrank) {
+// The body of S1, for its two callers: seed_query_kernel (kFused = false) and seed_direct_kernel (kFused = true), which goes
+// on to the direct phase in the same group.  After the xor-shuffle merge every lane of a group holds the same d[], so the
+// group's eight lanes all return the query, its seed distance dk and (lane 0) its place in its cell; nothing is read
+// again.  Lane 0 stores gthr and dk_out here; with kFused the caller stores the two words that wait for the direct phase:
+// cand_cnt (once: the mark or 0) and the place, whose atomic is issued first and consumed last.
+struct SeedOut { float qx, qy, qz, dk; int qi, rank; bool live; };
+template <bool kFused>
+__device__ __forceinline__ SeedOut seed_body(const float* __restrict__ q, int Q, int ldq,
+                                             const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
+                                             const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
+                                             int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
+                                             float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells,
+                                             float* __restrict__ dk_out, int32_t* __restrict__ qcnt, int32_t* __restrict__ qrank) {
     // housekeeping for the launches that follow
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < (int)(sizeof(SearchCounters) / 4); i += gridDim.x * kBlock) ((int32_t*)ctr)[i] = 0;
     if (ug_cnt) for (int i = blockIdx.x * kBlock + threadIdx.x; i < ug_cells; i += gridDim.x * kBlock) ug_cnt[i] = 0;
@@ -315,6 +354,7 @@ __global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __re
     const bool live = qi < Q;
     const int qq = live ? qi : 0;
     const float qx = q[qq], qy = q[qq + (size_t)ldq], qz = q[qq + 2 * (size_t)ldq];
+    SeedOut out{qx, qy, qz, INFINITY, qi, 0, live};
     if (ug_part) {                  // box of this workgroup's queries (the query grid's geometry follows from all of them)
         __shared__ float s_box[kBlock / 64][6];
         float v[6] = {live ? qx : INFINITY, live ? qy : INFINITY, live ? qz : INFINITY, live ? qx : -INFINITY, live ? qy : -INFINITY, live ? qz : -INFINITY};
@@ -339,7 +379,7 @@ __global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __re
             cand_cnt[qi] = 0; gthr[qi] = 0xFFFFFFFFu; dk_out[qi] = INFINITY;
             if (qcnt) qrank[qi] = atomicAdd(&qcnt[sort_key(qx, qy, qz, prep) >> 3], 1);
         }
-        return;
+        return out;
     }
     const int nx = prep->nx, ny = prep->ny, nz = prep->nz;
     const int cx = seed_cell(qx, prep->gx0, prep->inv_h, nx), cy = seed_cell(qy, prep->gy0, prep->inv_h, ny), cz = seed_cell(qz, prep->gz0, prep->inv_h, nz);
@@ -363,7 +403,7 @@ __global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __re
     const int key = sort_key(qx, qy, qz, prep) >> 3;
     int rank = 0;
     if (live && sub == 0) {
-        cand_cnt[qi] = 0;                                     // the query's candidate list starts empty
+        if (!kFused) cand_cnt[qi] = 0;                        // the query's candidate list starts empty
         if (qcnt) rank = atomicAdd(&qcnt[key], 1);
     }
     float d[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -394,11 +434,12 @@ __global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __re
         for (int k = 0; k < 4; ++k) d[k] = fminf(d[k], e[3 - k]);
         sort4(d);
     }
-    if (!live || sub != 0) return;
-    unsigned word = 0xFFFFFFFFu;                           // +inf: no hint
     // The k-th smallest exact distance of the sample bounds the true k-th nearest distance from above; any rank >= 2 keeps
     // both true neighbours under the threshold (kSeedRank = 2 since round 3).
     const float dk = d[kSeedRank - 1];
+    out.dk = dk; out.rank = rank;
+    if (!live || sub != 0) return out;
+    unsigned word = 0xFFFFFFFFu;                           // +inf: no hint
     if (dk < INFINITY) {
         const float tx = qx - prep->cx, ty = qy - prep->cy, tz = qz - prep->cz;
         const double r2 = (double)tx * tx + (double)ty * ty + (double)tz * tz;
@@ -409,7 +450,16 @@ __global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __re
     }
     gthr[qi] = word;
     dk_out[qi] = dk;                   // the distance itself: two real model points lie within dk of the query (culling)
-    if (qcnt) qrank[qi] = rank;
+    if (!kFused && qcnt) qrank[qi] = rank;
+    return out;
+}
+__global__ __launch_bounds__(kBlock, 8) void seed_query_kernel(const float* __restrict__ q, int Q, int ldq,
+                                                            const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
+                                                            const float4* __restrict__ slots, int seeded, unsigned* __restrict__ gthr,
+                                                            int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
+                                                            float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells,
+                                                            float* __restrict__ dk_out, int32_t* __restrict__ qcnt, int32_t* __restrict__ qrank) {
+    (void)seed_body<false>(q, Q, ldq, prep, cnt, slots, seeded, gthr, cand_cnt, ctr, ug_part, ug_cnt, ug_cells, dk_out, qcnt, qrank);
 }
 
 // ---- S3. exact re-rank + certificate: one 8-lane group per query --------------------------------------------------
@@ -499,19 +549,21 @@ __device__ __forceinline__ void group_top2_merge(float& d1, float& d2, int& i1, 
 // first row of the range and is masked.  The (start, end) table of a group's cells lives in LDS.
 constexpr int kDirectBatch = 4;
 constexpr int kDirectSlots = (kDirectCells + LPQ - 1) / LPQ;              // cells per lane
-__global__ __launch_bounds__(kBlock) void knn_direct_kernel(
-    const float* __restrict__ q, int Q, int ldq, const float* __restrict__ dk, const Prep* __restrict__ prep,
+// The body of S1d, for its two callers: knn_direct_kernel reads the query qi = blockIdx.x * (kBlock / LPQ) + group and its
+// seed distance D back from memory, seed_direct_kernel (kFused = true) hands them over in registers.  With kFused the
+// query's cand_cnt word is stored here once, the mark or 0; otherwise seed_query_kernel has stored the 0.  A workgroup
+// leaves its (answered, rows) pair in parts[blockIdx.x] with a plain store, whatever the slot held: the sums are formed by
+// the next launch (query_order_ranked_kernel), so no counter of this launch is cleared and added to by different workgroups.
+template <bool kFused>
+__device__ __forceinline__ void direct_body(
+    int qi, bool live, float qx, float qy, float qz, float D, const Prep* __restrict__ prep,
     const int32_t* __restrict__ sort_cnt, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm, int idx_base,
-    int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr) {
+    int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ cand_cnt, int2* __restrict__ parts) {
     constexpr int kGroups = kBlock / LPQ, kTab = LPQ * kDirectSlots;
     __shared__ int s_end[kGroups][kTab], s_off[kGroups][kTab];          // per cell: end in the concatenation, sorted row - position
     __shared__ int s_n[2];
     const int lane = threadIdx.x & (LPQ - 1), grp = threadIdx.x / LPQ;
-    const int qi = blockIdx.x * kGroups + grp;
-    const bool live = qi < Q;
-    const int qq = live ? qi : 0;
     if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
-    const float qx = q[qq], qy = q[qq + (size_t)ldq], qz = q[qq + 2 * (size_t)ldq], D = dk[qq];
     const float qv[3] = {qx, qy, qz}, s0[3] = {prep->sx0, prep->sy0, prep->sz0};
     DirectRange R;
     bool ok = direct_range(qv, D, s0, prep->inv_s, (1 << kSortBits) - 1, &R) && live;
@@ -575,11 +627,35 @@ __global__ __launch_bounds__(kBlock) void knn_direct_kernel(
     if (ok && lane == 0) {
         idx[(size_t)qi * 2] = i1 + idx_base; idx[(size_t)qi * 2 + 1] = i2 + idx_base;
         dist[(size_t)qi * 2] = d1; dist[(size_t)qi * 2 + 1] = d2;
-        cand_cnt[qi] = kDirectMark;
+        if (!kFused) cand_cnt[qi] = kDirectMark;
         atomicAdd(&s_n[0], 1); atomicAdd(&s_n[1], rows);
     }
+    if (kFused && live && lane == 0) cand_cnt[qi] = ok ? kDirectMark : 0;
     __syncthreads();
-    if (threadIdx.x == 0 && s_n[0] > 0) { atomicAdd(&ctr->n_direct, s_n[0]); atomicAdd(&ctr->direct_rows, s_n[1]); }
+    if (threadIdx.x == 0) parts[blockIdx.x] = make_int2(s_n[0], s_n[1]);
+}
+__global__ __launch_bounds__(kBlock) void knn_direct_kernel(
+    const float* __restrict__ q, int Q, int ldq, const float* __restrict__ dk, const Prep* __restrict__ prep,
+    const int32_t* __restrict__ sort_cnt, const float* __restrict__ ms, int M, const int32_t* __restrict__ perm, int idx_base,
+    int32_t* __restrict__ idx, float* __restrict__ dist, int32_t* __restrict__ cand_cnt, int2* __restrict__ parts) {
+    const int qi = blockIdx.x * (kBlock / LPQ) + threadIdx.x / LPQ;
+    const bool live = qi < Q;
+    const int qq = live ? qi : 0;
+    direct_body<false>(qi, live, q[qq], q[qq + (size_t)ldq], q[qq + 2 * (size_t)ldq], dk[qq], prep, sort_cnt, ms, M, perm, idx_base, idx, dist,
+                       cand_cnt, parts);
+}
+// S1 + S1d in ONE launch, for a seeded model: the seed phase and then, in the same group with the query and dk still in
+// registers, the direct phase.  Same geometry as either kernel alone (one 8-lane group per query, grid ceil(8 Q / kBlock));
+// same stores, same bits ("knn_seed_fused" = 1 runs the two launches instead: the A/B of one binary).
+__global__ __launch_bounds__(kBlock, 8) void seed_direct_kernel(
+    const float* __restrict__ q, int Q, int ldq, const Prep* __restrict__ prep, const int32_t* __restrict__ cnt,
+    const float4* __restrict__ slots, unsigned* __restrict__ gthr, int32_t* __restrict__ cand_cnt, SearchCounters* __restrict__ ctr,
+    float* __restrict__ ug_part, int32_t* __restrict__ ug_cnt, int ug_cells, float* __restrict__ dk_out, int32_t* __restrict__ qcnt,
+    int32_t* __restrict__ qrank, const int32_t* __restrict__ sort_cnt, const float* __restrict__ ms, int M,
+    const int32_t* __restrict__ perm, int idx_base, int32_t* __restrict__ idx, float* __restrict__ dist, int2* __restrict__ parts) {
+    const SeedOut s = seed_body<true>(q, Q, ldq, prep, cnt, slots, 1, gthr, cand_cnt, ctr, ug_part, ug_cnt, ug_cells, dk_out, qcnt, qrank);
+    direct_body<true>(s.qi, s.live, s.qx, s.qy, s.qz, s.dk, prep, sort_cnt, ms, M, perm, idx_base, idx, dist, cand_cnt, parts);
+    if (s.live && (threadIdx.x & (LPQ - 1)) == 0 && qcnt) qrank[s.qi] = s.rank;
 }
 
 __global__ __launch_bounds__(kBlock) void knn_finalize_kernel(
@@ -914,7 +990,7 @@ __global__ void knn_stats_kernel(const SearchCounters* __restrict__ ctr, long lo
     atomicAdd(&stats[4], (unsigned long long)(unsigned)ctr->units); atomicAdd(&stats[5], 32ull * (unsigned long long)nv);
 }
 
-// pcreg_debug_set("knn_direct_stats", 1): this search's direct answers added to the process-wide sums (after S1d)
+// pcreg_debug_set("knn_direct_stats", 1): this search's direct answers added to the process-wide sums (after S1b, which publishes them)
 __global__ void knn_direct_stats_kernel(const SearchCounters* __restrict__ ctr, unsigned long long* __restrict__ stats) {
     if (threadIdx.x != 0) return;
     atomicAdd(&stats[0], 1ull); atomicAdd(&stats[1], (unsigned long long)(unsigned)ctr->n_direct);
@@ -1023,22 +1099,34 @@ int launch_model_search(const ModelView& v, const float* q, int Q, int ldq, int3
     const bool grid = with_grid && v.M > 0;          // (an empty model matches nothing: the match stage never looks at the grid)
     const bool order = v.M > 0;                      // (an empty model: no prepared block, no candidate launch)
     if (order) PCREG_HIP(hipMemsetAsync(s.qcnt, 0, (size_t)kQueryKeys * 4, st));
-    hipLaunchKernelGGL(seed_query_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, (const int32_t*)v.seed_cnt,
-                       (const float4*)v.seed_slots, (v.seeded && v.M > 0) ? 1 : 0, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr,
-                       grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr, s.flag_list);
+    // S1d: the seeded queries whose cell range is small are answered and marked; the launches below skip them.  Not with
+    // "knn_direct" = 1 (every query takes the tile walk: the A/B of one binary), and not while "knn_stats" collects: its
+    // counters are defined over the walk of the whole query set.  S1 and S1d are one launch (seed_direct_kernel) unless
+    // "knn_seed_fused" = 1 asks for the two.  The direct phase's per-workgroup (answered, rows) pairs go to the head of
+    // cand_ent, which is dead from here to the candidate kernel (ug_nparts pairs of 8 bytes; a query's list is larger).
+    const bool direct = v.seeded && v.M > 0 && debug_flag(kDbgKnnDirect) == 0 && debug_flag(kDbgKnnStats) == 0;
+    const bool fused = direct && debug_flag(kDbgKnnSeedFused) == 0;
+    int2* dparts = direct ? (int2*)s.cand_ent : nullptr;
+    static_assert((size_t)kF16MaxS * KC * 8 >= sizeof(int2), "the direct phase's pairs fit the head of cand_ent");
     // (a query's place inside its cell waits in flag_list, which is free until knn_finalize_kernel lists the unproven queries)
-    // S1d: the seeded queries whose cell range is small are answered here and marked; the launches below skip them.  Not
-    // with "knn_direct" = 1 (every query takes the tile walk: the A/B of one binary), and not while "knn_stats" collects: its
-    // counters are defined over the walk of the whole query set.
-    if (v.seeded && v.M > 0 && debug_flag(kDbgKnnDirect) == 0 && debug_flag(kDbgKnnStats) == 0)
-        hipLaunchKernelGGL(knn_direct_kernel, dim3((Q + kBlock / LPQ - 1) / (kBlock / LPQ)), dim3(kBlock), 0, st, q, Q, ldq, (const float*)s.dk,
+    if (fused)
+        hipLaunchKernelGGL(seed_direct_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, (const int32_t*)v.seed_cnt,
+                           (const float4*)v.seed_slots, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr, grid ? s.ug_cnt : nullptr, s.ug_cells,
+                           s.dk, s.qcnt, s.flag_list, (const int32_t*)v.sort_cnt, (const float*)v.ms, v.M, (const int32_t*)v.perm, (int)idx_base,
+                           idx, dist, dparts);
+    else
+        hipLaunchKernelGGL(seed_query_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep, (const int32_t*)v.seed_cnt,
+                           (const float4*)v.seed_slots, (v.seeded && v.M > 0) ? 1 : 0, s.gthr, s.cand_cnt, ctr, grid ? s.ug_part : nullptr,
+                           grid ? s.ug_cnt : nullptr, s.ug_cells, s.dk, order ? s.qcnt : nullptr, s.flag_list);
+    if (direct && !fused)
+        hipLaunchKernelGGL(knn_direct_kernel, dim3(s.ug_nparts), dim3(kBlock), 0, st, q, Q, ldq, (const float*)s.dk,
                            (const Prep*)v.prep, (const int32_t*)v.sort_cnt, (const float*)v.ms, v.M, (const int32_t*)v.perm, (int)idx_base, idx, dist,
-                           s.cand_cnt, ctr);
+                           s.cand_cnt, dparts);
+    if (order)             // (also publishes the direct phase's sums in ctr: before the counters below and the plan read them)
+        hipLaunchKernelGGL(query_order_ranked_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep,
+                           (const int32_t*)s.qcnt, (const int32_t*)s.flag_list, s.qperm, (const int2*)dparts, s.ug_nparts, ctr);
     if (unsigned long long* dstats = knn_direct_stats_dev())
         hipLaunchKernelGGL(knn_direct_stats_kernel, dim3(1), dim3(64), 0, st, (const SearchCounters*)ctr, dstats);
-    if (order)
-        hipLaunchKernelGGL(query_order_ranked_kernel, dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q, Q, ldq, (const Prep*)v.prep,
-                           (const int32_t*)s.qcnt, (const int32_t*)s.flag_list, s.qperm);
     int W = 1;
     const int variant = PCREG_EXP_ENV("PCREG_KNN_VARIANT", 40);      // 41: timing-only form of the candidate kernel (EXPERIMENTS builds)
     const int target_env = PCREG_EXP_ENV("PCREG_KNN_BLOCKS", 0);      // (any shape fits: the lists are sized for kF16MaxS workgroups)

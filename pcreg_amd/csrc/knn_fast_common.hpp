@@ -128,8 +128,8 @@ struct SearchCounters {
     int32_t ticket;                  // match_finish_kernel's workgroup tickets
     int32_t finished;                // ... and how many of its workgroups are through (the last one clears ticket / status again)
     int32_t units;                   // (candidate wave, 64-row unit) pairs the visit plan marks for scoring (knn_plan_kernel)
-    int32_t n_direct;                // queries knn_direct_kernel answered from their ordering-grid cells
-    int32_t direct_rows;             // ... and the rows it ranked for them
+    int32_t n_direct;                // queries the direct phase answered from their ordering-grid cells
+    int32_t direct_rows;             // ... and the rows it ranked for them (both published by query_order_ranked_kernel)
     int32_t pad[26];
     int32_t visited[kVisitSlots];    // (query block, model tile) pairs the candidate kernel scored, spread over words by workgroup
     int32_t done[kMaxQTiles];        // tail (many-form): arrivals per tile of listed queries
