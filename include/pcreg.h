@@ -751,6 +751,80 @@ int pcreg_aggregate_matches(const double* pts1, const double* pts2, int n, int l
 int pcreg_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count /* or NULL */,
                               int32_t* label /* or NULL */, int* n_out);
 
+/* The normal-distributions transform: a cloud summarised once as one Gaussian per occupied voxel (the TABLE), and candidate
+ * transforms of a query cloud refined against it by Gauss-Newton steps that need no nearest-row search -- the refinement MATLAB
+ * offers as pcregisterndt, beside pcreg_model_refit_f32 (point to point) and pcreg_model_refit_plane_f32 (point to plane).
+ * It is a STEP, not a registration policy: no convergence test, no line search, no multi-resolution schedule, and no claim of
+ * pcregisterndt's bits.  The step is the Gauss-Newton, iteratively re-weighted form (each pair's Mahalanobis residual weighted
+ * by its current likelihood), so the matrix is a sum of positive semi-definite terms and the point-to-plane solve applies.
+ * THE CONTRACT of every tier (device, host, Python):
+ * THE TABLE is built from (pts: n x 3 fp32 column-major with leading dimension ld >= n; step: a double, finite and > 0;
+ * min_points: an int >= 3, 6 where a default is offered).
+ * THE GRID is pcreg_downsample_grid_f32's, word for word: a row is live when its three coordinates are finite; lo[d] is the fp32
+ * minimum of coordinate d over the live rows; the cell of a live row is c[d] = (int64) floor(((double)x[d] - (double)lo[d]) / step),
+ * IEEE subtraction and division in double; a cloud whose largest cell index along an axis is >= 2^21 is refused (PCREG_E_ARG, no
+ * handle); a voxel is a distinct (c0, c1, c2), and the voxels are taken in ascending lexicographic order, c0 most significant.
+ * A GAUSSIAN, per voxel with count >= min_points, everything in double on the widened fp32 values, the members in ascending
+ * original row order, no contraction:
+ *   1. mean: per coordinate s = 0.0, s = s + x_i in order; mean = s / (double)count (pcreg_downsample_grid_f32's mean before its
+ *      rounding to fp32).
+ *   2. the six central second moments (xx xy xz yy yz zz): m_ab = 0.0; per member d = x_i - mean by component, m_ab = m_ab + d_a * d_b
+ *      (a product, then an addition); cov_ab = m_ab / (double)(count - 1).
+ *   3. eigenvalues l_0, l_1, l_2 and eigenvectors v_k of cov by the library's cyclic Jacobi in its exactly-rounded form (the one
+ *      pcreg_model_fit_cylinders_f32 uses: at most 60 sweeps over (0,1), (0,2), (1,2), the cosine c = 1 / sqrt(t t + 1)).
+ *   4. lmax = the largest l_k.  The voxel is VOID -- it holds no Gaussian -- when some l_k is not finite or lmax is not above 0 (all
+ *      members equal).  Otherwise every l_k below 0.01 * lmax is raised to 0.01 * lmax, which bounds the condition number of C by
+ *      100: a flat or a thin voxel keeps a finite pull along its degenerate axes.
+ *   5. C = sum_k v_k v_k^T / l_k, per entry a <= b: C_ab = ((v_0a * v_0b) / l_0 + (v_1a * v_1b) / l_1) + (v_2a * v_2b) / l_2.
+ * The table holds the Gaussian voxels only, ascending: cell (c0, c1, c2), count, mean[3], C[6] (xx xy xz yy yz zz).  The handle
+ * also keeps lo, step and the ORIGIN o = 0.5f * lo + 0.5f * hi per coordinate in fp32, hi the fp32 maximum of the live rows
+ * (pcreg_model_refit_plane_f32's rule).  n = 0 or no live row: a table without voxels; lo and o are 0.
+ * THE STEP takes q (Q fp32 points column-major, ldq >= Q), B transforms of 16 doubles used as quickTF.m uses them, neighbors (1 or
+ * 7) and outlier_ratio (a double in [0, 1), 0.55 where a default is offered).
+ * THE MOVED POINT p of (transform b, query i) is scoring's TRANSFORMED QUERY (pcreg_model_score_f32: the chain in double, rounded
+ * once to fp32).  The all-zero transform moves nothing: it has no pair.
+ * THE PAIRS of a moved point: cell[d] = floor(((double)p[d] - (double)lo[d]) / step).  The CANDIDATE voxels are that cell
+ * (neighbors = 1), or that cell followed by its six face neighbours in the order -x, +x, -y, +y, -z, +z (neighbors = 7).  A
+ * candidate with a cell coordinate outside [0, 2^21) -- a non-finite coordinate of p leaves every candidate there -- is skipped,
+ * and so is one that is not a Gaussian of the table.  Every remaining (point, voxel) is a PAIR; n_pairs[b] their number.
+ * PER PAIR, in double, no contraction except where fma is written; p widened, o the origin, (mean, C) the voxel's;
+ * cross(a, b) = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x), every component fl(fl(..) - fl(..)):
+ *   x = p - mean;  u = p - o;  y = C x, y_a = (C_a0 x_0 + C_a1 x_1) + C_a2 x_2;  qq = (x_0 y_0 + x_1 y_1) + x_2 y_2;
+ *   e = exp(-((d2 / 2) * qq)), the device's double exp;
+ *   the Jacobian of p under a small rotation w about o and a translation t is J = (c_0, c_1, c_2, I), c_i = e_i x u, so that
+ *   J_i . v = cross(u, v)_i for i < 3 and v_(i-3) for i >= 3:
+ *   W_a = cross(u, row a of C), a = 0, 1, 2;   M_j = cross(u, (W_0[j], W_1[j], W_2[j])), j = 0, 1, 2;   gy = cross(u, y);
+ *   a_ij = J_i^T C J_j:  M_j[i] for i <= j < 3;  W_(j-3)[i] for i < 3 <= j;  C_(i-3)(j-3) for 3 <= i <= j;
+ *   h_i = J_i . y:  gy[i] for i < 3;  y_(i-3) for i >= 3.
+ * THE 28 SUMS over the pairs in ascending (query, candidate) order:
+ *   [0..20] A_ij = fma(e, a_ij, A_ij), i <= j, the upper triangle row-major;  [21..26] g_i = fma(e, h_i, g_i);  [27] sum_e = sum_e + e.
+ * Their order is pcreg_model_refit_plane_f32's: a thread adds its 8 consecutive queries in order, the wave's butterfly follows,
+ * the four waves of a chunk of 2048 queries in ascending order, the chunks in ascending order from 0.  No floating-point atomic.
+ * d2, once per call on the host in double with res = step:  c1 = 10 (1 - outlier_ratio);  c2 = outlier_ratio / ((res res) res);
+ *   d3 = -log(c2);  d1 = -log(c1 + c2) - d3;  d2 = -2 log((-log(c1 exp(-0.5) + c2) - d3) / d1).  outlier_ratio = 0 means d2 = 1: an
+ *   unweighted Mahalanobis fit apart from the factor e.
+ * THE FIT is pcreg_model_refit_plane_f32's, unchanged, on these 28 sums with n_pairs in n_plane's place (its 28th sum is reported,
+ * not used): A x = -g by the scaled Cholesky, the Cayley rotation, T_step about o, T_out = T * T_step.  EMPTY by its rules:
+ * empty[b] = 1 and 32 zeros for the all-zero T[b], n_pairs < 6, an A_ii not a finite number above 0, a pivot not above 2^-26, a
+ * non-finite x or T_step.  n_pairs and sum_e are reported either way.  Q = 0 or a table without Gaussians: every transform is
+ * empty, n_pairs 0 and sum_e 0.0.  B = 0: nothing is written.
+ * Everything is a function of the inputs only: no floating-point atomic; the order in which workgroups run, the stream and the
+ * workspace's previous contents change no bit (the step has no batching).
+ * pcreg_ndt_create uploads the cloud, builds the table on the device and keeps only the table.  pcreg_ndt_size: the occupied voxels
+ * and the Gaussians among them.  pcreg_ndt_get copies out, each pointer or NULL: cells [G][3] int32, counts [G], means [G][3],
+ * C [G][6] row-major per Gaussian, lo [3], origin [3].  pcreg_ndt_refit_f32 runs `steps` >= 1 steps on the device with one upload
+ * and one read, each step's T_out the next one's T; n_pairs, sum_e and empty describe the transform that went INTO the last step.
+ * PCREG_E_ARG: n < 0, ld < n, pts NULL with n > 0, step not finite or <= 0, min_points < 3, a refused cloud; for the step Q < 0 or
+ * above 4 Mi, B < 0, ldq < Q, neighbors not 1 or 7, outlier_ratio outside [0, 1) or NaN, steps < 1, a NULL handle, a NULL q with
+ * Q > 0, a NULL T or output with B > 0. */
+typedef struct pcreg_ndt pcreg_ndt;
+int pcreg_ndt_create(const float* pts, int n, int ld, double step, int min_points, pcreg_ndt** ndt);
+int pcreg_ndt_destroy(pcreg_ndt* ndt);
+int pcreg_ndt_size(const pcreg_ndt* ndt, int* n_voxels, int* n_gaussians);
+int pcreg_ndt_get(const pcreg_ndt* ndt, int32_t* cells, int32_t* counts, double* means, double* C, float* lo, float* origin);
+int pcreg_ndt_refit_f32(pcreg_ndt* ndt, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, int neighbors,
+                        double outlier_ratio, int steps, double* T_out /* [B][16] */, int32_t* n_pairs, double* sum_e, int32_t* empty);
+
 /* getLocalPoints.m:8-35  [pts_sphere, dists] = getLocalPoints(pts, R, c, min_points, max_points): the points of the cloud strictly
  * inside the open box AND the open ball of radius R around c, RELATIVE to c, in the cloud's order; [] when the box holds fewer
  * than min_points (:17) or the ball fewer than min_points / more than max_points (:31).  pts: N x 3 column-major (ld >= N).
@@ -1439,6 +1513,29 @@ size_t pcreg_dev_downsample_grid_workspace(int n);
 int pcreg_dev_downsample_grid_chunk(void);
 int pcreg_dev_downsample_grid_f32(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label,
                                   int32_t* n_out, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_ndt's contract on the device.  pcreg_dev_ndt_create: pts is a device pointer; the table is built on `stream`
+ * by pcreg_dev_downsample_grid_f32's chain up to the voxel order, one thread per voxel for the Gaussians and a chunk scan that
+ * compacts them; it is a one-off and synchronises the stream twice (the voxel count sizes the scratch, the Gaussian count is kept).
+ * The handle owns its table and does not keep pts.  pcreg_dev_ndt_size / pcreg_dev_ndt_get are pcreg_ndt_size / pcreg_ndt_get (the
+ * outputs are HOST pointers; get synchronises the device).
+ * pcreg_dev_ndt_refit_f32 is ONE step: q, T_dev [B][16], T_out [B][16], T_step [B][16] (or NULL: not wanted), n_pairs, sum_e and
+ * empty [B] are device pointers; T_out may not alias T_dev.  Nothing synchronises, nothing is read on the host, no workgroup
+ * waits for another: one launch of a workgroup per (transform, chunk of 2048 queries) -- a thread moves its 8 consecutive queries,
+ * finds their candidate voxels by a branch-free binary search of the table's sorted keys and adds the pairs' 28 sums -- and one of
+ * a wave per transform for the fit.  There is no batching.  Workspace, with P = B * max(ceil(Q / 2048), 1):
+ *   roundup(224 P, 256) + roundup(4 P, 256) bytes;
+ * a shorter one is PCREG_E_ARG, and so is a NULL one unless that is 0 bytes.  A handle may serve several streams at once, each
+ * call with its own workspace.  pcreg_dev_ndt_refit_workspace returns 0 for arguments the step refuses. */
+typedef struct pcreg_dev_ndt pcreg_dev_ndt;
+int pcreg_dev_ndt_create(const float* pts, int n, int ld, double step, int min_points, void* stream, pcreg_dev_ndt** ndt);
+int pcreg_dev_ndt_destroy(pcreg_dev_ndt* ndt);
+int pcreg_dev_ndt_size(const pcreg_dev_ndt* ndt, int* n_voxels, int* n_gaussians);
+int pcreg_dev_ndt_get(const pcreg_dev_ndt* ndt, int32_t* cells, int32_t* counts, double* means, double* C, float* lo, float* origin);
+size_t pcreg_dev_ndt_refit_workspace(int Q, int B);
+int pcreg_dev_ndt_refit_f32(const pcreg_dev_ndt* ndt, const float* q, int Q, int ldq, const double* T_dev /* [B][16] on the device */,
+                            int B, int neighbors, double outlier_ratio, double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                            int32_t* n_pairs /* [B] */, double* sum_e /* [B] */, int32_t* empty /* [B] */, void* workspace,
+                            size_t workspace_bytes, void* stream);
 /* T = estimateTransform(pts1(idx, :), pts2(idx, :)) with the index list on the device (completeExperiment.m:458 on ransac's
  * inlier_idx): rows idx[0 .. *n_idx_dev) (idx_base-based; the count is clamped into [0, cap], every index into the cap rows) of
  * pts1 / pts2 (cap x 3 column-major, leading dimension ld >= cap).  The arithmetic of pcreg_dev_refine_by_distance with every

@@ -130,6 +130,15 @@
 //                                          (c1, c2, c3) order; counts the rows of every voxel, labels the 1-based output row of
 //                                          every input row, 0 for a row with a NaN or Inf; the last two are built only when asked
 //                                          for; the input keeps its class, a double cloud is refused (matlab/pcdownsampleFast.m)
+//   'ndtCreate', pts (single n x 3), step, minPoints        -> handle (uint64), nVoxels, nGaussians: the cloud summarised ONCE as one
+//                                          Gaussian per voxel of gridStep `step` with at least minPoints (>= 3) rows -- the table NDT
+//                                          steps refine against (pcreg_ndt_create; matlab/ndtModel.m) | 'ndtDestroy', handle
+//   'ndtRefit', handle, pts (single Q x 3), T (double 4 x 4 x B), neighbors (1 | 7), outlierRatio (in [0, 1)), steps -> Tout (double
+//                                          4 x 4 x B), nPairs (B x 1 int32), sumE (B x 1 double): B transforms refined by `steps`
+//                                          Gauss-Newton NDT steps -- each moved point against the Gaussian of its voxel (and of its
+//                                          six face neighbours), no nearest-row search; a zero page where there is no fit; the
+//                                          counts and sums are those of the transform that went into the last step.  A step, not
+//                                          pcregisterndt's policy (matlab/refitNdtModel.m, matlab/refitNdtFast.m)
 //   'descCreate', desc (double n x D) -> handle (uint64) | 'getMatchesOnSet', hSurface, hModel, int32 rows | [], par -> matches
 //                                          | 'descDestroy', handle        (one surface set, many row subsets of one model set)
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
@@ -205,6 +214,10 @@ static int cluster_on_handle(pcreg_model* h, float r, mxArray* out[3]) {
 static bool normals_k_ok(const mxArray* a) {
     return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 3.0 && mxGetScalar(a) <= (double)PCREG_KNN_MAX_K &&
            mxGetScalar(a) == (double)(int)mxGetScalar(a);
+}
+// a real double scalar that is a whole number in [lo, hi] (NaN refused)
+static bool whole_scalar_ok(const mxArray* a, double lo, double hi) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= lo && mxGetScalar(a) <= hi && mxGetScalar(a) == (double)(int)mxGetScalar(a);
 }
 static bool viewpoint_ok(const mxArray* a) { return mxIsEmpty(a) || (mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 3); }
 // the outputs of 'modelNormals' / 'pointNormals': normals (M x 3 single) and, with want_var, variation (M x 1 single).  Nothing is
@@ -1069,6 +1082,50 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(op); mxDestroyArray(og); }
             }
         }
+    } else if (!strcmp(cmd, "ndtCreate")) {                   // [h, nVoxels, nGaussians] = pcreg_mex('ndtCreate', single(pts), step, minPoints)
+        if (nrhs != 4 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !whole_scalar_ok(prhs[3], 3.0, 1e9) || !mxIsDouble(prhs[2]) ||
+            mxGetM(prhs[2]) * mxGetN(prhs[2]) != 1 || !(mxGetScalar(prhs[2]) > 0.0) || !std::isfinite(mxGetScalar(prhs[2])))
+            usage = "ndtCreate: pts (single n x 3), step (a finite double scalar > 0), minPoints (a whole number >= 3)";
+        else {
+            const int n = (int)mxGetM(prhs[1]);
+            pcreg_ndt* h = nullptr;
+            int nv = 0, ng = 0;
+            rc = pcreg_ndt_create((const float*)mxGetData(prhs[1]), n, n > 0 ? n : 1, mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), &h);
+            if (rc == PCREG_OK) rc = pcreg_ndt_size(h, &nv, &ng);
+            if (rc == PCREG_OK) {
+                plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL); *(uint64_t*)mxGetData(plhs[0]) = (uint64_t)(uintptr_t)h;
+                if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)nv);
+                if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)ng);
+            } else if (h) (void)pcreg_ndt_destroy(h);
+        }
+    } else if (!strcmp(cmd, "ndtRefit")) {                    // [Tout, nPairs, sumE] = pcreg_mex('ndtRefit', h, single(pts), T, neighbors, outlierRatio, steps)
+        if (nrhs != 7 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !whole_scalar_ok(prhs[4], 1.0, 7.0) ||
+            (mxGetScalar(prhs[4]) != 1.0 && mxGetScalar(prhs[4]) != 7.0) || !mxIsDouble(prhs[5]) || mxGetM(prhs[5]) * mxGetN(prhs[5]) != 1 ||
+            !(mxGetScalar(prhs[5]) >= 0.0) || !(mxGetScalar(prhs[5]) < 1.0) || !whole_scalar_ok(prhs[6], 1.0, 1e6))
+            usage = "ndtRefit: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), neighbors (1 or 7), outlierRatio (a double scalar in [0, 1)), "
+                    "steps (a whole number >= 1)";
+        else {
+            pcreg_ndt* h = (pcreg_ndt*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const mwSize dims[3] = {4, 4, (mwSize)B};
+            mxArray* ot = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+            mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+            mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+            rc = pcreg_ndt_refit_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, (int)mxGetScalar(prhs[4]),
+                                     mxGetScalar(prhs[5]), (int)mxGetScalar(prhs[6]), mxGetPr(ot), (int32_t*)mxGetData(on), mxGetPr(os),
+                                     (int32_t*)mxGetData(oe));
+            mxDestroyArray(oe);
+            if (rc == PCREG_OK) {
+                plhs[0] = ot;
+                if (nlhs > 1) plhs[1] = on; else mxDestroyArray(on);
+                if (nlhs > 2) plhs[2] = os; else mxDestroyArray(os);
+            } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); }
+        }
+    } else if (!strcmp(cmd, "ndtDestroy")) {
+        if (nrhs != 2 || !mxIsUint64(prhs[1])) usage = "ndtDestroy: handle (uint64)";
+        else rc = pcreg_ndt_destroy((pcreg_ndt*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]));
     } else if (!strcmp(cmd, "modelCluster")) {                // [label, clOff, members] = pcreg_mex('modelCluster', h, r): clusterPoints(model, r)
         if (nrhs != 3 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2])) usage = "modelCluster: handle (uint64), r (a real scalar >= 0)";
         else {

@@ -76,6 +76,8 @@ SYMBOLS = [
     "pcreg_unique_rows3", "pcreg_aggregate_matches", "pcreg_dev_unique_rows3_workspace", "pcreg_dev_unique_rows3_f64",
     "pcreg_dev_aggregate_matches_workspace", "pcreg_dev_aggregate_matches", "pcreg_dev_estimate_transform_indexed",
     "pcreg_downsample_grid_f32", "pcreg_dev_downsample_grid_workspace", "pcreg_dev_downsample_grid_chunk", "pcreg_dev_downsample_grid_f32",
+    "pcreg_ndt_create", "pcreg_ndt_destroy", "pcreg_ndt_size", "pcreg_ndt_get", "pcreg_ndt_refit_f32",
+    "pcreg_dev_ndt_create", "pcreg_dev_ndt_destroy", "pcreg_dev_ndt_size", "pcreg_dev_ndt_get", "pcreg_dev_ndt_refit_workspace", "pcreg_dev_ndt_refit_f32",
     "pcreg_dev_model_match_f32", "pcreg_dev_model_match_table_f32", "pcreg_dev_match_from_table_f32",
     "pcreg_align_points_knn", "pcreg_align_points_knn_f32", "pcreg_align_points_knn_batched", "pcreg_spatial_histogram_descriptors",
     "pcreg_spatial_histogram_descriptors_f32", "pcreg_spatial_histogram_descriptors_mixed",
@@ -225,6 +227,20 @@ def lib() -> C.CDLL:
             vp, i, d = C.c_void_p, C.c_int, C.c_double                           # (a double by value: declared)
             L.pcreg_dev_downsample_grid_f32.argtypes = [vp, i, i, d, vp, i, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_downsample_grid_f32.argtypes = [vp, i, i, d, vp, i, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_ndt_refit_workspace"):     # (an older build given through PCREG_LIB lacks the NDT)
+            L.pcreg_dev_ndt_refit_workspace.restype = C.c_size_t
+            L.pcreg_dev_ndt_refit_workspace.argtypes = [C.c_int, C.c_int]
+            vp, i, d = C.c_void_p, C.c_int, C.c_double
+            L.pcreg_dev_ndt_create.argtypes = [vp, i, i, d, i, vp, vp]
+            L.pcreg_ndt_create.argtypes = [vp, i, i, d, i, vp]
+            for name in ("pcreg_dev_ndt_destroy", "pcreg_ndt_destroy"):
+                getattr(L, name).argtypes = [vp]
+            for name in ("pcreg_dev_ndt_size", "pcreg_ndt_size"):
+                getattr(L, name).argtypes = [vp, vp, vp]
+            for name in ("pcreg_dev_ndt_get", "pcreg_ndt_get"):
+                getattr(L, name).argtypes = [vp] * 7
+            L.pcreg_dev_ndt_refit_f32.argtypes = [vp, vp, i, i, vp, i, i, d, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_ndt_refit_f32.argtypes = [vp, vp, i, i, vp, i, i, d, i, vp, vp, vp, vp]
         for name, args in (("pcreg_debug_knn_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_knn_unit_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_knn_direct_stats", [C.POINTER(C.c_longlong), C.c_int]),

@@ -1390,6 +1390,83 @@ class Model:
             pass
 
 
+class NdtModel:
+    """A cloud summarised ONCE as one Gaussian per occupied voxel (pcreg_ndt_create, whose contract this is): the table that
+    NDT steps refine candidate transforms against, without a nearest-row search.  points: n x 3 float32; step: the voxel size;
+    min_points: the rows a voxel needs to hold a Gaussian.  A step, not a registration policy: no convergence test, no line
+    search, no multi-resolution schedule.  Use as a context manager or call close()."""
+
+    def __init__(self, points, step: float, min_points: int = 6):
+        step, min_points = float(step), int(min_points)
+        if not (math.isfinite(step) and step > 0.0):
+            raise ValueError(f"step must be a finite number > 0, got {step}")
+        if min_points < 3:
+            raise ValueError(f"min_points must be at least 3, got {min_points}")
+        p = _fcol(points, np.float32)
+        if p.shape[1] != 3:
+            raise ValueError("points must be N x 3")
+        n = p.shape[0]
+        self.step, self.min_points = step, min_points
+        self._h = C.c_void_p()
+        check(lib().pcreg_ndt_create(p.ctypes.data if n else None, n, max(n, 1), step, min_points, C.byref(self._h)))
+        nv, ng = C.c_int(), C.c_int()
+        check(lib().pcreg_ndt_size(self._h, C.byref(nv), C.byref(ng)))
+        self.n_voxels, self.n_gaussians = nv.value, ng.value
+
+    def gaussians(self) -> dict:
+        """-> cells [G, 3] int32, counts [G] int32, means [G, 3] float64, C [G, 6] float64 (xx xy xz yy yz zz of the floored inverse
+        covariance), lo [3] and origin [3] float32; the Gaussians ascend by cell"""
+        if not self._h.value:
+            raise ValueError("the NDT handle is closed")
+        G = self.n_gaussians
+        cells, counts = np.zeros((G, 3), np.int32), np.zeros(G, np.int32)
+        means, Cm = np.zeros((G, 3), np.float64), np.zeros((G, 6), np.float64)
+        lo, origin = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(lib().pcreg_ndt_get(self._h, cells.ctypes.data, counts.ctypes.data, means.ctypes.data, Cm.ctypes.data, lo.ctypes.data, origin.ctypes.data))
+        return dict(cells=cells, counts=counts, means=means, C=Cm, lo=lo, origin=origin)
+
+    def refit(self, query, T, neighbors: int = 1, outlier_ratio: float = 0.55, steps: int = 1) -> dict:
+        """B transforms refined by `steps` NDT steps (pcreg_ndt_refit_f32): -> T [B, 4, 4] as quickTF uses them, empty [B] bool,
+        n_pairs [B] int32 and sum_e [B] float64 (the pairs and the sum of their likelihood weights) for the transform that went
+        INTO the last step"""
+        if not self._h.value:
+            raise ValueError("the NDT handle is closed")
+        neighbors, outlier_ratio, steps = int(neighbors), float(outlier_ratio), int(steps)
+        if neighbors not in (1, 7):
+            raise ValueError(f"neighbors must be 1 or 7, got {neighbors}")
+        if not 0.0 <= outlier_ratio < 1.0:
+            raise ValueError(f"outlier_ratio must lie in [0, 1), got {outlier_ratio}")
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        out = np.zeros((max(B, 1), 16), dtype=np.float64)
+        n_pairs, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(2))
+        sum_e = np.zeros(max(B, 1), dtype=np.float64)
+        check(lib().pcreg_ndt_refit_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, neighbors,
+                                        outlier_ratio, steps, out.ctypes.data, n_pairs.ctypes.data, sum_e.ctypes.data, empty.ctypes.data))
+        return dict(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, n_pairs=n_pairs[:B], sum_e=sum_e[:B])
+
+    def close(self):
+        if self._h.value:
+            lib().pcreg_ndt_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def match_points(query, model, thr_abs: float, max_ratio: float, unique: bool = True) -> np.ndarray:
     """matchFeatures' filter chain on raw 3-D fp32 points -> P x 2 uint32 (1-based)."""
     q, m = _fcol(query, np.float32), _fcol(model, np.float32)

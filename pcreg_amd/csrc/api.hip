@@ -2493,6 +2493,138 @@ int pcreg_dev_downsample_grid_f32(const float* pts, int n, int ld, double step, 
     GUARD();
     return launch_downsample_grid(pts, n, ld, step, out, ldo, count, label, n_out, info, workspace, workspace_bytes, (hipStream_t)stream);
 }
+// ---- the normal-distributions transform (ndt.hip) ---------------------------------------------------------------
+}  // extern "C" (the handle types are C++ structs behind opaque C names)
+struct pcreg_dev_ndt { pcreg::NdtView v; };
+struct pcreg_ndt { pcreg_dev_ndt* d; };
+extern "C" {
+
+static int dev_ndt_create(const float* pts, int n, int ld, double step, int min_points, hipStream_t st, pcreg_dev_ndt** out) {
+    *out = nullptr;
+    NdtView v{};
+    TRY(ndt_build(pts, n, ld, step, min_points, st, &v));
+    *out = new pcreg_dev_ndt{v};
+    return PCREG_OK;
+}
+// the table's Gaussians copied out (host pointers, each or NULL); the device is idle behind it
+static int dev_ndt_get(const pcreg_dev_ndt* h, int32_t* cells, int32_t* counts, double* means, double* C, float* lo, float* origin) {
+    const NdtView& v = h->v;
+    for (int c = 0; c < 3; ++c) { if (lo) lo[c] = v.lo[c]; if (origin) origin[c] = v.o[c]; }
+    if (v.G == 0 || !(cells || counts || means || C)) return PCREG_OK;
+    std::vector<NdtRec> rec((size_t)v.G);
+    PCREG_HIP(hipMemcpy(rec.data(), v.rec, sizeof(NdtRec) * (size_t)v.G, hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < (size_t)v.G; ++g) {
+        const NdtRec& r = rec[g];
+        if (cells) { cells[3 * g] = (int32_t)(r.key >> 42); cells[3 * g + 1] = (int32_t)((r.key >> 21) & 0x1FFFFF); cells[3 * g + 2] = (int32_t)(r.key & 0x1FFFFF); }
+        if (counts) counts[g] = r.count;
+        if (means) for (int c = 0; c < 3; ++c) means[3 * g + c] = r.mean[c];
+        if (C) for (int c = 0; c < 6; ++c) C[6 * g + c] = r.C[c];
+    }
+    return PCREG_OK;
+}
+
+int pcreg_dev_ndt_create(const float* pts, int n, int ld, double step, int min_points, void* stream, pcreg_dev_ndt** ndt) {
+    PCREG_ARG(ndt != nullptr && n >= 0 && ld >= n && (n == 0 || pts != nullptr) && std::isfinite(step) && step > 0.0 && min_points >= 3);
+    GUARD();
+    return dev_ndt_create(pts, n, ld, step, min_points, (hipStream_t)stream, ndt);
+}
+int pcreg_dev_ndt_destroy(pcreg_dev_ndt* ndt) {
+    if (!ndt) return PCREG_OK;
+    std::lock_guard<std::mutex> lock(g_mu);
+    (void)hipDeviceSynchronize();                 // steps that still read the table
+    (void)hipFree(ndt->v.block);
+    delete ndt;
+    return PCREG_OK;
+}
+int pcreg_dev_ndt_size(const pcreg_dev_ndt* ndt, int* n_voxels, int* n_gaussians) {
+    PCREG_ARG(ndt && n_voxels && n_gaussians);
+    *n_voxels = ndt->v.n_vox;
+    *n_gaussians = ndt->v.G;
+    return PCREG_OK;
+}
+int pcreg_dev_ndt_get(const pcreg_dev_ndt* ndt, int32_t* cells, int32_t* counts, double* means, double* C, float* lo, float* origin) {
+    PCREG_ARG(ndt != nullptr);
+    GUARD();
+    return dev_ndt_get(ndt, cells, counts, means, C, lo, origin);
+}
+size_t pcreg_dev_ndt_refit_workspace(int Q, int B) { return ndt_refit_ws_bytes(Q, B); }
+int pcreg_dev_ndt_refit_f32(const pcreg_dev_ndt* ndt, const float* q, int Q, int ldq, const double* T_dev, int B, int neighbors, double outlier_ratio,
+                            double* T_out, double* T_step, int32_t* n_pairs, double* sum_e, int32_t* empty, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    PCREG_ARG(ndt != nullptr);
+    GUARD();
+    return launch_ndt_refit(ndt->v, q, Q, ldq, T_dev, B, neighbors, outlier_ratio, T_out, T_step, n_pairs, sum_e, empty, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
+// the host tier: the cloud is uploaded for the build and freed behind it; the handle keeps the table
+int pcreg_ndt_create(const float* pts, int n, int ld, double step, int min_points, pcreg_ndt** ndt) {
+    PCREG_ARG(ndt != nullptr && n >= 0 && ld >= n && (n == 0 || pts != nullptr) && std::isfinite(step) && step > 0.0 && min_points >= 3);
+    GUARD();
+    *ndt = nullptr;
+    float* dp = nullptr;
+    PCREG_HIP(hipMalloc((void**)&dp, sizeof(float) * 3 * (size_t)(n > 0 ? n : 1)));
+    int rc = upload_cols(pts, n, ld, 3, dp, g_stream);
+    pcreg_dev_ndt* d = nullptr;
+    if (!rc) rc = dev_ndt_create(dp, n, n > 0 ? n : 1, step, min_points, g_stream, &d);       // (synchronises the stream)
+    (void)hipFree(dp);
+    if (rc) return rc;
+    *ndt = new pcreg_ndt{d};
+    return PCREG_OK;
+}
+int pcreg_ndt_destroy(pcreg_ndt* ndt) {
+    if (!ndt) return PCREG_OK;
+    const int rc = pcreg_dev_ndt_destroy(ndt->d);
+    delete ndt;
+    return rc;
+}
+int pcreg_ndt_size(const pcreg_ndt* ndt, int* n_voxels, int* n_gaussians) {
+    PCREG_ARG(ndt != nullptr);
+    return pcreg_dev_ndt_size(ndt->d, n_voxels, n_gaussians);
+}
+int pcreg_ndt_get(const pcreg_ndt* ndt, int32_t* cells, int32_t* counts, double* means, double* C, float* lo, float* origin) {
+    PCREG_ARG(ndt != nullptr);
+    GUARD();
+    return dev_ndt_get(ndt->d, cells, counts, means, C, lo, origin);
+}
+// B transforms stepped `steps` times: pcreg_model_refit_plane_f32's staging -- one upload, two result blocks that take turns, ONE
+// block read back: the last step's [T_out 16 B doubles][sum_e B][n_pairs B int32][empty B int32]
+int pcreg_ndt_refit_f32(pcreg_ndt* ndt, const float* q, int Q, int ldq, const double* T, int B, int neighbors, double outlier_ratio, int steps,
+                        double* T_out, int32_t* n_pairs, double* sum_e, int32_t* empty) {
+    double d2;
+    PCREG_ARG(ndt && Q >= 0 && B >= 0 && ldq >= Q && Q <= ndt_max_queries() && steps >= 1 && (neighbors == 1 || neighbors == 7));
+    PCREG_ARG(ndt_d2(ndt->d->v.step, outlier_ratio, &d2));
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_pairs && sum_e && empty)));
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const size_t wsb = ndt_refit_ws_bytes(Q, B), nB = (size_t)B;
+    float* dq; double *dT, *dout; char* ws;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * nB, &dT));
+    TRY(st.take(2 * 18 * nB, &dout));                                      // two result blocks of 18 B doubles' room (17 B and 2 B int32)
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    const double* in = dT;
+    double* blk = dout;
+    for (int s = 0; s < steps; ++s) {
+        blk = dout + (size_t)(s & 1) * 18 * nB;
+        int32_t* ib = (int32_t*)(blk + 17 * nB);
+        TRY(launch_ndt_refit(ndt->d->v, dq, Q, Q, in, B, neighbors, outlier_ratio, blk, nullptr, ib, blk + 16 * nB, ib + nB, ws, wsb, g_stream));
+        in = blk;
+    }
+    std::vector<double> host(18 * nB);
+    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 18 * nB, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const int32_t* hi = (const int32_t*)(host.data() + 17 * nB);
+    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
+    memcpy(sum_e, host.data() + 16 * nB, sizeof(double) * nB);
+    memcpy(n_pairs, hi, sizeof(int32_t) * nB);
+    memcpy(empty, hi + nB, sizeof(int32_t) * nB);
+    return PCREG_OK;
+}
+
 size_t pcreg_dev_aggregate_matches_workspace(int n_cap) { return aggregate_matches_ws_bytes(n_cap); }
 int pcreg_dev_aggregate_matches(const double* pts1, const double* pts2, const int32_t* n_dev, int n_cap, int ld, double* out1, double* out2,
                                 int ldo, int32_t idx_base, int32_t* ia, int32_t* n_out, void* workspace, size_t workspace_bytes, void* stream) {

@@ -333,6 +333,31 @@ size_t downsample_grid_ws_bytes(int n);
 int downsample_grid_chunk();                        // records per workgroup of the sort (the tests' T)
 int launch_downsample_grid(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int32_t* n_out,
                            int32_t* info, void* ws, size_t ws_bytes, hipStream_t st);
+// ... its chain up to the voxel order (D1 .. D6), for another consumer of the order (ndt.hip): the header the device derives, the
+// two buffers of rows of which hdr->passes & 1 picks the sorted one (live rows first, by voxel, ascending row inside a voxel) and
+// the first record of every voxel; *n_out voxels.  The workspace is launch_downsample_grid's
+struct VoxelHdr {
+    float lo[3], hi[3];
+    int32_t w[3];                                    // bits of the largest cell index per axis
+    int32_t used;                                    // key bits the sort orders by: w0 + w1 + w2 (+ 1 with a dead row)
+    int32_t passes;                                  // ceil(used / 8)
+    int32_t info;                                    // 1: refused
+    int32_t n_live;
+};
+struct VoxelOrder { const VoxelHdr* hdr; const uint32_t* row[2]; const int32_t* vstart; };
+int launch_voxel_order(const float* pts, int n, int ld, double step, int32_t* n_out, int32_t* info, void* ws, size_t ws_bytes, hipStream_t st,
+                       VoxelOrder* order);
+// The normal-distributions transform (ndt.hip, ndt_gauss.hpp).  A table: the Gaussian voxels of a cloud ascending by
+// key = c0 << 42 | c1 << 21 | c2, one 128-byte record each and the keys once more on their own (what a lookup searches); lo, the
+// origin o = 0.5f lo + 0.5f hi and the step of the grid.  ndt_build reads back twice; launch_ndt_refit is one asynchronous step.
+struct NdtRec { unsigned long long key; int32_t count; int32_t pad; double mean[3]; double C[6]; double fill[5]; };
+struct NdtView { const unsigned long long* keys; const NdtRec* rec; int G, n_vox, min_points; double step; float lo[3], o[3]; void* block; };
+int ndt_build(const float* pts, int n, int ld, double step, int min_points, hipStream_t st, NdtView* view);
+int ndt_max_queries();
+bool ndt_d2(double step, double outlier_ratio, double* d2);      // false: outlier_ratio outside [0, 1)
+size_t ndt_refit_ws_bytes(int Q, int B);
+int launch_ndt_refit(const NdtView& v, const float* q, int Q, int ldq, const double* T_dev, int B, int neighbors, double outlier_ratio, double* T_out,
+                     double* T_step, int32_t* n_pairs, double* sum_e, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
 // the match stage on a finished search (knn_points.hip): threshold + ratio + Unique (query grid of the search's workspace)
 // + ordered compaction in ONE launch; the two halves around the multi-GPU table exchange
 int launch_match_finish(const ModelView& v, const float* q, int Q, int ldq, const int32_t* idx, const float* dist, float thr,

@@ -48,14 +48,7 @@ constexpr int kDsPasses = 8;                         // 8-bit digits of a 64-bit
 constexpr double kDsMaxCells = 2097152.0;            // 2^21: a cell index at or above it refuses the cloud
 static_assert(kDsT == kScanChunk && kDsBlock == kScanBlock, "D5 / D6 are the chunk scan of chunk_scan.hpp");
 
-struct DsHdr {
-    float lo[3], hi[3];
-    int32_t w[3];                                    // bits of the largest cell index per axis
-    int32_t used;                                    // key bits the sort orders by: w0 + w1 + w2 (+ 1 with a dead row)
-    int32_t passes;                                  // ceil(used / 8)
-    int32_t info;                                    // 1: refused
-    int32_t n_live;
-};
+typedef VoxelHdr DsHdr;                             // (common.hpp: the NDT table's chain reads it too)
 
 __device__ __forceinline__ bool ds_live(float x, float y, float z) {
     return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;       // (false for NaN)
@@ -397,10 +390,11 @@ size_t downsample_grid_ws_bytes(int n) {
 }
 int downsample_grid_chunk() { return kDsT; }
 
-int launch_downsample_grid(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int32_t* n_out,
-                           int32_t* info, void* ws, size_t ws_bytes, hipStream_t st) {
-    PCREG_ARG(n >= 0 && n <= 0x7FFFFFFF - kDsT && ld >= n && ldo >= n && std::isfinite(step) && step > 0.0 && n_out && info &&
-              (n == 0 || (pts && out)));
+// D1 .. D6: the chain up to the first record of every voxel.  *order (may be null) names what D7 -- or another consumer of the voxel
+// order (ndt.hip) -- reads: the header, the two row buffers of which the header's passes & 1 picks the sorted one, vstart
+int launch_voxel_order(const float* pts, int n, int ld, double step, int32_t* n_out, int32_t* info, void* ws, size_t ws_bytes, hipStream_t st,
+                       VoxelOrder* order) {
+    PCREG_ARG(n >= 0 && n <= 0x7FFFFFFF - kDsT && ld >= n && std::isfinite(step) && step > 0.0 && n_out && info && (n == 0 || pts));
     size_t need;
     const DownsampleWs s = downsample_ws_layout(n, ws, &need);
     PCREG_ARG(ws && ws_bytes >= need);
@@ -419,9 +413,24 @@ int launch_downsample_grid(const float* pts, int n, int ld, double step, float* 
         hipLaunchKernelGGL(ds_heads_count_kernel, grid, block, 0, st, s.buf[0], s.buf[1], (const DsHdr*)s.hdr, s.csum);
     }
     hipLaunchKernelGGL(ds_heads_compact_kernel, grid, block, 0, st, s.buf[0], s.buf[1], n, (const DsHdr*)s.hdr, (const int32_t*)s.csum, s.vstart, n_out);
-    if (n > 0)
+    PCREG_HIP(hipGetLastError());
+    if (order) *order = VoxelOrder{s.hdr, {s.buf[0].row, s.buf[1].row}, s.vstart};
+    return PCREG_OK;
+}
+
+int launch_downsample_grid(const float* pts, int n, int ld, double step, float* out, int ldo, int32_t* count, int32_t* label, int32_t* n_out,
+                           int32_t* info, void* ws, size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(n >= 0 && n <= 0x7FFFFFFF - kDsT && ld >= n && ldo >= n && std::isfinite(step) && step > 0.0 && n_out && info &&
+              (n == 0 || (pts && out)));
+    const int rc = launch_voxel_order(pts, n, ld, step, n_out, info, ws, ws_bytes, st, nullptr);
+    if (rc) return rc;
+    if (n > 0) {
+        size_t need;
+        const DownsampleWs s = downsample_ws_layout(n, ws, &need);
+        const dim3 block(kDsBlock), rows((n + kDsBlock - 1) / kDsBlock);
         hipLaunchKernelGGL(ds_means_kernel, rows, block, 0, st, pts, n, ld, s.buf[0], s.buf[1], (const DsHdr*)s.hdr, (const int32_t*)s.vstart,
                            (const int32_t*)n_out, out, ldo, count, label);
+    }
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -670,6 +670,100 @@ def downsample_grid(points_soa: torch.Tensor, step: float, stream=None, out=None
     return o, count, label, n_out, info
 
 
+class NdtModel:
+    """A cloud summarised ONCE as one Gaussian per occupied voxel (pcreg_dev_ndt_create; the contract is pcreg_ndt's,
+    include/pcreg.h), against which candidate transforms are refined by NDT steps that need no nearest-row search.
+    points_soa: a [3, n] float32 tensor with contiguous rows; step: the voxel size; min_points: the rows a voxel needs to hold
+    a Gaussian.  The build runs on torch's current stream and synchronises it; the handle keeps its own table, not the cloud."""
+
+    def __init__(self, points_soa: torch.Tensor, step: float, min_points: int = 6):
+        if points_soa.dtype != torch.float32 or points_soa.dim() != 2 or points_soa.shape[0] != 3 or (points_soa.shape[1] and points_soa.stride(1) != 1):
+            raise TypeError("a cloud is a [3, n] float32 tensor with contiguous rows (column-major n x 3)")
+        step, min_points = float(step), int(min_points)
+        if not (step > 0.0 and step != float("inf")):
+            raise ValueError(f"step must be a finite number > 0, got {step}")
+        if min_points < 3:
+            raise ValueError(f"min_points must be at least 3, got {min_points}")
+        n = int(points_soa.shape[1])
+        self.device, self.step, self.min_points = points_soa.device, step, min_points
+        self.handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib().pcreg_dev_ndt_create(_p(points_soa) if n else None, n, max(int(points_soa.stride(0)), n) if n else 1, step, min_points,
+                                             _stream(), C.byref(self.handle)))
+        nv, ng = C.c_int(), C.c_int()
+        check(lib().pcreg_dev_ndt_size(self.handle, C.byref(nv), C.byref(ng)))
+        self.n_voxels, self.n_gaussians = nv.value, ng.value
+
+    def gaussians(self):
+        """-> dict of numpy arrays: cells [G, 3] int32, counts [G] int32, means [G, 3] float64, C [G, 6] float64 (xx xy xz yy yz
+        zz of the floored inverse covariance), lo [3] and origin [3] float32; the Gaussians ascend by cell.  Synchronises."""
+        import numpy as np
+        G = self.n_gaussians
+        cells, counts = np.zeros((G, 3), np.int32), np.zeros(G, np.int32)
+        means, Cm = np.zeros((G, 3), np.float64), np.zeros((G, 6), np.float64)
+        lo, origin = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        with torch.cuda.device(self.device):
+            check(lib().pcreg_dev_ndt_get(self.handle, cells.ctypes.data, counts.ctypes.data, means.ctypes.data, Cm.ctypes.data, lo.ctypes.data,
+                                          origin.ctypes.data))
+        return dict(cells=cells, counts=counts, means=means, C=Cm, lo=lo, origin=origin)
+
+    def refit(self, q_soa: torch.Tensor, T_dev: torch.Tensor, neighbors: int = 1, outlier_ratio: float = 0.55, steps: int = 1, out=None):
+        """B transforms refined by the NDT step, `steps` times over, on torch's current stream (pcreg_dev_ndt_refit_f32 once per
+        step, a step's T_out the next one's input, no host synchronisation): q_soa a [3, Q] float32 tensor with contiguous rows,
+        T_dev a contiguous float64 tensor of B x 16 numbers; neighbors 1 (a point's own voxel) or 7 (and its face neighbours)
+        -> (T_out [B, 16], T_step [B, 16], n_pairs [B] int32, sum_e [B] float64, empty [B] int32), the counts and sums for the
+        transform that went INTO the last step.  T_dev is not written.  The workspace is cached on the handle; calls that may
+        overlap on two streams pass buffers of their own, out=(T_out, T_step, n_pairs, sum_e, empty, ws, T_tmp) with ws of
+        pcreg_dev_ndt_refit_workspace(Q, B) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or (q_soa.shape[1] and q_soa.stride(1) != 1):
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
+            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        neighbors, outlier_ratio, steps = int(neighbors), float(outlier_ratio), int(steps)
+        if neighbors not in (1, 7):
+            raise ValueError(f"neighbors must be 1 or 7, got {neighbors}")
+        if not 0.0 <= outlier_ratio < 1.0:
+            raise ValueError(f"outlier_ratio must lie in [0, 1), got {outlier_ratio}")
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
+        need = max(int(lib().pcreg_dev_ndt_refit_workspace(Q, B)), 256)
+        if out is not None:
+            T_out, T_step, n_pairs, sum_e, empty, ws, T_tmp = out
+            if steps > 1 and T_tmp is None:
+                raise ValueError("more than one step needs the second transform block, T_tmp")
+        else:
+            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            n_pairs, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+            sum_e = torch.empty(B, dtype=torch.float64, device=dev)
+            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
+            ws = getattr(self, "_refit_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._refit_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if B:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                src = T_dev
+                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
+                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
+                    check(lib().pcreg_dev_ndt_refit_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1) if Q else 1, _p(src), B,
+                                                        neighbors, outlier_ratio, _p(dst), _p(T_step), _p(n_pairs), _p(sum_e), _p(empty), _p(ws),
+                                                        C.c_size_t(ws.numel()), _stream()))
+                    src = dst
+        return T_out, T_step, n_pairs, sum_e, empty
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            lib().pcreg_dev_ndt_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def release_dropped() -> None:
     """Free the prepared models that as_prepared() replaced (pcreg_dev_model_destroy synchronises the device: not something to
     do between two launches of a hot loop, which is where a replaced cache entry used to die)."""

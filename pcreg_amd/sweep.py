@@ -521,7 +521,8 @@ def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, 
     return score_summary(both[2 * n:], both[:2 * n].view(np.float64), Q)
 
 
-def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None):
+def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None, ndt=None,
+                  neighbors: int = 1, outlier_ratio: float = 0.55):
     """Every trial of a sweep's result refitted on the dense clouds (PreparedModel.refit_transforms): completeExperimentFast.m:383-394's
     T_refine with the dense surface ([3, Q] float32) and the prepared dense model in the place of a cluster's re-matched
     keypoints, `steps` times over.  The orientation is score_trials': invertTF(transforms[t]) puts the surface on the model and
@@ -530,12 +531,21 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
     refit is empty; score_trials' dict for the pairs of the last step (the transform that went into it).  One upload and one
     read, whatever `steps`; the radius is squared once in single.  normals (the [3, M] tensor PreparedModel.normals returns): the
     steps are point-to-plane steps (PreparedModel.refit_plane) instead of estimateTransform steps -- the same orientation, the same
-    outputs, a trial whose planes give no fit None."""
+    outputs, a trial whose planes give no fit None.  ndt (a device.NdtModel of the dense model): the steps are NDT steps
+    (NdtModel.refit with `neighbors` and `outlier_ratio`) instead -- no nearest-row search, so model and max_dist are not used and
+    may be None; the same orientation; the summary is then dict(n_pairs, sum_e) of the last step, a trial without a fit None."""
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
     Q, n = int(surface_soa.shape[1]), len(tf)
     if n == 0:
         return [], score_summary(np.zeros(0, np.int32), np.zeros(0), Q)
     T_dev = torch.from_numpy(_transforms16(tf)).to(surface_soa.device)
+    if ndt is not None:
+        T_out, _step, n_pairs, sum_e, empty = ndt.refit(surface_soa, T_dev, neighbors=neighbors, outlier_ratio=outlier_ratio, steps=steps)
+        both = torch.cat([T_out.reshape(-1).view(torch.int32), sum_e.view(torch.int32), n_pairs, empty]).cpu().numpy()
+        mats = both[:32 * n].view(np.float64).reshape(n, 4, 4).transpose(0, 2, 1)
+        gone = both[35 * n:] != 0
+        out = [None if gone[t] else invertTF(np.ascontiguousarray(mats[t])) for t in range(n)]
+        return out, dict(n_pairs=both[34 * n:35 * n].copy(), sum_e=both[32 * n:34 * n].view(np.float64).copy())
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
     if normals is None:
         T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
