@@ -323,6 +323,61 @@ int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, co
 int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
                                 int steps, const float* normals /* host M x 3, or NULL */, int ldn, int k, double* T_out /* [B][16] */,
                                 int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty);
+/* The PLANE-TO-PLANE step of a refinement (generalized ICP; what MATLAB's pcregistericp offers as Metric = 'planeToPlane'), beside
+ * pcreg_model_refit_f32 (point to point) and pcreg_model_refit_plane_f32 (point to plane): every pair is weighted by the inverse of
+ * the sum of two regularised covariances, one per side, each flat along its own surface normal.  A pair so pulls fully ACROSS
+ * either surface and about half as hard ALONG them, so the matrix stays definite where the point-to-plane step has nothing to
+ * hold on to (a flat model).  A step, not an ICP policy: no convergence test, no robust kernel, no claim of pcregistericp's bits.
+ * THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- those of pcreg_model_refit_plane_f32 (a prepared model, Q fp32 points column-major with ldq, B transforms of 16 doubles
+ * used as quickTF.m uses them, r2 >= 0 with +inf allowed, the model's NORMALS M x 3 fp32 column-major by ORIGINAL row with
+ * ldn >= M), the QUERY NORMALS Q x 3 fp32 column-major by query index with ldnq >= Q -- exactly what the normals entry points write
+ * for a model made of the queries -- and EPSILON, a double in (0, 1] (1e-3 where a default is offered): the covariance of a side
+ * is C = I - (1 - epsilon) n n^T, eigenvalues (1, 1, epsilon) for a unit normal, epsilon along it.  Normals are used as given and
+ * are not renormalised.
+ * THE PAIRS are scoring's, word for word (pcreg_model_refit_plane_f32: the transformed query p', the nearest row within the
+ * radius, ties to the lowest original row); n_close[b] and sum_d2[b] are THE SAME BITS pcreg_model_score_f32 returns.  A
+ * PLANE-TO-PLANE PAIR is a pair in which the model row's normal n and the query's normal nq each have three finite components and
+ * the 3 x 3 matrix S below factorises with three pivots that are finite and above 0; n_pairs[b] their number.
+ * PER PAIR (pcreg_amd/csrc/gicp_pair.hpp holds the one definition), in double on the widened fp32 values, without contraction;
+ * a = 1 - epsilon, computed once on the host:
+ *   1. the moved normal v_j = (nq_x T[4j] + nq_y T[4j+1]) + nq_z T[4j+2], j = 0, 1, 2: quickTF's chain without the translation; v
+ *      stays in double.
+ *   2. S = 2 I - a (n n^T + v v^T), which is C_model + R C_query R^T:  t_ij = n_i * n_j + v_i * v_j;  S_ii = 2.0 - a * t_ii;
+ *      S_ij = 0.0 - a * t_ij for i < j.
+ *   3. S = L L^T:  p0 = S_xx;  l00 = sqrt(p0);  l10 = S_xy / l00;  l20 = S_xz / l00;  p1 = S_yy - l10 * l10;  l11 = sqrt(p1);
+ *      l21 = (S_yz - l20 * l10) / l11;  p2 = (S_zz - l20 * l20) - l21 * l21;  l22 = sqrt(p2).  The pair is dropped as soon as a
+ *      pivot p_k is not a finite number above 0.
+ *   4. M = L^-1:  m00 = 1.0 / l00;  m11 = 1.0 / l11;  m22 = 1.0 / l22;  m10 = -(l10 * m00) / l11;  m21 = -(l21 * m11) / l22;
+ *      m20 = -(l20 * m00 + l21 * m10) / l22.
+ *   5. W = S^-1 = M^T M:  W_xx = (m00 * m00 + m10 * m10) + m20 * m20;  W_xy = m10 * m11 + m20 * m21;  W_xz = m20 * m22;
+ *      W_yy = m11 * m11 + m21 * m21;  W_yz = m21 * m22;  W_zz = m22 * m22.
+ *   6. e = p - m and u = p - o (o, m, p as in pcreg_model_refit_plane_f32), and pcreg_ndt_refit_f32's PER PAIR terms with C := W
+ *      and x := e:  y = W e,  qq = (e_0 y_0 + e_1 y_1) + e_2 y_2,  a_ij = J_i^T W J_j,  h_i = J_i . y.
+ * THE SIGN of either set of normals cannot matter: n and v enter S through the products n_i n_j and v_i v_j alone, and negating nq
+ * negates v exactly, so negating a normal gives the same bits.  With unit normals the eigenvalues of S lie in [2 epsilon, 2];
+ * epsilon = 1 gives S = 2 I exactly (an unweighted point-to-point Gauss-Newton step).  A normal much longer than 1 makes S
+ * indefinite and the pair is dropped.
+ * THE 28 SUMS over the plane-to-plane pairs in ascending query order, each sum = sum + term (fma(1, term, sum)):
+ *   [0..20] A_ij for i <= j, the upper triangle row-major;  [21..26] g_i accumulates h_i;  [27] sum_res2 accumulates qq = e^T W e.
+ * Their order is pcreg_model_refit_plane_f32's: a thread adds its 8 consecutive queries in order, the wave's butterfly follows,
+ * the four waves of a chunk of 2048 queries in ascending order, the chunks in ascending order from 0.  No floating-point atomic.
+ * THE FIT is pcreg_model_refit_plane_f32's, unchanged, on these 28 sums with n_pairs in n_plane's place: the scaled Cholesky, the
+ * pivot floor 2^-26, the Cayley rotation, T_step about o, T_out = T * T_step.  EMPTY by its rules: empty[b] = 1 and 32 zeros for
+ * the all-zero T[b], n_pairs < 6, an A_ii not a finite number above 0, a pivot not above 2^-26, a non-finite x or T_step.  The
+ * counts and sums are reported either way; a failed candidate stays failed when the step is repeated.
+ * Q = 0 or a model without rows: every transform is empty, the counts and sums 0.  B = 0: nothing is written.
+ * THIS entry runs `steps` >= 1 such steps on the device with one upload and one read, with pcreg_model_refit_plane_f32's staging
+ * and its meaning of the outputs.  normals == NULL: the model's normals are computed once on the device with this k, as there.
+ * qnormals == NULL: the query normals are computed once on the device from a temporary prepared model of q, with the same k and no
+ * viewpoint; the temporary is released before the call returns.  Both given: k is ignored.
+ * PCREG_E_ARG: pcreg_model_refit_plane_f32's cases (k is checked when either set is NULL); ldnq < Q with qnormals given; epsilon NaN
+ * or outside (0, 1]. */
+int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                               int steps, const float* normals /* host M x 3, or NULL */, int ldn,
+                               const float* qnormals /* host Q x 3, or NULL */, int ldnq, int k, double epsilon,
+                               double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2,
+                               int32_t* empty);
 /* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
  * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
@@ -1114,6 +1169,20 @@ int pcreg_dev_model_refit_plane_f32(const pcreg_dev_model* model, const float* q
                                     int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_plane /* [B] */,
                                     double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
                                     void* workspace, size_t workspace_bytes, void* stream);
+/* ONE step of pcreg_model_refit_gicp_f32's contract on the device: pcreg_dev_model_refit_plane_f32's arguments and
+ * rules, with qnormals_dev [3 * ldnq] -- what pcreg_dev_model_normals_f32 writes for a model made of the queries -- and epsilon
+ * added, and n_pairs in n_plane's place.  The chain is the plane refit's with the plane-to-plane sums in the point-to-plane ones'
+ * place; the workspace has the plane refit's size and layout.  PCREG_E_ARG also for ldnq < Q, qnormals_dev NULL with Q > 0, and
+ * epsilon NaN or outside (0, 1]. */
+size_t pcreg_dev_model_refit_gicp_workspace(int Q, int B, int M);
+int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                   const double* T_dev /* [B][16] on the device */, int B, float r2,
+                                   const float* normals_dev /* [3][ldn] */, int ldn,
+                                   const float* qnormals_dev /* [3][ldnq] */, int ldnq, double epsilon,
+                                   double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                                   int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_pairs /* [B] */,
+                                   double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 /* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain
  * (DESIGN 4.11).  label [M], indexed by ORIGINAL row: the 0-based number of the row's cluster, clusters numbered in ascending

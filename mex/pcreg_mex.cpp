@@ -33,6 +33,12 @@
 //                                          page where there is no fit (fewer than six planes, a direction the planes leave free, an
 //                                          all-zero T(:, :, b)); the counts and sums are those of the transform that went into the
 //                                          last step, sqrt(sumRes2 ./ double(nPlane)) its plane RMSE (matlab/refitPlaneModel.m)
+//   'modelRefitGicp', handle, pts (single Q x 3), T (double 4 x 4 x B), maxDist, steps, normals (single M x 3 | []), ptsNormals (single
+//                                          Q x 3 | []), k, epsilon -> Tout (double 4 x 4 x B), nClose (B x 1 int32), sumD2 (B x 1
+//                                          double), nPairs (B x 1 int32), sumRes2 (B x 1 double): 'modelRefitPlane' with the
+//                                          plane-to-plane (generalized ICP) step in its place; either set of normals may be [] to
+//                                          compute it once with k (3 .. 32); epsilon in (0, 1] is the covariance along a normal; a
+//                                          zero page where there is no fit (matlab/refitGicpModel.m)
 //   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
 //                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
@@ -1072,6 +1078,48 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                                             (int)mxGetScalar(prhs[5]), given ? (const float*)mxGetData(prhs[6]) : nullptr, M > 0 ? M : 1,
                                                             (int)mxGetScalar(prhs[7]), mxGetPr(ot), (int32_t*)mxGetData(on), mxGetPr(os),
                                                             (int32_t*)mxGetData(op), mxGetPr(og), (int32_t*)mxGetData(oe));
+                mxDestroyArray(oe);
+                if (rc == PCREG_OK) {
+                    plhs[0] = ot;
+                    if (nlhs > 1) plhs[1] = on; else mxDestroyArray(on);
+                    if (nlhs > 2) plhs[2] = os; else mxDestroyArray(os);
+                    if (nlhs > 3) plhs[3] = op; else mxDestroyArray(op);
+                    if (nlhs > 4) plhs[4] = og; else mxDestroyArray(og);
+                } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(op); mxDestroyArray(og); }
+            }
+        }
+    } else if (!strcmp(cmd, "modelRefitGicp")) {              // [Tout, nClose, sumD2, nPairs, sumRes2] = pcreg_mex('modelRefitGicp', h, single(pts), T, maxDist, steps, normals, ptsNormals, k, epsilon)
+        if (nrhs != 10 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !radius_ok(prhs[4]) || !mxIsDouble(prhs[5]) ||
+            mxGetM(prhs[5]) * mxGetN(prhs[5]) != 1 || !(mxGetScalar(prhs[5]) >= 1.0) || !(mxGetScalar(prhs[5]) <= 1e6) ||
+            mxGetScalar(prhs[5]) != (double)(int)mxGetScalar(prhs[5]) || (!mxIsEmpty(prhs[6]) && (!mxIsSingle(prhs[6]) || mxGetN(prhs[6]) != 3)) ||
+            (!mxIsEmpty(prhs[7]) && (!mxIsSingle(prhs[7]) || mxGetN(prhs[7]) != 3)) || !normals_k_ok(prhs[8]) || !mxIsDouble(prhs[9]) ||
+            mxGetM(prhs[9]) * mxGetN(prhs[9]) != 1 || !(mxGetScalar(prhs[9]) > 0.0) || !(mxGetScalar(prhs[9]) <= 1.0))
+            usage = "modelRefitGicp: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), steps (a whole number >= 1), "
+                    "normals (single M x 3, or [] to compute them), ptsNormals (single Q x 3, or [] to compute them), k (a whole number 3 .. 32), "
+                    "epsilon (a double scalar in (0, 1])";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool given = !mxIsEmpty(prhs[6]), given_q = !mxIsEmpty(prhs[7]);
+            int M = 0;
+            rc = pcreg_model_size(h, &M);
+            if (rc == PCREG_OK && given && (int)mxGetM(prhs[6]) != M) usage = "modelRefitGicp: normals must have one row per model row";
+            else if (rc == PCREG_OK && given_q && (int)mxGetM(prhs[7]) != Q) usage = "modelRefitGicp: ptsNormals must have one row per row of pts";
+            else if (rc == PCREG_OK) {
+                const mwSize dims[3] = {4, 4, (mwSize)B};
+                mxArray* ot = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+                mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+                mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+                mxArray* op = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+                mxArray* og = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+                mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+                if (B > 0) rc = pcreg_model_refit_gicp_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2,
+                                                           (int)mxGetScalar(prhs[5]), given ? (const float*)mxGetData(prhs[6]) : nullptr, M > 0 ? M : 1,
+                                                           given_q ? (const float*)mxGetData(prhs[7]) : nullptr, Q > 0 ? Q : 1,
+                                                           (int)mxGetScalar(prhs[8]), mxGetScalar(prhs[9]), mxGetPr(ot), (int32_t*)mxGetData(on),
+                                                           mxGetPr(os), (int32_t*)mxGetData(op), mxGetPr(og), (int32_t*)mxGetData(oe));
                 mxDestroyArray(oe);
                 if (rc == PCREG_OK) {
                     plhs[0] = ot;

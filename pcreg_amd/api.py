@@ -1283,6 +1283,54 @@ class Model:
                    sum_res2=sum_res2[:B], plane_rmse=plane_rmse)
         return res
 
+    def refit_gicp(self, query, T, r2: float, steps: int = 1, normals=None, query_normals=None, k: int = 6, epsilon: float = 1e-3):
+        """B transforms refitted by the plane-to-plane (generalized ICP) step against the prepared model, `steps` times over
+        (pcreg_model_refit_gicp_f32, whose contract this is): the pairs are refit_transforms', a pair is weighted by the inverse
+        of the sum of the two sides' covariances, each I - (1 - epsilon) n n^T about its own normal, and T <- T * T_step.
+        normals: [M, 3] float32 by original row, as Model.normals returns them; query_normals: [Q, 3] float32 by query, as
+        Model(query).normals returns them (a pair with a non-finite component on either side is dropped; the signs are
+        immaterial); either None: computed once on the device from the k nearest rows of its own cloud.  epsilon in (0, 1].
+        -> refit_transforms' dict plus n_pairs [B] int32, the plane-to-plane pairs; sum_res2 [B] float64, the sum of their
+        e^T W e; pair_rmse = sqrt(sum_res2 / n_pairs), NaN where there is none -- all for the transform that went INTO the last
+        step.  empty is also set where fewer than six pairs, or pairs that leave a direction free, give no fit."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2 = _range_r2(r2)
+        steps, epsilon = int(steps), float(epsilon)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if not 0.0 < epsilon <= 1.0:
+            raise ValueError(f"epsilon must lie in (0, 1], got {epsilon}")
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        nrm = nq = None
+        if normals is not None:
+            nrm = _fcol(normals, np.float32)
+            if nrm.shape[0] != self.M:
+                raise ValueError(f"normals are [M, 3] with M = {self.M} rows, got {nrm.shape[0]}")
+        if query_normals is not None:
+            nq = _fcol(query_normals, np.float32)
+            if nq.shape[0] != Q:
+                raise ValueError(f"query normals are [Q, 3] with Q = {Q} rows, got {nq.shape[0]}")
+        if nrm is None or nq is None:
+            k, _ = _normals_args(k, None)
+        out = np.zeros((max(B, 1), 16), dtype=np.float64)
+        n_close, n_pairs, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(3))
+        sum_d2, sum_res2 = (np.zeros(max(B, 1), dtype=np.float64) for _ in range(2))
+        check(lib().pcreg_model_refit_gicp_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                               nrm.ctypes.data if nrm is not None else None, max(self.M, 1),
+                                               nq.ctypes.data if nq is not None else None, max(Q, 1), int(k), epsilon, out.ctypes.data,
+                                               n_close.ctypes.data, sum_d2.ctypes.data, n_pairs.ctypes.data, sum_res2.ctypes.data,
+                                               empty.ctypes.data))
+        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pair_rmse = np.where(n_pairs[:B] > 0, np.sqrt(sum_res2[:B] / n_pairs[:B]), np.nan)
+        res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, n_pairs=n_pairs[:B],
+                   sum_res2=sum_res2[:B], pair_rmse=pair_rmse)
+        return res
+
     def cluster(self, r2: float):
         """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,
         members [M] int32), 0-based -- cluster_points' contract."""

@@ -424,6 +424,20 @@ int pcreg_dev_model_refit_plane_f32(const pcreg_dev_model* model, const float* q
     return launch_model_refit_plane(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty,
                                     workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_refit_gicp_workspace(int Q, int B, int M) { return refit_gicp_ws_bytes(Q, B, M); }
+int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                   const float* normals, int ldn, const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step,
+                                   int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && normals && ldn >= 0);
+    PCREG_ARG(ldnq >= Q && (Q == 0 || qnormals) && epsilon > 0.0 && epsilon <= 1.0);                      // (a NaN epsilon fails both)
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && n_pairs && sum_res2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_gicp_ws_bytes(Q, B, 0));              // (the size does not depend on M)
+    PCREG_ARG(ldn >= model->v.M);                                            // (host data of the handle: refused before the device, as the rest)
+    GUARD();
+    return launch_model_refit_gicp(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, qnormals, ldnq, epsilon, T_out, T_step, n_close, sum_d2,
+                                   n_pairs, sum_res2, empty, workspace, workspace_bytes, (hipStream_t)stream);
+}
 size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -807,6 +821,67 @@ int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int l
     memcpy(sum_res2, host.data() + 17 * nB, sizeof(double) * nB);
     memcpy(n_close, hi, sizeof(int32_t) * nB);
     memcpy(n_plane, hi + nB, sizeof(int32_t) * nB);
+    memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
+    return PCREG_OK;
+}
+
+// B transforms refitted `steps` times by the plane-to-plane step: pcreg_model_refit_plane_f32's staging and result block, with the
+// query normals beside the model normals -- each uploaded once, or computed once on the device by the normals chain (k nearest
+// rows, no viewpoint; the queries' from a prepared model of q that lives in the staging and goes with it)
+int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
+                               const float* normals, int ldn, const float* qnormals, int ldnq, int k, double epsilon, double* T_out,
+                               int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty) {
+    PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && n_pairs && sum_res2 && empty)));
+    PCREG_ARG(epsilon > 0.0 && epsilon <= 1.0);                               // (a NaN epsilon fails both)
+    PCREG_ARG((normals && qnormals) || (k >= 3 && k <= kKnnMaxK));
+    PCREG_ARG((!normals || ldn >= 0) && (!qnormals || ldnq >= Q));
+    PCREG_ARG(model->dm != nullptr && (!normals || ldn >= model->M));
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const ModelView& v = model->dm->v;
+    const int M = v.M;
+    const bool own_q = !qnormals && Q > 0;
+    const size_t wsb = refit_gicp_ws_bytes(Q, B, M), nB = (size_t)B;
+    const size_t nwsb = std::max(normals || M == 0 ? (size_t)0 : normals_ws_bytes(M, k), own_q ? normals_ws_bytes(Q, k) : (size_t)0);
+    float *dq, *dn, *dnq; double *dT, *dout; char *ws, *nws, *qblock;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * nB, &dT));
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
+    TRY(st.take(3 * (size_t)(Q > 0 ? Q : 1), &dnq));
+    TRY(st.take(2 * 20 * nB, &dout));                                      // two result blocks of 20 B doubles' room (18 B and 3 B int32)
+    TRY(st.take(wsb, &ws));
+    TRY(st.take(nwsb, &nws));
+    TRY(st.take(own_q ? model_prep_bytes(Q) : 0, &qblock));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
+    else if (M > 0) TRY(launch_model_normals(v, k, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
+    if (qnormals) TRY(upload_cols(qnormals, Q, ldnq, 3, dnq, g_stream));
+    else if (own_q) {
+        const ModelView qv = model_view(dq, Q, Q, qblock);
+        TRY(launch_model_prepare(qv, g_stream));
+        TRY(launch_model_normals(qv, k, nullptr, dnq, Q, nullptr, nws, nwsb, g_stream));
+    }
+    const double* in = dT;
+    double* blk = dout;
+    for (int s = 0; s < steps; ++s) {
+        blk = dout + (size_t)(s & 1) * 20 * nB;
+        int32_t* ib = (int32_t*)(blk + 18 * nB);
+        TRY(launch_model_refit_gicp(v, dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, dnq, Q > 0 ? Q : 1, epsilon, blk, nullptr, ib, blk + 16 * nB, ib + nB,
+                                    blk + 17 * nB, ib + 2 * nB, ws, wsb, g_stream));
+        in = blk;
+    }
+    std::vector<double> host(20 * nB);
+    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 20 * nB, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const int32_t* hi = (const int32_t*)(host.data() + 18 * nB);
+    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
+    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
+    memcpy(sum_res2, host.data() + 17 * nB, sizeof(double) * nB);
+    memcpy(n_close, hi, sizeof(int32_t) * nB);
+    memcpy(n_pairs, hi + nB, sizeof(int32_t) * nB);
     memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
     return PCREG_OK;
 }

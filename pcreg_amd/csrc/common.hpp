@@ -247,6 +247,13 @@ size_t refit_plane_ws_bytes(int Q, int B, int M);
 int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                              double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty,
                              void* ws, size_t ws_bytes, hipStream_t st);
+// the same chain with the plane-to-plane (generalized ICP) sums in the point-to-plane ones' place (knn_score.hip, gicp_pair.hpp; DESIGN
+// 4.26): qnormals [3][ldnq] on the device by query; n_pairs the pairs both of whose normals are finite and whose S factorises,
+// sum_res2 their e . (W e).  The workspace is the plane refit's
+size_t refit_gicp_ws_bytes(int Q, int B, int M);
+int launch_model_refit_gicp(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
+                            const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
+                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
 // connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,

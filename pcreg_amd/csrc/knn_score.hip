@@ -27,12 +27,17 @@
 //   P5  plane_moments_kernel          per (transform, chunk of 2048 queries): the 28 sums of the plane pairs in query order -- a
 //                                     hit whose row has a finite normal, gathered by that row -- and their number; a fixed tree
 //   P6  plane_finish_kernel           per transform: the chunks ascending, plane_fit (plane_fit.hpp), T * T_step
+//
+// The plane-to-plane refit (pcreg_model_refit_gicp_f32's contract) is the plane refit's chain and workspace with
+//   G5  gicp_moments_kernel           in P5's place: a pair is weighted by W = (C_model + R C_query R^T)^-1 from the two normals
+//                                     (gicp_pair.hpp); the 28 sums are NDT's per-pair terms with C := W, unweighted; P6 follows
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
 #include "chunk_scan.hpp"
 #include "moments.hpp"
 #include "plane_fit.hpp"
+#include "gicp_pair.hpp"
 #include <climits>
 #include <cmath>
 
@@ -293,6 +298,104 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float* __re
     chunk_sum(cnt, pplane);
 }
 
+// ---- G5. the plane-to-plane refit's sums --------------------------------------------------------------------------------
+// workgroup bl * chunks + c and thread t as plane_moments_kernel, and its first step: the eight (best, row) loads.  The 24
+// gathers of model normals they address and the thread's 24 query-normal loads are issued together next.  Then, in query order
+// and in double on the widened values without contraction: gicp_pair (gicp_pair.hpp) gives W or drops the pair; e = p - m,
+// u = p - o, and pcreg_ndt_refit_f32's per-pair terms with C := W and x := e, added plainly (fma(1, term, sum) is sum + term):
+// A_ij (i <= j, row-major), g_i, and e . (W e) in the 28th place.  The tree after the loop is plane_moments_kernel's.
+__device__ __forceinline__ void gicp_cross(const double (&a)[3], double b0, double b1, double b2, double (&c)[3]) {
+    c[0] = a[1] * b2 - a[2] * b1;
+    c[1] = a[2] * b0 - a[0] * b2;
+    c[2] = a[0] * b1 - a[1] * b0;
+}
+__global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
+                                                              const int32_t* __restrict__ prow, const float* __restrict__ normals, int ldn, int M,
+                                                              const float* __restrict__ qnormals, int ldnq, const double* __restrict__ T, double a, int Q,
+                                                              int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ psums,
+                                                              int32_t* __restrict__ ppairs) {
+    __shared__ double s_m[kBlock / 64][kPlaneSums];
+    const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
+    const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
+    const double o[3] = {(double)prep->cx, (double)prep->cy, (double)prep->cz};
+    const double* __restrict__ Tb = T + (size_t)bl * 16;
+    int row[kScanPer];
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        row[u] = -1;
+        if (i0 + u < Q) {
+            const size_t s = (size_t)bl * Q + i0 + u;
+            const float d = best[s];
+            const int r = prow[s];
+            if (d == d && (unsigned)r < (unsigned)M) row[u] = r;      // (a hit's row is a model row: the walk wrote it)
+        }
+    }
+    float nm[kScanPer][3], nq[kScanPer][3];
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        const int r = row[u] >= 0 ? row[u] : 0;
+        const int i = row[u] >= 0 ? i0 + u : 0;                       // (a hit's query is below Q)
+        const float qnan = __int_as_float(0x7FC00000);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            nm[u][k] = row[u] >= 0 ? normals[r + k * (size_t)ldn] : qnan;
+            nq[u][k] = row[u] >= 0 ? qnormals[i + k * (size_t)ldnq] : qnan;
+        }
+    }
+    double acc[27], rr = 0.0;
+    int32_t cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int u = 0; u < kScanPer; ++u) {
+        double C[6];
+        if (!gicp_pair(nm[u], nq[u], Tb, a, C)) continue;             // (a miss's normals are NaN)
+        const size_t s = (size_t)bl * Q + i0 + u;
+        const double m0 = (double)win[s], m1 = (double)win[s + (size_t)S], m2 = (double)win[s + 2 * (size_t)S];
+        const double p0 = (double)tq[s], p1 = (double)tq[s + (size_t)S], p2 = (double)tq[s + 2 * (size_t)S];
+        const double x[3] = {p0 - m0, p1 - m1, p2 - m2};
+        const double uu[3] = {p0 - o[0], p1 - o[1], p2 - o[2]};
+        const double y[3] = {(C[0] * x[0] + C[1] * x[1]) + C[2] * x[2], (C[1] * x[0] + C[3] * x[1]) + C[4] * x[2],
+                             (C[2] * x[0] + C[4] * x[1]) + C[5] * x[2]};
+        const double qq = (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
+        // W_a = u x (row a of C): (W_a)_j is component a of C c_j, c_j = e_j x u
+        double W[3][3], K[3], Mm[3], gy[3];
+        gicp_cross(uu, C[0], C[1], C[2], W[0]);
+        gicp_cross(uu, C[1], C[3], C[4], W[1]);
+        gicp_cross(uu, C[2], C[4], C[5], W[2]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            K[0] = W[0][j]; K[1] = W[1][j]; K[2] = W[2][j];
+            gicp_cross(uu, K[0], K[1], K[2], Mm);                     // Mm_i = c_i . C c_j
+#pragma unroll
+            for (int i = 0; i <= j; ++i) acc[plane_tri(i, j)] = acc[plane_tri(i, j)] + Mm[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) acc[plane_tri(i, 3 + j)] = acc[plane_tri(i, 3 + j)] + W[j][i];       // c_i . (column j of C)
+        }
+        acc[plane_tri(3, 3)] = acc[plane_tri(3, 3)] + C[0]; acc[plane_tri(3, 4)] = acc[plane_tri(3, 4)] + C[1];
+        acc[plane_tri(3, 5)] = acc[plane_tri(3, 5)] + C[2]; acc[plane_tri(4, 4)] = acc[plane_tri(4, 4)] + C[3];
+        acc[plane_tri(4, 5)] = acc[plane_tri(4, 5)] + C[4]; acc[plane_tri(5, 5)] = acc[plane_tri(5, 5)] + C[5];
+        gicp_cross(uu, y[0], y[1], y[2], gy);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { acc[21 + i] = acc[21 + i] + gy[i]; acc[24 + i] = acc[24 + i] + y[i]; }
+        rr = rr + qq;
+        ++cnt;
+    }
+    wave_sum27(acc);
+    rr = wave_sum(rr);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
+        s_m[threadIdx.x >> 6][27] = rr;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneSums) {
+        const int k = threadIdx.x;
+        psums[(size_t)blockIdx.x * kPlaneSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
+    }
+    chunk_sum(cnt, ppairs);
+}
+
 // ---- P6. the plane refit's fit ------------------------------------------------------------------------------------------
 // one wave per transform bl of the batch: lane k < 28 adds sum k over the chunks in ascending order, lane 28 the plane counts;
 // every lane then runs plane_fit on the same 28 numbers about the origin the sums were taken about.  T_out = T_in * T_step by
@@ -357,6 +460,7 @@ int score_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk);
 // The refit's is that followed by [winning rows' coordinates, 3 S] [chunk moments, 27 P]: + roundup(12 S, 256) + roundup(216 P, 256)
 // The plane refit's is the refit's with 28 chunk sums instead of 27, followed by [winning row per slot, S] [chunk plane counts, P]:
 // + roundup(12 S, 256) + roundup(224 P, 256) + roundup(4 S, 256) + roundup(4 P, 256)
+// The plane-to-plane refit needs nothing more: it runs in the plane refit's layout, its pair counts in the plane counts' place.
 enum ScoreMode { kModeScore = 0, kModeRefit = 1, kModePlane = 2 };
 struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; int32_t* prow; int32_t* pplane; };
 ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes) {
@@ -386,15 +490,19 @@ ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes)
 struct RefitOut { double* T_out; double* T_step; int32_t* empty; };
 // ... and what the plane refit takes and gives beyond that: a normal per ORIGINAL row, the plane pairs and their squared residuals
 struct PlaneIo { const float* normals; int ldn; int32_t* n_plane; double* sum_res2; };
+// ... and the plane-to-plane refit beyond that (with `plane`, whose n_plane then counts its pairs): a normal per query, 1 - epsilon
+struct GicpIo { const float* qnormals; int ldnq; double a; };
 
-// the chain of every call; `refit` null: scoring; `plane` (with refit) non-null: the point-to-plane fit instead of estimateTransform
+// the chain of every call; `refit` null: scoring; `plane` (with refit) non-null: the point-to-plane fit instead of estimateTransform;
+// `gicp` (with plane) non-null: the plane-to-plane sums instead of the point-to-plane ones, in the same workspace
 int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close, double* sum_d2,
-                int32_t* idx, float* dist, const RefitOut* refit, const PlaneIo* plane, void* ws, size_t ws_bytes, hipStream_t st) {
+                int32_t* idx, float* dist, const RefitOut* refit, const PlaneIo* plane, const GicpIo* gicp, void* ws, size_t ws_bytes,
+                hipStream_t st) {
     PCREG_ARG(Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxSlots && r2 >= 0.0f);
     size_t need;
     const ScoreWs s = score_ws_layout(Q, B, plane ? kModePlane : refit ? kModeRefit : kModeScore, ws, &need);
     if (ws_bytes < need) {
-        set_error("bad argument: %s workspace too small: %zu < %zu", plane ? "plane refit" : refit ? "refit" : "score", ws_bytes, need);
+        set_error("bad argument: %s workspace too small: %zu < %zu", gicp ? "plane-to-plane refit" : plane ? "plane refit" : refit ? "refit" : "score", ws_bytes, need);
         return PCREG_E_ARG;
     }
     if (B == 0) return PCREG_OK;
@@ -438,9 +546,14 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
         hipLaunchKernelGGL(score_total_kernel, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, nb,
                            chunks, n_close + b0, sum_d2 + b0);
         if (plane) {
-            hipLaunchKernelGGL(plane_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
-                               (const float*)s.win, (const int32_t*)s.prow, plane->normals, plane->ldn, v.M, Q, S, chunks, (const Prep*)v.prep, s.pmom,
-                               s.pplane);
+            if (gicp)
+                hipLaunchKernelGGL(gicp_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
+                                   (const float*)s.win, (const int32_t*)s.prow, plane->normals, plane->ldn, v.M, gicp->qnormals, gicp->ldnq,
+                                   T_dev + (size_t)b0 * 16, gicp->a, Q, S, chunks, (const Prep*)v.prep, s.pmom, s.pplane);
+            else
+                hipLaunchKernelGGL(plane_moments_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, (const float*)s.tq,
+                                   (const float*)s.win, (const int32_t*)s.prow, plane->normals, plane->ldn, v.M, Q, S, chunks, (const Prep*)v.prep,
+                                   s.pmom, s.pplane);
             PCREG_HIP(hipGetLastError());
             hipLaunchKernelGGL(plane_finish_kernel, dim3(nb), dim3(64), 0, st, (const double*)s.pmom, (const int32_t*)s.pplane, chunks, (const Prep*)v.prep,
                                T_dev + (size_t)b0 * 16, refit->T_out + (size_t)b0 * 16, refit->T_step ? refit->T_step + (size_t)b0 * 16 : nullptr,
@@ -481,13 +594,13 @@ size_t refit_plane_ws_bytes(int Q, int B, int M) {
 
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
                        double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, nullptr, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, nullptr, nullptr, ws, ws_bytes, st);
 }
 
 int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
                        int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
     const RefitOut out{T_out, T_step, empty};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, nullptr, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, nullptr, nullptr, ws, ws_bytes, st);
 }
 
 int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
@@ -496,7 +609,20 @@ int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq,
     PCREG_ARG(ldn >= v.M && (normals || v.M == 0));
     const RefitOut out{T_out, T_step, empty};
     const PlaneIo plane{normals, ldn, n_plane, sum_res2};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, nullptr, ws, ws_bytes, st);
+}
+
+// the plane refit's workspace, as it is: the same slots and partials, with the pairs' count in the plane count's place
+size_t refit_gicp_ws_bytes(int Q, int B, int M) { return refit_plane_ws_bytes(Q, B, M); }
+
+int launch_model_refit_gicp(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
+                            const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
+                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(ldn >= v.M && (normals || v.M == 0) && Q >= 0 && ldnq >= Q && (qnormals || Q == 0) && epsilon > 0.0 && epsilon <= 1.0);
+    const RefitOut out{T_out, T_step, empty};
+    const PlaneIo plane{normals, ldn, n_pairs, sum_res2};
+    const GicpIo gicp{qnormals, ldnq, 1.0 - epsilon};
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, &gicp, ws, ws_bytes, st);
 }
 
 }  // namespace pcreg

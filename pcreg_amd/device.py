@@ -264,6 +264,63 @@ class PreparedModel:
                     src = dst
         return T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty
 
+    def refit_gicp(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, normals: torch.Tensor, q_normals: torch.Tensor, epsilon: float = 1e-3,
+                   steps: int = 1, out=None):
+        """B transforms refitted by the plane-to-plane (generalized ICP) step, `steps` times over, on torch's current stream
+        (pcreg_dev_model_refit_gicp_f32 once per step, a step's T_out the next one's input, no host synchronisation in between;
+        the contract is pcreg_model_refit_gicp_f32's): q_soa, T_dev, r2, normals and steps as refit_plane takes them; q_normals
+        the [3, Q] float32 tensor PreparedModel.normals returns for a model made of the queries (by query; the signs are
+        immaterial); epsilon in (0, 1] -> (T_out [B, 16], T_step [B, 16], n_close [B] int32, sum_d2 [B] float64, n_pairs [B]
+        int32, sum_res2 [B] float64, empty [B] int32), the counts and sums for the transform that went INTO the last step.
+        Nothing given is written.  The workspace and the second transform block are cached on the model; calls that may overlap
+        on two streams pass buffers of their own, out=(T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws, T_tmp) with
+        ws of pcreg_dev_model_refit_gicp_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
+            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        M, Q = self.M, int(q_soa.shape[1])
+        if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
+                or normals.device != q_soa.device):
+            raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the queries' device (the row stride is the leading dimension)")
+        if (q_normals.dtype != torch.float32 or q_normals.dim() != 2 or q_normals.shape[0] != 3 or q_normals.shape[1] != Q
+                or (Q and q_normals.stride(1) != 1) or q_normals.device != q_soa.device):
+            raise TypeError("query normals are a [3, Q] float32 tensor with contiguous rows on the queries' device (the row stride is the leading dimension)")
+        r2, steps, epsilon = float(r2), int(steps), float(epsilon)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if not 0.0 < epsilon <= 1.0:
+            raise ValueError(f"epsilon must lie in (0, 1], got {epsilon}")
+        dev, B = q_soa.device, T_dev.numel() // 16
+        need = max(int(lib().pcreg_dev_model_refit_gicp_workspace(Q, B, M)), 256)
+        if out is not None:
+            T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws, T_tmp = out
+            if steps > 1 and T_tmp is None:
+                raise ValueError("more than one step needs the second transform block, T_tmp")
+        else:
+            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            n_close, n_pairs, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+            sum_d2, sum_res2 = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
+            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
+            ws = getattr(self, "_refit_gicp_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._refit_gicp_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if B:                                          # (an empty tensor has no address to pass)
+            nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=dev)      # (no rows: any address, never read)
+            with torch.cuda.device(dev):
+                src = T_dev
+                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
+                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
+                    check(lib().pcreg_dev_model_refit_gicp_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B, r2,
+                                                               _p(nrm), max(int(nrm.stride(0)), M), _p(q_normals) if Q else None,
+                                                               max(int(q_normals.stride(0)), Q, 1) if Q else 1, epsilon, _p(dst), _p(T_step), _p(n_close),
+                                                               _p(sum_d2), _p(n_pairs), _p(sum_res2), _p(empty), _p(ws), ws.numel(), _stream()))
+                    src = dst
+        return T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty
+
     def cluster(self, r2: float, out=None):
         """clusterPoints(model, r) over the model's own rows with r2 = r^2, on torch's current stream
         (pcreg_dev_model_cluster_f32): -> (label [M] int32, the 0-based cluster of every row; n_clusters [1] int32; first [M]

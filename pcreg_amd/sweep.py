@@ -522,7 +522,7 @@ def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, 
 
 
 def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None, ndt=None,
-                  neighbors: int = 1, outlier_ratio: float = 0.55):
+                  neighbors: int = 1, outlier_ratio: float = 0.55, surface_normals=None, epsilon: float = 1e-3):
     """Every trial of a sweep's result refitted on the dense clouds (PreparedModel.refit_transforms): completeExperimentFast.m:383-394's
     T_refine with the dense surface ([3, Q] float32) and the prepared dense model in the place of a cluster's re-matched
     keypoints, `steps` times over.  The orientation is score_trials': invertTF(transforms[t]) puts the surface on the model and
@@ -531,7 +531,8 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
     refit is empty; score_trials' dict for the pairs of the last step (the transform that went into it).  One upload and one
     read, whatever `steps`; the radius is squared once in single.  normals (the [3, M] tensor PreparedModel.normals returns): the
     steps are point-to-plane steps (PreparedModel.refit_plane) instead of estimateTransform steps -- the same orientation, the same
-    outputs, a trial whose planes give no fit None.  ndt (a device.NdtModel of the dense model): the steps are NDT steps
+    outputs, a trial whose planes give no fit None.  normals and surface_normals (the [3, Q] tensor PreparedModel.normals returns for a
+    model made of the surface): the steps are plane-to-plane steps (PreparedModel.refit_gicp with `epsilon`) instead.  ndt (a device.NdtModel of the dense model): the steps are NDT steps
     (NdtModel.refit with `neighbors` and `outlier_ratio`) instead -- no nearest-row search, so model and max_dist are not used and
     may be None; the same orientation; the summary is then dict(n_pairs, sum_e) of the last step, a trial without a fit None."""
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
@@ -549,8 +550,11 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
     if normals is None:
         T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
-    else:
+    elif surface_normals is None:
         T_out, _step, n_close, sum_d2, _n_plane, _res2, empty = model.refit_plane(surface_soa, T_dev, r2, normals, steps=steps)
+    else:
+        T_out, _step, n_close, sum_d2, _n_pairs, _res2, empty = model.refit_gicp(surface_soa, T_dev, r2, normals, surface_normals, epsilon=epsilon,
+                                                                                 steps=steps)
     both = torch.cat([T_out.reshape(-1).view(torch.int32), sum_d2.view(torch.int32), n_close, empty]).cpu().numpy()
     mats = both[:32 * n].view(np.float64).reshape(n, 4, 4).transpose(0, 2, 1)
     gone = both[35 * n:] != 0
