@@ -378,6 +378,68 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
                                const float* qnormals /* host Q x 3, or NULL */, int ldnq, int k, double epsilon,
                                double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2,
                                int32_t* empty);
+/* The COHERENT-POINT-DRIFT step of a refinement (rigid CPD; what MATLAB users reach for as pcregistercpd with Transform = 'Rigid'),
+ * beside the three ICP steps and pcreg_ndt_refit_f32: every moved point is paired SOFTLY with EVERY live model row by a Gaussian
+ * of their distance against a uniform outlier term, and the Gaussian's variance is annealed by its own closed form.  No radius, no
+ * normals, no voxel size; a wide capture range; with a small variance it turns into the point-to-point step.  A step, not
+ * pcregistercpd: no convergence test, no scale, no affine or non-rigid variant, no fast Gauss transform, no claim of its bits.
+ * THE COST is B * Q * M pairs a step: this is for downsampled clouds (10^3 .. 10^4 points a side); nothing guards the size.
+ * THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- a prepared model of M rows, Q fp32 points column-major with ldq, B transforms of 16 doubles used as quickTF.m uses
+ * them, sigma2_in [B] doubles (0 asks for the initial value below), and the OUTLIER weight w, a double in [0, 1).
+ * ROLES: the moved queries are the DATA, the model rows the CENTROIDS of an equal-weight isotropic mixture plus a uniform term
+ * (the reverse of Myronenko's roles; for a rigid motion without scale the same objective, and the right one for a surface that
+ * is a crop of its model: every surface point has a partner, most model rows have none).
+ * LIVE: a model row with three finite coordinates, and a query whose moved point p' has three finite coordinates (so a query
+ * with a non-finite coordinate takes no part, and under an all-zero T[b] none does); Ml and Ql[b] their numbers, n_live[b] = Ql.
+ * PER transform b and live query i:  p' is scoring's moved point, word for word (pcreg_model_score_f32: double arithmetic
+ * without contraction, rounded once to fp32).  Against a live row m_j, in fp32: dx = m_j - p' by component,
+ * d2_ij = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) -- the library's distance.  dmin_i = its minimum over the live rows: THE SAME BITS
+ * pcreg_model_score_f32 reports as the nearest distance with r2 = +inf, taken from that chain; sum_d2[b] is that chain's sum.
+ * With h = 1 / (2 sigma2) in double and k2 = (float)(-(h * log2(e))):
+ *   e_ij = exp2((d2_ij - dmin_i) * k2) in fp32, in (0, 1] (the device's exp2 is within a unit or two in the last place; a result
+ *   below 2^-126 may be 0);  S_i = sum_j e_ij >= 1;  V_i = sum_j e_ij (m_j - p'_i) by fmaf(e, dx, V);  W_i = sum_j fmaf(e, d2, W).
+ * THE SHIFT by dmin_i is part of the contract: no 0 / 0 can arise.  The fp32 sums run over the live rows in ascending ORIGINAL row
+ * order, in L = ceil(M / R) slices of R = 256 ceil(ceil(M / 256) / 32) rows (at most 32 slices; the last one shorter): a
+ * slice's sum is sequential from 0, and the slices are added in ascending order from the first.
+ * Then in double on the widened values, without contraction:
+ *   c = ((2 pi sigma2) * sqrt(2 pi sigma2)) * (w / (1 - w)) * (Ml / Ql), or 0 when w == 0;  out_i = c * exp(dmin_i * h), or 0 when
+ *   c == 0;  g_i = 1 / (S_i + out_i);  p_i = g_i * S_i.
+ * With w = 0 every live query has p_i = 1 however far the model is.  With w > 0 a far query's exp may overflow to +inf, which
+ * gives g_i = 0: the right limit.
+ * THE 19 SUMS over the live queries, doubles, about the origin o -- the middle of the LIVE rows' box, 0.5f lo + 0.5f hi in fp32:
+ * pcreg_model_refit_f32's origin whenever that is finite (an infinite row spoils that one, not this) -- with
+ * u_i = p'_i - o, y_i = p_i u_i + g_i V_i (the weighted model side) and uu = (u0 u0 + u1 u1) + u2 u2:
+ *   Np = sum p_i;  sum p_i u_i (3);  sum y_i (3);  sum u_i (x) y_i (9);  sum p_i uu;
+ *   sum ((p_i uu + 2 ((u0 gV0 + u1 gV1) + u2 gV2)) + g_i W_i);  sum_res2 = sum g_i W_i, the weighted squared residual of the transform
+ *   that went in.
+ * Their order is pcreg_model_refit_plane_f32's: a thread adds its 8 consecutive queries in order, the wave's butterfly follows, the
+ * four waves of a chunk of 2048 queries in ascending order, the chunks in ascending order from 0.  No floating-point atomic; every
+ * order depends on (Q, M) alone.
+ * THE FIT (pcreg_amd/csrc/cpd_fit.hpp holds the one definition): the weighted means, the centred 3 x 3 cross-covariance A, the
+ * rotation R that maximises tr(A' R) WITH the determinant correction (coherent point drift's rule; estimateTransform.m has none)
+ * from the Jacobi of A' A in a fixed operation order, t from the means, T_step about o, T_out = T * T_step by
+ * pcreg_model_refit_f32's product, and
+ *   sigma2_out = (weighted |m - mean|^2 - 2 tr(A' R) + weighted |p' - mean|^2) / (3 Np).
+ * THE INITIAL VARIANCE: sigma2_in[b] == 0 asks for the mean squared distance over ALL (live query, live row) pairs divided by 3,
+ * in closed form from eight sums about o -- sum u, sum uu over the live queries (the 19 sums' order) and sum v, sum vv, v = m - o,
+ * over the live rows (thread t of 256 adds original rows t, t + 256, .. in order, then the butterfly and the four waves ascending):
+ *   sigma2 = ((sum uu / Ql + sum vv / Ml) - 2 (mean u . mean v)) / 3.
+ * EMPTY: empty[b] = 1, T_out[b] (and T_step[b]) sixteen 0.0 and sigma2_out[b] = 0 when T[b] is all zero or not finite; Ql < 3 or
+ * Ml < 3; sigma2_in[b] is negative or NaN; sigma2, h or k2 is not finite and non-zero; Np is not a finite number above 0; the
+ * second largest singular value of A is not above 2^-26 times the largest (a rotation the data does not determine is not
+ * invented); sigma2_out is not a finite number above 0; T_step is not finite.  n_live and sum_d2 are reported either way, Np and
+ * sum_res2 whenever the candidate got as far as its sums (0 otherwise).  A failed candidate stays failed when the step is repeated.
+ * Q = 0 or a model without rows: every transform is empty, the counts and sums 0.  B = 0: nothing is written.
+ * THIS entry runs `steps` >= 1 such steps on the device with one upload and one read; each step's sigma2_out is the next one's
+ * sigma2_in, and Np, sum_res2, sum_d2 and n_live describe the transform that went INTO the last step.
+ * DETERMINISM: the outputs of a candidate are the same bits on every call, at any position b, for any B, on any stream,
+ * whatever the batching and whichever handle holds the model.
+ * PCREG_E_ARG: pcreg_model_refit_f32's cases; outlier NaN or outside [0, 1); steps < 1. */
+int pcreg_model_refit_cpd_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B,
+                              const double* sigma2_in /* host [B] */, double outlier, int steps, double* T_out /* [B][16] */,
+                              double* sigma2_out /* [B] */, double* Np /* [B] */, double* sum_res2 /* [B] */, double* sum_d2 /* [B] */,
+                              int32_t* n_live /* [B] */, int32_t* empty /* [B] */);
 /* clusterPoints.m:16-45  clusters = clusterPoints(pts, r) against the handle, with the SQUARED radius r2 = r^2: the connected
  * components of the graph in which rows i != j of the model are adjacent iff their fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 (inclusive; a NaN distance never passes; with r2 = +inf an overflowed distance between
@@ -1183,6 +1245,21 @@ int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q,
                                    int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_pairs /* [B] */,
                                    double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
                                    void* workspace, size_t workspace_bytes, void* stream);
+/* ONE step of pcreg_model_refit_cpd_f32's contract on the device: everything is a device pointer, nothing
+ * synchronises, T_step may be NULL, T_out may not alias T_dev (sigma2_out may alias sigma2_in).  The shift dmin comes from
+ * pcreg_dev_model_score_f32's chain at r2 = +inf inside the call.  The workspace, with nb = max(1, min(B, floor(131072 / max(Q, 1))))
+ * transforms a batch, S = max(nb Q, 1), P = nb max(ceil(Q / 2048), 1), L = max(the contract's number of slices, 1), and roundup(x)
+ * to a multiple of 256:
+ *   roundup(pcreg_dev_model_score_workspace(Q, B, M)) + roundup(4 max(B Q, 1)) + roundup(4 max(B, 1)) + 256 + roundup(12 S)
+ *   + roundup(32 P) + roundup(4 P) + roundup(48 nb) + roundup(20 L S) + roundup(152 P) bytes
+ * (0 for an argument out of range).  PCREG_E_ARG also for a workspace shorter than that. */
+size_t pcreg_dev_model_refit_cpd_workspace(int Q, int B, int M);
+int pcreg_dev_model_refit_cpd_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                  const double* T_dev /* [B][16] on the device */, int B, const double* sigma2_in /* [B] */,
+                                  double outlier, double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                                  double* sigma2_out /* [B] */, double* Np /* [B] */, double* sum_res2 /* [B] */,
+                                  double* sum_d2 /* [B] */, int32_t* n_live /* [B] */, int32_t* empty /* [B] */,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* clusterPoints(model, r) on the device: the connected components of the graph "rows i != j with fp32 squared distance
  * fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2" over the model's own rows (pcreg_model_cluster_f32's contract), in one launch chain
  * (DESIGN 4.11).  label [M], indexed by ORIGINAL row: the 0-based number of the row's cluster, clusters numbered in ascending

@@ -39,6 +39,13 @@
 //                                          plane-to-plane (generalized ICP) step in its place; either set of normals may be [] to
 //                                          compute it once with k (3 .. 32); epsilon in (0, 1] is the covariance along a normal; a
 //                                          zero page where there is no fit (matlab/refitGicpModel.m)
+//   'modelRefitCpd', handle, pts (single Q x 3), T (double 4 x 4 x B), sigma2 (double scalar | B x 1), outlier, steps -> Tout (double
+//                                          4 x 4 x B), sigma2Out, Np, sumRes2, sumD2 (B x 1 double each), nLive (B x 1 int32): rigid
+//                                          coherent-point-drift steps, every moved point softly against EVERY model row (B * Q * M
+//                                          pairs a step: for downsampled clouds); sigma2 0 asks for the initial variance, outlier in
+//                                          [0, 1); a zero page and sigma2Out 0 where there is no fit; sigma2Out is the variance AFTER
+//                                          the last step, the sums and nLive are those of the transform that went into it
+//                                          (matlab/refitCpdModel.m)
 //   'modelCluster', handle, r | 'clusterPoints', pts (single M x 3), r -> label (M x 1 int32, the 1-based cluster of every row),
 //                                          clOff (C + 1 int32 offsets), members (M x 1 int32, 1-based rows): cluster c is
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
@@ -1129,6 +1136,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                     if (nlhs > 4) plhs[4] = og; else mxDestroyArray(og);
                 } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(op); mxDestroyArray(og); }
             }
+        }
+    } else if (!strcmp(cmd, "modelRefitCpd")) {               // [Tout, sigma2Out, Np, sumRes2, sumD2, nLive] = pcreg_mex('modelRefitCpd', h, single(pts), T, sigma2, outlier, steps)
+        const int Bt = nrhs == 7 && mxIsDouble(prhs[3]) && !mxIsEmpty(prhs[3]) ? (int)(mxGetN(prhs[3]) / 4) : 0;
+        if (nrhs != 7 || !mxIsUint64(prhs[1]) || !mxIsSingle(prhs[2]) || mxGetN(prhs[2]) != 3 || !mxIsDouble(prhs[3]) ||
+            (mxGetM(prhs[3]) != 4 && !mxIsEmpty(prhs[3])) || mxGetN(prhs[3]) % 4 != 0 || !mxIsDouble(prhs[4]) ||
+            (mxGetM(prhs[4]) * mxGetN(prhs[4]) != 1 && mxGetM(prhs[4]) * mxGetN(prhs[4]) != (size_t)Bt) || !mxIsDouble(prhs[5]) ||
+            mxGetM(prhs[5]) * mxGetN(prhs[5]) != 1 || !(mxGetScalar(prhs[5]) >= 0.0) || !(mxGetScalar(prhs[5]) < 1.0) || !whole_scalar_ok(prhs[6], 1.0, 1e6))
+            usage = "modelRefitCpd: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), sigma2 (a double scalar or one per page of T; 0 asks for "
+                    "the initial variance), outlier (a double scalar in [0, 1)), steps (a whole number >= 1)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = Bt;
+            std::vector<double> sig((size_t)(B > 0 ? B : 1), mxGetPr(prhs[4])[0]);
+            if (mxGetM(prhs[4]) * mxGetN(prhs[4]) == (size_t)B) memcpy(sig.data(), mxGetPr(prhs[4]), sizeof(double) * (size_t)B);
+            const mwSize dims[3] = {4, 4, (mwSize)B};
+            mxArray* ot = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+            mxArray* od[4];
+            for (mxArray*& a : od) a = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+            mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);       // (an empty fit is a zero page of Tout already)
+            rc = pcreg_model_refit_cpd_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, sig.data(), mxGetScalar(prhs[5]),
+                                           (int)mxGetScalar(prhs[6]), mxGetPr(ot), mxGetPr(od[0]), mxGetPr(od[1]), mxGetPr(od[2]), mxGetPr(od[3]),
+                                           (int32_t*)mxGetData(on), (int32_t*)mxGetData(oe));
+            mxDestroyArray(oe);
+            if (rc == PCREG_OK) {
+                plhs[0] = ot;
+                for (int i = 0; i < 4; ++i) { if (nlhs > 1 + i) plhs[1 + i] = od[i]; else mxDestroyArray(od[i]); }
+                if (nlhs > 5) plhs[5] = on; else mxDestroyArray(on);
+            } else { mxDestroyArray(ot); for (mxArray* a : od) mxDestroyArray(a); mxDestroyArray(on); }
         }
     } else if (!strcmp(cmd, "ndtCreate")) {                   // [h, nVoxels, nGaussians] = pcreg_mex('ndtCreate', single(pts), step, minPoints)
         if (nrhs != 4 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !whole_scalar_ok(prhs[3], 3.0, 1e9) || !mxIsDouble(prhs[2]) ||

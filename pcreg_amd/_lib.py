@@ -66,6 +66,7 @@ SYMBOLS = [
     "pcreg_model_normals_f32", "pcreg_point_normals_f32", "pcreg_dev_model_normals_workspace", "pcreg_dev_model_normals_f32",
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_model_refit_gicp_f32", "pcreg_dev_model_refit_gicp_workspace", "pcreg_dev_model_refit_gicp_f32",
+    "pcreg_model_refit_cpd_f32", "pcreg_dev_model_refit_cpd_workspace", "pcreg_dev_model_refit_cpd_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
     "pcreg_model_fpfh_f32", "pcreg_point_fpfh_f32", "pcreg_dev_model_fpfh_workspace", "pcreg_dev_model_fpfh_f32",
     "pcreg_model_fpfh_radius_f32", "pcreg_point_fpfh_radius_f32", "pcreg_dev_model_fpfh_radius_workspace", "pcreg_dev_model_fpfh_radius_count_f32",
@@ -223,6 +224,12 @@ def lib() -> C.CDLL:
             vp, i, f, d = C.c_void_p, C.c_int, C.c_float, C.c_double            # (a double by value: declared)
             L.pcreg_dev_model_refit_gicp_f32.argtypes = [vp, vp, i, i, vp, i, f, vp, i, vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_refit_gicp_f32.argtypes = [vp, vp, i, i, vp, i, f, i, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_model_refit_cpd_workspace"):     # (an older build given through PCREG_LIB lacks the coherent-point-drift refit)
+            L.pcreg_dev_model_refit_cpd_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_refit_cpd_workspace.argtypes = [C.c_int] * 3
+            vp, i, d = C.c_void_p, C.c_int, C.c_double                          # (a double by value: declared)
+            L.pcreg_dev_model_refit_cpd_f32.argtypes = [vp, vp, i, i, vp, i, vp, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_refit_cpd_f32.argtypes = [vp, vp, i, i, vp, i, vp, d, i, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_unique_rows3_workspace"):    # (an older build given through PCREG_LIB lacks unique_rows)
             for name in ("pcreg_dev_unique_rows3_workspace", "pcreg_dev_aggregate_matches_workspace"):
                 getattr(L, name).restype = C.c_size_t

@@ -1331,6 +1331,45 @@ class Model:
                    sum_res2=sum_res2[:B], pair_rmse=pair_rmse)
         return res
 
+    def refit_cpd(self, query, T, sigma2=0.0, outlier: float = 0.1, steps: int = 1):
+        """B transforms refitted by the coherent-point-drift step (rigid CPD) against the prepared model, `steps` times over
+        (pcreg_model_refit_cpd_f32, whose contract this is): every moved query is paired softly with EVERY live model row by
+        exp(-d2 / (2 sigma2)) against a uniform outlier term of weight `outlier` in [0, 1), the weighted rigid fit with the
+        determinant correction follows, T <- T * T_step, and the variance is annealed by its own closed form.  No radius, no
+        normals, no voxel size.  The cost is B * Q * M pairs a step: for downsampled clouds.
+        sigma2: a number or [B] float64, the variance each candidate starts from; 0 (the default) asks for the initial value,
+        the mean squared distance over all pairs divided by 3; negative or NaN makes the candidate empty.
+        -> dict(T [B, 4, 4] as quickTF uses them, a ZERO matrix where empty; empty [B] bool; sigma2 [B] float64, the variance
+        AFTER the last step (feed it to a later call), 0 where empty; and for the transform that went INTO the last step: Np [B]
+        float64, the sum of the posterior weights; sum_res2 [B] float64, the weighted squared residual; sum_d2 [B] float64, the
+        sum of the squared nearest-row distances (score_transforms' bits at r2 = +inf); n_live [B] int32, the queries whose moved
+        point is finite)."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        steps, outlier = int(steps), float(outlier)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if not 0.0 <= outlier < 1.0:
+            raise ValueError(f"outlier must lie in [0, 1), got {outlier}")
+        q = _fcol(query, np.float32)
+        Q = q.shape[0]
+        T16 = _transforms16(T)
+        B = T16.shape[0]
+        sig = np.asarray(sigma2, dtype=np.float64).reshape(-1)
+        if sig.size == 1:
+            sig = np.full(max(B, 1), sig[0])
+        elif sig.size != B:
+            raise ValueError(f"sigma2 is a number or one per transform ({B}), got {sig.size}")
+        sig = np.ascontiguousarray(sig) if B else np.zeros(1)
+        out = np.zeros((max(B, 1), 16), dtype=np.float64)
+        sig_out, Np, sum_res2, sum_d2 = (np.zeros(max(B, 1), dtype=np.float64) for _ in range(4))
+        n_live, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(2))
+        check(lib().pcreg_model_refit_cpd_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, sig.ctypes.data,
+                                              outlier, steps, out.ctypes.data, sig_out.ctypes.data, Np.ctypes.data, sum_res2.ctypes.data,
+                                              sum_d2.ctypes.data, n_live.ctypes.data, empty.ctypes.data))
+        return dict(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, sigma2=sig_out[:B], Np=Np[:B],
+                    sum_res2=sum_res2[:B], sum_d2=sum_d2[:B], n_live=n_live[:B])
+
     def cluster(self, r2: float):
         """clusterPoints(model, r) on the prepared model's own rows with r2 = r^2: (label [M] int32, cl_off [C + 1] int32,
         members [M] int32), 0-based -- cluster_points' contract."""

@@ -438,6 +438,18 @@ int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q,
     return launch_model_refit_gicp(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, qnormals, ldnq, epsilon, T_out, T_step, n_close, sum_d2,
                                    n_pairs, sum_res2, empty, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_refit_cpd_workspace(int Q, int B, int M) { return refit_cpd_ws_bytes(Q, B, M); }
+int pcreg_dev_model_refit_cpd_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, const double* sigma2_in,
+                                  double outlier, double* T_out, double* T_step, double* sigma2_out, double* Np, double* sum_res2, double* sum_d2,
+                                  int32_t* n_live, int32_t* empty, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ);
+    PCREG_ARG(outlier >= 0.0 && outlier < 1.0);                              // (a NaN fails both)
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && sigma2_in && T_out && T_out != T_dev && sigma2_out && Np && sum_res2 && sum_d2 && n_live && empty)));
+    PCREG_ARG(workspace_bytes >= refit_cpd_ws_bytes(Q, B, model->v.M));      // (host data of the handle: refused before the device, as the rest)
+    GUARD();
+    return launch_model_refit_cpd(model->v, q, Q, ldq, T_dev, B, sigma2_in, outlier, T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty,
+                                  workspace, workspace_bytes, (hipStream_t)stream);
+}
 size_t pcreg_dev_model_cluster_workspace(int M) { return cluster_ws_bytes(M); }
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -883,6 +895,53 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
     memcpy(n_close, hi, sizeof(int32_t) * nB);
     memcpy(n_pairs, hi + nB, sizeof(int32_t) * nB);
     memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
+    return PCREG_OK;
+}
+
+// B transforms refitted `steps` times by the coherent-point-drift step: one upload, `steps` device steps, one read.  A step's
+// result block is 21 B doubles' room -- T_out (16 B), sigma2_out, Np, sum_res2, sum_d2 (B each), then n_live and empty (B int32 each)
+// -- and two blocks alternate, so a step reads its transforms and its sigma2 from the block before it
+int pcreg_model_refit_cpd_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, const double* sigma2_in, double outlier,
+                              int steps, double* T_out, double* sigma2_out, double* Np, double* sum_res2, double* sum_d2, int32_t* n_live,
+                              int32_t* empty) {
+    PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && steps >= 1);
+    PCREG_ARG(outlier >= 0.0 && outlier < 1.0);                              // (a NaN fails both)
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T && sigma2_in && T_out && sigma2_out && Np && sum_res2 && sum_d2 && n_live && empty)));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    if (B == 0) return PCREG_OK;
+    Stage st{scratch()};
+    const ModelView& v = model->dm->v;
+    const size_t wsb = refit_cpd_ws_bytes(Q, B, v.M), nB = (size_t)B;
+    float* dq; double *dT, *dsig, *dout; char* ws;
+    TRY(st.take(3 * (size_t)Q, &dq));
+    TRY(st.take(16 * nB, &dT));
+    TRY(st.take(nB, &dsig));
+    TRY(st.take(2 * 21 * nB, &dout));
+    TRY(st.take(wsb, &ws));
+    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dsig, sigma2_in, sizeof(double) * nB, hipMemcpyHostToDevice, g_stream));
+    const double *in = dT, *sig = dsig;
+    double* blk = dout;
+    for (int s = 0; s < steps; ++s) {
+        blk = dout + (size_t)(s & 1) * 21 * nB;
+        int32_t* ib = (int32_t*)(blk + 20 * nB);
+        TRY(launch_model_refit_cpd(v, dq, Q, Q, in, B, sig, outlier, blk, nullptr, blk + 16 * nB, blk + 17 * nB, blk + 18 * nB, blk + 19 * nB, ib, ib + nB,
+                                   ws, wsb, g_stream));
+        in = blk; sig = blk + 16 * nB;
+    }
+    std::vector<double> host(21 * nB);
+    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 21 * nB, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    const int32_t* hi = (const int32_t*)(host.data() + 20 * nB);
+    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
+    memcpy(sigma2_out, host.data() + 16 * nB, sizeof(double) * nB);
+    memcpy(Np, host.data() + 17 * nB, sizeof(double) * nB);
+    memcpy(sum_res2, host.data() + 18 * nB, sizeof(double) * nB);
+    memcpy(sum_d2, host.data() + 19 * nB, sizeof(double) * nB);
+    memcpy(n_live, hi, sizeof(int32_t) * nB);
+    memcpy(empty, hi + nB, sizeof(int32_t) * nB);
     return PCREG_OK;
 }
 

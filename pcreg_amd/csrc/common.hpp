@@ -254,6 +254,13 @@ size_t refit_gicp_ws_bytes(int Q, int B, int M);
 int launch_model_refit_gicp(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                             const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
                             int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
+// one coherent-point-drift step of the same B transforms (cpd.hip, cpd_fit.hpp): every moved point against every live
+// model row, B Q M pairs; sigma2_in [B] on the device (0: the closed-form initial value), outlier in [0, 1); sum_d2 the scoring chain's
+// at r2 = +inf (the shift), n_live the queries whose moved point is finite.  T_step may be null; T_out may not alias T_dev
+size_t refit_cpd_ws_bytes(int Q, int B, int M);
+int launch_model_refit_cpd(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, const double* sigma2_in, double outlier,
+                           double* T_out, double* T_step, double* sigma2_out, double* Np, double* sum_res2, double* sum_d2, int32_t* n_live,
+                           int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
 // connected components of "distance <= r2" over the model's own rows (knn_cluster.hip): walk + union-find, flatten, number
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,

@@ -321,6 +321,59 @@ class PreparedModel:
                     src = dst
         return T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty
 
+    def refit_cpd(self, q_soa: torch.Tensor, T_dev: torch.Tensor, sigma2=0.0, outlier: float = 0.1, steps: int = 1, out=None):
+        """B transforms refitted by the coherent-point-drift step (rigid CPD), `steps` times over, on torch's current stream
+        (pcreg_dev_model_refit_cpd_f32 once per step, a step's T_out and sigma2_out the next one's inputs, no host
+        synchronisation in between; the contract is pcreg_model_refit_cpd_f32's): q_soa and T_dev as refit_transforms takes them;
+        sigma2 a number or a [B] float64 tensor on the queries' device, 0 asking for the closed-form initial variance; outlier
+        in [0, 1).  The cost is B * Q * M pairs a step: for downsampled clouds.  -> (T_out [B, 16], T_step [B, 16], sigma2_out [B]
+        float64, Np [B] float64, sum_res2 [B] float64, sum_d2 [B] float64, n_live [B] int32, empty [B] int32), the sums and
+        counts for the transform that went INTO the last step.  Nothing given is written.  The workspace and the second
+        transform block are cached on the model; calls that may overlap on two streams pass buffers of their own,
+        out=(T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty, ws, T_tmp) with ws of
+        pcreg_dev_model_refit_cpd_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
+            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        M, Q = self.M, int(q_soa.shape[1])
+        steps, outlier = int(steps), float(outlier)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if not 0.0 <= outlier < 1.0:
+            raise ValueError(f"outlier must lie in [0, 1), got {outlier}")
+        dev, B = q_soa.device, T_dev.numel() // 16
+        if isinstance(sigma2, torch.Tensor):
+            if sigma2.dtype != torch.float64 or not sigma2.is_contiguous() or sigma2.numel() != B or sigma2.device != dev:
+                raise TypeError("sigma2 is a number or a contiguous float64 tensor of B numbers on the queries' device")
+            sig = sigma2
+        else:
+            sig = torch.full((max(B, 1),), float(sigma2), dtype=torch.float64, device=dev)
+        need = max(int(lib().pcreg_dev_model_refit_cpd_workspace(Q, B, M)), 256)
+        if out is not None:
+            T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty, ws, T_tmp = out
+            if steps > 1 and T_tmp is None:
+                raise ValueError("more than one step needs the second transform block, T_tmp")
+        else:
+            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
+            sigma2_out, Np, sum_res2, sum_d2 = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(4))
+            n_live, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
+            ws = getattr(self, "_refit_cpd_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._refit_cpd_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if B:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                src = T_dev
+                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
+                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
+                    check(lib().pcreg_dev_model_refit_cpd_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B,
+                                                              _p(sig), outlier, _p(dst), _p(T_step), _p(sigma2_out), _p(Np), _p(sum_res2), _p(sum_d2),
+                                                              _p(n_live), _p(empty), _p(ws), ws.numel(), _stream()))
+                    src, sig = dst, sigma2_out         # (sigma2_out may alias sigma2_in: a step reads it before its last kernel writes it)
+        return T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty
+
     def cluster(self, r2: float, out=None):
         """clusterPoints(model, r) over the model's own rows with r2 = r^2, on torch's current stream
         (pcreg_dev_model_cluster_f32): -> (label [M] int32, the 0-based cluster of every row; n_clusters [1] int32; first [M]

@@ -522,7 +522,7 @@ def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, 
 
 
 def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None, ndt=None,
-                  neighbors: int = 1, outlier_ratio: float = 0.55, surface_normals=None, epsilon: float = 1e-3):
+                  neighbors: int = 1, outlier_ratio: float = 0.55, surface_normals=None, epsilon: float = 1e-3, cpd=None):
     """Every trial of a sweep's result refitted on the dense clouds (PreparedModel.refit_transforms): completeExperimentFast.m:383-394's
     T_refine with the dense surface ([3, Q] float32) and the prepared dense model in the place of a cluster's re-matched
     keypoints, `steps` times over.  The orientation is score_trials': invertTF(transforms[t]) puts the surface on the model and
@@ -534,7 +534,10 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
     outputs, a trial whose planes give no fit None.  normals and surface_normals (the [3, Q] tensor PreparedModel.normals returns for a
     model made of the surface): the steps are plane-to-plane steps (PreparedModel.refit_gicp with `epsilon`) instead.  ndt (a device.NdtModel of the dense model): the steps are NDT steps
     (NdtModel.refit with `neighbors` and `outlier_ratio`) instead -- no nearest-row search, so model and max_dist are not used and
-    may be None; the same orientation; the summary is then dict(n_pairs, sum_e) of the last step, a trial without a fit None."""
+    may be None; the same orientation; the summary is then dict(n_pairs, sum_e) of the last step, a trial without a fit None.
+    cpd (a dict(sigma2=, outlier=), either key optional: PreparedModel.refit_cpd's defaults): the steps are coherent-point-drift
+    steps instead -- every surface point softly against every model row, so max_dist is not used and may be None; the same
+    orientation; the summary is then dict(sigma2, Np, sum_res2, sum_d2, n_live) of the last step, a trial without a fit None."""
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
     Q, n = int(surface_soa.shape[1]), len(tf)
     if n == 0:
@@ -547,6 +550,16 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
         gone = both[35 * n:] != 0
         out = [None if gone[t] else invertTF(np.ascontiguousarray(mats[t])) for t in range(n)]
         return out, dict(n_pairs=both[34 * n:35 * n].copy(), sum_e=both[32 * n:34 * n].view(np.float64).copy())
+    if cpd is not None:
+        T_out, _step, sig, Np, res2, sum_d2, n_live, empty = model.refit_cpd(surface_soa, T_dev, sigma2=cpd.get("sigma2", 0.0),
+                                                                            outlier=cpd.get("outlier", 0.1), steps=steps)
+        both = torch.cat([T_out.reshape(-1).view(torch.int32), sig.view(torch.int32), Np.view(torch.int32), res2.view(torch.int32),
+                          sum_d2.view(torch.int32), n_live, empty]).cpu().numpy()
+        mats = both[:32 * n].view(np.float64).reshape(n, 4, 4).transpose(0, 2, 1)
+        gone = both[41 * n:] != 0
+        out = [None if gone[t] else invertTF(np.ascontiguousarray(mats[t])) for t in range(n)]
+        f64 = lambda k: both[(32 + 2 * k) * n:(34 + 2 * k) * n].view(np.float64).copy()
+        return out, dict(sigma2=f64(0), Np=f64(1), sum_res2=f64(2), sum_d2=f64(3), n_live=both[40 * n:41 * n].copy())
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
     if normals is None:
         T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
