@@ -94,7 +94,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * cell range from their ordering-grid cells; while "knn_stats" is on every query takes the walk as well, because those counters
  * are defined over the walk of the whole query set), "knn_direct_stats" (counters for pcreg_debug_knn_direct_stats; it forces
  * nothing), "knn_seed_fused" (1: the two-nearest search seeds and answers directly in two launches instead of one; same
- * bits); value 0
+ * bits), "ransac_bhand" (1: the staged RANSAC chain's bounded second pass walks every refit to its stop instead of handing
+ * the refits still undecided after a few blocks to its block-parallel finish; same bits); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -123,6 +124,11 @@ int  pcreg_debug_knn_direct_stats(long long out[3], int reset);
  * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
  * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */
 int  pcreg_debug_ransac_stats(long long out[3], int reset);
+/* With pcreg_debug_set("ransac_stats", 1): the handover of the bounded second pass summed over the calls since the
+ * last reset -- out[0] refits handed over to the finish, [1] (refit, 512-correspondence block) units the finish scored (they
+ * are part of pcreg_debug_ransac_stats' out[1] as well).  out[2] is no counter: the number of blocks a refit is walked before
+ * it is handed over, whether or not the key is on.  Resets its two counters only; the read synchronises the device. */
+int  pcreg_debug_ransac_handover(long long out[3], int reset);
 /* With pcreg_debug_set("cluster_stats", 1): the counters of the clustering walk summed over the calls since the last reset --
  * out[0] calls, [1] hits (scored row pairs within the radius), [2] compare-and-swap attempts on the union-find, [3] attempts
  * that failed (another lane had merged first).  Off: no extra work.  The read synchronises the device.  (The walk's visited and

@@ -52,7 +52,7 @@ class DevRansacResult(C.Structure):
 # every symbol include/pcreg.h declares (tests/test_abi.py checks the two lists agree)
 SYMBOLS = [
     "pcreg_last_error", "pcreg_version", "pcreg_device_count", "pcreg_set_device", "pcreg_device_name", "pcreg_debug_set", "pcreg_debug_match_stats",
-    "pcreg_debug_knn_stats", "pcreg_debug_knn_unit_stats", "pcreg_debug_knn_direct_stats", "pcreg_debug_ransac_stats", "pcreg_debug_cluster_stats", "pcreg_debug_desc_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
+    "pcreg_debug_knn_stats", "pcreg_debug_knn_unit_stats", "pcreg_debug_knn_direct_stats", "pcreg_debug_ransac_stats", "pcreg_debug_ransac_handover", "pcreg_debug_cluster_stats", "pcreg_debug_desc_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
     "pcreg_estimate_transform", "pcreg_calc_dists", "pcreg_ransac", "pcreg_ransac_batched",
     "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
     "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_size", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
@@ -259,6 +259,7 @@ def lib() -> C.CDLL:
                            ("pcreg_debug_knn_unit_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_knn_direct_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_ransac_stats", [C.POINTER(C.c_longlong), C.c_int]),
+                           ("pcreg_debug_ransac_handover", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_desc_stats", [C.POINTER(C.c_longlong), C.c_int]),
                            ("pcreg_debug_dev_model_export", [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),
                            ("pcreg_debug_search_export", [C.c_void_p, C.c_size_t, C.c_int, C.c_int] + [C.c_void_p] * 3)):

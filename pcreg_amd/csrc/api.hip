@@ -84,7 +84,7 @@ static std::atomic<int> g_debug[kDbgCount];
 int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); }
 // one block of device counters behind a debug key: allocated (zeroed) at the first use while the key is on
 struct Counters { DebugKey key; int n; unsigned long long* dev; };
-static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 6, nullptr}, g_ransac_stats{kDbgRansacStats, 3, nullptr},
+static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 6, nullptr}, g_ransac_stats{kDbgRansacStats, 5, nullptr},
                 g_cluster_stats{kDbgClusterStats, 4, nullptr}, g_desc_stats{kDbgDescStats, 10, nullptr},
                 g_knn_direct_stats{kDbgKnnDirectStats, 3, nullptr};
 static unsigned long long* counters_dev(Counters& c) {
@@ -130,7 +130,9 @@ int pcreg_debug_set(const char* key, int value) {
                                                         // are defined over the walk of the whole query set.  "knn_direct_stats" only counts.
                                                         // "knn_seed_fused": 0 (the default) seeds and answers directly in one launch, 1 in
                                                         // two (same bits: the A/B of one binary).
-                                                        "knn_direct", "knn_direct_stats", "knn_seed_fused"};
+                                                        // "ransac_bhand": 0 (the default) hands the bounded second pass's long walks to
+                                                        // its block-parallel finish, 1 walks every refit to its stop (same bits).
+                                                        "knn_direct", "knn_direct_stats", "knn_seed_fused", "ransac_bhand"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -142,7 +144,12 @@ int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counter
 int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 0, 4); }
 int pcreg_debug_knn_unit_stats(long long out[2], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 4, 2); }
 int pcreg_debug_knn_direct_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_knn_direct_stats, out, reset); }
-int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset); }
+int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset, 0, 3); }
+int pcreg_debug_ransac_handover(long long out[3], int reset) {
+    TRY(pcreg::counters_read(pcreg::g_ransac_stats, out, reset, 3, 2));
+    out[2] = pcreg::ransac_handover_blocks();
+    return PCREG_OK;
+}
 int pcreg_debug_cluster_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_cluster_stats, out, reset); }
 int pcreg_debug_desc_stats(long long out[10], int reset) {     // (a read stages 8 words: the last two with a second one)
     PCREG_ARG(out != nullptr);

@@ -101,6 +101,8 @@ enum DebugKey {
     kDbgKnnDirectStats,        // "knn_direct_stats": the direct answers are counted (pcreg_debug_knn_direct_stats); forces nothing
     kDbgKnnSeedFused,          // "knn_seed_fused": 0 = seeding and the direct answers are one launch (seed_direct_kernel), 1 = two launches
                                // (seed_query_kernel, knn_direct_kernel); same bits
+    kDbgRansacBHand,           // "ransac_bhand": 0 = the bounded second pass hands the refits still undecided after kBHand blocks to its
+                               // block-parallel finish (rs_bfinish_kernel), 1 = it walks every refit to its stop; same bits
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -118,6 +120,7 @@ unsigned long long* knn_stats_dev();
 unsigned long long* knn_direct_stats_dev();
 // Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
 //   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
+//   [3] refits handed over to the finish   [4] units the finish scored, also part of [1] (pcreg_debug_ransac_handover reads [3], [4])
 unsigned long long* ransac_stats_dev();
 // Device counters of the clustering walk (knn_cluster.hip), or null while "cluster_stats" is off:
 //   [0] calls   [1] hits   [2] compare-and-swap attempts   [3] failed attempts
@@ -166,6 +169,7 @@ static int upload_cols(const T* host, int n, int ld, int cols, T* dev, hipStream
 struct RansacDims { int n_cap; int iters; int B; };
 
 size_t ransac_workspace_bytes(int iters, int B, int n_cap);
+int ransac_handover_blocks();      // kBHand: blocks the bounded second pass walks before it hands over
 int launch_ransac(const double* p1, const double* p2, int ld, const int32_t* offsets /*B+1 dev or null*/,
                   const int32_t* n_dev /*single registration: device n, or null*/, int n_cap, int B,
                   const pcreg_ransac_opts& o, const int32_t* sample_idx_dev,

@@ -1013,13 +1013,30 @@ constexpr int kRec = 16;                        // doubles per correspondence re
 constexpr int kSChunk = PCREG_SCHUNK;                     // hypotheses per workgroup
 // bounded second pass (rs_bounded_kernel): decision blocks of kSS * 64 correspondences, up to kBSeeds refits scored
 // in full first, kBBuckets residual buckets for the pass's order
-constexpr int kBBlk = kSS * 64, kBSeeds = 64, kBBuckets = 16, kBChunk = 4;
+#ifndef PCREG_BCHUNK
+#define PCREG_BCHUNK 4
+#endif
+#ifndef PCREG_BHAND
+#define PCREG_BHAND 8
+#endif
+constexpr int kBBlk = kSS * 64, kBSeeds = 64, kBBuckets = 16, kBChunk = PCREG_BCHUNK;
+// blocks a chunk of rs_bounded_kernel walks before it hands its undecided refits to rs_bfinish_kernel; a multiple of 4 (the finish
+// works in workgroups of kSPts rows).  Measured choice among 4, 8, 12, 16: docs/BENCH_NOTES.md, 2026-10-21
+constexpr int kBHand = PCREG_BHAND;
+static_assert(kBHand % (kSPts / kBBlk) == 0, "the finish starts at a workgroup's first row");
+// the finish: listed refits per workgroup and trip (shorter chunks than the scoring passes' kSChunk: the list is short, and the
+// cold fp32 rows want many waves per SIMD behind them), workgroups of its grid (each takes every gridDim.y-th chunk)
+constexpr int kBFChunk = 8, kBFGrid = 4096;
 struct BCtr {
     int32_t lb;                  // largest exact refit count known so far (atomic max; only grows)
     int32_t hstar;               // the refit whose residuals order the pass (first maximum of cnt1 among the refits)
     int32_t hist[kBBuckets], cursor[kBBuckets];
     int32_t seed_cnt[kBSeeds];   // exact counts of the seed refits (summed over the point blocks)
-    unsigned long long stats[3]; // this call's counters in ransac_stats_dev()'s layout (EXPERIMENTS print)
+    unsigned long long stats[5]; // this call's counters in ransac_stats_dev()'s layout (EXPERIMENTS print)
+    int32_t n_rest;              // refits handed over to rs_bfinish_kernel: the used length of blist / T32c
+#ifdef PCREG_EXPERIMENTS
+    int32_t stop_hist[64];       // refits by the block after which their walk ended (the last bin: that block or later; PCREG_RANSAC_DEBUG print)
+#endif
     int32_t seed_h[kBSeeds];     // the seed refits (-1: none); written every call
 };
 constexpr int kBCtrClearWords = (int)(offsetof(BCtr, seed_h) / 4);
@@ -1066,9 +1083,15 @@ struct StagedArgs {
     int32_t* perm;               // [n32]
     unsigned char* bkt;          // [n32]
     void* bctr;                  // BCtr
+    // the handover (rs_bounded_kernel -> rs_bfinish_kernel): the refits still undecided after kBHand blocks, in arrival order
+    int32_t* blist;              // [iters] their indices (the bytes of pass_list, dead by then: ransac_ws_layout)
+    float* T32c;                 // [iters][16] their fp32 rows (T32b's, in list order: the finish prefetches them as it walks the
+                                 // list; the bytes of T32a, dead by then)
 #ifdef PCREG_EXPERIMENTS
     int noband;                  // PCREG_RANSAC_NOBAND=1, TIMING ONLY (wrong counts): the screen's band branch never runs -- what the
                                  // fp64 re-scores cost in rs_score32 / rs_bprep / rs_bounded is the difference to a run without it
+    int bhist;                   // PCREG_RANSAC_DEBUG=1: rs_bounded_kernel counts its refits by the block their walk ended after
+                                 // (10^4 atomics on a few words: it slows the kernel, so only the print's runs take it)
 #endif
 };
 #ifdef PCREG_EXPERIMENTS
@@ -1464,36 +1487,48 @@ __device__ __forceinline__ float sqdist32(const float (&p)[6], const float (&T)[
 // both ballots: 119 instructions and a dependent round trip per trip, eight trips a hit, against 72 per band slot now
 // (172.9 -> 151.9 us per pass at the benchmark's shape; with the band branch compiled out, PCREG_RANSAC_NOBAND, 148.5).
 // The fp32 row's SGPRs are dead inside the loop, so T64's scalar load reuses them (SGPR spills 31 -> 8).
+// The body of two kernels.  LIST = false, rs_score32_kernel: hypotheses [0, iters) with their `valid` flags over all rows of
+// sa.c32.  LIST = true, rs_bfinish_kernel (the bounded pass's finish, below): the slots [0, n_rest) of the handover list -- row k
+// of T32 belongs to refit blist[k], every one of them exists -- over the rows at positions [row0, n) of the permuted copy
+// sa.p32; only cold code differs (the ranges, the band branch's fp64 transform and raw rows, the epilogue's index).  units
+// (LIST, null: off): [1], [4] += the (refit, 512 rows) units scored.
 typedef int rs_i32x16 __attribute__((ext_vector_type(16)));
-template <bool EMIT>
-__global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, const double* __restrict__ TT,
-                                                              const float* __restrict__ T32,
-                                                              const unsigned char* __restrict__ valid,
-                                                              int32_t* __restrict__ acc /* null: this block's row of partial counts; else counts are ADDED to acc[h] (integers: order-free) */) {
+template <bool EMIT, bool LIST, int CH>
+__device__ __forceinline__ void rs_score32_body(const StagedArgs& sa, const double* __restrict__ TT, const float* __restrict__ T32,
+                                                const unsigned char* __restrict__ valid, int32_t* __restrict__ acc,
+                                                const int row0, unsigned long long* __restrict__ units) {
+    static_assert(!(EMIT && LIST), "the finish keeps no masks");
     const RansacArgs& a = sa.a;
-    __shared__ int s_cnt[kSW][kSChunk];
+    __shared__ int s_cnt[kSW][CH];
     const int n = staged_n(a);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h0 = blockIdx.y * kSChunk, h1 = min(a.iters, h0 + kSChunk);
+    const int n_h = LIST ? min(((const BCtr*)sa.bctr)->n_rest, a.iters) : a.iters;
+    if (LIST && ((int)blockIdx.y * CH >= n_h || row0 + (int)blockIdx.x * kSPts >= n)) return;      // (workgroup-uniform) past the list's end, or past n
+    const float* __restrict__ x32 = LIST ? sa.p32 : sa.c32;
     const double th = a.thDist;
-    for (int hl = threadIdx.x; hl < kSW * kSChunk; hl += kSW * 64) (&s_cnt[0][0])[hl] = 0;
-    unsigned long long vmask[(kSChunk + 63) / 64];
+    // one chunk of CH hypotheses per workgroup; the finish's grid cannot follow the list's length, so there a workgroup takes
+    // every gridDim.y-th chunk of the list
+    for (int h0 = blockIdx.y * CH;; h0 += gridDim.y * CH) {
+    const int h1 = min(n_h, h0 + CH);
+    for (int hl = threadIdx.x; hl < kSW * CH; hl += kSW * 64) (&s_cnt[0][0])[hl] = 0;
+    unsigned long long vmask[(CH + 63) / 64];
 #pragma unroll
-    for (int k = 0; k < (kSChunk + 63) / 64; ++k) {
+    for (int k = 0; k < (CH + 63) / 64; ++k) {
         const int h = h0 + k * 64 + lane;
-        vmask[k] = __ballot(h < h1 && k * 64 + lane < kSChunk && valid[h] != 0);
+        vmask[k] = __ballot(h < h1 && k * 64 + lane < CH && (LIST || valid[h] != 0));
     }
     __syncthreads();
-    for (int pb = blockIdx.x; pb * kSPts < n; pb += gridDim.x) {       // normally one trip
+    for (int pb = blockIdx.x; row0 + pb * kSPts < n; pb += gridDim.x) {       // normally one trip
         float q[kSS][6];
-        const int ibase = pb * kSPts + wave * kSS * 64 + lane;
+        const int ibase = row0 + pb * kSPts + wave * kSS * 64 + lane;
+        if (LIST && units && lane == 0 && ibase < n) { atomicAdd(&units[1], (unsigned long long)(h1 - h0)); atomicAdd(&units[4], (unsigned long long)(h1 - h0)); }
 #pragma unroll
         for (int s = 0; s < kSS; ++s) {
             const int i = ibase + s * 64;
             const bool act = i < n;
             const int ii = act ? i : 0;
 #pragma unroll
-            for (int c = 0; c < 6; ++c) q[s][c] = sa.c32[(size_t)c * sa.n32 + ii];
+            for (int c = 0; c < 6; ++c) q[s][c] = x32[(size_t)c * sa.n32 + ii];
             // a lane past the end scores NaN: neither screen test holds for it, so the hot loop carries no activity masks
             if (!act) q[s][0] = __builtin_nanf("");
         }
@@ -1517,12 +1552,13 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
             }                                                                                                      \
             if (band != 0u && !PCREG_NOBAND(sa)) {      /* 5 % of the (hypothesis, 512 correspondences) units on the benchmark: the SLOTS with somebody in */ \
                 double T64[12];      /* the band (one in 180) again, fp64 on the raw coordinates.  The screen's own ballots say which slots: bit s of */ \
-                _Pragma("unroll") for (int k = 0; k < 12; ++k) T64[k] = TT[(size_t)(H) * 12 + k];   /* `band`.  The loop walks the set bits only, rolled */ \
+                const int ht_ = LIST ? sa.blist[(H)] : (H);                                                        \
+                _Pragma("unroll") for (int k = 0; k < 12; ++k) T64[k] = TT[(size_t)ht_ * 12 + k];   /* `band`.  The loop walks the set bits only, rolled */ \
                 _Pragma("unroll 1") for (unsigned m = band; m != 0u; m &= m - 1u) {    /* (unrolled, its eight branches pushed the kernel from 75 to  */ \
                     const int s = __builtin_ctz(m);                      /* 171 VGPRs); a trip needs nothing of the slot's fp32 row: six fp64 loads in */ \
                     const int i = ibase + s * 64;                        /* one round trip, one sqdist, one ballot                                      */ \
                     const bool act = i < n;                                                                        \
-                    const int ii = act ? i : 0;                                                                    \
+                    const int ii = LIST ? sa.perm[act ? i : 0] : act ? i : 0;                                      \
                     double p[6];                                                                                   \
                     _Pragma("unroll") for (int c = 0; c < 3; ++c) { p[c] = a.p1[ii + (size_t)c * a.ld]; p[3 + c] = a.p2[ii + (size_t)c * a.ld]; } \
                     const unsigned long long bb = __ballot((sqdist(p, T64) < th) & act);                           \
@@ -1549,6 +1585,7 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
         // wait, along every path, for an instruction that touches the destination SGPRs).
         PCREG_ROW_LOAD(RA, h0)
         PCREG_ROW_WAIT(RA);
+#pragma unroll 1                 // (rolled whatever CH: two row sets, two loads and two waits in the emitted code)
         for (int h = h0; h < h1; h += 2) {
             PCREG_ROW_LOAD(RB, h + 1)
             PCREG_SCORE_HYP(h, RA)
@@ -1565,8 +1602,19 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
         int c = 0;
 #pragma unroll
         for (int w = 0; w < kSW; ++w) c += s_cnt[w][hl];
-        if (acc) { if (c) atomicAdd(&acc[h0 + hl], c); } else sa.part[(size_t)blockIdx.x * a.iters + h0 + hl] = c;
+        if (LIST) { if (c) atomicAdd(&acc[sa.blist[h0 + hl]], c); }
+        else if (acc) { if (c) atomicAdd(&acc[h0 + hl], c); } else sa.part[(size_t)blockIdx.x * a.iters + h0 + hl] = c;
     }
+    if (!LIST || h0 + (int)gridDim.y * CH >= n_h) break;
+    __syncthreads();                 // the sums above have read s_cnt before the next chunk clears it
+    }
+}
+template <bool EMIT>
+__global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, const double* __restrict__ TT,
+                                                              const float* __restrict__ T32,
+                                                              const unsigned char* __restrict__ valid,
+                                                              int32_t* __restrict__ acc /* null: this block's row of partial counts; else counts are ADDED to acc[h] (integers: order-free) */) {
+    rs_score32_body<EMIT, false, kSChunk>(sa, TT, T32, valid, acc, 0, nullptr);
 }
 
 // ---- bounded second pass --------------------------------------------------------------------------------------
@@ -1577,9 +1625,16 @@ __global__ __launch_bounds__(kSW * 64) void rs_score32_kernel(StagedArgs sa, con
 //   in >= thInlr  /  out > n - thInlr  ->  it succeeds / fails.
 // Once "cannot win" and one of the other two hold, the rest of its scan decides nothing: it stores thInlr (success) or 0
 // (failure), which the selection counts right and, both being below the maximum, never picks.  A refit with cnt2 >= LB -- the
-// maximum and every tie of it -- never meets out > n - LB, scans to the end and stores its exact count.  LB only grows and every
-// value it takes is an exact count, so a stale read only stops refits later.
-// Three launches: rs_bprep (seed refits scored in full + order buckets), rs_bscatter (the permuted copy), rs_bounded.
+// maximum and every tie of it -- never meets out > n - LB, is scanned to the end and stores its exact count.  LB only grows and
+// every value it takes is an exact count, so a stale read only stops refits later.
+// The rule is applied over the first kBHand blocks only: one wave walks a chunk's blocks one after another, and a refit near the
+// maximum would keep it walking all n / 512 of them while most of the chip idles.  What is still undecided after block
+// kBHand - 1 is HANDED OVER: its index and fp32 row go to the next free slot of a list, cnt2 gets its count so far, and
+// rs_bfinish_kernel adds the exact count of the remaining rows, block-parallel over the whole chip.  A refit that would have
+// stopped at a later block b now stores its exact count c instead of thInlr or 0; where it would have stopped, out > n - LB,
+// so c <= n - out < LB <= max, and c >= thInlr exactly when it succeeds: numSuccess, the maximum and the first index that
+// reaches it are unchanged, and the refits with c >= LB get the count they got from the walk.
+// Four launches: rs_bprep (seed refits scored in full + order buckets), rs_bscatter (the permuted copy), rs_bounded, rs_bfinish.
 
 // inliers of refit h among the kBBlk correspondences at positions [base, base + kBBlk) of an order (x32: the fp32 centred copy
 // in that order; perm: the original index of each position, null = identity): rs_score32_kernel's screen and its fp64
@@ -1776,10 +1831,14 @@ __global__ __launch_bounds__(256) void rs_bscatter_kernel(StagedArgs sa) {
 
 // One wave per chunk of C refits (lane j: refit h0 + j's fp32 row and inlier count), walking the blocks of the permuted order;
 // the block's rows are loaded once for all the chunk's live refits, the next block's while this one is scored.  Between blocks
-// the decision rule above, lane-parallel.  Seed refits store their exact counts from rs_bprep.  stats (null: off): passes, units
-// scanned (seed refits included), units of a full pass, added up (ransac_stats_dev()).
+// the decision rule above, lane-parallel.  Seed refits store their exact counts from rs_bprep.  bhand > 0 and more than bhand
+// blocks: the walk ends after block bhand - 1 and the refits still active are handed over (slot = the list's length so far +
+// the lane's rank among the active lanes; the list's order is arrival order and decides nothing: the finish adds integers);
+// such a wave publishes no LB, its counts being partial.  bhand = 0 ("ransac_bhand" 1) or at most bhand blocks: every refit is
+// walked to its stop or to the end, as before 2026-10-21.  stats (null: off): passes, units scanned (seed refits included; the
+// finish adds its own), units of a full pass, [3] refits handed over, added up (ransac_stats_dev()).
 template <int C>
-__global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned long long* __restrict__ stats) {
+__global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned long long* __restrict__ stats, const int bhand) {
     static_assert(C >= 1 && C <= 64, "one lane per refit");
     const RansacArgs& a = sa.a;
     BCtr* bc = (BCtr*)sa.bctr;
@@ -1789,6 +1848,8 @@ __global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned 
     const int h0 = blockIdx.x * C, hl = h0 + lane;
     const bool mine = lane < C && hl < a.iters;
     const int nb = (n + kBBlk - 1) / kBBlk;
+    const bool hand = bhand > 0 && nb > bhand;
+    const int nbw = hand ? bhand : nb;                   // blocks this wave walks
     const int sh = bc->seed_h[lane], sc = bc->seed_cnt[lane];
     int lb = sh >= 0 ? sc : 0;
 #pragma unroll
@@ -1814,7 +1875,7 @@ __global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned 
     // it was issued (lbr[0] / lbr[1] alternate with the blocks), so its latency hides behind the scoring
     int lbr0 = lb, lbr1 = lb;
     auto step = [&](int blk, const float (&cur)[kSS][6], float (&nxt)[kSS][6], int& lbr) {
-        if (blk + 1 < nb) rs_load_block(sa, sa.p32, (blk + 1) * kBBlk, n, nxt);
+        if (blk + 1 < nbw) rs_load_block(sa, sa.p32, (blk + 1) * kBBlk, n, nxt);
         const int base = blk * kBBlk;
         for (unsigned long long m = active; m != 0ull; m &= m - 1ull) {
             const int j = __builtin_ctzll(m);
@@ -1832,14 +1893,37 @@ __global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned 
         const int out_v = min(n, base + kBBlk) - in_v;
         const bool stop = ((active >> lane) & 1ull) && out_v > n - lb && (in_v >= thInlr || out_v > n - thInlr);
         if (stop) a.cnt2[hl] = in_v >= thInlr ? thInlr : 0;
+#ifdef PCREG_EXPERIMENTS
+        if (stop && sa.bhist) atomicAdd(&bc->stop_hist[min(blk, 63)], 1);
+#endif
         active &= ~__ballot(stop);
     };
-    for (int blk = 0; blk < nb && active != 0ull; blk += 2) {
+    for (int blk = 0; blk < nbw && active != 0ull; blk += 2) {
         step(blk, qa, qb, lbr0);
-        if (blk + 1 < nb && active != 0ull) step(blk + 1, qb, qa, lbr1);
+        if (blk + 1 < nbw && active != 0ull) step(blk + 1, qb, qa, lbr1);
+    }
+    if (hand && active != 0ull) {                        // (wave-uniform) the handover
+        const int na = __popcll(active);
+        int slot = 0;
+        if (lane == 0) slot = atomicAdd(&bc->n_rest, na);
+        slot = __shfl(slot, 0) + __popcll(active & ((1ull << lane) - 1ull));
+        if (((active >> lane) & 1ull) && slot < a.iters) {         // (always: at most one slot per refit)
+            sa.blist[slot] = hl;
+            float4* row = (float4*)(sa.T32c + (size_t)slot * 16);
+            row[0] = make_float4(comp[0], comp[1], comp[2], comp[3]);
+            row[1] = make_float4(comp[4], comp[5], comp[6], comp[7]);
+            row[2] = make_float4(comp[8], comp[9], comp[10], comp[11]);
+            row[3] = make_float4(comp[12], comp[13], 0.0f, 0.0f);
+            a.cnt2[hl] = in_v;                           // the first bhand blocks' exact count; the finish adds the rest's
+        }
+        if (stats && lane == 0) atomicAdd(&stats[3], (unsigned long long)na);
+        active = 0ull;
     }
     const bool full = (active >> lane) & 1ull;           // scanned to the end: the exact count
     if (full) a.cnt2[hl] = in_v;
+#ifdef PCREG_EXPERIMENTS
+    if (full && sa.bhist) atomicAdd(&bc->stop_hist[min(nb - 1, 63)], 1);
+#endif
     int mx = full ? in_v : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
@@ -1849,6 +1933,17 @@ __global__ __launch_bounds__(64) void rs_bounded_kernel(StagedArgs sa, unsigned 
         atomicAdd(&stats[1], units + (unsigned long long)__popcll(seeded) * (unsigned long long)nb);
         atomicAdd(&stats[2], (unsigned long long)__popcll(exist) * (unsigned long long)nb);
     }
+}
+
+// The finish of the bounded pass: the handed-over refits' counts over the rows the walk left, rs_score32_kernel's body with the
+// list as its hypotheses (one wave keeps 512 rows in registers and walks a chunk of the list).  The grid is sized from the
+// capacities (x: workgroups of kSPts rows behind row bhand * kBBlk, y: about kBFGrid workgroups in all, each walking every
+// gridDim.y-th chunk of CH list slots); a workgroup past the list's end or past n returns after reading those two words.
+// stats (null: off): [1], [4] += the units scored.  Five waves per SIMD asked for: the body under its chunk loop comes to 97
+// VGPRs, one more than five waves allow, and the cold fp32 rows need the waves (96 VGPRs, no scratch; six would spill).
+template <int CH>
+__global__ __launch_bounds__(kSW * 64) __attribute__((amdgpu_waves_per_eu(5, 5))) void rs_bfinish_kernel(StagedArgs sa, unsigned long long* __restrict__ stats, const int bhand) {
+    rs_score32_body<false, true, CH>(sa, (const double*)sa.a.TF, (const float*)sa.T32c, nullptr, sa.a.cnt2, bhand * kBBlk, stats);
 }
 
 // ================================================================ hypothesis kernel, fp32-screened (LDS-resident)
@@ -3290,9 +3385,12 @@ __global__ void calc_dists_kernel(const double* T16, const double* p1, const dou
 // 0.149 / 0.158 / 0.169 staged; (4000, 10^3) 0.099 against 0.119, (2500, 2 x 10^3) 0.079 against 0.114.
 static bool staged_pays(int n_cap, int iters) { return n_cap >= 4096 || (n_cap >= kStagedMinN && (long long)n_cap * iters >= 20000000LL); }
 // The bounded second pass pays where the full pass's work (n x iterNum pair scores, ~2.4 per ps on one idle MI355X) exceeds
-// the bounded pass's floor: a refit near the maximum walks all n / 512 blocks one after another in one wave (~1.4 us each), plus
-// ~30 us of seeding, ordering and launches.  Both measured at the bench's shape (n 32558, iterNum 10^4: 135 against 120 us) and
-// at the shapes of DESIGN 4.9's table; 10 % margin.
+// the bounded pass's floor.  The floor was written for the walk before the handover: a refit near the maximum walked all n / 512
+// blocks one after another in one wave (~1.4 us each), plus ~30 us of seeding, ordering and launches.  With the handover the
+// long walks are gone, but not the shape dependence: the seeds are scored in full (64 x n), every refit is walked over kBHand
+// blocks by one-wave workgroups at well under the full pass's rate, and the finish is a full pass over what is handed over.
+// Re-measured on 2026-10-21 at the seven shapes of DESIGN 4.9's table (full forced / bounded forced / default): the bounded side
+// wins by the 10 % margin at none of the six shapes this gate keeps on the full pass, so the gate stays where it was.
 static bool bounded_pays(int n_cap, int iters) {
     const double full_us = (double)n_cap * (double)iters / 2.4e6, bounded_us = 1.4 * (double)((n_cap + kBBlk - 1) / kBBlk) + 30.0;
     return full_us > 1.1 * bounded_us;
@@ -3336,9 +3434,14 @@ static RansacWs ransac_ws_layout(int iters, int B, int n_cap, void* base, size_t
         sa.perm = w.take<int32_t>((size_t)sa.n32);
         sa.bkt = w.take<unsigned char>((size_t)sa.n32);
         sa.bctr = w.take_bytes(align_up(sizeof(BCtr), 256));
+        // the handover list of the bounded pass takes no bytes of its own: by the time rs_bounded_kernel writes it the refit list
+        // (rs_pass1 -> rs_moments_mfma) and the sample fits' fp32 rows (rs_stage2 -> scoring pass 1) have had their last reader,
+        // and both are rewritten by the next call before anything reads them
+        sa.blist = sa.pass_list; sa.T32c = sa.T32a;
     }
     *bytes = w.bytes(); return s;
 }
+int ransac_handover_blocks() { return kBHand; }
 size_t ransac_workspace_bytes(int iters, int B, int n_cap) { size_t b; (void)ransac_ws_layout(iters, B, n_cap, nullptr, &b); return b; }
 
 // ransac_hyp32_kernel: launch classes by correspondences per registration (LDS = 72 B per correspondence, rounded up to 128 of
@@ -3422,6 +3525,7 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         sa.use_f32 = !debug_flag(kDbgRansacF64Score);
 #ifdef PCREG_EXPERIMENTS
         sa.noband = PCREG_EXP_ENV("PCREG_RANSAC_NOBAND", 0);
+        sa.bhist = PCREG_EXP_ENV("PCREG_RANSAC_DEBUG", 0);
 #endif
         int pb = (n_cap + kSPts - 1) / kSPts; if (pb > kSMaxPB) pb = kSMaxPB; if (pb < 1) pb = 1;
         sa.pb = pb;
@@ -3435,6 +3539,10 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
         // 9 launches (round 3: 11): stage1 (sample fits + records), stage2 (maxima + fp32 rows + the records' digits), scoring pass 1,
         // pass1, refit sums on the matrix cores, dense refit sums (normally idle), refits, scoring pass 2; then select, which also
         // does what rs_finish did
+        //   scoring pass 2 = rs_score32_kernel<false>                                               1 launch  (the full pass)
+        //                  = rs_bprep, rs_bscatter, rs_bounded                                      3 launches (bounded, capacity of at
+        //                                                                                           most kBHand blocks or "ransac_bhand" 1)
+        //                  = rs_bprep, rs_bscatter, rs_bounded (kBHand blocks), rs_bfinish          4 launches (bounded, the default)
         const int n_fit = (it + 255) / 256;
         hipLaunchKernelGGL(rs_stage1_kernel, dim3((unsigned)(n_fit + sa.n_rec_blocks)), dim3(256), 0, st, sa, n_fit);
         const int n_t32 = (it + 255) / 256, n_dig = sa.use_lane ? (int)staged_slots_cap(n_cap) * 2 : 0;
@@ -3467,25 +3575,53 @@ static int launch_ransac_impl(const double* p1, const double* p2, int ld, const 
                 const int S = std::min(kBSeeds, it), nbc = (n_cap + kBBlk - 1) / kBBlk;
                 const int n_seed_wg = (S * nbc + 3) / 4, n_ord_wg = (n_cap + 255) / 256;
                 unsigned long long* stats = ransac_stats_dev();          // "ransac_stats": process-wide counters
+                // the walk hands over after kBHand blocks ("ransac_bhand" 1: never, the walk as it was before the handover: the
+                // A/B of one binary); the host knows neither n nor the list's length, so the finish's grid covers the capacities
+                int bhand = debug_flag(kDbgRansacBHand) == 1 ? 0 : kBHand;
                 hipLaunchKernelGGL(rs_bprep_kernel, dim3((unsigned)(n_seed_wg + n_ord_wg)), dim3(256), 0, st, sa, n_seed_wg, S, nbc);
                 hipLaunchKernelGGL(rs_bscatter_kernel, dim3((unsigned)n_ord_wg), dim3(256), 0, st, sa);
 #ifdef PCREG_EXPERIMENTS
                 // PCREG_RANSAC_DEBUG=1: print this call's scanned fraction.  It synchronises the stream here, so it must not be set
                 // while a graph is being captured.  PCREG_RANSAC_BCHUNK: refits per wave (2 / 4 / 8).
+                // PCREG_RANSAC_BHAND: blocks before the handover (a multiple of 4; 0 = never).
                 const int dbg = PCREG_EXP_ENV("PCREG_RANSAC_DEBUG", 0), chunk = PCREG_EXP_ENV("PCREG_RANSAC_BCHUNK", kBChunk);
+                if (bhand) bhand = PCREG_EXP_ENV("PCREG_RANSAC_BHAND", kBHand) / 4 * 4;
                 unsigned long long* kst = dbg ? ((BCtr*)sa.bctr)->stats : stats;
-                if (chunk == 8) hipLaunchKernelGGL(rs_bounded_kernel<8>, dim3((unsigned)((it + 7) / 8)), dim3(64), 0, st, sa, kst);
-                else if (chunk == 2) hipLaunchKernelGGL(rs_bounded_kernel<2>, dim3((unsigned)((it + 1) / 2)), dim3(64), 0, st, sa, kst);
-                else hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, kst);
+                if (chunk == 8) hipLaunchKernelGGL(rs_bounded_kernel<8>, dim3((unsigned)((it + 7) / 8)), dim3(64), 0, st, sa, kst, bhand);
+                else if (chunk == 2) hipLaunchKernelGGL(rs_bounded_kernel<2>, dim3((unsigned)((it + 1) / 2)), dim3(64), 0, st, sa, kst, bhand);
+                else hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, kst, bhand);
+#else
+                unsigned long long* kst = stats;
+                hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, kst, bhand);
+#endif
+                if (bhand > 0 && n_cap > bhand * kBBlk) {
+                    const int fpb = std::min(kSMaxPB, (n_cap - bhand * kBBlk + kSPts - 1) / kSPts);
+#ifdef PCREG_EXPERIMENTS
+                    // PCREG_RANSAC_BFCHUNK: list slots per workgroup and trip (8 / 16 / 32); PCREG_RANSAC_BFGRID: workgroups of the grid
+                    const int fch = PCREG_EXP_ENV("PCREG_RANSAC_BFCHUNK", kBFChunk), fgrid = PCREG_EXP_ENV("PCREG_RANSAC_BFGRID", kBFGrid);
+                    const int fc = fch == 16 || fch == 32 ? fch : kBFChunk;
+                    const dim3 fg((unsigned)fpb, (unsigned)std::max(1, std::min((it + fc - 1) / fc, (fgrid + fpb - 1) / fpb)));
+                    if (fc == 16) hipLaunchKernelGGL(rs_bfinish_kernel<16>, fg, dim3(kSW * 64), 0, st, sa, kst, bhand);
+                    else if (fc == 32) hipLaunchKernelGGL(rs_bfinish_kernel<32>, fg, dim3(kSW * 64), 0, st, sa, kst, bhand);
+                    else hipLaunchKernelGGL(rs_bfinish_kernel<kBFChunk>, fg, dim3(kSW * 64), 0, st, sa, kst, bhand);
+#else
+                    const dim3 fg((unsigned)fpb, (unsigned)std::max(1, std::min((it + kBFChunk - 1) / kBFChunk, (kBFGrid + fpb - 1) / fpb)));
+                    hipLaunchKernelGGL(rs_bfinish_kernel<kBFChunk>, fg, dim3(kSW * 64), 0, st, sa, kst, bhand);
+#endif
+                }
+#ifdef PCREG_EXPERIMENTS
                 if (dbg) {
-                    unsigned long long u[3] = {0, 0, 0};
+                    unsigned long long u[5] = {0, 0, 0, 0, 0};
                     PCREG_HIP(hipMemcpyAsync(u, kst, sizeof u, hipMemcpyDeviceToHost, st));
                     PCREG_HIP(hipStreamSynchronize(st));
-                    fprintf(stderr, "[pcreg] ransac bounded pass 2: iters=%d n_cap=%d chunk=%d (refit, block) units scanned %llu of %llu (%.4f)\n", it, n_cap,
-                            chunk == 8 || chunk == 2 ? chunk : kBChunk, u[1], u[2], u[2] ? (double)u[1] / (double)u[2] : 0.0);
+                    fprintf(stderr, "[pcreg] ransac bounded pass 2: iters=%d n_cap=%d chunk=%d bhand=%d (refit, block) units scanned %llu of %llu (%.4f), %llu refits handed over, %llu units in the finish\n",
+                            it, n_cap, chunk == 8 || chunk == 2 ? chunk : kBChunk, bhand, u[1], u[2], u[2] ? (double)u[1] / (double)u[2] : 0.0, u[3], u[4]);
+                    int32_t hist[64];
+                    PCREG_HIP(hipMemcpy(hist, ((BCtr*)sa.bctr)->stop_hist, sizeof hist, hipMemcpyDeviceToHost));
+                    fprintf(stderr, "[pcreg] refits whose walk ended after block 1, 2, ... (handed-over refits not counted):");
+                    for (int b = 0; b < 64; ++b) fprintf(stderr, " %d", hist[b]);
+                    fprintf(stderr, "\n");
                 }
-#else
-                hipLaunchKernelGGL(rs_bounded_kernel<kBChunk>, dim3((unsigned)((it + kBChunk - 1) / kBChunk)), dim3(64), 0, st, sa, stats);
 #endif
             } else if (sa.use_f32)
                 hipLaunchKernelGGL(rs_score32_kernel<false>, sgrid, dim3(kSW * 64), 0, st, sa, (const double*)a.TF, (const float*)sa.T32b, (const unsigned char*)sa.v2,
