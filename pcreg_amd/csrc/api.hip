@@ -11,6 +11,8 @@
 #include <cmath>
 #include <mutex>
 #include <algorithm>
+#include <functional>
+#include <initializer_list>
 #include <vector>
 
 namespace pcreg {
@@ -757,9 +759,49 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     return PCREG_OK;
 }
 
-// B transforms refitted `steps` times on their close pairs: upload the queries and the transforms, run the steps on the device,
-// each step's T_out the next one's input (two blocks in turn: a step may not write over its input), and read ONE block back --
-// the last step's [T_out 16 B doubles][sum_d2 B doubles][n_close B int32][empty B int32]
+// The staging of every "B transforms refitted `steps` times" entry: the queries and the transforms are uploaded once, the steps
+// run on the device, each step's T_out the next one's input, and ONE result block is read back -- the last step's.  A block is
+// `cols` doubles' room per transform and starts with T_out (16 B doubles); two blocks take turns, because a step may not write
+// over its input.  The takes keep the Stage rule (every take before the first use) and each entry's order: take_inputs, the
+// entry's own inputs, take_blocks, the entry's own workspaces; then upload, the entry's own uploads, run.
+struct RefitCol { void* dst; int word; size_t bytes; };            // B elements of `bytes` bytes from 4-byte word `word` x B of the block
+struct RefitStaging {
+    Stage st{scratch()};
+    size_t nQ, nB; int cols;
+    float* dq = nullptr; double *dT = nullptr, *dout = nullptr; char* ws = nullptr;
+    RefitStaging(int Q, int B, int cols_) : nQ((size_t)Q), nB((size_t)B), cols(cols_) {}
+    int take_inputs() {
+        TRY(st.take(3 * nQ, &dq));
+        return st.take(16 * nB, &dT);
+    }
+    int take_blocks(size_t wsb) {
+        TRY(st.take(2 * (size_t)cols * nB, &dout));
+        return st.take(wsb, &ws);
+    }
+    int upload(const float* q, int ldq, const double* T) {
+        TRY(upload_cols(q, (int)nQ, ldq, 3, dq, g_stream));
+        PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+        return PCREG_OK;
+    }
+    // step(in, blk): one launch that reads the transforms at `in` (dT, then the block before) and fills the block `blk`
+    int run(int steps, const std::function<int(const double*, double*)>& step, std::initializer_list<RefitCol> table) {
+        const double* in = dT;
+        double* blk = dout;
+        for (int s = 0; s < steps; ++s) {
+            blk = dout + (size_t)(s & 1) * cols * nB;
+            TRY(step(in, blk));
+            in = blk;
+        }
+        std::vector<double> host((size_t)cols * nB);
+        PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g_stream));
+        PCREG_HIP(hipStreamSynchronize(g_stream));
+        for (const RefitCol& c : table) memcpy(c.dst, (const char*)host.data() + 4 * (size_t)c.word * nB, c.bytes * nB);
+        return PCREG_OK;
+    }
+};
+
+// B transforms refitted `steps` times on their close pairs; the block: [T_out 16 B doubles][sum_d2 B doubles][n_close B int32]
+// [empty B int32]
 int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps, double* T_out,
                           int32_t* n_close, double* sum_d2, int32_t* empty) {
     PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
@@ -767,37 +809,21 @@ int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     PCREG_ARG(model->dm != nullptr);
     GUARD();
     if (B == 0) return PCREG_OK;
-    Stage st{scratch()};
     const ModelView& v = model->dm->v;
     const size_t wsb = refit_ws_bytes(Q, B, v.M), nB = (size_t)B;
-    float* dq; double *dT, *dout; char* ws;
-    TRY(st.take(3 * (size_t)Q, &dq));
-    TRY(st.take(16 * nB, &dT));
-    TRY(st.take(2 * (17 * nB + nB), &dout));                               // two result blocks of 18 B doubles' room (17 B and 2 B int32)
-    TRY(st.take(wsb, &ws));
-    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
-    const double* in = dT;
-    double* blk = dout;
-    for (int s = 0; s < steps; ++s) {
-        blk = dout + (size_t)(s & 1) * 18 * nB;
-        TRY(launch_model_refit(v, dq, Q, Q, in, B, r2, blk, nullptr, (int32_t*)(blk + 17 * nB), blk + 16 * nB, (int32_t*)(blk + 17 * nB) + nB, ws, wsb,
-                               g_stream));
-        in = blk;
-    }
-    std::vector<double> host(18 * nB);
-    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 18 * nB, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
-    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
-    memcpy(n_close, host.data() + 17 * nB, sizeof(int32_t) * nB);
-    memcpy(empty, (const int32_t*)(host.data() + 17 * nB) + nB, sizeof(int32_t) * nB);
-    return PCREG_OK;
+    RefitStaging rs(Q, B, 18);                                             // 17 B doubles and 2 B int32
+    TRY(rs.take_inputs());
+    TRY(rs.take_blocks(wsb));
+    TRY(rs.upload(q, ldq, T));
+    return rs.run(steps, [&](const double* in, double* blk) {
+        int32_t* ib = (int32_t*)(blk + 17 * nB);
+        return launch_model_refit(v, rs.dq, Q, Q, in, B, r2, blk, nullptr, ib, blk + 16 * nB, ib + nB, rs.ws, wsb, g_stream);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {n_close, 34, 4}, {empty, 35, 4}});
 }
 
-// B transforms refitted `steps` times by the point-to-plane step: pcreg_model_refit_f32's staging, with the normals uploaded once
-// (or computed once on the device by the normals chain, k nearest rows and no viewpoint) before the first step, and ONE block read
-// back -- the last step's [T_out 16 B doubles][sum_d2 B][sum_res2 B][n_close B int32][n_plane B int32][empty B int32]
+// B transforms refitted `steps` times by the point-to-plane step, with the normals uploaded once (or computed once on the device
+// by the normals chain, k nearest rows and no viewpoint) before the first step; the block: [T_out 16 B doubles][sum_d2 B]
+// [sum_res2 B][n_close B int32][n_plane B int32][empty B int32]
 int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
                                 const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_plane,
                                 double* sum_res2, int32_t* empty) {
@@ -807,44 +833,26 @@ int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int l
     PCREG_ARG(model->dm != nullptr && (!normals || ldn >= model->M));
     GUARD();
     if (B == 0) return PCREG_OK;
-    Stage st{scratch()};
     const ModelView& v = model->dm->v;
     const int M = v.M;
     const size_t wsb = refit_plane_ws_bytes(Q, B, M), nwsb = normals || M == 0 ? 0 : normals_ws_bytes(M, k), nB = (size_t)B;
-    float *dq, *dn; double *dT, *dout; char *ws, *nws;
-    TRY(st.take(3 * (size_t)Q, &dq));
-    TRY(st.take(16 * nB, &dT));
-    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
-    TRY(st.take(2 * 20 * nB, &dout));                                      // two result blocks of 20 B doubles' room (18 B and 3 B int32)
-    TRY(st.take(wsb, &ws));
-    TRY(st.take(nwsb, &nws));
-    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    RefitStaging rs(Q, B, 20);                                             // 18 B doubles and 3 B int32
+    float* dn; char* nws;
+    TRY(rs.take_inputs());
+    TRY(rs.st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
+    TRY(rs.take_blocks(wsb));
+    TRY(rs.st.take(nwsb, &nws));
+    TRY(rs.upload(q, ldq, T));
     if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
     else if (M > 0) TRY(launch_model_normals(v, k, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
-    const double* in = dT;
-    double* blk = dout;
-    for (int s = 0; s < steps; ++s) {
-        blk = dout + (size_t)(s & 1) * 20 * nB;
+    return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 18 * nB);
-        TRY(launch_model_refit_plane(v, dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, blk, nullptr, ib, blk + 16 * nB, ib + nB, blk + 17 * nB, ib + 2 * nB, ws,
-                                     wsb, g_stream));
-        in = blk;
-    }
-    std::vector<double> host(20 * nB);
-    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 20 * nB, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    const int32_t* hi = (const int32_t*)(host.data() + 18 * nB);
-    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
-    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
-    memcpy(sum_res2, host.data() + 17 * nB, sizeof(double) * nB);
-    memcpy(n_close, hi, sizeof(int32_t) * nB);
-    memcpy(n_plane, hi + nB, sizeof(int32_t) * nB);
-    memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
-    return PCREG_OK;
+        return launch_model_refit_plane(v, rs.dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, blk, nullptr, ib, blk + 16 * nB, ib + nB, blk + 17 * nB, ib + 2 * nB,
+                                        rs.ws, wsb, g_stream);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_plane, 37, 4}, {empty, 38, 4}});
 }
 
-// B transforms refitted `steps` times by the plane-to-plane step: pcreg_model_refit_plane_f32's staging and result block, with the
+// B transforms refitted `steps` times by the plane-to-plane step: pcreg_model_refit_plane_f32's result block, with the
 // query normals beside the model normals -- each uploaded once, or computed once on the device by the normals chain (k nearest
 // rows, no viewpoint; the queries' from a prepared model of q that lives in the staging and goes with it)
 int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
@@ -858,56 +866,37 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
     PCREG_ARG(model->dm != nullptr && (!normals || ldn >= model->M));
     GUARD();
     if (B == 0) return PCREG_OK;
-    Stage st{scratch()};
     const ModelView& v = model->dm->v;
     const int M = v.M;
     const bool own_q = !qnormals && Q > 0;
     const size_t wsb = refit_gicp_ws_bytes(Q, B, M), nB = (size_t)B;
     const size_t nwsb = std::max(normals || M == 0 ? (size_t)0 : normals_ws_bytes(M, k), own_q ? normals_ws_bytes(Q, k) : (size_t)0);
-    float *dq, *dn, *dnq; double *dT, *dout; char *ws, *nws, *qblock;
-    TRY(st.take(3 * (size_t)Q, &dq));
-    TRY(st.take(16 * nB, &dT));
-    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
-    TRY(st.take(3 * (size_t)(Q > 0 ? Q : 1), &dnq));
-    TRY(st.take(2 * 20 * nB, &dout));                                      // two result blocks of 20 B doubles' room (18 B and 3 B int32)
-    TRY(st.take(wsb, &ws));
-    TRY(st.take(nwsb, &nws));
-    TRY(st.take(own_q ? model_prep_bytes(Q) : 0, &qblock));
-    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    RefitStaging rs(Q, B, 20);                                             // 18 B doubles and 3 B int32
+    float *dn, *dnq; char *nws, *qblock;
+    TRY(rs.take_inputs());
+    TRY(rs.st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
+    TRY(rs.st.take(3 * (size_t)(Q > 0 ? Q : 1), &dnq));
+    TRY(rs.take_blocks(wsb));
+    TRY(rs.st.take(nwsb, &nws));
+    TRY(rs.st.take(own_q ? model_prep_bytes(Q) : 0, &qblock));
+    TRY(rs.upload(q, ldq, T));
     if (normals) TRY(upload_cols(normals, M, ldn, 3, dn, g_stream));
     else if (M > 0) TRY(launch_model_normals(v, k, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
     if (qnormals) TRY(upload_cols(qnormals, Q, ldnq, 3, dnq, g_stream));
     else if (own_q) {
-        const ModelView qv = model_view(dq, Q, Q, qblock);
+        const ModelView qv = model_view(rs.dq, Q, Q, qblock);
         TRY(launch_model_prepare(qv, g_stream));
         TRY(launch_model_normals(qv, k, nullptr, dnq, Q, nullptr, nws, nwsb, g_stream));
     }
-    const double* in = dT;
-    double* blk = dout;
-    for (int s = 0; s < steps; ++s) {
-        blk = dout + (size_t)(s & 1) * 20 * nB;
+    return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 18 * nB);
-        TRY(launch_model_refit_gicp(v, dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, dnq, Q > 0 ? Q : 1, epsilon, blk, nullptr, ib, blk + 16 * nB, ib + nB,
-                                    blk + 17 * nB, ib + 2 * nB, ws, wsb, g_stream));
-        in = blk;
-    }
-    std::vector<double> host(20 * nB);
-    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 20 * nB, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    const int32_t* hi = (const int32_t*)(host.data() + 18 * nB);
-    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
-    memcpy(sum_d2, host.data() + 16 * nB, sizeof(double) * nB);
-    memcpy(sum_res2, host.data() + 17 * nB, sizeof(double) * nB);
-    memcpy(n_close, hi, sizeof(int32_t) * nB);
-    memcpy(n_pairs, hi + nB, sizeof(int32_t) * nB);
-    memcpy(empty, hi + 2 * nB, sizeof(int32_t) * nB);
-    return PCREG_OK;
+        return launch_model_refit_gicp(v, rs.dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, dnq, Q > 0 ? Q : 1, epsilon, blk, nullptr, ib, blk + 16 * nB, ib + nB,
+                                       blk + 17 * nB, ib + 2 * nB, rs.ws, wsb, g_stream);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_pairs, 37, 4}, {empty, 38, 4}});
 }
 
-// B transforms refitted `steps` times by the coherent-point-drift step: one upload, `steps` device steps, one read.  A step's
-// result block is 21 B doubles' room -- T_out (16 B), sigma2_out, Np, sum_res2, sum_d2 (B each), then n_live and empty (B int32 each)
-// -- and two blocks alternate, so a step reads its transforms and its sigma2 from the block before it
+// B transforms refitted `steps` times by the coherent-point-drift step; the block: [T_out 16 B doubles][sigma2_out B][Np B]
+// [sum_res2 B][sum_d2 B][n_live B int32][empty B int32].  A step reads its transforms AND its sigma2 from the block before it.
 int pcreg_model_refit_cpd_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, const double* sigma2_in, double outlier,
                               int steps, double* T_out, double* sigma2_out, double* Np, double* sum_res2, double* sum_d2, int32_t* n_live,
                               int32_t* empty) {
@@ -917,39 +906,21 @@ int pcreg_model_refit_cpd_f32(pcreg_model* model, const float* q, int Q, int ldq
     PCREG_ARG(model->dm != nullptr);
     GUARD();
     if (B == 0) return PCREG_OK;
-    Stage st{scratch()};
     const ModelView& v = model->dm->v;
     const size_t wsb = refit_cpd_ws_bytes(Q, B, v.M), nB = (size_t)B;
-    float* dq; double *dT, *dsig, *dout; char* ws;
-    TRY(st.take(3 * (size_t)Q, &dq));
-    TRY(st.take(16 * nB, &dT));
-    TRY(st.take(nB, &dsig));
-    TRY(st.take(2 * 21 * nB, &dout));
-    TRY(st.take(wsb, &ws));
-    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
+    RefitStaging rs(Q, B, 21);                                             // 20 B doubles and 2 B int32
+    double* dsig;
+    TRY(rs.take_inputs());
+    TRY(rs.st.take(nB, &dsig));
+    TRY(rs.take_blocks(wsb));
+    TRY(rs.upload(q, ldq, T));
     PCREG_HIP(hipMemcpyAsync(dsig, sigma2_in, sizeof(double) * nB, hipMemcpyHostToDevice, g_stream));
-    const double *in = dT, *sig = dsig;
-    double* blk = dout;
-    for (int s = 0; s < steps; ++s) {
-        blk = dout + (size_t)(s & 1) * 21 * nB;
+    return rs.run(steps, [&](const double* in, double* blk) {
+        const double* sig = in == rs.dT ? dsig : in + 16 * nB;             // (the first step's, then the sigma2_out beside the T_out it reads)
         int32_t* ib = (int32_t*)(blk + 20 * nB);
-        TRY(launch_model_refit_cpd(v, dq, Q, Q, in, B, sig, outlier, blk, nullptr, blk + 16 * nB, blk + 17 * nB, blk + 18 * nB, blk + 19 * nB, ib, ib + nB,
-                                   ws, wsb, g_stream));
-        in = blk; sig = blk + 16 * nB;
-    }
-    std::vector<double> host(21 * nB);
-    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 21 * nB, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    const int32_t* hi = (const int32_t*)(host.data() + 20 * nB);
-    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
-    memcpy(sigma2_out, host.data() + 16 * nB, sizeof(double) * nB);
-    memcpy(Np, host.data() + 17 * nB, sizeof(double) * nB);
-    memcpy(sum_res2, host.data() + 18 * nB, sizeof(double) * nB);
-    memcpy(sum_d2, host.data() + 19 * nB, sizeof(double) * nB);
-    memcpy(n_live, hi, sizeof(int32_t) * nB);
-    memcpy(empty, hi + nB, sizeof(int32_t) * nB);
-    return PCREG_OK;
+        return launch_model_refit_cpd(v, rs.dq, Q, Q, in, B, sig, outlier, blk, nullptr, blk + 16 * nB, blk + 17 * nB, blk + 18 * nB, blk + 19 * nB, ib,
+                                      ib + nB, rs.ws, wsb, g_stream);
+    }, {{T_out, 0, 128}, {sigma2_out, 32, 8}, {Np, 34, 8}, {sum_res2, 36, 8}, {sum_d2, 38, 8}, {n_live, 40, 4}, {empty, 41, 4}});
 }
 
 // clusterPoints on a prepared model: label the rows on the device, read the labels back, and form the CSR lists on the host by
@@ -2728,8 +2699,7 @@ int pcreg_ndt_get(const pcreg_ndt* ndt, int32_t* cells, int32_t* counts, double*
     GUARD();
     return dev_ndt_get(ndt->d, cells, counts, means, C, lo, origin);
 }
-// B transforms stepped `steps` times: pcreg_model_refit_plane_f32's staging -- one upload, two result blocks that take turns, ONE
-// block read back: the last step's [T_out 16 B doubles][sum_e B][n_pairs B int32][empty B int32]
+// B transforms stepped `steps` times (RefitStaging); the block: [T_out 16 B doubles][sum_e B][n_pairs B int32][empty B int32]
 int pcreg_ndt_refit_f32(pcreg_ndt* ndt, const float* q, int Q, int ldq, const double* T, int B, int neighbors, double outlier_ratio, int steps,
                         double* T_out, int32_t* n_pairs, double* sum_e, int32_t* empty) {
     double d2;
@@ -2738,32 +2708,15 @@ int pcreg_ndt_refit_f32(pcreg_ndt* ndt, const float* q, int Q, int ldq, const do
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_pairs && sum_e && empty)));
     GUARD();
     if (B == 0) return PCREG_OK;
-    Stage st{scratch()};
     const size_t wsb = ndt_refit_ws_bytes(Q, B), nB = (size_t)B;
-    float* dq; double *dT, *dout; char* ws;
-    TRY(st.take(3 * (size_t)Q, &dq));
-    TRY(st.take(16 * nB, &dT));
-    TRY(st.take(2 * 18 * nB, &dout));                                      // two result blocks of 18 B doubles' room (17 B and 2 B int32)
-    TRY(st.take(wsb, &ws));
-    TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
-    PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * nB, hipMemcpyHostToDevice, g_stream));
-    const double* in = dT;
-    double* blk = dout;
-    for (int s = 0; s < steps; ++s) {
-        blk = dout + (size_t)(s & 1) * 18 * nB;
+    RefitStaging rs(Q, B, 18);                                             // 17 B doubles and 2 B int32
+    TRY(rs.take_inputs());
+    TRY(rs.take_blocks(wsb));
+    TRY(rs.upload(q, ldq, T));
+    return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 17 * nB);
-        TRY(launch_ndt_refit(ndt->d->v, dq, Q, Q, in, B, neighbors, outlier_ratio, blk, nullptr, ib, blk + 16 * nB, ib + nB, ws, wsb, g_stream));
-        in = blk;
-    }
-    std::vector<double> host(18 * nB);
-    PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * 18 * nB, hipMemcpyDeviceToHost, g_stream));
-    PCREG_HIP(hipStreamSynchronize(g_stream));
-    const int32_t* hi = (const int32_t*)(host.data() + 17 * nB);
-    memcpy(T_out, host.data(), sizeof(double) * 16 * nB);
-    memcpy(sum_e, host.data() + 16 * nB, sizeof(double) * nB);
-    memcpy(n_pairs, hi, sizeof(int32_t) * nB);
-    memcpy(empty, hi + nB, sizeof(int32_t) * nB);
-    return PCREG_OK;
+        return launch_ndt_refit(ndt->d->v, rs.dq, Q, Q, in, B, neighbors, outlier_ratio, blk, nullptr, ib, blk + 16 * nB, ib + nB, rs.ws, wsb, g_stream);
+    }, {{T_out, 0, 128}, {sum_e, 32, 8}, {n_pairs, 34, 4}, {empty, 35, 4}});
 }
 
 size_t pcreg_dev_aggregate_matches_workspace(int n_cap) { return aggregate_matches_ws_bytes(n_cap); }

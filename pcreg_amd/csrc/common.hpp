@@ -245,6 +245,10 @@ int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const
 // about origin[0..2], the batch's per-slot buffers best / tq / win (ld S), n_close [nb] already totalled
 int launch_refit_finish(const double* pmom, const int32_t* n_close, const float* best, const float* tq, const float* win, int Q, int S, int chunks,
                         int nb, const float* origin, const double* T_in, double* T_out, double* T_step, int32_t* empty, hipStream_t st);
+// a refit call without pairs (Q = 0 or no rows), whatever the method (knn_score.hip): every transform empty = 1 with 32 zeros,
+// and a zero in each of the method's per-transform outputs that is not null
+struct RefitEmptyOuts { double* d[4]; int32_t* n; };
+int launch_refit_empty(int B, double* T_out, double* T_step, int32_t* empty, const RefitEmptyOuts& z, hipStream_t st);
 // the same chain with the point-to-plane fit in estimateTransform's place (knn_score.hip, plane_fit.hpp): normals
 // [3][ldn] on the device by ORIGINAL row; n_plane the pairs whose row has a finite normal, sum_res2 their squared plane residuals
 size_t refit_plane_ws_bytes(int Q, int B, int M);

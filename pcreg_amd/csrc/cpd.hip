@@ -7,11 +7,11 @@
 //                                         sum_d2 is its sum, the same bits pcreg_model_score_f32 gives
 //   D1  cpd_model_sums_kernel             one workgroup: the origin o (the middle of the live rows' box), then the live rows' number,
 //                                         sum v and sum |v|^2, v = m - o, in double; thread t adds ORIGINAL rows t, t + 256, .. in
-//                                         order, wave_sum, the four waves ascending
+//                                         order, chunk_tail_few
 // and per batch of whole transforms (at most 128 Ki query slots):
-//   D2  cpd_query_sums_kernel             per (transform, chunk of 2048 queries): the moved points p' (scoring's arithmetic, word
-//                                         for word) into tq, the live ones' number, sum u and sum |u|^2, u = p' - o; thread t adds
-//                                         its 8 consecutive queries in order, wave_sum, the four waves ascending
+//   D2  cpd_query_sums_kernel             per (transform, chunk of 2048 queries): the moved points p' (moved_point: scoring's) into
+//                                         tq, the live ones' number, sum u and sum |u|^2, u = p' - o; thread t adds its 8
+//                                         consecutive queries in order, chunk_tail_few
 //   D3  cpd_param_kernel                  thread per transform: the chunks ascending, the live count, sigma2 (the closed-form initial
 //                                         value where sigma2_in == 0), h = 1 / (2 sigma2), k2 = (float)(-(h log2 e)), c
 //   D4  cpd_weights_kernel                THE HOT PATH: per (transform, chunk, slice of the model's rows, ORIGINAL order): 8 queries a thread
@@ -19,16 +19,17 @@
 //                                         ballot, read at one address by all lanes: a broadcast), per pair three subtractions, the
 //                                         distance, one exp2 and the five fp32 sums S, V[3], W of e, e (m - p'), e d2
 //   D5  cpd_moments_kernel                per (transform, chunk): a query's slices added in ascending order in fp32, then in double
-//                                         g, p and the 19 sums of cpd_fit.hpp in query order; plane_moments_kernel's tree
-//   D6  cpd_finish_kernel                 per transform: the chunks ascending, cpd_fit, T * T_step
+//                                         g, p and the 19 sums of cpd_fit.hpp in query order; chunk_tail
+//   D6  cpd_finish_kernel                 per transform: finish_step with cpd_fit about the origin o
+// The step's skeleton -- the moved point, the chunk tail, the finish step, T * T_step and the empty rule -- is refit_step.hpp's
+// (DESIGN 4.28).
 // Every sum's order is a function of (Q, M) alone: no floating-point atomic, the rows are read in their original order (the prepared
 // model's sorted copy is placed by atomics and differs from one preparation to the next) and the slice count depends on M only, so a
 // candidate's bits do not depend on B, on its place, on the batch, on the stream or on which handle holds the model.
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
-#include "chunk_scan.hpp"
-#include "moments.hpp"
+#include "refit_step.hpp"
 #include "cpd_fit.hpp"
 #include <cmath>
 
@@ -43,9 +44,6 @@ constexpr int kCpdPar = 6;                        // per transform: sigma2, h, c
 constexpr int kCpdQSums = 4;                      // sum u (3), sum |u|^2
 static_assert(kScanBlock == kBlock && kScanPer == 8, "a thread owns 8 queries of a chunk of 2048");
 
-__device__ __forceinline__ bool cpd_finite(double v) { return v - v == 0.0; }
-
-int cpd_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk); }
 int cpd_batch(int Q, int B) { return std::max(1, std::min(B, kCpdSlots / (Q > 0 ? Q : 1))); }
 // the slices of the model's rows: whole tiles of 256 rows, at most 32 slices -- a function of M alone
 int cpd_slice_rows(int M) {
@@ -62,7 +60,6 @@ int cpd_slices(int M) { const int sr = cpd_slice_rows(M); return std::max(1, (M 
 // (a double: exact), [5..7] = o.
 __global__ __launch_bounds__(kBlock) void cpd_model_sums_kernel(const float* __restrict__ m, int M, int ldm, double* __restrict__ msum) {
     __shared__ float s_box[kBlock / 64][6];
-    __shared__ double s_m[kBlock / 64][5];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int r = threadIdx.x; r < M; r += kBlock) {
         const float x = m[r], y = m[r + (size_t)ldm], z = m[r + 2 * (size_t)ldm];
@@ -89,44 +86,32 @@ __global__ __launch_bounds__(kBlock) void cpd_model_sums_kernel(const float* __r
         of[c] = 0.5f * l + 0.5f * h;
     }
     const double ox = (double)of[0], oy = (double)of[1], oz = (double)of[2];
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, n = 0.0;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int r = threadIdx.x; r < M; r += kBlock) {
         const float x = m[r], y = m[r + (size_t)ldm], z = m[r + 2 * (size_t)ldm];
         if (finite3(x, y, z)) {
             const double v0 = (double)x - ox, v1 = (double)y - oy, v2 = (double)z - oz;
-            a0 = a0 + v0; a1 = a1 + v1; a2 = a2 + v2;
-            a3 = a3 + ((v0 * v0 + v1 * v1) + v2 * v2);
-            n = n + 1.0;
+            a[0] = a[0] + v0; a[1] = a[1] + v1; a[2] = a[2] + v2;
+            a[3] = a[3] + ((v0 * v0 + v1 * v1) + v2 * v2);
+            a[4] = a[4] + 1.0;
         }
     }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0) {
-        double* s = s_m[threadIdx.x >> 6];
-        s[0] = a0; s[1] = a1; s[2] = a2; s[3] = a3; s[4] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const int k = threadIdx.x;
-        msum[k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail_few(a, msum);                                      // (one workgroup: msum[0 .. 4])
     if (threadIdx.x == 0) { msum[5] = ox; msum[6] = oy; msum[7] = oz; }
 }
 
 // ---- D2. the moved points and the queries' sums -------------------------------------------------------------------------
-// workgroup bl * chunks + c, thread t: queries c * 2048 + 8 t .. + 7.  p' is score_transform_kernel's arithmetic (knn_score.hip),
-// word for word: an all-zero transform's are NaN.  A query is LIVE when its p' has three finite coordinates.
+// workgroup bl * chunks + c, thread t: queries c * 2048 + 8 t .. + 7.  p' is moved_point (refit_step.hpp), as in
+// score_transform_kernel: an all-zero transform's are NaN.  A query is LIVE when its p' has three finite coordinates.
 __global__ __launch_bounds__(kBlock) void cpd_query_sums_kernel(const float* __restrict__ q, int Q, int ldq, const double* __restrict__ T, int S, int chunks,
                                                                 const double* __restrict__ msum, float* __restrict__ tq, double* __restrict__ pq,
                                                                 int32_t* __restrict__ pql) {
-    __shared__ double s_m[kBlock / 64][kCpdQSums];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     const double ox = msum[5], oy = msum[6], oz = msum[7];
     double t[16];
-    bool empty = true;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { t[e] = T[(size_t)bl * 16 + e]; empty = empty && t[e] == 0.0; }
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const bool empty = load_transform(T, bl, t);
+    double a[kCpdQSums] = {0.0, 0.0, 0.0, 0.0};
     int32_t cnt = 0;
 #pragma unroll
     for (int u = 0; u < kScanPer; ++u) {
@@ -134,31 +119,18 @@ __global__ __launch_bounds__(kBlock) void cpd_query_sums_kernel(const float* __r
         if (i < Q) {
             const double x = (double)q[i], y = (double)q[i + (size_t)ldq], z = (double)q[i + 2 * (size_t)ldq];
             float p[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double v = ((x * t[4 * j] + y * t[4 * j + 1]) + z * t[4 * j + 2]) + t[4 * j + 3];
-                p[j] = empty ? __int_as_float(0x7FC00000) : (float)v;
-            }
+            moved_point(t, x, y, z, empty, p);
             const size_t s = (size_t)bl * Q + i;
             tq[s] = p[0]; tq[s + (size_t)S] = p[1]; tq[s + 2 * (size_t)S] = p[2];
             if (finite3(p[0], p[1], p[2])) {
                 const double u0 = (double)p[0] - ox, u1 = (double)p[1] - oy, u2 = (double)p[2] - oz;
-                a0 = a0 + u0; a1 = a1 + u1; a2 = a2 + u2;
-                a3 = a3 + ((u0 * u0 + u1 * u1) + u2 * u2);
+                a[0] = a[0] + u0; a[1] = a[1] + u1; a[2] = a[2] + u2;
+                a[3] = a[3] + ((u0 * u0 + u1 * u1) + u2 * u2);
                 ++cnt;
             }
         }
     }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-    if ((threadIdx.x & 63) == 0) {
-        double* s = s_m[threadIdx.x >> 6];
-        s[0] = a0; s[1] = a1; s[2] = a2; s[3] = a3;
-    }
-    __syncthreads();
-    if (threadIdx.x < kCpdQSums) {
-        const int k = threadIdx.x;
-        pq[(size_t)blockIdx.x * kCpdQSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail_few(a, pq);
     chunk_sum(cnt, pql);
 }
 
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void cpd_param_kernel(const double* __restr
     const int bl = blockIdx.x * kBlock + threadIdx.x;
     if (bl >= nb) return;
     bool t_zero = true, t_fin = true;
-    for (int e = 0; e < 16; ++e) { const double v = T[(size_t)bl * 16 + e]; t_zero = t_zero && v == 0.0; t_fin = t_fin && cpd_finite(v); }
+    for (int e = 0; e < 16; ++e) { const double v = T[(size_t)bl * 16 + e]; t_zero = t_zero && v == 0.0; t_fin = t_fin && fit_cylinders_finite(v); }
     double su[3] = {0.0, 0.0, 0.0}, suu = 0.0;
     int32_t ql = 0;
     for (int c = 0; c < chunks; ++c) {
@@ -186,10 +158,10 @@ __global__ __launch_bounds__(kBlock) void cpd_param_kernel(const double* __restr
         const double mu[3] = {su[0] / dq, su[1] / dq, su[2] / dq}, mv[3] = {msum[0] / ml, msum[1] / ml, msum[2] / ml};
         s2 = ((suu / dq + msum[3] / ml) - 2.0 * ((mu[0] * mv[0] + mu[1] * mv[1]) + mu[2] * mv[2])) / 3.0;
     }
-    ok = ok && s2 > 0.0 && cpd_finite(s2);
+    ok = ok && s2 > 0.0 && fit_cylinders_finite(s2);
     const double h = ok ? 1.0 / (2.0 * s2) : 0.0;
     const float k2 = (float)(-(h * 1.4426950408889634));
-    ok = ok && h > 0.0 && cpd_finite(h) && k2 < 0.0f && k2 > -INFINITY;
+    ok = ok && h > 0.0 && fit_cylinders_finite(h) && k2 < 0.0f && k2 > -INFINITY;
     double cc = 0.0;
     if (ok && w > 0.0) {
         const double tp = 6.283185307179586 * s2;
@@ -281,11 +253,10 @@ __global__ __launch_bounds__(kBlock) void cpd_weights_kernel(const float* __rest
 // contraction: out = c * exp(dmin * h) (0 when c == 0, whatever the exponential), g = 1 / (S + out), p = g * S, u = p' - o,
 // gV = g * V, y = p * u + gV by component, uu = (u0 u0 + u1 u1) + u2 u2, gW = g * W, and cpd_fit.hpp's 19 sums, each sum = sum + term:
 // p;  p * u_a;  y_a;  u_a * y_b;  p * uu;  (p * uu + 2 * ((u0 gV0 + u1 gV1) + u2 gV2)) + gW;  gW.
-// wave_sum27 on the 19 (the same bits as 19 wave_sums), the four waves in ascending order.
+// chunk_tail on the 19.
 __global__ __launch_bounds__(kBlock) void cpd_moments_kernel(const float* __restrict__ tq, const float* __restrict__ dmin, const float* __restrict__ part,
                                                              int n_slices, int Q, int S, int chunks, const double* __restrict__ par,
                                                              const double* __restrict__ msum, double* __restrict__ pmom) {
-    __shared__ double s_m[kBlock / 64][kCpdSums];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     const double* pb = par + (size_t)bl * kCpdPar;
@@ -324,68 +295,24 @@ __global__ __launch_bounds__(kBlock) void cpd_moments_kernel(const float* __rest
         acc[17] = acc[17] + ((p * uu + 2.0 * ((u0 * gV0 + u1 * gV1) + u2 * gV2)) + gW);
         acc[18] = acc[18] + gW;
     }
-    wave_sum27(acc);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kCpdSums; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kCpdSums) {
-        const int k = threadIdx.x;
-        pmom[(size_t)blockIdx.x * kCpdSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail<kCpdSums>(acc, 0.0, pmom);
 }
 
 // ---- D6. the fit --------------------------------------------------------------------------------------------------------
-// one wave per transform bl of the batch, as plane_finish_kernel: lane k < 19 adds sum k over the chunks in ascending order; every
-// lane then runs cpd_fit on the same 19 numbers about the origin they were taken about.  T_out = T_in * T_step by
-// refit_finish_kernel's product.  No fit, or a candidate D3 refused: empty = 1, 32 zeros and sigma2_out = 0.
+// finish_step (refit_step.hpp) over the 19 sums: cpd_fit about the origin they were taken about, unless D3 refused the candidate.
+// empty: sigma2_out = 0 beside the 32 zeros.
 __global__ __launch_bounds__(64) void cpd_finish_kernel(const double* __restrict__ pmom, int chunks, const double* __restrict__ par,
                                                         const double* __restrict__ msum, const double* __restrict__ T_in, double* __restrict__ T_out,
                                                         double* __restrict__ T_step, double* __restrict__ sigma2_out, double* __restrict__ Np,
                                                         double* __restrict__ sum_res2, int32_t* __restrict__ empty) {
-    __shared__ double s_sum[kCpdSums], s_S[16];
-    const int bl = blockIdx.x, lane = threadIdx.x;
-    if (lane < kCpdSums) {
-        double v = 0.0;
-        for (int c = 0; c < chunks; ++c) v += pmom[((size_t)bl * chunks + c) * kCpdSums + lane];
-        s_sum[lane] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    double sums[kCpdSums];
-#pragma unroll
-    for (int k = 0; k < kCpdSums; ++k) sums[k] = s_sum[k];
+    const int bl = blockIdx.x;
     const bool in_ok = par[(size_t)bl * kCpdPar + 3] != 0.0;
     const double o[3] = {msum[5], msum[6], msum[7]};
-    double T[16], sig = 0.0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) T[e] = 0.0;
-    const bool ok = in_ok && cpd_fit(sums, o, T, sig);
-    if (lane < 16) {
-        double v = 0.0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) if (e == lane) v = T[e];
-        v = ok ? v : 0.0;
-        s_S[lane] = v;
-        if (T_step) T_step[(size_t)bl * 16 + lane] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    if (lane < 16) {
-        const int r = lane & 3, c = lane >> 2;
-        const double* Ti = T_in + (size_t)bl * 16;
-        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
-        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
-    }
-    if (lane == 0) { empty[bl] = ok ? 0 : 1; sigma2_out[bl] = ok ? sig : 0.0; Np[bl] = sums[0]; sum_res2[bl] = sums[18]; }
-}
-
-// a call without pairs (Q = 0 or a model without rows): every transform is empty
-__global__ __launch_bounds__(kBlock) void cpd_empty_kernel(int B, double* __restrict__ T_out, double* __restrict__ T_step, double* __restrict__ sigma2_out,
-                                                           double* __restrict__ Np, double* __restrict__ sum_res2, double* __restrict__ sum_d2,
-                                                           int32_t* __restrict__ n_live, int32_t* __restrict__ empty) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < 16 * B) { T_out[i] = 0.0; if (T_step) T_step[i] = 0.0; }
-    if (i < B) { sigma2_out[i] = 0.0; Np[i] = 0.0; sum_res2[i] = 0.0; sum_d2[i] = 0.0; n_live[i] = 0; empty[i] = 1; }
+    double sums[kCpdSums], sig = 0.0;
+    int cnt;
+    const bool ok = finish_step<kCpdSums, false>(pmom, nullptr, chunks, T_in, T_out, T_step, empty,
+                                                 [&](const double (&s)[kCpdSums], int, double (&T)[16]) { return in_ok && cpd_fit(s, o, T, sig); }, sums, cnt);
+    if (threadIdx.x == 0) { sigma2_out[bl] = ok ? sig : 0.0; Np[bl] = sums[0]; sum_res2[bl] = sums[18]; }
 }
 
 // Workspace, with nb = max(1, min(B, floor(128 Ki / max(Q, 1)))) transforms a batch, S = max(nb Q, 1) slots, P = nb max(ceil(Q / 2048),
@@ -398,7 +325,7 @@ struct CpdWs { void* score; size_t score_bytes; float* dmin; int32_t* hits; doub
 CpdWs cpd_ws_layout(int Q, int B, int M, void* base, size_t* bytes) {
     CpdWs s{};
     const int nb = cpd_batch(Q, B);
-    const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * cpd_chunks(Q), L = (size_t)cpd_slices(M);
+    const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * scan_chunks(Q), L = (size_t)cpd_slices(M);
     WsWalk w(base);
     s.score_bytes = score_ws_bytes(Q, B, M);
     s.score = w.take_bytes(align_up(s.score_bytes, 256));
@@ -435,10 +362,7 @@ int launch_model_refit_cpd(const ModelView& v, const float* q, int Q, int ldq, c
     }
     if (B == 0) return PCREG_OK;
     if (Q == 0 || v.M == 0) {
-        hipLaunchKernelGGL(cpd_empty_kernel, dim3((unsigned)((16 * (size_t)B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, B, T_out, T_step, sigma2_out, Np,
-                           sum_res2, sum_d2, n_live, empty);
-        PCREG_HIP(hipGetLastError());
-        return PCREG_OK;
+        return launch_refit_empty(B, T_out, T_step, empty, RefitEmptyOuts{{sigma2_out, Np, sum_res2, sum_d2}, n_live}, st);
     }
     int rc = launch_model_score(v, q, Q, ldq, T_dev, B, INFINITY, s.hits, sum_d2, nullptr, s.dmin, s.score, s.score_bytes, st);
     if (rc) return rc;
@@ -447,7 +371,7 @@ int launch_model_refit_cpd(const ModelView& v, const float* q, int Q, int ldq, c
     PCREG_HIP(hipGetLastError());
     const int dbg_slots = debug_flag(kDbgScoreBatchSlots);        // "score_batch_slots": a lower cap here too, same results
     const int nb_max = dbg_slots > 0 ? std::max(1, std::min(cpd_batch(Q, B), dbg_slots / Q)) : cpd_batch(Q, B);
-    const int chunks = cpd_chunks(Q), n_slices = cpd_slices(v.M), slice_rows = cpd_slice_rows(v.M);
+    const int chunks = scan_chunks(Q), n_slices = cpd_slices(v.M), slice_rows = cpd_slice_rows(v.M);
     for (int b0 = 0; b0 < B; b0 += nb_max) {
         const int nb = std::min(nb_max, B - b0), S = nb * Q;
         const double* Tb = T_dev + (size_t)b0 * 16;

@@ -19,25 +19,28 @@
 // The refit (pcreg_model_refit_f32's contract) is the same chain with the walk's other instantiation, which also
 // keeps the winning row's coordinates per slot, and two more steps per batch:
 //   C5  refit_moments_kernel          per (transform, chunk of 2048 queries): the 27 moments of (model row, moved point) over the
-//                                     chunk's hits in query order, shifted by the middle of the model's box; a fixed tree
-//   C6  launch_refit_finish           per transform (ransac.hip): the chunks ascending, fit_moments / fit_3pt, T * T_step
+//                                     chunk's hits in query order, shifted by the middle of the model's box; chunk_tail
+//   C6  launch_refit_finish           per transform (ransac.hip): the chunks ascending, fit_moments / fit_3pt, step_compose
 //
 // The point-to-plane refit (pcreg_model_refit_plane_f32's contract) is the refit's chain up to C4 with the walk's
 // `idx` pointed at a workspace block, so the winning ORIGINAL row per slot is kept beside its coordinates, and then
 //   P5  plane_moments_kernel          per (transform, chunk of 2048 queries): the 28 sums of the plane pairs in query order -- a
-//                                     hit whose row has a finite normal, gathered by that row -- and their number; a fixed tree
-//   P6  plane_finish_kernel           per transform: the chunks ascending, plane_fit (plane_fit.hpp), T * T_step
+//                                     hit whose row has a finite normal, gathered by that row -- and their number; chunk_tail
+//   P6  plane_finish_kernel           per transform: finish_step with plane_fit (plane_fit.hpp) about the middle of the model's box
 //
 // The plane-to-plane refit (pcreg_model_refit_gicp_f32's contract) is the plane refit's chain and workspace with
 //   G5  gicp_moments_kernel           in P5's place: a pair is weighted by W = (C_model + R C_query R^T)^-1 from the two normals
-//                                     (gicp_pair.hpp); the 28 sums are NDT's per-pair terms with C := W, unweighted; P6 follows
+//                                     (gicp_pair.hpp); the 28 sums are info_pair.hpp's terms with C := W, unweighted; P6 follows
+//
+// What the three refits share with each other and with the NDT and coherent-point-drift steps (ndt.hip, cpd.hip) -- the moved
+// point, the chunk tail, the hit prologue, the finish step, T * T_step and the empty rule -- is refit_step.hpp's.
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
-#include "chunk_scan.hpp"
-#include "moments.hpp"
+#include "refit_step.hpp"
 #include "plane_fit.hpp"
 #include "gicp_pair.hpp"
+#include "info_pair.hpp"
 #include <climits>
 #include <cmath>
 
@@ -49,22 +52,18 @@ constexpr int kScoreMaxSlots = kMaxQTiles * 1024;    // 4 Mi query slots per wal
 static_assert(kScanBlock == kBlock, "score_reduce_kernel's threads own kScanPer consecutive queries each");
 
 // ---- C1. the transformed queries ----------------------------------------------------------------------------------------
-// slot s = bl * Q + i of the batch: [q_i, 1] * T_bl as quick_tf_kernel forms it (sweep.hip; -ffp-contract=off), rounded once
+// slot s = bl * Q + i of the batch: moved_point (refit_step.hpp) of [q_i, 1] * T_bl
 __global__ __launch_bounds__(kBlock) void score_transform_kernel(const float* __restrict__ q, int Q, int ldq, const double* __restrict__ T,
                                                                  int n_slots, float* __restrict__ tq) {
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= n_slots) return;
     const int bl = s / Q, i = s - bl * Q;
     double t[16];
-    bool empty = true;
+    const bool empty = load_transform(T, bl, t);
+    float p[3];
+    moved_point(t, (double)q[i], (double)q[i + (size_t)ldq], (double)q[i + 2 * (size_t)ldq], empty, p);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { t[e] = T[(size_t)bl * 16 + e]; empty = empty && t[e] == 0.0; }
-    const double x = (double)q[i], y = (double)q[i + (size_t)ldq], z = (double)q[i + 2 * (size_t)ldq];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double v = ((x * t[4 * j] + y * t[4 * j + 1]) + z * t[4 * j + 2]) + t[4 * j + 3];
-        tq[s + (size_t)j * n_slots] = empty ? __int_as_float(0x7FC00000) : (float)v;
-    }
+    for (int j = 0; j < 3; ++j) tq[s + (size_t)j * n_slots] = p[j];
 }
 
 // ---- C3. the walk -------------------------------------------------------------------------------------------------------
@@ -174,13 +173,12 @@ __global__ __launch_bounds__(kBlock) void score_total_kernel(const double* __res
 
 // ---- C5. the refit's moments --------------------------------------------------------------------------------------------
 // workgroup bl * chunks + c, as score_reduce_kernel: thread t adds the hits among its kScanPer consecutive queries in query order
-// into mom_accumulate's 27 sums (moments.hpp) of p = (model row, moved point), both widened to double; then wave_sum27's tree in
-// each wave and the four waves in ascending order.  The shifted sums are taken about ONE origin for both sides, the same for
+// into mom_accumulate's 27 sums (moments.hpp) of p = (model row, moved point), both widened to double; then chunk_tail
+// (refit_step.hpp).  The shifted sums are taken about ONE origin for both sides, the same for
 // every chunk, batch and call on a model: the middle of the model's box (Prep::cx, cy, cz), which the moved points lie around
 // when the transform is any good.  (The shift only keeps digits; fit_moments adds it back.)
 __global__ __launch_bounds__(kBlock) void refit_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
                                                                int Q, int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ pmom) {
-    __shared__ double s_m[kBlock / 64][27];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     const double ox = (double)prep->cx, oy = (double)prep->cy, oz = (double)prep->cz;
@@ -200,55 +198,37 @@ __global__ __launch_bounds__(kBlock) void refit_moments_kernel(const float* __re
             }
         }
     }
-    wave_sum27(acc);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 27) {
-        const int k = threadIdx.x;
-        pmom[(size_t)blockIdx.x * 27 + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail<27>(acc, 0.0, pmom);
 }
-// a call without pairs (Q = 0 or a model without rows): every transform is empty; n_plane / sum_res2: the plane refit's, or null
+// a call without pairs (Q = 0 or a model without rows): every transform is empty; z: the method's per-transform outputs, or nulls
 __global__ __launch_bounds__(kBlock) void refit_empty_kernel(int B, double* __restrict__ T_out, double* __restrict__ T_step, int32_t* __restrict__ empty,
-                                                             int32_t* __restrict__ n_plane, double* __restrict__ sum_res2) {
+                                                             RefitEmptyOuts z) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < 16 * B) { T_out[i] = 0.0; if (T_step) T_step[i] = 0.0; }
     if (i < B) {
         empty[i] = 1;
-        if (n_plane) n_plane[i] = 0;
-        if (sum_res2) sum_res2[i] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (z.d[k]) z.d[k][i] = 0.0;
+        if (z.n) z.n[i] = 0;
     }
 }
 
 // ---- P5. the plane refit's sums -----------------------------------------------------------------------------------------
 // workgroup bl * chunks + c and thread t as refit_moments_kernel.  A hit (best == best) with the winning original row `row` is a
 // PLANE PAIR when normals[row], normals[row + ldn], normals[row + 2 ldn] are all finite.  The eight (best, row) loads of a thread
-// are issued first and the 24 gathers they address next, so the dependent loads are in flight together; then, in query order and
-// in double on the widened values without contraction: e = p - m, r = (n_x e_x + n_y e_y) + n_z e_z, u = p - o, c = u x n,
-// J = (c, n), and the 28 sums by fma -- A_ij (i <= j, row-major), g_i = J_i r, rr.  wave_sum27 for the first 27 and wave_sum for rr
-// (the same bits as 28 wave_sums), the four waves in ascending order; the number of plane pairs through chunk_sum.
+// are issued first (hit_rows) and the 24 gathers they address next, so the dependent loads are in flight together; then, in query
+// order and in double on the widened values without contraction: e = p - m, r = (n_x e_x + n_y e_y) + n_z e_z, u = p - o,
+// c = u x n, J = (c, n), and the 28 sums by fma -- A_ij (i <= j, row-major), g_i = J_i r, rr.  chunk_tail; the number of plane
+// pairs through chunk_sum.
 __global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
                                                                const int32_t* __restrict__ prow, const float* __restrict__ normals, int ldn, int M, int Q,
                                                                int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ psums,
                                                                int32_t* __restrict__ pplane) {
-    __shared__ double s_m[kBlock / 64][kPlaneSums];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     const double ox = (double)prep->cx, oy = (double)prep->cy, oz = (double)prep->cz;
     int row[kScanPer];
-#pragma unroll
-    for (int u = 0; u < kScanPer; ++u) {
-        row[u] = -1;
-        if (i0 + u < Q) {
-            const size_t s = (size_t)bl * Q + i0 + u;
-            const float d = best[s];
-            const int r = prow[s];
-            if (d == d && (unsigned)r < (unsigned)M) row[u] = r;      // (a hit's row is a model row: the walk wrote it)
-        }
-    }
+    hit_rows(best, prow, bl, i0, Q, M, row);
     float nx[kScanPer], ny[kScanPer], nz[kScanPer];
 #pragma unroll
     for (int u = 0; u < kScanPer; ++u) {
@@ -283,53 +263,27 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(const float* __re
             ++cnt;
         }
     }
-    wave_sum27(acc);
-    rr = wave_sum(rr);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
-        s_m[threadIdx.x >> 6][27] = rr;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneSums) {
-        const int k = threadIdx.x;
-        psums[(size_t)blockIdx.x * kPlaneSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail<kPlaneSums>(acc, rr, psums);
     chunk_sum(cnt, pplane);
 }
 
 // ---- G5. the plane-to-plane refit's sums --------------------------------------------------------------------------------
-// workgroup bl * chunks + c and thread t as plane_moments_kernel, and its first step: the eight (best, row) loads.  The 24
-// gathers of model normals they address and the thread's 24 query-normal loads are issued together next.  Then, in query order
-// and in double on the widened values without contraction: gicp_pair (gicp_pair.hpp) gives W or drops the pair; e = p - m,
-// u = p - o, and pcreg_ndt_refit_f32's per-pair terms with C := W and x := e, added plainly (fma(1, term, sum) is sum + term):
-// A_ij (i <= j, row-major), g_i, and e . (W e) in the 28th place.  The tree after the loop is plane_moments_kernel's.
-__device__ __forceinline__ void gicp_cross(const double (&a)[3], double b0, double b1, double b2, double (&c)[3]) {
-    c[0] = a[1] * b2 - a[2] * b1;
-    c[1] = a[2] * b0 - a[0] * b2;
-    c[2] = a[0] * b1 - a[1] * b0;
-}
+// workgroup bl * chunks + c and thread t as plane_moments_kernel, and its first step: hit_rows.  The 24 gathers of model normals
+// they address and the thread's 24 query-normal loads are issued together next.  Then, in query order and in double on the
+// widened values without contraction: gicp_pair (gicp_pair.hpp) gives W or drops the pair; e = p - m, u = p - o, and info_pair's
+// terms (info_pair.hpp) with C := W and x := e, unweighted: A_ij (i <= j, row-major), g_i, and e . (W e) in the 28th place.
+// chunk_tail; the number of pairs through chunk_sum.
 __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float* __restrict__ best, const float* __restrict__ tq, const float* __restrict__ win,
                                                               const int32_t* __restrict__ prow, const float* __restrict__ normals, int ldn, int M,
                                                               const float* __restrict__ qnormals, int ldnq, const double* __restrict__ T, double a, int Q,
                                                               int S, int chunks, const Prep* __restrict__ prep, double* __restrict__ psums,
                                                               int32_t* __restrict__ ppairs) {
-    __shared__ double s_m[kBlock / 64][kPlaneSums];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     const double o[3] = {(double)prep->cx, (double)prep->cy, (double)prep->cz};
     const double* __restrict__ Tb = T + (size_t)bl * 16;
     int row[kScanPer];
-#pragma unroll
-    for (int u = 0; u < kScanPer; ++u) {
-        row[u] = -1;
-        if (i0 + u < Q) {
-            const size_t s = (size_t)bl * Q + i0 + u;
-            const float d = best[s];
-            const int r = prow[s];
-            if (d == d && (unsigned)r < (unsigned)M) row[u] = r;      // (a hit's row is a model row: the walk wrote it)
-        }
-    }
+    hit_rows(best, prow, bl, i0, Q, M, row);
     float nm[kScanPer][3], nq[kScanPer][3];
 #pragma unroll
     for (int u = 0; u < kScanPer; ++u) {
@@ -355,95 +309,29 @@ __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(const float* __res
         const double p0 = (double)tq[s], p1 = (double)tq[s + (size_t)S], p2 = (double)tq[s + 2 * (size_t)S];
         const double x[3] = {p0 - m0, p1 - m1, p2 - m2};
         const double uu[3] = {p0 - o[0], p1 - o[1], p2 - o[2]};
-        const double y[3] = {(C[0] * x[0] + C[1] * x[1]) + C[2] * x[2], (C[1] * x[0] + C[3] * x[1]) + C[4] * x[2],
-                             (C[2] * x[0] + C[4] * x[1]) + C[5] * x[2]};
-        const double qq = (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
-        // W_a = u x (row a of C): (W_a)_j is component a of C c_j, c_j = e_j x u
-        double W[3][3], K[3], Mm[3], gy[3];
-        gicp_cross(uu, C[0], C[1], C[2], W[0]);
-        gicp_cross(uu, C[1], C[3], C[4], W[1]);
-        gicp_cross(uu, C[2], C[4], C[5], W[2]);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            K[0] = W[0][j]; K[1] = W[1][j]; K[2] = W[2][j];
-            gicp_cross(uu, K[0], K[1], K[2], Mm);                     // Mm_i = c_i . C c_j
-#pragma unroll
-            for (int i = 0; i <= j; ++i) acc[plane_tri(i, j)] = acc[plane_tri(i, j)] + Mm[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) acc[plane_tri(i, 3 + j)] = acc[plane_tri(i, 3 + j)] + W[j][i];       // c_i . (column j of C)
-        }
-        acc[plane_tri(3, 3)] = acc[plane_tri(3, 3)] + C[0]; acc[plane_tri(3, 4)] = acc[plane_tri(3, 4)] + C[1];
-        acc[plane_tri(3, 5)] = acc[plane_tri(3, 5)] + C[2]; acc[plane_tri(4, 4)] = acc[plane_tri(4, 4)] + C[3];
-        acc[plane_tri(4, 5)] = acc[plane_tri(4, 5)] + C[4]; acc[plane_tri(5, 5)] = acc[plane_tri(5, 5)] + C[5];
-        gicp_cross(uu, y[0], y[1], y[2], gy);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { acc[21 + i] = acc[21 + i] + gy[i]; acc[24 + i] = acc[24 + i] + y[i]; }
+        double y[3], qq;
+        info_pair<false>(C, x, uu, 1.0, acc, y, qq);
         rr = rr + qq;
         ++cnt;
     }
-    wave_sum27(acc);
-    rr = wave_sum(rr);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
-        s_m[threadIdx.x >> 6][27] = rr;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneSums) {
-        const int k = threadIdx.x;
-        psums[(size_t)blockIdx.x * kPlaneSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail<kPlaneSums>(acc, rr, psums);
     chunk_sum(cnt, ppairs);
 }
 
 // ---- P6. the plane refit's fit ------------------------------------------------------------------------------------------
-// one wave per transform bl of the batch: lane k < 28 adds sum k over the chunks in ascending order, lane 28 the plane counts;
-// every lane then runs plane_fit on the same 28 numbers about the origin the sums were taken about.  T_out = T_in * T_step by
-// refit_finish_kernel's product (ransac.hip).  No fit, or an all-zero T_in: empty = 1 and 32 zeros.
+// finish_step (refit_step.hpp) over the 28 sums and the plane counts: plane_fit about the origin the sums were taken about,
+// unless T_in is all zero
 __global__ __launch_bounds__(64) void plane_finish_kernel(const double* __restrict__ psums, const int32_t* __restrict__ pplane, int chunks,
                                                           const Prep* __restrict__ prep, const double* __restrict__ T_in, double* __restrict__ T_out,
                                                           double* __restrict__ T_step, int32_t* __restrict__ n_plane, double* __restrict__ sum_res2,
                                                           int32_t* __restrict__ empty) {
-    __shared__ double s_sum[kPlaneSums], s_S[16];
-    __shared__ int32_t s_cnt;
-    const int bl = blockIdx.x, lane = threadIdx.x;
-    if (lane < kPlaneSums) {
-        double v = 0.0;
-        for (int c = 0; c < chunks; ++c) v += psums[((size_t)bl * chunks + c) * kPlaneSums + lane];
-        s_sum[lane] = v;
-    } else if (lane == kPlaneSums) {
-        int32_t n = 0;
-        for (int c = 0; c < chunks; ++c) n += pplane[(size_t)bl * chunks + c];
-        s_cnt = n;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    double sums[kPlaneSums];
-#pragma unroll
-    for (int k = 0; k < kPlaneSums; ++k) sums[k] = s_sum[k];
-    const int cnt = s_cnt;
-    bool in_empty = true;
-    for (int e = 0; e < 16; ++e) in_empty = in_empty && T_in[(size_t)bl * 16 + e] == 0.0;
+    const bool in_empty = transform_is_zero(T_in, blockIdx.x);
     const double o[3] = {(double)prep->cx, (double)prep->cy, (double)prep->cz};
-    double T[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) T[e] = 0.0;
-    const bool ok = !in_empty && plane_fit(sums, cnt, o, T);
-    if (lane < 16) {
-        double v = 0.0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) if (e == lane) v = T[e];
-        v = ok ? v : 0.0;
-        s_S[lane] = v;
-        if (T_step) T_step[(size_t)bl * 16 + lane] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    if (lane < 16) {
-        const int r = lane & 3, c = lane >> 2;
-        const double* Ti = T_in + (size_t)bl * 16;
-        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
-        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
-    }
-    if (lane == 0) { empty[bl] = ok ? 0 : 1; n_plane[bl] = cnt; sum_res2[bl] = sums[27]; }
+    double sums[kPlaneSums];
+    int cnt;
+    finish_step<kPlaneSums, true>(psums, pplane, chunks, T_in, T_out, T_step, empty,
+                                  [&](const double (&s)[kPlaneSums], int n, double (&T)[16]) { return !in_empty && plane_fit(s, n, o, T); }, sums, cnt);
+    if (threadIdx.x == 0) { n_plane[blockIdx.x] = cnt; sum_res2[blockIdx.x] = sums[27]; }
 }
 
 // whole transforms per batch under a cap of `slots` query slots (at least one: Q <= kScoreMaxSlots)
@@ -451,7 +339,6 @@ int score_batch(int Q, int B, int slots) {
     const int per = slots / (Q > 0 ? Q : 1);
     return std::max(1, std::min(B, per));
 }
-int score_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk); }
 
 // Workspace, S = max(nb Q, 1) slots and P = nb max(ceil(Q / 2048), 1) partials of a full batch of nb = max(1, min(B, floor(4 Mi /
 // max(Q, 1)))) transforms: [per-parent-cell counters] [transformed queries, 3 S] [slot -> query, S] [best d per slot, S]
@@ -466,7 +353,7 @@ struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* 
 ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes) {
     ScoreWs s{};
     const int nb = score_batch(Q, B, kScoreMaxSlots);
-    const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * score_chunks(Q);
+    const size_t S = std::max((size_t)nb * (size_t)(Q > 0 ? Q : 0), (size_t)1), P = (size_t)nb * scan_chunks(Q);
     WsWalk w(base);
     s.qcnt = (int32_t*)w.take_bytes((size_t)kQueryKeys * 4 + 256);
     s.tq = w.take<float>(3 * S);
@@ -515,16 +402,17 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
             PCREG_HIP(hipGetLastError());
         }
         if (refit) {
-            hipLaunchKernelGGL(refit_empty_kernel, dim3((unsigned)((16 * (size_t)B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, B, refit->T_out, refit->T_step,
-                               refit->empty, plane ? plane->n_plane : nullptr, plane ? plane->sum_res2 : nullptr);
-            PCREG_HIP(hipGetLastError());
+            RefitEmptyOuts z{};
+            if (plane) { z.d[0] = plane->sum_res2; z.n = plane->n_plane; }
+            int rc = launch_refit_empty(B, refit->T_out, refit->T_step, refit->empty, z, st);
+            if (rc) return rc;
         }
         return PCREG_OK;
     }
     if (plane) idx = s.prow;                                      // the winning row per slot of ONE batch (S entries: only the walk may write it)
     const int dbg_slots = debug_flag(kDbgScoreBatchSlots);        // "score_batch_slots": a lower cap, same results
     const int nb_max = score_batch(Q, B, dbg_slots > 0 ? std::min(dbg_slots, kScoreMaxSlots) : kScoreMaxSlots);
-    const int n_tiles = (v.M + kT16 - 1) / kT16, chunks = score_chunks(Q);
+    const int n_tiles = (v.M + kT16 - 1) / kT16, chunks = scan_chunks(Q);
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile, same bits
     for (int b0 = 0; b0 < B; b0 += nb_max) {
         const int nb = std::min(nb_max, B - b0), S = nb * Q;
@@ -590,6 +478,12 @@ size_t refit_plane_ws_bytes(int Q, int B, int M) {
     if (Q < 0 || B < 0 || Q > kScoreMaxSlots) return 0;
     size_t b; (void)score_ws_layout(Q, B, kModePlane, nullptr, &b);
     return b;
+}
+
+int launch_refit_empty(int B, double* T_out, double* T_step, int32_t* empty, const RefitEmptyOuts& z, hipStream_t st) {
+    hipLaunchKernelGGL(refit_empty_kernel, dim3((unsigned)((16 * (size_t)B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, B, T_out, T_step, empty, z);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
 }
 
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,

@@ -9,16 +9,18 @@
 //   N3  ndt_count_kernel,         the chunk scan's compaction (chunk_scan.hpp) of the Gaussian voxels, ascending: record and key of
 //       ndt_emit_kernel           Gaussian g; the last thread writes their number
 // THE STEP (launch_ndt_refit; nothing is read on the host, no kernel waits for another workgroup):
-//   S1  ndt_moments_kernel        per (transform, chunk of 2048 queries), thread t owns 8 consecutive queries: the moved points, the
-//                                 lookups, the pairs' 28 sums in (query, candidate) order, wave_sum27 + wave_sum, the four waves in
-//                                 ascending order through LDS; the number of pairs through chunk_sum
-//   S2  ndt_finish_kernel         per transform: the chunks ascending, plane_fit (plane_fit.hpp), T * T_step
+//   S1  ndt_moments_kernel        per (transform, chunk of 2048 queries), thread t owns 8 consecutive queries: the moved points
+//                                 (moved_point), the lookups, the pairs' 28 sums in (query, candidate) order (info_pair.hpp,
+//                                 weighted), chunk_tail; the number of pairs through chunk_sum
+//   S2  ndt_finish_kernel         per transform: finish_step with plane_fit (plane_fit.hpp) about the table's origin
+// The step's skeleton -- the moved point, the chunk tail, the finish step, T * T_step and the empty rule -- is refit_step.hpp's
+// (DESIGN 4.28).
 // Integer adds and fp64 sums in one fixed tree only: no floating-point atomic, no result depends on the order in which
 // workgroups run, the stream or what the workspace held.  There is no batching: the workspace is B x chunks partial sums.
 #include "common.hpp"
-#include "chunk_scan.hpp"
-#include "moments.hpp"
+#include "refit_step.hpp"
 #include "plane_fit.hpp"
+#include "info_pair.hpp"
 #include "ndt_gauss.hpp"
 #include <cmath>
 
@@ -76,12 +78,6 @@ __global__ __launch_bounds__(kNdtBlock) void ndt_emit_kernel(const int32_t* __re
 // ---- S1 ---------------------------------------------------------------------------------------------------------------
 struct NdtGrid { float lo[3]; float o[3]; double step; int G; };
 
-__device__ __forceinline__ void ndt_cross(const double (&a)[3], double b0, double b1, double b2, double (&c)[3]) {
-    c[0] = a[1] * b2 - a[2] * b1;
-    c[1] = a[2] * b0 - a[0] * b2;
-    c[2] = a[0] * b1 - a[1] * b0;
-}
-
 // workgroup bl * chunks + c: queries c * 2048 .. of transform bl; thread t its 8 consecutive queries, QG at a time.  The group's
 // QG * NB lookups run together: a branch-free binary search with a trip count fixed by G, every step's loads in flight at once,
 // then the loads of the keys they end on.  The pairs follow in (query, candidate) order.
@@ -89,13 +85,10 @@ template <int NB, int QG>
 __global__ __launch_bounds__(kNdtBlock) void ndt_moments_kernel(const float* __restrict__ q, int Q, int ldq, const double* __restrict__ T, NdtGrid g,
                                                                 const u64* __restrict__ keys, const NdtRec* __restrict__ rec, double half_d2, int chunks,
                                                                 double* __restrict__ psums, int32_t* __restrict__ pcnt) {
-    __shared__ double s_m[kNdtBlock / 64][kPlaneSums];
     const int bl = blockIdx.x / chunks, c = blockIdx.x - bl * chunks;
     const int i0 = c * kScanChunk + threadIdx.x * kScanPer;
     double t[16];
-    bool t_empty = true;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { t[e] = T[(size_t)bl * 16 + e]; t_empty = t_empty && t[e] == 0.0; }
+    const bool t_empty = load_transform(T, bl, t);
     const double o[3] = {(double)g.o[0], (double)g.o[1], (double)g.o[2]};
     double acc[27], se = 0.0;
     int32_t cnt = 0;
@@ -109,14 +102,14 @@ __global__ __launch_bounds__(kNdtBlock) void ndt_moments_kernel(const float* __r
 #pragma unroll
         for (int u = 0; u < QG; ++u) {
             const int i = i0 + grp * QG + u;
-            const bool on = i < Q && !t_empty;
             double x = 0.0, y = 0.0, z = 0.0;
             if (i < Q) { x = (double)q[i]; y = (double)q[i + (size_t)ldq]; z = (double)q[i + 2 * (size_t)ldq]; }
+            float mp[3];
+            moved_point(t, x, y, z, t_empty, mp);
             double cell[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                // scoring's moved point (score_transform_kernel): the chain in double, rounded once to fp32
-                const float pf = on ? (float)(((x * t[4 * j] + y * t[4 * j + 1]) + z * t[4 * j + 2]) + t[4 * j + 3]) : __int_as_float(0x7FC00000);
+                const float pf = i < Q ? mp[j] : __int_as_float(0x7FC00000);       // (a slot past Q: no point)
                 p[u][j] = (double)pf;
                 cell[j] = ndt_cell(pf, g.lo[j], g.step);
             }
@@ -151,107 +144,38 @@ __global__ __launch_bounds__(kNdtBlock) void ndt_moments_kernel(const float* __r
                 const NdtRec* __restrict__ r = rec + at[u][k];
                 const double C[6] = {r->C[0], r->C[1], r->C[2], r->C[3], r->C[4], r->C[5]};
                 const double x[3] = {p[u][0] - r->mean[0], p[u][1] - r->mean[1], p[u][2] - r->mean[2]};
-                const double y[3] = {(C[0] * x[0] + C[1] * x[1]) + C[2] * x[2], (C[1] * x[0] + C[3] * x[1]) + C[4] * x[2],
-                                     (C[2] * x[0] + C[4] * x[1]) + C[5] * x[2]};
-                const double qq = (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
-                const double e = exp(-(half_d2 * qq));
-                // W_a = u x (row a of C): (W_a)_j is component a of C c_j, c_j = e_j x u
-                double W[3][3], K[3], M[3], gy[3];
-                ndt_cross(uu, C[0], C[1], C[2], W[0]);
-                ndt_cross(uu, C[1], C[3], C[4], W[1]);
-                ndt_cross(uu, C[2], C[4], C[5], W[2]);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    K[0] = W[0][j]; K[1] = W[1][j]; K[2] = W[2][j];
-                    ndt_cross(uu, K[0], K[1], K[2], M);           // M_i = c_i . C c_j
-#pragma unroll
-                    for (int i = 0; i <= j; ++i) acc[plane_tri(i, j)] = fma(e, M[i], acc[plane_tri(i, j)]);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) acc[plane_tri(i, 3 + j)] = fma(e, W[j][i], acc[plane_tri(i, 3 + j)]);      // c_i . (column j of C)
-                }
-                acc[plane_tri(3, 3)] = fma(e, C[0], acc[plane_tri(3, 3)]); acc[plane_tri(3, 4)] = fma(e, C[1], acc[plane_tri(3, 4)]);
-                acc[plane_tri(3, 5)] = fma(e, C[2], acc[plane_tri(3, 5)]); acc[plane_tri(4, 4)] = fma(e, C[3], acc[plane_tri(4, 4)]);
-                acc[plane_tri(4, 5)] = fma(e, C[4], acc[plane_tri(4, 5)]); acc[plane_tri(5, 5)] = fma(e, C[5], acc[plane_tri(5, 5)]);
-                ndt_cross(uu, y[0], y[1], y[2], gy);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) { acc[21 + i] = fma(e, gy[i], acc[21 + i]); acc[24 + i] = fma(e, y[i], acc[24 + i]); }
+                double y[3];
+                const double e = exp(-(half_d2 * info_residual(C, x, y)));
+                info_terms<true>(C, y, uu, e, acc);
                 se = se + e;
                 ++cnt;
             }
         }
     }
-    wave_sum27(acc);
-    se = wave_sum(se);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) s_m[threadIdx.x >> 6][k] = acc[k];
-        s_m[threadIdx.x >> 6][27] = se;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneSums) {
-        const int k = threadIdx.x;
-        psums[(size_t)blockIdx.x * kPlaneSums + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    chunk_tail<kPlaneSums>(acc, se, psums);
     chunk_sum(cnt, pcnt);
 }
 
 // ---- S2 ---------------------------------------------------------------------------------------------------------------
-// plane_finish_kernel's shape (knn_score.hip): one wave per transform; lane k < 28 adds sum k over the chunks in ascending order,
-// lane 28 the pair counts; every lane then runs plane_fit on the same 28 numbers about the table's origin.  T_out = T_in * T_step
-// by the refit's product.  No fit, or an all-zero T_in: empty = 1 and 32 zeros.
+// finish_step (refit_step.hpp) over the 28 sums and the pair counts: plane_fit about the table's origin, unless T_in is all zero
 __global__ __launch_bounds__(64) void ndt_finish_kernel(const double* __restrict__ psums, const int32_t* __restrict__ pcnt, int chunks, NdtGrid g,
                                                         const double* __restrict__ T_in, double* __restrict__ T_out, double* __restrict__ T_step,
                                                         int32_t* __restrict__ n_pairs, double* __restrict__ sum_e, int32_t* __restrict__ empty) {
-    __shared__ double s_sum[kPlaneSums], s_S[16];
-    __shared__ int32_t s_cnt;
-    const int bl = blockIdx.x, lane = threadIdx.x;
-    if (lane < kPlaneSums) {
-        double v = 0.0;
-        for (int c = 0; c < chunks; ++c) v += psums[((size_t)bl * chunks + c) * kPlaneSums + lane];
-        s_sum[lane] = v;
-    } else if (lane == kPlaneSums) {
-        int32_t n = 0;
-        for (int c = 0; c < chunks; ++c) n += pcnt[(size_t)bl * chunks + c];
-        s_cnt = n;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    double sums[kPlaneSums];
-#pragma unroll
-    for (int k = 0; k < kPlaneSums; ++k) sums[k] = s_sum[k];
-    const int cnt = s_cnt;
-    bool in_empty = true;
-    for (int e = 0; e < 16; ++e) in_empty = in_empty && T_in[(size_t)bl * 16 + e] == 0.0;
+    const bool in_empty = transform_is_zero(T_in, blockIdx.x);
     const double o[3] = {(double)g.o[0], (double)g.o[1], (double)g.o[2]};
-    double T[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) T[e] = 0.0;
-    const bool ok = !in_empty && plane_fit(sums, cnt, o, T);
-    if (lane < 16) {
-        double v = 0.0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) if (e == lane) v = T[e];
-        v = ok ? v : 0.0;
-        s_S[lane] = v;
-        if (T_step) T_step[(size_t)bl * 16 + lane] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    if (lane < 16) {
-        const int r = lane & 3, c = lane >> 2;
-        const double* Ti = T_in + (size_t)bl * 16;
-        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
-        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
-    }
-    if (lane == 0) { empty[bl] = ok ? 0 : 1; n_pairs[bl] = cnt; sum_e[bl] = sums[27]; }
+    double sums[kPlaneSums];
+    int cnt;
+    finish_step<kPlaneSums, true>(psums, pcnt, chunks, T_in, T_out, T_step, empty,
+                                  [&](const double (&s)[kPlaneSums], int n, double (&T)[16]) { return !in_empty && plane_fit(s, n, o, T); }, sums, cnt);
+    if (threadIdx.x == 0) { n_pairs[blockIdx.x] = cnt; sum_e[blockIdx.x] = sums[27]; }
 }
-
-int ndt_chunks(int Q) { return std::max(1, (Q + kScanChunk - 1) / kScanChunk); }
 
 // Workspace of a step, P = B max(ceil(Q / 2048), 1) partials: [chunk sums, 28 P doubles] [chunk pair counts, P]:
 // roundup(224 P, 256) + roundup(4 P, 256) bytes
 struct NdtStepWs { double* psums; int32_t* pcnt; };
 NdtStepWs ndt_step_ws_layout(int Q, int B, void* base, size_t* bytes) {
     NdtStepWs s{};
-    const size_t P = (size_t)(B > 0 ? B : 0) * (size_t)ndt_chunks(Q);
+    const size_t P = (size_t)(B > 0 ? B : 0) * (size_t)scan_chunks(Q);
     WsWalk w(base);
     s.psums = w.take<double>((size_t)kPlaneSums * P);
     s.pcnt = w.take<int32_t>(P);
@@ -371,7 +295,7 @@ int launch_ndt_refit(const NdtView& v, const float* q, int Q, int ldq, const dou
     double d2 = 0.0;
     PCREG_ARG(ndt_d2(v.step, outlier_ratio, &d2));
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && n_pairs && sum_e && empty && T_out != T_dev)));
-    const int chunks = ndt_chunks(Q);
+    const int chunks = scan_chunks(Q);
     PCREG_ARG((long long)B * chunks <= 0x7FFFFFFF);
     size_t need;
     const NdtStepWs s = ndt_step_ws_layout(Q, B, ws, &need);

@@ -19,7 +19,7 @@
 //     moments per passing hypothesis followed by a second lane-parallel SVD.
 // No data leaves the chip between the sample fit and the final inlier list.
 #include "common.hpp"
-#include "moments.hpp"
+#include "refit_step.hpp"                           // refit_finish_kernel's tail (and moments.hpp)
 #include "wave_math.hpp"                             // splitmix64
 #include <cfloat>
 #include <cstddef>
@@ -3293,20 +3293,18 @@ __global__ __launch_bounds__(64) void estimate_transform_indexed_kernel(const do
 // bl of the batch.  pts1 = the winning model rows, pts2 = the moved points, over the slots with a hit (best == best) in query
 // order.  cnt > 3: the chunks' moments added in ascending order, fit_moments about the origin they were taken about (origin[0..2],
 // both sides).  cnt == 3: the three pairs collected from the per-slot buffers in query order, fit_3pt.  T_step in T16's layout;
-// T_out = T_in * T_step, every entry ((T(r,0) S(0,c) + T(r,1) S(1,c)) + T(r,2) S(2,c)) + T(r,3) S(3,c) (no contraction: the build's
-// flag).  A failed fit, cnt < 3 or an all-zero T_in: empty = 1 and 32 zeros.
+// T_out = T_in * T_step and the empty rule by step_compose (refit_step.hpp).  A failed fit, cnt < 3 or an all-zero T_in: empty.
 __global__ __launch_bounds__(64) void refit_finish_kernel(const double* __restrict__ pmom, const int32_t* __restrict__ n_close, const float* __restrict__ best,
                                                           const float* __restrict__ tq, const float* __restrict__ win, int Q, int S, int chunks,
                                                           const float* __restrict__ origin, const double* __restrict__ T_in, double* __restrict__ T_out,
                                                           double* __restrict__ T_step, int32_t* __restrict__ empty) {
-    __shared__ double s3[18], s_S[16];
+    __shared__ double s3[18];
     const int bl = blockIdx.x, lane = threadIdx.x;
     const int cnt = n_close[bl];
     double T[12]; bool ok = false;
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = 0.0;
-    bool in_empty = true;
-    for (int e = 0; e < 16; ++e) in_empty = in_empty && T_in[(size_t)bl * 16 + e] == 0.0;
+    const bool in_empty = transform_is_zero(T_in, bl);
     if (cnt == 3) {
         int got = 0;
         for (int i0 = 0; i0 < Q && got < 3; i0 += 64) {
@@ -3342,26 +3340,14 @@ __global__ __launch_bounds__(64) void refit_finish_kernel(const double* __restri
         ok = fit_moments(cnt, mom, o, T);
     }
     ok = ok && !in_empty;
-    if (lane < 16) {
-        const int k = lane & 3, j = lane >> 2;
-        double v = 0.0;
-        if (ok) {
-            double tv = 0.0;
+    double v = 0.0;                                               // entry `lane` of T_step: the fit's twelve and the row 0 0 0 1
+    if (ok && lane < 16) {
+        double tv = 0.0;
 #pragma unroll
-            for (int e = 0; e < 12; ++e) if (e == j * 4 + k) tv = T[e];
-            v = (j < 3) ? tv : (k == 3 ? 1.0 : 0.0);
-        }
-        s_S[k + 4 * j] = v;
-        if (T_step) T_step[(size_t)bl * 16 + k + 4 * j] = v;
+        for (int e = 0; e < 12; ++e) if (e == lane) tv = T[e];
+        v = lane < 12 ? tv : (lane == 15 ? 1.0 : 0.0);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    if (lane < 16) {
-        const int r = lane & 3, c = lane >> 2;
-        const double* Ti = T_in + (size_t)bl * 16;
-        const double v = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
-        T_out[(size_t)bl * 16 + r + 4 * c] = ok ? v : 0.0;
-    }
-    if (lane == 0) empty[bl] = ok ? 0 : 1;
+    step_compose(bl, lane, v, ok, T_in, T_out, T_step, empty);
 }
 
 __global__ void calc_dists_kernel(const double* T16, const double* p1, const double* p2, int n, int ld, double* d) {

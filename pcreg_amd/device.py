@@ -30,6 +30,52 @@ def soa(points: torch.Tensor) -> torch.Tensor:
     return points.t().contiguous()
 
 
+class _RefitSteps:
+    """What the five "B transforms refitted `steps` times" methods share (PreparedModel.refit_transforms, refit_plane, refit_gicp,
+    refit_cpd and NdtModel.refit).  Creating one checks q_soa, T_dev and steps; the method then checks its own arguments, and
+    run() finds the buffers and runs the steps."""
+
+    def __init__(self, q_soa: torch.Tensor, T_dev: torch.Tensor, steps: int, empty_any_stride: bool = False):
+        Q = int(q_soa.shape[1]) if q_soa.dim() == 2 else 0
+        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or ((Q or not empty_any_stride) and q_soa.stride(1) != 1):
+            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
+        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
+            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        self.steps = int(steps)
+        if self.steps < 1:
+            raise ValueError(f"steps must be at least 1, got {self.steps}")
+        self.T_dev, self.dev, self.Q, self.B = T_dev, q_soa.device, Q, T_dev.numel() // 16
+        self.q_args = (_p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1))      # (an empty tensor has no address to pass)
+
+    def run(self, owner, ws_attr: str, need: int, kinds, out, call):
+        """-> (T_out, T_step, one [B] tensor per dtype of `kinds`): allocated here with the workspace of `need` bytes cached on
+        owner.ws_attr and grown on demand, or unpacked from out=(T_out, T_step, ..., ws, T_tmp).  Then call(src, dst, T_step, ...,
+        ws) once per step, a step's dst the next one's src: the last step writes T_out, the blocks alternate backwards from it."""
+        dev, B, steps = self.dev, self.B, self.steps
+        need = max(int(need), 256)
+        if out is not None:
+            *res, ws, T_tmp = out
+            if len(res) != 2 + len(kinds):
+                raise ValueError(f"out holds {2 + len(kinds)} outputs, ws and T_tmp; got {len(out)} entries")
+            if steps > 1 and T_tmp is None:
+                raise ValueError("more than one step needs the second transform block, T_tmp")
+        else:
+            res = [torch.empty((B, 16), dtype=torch.float64, device=dev) for _ in range(2)] + [torch.empty(B, dtype=k, device=dev) for k in kinds]
+            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
+            ws = getattr(owner, ws_attr, None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                setattr(owner, ws_attr, ws)
+        if B:                                          # (an empty tensor has no address to pass)
+            with torch.cuda.device(dev):
+                src = self.T_dev
+                for s in range(steps):
+                    dst = res[0] if (steps - 1 - s) % 2 == 0 else T_tmp
+                    call(src, dst, *res[1:], ws)
+                    src = dst
+        return tuple(res)
+
+
 class PreparedModel:
     """A model shard prepared ONCE for any number of searches (pcreg_dev_model_create: bounding box, matrix-core operand
     tiles, model-wide seeding grid) -- one model, many surfaces is the reference's shape (completeExperimentFast.m:131-149).
@@ -179,40 +225,15 @@ class PreparedModel:
         The workspace and the second transform block are cached on the model; calls that may overlap on two streams pass
         buffers of their own, out=(T_out, T_step, n_close, sum_d2, empty, ws, T_tmp) with ws of
         pcreg_dev_model_refit_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
-        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
-            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
-        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
-            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
-        r2, steps = float(r2), int(steps)
+        st = _RefitSteps(q_soa, T_dev, steps)
+        r2 = float(r2)
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
-        if steps < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
-        dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
-        need = max(int(lib().pcreg_dev_model_refit_workspace(Q, B, self.M)), 256)
-        if out is not None:
-            T_out, T_step, n_close, sum_d2, empty, ws, T_tmp = out
-            if steps > 1 and T_tmp is None:
-                raise ValueError("more than one step needs the second transform block, T_tmp")
-        else:
-            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            n_close = torch.empty(B, dtype=torch.int32, device=dev)
-            sum_d2 = torch.empty(B, dtype=torch.float64, device=dev)
-            empty = torch.empty(B, dtype=torch.int32, device=dev)
-            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
-            ws = getattr(self, "_refit_ws_t", None)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._refit_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
-            with torch.cuda.device(dev):
-                src = T_dev
-                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
-                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
-                    check(lib().pcreg_dev_model_refit_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B, r2,
-                                                          _p(dst), _p(T_step), _p(n_close), _p(sum_d2), _p(empty), _p(ws), ws.numel(), _stream()))
-                    src = dst
-        return T_out, T_step, n_close, sum_d2, empty
+
+        def call(src, dst, T_step, n_close, sum_d2, empty, ws):
+            check(lib().pcreg_dev_model_refit_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(dst), _p(T_step), _p(n_close), _p(sum_d2), _p(empty),
+                                                  _p(ws), ws.numel(), _stream()))
+        return st.run(self, "_refit_ws_t", lib().pcreg_dev_model_refit_workspace(st.Q, st.B, self.M), (torch.int32, torch.float64, torch.int32), out, call)
 
     def refit_plane(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, normals: torch.Tensor, steps: int = 1, out=None):
         """B transforms refitted by the linearised point-to-plane step, `steps` times over, on torch's current stream
@@ -224,45 +245,22 @@ class PreparedModel:
         normals are not written.  The workspace and the second transform block are cached on the model; calls that may overlap
         on two streams pass buffers of their own, out=(T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty, ws, T_tmp) with
         ws of pcreg_dev_model_refit_plane_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
-        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
-            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
-        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
-            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
+        st = _RefitSteps(q_soa, T_dev, steps)
         M = self.M
         if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
                 or normals.device != q_soa.device):
             raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the queries' device (the row stride is the leading dimension)")
-        r2, steps = float(r2), int(steps)
+        r2 = float(r2)
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
-        if steps < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
-        dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
-        need = max(int(lib().pcreg_dev_model_refit_plane_workspace(Q, B, M)), 256)
-        if out is not None:
-            T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty, ws, T_tmp = out
-            if steps > 1 and T_tmp is None:
-                raise ValueError("more than one step needs the second transform block, T_tmp")
-        else:
-            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            n_close, n_plane, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
-            sum_d2, sum_res2 = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
-            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
-            ws = getattr(self, "_refit_plane_ws_t", None)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._refit_plane_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
-            nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=dev)      # (no rows: any address, never read)
-            with torch.cuda.device(dev):
-                src = T_dev
-                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
-                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
-                    check(lib().pcreg_dev_model_refit_plane_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B, r2,
-                                                                _p(nrm), max(int(nrm.stride(0)), M), _p(dst), _p(T_step), _p(n_close), _p(sum_d2),
-                                                                _p(n_plane), _p(sum_res2), _p(empty), _p(ws), ws.numel(), _stream()))
-                    src = dst
-        return T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty
+        nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=st.dev)      # (no rows: any address, never read)
+
+        def call(src, dst, T_step, n_close, sum_d2, n_plane, sum_res2, empty, ws):
+            check(lib().pcreg_dev_model_refit_plane_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(nrm), max(int(nrm.stride(0)), M), _p(dst),
+                                                        _p(T_step), _p(n_close), _p(sum_d2), _p(n_plane), _p(sum_res2), _p(empty), _p(ws), ws.numel(),
+                                                        _stream()))
+        return st.run(self, "_refit_plane_ws_t", lib().pcreg_dev_model_refit_plane_workspace(st.Q, st.B, M),
+                      (torch.int32, torch.float64, torch.int32, torch.float64, torch.int32), out, call)
 
     def refit_gicp(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, normals: torch.Tensor, q_normals: torch.Tensor, epsilon: float = 1e-3,
                    steps: int = 1, out=None):
@@ -275,51 +273,28 @@ class PreparedModel:
         Nothing given is written.  The workspace and the second transform block are cached on the model; calls that may overlap
         on two streams pass buffers of their own, out=(T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws, T_tmp) with
         ws of pcreg_dev_model_refit_gicp_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
-        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
-            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
-        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
-            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
-        M, Q = self.M, int(q_soa.shape[1])
+        st = _RefitSteps(q_soa, T_dev, steps)
+        M, Q = self.M, st.Q
         if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
                 or normals.device != q_soa.device):
             raise TypeError("normals are a [3, M] float32 tensor with contiguous rows on the queries' device (the row stride is the leading dimension)")
         if (q_normals.dtype != torch.float32 or q_normals.dim() != 2 or q_normals.shape[0] != 3 or q_normals.shape[1] != Q
                 or (Q and q_normals.stride(1) != 1) or q_normals.device != q_soa.device):
             raise TypeError("query normals are a [3, Q] float32 tensor with contiguous rows on the queries' device (the row stride is the leading dimension)")
-        r2, steps, epsilon = float(r2), int(steps), float(epsilon)
+        r2, epsilon = float(r2), float(epsilon)
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
-        if steps < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
         if not 0.0 < epsilon <= 1.0:
             raise ValueError(f"epsilon must lie in (0, 1], got {epsilon}")
-        dev, B = q_soa.device, T_dev.numel() // 16
-        need = max(int(lib().pcreg_dev_model_refit_gicp_workspace(Q, B, M)), 256)
-        if out is not None:
-            T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws, T_tmp = out
-            if steps > 1 and T_tmp is None:
-                raise ValueError("more than one step needs the second transform block, T_tmp")
-        else:
-            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            n_close, n_pairs, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
-            sum_d2, sum_res2 = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
-            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
-            ws = getattr(self, "_refit_gicp_ws_t", None)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._refit_gicp_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
-            nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=dev)      # (no rows: any address, never read)
-            with torch.cuda.device(dev):
-                src = T_dev
-                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
-                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
-                    check(lib().pcreg_dev_model_refit_gicp_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B, r2,
-                                                               _p(nrm), max(int(nrm.stride(0)), M), _p(q_normals) if Q else None,
-                                                               max(int(q_normals.stride(0)), Q, 1) if Q else 1, epsilon, _p(dst), _p(T_step), _p(n_close),
-                                                               _p(sum_d2), _p(n_pairs), _p(sum_res2), _p(empty), _p(ws), ws.numel(), _stream()))
-                    src = dst
-        return T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty
+        nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=st.dev)      # (no rows: any address, never read)
+
+        def call(src, dst, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws):
+            check(lib().pcreg_dev_model_refit_gicp_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(nrm), max(int(nrm.stride(0)), M),
+                                                       _p(q_normals) if Q else None, max(int(q_normals.stride(0)), Q, 1) if Q else 1, epsilon, _p(dst),
+                                                       _p(T_step), _p(n_close), _p(sum_d2), _p(n_pairs), _p(sum_res2), _p(empty), _p(ws), ws.numel(),
+                                                       _stream()))
+        return st.run(self, "_refit_gicp_ws_t", lib().pcreg_dev_model_refit_gicp_workspace(Q, st.B, M),
+                      (torch.int32, torch.float64, torch.int32, torch.float64, torch.int32), out, call)
 
     def refit_cpd(self, q_soa: torch.Tensor, T_dev: torch.Tensor, sigma2=0.0, outlier: float = 0.1, steps: int = 1, out=None):
         """B transforms refitted by the coherent-point-drift step (rigid CPD), `steps` times over, on torch's current stream
@@ -332,47 +307,24 @@ class PreparedModel:
         transform block are cached on the model; calls that may overlap on two streams pass buffers of their own,
         out=(T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty, ws, T_tmp) with ws of
         pcreg_dev_model_refit_cpd_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
-        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
-            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
-        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
-            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
-        M, Q = self.M, int(q_soa.shape[1])
-        steps, outlier = int(steps), float(outlier)
-        if steps < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
+        st = _RefitSteps(q_soa, T_dev, steps)
+        outlier = float(outlier)
         if not 0.0 <= outlier < 1.0:
             raise ValueError(f"outlier must lie in [0, 1), got {outlier}")
-        dev, B = q_soa.device, T_dev.numel() // 16
         if isinstance(sigma2, torch.Tensor):
-            if sigma2.dtype != torch.float64 or not sigma2.is_contiguous() or sigma2.numel() != B or sigma2.device != dev:
+            if sigma2.dtype != torch.float64 or not sigma2.is_contiguous() or sigma2.numel() != st.B or sigma2.device != st.dev:
                 raise TypeError("sigma2 is a number or a contiguous float64 tensor of B numbers on the queries' device")
             sig = sigma2
         else:
-            sig = torch.full((max(B, 1),), float(sigma2), dtype=torch.float64, device=dev)
-        need = max(int(lib().pcreg_dev_model_refit_cpd_workspace(Q, B, M)), 256)
-        if out is not None:
-            T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty, ws, T_tmp = out
-            if steps > 1 and T_tmp is None:
-                raise ValueError("more than one step needs the second transform block, T_tmp")
-        else:
-            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            sigma2_out, Np, sum_res2, sum_d2 = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(4))
-            n_live, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
-            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
-            ws = getattr(self, "_refit_cpd_ws_t", None)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._refit_cpd_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
-            with torch.cuda.device(dev):
-                src = T_dev
-                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
-                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
-                    check(lib().pcreg_dev_model_refit_cpd_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(src), B,
-                                                              _p(sig), outlier, _p(dst), _p(T_step), _p(sigma2_out), _p(Np), _p(sum_res2), _p(sum_d2),
-                                                              _p(n_live), _p(empty), _p(ws), ws.numel(), _stream()))
-                    src, sig = dst, sigma2_out         # (sigma2_out may alias sigma2_in: a step reads it before its last kernel writes it)
-        return T_out, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty
+            sig = torch.full((max(st.B, 1),), float(sigma2), dtype=torch.float64, device=st.dev)
+
+        def call(src, dst, T_step, sigma2_out, Np, sum_res2, sum_d2, n_live, empty, ws):
+            nonlocal sig
+            check(lib().pcreg_dev_model_refit_cpd_f32(self.handle, *st.q_args, _p(src), st.B, _p(sig), outlier, _p(dst), _p(T_step), _p(sigma2_out),
+                                                      _p(Np), _p(sum_res2), _p(sum_d2), _p(n_live), _p(empty), _p(ws), ws.numel(), _stream()))
+            sig = sigma2_out                           # (sigma2_out may alias sigma2_in: a step reads it before its last kernel writes it)
+        return st.run(self, "_refit_cpd_ws_t", lib().pcreg_dev_model_refit_cpd_workspace(st.Q, st.B, self.M),
+                      (torch.float64, torch.float64, torch.float64, torch.float64, torch.int32, torch.int32), out, call)
 
     def cluster(self, r2: float, out=None):
         """clusterPoints(model, r) over the model's own rows with r2 = r^2, on torch's current stream
@@ -825,42 +777,17 @@ class NdtModel:
         transform that went INTO the last step.  T_dev is not written.  The workspace is cached on the handle; calls that may
         overlap on two streams pass buffers of their own, out=(T_out, T_step, n_pairs, sum_e, empty, ws, T_tmp) with ws of
         pcreg_dev_ndt_refit_workspace(Q, B) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
-        if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or (q_soa.shape[1] and q_soa.stride(1) != 1):
-            raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
-        if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
-            raise TypeError("transforms are a contiguous float64 tensor of B x 16 numbers on the queries' device")
-        neighbors, outlier_ratio, steps = int(neighbors), float(outlier_ratio), int(steps)
+        st = _RefitSteps(q_soa, T_dev, steps, empty_any_stride=True)
+        neighbors, outlier_ratio = int(neighbors), float(outlier_ratio)
         if neighbors not in (1, 7):
             raise ValueError(f"neighbors must be 1 or 7, got {neighbors}")
         if not 0.0 <= outlier_ratio < 1.0:
             raise ValueError(f"outlier_ratio must lie in [0, 1), got {outlier_ratio}")
-        if steps < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
-        dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
-        need = max(int(lib().pcreg_dev_ndt_refit_workspace(Q, B)), 256)
-        if out is not None:
-            T_out, T_step, n_pairs, sum_e, empty, ws, T_tmp = out
-            if steps > 1 and T_tmp is None:
-                raise ValueError("more than one step needs the second transform block, T_tmp")
-        else:
-            T_out = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            T_step = torch.empty((B, 16), dtype=torch.float64, device=dev)
-            n_pairs, empty = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
-            sum_e = torch.empty(B, dtype=torch.float64, device=dev)
-            T_tmp = torch.empty((B, 16), dtype=torch.float64, device=dev) if steps > 1 else None
-            ws = getattr(self, "_refit_ws_t", None)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._refit_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
-            with torch.cuda.device(dev):
-                src = T_dev
-                for s in range(steps):                 # the last step writes T_out: the blocks alternate backwards from it
-                    dst = T_out if (steps - 1 - s) % 2 == 0 else T_tmp
-                    check(lib().pcreg_dev_ndt_refit_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1) if Q else 1, _p(src), B,
-                                                        neighbors, outlier_ratio, _p(dst), _p(T_step), _p(n_pairs), _p(sum_e), _p(empty), _p(ws),
-                                                        C.c_size_t(ws.numel()), _stream()))
-                    src = dst
-        return T_out, T_step, n_pairs, sum_e, empty
+
+        def call(src, dst, T_step, n_pairs, sum_e, empty, ws):
+            check(lib().pcreg_dev_ndt_refit_f32(self.handle, *st.q_args, _p(src), st.B, neighbors, outlier_ratio, _p(dst), _p(T_step), _p(n_pairs),
+                                                _p(sum_e), _p(empty), _p(ws), C.c_size_t(ws.numel()), _stream()))
+        return st.run(self, "_refit_ws_t", lib().pcreg_dev_ndt_refit_workspace(st.Q, st.B), (torch.int32, torch.float64, torch.int32), out, call)
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:

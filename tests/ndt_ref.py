@@ -224,6 +224,44 @@ def sums(tab, p, neighbors, d2):
     return out, len(qi)
 
 
+def info_pair64(C, x, u, e, acc0, weighted):
+    """info_pair.hpp in float64, one operation per operation, in its order: the 27 sums from acc0 after one pair (C [6] xx xy xz yy
+    yz zz, x [3], u [3]), y = C x and qq = x . y.  Products and differences are plain float64; weighted: each add is the correctly
+    rounded fma(e, term, sum) for a finite e > 0, formed exactly in rationals and rounded once; otherwise sum + term and e is not
+    read."""
+    from fractions import Fraction
+    C, x, u = (np.asarray(v, np.float64) for v in (C, x, u))
+    acc = [np.float64(v) for v in acc0]
+    e = float(e)
+
+    def add(k, term):
+        if not weighted:
+            acc[k] = acc[k] + term
+            return
+        exact = Fraction(e) * Fraction(float(term)) + Fraction(float(acc[k]))
+        # (an exact zero is -0.0 only as the sum of two negative zeros; e > 0, so the product has the term's sign)
+        acc[k] = np.float64(float(exact)) if exact else np.float64(-0.0 if term == 0 and np.signbit(term) and np.signbit(acc[k]) else 0.0)
+
+    def cross(a, b0, b1, b2):
+        return [a[1] * b2 - a[2] * b1, a[2] * b0 - a[0] * b2, a[0] * b1 - a[1] * b0]
+    y = [(C[0] * x[0] + C[1] * x[1]) + C[2] * x[2], (C[1] * x[0] + C[3] * x[1]) + C[4] * x[2], (C[2] * x[0] + C[4] * x[1]) + C[5] * x[2]]
+    qq = (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]
+    W = [cross(u, C[0], C[1], C[2]), cross(u, C[1], C[3], C[4]), cross(u, C[2], C[4], C[5])]
+    for j in range(3):
+        M = cross(u, W[0][j], W[1][j], W[2][j])
+        for i in range(j + 1):
+            add(plane_ref.tri(i, j), M[i])
+        for i in range(3):
+            add(plane_ref.tri(i, 3 + j), W[j][i])
+    for k, (a, b) in enumerate(((3, 3), (3, 4), (3, 5), (4, 4), (4, 5), (5, 5))):
+        add(plane_ref.tri(a, b), C[k])
+    gy = cross(u, y[0], y[1], y[2])
+    for i in range(3):
+        add(21 + i, gy[i])
+        add(24 + i, y[i])
+    return np.array(acc, np.float64), np.array(y, np.float64), np.float64(qq)
+
+
 def step(q, tab, T, neighbors=1, outlier_ratio=0.55):
     q = np.asarray(q, np.float32).reshape(-1, 3)
     T = np.asarray(T, np.float64).reshape(-1, 4, 4)
