@@ -120,6 +120,10 @@ int  pcreg_debug_knn_unit_stats(long long out[2], int reset);
  * cells, [2] the rows ranked for them.  The key does not change which path a query takes.  Off: no extra work; on: one small
  * launch per search, no host sync.  The read synchronises the device. */
 int  pcreg_debug_knn_direct_stats(long long out[3], int reset);
+/* With pcreg_debug_set("knn_stats", 1): the farthest point sampling summed over the calls since the last reset --
+ * out[0] steps run (the sum of n_out), [1] live rows measured against a sample; without culling that is nf x n_out.  Off: no
+ * extra work.  The read synchronises the device. */
+int  pcreg_debug_fps_stats(long long out[2], int reset);
 /* With pcreg_debug_set("ransac_stats", 1): the counters of the staged RANSAC chain's bounded second pass summed over the calls
  * since the last reset -- out[0] bounded passes run, [1] (refit, 512-correspondence block) units scanned (seed refits
  * included), [2] the units a full pass scans.  Off: no extra work.  The read synchronises the device. */
@@ -519,6 +523,41 @@ int pcreg_model_denoise_f32(pcreg_model* model, int k, double threshold, double*
  * ldm < M, m NULL with M > 0. */
 int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double threshold, double* mean_dist, int32_t* inliers,
                             int32_t* n_inliers, double* stats);
+/* Farthest point sampling of the rows of the model: at most K rows, each the live row farthest from all rows chosen before it, with
+ * the covering radius at every row (PointNet++'s sampling layer; Open3D's farthest_point_down_sample).  THE CONTRACT of every tier
+ * (device, host, MEX, Python):
+ * inputs -- a prepared model of M fp32 rows, M <= PCREG_FPS_MAX_ROWS; K >= 0, the capacity of idx / dist and the most samples wanted;
+ * start, a 0-based ORIGINAL row with 0 <= start < M, or -1 for the lowest live original row; stop_d2, a float >= 0 and not NaN
+ * (+inf is allowed and gives one sample).
+ * A row is LIVE when its three coordinates are finite.  Dead rows are never samples and never measured; nf is the live count.
+ * THE DISTANCE is the point search's: fmaf(dz,dz, fmaf(dy,dy, dx*dx)) with fp32 differences; it is sign-symmetric.
+ * THE STATE: D[i] = +inf and L[i] = 0 for every live row i.
+ * THE LOOP: s_0 = start (or the lowest live row).  For j = 0, 1, ...:
+ *   1. idx[j] = s_j; dist[j] is the value D[s_j] had when s_j was chosen; dist[0] = +inf.
+ *   2. For every live i, d = the distance of row i and row s_j; when d < D[i] (strictly), D[i] = d and L[i] = j + 1.
+ *   3. (mx, r): the largest D[i] over the live rows, ties to the LOWEST ORIGINAL row.
+ *   4. Stop with *n_out = j + 1 when j + 1 == K or when !(mx > stop_d2); otherwise s_{j+1} = r.
+ * So: with stop_d2 = 0 the loop ends by itself once every live row coincides with a sample (squared distances that underflow to 0
+ * included); a row never repeats in idx; dist[1..] is non-increasing; +inf distances (overflow) are ordinary values.
+ * outputs, each may be NULL except n_out -- idx [K]: int32 original rows in selection order, 0-based (1-based at the MEX / MATLAB
+ * edge); dist [K]: fp32, squared; *n_out; *cover_d2: one fp32, the mx of the last step -- after the call every live row is within
+ * sqrt(cover_d2) of a sample; min_dist [M]: fp32 by original row, the final D, NaN for a dead row; label [M]: int32 by original row,
+ * the final L: the 1-based position in idx of the nearest sample, ties to the EARLIEST sample, 0 for a dead row (and for a live row
+ * whose every distance overflowed to +inf, which the strict < never labels).  Only idx[0 .. n_out) and dist[0 .. n_out) are written.
+ * K = 0, M = 0 or nf = 0: *n_out = 0; cover_d2, min_dist and label are still written, as NaN / NaN / 0 for whatever rows exist;
+ * nothing else is written.  (K = 0 is judged first: it does not look at the start row.)
+ * The result is a function of (model rows, K, start, stop_d2) only: culling, the call, the stream and the workspace's previous
+ * contents change no bit.
+ * PCREG_E_ARG before anything runs: K < 0, start outside -1 .. M - 1 with M > 0, stop_d2 negative or NaN, model NULL, n_out NULL,
+ * M > PCREG_FPS_MAX_ROWS.  A start row that is DEAD is known only on the device: PCREG_E_ARG after the run, with a message that names
+ * start and no output written. */
+#define PCREG_FPS_MAX_ROWS 2097152               /* 2^21: 4096 tiles of 512 rows, the tile table one workgroup's LDS holds */
+int pcreg_model_fps_f32(pcreg_model* model, int K, int start, float stop_d2, int32_t* idx /* [K] or NULL */, float* dist /* [K] or NULL */,
+                        int32_t* n_out, float* cover_d2 /* or NULL */, float* min_dist /* [M] or NULL */, int32_t* label /* [M] or NULL */);
+/* The same without a handle: uploads and prepares the cloud for this call only.  Also PCREG_E_ARG: M < 0, ldm < M, m NULL with
+ * M > 0. */
+int pcreg_point_fps_f32(const float* m, int M, int ldm, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out,
+                        float* cover_d2, float* min_dist, int32_t* label);
 /* The FPFH descriptor of every row of the model (MATLAB's extractFPFHFeatures(ptCloud, 'NumNeighbors', k)): 33 numbers a row from
  * its k nearest rows and a normal per row.  The name and the pair features are Rusu's (Fast Point Feature Histograms, ICRA 2009);
  * the weighting and the normalisation have the form common implementations use.  THE CONTRACT of every tier (device, host, MEX,
@@ -1299,6 +1338,21 @@ size_t pcreg_dev_model_denoise_workspace(int M, int k);
 int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double threshold, double* mean_dist /* or NULL */,
                                 int32_t* inliers /* or NULL */, int32_t* n_inliers /* or NULL */, double* stats /* [4] or NULL */,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_fps_f32's contract on the device: idx [K], dist [K], n_out, cover_d2, min_dist [M], label [M] and info
+ * (one int32) are device pointers, each may be NULL except n_out.  info = 0 after a run; a DEAD start row, which only the device can
+ * see, gives info = 1 and *n_out = 0 with nothing else written.  Two launches: ONE workgroup of 1024 threads runs every step -- the
+ * steps are strictly sequential, and no workgroup waits for another -- keeping per 512-row tile its (max D, original row, sorted row)
+ * and box in LDS, 36 bytes a tile, which is what bounds M by PCREG_FPS_MAX_ROWS; a step visits only the tiles, and inside them the
+ * 64-row units, whose box DESIGN 4.1's rule does not certify farther from the sample than their largest D.  The second launch
+ * scatters min_dist and label to original-row order.  Nothing synchronises and nothing is read on the host.  Workspace, with
+ * R = max(M, 1) and U = 8 max(ceil(M / 512), 1): 2 roundup(4 R, 256) + roundup(16 U, 256) + 256 bytes, whatever K; 0 for M < 0 or
+ * M > PCREG_FPS_MAX_ROWS; a workspace shorter than that is PCREG_E_ARG too.  A handle may serve several streams at once, each call
+ * with its own workspace.  The debug key "knn_nocull" visits every tile and unit (same bits); "knn_stats" counts for
+ * pcreg_debug_fps_stats. */
+size_t pcreg_dev_model_fps_workspace(int M, int K);
+int pcreg_dev_model_fps_f32(const pcreg_dev_model* model, int K, int start, float stop_d2, int32_t* idx /* or NULL */,
+                            float* dist /* or NULL */, int32_t* n_out, float* cover_d2 /* or NULL */, float* min_dist /* or NULL */,
+                            int32_t* label /* or NULL */, int32_t* info /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* pcreg_model_fpfh_f32's contract on the device: normals_dev [3 * ldn] (what pcreg_dev_model_normals_f32 writes; may
  * not be NULL with M > 0), fpfh [M][33] double and spfh [M][33] uint8 (or NULL) are device pointers, both ROW-major by original row
  * -- fpfh is what pcreg_dev_get_matches takes as row-major descriptors with D = 33.  Three launches: the seed bound of every sorted

@@ -65,6 +65,16 @@
 //                                          NaN or Inf; thr = mean + threshold * std of the finite ones; a row is an inlier iff
 //                                          meanDist <= thr; the last two outputs are built only when asked for
 //                                          (matlab/pcdenoiseModel.m, matlab/pcdenoiseFast.m)
+//   'modelFps', handle, K, start, stopD2 | 'pointFps', pts (single M x 3), K, start, stopD2 -> idx (n x 1 uint32, 1-based rows in
+//                                          selection order), d2 (n x 1 single), label (M x 1 uint32), minD2 (M x 1 single), coverD2
+//                                          (single scalar): farthest point sampling (pcreg_model_fps_f32) -- at most K rows (a
+//                                          whole number >= 0), each the finite row farthest from all rows chosen before it; start a
+//                                          1-based row, or 0 for the lowest finite row; stopD2 a single scalar >= 0 (Inf allowed), the
+//                                          SQUARED distance at which the sampling stops early; d2 the squared distance of each
+//                                          sample to the earlier ones (d2(1) = Inf); label the 1-based position in idx of the
+//                                          nearest sample (0 for a row with a NaN or Inf) and minD2 the squared distance to it
+//                                          (NaN there); single stays single; outputs past the first are built only when asked
+//                                          for (matlab/farthestPointsModel.m, matlab/farthestPointsFast.m)
 //   'modelFpfh', handle, k, normals (single M x 3 | []), kNormals, viewpoint | 'pointFpfh', pts (single M x 3), k, normals, kNormals,
 //                                          viewpoint -> features (M x 33 double), spfh (M x 33 uint8):
 //                                          extractFPFHFeatures(ptCloud, 'NumNeighbors', k) in this library's rule -- the FPFH
@@ -342,6 +352,43 @@ static int denoise_on_handle(pcreg_model* h, int k, double t, int nout, mxArray*
         if (nout > 2) out[2] = mxCreateDoubleScalar(stats[0]);
     } else if (om) mxDestroyArray(om);
     mxDestroyArray(ti);
+    return rc;
+}
+
+// K, start and stopD2 of the sampling commands, a[0 .. 2]: two whole double scalars 0 .. 2^31 - 1 (start is 1-based, 0 = the lowest
+// finite row), a single scalar >= 0 and not NaN
+static bool fps_args_ok(const mxArray* const* a) {
+    return whole_scalar_ok(a[0], 0.0, 2147483647.0) && whole_scalar_ok(a[1], 0.0, 2147483647.0) && mxIsSingle(a[2]) &&
+           mxGetM(a[2]) * mxGetN(a[2]) == 1 && *(const float*)mxGetData(a[2]) >= 0.0f;
+}
+// the outputs of 'modelFps' / 'pointFps': idx (n x 1 uint32, 1-based) and, as far as nout asks, d2 (n x 1 single), label (M x 1
+// uint32), minD2 (M x 1 single), coverD2 (single scalar).  Nothing is left allocated on an error.
+static int fps_on_handle(pcreg_model* h, int K, int start1, float stop_d2, int nout, mxArray* out[5]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    mxArray* ti = mxCreateNumericMatrix((size_t)(K > 0 ? K : 1), 1, mxINT32_CLASS, mxREAL);
+    mxArray* td = nout > 1 ? mxCreateNumericMatrix((size_t)(K > 0 ? K : 1), 1, mxSINGLE_CLASS, mxREAL) : nullptr;
+    mxArray* ol = nout > 2 ? mxCreateNumericMatrix((size_t)M, 1, mxUINT32_CLASS, mxREAL) : nullptr;      // (a label is never negative)
+    mxArray* om = nout > 3 ? mxCreateNumericMatrix((size_t)M, 1, mxSINGLE_CLASS, mxREAL) : nullptr;
+    int32_t n = 0;
+    float cover = 0.0f;
+    rc = pcreg_model_fps_f32(h, K, start1 - 1, stop_d2, (int32_t*)mxGetData(ti), td ? (float*)mxGetData(td) : nullptr, &n, &cover,
+                             om && M > 0 ? (float*)mxGetData(om) : nullptr, ol && M > 0 ? (int32_t*)mxGetData(ol) : nullptr);
+    if (rc == PCREG_OK) {
+        out[0] = mxCreateNumericMatrix((size_t)n, 1, mxUINT32_CLASS, mxREAL);
+        const int32_t* src = (const int32_t*)mxGetData(ti);
+        uint32_t* dst = (uint32_t*)mxGetData(out[0]);
+        for (int32_t i = 0; i < n; ++i) dst[i] = (uint32_t)src[i] + 1u;
+        if (td) {
+            out[1] = mxCreateNumericMatrix((size_t)n, 1, mxSINGLE_CLASS, mxREAL);
+            if (n > 0) memcpy(mxGetData(out[1]), mxGetData(td), sizeof(float) * (size_t)n);
+        }
+        out[2] = ol; out[3] = om;
+        if (nout > 4) { out[4] = mxCreateNumericMatrix(1, 1, mxSINGLE_CLASS, mxREAL); *(float*)mxGetData(out[4]) = cover; }
+    } else { if (ol) mxDestroyArray(ol); if (om) mxDestroyArray(om); }
+    mxDestroyArray(ti);
+    if (td) mxDestroyArray(td);
     return rc;
 }
 
@@ -1323,7 +1370,30 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; }
         }
-    } else if (!strcmp(cmd, "modelIss")) {                    // [keypoints, saliency, eig, nNeighbors] = pcreg_mex('modelIss', h, r2s, r2n, t21, t32, minNb)
+    } else if (!strcmp(cmd, "modelFps")) {                    // [idx, d2, label, minD2, coverD2] = pcreg_mex('modelFps', h, K, start, stopD2)
+        if (nrhs != 5 || !mxIsUint64(prhs[1]) || !fps_args_ok(prhs + 2))
+            usage = "modelFps: handle (uint64), K (a whole number >= 0), start (a 1-based row, or 0 for the lowest finite row), stopD2 (a single "
+                    "scalar >= 0, the squared stop distance)";
+        else {
+            mxArray* out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            rc = fps_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (int)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]),
+                               *(const float*)mxGetData(prhs[4]), nlhs, out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; if (out[3]) plhs[3] = out[3]; if (out[4]) plhs[4] = out[4]; }
+        }
+    } else if (!strcmp(cmd, "pointFps")) {                    // [idx, d2, label, minD2, coverD2] = pcreg_mex('pointFps', single(pts), K, start, stopD2)
+        if (nrhs != 5 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !fps_args_ok(prhs + 2))
+            usage = "pointFps: pts (single M x 3), K (a whole number >= 0), start (a 1-based row, or 0 for the lowest finite row), stopD2 (a single "
+                    "scalar >= 0, the squared stop distance)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = fps_on_handle(h, (int)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), *(const float*)mxGetData(prhs[4]), nlhs, out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; if (out[1]) plhs[1] = out[1]; if (out[2]) plhs[2] = out[2]; if (out[3]) plhs[3] = out[3]; if (out[4]) plhs[4] = out[4]; }
+        }
+    } else if (!strcmp(cmd, "modelIss")) {                   // [keypoints, saliency, eig, nNeighbors] = pcreg_mex('modelIss', h, r2s, r2n, t21, t32, minNb)
         if (nrhs != 7 || !mxIsUint64(prhs[1]) || !iss_args_ok(prhs + 2))
             usage = "modelIss: handle (uint64), r2Salient and r2NonMax (single scalars, the squared radii: finite, normal, > 0), threshold21 and "
                     "threshold32 (finite double scalars > 0), minNeighbors (a whole number >= 1)";

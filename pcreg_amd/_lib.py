@@ -68,6 +68,7 @@ SYMBOLS = [
     "pcreg_model_refit_gicp_f32", "pcreg_dev_model_refit_gicp_workspace", "pcreg_dev_model_refit_gicp_f32",
     "pcreg_model_refit_cpd_f32", "pcreg_dev_model_refit_cpd_workspace", "pcreg_dev_model_refit_cpd_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
+    "pcreg_model_fps_f32", "pcreg_point_fps_f32", "pcreg_dev_model_fps_workspace", "pcreg_dev_model_fps_f32", "pcreg_debug_fps_stats",
     "pcreg_model_fpfh_f32", "pcreg_point_fpfh_f32", "pcreg_dev_model_fpfh_workspace", "pcreg_dev_model_fpfh_f32",
     "pcreg_model_fpfh_radius_f32", "pcreg_point_fpfh_radius_f32", "pcreg_dev_model_fpfh_radius_workspace", "pcreg_dev_model_fpfh_radius_count_f32",
     "pcreg_dev_model_fpfh_radius_f32",
@@ -169,6 +170,14 @@ def lib() -> C.CDLL:
             L.pcreg_dev_model_denoise_f32.argtypes = [vp, i, d, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_denoise_f32.argtypes = [vp, i, d, vp, vp, vp, vp]
             L.pcreg_point_denoise_f32.argtypes = [vp, i, i, i, d, vp, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_model_fps_workspace"):       # (an older build given through PCREG_LIB lacks the farthest point sampling)
+            L.pcreg_dev_model_fps_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_fps_workspace.argtypes = [C.c_int] * 2
+            vp, i, f = C.c_void_p, C.c_int, C.c_float                            # (a float by value: declared)
+            L.pcreg_dev_model_fps_f32.argtypes = [vp, i, i, f, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_fps_f32.argtypes = [vp, i, i, f, vp, vp, vp, vp, vp, vp]
+            L.pcreg_point_fps_f32.argtypes = [vp, i, i, i, i, f, vp, vp, vp, vp, vp, vp]
+            L.pcreg_debug_fps_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
         if hasattr(L, "pcreg_dev_model_fpfh_workspace"):      # (an older build given through PCREG_LIB lacks the FPFH)
             L.pcreg_dev_model_fpfh_workspace.restype = C.c_size_t
             L.pcreg_dev_model_fpfh_workspace.argtypes = [C.c_int] * 2

@@ -1069,6 +1069,50 @@ def point_denoise(pts, k: int = 4, threshold: float = 1.0) -> dict:
     return _denoise_call(lambda md, inl, n, st: check(lib().pcreg_point_denoise_f32(m.ctypes.data, M, max(M, 1), k, threshold, md, inl, n, st)), M)
 
 
+FPS_MAX_ROWS = 1 << 21      # PCREG_FPS_MAX_ROWS (include/pcreg.h)
+
+
+def _fps_args(M: int, K, start, stop_d2):
+    K, start, stop_d2 = int(K), int(start), float(stop_d2)
+    if K < 0:
+        raise ValueError(f"K must be >= 0, got {K}")
+    if M > FPS_MAX_ROWS:
+        raise ValueError(f"farthest point sampling serves at most {FPS_MAX_ROWS} rows, got {M}")
+    if M > 0 and not -1 <= start < M:
+        raise ValueError(f"start must be -1 or a 0-based row below {M}, got {start}")
+    if not stop_d2 >= 0.0:
+        raise ValueError(f"stop_d2 must be >= 0 and not NaN, got {stop_d2}")
+    return K, start, stop_d2
+
+
+def _fps_call(call, M: int, K: int) -> dict:
+    idx = np.zeros(max(K, 1), dtype=np.int32)
+    dist = np.zeros(max(K, 1), dtype=np.float32)
+    n = C.c_int32(0)
+    cover = C.c_float(0.0)
+    md = np.zeros(max(M, 1), dtype=np.float32)
+    lab = np.zeros(max(M, 1), dtype=np.int32)
+    call(idx.ctypes.data, dist.ctypes.data, C.byref(n), C.byref(cover), md.ctypes.data, lab.ctypes.data)
+    return dict(idx=idx[:n.value].copy(), dist=dist[:n.value].copy(), n_out=int(n.value), cover_d2=np.float32(cover.value), min_dist=md[:M],
+                label=lab[:M])
+
+
+def point_farthest_points(pts, K: int, start: int = -1, stop_d2: float = 0.0) -> dict:
+    """Farthest point sampling of pts (pcreg_model_fps_f32's contract): at most K rows, each the finite row farthest from all rows
+    chosen before it, starting at the 0-based row `start` (-1: the lowest finite row) and stopping early once every finite row is
+    within stop_d2 (a SQUARED distance) of a sample.  A dict of numpy arrays: idx [n_out] int32 0-based rows in selection order;
+    dist [n_out] float32, the squared distance of each sample to the ones before it (dist[0] = inf, non-increasing after);
+    n_out; cover_d2 (float32), the largest squared distance of a finite row to its nearest sample; min_dist [M] float32 and
+    label [M] int32, per row that distance and the 1-based position in idx of the nearest sample (NaN / 0 for a non-finite row).
+    The cloud is prepared for this call only: keep a Model for repeated calls."""
+    m = _fcol(pts, np.float32)
+    if m.ndim != 2 or m.shape[1] != 3:
+        raise ValueError("pts must be M x 3")
+    M = m.shape[0]
+    K, start, stop_d2 = _fps_args(M, K, start, stop_d2)
+    return _fps_call(lambda *o: check(lib().pcreg_point_fps_f32(m.ctypes.data, M, max(M, 1), K, start, stop_d2, *o)), M, K)
+
+
 def unique_rows(A):
     """[C, ia] = unique(A, 'rows') for an n x 3 float64 array: (C [u, 3], ia [u] int32, 0-based).  Rows in lexicographic order by
     column 1, 2, 3 as numbers (-0 == +0); the first occurrence represents its run and C = A[ia] carries its bits.  A NaN anywhere
@@ -1458,6 +1502,14 @@ class Model:
             raise RuntimeError("model handle closed")
         k, threshold = _denoise_args(k, threshold)
         return _denoise_call(lambda md, inl, n, st: check(lib().pcreg_model_denoise_f32(self._h, k, threshold, md, inl, n, st)), self.M)
+
+    def farthest_points(self, K: int, start: int = -1, stop_d2: float = 0.0) -> dict:
+        """Farthest point sampling of the prepared model's own rows: at most K well-spread rows and the covering radius with every
+        one of them -- point_farthest_points's dict and contract."""
+        if self._h is None:
+            raise RuntimeError("model handle closed")
+        K, start, stop_d2 = _fps_args(self.M, K, start, stop_d2)
+        return _fps_call(lambda *o: check(lib().pcreg_model_fps_f32(self._h, K, start, stop_d2, *o)), self.M, K)
 
     def close(self):
         if self._h.value:

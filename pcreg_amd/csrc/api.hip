@@ -88,7 +88,7 @@ int debug_flag(DebugKey k) { return g_debug[k].load(std::memory_order_relaxed); 
 struct Counters { DebugKey key; int n; unsigned long long* dev; };
 static Counters g_match_stats{kDbgMatchStats, 8, nullptr}, g_knn_stats{kDbgKnnStats, 6, nullptr}, g_ransac_stats{kDbgRansacStats, 5, nullptr},
                 g_cluster_stats{kDbgClusterStats, 4, nullptr}, g_desc_stats{kDbgDescStats, 10, nullptr},
-                g_knn_direct_stats{kDbgKnnDirectStats, 3, nullptr};
+                g_knn_direct_stats{kDbgKnnDirectStats, 3, nullptr}, g_fps_stats{kDbgKnnStats, 2, nullptr};
 static unsigned long long* counters_dev(Counters& c) {
     if (!debug_flag(c.key)) return nullptr;
     if (!c.dev) {
@@ -116,6 +116,7 @@ unsigned long long* ransac_stats_dev() { return counters_dev(g_ransac_stats); }
 unsigned long long* cluster_stats_dev() { return counters_dev(g_cluster_stats); }
 unsigned long long* desc_stats_dev() { return counters_dev(g_desc_stats); }
 unsigned long long* knn_direct_stats_dev() { return counters_dev(g_knn_direct_stats); }
+unsigned long long* fps_stats_dev() { return counters_dev(g_fps_stats); }
 }
 
 extern "C" {
@@ -146,6 +147,7 @@ int pcreg_debug_match_stats(long long out[8], int reset) { return pcreg::counter
 int pcreg_debug_knn_stats(long long out[4], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 0, 4); }
 int pcreg_debug_knn_unit_stats(long long out[2], int reset) { return pcreg::counters_read(pcreg::g_knn_stats, out, reset, 4, 2); }
 int pcreg_debug_knn_direct_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_knn_direct_stats, out, reset); }
+int pcreg_debug_fps_stats(long long out[2], int reset) { return pcreg::counters_read(pcreg::g_fps_stats, out, reset); }
 int pcreg_debug_ransac_stats(long long out[3], int reset) { return pcreg::counters_read(pcreg::g_ransac_stats, out, reset, 0, 3); }
 int pcreg_debug_ransac_handover(long long out[3], int reset) {
     TRY(pcreg::counters_read(pcreg::g_ransac_stats, out, reset, 3, 2));
@@ -480,6 +482,16 @@ int pcreg_dev_model_denoise_f32(const pcreg_dev_model* model, int k, double thre
     PCREG_ARG(workspace_bytes >= denoise_ws_bytes(0, k));                    // (the smallest any model needs; the launcher checks this model's)
     GUARD();
     return launch_model_denoise(model->v, k, threshold, mean_dist, inliers, n_inliers, stats, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t pcreg_dev_model_fps_workspace(int M, int K) { return fps_ws_bytes(M, K); }
+int pcreg_dev_model_fps_f32(const pcreg_dev_model* model, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out,
+                            float* cover_d2, float* min_dist, int32_t* label, int32_t* info, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    PCREG_ARG(model && n_out && workspace && fps_args_ok(model->v.M, K, start, stop_d2));      // (host data of the handle: refused before the device)
+    PCREG_ARG(workspace_bytes >= fps_ws_bytes(model->v.M, K));
+    GUARD();
+    return launch_model_fps(model->v, K, start, stop_d2, idx, dist, n_out, cover_d2, min_dist, label, info, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 size_t pcreg_dev_model_fpfh_workspace(int M, int k) { return fpfh_ws_bytes(M, k); }
 int pcreg_dev_model_fpfh_f32(const pcreg_dev_model* model, int k, const float* normals, int ldn, double* fpfh, uint8_t* spfh, void* workspace,
@@ -1056,6 +1068,60 @@ int pcreg_point_denoise_f32(const float* m, int M, int ldm, int k, double thresh
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return denoise_on_view(st, v, k, threshold, mean_dist, inliers, n_inliers, stats);
+}
+
+// farthest point sampling of a prepared model's own rows: the two launches on the device, ONE read of the three words (count, info,
+// cover), then the rows the count names and the per-row outputs; a dead start row (info = 1) is refused with nothing written
+static int fps_on_view(Stage& st, const ModelView& v, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out,
+                       float* cover_d2, float* min_dist, int32_t* label) {
+    const int M = v.M;
+    int32_t *didx, *dword, *dlabel; float *ddist, *dmin; char* ws;
+    const size_t wsb = fps_ws_bytes(M, K);
+    TRY(st.take(idx ? (size_t)K : 0, &didx));
+    TRY(st.take(dist ? (size_t)K : 0, &ddist));
+    TRY(st.take(4, &dword));                                     // n_out, info, cover_d2
+    TRY(st.take(min_dist ? (size_t)M : 0, &dmin));
+    TRY(st.take(label ? (size_t)M : 0, &dlabel));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_fps(v, K, start, stop_d2, idx ? didx : nullptr, dist ? ddist : nullptr, dword, (float*)(dword + 2), min_dist ? dmin : nullptr,
+                         label ? dlabel : nullptr, dword + 1, ws, wsb, g_stream));
+    int32_t w[4] = {0, 0, 0, 0};
+    PCREG_HIP(hipMemcpyAsync(w, dword, sizeof w, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));                   // the count fixes how many rows come back
+    if (w[1] != 0) {
+        set_error("bad argument: start = %d is a row with a non-finite coordinate", start);
+        return PCREG_E_ARG;
+    }
+    const int32_t n = w[0];
+    if (idx && n > 0) PCREG_HIP(hipMemcpyAsync(idx, didx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    if (dist && n > 0) PCREG_HIP(hipMemcpyAsync(dist, ddist, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    if (min_dist && M > 0) PCREG_HIP(hipMemcpyAsync(min_dist, dmin, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    if (label && M > 0) PCREG_HIP(hipMemcpyAsync(label, dlabel, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    *n_out = n;
+    if (cover_d2) memcpy(cover_d2, &w[2], sizeof(float));
+    return PCREG_OK;
+}
+int pcreg_model_fps_f32(pcreg_model* model, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out, float* cover_d2,
+                        float* min_dist, int32_t* label) {
+    PCREG_ARG(model && n_out && fps_args_ok(model->M, K, start, stop_d2));
+    PCREG_ARG(model->dm != nullptr);
+    GUARD();
+    Stage st{scratch()};
+    return fps_on_view(st, model->dm->v, K, start, stop_d2, idx, dist, n_out, cover_d2, min_dist, label);
+}
+int pcreg_point_fps_f32(const float* m, int M, int ldm, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out,
+                        float* cover_d2, float* min_dist, int32_t* label) {
+    PCREG_ARG(n_out && M >= 0 && ldm >= M && (M == 0 || m) && fps_args_ok(M, K, start, stop_d2));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return fps_on_view(st, v, K, start, stop_d2, idx, dist, n_out, cover_d2, min_dist, label);
 }
 
 // FPFH of a prepared model's own rows: the normals uploaded once (or computed by the normals chain with k_normals and the

@@ -118,6 +118,9 @@ unsigned long long* knn_stats_dev();
 // Device counters of the direct answers (knn_fast.hip: knn_direct_kernel), or null while "knn_direct_stats" is off:
 //   [0] two-nearest searches   [1] queries answered from their ordering-grid cells   [2] rows ranked for them
 unsigned long long* knn_direct_stats_dev();
+// Device counters of the farthest point sampling (knn_fps.hip), or null while "knn_stats" is off:
+//   [0] steps run   [1] rows measured against a sample (pcreg_debug_fps_stats)
+unsigned long long* fps_stats_dev();
 // Device counters of the staged RANSAC chain's bounded second pass (ransac.hip), or null while "ransac_stats" is off:
 //   [0] bounded passes run   [1] (refit, 512-correspondence block) units scanned, seed refits included   [2] units a full pass scans
 //   [3] refits handed over to the finish   [4] units the finish scored, also part of [1] (pcreg_debug_ransac_handover reads [3], [4])
@@ -283,6 +286,14 @@ int launch_model_normals(const ModelView& v, int k, const double* viewpoint, flo
 size_t denoise_ws_bytes(int M, int k);
 int launch_model_denoise(const ModelView& v, int k, double threshold, double* mean_dist, int32_t* inliers, int32_t* n_inliers, double* stats,
                          void* ws, size_t ws_bytes, hipStream_t st);
+// farthest point sampling of the model's own rows (knn_fps.hip): idx / dist [K] in selection order, n_out, cover_d2 and
+// info single device words, min_dist / label [M] by ORIGINAL row -- device pointers, each may be null except n_out.  fps_args_ok and
+// fps_max_rows are the argument rules every tier checks before it touches the device
+size_t fps_ws_bytes(int M, int K);
+bool fps_args_ok(int M, int K, int start, float stop_d2);
+int fps_max_rows();
+int launch_model_fps(const ModelView& v, int K, int start, float stop_d2, int32_t* idx, float* dist, int32_t* n_out, float* cover_d2,
+                     float* min_dist, int32_t* label, int32_t* info, void* ws, size_t ws_bytes, hipStream_t st);
 // the FPFH descriptor of every model row from its k nearest rows and a normal per row (knn_fpfh.hip): normals [3][ldn]
 // on the device by ORIGINAL row; fpfh [M][33] doubles and spfh [M][33] uint8 counts (or null), row-major by ORIGINAL row
 size_t fpfh_ws_bytes(int M, int k);

@@ -678,6 +678,41 @@ class PreparedModel:
             res.update(thr=stats[0], mean=stats[1], std=stats[2], n_finite=stats[3])
         return res
 
+    def farthest_points(self, K: int, start: int = -1, stop_d2: float = 0.0, out=None):
+        """Farthest point sampling of the model's own rows, on torch's current stream (pcreg_dev_model_fps_f32; the contract is
+        pcreg_model_fps_f32's): -> a dict of device tensors -- idx [K] int32 and dist [K] float32, whose first n_out [1] int32
+        entries are the 0-based original rows in selection order and their squared distances to the earlier samples (the rest is
+        not written); cover_d2 [1] float32; min_dist [M] float32 and label [M] int32 by ORIGINAL row; info [1] int32, 1 when the
+        start row has a non-finite coordinate (then n_out = 0 and nothing else is written).  Nothing synchronises: the caller reads
+        n_out and info when it needs them.  The workspace is cached on the model and grown on demand; calls that may overlap on two
+        streams pass buffers of their own, out=(idx, dist, n_out, cover_d2, min_dist, label, info, ws) with ws of
+        pcreg_dev_model_fps_workspace(M, K) bytes."""
+        K, start, stop_d2 = int(K), int(start), float(stop_d2)
+        dev, M = self.tensor.device, self.M
+        if K < 0 or (M > 0 and not -1 <= start < M) or not stop_d2 >= 0.0:
+            raise ValueError(f"K >= 0, start in -1 .. M - 1 and stop_d2 >= 0 are required, got {K}, {start}, {stop_d2}")
+        need = int(lib().pcreg_dev_model_fps_workspace(M, K))
+        if need == 0:
+            raise ValueError(f"farthest point sampling serves at most 2097152 rows, got {M}")
+        if out is not None:
+            idx, dist, n_out, cover, md, lab, info, ws = out
+        else:
+            idx = torch.empty(K, dtype=torch.int32, device=dev)
+            dist = torch.empty(K, dtype=torch.float32, device=dev)
+            n_out = torch.empty(1, dtype=torch.int32, device=dev)
+            cover = torch.empty(1, dtype=torch.float32, device=dev)
+            md = torch.empty(M, dtype=torch.float32, device=dev)
+            lab = torch.empty(M, dtype=torch.int32, device=dev)
+            info = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_fps_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._fps_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        opt = lambda t: _p(t) if t is not None and t.numel() else None      # (an empty tensor has no address to pass)
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_fps_f32(self.handle, K, start, stop_d2, opt(idx), opt(dist), _p(n_out), opt(cover), opt(md), opt(lab),
+                                                opt(info), _p(ws), ws.numel(), _stream()))
+        return dict(idx=idx, dist=dist, n_out=n_out, cover_d2=cover, min_dist=md, label=lab, info=info)
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             lib().pcreg_dev_model_destroy(self.handle)
