@@ -1081,8 +1081,9 @@ int pcreg_align_points_knn(const double* pts, int n, int ld, int C1, int C2,
 /* B supports in one launch (the per-keypoint loop of
  * getSpacialHistogramDescriptors.m:64-145 calls the same LRF per support):
  * support b owns rows [offsets[b], offsets[b+1]) of pts / aligned; coeff 9*B, c 3*B;
- * status[b] = 0 ok, 1 = support too small (n < 2).  A support may hold at most 8192 points (it is kept in the
- * registers of one workgroup); larger -> PCREG_E_ARG.  The reference's supports hold 500 ... 6000
+ * status[b] = 0 ok, 1 = support too small (n < 2), 2 = the support is larger than the launch holds (never from this
+ * entry, which sizes the launch itself: see pcreg_dev_align_points_knn_batched).  A support may hold at most 8192 points
+ * (it is kept in the registers of one workgroup); larger -> PCREG_E_ARG.  The reference's supports hold 500 ... 6000
  * (completeExperimentFast.m:300-302). */
 int pcreg_align_points_knn_batched(const double* pts, int total, int ld, const int32_t* offsets,
                                    int B, int C1, int C2, double* aligned, double* coeff,
@@ -1669,8 +1670,11 @@ int pcreg_dev_ransac_batched(const double* pts1, const double* pts2, int ld, con
 
 /* AlignPoints_KNN.m:17-59 for B supports resident in HBM (the device-tier form of
  * pcreg_align_points_knn_batched; same layouts, every pointer is device memory): support b owns rows
- * [offsets[b], offsets[b+1]) of pts / aligned (n x 3 column-major, ld >= total); max_n = the largest support;
- * coeff 9*B, c 3*B, status B (0 ok, 1 = fewer than 2 points).  Enqueued on `stream`, nothing synchronises. */
+ * [offsets[b], offsets[b+1]) of pts / aligned (n x 3 column-major, ld >= total); max_n = the largest support
+ * (<= 8192, else PCREG_E_ARG): it chooses the launch and is trusted, the offsets are not read on the host;
+ * coeff 9*B, c 3*B, status B: 0 ok, 1 = fewer than 2 points, 2 = the support holds more points than the launch chosen
+ * for max_n does (max_n was too small).  With a status other than 0 nothing else is written for that support: its rows
+ * of aligned, coeff and c keep what they held.  Enqueued on `stream`, nothing synchronises. */
 int pcreg_dev_align_points_knn_batched(const double* pts, int total, int ld, const int32_t* offsets, int B, int max_n,
                                        int C1, int C2, double* aligned, double* coeff, double* c, int32_t* status,
                                        void* stream);

@@ -98,6 +98,8 @@ __global__ __launch_bounds__(NT, NT == 128 ? 2 : (NT == 256 && PT > 8 ? 3 : (NT 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double* px = pts + off; const double* py = px + (size_t)ld; const double* pz = py + (size_t)ld;
     if (n < 2) { if (tid == 0) status[b] = 1; return; }
+    // a support the launch does not hold (the caller's max_n was too small) is refused, not truncated to its first PT * NT rows
+    if (n > PT * NT) { if (tid == 0) status[b] = 2; return; }
 
     PCREG_AL_STAMP(0)
     double X[PT], Y[PT], Z[PT];
