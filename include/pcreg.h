@@ -95,7 +95,8 @@ int  pcreg_device_name(char* buf, int cap);  /* e.g. "gfx950:..."               
  * are defined over the walk of the whole query set), "knn_direct_stats" (counters for pcreg_debug_knn_direct_stats; it forces
  * nothing), "knn_seed_fused" (1: the two-nearest search seeds and answers directly in two launches instead of one; same
  * bits), "ransac_bhand" (1: the staged RANSAC chain's bounded second pass walks every refit to its stop instead of handing
- * the refits still undecided after a few blocks to its block-parallel finish; same bits); value 0
+ * the refits still undecided after a few blocks to its block-parallel finish; same bits), "fgr_chain" (1: fast global
+ * registration runs its chained form, a sums and a finish launch per iteration, whatever the size; same bits); value 0
  * restores the default.  The library reads NO
  * environment variable (tests/test_abi.py greps the binary).  PCREG_E_ARG for an unknown key. */
 int  pcreg_debug_set(const char* key, int value);
@@ -186,6 +187,64 @@ int pcreg_ransac_batched(const double* pts1, const double* pts2, int total, int 
                          const int32_t* sample_idx, double* T, int32_t* inlier_idx,
                          int32_t* n_inliers, int32_t* num_success, int32_t* max_inliers,
                          int32_t* failed);
+
+/* Fast global registration (Zhou, Park, Koltun 2016; MATLAB's pcregisterfgr) of B sets of matched pairs, laid out as
+ * pcreg_ransac_batched has them: pts1 / pts2 n x 3 column-major doubles with leading dimension ld, registration b owns rows
+ * [offsets[b], offsets[b+1]); T is MATLAB's 4 x 4, column-major, [pts2, 1] * T = [pts1, 1].  No samples and no hypotheses: a
+ * Geman-McClure weight per pair is annealed from "every pair counts" to "only pairs within sqrt(delta2) count" and a six-unknown
+ * rigid step is solved at every stage, so the result depends on nothing but the inputs.
+ *
+ * THE CONTRACT, per registration b, in double throughout and uncontracted (csrc/fgr_pair.hpp holds every per-pair formula):
+ *  1. A pair is LIVE when its six coordinates are finite.  Dead pairs are never kept and take no part in anything.
+ *  2. The tuple test (n_tuples > 0).  Triple p = the three pair indices that pcreg_ransac's built-in sampler gives hypothesis p
+ *     with seed `seed + b`, or row p of the caller's tuple_idx [B][n_tuples][3] (1-based, each index clamped to [1, n] as pcreg_ransac
+ *     clamps its table).  It passes when its three pairs are live and each edge (i, j) has s2 * a < b && s2 * b < a with a =
+ *     |pts1_i - pts1_j|^2, b = |pts2_i - pts2_j|^2 (each (dx dx + dy dy) + dz dz) and s2 = tuple_scale^2.  A pair is KEPT when it
+ *     belongs to at least one passing triple: no multiplicity, no stop at a number of passes.  n_tuples == 0 keeps every live pair.
+ *  3. Fewer than 3 kept pairs: failed = 1, T sixteen zeros, mu0 = mu_final = cost = sum_d2 = 0 and n_inliers = 0 -- what a failed
+ *     pcreg_ransac leaves; n_live and n_kept still say why.  So does a registration of more than n_cap rows (device tier), with
+ *     n_live = n_kept = 0.
+ *  4. o = the middle of the box of the kept pts1 rows, 0.5 lo + 0.5 hi per axis.
+ *  5. opts->mu0 == 0 means mu0 = the larger squared diagonal of the boxes of the kept pts1 and of the kept pts2 rows.
+ *  6. T = T0[b] (NULL: the identity), mu = mu0.  For it = 0 .. iterations - 1: when it > 0 && it % decrease_every == 0, mu =
+ *     max(mu / division_factor, delta2); every kept pair k (ascending row order) has q = [pts2_k 1] * T, each component
+ *     ((x T[4j] + y T[4j+1]) + z T[4j+2]) + T[4j+3], r = q - pts1_k, rr = (r0 r0 + r1 r1) + r2 r2, t = mu / (mu + rr), w = t t,
+ *     u = q - o, and adds w times the 28 terms of the three plane pairs (normal e_c, residual r_c) to plane_fit.hpp's sums;
+ *     plane_fit(sums, 3 n_kept, o) gives T_step and T <- T * T_step.  A fit that answers "empty" ends the registration as in 3.
+ *  7. Results: T, failed, n (rows), n_live, n_kept, mu0, mu_final, cost = the sum of w rr under the final T and mu_final,
+ *     n_inliers = the kept pairs with rr <= delta2 under the final T and sum_d2 the sum of their rr; inlier_idx (capacity total,
+ *     the rows' layout: registration b's list starts at offsets[b]) 1-based within the registration, ascending; kept (optional,
+ *     total bytes, the rows' layout) 1 for a kept pair.
+ * THE SUM ORDER.  Kept pair k belongs to chunk k / 2048; thread t of the chunk's 256 adds pairs 2048 c + t, + 256, ... in that
+ * order from 0.0; the 64 lanes of a wave are added by the xor butterfly at distances 32, 16, 8, 4, 2, 1; the four waves as
+ * ((w0 + w1) + w2) + w3; the chunks ascending from 0.0.  cost and sum_d2 are summed the same way.  Nothing depends on B, on a
+ * registration's place in the batch, on the stream, on what the workspace held or on which of the two kernel forms ran
+ * (pcreg_debug_set("fgr_chain", 1) forces the chained form, which otherwise serves n_cap above pcreg_fgr_resident_capacity()).
+ *
+ * Argument rules (PCREG_E_ARG): delta2 >= 0, iterations >= 1, decrease_every >= 1, division_factor > 1, mu0 >= 0, n_tuples >= 0,
+ * 0 < tuple_scale <= 1, all finite; offsets ascending from 0 to total <= ld (host tier). */
+typedef struct pcreg_fgr_opts {
+    double   delta2;           /* the squared distance at which a pair stops counting; compared with SQUARED distances */
+    int32_t  iterations;
+    int32_t  decrease_every;
+    double   division_factor;
+    double   mu0;              /* 0: the default of rule 5 */
+    int32_t  n_tuples;         /* 0: no tuple test */
+    int32_t  reserved;         /* 0 */
+    double   tuple_scale;
+    uint64_t seed;             /* of the built-in triples (tuple_idx == NULL) */
+} pcreg_fgr_opts;
+typedef struct pcreg_fgr_result {
+    double  T[16];
+    double  mu0, mu_final, cost, sum_d2;
+    int32_t failed, n, n_live, n_kept, n_inliers, reserved;
+} pcreg_fgr_result;
+/* the largest n_cap the resident form serves (its kept pairs are staged in LDS, six doubles a pair) */
+int pcreg_fgr_resident_capacity(void);
+/* Host tier: one upload and one read.  T0 [B][16] or NULL, tuple_idx [B][n_tuples][3] or NULL, kept [total] or NULL. */
+int pcreg_fgr_batched(const double* pts1, const double* pts2, int total, int ld, const int32_t* offsets, int B,
+                      const pcreg_fgr_opts* opts, const double* T0, const int32_t* tuple_idx, pcreg_fgr_result* out,
+                      int32_t* inlier_idx, uint8_t* kept);
 
 /* fp32 3-D point search (the "KNN" of BASELINE.json's metric): for each query the two
  * nearest model points, squared distance fmaf(dz,dz,fmaf(dy,dy,dx*dx)), ties to the
@@ -1667,6 +1726,14 @@ size_t pcreg_dev_ransac_batched_workspace(int n_cap, int iterNum, int B);
 int pcreg_dev_ransac_batched(const double* pts1, const double* pts2, int ld, const int32_t* offsets, int B, int n_cap,
                              const pcreg_ransac_opts* opts, pcreg_dev_ransac_result* out, int32_t* inlier_idx,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_fgr_batched on device buffers (its contract, above): every pointer but opts is device memory, the offsets are not read on
+ * the host; n_cap = the largest registration: it chooses the kernel form and the launch and is trusted for that only (a
+ * registration of more rows reports failed = 1).  T0, tuple_idx and kept may be NULL.  out [B]; inlier_idx and kept have the rows'
+ * layout.  Enqueued on `stream`, nothing synchronises; the workspace (0 for an argument out of range) may hold anything. */
+size_t pcreg_dev_fgr_batched_workspace(int n_cap, int B, int iterations);
+int pcreg_dev_fgr_batched(const double* pts1, const double* pts2, int ld, const int32_t* offsets, int B, int n_cap,
+                          const pcreg_fgr_opts* opts, const double* T0, const int32_t* tuple_idx, pcreg_fgr_result* out,
+                          int32_t* inlier_idx, uint8_t* kept, void* workspace, size_t workspace_bytes, void* stream);
 
 /* AlignPoints_KNN.m:17-59 for B supports resident in HBM (the device-tier form of
  * pcreg_align_points_knn_batched; same layouts, every pointer is device memory): support b owns rows

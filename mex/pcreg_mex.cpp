@@ -167,6 +167,7 @@
 //   'getMatchesSegmented', descSurface, descModel, int32 rows, int32 segOff, par | 'getMatchesSegmentedOnSet', hSurface, hModel, ...
 //                                          -> pairs, nPairs                (every sphere of the sweep in one call)
 //   'ransacBatched', pts1, pts2, int32 offsets, coef, sample_idx|[], seed -> T (4x4xB), inlierIdx, nInliers, numSuccess, maxInliers, failed
+//   'fgrBatched', pts1, pts2, int32 offsets, opts, int32 tupleIdx|[], T0|[] -> T (4x4xB), inlierIdx, stats (B x 9), kept (uint8)   (fast global registration; matlab/fgrBatched.m, pcregisterfgrFast.m)
 //   'sphereCounts', featModel, centres, R -> counts | 'sphereSweep', hSurface, hModel, featSurface, featModel, centres, int32 numDesc,
 //       R_desc, par, putativeThresh, coef, seed -> modelRows, pairs, nPairs, trial, T, numSuccess, maxInliers, failed   (completeExperimentFast.m:52-224)
 //   'sphereModelCreate', hModel, featModel, centres, int32 numDesc, R_desc -> handle, modelRows | 'sphereSweepOnModel', hSphereModel, hSurface,
@@ -760,6 +761,76 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                     if (nlhs > 5) plhs[5] = col(fl, false);
                 }
                 mxDestroyArray(inl); mxDestroyArray(ni); mxDestroyArray(ns); mxDestroyArray(mi); mxDestroyArray(fl);
+            }
+        }
+    } else if (!strcmp(cmd, "fgrBatched")) {                   // [T, inlierIdx, stats, kept] =
+        // pcreg_mex('fgrBatched', pts1, pts2, int32(offsets), opts[, tupleIdx, T0]): fast global registration of B sets of matched pairs
+        // in one call (pcreg_fgr_batched's contract).  pts1 / pts2: the registrations' rows back to back (total x 3 doubles);
+        // offsets: B + 1 running row offsets (0-based); opts: a struct with delta2 (required, compared with SQUARED distances) and any of
+        // iterations (128), decrease_every (4), division_factor (1.4), mu0 (0: the default), n_tuples (0: no tuple test), tuple_scale
+        // (0.95), seed (0); tupleIdx: int32 3 x (n_tuples B), one COLUMN per triple, registration after registration, or []; T0: 4 x 4 x B
+        // doubles or [].  T: 4 x 4 x B (zeros where failed); inlierIdx: the lists back to back (1-based inside a registration); stats: B x 9
+        // doubles, the columns failed, n_live, n_kept, n_inliers, mu0, mu_final, cost, sum_d2, n; kept: total x 1 uint8.  matlab/fgrBatched.m
+        const mxArray* c = nrhs > 4 ? prhs[4] : nullptr;
+        bool no_delta = false;
+        if (c) (void)field(c, "delta2", 0.0, &no_delta);
+        if (nrhs < 5 || nrhs > 7 || !mxIsDouble(prhs[1]) || !mxIsDouble(prhs[2]) || !mxIsInt32(prhs[3]) || !mxIsStruct(c))
+            usage = "fgrBatched: pts1, pts2 (total x 3 doubles), int32 offsets, opts (a struct)[, int32 tupleIdx, T0]";
+        else if (no_delta) usage = "fgrBatched: opts.delta2 is required";
+        else {
+            pcreg_fgr_opts o;
+            o.delta2 = field(c, "delta2", 0.0); o.iterations = (int32_t)field(c, "iterations", 128);
+            o.decrease_every = (int32_t)field(c, "decrease_every", 4); o.division_factor = field(c, "division_factor", 1.4);
+            o.mu0 = field(c, "mu0", 0.0); o.n_tuples = (int32_t)field(c, "n_tuples", 0); o.reserved = 0;
+            o.tuple_scale = field(c, "tuple_scale", 0.95); o.seed = (uint64_t)field(c, "seed", 0.0);
+            const int total = (int)mxGetM(prhs[1]);
+            const int B = (int)(mxGetM(prhs[3]) * mxGetN(prhs[3])) - 1;
+            const int32_t* off = (const int32_t*)mxGetData(prhs[3]);
+            const bool has_tab = nrhs > 5 && !mxIsEmpty(prhs[5]), has_T0 = nrhs > 6 && !mxIsEmpty(prhs[6]);
+            if (B < 0 || off[0] != 0 || off[B] != total || (int)mxGetM(prhs[2]) != total || (total > 0 && (mxGetN(prhs[1]) != 3 || mxGetN(prhs[2]) != 3)))
+                usage = "fgrBatched: offsets must run from 0 to size(pts1, 1) = size(pts2, 1), and the points have 3 columns";
+            else if (has_tab && (!mxIsInt32(prhs[5]) || o.n_tuples < 0 || mxGetM(prhs[5]) * mxGetN(prhs[5]) != (size_t)3 * (size_t)o.n_tuples * (size_t)B))
+                usage = "fgrBatched: tupleIdx must be int32, 3 x (n_tuples * B)";
+            else if (has_T0 && (!mxIsDouble(prhs[6]) || mxGetM(prhs[6]) * mxGetN(prhs[6]) != (size_t)16 * (size_t)B))
+                usage = "fgrBatched: T0 must be 4 x 4 x B doubles";
+            else {
+                const size_t b1 = (size_t)(B > 0 ? B : 1), t1 = (size_t)(total > 0 ? total : 1);
+                mxArray* inl = mxCreateNumericMatrix(t1, 1, mxINT32_CLASS, mxREAL);
+                mxArray* res = mxCreateNumericMatrix(sizeof(pcreg_fgr_result), b1, mxUINT8_CLASS, mxREAL);
+                mxArray* kept = mxCreateNumericMatrix(t1, 1, mxUINT8_CLASS, mxREAL);
+                pcreg_fgr_result* r = (pcreg_fgr_result*)mxGetData(res);
+                rc = B == 0 ? PCREG_OK : pcreg_fgr_batched(mxGetPr(prhs[1]), mxGetPr(prhs[2]), total, (int)t1, off, B, &o, has_T0 ? mxGetPr(prhs[6]) : nullptr,
+                                                            has_tab ? (const int32_t*)mxGetData(prhs[5]) : nullptr, r, (int32_t*)mxGetData(inl),
+                                                            (uint8_t*)mxGetData(kept));
+                if (rc == PCREG_OK) {
+                    mwSize dims[3] = {4, 4, (mwSize)B};
+                    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+                    size_t tot_inl = 0;
+                    for (int b = 0; b < B; ++b) {
+                        memcpy(mxGetPr(plhs[0]) + (size_t)b * 16, r[b].T, 128);
+                        tot_inl += (size_t)r[b].n_inliers;
+                    }
+                    if (nlhs > 1) {                     // the inlier lists back to back, as a double column like find()
+                        plhs[1] = mxCreateDoubleMatrix(tot_inl, tot_inl ? 1 : 0, mxREAL);
+                        const int32_t* src = (const int32_t*)mxGetData(inl);
+                        size_t k = 0;
+                        for (int b = 0; b < B; ++b) for (int e = 0; e < r[b].n_inliers; ++e) mxGetPr(plhs[1])[k++] = (double)src[off[b] + e];
+                    }
+                    if (nlhs > 2) {
+                        plhs[2] = mxCreateDoubleMatrix(B, B ? 9 : 0, mxREAL);
+                        double* s = mxGetPr(plhs[2]);
+                        for (int b = 0; b < B; ++b) {
+                            const double v[9] = {(double)r[b].failed, (double)r[b].n_live, (double)r[b].n_kept, (double)r[b].n_inliers, r[b].mu0, r[b].mu_final,
+                                                 r[b].cost, r[b].sum_d2, (double)r[b].n};
+                            for (int k = 0; k < 9; ++k) s[(size_t)k * B + b] = v[k];
+                        }
+                    }
+                    if (nlhs > 3) {
+                        plhs[3] = mxCreateNumericMatrix(total, total ? 1 : 0, mxUINT8_CLASS, mxREAL);
+                        if (total > 0) memcpy(mxGetData(plhs[3]), mxGetData(kept), (size_t)total);
+                    }
+                }
+                mxDestroyArray(inl); mxDestroyArray(res); mxDestroyArray(kept);
             }
         }
     } else if (!strcmp(cmd, "getMatches")) {

@@ -49,11 +49,25 @@ class DevRansacResult(C.Structure):
                 ("max_inliers", C.c_int32), ("failed", C.c_int32), ("n", C.c_int32), ("winner", C.c_int32)]
 
 
+class FgrOpts(C.Structure):
+    """pcreg_fgr_opts (include/pcreg.h)."""
+    _fields_ = [("delta2", C.c_double), ("iterations", C.c_int32), ("decrease_every", C.c_int32), ("division_factor", C.c_double),
+                ("mu0", C.c_double), ("n_tuples", C.c_int32), ("reserved", C.c_int32), ("tuple_scale", C.c_double), ("seed", C.c_uint64)]
+
+
+class FgrResult(C.Structure):
+    """pcreg_fgr_result (include/pcreg.h)."""
+    _fields_ = [("T", C.c_double * 16), ("mu0", C.c_double), ("mu_final", C.c_double), ("cost", C.c_double), ("sum_d2", C.c_double),
+                ("failed", C.c_int32), ("n", C.c_int32), ("n_live", C.c_int32), ("n_kept", C.c_int32), ("n_inliers", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/pcreg.h declares (tests/test_abi.py checks the two lists agree)
 SYMBOLS = [
     "pcreg_last_error", "pcreg_version", "pcreg_device_count", "pcreg_set_device", "pcreg_device_name", "pcreg_debug_set", "pcreg_debug_match_stats",
     "pcreg_debug_knn_stats", "pcreg_debug_knn_unit_stats", "pcreg_debug_knn_direct_stats", "pcreg_debug_ransac_stats", "pcreg_debug_ransac_handover", "pcreg_debug_cluster_stats", "pcreg_debug_desc_stats", "pcreg_debug_dev_model_export", "pcreg_debug_search_export",
     "pcreg_estimate_transform", "pcreg_calc_dists", "pcreg_ransac", "pcreg_ransac_batched",
+    "pcreg_fgr_resident_capacity", "pcreg_fgr_batched", "pcreg_dev_fgr_batched_workspace", "pcreg_dev_fgr_batched",
     "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
     "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_size", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
     "pcreg_model_range_f32", "pcreg_range_points_f32", "pcreg_model_cluster_f32", "pcreg_cluster_points_f32",
@@ -239,6 +253,12 @@ def lib() -> C.CDLL:
             vp, i, d = C.c_void_p, C.c_int, C.c_double                          # (a double by value: declared)
             L.pcreg_dev_model_refit_cpd_f32.argtypes = [vp, vp, i, i, vp, i, vp, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_refit_cpd_f32.argtypes = [vp, vp, i, i, vp, i, vp, d, i, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_fgr_batched_workspace"):     # (an older build given through PCREG_LIB lacks fast global registration)
+            L.pcreg_dev_fgr_batched_workspace.restype = C.c_size_t
+            L.pcreg_dev_fgr_batched_workspace.argtypes = [C.c_int] * 3
+            vp, i = C.c_void_p, C.c_int
+            L.pcreg_dev_fgr_batched.argtypes = [vp, vp, i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_fgr_batched.argtypes = [vp, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_unique_rows3_workspace"):    # (an older build given through PCREG_LIB lacks unique_rows)
             for name in ("pcreg_dev_unique_rows3_workspace", "pcreg_dev_aggregate_matches_workspace"):
                 getattr(L, name).restype = C.c_size_t

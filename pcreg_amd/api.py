@@ -234,6 +234,101 @@ def ransac_batched(pts1_list, pts2_list, ransacCoef: dict, *, sample_idx=None, s
     return out
 
 
+# ------------------------------------------------------------- fast global registration
+FGR_DEFAULTS = dict(iterations=128, decrease_every=4, division_factor=1.4, mu0=0.0, n_tuples=0, tuple_scale=0.95, seed=0)
+"""What fgr / fgr_batched take where `opts` leaves a key out; delta2 has no default."""
+
+
+def _fgr_opts(opts: dict):
+    from ._lib import FgrOpts
+    if "delta2" not in opts:
+        raise KeyError("opts['delta2'] is required: the SQUARED distance at which a pair stops counting")
+    unknown = set(opts) - set(FGR_DEFAULTS) - {"delta2"}
+    if unknown:
+        raise KeyError(f"unknown fast-global-registration options {sorted(unknown)}")
+    o = {**FGR_DEFAULTS, **opts}
+    return FgrOpts(float(o["delta2"]), int(o["iterations"]), int(o["decrease_every"]), float(o["division_factor"]), float(o["mu0"]),
+                   int(o["n_tuples"]), 0, float(o["tuple_scale"]), int(o["seed"]) & ((1 << 64) - 1))
+
+
+def fgr_batched(pts1_list, pts2_list, opts: dict, tuple_idx=None, *, T0=None):
+    """Fast global registration (MATLAB's pcregisterfgr on matched pairs; pcreg_fgr_batched's contract, include/pcreg.h) of B
+    independent sets of matched pairs in one call: [pts2, 1] * T = [pts1, 1].  opts: delta2 (required) and any of FGR_DEFAULTS'
+    keys.  tuple_idx: B x n_tuples x 3 1-based triples for the tuple test in place of the built-in ones (seed + b); T0: B x 4 x 4
+    start transforms.  Returns one dict per registration: T (4 x 4, EMPTY when failed), failed, n_live, n_kept, mu0, mu_final,
+    cost, n_inliers, sum_d2, inlier_idx (1-based, ascending, int32) and kept (bool per pair).  Deterministic: no samples, no
+    hypotheses, every sum in one fixed order."""
+    from ._lib import FgrResult
+    B = len(pts1_list)
+    if B == 0:
+        return []
+    if len(pts2_list) != B:
+        raise ValueError("pts1_list and pts2_list differ in length")
+    sizes = [np.asarray(p).reshape(-1, 3).shape[0] for p in pts1_list]
+    if sizes != [np.asarray(p).reshape(-1, 3).shape[0] for p in pts2_list]:
+        raise ValueError("a registration's pts1 and pts2 differ in size")
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(sizes)
+    total = int(offsets[-1])
+    p1 = _pts3(np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in pts1_list], axis=0), "pts1")
+    p2 = _pts3(np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in pts2_list], axis=0), "pts2")
+    o = _fgr_opts(opts)
+    ti = None
+    if tuple_idx is not None:
+        ti = np.ascontiguousarray(tuple_idx, dtype=np.int32)
+        if ti.shape != (B, o.n_tuples, 3):
+            raise ValueError("tuple_idx must be B x n_tuples x 3")
+    t0 = None
+    if T0 is not None:
+        t0 = np.asarray(T0, dtype=np.float64)
+        if t0.shape != (B, 4, 4):
+            raise ValueError("T0 must be B x 4 x 4")
+        t0 = np.ascontiguousarray(t0.transpose(0, 2, 1))                         # (each 4 x 4 column-major)
+    res = (FgrResult * B)()
+    inl = np.zeros(max(total, 1), dtype=np.int32)
+    kept = np.zeros(max(total, 1), dtype=np.uint8)
+    ld = max(total, 1)
+    check(lib().pcreg_fgr_batched(p1.ctypes.data, p2.ctypes.data, total, ld, offsets.ctypes.data, B, C.addressof(o),
+                                  None if t0 is None else t0.ctypes.data, None if ti is None else ti.ctypes.data, C.addressof(res),
+                                  inl.ctypes.data, kept.ctypes.data))
+    out = []
+    for b in range(B):
+        r, a = res[b], int(offsets[b])
+        out.append(dict(T=EMPTY.copy() if r.failed else np.array(r.T[:]).reshape(4, 4, order="F"), failed=bool(r.failed), n_live=r.n_live,
+                        n_kept=r.n_kept, mu0=r.mu0, mu_final=r.mu_final, cost=r.cost, n_inliers=r.n_inliers, sum_d2=r.sum_d2,
+                        inlier_idx=inl[a:a + r.n_inliers].copy(), kept=kept[a:a + sizes[b]].astype(bool)))
+    return out
+
+
+def fgr(pts1, pts2, opts: dict, tuple_idx=None, *, T0=None):
+    """fgr_batched for one set of matched pairs: its dict."""
+    return fgr_batched([pts1], [pts2], opts, None if tuple_idx is None else np.asarray(tuple_idx)[None],
+                       T0=None if T0 is None else np.asarray(T0, dtype=np.float64)[None])[0]
+
+
+REGISTER_FGR_MATCH = dict(UNNORMALIZE=False, CHANGE_METRIC=False, Method="Exhaustive", MatchThreshold=100.0, MaxRatio=1.0, Metric="SSD",
+                          Unique=True, VERBOSE=0)
+"""register_fgr's getMatches parameters: every nearest descriptor, kept when the choice is mutual."""
+
+
+def register_fgr(moving, fixed, grid_step: float, *, max_distance=None, k: int = 16, opts=None, match=None) -> dict:
+    """The composition a pcregisterfgr(moving, fixed, gridStep) user expects, over this package's own calls: pcdownsample of both
+    clouds at grid_step, point_normals and point_fpfh (k neighbours) on both, getMatches (REGISTER_FGR_MATCH, Unique) of the moving
+    descriptors against the fixed ones, then fgr on the matched points with delta2 = max_distance^2 (default grid_step^2):
+    [moving, 1] * T = [fixed, 1].  Returns fgr's dict with `matches` (P x 2, 1-based rows of the two downsampled clouds) and the
+    clouds `moving_down` / `fixed_down` added."""
+    md = pcdownsample(moving, grid_step)[0]
+    fd = pcdownsample(fixed, grid_step)[0]
+    dm = point_fpfh(md, k, normals=point_normals(md, k))
+    df = point_fpfh(fd, k, normals=point_normals(fd, k))
+    matches = getMatches(dm, df, {**REGISTER_FGR_MATCH, **(match or {})})
+    d = float(grid_step if max_distance is None else max_distance)
+    r = fgr(fd[matches[:, 1].astype(np.int64) - 1].astype(np.float64), md[matches[:, 0].astype(np.int64) - 1].astype(np.float64),
+            {"delta2": d * d, **(opts or {})})
+    r.update(matches=matches, moving_down=md, fixed_down=fd)
+    return r
+
+
 GETINLIERS_COEFF = dict(minPtNum=3, iterNum=int(2e4), thDist=0.5, thInlrRatio=0.1, REFINE=True)
 """coeff of getInliersRANSAC.m:17-31."""
 

@@ -135,7 +135,9 @@ int pcreg_debug_set(const char* key, int value) {
                                                         // two (same bits: the A/B of one binary).
                                                         // "ransac_bhand": 0 (the default) hands the bounded second pass's long walks to
                                                         // its block-parallel finish, 1 walks every refit to its stop (same bits).
-                                                        "knn_direct", "knn_direct_stats", "knn_seed_fused", "ransac_bhand"};
+                                                        // "fgr_chain": 1 runs fast global registration's chained form whatever the size
+                                                        // (same bits).
+                                                        "knn_direct", "knn_direct_stats", "knn_seed_fused", "ransac_bhand", "fgr_chain"};
     PCREG_ARG(key != nullptr);
     for (int k = 0; k < pcreg::kDbgCount; ++k)
         if (!strcmp(key, names[k])) { pcreg::g_debug[k].store(value, std::memory_order_relaxed); return PCREG_OK; }
@@ -309,6 +311,51 @@ int pcreg_ransac_batched(const double* pts1, const double* pts2, int total, int 
     GUARD();
     return ransac_host(pts1, pts2, total, ld, offsets, B, opts, sample_idx, T, inlier_idx, n_inliers, num_success,
                        max_inliers, failed, nullptr, nullptr);
+}
+
+int pcreg_fgr_resident_capacity(void) { return fgr_resident_capacity(); }
+
+int pcreg_fgr_batched(const double* pts1, const double* pts2, int total, int ld, const int32_t* offsets, int B, const pcreg_fgr_opts* opts,
+                      const double* T0, const int32_t* tuple_idx, pcreg_fgr_result* out, int32_t* inlier_idx, uint8_t* kept) {
+    PCREG_ARG(pts1 && pts2 && offsets && opts && out && inlier_idx);
+    PCREG_ARG(total >= 0 && ld >= total && B >= 1);
+    PCREG_ARG(fgr_args_ok(*opts));
+    PCREG_ARG(offsets[0] == 0 && offsets[B] == total);
+    int max_n = 0;
+    for (int b = 0; b < B; ++b) {
+        PCREG_ARG(offsets[b + 1] >= offsets[b]);
+        max_n = std::max(max_n, offsets[b + 1] - offsets[b]);
+    }
+    GUARD();
+    const size_t wsb = fgr_ws_bytes(max_n, B, opts->iterations);
+    PCREG_ARG(wsb != 0);
+    const size_t tot = (size_t)(total > 0 ? total : 1), ntab = (size_t)B * (size_t)opts->n_tuples * 3;
+    Stage st{scratch()};
+    double *d1, *d2, *dT0; int32_t *dOff, *dInl, *dTab; uint8_t* dKept; pcreg_fgr_result* dOut; char* ws;
+    TRY(st.take(3 * tot, &d1));
+    TRY(st.take(3 * tot, &d2));
+    TRY(st.take((size_t)B + 1, &dOff));
+    TRY(st.take((size_t)B, &dOut));
+    TRY(st.take(tot, &dInl));
+    TRY(st.take(wsb, &ws));
+    // the optional buffers behind everything else, taken (empty) on every path: each keeps its slot
+    TRY(st.take(T0 ? 16 * (size_t)B : 0, &dT0));
+    TRY(st.take(tuple_idx ? ntab : 0, &dTab));
+    TRY(st.take(kept ? tot : 0, &dKept));
+    if (!T0) dT0 = nullptr;
+    if (!tuple_idx || ntab == 0) dTab = nullptr;
+    if (!kept) dKept = nullptr;
+    if (dT0) PCREG_HIP(hipMemcpyAsync(dT0, T0, sizeof(double) * 16 * (size_t)B, hipMemcpyHostToDevice, g_stream));
+    if (dTab) PCREG_HIP(hipMemcpyAsync(dTab, tuple_idx, sizeof(int32_t) * ntab, hipMemcpyHostToDevice, g_stream));
+    TRY(upload_cols(pts1, total, ld, 3, d1, g_stream));
+    TRY(upload_cols(pts2, total, ld, 3, d2, g_stream));
+    PCREG_HIP(hipMemcpyAsync(dOff, offsets, sizeof(int32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, g_stream));
+    TRY(launch_fgr(d1, d2, total, dOff, B, max_n, *opts, dT0, dTab, dOut, dInl, dKept, ws, wsb, g_stream));
+    PCREG_HIP(hipMemcpyAsync(out, dOut, sizeof(pcreg_fgr_result) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
+    if (total > 0) PCREG_HIP(hipMemcpyAsync(inlier_idx, dInl, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, g_stream));
+    if (kept && total > 0) PCREG_HIP(hipMemcpyAsync(kept, dKept, (size_t)total, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    return PCREG_OK;
 }
 
 int pcreg_knn2_points_f32(const float* q, int Q, int ldq, const float* m, int M, int ldm, int32_t* idx, float* dist) {
@@ -2641,6 +2688,17 @@ int pcreg_dev_ransac_batched(const double* pts1, const double* pts2, int ld, con
     GUARD();
     return launch_ransac(pts1, pts2, ld, offsets, nullptr, n_cap, B, *opts, nullptr, out, inlier_idx, nullptr, nullptr,
                          workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t pcreg_dev_fgr_batched_workspace(int n_cap, int B, int iterations) { return fgr_ws_bytes(n_cap, B, iterations); }
+int pcreg_dev_fgr_batched(const double* pts1, const double* pts2, int ld, const int32_t* offsets, int B, int n_cap, const pcreg_fgr_opts* opts,
+                          const double* T0, const int32_t* tuple_idx, pcreg_fgr_result* out, int32_t* inlier_idx, uint8_t* kept, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    PCREG_ARG(pts1 && pts2 && offsets && opts && out && inlier_idx && workspace && B >= 1 && n_cap >= 0 && ld >= 0);
+    PCREG_ARG(fgr_args_ok(*opts));
+    GUARD();
+    return launch_fgr(pts1, pts2, ld, offsets, B, n_cap, *opts, T0, opts->n_tuples > 0 ? tuple_idx : nullptr, out, inlier_idx, kept, workspace,
+                      workspace_bytes, (hipStream_t)stream);
 }
 
 int pcreg_dev_quick_tf(const double* pts, int n, int ld, const double T[16], double* out, int ldo, void* stream) {

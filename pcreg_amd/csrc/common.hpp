@@ -103,6 +103,8 @@ enum DebugKey {
                                // (seed_query_kernel, knn_direct_kernel); same bits
     kDbgRansacBHand,           // "ransac_bhand": 0 = the bounded second pass hands the refits still undecided after kBHand blocks to its
                                // block-parallel finish (rs_bfinish_kernel), 1 = it walks every refit to its stop; same bits
+    kDbgFgrChain,              // "fgr_chain": 1 = fast global registration runs its chained form (a sums and a finish launch per iteration)
+                               // whatever the size instead of the resident kernel; same bits
     kDbgCount
 };
 int debug_flag(DebugKey k);
@@ -419,6 +421,14 @@ int launch_normalize_rows2(double* f, int n, int ld, double* f2, int n2, int ld2
 int launch_match_features(const double* fS, int Q, int ldS, const double* fM, int M, int ldM, int D,
                           const pcreg_match_opts& o, uint32_t* pairs, double* metric, int32_t* P_dev,
                           void* ws, size_t ws_bytes, hipStream_t st);
+
+// fast global registration of B sets of matched pairs (fgr.hip, fgr_pair.hpp): pcreg_dev_fgr_batched's arguments.
+// fgr_args_ok is the argument rule every tier checks before it touches the device
+bool fgr_args_ok(const pcreg_fgr_opts& o);
+int fgr_resident_capacity();
+size_t fgr_ws_bytes(int n_cap, int B, int iterations);
+int launch_fgr(const double* p1, const double* p2, int ld, const int32_t* offsets, int B, int n_cap, const pcreg_fgr_opts& o, const double* T0,
+               const int32_t* tuple_idx, pcreg_fgr_result* out, int32_t* inlier_idx, uint8_t* kept, void* ws, size_t ws_bytes, hipStream_t st);
 
 // sphere-sweep driver pieces (sweep.hip) and the final refine (ransac.hip)
 int launch_sphere_counts(const double* feat, int V, const double* centres, int S, double R, int32_t* counts, hipStream_t st);

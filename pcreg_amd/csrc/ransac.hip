@@ -531,23 +531,9 @@ __device__ __forceinline__ void sample3(const RansacArgs& a, int b, int p, int n
         const int32_t* t = a.sample_idx + ((size_t)b * a.iters + p) * 3;
         s[0] = t[0] - 1; s[1] = t[1] - 1; s[2] = t[2] - 1;
     } else {
-        unsigned long long seed = a.seed + (unsigned long long)b;
-        unsigned r[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            unsigned long long h = splitmix64(seed ^ splitmix64((unsigned long long)(p + a.hyp0g) * 16ull + j));
-            r[j] = (unsigned)(((h >> 32) * (unsigned long long)(unsigned)(n - j)) >> 32);
-        }
-        unsigned i0 = r[0], i1 = r[1];
-        if (i1 >= i0) ++i1;
-        unsigned lo = min(i0, i1), hi = max(i0, i1), i2 = r[2];
-        if (i2 >= lo) ++i2;
-        if (i2 >= hi) ++i2;
-        s[0] = (int)i0; s[1] = (int)i1; s[2] = (int)i2;
+        sample3_builtin(a.seed + (unsigned long long)b, (unsigned long long)(p + a.hyp0g), n, s);
     }
-    // out-of-range tables must not fault the GPU: clamp (documented in pcreg.h)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) s[j] = min(max(s[j], 0), n - 1);
+    sample3_clamp(s, n);
 }
 
 // ---------------------------------------------------------------- hypothesis kernel

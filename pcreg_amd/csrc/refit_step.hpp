@@ -12,6 +12,7 @@
 #pragma once
 #include "chunk_scan.hpp"
 #include "moments.hpp"
+#include "compose.hpp"
 #include <algorithm>
 
 namespace pcreg {
@@ -45,30 +46,42 @@ __device__ __forceinline__ void moved_point(const double (&t)[16], double x, dou
 
 // ---- the chunk tail -----------------------------------------------------------------------------------------------------
 // v = N values every lane of a wave holds alike (a wave's sums): lane 0 of each wave through LDS, the four waves added in
-// ascending order, out[blockIdx.x * N + k] = sum k of this workgroup of kScanBlock threads
+// ascending order; thread k < N of the workgroup of kScanBlock threads returns sum k, the others 0.  (A caller that comes here
+// again in the same kernel puts a __syncthreads in between: the LDS array is read until every thread has returned.)
 template <int N>
-__device__ __forceinline__ void waves_sum_store(const double (&v)[N], double* __restrict__ out) {
+__device__ __forceinline__ double waves_sum(const double (&v)[N]) {
     __shared__ double s_m[kScanBlock / 64][N];
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < N; ++k) s_m[threadIdx.x >> 6][k] = v[k];
     }
     __syncthreads();
-    if (threadIdx.x < N) {
-        const int k = threadIdx.x;
-        out[(size_t)blockIdx.x * N + k] = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
-    }
+    const int k = threadIdx.x < N ? threadIdx.x : 0;
+    const double sum = ((s_m[0][k] + s_m[1][k]) + s_m[2][k]) + s_m[3][k];
+    return threadIdx.x < N ? sum : 0.0;
 }
-// the N <= 28 sums of a moments kernel: the thread's acc[0 .. min(N, 27)) and, where N is 28, `last`; wave_sum27 and wave_sum
+// ... out[blockIdx.x * N + k] = sum k of this workgroup
 template <int N>
-__device__ __forceinline__ void chunk_tail(double (&acc)[27], double last, double* __restrict__ out) {
+__device__ __forceinline__ void waves_sum_store(const double (&v)[N], double* __restrict__ out) {
+    const double sum = waves_sum(v);
+    if (threadIdx.x < N) out[(size_t)blockIdx.x * N + threadIdx.x] = sum;
+}
+// the N <= 28 sums of a moments kernel: the thread's acc[0 .. min(N, 27)) and, where N is 28, `last`; wave_sum27 and wave_sum, then
+// waves_sum.  chunk_sums returns sum k in thread k < N; chunk_tail stores it as waves_sum_store does
+template <int N>
+__device__ __forceinline__ double chunk_sums(double (&acc)[27], double last) {
     static_assert(N >= 1 && N <= 28, "27 sums through wave_sum27 and one more");
     wave_sum27(acc);
     double v[N];
 #pragma unroll
     for (int k = 0; k < (N < 27 ? N : 27); ++k) v[k] = acc[k];
     if constexpr (N == 28) v[27] = wave_sum(last);
-    waves_sum_store(v, out);
+    return waves_sum(v);
+}
+template <int N>
+__device__ __forceinline__ void chunk_tail(double (&acc)[27], double last, double* __restrict__ out) {
+    const double sum = chunk_sums<N>(acc, last);
+    if (threadIdx.x < N) out[(size_t)blockIdx.x * N + threadIdx.x] = sum;
 }
 // a few sums, each through wave_sum
 template <int N>
@@ -97,7 +110,7 @@ __device__ __forceinline__ void hit_rows(const float* __restrict__ best, const i
 
 // ---- the finish step ----------------------------------------------------------------------------------------------------
 // Lanes 0 .. 15 of the one wave of transform bl hold v = entry `lane` of T_step (zero where !ok): T_step (may be null) and
-// T_out = T_in * T_step, every entry ((T(r,0) S(0,c) + T(r,1) S(1,c)) + T(r,2) S(2,c)) + T(r,3) S(3,c) without contraction.
+// T_out = T_in * T_step, every entry compose.hpp's compose_entry.
 // !ok: empty = 1 and T_out zeros.
 __device__ __forceinline__ void step_compose(int bl, int lane, double v, bool ok, const double* __restrict__ T_in, double* __restrict__ T_out,
                                              double* __restrict__ T_step, int32_t* __restrict__ empty) {
@@ -109,8 +122,7 @@ __device__ __forceinline__ void step_compose(int bl, int lane, double v, bool ok
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
     if (lane < 16) {
         const int r = lane & 3, c = lane >> 2;
-        const double* Ti = T_in + (size_t)bl * 16;
-        const double w = ((Ti[r] * s_S[4 * c] + Ti[r + 4] * s_S[1 + 4 * c]) + Ti[r + 8] * s_S[2 + 4 * c]) + Ti[r + 12] * s_S[3 + 4 * c];
+        const double w = compose_entry(T_in + (size_t)bl * 16, s_S, r, c);
         T_out[(size_t)bl * 16 + r + 4 * c] = ok ? w : 0.0;
     }
     if (lane == 0) empty[bl] = ok ? 0 : 1;

@@ -92,6 +92,29 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     return z ^ (z >> 31);
 }
 
+// The built-in triple sampler of pcreg_ransac (the oracle's sample_table), its one definition: draw j of hypothesis p uses h =
+// splitmix64(seed ^ splitmix64(16 p + j)) and picks r = ((h >> 32) (n - j)) >> 32 among the indices not yet chosen, in ascending
+// order (a partial Fisher-Yates without replacement).  0-based out; n >= 3.  ransac.hip's hypotheses and fgr.hip's tuple test draw here.
+__device__ __forceinline__ void sample3_builtin(unsigned long long seed, unsigned long long p, int n, int (&s)[3]) {
+    unsigned r[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        unsigned long long h = splitmix64(seed ^ splitmix64(p * 16ull + j));
+        r[j] = (unsigned)(((h >> 32) * (unsigned long long)(unsigned)(n - j)) >> 32);
+    }
+    unsigned i0 = r[0], i1 = r[1];
+    if (i1 >= i0) ++i1;
+    unsigned lo = min(i0, i1), hi = max(i0, i1), i2 = r[2];
+    if (i2 >= lo) ++i2;
+    if (i2 >= hi) ++i2;
+    s[0] = (int)i0; s[1] = (int)i1; s[2] = (int)i2;
+}
+// out-of-range entries of a caller's table must not fault the GPU: clamped to [0, n - 1] (documented in pcreg.h)
+__device__ __forceinline__ void sample3_clamp(int (&s)[3], int n) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s[j] = min(max(s[j], 0), n - 1);
+}
+
 // a 128-bit integer rounded ONCE to double (to nearest, ties to even).  The top 64 bits of |v| with the bits below
 // them folded into the lowest one: 64 > 53 + 2, so the sticky bit never reaches the rounding position and the u64 -> double
 // conversion (correctly rounded) rounds the whole number; the power of two is exact.

@@ -1125,3 +1125,46 @@ class DescriptorPipeline:
                                  _p(self.result), _p(self.inliers), _p(ws), C.c_size_t(ws.numel()), _stream()))
 
     fetch_result = RegistrationPipeline.fetch_result
+
+
+def fgr_batched_dev(p1: torch.Tensor, p2: torch.Tensor, offsets: torch.Tensor, n_cap: int, opts: dict, T0: torch.Tensor = None,
+                    tuple_idx: torch.Tensor = None, kept: bool = False, ws: torch.Tensor = None):
+    """Fast global registration on device buffers (pcreg_dev_fgr_batched), enqueued on torch's current stream, nothing
+    read back.  p1 / p2: [3, ld] float64 (column-major n x 3 with leading dimension ld), offsets: [B + 1] int32 on the device,
+    n_cap: the largest registration (trusted for the launch only), opts: api.fgr_batched's dict; T0 [B, 16] float64, tuple_idx
+    [B, n_tuples, 3] int32 and ws (uint8, at least fgr_workspace_bytes) are optional.  -> (results [B, sizeof(pcreg_fgr_result)]
+    uint8, inlier_idx [ld] int32, kept [ld] uint8 or None): parse a row of results with fgr_results()."""
+    from ._lib import FgrResult
+    from .api import _fgr_opts
+    o = _fgr_opts(opts)
+    for t in (p1, p2):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != 3 or not t.is_contiguous():
+            raise TypeError("pts1 / pts2 are contiguous [3, ld] float64 tensors")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+        raise TypeError("offsets are B + 1 int32 numbers on the device")
+    dev, ld, B = p1.device, int(p1.shape[1]), offsets.numel() - 1
+    if tuple_idx is not None and (tuple_idx.dtype != torch.int32 or tuple(tuple_idx.shape) != (B, o.n_tuples, 3) or not tuple_idx.is_contiguous()):
+        raise TypeError("tuple_idx is a contiguous [B, n_tuples, 3] int32 tensor")
+    if T0 is not None and (T0.dtype != torch.float64 or T0.numel() != 16 * B or not T0.is_contiguous()):
+        raise TypeError("T0 is a contiguous float64 tensor of B x 16 numbers")
+    L = lib()
+    need = L.pcreg_dev_fgr_batched_workspace(int(n_cap), B, o.iterations)
+    if need == 0:
+        raise ValueError("fast global registration: n_cap, B or iterations out of range")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"fast global registration: the workspace is a contiguous uint8 tensor of at least {need} bytes")
+    results = torch.zeros((B, C.sizeof(FgrResult)), dtype=torch.uint8, device=dev)
+    inliers = torch.zeros(max(ld, 1), dtype=torch.int32, device=dev)
+    kept_t = torch.zeros(max(ld, 1), dtype=torch.uint8, device=dev) if kept else None
+    check(L.pcreg_dev_fgr_batched(_p(p1), _p(p2), ld, _p(offsets), B, int(n_cap), C.addressof(o), None if T0 is None else _p(T0),
+                                  None if tuple_idx is None else _p(tuple_idx), _p(results), _p(inliers), None if kept_t is None else _p(kept_t),
+                                  _p(ws), ws.numel(), _stream()))
+    return results, inliers, kept_t
+
+
+def fgr_results(raw) -> list:
+    """the rows of fgr_batched_dev's results on the host (a numpy uint8 [B, sizeof(pcreg_fgr_result)] array) -> FgrResult structs"""
+    from ._lib import FgrResult
+    return [FgrResult.from_buffer_copy(bytes(r)) for r in raw]

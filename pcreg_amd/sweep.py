@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as _l
 from ._lib import RansacOpts, check, lib
-from .api import _match_opts, _transforms16, cluster_points, invertTF, score_summary
+from .api import _fgr_opts, _match_opts, _transforms16, cluster_points, invertTF, score_summary
 from .device import DescriptorPipeline, PreparedModel, _p, _stream
 
 
@@ -384,6 +384,50 @@ class SphereSweep:
                     inlierIdx=np.zeros(0, np.int64) if failed else inliers, numSuccess=r.num_success, maxInliers=r.max_inliers,
                     maxInlierRatio=0.0 if failed or nu2 == 0 else 100.0 * r.max_inliers / nu2,
                     T_final=None if failed or empty_final else Tf, host_syncs=1)
+
+    def fgr_trials(self, result: dict, opts: dict) -> dict:
+        """Fast global registration (pcreg_dev_fgr_batched) of every trial of the last sweep in ransac's place: the
+        trial list of `result` gathered again from the buffers the sweep left on the device (pcreg_dev_sweep_gather, the same
+        packing as the sweep's own), ONE device call over the trials, ONE host synchronisation: the final read.  opts:
+        api.fgr_batched's dict (delta2 is compared with squared distances, as thDist is).  `result` must be the dict that sweep
+        returned.  -> dict(trial, statsPutative, statsInliers (kept pairs within delta2 of the final T), statsRatio (percent),
+        transforms (None where failed), inlierIdx (1-based rows of each trial's pairs), n_kept, cost, host_syncs)."""
+        from .device import fgr_batched_dev, fgr_results
+        st = getattr(self, "_agg", None)
+        if st is None or result is not st["result"]:
+            raise ValueError("fgr_trials: `result` is not the result of this object's last run() / run_streams() (or release() dropped its buffers)")
+        L = lib()
+        dev, sp = self.dev, _stream()
+        trial = np.asarray(result["trial"], dtype=np.int64)
+        nt, VS = len(trial), max(st["VS"], 1)
+        empty = dict(trial=trial, statsPutative=np.zeros(0, np.int64), statsInliers=np.zeros(0, np.int64), statsRatio=np.zeros(0), transforms=[],
+                     inlierIdx=[], n_kept=np.zeros(0, np.int64), cost=np.zeros(0), host_syncs=0)
+        if nt == 0:
+            return empty
+        sizes = np.asarray(result["num_putative"], dtype=np.int64)[trial]
+        offs = np.zeros(nt + 1, dtype=np.int64); offs[1:] = np.cumsum(sizes)
+        total = int(offs[-1])
+        # the trial list, its offsets and its length: one upload (aggregate() hands its members to the gather the same way)
+        ints = torch.from_numpy(np.concatenate([trial, offs, [nt]]).astype(np.int32)).to(dev)
+        t_dev, o_dev, k_dev = ints[:nt], ints[nt:2 * nt + 1], ints[2 * nt + 1:]
+        ld = max(total, 1)
+        p1 = torch.zeros((3, ld), dtype=torch.float64, device=dev); p2 = torch.zeros((3, ld), dtype=torch.float64, device=dev)
+        check(L.pcreg_dev_sweep_gather(_p(st["pairs_all"]), VS, _p(st["n_pairs"]), _p(t_dev), _p(o_dev), _p(k_dev), nt, _p(st["featS"]),
+                                       _p(st["feat_all"]), _p(st["roff_dev"]), _p(p1), _p(p2), ld, sp))
+        n_cap = int(sizes.max())
+        need = L.pcreg_dev_fgr_batched_workspace(n_cap, nt, _fgr_opts(opts).iterations)
+        if getattr(self, "_fgr_ws", None) is None or self._fgr_ws.numel() < need:
+            self._fgr_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        res, inl, _k = fgr_batched_dev(p1, p2, o_dev, n_cap, opts, ws=self._fgr_ws)
+        h = torch.cat([res.view(torch.int32).view(-1), inl]).cpu().numpy()                                            # ---- the one sync
+        nres = res.numel() // 4
+        rs = fgr_results(h[:nres].view(np.uint8).reshape(nt, -1))
+        inliers = h[nres:]
+        return dict(trial=trial, statsPutative=sizes.copy(), statsInliers=np.array([r.n_inliers for r in rs], dtype=np.int64),
+                    statsRatio=np.array([100.0 * r.n_inliers / max(int(n), 1) for r, n in zip(rs, sizes)]),
+                    transforms=[None if r.failed else np.array(r.T[:]).reshape(4, 4, order="F") for r in rs],
+                    inlierIdx=[inliers[offs[t]:offs[t] + rs[t].n_inliers].astype(np.int64) for t in range(nt)],
+                    n_kept=np.array([r.n_kept for r in rs], dtype=np.int64), cost=np.array([r.cost for r in rs]), host_syncs=1)
 
     def run_streams(self, par: dict, options: dict, R_desc: float, d_spheres: float = 5.0, min_pts: int = 1400,
                     putative_thresh: int = 170, seed: int = 0, n_streams: int = 8) -> dict:
