@@ -521,6 +521,30 @@ int pcreg_model_cluster_f32(pcreg_model* model, float r2, int32_t* label, int32_
 /* The same without a handle (clusterPoints(m, r)): uploads and prepares the cloud for this call only. */
 int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* label, int32_t* n_clusters, int32_t* cl_off,
                              int32_t* members);
+/* DBSCAN of the handle's rows -- MATLAB's dbscan(X, epsilon, minpts), scikit-learn's DBSCAN(eps, min_samples) -- with the SQUARED
+ * radius r2 = epsilon^2 as a float and minpts >= 1.  THE CONTRACT of every tier (device, host, MEX, Python):
+ *   NEIGHBOUR  rows i and j (j may equal i) are neighbours iff both are finite and fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= r2 in fp32:
+ *              pcreg_model_cluster_f32's predicate, inclusive; a finite row is its own neighbour; a row with a non-finite
+ *              coordinate has no neighbour, not even itself.
+ *   COUNT      count[i] = the neighbours of row i, itself included: an exact integer, 0 for a non-finite row.
+ *   CORE       core[i] = count[i] >= minpts.
+ *   CLUSTERS   the connected components of the graph over the CORE rows in which two core rows are adjacent iff they are
+ *              neighbours, numbered 0, 1, .. in ascending order of their smallest core row.
+ *   BORDER     a row that is not core and has a core neighbour belongs to the smallest-numbered cluster among its core
+ *              neighbours (what the sequential loops of MATLAB and scikit-learn give it).  It starts no cluster, joins no two
+ *              clusters and does not affect the numbering.
+ *   NOISE      every other row: label -1.  A non-finite row is always noise.
+ * label [M] (0-based, -1 for noise); *n_clusters (0 for M = 0); core [M] (0 / 1) and count [M]: either may be NULL.  cl_off
+ * [M + 1] / members [M] (both or neither may be NULL; with M = 0 label and members may be): the clusters in CSR form over the clusters ONLY, cluster c is
+ * members[cl_off[c] .. cl_off[c + 1]), 0-based rows ascending, border rows included, noise rows in no cluster;
+ * cl_off[0 .. n_clusters] is written.  minpts > M: all noise.  With minpts = 1 on finite rows the labels are
+ * pcreg_model_cluster_f32's bit for bit.  Exact and deterministic: a function of (model rows, r2, minpts) only.
+ * PCREG_E_ARG: r2 NaN or negative; minpts < 1; a NULL n_clusters; a NULL label with M > 0; one of cl_off / members alone. */
+int pcreg_model_dbscan_f32(pcreg_model* model, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core, int32_t* count,
+                           int32_t* cl_off, int32_t* members);
+/* The same without a handle: uploads and prepares the cloud (M x 3 column-major, ldm >= M) for this call only. */
+int pcreg_dbscan_points_f32(const float* m, int M, int ldm, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core,
+                            int32_t* count, int32_t* cl_off, int32_t* members);
 /* The surface normal of every row of the model from its k nearest rows (MATLAB's pcnormals(ptCloud, k); the third PCA axis
  * AlignPoints_KNN.m:29-34 takes of a neighbourhood).  THE CONTRACT of every tier (device, host, MEX, Python):
  * inputs -- a prepared model of M rows; k with 3 <= k <= PCREG_KNN_MAX_K; a viewpoint of three doubles on the host, or NULL.
@@ -1377,6 +1401,20 @@ int pcreg_dev_model_refit_cpd_f32(const pcreg_dev_model* model, const float* q, 
 size_t pcreg_dev_model_cluster_workspace(int M);
 int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t* label, int32_t* n_clusters, int32_t* first,
                                 int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+/* pcreg_model_dbscan_f32's contract on the device, in one launch chain without a host read: the neighbour count of
+ * every row by a full self-join, the union of the core rows by pcreg_dev_model_cluster_f32's walk with only core rows staged,
+ * flatten and number with only core roots counted, a second full self-join that gives every border row the smallest root among
+ * its core neighbours, and the labels.  label [M] int32 by ORIGINAL row, -1 for noise; n_clusters one int32 on the device; core
+ * [M] uint8, count [M] int32, first [M] (first[c] the smallest CORE row of cluster c) and sizes [M] (sizes[c] the rows of cluster
+ * c, border rows included): each of the four may be NULL; first and sizes are ZERO at and past n_clusters.  The result is a
+ * function of (model rows, r2, minpts) only -- not of the order of atomics, the order inside a cell, culling or the stream.
+ * Nothing synchronises; no workgroup waits for another.  PCREG_E_ARG: r2 NaN or negative, minpts < 1, a NULL model, label,
+ * n_clusters or workspace.  PCREG_E_WORKSPACE for a short workspace.
+ * Workspace: 4 * roundup(4 * max(M, 1), 256) + roundup(4 * max(ceil(M / 2048), 1), 256) bytes, whatever r2, minpts and the
+ * result.  A handle may serve several streams at once, each call with its own workspace. */
+size_t pcreg_dev_model_dbscan_workspace(int M);
+int pcreg_dev_model_dbscan_f32(const pcreg_dev_model* model, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core,
+                               int32_t* count, int32_t* first, int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 /* pcreg_model_normals_f32's contract on the device: normals [3 * ldn] and variation [M] (or NULL) are device
  * pointers, the viewpoint stays on the host (it travels as kernel arguments).  Two launches: the seed bound of every sorted row,
  * then one walk in which a workgroup owns 64 rows of a tile, keeps their k-lists in registers and finishes each row's normal

@@ -51,6 +51,13 @@
 //                                          members(clOff(c) + 1 : clOff(c + 1)), ascending; the connected components of the graph
 //                                          "distance <= r", numbered by their smallest row (clusterPoints.m:16-45;
 //                                          matlab/clusterPointsModel.m, matlab/clusterPointsFast.m)
+//   'modelDbscan', handle, epsilon, minpts | 'dbscanPoints', pts (single M x 3), epsilon, minpts -> label (M x 1 int32, the 1-based
+//                                          cluster of every row, -1 for noise), core (M x 1 uint8, 1 for a core row), clOff
+//                                          (C + 1 int32 offsets), members (int32, 1-based rows, the clustered rows only): DBSCAN as
+//                                          MATLAB's dbscan(X, epsilon, minpts) -- a row is core with at least minpts rows, itself
+//                                          included, within epsilon; clusters numbered by their smallest core row; a border row
+//                                          joins the smallest-numbered cluster among its core neighbours; always four outputs
+//                                          (matlab/dbscanModel.m, matlab/dbscanFast.m)
 //   'modelNormals', handle, k, viewpoint | 'pointNormals', pts (single M x 3), k, viewpoint -> normals (M x 3 single), variation
 //                                          (M x 1 single): the normal of every row from its k nearest rows (3 <= k <= 32, the row
 //                                          itself among them), the eigenvector of the smallest eigenvalue of their scatter in
@@ -231,6 +238,34 @@ static int cluster_on_handle(pcreg_model* h, float r, mxArray* out[3]) {
         memcpy(mxGetData(out[1]), off, ((size_t)nc + 1) * sizeof(int32_t));
     } else { mxDestroyArray(ol); mxDestroyArray(om); }
     mxDestroyArray(bo);
+    return rc;
+}
+
+// the four outputs of 'modelDbscan' / 'dbscanPoints': label (M x 1 int32, 1-based, -1 for noise), core (M x 1 uint8, 0 / 1), clOff
+// (C + 1 int32), members (int32, 1-based, the clustered rows only); single(epsilon) is squared once, in single.  Nothing is left
+// allocated on an error.
+static int dbscan_on_handle(pcreg_model* h, float eps, int minpts, mxArray* out[4]) {
+    int M = 0;
+    int rc = pcreg_model_size(h, &M);
+    if (rc != PCREG_OK) return rc;
+    mxArray* ol = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    mxArray* oc = mxCreateNumericMatrix((size_t)M, 1, mxUINT8_CLASS, mxREAL);
+    mxArray* bm = mxCreateNumericMatrix((size_t)M, 1, mxINT32_CLASS, mxREAL);
+    mxArray* bo = mxCreateNumericMatrix((size_t)M + 1, 1, mxINT32_CLASS, mxREAL);
+    int32_t *lab = (int32_t*)mxGetData(ol), *mem = (int32_t*)mxGetData(bm), *off = (int32_t*)mxGetData(bo);
+    int32_t nc = 0;
+    rc = pcreg_model_dbscan_f32(h, eps * eps, minpts, lab, &nc, (uint8_t*)mxGetData(oc), nullptr, off, mem);
+    if (rc == PCREG_OK) {
+        for (int i = 0; i < M; ++i) if (lab[i] >= 0) lab[i] += 1;
+        out[0] = ol; out[1] = oc;
+        out[2] = mxCreateNumericMatrix((size_t)nc + 1, 1, mxINT32_CLASS, mxREAL);
+        memcpy(mxGetData(out[2]), off, ((size_t)nc + 1) * sizeof(int32_t));
+        const int n = off[nc];
+        out[3] = mxCreateNumericMatrix((size_t)n, 1, mxINT32_CLASS, mxREAL);
+        int32_t* om = (int32_t*)mxGetData(out[3]);
+        for (int i = 0; i < n; ++i) om[i] = mem[i] + 1;
+    } else { mxDestroyArray(ol); mxDestroyArray(oc); }
+    mxDestroyArray(bm); mxDestroyArray(bo);
     return rc;
 }
 
@@ -1345,6 +1380,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (rc == PCREG_OK) rc = cluster_on_handle(h, (float)mxGetScalar(prhs[2]), out);
             if (h) (void)pcreg_model_destroy(h);
             if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; }
+        }
+    } else if (!strcmp(cmd, "modelDbscan")) {                 // [label, core, clOff, members] = pcreg_mex('modelDbscan', h, epsilon, minpts)
+        if (nrhs != 4 || !mxIsUint64(prhs[1]) || !radius_ok(prhs[2]) || !whole_scalar_ok(prhs[3], 1.0, 2147483647.0))
+            usage = "modelDbscan: handle (uint64), epsilon (a real scalar >= 0), minpts (a whole number >= 1)";
+        else {
+            mxArray* out[4] = {nullptr, nullptr, nullptr, nullptr};
+            rc = dbscan_on_handle((pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]), (float)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), out);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; plhs[3] = out[3]; }
+        }
+    } else if (!strcmp(cmd, "dbscanPoints")) {                // [label, core, clOff, members] = pcreg_mex('dbscanPoints', single(pts), epsilon, minpts)
+        if (nrhs != 4 || !mxIsSingle(prhs[1]) || mxGetN(prhs[1]) != 3 || !radius_ok(prhs[2]) || !whole_scalar_ok(prhs[3], 1.0, 2147483647.0))
+            usage = "dbscanPoints: pts (single M x 3), epsilon (a real scalar >= 0), minpts (a whole number >= 1)";
+        else {
+            const int M = (int)mxGetM(prhs[1]);
+            pcreg_model* h = nullptr;
+            rc = pcreg_model_create((const float*)mxGetData(prhs[1]), M, M > 0 ? M : 1, &h);
+            mxArray* out[4] = {nullptr, nullptr, nullptr, nullptr};
+            if (rc == PCREG_OK) rc = dbscan_on_handle(h, (float)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), out);
+            if (h) (void)pcreg_model_destroy(h);
+            if (rc == PCREG_OK) { plhs[0] = out[0]; plhs[1] = out[1]; plhs[2] = out[2]; plhs[3] = out[3]; }
         }
     } else if (!strcmp(cmd, "modelNormals")) {                // [normals, variation] = pcreg_mex('modelNormals', h, k, viewpoint)
         if (nrhs != 4 || !mxIsUint64(prhs[1]) || !normals_k_ok(prhs[2]) || !viewpoint_ok(prhs[3]))

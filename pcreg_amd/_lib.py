@@ -71,6 +71,7 @@ SYMBOLS = [
     "pcreg_knn2_points_f32", "pcreg_match_points_f32", "pcreg_match_features", "pcreg_get_matches", "pcreg_desc_set_create", "pcreg_desc_set_destroy", "pcreg_desc_set_size", "pcreg_get_matches_on_sets", "pcreg_get_matches_segmented_on_sets", "pcreg_sphere_counts", "pcreg_sphere_sweep", "pcreg_sphere_model_create", "pcreg_sphere_model_destroy", "pcreg_sphere_sweep_on_model", "pcreg_final_stage_limits", "pcreg_final_stage", "pcreg_get_matches_segmented", "pcreg_get_local_points",
     "pcreg_model_create", "pcreg_model_destroy", "pcreg_model_size", "pcreg_model_match_points_f32", "pcreg_model_knn_f32", "pcreg_knn_points_f32",
     "pcreg_model_range_f32", "pcreg_range_points_f32", "pcreg_model_cluster_f32", "pcreg_cluster_points_f32",
+    "pcreg_model_dbscan_f32", "pcreg_dbscan_points_f32", "pcreg_dev_model_dbscan_workspace", "pcreg_dev_model_dbscan_f32",
     "pcreg_dev_model_create", "pcreg_dev_model_destroy", "pcreg_dev_model_search_workspace", "pcreg_dev_model_search_f32",
     "pcreg_dev_model_knn_workspace", "pcreg_dev_model_knn_f32", "pcreg_dev_merge_topk_f32",
     "pcreg_dev_model_range_workspace", "pcreg_dev_model_range_count_f32", "pcreg_dev_model_range_fill_f32",
@@ -158,6 +159,13 @@ def lib() -> C.CDLL:
             L.pcreg_model_cluster_f32.argtypes = [vp, f, vp, vp, vp, vp]
             L.pcreg_cluster_points_f32.argtypes = [vp, i, i, f, vp, vp, vp, vp]
             L.pcreg_debug_cluster_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+        if hasattr(L, "pcreg_dev_model_dbscan_workspace"):    # (an older build given through PCREG_LIB lacks DBSCAN)
+            L.pcreg_dev_model_dbscan_workspace.restype = C.c_size_t
+            L.pcreg_dev_model_dbscan_workspace.argtypes = [C.c_int]
+            vp, i, f = C.c_void_p, C.c_int, C.c_float                            # (a float by value: declared)
+            L.pcreg_dev_model_dbscan_f32.argtypes = [vp, f, i, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+            L.pcreg_model_dbscan_f32.argtypes = [vp, f, i, vp, vp, vp, vp, vp, vp]
+            L.pcreg_dbscan_points_f32.argtypes = [vp, i, i, f, i, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_model_score_workspace"):     # (an older build given through PCREG_LIB lacks the transform scoring)
             L.pcreg_dev_model_score_workspace.restype = C.c_size_t
             L.pcreg_dev_model_score_workspace.argtypes = [C.c_int] * 3

@@ -751,6 +751,37 @@ def cluster_points(pts, r2: float):
     return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_cluster_points_f32(m.ctypes.data, M, max(M, 1), r2, lab, nc, off, mem)), M)
 
 
+def _dbscan_minpts(minpts) -> int:
+    if int(minpts) != minpts or int(minpts) < 1:
+        raise ValueError(f"minpts must be a whole number >= 1, got {minpts}")
+    return int(minpts)
+
+
+def _dbscan_call(call, M: int):
+    label = np.zeros(max(M, 1), dtype=np.int32)
+    core = np.zeros(max(M, 1), dtype=np.uint8)
+    cl_off = np.zeros(M + 1, dtype=np.int32)
+    members = np.zeros(max(M, 1), dtype=np.int32)
+    nc = C.c_int32(0)
+    call(label.ctypes.data, C.byref(nc), core.ctypes.data, cl_off.ctypes.data, members.ctypes.data)
+    return label[:M], core[:M] != 0, cl_off[:nc.value + 1].copy(), members[:cl_off[nc.value]].copy()
+
+
+def dbscan_points(pts, r2: float, minpts: int):
+    """DBSCAN of the rows of pts in fp32 with r2 = epsilon^2 (MATLAB's dbscan(X, epsilon, minpts), scikit-learn's
+    DBSCAN(eps, min_samples=minpts)): (label [M] int32, 0-based, -1 for noise; core [M] bool; cl_off [C + 1] int32; members int32).
+    A row is a core row when at least minpts rows, itself included, lie within the radius (squared distance <= r2, inclusive);
+    the clusters are the connected components of the core rows, numbered in ascending order of their smallest core row; a
+    border row joins the smallest-numbered cluster among its core neighbours; cluster c is members[cl_off[c] .. cl_off[c + 1]),
+    ascending, border rows included, noise rows in no cluster.  A row with a non-finite coordinate is noise.  The cloud is
+    prepared for this call only: keep a Model for repeated calls."""
+    r2, minpts = _range_r2(r2), _dbscan_minpts(minpts)
+    m = _fcol(pts, np.float32)
+    M = m.shape[0]
+    return _dbscan_call(lambda lab, nc, core, off, mem: check(lib().pcreg_dbscan_points_f32(m.ctypes.data, M, max(M, 1), r2, minpts, lab, nc, core,
+                                                                                          None, off, mem)), M)
+
+
 def _normals_args(k, viewpoint):
     k = int(k)
     if not 3 <= k <= KNN_MAX_K:
@@ -1516,6 +1547,15 @@ class Model:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
         return _cluster_call(lambda lab, nc, off, mem: check(lib().pcreg_model_cluster_f32(self._h, r2, lab, nc, off, mem)), self.M)
+
+    def dbscan(self, r2: float, minpts: int):
+        """DBSCAN of the prepared model's own rows with r2 = epsilon^2: (label [M] int32, core [M] bool, cl_off [C + 1] int32,
+        members int32), 0-based, noise -1 -- dbscan_points' contract."""
+        if not self._h.value:
+            raise ValueError("the model handle is closed")
+        r2, minpts = _range_r2(r2), _dbscan_minpts(minpts)
+        return _dbscan_call(lambda lab, nc, core, off, mem: check(lib().pcreg_model_dbscan_f32(self._h, r2, minpts, lab, nc, core, None, off, mem)),
+                            self.M)
 
     def normals(self, k: int, viewpoint=None, variation: bool = False):
         """The surface normal of every row of the prepared model from its k nearest rows: normals [M, 3] float32, and with

@@ -515,6 +515,13 @@ int pcreg_dev_model_cluster_f32(const pcreg_dev_model* model, float r2, int32_t*
     GUARD();
     return launch_model_cluster(model->v, r2, label, n_clusters, first, sizes, workspace, workspace_bytes, (hipStream_t)stream);
 }
+size_t pcreg_dev_model_dbscan_workspace(int M) { return dbscan_ws_bytes(M); }
+int pcreg_dev_model_dbscan_f32(const pcreg_dev_model* model, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core,
+                               int32_t* count, int32_t* first, int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+    PCREG_ARG(model && label && n_clusters && workspace && r2 >= 0.0f && minpts >= 1);
+    GUARD();
+    return launch_model_dbscan(model->v, r2, minpts, label, n_clusters, core, count, first, sizes, workspace, workspace_bytes, (hipStream_t)stream);
+}
 size_t pcreg_dev_model_normals_workspace(int M, int k) { return normals_ws_bytes(M, k); }
 int pcreg_dev_model_normals_f32(const pcreg_dev_model* model, int k, const double* viewpoint, float* normals, int ldn, float* variation,
                                 void* workspace, size_t workspace_bytes, void* stream) {
@@ -1026,6 +1033,60 @@ int pcreg_cluster_points_f32(const float* m, int M, int ldm, float r2, int32_t* 
     const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
     TRY(launch_model_prepare(v, g_stream));
     return cluster_on_view(st, v, r2, label, n_clusters, cl_off, members);
+}
+
+// DBSCAN on a prepared model: label, core and count on the device, read back; the CSR lists on the host as
+// cluster_on_view forms them, over the clusters only: a noise row (label -1) is in no list
+static int dbscan_on_view(Stage& st, const ModelView& v, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core, int32_t* count,
+                          int32_t* cl_off, int32_t* members) {
+    const int M = v.M;
+    *n_clusters = 0;
+    if (cl_off) cl_off[0] = 0;
+    if (M == 0) return PCREG_OK;
+    int32_t *dl, *dn, *dc = nullptr; uint8_t* dk = nullptr; char* ws;
+    const size_t wsb = dbscan_ws_bytes(M);
+    TRY(st.take((size_t)M, &dl));
+    TRY(st.take(1, &dn));
+    if (core) TRY(st.take((size_t)M, &dk));
+    if (count) TRY(st.take((size_t)M, &dc));
+    TRY(st.take(wsb, &ws));
+    TRY(launch_model_dbscan(v, r2, minpts, dl, dn, dk, dc, nullptr, nullptr, ws, wsb, g_stream));
+    int32_t nc = 0;
+    PCREG_HIP(hipMemcpyAsync(label, dl, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipMemcpyAsync(&nc, dn, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
+    if (core) PCREG_HIP(hipMemcpyAsync(core, dk, (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    if (count) PCREG_HIP(hipMemcpyAsync(count, dc, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, g_stream));
+    PCREG_HIP(hipStreamSynchronize(g_stream));
+    *n_clusters = nc;
+    if (!cl_off) return PCREG_OK;
+    for (int c = 0; c <= nc; ++c) cl_off[c] = 0;
+    for (int i = 0; i < M; ++i) if (label[i] >= 0) ++cl_off[label[i] + 1];
+    for (int c = 0; c < nc; ++c) cl_off[c + 1] += cl_off[c];
+    std::vector<int32_t> at(cl_off, cl_off + nc);
+    for (int i = 0; i < M; ++i) if (label[i] >= 0) members[at[label[i]]++] = i;
+    return PCREG_OK;
+}
+int pcreg_model_dbscan_f32(pcreg_model* model, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core, int32_t* count,
+                           int32_t* cl_off, int32_t* members) {
+    PCREG_ARG(model && n_clusters && r2 >= 0.0f && minpts >= 1 && (members || !cl_off || model->M == 0) && (cl_off || !members));
+    PCREG_ARG(model->dm != nullptr && (label || model->M == 0));
+    GUARD();
+    Stage st{scratch()};
+    return dbscan_on_view(st, model->dm->v, r2, minpts, label, n_clusters, core, count, cl_off, members);
+}
+int pcreg_dbscan_points_f32(const float* m, int M, int ldm, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core,
+                            int32_t* count, int32_t* cl_off, int32_t* members) {
+    PCREG_ARG(n_clusters && M >= 0 && ldm >= M && (M == 0 || (m && label)) && r2 >= 0.0f && minpts >= 1 && (members || !cl_off || M == 0) &&
+              (cl_off || !members));
+    GUARD();
+    Stage st{scratch()};
+    float* dm; char* block;
+    TRY(st.take(3 * (size_t)(M > 0 ? M : 1), &dm));
+    TRY(st.take(model_prep_bytes(M), &block));
+    TRY(upload_cols(m, M, ldm, 3, dm, g_stream));
+    const ModelView v = model_view(dm, M, M > 0 ? M : 1, block);
+    TRY(launch_model_prepare(v, g_stream));
+    return dbscan_on_view(st, v, r2, minpts, label, n_clusters, core, count, cl_off, members);
 }
 
 // normals of a prepared model's own rows: compute on the device (compact, ld = M), read back into the caller's leading dimension

@@ -278,6 +278,18 @@ int launch_model_refit_cpd(const ModelView& v, const float* q, int Q, int ldq, c
 size_t cluster_ws_bytes(int M);
 int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* n_clusters, int32_t* first, int32_t* sizes, void* ws,
                          size_t ws_bytes, hipStream_t st);
+// DBSCAN over the model's own rows: count walk, core union walk, flatten, number, border walk, label.  label [M],
+// core [M] (or null), count [M] (or null), first / sizes [M] (or null) by ORIGINAL row / cluster, n_clusters one int32 -- device
+// pointers.  The launcher and the union-find's kernels are knn_cluster.hip's; the two walks without a union are knn_dbscan.hip's:
+//   enqueue_dbscan_count   cnt_sorted[sorted row] = the row's neighbours, itself included (0 for a non-finite row); then, by
+//                          ORIGINAL row, cnt[i] the same, parent[i] = i, first / sizes cleared
+//   enqueue_dbscan_border  after the flatten: parent[i] of a non-core row with a core neighbour = the smallest root among them
+size_t dbscan_ws_bytes(int M);
+int launch_model_dbscan(const ModelView& v, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core, int32_t* count,
+                        int32_t* first, int32_t* sizes, void* ws, size_t ws_bytes, hipStream_t st);
+void enqueue_dbscan_count(const ModelView& v, float r2, int cull, int32_t* cnt_sorted, int32_t* cnt, int32_t* parent, int32_t* first,
+                          int32_t* sizes, hipStream_t st);
+void enqueue_dbscan_border(const ModelView& v, float r2, int cull, const int32_t* cnt_sorted, int minpts, int32_t* parent, hipStream_t st);
 // the surface normal of every model row from its k nearest rows (knn_normals.hip): normals [3][ldn] and variation [M]
 // (or null) by ORIGINAL row; viewpoint: three host doubles or null
 size_t normals_ws_bytes(int M, int k);

@@ -13,6 +13,11 @@
 //   C4  cluster_number_kernel   the chunk scan's second launch (chunk_scan.hpp): the cluster number of every root, first[],
 //                               n_clusters
 //   C5  cluster_label_kernel    label[i] = number[parent[i]]; sizes[] by integer atomicAdd, one per (wave, cluster)
+//
+// DBSCAN of the prepared model runs on the same union-find: with the neighbour count of every row (knn_dbscan.hip)
+// the walk stages and keeps live the CORE rows only (cluster_walk_kernel<true>), flatten and number take a root for a cluster
+// only if it is core, a border row is hooked under its smallest core neighbour's root after the flatten (knn_dbscan.hip), and
+// dbscan_label_kernel leaves the rest at -1.
 #include "common.hpp"
 #include "knn_fast_common.hpp"
 #include "knn_walk.hpp"
@@ -75,9 +80,13 @@ __global__ __launch_bounds__(kBlock) void cluster_init_kernel(int M, int32_t* __
 // D = r2 and B = tile a's box: every row pair of a skipped tile pair has a computed d > r2.  The walk itself is knn_walk.hpp's,
 // and so are the row prologue (walk_self_row), the staging rule (walk_row_finite) and the visit rule (walk_visits).
 // A non-finite row is staged as NaN and its own lanes admit nothing, so it stays a set of its own whatever r2.
+// kCoreOnly (DBSCAN's core walk): the same holds for every row with cnt[sorted row] < minpts, and a workgroup none of whose 64
+// rows is core leaves before the walk (the vote is the workgroup's, so nobody misses a barrier).
+template <bool kCoreOnly>
 __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
                                                               const float* __restrict__ tbox, int n_tiles, int cull, int skip_same, float r2,
-                                                              int32_t* parent, unsigned long long* __restrict__ stats,
+                                                              const int32_t* __restrict__ cnt, int minpts, int32_t* parent,
+                                                              unsigned long long* __restrict__ stats,
                                                               unsigned long long* __restrict__ cstats) {
     __shared__ WalkLds lds;
     const int ta = blockIdx.x / kWalkWgPerTile, part = blockIdx.x % kWalkWgPerTile;
@@ -86,14 +95,22 @@ __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __res
     float abox[6];
     walk_tile_box(tbox, ta, abox);
     const WalkSelfRow q = walk_self_row(ms, perm, M, ta, part);
-    const float rr = q.live ? r2 : -1.0f;                         // (a dead lane admits nothing: d is never negative)
+    bool live = q.live;
+    if constexpr (kCoreOnly) {
+        live = live && cnt[q.sr] >= minpts;
+        if (!__syncthreads_or(live ? 1 : 0)) return;
+    }
+    const float rr = live ? r2 : -1.0f;                           // (a dead lane admits nothing: d is never negative)
     int my_root = q.row_i;                                        // the last root this lane saw for its row
     unsigned long long n_hit = 0;
     int above = -1;                                               // on the diagonal only the rows behind this one
     walk_tiles(
         lds, ta, n_tiles, q.qx, q.qy, q.qz, part == 0 ? stats : nullptr,
         [&](int ct) { return walk_visits(tbox, ct, abox, r2, cull); },
-        [&](int r) { return walk_row_finite(ms, perm, M, r); },
+        [&](int r) {
+            if constexpr (kCoreOnly) return walk_row_core(ms, perm, M, cnt, minpts, r);
+            else return walk_row_finite(ms, perm, M, r);
+        },
         [&](int ct) { above = ct == ta ? q.rl : -1; },
         [&](int r, const float4 (&p)[4], float (&d)[4]) {
             const float qnan = __int_as_float(0x7FC00000);
@@ -119,7 +136,10 @@ __global__ __launch_bounds__(kBlock) void cluster_walk_kernel(const float* __res
 // ---- C3. flatten: parent[i] = the root of i; the number of roots per chunk ----------------------------------------------
 // (the walk is a finished launch: its parent[] is visible.  A thread's store only replaces an ancestor of i by the root, so
 // the threads that pass through i in the same launch still reach the same root.)
-__global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t* parent, int32_t* __restrict__ csum) {
+// cnt (by ORIGINAL row) and minpts are DBSCAN's: only a core root stands for a cluster.  clusterPoints passes no cnt: every row is core.
+__device__ __forceinline__ bool row_is_core(const int32_t* __restrict__ cnt, int minpts, int i) { return !cnt || cnt[i] >= minpts; }
+__global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t* parent, const int32_t* __restrict__ cnt, int minpts,
+                                                                 int32_t* __restrict__ csum) {
     const int base = blockIdx.x * kScanChunk;
     int32_t v = 0;
     for (int k = threadIdx.x; k < kScanChunk; k += kBlock) {
@@ -128,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t*
             int r = uf_load(parent, i);
             while (true) { const int n = uf_load(parent, r); if (n == r) break; r = n; }
             __hip_atomic_store(parent + i, r, PCREG_RLX_AGENT);
-            v += r == i ? 1 : 0;
+            v += r == i && row_is_core(cnt, minpts, i) ? 1 : 0;
         }
     }
     chunk_sum(v, csum);
@@ -137,13 +157,13 @@ __global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(int M, int32_t*
 // ---- C4. number the roots in row order --------------------------------------------------------------------------------
 // the two-launch chunk scan (chunk_scan.hpp) over the rows' "is a root": num[i] (roots only) = the roots before row i; the last
 // chunk writes n_clusters
-__global__ __launch_bounds__(kBlock) void cluster_number_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ csum,
-                                                                int32_t* __restrict__ num, int32_t* __restrict__ first,
-                                                                int32_t* __restrict__ n_clusters) {
+__global__ __launch_bounds__(kBlock) void cluster_number_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ cnt,
+                                                                int minpts, const int32_t* __restrict__ csum, int32_t* __restrict__ num,
+                                                                int32_t* __restrict__ first, int32_t* __restrict__ n_clusters) {
     const int i0 = blockIdx.x * kScanChunk + threadIdx.x * kScanPer;
     int32_t f[kScanPer], mine = 0;
 #pragma unroll
-    for (int u = 0; u < kScanPer; ++u) { f[u] = i0 + u < M && parent[i0 + u] == i0 + u ? 1 : 0; mine += f[u]; }
+    for (int u = 0; u < kScanPer; ++u) { f[u] = i0 + u < M && parent[i0 + u] == i0 + u && row_is_core(cnt, minpts, i0 + u) ? 1 : 0; mine += f[u]; }
     int32_t run = chunk_offset(csum, mine);
 #pragma unroll
     for (int u = 0; u < kScanPer; ++u) {
@@ -157,13 +177,8 @@ __global__ __launch_bounds__(kBlock) void cluster_number_kernel(int M, const int
 // sizes: one atomicAdd per (wave, cluster) -- the lanes of a wave that share a cluster are counted by their leader.  Rows that
 // follow each other mostly share a cluster when clusters are large (a million single adds to ONE word took 11 ms), and when
 // they do not, the adds go to different words anyway.
-__global__ __launch_bounds__(kBlock) void cluster_label_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ num,
-                                                               int32_t* __restrict__ label, int32_t* __restrict__ sizes) {
-    const int i = blockIdx.x * kBlock + threadIdx.x, lane = threadIdx.x & 63;
-    const bool live = i < M;
-    int c = -1;
-    if (live) { c = num[parent[i]]; label[i] = c; }
-    if (!sizes) return;
+__device__ __forceinline__ void wave_count_sizes(bool live, int c, int32_t* __restrict__ sizes) {
+    const int lane = threadIdx.x & 63;
     unsigned long long todo = __builtin_amdgcn_ballot_w64(live);
     while (todo) {                                                // (wave-uniform: every lane sees the same todo)
         const int lead = __ffsll((long long)todo) - 1;
@@ -172,6 +187,33 @@ __global__ __launch_bounds__(kBlock) void cluster_label_kernel(int M, const int3
         if (lane == lead) atomicAdd(&sizes[cl], (int)__popcll(same));
         todo &= ~same;
     }
+}
+__global__ __launch_bounds__(kBlock) void cluster_label_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ num,
+                                                               int32_t* __restrict__ label, int32_t* __restrict__ sizes) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < M;
+    int c = -1;
+    if (live) { c = num[parent[i]]; label[i] = c; }
+    if (sizes) wave_count_sizes(live, c, sizes);
+}
+// DBSCAN's: a core row carries its root's number; a non-core row that the border walk hooked under a root (parent[i] != i)
+// carries that root's; every other row is noise, -1, and counted in no cluster.  core / count (either may be null) are the
+// caller's copies of what the count walk found.
+__global__ __launch_bounds__(kBlock) void dbscan_label_kernel(int M, const int32_t* __restrict__ parent, const int32_t* __restrict__ num,
+                                                              const int32_t* __restrict__ cnt, int minpts, int32_t* __restrict__ label,
+                                                              uint8_t* __restrict__ core, int32_t* __restrict__ count,
+                                                              int32_t* __restrict__ sizes) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    int c = -1;
+    if (i < M) {
+        const int n = cnt[i], p = parent[i];
+        const bool is_core = n >= minpts;
+        if (is_core || p != i) c = num[p];
+        label[i] = c;
+        if (core) core[i] = is_core ? 1 : 0;
+        if (count) count[i] = n;
+    }
+    if (sizes) wave_count_sizes(c >= 0, c, sizes);
 }
 
 // Workspace: [parent, M] [cluster number of every root, M] [roots per chunk of 2048 rows]:
@@ -183,6 +225,22 @@ ClusterWs cluster_ws_layout(int M, void* base, size_t* bytes) {
     WsWalk w(base);
     s.parent = w.take<int32_t>(mm);
     s.num = w.take<int32_t>(mm);
+    s.csum = w.take<int32_t>((mm + kScanChunk - 1) / kScanChunk);
+    *bytes = w.bytes();
+    return s;
+}
+// DBSCAN's: [parent, M] [cluster number of every core root, M] [neighbour count by sorted row, M] [... by original row, M]
+// [core roots per chunk of 2048 rows]:
+// 4 * roundup(4 * max(M, 1), 256) + roundup(4 * max(ceil(M / 2048), 1), 256) bytes, whatever r2, minpts and the result
+struct DbscanWs { int32_t* parent; int32_t* num; int32_t* cnt_sorted; int32_t* cnt; int32_t* csum; };
+DbscanWs dbscan_ws_layout(int M, void* base, size_t* bytes) {
+    DbscanWs s{};
+    const size_t mm = (size_t)(M > 0 ? M : 1);
+    WsWalk w(base);
+    s.parent = w.take<int32_t>(mm);
+    s.num = w.take<int32_t>(mm);
+    s.cnt_sorted = w.take<int32_t>(mm);
+    s.cnt = w.take<int32_t>(mm);
     s.csum = w.take<int32_t>((mm + kScanChunk - 1) / kScanChunk);
     *bytes = w.bytes();
     return s;
@@ -210,14 +268,47 @@ int launch_model_cluster(const ModelView& v, float r2, int32_t* label, int32_t* 
     const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile pair, same bits
     const int skip_same = debug_flag(kDbgClusterNoSkip) ? 0 : 1; // "cluster_noskip": unite on every hit, same bits
     hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks), dim3(kBlock), 0, st, M, s.parent, first, sizes);
-    hipLaunchKernelGGL(cluster_walk_kernel, dim3((unsigned)(n_tiles * kWalkWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
-                       (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, skip_same, r2, s.parent, knn_stats_dev(),
-                       cluster_stats_dev());
-    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(chunks), dim3(kBlock), 0, st, M, s.parent, s.csum);
-    hipLaunchKernelGGL(cluster_number_kernel, dim3(chunks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.csum, s.num,
-                       first, n_clusters);
+    hipLaunchKernelGGL(cluster_walk_kernel<false>, dim3((unsigned)(n_tiles * kWalkWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
+                       (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, skip_same, r2, (const int32_t*)nullptr, 1, s.parent,
+                       knn_stats_dev(), cluster_stats_dev());
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(chunks), dim3(kBlock), 0, st, M, s.parent, (const int32_t*)nullptr, 1, s.csum);
+    hipLaunchKernelGGL(cluster_number_kernel, dim3(chunks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)nullptr, 1,
+                       (const int32_t*)s.csum, s.num, first, n_clusters);
     hipLaunchKernelGGL(cluster_label_kernel, dim3(blocks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.num, label,
                        sizes);
+    PCREG_HIP(hipGetLastError());
+    return PCREG_OK;
+}
+
+size_t dbscan_ws_bytes(int M) {
+    size_t b; (void)dbscan_ws_layout(M, nullptr, &b);
+    return b;
+}
+
+int launch_model_dbscan(const ModelView& v, float r2, int minpts, int32_t* label, int32_t* n_clusters, uint8_t* core, int32_t* count,
+                        int32_t* first, int32_t* sizes, void* ws, size_t ws_bytes, hipStream_t st) {
+    PCREG_ARG(r2 >= 0.0f && minpts >= 1 && n_clusters && (label || v.M == 0));
+    size_t need;
+    const DbscanWs s = dbscan_ws_layout(v.M, ws, &need);
+    if (ws_bytes < need) { set_error("dbscan workspace too small: %zu < %zu", ws_bytes, need); return PCREG_E_WORKSPACE; }
+    const int M = v.M;
+    if (M == 0) {                                                 // no cluster
+        PCREG_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), st));
+        return PCREG_OK;
+    }
+    const int n_tiles = (M + kT16 - 1) / kT16, chunks = (M + kScanChunk - 1) / kScanChunk, blocks = (M + kBlock - 1) / kBlock;
+    const int cull = debug_flag(kDbgKnnNoCull) ? 0 : 1;          // "knn_nocull": visit every tile pair, same bits
+    const int skip_same = debug_flag(kDbgClusterNoSkip) ? 0 : 1; // "cluster_noskip": unite on every hit, same bits
+    enqueue_dbscan_count(v, r2, cull, s.cnt_sorted, s.cnt, s.parent, first, sizes, st);
+    hipLaunchKernelGGL(cluster_walk_kernel<true>, dim3((unsigned)(n_tiles * kWalkWgPerTile)), dim3(kBlock), 0, st, (const float*)v.ms,
+                       (const int32_t*)v.perm, M, (const float*)v.tbox, n_tiles, cull, skip_same, r2, (const int32_t*)s.cnt_sorted, minpts,
+                       s.parent, knn_stats_dev(), cluster_stats_dev());
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(chunks), dim3(kBlock), 0, st, M, s.parent, (const int32_t*)s.cnt, minpts, s.csum);
+    hipLaunchKernelGGL(cluster_number_kernel, dim3(chunks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.cnt, minpts,
+                       (const int32_t*)s.csum, s.num, first, n_clusters);
+    enqueue_dbscan_border(v, r2, cull, s.cnt_sorted, minpts, s.parent, st);
+    hipLaunchKernelGGL(dbscan_label_kernel, dim3(blocks), dim3(kBlock), 0, st, M, (const int32_t*)s.parent, (const int32_t*)s.num,
+                       (const int32_t*)s.cnt, minpts, label, core, count, sizes);
     PCREG_HIP(hipGetLastError());
     return PCREG_OK;
 }

@@ -1,6 +1,6 @@
 // pcreg_amd/csrc/knn_walk.hpp -- the exact tile walk of the point search, its one definition: every walk kernel is
 // a prologue, walk_tiles with its lambdas, and an epilogue.  What the self-joins' prologues and lambdas have in common is here
-// as well, once: the finite test, what a row is staged as (walk_row, walk_row_finite), the visit rule (walk_visits), the
+// as well, once: the finite test, what a row is staged as (walk_row, walk_row_finite, walk_row_core), the visit rule (walk_visits), the
 // "knn_stats" header (walk_count_search), tile a's box (walk_tile_box) and this thread's row (walk_self_row).  The three
 // query-side kernels (knn_k.hip, knn_range.hip, knn_score.hip) share the header and still write their query prologue and visit
 // rule out: docs/BENCH_NOTES.md, 2026-10-20, has why.
@@ -47,6 +47,12 @@ __device__ __forceinline__ float4 walk_row_finite(const float* __restrict__ ms, 
         if (finite3(x, y, z)) return make_float4(x, y, z, __int_as_float(perm[r]));
     }
     return walk_no_row();
+}
+// ... and as DBSCAN's core walks stage it: a row with fewer than minpts neighbours is no row either.  cnt is by
+// SORTED row; a non-finite row's count is 0
+__device__ __forceinline__ float4 walk_row_core(const float* __restrict__ ms, const int32_t* __restrict__ perm, int M,
+                                                const int32_t* __restrict__ cnt, int minpts, int r) {
+    return r < M && cnt[r] >= minpts ? walk_row_finite(ms, perm, M, r) : walk_no_row();
 }
 
 // The visit rule: tile ct is scored unless DESIGN 4.1's rule (cull_rule.hpp) skips it for the box (lo xyz, hi xyz) and the

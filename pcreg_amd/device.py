@@ -353,6 +353,39 @@ class PreparedModel:
             check(lib().pcreg_dev_model_cluster_f32(self.handle, r2, _p(label), _p(n_clusters), _p(first), _p(sizes), _p(ws), ws.numel(), _stream()))
         return label, n_clusters, first, sizes
 
+    def dbscan(self, r2: float, minpts: int, out=None):
+        """DBSCAN of the model's own rows with r2 = epsilon^2 and minpts >= 1, on torch's current stream
+        (pcreg_dev_model_dbscan_f32; the contract is pcreg_model_dbscan_f32's): -> (label [M] int32, the 0-based cluster of every
+        row, -1 for noise; n_clusters [1] int32; core [M] uint8; count [M] int32, the rows within the radius of every row, itself
+        included; first [M] int32, first[c] the smallest core row of cluster c; sizes [M] int32, sizes[c] its rows, border rows
+        included; both zero at and past n_clusters).  Nothing synchronises.  The workspace is cached on the model and grown on
+        demand; calls that may overlap on two streams pass buffers of their own, out=(label, n_clusters, core, count, first,
+        sizes, ws) with ws of pcreg_dev_model_dbscan_workspace(M) bytes."""
+        r2 = float(r2)
+        if not r2 >= 0.0:
+            raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        if int(minpts) != minpts or int(minpts) < 1:
+            raise ValueError(f"minpts must be a whole number >= 1, got {minpts}")
+        minpts = int(minpts)
+        dev, M = self.tensor.device, self.M
+        need = max(int(lib().pcreg_dev_model_dbscan_workspace(M)), 256)
+        if out is not None:
+            label, n_clusters, core, count, first, sizes, ws = out
+        else:
+            label, count, first, sizes = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(4))
+            core = torch.empty(M, dtype=torch.uint8, device=dev)
+            n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = getattr(self, "_dbscan_ws_t", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._dbscan_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
+        if M == 0:                                     # (an empty tensor has no address to pass)
+            n_clusters.zero_()
+            return label, n_clusters, core, count, first, sizes
+        with torch.cuda.device(dev):
+            check(lib().pcreg_dev_model_dbscan_f32(self.handle, r2, minpts, _p(label), _p(n_clusters), _p(core), _p(count), _p(first), _p(sizes),
+                                                   _p(ws), ws.numel(), _stream()))
+        return label, n_clusters, core, count, first, sizes
+
     def normals(self, k: int, viewpoint=None, variation: bool = False, out=None):
         """The surface normal of every row of the model from its k nearest rows (3 <= k <= 32), on torch's current stream
         (pcreg_dev_model_normals_f32; the contract is pcreg_model_normals_f32's): -> normals, a [3, M] float32 tensor (row c the

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as _l
 from ._lib import RansacOpts, check, lib
-from .api import _fgr_opts, _match_opts, _transforms16, cluster_points, invertTF, score_summary
+from .api import _fgr_opts, _match_opts, _transforms16, cluster_points, dbscan_points, invertTF, score_summary
 from .device import DescriptorPipeline, PreparedModel, _p, _stream
 
 
@@ -502,21 +502,33 @@ def _good_trials(result: dict, thSucc: float, thInliers: float, thRatio: float, 
     return centres, tf, np.nonzero(mask)[0]                                                 # :239
 
 
+def _cluster_centres(loc, r: float, min_spheres):
+    """(cl_off, members) of the promising spheres' centres: cluster_points with the radius squared once in single, or, with
+    min_spheres an integer, dbscan_points(loc, r2, min_spheres), whose noise spheres are in no cluster."""
+    r32 = np.float32(r)
+    if min_spheres is None:
+        _, cl_off, members = cluster_points(loc, r32 * r32)                                 # :267
+    else:
+        _, _, cl_off, members = dbscan_points(loc, r32 * r32, min_spheres)
+    return cl_off, members
+
+
 def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, thRatio: float = 10, thPutative: float = 170,
-                       r: float | None = None, d_spheres: float = 5.0) -> list:
+                       r: float | None = None, d_spheres: float = 5.0, min_spheres: int | None = None) -> list:
     """completeExperimentFast.m:238-248 and :266-288, the link from a sweep's result to FinalStage.run: keep the trials whose
     statsSuccess / statsInliers / statsRatio (percent) / statsPutative reach the four thresholds, cluster their sphere centres
     with radius r (default 1.6 * d_spheres, :266) in ONE cluster_points call, and for every cluster return (locCur, transCur):
     locCur the mean of the cluster's centres in double, transCur the transform of the centre nearest to that mean (the first
     one on a tie, as MATLAB's min).  -> [(locCur [3], transCur [4, 4])] in the clusters' order, [] without a good sphere.  A trial
-    whose RANSAC failed has no transform and is never kept."""
+    whose RANSAC failed has no transform and is never kept.  min_spheres (an integer >= 1, default None: every sphere is in a
+    cluster) asks for DBSCAN's density rule: a centre is a core centre only with at least min_spheres centres, itself included,
+    within r, and a sphere that is neither core nor within r of a core centre is noise and belongs to no cluster."""
     centres, tf, good = _good_trials(result, thSucc, thInliers, thRatio, thPutative)
     if len(good) == 0:
         return []
     loc = centres[good]                                                                     # :247
     r = 1.6 * float(d_spheres) if r is None else float(r)                                   # :266
-    r32 = np.float32(r)
-    _, cl_off, members = cluster_points(loc, r32 * r32)                                     # :267
+    cl_off, members = _cluster_centres(loc, r, min_spheres)
     out = []
     for c in range(len(cl_off) - 1):
         rows = members[cl_off[c]:cl_off[c + 1]]
@@ -528,19 +540,21 @@ def promising_clusters(result: dict, thSucc: float = 0, thInliers: float = 28, t
 
 
 def largest_cluster(result: dict, thSucc: float = 0, thInliers: float = 28, thRatio: float = 10, thPutative: float = 170,
-                    r: float | None = None, d_spheres: float = 5.0):
+                    r: float | None = None, d_spheres: float = 5.0, min_spheres: int | None = None):
     """completeExperiment.m:379-389: the LARGEST cluster of promising spheres -- promising_clusters' thresholds and clustering (ONE
     cluster_points call, radius r, default 1.6 * d_spheres); `[~, idx] = max(cluster_size)` takes the first largest, which is the
     one with the smallest first row.  -> (trials, spheres): the members' trial ordinals (indices into result["trial"] / the stats)
     and sphere indices (into result["centres"]), int64, in ascending row order; two empty arrays without a good sphere.  A trial
-    whose RANSAC failed is never a member.  `spheres` is what SphereSweep.aggregate takes."""
+    whose RANSAC failed is never a member.  `spheres` is what SphereSweep.aggregate takes.  min_spheres: promising_clusters';
+    two empty arrays when every good sphere is noise."""
     centres, _, good = _good_trials(result, thSucc, thInliers, thRatio, thPutative)
     if len(good) == 0:
         return np.zeros(0, np.int64), np.zeros(0, np.int64)
     r = 1.6 * float(d_spheres) if r is None else float(r)
-    r32 = np.float32(r)
-    _, cl_off, members = cluster_points(centres[good], r32 * r32)
+    cl_off, members = _cluster_centres(centres[good], r, min_spheres)
     sizes = np.diff(np.asarray(cl_off, dtype=np.int64))
+    if len(sizes) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
     c = int(np.argmax(sizes))                                                               # the first maximum, as MATLAB's max
     rows = np.sort(np.asarray(members[cl_off[c]:cl_off[c + 1]], dtype=np.int64))
     trials = good[rows].astype(np.int64)
