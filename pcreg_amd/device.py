@@ -1161,12 +1161,13 @@ class DescriptorPipeline:
 
 
 def fgr_batched_dev(p1: torch.Tensor, p2: torch.Tensor, offsets: torch.Tensor, n_cap: int, opts: dict, T0: torch.Tensor = None,
-                    tuple_idx: torch.Tensor = None, kept: bool = False, ws: torch.Tensor = None):
+                    tuple_idx: torch.Tensor = None, kept: bool = False, ws: torch.Tensor = None, out=None):
     """Fast global registration on device buffers (pcreg_dev_fgr_batched), enqueued on torch's current stream, nothing
     read back.  p1 / p2: [3, ld] float64 (column-major n x 3 with leading dimension ld), offsets: [B + 1] int32 on the device,
     n_cap: the largest registration (trusted for the launch only), opts: api.fgr_batched's dict; T0 [B, 16] float64, tuple_idx
     [B, n_tuples, 3] int32 and ws (uint8, at least fgr_workspace_bytes) are optional.  -> (results [B, sizeof(pcreg_fgr_result)]
-    uint8, inlier_idx [ld] int32, kept [ld] uint8 or None): parse a row of results with fgr_results()."""
+    uint8, inlier_idx [ld] int32, kept [ld] uint8 or None): parse a row of results with fgr_results().  Calls that reuse their
+    buffers pass out=(results, inlier_idx, kept) (kept None when not wanted)."""
     from ._lib import FgrResult
     from .api import _fgr_opts
     o = _fgr_opts(opts)
@@ -1188,9 +1189,12 @@ def fgr_batched_dev(p1: torch.Tensor, p2: torch.Tensor, offsets: torch.Tensor, n
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
     elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
         raise ValueError(f"fast global registration: the workspace is a contiguous uint8 tensor of at least {need} bytes")
-    results = torch.zeros((B, C.sizeof(FgrResult)), dtype=torch.uint8, device=dev)
-    inliers = torch.zeros(max(ld, 1), dtype=torch.int32, device=dev)
-    kept_t = torch.zeros(max(ld, 1), dtype=torch.uint8, device=dev) if kept else None
+    if out is not None:
+        results, inliers, kept_t = out
+    else:
+        results = torch.zeros((B, C.sizeof(FgrResult)), dtype=torch.uint8, device=dev)
+        inliers = torch.zeros(max(ld, 1), dtype=torch.int32, device=dev)
+        kept_t = torch.zeros(max(ld, 1), dtype=torch.uint8, device=dev) if kept else None
     check(L.pcreg_dev_fgr_batched(_p(p1), _p(p2), ld, _p(offsets), B, int(n_cap), C.addressof(o), None if T0 is None else _p(T0),
                                   None if tuple_idx is None else _p(tuple_idx), _p(results), _p(inliers), None if kept_t is None else _p(kept_t),
                                   _p(ws), ws.numel(), _stream()))

@@ -62,13 +62,15 @@ def _knn(pm, surf, k, idx_base=0):
     return i.cpu().numpy(), d.cpu().numpy()
 
 
-def _top2(pm, surf, ws=None):
-    """ws: the caller's (workspace tensor, the workspace_bytes to pass) in place of one of the reported size"""
+def _top2(pm, surf, ws=None, alloc=None):
+    """ws: the caller's (workspace tensor, the workspace_bytes to pass) in place of one of the reported size; alloc(shape, dtype):
+    the caller's allocator of the two outputs"""
     from pcreg_amd._lib import check, lib
     Q = len(surf)
     q = _soa(surf)
-    idx = torch.empty((Q, 2), dtype=torch.int32, device=_dev())
-    dist = torch.empty((Q, 2), dtype=torch.float32, device=_dev())
+    alloc = alloc or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=_dev()))
+    idx = alloc((Q, 2), torch.int32)
+    dist = alloc((Q, 2), torch.float32)
     ws, ws_bytes = ws if ws is not None else (torch.empty(max(lib().pcreg_dev_model_search_workspace(Q, pm.M), 256), dtype=torch.uint8, device=_dev()), None)
     check(lib().pcreg_dev_model_search_f32(pm.handle, _p(q), Q, Q, C.c_int32(0), _p(idx), _p(dist), _p(ws),
                                            C.c_size_t(ws.numel() if ws_bytes is None else ws_bytes), _stream()))

@@ -25,9 +25,10 @@ def _stats(reset=False):
     return list(out)
 
 
-def _dev_ransac(p1, p2, coef, seed, sample_idx=None, extra_cap=0, ws=None):
+def _dev_ransac(p1, p2, coef, seed, sample_idx=None, extra_cap=0, ws=None, alloc=None):
     """pcreg_dev_ransac on [3, cap] device tensors with n = len(p1) <= cap on the device.  ws: the caller's (workspace tensor, the
-    workspace_bytes to pass) in place of one of the reported size."""
+    workspace_bytes to pass) in place of one of the reported size.  alloc(shape, dtype): the caller's allocator of the two outputs
+    in place of zeroed tensors."""
     import torch
     from pcreg_amd import _lib
     from pcreg_amd._lib import DevRansacResult, RansacOpts
@@ -41,7 +42,8 @@ def _dev_ransac(p1, p2, coef, seed, sample_idx=None, extra_cap=0, ws=None):
     o = RansacOpts(int(coef["minPtNum"]), int(coef["iterNum"]), float(coef["thDist"]), float(coef["thInlrRatio"]), int(bool(coef["REFINE"])), 0, int(seed))
     si = None if sample_idx is None else torch.from_numpy(np.ascontiguousarray(sample_idx, dtype=np.int32)).to(dev)
     ws, ws_bytes = ws if ws is not None else (torch.empty(L.pcreg_dev_ransac_workspace(cap, o.iterNum), dtype=torch.uint8, device=dev), None)
-    res = torch.zeros(C.sizeof(DevRansacResult), dtype=torch.uint8, device=dev); inl = torch.zeros(cap, dtype=torch.int32, device=dev)
+    alloc = alloc or (lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev))
+    res = alloc(C.sizeof(DevRansacResult), torch.uint8); inl = alloc(cap, torch.int32)
     _lib.check(L.pcreg_dev_ransac(_p(t1), _p(t2), _p(nd), cap, cap, C.byref(o), _p(si) if si is not None else None, _p(res), _p(inl),
                                   _p(ws), C.c_size_t(ws.numel() if ws_bytes is None else ws_bytes), _stream()))
     r = DevRansacResult.from_buffer_copy(res.cpu().numpy().tobytes())

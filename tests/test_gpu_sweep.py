@@ -292,16 +292,17 @@ def test_batched_sweep_counts_its_host_syncs(monkeypatch):
         np.testing.assert_array_equal(a, b)
 
 
-def _segments_direct(descS, descM, rows_list, par, metric=False, ws=None):
+def _segments_direct(descS, descM, rows_list, par, metric=False, ws=None, alloc=None):
     """pcreg_dev_get_matches_segmented on explicit row lists -> per-segment (pairs, metric).  ws: the caller's (workspace tensor,
-    the workspace_bytes to pass) in place of one of the reported size."""
+    the workspace_bytes to pass) in place of one of the reported size.  alloc(shape, dtype): the caller's allocator of the three
+    outputs (pairs, metric, n_pairs, in that order) in place of zeroed tensors and n_pairs = -1."""
     import ctypes as C
     import torch
     from pcreg_amd._lib import check, lib
     from pcreg_amd.api import _match_opts
     dev = torch.device("cuda", 0)
     L = lib()
-    p = lambda t: C.c_void_p(t.data_ptr())
+    p = lambda t: C.c_void_p(getattr(t, "empty_at", 0) or t.data_ptr())     # (empty_at: the address alloc gives an output of no elements)
     Q, D = descS.shape
     VM = descM.shape[0]
     S = len(rows_list)
@@ -313,9 +314,12 @@ def _segments_direct(descS, descM, rows_list, par, metric=False, ws=None):
     if rows.numel() == 0:
         rows = torch.zeros(1, dtype=torch.int32, device=dev)
     seg_off = torch.from_numpy(off).to(dev)
-    pairs = torch.zeros((S, Q, 2), dtype=torch.int32, device=dev)
-    met = torch.zeros((S, Q), dtype=torch.float64, device=dev)
-    n_pairs = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    if alloc is None:
+        pairs = torch.zeros((S, Q, 2), dtype=torch.int32, device=dev)
+        met = torch.zeros((S, Q), dtype=torch.float64, device=dev)
+        n_pairs = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    else:
+        pairs, met, n_pairs = alloc((S, Q, 2), torch.int32), alloc((S, Q), torch.float64), alloc(S, torch.int32)
     o = _match_opts(par)
     wsb = L.pcreg_dev_get_matches_segmented_workspace(Q, VM, D, S, tot, n_max)
     ws, ws_bytes = ws if ws is not None else (torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev), None)

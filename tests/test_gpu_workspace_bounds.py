@@ -5,6 +5,10 @@ the call succeeds, the guard still holds the pattern (a stray write past the rep
 test owns), and the outputs equal those of the same call on a separately allocated, generously sized workspace.  Once per entry
 workspace_bytes = need - 1 must be refused with PCREG_E_WORKSPACE.  The cases take every branch of the launchers that lays its
 buffers out differently (one layout function per workspace).
+
+The tight workspace holds 0xFF below `need` and the roomy one 0x00, so the comparison of the two also shows a launcher that reads
+a word before it writes it; every output is a tensor of sentinels between guards (tests/ws_state.py), so a slot that is never
+written does not read as a plausible 0 and a write in front of or behind an output shows.
 """
 import ctypes as C
 
@@ -12,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import ws_state
 from conftest import rigid_case
 
 pytestmark = pytest.mark.gpu
@@ -44,17 +49,27 @@ def _same(a, b, where=""):
         np.testing.assert_array_equal(a, b, err_msg=where)
 
 
+def _guarded(fn):
+    """fn(ws, new) -> outputs, new(shape, dtype) allocating every output as sentinels between guards that must come back untouched"""
+    def call(ws):
+        outs = ws_state.Outputs()
+        got = fn(ws, outs.new)
+        outs.check_guards()
+        return got
+    return call
+
+
 def _check_bounds(need, call, refuse=True):
     """call(ws) -> outputs (nested dicts / lists of arrays); ws = (workspace tensor, the workspace_bytes to pass)"""
     from pcreg_amd._lib import PCREG_E_WORKSPACE, PcregError
     need = int(need)
     assert need > 0
-    tight = torch.empty(need + GUARD, dtype=torch.uint8, device=_dev())
+    tight = torch.full((need + GUARD,), 0xFF, dtype=torch.uint8, device=_dev())
     tight[need:] = PATTERN
     out = call((tight, need))
     torch.cuda.synchronize()
     assert bool((tight[need:] == PATTERN).all()), "a write past the reported workspace size"
-    roomy = torch.empty(2 * need + GUARD, dtype=torch.uint8, device=_dev())
+    roomy = torch.zeros(2 * need + GUARD, dtype=torch.uint8, device=_dev())
     _same(out, call((roomy, roomy.numel())))
     if refuse:
         with pytest.raises(PcregError) as e:
@@ -90,38 +105,18 @@ def test_dev_ransac(shape, flags, refuse, debug_set):
     for key, value in flags.items():
         debug_set(key, value)
     out = []
-    _check_bounds(lib().pcreg_dev_ransac_workspace(n, iters), lambda ws: out.append(_dev_ransac(p1, p2, coef, 9, ws=ws)) or out[-1], refuse)
+    _check_bounds(lib().pcreg_dev_ransac_workspace(n, iters), _guarded(lambda ws, new: out.append(_dev_ransac(p1, p2, coef, 9, ws=ws, alloc=new)) or out[-1]), refuse)
     assert not out[0]["failed"] and out[0]["max_inliers"] > n // 2
 
 
 @pytest.mark.parametrize("cap,sizes", [(3000, [500, 1500, 2500, 3000]), (4000, [1000, 4000, 2500])],
                          ids=["fp32-launch-plus-fp64-launch", "tiled"])
 def test_dev_ransac_batched(cap, sizes):
-    from pcreg_amd._lib import DevRansacResult, RansacOpts, check, lib
-    L = lib()
+    from pcreg_amd._lib import lib
     B, iters = len(sizes), 500
-    cases = [rigid_case(n, 700 + n, noise=0.05, outlier_frac=0.3) for n in sizes]
-    off_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    ld = int(off_h[-1])
-    p1 = torch.from_numpy(np.ascontiguousarray(np.concatenate([c[0] for c in cases]).T)).to(_dev())
-    p2 = torch.from_numpy(np.ascontiguousarray(np.concatenate([c[1] for c in cases]).T)).to(_dev())
-    off = torch.from_numpy(off_h).to(_dev())
-    o = RansacOpts(3, iters, 0.1, 0.1, 1, 0, 11)
-    rs = C.sizeof(DevRansacResult)
-
-    def call(ws):
-        res = torch.zeros((B, rs), dtype=torch.uint8, device=_dev()); inl = torch.zeros(ld, dtype=torch.int32, device=_dev())
-        check(L.pcreg_dev_ransac_batched(_p(p1), _p(p2), ld, _p(off), B, cap, C.byref(o), _p(res), _p(inl), _p(ws[0]), C.c_size_t(ws[1]), _stream()))
-        raw, inl_h = res.cpu().numpy(), inl.cpu().numpy()
-        out = []
-        for b in range(B):
-            r = DevRansacResult.from_buffer_copy(raw[b].tobytes())
-            out.append(dict(T=np.array(r.T[:]), counts=[r.n_inliers, r.num_success, r.max_inliers, r.failed, r.n, r.winner],
-                            inl=inl_h[off_h[b]:off_h[b] + r.n_inliers]))
-        return out
-
+    call = _guarded(lambda ws, new: ws_state.ransac_batched_call(sizes, cap, iters, 11, ws[0], ws[1], new))
     first = []
-    _check_bounds(L.pcreg_dev_ransac_batched_workspace(cap, iters, B), lambda ws: first.append(call(ws)) or first[-1])
+    _check_bounds(lib().pcreg_dev_ransac_batched_workspace(cap, iters, B), lambda ws: first.append(call(ws)) or first[-1])
     assert all(r["counts"][3] == 0 and r["counts"][2] > n // 2 for r, n in zip(first[0], sizes))
 
 
@@ -143,18 +138,8 @@ def test_dev_get_matches(par_over):
     L = _lib.lib()
     Q, M, D = 300, 900, 64
     dS, dM = _count_descriptors(Q, M, D, 2)
-    tS = torch.from_numpy(np.ascontiguousarray(dS.T)).to(_dev())          # [D, Q]: feature-major
-    tM = torch.from_numpy(np.ascontiguousarray(dM.T)).to(_dev())
     o = _match_opts(dict(PAR, **par_over))
-
-    def call(ws):
-        pairs = torch.zeros((Q, 2), dtype=torch.int32, device=_dev()); metric = torch.zeros(Q, dtype=torch.float64, device=_dev())
-        n = torch.zeros(1, dtype=torch.int32, device=_dev())
-        _lib.check(L.pcreg_dev_get_matches(_p(tS), Q, Q, _p(tM), M, M, D, _lib.LAYOUT_FEATURE_MAJOR, C.byref(o), _p(pairs), _p(metric), _p(n),
-                                           _p(ws[0]), C.c_size_t(ws[1]), _stream()))
-        k = int(n.item())
-        return dict(k=k, pairs=pairs[:k].cpu().numpy(), metric=metric[:k].cpu().numpy())
-
+    call = _guarded(lambda ws, new: ws_state.get_matches_call(dS, dM, dict(PAR, **par_over), ws[0], ws[1], new))
     first = []
     _check_bounds(L.pcreg_dev_get_matches_workspace(Q, M, D), lambda ws: first.append(call(ws)) or first[-1], refuse=not par_over)
     if o.metric == _lib.METRIC_SAD:
@@ -170,28 +155,17 @@ def test_dev_get_matches_segmented():
     rows_list = [np.sort(rng.choice(VM, n, replace=False)) for n in (1800, 700, 1, 2500)] + [np.zeros(0, np.int64), np.arange(VM)]
     S, tot, n_max = len(rows_list), sum(len(r) for r in rows_list), VM
     need = lib().pcreg_dev_get_matches_segmented_workspace(Q, VM, D, S, tot, n_max)
-    _check_bounds(need, lambda ws: _segments_direct(dS, dM, rows_list, PAR, metric=True, ws=ws))
+    _check_bounds(need, _guarded(lambda ws, new: _segments_direct(dS, dM, rows_list, PAR, metric=True, ws=ws, alloc=new)))
 
 
 # ---- pcreg_dev_spatial_histogram_descriptors ----------------------------------------------------------------------------------
 def test_dev_descriptors():
-    from pcreg_amd._lib import check, lib
-    from pcreg_amd.api import _desc_opts
-    from pcreg_amd.device import soa
+    from pcreg_amd._lib import lib
     from test_gpu_descriptors import OPT, keypoints, strips
     L = lib()
-    pts = soa(torch.from_numpy(strips(40000, 0)).to(_dev())); kp = soa(torch.from_numpy(keypoints(300, 1)).to(_dev()))
-    P, S = pts.shape[1], kp.shape[1]
-    o = _desc_opts(OPT)
-
-    def call(ws):
-        feat = torch.zeros((S, 3), dtype=torch.float64, device=_dev()); desc = torch.zeros((S, 980), dtype=torch.float64, device=_dev())
-        counters = torch.zeros(2, dtype=torch.int32, device=_dev())
-        check(L.pcreg_dev_spatial_histogram_descriptors(_p(pts), P, pts.stride(0), _p(kp), S, kp.stride(0), C.byref(o), _p(feat), _p(desc),
-                                                        _p(counters), _p(ws[0]), C.c_size_t(ws[1]), _stream()))
-        V = int(counters[0].item())
-        return dict(counters=counters.cpu().numpy(), feat=feat[:V].cpu().numpy(), desc=desc[:V].cpu().numpy())
-
+    pts_h, kp_h = strips(40000, 0), keypoints(300, 1)
+    P, S = len(pts_h), len(kp_h)
+    call = _guarded(lambda ws, new: ws_state.descriptors_call(pts_h, kp_h, OPT, ws[0], ws[1], new))
     first = []
     _check_bounds(L.pcreg_dev_spatial_histogram_descriptors_workspace(P, S), lambda ws: first.append(call(ws)) or first[-1])
     assert first[0]["counters"][0] > 50 and first[0]["counters"][1] == 0
@@ -212,15 +186,15 @@ def test_dev_model_search_and_knn():
     M, Q, k = 50000, 3000, 8                                                # M above the seeding grid's minimum
     model, surf = _points(M, Q, 3)
     pm, _keep = _prepared(model)
-    _check_bounds(L.pcreg_dev_model_search_workspace(Q, M), lambda ws: list(_top2(pm, surf, ws=ws)))
+    _check_bounds(L.pcreg_dev_model_search_workspace(Q, M), _guarded(lambda ws, new: list(_top2(pm, surf, ws=ws, alloc=new))))
     q = _soa(surf)
 
-    def knn(ws):
-        idx = torch.zeros((Q, k), dtype=torch.int32, device=_dev()); dist = torch.zeros((Q, k), dtype=torch.float32, device=_dev())
+    def knn(ws, new):
+        idx = new((Q, k), torch.int32); dist = new((Q, k), torch.float32)
         check(L.pcreg_dev_model_knn_f32(pm.handle, _p(q), Q, Q, k, C.c_int32(0), _p(idx), _p(dist), _p(ws[0]), C.c_size_t(ws[1]), _stream()))
         return [idx.cpu().numpy(), dist.cpu().numpy()]
 
-    _check_bounds(L.pcreg_dev_model_knn_workspace(Q, M, k), knn)
+    _check_bounds(L.pcreg_dev_model_knn_workspace(Q, M, k), _guarded(knn))
 
 
 @pytest.mark.parametrize("exact", [0, 1], ids=["certified-f16", "knn_exact"])
@@ -234,31 +208,23 @@ def test_dev_knn2_points(exact, debug_set):
     if exact:
         debug_set("knn_exact", 1)
 
-    def call(ws):
-        idx = torch.zeros((Q, 2), dtype=torch.int32, device=_dev()); dist = torch.zeros((Q, 2), dtype=torch.float32, device=_dev())
+    def call(ws, new):
+        idx = new((Q, 2), torch.int32); dist = new((Q, 2), torch.float32)
         check(L.pcreg_dev_knn2_points_f32(_p(q), Q, Q, _p(m), M, M, C.c_int32(0), _p(idx), _p(dist), _p(ws[0]), C.c_size_t(ws[1]), _stream()))
         return [idx.cpu().numpy(), dist.cpu().numpy()]
 
     first = []
-    _check_bounds(L.pcreg_dev_knn2_points_f32_workspace(Q, M), lambda ws: first.append(call(ws)) or first[-1], refuse=not exact)
+    _check_bounds(L.pcreg_dev_knn2_points_f32_workspace(Q, M), lambda ws: first.append(_guarded(call)(ws)) or first[-1], refuse=not exact)
     assert (first[0][0][:, 0] >= 0).all() and (np.diff(first[0][1], axis=1) >= 0).all()
 
 
 # ---- pcreg_dev_sphere_select --------------------------------------------------------------------------------------------------
 def test_dev_sphere_select():
-    from pcreg_amd._lib import check, lib
+    from pcreg_amd._lib import lib
     L = lib()
     V = 6000
-    rng = np.random.default_rng(5)
-    feat = torch.from_numpy(rng.uniform([0, 0, 0], [40, 30, 20], (V, 3))).to(_dev())
-    cc = (C.c_double * 3)(22.0, 14.0, 9.0)
-
-    def call(ws):
-        idx = torch.zeros(V, dtype=torch.int32, device=_dev()); n = torch.zeros(1, dtype=torch.int32, device=_dev())
-        check(L.pcreg_dev_sphere_select(_p(feat), V, cc, C.c_double(8.0), _p(idx), _p(n), _p(ws[0]), C.c_size_t(ws[1]), _stream()))
-        k = int(n.item())
-        return dict(k=k, idx=idx[:k].cpu().numpy())
-
+    feat = np.random.default_rng(5).uniform([0, 0, 0], [40, 30, 20], (V, 3))
+    call = _guarded(lambda ws, new: ws_state.sphere_select_call(feat, (22.0, 14.0, 9.0), 8.0, ws[0], ws[1], new))
     first = []
     _check_bounds(L.pcreg_dev_sphere_select_workspace(V), lambda ws: first.append(call(ws)) or first[-1])
     assert 100 < first[0]["k"] < V
