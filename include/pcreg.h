@@ -336,7 +336,7 @@ int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, co
 /* Refit B candidate transforms by ONE LINEARISED POINT-TO-PLANE STEP on their close dense pairs (`steps` of them in this entry):
  * what pcreg_model_refit_f32 does with estimateTransform, done with the planes through the model rows instead, so that a pair may
  * be the wrong partner ALONG the surface as long as it is nearly the right one ACROSS it.  A step, not an ICP policy: no
- * convergence test, no weighting, no robust kernel.  THE CONTRACT of every tier (device, host, MEX, Python):
+ * convergence test, no weighting, no robust kernel (pcreg_model_refit_plane_trimmed_f32 keeps each candidate's closest pairs).  THE CONTRACT of every tier (device, host, MEX, Python):
  * inputs -- those of pcreg_model_refit_f32 (a prepared model, Q fp32 points column-major with ldq, B transforms of 16 doubles used
  * as quickTF.m uses them, a squared radius r2 >= 0, +inf allowed), and NORMALS: M x 3 fp32 column-major with leading dimension
  * ldn >= M, indexed by ORIGINAL row -- exactly what pcreg_model_normals_f32 and pcreg_dev_model_normals_f32 write.  A normal is
@@ -396,7 +396,8 @@ int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int l
  * pcreg_model_refit_f32 (point to point) and pcreg_model_refit_plane_f32 (point to plane): every pair is weighted by the inverse of
  * the sum of two regularised covariances, one per side, each flat along its own surface normal.  A pair so pulls fully ACROSS
  * either surface and about half as hard ALONG them, so the matrix stays definite where the point-to-plane step has nothing to
- * hold on to (a flat model).  A step, not an ICP policy: no convergence test, no robust kernel, no claim of pcregistericp's bits.
+ * hold on to (a flat model).  A step, not an ICP policy: no convergence test, no robust kernel (pcreg_model_refit_gicp_trimmed_f32 keeps
+ * each candidate's closest pairs), no claim of pcregistericp's bits.
  * THE CONTRACT of every tier (device, host, MEX, Python):
  * inputs -- those of pcreg_model_refit_plane_f32 (a prepared model, Q fp32 points column-major with ldq, B transforms of 16 doubles
  * used as quickTF.m uses them, r2 >= 0 with +inf allowed, the model's NORMALS M x 3 fp32 column-major by ORIGINAL row with
@@ -447,6 +448,47 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
                                const float* qnormals /* host Q x 3, or NULL */, int ldnq, int k, double epsilon,
                                double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2,
                                int32_t* empty);
+/* TRIMMED scoring and refits: the four entries above with one more control, the one pcregistericp calls InlierRatio --
+ * of each transform's candidate pairs only the closest fraction is kept.  It is the robust choice of pairs the steps above say
+ * they lack: on partly overlapping clouds a radius large enough to reach from the start pose also admits wrong partners, and
+ * the far share of the pairs is where they sit.  No claim of pcregistericp's bits.
+ * THE CONTRACT of every tier (device, host, MEX, Python):
+ * inputs -- those of the untrimmed entry, and keep_ratio, a double in (0, 1].
+ * THE CANDIDATE PAIRS of transform b are pcreg_model_score_f32's, unchanged: every query with a model row within r2, its nearest
+ * such row and the fp32 d of that pair.  n_within[b] is their number, and
+ *   keep = n_within == 0 ? 0 : min(n_within, max(1, (int)floor(keep_ratio * (double)n_within + 0.5)))
+ * in double, the product rounded first and then the sum (no contraction).
+ * THE KEPT PAIRS are the `keep` first candidate pairs in the order (d ascending, query index i ascending).  d is never negative
+ * and never NaN for a pair, so its bit pattern orders as an unsigned integer (+inf, which r2 = +inf admits, comes last).
+ * Equivalently: every pair with d < d2_cut[b] is kept, and among the pairs with d == d2_cut[b] the lowest i until `keep` is
+ * reached.  d2_cut[b] is the largest kept d, or +inf when keep is 0.  (What a sort and a truncation give.)
+ * EVERYTHING ELSE is the untrimmed entry's contract applied to the kept pairs, in ascending i: n_close and sum_d2 count and sum the
+ * kept pairs in the same fixed order and tree; T_step, T_out and empty follow the same rules (fewer than three kept pairs, or the
+ * all-zero T, give empty); n_plane / n_pairs and sum_res2 are taken among the kept pairs.  For scoring, idx / dist hold -1 / +inf
+ * at trimmed slots, as at misses.  With steps > 1 every step trims anew, and all outputs describe the transform that went into
+ * the last step.
+ * keep_ratio = 1.0 keeps everything: every output then has the untrimmed entry's bits, and n_within == n_close.
+ * r2 = +inf is allowed: InlierRatio with no distance at all.
+ * Everything is a function of the inputs alone: the selection is an exact radix select on integer counts, no floating-point
+ * atomic anywhere, and batching, culling, walk order and workgroup order change nothing.
+ * n_within and d2_cut are [B]; either may be NULL.  Q = 0 or a model without rows: n_within = 0, d2_cut = +inf.
+ * PCREG_E_ARG: the untrimmed entry's cases, and keep_ratio NaN, <= 0 or > 1. */
+int pcreg_model_score_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                                  double keep_ratio, int32_t* n_close, double* sum_d2, int32_t* idx /* [B][Q] or NULL */,
+                                  float* dist /* [B][Q] or NULL */, int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
+int pcreg_model_refit_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B, float r2,
+                                  double keep_ratio, int steps, double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2,
+                                  int32_t* empty, int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
+int pcreg_model_refit_plane_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B,
+                                        float r2, double keep_ratio, int steps, const float* normals /* host M x 3, or NULL */, int ldn,
+                                        int k, double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* n_plane,
+                                        double* sum_res2, int32_t* empty, int32_t* n_within /* [B] or NULL */,
+                                        float* d2_cut /* [B] or NULL */);
+int pcreg_model_refit_gicp_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T /* host [B][16] */, int B,
+                                       float r2, double keep_ratio, int steps, const float* normals /* host M x 3, or NULL */, int ldn,
+                                       const float* qnormals /* host Q x 3, or NULL */, int ldnq, int k, double epsilon,
+                                       double* T_out /* [B][16] */, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2,
+                                       int32_t* empty, int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
 /* The COHERENT-POINT-DRIFT step of a refinement (rigid CPD; what MATLAB users reach for as pcregistercpd with Transform = 'Rigid'),
  * beside the three ICP steps and pcreg_ndt_refit_f32: every moved point is paired SOFTLY with EVERY live model row by a Gaussian
  * of their distance against a uniform outlier term, and the Gaussian's variance is annealed by its own closed form.  No radius, no
@@ -1374,6 +1416,38 @@ int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q,
                                    int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_pairs /* [B] */,
                                    double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
                                    void* workspace, size_t workspace_bytes, void* stream);
+/* ONE step of the trimmed contract (pcreg_model_score_trimmed_f32) on the device: each entry takes its untrimmed
+ * twin's arguments and rules with keep_ratio after r2 and n_within / d2_cut [B] (device pointers, either may be NULL) at the end.
+ * Between the walk and the sums a trim pass selects each transform's keep-th smallest d by four 8-bit histogram passes and
+ * turns the other pairs into misses; no host read happens.  THE WORKSPACE IS THE UNTRIMMED TWIN'S, pcreg_dev_model_X_workspace(Q, B,
+ * M) bytes and not one more: the pass keeps its counters in blocks of that layout that are dead between the walk and the sums.
+ * PCREG_E_ARG also for keep_ratio NaN, <= 0 or > 1. */
+int pcreg_dev_model_score_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                      const double* T_dev /* [B][16] on the device */, int B, float r2, double keep_ratio,
+                                      int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* idx /* [B][Q] or NULL */,
+                                      float* dist /* [B][Q] or NULL */, void* workspace, size_t workspace_bytes, void* stream,
+                                      int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
+int pcreg_dev_model_refit_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                      const double* T_dev /* [B][16] on the device */, int B, float r2, double keep_ratio,
+                                      double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */, int32_t* n_close /* [B] */,
+                                      double* sum_d2 /* [B] */, int32_t* empty /* [B] */, void* workspace, size_t workspace_bytes,
+                                      void* stream, int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
+int pcreg_dev_model_refit_plane_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                            const double* T_dev /* [B][16] on the device */, int B, float r2, double keep_ratio,
+                                            const float* normals_dev /* [3][ldn] */, int ldn, double* T_out /* [B][16] */,
+                                            double* T_step /* [B][16] or NULL */, int32_t* n_close /* [B] */, double* sum_d2 /* [B] */,
+                                            int32_t* n_plane /* [B] */, double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
+                                            void* workspace, size_t workspace_bytes, void* stream,
+                                            int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
+int pcreg_dev_model_refit_gicp_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq,
+                                           const double* T_dev /* [B][16] on the device */, int B, float r2, double keep_ratio,
+                                           const float* normals_dev /* [3][ldn] */, int ldn,
+                                           const float* qnormals_dev /* [3][ldnq] */, int ldnq, double epsilon,
+                                           double* T_out /* [B][16] */, double* T_step /* [B][16] or NULL */,
+                                           int32_t* n_close /* [B] */, double* sum_d2 /* [B] */, int32_t* n_pairs /* [B] */,
+                                           double* sum_res2 /* [B] */, int32_t* empty /* [B] */,
+                                           void* workspace, size_t workspace_bytes, void* stream,
+                                           int32_t* n_within /* [B] or NULL */, float* d2_cut /* [B] or NULL */);
 /* ONE step of pcreg_model_refit_cpd_f32's contract on the device: everything is a device pointer, nothing
  * synchronises, T_step may be NULL, T_out may not alias T_dev (sigma2_out may alias sigma2_in).  The shift dmin comes from
  * pcreg_dev_model_score_f32's chain at r2 = +inf inside the call.  The workspace, with nb = max(1, min(B, floor(131072 / max(Q, 1))))

@@ -39,6 +39,15 @@
 //                                          plane-to-plane (generalized ICP) step in its place; either set of normals may be [] to
 //                                          compute it once with k (3 .. 32); epsilon in (0, 1] is the covariance along a normal; a
 //                                          zero page where there is no fit (matlab/refitGicpModel.m)
+//   'modelScoreTrimmed', 'modelRefitTrimmed', 'modelRefitPlaneTrimmed', 'modelRefitGicpTrimmed': the four commands above with keepRatio
+//                                          (a double scalar in (0, 1]) after maxDist and two more outputs at the end, nWithin (B x 1
+//                                          int32) and d2Cut (B x 1 single): of each transform's rows within maxDist only the closest
+//                                          keepRatio share is kept (pcregistericp's InlierRatio; ties to the lower row of pts),
+//                                          every other output is about the kept pairs, nWithin counts the pairs before the trim
+//                                          and d2Cut is the largest kept squared distance, Inf where nothing is kept; 'modelScoreTrimmed'
+//                                          has 0 / Inf at trimmed slots of idx / D2 (matlab/scoreTransformsTrimmedModel.m, refitTransformsTrimmedModel.m,
+//                                          refitPlaneTrimmedModel.m, refitGicpTrimmedModel.m: the untrimmed wrappers' arguments and a trailing
+//                                          'InlierRatio', rho)
 //   'modelRefitCpd', handle, pts (single Q x 3), T (double 4 x 4 x B), sigma2 (double scalar | B x 1), outlier, steps -> Tout (double
 //                                          4 x 4 x B), sigma2Out, Np, sumRes2, sumD2 (B x 1 double each), nLive (B x 1 int32): rigid
 //                                          coherent-point-drift steps, every moved point softly against EVERY model row (B * Q * M
@@ -218,6 +227,18 @@ static bool field_is(const mxArray* s, const char* name, const char* value) {
 // r of the radius commands: a real double or single scalar >= 0 (NaN refused)
 static bool radius_ok(const mxArray* a) {
     return (mxIsDouble(a) || mxIsSingle(a)) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 0.0;
+}
+// keepRatio of the trimmed commands: a real double scalar in (0, 1] (NaN refused)
+static bool ratio_ok(const mxArray* a) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) > 0.0 && mxGetScalar(a) <= 1.0;
+}
+// steps of the refit commands: a whole number 1 .. 1e6 as a double scalar
+static bool steps_ok(const mxArray* a) {
+    return mxIsDouble(a) && mxGetM(a) * mxGetN(a) == 1 && mxGetScalar(a) >= 1.0 && mxGetScalar(a) <= 1e6 && mxGetScalar(a) == (double)(int)mxGetScalar(a);
+}
+// pts (single Q x 3) and T (double 4 x 4 x B, or empty) of the scoring and refit commands
+static bool pts_t_ok(const mxArray* pts, const mxArray* T) {
+    return mxIsSingle(pts) && mxGetN(pts) == 3 && mxIsDouble(T) && (mxGetM(T) == 4 || mxIsEmpty(T)) && mxGetN(T) % 4 == 0;
 }
 // the three outputs of 'modelCluster' / 'clusterPoints': label (M x 1 int32, 1-based), clOff (C + 1 int32), members (M x 1 int32,
 // 1-based); single(r) is squared once, in single.  Nothing is left allocated on an error.
@@ -1288,6 +1309,143 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                     if (nlhs > 3) plhs[3] = op; else mxDestroyArray(op);
                     if (nlhs > 4) plhs[4] = og; else mxDestroyArray(og);
                 } else { mxDestroyArray(ot); mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(op); mxDestroyArray(og); }
+            }
+        }
+    } else if (!strcmp(cmd, "modelScoreTrimmed")) {           // [nClose, sumD2, idx, D2, nWithin, d2Cut] = pcreg_mex('modelScoreTrimmed', h, single(pts), T, maxDist, keepRatio)
+        if (nrhs != 6 || !mxIsUint64(prhs[1]) || !pts_t_ok(prhs[2], prhs[3]) || !radius_ok(prhs[4]) || !ratio_ok(prhs[5]))
+            usage = "modelScoreTrimmed: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), keepRatio (a double scalar in (0, 1])";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool rows = nlhs > 2;
+            mxArray* on = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* os = mxCreateDoubleMatrix((size_t)B, 1, mxREAL);
+            mxArray* oi = rows ? mxCreateNumericMatrix((size_t)Q, (size_t)B, mxINT32_CLASS, mxREAL) : nullptr;      // [B][Q] row-major = Q x B
+            mxArray* od = rows ? mxCreateNumericMatrix((size_t)Q, (size_t)B, mxSINGLE_CLASS, mxREAL) : nullptr;
+            mxArray* ow = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);
+            mxArray* oc = mxCreateNumericMatrix((size_t)B, 1, mxSINGLE_CLASS, mxREAL);
+            int32_t* di = rows ? (int32_t*)mxGetData(oi) : nullptr;
+            if (B > 0) rc = pcreg_model_score_trimmed_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2, mxGetScalar(prhs[5]),
+                                                          (int32_t*)mxGetData(on), mxGetPr(os), di, rows ? (float*)mxGetData(od) : nullptr,
+                                                          (int32_t*)mxGetData(ow), (float*)mxGetData(oc));
+            if (rc == PCREG_OK) {
+                for (size_t k = 0; rows && k < (size_t)Q * (size_t)B; ++k) di[k] += 1;
+                plhs[0] = on; plhs[1] = os;
+                if (rows) { plhs[2] = oi; plhs[3] = od; }
+                if (nlhs > 4) plhs[4] = ow; else mxDestroyArray(ow);
+                if (nlhs > 5) plhs[5] = oc; else mxDestroyArray(oc);
+            } else { mxDestroyArray(on); mxDestroyArray(os); mxDestroyArray(oi); mxDestroyArray(od); mxDestroyArray(ow); mxDestroyArray(oc); }
+        }
+    } else if (!strcmp(cmd, "modelRefitTrimmed")) {           // [Tout, nClose, sumD2, nWithin, d2Cut] = pcreg_mex('modelRefitTrimmed', h, single(pts), T, maxDist, keepRatio, steps)
+        if (nrhs != 7 || !mxIsUint64(prhs[1]) || !pts_t_ok(prhs[2], prhs[3]) || !radius_ok(prhs[4]) || !ratio_ok(prhs[5]) || !steps_ok(prhs[6]))
+            usage = "modelRefitTrimmed: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), keepRatio (a double scalar in "
+                    "(0, 1]), steps (a whole number >= 1)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const mwSize dims[3] = {4, 4, (mwSize)B};
+            mxArray* o[5] = {mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                             mxCreateDoubleMatrix((size_t)B, 1, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                             mxCreateNumericMatrix((size_t)B, 1, mxSINGLE_CLASS, mxREAL)};
+            mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+            if (B > 0) rc = pcreg_model_refit_trimmed_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2, mxGetScalar(prhs[5]),
+                                                          (int)mxGetScalar(prhs[6]), mxGetPr(o[0]), (int32_t*)mxGetData(o[1]), mxGetPr(o[2]),
+                                                          (int32_t*)mxGetData(oe), (int32_t*)mxGetData(o[3]), (float*)mxGetData(o[4]));
+            mxDestroyArray(oe);
+            if (rc == PCREG_OK) {
+                plhs[0] = o[0];
+                if (nlhs > 1) plhs[1] = o[1]; else mxDestroyArray(o[1]);
+                if (nlhs > 2) plhs[2] = o[2]; else mxDestroyArray(o[2]);
+                if (nlhs > 3) plhs[3] = o[3]; else mxDestroyArray(o[3]);
+                if (nlhs > 4) plhs[4] = o[4]; else mxDestroyArray(o[4]);
+            } else {
+                for (mxArray* a : o) mxDestroyArray(a);
+            }
+        }
+    } else if (!strcmp(cmd, "modelRefitPlaneTrimmed")) {      // [Tout, nClose, sumD2, nPlane, sumRes2, nWithin, d2Cut] = pcreg_mex('modelRefitPlaneTrimmed', h, single(pts), T, maxDist, keepRatio, steps, normals, k)
+        if (nrhs != 9 || !mxIsUint64(prhs[1]) || !pts_t_ok(prhs[2], prhs[3]) || !radius_ok(prhs[4]) || !ratio_ok(prhs[5]) || !steps_ok(prhs[6]) ||
+            (!mxIsEmpty(prhs[7]) && (!mxIsSingle(prhs[7]) || mxGetN(prhs[7]) != 3)) || !normals_k_ok(prhs[8]))
+            usage = "modelRefitPlaneTrimmed: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), keepRatio (a double scalar "
+                    "in (0, 1]), steps (a whole number >= 1), normals (single M x 3, or [] to compute them), k (a whole number 3 .. 32)";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool given = !mxIsEmpty(prhs[7]);
+            int M = 0;
+            rc = pcreg_model_size(h, &M);
+            if (rc == PCREG_OK && given && (int)mxGetM(prhs[7]) != M) usage = "modelRefitPlaneTrimmed: normals must have one row per model row";
+            else if (rc == PCREG_OK) {
+                const mwSize dims[3] = {4, 4, (mwSize)B};
+                mxArray* o[7] = {mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateDoubleMatrix((size_t)B, 1, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateDoubleMatrix((size_t)B, 1, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateNumericMatrix((size_t)B, 1, mxSINGLE_CLASS, mxREAL)};
+                mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+                if (B > 0) rc = pcreg_model_refit_plane_trimmed_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2,
+                                                                    mxGetScalar(prhs[5]), (int)mxGetScalar(prhs[6]),
+                                                                    given ? (const float*)mxGetData(prhs[7]) : nullptr, M > 0 ? M : 1, (int)mxGetScalar(prhs[8]),
+                                                                    mxGetPr(o[0]), (int32_t*)mxGetData(o[1]), mxGetPr(o[2]), (int32_t*)mxGetData(o[3]),
+                                                                    mxGetPr(o[4]), (int32_t*)mxGetData(oe), (int32_t*)mxGetData(o[5]), (float*)mxGetData(o[6]));
+                mxDestroyArray(oe);
+                if (rc == PCREG_OK) {
+                    plhs[0] = o[0];
+                    if (nlhs > 1) plhs[1] = o[1]; else mxDestroyArray(o[1]);
+                    if (nlhs > 2) plhs[2] = o[2]; else mxDestroyArray(o[2]);
+                    if (nlhs > 3) plhs[3] = o[3]; else mxDestroyArray(o[3]);
+                    if (nlhs > 4) plhs[4] = o[4]; else mxDestroyArray(o[4]);
+                    if (nlhs > 5) plhs[5] = o[5]; else mxDestroyArray(o[5]);
+                    if (nlhs > 6) plhs[6] = o[6]; else mxDestroyArray(o[6]);
+                } else {
+                    for (mxArray* a : o) mxDestroyArray(a);
+                }
+            }
+        }
+    } else if (!strcmp(cmd, "modelRefitGicpTrimmed")) {       // [Tout, nClose, sumD2, nPairs, sumRes2, nWithin, d2Cut] = pcreg_mex('modelRefitGicpTrimmed', h, single(pts), T, maxDist, keepRatio, steps, normals, ptsNormals, k, epsilon)
+        if (nrhs != 11 || !mxIsUint64(prhs[1]) || !pts_t_ok(prhs[2], prhs[3]) || !radius_ok(prhs[4]) || !ratio_ok(prhs[5]) || !steps_ok(prhs[6]) ||
+            (!mxIsEmpty(prhs[7]) && (!mxIsSingle(prhs[7]) || mxGetN(prhs[7]) != 3)) || (!mxIsEmpty(prhs[8]) && (!mxIsSingle(prhs[8]) || mxGetN(prhs[8]) != 3)) ||
+            !normals_k_ok(prhs[9]) || !mxIsDouble(prhs[10]) || mxGetM(prhs[10]) * mxGetN(prhs[10]) != 1 || !(mxGetScalar(prhs[10]) > 0.0) ||
+            !(mxGetScalar(prhs[10]) <= 1.0))
+            usage = "modelRefitGicpTrimmed: handle (uint64), pts (single Q x 3), T (double 4 x 4 x B), maxDist (a real scalar >= 0), keepRatio (a double scalar "
+                    "in (0, 1]), steps (a whole number >= 1), normals (single M x 3, or [] to compute them), ptsNormals (single Q x 3, or [] to compute them), "
+                    "k (a whole number 3 .. 32), epsilon (a double scalar in (0, 1])";
+        else {
+            pcreg_model* h = (pcreg_model*)(uintptr_t)*(const uint64_t*)mxGetData(prhs[1]);
+            const int Q = (int)mxGetM(prhs[2]), B = mxIsEmpty(prhs[3]) ? 0 : (int)(mxGetN(prhs[3]) / 4);
+            const float r = (float)mxGetScalar(prhs[4]), r2 = r * r;             // single(maxDist) squared once, in single
+            const bool given = !mxIsEmpty(prhs[7]), given_q = !mxIsEmpty(prhs[8]);
+            int M = 0;
+            rc = pcreg_model_size(h, &M);
+            if (rc == PCREG_OK && given && (int)mxGetM(prhs[7]) != M) usage = "modelRefitGicpTrimmed: normals must have one row per model row";
+            else if (rc == PCREG_OK && given_q && (int)mxGetM(prhs[8]) != Q) usage = "modelRefitGicpTrimmed: ptsNormals must have one row per row of pts";
+            else if (rc == PCREG_OK) {
+                const mwSize dims[3] = {4, 4, (mwSize)B};
+                mxArray* o[7] = {mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateDoubleMatrix((size_t)B, 1, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateDoubleMatrix((size_t)B, 1, mxREAL), mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL),
+                                 mxCreateNumericMatrix((size_t)B, 1, mxSINGLE_CLASS, mxREAL)};
+                mxArray* oe = mxCreateNumericMatrix((size_t)B, 1, mxINT32_CLASS, mxREAL);   // (an empty fit is a zero page of Tout already)
+                if (B > 0) rc = pcreg_model_refit_gicp_trimmed_f32(h, (const float*)mxGetData(prhs[2]), Q, Q > 0 ? Q : 1, mxGetPr(prhs[3]), B, r2,
+                                                                   mxGetScalar(prhs[5]), (int)mxGetScalar(prhs[6]),
+                                                                   given ? (const float*)mxGetData(prhs[7]) : nullptr, M > 0 ? M : 1,
+                                                                   given_q ? (const float*)mxGetData(prhs[8]) : nullptr, Q > 0 ? Q : 1,
+                                                                   (int)mxGetScalar(prhs[9]), mxGetScalar(prhs[10]), mxGetPr(o[0]), (int32_t*)mxGetData(o[1]),
+                                                                   mxGetPr(o[2]), (int32_t*)mxGetData(o[3]), mxGetPr(o[4]), (int32_t*)mxGetData(oe),
+                                                                   (int32_t*)mxGetData(o[5]), (float*)mxGetData(o[6]));
+                mxDestroyArray(oe);
+                if (rc == PCREG_OK) {
+                    plhs[0] = o[0];
+                    if (nlhs > 1) plhs[1] = o[1]; else mxDestroyArray(o[1]);
+                    if (nlhs > 2) plhs[2] = o[2]; else mxDestroyArray(o[2]);
+                    if (nlhs > 3) plhs[3] = o[3]; else mxDestroyArray(o[3]);
+                    if (nlhs > 4) plhs[4] = o[4]; else mxDestroyArray(o[4]);
+                    if (nlhs > 5) plhs[5] = o[5]; else mxDestroyArray(o[5]);
+                    if (nlhs > 6) plhs[6] = o[6]; else mxDestroyArray(o[6]);
+                } else {
+                    for (mxArray* a : o) mxDestroyArray(a);
+                }
             }
         }
     } else if (!strcmp(cmd, "modelRefitCpd")) {               // [Tout, sigma2Out, Np, sumRes2, sumD2, nLive] = pcreg_mex('modelRefitCpd', h, single(pts), T, sigma2, outlier, steps)

@@ -81,6 +81,10 @@ SYMBOLS = [
     "pcreg_model_normals_f32", "pcreg_point_normals_f32", "pcreg_dev_model_normals_workspace", "pcreg_dev_model_normals_f32",
     "pcreg_model_refit_plane_f32", "pcreg_dev_model_refit_plane_workspace", "pcreg_dev_model_refit_plane_f32",
     "pcreg_model_refit_gicp_f32", "pcreg_dev_model_refit_gicp_workspace", "pcreg_dev_model_refit_gicp_f32",
+    "pcreg_model_score_trimmed_f32", "pcreg_dev_model_score_trimmed_f32",
+    "pcreg_model_refit_trimmed_f32", "pcreg_dev_model_refit_trimmed_f32",
+    "pcreg_model_refit_plane_trimmed_f32", "pcreg_dev_model_refit_plane_trimmed_f32",
+    "pcreg_model_refit_gicp_trimmed_f32", "pcreg_dev_model_refit_gicp_trimmed_f32",
     "pcreg_model_refit_cpd_f32", "pcreg_dev_model_refit_cpd_workspace", "pcreg_dev_model_refit_cpd_f32",
     "pcreg_model_denoise_f32", "pcreg_point_denoise_f32", "pcreg_dev_model_denoise_workspace", "pcreg_dev_model_denoise_f32",
     "pcreg_model_fps_f32", "pcreg_point_fps_f32", "pcreg_dev_model_fps_workspace", "pcreg_dev_model_fps_f32", "pcreg_debug_fps_stats",
@@ -255,6 +259,17 @@ def lib() -> C.CDLL:
             vp, i, f, d = C.c_void_p, C.c_int, C.c_float, C.c_double            # (a double by value: declared)
             L.pcreg_dev_model_refit_gicp_f32.argtypes = [vp, vp, i, i, vp, i, f, vp, i, vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
             L.pcreg_model_refit_gicp_f32.argtypes = [vp, vp, i, i, vp, i, f, i, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pcreg_dev_model_score_trimmed_f32"):           # (an older build given through PCREG_LIB lacks the trimmed entries)
+            vp, i, f, d = C.c_void_p, C.c_int, C.c_float, C.c_double
+            # the untrimmed twins' lists with keep_ratio after r2 and n_within, d2_cut at the end
+            L.pcreg_dev_model_score_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+            L.pcreg_model_score_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, vp, vp, vp, vp, vp, vp]
+            L.pcreg_dev_model_refit_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+            L.pcreg_model_refit_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, i, vp, vp, vp, vp, vp, vp]
+            L.pcreg_dev_model_refit_plane_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+            L.pcreg_model_refit_plane_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, i, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.pcreg_dev_model_refit_gicp_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, vp, i, vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+            L.pcreg_model_refit_gicp_trimmed_f32.argtypes = [vp, vp, i, i, vp, i, f, d, i, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "pcreg_dev_model_refit_cpd_workspace"):     # (an older build given through PCREG_LIB lacks the coherent-point-drift refit)
             L.pcreg_dev_model_refit_cpd_workspace.restype = C.c_size_t
             L.pcreg_dev_model_refit_cpd_workspace.argtypes = [C.c_int] * 3

@@ -1314,6 +1314,31 @@ def score_summary(n_close, sum_d2, Q: int) -> dict:
     return dict(n_close=n_close, sum_d2=sum_d2, fitness=fitness, rmse=rmse)
 
 
+class _Trim:
+    """The keep_ratio of a Model method: false for None (the untrimmed entry); otherwise the checked ratio, the two
+    [B] outputs the trimmed entry fills (`args`, its last two arguments), and into(), which adds them to the method's dict."""
+
+    def __init__(self, keep_ratio, B: int):
+        self.ratio = None
+        if keep_ratio is None:
+            return
+        self.ratio = float(keep_ratio)
+        if not 0.0 < self.ratio <= 1.0:
+            raise ValueError(f"keep_ratio must lie in (0, 1], got {self.ratio}")
+        self.B = B
+        self.n_within = np.zeros(max(B, 1), dtype=np.int32)
+        self.d2_cut = np.full(max(B, 1), np.inf, dtype=np.float32)
+        self.args = (self.n_within.ctypes.data, self.d2_cut.ctypes.data)
+
+    def __bool__(self):
+        return self.ratio is not None
+
+    def into(self, res: dict) -> dict:
+        if self:
+            res.update(n_within=self.n_within[:self.B], d2_cut=self.d2_cut[:self.B])
+        return res
+
+
 class Model:
     """A model cloud uploaded and prepared ONCE (pcreg_model_create), matched against any number of surfaces: the host-tier
     handle a MATLAB caller keeps across the sphere loop of completeExperimentFast.m:131-149.  Use as a context manager or
@@ -1361,13 +1386,17 @@ class Model:
         Q = q.shape[0]
         return _range_call(lambda cap, so, i, d: check(lib().pcreg_model_range_f32(self._h, q.ctypes.data, Q, max(Q, 1), r2, cap, so.ctypes.data, i, d)), Q)
 
-    def score_transforms(self, query, T, r2: float, rows: bool = False):
+    def score_transforms(self, query, T, r2: float, rows: bool = False, keep_ratio=None):
         """How well B transforms put `query` (Q x 3) on the prepared model (pcreg_model_score_f32).  T: a [B, 4, 4] array or a
         sequence of 4 x 4 matrices used as quickTF uses them, None or an all-zero matrix being the empty transform (it scores
         nothing); r2 the squared radius -> dict(n_close [B] int32, the queries with a model row within r2 of their
         transformed place; sum_d2 [B] float64, the sum of those squared distances; fitness = n_close / Q; rmse =
         sqrt(sum_d2 / n_close), NaN where nothing is close), and with rows=True also idx [B, Q] int32 (0-based, -1 for none)
-        and dist [B, Q] float32 (squared, +inf for none) -- the bits of a brute-force fp32 search."""
+        and dist [B, Q] float32 (squared, +inf for none) -- the bits of a brute-force fp32 search.
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_model_score_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query, and everything above
+        is about the kept pairs -- and the dict gains n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B]
+        float32, the largest kept squared distance (+inf where nothing is kept).  idx / dist hold -1 / +inf at trimmed slots."""
         if not self._h.value:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
@@ -1379,20 +1408,30 @@ class Model:
         sum_d2 = np.zeros(max(B, 1), dtype=np.float64)
         idx = np.zeros((B, Q), dtype=np.int32) if rows else None
         dist = np.zeros((B, Q), dtype=np.float32) if rows else None
-        check(lib().pcreg_model_score_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
-                                          n_close.ctypes.data, sum_d2.ctypes.data, idx.ctypes.data if rows and B * Q else None,
-                                          dist.ctypes.data if rows and B * Q else None))
-        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        trim = _Trim(keep_ratio, B)
+        if trim:
+            check(lib().pcreg_model_score_trimmed_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                                      trim.ratio, n_close.ctypes.data, sum_d2.ctypes.data, idx.ctypes.data if rows and B * Q else None,
+                                                      dist.ctypes.data if rows and B * Q else None, *trim.args))
+        else:
+            check(lib().pcreg_model_score_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                              n_close.ctypes.data, sum_d2.ctypes.data, idx.ctypes.data if rows and B * Q else None,
+                                              dist.ctypes.data if rows and B * Q else None))
+        res = trim.into(score_summary(n_close[:B], sum_d2[:B], Q))
         if rows:
             res.update(idx=idx, dist=dist)
         return res
 
-    def refit_transforms(self, query, T, r2: float, steps: int = 1):
+    def refit_transforms(self, query, T, r2: float, steps: int = 1, keep_ratio=None):
         """B transforms refitted on their close pairs against the prepared model, `steps` times over (pcreg_model_refit_f32): per
         step, T_step = estimateTransform(model rows, moved points) over the points of `query` (Q x 3) with a model row within
         r2 of their transformed place, and T <- T * T_step.  T as score_transforms takes it -> dict(T [B, 4, 4] float64, the
         refitted transforms, used as quickTF uses them, a zero matrix where there is no fit; empty [B] bool; n_close, sum_d2,
-        fitness, rmse as score_transforms gives them for the transform that went INTO the last step)."""
+        fitness, rmse as score_transforms gives them for the transform that went INTO the last step).
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_model_refit_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query, and everything above
+        is about the kept pairs -- and the dict gains n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B]
+        float32, the largest kept squared distance (+inf where nothing is kept).  Every step trims anew."""
         if not self._h.value:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
@@ -1407,13 +1446,19 @@ class Model:
         n_close = np.zeros(max(B, 1), dtype=np.int32)
         sum_d2 = np.zeros(max(B, 1), dtype=np.float64)
         empty = np.zeros(max(B, 1), dtype=np.int32)
-        check(lib().pcreg_model_refit_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
-                                          out.ctypes.data, n_close.ctypes.data, sum_d2.ctypes.data, empty.ctypes.data))
-        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        trim = _Trim(keep_ratio, B)
+        if trim:
+            check(lib().pcreg_model_refit_trimmed_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                                      trim.ratio, steps, out.ctypes.data, n_close.ctypes.data, sum_d2.ctypes.data, empty.ctypes.data,
+                                                      *trim.args))
+        else:
+            check(lib().pcreg_model_refit_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                              out.ctypes.data, n_close.ctypes.data, sum_d2.ctypes.data, empty.ctypes.data))
+        res = trim.into(score_summary(n_close[:B], sum_d2[:B], Q))
         res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0)
         return res
 
-    def refit_plane(self, query, T, r2: float, steps: int = 1, normals=None, k: int = 6):
+    def refit_plane(self, query, T, r2: float, steps: int = 1, normals=None, k: int = 6, keep_ratio=None):
         """B transforms refitted by the linearised point-to-plane step against the prepared model, `steps` times over
         (pcreg_model_refit_plane_f32, whose contract this is): the pairs are refit_transforms', the residual of a pair is its
         distance from the plane through the model row, and T <- T * T_step.  normals: [M, 3] float32 by original row, as
@@ -1421,7 +1466,11 @@ class Model:
         compute them once on the device from the k nearest rows (6 is MATLAB's pcnormals default).  -> refit_transforms' dict
         plus n_plane [B] int32, the pairs with a plane; sum_res2 [B] float64, the sum of their squared plane residuals;
         plane_rmse = sqrt(sum_res2 / n_plane), NaN where there is none -- all for the transform that went INTO the last step.
-        empty is also set where fewer than six planes, or planes that leave a direction free, give no fit."""
+        empty is also set where fewer than six planes, or planes that leave a direction free, give no fit.
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_model_refit_plane_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query, and everything above
+        is about the kept pairs -- and the dict gains n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B]
+        float32, the largest kept squared distance (+inf where nothing is kept).  Every step trims anew."""
         if not self._h.value:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
@@ -1442,18 +1491,26 @@ class Model:
         out = np.zeros((max(B, 1), 16), dtype=np.float64)
         n_close, n_plane, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(3))
         sum_d2, sum_res2 = (np.zeros(max(B, 1), dtype=np.float64) for _ in range(2))
-        check(lib().pcreg_model_refit_plane_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
-                                                nrm.ctypes.data if nrm is not None else None, max(self.M, 1), int(k), out.ctypes.data,
-                                                n_close.ctypes.data, sum_d2.ctypes.data, n_plane.ctypes.data, sum_res2.ctypes.data,
-                                                empty.ctypes.data))
-        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        trim = _Trim(keep_ratio, B)
+        if trim:
+            check(lib().pcreg_model_refit_plane_trimmed_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                                            trim.ratio, steps, nrm.ctypes.data if nrm is not None else None, max(self.M, 1), int(k),
+                                                            out.ctypes.data, n_close.ctypes.data, sum_d2.ctypes.data, n_plane.ctypes.data,
+                                                            sum_res2.ctypes.data, empty.ctypes.data, *trim.args))
+        else:
+            check(lib().pcreg_model_refit_plane_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                                    nrm.ctypes.data if nrm is not None else None, max(self.M, 1), int(k), out.ctypes.data,
+                                                    n_close.ctypes.data, sum_d2.ctypes.data, n_plane.ctypes.data, sum_res2.ctypes.data,
+                                                    empty.ctypes.data))
+        res = trim.into(score_summary(n_close[:B], sum_d2[:B], Q))
         with np.errstate(divide="ignore", invalid="ignore"):
             plane_rmse = np.where(n_plane[:B] > 0, np.sqrt(sum_res2[:B] / n_plane[:B]), np.nan)
         res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, n_plane=n_plane[:B],
                    sum_res2=sum_res2[:B], plane_rmse=plane_rmse)
         return res
 
-    def refit_gicp(self, query, T, r2: float, steps: int = 1, normals=None, query_normals=None, k: int = 6, epsilon: float = 1e-3):
+    def refit_gicp(self, query, T, r2: float, steps: int = 1, normals=None, query_normals=None, k: int = 6, epsilon: float = 1e-3,
+                   keep_ratio=None):
         """B transforms refitted by the plane-to-plane (generalized ICP) step against the prepared model, `steps` times over
         (pcreg_model_refit_gicp_f32, whose contract this is): the pairs are refit_transforms', a pair is weighted by the inverse
         of the sum of the two sides' covariances, each I - (1 - epsilon) n n^T about its own normal, and T <- T * T_step.
@@ -1462,7 +1519,11 @@ class Model:
         immaterial); either None: computed once on the device from the k nearest rows of its own cloud.  epsilon in (0, 1].
         -> refit_transforms' dict plus n_pairs [B] int32, the plane-to-plane pairs; sum_res2 [B] float64, the sum of their
         e^T W e; pair_rmse = sqrt(sum_res2 / n_pairs), NaN where there is none -- all for the transform that went INTO the last
-        step.  empty is also set where fewer than six pairs, or pairs that leave a direction free, give no fit."""
+        step.  empty is also set where fewer than six pairs, or pairs that leave a direction free, give no fit.
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_model_refit_gicp_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query, and everything above
+        is about the kept pairs -- and the dict gains n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B]
+        float32, the largest kept squared distance (+inf where nothing is kept).  Every step trims anew."""
         if not self._h.value:
             raise ValueError("the model handle is closed")
         r2 = _range_r2(r2)
@@ -1489,12 +1550,20 @@ class Model:
         out = np.zeros((max(B, 1), 16), dtype=np.float64)
         n_close, n_pairs, empty = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(3))
         sum_d2, sum_res2 = (np.zeros(max(B, 1), dtype=np.float64) for _ in range(2))
-        check(lib().pcreg_model_refit_gicp_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
-                                               nrm.ctypes.data if nrm is not None else None, max(self.M, 1),
-                                               nq.ctypes.data if nq is not None else None, max(Q, 1), int(k), epsilon, out.ctypes.data,
-                                               n_close.ctypes.data, sum_d2.ctypes.data, n_pairs.ctypes.data, sum_res2.ctypes.data,
-                                               empty.ctypes.data))
-        res = score_summary(n_close[:B], sum_d2[:B], Q)
+        trim = _Trim(keep_ratio, B)
+        if trim:
+            check(lib().pcreg_model_refit_gicp_trimmed_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2,
+                                                           trim.ratio, steps, nrm.ctypes.data if nrm is not None else None, max(self.M, 1),
+                                                           nq.ctypes.data if nq is not None else None, max(Q, 1), int(k), epsilon, out.ctypes.data,
+                                                           n_close.ctypes.data, sum_d2.ctypes.data, n_pairs.ctypes.data, sum_res2.ctypes.data,
+                                                           empty.ctypes.data, *trim.args))
+        else:
+            check(lib().pcreg_model_refit_gicp_f32(self._h, q.ctypes.data if Q else None, Q, max(Q, 1), T16.ctypes.data if B else None, B, r2, steps,
+                                                   nrm.ctypes.data if nrm is not None else None, max(self.M, 1),
+                                                   nq.ctypes.data if nq is not None else None, max(Q, 1), int(k), epsilon, out.ctypes.data,
+                                                   n_close.ctypes.data, sum_d2.ctypes.data, n_pairs.ctypes.data, sum_res2.ctypes.data,
+                                                   empty.ctypes.data))
+        res = trim.into(score_summary(n_close[:B], sum_d2[:B], Q))
         with np.errstate(divide="ignore", invalid="ignore"):
             pair_rmse = np.where(n_pairs[:B] > 0, np.sqrt(sum_res2[:B] / n_pairs[:B]), np.nan)
         res.update(T=np.ascontiguousarray(out[:B].reshape(B, 4, 4).transpose(0, 2, 1)), empty=empty[:B] != 0, n_pairs=n_pairs[:B],

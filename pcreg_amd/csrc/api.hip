@@ -496,6 +496,56 @@ int pcreg_dev_model_refit_gicp_f32(const pcreg_dev_model* model, const float* q,
     return launch_model_refit_gicp(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, qnormals, ldnq, epsilon, T_out, T_step, n_close, sum_d2,
                                    n_pairs, sum_res2, empty, workspace, workspace_bytes, (hipStream_t)stream);
 }
+// the trimmed twins: the same checks and launchers, with the trim request; n_within and d2_cut may be null
+#define TRIM_RATIO_OK(x) ((x) > 0.0 && (x) <= 1.0)                           /* (a NaN fails both) */
+int pcreg_dev_model_score_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                      double keep_ratio, int32_t* n_close, double* sum_d2, int32_t* idx, float* dist, void* workspace,
+                                      size_t workspace_bytes, void* stream, int32_t* n_within, float* d2_cut) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && TRIM_RATIO_OK(keep_ratio));
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && n_close && sum_d2)));
+    PCREG_ARG(workspace_bytes >= score_ws_bytes(Q, B, 0));   // (the untrimmed size: it does not depend on M)
+    GUARD();
+    const TrimIo trim{keep_ratio, n_within, d2_cut};
+    return launch_model_score(model->v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, workspace, workspace_bytes, (hipStream_t)stream, &trim);
+}
+int pcreg_dev_model_refit_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                      double keep_ratio, double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* empty,
+                                      void* workspace, size_t workspace_bytes, void* stream, int32_t* n_within, float* d2_cut) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && TRIM_RATIO_OK(keep_ratio));
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_ws_bytes(Q, B, 0));   // (the untrimmed size: it does not depend on M)
+    GUARD();
+    const TrimIo trim{keep_ratio, n_within, d2_cut};
+    return launch_model_refit(model->v, q, Q, ldq, T_dev, B, r2, T_out, T_step, n_close, sum_d2, empty, workspace, workspace_bytes,
+                              (hipStream_t)stream, &trim);
+}
+int pcreg_dev_model_refit_plane_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                            double keep_ratio, const float* normals, int ldn, double* T_out, double* T_step, int32_t* n_close,
+                                            double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty, void* workspace,
+                                            size_t workspace_bytes, void* stream, int32_t* n_within, float* d2_cut) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && normals && ldn >= 0 && TRIM_RATIO_OK(keep_ratio));
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && n_plane && sum_res2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_plane_ws_bytes(Q, B, 0));   // (the untrimmed size: it does not depend on M)
+    PCREG_ARG(ldn >= model->v.M);
+    GUARD();
+    const TrimIo trim{keep_ratio, n_within, d2_cut};
+    return launch_model_refit_plane(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty,
+                                    workspace, workspace_bytes, (hipStream_t)stream, &trim);
+}
+int pcreg_dev_model_refit_gicp_trimmed_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, float r2,
+                                           double keep_ratio, const float* normals, int ldn, const float* qnormals, int ldnq, double epsilon,
+                                           double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2,
+                                           int32_t* empty, void* workspace, size_t workspace_bytes, void* stream, int32_t* n_within, float* d2_cut) {
+    PCREG_ARG(model && workspace && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && normals && ldn >= 0 && TRIM_RATIO_OK(keep_ratio));
+    PCREG_ARG(ldnq >= Q && (Q == 0 || qnormals) && epsilon > 0.0 && epsilon <= 1.0);
+    PCREG_ARG((Q == 0 || q) && (B == 0 || (T_dev && T_out && T_out != T_dev && n_close && sum_d2 && n_pairs && sum_res2 && empty)));
+    PCREG_ARG(workspace_bytes >= refit_gicp_ws_bytes(Q, B, 0));   // (the untrimmed size: it does not depend on M)
+    PCREG_ARG(ldn >= model->v.M);
+    GUARD();
+    const TrimIo trim{keep_ratio, n_within, d2_cut};
+    return launch_model_refit_gicp(model->v, q, Q, ldq, T_dev, B, r2, normals, ldn, qnormals, ldnq, epsilon, T_out, T_step, n_close, sum_d2,
+                                   n_pairs, sum_res2, empty, workspace, workspace_bytes, (hipStream_t)stream, &trim);
+}
 size_t pcreg_dev_model_refit_cpd_workspace(int Q, int B, int M) { return refit_cpd_ws_bytes(Q, B, M); }
 int pcreg_dev_model_refit_cpd_f32(const pcreg_dev_model* model, const float* q, int Q, int ldq, const double* T_dev, int B, const double* sigma2_in,
                                   double outlier, double* T_out, double* T_step, double* sigma2_out, double* Np, double* sum_res2, double* sum_d2,
@@ -796,9 +846,12 @@ int pcreg_range_points_f32(const float* q, int Q, int ldq, const float* m, int M
 
 // B transforms scored against a prepared model: upload the queries and the transforms, score, read the 12 B bytes of counts
 // and sums back, and the [B][Q] rows and distances when the caller asked for them
-int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int32_t* n_close,
-                          double* sum_d2, int32_t* idx, float* dist) {
+// (`keep`: the trimmed twin's ratio and its two outputs, each of which may be null -- DESIGN 4.32; null: the untrimmed call)
+struct HostTrim { double keep_ratio; int32_t* n_within; float* d2_cut; };
+static int model_score_host(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, const HostTrim* keep,
+                            int32_t* n_close, double* sum_d2, int32_t* idx, float* dist) {
     PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f);
+    PCREG_ARG(!keep || TRIM_RATIO_OK(keep->keep_ratio));
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T && n_close && sum_d2)));
     PCREG_ARG(model->dm != nullptr);
     GUARD();
@@ -806,7 +859,7 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     Stage st{scratch()};
     const ModelView& v = model->dm->v;
     const size_t wsb = score_ws_bytes(Q, B, v.M), bq = (size_t)B * Q;
-    float *dq, *dd; double *dT, *ds; int32_t *dn, *di; char* ws;
+    float *dq, *dd, *dc; double *dT, *ds; int32_t *dn, *di, *dw; char* ws;
     TRY(st.take(3 * (size_t)Q, &dq));
     TRY(st.take(16 * (size_t)B, &dT));
     TRY(st.take((size_t)B, &dn));
@@ -814,9 +867,14 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     TRY(st.take(idx ? bq : 0, &di));
     TRY(st.take(dist ? bq : 0, &dd));
     TRY(st.take(wsb, &ws));
+    TRY(st.take(keep ? (size_t)B : 0, &dw));
+    TRY(st.take(keep ? (size_t)B : 0, &dc));
     TRY(upload_cols(q, Q, ldq, 3, dq, g_stream));
     PCREG_HIP(hipMemcpyAsync(dT, T, sizeof(double) * 16 * (size_t)B, hipMemcpyHostToDevice, g_stream));
-    TRY(launch_model_score(v, dq, Q, Q, dT, B, r2, dn, ds, idx ? di : nullptr, dist ? dd : nullptr, ws, wsb, g_stream));
+    const TrimIo trim{keep ? keep->keep_ratio : 1.0, dw, dc};
+    TRY(launch_model_score(v, dq, Q, Q, dT, B, r2, dn, ds, idx ? di : nullptr, dist ? dd : nullptr, ws, wsb, g_stream, keep ? &trim : nullptr));
+    if (keep && keep->n_within) PCREG_HIP(hipMemcpyAsync(keep->n_within, dw, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
+    if (keep && keep->d2_cut) PCREG_HIP(hipMemcpyAsync(keep->d2_cut, dc, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(n_close, dn, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
     PCREG_HIP(hipMemcpyAsync(sum_d2, ds, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, g_stream));
     if (idx && bq) PCREG_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * bq, hipMemcpyDeviceToHost, g_stream));
@@ -825,12 +883,22 @@ int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, co
     return PCREG_OK;
 }
 
+int pcreg_model_score_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int32_t* n_close,
+                          double* sum_d2, int32_t* idx, float* dist) {
+    return model_score_host(model, q, Q, ldq, T, B, r2, nullptr, n_close, sum_d2, idx, dist);
+}
+int pcreg_model_score_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, double keep_ratio,
+                                  int32_t* n_close, double* sum_d2, int32_t* idx, float* dist, int32_t* n_within, float* d2_cut) {
+    const HostTrim keep{keep_ratio, n_within, d2_cut};
+    return model_score_host(model, q, Q, ldq, T, B, r2, &keep, n_close, sum_d2, idx, dist);
+}
+
 // The staging of every "B transforms refitted `steps` times" entry: the queries and the transforms are uploaded once, the steps
 // run on the device, each step's T_out the next one's input, and ONE result block is read back -- the last step's.  A block is
 // `cols` doubles' room per transform and starts with T_out (16 B doubles); two blocks take turns, because a step may not write
 // over its input.  The takes keep the Stage rule (every take before the first use) and each entry's order: take_inputs, the
 // entry's own inputs, take_blocks, the entry's own workspaces; then upload, the entry's own uploads, run.
-struct RefitCol { void* dst; int word; size_t bytes; };            // B elements of `bytes` bytes from 4-byte word `word` x B of the block
+struct RefitCol { void* dst; int word; size_t bytes; };            // B elements of `bytes` bytes from 4-byte word `word` x B of the block (dst null: not wanted)
 struct RefitStaging {
     Stage st{scratch()};
     size_t nQ, nB; int cols;
@@ -861,39 +929,51 @@ struct RefitStaging {
         std::vector<double> host((size_t)cols * nB);
         PCREG_HIP(hipMemcpyAsync(host.data(), blk, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g_stream));
         PCREG_HIP(hipStreamSynchronize(g_stream));
-        for (const RefitCol& c : table) memcpy(c.dst, (const char*)host.data() + 4 * (size_t)c.word * nB, c.bytes * nB);
+        for (const RefitCol& c : table) if (c.dst) memcpy(c.dst, (const char*)host.data() + 4 * (size_t)c.word * nB, c.bytes * nB);
         return PCREG_OK;
     }
 };
 
 // B transforms refitted `steps` times on their close pairs; the block: [T_out 16 B doubles][sum_d2 B doubles][n_close B int32]
-// [empty B int32]
-int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps, double* T_out,
-                          int32_t* n_close, double* sum_d2, int32_t* empty) {
+// [empty B int32], and in every refit's trimmed twin one more column at the end: [n_within B int32][d2_cut B float]
+static int model_refit_host(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, const HostTrim* keep, int steps,
+                            double* T_out, int32_t* n_close, double* sum_d2, int32_t* empty) {
     PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG(!keep || TRIM_RATIO_OK(keep->keep_ratio));
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && empty)));
     PCREG_ARG(model->dm != nullptr);
     GUARD();
     if (B == 0) return PCREG_OK;
     const ModelView& v = model->dm->v;
     const size_t wsb = refit_ws_bytes(Q, B, v.M), nB = (size_t)B;
-    RefitStaging rs(Q, B, 18);                                             // 17 B doubles and 2 B int32
+    RefitStaging rs(Q, B, keep ? 19 : 18);                                 // 17 B doubles and 2 B int32 (and the trim's column)
     TRY(rs.take_inputs());
     TRY(rs.take_blocks(wsb));
     TRY(rs.upload(q, ldq, T));
     return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 17 * nB);
-        return launch_model_refit(v, rs.dq, Q, Q, in, B, r2, blk, nullptr, ib, blk + 16 * nB, ib + nB, rs.ws, wsb, g_stream);
-    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {n_close, 34, 4}, {empty, 35, 4}});
+        const TrimIo trim{keep ? keep->keep_ratio : 1.0, ib + 2 * nB, (float*)(ib + 3 * nB)};
+        return launch_model_refit(v, rs.dq, Q, Q, in, B, r2, blk, nullptr, ib, blk + 16 * nB, ib + nB, rs.ws, wsb, g_stream, keep ? &trim : nullptr);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {n_close, 34, 4}, {empty, 35, 4}, {keep ? keep->n_within : nullptr, 36, 4}, {keep ? keep->d2_cut : nullptr, 37, 4}});
+}
+int pcreg_model_refit_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps, double* T_out,
+                          int32_t* n_close, double* sum_d2, int32_t* empty) {
+    return model_refit_host(model, q, Q, ldq, T, B, r2, nullptr, steps, T_out, n_close, sum_d2, empty);
+}
+int pcreg_model_refit_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, double keep_ratio, int steps,
+                                  double* T_out, int32_t* n_close, double* sum_d2, int32_t* empty, int32_t* n_within, float* d2_cut) {
+    const HostTrim keep{keep_ratio, n_within, d2_cut};
+    return model_refit_host(model, q, Q, ldq, T, B, r2, &keep, steps, T_out, n_close, sum_d2, empty);
 }
 
 // B transforms refitted `steps` times by the point-to-plane step, with the normals uploaded once (or computed once on the device
 // by the normals chain, k nearest rows and no viewpoint) before the first step; the block: [T_out 16 B doubles][sum_d2 B]
 // [sum_res2 B][n_close B int32][n_plane B int32][empty B int32]
-int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
-                                const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_plane,
-                                double* sum_res2, int32_t* empty) {
+static int model_refit_plane_host(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, const HostTrim* keep, int steps,
+                                  const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_plane,
+                                  double* sum_res2, int32_t* empty) {
     PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG(!keep || TRIM_RATIO_OK(keep->keep_ratio));
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && n_plane && sum_res2 && empty)));
     PCREG_ARG(normals ? ldn >= 0 : (k >= 3 && k <= kKnnMaxK));
     PCREG_ARG(model->dm != nullptr && (!normals || ldn >= model->M));
@@ -902,7 +982,7 @@ int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int l
     const ModelView& v = model->dm->v;
     const int M = v.M;
     const size_t wsb = refit_plane_ws_bytes(Q, B, M), nwsb = normals || M == 0 ? 0 : normals_ws_bytes(M, k), nB = (size_t)B;
-    RefitStaging rs(Q, B, 20);                                             // 18 B doubles and 3 B int32
+    RefitStaging rs(Q, B, keep ? 21 : 20);                                 // 18 B doubles and 3 B int32 (a word of padding, then the trim's column)
     float* dn; char* nws;
     TRY(rs.take_inputs());
     TRY(rs.st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
@@ -913,18 +993,32 @@ int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int l
     else if (M > 0) TRY(launch_model_normals(v, k, nullptr, dn, M, nullptr, nws, nwsb, g_stream));
     return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 18 * nB);
+        const TrimIo trim{keep ? keep->keep_ratio : 1.0, ib + 4 * nB, (float*)(ib + 5 * nB)};
         return launch_model_refit_plane(v, rs.dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, blk, nullptr, ib, blk + 16 * nB, ib + nB, blk + 17 * nB, ib + 2 * nB,
-                                        rs.ws, wsb, g_stream);
-    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_plane, 37, 4}, {empty, 38, 4}});
+                                        rs.ws, wsb, g_stream, keep ? &trim : nullptr);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_plane, 37, 4}, {empty, 38, 4},
+        {keep ? keep->n_within : nullptr, 40, 4}, {keep ? keep->d2_cut : nullptr, 41, 4}});
+}
+int pcreg_model_refit_plane_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
+                                const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_plane,
+                                double* sum_res2, int32_t* empty) {
+    return model_refit_plane_host(model, q, Q, ldq, T, B, r2, nullptr, steps, normals, ldn, k, T_out, n_close, sum_d2, n_plane, sum_res2, empty);
+}
+int pcreg_model_refit_plane_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, double keep_ratio,
+                                        int steps, const float* normals, int ldn, int k, double* T_out, int32_t* n_close, double* sum_d2,
+                                        int32_t* n_plane, double* sum_res2, int32_t* empty, int32_t* n_within, float* d2_cut) {
+    const HostTrim keep{keep_ratio, n_within, d2_cut};
+    return model_refit_plane_host(model, q, Q, ldq, T, B, r2, &keep, steps, normals, ldn, k, T_out, n_close, sum_d2, n_plane, sum_res2, empty);
 }
 
 // B transforms refitted `steps` times by the plane-to-plane step: pcreg_model_refit_plane_f32's result block, with the
 // query normals beside the model normals -- each uploaded once, or computed once on the device by the normals chain (k nearest
 // rows, no viewpoint; the queries' from a prepared model of q that lives in the staging and goes with it)
-int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
-                               const float* normals, int ldn, const float* qnormals, int ldnq, int k, double epsilon, double* T_out,
-                               int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty) {
+static int model_refit_gicp_host(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, const HostTrim* keep, int steps,
+                                 const float* normals, int ldn, const float* qnormals, int ldnq, int k, double epsilon, double* T_out,
+                                 int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty) {
     PCREG_ARG(model && Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxQ && r2 >= 0.0f && steps >= 1);
+    PCREG_ARG(!keep || TRIM_RATIO_OK(keep->keep_ratio));
     PCREG_ARG((Q == 0 || q) && (B == 0 || (T && T_out && n_close && sum_d2 && n_pairs && sum_res2 && empty)));
     PCREG_ARG(epsilon > 0.0 && epsilon <= 1.0);                               // (a NaN epsilon fails both)
     PCREG_ARG((normals && qnormals) || (k >= 3 && k <= kKnnMaxK));
@@ -937,7 +1031,7 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
     const bool own_q = !qnormals && Q > 0;
     const size_t wsb = refit_gicp_ws_bytes(Q, B, M), nB = (size_t)B;
     const size_t nwsb = std::max(normals || M == 0 ? (size_t)0 : normals_ws_bytes(M, k), own_q ? normals_ws_bytes(Q, k) : (size_t)0);
-    RefitStaging rs(Q, B, 20);                                             // 18 B doubles and 3 B int32
+    RefitStaging rs(Q, B, keep ? 21 : 20);                                 // 18 B doubles and 3 B int32 (a word of padding, then the trim's column)
     float *dn, *dnq; char *nws, *qblock;
     TRY(rs.take_inputs());
     TRY(rs.st.take(3 * (size_t)(M > 0 ? M : 1), &dn));
@@ -956,9 +1050,25 @@ int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ld
     }
     return rs.run(steps, [&](const double* in, double* blk) {
         int32_t* ib = (int32_t*)(blk + 18 * nB);
+        const TrimIo trim{keep ? keep->keep_ratio : 1.0, ib + 4 * nB, (float*)(ib + 5 * nB)};
         return launch_model_refit_gicp(v, rs.dq, Q, Q, in, B, r2, dn, M > 0 ? M : 1, dnq, Q > 0 ? Q : 1, epsilon, blk, nullptr, ib, blk + 16 * nB, ib + nB,
-                                       blk + 17 * nB, ib + 2 * nB, rs.ws, wsb, g_stream);
-    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_pairs, 37, 4}, {empty, 38, 4}});
+                                       blk + 17 * nB, ib + 2 * nB, rs.ws, wsb, g_stream, keep ? &trim : nullptr);
+    }, {{T_out, 0, 128}, {sum_d2, 32, 8}, {sum_res2, 34, 8}, {n_close, 36, 4}, {n_pairs, 37, 4}, {empty, 38, 4},
+        {keep ? keep->n_within : nullptr, 40, 4}, {keep ? keep->d2_cut : nullptr, 41, 4}});
+}
+int pcreg_model_refit_gicp_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, int steps,
+                               const float* normals, int ldn, const float* qnormals, int ldnq, int k, double epsilon, double* T_out,
+                               int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty) {
+    return model_refit_gicp_host(model, q, Q, ldq, T, B, r2, nullptr, steps, normals, ldn, qnormals, ldnq, k, epsilon, T_out, n_close, sum_d2, n_pairs,
+                                 sum_res2, empty);
+}
+int pcreg_model_refit_gicp_trimmed_f32(pcreg_model* model, const float* q, int Q, int ldq, const double* T, int B, float r2, double keep_ratio,
+                                       int steps, const float* normals, int ldn, const float* qnormals, int ldnq, int k, double epsilon,
+                                       double* T_out, int32_t* n_close, double* sum_d2, int32_t* n_pairs, double* sum_res2, int32_t* empty,
+                                       int32_t* n_within, float* d2_cut) {
+    const HostTrim keep{keep_ratio, n_within, d2_cut};
+    return model_refit_gicp_host(model, q, Q, ldq, T, B, r2, &keep, steps, normals, ldn, qnormals, ldnq, k, epsilon, T_out, n_close, sum_d2, n_pairs,
+                                 sum_res2, empty);
 }
 
 // B transforms refitted `steps` times by the coherent-point-drift step; the block: [T_out 16 B doubles][sigma2_out B][Np B]

@@ -24,13 +24,14 @@ __device__ __forceinline__ void chunk_sum(T v, T* __restrict__ csum) {
     if (threadIdx.x == 0) csum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
-// the sum of everything before this thread's elements: the chunks before this one, plus `mine` of the threads before this one
+// the sum of everything before this thread's elements: the chunks before chunk `chunk` of csum, plus `mine` of the threads before
+// this one (a grid of several scans side by side names its own chunk; chunk_offset is the one scan whose chunk is the workgroup)
 template <typename T>
-__device__ __forceinline__ T chunk_offset(const T* __restrict__ csum, T mine) {
+__device__ __forceinline__ T chunk_offset_at(const T* __restrict__ csum, int chunk, T mine) {
     __shared__ T s[kScanBlock / 64], s_thr[kScanBlock];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     T before = 0;
-    for (int c = tid; c < (int)blockIdx.x; c += kScanBlock) before += csum[c];
+    for (int c = tid; c < chunk; c += kScanBlock) before += csum[c];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
     if (lane == 0) s[wave] = before;
@@ -45,6 +46,10 @@ __device__ __forceinline__ T chunk_offset(const T* __restrict__ csum, T mine) {
         __syncthreads();
     }
     return run + (s_thr[tid] - mine);
+}
+template <typename T>
+__device__ __forceinline__ T chunk_offset(const T* __restrict__ csum, T mine) {
+    return chunk_offset_at<T>(csum, (int)blockIdx.x, mine);
 }
 
 // ---- the compaction of a predicate pred(i) on rows 0 .. n - 1 into an ascending row list, on the scan's two launches ----------

@@ -237,15 +237,26 @@ int launch_model_range_fill(const ModelView& v, const float* q, int Q, int ldq, 
 int launch_query_cells(const ModelView& v, const float* q, int Q, int ldq, int32_t* qcnt, hipStream_t st);
 // B transforms of one query cloud scored against the model (knn_score.hip): per transform the queries with a row within r2 and
 // the sum of their squared distances; idx / dist [B][Q] (either may be null) the nearest such row, -1 / +inf for none
+// `trim` (every launcher below that takes one; null: none, and nothing more is launched): keep only each transform's closest
+// pairs (knn_trim.hip) -- keep_ratio in (0, 1]; n_within [B] the pairs within r2, d2_cut [B] the largest kept d,
+// either may be null.  The workspace is the untrimmed call's: the pass works in blocks that are dead between the walk and the sums
+struct TrimIo { double keep_ratio; int32_t* n_within; float* d2_cut; };
+constexpr size_t kTrimSelBytes = 16;               // the select state of a transform (knn_trim.hip)
+// ... the pass itself on nb transforms' best [nb][Q] (Q > 0, chunks = ceil(Q / 2048)): hist [nb][256], sel [nb] states, tie [nb chunks];
+// idx / dist the caller's tables at the batch's first transform, or null; n_within / d2_cut at it too, or null
+int launch_score_trim(float* best, int Q, int chunks, int nb, double keep_ratio, int32_t* hist, void* sel, int32_t* tie, int32_t* idx, float* dist,
+                      int32_t* n_within, float* d2_cut, hipStream_t st);
+// ... and of a call without pairs: n_within = 0, d2_cut = +inf
+int launch_trim_empty(int B, int32_t* n_within, float* d2_cut, hipStream_t st);
 size_t score_ws_bytes(int Q, int B, int M);
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
-                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st);
+                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim = nullptr);
 // the same B transforms each refitted on its close pairs (knn_score.hip): T_step = estimateTransform(model rows, moved
 // points) over the queries with a row within r2, T_out = T * T_step, empty[b] = 1 and zeros where there is no fit; n_close and
 // sum_d2 are launch_model_score's bits.  T_step may be null; T_out may not alias T_dev
 size_t refit_ws_bytes(int Q, int B, int M);
 int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
-                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
+                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim = nullptr);
 // ... its last step per batch of nb transforms (ransac.hip, where fit_moments and fit_3pt live): chunk moments pmom [nb][chunks][27]
 // about origin[0..2], the batch's per-slot buffers best / tq / win (ld S), n_close [nb] already totalled
 int launch_refit_finish(const double* pmom, const int32_t* n_close, const float* best, const float* tq, const float* win, int Q, int S, int chunks,
@@ -259,14 +270,14 @@ int launch_refit_empty(int B, double* T_out, double* T_step, int32_t* empty, con
 size_t refit_plane_ws_bytes(int Q, int B, int M);
 int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                              double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty,
-                             void* ws, size_t ws_bytes, hipStream_t st);
+                             void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim = nullptr);
 // the same chain with the plane-to-plane (generalized ICP) sums in the point-to-plane ones' place (knn_score.hip, gicp_pair.hpp; DESIGN
 // 4.26): qnormals [3][ldnq] on the device by query; n_pairs the pairs both of whose normals are finite and whose S factorises,
 // sum_res2 their e . (W e).  The workspace is the plane refit's
 size_t refit_gicp_ws_bytes(int Q, int B, int M);
 int launch_model_refit_gicp(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                             const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
-                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st);
+                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim = nullptr);
 // one coherent-point-drift step of the same B transforms (cpd.hip, cpd_fit.hpp): every moved point against every live
 // model row, B Q M pairs; sigma2_in [B] on the device (0: the closed-form initial value), outlier in [0, 1); sum_d2 the scoring chain's
 // at r2 = +inf (the shift), n_live the queries whose moved point is finite.  T_step may be null; T_out may not alias T_dev

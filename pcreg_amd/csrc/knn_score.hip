@@ -348,8 +348,14 @@ int score_batch(int Q, int B, int slots) {
 // The plane refit's is the refit's with 28 chunk sums instead of 27, followed by [winning row per slot, S] [chunk plane counts, P]:
 // + roundup(12 S, 256) + roundup(224 P, 256) + roundup(4 S, 256) + roundup(4 P, 256)
 // The plane-to-plane refit needs nothing more: it runs in the plane refit's layout, its pair counts in the plane counts' place.
+// A trimmed call runs in its method's layout as it is: between the walk and the sums the per-parent-cell counters
+// and the slot -> query block are dead, and the chunk counts are not written yet.  Its digit counters and select states (1040 bytes
+// a transform) go into the larger of the first two, `trim_cap` transforms at a time (at least 126: 131 328 / 1040), its chunk tie
+// counts into the chunk counts' place.
 enum ScoreMode { kModeScore = 0, kModeRefit = 1, kModePlane = 2 };
-struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; int32_t* prow; int32_t* pplane; };
+struct ScoreWs { int32_t* qcnt; float* tq; int32_t* qperm; float* best; double* psum; int32_t* pcnt; float* win; double* pmom; int32_t* prow; int32_t* pplane;
+                 char* trim_at; int trim_cap; };
+constexpr size_t kTrimPer = 1024 + kTrimSelBytes;    // a transform's 256 digit counters and its select state
 ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes) {
     ScoreWs s{};
     const int nb = score_batch(Q, B, kScoreMaxSlots);
@@ -369,6 +375,9 @@ ScoreWs score_ws_layout(int Q, int B, ScoreMode mode, void* base, size_t* bytes)
         s.prow = w.take<int32_t>(S);
         s.pplane = w.take<int32_t>(P);
     }
+    const size_t cells = (size_t)kQueryKeys * 4 + 256, order = align_up(S * sizeof(int32_t), (size_t)256);
+    s.trim_at = order > cells ? (char*)s.qperm : (char*)s.qcnt;
+    s.trim_cap = (int)std::min(std::max(order, cells) / kTrimPer, (size_t)nb);
     *bytes = w.bytes();
     return s;
 }
@@ -383,9 +392,10 @@ struct GicpIo { const float* qnormals; int ldnq; double a; };
 // the chain of every call; `refit` null: scoring; `plane` (with refit) non-null: the point-to-plane fit instead of estimateTransform;
 // `gicp` (with plane) non-null: the plane-to-plane sums instead of the point-to-plane ones, in the same workspace
 int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close, double* sum_d2,
-                int32_t* idx, float* dist, const RefitOut* refit, const PlaneIo* plane, const GicpIo* gicp, void* ws, size_t ws_bytes,
-                hipStream_t st) {
+                int32_t* idx, float* dist, const RefitOut* refit, const PlaneIo* plane, const GicpIo* gicp, const TrimIo* trim, void* ws,
+                size_t ws_bytes, hipStream_t st) {
     PCREG_ARG(Q >= 0 && B >= 0 && ldq >= Q && Q <= kScoreMaxSlots && r2 >= 0.0f);
+    PCREG_ARG(!trim || (trim->keep_ratio > 0.0 && trim->keep_ratio <= 1.0));          // (a NaN fails both)
     size_t need;
     const ScoreWs s = score_ws_layout(Q, B, plane ? kModePlane : refit ? kModeRefit : kModeScore, ws, &need);
     if (ws_bytes < need) {
@@ -407,8 +417,9 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
             int rc = launch_refit_empty(B, refit->T_out, refit->T_step, refit->empty, z, st);
             if (rc) return rc;
         }
-        return PCREG_OK;
+        return trim ? launch_trim_empty(B, trim->n_within, trim->d2_cut, st) : PCREG_OK;
     }
+    int32_t* const user_idx = idx;                                // (the trim writes misses into the CALLER's tables only)
     if (plane) idx = s.prow;                                      // the winning row per slot of ONE batch (S entries: only the walk may write it)
     const int dbg_slots = debug_flag(kDbgScoreBatchSlots);        // "score_batch_slots": a lower cap, same results
     const int nb_max = score_batch(Q, B, dbg_slots > 0 ? std::min(dbg_slots, kScoreMaxSlots) : kScoreMaxSlots);
@@ -430,6 +441,17 @@ int score_chain(const ModelView& v, const float* q, int Q, int ldq, const double
             hipLaunchKernelGGL(score_walk_kernel<false>, walk_grid, dim3(kBlock), 0, st, (const float*)s.tq, S, (const int32_t*)s.qperm, (const float*)v.ms,
                                (const int32_t*)v.perm, v.M, (const float*)v.tbox, n_tiles, cull, r2, s.best, idx ? idx + at : nullptr,
                                dist ? dist + at : nullptr, (float*)nullptr, knn_stats_dev());
+        if (trim) {                                               // the kept pairs stay hits, the others become misses (knn_trim.hip)
+            PCREG_HIP(hipGetLastError());
+            for (int t0 = 0; t0 < nb; t0 += s.trim_cap) {       // (one round wherever a transform has 260 queries or more)
+                const int nt = std::min(s.trim_cap, nb - t0);
+                const size_t o = (size_t)t0 * Q;
+                rc = launch_score_trim(s.best + o, Q, chunks, nt, trim->keep_ratio, (int32_t*)s.trim_at, s.trim_at + 1024 * (size_t)nt,
+                                       s.pcnt + (size_t)t0 * chunks, user_idx ? user_idx + at + o : nullptr, dist ? dist + at + o : nullptr,
+                                       trim->n_within ? trim->n_within + b0 + t0 : nullptr, trim->d2_cut ? trim->d2_cut + b0 + t0 : nullptr, st);
+                if (rc) return rc;
+            }
+        }
         hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)(nb * chunks)), dim3(kBlock), 0, st, (const float*)s.best, Q, chunks, s.psum, s.pcnt);
         hipLaunchKernelGGL(score_total_kernel, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, nb,
                            chunks, n_close + b0, sum_d2 + b0);
@@ -487,23 +509,23 @@ int launch_refit_empty(int B, double* T_out, double* T_step, int32_t* empty, con
 }
 
 int launch_model_score(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, int32_t* n_close,
-                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st) {
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, nullptr, nullptr, ws, ws_bytes, st);
+                       double* sum_d2, int32_t* idx, float* dist, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim) {
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, idx, dist, nullptr, nullptr, nullptr, trim, ws, ws_bytes, st);
 }
 
 int launch_model_refit(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, double* T_out, double* T_step,
-                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
+                       int32_t* n_close, double* sum_d2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim) {
     const RefitOut out{T_out, T_step, empty};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, nullptr, nullptr, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, nullptr, nullptr, trim, ws, ws_bytes, st);
 }
 
 int launch_model_refit_plane(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                              double* T_out, double* T_step, int32_t* n_close, double* sum_d2, int32_t* n_plane, double* sum_res2, int32_t* empty,
-                             void* ws, size_t ws_bytes, hipStream_t st) {
+                             void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim) {
     PCREG_ARG(ldn >= v.M && (normals || v.M == 0));
     const RefitOut out{T_out, T_step, empty};
     const PlaneIo plane{normals, ldn, n_plane, sum_res2};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, nullptr, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, nullptr, trim, ws, ws_bytes, st);
 }
 
 // the plane refit's workspace, as it is: the same slots and partials, with the pairs' count in the plane count's place
@@ -511,12 +533,12 @@ size_t refit_gicp_ws_bytes(int Q, int B, int M) { return refit_plane_ws_bytes(Q,
 
 int launch_model_refit_gicp(const ModelView& v, const float* q, int Q, int ldq, const double* T_dev, int B, float r2, const float* normals, int ldn,
                             const float* qnormals, int ldnq, double epsilon, double* T_out, double* T_step, int32_t* n_close, double* sum_d2,
-                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st) {
+                            int32_t* n_pairs, double* sum_res2, int32_t* empty, void* ws, size_t ws_bytes, hipStream_t st, const TrimIo* trim) {
     PCREG_ARG(ldn >= v.M && (normals || v.M == 0) && Q >= 0 && ldnq >= Q && (qnormals || Q == 0) && epsilon > 0.0 && epsilon <= 1.0);
     const RefitOut out{T_out, T_step, empty};
     const PlaneIo plane{normals, ldn, n_pairs, sum_res2};
     const GicpIo gicp{qnormals, ldnq, 1.0 - epsilon};
-    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, &gicp, ws, ws_bytes, st);
+    return score_chain(v, q, Q, ldq, T_dev, B, r2, n_close, sum_d2, nullptr, nullptr, &out, &plane, &gicp, trim, ws, ws_bytes, st);
 }
 
 }  // namespace pcreg

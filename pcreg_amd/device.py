@@ -30,6 +30,17 @@ def soa(points: torch.Tensor) -> torch.Tensor:
     return points.t().contiguous()
 
 
+def _keep_ratio(keep_ratio) -> float:
+    """The trimmed entries' ratio: a number in (0, 1]."""
+    keep_ratio = float(keep_ratio)
+    if not 0.0 < keep_ratio <= 1.0:
+        raise ValueError(f"keep_ratio must lie in (0, 1], got {keep_ratio}")
+    return keep_ratio
+
+
+_TRIM_KINDS = (torch.int32, torch.float32)         # n_within, d2_cut: what a trimmed refit returns beyond its untrimmed twin
+
+
 class _RefitSteps:
     """What the five "B transforms refitted `steps` times" methods share (PreparedModel.refit_transforms, refit_plane, refit_gicp,
     refit_cpd and NdtModel.refit).  Creating one checks q_soa, T_dev and steps; the method then checks its own arguments, and
@@ -179,7 +190,7 @@ class PreparedModel:
             self.rangesearch_fill(q_soa, r2, seg_off, idx, dist, idx_base)
         return seg_off, idx, dist
 
-    def score_transforms(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, rows: bool = False, out=None):
+    def score_transforms(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, rows: bool = False, out=None, keep_ratio=None):
         """How well B transforms put a cloud on the model, on torch's current stream (pcreg_dev_model_score_f32): q_soa a [3, Q]
         float32 tensor with contiguous rows, T_dev a contiguous float64 tensor of B x 16 numbers (each transform column-major
         4 x 4, used as quickTF uses it; all zeros: the empty transform, which scores nothing), r2 the squared radius ->
@@ -188,7 +199,11 @@ class PreparedModel:
         float32, +inf for none).  Fitness is n_close / Q and the inlier RMSE sqrt(sum_d2 / n_close).  Nothing synchronises.
         The workspace is cached on the model and grown on demand; calls that may overlap on two streams pass buffers of
         their own, out=(n_close, sum_d2, idx, dist, ws) with ws of pcreg_dev_model_score_workspace(Q, B, M) bytes (idx and
-        dist None without rows)."""
+        dist None without rows).
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_dev_model_score_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query -- and two more tensors
+        end the tuple: n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B] float32, the largest kept squared
+        distance (+inf where nothing is kept); `out` then holds them too, before ws, which is the size it is without keep_ratio.  idx / dist hold -1 / +inf at trimmed slots."""
         if q_soa.dtype != torch.float32 or q_soa.dim() != 2 or q_soa.shape[0] != 3 or q_soa.stride(1) != 1:
             raise TypeError("queries are a [3, Q] float32 tensor with contiguous rows (column-major Q x 3)")
         if T_dev.dtype != torch.float64 or not T_dev.is_contiguous() or T_dev.numel() % 16 or T_dev.device != q_soa.device:
@@ -197,10 +212,18 @@ class PreparedModel:
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
         dev, Q, B = q_soa.device, int(q_soa.shape[1]), T_dev.numel() // 16
+        if keep_ratio is not None:
+            keep_ratio = _keep_ratio(keep_ratio)
         need = max(int(lib().pcreg_dev_model_score_workspace(Q, B, self.M)), 256)
-        if out is not None:
+        n_within = d2_cut = None
+        if out is not None and keep_ratio is not None:
+            n_close, sum_d2, idx, dist, n_within, d2_cut, ws = out
+        elif out is not None:
             n_close, sum_d2, idx, dist, ws = out
         else:
+            if keep_ratio is not None:
+                n_within = torch.empty(B, dtype=torch.int32, device=dev)
+                d2_cut = torch.empty(B, dtype=torch.float32, device=dev)
             n_close = torch.empty(B, dtype=torch.int32, device=dev)
             sum_d2 = torch.empty(B, dtype=torch.float64, device=dev)
             idx = torch.empty((B, Q), dtype=torch.int32, device=dev) if rows else None
@@ -208,14 +231,21 @@ class PreparedModel:
             ws = getattr(self, "_score_ws_t", None)
             if ws is None or ws.numel() < need or ws.device != dev:
                 ws = self._score_ws_t = torch.empty(need, dtype=torch.uint8, device=dev)
-        if B:                                          # (an empty tensor has no address to pass)
+        if B and keep_ratio is not None:
+            with torch.cuda.device(dev):
+                check(lib().pcreg_dev_model_score_trimmed_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(T_dev), B, r2,
+                                                              keep_ratio, _p(n_close), _p(sum_d2), _p(idx) if idx is not None and Q else None,
+                                                              _p(dist) if dist is not None and Q else None, _p(ws), ws.numel(), _stream(),
+                                                              _p(n_within), _p(d2_cut)))
+        elif B:                                        # (an empty tensor has no address to pass)
             with torch.cuda.device(dev):
                 check(lib().pcreg_dev_model_score_f32(self.handle, _p(q_soa) if Q else None, Q, max(int(q_soa.stride(0)), Q, 1), _p(T_dev), B, r2,
                                                       _p(n_close), _p(sum_d2), _p(idx) if idx is not None and Q else None,
                                                       _p(dist) if dist is not None and Q else None, _p(ws), ws.numel(), _stream()))
-        return (n_close, sum_d2, idx, dist) if rows else (n_close, sum_d2)
+        res = (n_close, sum_d2, idx, dist) if rows else (n_close, sum_d2)
+        return res + (n_within, d2_cut) if keep_ratio is not None else res
 
-    def refit_transforms(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, steps: int = 1, out=None):
+    def refit_transforms(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, steps: int = 1, out=None, keep_ratio=None):
         """B transforms refitted on their close pairs, `steps` times over, on torch's current stream (pcreg_dev_model_refit_f32
         once per step, a step's T_out the next one's input, no host synchronisation in between): q_soa, T_dev and r2 as
         score_transforms takes them -> (T_out [B, 16] float64, each transform column-major 4 x 4; T_step [B, 16], the last step's
@@ -224,18 +254,30 @@ class PreparedModel:
         than three pairs, an empty estimateTransform, an all-zero input -- and both matrices are zeros).  T_dev is not written.
         The workspace and the second transform block are cached on the model; calls that may overlap on two streams pass
         buffers of their own, out=(T_out, T_step, n_close, sum_d2, empty, ws, T_tmp) with ws of
-        pcreg_dev_model_refit_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        pcreg_dev_model_refit_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1).
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_dev_model_refit_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query -- and two more tensors
+        end the tuple: n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B] float32, the largest kept squared
+        distance (+inf where nothing is kept); `out` then holds them too, before ws, which is the size it is without keep_ratio.  Every step trims anew."""
         st = _RefitSteps(q_soa, T_dev, steps)
         r2 = float(r2)
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
+        if keep_ratio is not None:
+            keep_ratio = _keep_ratio(keep_ratio)
+
+            def call_trimmed(src, dst, T_step, n_close, sum_d2, empty, n_within, d2_cut, ws):
+                check(lib().pcreg_dev_model_refit_trimmed_f32(self.handle, *st.q_args, _p(src), st.B, r2, keep_ratio, _p(dst), _p(T_step), _p(n_close),
+                                                              _p(sum_d2), _p(empty), _p(ws), ws.numel(), _stream(), _p(n_within), _p(d2_cut)))
+            return st.run(self, "_refit_ws_t", lib().pcreg_dev_model_refit_workspace(st.Q, st.B, self.M),
+                          (torch.int32, torch.float64, torch.int32) + _TRIM_KINDS, out, call_trimmed)
 
         def call(src, dst, T_step, n_close, sum_d2, empty, ws):
             check(lib().pcreg_dev_model_refit_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(dst), _p(T_step), _p(n_close), _p(sum_d2), _p(empty),
                                                   _p(ws), ws.numel(), _stream()))
         return st.run(self, "_refit_ws_t", lib().pcreg_dev_model_refit_workspace(st.Q, st.B, self.M), (torch.int32, torch.float64, torch.int32), out, call)
 
-    def refit_plane(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, normals: torch.Tensor, steps: int = 1, out=None):
+    def refit_plane(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, normals: torch.Tensor, steps: int = 1, out=None, keep_ratio=None):
         """B transforms refitted by the linearised point-to-plane step, `steps` times over, on torch's current stream
         (pcreg_dev_model_refit_plane_f32 once per step, a step's T_out the next one's input, no host synchronisation in between;
         the contract is pcreg_model_refit_plane_f32's): q_soa, T_dev, r2 and steps as refit_transforms takes them; normals the
@@ -244,7 +286,11 @@ class PreparedModel:
         sum_res2 [B] float64, empty [B] int32), the counts and sums for the transform that went INTO the last step.  T_dev and
         normals are not written.  The workspace and the second transform block are cached on the model; calls that may overlap
         on two streams pass buffers of their own, out=(T_out, T_step, n_close, sum_d2, n_plane, sum_res2, empty, ws, T_tmp) with
-        ws of pcreg_dev_model_refit_plane_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        ws of pcreg_dev_model_refit_plane_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1).
+        keep_ratio (None: this call, untouched): a number in (0, 1] takes the trimmed entry (pcreg_dev_model_refit_plane_trimmed_f32) -- of each
+        transform's pairs within r2 only the closest keep_ratio share is kept, ties to the lower query -- and two more tensors
+        end the tuple: n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B] float32, the largest kept squared
+        distance (+inf where nothing is kept); `out` then holds them too, before ws, which is the size it is without keep_ratio.  Every step trims anew."""
         st = _RefitSteps(q_soa, T_dev, steps)
         M = self.M
         if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
@@ -254,6 +300,15 @@ class PreparedModel:
         if not r2 >= 0.0:
             raise ValueError(f"r2 (the squared radius) must be a number >= 0, got {r2}")
         nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=st.dev)      # (no rows: any address, never read)
+        if keep_ratio is not None:
+            keep_ratio = _keep_ratio(keep_ratio)
+
+            def call_trimmed(src, dst, T_step, n_close, sum_d2, n_plane, sum_res2, empty, n_within, d2_cut, ws):
+                check(lib().pcreg_dev_model_refit_plane_trimmed_f32(self.handle, *st.q_args, _p(src), st.B, r2, keep_ratio, _p(nrm),
+                                                                    max(int(nrm.stride(0)), M), _p(dst), _p(T_step), _p(n_close), _p(sum_d2), _p(n_plane),
+                                                                    _p(sum_res2), _p(empty), _p(ws), ws.numel(), _stream(), _p(n_within), _p(d2_cut)))
+            return st.run(self, "_refit_plane_ws_t", lib().pcreg_dev_model_refit_plane_workspace(st.Q, st.B, M),
+                          (torch.int32, torch.float64, torch.int32, torch.float64, torch.int32) + _TRIM_KINDS, out, call_trimmed)
 
         def call(src, dst, T_step, n_close, sum_d2, n_plane, sum_res2, empty, ws):
             check(lib().pcreg_dev_model_refit_plane_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(nrm), max(int(nrm.stride(0)), M), _p(dst),
@@ -273,6 +328,18 @@ class PreparedModel:
         Nothing given is written.  The workspace and the second transform block are cached on the model; calls that may overlap
         on two streams pass buffers of their own, out=(T_out, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws, T_tmp) with
         ws of pcreg_dev_model_refit_gicp_workspace(Q, B, M) bytes and T_tmp [B, 16] float64 (None with steps = 1)."""
+        return self._refit_gicp(q_soa, T_dev, r2, normals, q_normals, epsilon, steps, out, None)
+
+    def refit_gicp_trimmed(self, q_soa: torch.Tensor, T_dev: torch.Tensor, r2: float, keep_ratio: float, normals: torch.Tensor, q_normals: torch.Tensor,
+                           epsilon: float = 1e-3, steps: int = 1, out=None):
+        """refit_gicp with keep_ratio, a number in (0, 1] (pcreg_dev_model_refit_gicp_trimmed_f32): of each transform's
+        pairs within r2 every step keeps only the closest keep_ratio share, ties to the lower query, and two more tensors end the
+        tuple: n_within [B] int32, the pairs within r2 before the trim, and d2_cut [B] float32, the largest kept squared distance
+        (+inf where nothing is kept); `out` holds them too, before ws, which has refit_gicp's size.  (A method of its own where refit_transforms and refit_plane take a keyword: refit_gicp's parameter list is
+        pinned by tests/test_refit_gicp_abi.py.)"""
+        return self._refit_gicp(q_soa, T_dev, r2, normals, q_normals, epsilon, steps, out, _keep_ratio(keep_ratio))
+
+    def _refit_gicp(self, q_soa, T_dev, r2, normals, q_normals, epsilon, steps, out, keep_ratio):
         st = _RefitSteps(q_soa, T_dev, steps)
         M, Q = self.M, st.Q
         if (normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3 or normals.shape[1] != M or (M and normals.stride(1) != 1)
@@ -287,6 +354,16 @@ class PreparedModel:
         if not 0.0 < epsilon <= 1.0:
             raise ValueError(f"epsilon must lie in (0, 1], got {epsilon}")
         nrm = normals if M else torch.zeros((3, 1), dtype=torch.float32, device=st.dev)      # (no rows: any address, never read)
+        if keep_ratio is not None:
+
+            def call_trimmed(src, dst, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, n_within, d2_cut, ws):
+                check(lib().pcreg_dev_model_refit_gicp_trimmed_f32(self.handle, *st.q_args, _p(src), st.B, r2, keep_ratio, _p(nrm),
+                                                                   max(int(nrm.stride(0)), M), _p(q_normals) if Q else None,
+                                                                   max(int(q_normals.stride(0)), Q, 1) if Q else 1, epsilon, _p(dst), _p(T_step),
+                                                                   _p(n_close), _p(sum_d2), _p(n_pairs), _p(sum_res2), _p(empty), _p(ws), ws.numel(),
+                                                                   _stream(), _p(n_within), _p(d2_cut)))
+            return st.run(self, "_refit_gicp_ws_t", lib().pcreg_dev_model_refit_gicp_workspace(Q, st.B, M),
+                          (torch.int32, torch.float64, torch.int32, torch.float64, torch.int32) + _TRIM_KINDS, out, call_trimmed)
 
         def call(src, dst, T_step, n_close, sum_d2, n_pairs, sum_res2, empty, ws):
             check(lib().pcreg_dev_model_refit_gicp_f32(self.handle, *st.q_args, _p(src), st.B, r2, _p(nrm), max(int(nrm.stride(0)), M),

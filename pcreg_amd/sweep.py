@@ -561,26 +561,37 @@ def largest_cluster(result: dict, thSucc: float = 0, thInliers: float = 28, thRa
     return trials, np.asarray(result["trial"], dtype=np.int64)[trials]
 
 
-def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float) -> dict:
+def score_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, keep_ratio=None) -> dict:
     """Every trial of a sweep's result scored on the dense clouds (PreparedModel.score_transforms): put the surface ([3, Q]
     float32) on the prepared dense model with invertTF(transforms[t]) -- ransac's transforms map model onto surface -- and count
     the surface points with a model point within max_dist.  A failed trial (None) is the empty transform and scores nothing.
     -> dict(n_close [n] int32, sum_d2 [n] float64, fitness = n_close / Q, rmse = sqrt(sum_d2 / n_close), NaN where nothing is
     close), aligned with result["trial"].  One upload (the [n][16] block) and one read (12 bytes per trial); the radius is
-    squared once in single, and the comparison is the point search's: fp32, inclusive."""
+    squared once in single, and the comparison is the point search's: fp32, inclusive.  keep_ratio (None: as above): a number in
+    (0, 1] scores each trial on the closest keep_ratio share of its pairs within max_dist (PreparedModel.score_transforms'
+    keep_ratio), and the dict gains n_within [n] int32 and d2_cut [n] float32; one read of 20 bytes per trial."""
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
     Q, n = int(surface_soa.shape[1]), len(tf)
     if n == 0:
-        return score_summary(np.zeros(0, np.int32), np.zeros(0), Q)
+        res = score_summary(np.zeros(0, np.int32), np.zeros(0), Q)
+        if keep_ratio is not None:
+            res.update(n_within=np.zeros(0, np.int32), d2_cut=np.zeros(0, np.float32))
+        return res
     T_dev = torch.from_numpy(_transforms16(tf)).to(surface_soa.device)
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
+    if keep_ratio is not None:
+        n_close, sum_d2, n_within, d2_cut = model.score_transforms(surface_soa, T_dev, r2, keep_ratio=keep_ratio)
+        both = torch.cat([sum_d2.view(torch.int32), n_close, n_within, d2_cut.view(torch.int32)]).cpu().numpy()
+        res = score_summary(both[2 * n:3 * n], both[:2 * n].view(np.float64), Q)
+        res.update(n_within=both[3 * n:4 * n].copy(), d2_cut=both[4 * n:].view(np.float32).copy())
+        return res
     n_close, sum_d2 = model.score_transforms(surface_soa, T_dev, r2)
     both = torch.cat([sum_d2.view(torch.int32), n_close]).cpu().numpy()
     return score_summary(both[2 * n:], both[:2 * n].view(np.float64), Q)
 
 
 def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor, max_dist: float, steps: int = 1, normals=None, ndt=None,
-                  neighbors: int = 1, outlier_ratio: float = 0.55, surface_normals=None, epsilon: float = 1e-3, cpd=None):
+                  neighbors: int = 1, outlier_ratio: float = 0.55, surface_normals=None, epsilon: float = 1e-3, cpd=None, keep_ratio=None):
     """Every trial of a sweep's result refitted on the dense clouds (PreparedModel.refit_transforms): completeExperimentFast.m:383-394's
     T_refine with the dense surface ([3, Q] float32) and the prepared dense model in the place of a cluster's re-matched
     keypoints, `steps` times over.  The orientation is score_trials': invertTF(transforms[t]) puts the surface on the model and
@@ -595,7 +606,12 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
     may be None; the same orientation; the summary is then dict(n_pairs, sum_e) of the last step, a trial without a fit None.
     cpd (a dict(sigma2=, outlier=), either key optional: PreparedModel.refit_cpd's defaults): the steps are coherent-point-drift
     steps instead -- every surface point softly against every model row, so max_dist is not used and may be None; the same
-    orientation; the summary is then dict(sigma2, Np, sum_res2, sum_d2, n_live) of the last step, a trial without a fit None."""
+    orientation; the summary is then dict(sigma2, Np, sum_res2, sum_d2, n_live) of the last step, a trial without a fit None.
+    keep_ratio (None: as above; not with ndt or cpd, which pair no nearest rows): a number in (0, 1] makes every estimateTransform,
+    point-to-plane or plane-to-plane step keep the closest keep_ratio share of its pairs within max_dist; the
+    summary is then about the kept pairs and gains n_within [n] int32 and d2_cut [n] float32 of the last step."""
+    if keep_ratio is not None and (ndt is not None or cpd is not None):
+        raise ValueError("keep_ratio trims nearest-row pairs: the NDT and coherent-point-drift steps have none")
     tf = [None if T is None else invertTF(np.asarray(T, dtype=np.float64)) for T in result["transforms"]]
     Q, n = int(surface_soa.shape[1]), len(tf)
     if n == 0:
@@ -619,18 +635,27 @@ def refine_trials(result: dict, model: PreparedModel, surface_soa: torch.Tensor,
         f64 = lambda k: both[(32 + 2 * k) * n:(34 + 2 * k) * n].view(np.float64).copy()
         return out, dict(sigma2=f64(0), Np=f64(1), sum_res2=f64(2), sum_d2=f64(3), n_live=both[40 * n:41 * n].copy())
     r2 = float(np.float32(max_dist) * np.float32(max_dist))
+    trim = []                                                                               # (n_within, d2_cut) of a trimmed call
     if normals is None:
-        T_out, _step, n_close, sum_d2, empty = model.refit_transforms(surface_soa, T_dev, r2, steps=steps)
+        T_out, _step, n_close, sum_d2, empty, *trim = model.refit_transforms(surface_soa, T_dev, r2, steps=steps, keep_ratio=keep_ratio)
     elif surface_normals is None:
-        T_out, _step, n_close, sum_d2, _n_plane, _res2, empty = model.refit_plane(surface_soa, T_dev, r2, normals, steps=steps)
+        T_out, _step, n_close, sum_d2, _n_plane, _res2, empty, *trim = model.refit_plane(surface_soa, T_dev, r2, normals, steps=steps,
+                                                                                         keep_ratio=keep_ratio)
     else:
-        T_out, _step, n_close, sum_d2, _n_pairs, _res2, empty = model.refit_gicp(surface_soa, T_dev, r2, normals, surface_normals, epsilon=epsilon,
-                                                                                 steps=steps)
-    both = torch.cat([T_out.reshape(-1).view(torch.int32), sum_d2.view(torch.int32), n_close, empty]).cpu().numpy()
+        if keep_ratio is None:
+            got = model.refit_gicp(surface_soa, T_dev, r2, normals, surface_normals, epsilon=epsilon, steps=steps)
+        else:
+            got = model.refit_gicp_trimmed(surface_soa, T_dev, r2, keep_ratio, normals, surface_normals, epsilon=epsilon, steps=steps)
+        T_out, _step, n_close, sum_d2, _n_pairs, _res2, empty, *trim = got
+    both = torch.cat([T_out.reshape(-1).view(torch.int32), sum_d2.view(torch.int32), n_close, empty] +
+                     ([trim[0], trim[1].view(torch.int32)] if trim else [])).cpu().numpy()
     mats = both[:32 * n].view(np.float64).reshape(n, 4, 4).transpose(0, 2, 1)
-    gone = both[35 * n:] != 0
+    gone = both[35 * n:36 * n] != 0
     out = [None if gone[t] else invertTF(np.ascontiguousarray(mats[t])) for t in range(n)]
-    return out, score_summary(both[34 * n:35 * n], both[32 * n:34 * n].view(np.float64), Q)
+    summary = score_summary(both[34 * n:35 * n], both[32 * n:34 * n].view(np.float64), Q)
+    if trim:
+        summary.update(n_within=both[36 * n:37 * n].copy(), d2_cut=both[37 * n:].view(np.float32).copy())
+    return out, summary
 
 
 def quickTF_dev(pts_soa: torch.Tensor, TF: np.ndarray) -> torch.Tensor:
